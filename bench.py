@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — frames/sec of the SQAIR Discover/Propagate hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" = one pass of the hot path over one batch of synthetic input: noise draw on device, the
 T-frame forward unroll (HIP-graph replay of the launch sequence), IWAE / VIMCO reductions.  Inputs
@@ -11,7 +11,13 @@ K=5 IWAE particles, 4 object slots ("cfg2"); with N > 1 every rank processes its
 shard (weak scaling, the sharding of configs[2]; no collective on the data path of the forward pass).
 frames/step = B * T per rank (all K particles of a frame count as one frame).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with these extra objects:
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0): `value` (frames/s), `ms_per_step`, the
+elbo of the last step and `roofline` as the whole-step figure (algorithmic FLOPs of the step / the timed step).
+`--dump-outputs DIR` writes what the last timed step computed -- every array a caller of the forward path receives -- as
+DIR/<name>.npy (float32); the inputs are seeded, so two builds can be compared output for output.
+
+`--full` adds every other leg below (each one its own measurement, after the timed steps and the dump); the line then carries
+these extra objects:
   roofline     — dominant kernel family (the fp32-MFMA dense layers k_linear* / k_rnn_tail) from a PER-DISPATCH
                  TIMELINE of one step measured live, without a profiler: the same step replayed on
                  libsqair_hip_timeline.so (the library compiled with -DSQAIR_TIMELINE: every wave stamps its start
@@ -57,6 +63,7 @@ MACS_PER_FRAME_PARTICLE = {1: 10166288, 2: 13543744, 3: 13543744, 4: 20298656, 5
 EXECUTED_MFLOP_PER_FRAME = {1: 17.5, 2: 114.3, 3: 114.3, 4: 167.7, 5: 149.8}
 MIN_HBM_BYTES_PER_FRAME = {2: 101060, 3: 101060}   # minimum HBM bytes per frame (all K particles), cfg-2 shapes
 PROFILE_TAG = "r06"                    # profiles/<tag>_*.json|csv: the committed files of this round (tools/profile_round.sh)
+DUMP_BYTES_MAX = 64 << 20              # --dump-outputs: at most this much in all (a fixed, seeded sample of each array beyond it)
 
 
 def cpu_baseline(F, hw, P, obs, noise, hip_ref, budget_s=25.0):
@@ -122,6 +129,27 @@ def cpu_baseline(F, hw, P, obs, noise, hip_ref, budget_s=25.0):
                 ms_per_pass=med * 1e3, train_value=B * T / tmed, train_ms_per_pass=tmed * 1e3,
                 parity=dict(rows_with_identical_presence=float(same_rows.mean()), log_weights_max_rel_err=rel,
                             elbo_iwae_oracle=float(m.elbo_iwae), elbo_iwae_hip=hip_ref["elbo_iwae"]))
+
+
+def dump_outputs(core, out_dir):
+    """--dump-outputs: what the last forward step left in the core's output buffers, i.e. what a caller of the path receives
+    (the per-frame outputs it was bound with, the ELBO tensors, the scalar metrics), as <out_dir>/<name>.npy in float32."""
+    torch.cuda.synchronize()
+    arrays = dict(core.out)
+    arrays.update(log_weights=core.log_weights, elbo_iwae_per_example=core.elbo_iwae_per_example,
+                  importance_weights=core.importance_weights, vimco_signal=core.vimco_signal)
+    for i, name in enumerate(("elbo_vae", "elbo_iwae", "vimco_target", "ess")):   # sqair_elbo's scalars_out[0:4]
+        arrays[name] = core.scalars[i]
+    for i, name in enumerate(core.mean_names):
+        arrays["iw_mean_" + name] = core.iw_means[i]
+    total = 4 * sum(t.numel() for t in arrays.values())
+    rng = np.random.default_rng(0)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in sorted(arrays.items()):
+        a = t.detach().float().cpu().numpy()
+        if total > DUMP_BYTES_MAX and a.size > 1:   # the same flat positions for the same shapes, run after run
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, max(1, a.size * DUMP_BYTES_MAX // total), replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def timed_steps(step_fn, n, dist, device):
@@ -276,15 +304,21 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every extra leg (training step, roofline timeline, CPU baseline, streams, all outputs, "
+                         "slot chain, the N > 1 references); a plain run times the forward step only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of HIP-graph replay")
-    ap.add_argument("--no-timeline", action="store_true", help="skip the per-dispatch timeline (roofline objects become null)")
+    ap.add_argument("--no-timeline", action="store_true",
+                    help="with --full: skip the per-dispatch timeline (roofline objects become null)")
     ap.add_argument("--cfg", type=int, default=2, help="BASELINE.json config id used as the workload (default 2)")
     ap.add_argument("--train-steps", type=int, default=-1,
-                    help="steps of the extra training-step leg (default min(steps, 20); 0 = skip)")
+                    help="with --full: steps of the extra training-step leg (default min(steps, 20); 0 = skip)")
     ap.add_argument("--streams", type=int, default=3,
-                    help="extra object \"streams\": forward passes of this many INDEPENDENT batches in flight on their own "
-                         "streams (0 = skip; single GPU only; never part of `value`)")
+                    help="with --full: extra object \"streams\": forward passes of this many INDEPENDENT batches in flight on "
+                         "their own streams (0 = skip; single GPU only; never part of `value`)")
     ap.add_argument("--batch", type=int, default=0,
                     help="sequences per GPU (default: the configuration's own; other values are batch-scaling experiments, "
                          "not BASELINE's metric)")
@@ -301,6 +335,9 @@ def main():
     ap.add_argument("--transition", default="VanillaRNN", choices=["VanillaRNN", "GRU", "LSTM"],
                     help="slot RNN of both cores (shipped: VanillaRNN)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    full = args.full
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X (torch.cuda.is_available() is False)")
@@ -430,6 +467,8 @@ def main():
         ctypes.CDLL(None).fflush(None)
     elapsed = timed_steps(step, args.steps, dist, device)
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(core, args.dump_outputs)
     frames_per_step = B * T * world
     value = frames_per_step / (elapsed / args.steps)
 
@@ -445,7 +484,7 @@ def main():
     # backward; ONE HIP-graph replay) + the step's single collective (all-reduce of the flat fp32 gradient buffer over
     # RCCL) + fused RMSProp + weight re-pack.  Same workload, same barrier / max-over-ranks timing.
     train = None
-    n_train = min(args.steps, 20) if args.train_steps < 0 else args.train_steps
+    n_train = (min(args.steps, 20) if args.train_steps < 0 else args.train_steps) if full else 0
     if n_train > 0:
         trainer = Trainer(model, Ftr, use_graph=use_graph, comm=comm)
         tstep = lambda: trainer.step(seed=2000, global_batch=B * world, b0=rank * B)  # noqa: E731
@@ -509,7 +548,7 @@ def main():
     # the timed regions and outside `value`: weak scaling says N GPUs do N x the work in the same time; this says what ONE GPU
     # needs for the same N x work (the small-batch step is latency-bound, so one GPU is far better than 1/N of the job).
     single = None
-    if world > 1:
+    if full and world > 1:
         if rank == 0:
             try:
                 obs_g, nums_g = shard_data(B * world, 99)
@@ -545,7 +584,7 @@ def main():
     # ---- independent batches in flight (extra object "streams"): handles share nothing, so n of them replaying their graphs on
     # n streams overlap their dependent-launch chains.  Throughput of evaluation / serving, NOT the metric's one-pass-at-a-time rate.
     streams = None
-    if world == 1 and use_graph and args.streams > 1:
+    if full and world == 1 and use_graph and args.streams > 1:
         try:
             cores = [core]
             for i in range(1, args.streams):
@@ -586,7 +625,7 @@ def main():
     # glimpses, every log-probability: reference sqair/seq.py:121-177 writes them all, scripts/eval.py:191-224 and the notebook read
     # them); the timed region above asks for `elbo_iwae` only (outputs="minimal", what `sess.run(model.elbo_iwae)` evaluates).
     all_out = None
-    if rank == 0 and use_graph:
+    if full and rank == 0 and use_graph:
         try:
             from sqair_amd.timeline import time_steps
             core_a = SqairCore(F, hw, device=device)
@@ -612,7 +651,7 @@ def main():
     # launch each (sqair_amd/csrc/sqair_chain.h; bit-identical results: tests/test_slot_chain.py) -- at this workload and at half
     # the sequences, where every XCD serves a single 16-row tile.
     chain = None
-    if rank == 0 and world == 1 and use_graph and args.transition == "VanillaRNN" and args.time_transition == "GRU":
+    if full and rank == 0 and world == 1 and use_graph and args.transition == "VanillaRNN" and args.time_transition == "GRU":
         try:
             from sqair_amd.timeline import time_steps
             chain = {}
@@ -666,7 +705,7 @@ def main():
     gates = {"VanillaRNN": 1, "GRU": 3, "LSTM": 4}[args.transition] - 1   # extra gate blocks of the two slot RNNs
     algo_flops_step += float(B * T) * 2.0 * K * N * gates * ((416 + 256) + (256 + 256 + int(F.n_what) + 5 + 256)) * 256
     roofline = roofline_hbm = None
-    if use_graph and not args.no_timeline:
+    if full and use_graph and not args.no_timeline:
         try:
             roofline, roofline_hbm, train_tl = timeline_roofline(
                 F, Ftr, hw, P, obs, nums, algo_flops_step, ms_per_step, train["ms_per_step"] if train else None, args.cfg,
@@ -684,7 +723,7 @@ def main():
                         unit="TFLOP/s", frac=whole / PEAK_FP32_MFMA_TFLOPS, traffic=None)
 
     cpu = None
-    if not args.no_cpu_baseline:
+    if full and not args.no_cpu_baseline:
         # parity + timing on the same frames / parameters / noise as one GPU step
         full = Model(obs, None, core, K, presence=nums, outputs=["log_weights_per_timestep", "discrete_log_prob", "presence"])
         gen = torch.Generator(device=device)

@@ -128,7 +128,7 @@ def test_two_ranks_on_two_devices_all_reduce_over_rccl(tmp_path):
 
 
 def _bench_with_broken_rccl(extra):
-    code = ("import sys, runpy; sys.argv = ['bench.py', '--force-dist', '--steps', '1', '--warmup', '1', '--train-steps', '1', "
+    code = ("import sys, runpy; sys.argv = ['bench.py', '--full', '--force-dist', '--steps', '1', '--warmup', '1', '--train-steps', '1', "
             "'--no-cpu-baseline', '--no-timeline', '--streams', '0', '--cfg', '1'] + {extra!r}\n"
             "sys.path.insert(0, {root!r})\n"
             "import sqair_amd.rccl as R\n"
@@ -160,7 +160,7 @@ def test_bench_never_falls_back_silently_when_the_native_communicator_fails(tmp_
     # which communicator carried the all-reduce is said in one field (and rccl_ranks counts THAT communicator's ranks)
     assert line["collective_path"] == "torch-nccl" and line["train"]["collective_path"] == "torch-nccl" and line["rccl_ranks"] == 1
     # ... and the healthy branch: the native communicator on the launch stream
-    code_ok = ("import sys, runpy; sys.argv = ['bench.py', '--force-dist', '--steps', '1', '--warmup', '1', '--train-steps', '1', "
+    code_ok = ("import sys, runpy; sys.argv = ['bench.py', '--full', '--force-dist', '--steps', '1', '--warmup', '1', '--train-steps', '1', "
                "'--no-cpu-baseline', '--no-timeline', '--streams', '0', '--cfg', '1']\n"
                "runpy.run_path({bench!r}, run_name='__main__')\n").format(bench=os.path.join(ROOT, "bench.py"))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_PORT=str(_free_port()))
@@ -213,7 +213,7 @@ def test_bench_launches_its_own_ranks():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1",
                         "--train-steps", "2", "--no-cpu-baseline", "--cfg", "1"], env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -240,7 +240,7 @@ def test_bench_eight_ranks_functional_check_on_one_node():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     # (cfg-2's model at 3 sequences per rank: cfg-1 has K = 1, whose VIMCO target is NaN by the reference's own formula)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--cfg", "2", "--batch", "3", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--cfg", "2", "--batch", "3", "--steps", "2", "--warmup", "1",
            "--train-steps", "2", "--no-cpu-baseline", "--no-timeline"]
     if torch.cuda.device_count() < 8:
         cmd += ["--dist-backend", "gloo"]

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Runtime environment knobs that could change the cost of a dependent graph node: forward ms per pass at BASELINE configs[1]
-run() { echo -n "$1 : "; env $1 python bench.py --no-cpu-baseline --steps 40 --warmup 5 --train-steps 10 2>/dev/null | tail -1 | python -c "import json,sys; j=json.load(sys.stdin); print(round(j['ms_per_step'],3), round(j['train']['ms_per_step'],3))"; }
+run() { echo -n "$1 : "; env $1 python bench.py --full --no-cpu-baseline --steps 40 --warmup 5 --train-steps 10 2>/dev/null | tail -1 | python -c "import json,sys; j=json.load(sys.stdin); print(round(j['ms_per_step'],3), round(j['train']['ms_per_step'],3))"; }
 run "SQ_NONE=1"
 run "HIP_FORCE_DEV_KERNARG=1"
 run "HIP_FORCE_DEV_KERNARG=0"

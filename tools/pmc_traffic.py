@@ -1,7 +1,7 @@
 """Per-kernel HBM traffic from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) -> profiles/rNN_hbm_traffic.json.
 Run on the GPU box (counters in their own passes, --kernel-trace only; tools/profile_round.sh does all of this):
   cd /tmp && export TMPDIR=/tmp
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/pmc_f -- python $REPO/bench.py --steps 3 --warmup 1 --train-steps 3 --no-cpu-baseline --no-graph
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d pmc_f -- python $REPO/bench.py --full --steps 3 --warmup 1 --train-steps 3 --no-cpu-baseline --no-graph
   rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d /tmp/pmc_w -- python $REPO/bench.py ... (same)
   python $REPO/tools/pmc_traffic.py /tmp/pmc_f /tmp/pmc_w $REPO/gpurun_out/rNN_hbm_traffic.json
 bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024 (FETCH_SIZE doubled on gfx950, MI355X_MICROARCH.md section HBM).
@@ -54,7 +54,7 @@ def main():
                 family_bytes_per_launch={f: b / max(n, 1) for f, (n, b) in sorted(fam.items())},
                 dominant=dom, dominant_bytes_per_launch=dense[dom]["hbm_bytes_per_launch"] if dom else None,
                 dense_family_bytes_per_launch=sum(v["hbm_bytes_per_launch"] * v["launches"] for v in dense.values()) / max(tot_n, 1),
-                method="rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in two separate passes (python bench.py --steps 3 --warmup 1 "
+                method="rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in two separate passes (python bench.py --full --steps 3 --warmup 1 "
                        "--train-steps 3 --no-cpu-baseline --no-graph); bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024: FETCH_SIZE doubled per "
                        "MI355X_MICROARCH.md (gfx950 reports half the bytes of 16 B/lane coalesced reads), WRITE_SIZE uncalibrated; "
                        "`dominant` = the dense instantiation with the most launches; dense_family = launch-weighted mean over all "

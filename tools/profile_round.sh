@@ -22,7 +22,7 @@ cd /tmp
 python $REPO/tools/timeline.py --cfg 2 --out $OUT --tag $R 2>&1 | grep -v amdgpu.ids
 python $REPO/tools/timeline.py --cfg 4 --out $OUT --tag $R 2>&1 | grep -v amdgpu.ids
 python $REPO/tools/timeline.py --cfg 5 --out $OUT --tag $R 2>&1 | grep -v amdgpu.ids
-CMD="python $REPO/bench.py --steps 20 --warmup 3 --train-steps 20 --no-cpu-baseline --no-timeline --streams 0"
+CMD="python $REPO/bench.py --full --steps 20 --warmup 3 --train-steps 20 --no-cpu-baseline --no-timeline --streams 0"
 rm -rf /tmp/prof_s /tmp/pmc_f /tmp/pmc_w /tmp/prof_t
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_s -- $CMD > /tmp/prof_s.log 2>&1
 cp $(find /tmp/prof_s -name '*kernel_stats.csv' | head -1) $OUT/${R}_kernel_stats.csv
@@ -54,13 +54,13 @@ with open("$OUT/${R}_rocprof_trace_one_step.csv", "w") as fh:
         busy = sum(e[1] - e[0] for e in ev[a:b])
         print(leg, "under rocprofv3: span %.1f us, sum of durations %.1f us" % (span / 1e3, busy / 1e3))
 PY
-PCMD="python $REPO/bench.py --steps 3 --warmup 1 --train-steps 3 --no-cpu-baseline --no-graph --no-timeline --streams 0"
+PCMD="python $REPO/bench.py --full --steps 3 --warmup 1 --train-steps 3 --no-cpu-baseline --no-graph --no-timeline --streams 0"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/pmc_f -- $PCMD > /tmp/pmc_f.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d /tmp/pmc_w -- $PCMD > /tmp/pmc_w.log 2>&1
 python $REPO/tools/pmc_traffic.py /tmp/pmc_f /tmp/pmc_w $OUT/${R}_hbm_traffic.json > /dev/null
 # the same two counter passes for BASELINE configs 4 and 5 (rNN_hbm_traffic_cfg{4,5}.json)
 for C in 4 5; do
-  PC="python $REPO/bench.py --cfg $C --steps 3 --warmup 1 --train-steps 3 --no-cpu-baseline --no-graph --no-timeline --streams 0"
+  PC="python $REPO/bench.py --full --cfg $C --steps 3 --warmup 1 --train-steps 3 --no-cpu-baseline --no-graph --no-timeline --streams 0"
   rm -rf /tmp/pmc_f$C /tmp/pmc_w$C
   rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/pmc_f$C -- $PC > /tmp/pmc_f$C.log 2>&1
   rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d /tmp/pmc_w$C -- $PC > /tmp/pmc_w$C.log 2>&1
@@ -78,10 +78,10 @@ PY
 # the bench lines themselves, reading the fresh profiles (copied into place for this run)
 cp $OUT/${R}_hbm_traffic*.json $OUT/${R}_timeline*.json $OUT/${R}_timeline_*.csv $REPO/profiles/ 2>/dev/null
 cd $REPO
-python bench.py --steps 50 --warmup 5 > $OUT/${R}_bench.json 2> $OUT/${R}_bench.err
-python bench.py --cfg 4 --steps 30 --warmup 5 > $OUT/${R}_bench_cfg4.json 2> $OUT/${R}_bench_cfg4.err
-python bench.py --cfg 5 --steps 30 --warmup 5 > $OUT/${R}_bench_cfg5.json 2> $OUT/${R}_bench_cfg5.err
-python bench.py --batch 256 --steps 20 --warmup 3 --no-cpu-baseline > $OUT/${R}_bench_b256.json 2> $OUT/${R}_bench_b256.err
+python bench.py --full --steps 50 --warmup 5 > $OUT/${R}_bench.json 2> $OUT/${R}_bench.err
+python bench.py --full --cfg 4 --steps 30 --warmup 5 > $OUT/${R}_bench_cfg4.json 2> $OUT/${R}_bench_cfg4.err
+python bench.py --full --cfg 5 --steps 30 --warmup 5 > $OUT/${R}_bench_cfg5.json 2> $OUT/${R}_bench_cfg5.err
+python bench.py --full --batch 256 --steps 20 --warmup 3 --no-cpu-baseline > $OUT/${R}_bench_b256.json 2> $OUT/${R}_bench_b256.err
 python - <<PY
 import json
 for n in ("", "_cfg4", "_cfg5", "_b256"):
