@@ -822,7 +822,7 @@ Workspace sq_carve(const SqairHandle* h, int T, int B, float* base, bool train) 
     const int64_t P_ = (int64_t)c.img_h * c.img_w, P4 = (P_ + 3) / 4 * 4;
     w.obs_p = take(P4 != P_ ? (int64_t)T * B * P4 + 16 : 64);   // (+16: the last K chunk of the input encoder may read past the row)
   }
-  w.prof_ts = (unsigned long long*)take(5 * PROF_MAX * 2);
+  w.clear_n = o;   // a workspace clear covers every buffer above; the chain's control blocks below are sq_chain_poison's
   w.chain_ctl = (unsigned*)take(w.chain ? (int64_t)SQ_CHAIN_MAX_LAUNCHES * SQ_CHAIN_CTL_WORDS : 64);
   w.total = o;
   return w;
@@ -884,7 +884,7 @@ static int run_rnn_tail(SqairHandle* h, const TailArgs& ta, Dims d, LayerId id, 
     r.out = out; r.out_ld = out_ld; r.n_out = L.N;
     return sq_chain_add_rnn_tail(h, r);
   }
-  const int rc = sq_launch_rnn_tail(ta, d, hid, hid_ld, packed + pl.w + L.w_off, packed + pl.b + L.b_off, add, add_ld, out, out_ld, L.N, s, nullptr);
+  const int rc = sq_launch_rnn_tail(ta, d, hid, hid_ld, packed + pl.w + L.w_off, packed + pl.b + L.b_off, add, add_ld, out, out_ld, L.N, s);
   if (rc != 0) sq_set_error(h, "internal: k_rnn_tail launch rejected");
   return rc;
 }
@@ -917,15 +917,6 @@ static int run_what(SqairHandle* h, int mode, const float* x, int x_ld, int M, i
   return rc;
 }
 
-// three dependent slot layers: one launch each (a single multi-layer launch with in-launch hand-offs was built and
-// measured slower twice in round 1 -- tools/xcd_team.hip, DESIGN.md section 8 -- and left the library)
-#define RUN_CHAIN3(l0, id0, l1, id1, l2, id2, M) \
-  do {                                            \
-    RUN(l0, id0, M);                              \
-    RUN(l1, id1, M);                              \
-    RUN(l2, id2, M);                              \
-  } while (0)
-
 static int emit_crop(SqairHandle* h, const CropArgs& ca, POff po, Dims d, int nslots, hipStream_t s) {
   if (sq_chain_active(h)) return sq_chain_add_crop(h, ca);
   return sq_launch_crop(ca, po, d, nslots, s);
@@ -947,8 +938,6 @@ static bool sq_chain_on(const SqairHandle* h, int T, int B) {
          c.n_hidden == 256 && can_fuse_tail(h, L_PROP_RNN) && can_fuse_tail(h, L_DISC_RNN) && B * c.k_particles <= 320 && 2 * T <= SQ_CHAIN_MAX_LAUNCHES;
 #endif
 }
-static int emit_latsum(SqairHandle* h, const float* f, const float* rec_p, float* c, Dims d, hipStream_t s) { (void)h; return sq_launch_latent_sum(f, rec_p, c, d, s); }
-static int emit_compact(SqairHandle* h, const CompactArgs& ka, POff po, Dims d, hipStream_t s) { (void)h; return sq_launch_compact(ka, po, d, s); }
 
 // rows of n floats -> rows of pitch p4 >= n, zero padded
 __global__ void k_pad_rows(const float* __restrict__ src, float* __restrict__ dst, int n, int p4 SQ_TLP) {
@@ -965,6 +954,21 @@ __global__ void k_copy_cols(const float* __restrict__ src, float* __restrict__ d
     dst[r * nseg * truew + i] = src[r * nseg * padw + sg * padw + c];
   }
 }
+
+// What the two slot loops of a frame differ in -- propagation (E, tape phase 0) and discovery (G, phase 1) -- filled once per
+// frame; the slot step itself (sq_forward_impl: slot_front, slot_tail) is the same code for both.
+struct SlotPhase {
+  int ph;                             // tape phase
+  LayerId rnn, rnn2, t1, t2, s1;
+  const float *init_rec, *rnn_init;   // slot 0's previous record and RNN state ([hidden | cell] with an LSTM slot RNN)
+  float* rec;                         // the frame's records of this phase
+  const float* pre;                   // hoisted slot-RNN pre-activations: slot k at pre + k * pre_step, row stride pre_ld
+  int pre_step, pre_ld;
+  const float* pre_t1;                // T1's hoisted addend, laid out like `pre` (propagation), or none
+  const float* w3;                    // the transform's output layer (crop #2)
+  int w2_off, b2_off;                 // the steps predictor's output layer (slot tail)
+  bool fuse;                          // the slot's tail rides in the next slot's VanillaRNN launch (k_rnn_tail)
+};
 
 // parts: 1 = prologue (workspace clear, initial state, input encoder), 2 = the frame loop, 4 = epilogue (log-probabilities,
 // decoder, final state copies).
@@ -1011,7 +1015,7 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
   if (parts & 1) {
     // (clear_each_pass = false: the caller cleared this workspace once with sqair_clear_workspace and reuses it with the
     //  same T and B -- every buffer is then either rewritten by the pass or holds finite values / zeros it never overwrites)
-    if (h->clear_each_pass) sq_zero_fill(wsbase, (int64_t)((float*)w.prof_ts - wsbase), s);
+    if (h->clear_each_pass) sq_zero_fill(wsbase, w.clear_n, s);
     // initial state; discovery starts every frame with presence = 1 (core.py:150) -> disc_init_rec
     sq_launch_init_state(w.rec_m_all, w.state(w.temporal_m, 0, w.snh), w.state(w.prior_m, 0, w.psnh), w.last_id[0], w.disc_init_rec,
                          w.prop_rnn_init, w.disc_rnn_init, w.rn_init_state, w.w3_prop, w.w3_disc,
@@ -1129,70 +1133,96 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
         Lin q; q.seg(temporal_prev, snh, nh).out(w.lpre, 4 * nh); RUN(q, L_PROP_GRU2, M);
       }
     }
+    // ---- the slot step of both slot loops ----
+    const SlotPhase prop = {0, L_PROP_RNN, L_PROP_RNN2, L_PROP_T1, L_PROP_T2, L_PROP_S1, w.zero_rec, w.prop_rnn_init, rec_p_t,
+                            w.pre, pre_ld, N * pre_ld, w.pre + rw, w.w3_prop, po.prop_steps_l1_w, po.prop_steps_l1_b, fuse_prop};
+    const SlotPhase disc = {1, L_DISC_RNN, L_DISC_RNN2, L_DISC_T1, L_DISC_T2, L_DISC_S1, w.disc_init_rec, w.disc_rnn_init, rec_d_t,
+                            w.pre_d, 0, rw, nullptr, w.w3_disc, po.disc_steps_l1_w, po.disc_steps_l1_b, fuse_disc};
+    // slot RNN -> T1 -> T2 -> crop #2 (`ca` arrives with the phase's own fields) -> glimpse encoder (the what head unless the
+    // slot's what sample is fused into its own launch)
+    auto slot_front = [&](const SlotPhase& sp, int k, CropArgs ca, bool what_head) -> int {
+      const int rl = w.sld(nh), t1l = w.sld(T1_LD);
+      const float* pre_k = sp.pre + (size_t)k * sp.pre_step;
+      float* r_k = w.rslot(t, sp.ph, k);
+      float* t1 = w.slot(w.t1, T1_LD, t, sp.ph, k);
+      float* t2 = w.slot(w.t2, nh, t, sp.ph, k);
+      float* g2 = w.slot(w.g2, G2, t, sp.ph, k);
+      float* e1 = w.slot(w.e1, nh, t, sp.ph, k);
+      float* e2 = w.slot(w.e2, nh, t, sp.ph, k);
+      Lin a;
+      if (k == 0) a.seg(sp.init_rec, 0, rec::ZW).seg(sp.rnn_init, 0, nh);
+      else a.seg(sp.rec + (size_t)(k - 1) * RW, N * RW, rec::ZW).seg(w.rslot(t, sp.ph, k - 1), rl, nh);
+      if (c.rnn_cell == RNN_LSTM) {
+        float* gates = train ? w.slot(w.rgates, 4 * nh, t, sp.ph, k) : w.rgates;
+        a.add(pre_k, sp.pre_ld, rw).out(gates, w.sld(4 * nh));
+        RUN(a, sp.rnn, R);
+        sq_launch_lstm_cell2(gates, w.sld(4 * nh), k == 0 ? sp.rnn_init + nh : w.cslot(t, sp.ph, k - 1), k == 0 ? 0 : rl, r_k, rl,
+                             w.cslot(t, sp.ph, k), rl, R, nh, s);
+      } else if (c.rnn_cell == RNN_GRU) {  // snt.GRU in two launches, [z | r | tanh candidate] kept for the backward pass
+        float* g3 = train ? w.slot(w.rgates, 3 * nh, t, sp.ph, k) : w.rgates;
+        const int g3l = w.sld(3 * nh);
+        const float* hp = k == 0 ? sp.rnn_init : w.rslot(t, sp.ph, k - 1);
+        const int hpl = k == 0 ? 0 : rl;
+        a.add(pre_k, sp.pre_ld, rw).out(g3, g3l).gru1(hp, hpl, w.grh, nh, w.gxh, nh, nh);
+        a.a.o3 = g3 + nh; a.a.o3_ld = g3l;
+        RUN(a, sp.rnn, R);
+        Lin b2; b2.seg(w.grh, nh, nh).add(w.gxh, nh, nh).out(r_k, rl).gru2(hp, hpl, g3, g3l, nh);
+        b2.a.o1 = g3 + 2 * nh; b2.a.o1_ld = g3l;
+        RUN(b2, sp.rnn2, R);
+      } else if (k > 0 && sp.fuse) {  // the previous slot's tail rides in this launch
+        const int rc = run_rnn_tail(h, pending_tail, d, sp.rnn, w.rslot(t, sp.ph, k - 1), rl, pre_k, sp.pre_ld, r_k, rl, packed, s);
+        if (rc != 0) return rc;
+      } else {  // (VanillaRNN: rw == nh)
+        a.add(pre_k, sp.pre_ld, nh).out(r_k, rl).act(ACT_TANH);
+        RUN(a, sp.rnn, R);
+      }
+      // T1 columns [transform hidden 1 (ELU) | steps-predictor hidden pre-activation without `what` (linear)]
+      Lin b; b.seg(r_k, rl, nh).out(t1, t1l).act2(ACT_ELU, ACT_NONE, nh);
+      if (sp.pre_t1) b.add(sp.pre_t1 + (size_t)k * sp.pre_step, sp.pre_ld, nh + nh / 2);
+      RUN(b, sp.t1, R);
+      Lin cc; cc.seg(t1, t1l, nh).out(t2, rl).act(ACT_ELU); RUN(cc, sp.t2, R);
+      ca.img = img; ca.out = g2; ca.out_row_mul = w.tape ? N : 1; ca.rec_new = sp.rec; ca.t2 = t2; ca.t2_ld = rl; ca.w3 = sp.w3;
+      ca.noise = nz; ca.flat = flat; ca.slot = k;
+      if (train) { ca.tp_out = w.slot(w.tp, TP_LD, t, sp.ph, k); ca.tp_out_ld = w.sld(TP_LD); }
+      emit_crop(h, ca, po, d, 1, s);
+      // (three dependent slot layers, one launch each: a single multi-layer launch with in-launch hand-offs was built and
+      //  measured slower twice in round 1 -- tools/xcd_team.hip, DESIGN.md section 8 -- and left the library)
+      Lin ea; ea.seg(g2, w.sld(G2), G2).out(e1, rl).act(ACT_ELU); RUN(ea, L_GENC0, R);
+      Lin eb; eb.seg(e1, rl, nh).out(e2, rl).act(ACT_ELU); RUN(eb, L_GENC1, R);
+      if (what_head) {
+        Lin e; e.seg(e2, rl, nh).out(w.slot(w.enc, ENC_LD, t, sp.ph, k), w.sld(ENC_LD)).act2(ACT_NONE, ACT_SOFTPLUS_MIN, nw);
+        RUN(e, L_WHAT_HEAD, R);
+      }
+      return 0;
+    };
+    // the slot's tail (sqair_glue.h: TailArgs): launched now, or handed to the next slot's RNN launch
+    auto slot_tail = [&](const SlotPhase& sp, int k, const float* hraw, int h_ld) {
+      TailArgs ta; memset(&ta, 0, sizeof(ta));
+      ta.is_disc = sp.ph; ta.slot = k; ta.hraw = hraw; ta.h_ld = h_ld; ta.enc = w.slot(w.enc, ENC_LD, t, sp.ph, k); ta.enc_ld = w.sld(ENC_LD);
+      ta.rec_prev = rec_prev; ta.rec_new = sp.rec; ta.noise = nz; ta.s1p = w.slot(w.t1, T1_LD, t, sp.ph, k) + nh; ta.s1p_ld = w.sld(T1_LD);
+      ta.wp = packed + pl.w + h->layers[sp.s1].w_off; ta.flat = flat; ta.w2_off = sp.w2_off; ta.b2_off = sp.b2_off;
+      if (train) { ta.s1h_out = w.slot(w.s1h, S1_LD, t, sp.ph, k); ta.s1h_ld = w.sld(S1_LD); }
+      ta.what_done = fw ? 1 : 0;
+      if (sp.fuse && k + 1 < N) pending_tail = ta;  // computed inside the next slot's RNN launch
+      else emit_tail(h, ta, d, s);
+    };
+
     // ---- E. propagation slots (propagate.py:168-184 static_rnn over PropagationCore) ----
     if (w.chain) sq_chain_begin(h, d, po, wsbase, ws_bytes);
     for (int k = 0; k < N; ++k) {
-      const float* pre_k = w.pre + (size_t)k * pre_ld;
-      const int pre_rld = N * pre_ld;
-      float* r_k = w.rslot(t, 0, k);
-      const int rl = w.sld(nh), t1l = w.sld(T1_LD), gl2 = w.sld(G2), el = w.sld(ENC_LD), hl = w.sld(HRAW_LD);
-      float* t1 = w.slot(w.t1, T1_LD, t, 0, k);
-      float* t2 = w.slot(w.t2, nh, t, 0, k);
-      float* g2 = w.slot(w.g2, G2, t, 0, k);
-      float* e1 = w.slot(w.e1, nh, t, 0, k);
-      float* e2 = w.slot(w.e2, nh, t, 0, k);
-      float* enc = w.slot(w.enc, ENC_LD, t, 0, k);
-      float* hraw = w.slot(w.hraw, HRAW_LD, t, 0, k);
-      float* gz = w.slot(w.gz, nh, t, 0, k);
-      {
-        Lin a;
-        if (k == 0) a.seg(w.zero_rec, 0, rec::ZW).seg(w.prop_rnn_init, 0, nh);
-        else a.seg(rec_p_t + (size_t)(k - 1) * RW, N * RW, rec::ZW).seg(w.rslot(t, 0, k - 1), rl, nh);
-        if (c.rnn_cell == RNN_LSTM) {
-          float* gates = train ? w.slot(w.rgates, 4 * nh, t, 0, k) : w.rgates;
-          a.add(pre_k, pre_rld, rw).out(gates, w.sld(4 * nh));
-          RUN(a, L_PROP_RNN, R);
-          sq_launch_lstm_cell2(gates, w.sld(4 * nh), k == 0 ? w.prop_rnn_init + nh : w.cslot(t, 0, k - 1), k == 0 ? 0 : rl, r_k, rl,
-                               w.cslot(t, 0, k), rl, R, nh, s);
-        } else if (c.rnn_cell == RNN_GRU) {  // snt.GRU in two launches, [z | r | tanh candidate] kept for the backward pass
-          float* g3 = train ? w.slot(w.rgates, 3 * nh, t, 0, k) : w.rgates;
-          const int g3l = w.sld(3 * nh);
-          const float* hp = k == 0 ? w.prop_rnn_init : w.rslot(t, 0, k - 1);
-          const int hpl = k == 0 ? 0 : rl;
-          a.add(pre_k, pre_rld, rw).out(g3, g3l).gru1(hp, hpl, w.grh, nh, w.gxh, nh, nh);
-          a.a.o3 = g3 + nh; a.a.o3_ld = g3l;
-          RUN(a, L_PROP_RNN, R);
-          Lin b2; b2.seg(w.grh, nh, nh).add(w.gxh, nh, nh).out(r_k, rl).gru2(hp, hpl, g3, g3l, nh);
-          b2.a.o1 = g3 + 2 * nh; b2.a.o1_ld = g3l;
-          RUN(b2, L_PROP_RNN2, R);
-        } else if (k > 0 && fuse_prop) {  // the previous slot's tail rides in this launch
-          const int rc = run_rnn_tail(h, pending_tail, d, L_PROP_RNN, w.rslot(t, 0, k - 1), rl, pre_k, pre_rld, r_k, rl, packed, s);
-          if (rc != 0) return rc;
-        } else {
-          a.add(pre_k, pre_rld, nh).out(r_k, rl).act(ACT_TANH);
-          RUN(a, L_PROP_RNN, R);
-        }
-      }
-      {
-        // T1 columns [transform hidden 1 (ELU) | steps-predictor hidden pre-activation without `what` (linear)]
-        Lin a; a.seg(r_k, rl, nh).add(pre_k + rw, pre_rld, nh + nh / 2).out(t1, t1l).act2(ACT_ELU, ACT_NONE, nh);
-        RUN(a, L_PROP_T1, R);
-        Lin b; b.seg(t1, t1l, nh).out(t2, rl).act(ACT_ELU); RUN(b, L_PROP_T2, R);
-      }
       {
         CropArgs ca; memset(&ca, 0, sizeof(ca));
-        ca.mode = CROP_PROP2; ca.img = img; ca.mask = c.masked_glimpse ? mask : nullptr; ca.mask_row_mul = N;
-        ca.mask_row_add = k; ca.out = g2; ca.out_row_mul = w.tape ? N : 1; ca.rec_prev = rec_prev; ca.rec_new = rec_p_t;
-        ca.t2 = t2; ca.t2_ld = rl; ca.w3 = w.w3_prop; ca.noise = nz; ca.flat = flat; ca.slot = k;
-        if (train) { ca.tp_out = w.slot(w.tp, TP_LD, t, 0, k); ca.tp_out_ld = w.sld(TP_LD); }
-        emit_crop(h, ca, po, d, 1, s);
+        ca.mode = CROP_PROP2; ca.mask = c.masked_glimpse ? mask : nullptr; ca.mask_row_mul = N; ca.mask_row_add = k; ca.rec_prev = rec_prev;
+        const int rc = slot_front(prop, k, ca, true);
+        if (rc != 0) return rc;
       }
-      {
-        Lin a; a.seg(g2, gl2, G2).out(e1, rl).act(ACT_ELU);
-        Lin b; b.seg(e1, rl, nh).out(e2, rl).act(ACT_ELU);
-        Lin e; e.seg(e2, rl, nh).out(enc, el).act2(ACT_NONE, ACT_SOFTPLUS_MIN, nw);
-        RUN_CHAIN3(a, L_GENC0, b, L_GENC1, e, L_WHAT_HEAD, R);
-      }
+      const float* pre_k = w.pre + (size_t)k * pre_ld;
+      const int pre_rld = N * pre_ld;
+      const float* r_k = w.rslot(t, 0, k);
+      const int rl = w.sld(nh), el = w.sld(ENC_LD), hl = w.sld(HRAW_LD);
+      const float* enc = w.slot(w.enc, ENC_LD, t, 0, k);
+      float* hraw = w.slot(w.hraw, HRAW_LD, t, 0, k);
+      float* gz = w.slot(w.gz, nh, t, 0, k);
       if (c.time_cell == CELL_LSTM) {
         float* gates = train ? w.lgates + ((size_t)t * M + k) * 4 * nh : w.lgates;
         const int gld = train ? N * 4 * nh : 4 * nh;
@@ -1225,17 +1255,7 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
         if (fw) { const int rc = run_what(h, 1, temporal_p + (size_t)k * nh, N * nh, R, k, nz, enc, el, rec_prev, rec_p_t, packed, s); if (rc != 0) return rc; }
         else { Lin hd; hd.seg(temporal_p + (size_t)k * nh, N * nh, nh).out(hraw, hl); RUN(hd, L_PROP_HEADS, R); }
       }
-      {
-        TailArgs ta; memset(&ta, 0, sizeof(ta));
-        ta.is_disc = 0; ta.slot = k; ta.hraw = hraw; ta.h_ld = hl; ta.enc = enc; ta.enc_ld = el;
-        ta.rec_prev = rec_prev; ta.rec_new = rec_p_t; ta.noise = nz; ta.s1p = t1 + nh; ta.s1p_ld = t1l;
-        ta.wp = packed + pl.w + h->layers[L_PROP_S1].w_off; ta.flat = flat;
-        ta.w2_off = po.prop_steps_l1_w; ta.b2_off = po.prop_steps_l1_b;
-        if (train) { ta.s1h_out = w.slot(w.s1h, S1_LD, t, 0, k); ta.s1h_ld = w.sld(S1_LD); }
-        ta.what_done = fw ? 1 : 0;
-        if (fuse_prop && k + 1 < N) pending_tail = ta;  // computed inside the next slot's RNN launch
-        else emit_tail(h, ta, d, s);
-      }
+      slot_tail(prop, k, hraw, hl);
     }
     if (w.chain) {
       const int rc = sq_chain_flush(h, w.chain_ctl + (size_t)(2 * t) * SQ_CHAIN_CTL_WORDS, 2 * t, s);
@@ -1254,7 +1274,7 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
     {
       Lin a; a.seg(rec_p_t, RW, rec::ZW).out(lea, nh).act(ACT_ELU); RUN(a, L_LAT0, M);
       Lin b; b.seg(lea, nh, nh).out(leb, nh).act(ACT_ELU); RUN(b, L_LAT1, M);
-      emit_latsum(h, leb, rec_p_t, cvec, d, s);
+      sq_launch_latent_sum(leb, rec_p_t, cvec, d, s);
       Lin p; p.seg(cvec, nh, nh).add(w.pre_disc + (size_t)t * B * rw, rw, rw, K).out(w.pre_d, rw); RUN(p, L_PRED, R);
       if (c.rec_where_prior) {
         Lin q; q.seg(w.rn_init_state, 0, 4).seg(cvec, nh, nh).out(spre_t, 128); RUN(q, L_RNCOND, R);
@@ -1263,75 +1283,17 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
     // ---- G. discovery steps (sqair_modules.py:129-147 static_rnn over DiscoveryCore) ----
     if (w.chain) sq_chain_begin(h, d, po, wsbase, ws_bytes);
     for (int j = 0; j < N; ++j) {
-      float* r_j = w.rslot(t, 1, j);
-      const int rl = w.sld(nh), t1l = w.sld(T1_LD), gl2 = w.sld(G2), el = w.sld(ENC_LD);
-      float* t1 = w.slot(w.t1, T1_LD, t, 1, j);
-      float* t2 = w.slot(w.t2, nh, t, 1, j);
-      float* g2 = w.slot(w.g2, G2, t, 1, j);
-      float* e1 = w.slot(w.e1, nh, t, 1, j);
-      float* e2 = w.slot(w.e2, nh, t, 1, j);
-      float* enc = w.slot(w.enc, ENC_LD, t, 1, j);
-      {
-        Lin a;
-        if (j == 0) a.seg(w.disc_init_rec, 0, rec::ZW).seg(w.disc_rnn_init, 0, nh);
-        else a.seg(rec_d_t + (size_t)(j - 1) * RW, N * RW, rec::ZW).seg(w.rslot(t, 1, j - 1), rl, nh);
-        if (c.rnn_cell == RNN_LSTM) {
-          float* gates = train ? w.slot(w.rgates, 4 * nh, t, 1, j) : w.rgates;
-          a.add(w.pre_d, rw, rw).out(gates, w.sld(4 * nh));
-          RUN(a, L_DISC_RNN, R);
-          sq_launch_lstm_cell2(gates, w.sld(4 * nh), j == 0 ? w.disc_rnn_init + nh : w.cslot(t, 1, j - 1), j == 0 ? 0 : rl, r_j, rl,
-                               w.cslot(t, 1, j), rl, R, nh, s);
-        } else if (c.rnn_cell == RNN_GRU) {
-          float* g3 = train ? w.slot(w.rgates, 3 * nh, t, 1, j) : w.rgates;
-          const int g3l = w.sld(3 * nh);
-          const float* hp = j == 0 ? w.disc_rnn_init : w.rslot(t, 1, j - 1);
-          const int hpl = j == 0 ? 0 : rl;
-          a.add(w.pre_d, rw, rw).out(g3, g3l).gru1(hp, hpl, w.grh, nh, w.gxh, nh, nh);
-          a.a.o3 = g3 + nh; a.a.o3_ld = g3l;
-          RUN(a, L_DISC_RNN, R);
-          Lin b2; b2.seg(w.grh, nh, nh).add(w.gxh, nh, nh).out(r_j, rl).gru2(hp, hpl, g3, g3l, nh);
-          b2.a.o1 = g3 + 2 * nh; b2.a.o1_ld = g3l;
-          RUN(b2, L_DISC_RNN2, R);
-        } else if (j > 0 && fuse_disc) {
-          const int rc = run_rnn_tail(h, pending_tail, d, L_DISC_RNN, w.rslot(t, 1, j - 1), rl, w.pre_d, nh, r_j, rl, packed, s);
-          if (rc != 0) return rc;
-        } else {
-          a.add(w.pre_d, nh, nh).out(r_j, rl).act(ACT_TANH);
-          RUN(a, L_DISC_RNN, R);
-        }
-        Lin b; b.seg(r_j, rl, nh).out(t1, t1l).act2(ACT_ELU, ACT_NONE, nh); RUN(b, L_DISC_T1, R);
-        Lin cc; cc.seg(t1, t1l, nh).out(t2, rl).act(ACT_ELU); RUN(cc, L_DISC_T2, R);
-      }
       {
         CropArgs ca; memset(&ca, 0, sizeof(ca));
-        ca.mode = CROP_DISC; ca.img = img; ca.out = g2; ca.out_row_mul = w.tape ? N : 1; ca.rec_new = rec_d_t; ca.t2 = t2;
-        ca.t2_ld = rl; ca.w3 = w.w3_disc; ca.noise = nz; ca.flat = flat; ca.slot = j;
-        if (train) { ca.tp_out = w.slot(w.tp, TP_LD, t, 1, j); ca.tp_out_ld = w.sld(TP_LD); }
-        emit_crop(h, ca, po, d, 1, s);
-        Lin a; a.seg(g2, gl2, G2).out(e1, rl).act(ACT_ELU);
-        Lin b; b.seg(e1, rl, nh).out(e2, rl).act(ACT_ELU);
-        Lin e; e.seg(e2, rl, nh).out(enc, el).act2(ACT_NONE, ACT_SOFTPLUS_MIN, nw);
-        if (fw) {   // the Gaussian head writes the slot's what sample itself (`enc` has no other reader in a discovery slot)
-          RUN(a, L_GENC0, R);
-          RUN(b, L_GENC1, R);
-          const int rc = run_what(h, 0, e2, rl, R, j, nz, nullptr, 0, nullptr, rec_d_t, packed, s);
-          if (rc != 0) return rc;
-
-        } else {
-          RUN_CHAIN3(a, L_GENC0, b, L_GENC1, e, L_WHAT_HEAD, R);
-        }
+        ca.mode = CROP_DISC;
+        const int rc = slot_front(disc, j, ca, !fw);
+        if (rc != 0) return rc;
       }
-      {
-        TailArgs ta; memset(&ta, 0, sizeof(ta));
-        ta.is_disc = 1; ta.slot = j; ta.enc = enc; ta.enc_ld = el; ta.rec_prev = rec_prev; ta.rec_new = rec_d_t;
-        ta.noise = nz; ta.s1p = t1 + nh; ta.s1p_ld = t1l;
-        ta.wp = packed + pl.w + h->layers[L_DISC_S1].w_off; ta.flat = flat;
-        ta.w2_off = po.disc_steps_l1_w; ta.b2_off = po.disc_steps_l1_b;
-        if (train) { ta.s1h_out = w.slot(w.s1h, S1_LD, t, 1, j); ta.s1h_ld = w.sld(S1_LD); }
-        ta.what_done = fw ? 1 : 0;
-        if (fuse_disc && j + 1 < N) pending_tail = ta;
-        else emit_tail(h, ta, d, s);
+      if (fw) {   // the Gaussian head writes the slot's what sample itself (`enc` has no other reader in a discovery slot)
+        const int rc = run_what(h, 0, w.slot(w.e2, nh, t, 1, j), w.sld(nh), R, j, nz, nullptr, 0, nullptr, rec_d_t, packed, s);
+        if (rc != 0) return rc;
       }
+      slot_tail(disc, j, nullptr, 0);
     }
     if (w.chain) {
       const int rc = sq_chain_flush(h, w.chain_ctl + (size_t)(2 * t + 1) * SQ_CHAIN_CTL_WORDS, 2 * t + 1, s);
@@ -1347,7 +1309,7 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
       ka.rec_next = rec_next; ka.temporal_next = w.state(w.temporal_m, t + 1, w.snh); ka.prior_next = w.state(w.prior_m, t + 1, w.psnh);
       ka.flat = flat; ka.t = t; ka.out = out;
       ka.src_out = train ? w.src + (size_t)t * M : nullptr;
-      emit_compact(h, ka, po, d, s);
+      sq_launch_compact(ka, po, d, s);
     }
   }
   if (!(parts & 4)) return 0;
@@ -1429,7 +1391,7 @@ extern "C" int sqair_clear_workspace(SqairHandle* h, void* workspace, int64_t wo
   const int64_t need = train ? sqair_train_workspace_bytes(h, T, B) : sqair_workspace_bytes(h, T, B);
   if (workspace_bytes < need) { sq_set_error(h, "sqair_clear_workspace: workspace too small"); return -1; }
   const Workspace w = sq_carve(h, T, B, (float*)workspace, train != 0);
-  sq_zero_fill((float*)workspace, (int64_t)((float*)w.prof_ts - (float*)workspace), (hipStream_t)stream);
+  sq_zero_fill((float*)workspace, w.clear_n, (hipStream_t)stream);
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -157,7 +157,7 @@ struct WhatArgs {
 int sq_launch_linear_what(const WhatArgs& a, hipStream_t s);
 int sq_launch_slot_tail(const TailArgs& a, Dims d, hipStream_t s);
 int sq_launch_rnn_tail(const TailArgs& ta, Dims d, const float* hid, int hid_ld, const float* wp, const float* bias, const float* add,
-                       int add_ld, float* out, int out_ld, int n_out, hipStream_t s, unsigned long long* prof_ts);
+                       int add_ld, float* out, int out_ld, int n_out, hipStream_t s);
 int sq_launch_latent_sum(const float* f, const float* rec_p, float* c, Dims d, hipStream_t s);
 
 struct LogprobArgs {

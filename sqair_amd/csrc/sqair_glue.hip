@@ -406,7 +406,7 @@ template <int NH, int TN, bool WD>  // hidden-state chunks per wave = nh / 64; T
 __global__ __launch_bounds__(256) void k_rnn_tail(const TailArgs ta, const Dims d, const float* __restrict__ hid, const int hid_ld,
                                                   const float* __restrict__ wp0, const float* __restrict__ bias,
                                                   const float* __restrict__ add, const int add_ld, float* __restrict__ out,
-                                                  const int out_ld, const int n_out, unsigned long long* __restrict__ prof_ts SQ_TLP) {
+                                                  const int out_ld, const int n_out SQ_TLP) {
   SQ_TL_SCOPE;
   __shared__ __attribute__((aligned(16))) float zt[16 * ZLD];
   __shared__ float rs[4][16];
@@ -415,8 +415,6 @@ __global__ __launch_bounds__(256) void k_rnn_tail(const TailArgs ta, const Dims 
   const int tile_n0 = blockIdx.x * TN, row0 = blockIdx.y * 16;
   const int n_tiles = (n_out + 15) >> 4;
   constexpr int KC = 4 + 4 * NH;
-  unsigned long long t_start = 0;
-  if (prof_ts != nullptr && tid == 0) t_start = wall_clock64();
   // operands of the layer that do not depend on the tail: weights of my chunks, the hidden-state segment, the epilogue operands
   const float* hrow = hid + (size_t)min(row0 + l15, d.R - 1) * hid_ld;
   f32x4_t bz[TN], bh[TN][NH], ah[NH];
@@ -472,15 +470,6 @@ __global__ __launch_bounds__(256) void k_rnn_tail(const TailArgs ta, const Dims 
     const float* rt = red + t * 1024;
     if (m < d.R && n < n_out && tile_n0 + t < n_tiles)
       out[(size_t)m * out_ld + n] = sq_tanh(rt[tid] + rt[256 + tid] + rt[512 + tid] + rt[768 + tid] + p_bias[t] + p_add[t]);
-  }
-  if (prof_ts != nullptr) {
-    __syncthreads();
-    // (stamped by the last column-tile workgroup of every row tile and by workgroup (0, 0) only: one atomic pair per workgroup
-    // serialises thousands of them on one address and made the many-workgroup launches look 2-3x longer than they are)
-    if (tid == 0 && (blockIdx.x == gridDim.x - 1 || (blockIdx.x == 0 && blockIdx.y == 0))) {
-      atomicMin(prof_ts, t_start);
-      atomicMax(prof_ts + 4096, wall_clock64());
-    }
   }
 }
 
@@ -601,9 +590,9 @@ int sq_launch_slot_tail(const TailArgs& a, Dims d, hipStream_t s) {
 // tail of slot `ta.slot` + the VanillaRNN layer of the next slot: out = tanh([z-record | hid] W + bias + add); wp / bias point at
 // the layer's packed weights (K chunks: 4 of the z-record, nh / 16 of the hidden state) and packed bias
 int sq_launch_rnn_tail(const TailArgs& ta, Dims d, const float* hid, int hid_ld, const float* wp, const float* bias, const float* add,
-                       int add_ld, float* out, int out_ld, int n_out, hipStream_t s, unsigned long long* prof_ts) {
+                       int add_ld, float* out, int out_ld, int n_out, hipStream_t s) {
 #ifdef SQAIR_WIDE
-  (void)ta; (void)d; (void)hid; (void)hid_ld; (void)wp; (void)bias; (void)add; (void)add_ld; (void)out; (void)out_ld; (void)n_out; (void)s; (void)prof_ts;
+  (void)ta; (void)d; (void)hid; (void)hid_ld; (void)wp; (void)bias; (void)add; (void)add_ld; (void)out; (void)out_ld; (void)n_out; (void)s;
   return -1;   // (the wide build never fuses the tail: can_fuse_tail, sqair_api.hip)
 #else
   const int nt = (n_out + 15) / 16, mt = (d.R + 15) / 16;
@@ -618,8 +607,8 @@ int sq_launch_rnn_tail(const TailArgs& ta, Dims d, const float* hid, int hid_ld,
     const dim3 g((nt + 1) / 2, mt);
 #define SQ_RT(NH, TN)                                                                                                              \
     do {                                                                                                                             \
-      if (ta.what_done) SQ_LAUNCH((k_rnn_tail<NH, TN, true>), g, dim3(256), 0, s, ta, d, hid, hid_ld, wp, bias, add, add_ld, out, out_ld, n_out, prof_ts); \
-      else SQ_LAUNCH((k_rnn_tail<NH, TN, false>), g, dim3(256), 0, s, ta, d, hid, hid_ld, wp, bias, add, add_ld, out, out_ld, n_out, prof_ts); \
+      if (ta.what_done) SQ_LAUNCH((k_rnn_tail<NH, TN, true>), g, dim3(256), 0, s, ta, d, hid, hid_ld, wp, bias, add, add_ld, out, out_ld, n_out); \
+      else SQ_LAUNCH((k_rnn_tail<NH, TN, false>), g, dim3(256), 0, s, ta, d, hid, hid_ld, wp, bias, add, add_ld, out, out_ld, n_out); \
     } while (0)
     if (d.nh == 256) SQ_RT(4, 2);
     else if (d.nh == 128) SQ_RT(2, 2);

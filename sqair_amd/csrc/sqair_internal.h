@@ -147,7 +147,6 @@ struct Lin {
 // records, so a slot launch addresses it with row stride N * width and the batched weight-gradient GEMMs see all
 // uses of a layer as one long row range).
 // ------------------------------------------------------------------------------------------------
-constexpr int PROF_MAX = 4096;
 // leading dimensions of the activation buffers: room for the widest layer the build accepts (prior statistics 2 (4 + n_what) + 1,
 // glimpse-encoder Gaussian 2 n_what, loc1 n_what, raw heads 5 n_what, transform hidden | steps hidden 1.5 n_hidden, steps hidden
 // n_hidden / 2), each a multiple of 16
@@ -179,8 +178,8 @@ struct Workspace {
   float *qz, *pz, *dlp, *dll, *glimpse, *dec_a, *dec_b;
   float* gen;                                    // sample_from_prior: [T][M][64] prior samples + original presences
   float* obs_p;                                  // frames whose H * W is not a multiple of 4: zero-padded copy [T*B][P4] (else unused)
-  unsigned long long* prof_ts;
-  int64_t total;  // floats
+  int64_t clear_n;  // floats from the base that a workspace clear covers: every buffer carved before chain_ctl
+  int64_t total;    // floats
 
   float* frame(float* base, int64_t per_frame, int t) const { return base + (tape ? (size_t)t * per_frame : 0); }
   float* state(float* base, int t, int width) const { return base + (size_t)(tape ? t : (t & 1)) * M * width; }

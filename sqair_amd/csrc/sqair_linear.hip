@@ -95,8 +95,7 @@ int sq_launch_pack_bias(const float* flat, float* packed_b, const int* idxa, con
 // of NCH with every load of a block in flight at once.
 // ---------------------------------------------------------------------------------------------------
 template <int NCH>
-__global__ __launch_bounds__(256) void k_linear_rows(const LinArgs a, const int kc_total, const int n_tiles,
-                                                     unsigned long long* __restrict__ prof_ts SQ_TLP) {
+__global__ __launch_bounds__(256) void k_linear_rows(const LinArgs a, const int kc_total, const int n_tiles SQ_TLP) {
   SQ_TL_SCOPE;
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
@@ -106,8 +105,6 @@ __global__ __launch_bounds__(256) void k_linear_rows(const LinArgs a, const int 
   (void)n_tiles;
   const int arow = min(tile_m * 16 + (lane & 15), a.M - 1);
   const int kq = lane >> 4;
-  unsigned long long t_start = 0;
-  if (prof_ts != nullptr && tid == 0) t_start = wall_clock64();
 
   // epilogue operands of the 4 outputs of this lane: rows 4*kq + i, column lane & 15
   const int n = tile_n * 16 + (lane & 15);
@@ -195,15 +192,6 @@ __global__ __launch_bounds__(256) void k_linear_rows(const LinArgs a, const int 
       }
     }
   }
-  if (prof_ts != nullptr) {
-    __syncthreads();
-    // (stamped by the last column-tile workgroup of every row tile and by workgroup (0, 0) only: one atomic pair per workgroup
-    // serialises thousands of them on one address and made the many-workgroup launches look 2-3x longer than they are)
-    if (tid == 0 && (blockIdx.x == gridDim.x - 1 || (blockIdx.x == 0 && blockIdx.y == 0))) {
-      atomicMin(prof_ts, t_start);
-      atomicMax(prof_ts + 4096, wall_clock64());
-    }
-  }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -218,8 +206,7 @@ __global__ __launch_bounds__(256) void k_linear_rows(const LinArgs a, const int 
 // so the tile shape is a pure performance choice.  All three epilogues.
 // ---------------------------------------------------------------------------------------------------
 template <int NCH, int MT, int NT, bool COAL = false>
-__global__ __launch_bounds__(256) void k_linear_mt(const LinArgs a, const int kc_total, const int n_tiles,
-                                                   unsigned long long* __restrict__ prof_ts SQ_TLP) {
+__global__ __launch_bounds__(256) void k_linear_mt(const LinArgs a, const int kc_total, const int n_tiles SQ_TLP) {
   SQ_TL_SCOPE;
   static_assert(MT == 1 || MT == 2, "row tiles per wave");
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, kq = lane >> 4;
@@ -231,8 +218,6 @@ __global__ __launch_bounds__(256) void k_linear_mt(const LinArgs a, const int kc
   const int bp_src = (4 * (lane & 15) + kq) * 4;       // byte address for ds_bpermute: the loading lane that holds my operand
   const int tile_n0 = blockIdx.x * NT;
   const int tile_m0 = (blockIdx.y * 4 + wave) * MT;
-  unsigned long long t_start = 0;
-  if (prof_ts != nullptr && tid == 0) t_start = wall_clock64();
   // segment table (wave-uniform) + per-lane row pointers of the (up to two) row tiles, all in NAMED locals: a select
   // chain over members of the by-value argument struct or over elements of a local array is turned into an indexed load
   // from a scratch copy (seen in this kernel's first version: flat loads, s_waitcnt vmcnt(0) after each of them)
@@ -381,15 +366,6 @@ __global__ __launch_bounds__(256) void k_linear_mt(const LinArgs a, const int kc
       x_epilogue(a, m, n, epi_s[wave][e][lane] + a.bias[n] + p_add, p_e0, p_e1, p_scale);
     }
   }
-  if (prof_ts != nullptr) {
-    __syncthreads();
-    // (stamped by the last column-tile workgroup of every row tile and by workgroup (0, 0) only: one atomic pair per workgroup
-    // serialises thousands of them on one address and made the many-workgroup launches look 2-3x longer than they are)
-    if (tid == 0 && (blockIdx.x == gridDim.x - 1 || (blockIdx.x == 0 && blockIdx.y == 0))) {
-      atomicMin(prof_ts, t_start);
-      atomicMax(prof_ts + 4096, wall_clock64());
-    }
-  }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -403,8 +379,7 @@ __global__ __launch_bounds__(256) void k_linear_mt(const LinArgs a, const int kc
 // the last bits (different summation order), never between two launches of this kernel.
 // ---------------------------------------------------------------------------------------------------
 template <int TN>
-__global__ __launch_bounds__(256) void k_linear_lds(const LinArgs a, const int kc_total, const int n_tiles,
-                                                    unsigned long long* __restrict__ prof_ts SQ_TLP) {
+__global__ __launch_bounds__(256) void k_linear_lds(const LinArgs a, const int kc_total, const int n_tiles SQ_TLP) {
   SQ_TL_SCOPE;
   constexpr int LDA = 36;  // 32 floats of a K step + 4 of padding: the 16 rows of a fragment read land on distinct 16-byte slots
   __shared__ __attribute__((aligned(16))) float lds[2 * 128 * LDA];
@@ -412,8 +387,6 @@ __global__ __launch_bounds__(256) void k_linear_lds(const LinArgs a, const int k
   const int wave_m = wave >> 1, wave_n = wave & 1;
   const int row0 = blockIdx.y * 128;
   const int tile_n0 = (blockIdx.x * 2 + wave_n) * TN;
-  unsigned long long t_start = 0;
-  if (prof_ts != nullptr && tid == 0) t_start = wall_clock64();
   // segment table in named locals (see k_linear_mt)
   const float* sp0 = a.seg[0].p; const float* sp1 = a.seg[1].p; const float* sp2 = a.seg[2].p; const float* sp3 = a.seg[3].p;
   const int sl0 = a.seg[0].ld, sl1 = a.seg[1].ld, sl2 = a.seg[2].ld, sl3 = a.seg[3].ld;
@@ -531,15 +504,6 @@ __global__ __launch_bounds__(256) void k_linear_lds(const LinArgs a, const int k
         if (g2) { p_e0 = a.e0[(size_t)m * a.e0_ld + n]; p_e1 = a.e1[(size_t)m * a.e1_ld + n]; }
         x_epilogue(a, m, n, epi[e * 64 + lane] + a.bias[n] + p_add, p_e0, p_e1, p_scale);
       }
-    }
-  }
-  if (prof_ts != nullptr) {
-    __syncthreads();
-    // (stamped by the last column-tile workgroup of every row tile and by workgroup (0, 0) only: one atomic pair per workgroup
-    // serialises thousands of them on one address and made the many-workgroup launches look 2-3x longer than they are)
-    if (tid == 0 && (blockIdx.x == gridDim.x - 1 || (blockIdx.x == 0 && blockIdx.y == 0))) {
-      atomicMin(prof_ts, t_start);
-      atomicMax(prof_ts + 4096, wall_clock64());
     }
   }
 }
@@ -919,7 +883,6 @@ static MtShape pick_mt_shape(int M, int n_tiles, int kc) {
     const char* e = SQ_KNOB_STR("SQAIR_MT");
     if (e != nullptr) sscanf(e, "%d,%d,%d", &ov_mt, &ov_nt, &ov_coal);
   }
-  (void)kc;
   MtShape sh;
   if (M >= 2048) sh = MtShape{1, (M >= 16384 && n_tiles >= 2) ? 2 : 1, 1};
   else if (n_tiles >= 64) sh = MtShape{1, 1, 1};
@@ -931,40 +894,34 @@ static MtShape pick_mt_shape(int M, int n_tiles, int kc) {
 }
 
 template <int NCH, int MT, int NT>
-static void launch_mt(const LinArgs& a, const PackedLayer& L, int mt, bool coal, hipStream_t s, unsigned long long* prof_ts) {
+static void launch_mt(const LinArgs& a, const PackedLayer& L, int mt, bool coal, hipStream_t s) {
   const dim3 g((L.nt + NT - 1) / NT, (mt + 4 * MT - 1) / (4 * MT));
-  if (coal) SQ_LAUNCH((k_linear_mt<NCH, MT, NT, true>), g, dim3(256), 0, s, a, L.kc, L.nt, prof_ts);
-  else SQ_LAUNCH((k_linear_mt<NCH, MT, NT, false>), g, dim3(256), 0, s, a, L.kc, L.nt, prof_ts);
+  if (coal) SQ_LAUNCH((k_linear_mt<NCH, MT, NT, true>), g, dim3(256), 0, s, a, L.kc, L.nt);
+  else SQ_LAUNCH((k_linear_mt<NCH, MT, NT, false>), g, dim3(256), 0, s, a, L.kc, L.nt);
 }
 
 template <int NCH, int NSEG>
-static void launch_seg(const LinArgs& a, const PackedLayer& L, hipStream_t s, unsigned long long* prof_ts) {
+static void launch_seg(const LinArgs& a, const PackedLayer& L, hipStream_t s) {
   const dim3 g(L.nt, (a.M + 15) / 16);
   // the GRU gate epilogues are compiled out of the instantiation the plain layers use (the slot loop rotates through ~10 code
   // objects; the smaller they are, the more of them stay in the instruction cache)
-#define SQ_LAUNCH_KL(G, P) SQ_LAUNCH((k_linear<NCH, NSEG, G, P>), g, dim3(256), 0, s, a.seg[0].p, a.wp, a.seg[0].ld, a.seg[0].width, a.seg[0].rmul, a.M, L.kc, L.nt, a.wzero, a, prof_ts)
-  // (likewise the device-clock stamps of the profiling pass exist only in the instantiations that pass launches)
-  if (prof_ts == nullptr) {
-    if (a.epi == EPI_ACT) SQ_LAUNCH_KL(false, false); else SQ_LAUNCH_KL(true, false);
-  } else {
-    if (a.epi == EPI_ACT) SQ_LAUNCH_KL(false, true); else SQ_LAUNCH_KL(true, true);
-  }
+#define SQ_LAUNCH_KL(G) SQ_LAUNCH((k_linear<NCH, NSEG, G>), g, dim3(256), 0, s, a.seg[0].p, a.wp, a.seg[0].ld, a.seg[0].width, a.seg[0].rmul, a.M, L.kc, L.nt, a.wzero, a)
+  if (a.epi == EPI_ACT) SQ_LAUNCH_KL(false); else SQ_LAUNCH_KL(true);
 #undef SQ_LAUNCH_KL
 }
 template <int NCH>
-static void launch_nch(const LinArgs& a, const PackedLayer& L, int grid, hipStream_t s, unsigned long long* prof_ts) {
-  (void)grid;
+static void launch_nch(const LinArgs& a, const PackedLayer& L, hipStream_t s) {
   switch (a.nseg) {  // the segment count is a template parameter: dead segment-selection code disappears
-    case 1: launch_seg<NCH, 1>(a, L, s, prof_ts); break;
-    case 2: launch_seg<NCH, 2>(a, L, s, prof_ts); break;
-    case 3: launch_seg<NCH, 3>(a, L, s, prof_ts); break;
-    default: launch_seg<NCH, 4>(a, L, s, prof_ts); break;
+    case 1: launch_seg<NCH, 1>(a, L, s); break;
+    case 2: launch_seg<NCH, 2>(a, L, s); break;
+    case 3: launch_seg<NCH, 3>(a, L, s); break;
+    default: launch_seg<NCH, 4>(a, L, s); break;
   }
 }
 
 static unsigned rmul_of(int rdiv) { return rdiv <= 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)rdiv) + 1u; }
 
-int sq_launch_linear(const LinArgs& a_in, const PackedLayer& L, hipStream_t s, unsigned long long* prof_ts) {
+int sq_launch_linear(const LinArgs& a_in, const PackedLayer& L, hipStream_t s) {
   LinArgs a = a_in;
   for (int i = 0; i < a.nseg; ++i) a.seg[i].rmul = rmul_of(a.seg[i].rdiv);
   a.add_rmul = rmul_of(a.add_rdiv);
@@ -994,12 +951,12 @@ int sq_launch_linear(const LinArgs& a_in, const PackedLayer& L, hipStream_t s, u
   // tools/time_linear.py, back to back, 1920 x 362 x 1152 35.7 -> 33.2 us, 1920 x 312 x 768 21.2 -> 19.2 (every 256 / 400-column
   // layer would be twice as slow; at 1280 rows 362 x 1152 gains back to back, 24.3 -> 21.1, but not in the pass, and
   // 312 x 768 loses, 14.7 -> 18.4).  cfg-4 (1920 rows per frame): forward 6.13 -> 6.07 ms, training 14.16 -> 14.12.
-  const bool mid_wide = prof_ts == nullptr && L.kc > 4 && a.M >= 1792 && L.nt >= 48;
+  const bool mid_wide = L.kc > 4 && a.M >= 1792 && L.nt >= 48;
   if (a.M >= mt_rows || mid_wide) {
     // (all of them accumulate in the same order: the tile shape never changes a result)
     if (L.kc <= 4) {  // K <= 64: one block of loads, nothing to pipeline
       const dim3 grid_r(L.nt, (mt + 3) / 4);
-      SQ_LAUNCH(k_linear_rows<4>, grid_r, dim3(256), 0, s, a, L.kc, L.nt, prof_ts);
+      SQ_LAUNCH(k_linear_rows<4>, grid_r, dim3(256), 0, s, a, L.kc, L.nt);
       return 0;
     }
     // the LDS-tiled kernel pays once its 128 x 64 workgroup tiles fill the chip twice over (measured, tools/time_linear.py:
@@ -1009,7 +966,7 @@ int sq_launch_linear(const LinArgs& a_in, const PackedLayer& L, hipStream_t s, u
     // 28 -> 25, 5120 x 256 x 256 18 -> 17.4); the 128 x 64 tile (TNW = 2) beats 128 x 128 wherever the tile count is what
     // limits (all of these shapes: 80 - 1600 tiles on 256 CUs)
     static const int big = SQ_KNOB_INT("SQAIR_BIG", 2);  // measurement knob: 0 = off
-    if (big > 0 && prof_ts == nullptr && L.nt >= 4) {
+    if (big > 0 && L.nt >= 4) {
 #ifdef SQAIR_KNOBS
       if (const char* e = SQ_KNOB_STR("SQAIR_BIG_SHAPE")) {   // "TMW,TNW": forced tile (measurement)
         const int tm = e[0] - '0', tn = e[2] - '0';
@@ -1030,12 +987,12 @@ int sq_launch_linear(const LinArgs& a_in, const PackedLayer& L, hipStream_t s, u
     }
     static const int lds_wgs = SQ_KNOB_INT("SQAIR_LDS_WGS", 512);  // measurement knob
     if (((a.M + 127) / 128) * ((L.nt + 3) / 4) >= lds_wgs) {
-      SQ_LAUNCH((k_linear_lds<2>), dim3((L.nt + 3) / 4, (a.M + 127) / 128), dim3(256), 0, s, a, L.kc, L.nt, prof_ts);
+      SQ_LAUNCH((k_linear_lds<2>), dim3((L.nt + 3) / 4, (a.M + 127) / 128), dim3(256), 0, s, a, L.kc, L.nt);
       return 0;
     }
     const MtShape sh = pick_mt_shape(a.M, L.nt, L.kc);
-    if (sh.nt >= 2) launch_mt<4, 1, 2>(a, L, mt, sh.coal != 0, s, prof_ts);
-    else launch_mt<4, 1, 1>(a, L, mt, sh.coal != 0, s, prof_ts);
+    if (sh.nt >= 2) launch_mt<4, 1, 2>(a, L, mt, sh.coal != 0, s);
+    else launch_mt<4, 1, 1>(a, L, mt, sh.coal != 0, s);
     return 0;
   }
   const int per_wave = (L.kc + 3) / 4;
@@ -1044,21 +1001,21 @@ int sq_launch_linear(const LinArgs& a_in, const PackedLayer& L, hipStream_t s, u
   // back to back (tools/time_linear.py): 640 x 1152 x 384 17.9 -> 12.1 us, 640 x 768 x 320 17.3 -> 8.8; at K <= 400 the
   // 16 x 16 tile is as fast or faster (640 x 362 x 1152 13.6 / 13.2, 640 x 312 x 768 8.6 / 9.5) and keeps those layers
   static const int t2_rows = SQ_KNOB_INT("SQAIR_T2_ROWS", 512), t2_kc = SQ_KNOB_INT("SQAIR_T2_KC", 40);  // measurement knobs
-  if (a.M >= t2_rows && L.nt >= 4 && L.kc >= t2_kc && prof_ts == nullptr) {
+  if (a.M >= t2_rows && L.nt >= 4 && L.kc >= t2_kc) {
     launch_t2_any(a, L, s);
     return 0;
   }
   switch (per_wave) {
-    case 1: launch_nch<1>(a, L, grid, s, prof_ts); break;
-    case 2: launch_nch<2>(a, L, grid, s, prof_ts); break;
-    case 3: launch_nch<3>(a, L, grid, s, prof_ts); break;
-    case 4: launch_nch<4>(a, L, grid, s, prof_ts); break;
-    case 5: launch_nch<5>(a, L, grid, s, prof_ts); break;
-    case 6: launch_nch<6>(a, L, grid, s, prof_ts); break;
-    case 7: launch_nch<7>(a, L, grid, s, prof_ts); break;
-    case 8: launch_nch<8>(a, L, grid, s, prof_ts); break;
-    case 9: launch_nch<9>(a, L, grid, s, prof_ts); break;
-    default: launch_nch<10>(a, L, grid, s, prof_ts); break;  // deeper K: blocks of 10 chunks per wave
+    case 1: launch_nch<1>(a, L, s); break;
+    case 2: launch_nch<2>(a, L, s); break;
+    case 3: launch_nch<3>(a, L, s); break;
+    case 4: launch_nch<4>(a, L, s); break;
+    case 5: launch_nch<5>(a, L, s); break;
+    case 6: launch_nch<6>(a, L, s); break;
+    case 7: launch_nch<7>(a, L, s); break;
+    case 8: launch_nch<8>(a, L, s); break;
+    case 9: launch_nch<9>(a, L, s); break;
+    default: launch_nch<10>(a, L, s); break;  // deeper K: blocks of 10 chunks per wave
   }
   return 0;
 }

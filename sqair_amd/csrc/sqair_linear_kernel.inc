@@ -2,11 +2,10 @@
 // tools/linear_floor.hip (ablation variants selected with SQ_ABL_* macros).
 // NCH = K-chunks per wave handled per block of the (normally single-trip) chunk loop; the host picks
 // the instantiation that covers ceil(kc / 4) so that all operand loads of a wave are in flight at once.
-template <int NCH, int NSEG = 4, bool GRU = true, bool PROF = true>
+template <int NCH, int NSEG = 4, bool GRU = true>
 __global__ __launch_bounds__(256) void SQ_KLINEAR_NAME(const float* __restrict__ p0, const float* __restrict__ wp0, const int ld0,
                                                 const int width0, const unsigned rmul0, const int M0, const int kc_total,
-                                                const int n_tiles, const float* __restrict__ wzero0, const LinArgs a,
-                                                unsigned long long* __restrict__ prof_ts SQ_TLP) {
+                                                const int n_tiles, const float* __restrict__ wzero0, const LinArgs a SQ_TLP) {
   SQ_TL_SCOPE;
   // The leading scalars repeat segment 0 / the weight pointer / M of `a`: scalar kernel arguments are eligible for
   // kernarg preloading into SGPRs (-mllvm -amdgpu-kernarg-preload-count), a by-value struct is not — with them the
@@ -35,8 +34,6 @@ __global__ __launch_bounds__(256) void SQ_KLINEAR_NAME(const float* __restrict__
 #endif
   const int arow = min(tile_m * 16 + (lane & 15), M0 - 1);
   const int kq = lane >> 4;
-  unsigned long long t_start = 0;
-  if (PROF && prof_ts != nullptr && tid == 0) t_start = wall_clock64();
 
   const f32x4* __restrict__ wp = reinterpret_cast<const f32x4*>(wp0) + ((size_t)tile_n * kc_total) * 64 + lane;
   const int nmine = (kc_total - wave + 3) >> 2;  // this wave owns global chunks g = wave + 4 i
@@ -79,8 +76,6 @@ __global__ __launch_bounds__(256) void SQ_KLINEAR_NAME(const float* __restrict__
   }
 
 #undef SQ_ROWOF
-  unsigned long long t_setup = 0, t_mfma = 0;
-  if (PROF && prof_ts != nullptr && tid == 0) t_setup = wall_clock64();
   f32x4 acc0 = {0.0f, 0.0f, 0.0f, 0.0f}, acc1 = {0.0f, 0.0f, 0.0f, 0.0f};
 #ifdef SQ_ABL_NO_A
 #define SQ_KL_LOADA(p) f32x4{1.0f, 1.0f, 1.0f, 1.0f}
@@ -174,7 +169,6 @@ __global__ __launch_bounds__(256) void SQ_KLINEAR_NAME(const float* __restrict__
     }
   }
 #endif
-  if (PROF && prof_ts != nullptr && tid == 0) t_mfma = wall_clock64();
   // split-K reduction: acc[i] of lane l is C[row = 4*(l>>4) + i][col = l & 15]
   float* r = red + wave * 256;
   r[(4 * kq + 0) * 16 + (lane & 15)] = acc0.x + acc1.x;
@@ -201,20 +195,6 @@ __global__ __launch_bounds__(256) void SQ_KLINEAR_NAME(const float* __restrict__
       const float hc = sq_tanh(v);
       a.out[(size_t)m * a.out_ld + n] = sq_gru_blend(p_e1, p_e0, hc);
       if (a.o1 != nullptr) a.o1[(size_t)m * a.o1_ld + n] = hc;
-    }
-  }
-  if (PROF && prof_ts != nullptr) {
-    __syncthreads();
-    // (stamped by the last column-tile workgroup of every row tile and by workgroup (0, 0) only: one atomic pair per workgroup
-    // serialises thousands of them on one address and made the many-workgroup launches look 2-3x longer than they are)
-    if (tid == 0 && (blockIdx.x == gridDim.x - 1 || (blockIdx.x == 0 && blockIdx.y == 0))) {
-      atomicMin(prof_ts, t_start);
-      atomicMax(prof_ts + 4096, wall_clock64());  // end slots follow the PROF_MAX start slots
-      if (blockIdx.x == 0 && blockIdx.y == 0) {  // phase stamps of workgroup (0,0): setup done, MFMAs done
-        prof_ts[2 * 4096] = t_setup - t_start;
-        prof_ts[3 * 4096] = t_mfma - t_start;
-        prof_ts[4 * 4096] = wall_clock64() - t_start;
-      }
     }
   }
 }

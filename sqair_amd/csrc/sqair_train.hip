@@ -206,6 +206,21 @@ extern "C" int64_t sqair_backward_bytes(const SqairHandle* h, int T, int B) {
 
 #define CK(x) do { int _r = (x); if (_r != 0) { sq_set_error(h, std::string("sqair_backward: ") + #x); return _r; } } while (0)
 
+// What the two slot loops of the reverse sweep differ in -- propagation (tape phase 0) and discovery (phase 1) -- filled once per
+// frame; the lower part of the slot adjoint (sqair_backward: slot_adjoint) is the same code for both.
+struct SlotAdjPhase {
+  int ph;                              // tape phase
+  LayerId rnn, rnn2, t1, t2;
+  const float* rec; float* d_rec;      // the frame's records of this phase and their gradient
+  const float* rnn_init;               // slot 0's RNN state ([hidden | cell] with an LSTM slot RNN)
+  float* d_init;                       // gradient of slot 0's hidden state, the frame's rows (column sum after the sweep)
+  float* d_init_cell;                  // LSTM slot RNN: gradient of slot 0's cell state in flat_grad
+  float* d_pre; int d_pre_step, d_pre_ld;   // second copies of the slot-RNN and T1 pre-activation gradients (propagation: slot k's
+                                            // block of the frame's d_pre at d_pre + k * d_pre_step, row stride d_pre_ld), or none
+  const float* w3;                     // the transform's output layer
+  bool d_r_every_slot;                 // d_r[k & 1] holds a contribution in the last slot too (propagation: the temporal cell's gate dX)
+};
+
 extern "C" int sqair_backward(SqairHandle* h, const float* flat, const void* packedv, const float* obs, const float* noise,
                               const float* importance_weights, const float* vimco_signal, int T, int B, int t_offset,
                               void* train_workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes,
@@ -343,8 +358,6 @@ extern "C" int sqair_backward(SqairHandle* h, const float* flat, const void* pac
     CK(sq_launch_logprob_bwd(la, po, d, T, s));
   }
 
-  // the adjoint of the transform's 8-wide output layer rides in the crop adjoint that produces its input (80 launches fewer)
-  const bool fuse_t3 = !SQ_KNOB_SET("SQAIR_NO_T3_FUSION");
   // ================= reverse sweep over the frames =================
   for (int t = T - 1; t >= 0; --t) {
     const float* img = obs + (size_t)t * B * PL;
@@ -371,22 +384,79 @@ extern "C" int sqair_backward(SqairHandle* h, const float* flat, const void* pac
       ka.d_new_temporal = b.d_new_t + (size_t)t * R * snh; ka.d_new_prior = b.d_new_p + (size_t)t * R * psnh;
       sq_launch_compact_bwd(ka, po, d, s);
     }
+    // ---- the lower part of a slot's adjoint, the same for both slot loops: glimpse encoder (WHAT_HEAD -> GENC1 -> GENC0 dX),
+    //      crop #2 (`ca` arrives with the phase's own fields) with the adjoint of the transform's 8-wide output layer inside
+    //      (80 launches fewer), T2 dX, then the slot RNN: T1 dX, the cell adjoint, the RNN layer's dX into the previous slot
+    auto slot_adjoint = [&](const SlotAdjPhase& sp, int k, CropChainBwdArgs ca) -> int {
+      float* d_t1 = slotp(b.d_t1, T1_LD, t, sp.ph, k);
+      float* d_t2 = slotp(b.d_t2, nh, t, sp.ph, k);
+      float* d_tp = slotp(b.d_tp, TP_LD, t, sp.ph, k);
+      float* d_e1 = slotp(b.d_e1, nh, t, sp.ph, k);
+      float* d_e2 = slotp(b.d_e2, nh, t, sp.ph, k);
+      float* d_enc3 = slotp(b.d_enc3, ENC_LD, t, sp.ph, k);
+      float* d_rnn = slotp(b.d_rnn, rw, t, sp.ph, k);
+      const int drl = N * rw;
+      const float* r_k = cslotp(w.r, nh, t, sp.ph, k);
+      const float* t1 = cslotp(w.t1, T1_LD, t, sp.ph, k);
+      const float* t2 = cslotp(w.t2, nh, t, sp.ph, k);
+      const float* e1 = cslotp(w.e1, nh, t, sp.ph, k);
+      const float* e2 = cslotp(w.e2, nh, t, sp.ph, k);
+      float* d_pre_k = sp.d_pre ? sp.d_pre + (size_t)k * sp.d_pre_step : nullptr;   // columns: rnn 0:rw | T1 rw:rw+nh | ...
+      { Dx x(d_enc3, el); x.to(0, nh, d_e2, rl).dact(e2, rl, ACT_ELU); CK(rundx(L_WHAT_HEAD, x, R)); }
+      { Dx x(d_e2, rl); x.to(0, nh, d_e1, rl).dact(e1, rl, ACT_ELU); CK(rundx(L_GENC1, x, R)); }
+      { Dx x(d_e1, rl); x.to(0, G2, b.d_g, G2); CK(rundx(L_GENC0, x, R)); }
+      ca.slot = k; ca.img = img; ca.rec_prev = rec_prev; ca.rec_new = sp.rec; ca.d_rec_prev = d_rec_prev; ca.d_rec_new = sp.d_rec;
+      ca.g_out = b.d_g; ca.g_row_mul = 1; ca.tp = cslotp(w.tp, TP_LD, t, sp.ph, k); ca.tp_ld = tpl; ca.d_tp = d_tp; ca.dtp_ld = tpl;
+      ca.noise = nz; ca.flat = flat; ca.flat_grad = flat_grad; ca.w3 = sp.w3; ca.t2 = t2; ca.t2_ld = rl; ca.d_t2 = d_t2; ca.dt2_ld = rl;
+      CK(sq_launch_crop_chain_bwd(ca, po, d, 1, s));
+      { Dx x(d_t2, rl); x.to(0, nh, d_t1, t1l).dact(t1, t1l, ACT_ELU).dup(d_pre_k ? d_pre_k + rw : nullptr, sp.d_pre_ld); CK(rundx(sp.t2, x, R)); }
+      // d h_k = T1^T + what d_r[k & 1] holds (the next slot's RNN; in propagation also the temporal cell's gate GEMM)
+      const bool d_r_in = k < N - 1 || sp.d_r_every_slot;
+      if (c.rnn_cell == RNN_LSTM) {  // cell adjoint -> gate pre-activation gradients, d c_{k-1}
+        Dx x(d_t1, t1l); x.to(0, nh, b.d_hk, nh);
+        if (d_r_in) x.add(b.d_r[k & 1], nh);
+        CK(rundx(sp.t1, x, R));
+        sq_launch_lstm_cell_bwd(cslotp(w.rgates, 4 * nh, t, sp.ph, k), N * 4 * nh, k == 0 ? sp.rnn_init + nh : cslotp(w.rc, nh, t, sp.ph, k - 1),
+                                k == 0 ? 0 : rl, b.d_hk, nh, k < N - 1 ? b.d_cs[k & 1] : nullptr, nh, d_rnn, drl, b.d_cs[(k + 1) & 1], nh, R, nh, s,
+                                d_pre_k, sp.d_pre_ld);
+      } else if (c.rnn_cell == RNN_GRU) {  // GRU adjoint in the two stages of the temporal cell; d h_{k-1} starts in d_r[(k-1)&1] / d_init
+        Dx x(d_t1, t1l); x.to(0, nh, b.d_hk, nh);
+        if (d_r_in) x.add(b.d_r[k & 1], nh);
+        CK(rundx(sp.t1, x, R));
+        const float* g3 = cslotp(w.rgates, 3 * nh, t, sp.ph, k);
+        const float* hp = k == 0 ? sp.rnn_init : cslotp(w.r, nh, t, sp.ph, k - 1);
+        const int g3l = N * 3 * nh, hpl = k == 0 ? 0 : rl;
+        float* dhp = k > 0 ? b.d_r[(k - 1) & 1] : sp.d_init;
+        sq_launch_gru_bwd_a(b.d_hk, nh, g3, g3l, g3 + 2 * nh, g3l, hp, hpl, d_rnn, drl, dhp, nh, R, nh, 0, s, d_pre_k, sp.d_pre_ld,
+                            d_pre_k ? 2 * nh : -1);
+        { Dx y(d_rnn + 2 * nh, drl); y.to(0, nh, b.d_rh, nh); CK(rundx(sp.rnn2, y, R)); }
+        sq_launch_gru_bwd_b(b.d_rh, nh, g3 + nh, g3l, hp, hpl, d_rnn, drl, dhp, nh, R, nh, s, d_pre_k ? d_pre_k + nh : nullptr, sp.d_pre_ld);
+      } else {  // tanh' -> d pre-activation (incl. the steps-predictor columns of T1)
+        Dx x(d_t1, t1l); x.to(0, nh, d_rnn, rl);
+        if (d_r_in) x.add(b.d_r[k & 1], nh);
+        x.dact(r_k, rl, ACT_TANH).dup(d_pre_k, sp.d_pre_ld);
+        CK(rundx(sp.t1, x, R));
+      }
+      Dx x(d_rnn, drl);
+      if (k > 0) {
+        x.to(0, rec::ZW, sp.d_rec + (size_t)(k - 1) * RW, N * RW).acc();
+        x.to(rec::ZWP, rec::ZWP + nh, b.d_r[(k - 1) & 1], nh);
+      } else {
+        x.to(rec::ZWP, rec::ZWP + nh, sp.d_init, nh);   // d (initial hidden state): column sum after the sweep
+      }
+      if (c.rnn_cell == RNN_GRU) x.acc();   // the gate adjoints above already put their direct part there
+      CK(rundx(sp.rnn, x, R));
+      if (k == 0 && c.rnn_cell == RNN_LSTM) sq_launch_colsum(b.d_cs[1], nh, R, nh, sp.d_init_cell, 1, s);
+      return 0;
+    };
+
     // ---- G^T. discovery steps
     float* d_pre_d = b.d_pre_d + (size_t)t * R * rw;
+    const SlotAdjPhase disc = {1, L_DISC_RNN, L_DISC_RNN2, L_DISC_T1, L_DISC_T2, rec_d_t, d_rec_d_t, w.disc_rnn_init,
+                               b.d_init_d + (size_t)t * R * nh, flat_grad + po.disc_rnn_init + nh, nullptr, 0, 0, w.w3_disc, false};
     for (int j = N - 1; j >= 0; --j) {
       float* d_t1 = slotp(b.d_t1, T1_LD, t, 1, j);
-      float* d_t2 = slotp(b.d_t2, nh, t, 1, j);
-      float* d_tp = slotp(b.d_tp, TP_LD, t, 1, j);
-      float* d_e1 = slotp(b.d_e1, nh, t, 1, j);
-      float* d_e2 = slotp(b.d_e2, nh, t, 1, j);
       float* d_enc3 = slotp(b.d_enc3, ENC_LD, t, 1, j);
-      float* d_rnn = slotp(b.d_rnn, rw, t, 1, j);
-      const int drl = N * rw;
-      const float* r_j = cslotp(w.r, nh, t, 1, j);
-      const float* t1 = cslotp(w.t1, T1_LD, t, 1, j);
-      const float* t2 = cslotp(w.t2, nh, t, 1, j);
-      const float* e1 = cslotp(w.e1, nh, t, 1, j);
-      const float* e2 = cslotp(w.e2, nh, t, 1, j);
       const float* enc = cslotp(w.enc, ENC_LD, t, 1, j);
       {
         TailBwdArgs ta; memset(&ta, 0, sizeof(ta));
@@ -397,54 +467,10 @@ extern "C" int sqair_backward(SqairHandle* h, const float* flat, const void* pac
         ta.wwhat_off = (int)P(h, "disc.steps.l0.w") + nh * nsp;
         CK(sq_launch_slot_tail_bwd(ta, d, s));
       }
-      { Dx x(d_enc3, el); x.to(0, nh, d_e2, rl).dact(e2, rl, ACT_ELU); CK(rundx(L_WHAT_HEAD, x, R)); }
-      { Dx x(d_e2, rl); x.to(0, nh, d_e1, rl).dact(e1, rl, ACT_ELU); CK(rundx(L_GENC1, x, R)); }
-      { Dx x(d_e1, rl); x.to(0, G2, b.d_g, G2); CK(rundx(L_GENC0, x, R)); }
-      {
-        CropChainBwdArgs ca; memset(&ca, 0, sizeof(ca));
-        ca.mode = CROP_DISC; ca.slot = j; ca.img = img; ca.rec_prev = rec_prev; ca.rec_new = rec_d_t; ca.d_rec_prev = d_rec_prev;
-        ca.d_rec_new = d_rec_d_t; ca.g_out = b.d_g; ca.g_row_mul = 1; ca.tp = cslotp(w.tp, TP_LD, t, 1, j); ca.tp_ld = tpl;
-        ca.d_tp = d_tp; ca.dtp_ld = tpl; ca.noise = nz; ca.flat = flat; ca.flat_grad = flat_grad;
-        if (fuse_t3) { ca.w3 = w.w3_disc; ca.t2 = t2; ca.t2_ld = rl; ca.d_t2 = d_t2; ca.dt2_ld = rl; }
-        CK(sq_launch_crop_chain_bwd(ca, po, d, 1, s));
-      }
-      if (!fuse_t3) { Dx x(d_tp, tpl); x.to(0, nh, d_t2, rl).dact(t2, rl, ACT_ELU); CK(rundx(L_DISC_T3, x, R)); }
-      { Dx x(d_t2, rl); x.to(0, nh, d_t1, t1l).dact(t1, t1l, ACT_ELU); CK(rundx(L_DISC_T2, x, R)); }
-      if (c.rnn_cell == RNN_LSTM) {  // d h_j = T1^T + the next slot's RNN; cell adjoint -> gate pre-activation gradients, d c_{j-1}
-        Dx x(d_t1, t1l); x.to(0, nh, b.d_hk, nh);
-        if (j < N - 1) x.add(b.d_r[j & 1], nh);
-        CK(rundx(L_DISC_T1, x, R));
-        sq_launch_lstm_cell_bwd(cslotp(w.rgates, 4 * nh, t, 1, j), N * 4 * nh, j == 0 ? w.disc_rnn_init + nh : cslotp(w.rc, nh, t, 1, j - 1),
-                                j == 0 ? 0 : rl, b.d_hk, nh, j < N - 1 ? b.d_cs[j & 1] : nullptr, nh, d_rnn, drl, b.d_cs[(j + 1) & 1], nh, R, nh, s);
-      } else if (c.rnn_cell == RNN_GRU) {  // GRU adjoint in the two stages of the temporal cell; d h_{j-1} starts in d_r[(j-1)&1] / tmp
-        Dx x(d_t1, t1l); x.to(0, nh, b.d_hk, nh);
-        if (j < N - 1) x.add(b.d_r[j & 1], nh);
-        CK(rundx(L_DISC_T1, x, R));
-        const float* g3 = cslotp(w.rgates, 3 * nh, t, 1, j);
-        const float* hp = j == 0 ? w.disc_rnn_init : cslotp(w.r, nh, t, 1, j - 1);
-        const int g3l = N * 3 * nh, hpl = j == 0 ? 0 : rl;
-        float* dhp = j > 0 ? b.d_r[(j - 1) & 1] : b.d_init_d + (size_t)t * R * nh;
-        sq_launch_gru_bwd_a(b.d_hk, nh, g3, g3l, g3 + 2 * nh, g3l, hp, hpl, d_rnn, drl, dhp, nh, R, nh, 0, s);
-        { Dx y(d_rnn + 2 * nh, drl); y.to(0, nh, b.d_rh, nh); CK(rundx(L_DISC_RNN2, y, R)); }
-        sq_launch_gru_bwd_b(b.d_rh, nh, g3 + nh, g3l, hp, hpl, d_rnn, drl, dhp, nh, R, nh, s);
-      } else {  // d r_j = T1^T (incl. the steps-predictor columns) + what the next slot's RNN sent back; tanh' -> d pre-activation
-        Dx x(d_t1, t1l); x.to(0, nh, d_rnn, rl);
-        if (j < N - 1) x.add(b.d_r[j & 1], nh);
-        x.dact(r_j, rl, ACT_TANH);
-        CK(rundx(L_DISC_T1, x, R));
-      }
-      if (j > 0) {
-        Dx x(d_rnn, drl);
-        x.to(0, rec::ZW, d_rec_d_t + (size_t)(j - 1) * RW, N * RW).acc();
-        x.to(rec::ZWP, rec::ZWP + nh, b.d_r[(j - 1) & 1], nh);
-        if (c.rnn_cell == RNN_GRU) x.acc();   // the gate adjoints above already put their direct part there
-        CK(rundx(L_DISC_RNN, x, R));
-      } else {
-        Dx x(d_rnn, drl); x.to(rec::ZWP, rec::ZWP + nh, b.d_init_d + (size_t)t * R * nh, nh);   // d (initial hidden state): column sum after the sweep
-        if (c.rnn_cell == RNN_GRU) x.acc();
-        CK(rundx(L_DISC_RNN, x, R));
-        if (c.rnn_cell == RNN_LSTM) sq_launch_colsum(b.d_cs[1], nh, R, nh, flat_grad + po.disc_rnn_init + nh, 1, s);
-      }
+      CropChainBwdArgs ca; memset(&ca, 0, sizeof(ca));
+      ca.mode = CROP_DISC;
+      const int rc = slot_adjoint(disc, j, ca);
+      if (rc != 0) return rc;
     }
     // ---- F^T. conditioning of discovery on the propagated latents
     sq_launch_sum_slots(b.d_rnn + (size_t)(T + t) * M * rw, d_pre_d, b.d_pre_disc + (size_t)t * B * rw, B, K, N, rw, s);
@@ -470,23 +496,14 @@ extern "C" int sqair_backward(SqairHandle* h, const float* flat, const void* pac
     // sigmoid's derivative in place below
     float* const d_mask_t = b.d_maskpre + (size_t)t * M * G2;
     const float* mask = w.frame(w.mask, (int64_t)M * G2, t);
+    const SlotAdjPhase prop = {0, L_PROP_RNN, L_PROP_RNN2, L_PROP_T1, L_PROP_T2, rec_p_t, d_rec_p_t, w.prop_rnn_init,
+                               b.d_init_p + (size_t)t * R * nh, flat_grad + po.prop_rnn_init + nh, d_pre, pre_ld, N * pre_ld, w.w3_prop, true};
     for (int k = N - 1; k >= 0; --k) {
       float* d_t1 = slotp(b.d_t1, T1_LD, t, 0, k);
-      float* d_t2 = slotp(b.d_t2, nh, t, 0, k);
-      float* d_tp = slotp(b.d_tp, TP_LD, t, 0, k);
-      float* d_e1 = slotp(b.d_e1, nh, t, 0, k);
-      float* d_e2 = slotp(b.d_e2, nh, t, 0, k);
       float* d_enc3 = slotp(b.d_enc3, ENC_LD, t, 0, k);
-      float* d_rnn = slotp(b.d_rnn, rw, t, 0, k);
-      const int drl = N * rw;
       float* d_gru1 = b.d_gru1 + ((size_t)t * M + k) * gw;   // [T][R][N][3nh (GRU) | 4nh (LSTM)], row stride N*gw
       float* d_hraw = b.d_hraw + ((size_t)t * M + k) * HRAW_LD;
       const int g1l = N * gw;
-      const float* r_k = cslotp(w.r, nh, t, 0, k);
-      const float* t1 = cslotp(w.t1, T1_LD, t, 0, k);
-      const float* t2 = cslotp(w.t2, nh, t, 0, k);
-      const float* e1 = cslotp(w.e1, nh, t, 0, k);
-      const float* e2 = cslotp(w.e2, nh, t, 0, k);
       const float* enc = cslotp(w.enc, ENC_LD, t, 0, k);
       const float* tau_k = temporal_prev + (size_t)k * snh;   // GRU: the state; LSTM: [hidden | cell], features = cell
       float* d_tau_k = d_tau + (size_t)k * snh;
@@ -538,55 +555,10 @@ extern "C" int sqair_backward(SqairHandle* h, const float* flat, const void* pac
         x.to(nh + 16, nh + 16 + 2 * nw, d_enc3, el).add(b.d_enc, ENC_LD).dact(enc, el, ACT_NONE, ACT_SOFTPLUS_MIN, nw);
         CK(rundx(L_PROP_GRU1, x, R));
       }
-      { Dx x(d_enc3, el); x.to(0, nh, d_e2, rl).dact(e2, rl, ACT_ELU); CK(rundx(L_WHAT_HEAD, x, R)); }
-      { Dx x(d_e2, rl); x.to(0, nh, d_e1, rl).dact(e1, rl, ACT_ELU); CK(rundx(L_GENC1, x, R)); }
-      { Dx x(d_e1, rl); x.to(0, G2, b.d_g, G2); CK(rundx(L_GENC0, x, R)); }
-      {
-        CropChainBwdArgs ca; memset(&ca, 0, sizeof(ca));
-        ca.mode = CROP_PROP2; ca.slot = k; ca.img = img; ca.rec_prev = rec_prev; ca.rec_new = rec_p_t; ca.d_rec_prev = d_rec_prev;
-        ca.d_rec_new = d_rec_p_t; ca.mask = c.masked_glimpse ? mask : nullptr; ca.mask_row_mul = N; ca.mask_row_add = k;
-        ca.d_mask = d_mask_t; ca.g_out = b.d_g; ca.g_row_mul = 1; ca.tp = cslotp(w.tp, TP_LD, t, 0, k); ca.tp_ld = tpl;
-        ca.d_tp = d_tp; ca.dtp_ld = tpl; ca.noise = nz; ca.flat = flat; ca.flat_grad = flat_grad;
-        if (fuse_t3) { ca.w3 = w.w3_prop; ca.t2 = t2; ca.t2_ld = rl; ca.d_t2 = d_t2; ca.dt2_ld = rl; }
-        CK(sq_launch_crop_chain_bwd(ca, po, d, 1, s));
-      }
-      if (!fuse_t3) { Dx x(d_tp, tpl); x.to(0, nh, d_t2, rl).dact(t2, rl, ACT_ELU); CK(rundx(L_PROP_T3, x, R)); }
-      { Dx x(d_t2, rl); x.to(0, nh, d_t1, t1l).dact(t1, t1l, ACT_ELU).dup(d_pre_k + rw, pre_rld); CK(rundx(L_PROP_T2, x, R)); }
-      if (c.rnn_cell == RNN_LSTM) {  // d h_k total, then the cell adjoint (second copy: this slot's block of d_pre)
-        Dx x(d_t1, t1l);
-        x.to(0, nh, b.d_hk, nh).add(b.d_r[k & 1], nh);
-        CK(rundx(L_PROP_T1, x, R));
-        sq_launch_lstm_cell_bwd(cslotp(w.rgates, 4 * nh, t, 0, k), N * 4 * nh, k == 0 ? w.prop_rnn_init + nh : cslotp(w.rc, nh, t, 0, k - 1),
-                                k == 0 ? 0 : rl, b.d_hk, nh, k < N - 1 ? b.d_cs[k & 1] : nullptr, nh, d_rnn, drl, b.d_cs[(k + 1) & 1], nh, R, nh, s,
-                                d_pre_k, pre_rld);
-      } else if (c.rnn_cell == RNN_GRU) {
-        Dx x(d_t1, t1l);
-        x.to(0, nh, b.d_hk, nh).add(b.d_r[k & 1], nh);
-        CK(rundx(L_PROP_T1, x, R));
-        const float* g3 = cslotp(w.rgates, 3 * nh, t, 0, k);
-        const float* hp = k == 0 ? w.prop_rnn_init : cslotp(w.r, nh, t, 0, k - 1);
-        const int g3l = N * 3 * nh, hpl = k == 0 ? 0 : rl;
-        float* dhp = k > 0 ? b.d_r[(k - 1) & 1] : b.d_init_p + (size_t)t * R * nh;
-        sq_launch_gru_bwd_a(b.d_hk, nh, g3, g3l, g3 + 2 * nh, g3l, hp, hpl, d_rnn, drl, dhp, nh, R, nh, 0, s, d_pre_k, pre_rld, 2 * nh);
-        { Dx y(d_rnn + 2 * nh, drl); y.to(0, nh, b.d_rh, nh); CK(rundx(L_PROP_RNN2, y, R)); }
-        sq_launch_gru_bwd_b(b.d_rh, nh, g3 + nh, g3l, hp, hpl, d_rnn, drl, dhp, nh, R, nh, s, d_pre_k + nh, pre_rld);
-      } else {  // d r_k total = T1^T + (gate GEMM + next slot's RNN, accumulated in d_r[k & 1]); tanh' -> RNN pre-activation
-        Dx x(d_t1, t1l);
-        x.to(0, nh, d_rnn, rl).add(b.d_r[k & 1], nh).dact(r_k, rl, ACT_TANH).dup(d_pre_k, pre_rld);
-        CK(rundx(L_PROP_T1, x, R));
-      }
-      if (k > 0) {
-        Dx x(d_rnn, drl);
-        x.to(0, rec::ZW, d_rec_p_t + (size_t)(k - 1) * RW, N * RW).acc();
-        x.to(rec::ZWP, rec::ZWP + nh, b.d_r[(k - 1) & 1], nh);
-        if (c.rnn_cell == RNN_GRU) x.acc();
-        CK(rundx(L_PROP_RNN, x, R));
-      } else {
-        Dx x(d_rnn, drl); x.to(rec::ZWP, rec::ZWP + nh, b.d_init_p + (size_t)t * R * nh, nh);
-        if (c.rnn_cell == RNN_GRU) x.acc();
-        CK(rundx(L_PROP_RNN, x, R));
-        if (c.rnn_cell == RNN_LSTM) sq_launch_colsum(b.d_cs[1], nh, R, nh, flat_grad + po.prop_rnn_init + nh, 1, s);
-      }
+      CropChainBwdArgs ca; memset(&ca, 0, sizeof(ca));
+      ca.mode = CROP_PROP2; ca.mask = c.masked_glimpse ? mask : nullptr; ca.mask_row_mul = N; ca.mask_row_add = k; ca.d_mask = d_mask_t;
+      const int rc = slot_adjoint(prop, k, ca);
+      if (rc != 0) return rc;
     }
     // ---- D^T. the loop-invariant pre-activation GEMM: segments [m1 nw (pad 64) | z_{t-1} record 56 (pad 64) | temporal nh]
     float* d_m1 = b.d_m1 + (size_t)t * M * M1_LD;

@@ -38,7 +38,7 @@ int main() {
     LinArgs a = LinArgs();
     a.seg[0] = LinSeg{(i & 1) ? y : x, K, K, 1}; a.nseg = 1; a.wp = w + 256; a.wzero = w; a.bias = b; a.out = (i & 1) ? x : y; a.out_ld = N;
     a.M = M; a.N = N; a.epi = EPI_ACT; a.act_a = ACT_ELU; a.act_split = 1 << 30; a.scale = 1.0f; a.add_rdiv = 1;
-    hipLaunchKernelGGL((k_fwd<4, 1, false, false>), dim3(nt, M / 16), dim3(256), 0, s, a.seg[0].p, a.wp, a.seg[0].ld, a.seg[0].width, a.seg[0].rmul, a.M, kc, nt, a.wzero, a, (unsigned long long*)nullptr); }));
+    hipLaunchKernelGGL((k_fwd<4, 1, false>), dim3(nt, M / 16), dim3(256), 0, s, a.seg[0].p, a.wp, a.seg[0].ld, a.seg[0].width, a.seg[0].rmul, a.M, kc, nt, a.wzero, a); }));
   for (int variant = 0; variant < 3; ++variant) {
     const char* nm[] = {"k_linear_dx<4>: 1 range, elu' from saved", "k_linear_dx<4>: 1 range, accumulate + saved", "k_linear_dx<4>: 3 ranges"};
     printf("%-44s %.2f us/node\n", nm[variant], time_graph(s, NODES, REPS, [&](int i) {

@@ -96,7 +96,7 @@ int main(int argc, char** argv) {
 #define RUN(name, kern, NCHV, m, ntu)                                                                             \
   printf("%-34s %.2f us/node\n", name, time_graph(s, NODES, REPS, [&](int) {                                       \
     LinArgs a = mk(m, ntu);                                                                                        \
-    hipLaunchKernelGGL((kern<NCHV, 1, false, false>), dim3((ntu), ((m) + 15) / 16), dim3(256), 0, s, a.seg[0].p, a.wp, a.seg[0].ld, a.seg[0].width, a.seg[0].rmul, a.M, kc, ntu, a.wzero, a, (unsigned long long*)nullptr); }));
+    hipLaunchKernelGGL((kern<NCHV, 1, false>), dim3((ntu), ((m) + 15) / 16), dim3(256), 0, s, a.seg[0].p, a.wp, a.seg[0].ld, a.seg[0].width, a.seg[0].rmul, a.M, kc, ntu, a.wzero, a); }));
 #define ALL(NCHV)                                                   \
   RUN("full", k_full, NCHV, M, nt)                                  \
   RUN("no MFMA (VALU fma instead)", k_nomfma, NCHV, M, nt)          \
