@@ -180,6 +180,28 @@ int sqair_graph_capture(SqairHandle* h, const float* flat_params, const void* pa
 int sqair_graph_launch(SqairHandle* h, void* stream);
 int sqair_graph_nodes(const SqairHandle* h); /* kernel nodes in the captured graph */
 
+/* ---- carried model state (streaming inference) ----------------------------------------------------
+ * A pass normally starts every particle row from the trainable initial state.  With a state set, the following sqair_forward /
+ * sqair_graph_capture calls (and sqair_forward calls between sqair_capture_begin / _end) of this handle instead start each row
+ * from a state blob and write the state after their last frame into another (or the same) blob, so that a sequence can be fed
+ * in chunks of any length -- down to one frame per call -- with the same results as one pass over the whole sequence.
+ * A blob row holds everything frame t + 1 reads of frame t: the N slot records (what / where / presence / logit / id ...), the
+ * temporal and propagation-prior cell states, the last used object id, and the row's frame counter (the index the
+ * time-dependent step prior sees; it replaces t_offset).  The blob is OPAQUE: device memory of sqair_state_bytes(h, B) bytes,
+ * only meaningful to a handle of the same build (product / wide), configuration and B.
+ *   state_in   NULL: every row starts fresh at t_offset (the state after the pass is still exported);
+ *   state_out  NULL: nothing is exported; may equal state_in (import happens in the prologue, export at the end of the pass,
+ *              in stream order: one captured graph can then be replayed frame after frame);
+ *   src_rows   optional device int32[B*K]: row r is imported from blob row src_rows[r]; -1 (or any index outside [-1, B*K))
+ *              starts row r fresh (counter 0).  Resets lanes, resamples particles (src[b*K + k] = b*K + k'), recomposes a
+ *              batch.  NULL = identity.  Needs state_in.
+ * All three NULL switches the state off.  Pointers are remembered by the handle and frozen into captured graphs.  Refused
+ * (return -1, text in sqair_last_error, before any HIP call): sqair_forward_train / sqair_backward while a state is set, a
+ * configuration with sample_from_prior, t_offset != 0 with state_in set, a pass whose B is not the B given here, and
+ * state_bytes < sqair_state_bytes(h, B). */
+int64_t sqair_state_bytes(const SqairHandle* h, int B);
+int sqair_set_state(SqairHandle* h, const void* state_in, void* state_out, const int32_t* src_rows, int64_t state_bytes, int B);
+
 /* ---- objective ---------------------------------------------------------------------------------
  * Fused IWAE / VIMCO reductions over [T,B,K] (reference: Model._build sqair/model.py:88-103,
  * targets.iwae / vimco_control_variate / vimco sqair/targets.py:38-75, make_target model.py:150-158,

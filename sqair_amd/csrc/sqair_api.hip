@@ -822,12 +822,68 @@ Workspace sq_carve(const SqairHandle* h, int T, int B, float* base, bool train) 
     const int64_t P_ = (int64_t)c.img_h * c.img_w, P4 = (P_ + 3) / 4 * 4;
     w.obs_p = take(P4 != P_ ? (int64_t)T * B * P4 + 16 : 64);   // (+16: the last K chunk of the input encoder may read past the row)
   }
+  w.t_row = (int*)take(R);
   w.clear_n = o;   // a workspace clear covers every buffer above; the chain's control blocks below are sq_chain_poison's
   w.chain_ctl = (unsigned*)take(w.chain ? (int64_t)SQ_CHAIN_MAX_LAUNCHES * SQ_CHAIN_CTL_WORDS : 64);
   w.total = o;
   return w;
 }
 static Workspace carve(const SqairHandle* h, int T, int B, float* base) { return sq_carve(h, T, B, base, false); }
+
+// carried model state: one blob row per particle row (StateArgs, sqair_glue.h), 4-word aligned
+int64_t sq_state_row_floats(const SqairHandle* h) {
+  const SqairConfig& c = h->cfg;
+  const int64_t N = c.n_steps_per_image, nh = c.n_hidden;
+  const int64_t snh = c.time_cell == CELL_LSTM ? 2 * nh : nh, psnh = c.prior_cell == CELL_LSTM ? 2 * nh : nh;
+  return (N * (rec::W + snh + psnh) + 2 + 3) / 4 * 4;
+}
+extern "C" int64_t sqair_state_bytes(const SqairHandle* h, int B) {
+  if (!h || B < 1) return -1;
+  return (int64_t)B * h->cfg.k_particles * sq_state_row_floats(h) * 4;
+}
+extern "C" int sqair_set_state(SqairHandle* h, const void* state_in, void* state_out, const int32_t* src_rows, int64_t state_bytes, int B) {
+  if (!h) return -1;
+  if (!state_in && !state_out && !src_rows) {
+    h->state_on = false; h->state_in = nullptr; h->state_out = nullptr; h->state_src = nullptr; h->state_B = 0;
+    return 0;
+  }
+  if (h->cfg.sample_from_prior) {
+    sq_set_error(h, "sqair_set_state: not with sample_from_prior (generation decides per frame on the host)");
+    return -1;
+  }
+  if (src_rows && !state_in) {
+    sq_set_error(h, "sqair_set_state: a source map needs state_in");
+    return -1;
+  }
+  if (B < 1 || state_bytes < sqair_state_bytes(h, B)) {
+    sq_set_error(h, "sqair_set_state: state_bytes " + std::to_string(state_bytes) + " < sqair_state_bytes(h, " + std::to_string(B) +
+                        ") = " + std::to_string(B < 1 ? -1 : sqair_state_bytes(h, B)));
+    return -1;
+  }
+  h->state_on = true; h->state_in = state_in; h->state_out = state_out; h->state_src = src_rows; h->state_B = B;
+  return 0;
+}
+// the refusals of a pass with a carried state (host only: before any HIP call)
+int sq_state_refusal(SqairHandle* h, bool train, int B, int t_offset) {
+  if (!h->state_on) return 0;
+  if (train) {
+    sq_set_error(h, "a carried state (sqair_set_state) is for inference passes: training / backward with one is not supported");
+    return -1;
+  }
+  if (h->cfg.sample_from_prior) {
+    sq_set_error(h, "a carried state (sqair_set_state) does not combine with sample_from_prior");
+    return -1;
+  }
+  if (h->state_in && t_offset != 0) {
+    sq_set_error(h, "with state_in set (sqair_set_state) t_offset must be 0: the state's frame counter is the time index");
+    return -1;
+  }
+  if (B != h->state_B) {
+    sq_set_error(h, "B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
+    return -1;
+  }
+  return 0;
+}
 
 extern "C" int64_t sqair_workspace_bytes(const SqairHandle* h, int T, int B) {
   if (!h || T < 1 || B < 1) return -1;
@@ -970,12 +1026,29 @@ struct SlotPhase {
   bool fuse;                          // the slot's tail rides in the next slot's VanillaRNN launch (k_rnn_tail)
 };
 
+// the carried state's rows of frame t of a pass (k_state_import: t = 0, k_state_export: t = T)
+static StateArgs state_args(const SqairHandle* h, const Workspace& w, int t, int t0) {
+  StateArgs a; memset(&a, 0, sizeof(a));
+  a.rec = w.rec_m_all + (size_t)t * w.M * rec::W;
+  a.temporal = w.state(w.temporal_m, t, w.snh);
+  a.prior = w.state(w.prior_m, t, w.psnh);
+  a.last_id = w.last_id[t & 1];
+  a.t_row = w.t_row;
+  a.blob_in = (const float*)h->state_in;
+  a.blob_out = (float*)h->state_out;
+  a.src = h->state_src;
+  a.R = w.R; a.n_rec = w.N * rec::W; a.n_tmp = w.N * w.snh; a.n_pri = w.N * w.psnh; a.row_words = (int)sq_state_row_floats(h);
+  a.t0 = t0;
+  return a;
+}
+
 // parts: 1 = prologue (workspace clear, initial state, input encoder), 2 = the frame loop, 4 = epilogue (log-probabilities,
 // decoder, final state copies).
 int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, const float* obs, const float* noise,
                     int T, int B, int t_offset, const SqairOutputs* outp, float* wsbase, int64_t ws_bytes,
                     hipStream_t s, bool train, int parts) {
   const SqairConfig& c = h->cfg;
+  if (sq_state_refusal(h, train, B, t_offset) != 0) return -1;
   if (!flat || !packed || !obs || !noise || !outp || !wsbase || T < 1 || B < 1) {
     sq_set_error(h, "sqair_forward: null argument or bad T/B");
     return -1;
@@ -1020,6 +1093,8 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
     sq_launch_init_state(w.rec_m_all, w.state(w.temporal_m, 0, w.snh), w.state(w.prior_m, 0, w.psnh), w.last_id[0], w.disc_init_rec,
                          w.prop_rnn_init, w.disc_rnn_init, w.rn_init_state, w.w3_prop, w.w3_disc,
                          (int)P(h, "prop.transform.l2.w"), (int)P(h, "disc.transform.l2.w"), flat, po, d, s);
+    // carried state (sqair_set_state): frame 0's records / states / last_id of each row from the caller's blob, and its counter
+    if (h->state_on) sq_launch_state_import(state_args(h, w, 0, t_offset), s);
     if (w.chain) {
       // hand-off words of the chain launches of this pass -> sentinel; their control blocks -> zero (one launch)
       ChainPoisonList pl; memset(&pl, 0, sizeof(pl));
@@ -1319,6 +1394,7 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
     la.rec_p = w.rec_p_all; la.rec_d = w.rec_d_all; la.rec_prev = w.rec_m_all; la.pstats = w.pstats; la.ps_ld = PS_LD;
     la.spre = w.spre; la.flat = flat; la.t_global = t_offset; la.t = 0; la.n_frames = T; la.qz = w.qz; la.pz = w.pz;
     la.disc_lp = w.dlp; la.out = out; la.cfg = c; la.gen = c.sample_from_prior ? w.gen : nullptr;
+    la.t_row = h->state_on ? w.t_row : nullptr;   // (carried state: each row's own frame index)
     if (sq_launch_logprob(la, po, d, s) != 0) { sq_set_error(h, "sqair_forward: the log-probability launch failed (dynamic LDS limit)"); return -2; }
   }
   // ---- J. decoder of all T frames as three M = T*B'*N row GEMMs + one insert / log-likelihood launch
@@ -1349,6 +1425,8 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
   }
   if (out.final_last_used_id)
     sq_copy(out.final_last_used_id, w.last_id[T & 1], (int64_t)R, s);
+  // carried state: frame T's rows into the caller's blob (after every reader of the imported rows: in place is fine)
+  if (h->state_on && h->state_out) sq_launch_state_export(state_args(h, w, T, T), s);
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -1374,6 +1452,7 @@ extern "C" int sqair_forward_train(SqairHandle* h, const float* flat_params, con
                                    const float* noise, int T, int B, int t_offset, const SqairOutputs* out,
                                    void* workspace, int64_t workspace_bytes, void* stream) {
   if (!h) return -1;
+  if (sq_state_refusal(h, true, B, t_offset) != 0) return -1;
   if (!sq_trainable_frame(h)) return -1;
   return sq_forward_impl(h, flat_params, (const float*)packed, obs, noise, T, B, t_offset, out, (float*)workspace,
                          workspace_bytes, (hipStream_t)stream, true, 7);
@@ -1606,11 +1685,15 @@ extern "C" int sqair_graph_capture(SqairHandle* h, const float* flat_params, con
                                    const float* noise, int T, int B, int t_offset, const SqairOutputs* out,
                                    void* workspace, int64_t workspace_bytes, void* stream) {
   if (!h) return -1;
+  if (sq_state_refusal(h, false, B, t_offset) != 0) return -1;
   hipStream_t s = (hipStream_t)stream;
   if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
   if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
   if (h->opt_slot_chain) {  // one eager pass: the chain launches' op tables are uploaded outside the capture (sqair_chain.hip)
+    void* const state_out = h->state_out;   // (a carried state is imported but not exported: the capture leaves it as it was)
+    h->state_out = nullptr;
     const int rc0 = forward_impl(h, flat_params, (const float*)packed, obs, noise, T, B, t_offset, out, (float*)workspace, workspace_bytes, s);
+    h->state_out = state_out;
     if (rc0 != 0) return rc0;
     SQ_CHECK_HIP(hipStreamSynchronize(s));
   }

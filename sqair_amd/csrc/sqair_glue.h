@@ -166,6 +166,7 @@ struct LogprobArgs {
   const float* spre;                  // [R,128] pre-activation of the where-prior conditioning state (without e)
   const float* flat;
   int t_global;                       // absolute frame index (categorical prior is time dependent)
+  const int* t_row;                   // carried state: absolute index of frame 0 per row [R] (replaces t_global), or NULL
   int t;                              // index of the first frame inside the output tensors
   int n_frames;                       // frames covered by the launch (inputs are [n_frames][...] contiguous)
   float* qz; float* pz; float* disc_lp;  // frame scalars [R]
@@ -174,6 +175,24 @@ struct LogprobArgs {
   SqairConfig cfg;
 };
 int sq_launch_logprob(const LogprobArgs& a, POff po, Dims d, hipStream_t s);
+
+// Carried model state (sqair_set_state).  One blob row per particle row r, 32-bit words:
+//   [N * rec::W slot records | N * snh temporal state | N * psnh prior state | last_id | frame counter (int32) | zero padding]
+// in the kernels' own (padded) widths, copied verbatim: opaque, and only meaningful to the build and configuration that wrote it.
+struct StateArgs {
+  float* rec;                  // frame-0 (import) / frame-T (export) slot records [R][N][rec::W]
+  float* temporal;             // [R][N][snh]
+  float* prior;                // [R][N][psnh]
+  float* last_id;              // [R]
+  int* t_row;                  // [R] frame counter of each row at frame 0 of the pass
+  const float* blob_in;        // import: NULL = every row fresh
+  float* blob_out;             // export
+  const int* src;              // import: source row of each row, -1 (or out of [-1, R)) = fresh; NULL = identity
+  int R, n_rec, n_tmp, n_pri, row_words;
+  int t0;                      // import: counter of a fresh row; export: frames of the pass (added to the counter)
+};
+int sq_launch_state_import(const StateArgs& a, hipStream_t s);
+int sq_launch_state_export(const StateArgs& a, hipStream_t s);
 
 // Generation modes (sqair_modules.py:157-170, :294-302).  Generation record of slot (r, k), 64 floats:
 //   [0:4] where ~ prior, [4:54] what ~ prior, [54] presence ~ Bernoulli(prior logit), [55] the posterior path's own

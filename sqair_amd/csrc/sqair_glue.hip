@@ -77,6 +77,74 @@ int sq_launch_init_state(float* rec_m, float* temporal_m, float* prior_m, float*
 }
 
 // ------------------------------------------------------------------------------------------------
+// carried model state (sqair_set_state; StateArgs in sqair_glue.h)
+// ------------------------------------------------------------------------------------------------
+// k_state_import runs right after k_init_state and overwrites, per particle row, exactly what k_init_state wrote for it: frame 0's
+// slot records (rec_m_all[0]), temporal state (temporal_m frame 0), prior state (prior_m frame 0) and last_id[0].  Everything
+// frame t + 1 reads of frame t lives in these four buffers; their readers in a pass (sq_forward_impl, sections A..J):
+//   rec_prev       A prior cell ([what, where] of every slot); C crop #1 (where, presence); D loop-invariant pre-activations;
+//                  E propagation crop #2, k_linear_what (mode 1) and the slot tail (where / what / presence / logit / id);
+//                  I k_compact (presence, id); H k_logprob (rec_m_all[t]: presence, logit, what, where of frame t - 1);
+//                  generation (refused with a carried state); the slot chain through its op tables (same addresses)
+//   temporal_prev  B where-bias / mask MLP (tau); D pre-activations (tau) and the LSTM recurrent rows; E the temporal cell of
+//                  every propagation slot (GRU state / LSTM [h | c])
+//   prior_prev     A the propagation-prior cell (GRU state / LSTM [h | c])
+//   last_id        I k_compact (ids of newly discovered objects)
+// The decoder (J) reads frames 1..T only; the per-pass constants k_init_state also writes (disc_init_rec, slot-RNN initial
+// states, w3 copies) are parameters, not state.  The row's frame counter goes to t_row (k_logprob: t_global = t_row[r] + frame).
+__global__ __launch_bounds__(256) void k_state_import(const StateArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  const int r = blockIdx.x, tid = threadIdx.x;
+  int sr = a.blob_in == nullptr ? -1 : (a.src != nullptr ? a.src[r] : r);
+  if (sr < -1 || sr >= a.R) sr = -1;   // (never read outside the blob: an index out of range starts the row fresh)
+  if (sr < 0) {                        // fresh: keep what k_init_state wrote
+    if (tid == 0) a.t_row[r] = a.t0;
+    return;
+  }
+  // 32-bit words copied as they are (bit-identical by construction, whatever the values)
+  const unsigned* b = reinterpret_cast<const unsigned*>(a.blob_in) + (size_t)sr * a.row_words;
+  unsigned* rec = reinterpret_cast<unsigned*>(a.rec) + (size_t)r * a.n_rec;
+  unsigned* tmp = reinterpret_cast<unsigned*>(a.temporal) + (size_t)r * a.n_tmp;
+  unsigned* pri = reinterpret_cast<unsigned*>(a.prior) + (size_t)r * a.n_pri;
+  for (int i = tid; i < a.n_rec; i += 256) rec[i] = b[i];
+  b += a.n_rec;
+  for (int i = tid; i < a.n_tmp; i += 256) tmp[i] = b[i];
+  b += a.n_tmp;
+  for (int i = tid; i < a.n_pri; i += 256) pri[i] = b[i];
+  b += a.n_pri;
+  if (tid == 0) {
+    reinterpret_cast<unsigned*>(a.last_id)[r] = b[0];
+    a.t_row[r] = (int)b[1];
+  }
+}
+// k_state_export: frame T's records and states, last_id[T & 1] and the counter advanced by the pass's T frames.  Runs at the end
+// of the epilogue, after every reader of the imported rows: the blob may be the one the pass imported from.
+__global__ __launch_bounds__(256) void k_state_export(const StateArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  const int r = blockIdx.x, tid = threadIdx.x;
+  unsigned* b = reinterpret_cast<unsigned*>(a.blob_out) + (size_t)r * a.row_words;
+  const unsigned* rec = reinterpret_cast<const unsigned*>(a.rec) + (size_t)r * a.n_rec;
+  const unsigned* tmp = reinterpret_cast<const unsigned*>(a.temporal) + (size_t)r * a.n_tmp;
+  const unsigned* pri = reinterpret_cast<const unsigned*>(a.prior) + (size_t)r * a.n_pri;
+  for (int i = tid; i < a.n_rec; i += 256) b[i] = rec[i];
+  b += a.n_rec;
+  for (int i = tid; i < a.n_tmp; i += 256) b[i] = tmp[i];
+  b += a.n_tmp;
+  for (int i = tid; i < a.n_pri; i += 256) b[i] = pri[i];
+  b += a.n_pri;
+  const int tail = a.row_words - a.n_rec - a.n_tmp - a.n_pri;   // last_id, counter, padding
+  if (tid < tail) b[tid] = tid == 0 ? reinterpret_cast<const unsigned*>(a.last_id)[r] : tid == 1 ? (unsigned)(a.t_row[r] + a.t0) : 0u;
+}
+int sq_launch_state_import(const StateArgs& a, hipStream_t s) {
+  SQ_LAUNCH(k_state_import, dim3(a.R), dim3(256), 0, s, a);
+  return 0;
+}
+int sq_launch_state_export(const StateArgs& a, hipStream_t s) {
+  SQ_LAUNCH(k_state_export, dim3(a.R), dim3(256), 0, s, a);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Spatial-transformer crop (reference: sqair/modules.py:170-227; Sonnet AffineGridWarper +
 // tf.contrib.resampler).  One workgroup per sequence b stages the frame in LDS
 // once and cuts the glimpses of all K particles of that sequence from it.  The `where` sample of
@@ -712,7 +780,7 @@ __global__ __launch_bounds__(64 * SQ_LOGPROB_WAVES) void k_logprob(const Logprob
   __syncthreads();
   const int lane = tid & 63, wave = tid >> 6;
   const size_t tr = (size_t)(a.t + fr) * d.R + r;
-  const int t_global = a.t_global + fr;
+  const int t_global = (a.t_row != nullptr ? a.t_row[r] : a.t_global) + fr;
   const float LOG2PI = 1.83787706640934548356f;
 
   for (int k = wave; k < N; k += NWV) {

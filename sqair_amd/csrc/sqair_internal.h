@@ -73,6 +73,12 @@ struct SqairHandle {
   void* chain = nullptr;        // ChainState (sqair_chain.hip)
   bool clear_each_pass = true;  // zero the caller's workspace at the start of every pass (sqair_set_workspace_clearing)
   const float* gen_noise = nullptr;  // sqair_set_generation_noise
+  // carried model state (sqair_set_state): the following inference passes import it in the prologue / export it in the epilogue
+  bool state_on = false;
+  const void* state_in = nullptr;    // [R] rows of sq_state_row_floats(), or NULL = every row starts fresh
+  void* state_out = nullptr;         // may equal state_in
+  const int32_t* state_src = nullptr;  // [R] source row of each imported row (-1 = fresh), or NULL = identity
+  int state_B = 0;
   // generic capture slots (sqair_capture_begin / _end / _launch): any sequence of C-ABI calls as one HIP graph
   hipGraph_t cap_graph[4] = {nullptr, nullptr, nullptr, nullptr};
   hipGraphExec_t cap_exec[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -81,6 +87,7 @@ struct SqairHandle {
 
 inline int64_t align64(int64_t x) { return (x + 63) / 64 * 64; }
 constexpr int64_t SQ_TRAIN_MAX_FRAME_BYTES = 150 * 1024;   // dynamic LDS the crop adjoint may ask for (sq_allow_big_lds)
+int sq_state_refusal(SqairHandle* h, bool train, int B, int t_offset);   // -1 + error text: a pass a carried state rules out
 bool sq_trainable_frame(SqairHandle* h);                   // false + error text when the handle's frames cannot be trained
 // The partial adjoint kept for unit tests (sqair_backward_decoder) takes the caller's frames as they are, and the full adjoint
 // kernels stage frames in 16-byte units: it wants H * W to be a multiple of 4 (the full passes stage other frames through a
@@ -178,6 +185,7 @@ struct Workspace {
   float *qz, *pz, *dlp, *dll, *glimpse, *dec_a, *dec_b;
   float* gen;                                    // sample_from_prior: [T][M][64] prior samples + original presences
   float* obs_p;                                  // frames whose H * W is not a multiple of 4: zero-padded copy [T*B][P4] (else unused)
+  int* t_row;                                    // carried state: frame counter of each row at frame 0 of the pass [R]
   int64_t clear_n;  // floats from the base that a workspace clear covers: every buffer carved before chain_ctl
   int64_t total;    // floats
 
@@ -194,6 +202,8 @@ struct Workspace {
   }
 };
 Workspace sq_carve(const SqairHandle* h, int T, int B, float* base, bool train);
+// carried model state (sqair_set_state): floats of one particle row of the state blob
+int64_t sq_state_row_floats(const SqairHandle* h);
 
 // zero fill as a kernel (not a memset node: see sqair_train.hip); p 16-byte aligned
 void sq_zero_fill(float* p, int64_t n, hipStream_t s);

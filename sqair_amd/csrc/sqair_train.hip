@@ -225,6 +225,7 @@ extern "C" int sqair_backward(SqairHandle* h, const float* flat, const void* pac
                               const float* importance_weights, const float* vimco_signal, int T, int B, int t_offset,
                               void* train_workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes,
                               float* flat_grad, void* stream) {
+  if (h && sq_state_refusal(h, true, B, t_offset) != 0) return -1;
   if (!h || !flat || !packedv || !obs || !noise || !importance_weights || !vimco_signal || !train_workspace || !scratch || !flat_grad)
     return -1;
   if (workspace_bytes < sqair_train_workspace_bytes(h, T, B) || scratch_bytes < sqair_backward_bytes(h, T, B)) {
