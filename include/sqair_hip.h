@@ -202,6 +202,40 @@ int sqair_graph_nodes(const SqairHandle* h); /* kernel nodes in the captured gra
 int64_t sqair_state_bytes(const SqairHandle* h, int B);
 int sqair_set_state(SqairHandle* h, const void* state_in, void* state_out, const int32_t* src_rows, int64_t state_bytes, int B);
 
+/* ---- SMC resampling of a carried state (adaptive particle filter) --------------------------------------------------
+ * A pass's per-frame log weight (log_weights_per_timestep) is the incremental importance weight of a particle filter whose
+ * proposal is the inference network.  With SMC set, every following pass with a carried state ends with one more kernel (after
+ * the state export) that, per lane b (sequence), turns the lane's weights into the source map of the NEXT pass, on the device:
+ *   a_k = log_w[b*K + k] + sum over this pass's frames of log_weights_per_timestep   (frame order, fp32)
+ *   m = max_k a_k, e_k = exp(a_k - m), S = sum e_k, ESS = S^2 / sum e_k^2        (fixed order: same bits on every replay)
+ *   log_evidence[b] = log_z[b] + m + log(S / K)    (SMC estimate of log p(x_1..t)),  ess[b] = ESS   (both before resampling)
+ *   resample iff ess_frac == 1 or ESS < ess_frac * K:
+ *     systematic, one u per lane (uniforms[b], or Philox keyed by (seed, b, frame counter of row b*K after the pass)):
+ *     src_rows[b*K + j] = b*K + (smallest k with c_k > (j + u) * S / K, at most K - 1), c = inclusive prefix sum of e;
+ *     log_z[b] += m + log(S / K), log_w of the lane = 0, resampled[b] = 1
+ *   otherwise: src_rows of the lane = identity, log_w[b*K + k] = a_k, resampled[b] = 0.
+ * The next pass's state import gathers the rows through src_rows (records, cell states, ids, counters): the path a caller's
+ * own source map takes.  Resampling happens at pass boundaries only: one-frame passes give per-frame SMC.
+ * u_out[b] receives the lane's uniform of the pass whether or not the lane resampled.
+ * Pointers are remembered by the handle and frozen into captured graphs, as the state's are.  A sqair_set_state call that
+ * switches the state off (all NULL), drops state_in, or changes the source map or B switches SMC off too.  NULL smc: off.  Refused (return -1, text in sqair_last_error, before
+ * any HIP call): no state set, a state without state_in or without a source map, src_rows other than the state's source map,
+ * ess_frac NaN or outside [0, 1], a NULL log_w / log_z / log_evidence / ess / resampled, a B other than the state's; and at
+ * pass time, a pass with SMC on whose out->log_weights_per_timestep is NULL. */
+typedef struct {
+  float ess_frac;            /* resample iff ess_frac == 1 or ESS < ess_frac * K; 0 = never */
+  uint64_t seed;             /* Philox key when uniforms == NULL */
+  const float* uniforms;     /* [B] or NULL */
+  float* log_w;              /* [B*K] in/out: log weights accumulated since the lane's last resampling */
+  float* log_z;              /* [B]   in/out: log evidence banked at resamplings */
+  float* log_evidence;       /* [B] out */
+  float* ess;                /* [B] out, before resampling */
+  float* u_out;              /* [B] out or NULL */
+  int32_t* resampled;        /* [B] out */
+  int32_t* src_rows;         /* must be the source map given to sqair_set_state; written for the next pass */
+} SqairSmc;
+int sqair_set_smc(SqairHandle* h, const SqairSmc* smc, int B);   /* NULL smc: off */
+
 /* ---- objective ---------------------------------------------------------------------------------
  * Fused IWAE / VIMCO reductions over [T,B,K] (reference: Model._build sqair/model.py:88-103,
  * targets.iwae / vimco_control_variate / vimco sqair/targets.py:38-75, make_target model.py:150-158,

@@ -41,6 +41,15 @@ class SqairOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in OUTPUT_FIELDS]
 
 
+class SqairSmc(C.Structure):
+    """SMC resampling of a carried state (include/sqair_hip.h: sqair_set_smc); every pointer is a device address."""
+    _fields_ = [
+        ("ess_frac", C.c_float), ("seed", C.c_uint64), ("uniforms", C.c_void_p), ("log_w", C.c_void_p), ("log_z", C.c_void_p),
+        ("log_evidence", C.c_void_p), ("ess", C.c_void_p), ("u_out", C.c_void_p), ("resampled", C.c_void_p),
+        ("src_rows", C.c_void_p),
+    ]
+
+
 _PROTOS = {
     "sqair_abi_version": (C.c_int, []),
     "sqair_build_id": (C.c_char_p, []),
@@ -103,6 +112,7 @@ _PROTOS = {
     "sqair_set_generation_noise": (C.c_int, [C.c_void_p, C.c_void_p]),
     "sqair_state_bytes": (C.c_int64, [C.c_void_p, C.c_int]),
     "sqair_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),
+    "sqair_set_smc": (C.c_int, [C.c_void_p, C.POINTER(SqairSmc), C.c_int]),
     "sqair_fill_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]),
     "sqair_capture_begin": (C.c_int, [C.c_void_p, C.c_void_p]),
     "sqair_capture_end": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),

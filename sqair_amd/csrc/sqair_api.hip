@@ -845,6 +845,7 @@ extern "C" int sqair_set_state(SqairHandle* h, const void* state_in, void* state
   if (!h) return -1;
   if (!state_in && !state_out && !src_rows) {
     h->state_on = false; h->state_in = nullptr; h->state_out = nullptr; h->state_src = nullptr; h->state_B = 0;
+    h->smc_on = false; h->smc = SqairSmc{};   // (SMC resamples the carried state: off with it)
     return 0;
   }
   if (h->cfg.sample_from_prior) {
@@ -860,8 +861,47 @@ extern "C" int sqair_set_state(SqairHandle* h, const void* state_in, void* state
                         ") = " + std::to_string(B < 1 ? -1 : sqair_state_bytes(h, B)));
     return -1;
   }
+  if (h->smc_on && (!state_in || src_rows != h->state_src || B != h->state_B)) {   // (what SMC was registered against is gone)
+    h->smc_on = false; h->smc = SqairSmc{};
+  }
   h->state_on = true; h->state_in = state_in; h->state_out = state_out; h->state_src = src_rows; h->state_B = B;
   return 0;
+}
+extern "C" int sqair_set_smc(SqairHandle* h, const SqairSmc* smc, int B) {
+  if (!h) return -1;
+  if (!smc) {
+    h->smc_on = false; h->smc = SqairSmc{};
+    return 0;
+  }
+  if (!h->state_on || !h->state_in || !h->state_src) {
+    sq_set_error(h, "sqair_set_smc: needs a carried state with state_in and a source map (sqair_set_state) to resample");
+    return -1;
+  }
+  if (smc->src_rows != h->state_src) {
+    sq_set_error(h, "sqair_set_smc: src_rows must be the source map given to sqair_set_state");
+    return -1;
+  }
+  if (!(smc->ess_frac >= 0.0f && smc->ess_frac <= 1.0f)) {   // (NaN fails both)
+    sq_set_error(h, "sqair_set_smc: ess_frac must lie in [0, 1]");
+    return -1;
+  }
+  if (!smc->log_w || !smc->log_z || !smc->log_evidence || !smc->ess || !smc->resampled) {
+    sq_set_error(h, "sqair_set_smc: log_w, log_z, log_evidence, ess and resampled must not be NULL");
+    return -1;
+  }
+  if (B != h->state_B) {
+    sq_set_error(h, "sqair_set_smc: B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " +
+                        std::to_string(h->state_B));
+    return -1;
+  }
+  h->smc_on = true; h->smc = *smc;
+  return 0;
+}
+// the refusal of a pass with SMC on (host only: before any HIP call)
+static int sq_smc_refusal(SqairHandle* h, const SqairOutputs* outp) {
+  if (!h->smc_on || (outp && outp->log_weights_per_timestep)) return 0;
+  sq_set_error(h, "SMC (sqair_set_smc) resamples on log_weights_per_timestep: a pass with SMC on must bind that output");
+  return -1;
 }
 // the refusals of a pass with a carried state (host only: before any HIP call)
 int sq_state_refusal(SqairHandle* h, bool train, int B, int t_offset) {
@@ -1048,7 +1088,7 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
                     int T, int B, int t_offset, const SqairOutputs* outp, float* wsbase, int64_t ws_bytes,
                     hipStream_t s, bool train, int parts) {
   const SqairConfig& c = h->cfg;
-  if (sq_state_refusal(h, train, B, t_offset) != 0) return -1;
+  if (sq_state_refusal(h, train, B, t_offset) != 0 || sq_smc_refusal(h, outp) != 0) return -1;
   if (!flat || !packed || !obs || !noise || !outp || !wsbase || T < 1 || B < 1) {
     sq_set_error(h, "sqair_forward: null argument or bad T/B");
     return -1;
@@ -1427,6 +1467,15 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
     sq_copy(out.final_last_used_id, w.last_id[T & 1], (int64_t)R, s);
   // carried state: frame T's rows into the caller's blob (after every reader of the imported rows: in place is fine)
   if (h->state_on && h->state_out) sq_launch_state_export(state_args(h, w, T, T), s);
+  // SMC: this pass's log weights -> ESS, evidence and the next pass's source map (sqair_set_smc)
+  if (h->smc_on) {
+    SmcArgs a; memset(&a, 0, sizeof(a));
+    a.lw = out.log_weights_per_timestep; a.t_row = w.t_row; a.uniforms = h->smc.uniforms;
+    a.log_w = h->smc.log_w; a.log_z = h->smc.log_z; a.log_evidence = h->smc.log_evidence; a.ess = h->smc.ess;
+    a.u_out = h->smc.u_out; a.resampled = h->smc.resampled; a.src = h->smc.src_rows;
+    a.seed = h->smc.seed; a.ess_frac = h->smc.ess_frac; a.T = T; a.B = B; a.K = K;
+    sq_launch_smc_resample(a, s);
+  }
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -1685,15 +1734,18 @@ extern "C" int sqair_graph_capture(SqairHandle* h, const float* flat_params, con
                                    const float* noise, int T, int B, int t_offset, const SqairOutputs* out,
                                    void* workspace, int64_t workspace_bytes, void* stream) {
   if (!h) return -1;
-  if (sq_state_refusal(h, false, B, t_offset) != 0) return -1;
+  if (sq_state_refusal(h, false, B, t_offset) != 0 || sq_smc_refusal(h, out) != 0) return -1;
   hipStream_t s = (hipStream_t)stream;
   if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
   if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
   if (h->opt_slot_chain) {  // one eager pass: the chain launches' op tables are uploaded outside the capture (sqair_chain.hip)
-    void* const state_out = h->state_out;   // (a carried state is imported but not exported: the capture leaves it as it was)
+    void* const state_out = h->state_out;   // (a carried state is imported but not exported, nor resampled: the capture leaves
+    const bool smc_on = h->smc_on;           //  the state, its source map and the SMC weights as they were)
     h->state_out = nullptr;
+    h->smc_on = false;
     const int rc0 = forward_impl(h, flat_params, (const float*)packed, obs, noise, T, B, t_offset, out, (float*)workspace, workspace_bytes, s);
     h->state_out = state_out;
+    h->smc_on = smc_on;
     if (rc0 != 0) return rc0;
     SQ_CHECK_HIP(hipStreamSynchronize(s));
   }

@@ -116,6 +116,20 @@ void sq_set_error(SqairHandle* h, const std::string& msg);
 // handle each) has to set it on each of them.  Returns 0 or -2; the HIP error is not swallowed.
 int sq_allow_big_lds(const void* kernel, int bytes);
 
+// Philox4x32-10 (Salmon et al., SC'11): counter (c0..c3), key (k0, k1) -> four independent 32-bit words.  The device generator of
+// sqair_fill_noise (sqair_train.hip) and of the SMC resampler's uniforms (k_smc_resample, sqair_glue.hip).
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
+                                              unsigned out[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
+    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
 // launchers (sqair_linear.hip)
 int sq_launch_linear(const LinArgs& a, const PackedLayer& L, hipStream_t s);
 int sq_launch_pack(const float* flat, float* packed_w, const int* idx, int64_t n, hipStream_t s);

@@ -194,6 +194,24 @@ struct StateArgs {
 int sq_launch_state_import(const StateArgs& a, hipStream_t s);
 int sq_launch_state_export(const StateArgs& a, hipStream_t s);
 
+// SMC resampling of the carried state (sqair_set_smc): one workgroup per lane b, thread k = particle k of the lane (K <= 256).
+struct SmcArgs {
+  const float* lw;             // this pass's log_weights_per_timestep [T][R]
+  const int* t_row;            // [R] frame counter of each row at frame 0 of the pass
+  const float* uniforms;       // [B] or NULL: Philox keyed by (seed, b, counter of row b*K after the pass)
+  float* log_w;                // [R] in/out
+  float* log_z;                // [B] in/out
+  float* log_evidence;         // [B] out
+  float* ess;                  // [B] out
+  float* u_out;                // [B] out or NULL
+  int* resampled;              // [B] out
+  int* src;                    // [R] out: source map of the next pass's k_state_import
+  unsigned long long seed;
+  float ess_frac;
+  int T, B, K;
+};
+int sq_launch_smc_resample(const SmcArgs& a, hipStream_t s);
+
 // Generation modes (sqair_modules.py:157-170, :294-302).  Generation record of slot (r, k), 64 floats:
 //   [0:4] where ~ prior, [4:54] what ~ prior, [54] presence ~ Bernoulli(prior logit), [55] the posterior path's own
 //   propagation presence, [56] the posterior path's own discovery presence of step k

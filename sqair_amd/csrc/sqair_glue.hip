@@ -144,6 +144,85 @@ int sq_launch_state_export(const StateArgs& a, hipStream_t s) {
   return 0;
 }
 
+// k_smc_resample (sqair_set_smc; SmcArgs in sqair_glue.h): the last launch of a pass with SMC on, after k_state_export.  Lane b's
+// log weights a_k = log_w + this pass's per-frame log weights (frame order) -> ESS and the evidence, then either a systematic
+// resampling written as the next pass's source map (k_state_import gathers the chosen rows out of the blob k_state_export just
+// wrote) or the identity map with the weights carried on.  Every lane-wide sum (max, S, sum e^2, the prefix c) is one thread's
+// loop in index order: the same bits on every replay, and K <= 256 adds are nothing next to the pass.
+constexpr unsigned SQ_SMC_PHILOX_TAG = 0x534D4352u;   // ("SMCR") counter word 1: never an element index of sqair_fill_noise
+__global__ __launch_bounds__(256) void k_smc_resample(const SmcArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ float s_a[SQ_MAX_K];   // a_k
+  __shared__ float s_c[SQ_MAX_K];   // e_k, then the inclusive prefix c_k
+  __shared__ float s_st[3];         // m, S, u
+  __shared__ int s_do;
+  const int b = blockIdx.x, k = threadIdx.x, K = a.K, R = a.B * K, r = b * K + k;
+  float acc = 0.0f;
+  if (k < K) {
+    acc = a.log_w[r];
+    for (int t = 0; t < a.T; ++t) acc += a.lw[(size_t)t * R + r];
+    s_a[k] = acc;
+  }
+  __syncthreads();
+  if (k == 0) {
+    float m = s_a[0];
+    for (int i = 1; i < K; ++i) m = fmaxf(m, s_a[i]);
+    s_st[0] = m;
+  }
+  __syncthreads();
+  if (k < K) s_c[k] = expf(acc - s_st[0]);
+  __syncthreads();
+  if (k == 0) {
+    const float m = s_st[0];
+    float c = 0.0f, q = 0.0f;
+    for (int i = 0; i < K; ++i) {
+      const float e = s_c[i];
+      c += e;
+      q += e * e;
+      s_c[i] = c;
+    }
+    const float ess = c * c / q, lse = m + logf(c / (float)K);
+    const float lz = a.log_z[b];
+    a.log_evidence[b] = lz + lse;
+    a.ess[b] = ess;
+    const int go = a.ess_frac == 1.0f || ess < a.ess_frac * (float)K;
+    float u;   // (drawn whether or not the lane resamples: u_out always holds this pass's u)
+    if (a.uniforms != nullptr) {
+      u = a.uniforms[b];
+    } else {
+      const unsigned ctr = (unsigned)(a.t_row[b * K] + a.T);   // (the lane's frame counter after the pass)
+      unsigned w[4];
+      philox4x32_10((unsigned)b, SQ_SMC_PHILOX_TAG, ctr, 0u, (unsigned)a.seed, (unsigned)(a.seed >> 32), w);
+      u = (float)(w[0] >> 8) * (1.0f / 16777216.0f);   // [0, 1), 24 bits
+    }
+    if (a.u_out != nullptr) a.u_out[b] = u;
+    if (go) a.log_z[b] = lz + lse;
+    a.resampled[b] = go;
+    s_st[1] = c; s_st[2] = u; s_do = go;
+  }
+  __syncthreads();
+  if (k >= K) return;
+  if (s_do) {
+    // output k: the smallest i with c_i > (k + u) S / K (the last particle if none: float rounding of c_{K-1} vs S)
+    const float thr = ((float)k + s_st[2]) * s_st[1] / (float)K;
+    int lo = 0, hi = K - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (s_c[mid] > thr) hi = mid;
+      else lo = mid + 1;
+    }
+    a.src[r] = b * K + lo;
+    a.log_w[r] = 0.0f;
+  } else {
+    a.src[r] = r;
+    a.log_w[r] = acc;
+  }
+}
+int sq_launch_smc_resample(const SmcArgs& a, hipStream_t s) {
+  SQ_LAUNCH(k_smc_resample, dim3(a.B), dim3(256), 0, s, a);
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Spatial-transformer crop (reference: sqair/modules.py:170-227; Sonnet AffineGridWarper +
 // tf.contrib.resampler).  One workgroup per sequence b stages the frame in LDS

@@ -79,6 +79,9 @@ struct SqairHandle {
   void* state_out = nullptr;         // may equal state_in
   const int32_t* state_src = nullptr;  // [R] source row of each imported row (-1 = fresh), or NULL = identity
   int state_B = 0;
+  // SMC resampling of the carried state (sqair_set_smc): one k_smc_resample launch after the state export
+  bool smc_on = false;
+  SqairSmc smc = {};                 // (smc.src_rows == state_src and its B == state_B while smc_on)
   // generic capture slots (sqair_capture_begin / _end / _launch): any sequence of C-ABI calls as one HIP graph
   hipGraph_t cap_graph[4] = {nullptr, nullptr, nullptr, nullptr};
   hipGraphExec_t cap_exec[4] = {nullptr, nullptr, nullptr, nullptr};

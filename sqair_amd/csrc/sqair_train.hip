@@ -790,18 +790,8 @@ extern "C" int sqair_add_l2_grad(SqairHandle* h, const float* flat_params, float
 // al., SC'11), counter = (global element index, step), key = seed: every element is a pure function of (seed, step,
 // its position in the GLOBAL batch), so a rank that owns sequences [b0, b0 + B) of a global batch draws exactly the rows it
 // would have seen on one GPU (the reference draws inside the TF graph: tfd .sample() at core.py:226, modules.py:60, :485).
+// philox4x32_10 itself is in sqair_common.h (the SMC resampler draws from it too).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned out[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 __global__ void k_fill_noise(float* __restrict__ noise, int64_t n_local, int64_t per_frame_local, int64_t per_frame_global,
                              int64_t row0_elems, int nzw, unsigned long long seed, unsigned long long step SQ_TLP) {
   SQ_TL_SCOPE;

@@ -11,21 +11,42 @@ noise (tests/test_stream_state.py).  Without explicit ``noise`` a step draws its
 (seed, frame index of the step's first frame, row): NOT the draws a whole-sequence pass with the same seed makes (that one keys
 every frame of the pass by one step index), so results agree with such a pass only in distribution.
 
+With ``resample="systematic"`` the stream is an adaptive particle filter run inside the pass (include/sqair_hip.h:
+sqair_set_smc): the per-frame log weights are the incremental importance weights of a filter whose proposal is the inference
+network, and a kernel at the end of every pass computes each lane's ESS and log evidence and, when ESS < ess_frac * K (always for
+ess_frac = 1, never for 0), resamples the lane's particles systematically by writing the source map of the next step -- no host
+decision, so the one captured graph still serves every frame.  Resampling happens at step boundaries: frames_per_step = 1 gives
+per-frame SMC.  The uniform of a lane is the step's ``uniforms[b]`` when given, else Philox keyed by (``seed``, lane, frame
+counter).  ``log_weight_sum`` is then the device accumulator of each row's log weight SINCE ITS LANE'S LAST RESAMPLING (zeroed
+there; the evidence banked at resamplings is ``log_z``), and ``step()`` adds ``ess``, ``resampled``, ``log_evidence`` (the SMC
+estimate of log p(x_1..t) per lane) and ``ancestors`` (the source map of the next step) to its outputs.
+
 The stream takes over its core's handle: while it is open, every inference pass of that handle carries the state.  ``close()``
 hands the handle back.
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 import torch
+
+from sqair_amd import _capi
 
 DEFAULT_OUTPUTS = ("what", "where", "presence", "obj_id", "log_weights_per_timestep")
 
 
 class SqairStream(object):
-    def __init__(self, core, B, frames_per_step=1, outputs=DEFAULT_OUTPUTS, use_graph=True, seed=0):
+    def __init__(self, core, B, frames_per_step=1, outputs=DEFAULT_OUTPUTS, use_graph=True, seed=0, resample=None, ess_frac=0.5):
         if core.cfg.sample_from_prior:
             raise ValueError("SqairStream: generation modes (sample_from_prior) do not carry a state across calls")
+        if resample not in (None, "systematic"):
+            raise ValueError("SqairStream: resample must be None or 'systematic'")
+        ess_frac = float(ess_frac)
+        if resample is not None and not 0.0 <= ess_frac <= 1.0:   # (NaN fails too)
+            raise ValueError("SqairStream: ess_frac must lie in [0, 1]")
+        self.smc = resample is not None
+        self.ess_frac = ess_frac
         self.core = core
         self.B, self.K = int(B), core.K
         self.R = self.B * self.K
@@ -46,13 +67,39 @@ class SqairStream(object):
             self._identity = torch.arange(self.R, dtype=torch.int32, device=dev)
             self._src = self._identity.clone()   # (frozen into the captured graph; refreshed before a step that needs another map)
             self.log_weight_sum = torch.zeros(self.R, dtype=torch.float32, device=dev)
-        self._src_is_identity = True
-        self._armed = np.full(self.R, -1, dtype=np.int64)   # host-side source map of the next step (None: identity); first: all fresh
+            if self.smc:   # (SMC: the kernel writes _src after every pass; the first step starts every row fresh)
+                self._src.fill_(-1)
+                self.log_z = torch.zeros(self.B, dtype=torch.float32, device=dev)
+                self.log_evidence = torch.zeros(self.B, dtype=torch.float32, device=dev)
+                self.ess = torch.zeros(self.B, dtype=torch.float32, device=dev)
+                self.u = torch.zeros(self.B, dtype=torch.float32, device=dev)   # the uniform of each lane's last step
+                self.resampled = torch.zeros(self.B, dtype=torch.int32, device=dev)
+                self._uniforms = torch.zeros(self.B, dtype=torch.float32, device=dev)
+        self._src_is_identity = True   # (SMC: _src is written on the device only, never refreshed from the host)
+        # host-side source map of the next step (None: identity); first: all fresh.  SMC composes maps on the device instead.
+        self._armed = None if self.smc else np.full(self.R, -1, dtype=np.int64)
         self._graph = False
+        self._smc_uniforms = None   # registered with the caller's uniforms (True) or Philox (False)
         core.stream.synchronize()
         core.check(lib.sqair_set_state(core.handle, self.state.data_ptr(), self.state.data_ptr(), self._src.data_ptr(),
                                        self.state.numel() * 4, self.B), "sqair_set_state")
+        if self.smc:
+            self._set_smc(False)
         core._graph_ready = False   # (the handle's graph is now this stream's)
+
+    def _set_smc(self, uniforms):
+        """Registers the SMC buffers (sqair_set_smc), the lane uniforms read from ``_uniforms`` or drawn by Philox.  The pointers
+        are frozen into the captured graph: switching between the two recaptures it on the next step."""
+        if self._smc_uniforms is uniforms:
+            return
+        smc = _capi.SqairSmc(ess_frac=self.ess_frac, seed=self.seed & 0xFFFFFFFFFFFFFFFF,
+                             uniforms=self._uniforms.data_ptr() if uniforms else None, log_w=self.log_weight_sum.data_ptr(),
+                             log_z=self.log_z.data_ptr(), log_evidence=self.log_evidence.data_ptr(), ess=self.ess.data_ptr(),
+                             u_out=self.u.data_ptr(), resampled=self.resampled.data_ptr(), src_rows=self._src.data_ptr())
+        core = self.core
+        core.check(core.lib.sqair_set_smc(core.handle, C.byref(smc), self.B), "sqair_set_smc")
+        self._smc_uniforms = uniforms
+        self._graph = False
 
     # ---- source map -------------------------------------------------------------------------------------------------------
     def _pending(self):
@@ -63,6 +110,17 @@ class SqairStream(object):
         lanes = np.atleast_1d(np.asarray(lanes))
         if lanes.size and (lanes.dtype.kind not in "iu" or lanes.min() < 0 or lanes.max() >= self.B):
             raise ValueError("SqairStream.reset: lanes must be integers in [0, {})".format(self.B))
+        if self.smc:   # on the device, after the map the last step's resampler wrote: the lane's rows fresh, its weights zero
+            core = self.core
+            with torch.cuda.device(core.device):
+                core._join_in()
+                with core.on_stream():
+                    for j in sorted(set(lanes.tolist())):
+                        self._src[j * self.K:(j + 1) * self.K].fill_(-1)
+                        self.log_weight_sum[j * self.K:(j + 1) * self.K].zero_()
+                        self.log_z[j:j + 1].zero_()
+                core._join_out()
+            return
         m = self._pending().copy()
         for j in lanes.tolist():
             m[j * self.K:(j + 1) * self.K] = -1
@@ -70,18 +128,33 @@ class SqairStream(object):
 
     def resample(self, src_rows):
         """Row r of the next step continues row src_rows[r] (-1: starts fresh); e.g. SMC resampling of the particles of each
-        sequence, src[b*K + k] = b*K + k'.  Composes with a reset armed before it.  The running log-weight sums follow the rows."""
+        sequence, src[b*K + k] = b*K + k'.  Composes with a reset armed before it.  The running log-weight sums follow the rows.
+        With SMC on it composes on the device with the map the last step's resampler wrote: src_new[r] = src[src_rows[r]]."""
         src = np.asarray(src_rows)
         if src.shape != (self.R,) or src.dtype.kind not in "iu" or (src.size and (src.min() < -1 or src.max() >= self.R)):
             raise ValueError("SqairStream.resample: src_rows must be {} integers in [-1, {})".format(self.R, self.R))
+        if self.smc:
+            core = self.core
+            with torch.cuda.device(core.device):
+                core._join_in()
+                with core.on_stream():
+                    s = torch.as_tensor(src.astype(np.int64)).pin_memory().to(core.device, non_blocking=True)
+                    keep = s >= 0
+                    s = s.clamp_min(0)
+                    self._src.copy_(torch.where(keep, self._src[s], torch.full_like(self._src, -1)))
+                    self.log_weight_sum.copy_(torch.where(keep, self.log_weight_sum[s], torch.zeros_like(self.log_weight_sum)))
+                core._join_out()
+            return
         m = self._pending()
         self._armed = np.where(src >= 0, m[np.maximum(src, 0)], -1)
 
     # ---- stepping ---------------------------------------------------------------------------------------------------------
-    def step(self, frames, noise=None, seed=None):
+    def step(self, frames, noise=None, seed=None, uniforms=None):
         """Consumes frames [T', B, H, W] (T' = frames_per_step); returns this step's per-frame outputs {name: [T', B*K, ...]}
         (copies, valid on the current stream).  ``noise`` [T', B*K, 2, N, 4 + n_what + 1]; default: the library's generator
-        keyed by (``seed`` or the stream's seed, frame index)."""
+        keyed by (``seed`` or the stream's seed, frame index).  With SMC on, also ``ess``, ``resampled``, ``log_evidence`` [B]
+        and ``ancestors`` [B*K] (the next step's source map), device copies taken before anything is read on the host;
+        ``uniforms`` [B] in [0, 1): this step's systematic-resampling uniforms (default: Philox)."""
         core = self.core
         frames = torch.as_tensor(frames, dtype=torch.float32)
         if frames.dim() == 5:
@@ -94,6 +167,14 @@ class SqairStream(object):
             if noise.numel() != core.noise.numel():
                 raise ValueError("SqairStream.step: noise of shape {} given, {} expected".format(tuple(noise.shape),
                                                                                                tuple(core.noise.shape)))
+        if uniforms is not None:
+            if not self.smc:
+                raise ValueError("SqairStream.step: uniforms are for a stream with resample='systematic'")
+            uniforms = torch.as_tensor(uniforms, dtype=torch.float32)
+            if tuple(uniforms.shape) != (self.B,):
+                raise ValueError("SqairStream.step: uniforms of shape {} given, [{}] expected".format(tuple(uniforms.shape), self.B))
+        if self.smc:
+            self._set_smc(uniforms is not None)
         lib = core.lib
         with torch.cuda.device(core.device):
             core._join_in()
@@ -103,6 +184,9 @@ class SqairStream(object):
                     core.noise.copy_(noise.reshape(core.noise.shape), non_blocking=True)
                 else:
                     core.draw_noise(seed=self.seed if seed is None else int(seed), step=self.frame)
+                if uniforms is not None:
+                    self._uniforms.copy_(uniforms, non_blocking=True)
+                # (SMC: nothing armed; the source map is the one the last step's resampler wrote, resets / resamples composed in)
                 if self._armed is not None:
                     m = torch.as_tensor(self._armed.astype(np.int32))
                     self._src.copy_(m, non_blocking=True)
@@ -122,7 +206,11 @@ class SqairStream(object):
                 else:
                     core.check(lib.sqair_forward(*core._args(0)), "sqair_forward")
                 out = {k: core.out[k].clone() for k in self.outputs}
-                self.log_weight_sum += out["log_weights_per_timestep"].sum(0)
+                if self.smc:   # (log_weight_sum is the resampler's accumulator)
+                    out.update(ess=self.ess.clone(), resampled=self.resampled.clone(), log_evidence=self.log_evidence.clone(),
+                               ancestors=self._src.clone())
+                else:
+                    self.log_weight_sum += out["log_weights_per_timestep"].sum(0)
             core._join_out()
         self.frame += self.T
         return out

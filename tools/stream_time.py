@@ -6,6 +6,11 @@ Two shapes: cfg-2's batch (B = 32 sequences x K = 5 particles, N = 4) and one ca
 the device beforehand, so a step is: frame copy, noise fill, the one-frame pass, the output copies and the log-weight sum.
 
     python tools/stream_time.py [--steps 500] [--warmup 50] [--out profiles/stream_time.json]
+
+With --smc: the same step with in-graph SMC resampling (SqairStream(resample="systematic"), include/sqair_hip.h: sqair_set_smc)
+at ess_frac 0.5 and 1.0 next to SMC off, at cfg-2's batch and for one camera with K = 5 particles:
+
+    python tools/stream_time.py --smc [--out profiles/stream_time_smc.json]
 """
 import argparse
 import json
@@ -25,7 +30,7 @@ from sqair_amd.params import init_params  # noqa: E402
 from sqair_amd.stream import SqairStream  # noqa: E402
 
 
-def time_stream(B, K, N, steps, warmup, hw=(50, 50)):
+def time_stream(B, K, N, steps, warmup, hw=(50, 50), resample=None, ess_frac=0.5):
     F = make_flags(k_particles=K, n_steps_per_image=N)
     d = make_sequences(B, T=50, canvas=hw, seed=7)   # (fed cyclically)
     obs = torch.as_tensor(to_float(d["imgs"])).cuda()
@@ -33,7 +38,7 @@ def time_stream(B, K, N, steps, warmup, hw=(50, 50)):
          init_params(F, hw, seed=0, mean_img=obs.mean((0, 1)).cpu().numpy(), jitter=0.02).items()}
     core = SqairCore(F, hw)
     core.set_params(P)
-    st = SqairStream(core, B, frames_per_step=1, use_graph=True)
+    st = SqairStream(core, B, frames_per_step=1, use_graph=True, resample=resample, ess_frac=ess_frac)
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
     with core.on_stream():
         for t in range(warmup):
@@ -53,8 +58,11 @@ def time_stream(B, K, N, steps, warmup, hw=(50, 50)):
             st.step(obs[i % 50:i % 50 + 1])
         b.record()
         torch.cuda.synchronize()
+    extra = {}
+    if resample is not None:   # (how often the lanes of the last back-to-back step resampled: the work is the same either way)
+        extra = dict(resample=resample, ess_frac=ess_frac, resampled_last_step=int(st.resampled.sum()))
     st.close()
-    return dict(B=B, K=K, N=N, hw=list(hw), steps=steps, warmup=warmup, graph_nodes=core.graph_nodes(),
+    return dict(B=B, K=K, N=N, hw=list(hw), steps=steps, warmup=warmup, graph_nodes=core.graph_nodes(), **extra,
                 ms_per_frame_median=float(np.median(ms)), ms_per_frame_p10=float(np.percentile(ms, 10)),
                 ms_per_frame_p90=float(np.percentile(ms, 90)), ms_per_frame_back_to_back=float(a.elapsed_time(b) / steps))
 
@@ -64,12 +72,21 @@ def main():
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--smc", action="store_true", help="SMC resampling off / ess_frac 0.5 / 1.0 (profiles/stream_time_smc.json)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     ov, _, _, _ = config_inputs(2)
-    res = dict(build_id=_capi.build_id(), device=torch.cuda.get_device_name(0), shapes=[
-        dict(name="cfg2_batch", **time_stream(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup)),
-        dict(name="one_camera", **time_stream(1, 1, ov["n_steps_per_image"], args.steps, args.warmup))])
+    if args.smc:
+        shapes = []
+        for name, B, K in (("cfg2_batch", 32, ov["k_particles"]), ("one_camera_k5", 1, 5)):
+            for resample, frac in ((None, 0.5), ("systematic", 0.5), ("systematic", 1.0)):
+                tag = "off" if resample is None else "smc_{}".format(frac)
+                shapes.append(dict(name=name + "_" + tag, **time_stream(B, K, ov["n_steps_per_image"], args.steps, args.warmup,
+                                                                         resample=resample, ess_frac=frac)))
+    else:
+        shapes = [dict(name="cfg2_batch", **time_stream(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup)),
+                  dict(name="one_camera", **time_stream(1, 1, ov["n_steps_per_image"], args.steps, args.warmup))]
+    res = dict(build_id=_capi.build_id(), device=torch.cuda.get_device_name(0), shapes=shapes)
     print(json.dumps(res))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
