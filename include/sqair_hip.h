@@ -211,9 +211,12 @@ int sqair_set_state(SqairHandle* h, const void* state_in, void* state_out, const
  *   log_evidence[b] = log_z[b] + m + log(S / K)    (SMC estimate of log p(x_1..t)),  ess[b] = ESS   (both before resampling)
  *   resample iff ess_frac == 1 or ESS < ess_frac * K:
  *     systematic, one u per lane (uniforms[b], or Philox keyed by (seed, b, frame counter of row b*K after the pass)):
- *     src_rows[b*K + j] = b*K + (smallest k with c_k > (j + u) * S / K, at most K - 1), c = inclusive prefix sum of e;
+ *     src_rows[b*K + j] = b*K + (smallest k with c_k > (j + u) * S / K; if fp32 rounding leaves none, the first k with
+ *     c_k = S: the last particle of positive weight, never a zero-weight one), c = inclusive prefix sum of e;
  *     log_z[b] += m + log(S / K), log_w of the lane = 0, resampled[b] = 1
  *   otherwise: src_rows of the lane = identity, log_w[b*K + k] = a_k, resampled[b] = 0.
+ *   A lane whose ESS is not finite (a NaN or +inf a_k, or every a_k at -inf) never resamples, whatever ess_frac: identity map,
+ *   a_k carried in log_w unchanged, log_z kept, resampled[b] = 0; its ess and log_evidence show the non-finite value.
  * The next pass's state import gathers the rows through src_rows (records, cell states, ids, counters): the path a caller's
  * own source map takes.  Resampling happens at pass boundaries only: one-frame passes give per-frame SMC.
  * u_out[b] receives the lane's uniform of the pass whether or not the lane resampled.
@@ -235,6 +238,13 @@ typedef struct {
   int32_t* src_rows;         /* must be the source map given to sqair_set_state; written for the next pass */
 } SqairSmc;
 int sqair_set_smc(SqairHandle* h, const SqairSmc* smc, int B);   /* NULL smc: off */
+/* Kernel-level check of the resampler (tests): the kernel above on caller buffers, no state and no pass.  lw [T][B*K] stands for
+ * the pass's log_weights_per_timestep, t_row [B*K] for the rows' frame counters at frame 0 of the pass (read only for Philox,
+ * when smc->uniforms is NULL; may then be NULL otherwise), smc->src_rows [B*K] receives the map.  1 <= K <= 256.  Refused
+ * (return -1, before any HIP call): NULL lw / smc, T, B or K out of range, ess_frac NaN or outside [0, 1], a NULL log_w / log_z /
+ * log_evidence / ess / resampled / src_rows, or no uniforms and no t_row. */
+int sqair_smc_resample_test(SqairHandle* h, const float* lw, int T, int B, int K, const int32_t* t_row, const SqairSmc* smc,
+                            void* stream);
 
 /* ---- objective ---------------------------------------------------------------------------------
  * Fused IWAE / VIMCO reductions over [T,B,K] (reference: Model._build sqair/model.py:88-103,

@@ -627,8 +627,12 @@ class SqairOracle(object):
             pr = torch.tensor(1.0 - c.step_success_prob, dtype=self.dtype)
             p_num = num_steps * torch.log1p(-pr) + torch.log(pr)
         else:
-            logits = P["disc.step_prior_bias"] + (0.0 if t == 0 else 1.0) * P["disc.step_prior_timestep_bias"]
-            logits = logits[None] + mlp_1hidden_out(P, "disc.steps_prior", prior_conditioning)
+            if torch.is_tensor(t):   # per-row frame counters (a carried state, k_logprob's t_row + frame): the bias where t > 0
+                logits = P["disc.step_prior_bias"] + (t > 0).to(self.dtype)[:, None] * P["disc.step_prior_timestep_bias"]
+                logits = logits + mlp_1hidden_out(P, "disc.steps_prior", prior_conditioning)
+            else:
+                logits = P["disc.step_prior_bias"] + (0.0 if t == 0 else 1.0) * P["disc.step_prior_timestep_bias"]
+                logits = logits[None] + mlp_1hidden_out(P, "disc.steps_prior", prior_conditioning)
             logits = elu(logits)
             p_num = torch.log_softmax(logits, -1).gather(-1, num_steps.long().unsqueeze(-1)).squeeze(-1)
         o = dict(ho)
@@ -662,7 +666,7 @@ class SqairOracle(object):
         """SQAIRTimestep._build/_propagate_and_discover/_choose_latents (sqair_modules.py:446-582)."""
         c = self.cfg
         B, N = img.shape[0], c.N
-        do_generate = c.generate_after > 0 and t > c.generate_after  # seq.py:198-200
+        do_generate = not torch.is_tensor(t) and c.generate_after > 0 and t > c.generate_after  # seq.py:198-200 (t: per row)
         gn = gen_noise if gen_noise is not None else torch.zeros_like(noise)
         prop = self.propagate(img, z_tm1, temporal_state, prior_state, noise[:, 0], gn[:, 0], do_generate)
         cond = self.encode_latents(prop["what"], prop["where"], prop["presence"])
@@ -711,20 +715,50 @@ class SqairOracle(object):
         std = nz * c.output_std + (1.0 - nz) * c.background_std
         return canvas, std, glimpse.reshape(B, N, c.G, c.G)
 
+    # ---- carried state (streaming inference: include/sqair_hip.h sqair_set_state) -----
+    def initial_state(self, B):
+        """What frame 0 of a pass reads for B rows that start fresh: z (what, where, presence, presence logit), the temporal
+        and prior cell states, prev_ids, last_id and the per-row frame counter t (0)."""
+        c = self.cfg
+        N, nw, dt = c.N, c.n_what, self.dtype
+        return SimpleNamespace(
+            z=(torch.zeros(B, N, nw, dtype=dt), torch.zeros(B, N, 4, dtype=dt), torch.zeros(B, N, 1, dtype=dt),
+               torch.zeros(B, N, 1, dtype=dt)),
+            temporal=self.initial_temporal_state()[None].expand(B, N, -1), prior=self.initial_prior_state()[None].expand(B, N, -1),
+            prev_ids=-torch.ones(B, N, 1, dtype=dt), last_id=-torch.ones(B, 1, dtype=dt), t=torch.zeros(B, dtype=torch.int64))
+
+    def gather_state(self, state, src):
+        """Row r of the result continues row src[r] of ``state``; src[r] = -1 starts it fresh (counter 0): the semantics of the
+        device source map (k_state_import)."""
+        src = torch.as_tensor(np.asarray(src), dtype=torch.int64)
+        fresh = self.initial_state(src.shape[0])
+        keep = src >= 0
+        idx = src.clamp(min=0)
+
+        def g(x, x0):
+            m = keep.reshape((-1,) + (1,) * (x.dim() - 1))
+            return torch.where(m, x[idx], x0)
+        return SimpleNamespace(z=tuple(g(a, b) for a, b in zip(state.z, fresh.z)), temporal=g(state.temporal, fresh.temporal),
+                               prior=g(state.prior, fresh.prior), prev_ids=g(state.prev_ids, fresh.prev_ids),
+                               last_id=g(state.last_id, fresh.last_id), t=g(state.t, fresh.t))
+
     # ---- sequence unroll -------------------------------------------------------------
-    def sequence(self, tiled_obs, noise, gen_noise=None):
+    def sequence(self, tiled_obs, noise, gen_noise=None, state=None, return_state=False):
         """SequentialAIR._build/_prepare_loop_vars/_loop_body/_compute_log_weights
-        (seq.py:69-279).  tiled_obs [T,B',H,W]; noise [T,B',2,N,4+n_what+1]."""
+        (seq.py:69-279).  tiled_obs [T,B',H,W]; noise [T,B',2,N,4+n_what+1].  ``state`` (initial_state / gather_state / the
+        final state of an earlier call): the rows start from it and the step prior's t is the row's frame counter + frame.
+        With ``return_state`` the result is (outputs, final state)."""
         c = self.cfg
         T, B = tiled_obs.shape[:2]
         N, nw, nh = c.N, c.n_what, c.n_hidden
         dt = self.dtype
-        z = (torch.zeros(B, N, nw, dtype=dt), torch.zeros(B, N, 4, dtype=dt), torch.zeros(B, N, 1, dtype=dt),
-             torch.zeros(B, N, 1, dtype=dt))
-        temporal = self.initial_temporal_state()[None].expand(B, N, -1)
-        prior = self.initial_prior_state()[None].expand(B, N, -1)
-        prev_ids = -torch.ones(B, N, 1, dtype=dt)
-        last_id = -torch.ones(B, 1, dtype=dt)
+        if state is None:
+            s0 = self.initial_state(B)
+        else:
+            if c.sample_from_prior:
+                raise ValueError("the generation modes (sample_from_prior) do not carry a state")
+            s0 = state
+        z, temporal, prior, prev_ids, last_id = s0.z, s0.temporal, s0.prior, s0.prev_ids, s0.last_id
         tas = OrderedDict()
 
         def write(name, val):
@@ -734,7 +768,8 @@ class SqairOracle(object):
 
         for t in range(T):
             img = tiled_obs[t]
-            o = self.timestep(img, z, temporal, prior, last_id, prev_ids, t, noise[t], None if gen_noise is None else gen_noise[t])
+            tt = t if state is None else s0.t + t
+            o = self.timestep(img, z, temporal, prior, last_id, prev_ids, tt, noise[t], None if gen_noise is None else gen_noise[t])
             z_t = o["z_t"]
             canvas, std, glimpse = self.decode(z_t[0], z_t[1], z_t[2])
             data_ll = normal_log_prob(img, canvas, std).sum((1, 2))
@@ -787,6 +822,8 @@ class SqairOracle(object):
         out["_final_temporal_state"] = temporal
         out["_final_prior_state"] = prior
         out["_final_last_used_id"] = last_id
+        if return_state:
+            return out, SimpleNamespace(z=z, temporal=temporal, prior=prior, prev_ids=prev_ids, last_id=last_id, t=s0.t + T)
         return out
 
     # ---- Model (model.py) ------------------------------------------------------------

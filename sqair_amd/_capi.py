@@ -113,6 +113,8 @@ _PROTOS = {
     "sqair_state_bytes": (C.c_int64, [C.c_void_p, C.c_int]),
     "sqair_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),
     "sqair_set_smc": (C.c_int, [C.c_void_p, C.POINTER(SqairSmc), C.c_int]),
+    "sqair_smc_resample_test": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(SqairSmc),
+                                         C.c_void_p]),
     "sqair_fill_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]),
     "sqair_capture_begin": (C.c_int, [C.c_void_p, C.c_void_p]),
     "sqair_capture_end": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),

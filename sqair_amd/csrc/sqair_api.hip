@@ -903,6 +903,34 @@ static int sq_smc_refusal(SqairHandle* h, const SqairOutputs* outp) {
   sq_set_error(h, "SMC (sqair_set_smc) resamples on log_weights_per_timestep: a pass with SMC on must bind that output");
   return -1;
 }
+// kernel-level check of the SMC resampler (tests/test_smc_kernel.py): k_smc_resample on caller buffers, K given (1..SQ_MAX_K), no
+// state and no pass.  lw [T][B*K]; t_row [B*K] (read only for Philox, when smc->uniforms is NULL); smc->src_rows [B*K] out.
+extern "C" int sqair_smc_resample_test(SqairHandle* h, const float* lw, int T, int B, int K, const int32_t* t_row,
+                                       const SqairSmc* smc, void* stream) {
+  if (!h) return -1;
+  if (!lw || !smc || T < 1 || B < 1 || K < 1 || K > SQ_MAX_K || (int64_t)B * K > INT32_MAX) {
+    sq_set_error(h, "sqair_smc_resample_test: null lw / smc or bad T / B / K (1 <= K <= " + std::to_string(SQ_MAX_K) + ")");
+    return -1;
+  }
+  if (!(smc->ess_frac >= 0.0f && smc->ess_frac <= 1.0f)) {   // (NaN fails both)
+    sq_set_error(h, "sqair_smc_resample_test: ess_frac must lie in [0, 1]");
+    return -1;
+  }
+  if (!smc->log_w || !smc->log_z || !smc->log_evidence || !smc->ess || !smc->resampled || !smc->src_rows ||
+      (!smc->uniforms && !t_row)) {
+    sq_set_error(h, "sqair_smc_resample_test: log_w, log_z, log_evidence, ess, resampled, src_rows (and t_row without uniforms) "
+                    "must not be NULL");
+    return -1;
+  }
+  SmcArgs a; memset(&a, 0, sizeof(a));
+  a.lw = lw; a.t_row = t_row; a.uniforms = smc->uniforms;
+  a.log_w = smc->log_w; a.log_z = smc->log_z; a.log_evidence = smc->log_evidence; a.ess = smc->ess;
+  a.u_out = smc->u_out; a.resampled = smc->resampled; a.src = smc->src_rows;
+  a.seed = smc->seed; a.ess_frac = smc->ess_frac; a.T = T; a.B = B; a.K = K;
+  sq_launch_smc_resample(a, (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
 // the refusals of a pass with a carried state (host only: before any HIP call)
 int sq_state_refusal(SqairHandle* h, bool train, int B, int t_offset) {
   if (!h->state_on) return 0;

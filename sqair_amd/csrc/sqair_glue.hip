@@ -185,7 +185,9 @@ __global__ __launch_bounds__(256) void k_smc_resample(const SmcArgs a SQ_TLP) {
     const float lz = a.log_z[b];
     a.log_evidence[b] = lz + lse;
     a.ess[b] = ess;
-    const int go = a.ess_frac == 1.0f || ess < a.ess_frac * (float)K;
+    // (a NaN or infinite a_k, or every a_k at -inf, gives a non-finite ESS: such a lane never resamples, whatever ess_frac, so
+    //  the identity map and the carried a_k keep the bad values where the caller can see them)
+    const int go = isfinite(ess) && (a.ess_frac == 1.0f || ess < a.ess_frac * (float)K);
     float u;   // (drawn whether or not the lane resamples: u_out always holds this pass's u)
     if (a.uniforms != nullptr) {
       u = a.uniforms[b];
@@ -203,12 +205,14 @@ __global__ __launch_bounds__(256) void k_smc_resample(const SmcArgs a SQ_TLP) {
   __syncthreads();
   if (k >= K) return;
   if (s_do) {
-    // output k: the smallest i with c_i > (k + u) S / K (the last particle if none: float rounding of c_{K-1} vs S)
-    const float thr = ((float)k + s_st[2]) * s_st[1] / (float)K;
+    // output k: the smallest i with c_i > (k + u) S / K.  If none (fp32 rounding of (k + u) S / K up to S = c_{K-1}: k = K - 1
+    // and u near 1), the smallest i with c_i >= S, i.e. the last particle of positive weight, never a zero-weight one after it.
+    // The predicate is monotone in i and true at K - 1; below S it is c_i > thr alone.
+    const float thr = ((float)k + s_st[2]) * s_st[1] / (float)K, S = s_st[1];
     int lo = 0, hi = K - 1;
     while (lo < hi) {
       const int mid = (lo + hi) >> 1;
-      if (s_c[mid] > thr) hi = mid;
+      if (s_c[mid] > thr || s_c[mid] >= S) hi = mid;
       else lo = mid + 1;
     }
     a.src[r] = b * K + lo;
