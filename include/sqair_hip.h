@@ -246,6 +246,43 @@ int sqair_set_smc(SqairHandle* h, const SqairSmc* smc, int B);   /* NULL smc: of
 int sqair_smc_resample_test(SqairHandle* h, const float* lw, int T, int B, int K, const int32_t* t_row, const SqairSmc* smc,
                             void* stream);
 
+/* ---- forecasting: the generative prior rolled forward from a carried state ------------------------------------------------
+ * A forecast of F frames starts from the rows the NEXT pass would start from: state_in of sqair_set_state gathered through a source
+ * map (src_rows, or the map given to sqair_set_state when NULL; -1 = the fresh initial state, as a pass's import).  Frame f = 0..F-1
+ * is the reference's generated frame (seq.py:198-200, sqair_modules.py:157-170, :294-302) with discovery empty:
+ *   (where_loc, where_scale, what_loc, what_scale, logit), prior_state' = PropagatePrior(z_{t-1}, prior_state)
+ *       (prop_prior_type rnn / rw / guided as in the generation modes);
+ *   where = where_loc + where_scale * eps[0:4], what = what_loc + what_scale * eps[4:4+n_what], presence = u < sigmoid(logit)
+ *       with eps / u entry k of noise slot s = 0 of the frame (the forward pass's noise layout; s = 1 is not read);
+ *   the record carried to the next frame holds presence_logit = that prior logit and presence_prob = sigmoid(logit);
+ *   ids and compaction are the reference's merge with nothing discovered: compute_object_ids(last_id, prev_ids, presence, 0), then
+ *       the N slots present-first in a stable order, each with its new prior state; last_id does not change;
+ *   the decoder renders canvas mean and glimpses of the frame (no likelihood: there is no observation).
+ * A forecast writes nothing but `out` and its own workspace: not the state blob, the source map, SMC buffers or any forward
+ * workspace, so it may interleave with passes.  It is capturable (sqair_capture_begin / _end): no host sync, no allocation.
+ * Summaries per lane b (SMC-weighted predictive): w_k = softmax over the lane's K entries of log_w (NULL: uniform),
+ *   mean_canvas[f, b] = sum_k w_k canvas[f, b*K + k], expected_count[f, b] = sum_k w_k (present slots of particle k), sums over k in
+ *   index order (the same bits on every replay).  A lane whose log weights hold a NaN or +inf, or are all -inf, gets NaN summaries.
+ * Refused (return -1, text in sqair_last_error, before any HIP call): no state with state_in set, a B other than the state's,
+ * F < 1, NULL noise, workspace_bytes < sqair_forecast_workspace_bytes(h, F, B), a configuration with sample_from_prior. */
+typedef struct SqairForecastOutputs {   /* every pointer optional */
+  float* what;            /* [F,B',N,n_what] */
+  float* where;           /* [F,B',N,4] */
+  float* presence;        /* [F,B',N] */
+  float* presence_prob;   /* [F,B',N] sigmoid of the prior logit */
+  float* presence_logit;  /* [F,B',N] */
+  float* obj_id;          /* [F,B',N] */
+  float* canvas;          /* [F,B',H,W] decoder mean */
+  float* glimpse;         /* [F,B',N,G,G] */
+  const float* log_w;     /* [B'] in: particle log weights for the summaries; NULL = uniform */
+  float* mean_canvas;     /* [F,B,H,W]  sum_k w_k canvas_k,  w = softmax over the lane's K log weights */
+  float* expected_count;  /* [F,B]      sum_k w_k * (objects present in particle k) */
+} SqairForecastOutputs;
+int64_t sqair_forecast_workspace_bytes(const SqairHandle* h, int F, int B);
+int sqair_forecast(SqairHandle* h, const float* flat_params, const void* packed, const float* noise /*[F,B',2,N,nzw]*/,
+                   int F, int B, const int32_t* src_rows /*NULL: the map of sqair_set_state*/,
+                   const SqairForecastOutputs* out, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- objective ---------------------------------------------------------------------------------
  * Fused IWAE / VIMCO reductions over [T,B,K] (reference: Model._build sqair/model.py:88-103,
  * targets.iwae / vimco_control_variate / vimco sqair/targets.py:38-75, make_target model.py:150-158,

@@ -50,6 +50,12 @@ class SqairSmc(C.Structure):
     ]
 
 
+class SqairForecastOutputs(C.Structure):
+    """Outputs of sqair_forecast (include/sqair_hip.h); every pointer is a device address or None."""
+    _fields_ = [(n, C.c_void_p) for n in ("what", "where", "presence", "presence_prob", "presence_logit", "obj_id", "canvas", "glimpse",
+                                          "log_w", "mean_canvas", "expected_count")]
+
+
 _PROTOS = {
     "sqair_abi_version": (C.c_int, []),
     "sqair_build_id": (C.c_char_p, []),
@@ -115,6 +121,9 @@ _PROTOS = {
     "sqair_set_smc": (C.c_int, [C.c_void_p, C.POINTER(SqairSmc), C.c_int]),
     "sqair_smc_resample_test": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(SqairSmc),
                                          C.c_void_p]),
+    "sqair_forecast_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
+    "sqair_forecast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                 C.POINTER(SqairForecastOutputs), C.c_void_p, C.c_int64, C.c_void_p]),
     "sqair_fill_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]),
     "sqair_capture_begin": (C.c_int, [C.c_void_p, C.c_void_p]),
     "sqair_capture_end": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),

@@ -1825,6 +1825,169 @@ extern "C" int sqair_set_generation_noise(SqairHandle* h, const float* gen_noise
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// forecast (include/sqair_hip.h: sqair_forecast): the propagation prior rolled F frames forward from the carried state, discovery
+// empty, then the decoder of all F frames and the predictive summaries
+// ------------------------------------------------------------------------------------------------
+struct FcWorkspace {
+  float* rec;        // [F + 1][M][rec::W]: frame 0 = the imported state, frame f + 1 = forecast frame f
+  float* temporal;   // [M][snh] (written by the import, never read)
+  float* prior[2];   // [M][psnh] compacted prior states, ping-pong over frames
+  float* prior_p;    // [M][psnh] the prior cell's output of the frame
+  float *pgz, *pgrh, *pgxh;   // prior cell internals (GRU: z gate, r h, x h; LSTM: pgz = the four gate pre-activations)
+  float* pstats;     // [M][PS_LD]
+  float* last_id;    // [R]
+  int* t_row;        // [R]
+  float *disc_init_rec, *prop_rnn_init, *disc_rnn_init, *rn_init_state, *w3_prop, *w3_disc;   // (k_init_state writes them)
+  float *dec_a, *dec_b, *glimpse;   // decoder of all F frames [F * M][nh | G*G]
+  float* canvas;     // [F][R][H*W] when the caller asks for summaries but not for the canvas
+  int64_t total;     // floats
+};
+static FcWorkspace fc_carve(const SqairHandle* h, int F, int B, float* base) {
+  const SqairConfig& c = h->cfg;
+  const int64_t nh = c.n_hidden, N = c.n_steps_per_image, R = (int64_t)B * c.k_particles, M = R * N;
+  const int64_t snh = c.time_cell == CELL_LSTM ? 2 * nh : nh, psnh = c.prior_cell == CELL_LSTM ? 2 * nh : nh;
+  FcWorkspace w;
+  memset(&w, 0, sizeof(w));
+  int64_t o = 0;
+  auto take = [&](int64_t n) {
+    float* p = base ? base + o : nullptr;
+    o += align64(n);
+    return p;
+  };
+  w.rec = take((int64_t)(F + 1) * M * rec::W);
+  w.temporal = take(M * snh);
+  w.prior[0] = take(M * psnh);
+  w.prior[1] = take(M * psnh);
+  w.prior_p = take(M * psnh);
+  w.pgz = take(M * (c.prior_cell == CELL_LSTM ? 4 * nh : nh));
+  w.pgrh = take(M * nh);
+  w.pgxh = take(M * nh);
+  w.pstats = take(M * PS_LD);
+  w.last_id = take(R);
+  w.t_row = (int*)take(R);
+  w.disc_init_rec = take(rec::W);
+  w.prop_rnn_init = take(2 * nh);
+  w.disc_rnn_init = take(2 * nh);
+  w.rn_init_state = take(4);
+  w.w3_prop = take(nh * 8 + 8);
+  w.w3_disc = take(nh * 8 + 8);
+  w.dec_a = take((int64_t)F * M * nh);
+  w.dec_b = take((int64_t)F * M * nh);
+  w.glimpse = take((int64_t)F * M * c.glimpse_size * c.glimpse_size);
+  w.canvas = take((int64_t)F * R * c.img_h * c.img_w);
+  w.total = o;
+  return w;
+}
+extern "C" int64_t sqair_forecast_workspace_bytes(const SqairHandle* h, int F, int B) {
+  if (!h || F < 1 || B < 1) return -1;
+  return fc_carve(h, F, B, nullptr).total * 4;
+}
+extern "C" int sqair_forecast(SqairHandle* h, const float* flat_params, const void* packed_v, const float* noise, int F, int B,
+                              const int32_t* src_rows, const SqairForecastOutputs* outp, void* workspace, int64_t workspace_bytes,
+                              void* stream) {
+  if (!h) return -1;
+  const SqairConfig& c = h->cfg;
+  if (c.sample_from_prior) {
+    sq_set_error(h, "sqair_forecast: not with sample_from_prior (the forecast is the generation mode, from a carried state)");
+    return -1;
+  }
+  if (!h->state_on || !h->state_in) {
+    sq_set_error(h, "sqair_forecast: needs a carried state with state_in (sqair_set_state) to start from");
+    return -1;
+  }
+  if (B != h->state_B) {
+    sq_set_error(h, "sqair_forecast: B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " +
+                        std::to_string(h->state_B));
+    return -1;
+  }
+  if (F < 1) {
+    sq_set_error(h, "sqair_forecast: F must be >= 1");
+    return -1;
+  }
+  if (!noise) {
+    sq_set_error(h, "sqair_forecast: noise must not be NULL");
+    return -1;
+  }
+  if (!flat_params || !packed_v || !outp || !workspace) {
+    sq_set_error(h, "sqair_forecast: null parameters, packed buffer, outputs or workspace");
+    return -1;
+  }
+  if (workspace_bytes < sqair_forecast_workspace_bytes(h, F, B)) {
+    sq_set_error(h, "sqair_forecast: workspace_bytes " + std::to_string(workspace_bytes) + " < sqair_forecast_workspace_bytes(h, " +
+                        std::to_string(F) + ", " + std::to_string(B) + ") = " + std::to_string(sqair_forecast_workspace_bytes(h, F, B)));
+    return -1;
+  }
+  const float* packed = (const float*)packed_v;
+  const float* flat = sq_flat(h, flat_params, packed);
+  sq_chain_reset(h);
+  hipStream_t s = (hipStream_t)stream;
+  const SqairForecastOutputs out = *outp;
+  const int nh = c.n_hidden, N = c.n_steps_per_image, K = c.k_particles, R = B * K, M = R * N, RW = rec::W;
+  const int G2 = c.glimpse_size * c.glimpse_size;
+  const Dims d = make_dims(c, B);
+  const int psnh = d.psnh;
+  const POff po = h->po;
+  const FcWorkspace w = fc_carve(h, F, B, (float*)workspace);
+  // prologue: the rows the next pass would start from (the pass's own k_init_state + k_state_import, into this workspace)
+  sq_launch_init_state(w.rec, w.temporal, w.prior[0], w.last_id, w.disc_init_rec, w.prop_rnn_init, w.disc_rnn_init, w.rn_init_state,
+                       w.w3_prop, w.w3_disc, (int)P(h, "prop.transform.l2.w"), (int)P(h, "disc.transform.l2.w"), flat, po, d, s);
+  {
+    StateArgs a; memset(&a, 0, sizeof(a));
+    a.rec = w.rec; a.temporal = w.temporal; a.prior = w.prior[0]; a.last_id = w.last_id; a.t_row = w.t_row;
+    a.blob_in = (const float*)h->state_in; a.src = src_rows ? src_rows : h->state_src;
+    a.R = R; a.n_rec = N * RW; a.n_tmp = N * d.snh; a.n_pri = N * psnh; a.row_words = (int)sq_state_row_floats(h); a.t0 = 0;
+    sq_launch_state_import(a, s);
+  }
+  // per frame: the prior cell over all M slots (section A of the pass), then sampling + ids + compaction in one launch
+  for (int f = 0; f < F; ++f) {
+    const float* rec_prev = w.rec + (size_t)f * M * RW;
+    const float* prior_prev = w.prior[f & 1];
+    if (c.prior_cell == CELL_LSTM) {
+      Lin g; g.seg(rec_prev, RW, rec::ZW).seg(prior_prev, psnh, nh).out(w.pgz, 4 * nh); RUN(g, L_PRIOR_GRU1, M);
+      sq_launch_lstm_cell(w.pgz, 4 * nh, prior_prev + nh, psnh, w.prior_p, psnh, M, nh, s);
+    } else if (c.prior_cell == CELL_VANILLA) {
+      Lin g; g.seg(rec_prev, RW, rec::ZW).seg(prior_prev, nh, nh).out(w.prior_p, nh).act(ACT_TANH); RUN(g, L_PRIOR_GRU1, M);
+    } else {
+      Lin g1l; g1l.seg(rec_prev, RW, rec::ZW).seg(prior_prev, nh, nh).out(w.pgz, nh).gru1(prior_prev, nh, w.pgrh, nh, w.pgxh, nh, nh);
+      RUN(g1l, L_PRIOR_GRU1, M);
+      Lin g2l; g2l.seg(w.pgrh, nh, nh).add(w.pgxh, nh, nh).out(w.prior_p, nh).gru2(prior_prev, nh, w.pgz, nh, nh);
+      RUN(g2l, L_PRIOR_GRU2, M);
+    }
+    Lin pll; pll.seg(w.prior_p, psnh, nh).out(w.pstats, PS_LD); RUN(pll, L_PRIOR_LIN, M);
+    ForecastArgs fa; memset(&fa, 0, sizeof(fa));
+    fa.rec_prev = rec_prev; fa.pstats = w.pstats; fa.ps_ld = PS_LD; fa.prior_p = w.prior_p;
+    fa.noise = noise + (size_t)f * R * 2 * N * d.nzw; fa.rec_next = w.rec + (size_t)(f + 1) * M * RW; fa.prior_next = w.prior[(f + 1) & 1];
+    fa.f = f; fa.out = out; fa.cfg = c;
+    sq_launch_forecast_step(fa, d, s);
+  }
+  // decoder of all F frames (section J of the pass without the likelihood): three M = F*B'*N row GEMMs + the canvas-only insert
+  const float* rec_all = w.rec + (size_t)M * RW;
+  float* canvas = out.canvas ? out.canvas : w.canvas;
+  const bool want_canvas = out.canvas || out.mean_canvas;
+  if (want_canvas || out.glimpse) {
+    const int MT = F * M;
+    float* gl = out.glimpse ? out.glimpse : w.glimpse;
+    Lin a; a.seg(rec_all, RW, rec::ZW).out(w.dec_a, nh).act(ACT_ELU); RUN(a, L_DEC0, MT);
+    Lin b; b.seg(w.dec_a, nh, nh).out(w.dec_b, nh).act(ACT_ELU); RUN(b, L_DEC1, MT);
+    Lin g; g.seg(w.dec_b, nh, nh).out(gl, G2); g.a.scale_ptr = flat + po.dec_output_scale; RUN(g, L_DEC2, MT);
+    if (want_canvas) {
+      InsertArgs ia; memset(&ia, 0, sizeof(ia));
+      ia.glimpse = gl; ia.rec = rec_all; ia.rec_ld = RW; ia.mean_img = flat + po.dec_mean_img; ia.canvas = canvas; ia.n_frames = F;
+      ia.std_fg = c.output_std; ia.std_bg = c.background_std;
+      if (sq_launch_insert_canvas(ia, d, s) != 0) { sq_set_error(h, "sqair_forecast: the decoder canvas launch failed (dynamic LDS limit)"); return -2; }
+    }
+  }
+  if (out.mean_canvas || out.expected_count) {
+    ForecastSummaryArgs sa; memset(&sa, 0, sizeof(sa));
+    sa.canvas = canvas; sa.rec = rec_all; sa.log_w = out.log_w; sa.mean_canvas = out.mean_canvas; sa.expected_count = out.expected_count;
+    sa.F = F;
+    sq_launch_forecast_summary(sa, d, s);
+  }
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 extern "C" int sqair_graph_launch(SqairHandle* h, void* stream) {
   if (!h || !h->graph_exec) {
     sq_set_error(h, "sqair_graph_launch: no captured graph");

@@ -234,6 +234,35 @@ struct GenArgs {
 int sq_launch_generate_prop(const GenArgs& a, POff po, Dims d, hipStream_t s);
 int sq_launch_generate_disc(const GenArgs& a, POff po, Dims d, hipStream_t s);
 
+// Forecast (sqair_forecast): frame f of a rollout of the propagation prior from a carried state, discovery empty.  k_forecast_step
+// samples every slot of a row from the prior statistics of this frame (the draws of k_generate_prop, same helpers), numbers the
+// objects (compute_object_ids with no discovery) and compacts the N slots present-first into the next frame's records and prior
+// states.  One wavefront per (row, slot).
+struct ForecastArgs {
+  const float* rec_prev;               // records of frame f - 1 [R][N][rec::W]
+  const float* pstats; int ps_ld;      // raw prior linear output of this frame [(R*N)][ps_ld]
+  const float* prior_p;                // the prior cell's new state of every slot [R][N][psnh]
+  const float* noise;                  // noise of frame f [R][2][N][nzw] (slot s = 0 read)
+  float* rec_next;                     // records of frame f [R][N][rec::W] (every word written)
+  float* prior_next;                   // compacted prior states [R][N][psnh]
+  int f;                               // frame index inside the outputs
+  SqairForecastOutputs out;            // per-frame outputs (what, where, presence, presence_prob, presence_logit, obj_id)
+  SqairConfig cfg;
+};
+int sq_launch_forecast_step(const ForecastArgs& a, Dims d, hipStream_t s);
+// Predictive summaries of a forecast: one workgroup per (frame, lane b); w = softmax of the lane's K log weights (NULL: uniform),
+// mean_canvas[f][b] = sum_k w_k canvas[f][b*K + k], expected_count[f][b] = sum_k w_k (present slots of particle k).  Every sum over k
+// runs in index order.
+struct ForecastSummaryArgs {
+  const float* canvas;                 // [F][R][H*W]
+  const float* rec;                    // records of frames 0..F-1 [F][R][N][rec::W]
+  const float* log_w;                  // [R] or NULL
+  float* mean_canvas;                  // [F][B][H*W] or NULL
+  float* expected_count;               // [F][B] or NULL
+  int F;
+};
+int sq_launch_forecast_summary(const ForecastSummaryArgs& a, Dims d, hipStream_t s);
+
 struct CompactArgs {
   const float* rec_p; const float* rec_d; const float* rec_prev;
   const float* temporal_p; const float* prior_p;
@@ -262,6 +291,9 @@ struct InsertArgs {
   float std_fg, std_bg;
 };
 int sq_launch_insert_loglik(const InsertArgs& a, Dims d, hipStream_t s);
+// The same kernels instantiated without an observation (forecast): canvas only -- img, data_ll, qz / pz and the scalar outputs are
+// not read or written.  a.canvas must be set.
+int sq_launch_insert_canvas(const InsertArgs& a, Dims d, hipStream_t s);
 
 int sq_launch_elbo(const float* log_w_t, const float* disc_lp_t, int T, int B, int K, float* log_weights,
                    float* elbo_per_ex, float* iw, float* signal, float* scalars, const float* const* means_in,

@@ -1073,13 +1073,29 @@ int sq_launch_logprob(const LogprobArgs& a, POff po, Dims d, hipStream_t s) {
 // Generation modes (reference: Propagate._compute_log_probs sqair/sqair_modules.py:294-302, Discover._compute_log_probs
 // :157-170, do_generate sqair/seq.py:198-200, RecurrentNormal.sample sqair/modules.py:619-629).  One wavefront per row.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float gen_prior_logit(const GenArgs& a, const float* rm, const float* ps) {
+// The draws from the propagation prior, shared by the generation modes (k_generate_prop) and the forecast (k_forecast_step) so that
+// both compute the same bits from the same inputs.  rm: the slot's record of t - 1; ps: its raw prior statistics
+// [logit | where_loc 4 | what_loc nw | where_scale 4 | what_scale nw] (propagate.py:68-98, rw / guided :123-158).
+__device__ __forceinline__ float sq_prior_logit(const SqairConfig& cfg, const float* rm, const float* ps) {
   const float pres_tm1 = rm[rec::PRES];
-  float pl = ps[0] + a.cfg.prop_prior_step_bias;
+  float pl = ps[0] + cfg.prop_prior_step_bias;
   pl = pres_tm1 * pl + (pres_tm1 - 1.0f) * 88.0f;
-  if (a.cfg.prop_prior_type != 0) pl = rm[rec::LOGIT] + 0.1f * pl;
+  if (cfg.prop_prior_type != 0) pl = rm[rec::LOGIT] + 0.1f * pl;
   return pl;
 }
+__device__ __forceinline__ float sq_prior_what_sample(const SqairConfig& cfg, const float* rm, const float* ps, int nw, int wc, float eps) {
+  float ploc = ps[5 + wc];
+  if (cfg.prop_prior_type == 1) ploc = rm[rec::WHAT + wc];
+  else if (cfg.prop_prior_type == 2) ploc = rm[rec::WHAT + wc] + 0.1f * ploc;
+  return ploc + (sq_softplus(ps[9 + nw + wc]) + 1e-2f) * eps;
+}
+__device__ __forceinline__ float sq_prior_where_sample(const SqairConfig& cfg, const float* rm, const float* ps, int nw, int c, float eps) {
+  float ploc = ps[1 + c];
+  if (cfg.prop_prior_type == 1) ploc = rm[rec::WHERE + c];
+  else if (cfg.prop_prior_type == 2) ploc = rm[rec::WHERE + c] + 0.1f * ploc;
+  return ploc + (sq_softplus(ps[5 + nw + c]) + 1e-2f) * eps;
+}
+__device__ __forceinline__ float gen_prior_logit(const GenArgs& a, const float* rm, const float* ps) { return sq_prior_logit(a.cfg, rm, ps); }
 // propagation: samples of the prior for every slot -> generation record; replaces the hidden outputs when generating
 __global__ __launch_bounds__(64) void k_generate_prop(const GenArgs a, const Dims d SQ_TLP) {
   SQ_TL_SCOPE;
@@ -1092,18 +1108,12 @@ __global__ __launch_bounds__(64) void k_generate_prop(const GenArgs a, const Dim
     const float* gn = a.gen_noise + (((size_t)r * 2 + 0) * N + k) * d.nzw;
     float* g = a.gen + rk * gen::W;
     SQ_WHAT_LANES(wc, lane, nw) {
-      float ploc = ps[5 + wc];
-      if (a.cfg.prop_prior_type == 1) ploc = rm[rec::WHAT + wc];
-      else if (a.cfg.prop_prior_type == 2) ploc = rm[rec::WHAT + wc] + 0.1f * ploc;
-      const float v = ploc + (sq_softplus(ps[9 + nw + wc]) + 1e-2f) * gn[4 + wc];
+      const float v = sq_prior_what_sample(a.cfg, rm, ps, nw, wc, gn[4 + wc]);
       g[gen::WHAT + wc] = v;
       if (a.do_generate) rp[rec::WHAT + wc] = v;
     }
     if (lane < 4) {
-      float ploc = ps[1 + lane];
-      if (a.cfg.prop_prior_type == 1) ploc = rm[rec::WHERE + lane];
-      else if (a.cfg.prop_prior_type == 2) ploc = rm[rec::WHERE + lane] + 0.1f * ploc;
-      const float v = ploc + (sq_softplus(ps[5 + nw + lane]) + 1e-2f) * gn[lane];
+      const float v = sq_prior_where_sample(a.cfg, rm, ps, nw, lane, gn[lane]);
       g[gen::WHERE + lane] = v;
       if (a.do_generate) rp[rec::WHERE + lane] = v;
     }
@@ -1176,6 +1186,110 @@ int sq_launch_generate_prop(const GenArgs& a, POff po, Dims d, hipStream_t s) {
 }
 int sq_launch_generate_disc(const GenArgs& a, POff po, Dims d, hipStream_t s) {
   SQ_LAUNCH(k_generate_disc, dim3(d.R), dim3(64), 0, s, a, po, d);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Forecast (sqair_forecast; ForecastArgs in sqair_glue.h): one generated frame with discovery empty.  One wavefront per (row, slot k):
+// lane j < N draws slot j's presence, a ballot gives the stable present-first destination of every slot (k_compact with the N
+// discovered slots all absent: they never reach the first N), then slot k's new record -- every word of it -- and its prior state go
+// to its destination.  (The N presences are drawn by each of the row's N wavefronts: a few loads, against a loop over the slots in
+// one wavefront whose dependent memory round trips made it the longest launch of a forecast frame, 11 us at cfg-2.)
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_forecast_step(const ForecastArgs a, const Dims d SQ_TLP) {
+  SQ_TL_SCOPE;
+  const int r = blockIdx.x, k = blockIdx.y, lane = threadIdx.x, N = d.N, nw = d.nw;
+  float lg = 0.0f, pres = 0.0f;
+  if (lane < N) {
+    const size_t rk = (size_t)r * N + lane;
+    lg = sq_prior_logit(a.cfg, a.rec_prev + rk * rec::W, a.pstats + rk * a.ps_ld);
+    pres = a.noise[(((size_t)r * 2 + 0) * N + lane) * d.nzw + 4 + nw] < sq_sigmoid(lg) ? 1.0f : 0.0f;
+  }
+  const unsigned long long all = (1ull << N) - 1ull;   // (N <= 16)
+  const unsigned long long present = __ballot(lane < N && pres != 0.0f) & all;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const int dst_l = (pres != 0.0f) ? __popcll(present & below) : __popcll(present) + __popcll(~present & all & below);
+  {
+    const size_t rk = (size_t)r * N + k;
+    const float* rm = a.rec_prev + rk * rec::W;
+    const float* ps = a.pstats + rk * a.ps_ld;
+    const float* gn = a.noise + (((size_t)r * 2 + 0) * N + k) * d.nzw;
+    const int dst = __shfl(dst_l, k);
+    const float lgk = __shfl(lg, k), pk = __shfl(pres, k);
+    const float id = rm[rec::ID] * pk - (1.0f - pk);   // compute_object_ids of a propagated slot
+    float* rn = a.rec_next + ((size_t)r * N + dst) * rec::W;
+    const size_t o = ((size_t)a.f * d.R + r) * N + dst;
+    for (int i = lane; i < rec::W; i += 64) {
+      float v = 0.0f;
+      if (i < 4) {
+        v = sq_prior_where_sample(a.cfg, rm, ps, nw, i, gn[i]);
+        if (a.out.where) a.out.where[o * 4 + i] = v;
+      } else if (i < rec::WHAT + nw) {
+        v = sq_prior_what_sample(a.cfg, rm, ps, nw, i - rec::WHAT, gn[i]);
+        if (a.out.what) a.out.what[o * nw + (i - rec::WHAT)] = v;
+      } else if (i == rec::PRES) {
+        v = pk;
+      } else if (i == rec::LOGIT) {
+        v = lgk;
+      } else if (i == rec::PROB) {
+        v = sq_sigmoid(lgk);
+      } else if (i == rec::ID) {
+        v = id;
+      }
+      rn[i] = v;
+    }
+    if (lane == 0) {
+      if (a.out.presence) a.out.presence[o] = pk;
+      if (a.out.presence_prob) a.out.presence_prob[o] = sq_sigmoid(lgk);
+      if (a.out.presence_logit) a.out.presence_logit[o] = lgk;
+      if (a.out.obj_id) a.out.obj_id[o] = id;
+    }
+    typedef float cf4 __attribute__((ext_vector_type(4)));
+    const cf4* src = reinterpret_cast<const cf4*>(a.prior_p + rk * d.psnh);
+    cf4* dstp = reinterpret_cast<cf4*>(a.prior_next + ((size_t)r * N + dst) * d.psnh);
+    for (int i = lane; i < d.psnh / 4; i += 64) dstp[i] = src[i];
+  }
+}
+int sq_launch_forecast_step(const ForecastArgs& a, Dims d, hipStream_t s) {
+  SQ_LAUNCH(k_forecast_step, dim3(d.R, d.N), dim3(64), 0, s, a, d);
+  return 0;
+}
+// Predictive summaries (ForecastSummaryArgs): workgroup (b, f).  Thread 0 turns the lane's log weights into w_k (max, exp, sum, divide,
+// each a loop in index order); a NaN or +inf weight, or all of them -inf, makes S -- and so every w_k -- NaN.
+__global__ __launch_bounds__(256) void k_forecast_summary(const ForecastSummaryArgs a, const Dims d SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ float s_w[SQ_MAX_K];
+  const int b = blockIdx.x, f = blockIdx.y, tid = threadIdx.x, K = d.K, N = d.N, P = d.H * d.W;
+  const size_t row0 = (size_t)f * d.R + (size_t)b * K;   // (frame f, particle 0 of lane b)
+  if (tid == 0) {
+    float m = a.log_w ? a.log_w[b * K] : 0.0f;
+    for (int k = 1; k < K; ++k) m = fmaxf(m, a.log_w ? a.log_w[b * K + k] : 0.0f);
+    float S = 0.0f;
+    for (int k = 0; k < K; ++k) {
+      const float e = expf((a.log_w ? a.log_w[b * K + k] : 0.0f) - m);
+      s_w[k] = e;
+      S += e;
+    }
+    float cnt = 0.0f;
+    for (int k = 0; k < K; ++k) {
+      const float w = s_w[k] / S;
+      s_w[k] = w;
+      float n = 0.0f;
+      for (int j = 0; j < N; ++j) n += a.rec[((row0 + k) * N + j) * rec::W + rec::PRES];
+      cnt += w * n;
+    }
+    if (a.expected_count) a.expected_count[(size_t)f * d.B + b] = cnt;
+  }
+  __syncthreads();
+  if (!a.mean_canvas) return;
+  for (int p = tid; p < P; p += 256) {
+    float acc = 0.0f;
+    for (int k = 0; k < K; ++k) acc += s_w[k] * a.canvas[(row0 + k) * P + p];
+    a.mean_canvas[((size_t)f * d.B + b) * P + p] = acc;
+  }
+}
+int sq_launch_forecast_summary(const ForecastSummaryArgs& a, Dims d, hipStream_t s) {
+  SQ_LAUNCH(k_forecast_summary, dim3(d.B, a.F), dim3(256), 0, s, a, d);
   return 0;
 }
 
@@ -1312,7 +1426,8 @@ int sq_launch_compact(const CompactArgs& a, POff po, Dims d, hipStream_t s) {
 // glimpses sit in LDS, the canvas is built band by band over the slots' boxes (sqair_canvas.h), then
 // every thread finishes its pixels of the band: the canvas is written at most once, the frame read once.
 // ------------------------------------------------------------------------------------------------
-template <int PF, int ROWS>
+// LL = false (forecast, sq_launch_insert_canvas): canvas only -- no frame, no likelihood, no scalar outputs.
+template <int PF, int ROWS, bool LL = true>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_insert_loglik(const InsertArgs a, const Dims d, const int band_rows SQ_TLP) {
   SQ_TL_SCOPE;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1325,7 +1440,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
   const size_t fs = (size_t)fr * d.R * N + (size_t)r * N;  // first slot of this (frame, row)
   const float* __restrict__ img = a.img + ((size_t)fr * d.B + b) * d.P4;
   const size_t frr = (size_t)fr * d.R + r;
-  const float qv = a.qz != nullptr ? a.qz[frr] : 0.0f, pv = a.qz != nullptr ? a.pz[frr] : 0.0f;  // requested early
+  const float qv = LL && a.qz != nullptr ? a.qz[frr] : 0.0f, pv = LL && a.qz != nullptr ? a.pz[frr] : 0.0f;  // requested early
   if (a.rec) sq_canvas_prologue(c, a.glimpse + fs * G2, a.rec + fs * a.rec_ld + rec::WHERE, a.rec_ld, a.rec + fs * a.rec_ld + rec::PRES, a.rec_ld, N, G, H, W);
   else sq_canvas_prologue(c, a.glimpse + fs * G2, a.where_plain + (size_t)r * N * 4, 4, a.pres_plain + (size_t)r * N, 1, N, G, H, W);
   float ll = 0.0f;
@@ -1343,7 +1458,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
 #pragma unroll
     for (int q = 0; q < PF; ++q) {
       const int p = tid + q * 256;
-      xv[q] = p < n ? img[pix0 + p] : 0.0f;
+      xv[q] = LL && p < n ? img[pix0 + p] : 0.0f;
       mv[q] = p < n ? a.mean_img[pix0 + p] : 0.0f;
     }
     sq_canvas_band<ROWS>(c, yb0, yb1, N, G, H, W);
@@ -1355,18 +1470,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
       if (p < n) {
         const float m = any_on ? sq_sigmoid(-10.0f + msv * 20.0f) : m_bg;
         const float cv = c.cv[p] + mv[q] * m;
-        if (one_sd) {
-          const float dd = (xv[q] - cv) * inv_sd;
-          ll += fmaf(-0.5f * dd, dd, lp0);
-        } else {
-          const float sd = m * a.std_fg + (1.0f - m) * a.std_bg;
-          ll += sq_normal_lp(xv[q], cv, sd);
+        if constexpr (LL) {
+          if (one_sd) {
+            const float dd = (xv[q] - cv) * inv_sd;
+            ll += fmaf(-0.5f * dd, dd, lp0);
+          } else {
+            const float sd = m * a.std_fg + (1.0f - m) * a.std_bg;
+            ll += sq_normal_lp(xv[q], cv, sd);
+          }
         }
         if (a.canvas) a.canvas[frr * P + pix0 + p] = cv;
       }
     }
     if (yb1 + 1 < H) __syncthreads();  // the next band clears c.cv / c.ms
   }
+  if constexpr (!LL) return;
   ll = sq_wave_sum(ll);
   if ((tid & 63) == 0) red_s[tid >> 6] = ll;
   __syncthreads();
@@ -1388,7 +1506,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
 // The same for frames wider than a wavefront, ROW-WAVE formulation (sqair_canvas.h): wave w owns rows w, w + 4, ...; lane l the
 // CPL adjacent columns from CPL l.  NMAX bounds the slots whose column taps a thread keeps in registers (3 NMAX CPL VGPRs); FULLW:
 // W == 64 CPL (vector loads of the frame, no column guards).
-template <int NMAX, int CPL, bool FULLW, bool ONE_SD, int WAVES, int PD>
+// LL = false: canvas only, as k_insert_loglik's
+template <int NMAX, int CPL, bool FULLW, bool ONE_SD, int WAVES, int PD, bool LL = true>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(SQ_ROWS_WPE(NMAX, CPL), 8))) void k_insert_loglik_rows(const InsertArgs a, const Dims d SQ_TLP) {
   SQ_TL_SCOPE;
   static_assert(CPL == 2 || CPL == 4, "column pairs");
@@ -1405,7 +1524,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(SQ_R
   const char* __restrict__ img = reinterpret_cast<const char*>(a.img + ((size_t)fr * d.B + b) * d.P4);
   const char* __restrict__ mean = reinterpret_cast<const char*>(a.mean_img);
   const size_t frr = (size_t)fr * d.R + r;
-  const float qv = a.qz != nullptr ? a.qz[frr] : 0.0f, pv = a.qz != nullptr ? a.pz[frr] : 0.0f;  // requested early
+  const float qv = LL && a.qz != nullptr ? a.qz[frr] : 0.0f, pv = LL && a.qz != nullptr ? a.pz[frr] : 0.0f;  // requested early
   // frame / mean-image values of a row: one 32-bit byte offset per lane on two scalar bases; PD rows in flight -- the ring slot of a
   // row is re-requested for the row PD trips ahead as soon as it has been read (a trip over a row no box meets is ~25 instructions:
   // one row ahead does not cover a memory round trip)
@@ -1415,17 +1534,20 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(SQ_R
     if (FULLW) {
       const unsigned off = (unsigned)(y * W * 4) + (unsigned)lane * (CPL * 4);
       if (CPL == 2) {
-        xn[u][0] = *reinterpret_cast<const sq_f2*>(img + off);
+        if constexpr (LL) xn[u][0] = *reinterpret_cast<const sq_f2*>(img + off);
         mn[u][0] = *reinterpret_cast<const sq_f2*>(mean + off);
-      } else {
+      } else if constexpr (LL) {
         const sq_f4 xx = *reinterpret_cast<const sq_f4*>(img + off), mm = *reinterpret_cast<const sq_f4*>(mean + off);
         xn[u][0] = xx.xy; xn[u][CP - 1] = xx.zw; mn[u][0] = mm.xy; mn[u][CP - 1] = mm.zw;
+      } else {
+        const sq_f4 mm = *reinterpret_cast<const sq_f4*>(mean + off);
+        mn[u][0] = mm.xy; mn[u][CP - 1] = mm.zw;
       }
     } else {
 #pragma unroll
       for (int q = 0; q < CP; ++q) {   // (clamped addresses, unconditional loads)
         const unsigned o0 = (unsigned)(y * W + min(lane * CPL + 2 * q, W - 1)) * 4, o1 = (unsigned)(y * W + min(lane * CPL + 2 * q + 1, W - 1)) * 4;
-        xn[u][q] = sq_f2{*reinterpret_cast<const float*>(img + o0), *reinterpret_cast<const float*>(img + o1)};
+        if constexpr (LL) xn[u][q] = sq_f2{*reinterpret_cast<const float*>(img + o0), *reinterpret_cast<const float*>(img + o1)};
         mn[u][q] = sq_f2{*reinterpret_cast<const float*>(mean + o0), *reinterpret_cast<const float*>(mean + o1)};
       }
     }
@@ -1466,7 +1588,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(SQ_R
     sq_f2 xv[CP], mv[CP], cvv[CP], mk[CP];
 #pragma unroll
     for (int q = 0; q < CP; ++q) {
-      xv[q] = xn[u][q];
+      if constexpr (LL) xv[q] = xn[u][q];
       mv[q] = mn[u][q];
     }
     const unsigned rm = __builtin_amdgcn_readfirstlane(rm_n);   // slots whose box meets this row (one LDS address for the wave)
@@ -1516,7 +1638,8 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(SQ_R
     }
 #pragma unroll
     for (int q = 0; q < CP; ++q) {
-      if (ONE_SD) {
+      if constexpr (!LL) {
+      } else if (ONE_SD) {
         sq_f2 df = xv[q] - cvv[q];
         if (!FULLW) df *= vw[q];
         ss = sq_fma2(df, df, ss);
@@ -1534,6 +1657,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(SQ_R
       }
     }
   }
+  if constexpr (!LL) return;
   if (ONE_SD) {   // sum over pixels of -0.5 ((x - c) / sd)^2 - log sd - log sqrt(2 pi)
     const float inv_sd = 1.0f / a.std_fg, lp0 = -logf(a.std_fg) - 0.91893853320467274178f;
     const int nrows = (H - wave + WAVES - 1) / WAVES;
@@ -1567,43 +1691,47 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(SQ_R
 #ifndef SQ_ROWS_PD
 #define SQ_ROWS_PD 1      // rows of frame / mean-image values in flight per wave
 #endif
-template <int NMAX, int CPL, bool FULLW, bool ONE_SD>
+template <int NMAX, int CPL, bool FULLW, bool ONE_SD, bool LL>
 static int launch_insert_rows2(const InsertArgs& a, const Dims& d, dim3 grid, hipStream_t s) {
   constexpr int WAVES = SQ_ROWS_WAVES, PD = SQ_ROWS_PD;
   const size_t shm = sq_canvas_rows_lds_floats(d.N, d.G, d.H) * sizeof(float);
-  if (shm > 48 * 1024 && sq_allow_big_lds((const void*)k_insert_loglik_rows<NMAX, CPL, FULLW, ONE_SD, WAVES, PD>, 150 * 1024) != 0) return -2;
-  SQ_LAUNCH((k_insert_loglik_rows<NMAX, CPL, FULLW, ONE_SD, WAVES, PD>), grid, dim3(64 * WAVES), shm, s, a, d);
+  if (shm > 48 * 1024 && sq_allow_big_lds((const void*)k_insert_loglik_rows<NMAX, CPL, FULLW, ONE_SD, WAVES, PD, LL>, 150 * 1024) != 0) return -2;
+  SQ_LAUNCH((k_insert_loglik_rows<NMAX, CPL, FULLW, ONE_SD, WAVES, PD, LL>), grid, dim3(64 * WAVES), shm, s, a, d);
   return 0;
 }
-template <int NMAX, int CPL>
+template <int NMAX, int CPL, bool LL>
 static int launch_insert_rows(const InsertArgs& a, const Dims& d, dim3 grid, hipStream_t s) {
   // vector loads of a row: W == 64 CPL, and rows / frames that start on the vector's alignment (the parameter buffer's mean image
   // is only float-aligned in general)
   const size_t al = (size_t)CPL * 4 - 1;
   const bool fullw = d.W == 64 * CPL && (((size_t)a.img | (size_t)a.mean_img | (size_t)a.canvas) & al) == 0 && (d.P4 * 4 & al) == 0;
+  if (!LL) return fullw ? launch_insert_rows2<NMAX, CPL, true, true, false>(a, d, grid, s) : launch_insert_rows2<NMAX, CPL, false, true, false>(a, d, grid, s);
   const bool one_sd = a.std_fg == a.std_bg;
-  if (fullw) return one_sd ? launch_insert_rows2<NMAX, CPL, true, true>(a, d, grid, s) : launch_insert_rows2<NMAX, CPL, true, false>(a, d, grid, s);
-  return one_sd ? launch_insert_rows2<NMAX, CPL, false, true>(a, d, grid, s) : launch_insert_rows2<NMAX, CPL, false, false>(a, d, grid, s);
+  if (fullw) return one_sd ? launch_insert_rows2<NMAX, CPL, true, true, true>(a, d, grid, s) : launch_insert_rows2<NMAX, CPL, true, false, true>(a, d, grid, s);
+  return one_sd ? launch_insert_rows2<NMAX, CPL, false, true, true>(a, d, grid, s) : launch_insert_rows2<NMAX, CPL, false, false, true>(a, d, grid, s);
 }
-int sq_launch_insert_loglik(const InsertArgs& a, Dims d, hipStream_t s) {
+template <bool LL>
+static int launch_insert(const InsertArgs& a, Dims d, hipStream_t s) {
   const bool wide = d.W > SQ_CANVAS_WIDE;
   const int band_rows = sq_canvas_band_rows(d.H, d.W, wide ? SQ_CANVAS_PF_FWD_W : SQ_CANVAS_PF_FWD);
   const size_t shm = sq_canvas_lds_floats(d.N, d.G, d.H, d.W, band_rows) * sizeof(float);
   const dim3 grid(d.R, a.n_frames > 0 ? a.n_frames : 1);
   // frames of 65 .. 256 columns with up to 8 slots: the row-wave kernel (cfg-5: 89 -> see DESIGN); everything else in bands
   if (wide && d.W <= 256 && d.N <= 8 && d.G >= 2 && d.G <= 20 && sq_canvas_rows_lds_floats(d.N, d.G, d.H) * sizeof(float) <= 150 * 1024) {
-    if (d.W <= 128) return d.N <= 4 ? launch_insert_rows<4, 2>(a, d, grid, s) : launch_insert_rows<8, 2>(a, d, grid, s);
-    return d.N <= 4 ? launch_insert_rows<4, 4>(a, d, grid, s) : launch_insert_rows<8, 4>(a, d, grid, s);
+    if (d.W <= 128) return d.N <= 4 ? launch_insert_rows<4, 2, LL>(a, d, grid, s) : launch_insert_rows<8, 2, LL>(a, d, grid, s);
+    return d.N <= 4 ? launch_insert_rows<4, 4, LL>(a, d, grid, s) : launch_insert_rows<8, 4, LL>(a, d, grid, s);
   }
   if (wide) {
-    if (shm > 48 * 1024 && sq_allow_big_lds((const void*)k_insert_loglik<SQ_CANVAS_PF_FWD_W, SQ_CANVAS_ROWS_FWD_W>, 150 * 1024) != 0) return -2;
-    SQ_LAUNCH((k_insert_loglik<SQ_CANVAS_PF_FWD_W, SQ_CANVAS_ROWS_FWD_W>), grid, dim3(256), shm, s, a, d, band_rows);
+    if (shm > 48 * 1024 && sq_allow_big_lds((const void*)k_insert_loglik<SQ_CANVAS_PF_FWD_W, SQ_CANVAS_ROWS_FWD_W, LL>, 150 * 1024) != 0) return -2;
+    SQ_LAUNCH((k_insert_loglik<SQ_CANVAS_PF_FWD_W, SQ_CANVAS_ROWS_FWD_W, LL>), grid, dim3(256), shm, s, a, d, band_rows);
   } else {
-    if (shm > 48 * 1024 && sq_allow_big_lds((const void*)k_insert_loglik<SQ_CANVAS_PF_FWD, SQ_CANVAS_ROWS_FWD>, 150 * 1024) != 0) return -2;
-    SQ_LAUNCH((k_insert_loglik<SQ_CANVAS_PF_FWD, SQ_CANVAS_ROWS_FWD>), grid, dim3(256), shm, s, a, d, band_rows);
+    if (shm > 48 * 1024 && sq_allow_big_lds((const void*)k_insert_loglik<SQ_CANVAS_PF_FWD, SQ_CANVAS_ROWS_FWD, LL>, 150 * 1024) != 0) return -2;
+    SQ_LAUNCH((k_insert_loglik<SQ_CANVAS_PF_FWD, SQ_CANVAS_ROWS_FWD, LL>), grid, dim3(256), shm, s, a, d, band_rows);
   }
   return 0;
 }
+int sq_launch_insert_loglik(const InsertArgs& a, Dims d, hipStream_t s) { return launch_insert<true>(a, d, s); }
+int sq_launch_insert_canvas(const InsertArgs& a, Dims d, hipStream_t s) { return launch_insert<false>(a, d, s); }
 
 // ------------------------------------------------------------------------------------------------
 // IWAE / VIMCO reductions over [T, B, K] in one launch (reference: sqair/model.py:88-103,:150-158,

@@ -21,6 +21,12 @@ counter).  ``log_weight_sum`` is then the device accumulator of each row's log w
 there; the evidence banked at resamplings is ``log_z``), and ``step()`` adds ``ess``, ``resampled``, ``log_evidence`` (the SMC
 estimate of log p(x_1..t) per lane) and ``ancestors`` (the source map of the next step) to its outputs.
 
+``forecast(F)`` answers the tracker's next question -- where will the objects be, what will the next frames look like: it rolls the
+generative prior F frames forward from the rows the next ``step()`` would start from (include/sqair_hip.h: sqair_forecast), with
+discovery empty, and renders every frame.  Per particle it returns the sampled objects and the decoder's canvas; per lane the
+predictive mean canvas and expected object count under the particles' weights.  It writes nothing the steps read: forecasting
+between steps leaves every step's results unchanged.
+
 The stream takes over its core's handle: while it is open, every inference pass of that handle carries the state.  ``close()``
 hands the handle back.
 """
@@ -34,6 +40,9 @@ import torch
 from sqair_amd import _capi
 
 DEFAULT_OUTPUTS = ("what", "where", "presence", "obj_id", "log_weights_per_timestep")
+FORECAST_OUTPUTS = ("what", "where", "presence", "presence_prob", "presence_logit", "obj_id", "canvas", "glimpse")
+# Philox step key of the default forecast noise: the top bit set, the frames consumed below it -- never a step's key (its frame index)
+FORECAST_NOISE_TAG = 1 << 63
 
 
 class SqairStream(object):
@@ -79,6 +88,7 @@ class SqairStream(object):
         # host-side source map of the next step (None: identity); first: all fresh.  SMC composes maps on the device instead.
         self._armed = None if self.smc else np.full(self.R, -1, dtype=np.int64)
         self._graph = False
+        self._fc = {}               # forecast buffers of the LAST (F, outputs, summaries) only: workspace, noise, map, weights, outputs
         self._smc_uniforms = None   # registered with the caller's uniforms (True) or Philox (False)
         core.stream.synchronize()
         core.check(lib.sqair_set_state(core.handle, self.state.data_ptr(), self.state.data_ptr(), self._src.data_ptr(),
@@ -214,6 +224,85 @@ class SqairStream(object):
             core._join_out()
         self.frame += self.T
         return out
+
+    # ---- forecasting ------------------------------------------------------------------------------------------------------
+    def forecast(self, F, noise=None, seed=None, outputs=FORECAST_OUTPUTS, summaries=True):
+        """Rolls the generative prior F frames forward from the rows the next ``step()`` would start from -- the state blob through
+        the pending source map (a reset or resample armed since the last step, else identity; with SMC the map the resampler
+        wrote) -- and returns {name: [F, B*K, ...]} for ``outputs`` (of FORECAST_OUTPUTS).  With ``summaries`` also the lanes'
+        predictive ``mean_canvas`` [F, B, H, W] and ``expected_count`` [F, B] under the particle weights, and those normalised
+        ``weights`` [B, K] (softmax of each lane's running log-weight sums, gathered through the same map).  ``noise``
+        [F, B*K, 2, N, 4 + n_what + 1] (slot s = 0 is read); default: the library's Philox keyed by (``seed`` or the stream's
+        seed, FORECAST_NOISE_TAG | frames consumed), apart from every step's draws.  Copies, valid on the current stream.  Nothing
+        the steps read is written.  The stream keeps one set of forecast buffers (workspace, noise, outputs), for the last
+        (F, outputs, summaries) asked for: repeating a shape reuses them, another shape frees them and allocates its own."""
+        F = int(F)
+        if F < 1:
+            raise ValueError("SqairStream.forecast: F must be >= 1")
+        outputs = tuple(outputs)
+        bad = [n for n in outputs if n not in FORECAST_OUTPUTS]
+        if bad:
+            raise ValueError("SqairStream.forecast: unknown outputs {} (choose from {})".format(bad, FORECAST_OUTPUTS))
+        core = self.core
+        lib, dev = core.lib, core.device
+        R, N, nzw = self.R, core.N, core.nzw
+        if noise is not None:
+            noise = torch.as_tensor(noise, dtype=torch.float32)
+            if noise.numel() != F * R * 2 * N * nzw:
+                raise ValueError("SqairStream.forecast: noise of shape {} given, [{}, {}, 2, {}, {}] expected".format(
+                    tuple(noise.shape), F, R, N, nzw))
+        key = (F, outputs, bool(summaries))
+        with torch.cuda.device(dev):
+            core._join_in()
+            with core.on_stream():
+                fc = self._fc.get(key)
+                if fc is None:   # (another shape: the previous buffers are released first -- a growing horizon does not pile up)
+                    self._fc.clear()
+                    fc = self._forecast_buffers(F, outputs, summaries)
+                    self._fc[key] = fc
+                if noise is not None:
+                    fc["noise"].copy_(noise.reshape(fc["noise"].shape), non_blocking=True)
+                else:
+                    core.check(lib.sqair_fill_noise(core.handle, fc["noise"].data_ptr(), F, self.B, self.B, 0,
+                                                    (self.seed if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF,
+                                                    FORECAST_NOISE_TAG | self.frame, core._stream()), "sqair_fill_noise")
+                if self.smc:   # (the resampler's map and weights are already indexed by next-step rows)
+                    src, lw = self._src, self.log_weight_sum
+                else:          # the pending host-side map, uploaded into the forecast's own buffer; the weights follow it
+                    m = self._pending()
+                    src = fc["src"]
+                    src.copy_(torch.as_tensor(m.astype(np.int32)), non_blocking=True)
+                    keep = src >= 0
+                    lw = fc["log_w"]
+                    lw.copy_(torch.where(keep, self.log_weight_sum[src.long().clamp_min(0)], torch.zeros_like(lw)))
+                out = fc["out"]
+                c_out = _capi.SqairForecastOutputs(**{n: t.data_ptr() for n, t in out.items()})
+                if summaries:
+                    c_out.log_w = lw.data_ptr()
+                core.check(lib.sqair_forecast(core.handle, core.flat.data_ptr(), core.packed.data_ptr(), fc["noise"].data_ptr(), F,
+                                              self.B, src.data_ptr(), C.byref(c_out), fc["ws"].data_ptr(), fc["ws"].numel() * 4,
+                                              core._stream()), "sqair_forecast")
+                res = {k: v.clone() for k, v in out.items()}
+                if summaries:
+                    res["weights"] = torch.softmax(lw.reshape(self.B, self.K), -1)
+            core._join_out()
+        return res
+
+    def _forecast_buffers(self, F, outputs, summaries):
+        core = self.core
+        R, N, B = self.R, core.N, self.B
+        shapes = dict(what=(F, R, N, core.nw), where=(F, R, N, 4), presence=(F, R, N), presence_prob=(F, R, N),
+                      presence_logit=(F, R, N), obj_id=(F, R, N), canvas=(F, R, core.H, core.W),
+                      glimpse=(F, R, N, core.G, core.G))
+        if summaries:
+            shapes.update(mean_canvas=(F, B, core.H, core.W), expected_count=(F, B))
+            outputs = outputs + ("mean_canvas", "expected_count")
+        z = lambda shp, dt=torch.float32: torch.zeros(shp, dtype=dt, device=core.device)
+        nb = core.lib.sqair_forecast_workspace_bytes(core.handle, F, B)
+        if nb < 0:
+            raise RuntimeError("sqair_forecast_workspace_bytes failed")
+        return dict(ws=z(nb // 4), noise=z((F, R, 2, N, core.nzw)), src=z(R, torch.int32), log_w=z(R),
+                    out={n: z(shapes[n]) for n in outputs})
 
     def close(self):
         """Switches the carried state off on the core's handle (its passes start from the initial state again)."""
