@@ -196,7 +196,8 @@ int sqair_graph_nodes(const SqairHandle* h); /* kernel nodes in the captured gra
  *              starts row r fresh (counter 0).  Resets lanes, resamples particles (src[b*K + k] = b*K + k'), recomposes a
  *              batch.  NULL = identity.  Needs state_in.
  * All three NULL switches the state off.  Pointers are remembered by the handle and frozen into captured graphs.  Refused
- * (return -1, text in sqair_last_error, before any HIP call): sqair_forward_train / sqair_backward while a state is set, a
+ * (return -1, text in sqair_last_error, before any HIP call): sqair_forward_train / sqair_backward while a state is set (training
+ * with a carried state has its own calls, sqair_forward_train_carry / sqair_backward_carry, below), a
  * configuration with sample_from_prior, t_offset != 0 with state_in set, a pass whose B is not the B given here, and
  * state_bytes < sqair_state_bytes(h, B). */
 int64_t sqair_state_bytes(const SqairHandle* h, int B);
@@ -362,6 +363,43 @@ int sqair_backward(SqairHandle* h, const float* flat_params, const void* packed,
                    const float* importance_weights, const float* vimco_signal, int T, int B, int t_offset,
                    void* train_workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes,
                    float* flat_grad, void* stream);
+
+/* ---- training with a carried state (truncated BPTT over a stream) -------------------------------------------------------
+ * A carried training chunk is T' frames of B lanes that start from a state blob (the blob of sqair_set_state) instead of the
+ * trainable initial state.  Row r starts from
+ *   blob row src_rows[r] when state_in is set and src_rows[r] >= 0 (identity without src_rows): held CONSTANT -- no gradient
+ *     flows into it, as with the noise -- and its frame counter is the blob's;
+ *   the trainable initial state otherwise (src_rows[r] = -1 or outside [-1, B*K), or state_in NULL), counter 0: gradient
+ *     flows into seq.temporal_init(_c) / seq.prior_init(_c) as in sqair_backward.
+ * The frames run exactly as a pass does; the categorical step prior's t is the row's counter plus the frame index.  The target
+ * is the one of sqair_elbo on [T', B*K] unchanged: VIMCO over the chunk's own log weights and discrete log-probs, / T'.  Log
+ * weights of earlier chunks are NOT part of it.  sqair_backward_carry returns d target / d theta with the imported rows held
+ * constant.  After the forward, frame T''s state (records, cell states, ids, counters) goes to state_out, exactly as an
+ * inference pass exports it, so that a video trained chunk by chunk carries identities and counters from chunk to chunk.
+ * The backward reads neither the blob nor src_rows: the forward records in the training workspace which rows it imported and
+ * their counters (the resampler may already have rewritten src_rows for the next chunk).
+ * SMC at chunk boundaries: with `smc` set the forward ends with the resampler of sqair_set_smc, after the export.  Only
+ * ess_frac == 1 (resample every lane at every boundary, so that the carried weights are zero and leaving them out of the
+ * target is exact); the elbo_iwae of sqair_elbo summed over the chunks of a lane is then its log_evidence (a FIVO bound).
+ * Refused (return -1, text in sqair_last_error, before any HIP call): a NULL carry, a B other than carry->B, state_bytes <
+ * sqair_state_bytes(h, B), src_rows without state_in, a handle with sqair_set_state on, sample_from_prior, frames too large to
+ * train, an smc with ess_frac != 1 (the adaptive target is not supported), a NULL SMC buffer or smc->src_rows != src_rows, an smc
+ * with out->log_weights_per_timestep NULL.  Both calls are capturable (sqair_capture_begin / _end); pointers are frozen. */
+typedef struct {
+  const void* state_in;      /* blob to import from; NULL: every row fresh */
+  void* state_out;           /* blob to export frame T' into; NULL: no export; may equal state_in */
+  const int32_t* src_rows;   /* [B*K] device; NULL = identity; -1 (or out of range) = fresh */
+  int64_t state_bytes;       /* >= sqair_state_bytes(h, B) */
+  int32_t B;
+  const SqairSmc* smc;       /* optional: resample at the end of the forward; ess_frac must be 1, smc->src_rows == src_rows */
+} SqairCarry;
+int sqair_forward_train_carry(SqairHandle* h, const float* flat_params, const void* packed, const float* obs, const float* noise,
+                              int T, int B, const SqairCarry* carry, const SqairOutputs* out, void* train_workspace,
+                              int64_t workspace_bytes, void* stream);
+int sqair_backward_carry(SqairHandle* h, const float* flat_params, const void* packed, const float* obs, const float* noise,
+                         const float* importance_weights, const float* vimco_signal, int T, int B, const SqairCarry* carry,
+                         void* train_workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes,
+                         float* flat_grad, void* stream);
 
 /* ---- workspace clearing.  By default every pass starts by zero-filling the caller's workspace (60 MB for inference,
  * 308 MB for the training tape at BASELINE configs[1]: ~1-2 % of a step), so that a workspace may hold garbage and may be

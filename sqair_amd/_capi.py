@@ -50,6 +50,14 @@ class SqairSmc(C.Structure):
     ]
 
 
+class SqairCarry(C.Structure):
+    """A carried training chunk (include/sqair_hip.h: sqair_forward_train_carry / sqair_backward_carry); device addresses."""
+    _fields_ = [
+        ("state_in", C.c_void_p), ("state_out", C.c_void_p), ("src_rows", C.c_void_p), ("state_bytes", C.c_int64),
+        ("B", C.c_int32), ("smc", C.POINTER(SqairSmc)),
+    ]
+
+
 class SqairForecastOutputs(C.Structure):
     """Outputs of sqair_forecast (include/sqair_hip.h); every pointer is a device address or None."""
     _fields_ = [(n, C.c_void_p) for n in ("what", "where", "presence", "presence_prob", "presence_logit", "obj_id", "canvas", "glimpse",
@@ -115,6 +123,10 @@ _PROTOS = {
     "sqair_backward_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
     "sqair_backward": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                  C.c_void_p, C.c_void_p]),
+    "sqair_forward_train_carry": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.POINTER(SqairCarry), C.POINTER(SqairOutputs),
+                                                                C.c_void_p, C.c_int64, C.c_void_p]),
+    "sqair_backward_carry": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.POINTER(SqairCarry), C.c_void_p, C.c_int64,
+                                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "sqair_set_generation_noise": (C.c_int, [C.c_void_p, C.c_void_p]),
     "sqair_state_bytes": (C.c_int64, [C.c_void_p, C.c_int]),
     "sqair_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),

@@ -823,6 +823,7 @@ Workspace sq_carve(const SqairHandle* h, int T, int B, float* base, bool train) 
     w.obs_p = take(P4 != P_ ? (int64_t)T * B * P4 + 16 : 64);   // (+16: the last K chunk of the input encoder may read past the row)
   }
   w.t_row = (int*)take(R);
+  w.fresh = train ? take(M) : nullptr;   // (training with a carried state; inference workspaces keep their size)
   w.clear_n = o;   // a workspace clear covers every buffer above; the chain's control blocks below are sq_chain_poison's
   w.chain_ctl = (unsigned*)take(w.chain ? (int64_t)SQ_CHAIN_MAX_LAUNCHES * SQ_CHAIN_CTL_WORDS : 64);
   w.total = o;
@@ -929,6 +930,31 @@ extern "C" int sqair_smc_resample_test(SqairHandle* h, const float* lw, int T, i
   a.seed = smc->seed; a.ess_frac = smc->ess_frac; a.T = T; a.B = B; a.K = K;
   sq_launch_smc_resample(a, (hipStream_t)stream);
   SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+// the refusals of a carried training call (host only: before any HIP call)
+int sq_carry_refusal(SqairHandle* h, const char* fn, int B, const SqairCarry* carry, const SqairOutputs* out) {
+  const std::string f = std::string(fn) + ": ";
+  auto no = [&](const std::string& why) { sq_set_error(h, f + why); return -1; };
+  if (!carry) return no("a NULL carry (SqairCarry)");
+  if (B != carry->B) return no("B = " + std::to_string(B) + " but the carry is for B = " + std::to_string(carry->B));
+  if (B < 1 || carry->state_bytes < sqair_state_bytes(h, B))
+    return no("state_bytes " + std::to_string(carry->state_bytes) + " < sqair_state_bytes(h, " + std::to_string(B) + ") = " +
+              std::to_string(B < 1 ? -1 : sqair_state_bytes(h, B)));
+  if (carry->src_rows && !carry->state_in) return no("a source map needs state_in");
+  if (h->state_on) return no("the handle carries an inference state (sqair_set_state): switch it off before training with a carry");
+  if (h->cfg.sample_from_prior) return no("a carried state does not combine with sample_from_prior");
+  if (!sq_trainable_frame(h)) return -1;
+  if (const SqairSmc* m = carry->smc) {
+    if (m->ess_frac != 1.0f)
+      return no("SMC at chunk boundaries needs ess_frac == 1: adaptive resampling (carried weights inside the target) is not "
+                "supported by training");
+    if (!m->log_w || !m->log_z || !m->log_evidence || !m->ess || !m->resampled || !m->src_rows)
+      return no("the SMC buffers log_w, log_z, log_evidence, ess, resampled and src_rows must not be NULL");
+    if (m->src_rows != carry->src_rows) return no("smc->src_rows must be the carry's src_rows");
+    if (out && !out->log_weights_per_timestep)
+      return no("SMC resamples on log_weights_per_timestep: a carried step with SMC must bind that output");
+  }
   return 0;
 }
 // the refusals of a pass with a carried state (host only: before any HIP call)
@@ -1094,29 +1120,46 @@ struct SlotPhase {
   bool fuse;                          // the slot's tail rides in the next slot's VanillaRNN launch (k_rnn_tail)
 };
 
+// The carried-state settings of one pass, resolved once: the handle's (sqair_set_state / sqair_set_smc: inference passes) or
+// a carried training call's (SqairCarry).  `fresh`: k_state_import records each row's fresh / imported flag for the backward.
+struct SqStateRes {
+  bool on;
+  const void* in; void* out; const int32_t* src;
+  bool fresh;
+  bool smc_on; SqairSmc smc;
+};
+static SqStateRes sq_handle_state(const SqairHandle* h) {
+  return SqStateRes{h->state_on, h->state_in, h->state_out, h->state_src, false, h->smc_on, h->smc};
+}
+static SqStateRes sq_carry_state(const SqairCarry* c) {
+  return SqStateRes{true, c->state_in, c->state_out, c->src_rows, true, c->smc != nullptr, c->smc ? *c->smc : SqairSmc{}};
+}
 // the carried state's rows of frame t of a pass (k_state_import: t = 0, k_state_export: t = T)
-static StateArgs state_args(const SqairHandle* h, const Workspace& w, int t, int t0) {
+static StateArgs state_args(const SqairHandle* h, const SqStateRes& st, const Workspace& w, int t, int t0) {
   StateArgs a; memset(&a, 0, sizeof(a));
   a.rec = w.rec_m_all + (size_t)t * w.M * rec::W;
   a.temporal = w.state(w.temporal_m, t, w.snh);
   a.prior = w.state(w.prior_m, t, w.psnh);
   a.last_id = w.last_id[t & 1];
   a.t_row = w.t_row;
-  a.blob_in = (const float*)h->state_in;
-  a.blob_out = (float*)h->state_out;
-  a.src = h->state_src;
+  a.fresh = st.fresh && t == 0 ? w.fresh : nullptr;
+  a.blob_in = (const float*)st.in;
+  a.blob_out = (float*)st.out;
+  a.src = st.src;
   a.R = w.R; a.n_rec = w.N * rec::W; a.n_tmp = w.N * w.snh; a.n_pri = w.N * w.psnh; a.row_words = (int)sq_state_row_floats(h);
   a.t0 = t0;
   return a;
 }
 
 // parts: 1 = prologue (workspace clear, initial state, input encoder), 2 = the frame loop, 4 = epilogue (log-probabilities,
-// decoder, final state copies).
+// decoder, final state copies).  carry: the settings of a carried training call (refused or not by its entry point); NULL =
+// the handle's carried state, if any.
 int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, const float* obs, const float* noise,
                     int T, int B, int t_offset, const SqairOutputs* outp, float* wsbase, int64_t ws_bytes,
-                    hipStream_t s, bool train, int parts) {
+                    hipStream_t s, bool train, int parts, const SqStateRes* carry = nullptr) {
   const SqairConfig& c = h->cfg;
-  if (sq_state_refusal(h, train, B, t_offset) != 0 || sq_smc_refusal(h, outp) != 0) return -1;
+  if (!carry && (sq_state_refusal(h, train, B, t_offset) != 0 || sq_smc_refusal(h, outp) != 0)) return -1;
+  const SqStateRes st = carry ? *carry : sq_handle_state(h);
   if (!flat || !packed || !obs || !noise || !outp || !wsbase || T < 1 || B < 1) {
     sq_set_error(h, "sqair_forward: null argument or bad T/B");
     return -1;
@@ -1162,7 +1205,7 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
                          w.prop_rnn_init, w.disc_rnn_init, w.rn_init_state, w.w3_prop, w.w3_disc,
                          (int)P(h, "prop.transform.l2.w"), (int)P(h, "disc.transform.l2.w"), flat, po, d, s);
     // carried state (sqair_set_state): frame 0's records / states / last_id of each row from the caller's blob, and its counter
-    if (h->state_on) sq_launch_state_import(state_args(h, w, 0, t_offset), s);
+    if (st.on) sq_launch_state_import(state_args(h, st, w, 0, t_offset), s);
     if (w.chain) {
       // hand-off words of the chain launches of this pass -> sentinel; their control blocks -> zero (one launch)
       ChainPoisonList pl; memset(&pl, 0, sizeof(pl));
@@ -1462,7 +1505,7 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
     la.rec_p = w.rec_p_all; la.rec_d = w.rec_d_all; la.rec_prev = w.rec_m_all; la.pstats = w.pstats; la.ps_ld = PS_LD;
     la.spre = w.spre; la.flat = flat; la.t_global = t_offset; la.t = 0; la.n_frames = T; la.qz = w.qz; la.pz = w.pz;
     la.disc_lp = w.dlp; la.out = out; la.cfg = c; la.gen = c.sample_from_prior ? w.gen : nullptr;
-    la.t_row = h->state_on ? w.t_row : nullptr;   // (carried state: each row's own frame index)
+    la.t_row = st.on ? w.t_row : nullptr;   // (carried state: each row's own frame index)
     if (sq_launch_logprob(la, po, d, s) != 0) { sq_set_error(h, "sqair_forward: the log-probability launch failed (dynamic LDS limit)"); return -2; }
   }
   // ---- J. decoder of all T frames as three M = T*B'*N row GEMMs + one insert / log-likelihood launch
@@ -1494,14 +1537,14 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
   if (out.final_last_used_id)
     sq_copy(out.final_last_used_id, w.last_id[T & 1], (int64_t)R, s);
   // carried state: frame T's rows into the caller's blob (after every reader of the imported rows: in place is fine)
-  if (h->state_on && h->state_out) sq_launch_state_export(state_args(h, w, T, T), s);
-  // SMC: this pass's log weights -> ESS, evidence and the next pass's source map (sqair_set_smc)
-  if (h->smc_on) {
+  if (st.on && st.out) sq_launch_state_export(state_args(h, st, w, T, T), s);
+  // SMC: this pass's log weights -> ESS, evidence and the next pass's source map (sqair_set_smc / SqairCarry.smc)
+  if (st.smc_on) {
     SmcArgs a; memset(&a, 0, sizeof(a));
-    a.lw = out.log_weights_per_timestep; a.t_row = w.t_row; a.uniforms = h->smc.uniforms;
-    a.log_w = h->smc.log_w; a.log_z = h->smc.log_z; a.log_evidence = h->smc.log_evidence; a.ess = h->smc.ess;
-    a.u_out = h->smc.u_out; a.resampled = h->smc.resampled; a.src = h->smc.src_rows;
-    a.seed = h->smc.seed; a.ess_frac = h->smc.ess_frac; a.T = T; a.B = B; a.K = K;
+    a.lw = out.log_weights_per_timestep; a.t_row = w.t_row; a.uniforms = st.smc.uniforms;
+    a.log_w = st.smc.log_w; a.log_z = st.smc.log_z; a.log_evidence = st.smc.log_evidence; a.ess = st.smc.ess;
+    a.u_out = st.smc.u_out; a.resampled = st.smc.resampled; a.src = st.smc.src_rows;
+    a.seed = st.smc.seed; a.ess_frac = st.smc.ess_frac; a.T = T; a.B = B; a.K = K;
     sq_launch_smc_resample(a, s);
   }
   SQ_CHECK_HIP(hipGetLastError());
@@ -1533,6 +1576,22 @@ extern "C" int sqair_forward_train(SqairHandle* h, const float* flat_params, con
   if (!sq_trainable_frame(h)) return -1;
   return sq_forward_impl(h, flat_params, (const float*)packed, obs, noise, T, B, t_offset, out, (float*)workspace,
                          workspace_bytes, (hipStream_t)stream, true, 7);
+}
+// Training forward of a carried chunk (include/sqair_hip.h: SqairCarry): the pass of sqair_forward_train with the state import /
+// export / SMC settings of the carry instead of the handle's; every row's counter and fresh / imported flag stay in the workspace
+// for sqair_backward_carry.
+extern "C" int sqair_forward_train_carry(SqairHandle* h, const float* flat_params, const void* packed, const float* obs,
+                                         const float* noise, int T, int B, const SqairCarry* carry, const SqairOutputs* out,
+                                         void* train_workspace, int64_t workspace_bytes, void* stream) {
+  if (!h) return -1;
+  if (sq_carry_refusal(h, "sqair_forward_train_carry", B, carry, out) != 0) return -1;
+  if (!out) {
+    sq_set_error(h, "sqair_forward_train_carry: null argument");
+    return -1;
+  }
+  const SqStateRes st = sq_carry_state(carry);
+  return sq_forward_impl(h, flat_params, (const float*)packed, obs, noise, T, B, 0, out, (float*)train_workspace, workspace_bytes,
+                         (hipStream_t)stream, true, 7, &st);
 }
 
 // ------------------------------------------------------------------------------------------------

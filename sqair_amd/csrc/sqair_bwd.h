@@ -11,6 +11,7 @@ struct LogprobBwdArgs {
   float* d_spre;                                                 // [T][R][128] (written)
   const float* flat; float* flat_grad;
   int t_global0;
+  const int* t_row;                                              // [R] each row's frame counter (carried state), or NULL: t_global0
   SqairConfig cfg;
 };
 

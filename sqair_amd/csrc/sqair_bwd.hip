@@ -1318,7 +1318,7 @@ __global__ __launch_bounds__(256) void k_logprob_bwd(const LogprobBwdArgs a, con
   __syncthreads();
   const float* flat = fl;
   float* fg = gl;
-  const int t_global = a.t_global0 + fr;
+  const int t_global = (a.t_row != nullptr ? a.t_row[r] : a.t_global0) + fr;   // (k_logprob's rule)
   // ---------------- forward quantities needed below: lane k holds the prior logit of slot k; e_sum
   float pl_k = 0.0f, e_sum;
   {

@@ -185,6 +185,7 @@ struct StateArgs {
   float* prior;                // [R][N][psnh]
   float* last_id;              // [R]
   int* t_row;                  // [R] frame counter of each row at frame 0 of the pass
+  float* fresh;                // import, training with a carried state: [R][N] 1 = the row starts fresh, 0 = imported; or NULL
   const float* blob_in;        // import: NULL = every row fresh
   float* blob_out;             // export
   const int* src;              // import: source row of each row, -1 (or out of [-1, R)) = fresh; NULL = identity

@@ -97,6 +97,9 @@ __global__ __launch_bounds__(256) void k_state_import(const StateArgs a SQ_TLP) 
   const int r = blockIdx.x, tid = threadIdx.x;
   int sr = a.blob_in == nullptr ? -1 : (a.src != nullptr ? a.src[r] : r);
   if (sr < -1 || sr >= a.R) sr = -1;   // (never read outside the blob: an index out of range starts the row fresh)
+  // training with a carried state: the row's slots weigh the initial-state gradient with 1 (fresh) or 0 (imported, constant)
+  const int N = a.n_rec / rec::W;
+  if (a.fresh != nullptr && tid < N) a.fresh[(size_t)r * N + tid] = sr < 0 ? 1.0f : 0.0f;
   if (sr < 0) {                        // fresh: keep what k_init_state wrote
     if (tid == 0) a.t_row[r] = a.t0;
     return;

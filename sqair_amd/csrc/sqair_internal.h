@@ -91,6 +91,9 @@ struct SqairHandle {
 inline int64_t align64(int64_t x) { return (x + 63) / 64 * 64; }
 constexpr int64_t SQ_TRAIN_MAX_FRAME_BYTES = 150 * 1024;   // dynamic LDS the crop adjoint may ask for (sq_allow_big_lds)
 int sq_state_refusal(SqairHandle* h, bool train, int B, int t_offset);   // -1 + error text: a pass a carried state rules out
+// -1 + error text: a carried training call (sqair_forward_train_carry / sqair_backward_carry) that SqairCarry rules out; `out`
+// (forward only, else NULL) is checked for the log weights SMC resamples on
+int sq_carry_refusal(SqairHandle* h, const char* fn, int B, const SqairCarry* carry, const SqairOutputs* out);
 bool sq_trainable_frame(SqairHandle* h);                   // false + error text when the handle's frames cannot be trained
 // The partial adjoint kept for unit tests (sqair_backward_decoder) takes the caller's frames as they are, and the full adjoint
 // kernels stage frames in 16-byte units: it wants H * W to be a multiple of 4 (the full passes stage other frames through a
@@ -189,6 +192,7 @@ struct Workspace {
   float* gen;                                    // sample_from_prior: [T][M][64] prior samples + original presences
   float* obs_p;                                  // frames whose H * W is not a multiple of 4: zero-padded copy [T*B][P4] (else unused)
   int* t_row;                                    // carried state: frame counter of each row at frame 0 of the pass [R]
+  float* fresh;                                  // train: 1 / 0 per row slot [R][N], fresh / imported row (k_state_import)
   int64_t clear_n;  // floats from the base that a workspace clear covers: every buffer carved before chain_ctl
   int64_t total;    // floats
 

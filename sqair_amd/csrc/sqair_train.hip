@@ -221,11 +221,12 @@ struct SlotAdjPhase {
   bool d_r_every_slot;                 // d_r[k & 1] holds a contribution in the last slot too (propagation: the temporal cell's gate dX)
 };
 
-extern "C" int sqair_backward(SqairHandle* h, const float* flat, const void* packedv, const float* obs, const float* noise,
-                              const float* importance_weights, const float* vimco_signal, int T, int B, int t_offset,
-                              void* train_workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes,
-                              float* flat_grad, void* stream) {
-  if (h && sq_state_refusal(h, true, B, t_offset) != 0) return -1;
+// carried: after sqair_forward_train_carry -- each row's step-prior time is its counter plus the frame (w.t_row), and the frame-0
+// initial-state gradients take only the rows that started fresh (w.fresh); the imported rows are constants.
+static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, const float* obs, const float* noise,
+                       const float* importance_weights, const float* vimco_signal, int T, int B, int t_offset, bool carried,
+                       void* train_workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes,
+                       float* flat_grad, void* stream) {
   if (!h || !flat || !packedv || !obs || !noise || !importance_weights || !vimco_signal || !train_workspace || !scratch || !flat_grad)
     return -1;
   if (workspace_bytes < sqair_train_workspace_bytes(h, T, B) || scratch_bytes < sqair_backward_bytes(h, T, B)) {
@@ -356,6 +357,7 @@ extern "C" int sqair_backward(SqairHandle* h, const float* flat, const void* pac
     la.spre = w.spre; la.g_lw = b.g_lw; la.g_dl = b.g_dl; la.d_rec_p = b.d_rec_p; la.d_rec_d = b.d_rec_d;
     la.d_rec_m = b.d_rec_m; la.d_pstats = b.d_pstats; la.d_spre = b.d_spre; la.flat = flat; la.flat_grad = flat_grad;
     la.t_global0 = t_offset; la.cfg = c;
+    la.t_row = carried ? w.t_row : nullptr;
     CK(sq_launch_logprob_bwd(la, po, d, T, s));
   }
 
@@ -650,8 +652,10 @@ extern "C" int sqair_backward(SqairHandle* h, const float* flat, const void* pac
     if (c.rec_where_prior) cs.add(b.d_rn0, 4, T * R, 4, flat_grad + po.rn_init_state, s);
     cs.add(b.d_new_t, snh, T * R, snh, flat_grad + po.temporal_init, s);
     cs.add(b.d_new_p, psnh, T * R, psnh, flat_grad + po.prior_init, s);
-    cs.add(b.d_tm(0), snh, M, snh, flat_grad + po.temporal_init, s);
-    cs.add(b.d_pm(0), psnh, M, psnh, flat_grad + po.prior_init, s);
+    // frame 0: every row from the initial state, or with a carry only the fresh ones (weight 1 / 0 per row slot)
+    const float* fresh = carried ? w.fresh : nullptr;
+    cs.add(b.d_tm(0), snh, M, snh, flat_grad + po.temporal_init, s, fresh, 1);
+    cs.add(b.d_pm(0), psnh, M, psnh, flat_grad + po.prior_init, s, fresh, 1);
     // output layer of the steps predictors (nh/2 -> 1): d w2 = s1h^T d_raw, d b2 = sum d_raw, all uses at once
     const size_t ph1 = (size_t)T * R * N;
     cs.add(w.s1h, S1_LD, (int)ph1, nsp, flat_grad + po.prop_steps_l1_w, s, b.d_raw, 1);
@@ -738,6 +742,25 @@ extern "C" int sqair_backward(SqairHandle* h, const float* flat, const void* pac
   if (h->padded) sq_flat_gather(h, flat_grad, user_grad, packedv, s);
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
+}
+extern "C" int sqair_backward(SqairHandle* h, const float* flat, const void* packedv, const float* obs, const float* noise,
+                              const float* importance_weights, const float* vimco_signal, int T, int B, int t_offset,
+                              void* train_workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes,
+                              float* flat_grad, void* stream) {
+  if (h && sq_state_refusal(h, true, B, t_offset) != 0) return -1;
+  return sq_backward(h, flat, packedv, obs, noise, importance_weights, vimco_signal, T, B, t_offset, false, train_workspace,
+                     workspace_bytes, scratch, scratch_bytes, flat_grad, stream);
+}
+// Backward of a carried chunk (include/sqair_hip.h: SqairCarry), after sqair_forward_train_carry and sqair_elbo.  The carry is
+// checked as the forward checks it; neither its blob nor its source map is read.
+extern "C" int sqair_backward_carry(SqairHandle* h, const float* flat, const void* packedv, const float* obs, const float* noise,
+                                    const float* importance_weights, const float* vimco_signal, int T, int B, const SqairCarry* carry,
+                                    void* train_workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes,
+                                    float* flat_grad, void* stream) {
+  if (!h) return -1;
+  if (sq_carry_refusal(h, "sqair_backward_carry", B, carry, nullptr) != 0) return -1;
+  return sq_backward(h, flat, packedv, obs, noise, importance_weights, vimco_signal, T, B, 0, true, train_workspace,
+                     workspace_bytes, scratch, scratch_bytes, flat_grad, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -343,6 +343,85 @@ class SqairCore(object):
             self.train_ws.data_ptr(), nb, self.bwd_scratch.data_ptr(), self.bwd_scratch.numel() * 4,
             self.flat_grad.data_ptr(), self._stream()), "sqair_backward")
 
+    # ---- training with a carried state (include/sqair_hip.h: SqairCarry) --------------------------------------------------------
+    def _train_buffers(self):
+        nb = self.lib.sqair_train_workspace_bytes(self.handle, self.T, self.B)
+        if getattr(self, "train_ws", None) is None or self.train_ws.numel() * 4 < nb:
+            self.train_ws = torch.empty(nb // 4, dtype=torch.float32, device=self.device)
+            self._clear_ws(self.train_ws, True)
+        nb = self.lib.sqair_backward_bytes(self.handle, self.T, self.B)
+        if getattr(self, "bwd_scratch", None) is None or self.bwd_scratch.numel() * 4 < nb:
+            self.bwd_scratch = torch.empty(nb // 4, dtype=torch.float32, device=self.device)
+        if getattr(self, "flat_grad", None) is None:
+            self.flat_grad = torch.zeros_like(self.flat)
+
+    def forward_carry(self, carry):
+        """forward(train=True) of a carried chunk: ``carry`` (a ``_capi.SqairCarry`` the caller keeps alive) names the blob the rows
+        start from, the blob frame T goes to and optionally the SMC resampler that ends the pass."""
+        with torch.cuda.device(self.device):
+            self._join_in()
+            self._train_buffers()
+            self._issue_carry(carry, backward=False)
+            self._join_out()
+
+    def backward_carry(self, carry):
+        """backward() of the chunk forward_carry(carry) ran: the imported rows are constants.  Returns ``self.flat_grad``."""
+        assert getattr(self, "train_ws", None) is not None, "backward_carry() needs forward_carry() first"
+        with torch.cuda.device(self.device):
+            self._join_in()
+            self._issue_carry(carry, forward=False)
+            self._join_out()
+        return self.flat_grad
+
+    def grad_step_carry(self, carry, use_graph=True):
+        """grad_step() of a carried chunk.  The first call for a (shape, carry) runs eagerly -- the chunk's one real step, which
+        advances the carried state -- and then captures the same calls without running them; later calls replay the graph."""
+        if not use_graph:
+            self.forward_carry(carry)
+            return self.backward_carry(carry)
+        key = (self._shape, "carry", _carry_key(carry))
+        if not getattr(self, "_train_graph_ready", False) or self._train_graph_key != key:
+            self.forward_carry(carry)
+            self.backward_carry(carry)
+            torch.cuda.synchronize(self.device)
+            with torch.cuda.device(self.device):
+                self.check(self.lib.sqair_capture_begin(self.handle, self._stream()), "sqair_capture_begin")
+                try:
+                    self._issue_carry(carry)
+                finally:
+                    n = self.lib.sqair_capture_end(self.handle, self._stream(), 1)
+                if n < 0:
+                    self.check(n, "sqair_capture_end")
+            self.train_graph_nodes = n
+            self._train_graph_ready = True
+            self._train_graph_key = key
+            return self.flat_grad
+        with torch.cuda.device(self.device):
+            self._join_in()
+            self.check(self.lib.sqair_capture_launch(self.handle, 1, self._stream()), "sqair_capture_launch")
+            self._join_out()
+        return self.flat_grad
+
+    def _issue_carry(self, carry, forward=True, backward=True):
+        """The raw calls of a carried gradient evaluation (forward + ELBO, backward) on the core's stream: capturable."""
+        ws, nb = self.train_ws.data_ptr(), self.train_ws.numel() * 4
+        if forward:
+            self.check(self.lib.sqair_forward_train_carry(
+                self.handle, self.flat.data_ptr(), self.packed.data_ptr(), self.obs.data_ptr(), self.noise.data_ptr(), self.T, self.B,
+                C.byref(carry), C.byref(self.c_out), ws, nb, self._stream()), "sqair_forward_train_carry")
+            dlp = self.out["discrete_log_prob"].data_ptr() if "discrete_log_prob" in self.out else None
+            self.check(self.lib.sqair_elbo(
+                self.handle, self.out["log_weights_per_timestep"].data_ptr(), dlp, self.T, self.B,
+                self.log_weights.data_ptr(), self.elbo_iwae_per_example.data_ptr(),
+                self.importance_weights.data_ptr(), self.vimco_signal.data_ptr(), self.scalars.data_ptr(),
+                self.c_means, len(self.mean_names), self.iw_means.data_ptr(), self._stream()), "sqair_elbo")
+        if backward:
+            self.check(self.lib.sqair_backward_carry(
+                self.handle, self.flat.data_ptr(), self.packed.data_ptr(), self.obs.data_ptr(), self.noise.data_ptr(),
+                self.importance_weights.data_ptr(), self.vimco_signal.data_ptr(), self.T, self.B, C.byref(carry), ws, nb,
+                self.bwd_scratch.data_ptr(), self.bwd_scratch.numel() * 4, self.flat_grad.data_ptr(), self._stream()),
+                "sqair_backward_carry")
+
     def grads_by_name(self):
         """The last backward()'s gradients as a dict name -> tensor (reference variable shapes)."""
         out = {}
@@ -425,6 +504,15 @@ class SqairCore(object):
             self.check(self.lib.sqair_check_finite(
                 self.handle, tensor.data_ptr(), tensor.numel(), what.encode(), self._finite_flag.data_ptr(), self._stream()),
                 "sqair_check_finite")
+
+
+def _carry_key(carry):
+    """What a captured carried step freezes of its SqairCarry: every pointer (and the SMC settings)."""
+    smc = None
+    if carry.smc:
+        m = carry.smc.contents
+        smc = tuple(getattr(m, f) for f, _ in m._fields_)
+    return (carry.state_in, carry.state_out, carry.src_rows, carry.state_bytes, carry.B, smc)
 
 
 class Model(object):

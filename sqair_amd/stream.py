@@ -29,6 +29,10 @@ between steps leaves every step's results unchanged.
 
 The stream takes over its core's handle: while it is open, every inference pass of that handle carries the state.  ``close()``
 hands the handle back.
+
+``state``: a blob of the same core and B to continue from (for example ``StreamTrainer.state``, sqair_amd/train.py, after training on
+the stream): the first step then imports every row from it instead of starting fresh.  It is copied; the stream's frame count
+(the default noise key) starts at 0.
 """
 from __future__ import annotations
 
@@ -46,7 +50,8 @@ FORECAST_NOISE_TAG = 1 << 63
 
 
 class SqairStream(object):
-    def __init__(self, core, B, frames_per_step=1, outputs=DEFAULT_OUTPUTS, use_graph=True, seed=0, resample=None, ess_frac=0.5):
+    def __init__(self, core, B, frames_per_step=1, outputs=DEFAULT_OUTPUTS, use_graph=True, seed=0, resample=None, ess_frac=0.5,
+                 state=None):
         if core.cfg.sample_from_prior:
             raise ValueError("SqairStream: generation modes (sample_from_prior) do not carry a state across calls")
         if resample not in (None, "systematic"):
@@ -87,6 +92,15 @@ class SqairStream(object):
         self._src_is_identity = True   # (SMC: _src is written on the device only, never refreshed from the host)
         # host-side source map of the next step (None: identity); first: all fresh.  SMC composes maps on the device instead.
         self._armed = None if self.smc else np.full(self.R, -1, dtype=np.int64)
+        if state is not None:   # hand-over: the first step continues every row of the given blob
+            state = torch.as_tensor(state)
+            if state.dtype != torch.float32 or state.numel() != self.state.numel():
+                raise ValueError("SqairStream: state must be a float32 blob of sqair_state_bytes(core, B) = {} bytes".format(
+                    self.state.numel() * 4))
+            with torch.cuda.device(dev):
+                self.state.copy_(state.reshape(-1))
+                self._src.copy_(self._identity)
+            self._armed = None
         self._graph = False
         self._fc = {}               # forecast buffers of the LAST (F, outputs, summaries) only: workspace, noise, map, weights, outputs
         self._smc_uniforms = None   # registered with the caller's uniforms (True) or Philox (False)

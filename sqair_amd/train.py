@@ -167,3 +167,173 @@ class Trainer(object):
             self.opt.apply_gradients(g, learning_rate(F, self.step_no), grad_scale=scale)
         self.step_no += 1
         return g
+
+
+class StreamTrainer(object):
+    """Training on a stream, chunk by chunk: truncated BPTT with a carried state (include/sqair_hip.h: SqairCarry), the
+    ``SqairStream`` idiom for training.  Every ``step(frames)`` takes the next T' = frames_per_step frames of B lanes, starts each
+    particle row from the state the previous step left (the first step starts every row fresh), evaluates the chunk's VIMCO
+    target / T' and its gradient with the imported state held constant, applies l2, the all-reduce and the optimiser exactly as
+    ``Trainer.step`` does, and keeps frame T''s state (records, cell states, ids, counters) in ``state`` for the next step.
+
+    ``resample="systematic"``: the forward ends with the SMC resampler at ess_frac = 1 (every lane, every chunk boundary), so the
+    sum of a lane's chunk elbo_iwae is its SMC log evidence (``log_evidence``), the FIVO bound; ``ess`` and ``ancestors`` (the next
+    step's source map) as in ``SqairStream``.  Default noise: the library's Philox keyed by (seed, index of the chunk's first frame,
+    position in the global batch), so that data-parallel ranks draw what one GPU would.  ``state`` can be handed to
+    ``SqairStream(core, B, state=...)`` of the same core and B.  The trainer takes no registration on the handle: close a
+    ``SqairStream`` of the same core before stepping."""
+
+    def __init__(self, core_or_model, F, B, frames_per_step=1, seed=0, resample=None, use_graph=True, comm=None, collective=True,
+                 outputs=("what", "where", "presence", "obj_id")):
+        import torch
+        from . import _capi
+        core = getattr(core_or_model, "core", core_or_model)
+        if core.cfg.sample_from_prior:
+            raise ValueError("StreamTrainer: generation modes (sample_from_prior) do not carry a state")
+        if resample not in (None, "systematic"):
+            raise ValueError("StreamTrainer: resample must be None or 'systematic'")
+        self.core, self.F = core, F
+        self.B, self.K, self.T = int(B), core.K, int(frames_per_step)
+        if self.B < 1 or self.T < 1:
+            raise ValueError("StreamTrainer: B and frames_per_step must be >= 1")
+        self.R = self.B * self.K
+        self.smc = resample is not None
+        self.seed = int(seed)
+        self.comm, self.collective, self.use_graph = comm, bool(collective), bool(use_graph)
+        self.opt = Optimizer(core, getattr(F, "opt", "rmsprop"))
+        self.step_no = 0
+        self.frame = 0          # frames consumed so far
+        names = ["log_weights_per_timestep", "discrete_log_prob", "data_ll_per_sample", "kl_per_sample",
+                 "log_q_z_given_x_per_sample", "log_p_z_per_sample", "num_steps_per_sample", "num_disc_steps_per_sample",
+                 "num_prop_steps_per_sample"]
+        core.bind(self.T, self.B, names + [n for n in outputs if n not in names])
+        dev = core.device
+        z = lambda n, dt=torch.float32: torch.zeros(n, dtype=dt, device=dev)
+        with torch.cuda.device(dev):
+            self.state = z(core.lib.sqair_state_bytes(core.handle, self.B) // 4)
+            self._identity = torch.arange(self.R, dtype=torch.int32, device=dev)
+            self._src = self._identity.clone()   # (frozen into the captured graph; refreshed before a step that needs another map)
+            if self.smc:   # (the resampler writes _src after every step; the first step starts every row fresh)
+                self._src.fill_(-1)
+            self.log_weight_sum = z(self.R)
+            if self.smc:
+                self.log_z, self.log_evidence, self.ess, self.u = z(self.B), z(self.B), z(self.B), z(self.B)
+                self.resampled = z(self.B, torch.int32)
+                self._uniforms = z(self.B)
+        self._armed = None if self.smc else np.full(self.R, -1, dtype=np.int64)   # host-side map of the next step; first: all fresh
+        self._src_is_identity = True
+        self._carries = {}      # SqairCarry (and its SqairSmc) per uniforms mode, kept alive while the trainer lives
+        core.stream.synchronize()
+
+    @property
+    def ancestors(self):
+        """SMC: the source map of the next step (written by the resampler)."""
+        return self._src
+
+    def _carry(self, uniforms):
+        from . import _capi
+        c = self._carries.get(uniforms)
+        if c is None:
+            smc = None
+            if self.smc:
+                smc = _capi.SqairSmc(ess_frac=1.0, seed=self.seed & 0xFFFFFFFFFFFFFFFF,
+                                     uniforms=self._uniforms.data_ptr() if uniforms else None, log_w=self.log_weight_sum.data_ptr(),
+                                     log_z=self.log_z.data_ptr(), log_evidence=self.log_evidence.data_ptr(), ess=self.ess.data_ptr(),
+                                     u_out=self.u.data_ptr(), resampled=self.resampled.data_ptr(), src_rows=self._src.data_ptr())
+            c = _capi.SqairCarry(state_in=self.state.data_ptr(), state_out=self.state.data_ptr(), src_rows=self._src.data_ptr(),
+                                 state_bytes=self.state.numel() * 4, B=self.B, smc=C.pointer(smc) if smc is not None else None)
+            self._carries[uniforms] = c
+            c._smc = smc   # (the SqairSmc the pointer names lives as long as the carry)
+        return c
+
+    # ---- source map (SqairStream's semantics) ------------------------------------------------------------------------------
+    def _pending(self):
+        return np.arange(self.R, dtype=np.int64) if self._armed is None else self._armed
+
+    def reset(self, lanes):
+        """Lanes (in [0, B)) whose next step starts a new clip: their K particle rows start fresh, counter 0."""
+        import torch
+        lanes = np.atleast_1d(np.asarray(lanes))
+        if lanes.size and (lanes.dtype.kind not in "iu" or lanes.min() < 0 or lanes.max() >= self.B):
+            raise ValueError("StreamTrainer.reset: lanes must be integers in [0, {})".format(self.B))
+        if self.smc:   # on the device, after the map the last step's resampler wrote
+            core = self.core
+            with core.on_stream():
+                for j in sorted(set(lanes.tolist())):
+                    self._src[j * self.K:(j + 1) * self.K].fill_(-1)
+                    self.log_weight_sum[j * self.K:(j + 1) * self.K].zero_()
+                    self.log_z[j:j + 1].zero_()
+            return
+        m = self._pending().copy()
+        for j in lanes.tolist():
+            m[j * self.K:(j + 1) * self.K] = -1
+        self._armed = m
+
+    def resample(self, src_rows):
+        """Row r of the next step continues row src_rows[r] (-1: fresh); composes with a reset armed before it.  Not with SMC (the
+        resampler writes the map)."""
+        if self.smc:
+            raise ValueError("StreamTrainer.resample: the SMC resampler writes the source map (resample='systematic')")
+        src = np.asarray(src_rows)
+        if src.shape != (self.R,) or src.dtype.kind not in "iu" or (src.size and (src.min() < -1 or src.max() >= self.R)):
+            raise ValueError("StreamTrainer.resample: src_rows must be {} integers in [-1, {})".format(self.R, self.R))
+        m = self._pending()
+        self._armed = np.where(src >= 0, m[np.maximum(src, 0)], -1)
+
+    # ---- stepping ------------------------------------------------------------------------------------------------------------
+    def step(self, frames, noise=None, seed=None, uniforms=None, global_batch=None, b0=0):
+        """One training step on the next chunk: frames [T', B, H, W]; ``noise`` [T', B*K, 2, N, 4 + n_what + 1] (default: Philox
+        keyed by (``seed`` or the trainer's seed, the chunk's first frame, position in the global batch ``global_batch`` / ``b0``));
+        ``uniforms`` [B] (SMC only: the resampler's uniforms; default Philox).  Asynchronous on the core's stream.  Returns the
+        flat gradient buffer after the optimiser step (on a multi-rank job the SUM over the ranks, as ``Trainer.step``)."""
+        import torch
+        from .dist import allreduce_flat_grads
+        core, F = self.core, self.F
+        frames = torch.as_tensor(frames, dtype=torch.float32)
+        if frames.dim() == 5:
+            frames = frames[..., 0]
+        if tuple(frames.shape) != (self.T, self.B, core.H, core.W):
+            raise ValueError("StreamTrainer.step: frames of shape {} given, [{}, {}, {}, {}] expected".format(
+                tuple(frames.shape), self.T, self.B, core.H, core.W))
+        if noise is not None:
+            noise = torch.as_tensor(noise, dtype=torch.float32)
+            if noise.numel() != core.noise.numel():
+                raise ValueError("StreamTrainer.step: noise of shape {} given, {} expected".format(tuple(noise.shape),
+                                                                                                 tuple(core.noise.shape)))
+        if uniforms is not None:
+            if not self.smc:
+                raise ValueError("StreamTrainer.step: uniforms are for a trainer with resample='systematic'")
+            uniforms = torch.as_tensor(uniforms, dtype=torch.float32)
+            if tuple(uniforms.shape) != (self.B,):
+                raise ValueError("StreamTrainer.step: uniforms of shape {} given, [{}] expected".format(tuple(uniforms.shape), self.B))
+        with core.on_stream():
+            core.obs.copy_(frames, non_blocking=True)
+            if noise is not None:
+                core.noise.copy_(noise.reshape(core.noise.shape), non_blocking=True)
+            else:
+                core.draw_noise(seed=self.seed if seed is None else int(seed), step=self.frame, global_batch=global_batch, b0=b0)
+            if uniforms is not None:
+                self._uniforms.copy_(uniforms, non_blocking=True)
+            if not self.smc:
+                if self._armed is not None:
+                    m = torch.as_tensor(self._armed.astype(np.int32))
+                    self._src.copy_(m, non_blocking=True)
+                    lw = self.log_weight_sum[torch.as_tensor(np.maximum(self._armed, 0), device=core.device)]
+                    self.log_weight_sum.copy_(torch.where(m.to(core.device) >= 0, lw, torch.zeros_like(lw)))
+                    self._src_is_identity = False
+                    self._armed = None
+                elif not self._src_is_identity:
+                    self._src.copy_(self._identity)
+                    self._src_is_identity = True
+            g = core.grad_step_carry(self._carry(uniforms is not None), use_graph=self.use_graph)
+            if not self.smc:
+                self.log_weight_sum += core.out["log_weights_per_timestep"].sum(0)
+            l2 = float(getattr(F, "l2", 0.0))
+            if l2 != 0.0:
+                core.check(core.lib.sqair_add_l2_grad(
+                    core.handle, core.flat.data_ptr(), g.data_ptr(), core.n_params, l2, core._stream()), "sqair_add_l2_grad")
+            scale = allreduce_flat_grads(g, comm=self.comm, stream=core.stream) if self.collective else 1.0
+            self.opt.apply_gradients(g, learning_rate(F, self.step_no), grad_scale=scale)
+        self.step_no += 1
+        self.frame += self.T
+        return g
