@@ -418,6 +418,14 @@ int sqair_clear_workspace(SqairHandle* h, void* workspace, int64_t workspace_byt
  *                 encoder's Gaussian head of a discovery slot, the temporal cell's heads of a propagation slot -- instead of in
  *                 the slot tail (csrc/sqair_glue.h: WhatArgs).  Results are bit-identical either way; re-capture graphs after
  *                 changing it.  (Training passes and the slot chain always derive the sample in the tail.)
+ *   "specialised" (default 1): when the handle's dimensions are the shipped model family's (50 x 50 frames, 20 x 20 glimpses,
+ *                 4 slots, n_what 50, n_hidden 256, GRU temporal and prior cells), the crops of the slot loop and the
+ *                 compaction run in instantiations that have those dimensions and the launch's mode compiled in
+ *                 (csrc/sqair_glue.h: sq_spec_ok).
+ *                 Every other configuration runs the generic instantiations; 0 = always.  Results are bit-identical either way
+ *                 (tests/test_hip_specialised.py); re-capture graphs after changing it.
+ *   "specialised_mask" (default 3): which kernels "specialised" covers -- 1 crops, 2 compaction.  A measurement aid: one
+ *                 kernel at a time inside one binary.
  *   "vi_target" (default 0): the learning signal sqair_elbo writes (and sqair_backward consumes) and the proxy loss in
  *                 scalars_out[2]: 0 = VIMCO, log w - control variate (sqair/targets.py:62-75: what the reference's make_target
  *                 uses); 1 = plain REINFORCE, log w (sqair/targets.py:78-89, advertised in Model.VI_TARGETS).

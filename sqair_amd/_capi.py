@@ -150,6 +150,7 @@ _PROTOS = {
                                               C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_void_p]),
     "sqair_debug_dense_log": (C.c_int, [C.c_void_p, C.c_int]),
     "sqair_debug_dense_log_entry": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "sqair_debug_specialised_launches": (C.c_int64, []),
     "sqair_debug_layers": (C.c_int, [C.c_void_p]),
     "sqair_debug_padded_count": (C.c_int64, [C.c_void_p, C.POINTER(C.c_int)]),
     "sqair_debug_layer": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
@@ -217,6 +218,8 @@ def lib(path=None, allow_stale=False):
             raise ImportError("{}: ABI version {} but this binding speaks {}; rebuild (python sqair_amd/csrc/build.py)".format(
                 os.path.basename(path), l.sqair_abi_version(), ABI_VERSION))
         for name, (res, args) in _PROTOS.items():
+            if allow_stale and name.startswith("sqair_debug") and not hasattr(l, name):
+                continue   # (tools/ab_libs.py: a build of an older revision has the same ABI version but may lack a newer debug query)
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args

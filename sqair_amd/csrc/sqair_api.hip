@@ -1186,6 +1186,7 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
   // P4 = H * W rounded up to 4, made once in the prologue; otherwise on the caller's buffer as it is.
   const float* const obs_user = obs;
   if ((P_ & 3) != 0) { d.P4 = (P_ + 3) / 4 * 4; obs = w.obs_p; }
+  d.spec = h->opt_specialised && sq_spec_ok(d) ? (h->opt_specialised_mask & SPEC_ALL) : 0;   // (sqair_glue.h: the slot loop's kernels with this family's dimensions compiled in)
   const int PL = d.P4;
   const int pre_ld = h->layers[L_PRE].nt * 16;
   const int RW = rec::W, snh = d.snh, psnh = d.psnh;
@@ -1706,6 +1707,8 @@ extern "C" int sqair_set_option(SqairHandle* h, const char* name, int value) {
   const std::string n(name);
   if (n == "tail_fusion") { h->opt_tail_fusion = value != 0; return 0; }
   if (n == "what_fusion") { h->opt_what_fusion = value != 0; return 0; }   // (results do not depend on it; drop captured graphs after changing it)
+  if (n == "specialised") { h->opt_specialised = value != 0; return 0; }   // (the same: results do not depend on it; re-capture graphs)
+  if (n == "specialised_mask") { h->opt_specialised_mask = value; return 0; }   // (SPEC_* bits of sqair_glue.h: one kernel at a time, for measurements)
   if (n == "vi_target") {   // 0 = vimco (the reference's make_target), 1 = reinforce (targets.py:78-89)
     if (value != 0 && value != 1) { sq_set_error(h, "sqair_set_option: vi_target is 0 (vimco) or 1 (reinforce)"); return -2; }
     h->opt_vi_target = value;
@@ -1723,7 +1726,7 @@ extern "C" int sqair_set_option(SqairHandle* h, const char* name, int value) {
     if (sq_chain_set_arena_kb(h, value) != 0) { sq_set_error(h, "sqair_set_option: slot_chain_arena_kb is 64 .. 1048576, set before the first pass"); return -2; }
     return 0;
   }
-  sq_set_error(h, "sqair_set_option: unknown option '" + n + "' (known: tail_fusion, what_fusion, slot_chain, slot_chain_arena_kb, vi_target)");
+  sq_set_error(h, "sqair_set_option: unknown option '" + n + "' (known: tail_fusion, what_fusion, specialised, specialised_mask, slot_chain, slot_chain_arena_kb, vi_target)");
   return -2;
 }
 
@@ -2372,6 +2375,8 @@ extern "C" int sqair_lstm_cell_bwd_test(SqairHandle* h, const float* gates, cons
 // host-only introspection of the packing plan (tests/test_pack_plan.py emulates the packed GEMMs on
 // the CPU from these tables to check the row / column maps without a GPU)
 // ------------------------------------------------------------------------------------------------
+// launches of specialised instantiations (sqair_glue.h) issued or captured by this process so far: lets a test see which path a pass took
+extern "C" int64_t sqair_debug_specialised_launches(void) { return (int64_t)sq_spec_launches(); }
 extern "C" int sqair_debug_layers(const SqairHandle* h) { return h ? (int)L_COUNT : -1; }
 // padded inventory: total floats of the padded flat buffer; u2i (optional, n = sqair_param_count entries): where element j of the
 // caller's flat buffer lives in it

@@ -46,7 +46,33 @@ struct Dims {
   int P4;                           // floats between consecutive frames in the buffer the kernels read frames from: H * W, or --
                                     // inside a pass over frames whose H * W is not a multiple of 4 -- H * W rounded up to 4 (the
                                     // pass stages such frames through a zero-padded copy so that every frame starts 16-byte aligned)
+  int spec;                         // which of the slot loop's kernels the pass launches in their specialised instantiations (SPEC_* bits;
+                                    // sq_spec_ok below and sqair_set_option("specialised")); set by the forward pass, 0 everywhere else
 };
+// Specialised instantiations of the slot loop's crops and of the compaction (k_crop_row, k_compact).  These launches are
+// hops of a chain of dependent launches whose length is the instruction stream of their longest wave, and much
+// of that stream is arithmetic on values the host knows: the dimensions of the shipped model family and the mode of the launch.  When a handle's dimensions are the ones below, the launchers pick an instantiation that has them as
+// compile-time constants (Dims replaced by sq_spec_dims inside the kernel, the mode a template argument): same expressions in the
+// same order on the same operands, so the results are bit-identical to the generic instantiation, which serves everything else.
+namespace spec {
+constexpr int H = 50, W = 50, G = 20, N = 4, NW = 50, NH = 256;
+}
+inline bool sq_spec_ok(const Dims& d) {
+#ifdef SQAIR_WIDE
+  (void)d;
+  return false;   // (the wide build keeps its plain-loop kernels)
+#else
+  return d.H == spec::H && d.W == spec::W && d.G == spec::G && d.N == spec::N && d.nw == spec::NW && d.nh == spec::NH &&
+         d.nzw == 4 + spec::NW + 1 && d.snh == spec::NH && d.toff == 0 && d.psnh == spec::NH && d.P4 == spec::H * spec::W;
+#endif
+}
+// Which kernels take their specialised instantiation is a mask in Dims::spec, all of them by default: with one bit set
+// (sqair_set_option("specialised_mask")) each of them is timed, or checked for equal bits, on its own inside ONE binary -- two builds
+// that differ in the set of kernels they contain differ by +-0.03 ms per cfg-2 step from code placement alone.
+enum { SPEC_CROP = 1, SPEC_COMPACT = 2, SPEC_ALL = 3 };
+// launches of specialised instantiations issued (or captured) by this process so far: a debug query for the tests
+long long sq_spec_launches();
+void sq_spec_count(int n);
 #ifdef __HIPCC__
 __device__ __forceinline__ int sq_div(int e, SqMagic m) { return (int)(__umulhi((unsigned)e, m.mul) + ((unsigned)e & m.one)); }
 #endif
@@ -61,10 +87,21 @@ inline Dims make_dims(const SqairConfig& c, int B) {
   return Dims{c.img_h, c.img_w, c.glimpse_size, c.n_steps_per_image, c.n_what, c.n_hidden, c.k_particles, B * c.k_particles, B,
               4 + c.n_what + 1, lstm ? 2 * c.n_hidden : c.n_hidden, lstm ? c.n_hidden : 0,
               (c.prior_cell == CELL_LSTM) ? 2 * c.n_hidden : c.n_hidden, c.rnn_cell == RNN_LSTM ? 2 * c.n_hidden : c.n_hidden,
-              sq_magic(c.n_what), sq_magic(c.glimpse_size), sq_magic(c.k_particles), c.img_h * c.img_w};
+              sq_magic(c.n_what), sq_magic(c.glimpse_size), sq_magic(c.k_particles), c.img_h * c.img_w, 0};
 }
 
 #ifdef __HIPCC__
+// Dims of a specialised instantiation: what sq_spec_ok has checked becomes a constant, the rest (R, B, K and its multiplier) stays
+template <int X> constexpr SqMagic sq_magic_c() { return SqMagic{(unsigned)((1ull << 32) / (unsigned)X + 1), 0u}; }
+template <bool SP>
+__device__ __forceinline__ Dims sq_spec_dims(const Dims& d) {
+  if (!SP) return d;
+  Dims c = d;
+  c.H = spec::H; c.W = spec::W; c.G = spec::G; c.N = spec::N; c.nw = spec::NW; c.nh = spec::NH; c.nzw = 4 + spec::NW + 1;
+  c.snh = spec::NH; c.toff = 0; c.psnh = spec::NH; c.P4 = spec::H * spec::W;
+  c.nw_mul = sq_magic_c<spec::NW>(); c.g_mul = sq_magic_c<spec::G>();
+  return c;
+}
 // Particle row handled by workgroup i of a launch with one workgroup per row (grid.x = R, R a multiple of 8).  Workgroups go to
 // the eight XCDs round-robin (XCD = i % 8), each XCD has its own L2, and the K particles of a sequence read the SAME frame: with
 // rows taken in launch order a frame was fetched into up to K of the eight L2s (PMC: 2.5x the algorithmic bytes of k_crop_row).

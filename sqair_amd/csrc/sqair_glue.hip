@@ -1,6 +1,8 @@
 // Non-GEMM kernels of the SQAIR hot path: spatial-transformer crop / insert, sampling, presence,
 // log-probabilities with the presence mask applied in-kernel, slot compaction and the IWAE / VIMCO
 // reductions.  All HBM-bound gather / scatter / reduce work (class 2).
+#include <atomic>
+
 #include "sqair_glue.h"
 #include "sqair_rowops.h"
 #include "sqair_canvas.h"
@@ -239,16 +241,29 @@ int sq_launch_smc_resample(const SmcArgs& a, hipStream_t s) {
 
 // one workgroup per particle row (a per-sequence kernel staging the frame in LDS for its K particles had only B = 32
 // workgroups at the headline config and measured 10.3 us; this one 5-6 us with the frame served by L1 / L2)
-template <bool STAGED>
+template <bool STAGED, int MODE = -1>   // MODE: -1 generic, else the specialised instantiation of that CropMode (sqair_rowops.h)
 __global__ __launch_bounds__(256) void k_crop_row(const CropArgs a, const POff po, const Dims d SQ_TLP) {
   SQ_TL_SCOPE;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  x_crop_row<LdPlain, STAGED>(a, po, d, sq_row_of_wg(blockIdx.x, d), a.mode == CROP_PROP1 ? (int)blockIdx.y : a.slot, smem);
+  if constexpr (MODE >= 0) x_crop_row_spec<LdPlain, MODE>(a, po, d, sq_row_of_wg(blockIdx.x, d), MODE == CROP_PROP1 ? (int)blockIdx.y : a.slot, smem);
+  else x_crop_row<LdPlain, STAGED>(a, po, d, sq_row_of_wg(blockIdx.x, d), a.mode == CROP_PROP1 ? (int)blockIdx.y : a.slot, smem);
 }
+
+static std::atomic<long long> g_spec_launches{0};
+long long sq_spec_launches() { return g_spec_launches.load(); }
+void sq_spec_count(int n) { g_spec_launches += n; }
 
 int sq_launch_crop(const CropArgs& a, POff po, Dims d, int nslots, hipStream_t s) {
   const bool staged = d.H * d.W <= SQ_CROP_STAGE_MAX_PIXELS;
   const size_t shm = (4 + (size_t)4 * d.G + (staged ? (size_t)d.H * d.W : 0)) * sizeof(float);
+#ifndef SQAIR_WIDE
+  // the slot loop's crops of the shipped model family: one instantiation per mode (what they fix: sqair_rowops.h)
+  if ((d.spec & SPEC_CROP) && staged && (a.mask != nullptr) == (a.mode != CROP_DISC) && (a.mode == CROP_PROP1 || a.t2 != nullptr)) {
+    if (a.mode == CROP_PROP1) { SQ_LAUNCH((k_crop_row<true, CROP_PROP1>), dim3(d.R, nslots), dim3(256), shm, s, a, po, d); sq_spec_count(1); return 0; }
+    if (a.mode == CROP_PROP2) { SQ_LAUNCH((k_crop_row<true, CROP_PROP2>), dim3(d.R, nslots), dim3(256), shm, s, a, po, d); sq_spec_count(1); return 0; }
+    if (a.mode == CROP_DISC) { SQ_LAUNCH((k_crop_row<true, CROP_DISC>), dim3(d.R, nslots), dim3(256), shm, s, a, po, d); sq_spec_count(1); return 0; }
+  }
+#endif
   if (staged) SQ_LAUNCH(k_crop_row<true>, dim3(d.R, nslots), dim3(256), shm, s, a, po, d);
   else SQ_LAUNCH(k_crop_row<false>, dim3(d.R, nslots), dim3(256), shm, s, a, po, d);
   return 0;
@@ -1302,8 +1317,11 @@ int sq_launch_forecast_summary(const ForecastSummaryArgs& a, Dims d, hipStream_t
 // One workgroup per row: 2N presence bits -> stable present-first permutation -> copy the N
 // survivors (record + prior state + temporal state) into the next frame's state.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_compact(const CompactArgs a, const POff po, const Dims d SQ_TLP) {
+template <bool SP>   // SP: the specialised instantiation (sqair_glue.h: sq_spec_ok) -- slot count and state widths are constants
+__global__ __launch_bounds__(256) void k_compact(const CompactArgs a, const POff po, const Dims d_in SQ_TLP) {
   SQ_TL_SCOPE;
+  const Dims d_sp = sq_spec_dims<SP>(d_in);
+  const Dims& d = SP ? d_sp : d_in;
   __shared__ int src_s[SQ_MAXN];
   __shared__ float id_s[SQ_MAXN];
   const int r = blockIdx.x, tid = threadIdx.x;
@@ -1417,7 +1435,10 @@ __global__ __launch_bounds__(256) void k_compact(const CompactArgs a, const POff
   }
 }
 int sq_launch_compact(const CompactArgs& a, POff po, Dims d, hipStream_t s) {
-  SQ_LAUNCH(k_compact, dim3(d.R), dim3(256), 0, s, a, po, d);
+#ifndef SQAIR_WIDE
+  if (d.spec & SPEC_COMPACT) { SQ_LAUNCH(k_compact<true>, dim3(d.R), dim3(256), 0, s, a, po, d); sq_spec_count(1); return 0; }
+#endif
+  SQ_LAUNCH(k_compact<false>, dim3(d.R), dim3(256), 0, s, a, po, d);
   return 0;
 }
 

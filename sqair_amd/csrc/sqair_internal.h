@@ -65,6 +65,8 @@ struct SqairHandle {
   std::vector<int> dense_log;          // of the passes issued while it was on (host side only: nothing changes on the device)
   float debug_us = 0.0f;
   bool opt_what_fusion = true;  // sqair_set_option("what_fusion"): the what sample of a slot inside the layer that produces its operands (bit-identical)
+  bool opt_specialised = true;  // sqair_set_option("specialised"): the slot loop's per-row kernels in their instantiations for the shipped dimensions (bit-identical)
+  int opt_specialised_mask = 3;    // sqair_set_option("specialised_mask"): which of them (SPEC_* bits, sqair_glue.h); a measurement aid
   bool opt_tail_fusion = true;  // sqair_set_option("tail_fusion"): the tail of slot k inside slot k + 1's RNN launch (bit-identical either way)
   bool opt_slot_chain = false;  // sqair_set_option("slot_chain"): the slot launches of a frame's propagation / discovery loop as one
                                 // persistent launch each (sqair_chain.h; bit-identical; set BEFORE sizing / clearing workspaces)
