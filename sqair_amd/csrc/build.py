@@ -22,7 +22,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-SOURCES = ["sqair_api.hip", "sqair_linear.hip", "sqair_glue.hip", "sqair_bwd.hip", "sqair_train.hip", "sqair_linear_dx.hip", "sqair_chain.hip"]
+SOURCES = ["sqair_api.hip", "sqair_state.hip", "sqair_linear.hip", "sqair_glue.hip", "sqair_bwd.hip", "sqair_train.hip", "sqair_linear_dx.hip", "sqair_chain.hip"]
 OUT = os.path.join(os.path.dirname(HERE), "libsqair_hip.so")
 OUT_TIMELINE = os.path.join(os.path.dirname(HERE), "libsqair_hip_timeline.so")
 OUT_KNOBS = os.path.join(ROOT, "tools", "bin", "libsqair_hip_knobs.so")
@@ -64,7 +64,7 @@ def build(force=False, verbose=False, variant="product"):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     common = [f for f in HIPCC_FLAGS if f != "-shared"] + defs + \
         ['-DSQAIR_BUILD_ID="{}"'.format(sid), '-DSQAIR_BUILD_VARIANT="{}"'.format(variant)]
-    # one hipcc per translation unit, all at once (the six files take ~25 s each), then the link
+    # one hipcc per translation unit, all at once (the files take ~25 s each), then the link
     objdir = os.path.join(HERE, "_obj", variant)
     os.makedirs(objdir, exist_ok=True)
     objs = [os.path.join(objdir, s.replace(".hip", ".o")) for s in SOURCES]

@@ -1,5 +1,6 @@
 // libsqair_hip.so — handle, parameter inventory, weight packing plan, and the launch sequence of the
-// SQAIR forward pass.  Host code only; kernels live in sqair_linear.hip / sqair_glue.hip.
+// SQAIR forward pass.  Host code only; kernels live in sqair_linear.hip / sqair_glue.hip; the carried state and the forecast in
+// sqair_state.hip.
 //
 // The launch sequence of one frame restates SQAIRTimestep + AIRDecoder (reference:
 // sqair/sqair_modules.py:446-582, sqair/core.py:164-359, sqair/propagate.py:68-184,
@@ -831,154 +832,6 @@ Workspace sq_carve(const SqairHandle* h, int T, int B, float* base, bool train) 
 }
 static Workspace carve(const SqairHandle* h, int T, int B, float* base) { return sq_carve(h, T, B, base, false); }
 
-// carried model state: one blob row per particle row (StateArgs, sqair_glue.h), 4-word aligned
-int64_t sq_state_row_floats(const SqairHandle* h) {
-  const SqairConfig& c = h->cfg;
-  const int64_t N = c.n_steps_per_image, nh = c.n_hidden;
-  const int64_t snh = c.time_cell == CELL_LSTM ? 2 * nh : nh, psnh = c.prior_cell == CELL_LSTM ? 2 * nh : nh;
-  return (N * (rec::W + snh + psnh) + 2 + 3) / 4 * 4;
-}
-extern "C" int64_t sqair_state_bytes(const SqairHandle* h, int B) {
-  if (!h || B < 1) return -1;
-  return (int64_t)B * h->cfg.k_particles * sq_state_row_floats(h) * 4;
-}
-extern "C" int sqair_set_state(SqairHandle* h, const void* state_in, void* state_out, const int32_t* src_rows, int64_t state_bytes, int B) {
-  if (!h) return -1;
-  if (!state_in && !state_out && !src_rows) {
-    h->state_on = false; h->state_in = nullptr; h->state_out = nullptr; h->state_src = nullptr; h->state_B = 0;
-    h->smc_on = false; h->smc = SqairSmc{};   // (SMC resamples the carried state: off with it)
-    return 0;
-  }
-  if (h->cfg.sample_from_prior) {
-    sq_set_error(h, "sqair_set_state: not with sample_from_prior (generation decides per frame on the host)");
-    return -1;
-  }
-  if (src_rows && !state_in) {
-    sq_set_error(h, "sqair_set_state: a source map needs state_in");
-    return -1;
-  }
-  if (B < 1 || state_bytes < sqair_state_bytes(h, B)) {
-    sq_set_error(h, "sqair_set_state: state_bytes " + std::to_string(state_bytes) + " < sqair_state_bytes(h, " + std::to_string(B) +
-                        ") = " + std::to_string(B < 1 ? -1 : sqair_state_bytes(h, B)));
-    return -1;
-  }
-  if (h->smc_on && (!state_in || src_rows != h->state_src || B != h->state_B)) {   // (what SMC was registered against is gone)
-    h->smc_on = false; h->smc = SqairSmc{};
-  }
-  h->state_on = true; h->state_in = state_in; h->state_out = state_out; h->state_src = src_rows; h->state_B = B;
-  return 0;
-}
-extern "C" int sqair_set_smc(SqairHandle* h, const SqairSmc* smc, int B) {
-  if (!h) return -1;
-  if (!smc) {
-    h->smc_on = false; h->smc = SqairSmc{};
-    return 0;
-  }
-  if (!h->state_on || !h->state_in || !h->state_src) {
-    sq_set_error(h, "sqair_set_smc: needs a carried state with state_in and a source map (sqair_set_state) to resample");
-    return -1;
-  }
-  if (smc->src_rows != h->state_src) {
-    sq_set_error(h, "sqair_set_smc: src_rows must be the source map given to sqair_set_state");
-    return -1;
-  }
-  if (!(smc->ess_frac >= 0.0f && smc->ess_frac <= 1.0f)) {   // (NaN fails both)
-    sq_set_error(h, "sqair_set_smc: ess_frac must lie in [0, 1]");
-    return -1;
-  }
-  if (!smc->log_w || !smc->log_z || !smc->log_evidence || !smc->ess || !smc->resampled) {
-    sq_set_error(h, "sqair_set_smc: log_w, log_z, log_evidence, ess and resampled must not be NULL");
-    return -1;
-  }
-  if (B != h->state_B) {
-    sq_set_error(h, "sqair_set_smc: B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " +
-                        std::to_string(h->state_B));
-    return -1;
-  }
-  h->smc_on = true; h->smc = *smc;
-  return 0;
-}
-// the refusal of a pass with SMC on (host only: before any HIP call)
-static int sq_smc_refusal(SqairHandle* h, const SqairOutputs* outp) {
-  if (!h->smc_on || (outp && outp->log_weights_per_timestep)) return 0;
-  sq_set_error(h, "SMC (sqair_set_smc) resamples on log_weights_per_timestep: a pass with SMC on must bind that output");
-  return -1;
-}
-// kernel-level check of the SMC resampler (tests/test_smc_kernel.py): k_smc_resample on caller buffers, K given (1..SQ_MAX_K), no
-// state and no pass.  lw [T][B*K]; t_row [B*K] (read only for Philox, when smc->uniforms is NULL); smc->src_rows [B*K] out.
-extern "C" int sqair_smc_resample_test(SqairHandle* h, const float* lw, int T, int B, int K, const int32_t* t_row,
-                                       const SqairSmc* smc, void* stream) {
-  if (!h) return -1;
-  if (!lw || !smc || T < 1 || B < 1 || K < 1 || K > SQ_MAX_K || (int64_t)B * K > INT32_MAX) {
-    sq_set_error(h, "sqair_smc_resample_test: null lw / smc or bad T / B / K (1 <= K <= " + std::to_string(SQ_MAX_K) + ")");
-    return -1;
-  }
-  if (!(smc->ess_frac >= 0.0f && smc->ess_frac <= 1.0f)) {   // (NaN fails both)
-    sq_set_error(h, "sqair_smc_resample_test: ess_frac must lie in [0, 1]");
-    return -1;
-  }
-  if (!smc->log_w || !smc->log_z || !smc->log_evidence || !smc->ess || !smc->resampled || !smc->src_rows ||
-      (!smc->uniforms && !t_row)) {
-    sq_set_error(h, "sqair_smc_resample_test: log_w, log_z, log_evidence, ess, resampled, src_rows (and t_row without uniforms) "
-                    "must not be NULL");
-    return -1;
-  }
-  SmcArgs a; memset(&a, 0, sizeof(a));
-  a.lw = lw; a.t_row = t_row; a.uniforms = smc->uniforms;
-  a.log_w = smc->log_w; a.log_z = smc->log_z; a.log_evidence = smc->log_evidence; a.ess = smc->ess;
-  a.u_out = smc->u_out; a.resampled = smc->resampled; a.src = smc->src_rows;
-  a.seed = smc->seed; a.ess_frac = smc->ess_frac; a.T = T; a.B = B; a.K = K;
-  sq_launch_smc_resample(a, (hipStream_t)stream);
-  SQ_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-// the refusals of a carried training call (host only: before any HIP call)
-int sq_carry_refusal(SqairHandle* h, const char* fn, int B, const SqairCarry* carry, const SqairOutputs* out) {
-  const std::string f = std::string(fn) + ": ";
-  auto no = [&](const std::string& why) { sq_set_error(h, f + why); return -1; };
-  if (!carry) return no("a NULL carry (SqairCarry)");
-  if (B != carry->B) return no("B = " + std::to_string(B) + " but the carry is for B = " + std::to_string(carry->B));
-  if (B < 1 || carry->state_bytes < sqair_state_bytes(h, B))
-    return no("state_bytes " + std::to_string(carry->state_bytes) + " < sqair_state_bytes(h, " + std::to_string(B) + ") = " +
-              std::to_string(B < 1 ? -1 : sqair_state_bytes(h, B)));
-  if (carry->src_rows && !carry->state_in) return no("a source map needs state_in");
-  if (h->state_on) return no("the handle carries an inference state (sqair_set_state): switch it off before training with a carry");
-  if (h->cfg.sample_from_prior) return no("a carried state does not combine with sample_from_prior");
-  if (!sq_trainable_frame(h)) return -1;
-  if (const SqairSmc* m = carry->smc) {
-    if (m->ess_frac != 1.0f)
-      return no("SMC at chunk boundaries needs ess_frac == 1: adaptive resampling (carried weights inside the target) is not "
-                "supported by training");
-    if (!m->log_w || !m->log_z || !m->log_evidence || !m->ess || !m->resampled || !m->src_rows)
-      return no("the SMC buffers log_w, log_z, log_evidence, ess, resampled and src_rows must not be NULL");
-    if (m->src_rows != carry->src_rows) return no("smc->src_rows must be the carry's src_rows");
-    if (out && !out->log_weights_per_timestep)
-      return no("SMC resamples on log_weights_per_timestep: a carried step with SMC must bind that output");
-  }
-  return 0;
-}
-// the refusals of a pass with a carried state (host only: before any HIP call)
-int sq_state_refusal(SqairHandle* h, bool train, int B, int t_offset) {
-  if (!h->state_on) return 0;
-  if (train) {
-    sq_set_error(h, "a carried state (sqair_set_state) is for inference passes: training / backward with one is not supported");
-    return -1;
-  }
-  if (h->cfg.sample_from_prior) {
-    sq_set_error(h, "a carried state (sqair_set_state) does not combine with sample_from_prior");
-    return -1;
-  }
-  if (h->state_in && t_offset != 0) {
-    sq_set_error(h, "with state_in set (sqair_set_state) t_offset must be 0: the state's frame counter is the time index");
-    return -1;
-  }
-  if (B != h->state_B) {
-    sq_set_error(h, "B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
-    return -1;
-  }
-  return 0;
-}
-
 extern "C" int64_t sqair_workspace_bytes(const SqairHandle* h, int T, int B) {
   if (!h || T < 1 || B < 1) return -1;
   return sq_carve(h, T, B, nullptr, false).total * 4;
@@ -1105,6 +958,31 @@ __global__ void k_copy_cols(const float* __restrict__ src, float* __restrict__ d
   }
 }
 
+// Section A of a frame (propagate.py:68-98): the propagation-prior cell over [what, where]_{t-1} of all M slot rows, then the
+// layer of the prior's statistics.  The forecast (sqair_state.hip) rolls the same step forward.  pgz: the GRU's z gate [M][nh] or
+// the LSTM's gate pre-activations [M][4 nh]; pgrh, pgxh: the GRU's hand-offs between its two launches; o3, o1: the GRU's reset
+// gate and candidate, kept for the backward pass, or NULL.
+int sq_prior_step(SqairHandle* h, const float* packed, hipStream_t s, int M, const float* rec_prev, const float* prior_prev,
+                  float* prior_p, float* pgz, float* pgrh, float* pgxh, float* pstats, float* o3, float* o1) {
+  const SqairConfig& c = h->cfg;
+  const int nh = c.n_hidden, psnh = c.prior_cell == CELL_LSTM ? 2 * nh : nh;
+  if (c.prior_cell == CELL_LSTM) {
+    Lin g; g.seg(rec_prev, rec::W, rec::ZW).seg(prior_prev, psnh, nh).out(pgz, 4 * nh); RUN(g, L_PRIOR_GRU1, M);
+    sq_launch_lstm_cell(pgz, 4 * nh, prior_prev + nh, psnh, prior_p, psnh, M, nh, s);
+  } else if (c.prior_cell == CELL_VANILLA) {
+    Lin g; g.seg(rec_prev, rec::W, rec::ZW).seg(prior_prev, nh, nh).out(prior_p, nh).act(ACT_TANH); RUN(g, L_PRIOR_GRU1, M);
+  } else {
+    Lin g1l; g1l.seg(rec_prev, rec::W, rec::ZW).seg(prior_prev, nh, nh).out(pgz, nh).gru1(prior_prev, nh, pgrh, nh, pgxh, nh, nh);
+    if (o3) { g1l.a.o3 = o3; g1l.a.o3_ld = nh; }
+    RUN(g1l, L_PRIOR_GRU1, M);
+    Lin g2l; g2l.seg(pgrh, nh, nh).add(pgxh, nh, nh).out(prior_p, nh).gru2(prior_prev, nh, pgz, nh, nh);
+    if (o1) { g2l.a.o1 = o1; g2l.a.o1_ld = nh; }
+    RUN(g2l, L_PRIOR_GRU2, M);
+  }
+  Lin pll; pll.seg(prior_p, psnh, nh).out(pstats, PS_LD); RUN(pll, L_PRIOR_LIN, M);
+  return 0;
+}
+
 // What the two slot loops of a frame differ in -- propagation (E, tape phase 0) and discovery (G, phase 1) -- filled once per
 // frame; the slot step itself (sq_forward_impl: slot_front, slot_tail) is the same code for both.
 struct SlotPhase {
@@ -1119,37 +997,6 @@ struct SlotPhase {
   int w2_off, b2_off;                 // the steps predictor's output layer (slot tail)
   bool fuse;                          // the slot's tail rides in the next slot's VanillaRNN launch (k_rnn_tail)
 };
-
-// The carried-state settings of one pass, resolved once: the handle's (sqair_set_state / sqair_set_smc: inference passes) or
-// a carried training call's (SqairCarry).  `fresh`: k_state_import records each row's fresh / imported flag for the backward.
-struct SqStateRes {
-  bool on;
-  const void* in; void* out; const int32_t* src;
-  bool fresh;
-  bool smc_on; SqairSmc smc;
-};
-static SqStateRes sq_handle_state(const SqairHandle* h) {
-  return SqStateRes{h->state_on, h->state_in, h->state_out, h->state_src, false, h->smc_on, h->smc};
-}
-static SqStateRes sq_carry_state(const SqairCarry* c) {
-  return SqStateRes{true, c->state_in, c->state_out, c->src_rows, true, c->smc != nullptr, c->smc ? *c->smc : SqairSmc{}};
-}
-// the carried state's rows of frame t of a pass (k_state_import: t = 0, k_state_export: t = T)
-static StateArgs state_args(const SqairHandle* h, const SqStateRes& st, const Workspace& w, int t, int t0) {
-  StateArgs a; memset(&a, 0, sizeof(a));
-  a.rec = w.rec_m_all + (size_t)t * w.M * rec::W;
-  a.temporal = w.state(w.temporal_m, t, w.snh);
-  a.prior = w.state(w.prior_m, t, w.psnh);
-  a.last_id = w.last_id[t & 1];
-  a.t_row = w.t_row;
-  a.fresh = st.fresh && t == 0 ? w.fresh : nullptr;
-  a.blob_in = (const float*)st.in;
-  a.blob_out = (float*)st.out;
-  a.src = st.src;
-  a.R = w.R; a.n_rec = w.N * rec::W; a.n_tmp = w.N * w.snh; a.n_pri = w.N * w.psnh; a.row_words = (int)sq_state_row_floats(h);
-  a.t0 = t0;
-  return a;
-}
 
 // parts: 1 = prologue (workspace clear, initial state, input encoder), 2 = the frame loop, 4 = epilogue (log-probabilities,
 // decoder, final state copies).  carry: the settings of a carried training call (refused or not by its entry point); NULL =
@@ -1192,6 +1039,11 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
   const int RW = rec::W, snh = d.snh, psnh = d.psnh;
   const int rw = sq_rnn_width(c);  // slot-RNN pre-activation width; pre columns: [rnn rw | T1 nh | S1 nh/2 | GRU z, r]
   const PackedLayout pl = packed_layout(h);
+  // the carried state's rows of frame t of the pass (k_state_import: t = 0, k_state_export: t = T)
+  auto state_at = [&](int t, int t0) {
+    return sq_state_args(h, st, R, w.rec_m_all + (size_t)t * M * RW, w.state(w.temporal_m, t, w.snh), w.state(w.prior_m, t, w.psnh),
+                         w.last_id[t & 1], w.t_row, st.fresh && t == 0 ? w.fresh : nullptr, t0);
+  };
 
   // ---- sequence prologue -----------------------------------------------------------------------
   // The GEMM A-operand contract wants every float it may touch to be finite (padding meets zero weights, but
@@ -1206,7 +1058,7 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
                          w.prop_rnn_init, w.disc_rnn_init, w.rn_init_state, w.w3_prop, w.w3_disc,
                          (int)P(h, "prop.transform.l2.w"), (int)P(h, "disc.transform.l2.w"), flat, po, d, s);
     // carried state (sqair_set_state): frame 0's records / states / last_id of each row from the caller's blob, and its counter
-    if (st.on) sq_launch_state_import(state_args(h, st, w, 0, t_offset), s);
+    if (st.on) sq_launch_state_import(state_at(0, t_offset), s);
     if (w.chain) {
       // hand-off words of the chain launches of this pass -> sentinel; their control blocks -> zero (one launch)
       ChainPoisonList pl; memset(&pl, 0, sizeof(pl));
@@ -1277,24 +1129,11 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
     float* cvec = w.frame(w.c, (int64_t)R * nh, t);
 
     // ---- A. propagation prior (propagate.py:68-98): GRU over [what, where]_{t-1}, all slots ----
-    if (c.prior_cell == CELL_LSTM) {
-      float* pg = w.frame(w.pgz, (int64_t)M * 4 * nh, t);
-      Lin g; g.seg(rec_prev, RW, rec::ZW).seg(prior_prev, psnh, nh).out(pg, 4 * nh); RUN(g, L_PRIOR_GRU1, M);
-      sq_launch_lstm_cell(pg, 4 * nh, prior_prev + nh, psnh, prior_p, psnh, M, nh, s);
-      Lin pll; pll.seg(prior_p, psnh, nh).out(pstats_t, PS_LD); RUN(pll, L_PRIOR_LIN, M);
-    } else if (c.prior_cell == CELL_VANILLA) {
-      Lin g; g.seg(rec_prev, RW, rec::ZW).seg(prior_prev, nh, nh).out(prior_p, nh).act(ACT_TANH); RUN(g, L_PRIOR_GRU1, M);
-      Lin pll; pll.seg(prior_p, nh, nh).out(pstats_t, PS_LD); RUN(pll, L_PRIOR_LIN, M);
-    } else {
-      float* pgz = w.frame(w.pgz, (int64_t)M * nh, t);
-      Lin g1l; g1l.seg(rec_prev, RW, rec::ZW).seg(prior_prev, nh, nh).out(pgz, nh)
-                 .gru1(prior_prev, nh, w.pgrh, nh, w.pgxh, nh, nh);
-      if (train) { g1l.a.o3 = w.frame(w.pgr, (int64_t)M * nh, t); g1l.a.o3_ld = nh; }
-      RUN(g1l, L_PRIOR_GRU1, M);
-      Lin g2l; g2l.seg(w.pgrh, nh, nh).add(w.pgxh, nh, nh).out(prior_p, nh).gru2(prior_prev, nh, pgz, nh, nh);
-      if (train) { g2l.a.o1 = w.frame(w.pghc, (int64_t)M * nh, t); g2l.a.o1_ld = nh; }
-      RUN(g2l, L_PRIOR_GRU2, M);
-      Lin pll; pll.seg(prior_p, nh, nh).out(pstats_t, PS_LD); RUN(pll, L_PRIOR_LIN, M);
+    {
+      const int rc = sq_prior_step(h, packed, s, M, rec_prev, prior_prev, prior_p,
+                                   w.frame(w.pgz, (int64_t)M * (c.prior_cell == CELL_LSTM ? 4 * nh : nh), t), w.pgrh, w.pgxh, pstats_t,
+                                   train ? w.frame(w.pgr, (int64_t)M * nh, t) : nullptr, train ? w.frame(w.pghc, (int64_t)M * nh, t) : nullptr);
+      if (rc != 0) return rc;
     }
     // ---- B. where-bias MLP and glimpse-mask MLP of every slot (core.py:292, modules.py:350-356) ----
     {
@@ -1417,14 +1256,10 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
                   .add(w.lpre + (size_t)k * 4 * nh, N * 4 * nh, 4 * nh).out(gates, gld);
         RUN(gl, L_PROP_GRU1, R);
         sq_launch_lstm_cell(gates, gld, tau_prev + (size_t)k * snh, N * snh, temporal_p + (size_t)k * snh, N * snh, R, nh, s);
-        if (fw) { const int rc = run_what(h, 1, temporal_p + (size_t)k * snh, N * snh, R, k, nz, enc, el, rec_prev, rec_p_t, packed, s); if (rc != 0) return rc; }
-        else { Lin hd; hd.seg(temporal_p + (size_t)k * snh, N * snh, nh).out(hraw, hl); RUN(hd, L_PROP_HEADS, R); }
       } else if (c.time_cell == CELL_VANILLA) {  // tau' = tanh(x W_i + [tau W_h + b, hoisted into `pre`]) in one launch
         Lin g; g.seg(r_k, rl, nh).seg(rec_p_t + (size_t)k * RW + rec::WHERE, N * RW, 4).seg(enc, el, 2 * nw)
                  .add(pre_k + rw + nh + nh / 2, pre_rld, nh).out(temporal_p + (size_t)k * nh, N * nh).act(ACT_TANH);
         RUN(g, L_PROP_GRU1, R);
-        if (fw) { const int rc = run_what(h, 1, temporal_p + (size_t)k * nh, N * nh, R, k, nz, enc, el, rec_prev, rec_p_t, packed, s); if (rc != 0) return rc; }
-        else { Lin hd; hd.seg(temporal_p + (size_t)k * nh, N * nh, nh).out(hraw, hl); RUN(hd, L_PROP_HEADS, R); }
       } else {
         const float* tau_k = temporal_prev + (size_t)k * nh;
         float* grh_k = w.chain ? w.slot(w.grh, nh, t, 0, k) : w.grh;   // (the chain: every slot's hand-offs in their own buffers)
@@ -1439,9 +1274,11 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
                    .gru2(tau_k, N * nh, gz, rl, nh);
         if (train) { g2l.a.o1 = w.slot(w.ghc, nh, t, 0, k); g2l.a.o1_ld = rl; }
         RUN(g2l, L_PROP_GRU2, R);
-        if (fw) { const int rc = run_what(h, 1, temporal_p + (size_t)k * nh, N * nh, R, k, nz, enc, el, rec_prev, rec_p_t, packed, s); if (rc != 0) return rc; }
-        else { Lin hd; hd.seg(temporal_p + (size_t)k * nh, N * nh, nh).out(hraw, hl); RUN(hd, L_PROP_HEADS, R); }
       }
+      // the heads on the slot's new temporal state (snh == nh unless the temporal cell is an LSTM): the what sample in the
+      // layer's own launch, or the raw heads for the tail
+      if (fw) { const int rc = run_what(h, 1, temporal_p + (size_t)k * snh, N * snh, R, k, nz, enc, el, rec_prev, rec_p_t, packed, s); if (rc != 0) return rc; }
+      else { Lin hd; hd.seg(temporal_p + (size_t)k * snh, N * snh, nh).out(hraw, hl); RUN(hd, L_PROP_HEADS, R); }
       slot_tail(prop, k, hraw, hl);
     }
     if (w.chain) {
@@ -1538,16 +1375,9 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
   if (out.final_last_used_id)
     sq_copy(out.final_last_used_id, w.last_id[T & 1], (int64_t)R, s);
   // carried state: frame T's rows into the caller's blob (after every reader of the imported rows: in place is fine)
-  if (st.on && st.out) sq_launch_state_export(state_args(h, st, w, T, T), s);
+  if (st.on && st.out) sq_launch_state_export(state_at(T, T), s);
   // SMC: this pass's log weights -> ESS, evidence and the next pass's source map (sqair_set_smc / SqairCarry.smc)
-  if (st.smc_on) {
-    SmcArgs a; memset(&a, 0, sizeof(a));
-    a.lw = out.log_weights_per_timestep; a.t_row = w.t_row; a.uniforms = st.smc.uniforms;
-    a.log_w = st.smc.log_w; a.log_z = st.smc.log_z; a.log_evidence = st.smc.log_evidence; a.ess = st.smc.ess;
-    a.u_out = st.smc.u_out; a.resampled = st.smc.resampled; a.src = st.smc.src_rows;
-    a.seed = st.smc.seed; a.ess_frac = st.smc.ess_frac; a.T = T; a.B = B; a.K = K;
-    sq_launch_smc_resample(a, s);
-  }
+  if (st.smc_on) sq_launch_smc_resample(sq_smc_args(st.smc, out.log_weights_per_timestep, w.t_row, T, B, K), s);
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -1884,169 +1714,6 @@ extern "C" int sqair_chain_status(SqairHandle* h, void* workspace, int T, int B,
 extern "C" int sqair_set_generation_noise(SqairHandle* h, const float* gen_noise) {
   if (!h) return -1;
   h->gen_noise = gen_noise;
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// forecast (include/sqair_hip.h: sqair_forecast): the propagation prior rolled F frames forward from the carried state, discovery
-// empty, then the decoder of all F frames and the predictive summaries
-// ------------------------------------------------------------------------------------------------
-struct FcWorkspace {
-  float* rec;        // [F + 1][M][rec::W]: frame 0 = the imported state, frame f + 1 = forecast frame f
-  float* temporal;   // [M][snh] (written by the import, never read)
-  float* prior[2];   // [M][psnh] compacted prior states, ping-pong over frames
-  float* prior_p;    // [M][psnh] the prior cell's output of the frame
-  float *pgz, *pgrh, *pgxh;   // prior cell internals (GRU: z gate, r h, x h; LSTM: pgz = the four gate pre-activations)
-  float* pstats;     // [M][PS_LD]
-  float* last_id;    // [R]
-  int* t_row;        // [R]
-  float *disc_init_rec, *prop_rnn_init, *disc_rnn_init, *rn_init_state, *w3_prop, *w3_disc;   // (k_init_state writes them)
-  float *dec_a, *dec_b, *glimpse;   // decoder of all F frames [F * M][nh | G*G]
-  float* canvas;     // [F][R][H*W] when the caller asks for summaries but not for the canvas
-  int64_t total;     // floats
-};
-static FcWorkspace fc_carve(const SqairHandle* h, int F, int B, float* base) {
-  const SqairConfig& c = h->cfg;
-  const int64_t nh = c.n_hidden, N = c.n_steps_per_image, R = (int64_t)B * c.k_particles, M = R * N;
-  const int64_t snh = c.time_cell == CELL_LSTM ? 2 * nh : nh, psnh = c.prior_cell == CELL_LSTM ? 2 * nh : nh;
-  FcWorkspace w;
-  memset(&w, 0, sizeof(w));
-  int64_t o = 0;
-  auto take = [&](int64_t n) {
-    float* p = base ? base + o : nullptr;
-    o += align64(n);
-    return p;
-  };
-  w.rec = take((int64_t)(F + 1) * M * rec::W);
-  w.temporal = take(M * snh);
-  w.prior[0] = take(M * psnh);
-  w.prior[1] = take(M * psnh);
-  w.prior_p = take(M * psnh);
-  w.pgz = take(M * (c.prior_cell == CELL_LSTM ? 4 * nh : nh));
-  w.pgrh = take(M * nh);
-  w.pgxh = take(M * nh);
-  w.pstats = take(M * PS_LD);
-  w.last_id = take(R);
-  w.t_row = (int*)take(R);
-  w.disc_init_rec = take(rec::W);
-  w.prop_rnn_init = take(2 * nh);
-  w.disc_rnn_init = take(2 * nh);
-  w.rn_init_state = take(4);
-  w.w3_prop = take(nh * 8 + 8);
-  w.w3_disc = take(nh * 8 + 8);
-  w.dec_a = take((int64_t)F * M * nh);
-  w.dec_b = take((int64_t)F * M * nh);
-  w.glimpse = take((int64_t)F * M * c.glimpse_size * c.glimpse_size);
-  w.canvas = take((int64_t)F * R * c.img_h * c.img_w);
-  w.total = o;
-  return w;
-}
-extern "C" int64_t sqair_forecast_workspace_bytes(const SqairHandle* h, int F, int B) {
-  if (!h || F < 1 || B < 1) return -1;
-  return fc_carve(h, F, B, nullptr).total * 4;
-}
-extern "C" int sqair_forecast(SqairHandle* h, const float* flat_params, const void* packed_v, const float* noise, int F, int B,
-                              const int32_t* src_rows, const SqairForecastOutputs* outp, void* workspace, int64_t workspace_bytes,
-                              void* stream) {
-  if (!h) return -1;
-  const SqairConfig& c = h->cfg;
-  if (c.sample_from_prior) {
-    sq_set_error(h, "sqair_forecast: not with sample_from_prior (the forecast is the generation mode, from a carried state)");
-    return -1;
-  }
-  if (!h->state_on || !h->state_in) {
-    sq_set_error(h, "sqair_forecast: needs a carried state with state_in (sqair_set_state) to start from");
-    return -1;
-  }
-  if (B != h->state_B) {
-    sq_set_error(h, "sqair_forecast: B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " +
-                        std::to_string(h->state_B));
-    return -1;
-  }
-  if (F < 1) {
-    sq_set_error(h, "sqair_forecast: F must be >= 1");
-    return -1;
-  }
-  if (!noise) {
-    sq_set_error(h, "sqair_forecast: noise must not be NULL");
-    return -1;
-  }
-  if (!flat_params || !packed_v || !outp || !workspace) {
-    sq_set_error(h, "sqair_forecast: null parameters, packed buffer, outputs or workspace");
-    return -1;
-  }
-  if (workspace_bytes < sqair_forecast_workspace_bytes(h, F, B)) {
-    sq_set_error(h, "sqair_forecast: workspace_bytes " + std::to_string(workspace_bytes) + " < sqair_forecast_workspace_bytes(h, " +
-                        std::to_string(F) + ", " + std::to_string(B) + ") = " + std::to_string(sqair_forecast_workspace_bytes(h, F, B)));
-    return -1;
-  }
-  const float* packed = (const float*)packed_v;
-  const float* flat = sq_flat(h, flat_params, packed);
-  sq_chain_reset(h);
-  hipStream_t s = (hipStream_t)stream;
-  const SqairForecastOutputs out = *outp;
-  const int nh = c.n_hidden, N = c.n_steps_per_image, K = c.k_particles, R = B * K, M = R * N, RW = rec::W;
-  const int G2 = c.glimpse_size * c.glimpse_size;
-  const Dims d = make_dims(c, B);
-  const int psnh = d.psnh;
-  const POff po = h->po;
-  const FcWorkspace w = fc_carve(h, F, B, (float*)workspace);
-  // prologue: the rows the next pass would start from (the pass's own k_init_state + k_state_import, into this workspace)
-  sq_launch_init_state(w.rec, w.temporal, w.prior[0], w.last_id, w.disc_init_rec, w.prop_rnn_init, w.disc_rnn_init, w.rn_init_state,
-                       w.w3_prop, w.w3_disc, (int)P(h, "prop.transform.l2.w"), (int)P(h, "disc.transform.l2.w"), flat, po, d, s);
-  {
-    StateArgs a; memset(&a, 0, sizeof(a));
-    a.rec = w.rec; a.temporal = w.temporal; a.prior = w.prior[0]; a.last_id = w.last_id; a.t_row = w.t_row;
-    a.blob_in = (const float*)h->state_in; a.src = src_rows ? src_rows : h->state_src;
-    a.R = R; a.n_rec = N * RW; a.n_tmp = N * d.snh; a.n_pri = N * psnh; a.row_words = (int)sq_state_row_floats(h); a.t0 = 0;
-    sq_launch_state_import(a, s);
-  }
-  // per frame: the prior cell over all M slots (section A of the pass), then sampling + ids + compaction in one launch
-  for (int f = 0; f < F; ++f) {
-    const float* rec_prev = w.rec + (size_t)f * M * RW;
-    const float* prior_prev = w.prior[f & 1];
-    if (c.prior_cell == CELL_LSTM) {
-      Lin g; g.seg(rec_prev, RW, rec::ZW).seg(prior_prev, psnh, nh).out(w.pgz, 4 * nh); RUN(g, L_PRIOR_GRU1, M);
-      sq_launch_lstm_cell(w.pgz, 4 * nh, prior_prev + nh, psnh, w.prior_p, psnh, M, nh, s);
-    } else if (c.prior_cell == CELL_VANILLA) {
-      Lin g; g.seg(rec_prev, RW, rec::ZW).seg(prior_prev, nh, nh).out(w.prior_p, nh).act(ACT_TANH); RUN(g, L_PRIOR_GRU1, M);
-    } else {
-      Lin g1l; g1l.seg(rec_prev, RW, rec::ZW).seg(prior_prev, nh, nh).out(w.pgz, nh).gru1(prior_prev, nh, w.pgrh, nh, w.pgxh, nh, nh);
-      RUN(g1l, L_PRIOR_GRU1, M);
-      Lin g2l; g2l.seg(w.pgrh, nh, nh).add(w.pgxh, nh, nh).out(w.prior_p, nh).gru2(prior_prev, nh, w.pgz, nh, nh);
-      RUN(g2l, L_PRIOR_GRU2, M);
-    }
-    Lin pll; pll.seg(w.prior_p, psnh, nh).out(w.pstats, PS_LD); RUN(pll, L_PRIOR_LIN, M);
-    ForecastArgs fa; memset(&fa, 0, sizeof(fa));
-    fa.rec_prev = rec_prev; fa.pstats = w.pstats; fa.ps_ld = PS_LD; fa.prior_p = w.prior_p;
-    fa.noise = noise + (size_t)f * R * 2 * N * d.nzw; fa.rec_next = w.rec + (size_t)(f + 1) * M * RW; fa.prior_next = w.prior[(f + 1) & 1];
-    fa.f = f; fa.out = out; fa.cfg = c;
-    sq_launch_forecast_step(fa, d, s);
-  }
-  // decoder of all F frames (section J of the pass without the likelihood): three M = F*B'*N row GEMMs + the canvas-only insert
-  const float* rec_all = w.rec + (size_t)M * RW;
-  float* canvas = out.canvas ? out.canvas : w.canvas;
-  const bool want_canvas = out.canvas || out.mean_canvas;
-  if (want_canvas || out.glimpse) {
-    const int MT = F * M;
-    float* gl = out.glimpse ? out.glimpse : w.glimpse;
-    Lin a; a.seg(rec_all, RW, rec::ZW).out(w.dec_a, nh).act(ACT_ELU); RUN(a, L_DEC0, MT);
-    Lin b; b.seg(w.dec_a, nh, nh).out(w.dec_b, nh).act(ACT_ELU); RUN(b, L_DEC1, MT);
-    Lin g; g.seg(w.dec_b, nh, nh).out(gl, G2); g.a.scale_ptr = flat + po.dec_output_scale; RUN(g, L_DEC2, MT);
-    if (want_canvas) {
-      InsertArgs ia; memset(&ia, 0, sizeof(ia));
-      ia.glimpse = gl; ia.rec = rec_all; ia.rec_ld = RW; ia.mean_img = flat + po.dec_mean_img; ia.canvas = canvas; ia.n_frames = F;
-      ia.std_fg = c.output_std; ia.std_bg = c.background_std;
-      if (sq_launch_insert_canvas(ia, d, s) != 0) { sq_set_error(h, "sqair_forecast: the decoder canvas launch failed (dynamic LDS limit)"); return -2; }
-    }
-  }
-  if (out.mean_canvas || out.expected_count) {
-    ForecastSummaryArgs sa; memset(&sa, 0, sizeof(sa));
-    sa.canvas = canvas; sa.rec = rec_all; sa.log_w = out.log_w; sa.mean_canvas = out.mean_canvas; sa.expected_count = out.expected_count;
-    sa.F = F;
-    sq_launch_forecast_summary(sa, d, s);
-  }
-  SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }
 

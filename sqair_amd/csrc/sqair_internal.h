@@ -1,4 +1,5 @@
-// Internal declarations shared by sqair_api.hip (handle, plan, forward pass) and sqair_train.hip (backward pass).
+// Internal declarations shared by sqair_api.hip (handle, plan, forward pass), sqair_state.hip (carried state, forecast) and
+// sqair_train.hip (backward pass).
 #pragma once
 #include <cstdio>
 #include <cstring>
@@ -211,8 +212,30 @@ struct Workspace {
   }
 };
 Workspace sq_carve(const SqairHandle* h, int T, int B, float* base, bool train);
-// carried model state (sqair_set_state): floats of one particle row of the state blob
-int64_t sq_state_row_floats(const SqairHandle* h);
+
+// A helper shared between translation units that stays out of the library's dynamic symbol table.  Only helpers newer than that
+// table carry it: the older ones (sq_carve, sq_run, sq_state_refusal, ...) were exported before and stay so, the table unchanged.
+#define SQ_LOCAL __attribute__((visibility("hidden")))
+
+// ---- carried model state (sqair_state.hip) ----
+int64_t sq_state_row_floats(const SqairHandle* h);   // floats of one particle row of the state blob
+// The carried-state settings of one pass, resolved once: the handle's (sqair_set_state / sqair_set_smc: inference passes) or
+// a carried training call's (SqairCarry).  `fresh`: k_state_import records each row's fresh / imported flag for the backward.
+struct SqStateRes {
+  bool on;
+  const void* in; void* out; const int32_t* src;
+  bool fresh;
+  bool smc_on; SqairSmc smc;
+};
+SQ_LOCAL SqStateRes sq_handle_state(const SqairHandle* h);
+SQ_LOCAL SqStateRes sq_carry_state(const SqairCarry* c);
+SQ_LOCAL int sq_smc_refusal(SqairHandle* h, const SqairOutputs* outp);   // -1 + error text: a pass with SMC on that does not bind the log weights
+SQ_LOCAL StateArgs sq_state_args(const SqairHandle* h, const SqStateRes& st, int R, float* rec, float* temporal, float* prior, float* last_id,
+                                 int* t_row, float* fresh, int t0);
+SQ_LOCAL SmcArgs sq_smc_args(const SqairSmc& m, const float* lw, const int32_t* t_row, int T, int B, int K);
+// section A of a frame of the pass, and a frame of the forecast: the propagation-prior cell and its statistics (sqair_api.hip)
+SQ_LOCAL int sq_prior_step(SqairHandle* h, const float* packed, hipStream_t s, int M, const float* rec_prev, const float* prior_prev,
+                           float* prior_p, float* pgz, float* pgrh, float* pgxh, float* pstats, float* o3, float* o1);
 
 // zero fill as a kernel (not a memset node: see sqair_train.hip); p 16-byte aligned
 void sq_zero_fill(float* p, int64_t n, hipStream_t s);

@@ -1,0 +1,275 @@
+// libsqair_hip.so -- the carried model state on the native side of the C ABI (include/sqair_hip.h): the state blob and its
+// registration on a handle (sqair_set_state / sqair_set_smc), the refusals of the passes and carried training calls a state rules
+// out, the settings one pass resolves them to (SqStateRes: the handle's, or a SqairCarry's), and the forecast that rolls the prior
+// forward from a state (sqair_forecast).  Host code only; the pass that imports / exports / resamples the state is
+// sq_forward_impl (sqair_api.hip), the kernels live in sqair_glue.hip.
+#include "sqair_internal.h"
+#include "sqair_chain.h"
+
+static int sq_no(SqairHandle* h, const std::string& why) { sq_set_error(h, why); return -1; }   // a refusal: -1 + error text
+
+// carried model state: one blob row per particle row (StateArgs, sqair_glue.h), 4-word aligned
+int64_t sq_state_row_floats(const SqairHandle* h) {
+  const SqairConfig& c = h->cfg;
+  const int64_t N = c.n_steps_per_image, nh = c.n_hidden;
+  const int64_t snh = c.time_cell == CELL_LSTM ? 2 * nh : nh, psnh = c.prior_cell == CELL_LSTM ? 2 * nh : nh;
+  return (N * (rec::W + snh + psnh) + 2 + 3) / 4 * 4;
+}
+extern "C" int64_t sqair_state_bytes(const SqairHandle* h, int B) {
+  if (!h || B < 1) return -1;
+  return (int64_t)B * h->cfg.k_particles * sq_state_row_floats(h) * 4;
+}
+extern "C" int sqair_set_state(SqairHandle* h, const void* state_in, void* state_out, const int32_t* src_rows, int64_t state_bytes, int B) {
+  if (!h) return -1;
+  if (!state_in && !state_out && !src_rows) {
+    h->state_on = false; h->state_in = nullptr; h->state_out = nullptr; h->state_src = nullptr; h->state_B = 0;
+    h->smc_on = false; h->smc = SqairSmc{};   // (SMC resamples the carried state: off with it)
+    return 0;
+  }
+  if (h->cfg.sample_from_prior) return sq_no(h, "sqair_set_state: not with sample_from_prior (generation decides per frame on the host)");
+  if (src_rows && !state_in) return sq_no(h, "sqair_set_state: a source map needs state_in");
+  if (B < 1 || state_bytes < sqair_state_bytes(h, B))
+    return sq_no(h, "sqair_set_state: state_bytes " + std::to_string(state_bytes) + " < sqair_state_bytes(h, " + std::to_string(B) +
+                    ") = " + std::to_string(B < 1 ? -1 : sqair_state_bytes(h, B)));
+  if (h->smc_on && (!state_in || src_rows != h->state_src || B != h->state_B)) {   // (what SMC was registered against is gone)
+    h->smc_on = false; h->smc = SqairSmc{};
+  }
+  h->state_on = true; h->state_in = state_in; h->state_out = state_out; h->state_src = src_rows; h->state_B = B;
+  return 0;
+}
+// The fields of an SqairSmc that each of its three users checks, -1 + "<who>..." when one is off: ess_frac (in [0, 1]; `train`:
+// exactly 1, every lane resampled at every chunk boundary) and the buffers every resampler writes.  `rest`: the caller's own
+// further pointers are set too; `names`: how its message lists them all.
+static int sq_smc_fields(SqairHandle* h, const std::string& who, const SqairSmc& m, bool train, bool rest, const char* names) {
+  if (train && m.ess_frac != 1.0f)
+    return sq_no(h, who + "SMC at chunk boundaries needs ess_frac == 1: adaptive resampling (carried weights inside the target) is not "
+                          "supported by training");
+  if (!(m.ess_frac >= 0.0f && m.ess_frac <= 1.0f)) return sq_no(h, who + "ess_frac must lie in [0, 1]");   // (NaN fails both)
+  if (!m.log_w || !m.log_z || !m.log_evidence || !m.ess || !m.resampled || !rest) return sq_no(h, who + names + " must not be NULL");
+  return 0;
+}
+extern "C" int sqair_set_smc(SqairHandle* h, const SqairSmc* smc, int B) {
+  if (!h) return -1;
+  if (!smc) {
+    h->smc_on = false; h->smc = SqairSmc{};
+    return 0;
+  }
+  if (!h->state_on || !h->state_in || !h->state_src)
+    return sq_no(h, "sqair_set_smc: needs a carried state with state_in and a source map (sqair_set_state) to resample");
+  if (smc->src_rows != h->state_src) return sq_no(h, "sqair_set_smc: src_rows must be the source map given to sqair_set_state");
+  if (sq_smc_fields(h, "sqair_set_smc: ", *smc, false, true, "log_w, log_z, log_evidence, ess and resampled") != 0) return -1;
+  if (B != h->state_B)
+    return sq_no(h, "sqair_set_smc: B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
+  h->smc_on = true; h->smc = *smc;
+  return 0;
+}
+// the refusal of a pass with SMC on (host only: before any HIP call)
+int sq_smc_refusal(SqairHandle* h, const SqairOutputs* outp) {
+  if (!h->smc_on || (outp && outp->log_weights_per_timestep)) return 0;
+  return sq_no(h, "SMC (sqair_set_smc) resamples on log_weights_per_timestep: a pass with SMC on must bind that output");
+}
+// the resampler's arguments: this pass's log weights `lw` [T][B*K] and row counters `t_row`, the rest from the caller's SqairSmc
+SmcArgs sq_smc_args(const SqairSmc& m, const float* lw, const int32_t* t_row, int T, int B, int K) {
+  SmcArgs a; memset(&a, 0, sizeof(a));
+  a.lw = lw; a.t_row = t_row; a.uniforms = m.uniforms;
+  a.log_w = m.log_w; a.log_z = m.log_z; a.log_evidence = m.log_evidence; a.ess = m.ess;
+  a.u_out = m.u_out; a.resampled = m.resampled; a.src = m.src_rows;
+  a.seed = m.seed; a.ess_frac = m.ess_frac; a.T = T; a.B = B; a.K = K;
+  return a;
+}
+// kernel-level check of the SMC resampler (tests/test_smc_kernel.py): k_smc_resample on caller buffers, K given (1..SQ_MAX_K), no
+// state and no pass.  lw [T][B*K]; t_row [B*K] (read only for Philox, when smc->uniforms is NULL); smc->src_rows [B*K] out.
+extern "C" int sqair_smc_resample_test(SqairHandle* h, const float* lw, int T, int B, int K, const int32_t* t_row,
+                                       const SqairSmc* smc, void* stream) {
+  if (!h) return -1;
+  if (!lw || !smc || T < 1 || B < 1 || K < 1 || K > SQ_MAX_K || (int64_t)B * K > INT32_MAX)
+    return sq_no(h, "sqair_smc_resample_test: null lw / smc or bad T / B / K (1 <= K <= " + std::to_string(SQ_MAX_K) + ")");
+  if (sq_smc_fields(h, "sqair_smc_resample_test: ", *smc, false, smc->src_rows && (smc->uniforms || t_row),
+                    "log_w, log_z, log_evidence, ess, resampled, src_rows (and t_row without uniforms)") != 0)
+    return -1;
+  sq_launch_smc_resample(sq_smc_args(*smc, lw, t_row, T, B, K), (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+// the refusals of a carried training call (host only: before any HIP call)
+int sq_carry_refusal(SqairHandle* h, const char* fn, int B, const SqairCarry* carry, const SqairOutputs* out) {
+  const std::string f = std::string(fn) + ": ";
+  auto no = [&](const std::string& why) { return sq_no(h, f + why); };
+  if (!carry) return no("a NULL carry (SqairCarry)");
+  if (B != carry->B) return no("B = " + std::to_string(B) + " but the carry is for B = " + std::to_string(carry->B));
+  if (B < 1 || carry->state_bytes < sqair_state_bytes(h, B))
+    return no("state_bytes " + std::to_string(carry->state_bytes) + " < sqair_state_bytes(h, " + std::to_string(B) + ") = " +
+              std::to_string(B < 1 ? -1 : sqair_state_bytes(h, B)));
+  if (carry->src_rows && !carry->state_in) return no("a source map needs state_in");
+  if (h->state_on) return no("the handle carries an inference state (sqair_set_state): switch it off before training with a carry");
+  if (h->cfg.sample_from_prior) return no("a carried state does not combine with sample_from_prior");
+  if (!sq_trainable_frame(h)) return -1;
+  if (const SqairSmc* m = carry->smc) {
+    if (sq_smc_fields(h, f, *m, true, m->src_rows, "the SMC buffers log_w, log_z, log_evidence, ess, resampled and src_rows") != 0)
+      return -1;
+    if (m->src_rows != carry->src_rows) return no("smc->src_rows must be the carry's src_rows");
+    if (out && !out->log_weights_per_timestep)
+      return no("SMC resamples on log_weights_per_timestep: a carried step with SMC must bind that output");
+  }
+  return 0;
+}
+// the refusals of a pass with a carried state (host only: before any HIP call)
+int sq_state_refusal(SqairHandle* h, bool train, int B, int t_offset) {
+  if (!h->state_on) return 0;
+  if (train) return sq_no(h, "a carried state (sqair_set_state) is for inference passes: training / backward with one is not supported");
+  if (h->cfg.sample_from_prior) return sq_no(h, "a carried state (sqair_set_state) does not combine with sample_from_prior");
+  if (h->state_in && t_offset != 0)
+    return sq_no(h, "with state_in set (sqair_set_state) t_offset must be 0: the state's frame counter is the time index");
+  if (B != h->state_B)
+    return sq_no(h, "B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
+  return 0;
+}
+
+SqStateRes sq_handle_state(const SqairHandle* h) {
+  return SqStateRes{h->state_on, h->state_in, h->state_out, h->state_src, false, h->smc_on, h->smc};
+}
+SqStateRes sq_carry_state(const SqairCarry* c) {
+  return SqStateRes{true, c->state_in, c->state_out, c->src_rows, true, c->smc != nullptr, c->smc ? *c->smc : SqairSmc{}};
+}
+// k_state_import's / k_state_export's arguments: the frame's records, states, last ids and row counters `t_row` (and, for the
+// import of a training pass, its fresh / imported flags, else NULL) against the blobs and source map of `st`
+StateArgs sq_state_args(const SqairHandle* h, const SqStateRes& st, int R, float* rec, float* temporal, float* prior, float* last_id,
+                        int* t_row, float* fresh, int t0) {
+  const Dims d = make_dims(h->cfg, 1);
+  StateArgs a; memset(&a, 0, sizeof(a));
+  a.rec = rec; a.temporal = temporal; a.prior = prior; a.last_id = last_id; a.t_row = t_row; a.fresh = fresh;
+  a.blob_in = (const float*)st.in;
+  a.blob_out = (float*)st.out;
+  a.src = st.src;
+  a.R = R; a.n_rec = d.N * rec::W; a.n_tmp = d.N * d.snh; a.n_pri = d.N * d.psnh; a.row_words = (int)sq_state_row_floats(h);
+  a.t0 = t0;
+  return a;
+}
+
+// ------------------------------------------------------------------------------------------------
+// forecast (include/sqair_hip.h: sqair_forecast): the propagation prior rolled F frames forward from the carried state, discovery
+// empty, then the decoder of all F frames and the predictive summaries
+// ------------------------------------------------------------------------------------------------
+struct FcWorkspace {
+  float* rec;        // [F + 1][M][rec::W]: frame 0 = the imported state, frame f + 1 = forecast frame f
+  float* temporal;   // [M][snh] (written by the import, never read)
+  float* prior[2];   // [M][psnh] compacted prior states, ping-pong over frames
+  float* prior_p;    // [M][psnh] the prior cell's output of the frame
+  float *pgz, *pgrh, *pgxh;   // prior cell internals (GRU: z gate, r h, x h; LSTM: pgz = the four gate pre-activations)
+  float* pstats;     // [M][PS_LD]
+  float* last_id;    // [R]
+  int* t_row;        // [R]
+  float *disc_init_rec, *prop_rnn_init, *disc_rnn_init, *rn_init_state, *w3_prop, *w3_disc;   // (k_init_state writes them)
+  float *dec_a, *dec_b, *glimpse;   // decoder of all F frames [F * M][nh | G*G]
+  float* canvas;     // [F][R][H*W] when the caller asks for summaries but not for the canvas
+  int64_t total;     // floats
+};
+static FcWorkspace fc_carve(const SqairHandle* h, int F, int B, float* base) {
+  const SqairConfig& c = h->cfg;
+  const int64_t nh = c.n_hidden, N = c.n_steps_per_image, R = (int64_t)B * c.k_particles, M = R * N;
+  const int64_t snh = c.time_cell == CELL_LSTM ? 2 * nh : nh, psnh = c.prior_cell == CELL_LSTM ? 2 * nh : nh;
+  FcWorkspace w;
+  memset(&w, 0, sizeof(w));
+  int64_t o = 0;
+  auto take = [&](int64_t n) {
+    float* p = base ? base + o : nullptr;
+    o += align64(n);
+    return p;
+  };
+  w.rec = take((int64_t)(F + 1) * M * rec::W);
+  w.temporal = take(M * snh);
+  w.prior[0] = take(M * psnh);
+  w.prior[1] = take(M * psnh);
+  w.prior_p = take(M * psnh);
+  w.pgz = take(M * (c.prior_cell == CELL_LSTM ? 4 * nh : nh));
+  w.pgrh = take(M * nh);
+  w.pgxh = take(M * nh);
+  w.pstats = take(M * PS_LD);
+  w.last_id = take(R);
+  w.t_row = (int*)take(R);
+  w.disc_init_rec = take(rec::W);
+  w.prop_rnn_init = take(2 * nh);
+  w.disc_rnn_init = take(2 * nh);
+  w.rn_init_state = take(4);
+  w.w3_prop = take(nh * 8 + 8);
+  w.w3_disc = take(nh * 8 + 8);
+  w.dec_a = take((int64_t)F * M * nh);
+  w.dec_b = take((int64_t)F * M * nh);
+  w.glimpse = take((int64_t)F * M * c.glimpse_size * c.glimpse_size);
+  w.canvas = take((int64_t)F * R * c.img_h * c.img_w);
+  w.total = o;
+  return w;
+}
+extern "C" int64_t sqair_forecast_workspace_bytes(const SqairHandle* h, int F, int B) {
+  if (!h || F < 1 || B < 1) return -1;
+  return fc_carve(h, F, B, nullptr).total * 4;
+}
+extern "C" int sqair_forecast(SqairHandle* h, const float* flat_params, const void* packed_v, const float* noise, int F, int B,
+                              const int32_t* src_rows, const SqairForecastOutputs* outp, void* workspace, int64_t workspace_bytes,
+                              void* stream) {
+  if (!h) return -1;
+  const SqairConfig& c = h->cfg;
+  if (c.sample_from_prior) return sq_no(h, "sqair_forecast: not with sample_from_prior (the forecast is the generation mode, from a carried state)");
+  if (!h->state_on || !h->state_in) return sq_no(h, "sqair_forecast: needs a carried state with state_in (sqair_set_state) to start from");
+  if (B != h->state_B)
+    return sq_no(h, "sqair_forecast: B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
+  if (F < 1) return sq_no(h, "sqair_forecast: F must be >= 1");
+  if (!noise) return sq_no(h, "sqair_forecast: noise must not be NULL");
+  if (!flat_params || !packed_v || !outp || !workspace) return sq_no(h, "sqair_forecast: null parameters, packed buffer, outputs or workspace");
+  if (workspace_bytes < sqair_forecast_workspace_bytes(h, F, B))
+    return sq_no(h, "sqair_forecast: workspace_bytes " + std::to_string(workspace_bytes) + " < sqair_forecast_workspace_bytes(h, " +
+                    std::to_string(F) + ", " + std::to_string(B) + ") = " + std::to_string(sqair_forecast_workspace_bytes(h, F, B)));
+  const float* packed = (const float*)packed_v;
+  const float* flat = sq_flat(h, flat_params, packed);
+  sq_chain_reset(h);
+  hipStream_t s = (hipStream_t)stream;
+  const SqairForecastOutputs out = *outp;
+  const int nh = c.n_hidden, N = c.n_steps_per_image, K = c.k_particles, R = B * K, M = R * N, RW = rec::W;
+  const int G2 = c.glimpse_size * c.glimpse_size;
+  const Dims d = make_dims(c, B);
+  const int psnh = d.psnh;
+  const POff po = h->po;
+  const FcWorkspace w = fc_carve(h, F, B, (float*)workspace);
+  // prologue: the rows the next pass would start from (the pass's own k_init_state + k_state_import, into this workspace)
+  sq_launch_init_state(w.rec, w.temporal, w.prior[0], w.last_id, w.disc_init_rec, w.prop_rnn_init, w.disc_rnn_init, w.rn_init_state,
+                       w.w3_prop, w.w3_disc, (int)P(h, "prop.transform.l2.w"), (int)P(h, "disc.transform.l2.w"), flat, po, d, s);
+  const SqStateRes st = {true, h->state_in, nullptr, src_rows ? src_rows : h->state_src, false, false, SqairSmc{}};
+  sq_launch_state_import(sq_state_args(h, st, R, w.rec, w.temporal, w.prior[0], w.last_id, w.t_row, nullptr, 0), s);
+  // per frame: the prior cell over all M slots (section A of the pass), then sampling + ids + compaction in one launch
+  for (int f = 0; f < F; ++f) {
+    const float* rec_prev = w.rec + (size_t)f * M * RW;
+    const float* prior_prev = w.prior[f & 1];
+    const int rc = sq_prior_step(h, packed, s, M, rec_prev, prior_prev, w.prior_p, w.pgz, w.pgrh, w.pgxh, w.pstats, nullptr, nullptr);
+    if (rc != 0) return rc;
+    ForecastArgs fa; memset(&fa, 0, sizeof(fa));
+    fa.rec_prev = rec_prev; fa.pstats = w.pstats; fa.ps_ld = PS_LD; fa.prior_p = w.prior_p;
+    fa.noise = noise + (size_t)f * R * 2 * N * d.nzw; fa.rec_next = w.rec + (size_t)(f + 1) * M * RW; fa.prior_next = w.prior[(f + 1) & 1];
+    fa.f = f; fa.out = out; fa.cfg = c;
+    sq_launch_forecast_step(fa, d, s);
+  }
+  // decoder of all F frames (section J of the pass without the likelihood): three M = F*B'*N row GEMMs + the canvas-only insert
+  const float* rec_all = w.rec + (size_t)M * RW;
+  float* canvas = out.canvas ? out.canvas : w.canvas;
+  const bool want_canvas = out.canvas || out.mean_canvas;
+  if (want_canvas || out.glimpse) {
+    const int MT = F * M;
+    float* gl = out.glimpse ? out.glimpse : w.glimpse;
+    Lin a; a.seg(rec_all, RW, rec::ZW).out(w.dec_a, nh).act(ACT_ELU); RUN(a, L_DEC0, MT);
+    Lin b; b.seg(w.dec_a, nh, nh).out(w.dec_b, nh).act(ACT_ELU); RUN(b, L_DEC1, MT);
+    Lin g; g.seg(w.dec_b, nh, nh).out(gl, G2); g.a.scale_ptr = flat + po.dec_output_scale; RUN(g, L_DEC2, MT);
+    if (want_canvas) {
+      InsertArgs ia; memset(&ia, 0, sizeof(ia));
+      ia.glimpse = gl; ia.rec = rec_all; ia.rec_ld = RW; ia.mean_img = flat + po.dec_mean_img; ia.canvas = canvas; ia.n_frames = F;
+      ia.std_fg = c.output_std; ia.std_bg = c.background_std;
+      if (sq_launch_insert_canvas(ia, d, s) != 0) { sq_set_error(h, "sqair_forecast: the decoder canvas launch failed (dynamic LDS limit)"); return -2; }
+    }
+  }
+  if (out.mean_canvas || out.expected_count) {
+    ForecastSummaryArgs sa; memset(&sa, 0, sizeof(sa));
+    sa.canvas = canvas; sa.rec = rec_all; sa.log_w = out.log_w; sa.mean_canvas = out.mean_canvas; sa.expected_count = out.expected_count;
+    sa.F = F;
+    sq_launch_forecast_summary(sa, d, s);
+  }
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}

@@ -254,45 +254,37 @@ class SqairCore(object):
         with torch.cuda.device(self.device):
             self._join_in()
             if train:
-                nb = self.lib.sqair_train_workspace_bytes(self.handle, self.T, self.B)
-                if getattr(self, "train_ws", None) is None or self.train_ws.numel() * 4 < nb:
-                    self.train_ws = torch.empty(nb // 4, dtype=torch.float32, device=self.device)
-                    self._clear_ws(self.train_ws, True)
-                args = list(self._args(t_offset))
-                args[9], args[10] = self.train_ws.data_ptr(), nb
-                self.check(self.lib.sqair_forward_train(*args), "sqair_forward_train")
-            elif use_graph:
-                if not self._graph_ready:
-                    torch.cuda.synchronize(self.device)
-                    self.check(self.lib.sqair_graph_capture(*self._args(t_offset)), "sqair_graph_capture")
-                    self._graph_ready = True
-                self.check(self.lib.sqair_graph_launch(self.handle, self._stream()), "sqair_graph_launch")
+                self._train_buffers()
+                self._issue_train(t_offset, backward=False)   # (the pass and the reductions)
             else:
-                self.check(self.lib.sqair_forward(*self._args(t_offset)), "sqair_forward")
-            dlp = self.out["discrete_log_prob"].data_ptr() if "discrete_log_prob" in self.out else None
-            self.check(self.lib.sqair_elbo(
-                self.handle, self.out["log_weights_per_timestep"].data_ptr(), dlp, self.T, self.B,
-                self.log_weights.data_ptr(), self.elbo_iwae_per_example.data_ptr(),
-                self.importance_weights.data_ptr(), self.vimco_signal.data_ptr(), self.scalars.data_ptr(),
-                self.c_means, len(self.mean_names), self.iw_means.data_ptr(), self._stream()), "sqair_elbo")
+                if use_graph:
+                    if not self._graph_ready:
+                        torch.cuda.synchronize(self.device)
+                        self.check(self.lib.sqair_graph_capture(*self._args(t_offset)), "sqair_graph_capture")
+                        self._graph_ready = True
+                    self.check(self.lib.sqair_graph_launch(self.handle, self._stream()), "sqair_graph_launch")
+                else:
+                    self.check(self.lib.sqair_forward(*self._args(t_offset)), "sqair_forward")
+                self._elbo()
             self._join_out()
+
+    def _elbo(self):
+        """The ELBO / VIMCO reductions of the pass just issued (no stream joins: capturable)."""
+        dlp = self.out["discrete_log_prob"].data_ptr() if "discrete_log_prob" in self.out else None
+        self.check(self.lib.sqair_elbo(
+            self.handle, self.out["log_weights_per_timestep"].data_ptr(), dlp, self.T, self.B,
+            self.log_weights.data_ptr(), self.elbo_iwae_per_example.data_ptr(),
+            self.importance_weights.data_ptr(), self.vimco_signal.data_ptr(), self.scalars.data_ptr(),
+            self.c_means, len(self.mean_names), self.iw_means.data_ptr(), self._stream()), "sqair_elbo")
 
     def backward(self, t_offset=0):
         """Full backward pass after forward(train=True): gradient of the VIMCO target / T w.r.t. every parameter.
         Leaves it in ``self.flat_grad`` (flat layout) on the core's stream; returns that tensor."""
         assert getattr(self, "train_ws", None) is not None, "backward() needs forward(train=True) first"
         with torch.cuda.device(self.device):
-            nb = self.lib.sqair_backward_bytes(self.handle, self.T, self.B)
-            if getattr(self, "bwd_scratch", None) is None or self.bwd_scratch.numel() * 4 < nb:
-                self.bwd_scratch = torch.empty(nb // 4, dtype=torch.float32, device=self.device)
-            if getattr(self, "flat_grad", None) is None:
-                self.flat_grad = torch.zeros_like(self.flat)
+            self._train_buffers()
             self._join_in()
-            self.check(self.lib.sqair_backward(
-                self.handle, self.flat.data_ptr(), self.packed.data_ptr(), self.obs.data_ptr(), self.noise.data_ptr(),
-                self.importance_weights.data_ptr(), self.vimco_signal.data_ptr(), self.T, self.B, int(t_offset),
-                self.train_ws.data_ptr(), self.train_ws.numel() * 4, self.bwd_scratch.data_ptr(), nb,
-                self.flat_grad.data_ptr(), self._stream()), "sqair_backward")
+            self._issue_train(t_offset, forward=False)
             self._join_out()
         return self.flat_grad
 
@@ -303,48 +295,53 @@ class SqairCore(object):
         if not use_graph:
             self.forward(t_offset=t_offset, train=True)
             return self.backward(t_offset=t_offset)
-        if not getattr(self, "_train_graph_ready", False) or self._train_graph_key != (self._shape, int(t_offset)):
-            # first call: run eagerly once (allocates tape / scratch, uploads the plan), then capture
-            self.forward(t_offset=t_offset, train=True)
-            self.backward(t_offset=t_offset)
+        return self._graphed((self._shape, int(t_offset)), lambda: (self.forward(t_offset=t_offset, train=True), self.backward(t_offset)),
+                             lambda: self._issue_train(t_offset), replay_after_capture=True)
+
+    def _graphed(self, key, eager, issue, replay_after_capture):
+        """The gradient-evaluation graph of ``key``, replayed; returns ``flat_grad``.  The first call for a key runs ``eager()`` once
+        (allocates tape / scratch, uploads the plan), then captures the raw calls of ``issue()`` into capture slot 1 without running
+        them.  ``replay_after_capture``: whether that first call then replays the graph too -- not when the eager run was itself
+        the step (a carried chunk: it advanced the state, a replay would step twice)."""
+        if not getattr(self, "_train_graph_ready", False) or self._train_graph_key != key:
+            eager()
             torch.cuda.synchronize(self.device)
             with torch.cuda.device(self.device):
                 self.check(self.lib.sqair_capture_begin(self.handle, self._stream()), "sqair_capture_begin")
                 try:
-                    self._issue_train(t_offset)
+                    issue()
                 finally:
                     n = self.lib.sqair_capture_end(self.handle, self._stream(), 1)
                 if n < 0:
                     self.check(n, "sqair_capture_end")
             self.train_graph_nodes = n
             self._train_graph_ready = True
-            self._train_graph_key = (self._shape, int(t_offset))
+            self._train_graph_key = key
+            if not replay_after_capture:
+                return self.flat_grad
         with torch.cuda.device(self.device):
             self._join_in()
             self.check(self.lib.sqair_capture_launch(self.handle, 1, self._stream()), "sqair_capture_launch")
             self._join_out()
         return self.flat_grad
 
-    def _issue_train(self, t_offset):
-        """The raw call sequence of a gradient evaluation on the core's stream (no stream joins: capturable)."""
-        nb = self.train_ws.numel() * 4
-        args = list(self._args(t_offset))
-        args[9], args[10] = self.train_ws.data_ptr(), nb
-        self.check(self.lib.sqair_forward_train(*args), "sqair_forward_train")
-        dlp = self.out["discrete_log_prob"].data_ptr() if "discrete_log_prob" in self.out else None
-        self.check(self.lib.sqair_elbo(
-            self.handle, self.out["log_weights_per_timestep"].data_ptr(), dlp, self.T, self.B,
-            self.log_weights.data_ptr(), self.elbo_iwae_per_example.data_ptr(),
-            self.importance_weights.data_ptr(), self.vimco_signal.data_ptr(), self.scalars.data_ptr(),
-            self.c_means, len(self.mean_names), self.iw_means.data_ptr(), self._stream()), "sqair_elbo")
-        self.check(self.lib.sqair_backward(
-            self.handle, self.flat.data_ptr(), self.packed.data_ptr(), self.obs.data_ptr(), self.noise.data_ptr(),
-            self.importance_weights.data_ptr(), self.vimco_signal.data_ptr(), self.T, self.B, int(t_offset),
-            self.train_ws.data_ptr(), nb, self.bwd_scratch.data_ptr(), self.bwd_scratch.numel() * 4,
-            self.flat_grad.data_ptr(), self._stream()), "sqair_backward")
+    def _issue_train(self, t_offset, forward=True, backward=True):
+        """The raw calls of a gradient evaluation (forward + ELBO, backward) on the core's stream (no stream joins: capturable)."""
+        ws, nb = self.train_ws.data_ptr(), self.train_ws.numel() * 4
+        if forward:
+            args = list(self._args(t_offset))
+            args[9], args[10] = ws, nb
+            self.check(self.lib.sqair_forward_train(*args), "sqair_forward_train")
+            self._elbo()
+        if backward:
+            self.check(self.lib.sqair_backward(
+                self.handle, self.flat.data_ptr(), self.packed.data_ptr(), self.obs.data_ptr(), self.noise.data_ptr(),
+                self.importance_weights.data_ptr(), self.vimco_signal.data_ptr(), self.T, self.B, int(t_offset), ws, nb,
+                self.bwd_scratch.data_ptr(), self.bwd_scratch.numel() * 4, self.flat_grad.data_ptr(), self._stream()), "sqair_backward")
 
-    # ---- training with a carried state (include/sqair_hip.h: SqairCarry) --------------------------------------------------------
     def _train_buffers(self):
+        """Sizes the tape, the backward's scratch and the flat gradient for the bound (T, B) on first use; a fresh tape is cleared
+        once (``_clear_ws``)."""
         nb = self.lib.sqair_train_workspace_bytes(self.handle, self.T, self.B)
         if getattr(self, "train_ws", None) is None or self.train_ws.numel() * 4 < nb:
             self.train_ws = torch.empty(nb // 4, dtype=torch.float32, device=self.device)
@@ -355,6 +352,7 @@ class SqairCore(object):
         if getattr(self, "flat_grad", None) is None:
             self.flat_grad = torch.zeros_like(self.flat)
 
+    # ---- training with a carried state (include/sqair_hip.h: SqairCarry) --------------------------------------------------------
     def forward_carry(self, carry):
         """forward(train=True) of a carried chunk: ``carry`` (a ``_capi.SqairCarry`` the caller keeps alive) names the blob the rows
         start from, the blob frame T goes to and optionally the SMC resampler that ends the pass."""
@@ -379,28 +377,8 @@ class SqairCore(object):
         if not use_graph:
             self.forward_carry(carry)
             return self.backward_carry(carry)
-        key = (self._shape, "carry", _carry_key(carry))
-        if not getattr(self, "_train_graph_ready", False) or self._train_graph_key != key:
-            self.forward_carry(carry)
-            self.backward_carry(carry)
-            torch.cuda.synchronize(self.device)
-            with torch.cuda.device(self.device):
-                self.check(self.lib.sqair_capture_begin(self.handle, self._stream()), "sqair_capture_begin")
-                try:
-                    self._issue_carry(carry)
-                finally:
-                    n = self.lib.sqair_capture_end(self.handle, self._stream(), 1)
-                if n < 0:
-                    self.check(n, "sqair_capture_end")
-            self.train_graph_nodes = n
-            self._train_graph_ready = True
-            self._train_graph_key = key
-            return self.flat_grad
-        with torch.cuda.device(self.device):
-            self._join_in()
-            self.check(self.lib.sqair_capture_launch(self.handle, 1, self._stream()), "sqair_capture_launch")
-            self._join_out()
-        return self.flat_grad
+        return self._graphed((self._shape, "carry", _carry_key(carry)), lambda: (self.forward_carry(carry), self.backward_carry(carry)),
+                             lambda: self._issue_carry(carry), replay_after_capture=False)
 
     def _issue_carry(self, carry, forward=True, backward=True):
         """The raw calls of a carried gradient evaluation (forward + ELBO, backward) on the core's stream: capturable."""
@@ -409,12 +387,7 @@ class SqairCore(object):
             self.check(self.lib.sqair_forward_train_carry(
                 self.handle, self.flat.data_ptr(), self.packed.data_ptr(), self.obs.data_ptr(), self.noise.data_ptr(), self.T, self.B,
                 C.byref(carry), C.byref(self.c_out), ws, nb, self._stream()), "sqair_forward_train_carry")
-            dlp = self.out["discrete_log_prob"].data_ptr() if "discrete_log_prob" in self.out else None
-            self.check(self.lib.sqair_elbo(
-                self.handle, self.out["log_weights_per_timestep"].data_ptr(), dlp, self.T, self.B,
-                self.log_weights.data_ptr(), self.elbo_iwae_per_example.data_ptr(),
-                self.importance_weights.data_ptr(), self.vimco_signal.data_ptr(), self.scalars.data_ptr(),
-                self.c_means, len(self.mean_names), self.iw_means.data_ptr(), self._stream()), "sqair_elbo")
+            self._elbo()
         if backward:
             self.check(self.lib.sqair_backward_carry(
                 self.handle, self.flat.data_ptr(), self.packed.data_ptr(), self.obs.data_ptr(), self.noise.data_ptr(),

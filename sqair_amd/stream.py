@@ -42,6 +42,7 @@ import numpy as np
 import torch
 
 from sqair_amd import _capi
+from sqair_amd.carried import CarriedState, carried
 
 DEFAULT_OUTPUTS = ("what", "where", "presence", "obj_id", "log_weights_per_timestep")
 FORECAST_OUTPUTS = ("what", "where", "presence", "presence_prob", "presence_logit", "obj_id", "canvas", "glimpse")
@@ -74,103 +75,47 @@ class SqairStream(object):
         self.use_graph = bool(use_graph)
         self.seed = int(seed)
         self.frame = 0          # frames consumed so far (host side; the rows' own counters are in the blob)
-        lib, dev = core.lib, core.device
         core.bind(self.T, self.B, list(outputs))
-        with torch.cuda.device(dev):
-            self.state = torch.zeros(lib.sqair_state_bytes(core.handle, self.B) // 4, dtype=torch.float32, device=dev)
-            self._identity = torch.arange(self.R, dtype=torch.int32, device=dev)
-            self._src = self._identity.clone()   # (frozen into the captured graph; refreshed before a step that needs another map)
-            self.log_weight_sum = torch.zeros(self.R, dtype=torch.float32, device=dev)
-            if self.smc:   # (SMC: the kernel writes _src after every pass; the first step starts every row fresh)
-                self._src.fill_(-1)
-                self.log_z = torch.zeros(self.B, dtype=torch.float32, device=dev)
-                self.log_evidence = torch.zeros(self.B, dtype=torch.float32, device=dev)
-                self.ess = torch.zeros(self.B, dtype=torch.float32, device=dev)
-                self.u = torch.zeros(self.B, dtype=torch.float32, device=dev)   # the uniform of each lane's last step
-                self.resampled = torch.zeros(self.B, dtype=torch.int32, device=dev)
-                self._uniforms = torch.zeros(self.B, dtype=torch.float32, device=dev)
-        self._src_is_identity = True   # (SMC: _src is written on the device only, never refreshed from the host)
-        # host-side source map of the next step (None: identity); first: all fresh.  SMC composes maps on the device instead.
-        self._armed = None if self.smc else np.full(self.R, -1, dtype=np.int64)
+        # the blob, the source map (host-side until a step uploads it; SMC: on the device) and the weights (sqair_amd/carried.py)
+        cs = self.carried = CarriedState(core, self.B, "SqairStream", self.smc)
         if state is not None:   # hand-over: the first step continues every row of the given blob
-            state = torch.as_tensor(state)
-            if state.dtype != torch.float32 or state.numel() != self.state.numel():
-                raise ValueError("SqairStream: state must be a float32 blob of sqair_state_bytes(core, B) = {} bytes".format(
-                    self.state.numel() * 4))
-            with torch.cuda.device(dev):
-                self.state.copy_(state.reshape(-1))
-                self._src.copy_(self._identity)
-            self._armed = None
+            cs.adopt(state)
         self._graph = False
         self._fc = {}               # forecast buffers of the LAST (F, outputs, summaries) only: workspace, noise, map, weights, outputs
         self._smc_uniforms = None   # registered with the caller's uniforms (True) or Philox (False)
         core.stream.synchronize()
-        core.check(lib.sqair_set_state(core.handle, self.state.data_ptr(), self.state.data_ptr(), self._src.data_ptr(),
-                                       self.state.numel() * 4, self.B), "sqair_set_state")
+        core.check(core.lib.sqair_set_state(core.handle, cs.state.data_ptr(), cs.state.data_ptr(), cs._src.data_ptr(),
+                                            cs.state.numel() * 4, self.B), "sqair_set_state")
         if self.smc:
             self._set_smc(False)
         core._graph_ready = False   # (the handle's graph is now this stream's)
+
+    # the carried state's, read-only (the last three: what the tests and tools look at)
+    state, log_weight_sum, log_z, log_evidence, ess, u, resampled, _src, _armed, _src_is_identity = (
+        carried(n) for n in ("state", "log_weight_sum", "log_z", "log_evidence", "ess", "u", "resampled", "_src", "_armed",
+                             "_src_is_identity"))
 
     def _set_smc(self, uniforms):
         """Registers the SMC buffers (sqair_set_smc), the lane uniforms read from ``_uniforms`` or drawn by Philox.  The pointers
         are frozen into the captured graph: switching between the two recaptures it on the next step."""
         if self._smc_uniforms is uniforms:
             return
-        smc = _capi.SqairSmc(ess_frac=self.ess_frac, seed=self.seed & 0xFFFFFFFFFFFFFFFF,
-                             uniforms=self._uniforms.data_ptr() if uniforms else None, log_w=self.log_weight_sum.data_ptr(),
-                             log_z=self.log_z.data_ptr(), log_evidence=self.log_evidence.data_ptr(), ess=self.ess.data_ptr(),
-                             u_out=self.u.data_ptr(), resampled=self.resampled.data_ptr(), src_rows=self._src.data_ptr())
+        smc = self.carried.smc_struct(self.ess_frac, self.seed, uniforms)
         core = self.core
         core.check(core.lib.sqair_set_smc(core.handle, C.byref(smc), self.B), "sqair_set_smc")
         self._smc_uniforms = uniforms
         self._graph = False
 
     # ---- source map -------------------------------------------------------------------------------------------------------
-    def _pending(self):
-        return np.arange(self.R, dtype=np.int64) if self._armed is None else self._armed
-
     def reset(self, lanes):
         """Lanes (sequences, in [0, B)) whose next step starts a new clip: their K particle rows start fresh, counter 0."""
-        lanes = np.atleast_1d(np.asarray(lanes))
-        if lanes.size and (lanes.dtype.kind not in "iu" or lanes.min() < 0 or lanes.max() >= self.B):
-            raise ValueError("SqairStream.reset: lanes must be integers in [0, {})".format(self.B))
-        if self.smc:   # on the device, after the map the last step's resampler wrote: the lane's rows fresh, its weights zero
-            core = self.core
-            with torch.cuda.device(core.device):
-                core._join_in()
-                with core.on_stream():
-                    for j in sorted(set(lanes.tolist())):
-                        self._src[j * self.K:(j + 1) * self.K].fill_(-1)
-                        self.log_weight_sum[j * self.K:(j + 1) * self.K].zero_()
-                        self.log_z[j:j + 1].zero_()
-                core._join_out()
-            return
-        m = self._pending().copy()
-        for j in lanes.tolist():
-            m[j * self.K:(j + 1) * self.K] = -1
-        self._armed = m
+        self.carried.reset(lanes)
 
     def resample(self, src_rows):
         """Row r of the next step continues row src_rows[r] (-1: starts fresh); e.g. SMC resampling of the particles of each
         sequence, src[b*K + k] = b*K + k'.  Composes with a reset armed before it.  The running log-weight sums follow the rows.
         With SMC on it composes on the device with the map the last step's resampler wrote: src_new[r] = src[src_rows[r]]."""
-        src = np.asarray(src_rows)
-        if src.shape != (self.R,) or src.dtype.kind not in "iu" or (src.size and (src.min() < -1 or src.max() >= self.R)):
-            raise ValueError("SqairStream.resample: src_rows must be {} integers in [-1, {})".format(self.R, self.R))
-        if self.smc:
-            core = self.core
-            with torch.cuda.device(core.device):
-                core._join_in()
-                with core.on_stream():
-                    s = torch.as_tensor(src.astype(np.int64)).pin_memory().to(core.device, non_blocking=True)
-                    keep = s >= 0
-                    s = s.clamp_min(0)
-                    self._src.copy_(torch.where(keep, self._src[s], torch.full_like(self._src, -1)))
-                    self.log_weight_sum.copy_(torch.where(keep, self.log_weight_sum[s], torch.zeros_like(self.log_weight_sum)))
-                core._join_out()
-            return
-        m = self._pending()
-        self._armed = np.where(src >= 0, m[np.maximum(src, 0)], -1)
+        self.carried.resample(src_rows)
 
     # ---- stepping ---------------------------------------------------------------------------------------------------------
     def step(self, frames, noise=None, seed=None, uniforms=None):
@@ -179,48 +124,15 @@ class SqairStream(object):
         keyed by (``seed`` or the stream's seed, frame index).  With SMC on, also ``ess``, ``resampled``, ``log_evidence`` [B]
         and ``ancestors`` [B*K] (the next step's source map), device copies taken before anything is read on the host;
         ``uniforms`` [B] in [0, 1): this step's systematic-resampling uniforms (default: Philox)."""
-        core = self.core
-        frames = torch.as_tensor(frames, dtype=torch.float32)
-        if frames.dim() == 5:
-            frames = frames[..., 0]
-        if tuple(frames.shape) != (self.T, self.B, core.H, core.W):
-            raise ValueError("SqairStream.step: frames of shape {} given, [{}, {}, {}, {}] expected".format(
-                tuple(frames.shape), self.T, self.B, core.H, core.W))
-        if noise is not None:
-            noise = torch.as_tensor(noise, dtype=torch.float32)
-            if noise.numel() != core.noise.numel():
-                raise ValueError("SqairStream.step: noise of shape {} given, {} expected".format(tuple(noise.shape),
-                                                                                               tuple(core.noise.shape)))
-        if uniforms is not None:
-            if not self.smc:
-                raise ValueError("SqairStream.step: uniforms are for a stream with resample='systematic'")
-            uniforms = torch.as_tensor(uniforms, dtype=torch.float32)
-            if tuple(uniforms.shape) != (self.B,):
-                raise ValueError("SqairStream.step: uniforms of shape {} given, [{}] expected".format(tuple(uniforms.shape), self.B))
+        core, cs = self.core, self.carried
+        frames, noise, uniforms = cs.check_inputs(self.T, frames, noise, uniforms, "stream")
         if self.smc:
             self._set_smc(uniforms is not None)
         lib = core.lib
         with torch.cuda.device(core.device):
             core._join_in()
             with core.on_stream():
-                core.obs.copy_(frames, non_blocking=True)
-                if noise is not None:
-                    core.noise.copy_(noise.reshape(core.noise.shape), non_blocking=True)
-                else:
-                    core.draw_noise(seed=self.seed if seed is None else int(seed), step=self.frame)
-                if uniforms is not None:
-                    self._uniforms.copy_(uniforms, non_blocking=True)
-                # (SMC: nothing armed; the source map is the one the last step's resampler wrote, resets / resamples composed in)
-                if self._armed is not None:
-                    m = torch.as_tensor(self._armed.astype(np.int32))
-                    self._src.copy_(m, non_blocking=True)
-                    lw = self.log_weight_sum[torch.as_tensor(np.maximum(self._armed, 0), device=core.device)]
-                    self.log_weight_sum.copy_(torch.where(m.to(core.device) >= 0, lw, torch.zeros_like(lw)))
-                    self._src_is_identity = False
-                    self._armed = None
-                elif not self._src_is_identity:
-                    self._src.copy_(self._identity)
-                    self._src_is_identity = True
+                cs.feed(frames, noise, uniforms, self.seed if seed is None else int(seed), self.frame)
                 if self.use_graph:
                     if not self._graph:
                         core.stream.synchronize()
@@ -231,10 +143,10 @@ class SqairStream(object):
                     core.check(lib.sqair_forward(*core._args(0)), "sqair_forward")
                 out = {k: core.out[k].clone() for k in self.outputs}
                 if self.smc:   # (log_weight_sum is the resampler's accumulator)
-                    out.update(ess=self.ess.clone(), resampled=self.resampled.clone(), log_evidence=self.log_evidence.clone(),
-                               ancestors=self._src.clone())
+                    out.update(ess=cs.ess.clone(), resampled=cs.resampled.clone(), log_evidence=cs.log_evidence.clone(),
+                               ancestors=cs._src.clone())
                 else:
-                    self.log_weight_sum += out["log_weights_per_timestep"].sum(0)
+                    cs.log_weight_sum += out["log_weights_per_timestep"].sum(0)
             core._join_out()
         self.frame += self.T
         return out
@@ -257,7 +169,7 @@ class SqairStream(object):
         bad = [n for n in outputs if n not in FORECAST_OUTPUTS]
         if bad:
             raise ValueError("SqairStream.forecast: unknown outputs {} (choose from {})".format(bad, FORECAST_OUTPUTS))
-        core = self.core
+        core, cs = self.core, self.carried
         lib, dev = core.lib, core.device
         R, N, nzw = self.R, core.N, core.nzw
         if noise is not None:
@@ -281,14 +193,14 @@ class SqairStream(object):
                                                     (self.seed if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF,
                                                     FORECAST_NOISE_TAG | self.frame, core._stream()), "sqair_fill_noise")
                 if self.smc:   # (the resampler's map and weights are already indexed by next-step rows)
-                    src, lw = self._src, self.log_weight_sum
+                    src, lw = cs._src, cs.log_weight_sum
                 else:          # the pending host-side map, uploaded into the forecast's own buffer; the weights follow it
-                    m = self._pending()
+                    m = cs.pending()
                     src = fc["src"]
                     src.copy_(torch.as_tensor(m.astype(np.int32)), non_blocking=True)
                     keep = src >= 0
                     lw = fc["log_w"]
-                    lw.copy_(torch.where(keep, self.log_weight_sum[src.long().clamp_min(0)], torch.zeros_like(lw)))
+                    lw.copy_(torch.where(keep, cs.log_weight_sum[src.long().clamp_min(0)], torch.zeros_like(lw)))
                 out = fc["out"]
                 c_out = _capi.SqairForecastOutputs(**{n: t.data_ptr() for n, t in out.items()})
                 if summaries:

@@ -13,6 +13,8 @@ import ctypes as C
 
 import numpy as np
 
+from .carried import CarriedState, carried
+
 
 def lr_schedule(F):
     """Returns (boundaries, values) of the piecewise-constant learning rate (experiment.py:127-138):
@@ -107,6 +109,20 @@ class Optimizer(object):
         core.pack()
 
 
+def _finish_step(tr, g):
+    """The tail of a training step of ``tr`` (a ``Trainer`` or a ``StreamTrainer``), on the core's stream: the l2 term, the all-reduce
+    of the flat gradient ``g`` over the ranks (the single collective of the step), the optimiser, the step count."""
+    from .dist import allreduce_flat_grads
+    core, F = tr.core, tr.F
+    l2 = float(getattr(F, "l2", 0.0))
+    if l2 != 0.0:
+        core.check(core.lib.sqair_add_l2_grad(
+            core.handle, core.flat.data_ptr(), g.data_ptr(), core.n_params, l2, core._stream()), "sqair_add_l2_grad")
+    scale = allreduce_flat_grads(g, comm=tr.comm, stream=core.stream) if tr.collective else 1.0
+    tr.opt.apply_gradients(g, learning_rate(F, tr.step_no), grad_scale=scale)
+    tr.step_no += 1
+
+
 class Trainer(object):
     """One rank of the reference's training loop (experiment.py:150-185): per step draw noise, evaluate the VIMCO
     target and its gradients on this rank's shard of sequences (ONE HIP graph replay), all-reduce the flat gradient
@@ -132,9 +148,7 @@ class Trainer(object):
         over the global batch is applied inside the optimiser kernel (``grad_scale``), so a caller that logs or clips these
         values must scale them by ``1 / world`` itself."""
         import torch
-        from . import _capi
-        from .dist import allreduce_flat_grads
-        core, F = self.core, self.F
+        core = self.core
         if obs is not None:
             obs = torch.as_tensor(obs, dtype=torch.float32)
             if obs.dim() == 5:
@@ -159,13 +173,7 @@ class Trainer(object):
             else:
                 core.draw_noise(generator)
             g = core.grad_step(use_graph=self.use_graph)
-            l2 = float(getattr(F, "l2", 0.0))
-            if l2 != 0.0:
-                core.check(core.lib.sqair_add_l2_grad(
-                    core.handle, core.flat.data_ptr(), g.data_ptr(), core.n_params, l2, core._stream()), "sqair_add_l2_grad")
-            scale = allreduce_flat_grads(g, comm=self.comm, stream=core.stream) if self.collective else 1.0
-            self.opt.apply_gradients(g, learning_rate(F, self.step_no), grad_scale=scale)
-        self.step_no += 1
+            _finish_step(self, g)
         return g
 
 
@@ -185,8 +193,6 @@ class StreamTrainer(object):
 
     def __init__(self, core_or_model, F, B, frames_per_step=1, seed=0, resample=None, use_graph=True, comm=None, collective=True,
                  outputs=("what", "where", "presence", "obj_id")):
-        import torch
-        from . import _capi
         core = getattr(core_or_model, "core", core_or_model)
         if core.cfg.sample_from_prior:
             raise ValueError("StreamTrainer: generation modes (sample_from_prior) do not carry a state")
@@ -207,78 +213,38 @@ class StreamTrainer(object):
                  "log_q_z_given_x_per_sample", "log_p_z_per_sample", "num_steps_per_sample", "num_disc_steps_per_sample",
                  "num_prop_steps_per_sample"]
         core.bind(self.T, self.B, names + [n for n in outputs if n not in names])
-        dev = core.device
-        z = lambda n, dt=torch.float32: torch.zeros(n, dtype=dt, device=dev)
-        with torch.cuda.device(dev):
-            self.state = z(core.lib.sqair_state_bytes(core.handle, self.B) // 4)
-            self._identity = torch.arange(self.R, dtype=torch.int32, device=dev)
-            self._src = self._identity.clone()   # (frozen into the captured graph; refreshed before a step that needs another map)
-            if self.smc:   # (the resampler writes _src after every step; the first step starts every row fresh)
-                self._src.fill_(-1)
-            self.log_weight_sum = z(self.R)
-            if self.smc:
-                self.log_z, self.log_evidence, self.ess, self.u = z(self.B), z(self.B), z(self.B), z(self.B)
-                self.resampled = z(self.B, torch.int32)
-                self._uniforms = z(self.B)
-        self._armed = None if self.smc else np.full(self.R, -1, dtype=np.int64)   # host-side map of the next step; first: all fresh
-        self._src_is_identity = True
+        # the blob, the source map (host-side until a step uploads it; SMC: the resampler's) and the weights (sqair_amd/carried.py)
+        self.carried = CarriedState(core, self.B, "StreamTrainer", self.smc)
         self._carries = {}      # SqairCarry (and its SqairSmc) per uniforms mode, kept alive while the trainer lives
         core.stream.synchronize()
 
-    @property
-    def ancestors(self):
-        """SMC: the source map of the next step (written by the resampler)."""
-        return self._src
+    # the carried state's, read-only; ``ancestors`` (SMC): the source map of the next step, written by the resampler
+    state, log_weight_sum, log_z, log_evidence, ess, u, resampled, ancestors = (
+        carried(n) for n in ("state", "log_weight_sum", "log_z", "log_evidence", "ess", "u", "resampled", "_src"))
 
     def _carry(self, uniforms):
         from . import _capi
         c = self._carries.get(uniforms)
         if c is None:
-            smc = None
-            if self.smc:
-                smc = _capi.SqairSmc(ess_frac=1.0, seed=self.seed & 0xFFFFFFFFFFFFFFFF,
-                                     uniforms=self._uniforms.data_ptr() if uniforms else None, log_w=self.log_weight_sum.data_ptr(),
-                                     log_z=self.log_z.data_ptr(), log_evidence=self.log_evidence.data_ptr(), ess=self.ess.data_ptr(),
-                                     u_out=self.u.data_ptr(), resampled=self.resampled.data_ptr(), src_rows=self._src.data_ptr())
-            c = _capi.SqairCarry(state_in=self.state.data_ptr(), state_out=self.state.data_ptr(), src_rows=self._src.data_ptr(),
-                                 state_bytes=self.state.numel() * 4, B=self.B, smc=C.pointer(smc) if smc is not None else None)
+            cs = self.carried
+            smc = cs.smc_struct(1.0, self.seed, uniforms) if self.smc else None
+            c = _capi.SqairCarry(state_in=cs.state.data_ptr(), state_out=cs.state.data_ptr(), src_rows=cs._src.data_ptr(),
+                                 state_bytes=cs.state.numel() * 4, B=self.B, smc=C.pointer(smc) if smc is not None else None)
             self._carries[uniforms] = c
             c._smc = smc   # (the SqairSmc the pointer names lives as long as the carry)
         return c
 
     # ---- source map (SqairStream's semantics) ------------------------------------------------------------------------------
-    def _pending(self):
-        return np.arange(self.R, dtype=np.int64) if self._armed is None else self._armed
-
     def reset(self, lanes):
         """Lanes (in [0, B)) whose next step starts a new clip: their K particle rows start fresh, counter 0."""
-        import torch
-        lanes = np.atleast_1d(np.asarray(lanes))
-        if lanes.size and (lanes.dtype.kind not in "iu" or lanes.min() < 0 or lanes.max() >= self.B):
-            raise ValueError("StreamTrainer.reset: lanes must be integers in [0, {})".format(self.B))
-        if self.smc:   # on the device, after the map the last step's resampler wrote
-            core = self.core
-            with core.on_stream():
-                for j in sorted(set(lanes.tolist())):
-                    self._src[j * self.K:(j + 1) * self.K].fill_(-1)
-                    self.log_weight_sum[j * self.K:(j + 1) * self.K].zero_()
-                    self.log_z[j:j + 1].zero_()
-            return
-        m = self._pending().copy()
-        for j in lanes.tolist():
-            m[j * self.K:(j + 1) * self.K] = -1
-        self._armed = m
+        self.carried.reset(lanes)
 
     def resample(self, src_rows):
         """Row r of the next step continues row src_rows[r] (-1: fresh); composes with a reset armed before it.  Not with SMC (the
         resampler writes the map)."""
         if self.smc:
             raise ValueError("StreamTrainer.resample: the SMC resampler writes the source map (resample='systematic')")
-        src = np.asarray(src_rows)
-        if src.shape != (self.R,) or src.dtype.kind not in "iu" or (src.size and (src.min() < -1 or src.max() >= self.R)):
-            raise ValueError("StreamTrainer.resample: src_rows must be {} integers in [-1, {})".format(self.R, self.R))
-        m = self._pending()
-        self._armed = np.where(src >= 0, m[np.maximum(src, 0)], -1)
+        self.carried.resample(src_rows)
 
     # ---- stepping ------------------------------------------------------------------------------------------------------------
     def step(self, frames, noise=None, seed=None, uniforms=None, global_batch=None, b0=0):
@@ -286,54 +252,13 @@ class StreamTrainer(object):
         keyed by (``seed`` or the trainer's seed, the chunk's first frame, position in the global batch ``global_batch`` / ``b0``));
         ``uniforms`` [B] (SMC only: the resampler's uniforms; default Philox).  Asynchronous on the core's stream.  Returns the
         flat gradient buffer after the optimiser step (on a multi-rank job the SUM over the ranks, as ``Trainer.step``)."""
-        import torch
-        from .dist import allreduce_flat_grads
-        core, F = self.core, self.F
-        frames = torch.as_tensor(frames, dtype=torch.float32)
-        if frames.dim() == 5:
-            frames = frames[..., 0]
-        if tuple(frames.shape) != (self.T, self.B, core.H, core.W):
-            raise ValueError("StreamTrainer.step: frames of shape {} given, [{}, {}, {}, {}] expected".format(
-                tuple(frames.shape), self.T, self.B, core.H, core.W))
-        if noise is not None:
-            noise = torch.as_tensor(noise, dtype=torch.float32)
-            if noise.numel() != core.noise.numel():
-                raise ValueError("StreamTrainer.step: noise of shape {} given, {} expected".format(tuple(noise.shape),
-                                                                                                 tuple(core.noise.shape)))
-        if uniforms is not None:
-            if not self.smc:
-                raise ValueError("StreamTrainer.step: uniforms are for a trainer with resample='systematic'")
-            uniforms = torch.as_tensor(uniforms, dtype=torch.float32)
-            if tuple(uniforms.shape) != (self.B,):
-                raise ValueError("StreamTrainer.step: uniforms of shape {} given, [{}] expected".format(tuple(uniforms.shape), self.B))
+        core, cs = self.core, self.carried
+        frames, noise, uniforms = cs.check_inputs(self.T, frames, noise, uniforms, "trainer")
         with core.on_stream():
-            core.obs.copy_(frames, non_blocking=True)
-            if noise is not None:
-                core.noise.copy_(noise.reshape(core.noise.shape), non_blocking=True)
-            else:
-                core.draw_noise(seed=self.seed if seed is None else int(seed), step=self.frame, global_batch=global_batch, b0=b0)
-            if uniforms is not None:
-                self._uniforms.copy_(uniforms, non_blocking=True)
-            if not self.smc:
-                if self._armed is not None:
-                    m = torch.as_tensor(self._armed.astype(np.int32))
-                    self._src.copy_(m, non_blocking=True)
-                    lw = self.log_weight_sum[torch.as_tensor(np.maximum(self._armed, 0), device=core.device)]
-                    self.log_weight_sum.copy_(torch.where(m.to(core.device) >= 0, lw, torch.zeros_like(lw)))
-                    self._src_is_identity = False
-                    self._armed = None
-                elif not self._src_is_identity:
-                    self._src.copy_(self._identity)
-                    self._src_is_identity = True
+            cs.feed(frames, noise, uniforms, self.seed if seed is None else int(seed), self.frame, global_batch=global_batch, b0=b0)
             g = core.grad_step_carry(self._carry(uniforms is not None), use_graph=self.use_graph)
             if not self.smc:
-                self.log_weight_sum += core.out["log_weights_per_timestep"].sum(0)
-            l2 = float(getattr(F, "l2", 0.0))
-            if l2 != 0.0:
-                core.check(core.lib.sqair_add_l2_grad(
-                    core.handle, core.flat.data_ptr(), g.data_ptr(), core.n_params, l2, core._stream()), "sqair_add_l2_grad")
-            scale = allreduce_flat_grads(g, comm=self.comm, stream=core.stream) if self.collective else 1.0
-            self.opt.apply_gradients(g, learning_rate(F, self.step_no), grad_scale=scale)
-        self.step_no += 1
+                cs.log_weight_sum += core.out["log_weights_per_timestep"].sum(0)
+            _finish_step(self, g)
         self.frame += self.T
         return g
