@@ -247,6 +247,76 @@ int sqair_set_smc(SqairHandle* h, const SqairSmc* smc, int B);   /* NULL smc: of
 int sqair_smc_resample_test(SqairHandle* h, const float* lw, int T, int B, int K, const int32_t* t_row, const SqairSmc* smc,
                             void* stream);
 
+/* ---- track history: the last L passes kept on the device, traced into fixed-lag smoothed trajectories -------------------------
+ * With a history set, every following inference pass with a carried state ends with one more kernel, k_history_push, after the
+ * state export and BEFORE the SMC resampler (which overwrites the source map the push records).  It writes slot (passes pushed
+ * so far) mod L of a ring, an OPAQUE device blob of sqair_history_bytes(h, L, T, B, fields) bytes that the caller ZERO-FILLS before
+ * registering it (zeroing it again forgets the history).  A slot holds, for one pass of T frames:
+ *   the chosen per-frame outputs [T, B*K, N, .] in their own widths (n_what, not the record's padded width), 32-bit words copied
+ *     as they are out of the pass's SqairOutputs buffers (the pass must bind them: a NULL one is refused at pass time);
+ *   parent[B*K]  the source map the pass imported through, as k_state_import read it: -1 = the row started fresh (also: no
+ *     state_in, an index outside [0, B*K)), identity without a map;
+ *   t0[B*K]      the row's frame counter at frame 0 of the pass (the index the time-dependent step prior saw).
+ * The number of passes pushed lives in the ring's header ON THE DEVICE; the kernel reads and advances it, so one captured graph
+ * serves every pass, the wrap-around included.  All passes pushed into one ring have the same T (a pass with another T is refused).
+ * A pass with history on has exactly one graph node more; with history off nothing is launched.
+ * `fields`: a bit set; where, presence and obj_id are mandatory.
+ * Refused (return -1, text in sqair_last_error, before any HIP call): no state set, L < 1, fields without the mandatory three or
+ * with unknown bits, ring_bytes < sqair_history_bytes(h, L, 1, B of the state, fields); at pass time: a B other than the
+ * state's, ring_bytes < sqair_history_bytes for the pass's T, a T other than the ring's earlier passes', a NULL output among the
+ * fields.  NULL ring: off.  sqair_set_state switching the state off switches history off too.  Training passes
+ * (sqair_forward_train*, sqair_forward_train_carry) never push: a history for training on streams is out of scope. */
+#define SQAIR_HIST_WHERE    1u
+#define SQAIR_HIST_PRESENCE 2u
+#define SQAIR_HIST_OBJ_ID   4u
+#define SQAIR_HIST_WHAT     8u
+#define SQAIR_HIST_LOG_W    16u   /* log_weights_per_timestep */
+#define SQAIR_HIST_MANDATORY 7u
+#define SQAIR_HIST_ALL       31u
+int64_t sqair_history_bytes(const SqairHandle* h, int L, int T, int B, uint32_t fields);   /* -1: bad arguments */
+int sqair_set_history(SqairHandle* h, void* ring, int64_t ring_bytes, int L, uint32_t fields);
+/* Traces the ancestral path of every particle row back over the last `lag` passes of `ring` (the ring registered with
+ * sqair_set_history; 1 <= lag <= L): the trajectories of the surviving particles, i.e. the fixed-lag smoothing distribution of
+ * the filter.  Passes never pushed, or already overwritten, count as absent.
+ * Start rows:  src_next == NULL: the rows of the LAST pass's outputs, a = r;
+ *              src_next [B*K] : the rows the NEXT pass would start from, a = src_next[r] (the forecast's convention; after an
+ *                               SMC resampling the equally weighted surviving set); -1 (or out of range) gives an empty path.
+ * The walk, from the newest pass i = lag - 1 to the oldest i = 0:  ancestor_row[i, r] = a;  a = parent_i[a].  A fresh row (-1)
+ * ends the path: every older frame of r is invalid.
+ * Outputs, every pointer optional, frames ordered oldest -> newest, frame f = i * T + t of F = lag * T:
+ *   where / presence / obj_id / what / log_w: the stored 32-bit words of the ancestor's row, zero where invalid (what / log_w
+ *     only when the ring holds the field);  valid = 1 / 0;  frame_index = t0 + t, -1 where invalid;
+ *   unique_ancestors[i, b]: the number of distinct ancestor rows among lane b's K paths at pass i (path degeneracy: how far
+ *     back the smoothing still has more than one hypothesis).
+ * Track table (any of the track_* pointers set; max_tracks = M >= 1): slots are not tracks, compaction moves an object between
+ * them.  Per traced row, the ids present (presence == 1) in at least one valid frame of its path, ascending, the first M of them:
+ *   track_id [R, M] (-1 padded), n_tracks [R] the true distinct count (above M: the table was truncated),
+ *   track_present [F, R, M] 1 / 0 and track_where [F, R, M, 4], zero where the id is absent in that frame.
+ * Everything is a copy or an integer count: the same bits on every replay.  Writes `out` and the ring's own trace scratch only
+ * (nothing a pass reads), so it may interleave with passes; capturable (no host sync, no allocation).  One trace at a time per ring.
+ * Refused (return -1, text in sqair_last_error, before any HIP call): no history set or a ring other than the registered one,
+ * lag < 1 or > L, a NULL out, out->T < 1 or other than the T of the passes pushed, what / log_w asked of a ring without the
+ * field, a track pointer with max_tracks outside [1, 1024]. */
+typedef struct SqairTraceOutputs {
+  int32_t T;                 /* frames per pass the buffers are sized for (F = lag * T) */
+  int32_t max_tracks;        /* M of the track table; read only when a track_* pointer is set */
+  float* where;              /* [F,B',N,4] */
+  float* presence;           /* [F,B',N] */
+  float* obj_id;             /* [F,B',N] */
+  float* what;               /* [F,B',N,n_what] */
+  float* log_w;              /* [F,B'] */
+  int32_t* valid;            /* [F,B'] */
+  int32_t* frame_index;      /* [F,B'] */
+  int32_t* ancestor_row;     /* [lag,B'] */
+  int32_t* unique_ancestors; /* [lag,B] */
+  int32_t* track_id;         /* [B',M] */
+  int32_t* n_tracks;         /* [B'] */
+  float* track_present;      /* [F,B',M] */
+  float* track_where;        /* [F,B',M,4] */
+} SqairTraceOutputs;
+int sqair_history_trace(SqairHandle* h, void* ring, const int32_t* src_next, int lag, const SqairTraceOutputs* out,
+                        void* stream);
+
 /* ---- forecasting: the generative prior rolled forward from a carried state ------------------------------------------------
  * A forecast of F frames starts from the rows the NEXT pass would start from: state_in of sqair_set_state gathered through a source
  * map (src_rows, or the map given to sqair_set_state when NULL; -1 = the fresh initial state, as a pass's import).  Frame f = 0..F-1

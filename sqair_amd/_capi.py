@@ -64,6 +64,18 @@ class SqairForecastOutputs(C.Structure):
                                           "log_w", "mean_canvas", "expected_count")]
 
 
+# track history (include/sqair_hip.h: sqair_set_history): the bit of each field a ring slot may hold; the first three are mandatory
+HISTORY_FIELDS = {"where": 1, "presence": 2, "obj_id": 4, "what": 8, "log_weights_per_timestep": 16}
+HISTORY_MANDATORY = ("where", "presence", "obj_id")
+TRACE_FIELDS = ("where", "presence", "obj_id", "what", "log_w", "valid", "frame_index", "ancestor_row", "unique_ancestors", "track_id",
+                "n_tracks", "track_present", "track_where")
+
+
+class SqairTraceOutputs(C.Structure):
+    """Outputs of sqair_history_trace (include/sqair_hip.h); T = frames per pass, every pointer a device address or None."""
+    _fields_ = [("T", C.c_int32), ("max_tracks", C.c_int32)] + [(n, C.c_void_p) for n in TRACE_FIELDS]
+
+
 _PROTOS = {
     "sqair_abi_version": (C.c_int, []),
     "sqair_build_id": (C.c_char_p, []),
@@ -133,6 +145,9 @@ _PROTOS = {
     "sqair_set_smc": (C.c_int, [C.c_void_p, C.POINTER(SqairSmc), C.c_int]),
     "sqair_smc_resample_test": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(SqairSmc),
                                          C.c_void_p]),
+    "sqair_history_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32]),
+    "sqair_set_history": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_uint32]),
+    "sqair_history_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SqairTraceOutputs), C.c_void_p]),
     "sqair_forecast_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
     "sqair_forecast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                  C.POINTER(SqairForecastOutputs), C.c_void_p, C.c_int64, C.c_void_p]),

@@ -59,7 +59,8 @@ class SourceMap(object):
 class CarriedState(SourceMap):
     """The device side: ``state`` (the blob), ``_src`` (the source map the pass reads, frozen into captured graphs),
     ``log_weight_sum`` [R] and, with ``smc``, the resampler's ``log_z``, ``log_evidence``, ``ess``, ``u``, ``resampled`` [B] and its
-    ``_uniforms`` input.  With SMC the kernel writes ``_src`` after every pass and nothing is ever armed on the host."""
+    ``_uniforms`` input.  With SMC the kernel writes ``_src`` after every pass and nothing is ever armed on the host.  ``ring``: the
+    track history's device ring of the last ``history`` steps (``set_history``), or None."""
 
     def __init__(self, core, B, who, smc):
         import torch
@@ -80,6 +81,48 @@ class CarriedState(SourceMap):
                 self._uniforms = z(self.B)
                 self._armed = None
         self._src_is_identity = True   # (SMC: _src is written on the device only, never refreshed from the host)
+        self.ring, self.history, self.history_fields = None, None, ()   # the track history's ring (set_history)
+
+    @staticmethod
+    def check_history(L, fields, who):
+        """The fields a ring of the last ``L`` steps holds: ``fields`` (of _capi.HISTORY_FIELDS) plus the mandatory three."""
+        from . import _capi
+        if isinstance(L, bool) or not isinstance(L, (int, np.integer)) or L < 1:
+            raise ValueError("{}: history must be an integer >= 1 (the number of steps kept) or None".format(who))
+        fields = (fields,) if isinstance(fields, str) else tuple(fields)
+        bad = [f for f in fields if f not in _capi.HISTORY_FIELDS]
+        if bad:
+            raise ValueError("{}: unknown history_fields {} (choose from {})".format(who, bad, tuple(_capi.HISTORY_FIELDS)))
+        return tuple(f for f in _capi.HISTORY_FIELDS if f in fields or f in _capi.HISTORY_MANDATORY)
+
+    def set_history(self, L, fields, T):
+        """Allocates the zero-filled ring of the last ``L`` steps of ``T`` frames holding ``fields`` (check_history) and returns
+        (ring, bytes, field bits) for sqair_set_history."""
+        import torch
+        from . import _capi
+        fields = self.check_history(L, fields, self.who)
+        bits = sum(_capi.HISTORY_FIELDS[f] for f in fields)
+        core = self.core
+        nb = core.lib.sqair_history_bytes(core.handle, int(L), int(T), self.B, bits)
+        if nb < 0:
+            raise RuntimeError("sqair_history_bytes failed")
+        with torch.cuda.device(core.device):
+            self.ring = torch.zeros(nb // 4, dtype=torch.int32, device=core.device)
+        self.history, self.history_fields = int(L), fields
+        return self.ring, nb, bits
+
+    def next_rows(self, src_buf, lw_buf):
+        """The rows the next step would start from, on the core's stream: (source map int32 [R], running log weights [R] gathered
+        through it).  With SMC these are the resampler's own ``_src`` and ``log_weight_sum`` (already indexed by next-step rows);
+        else the pending host-side map is uploaded into ``src_buf`` and the weights that follow it into ``lw_buf``.  What
+        ``forecast`` and ``tracks`` start from and weigh by."""
+        import torch
+        if self.smc:
+            return self._src, self.log_weight_sum
+        src_buf.copy_(torch.as_tensor(self.pending().astype(np.int32)), non_blocking=True)
+        keep = src_buf >= 0
+        lw_buf.copy_(torch.where(keep, self.log_weight_sum[src_buf.long().clamp_min(0)], torch.zeros_like(lw_buf)))
+        return src_buf, lw_buf
 
     def adopt(self, state):
         """Hand-over: the first step continues every row of the given blob (copied)."""

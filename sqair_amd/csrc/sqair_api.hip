@@ -1005,7 +1005,7 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
                     int T, int B, int t_offset, const SqairOutputs* outp, float* wsbase, int64_t ws_bytes,
                     hipStream_t s, bool train, int parts, const SqStateRes* carry = nullptr) {
   const SqairConfig& c = h->cfg;
-  if (!carry && (sq_state_refusal(h, train, B, t_offset) != 0 || sq_smc_refusal(h, outp) != 0)) return -1;
+  if (!carry && (sq_state_refusal(h, train, B, t_offset) != 0 || sq_smc_refusal(h, outp) != 0 || sq_history_refusal(h, T, B, outp) != 0)) return -1;
   const SqStateRes st = carry ? *carry : sq_handle_state(h);
   if (!flat || !packed || !obs || !noise || !outp || !wsbase || T < 1 || B < 1) {
     sq_set_error(h, "sqair_forward: null argument or bad T/B");
@@ -1376,6 +1376,9 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
     sq_copy(out.final_last_used_id, w.last_id[T & 1], (int64_t)R, s);
   // carried state: frame T's rows into the caller's blob (after every reader of the imported rows: in place is fine)
   if (st.on && st.out) sq_launch_state_export(state_at(T, T), s);
+  // track history: this pass's rows, the map it imported through and its counters into the ring (sqair_set_history) -- before the
+  // resampler overwrites that map
+  if (st.hist_on) sq_launch_history_push(sq_history_push_args(h, st, out, w.t_row, T, B), s);
   // SMC: this pass's log weights -> ESS, evidence and the next pass's source map (sqair_set_smc / SqairCarry.smc)
   if (st.smc_on) sq_launch_smc_resample(sq_smc_args(st.smc, out.log_weights_per_timestep, w.t_row, T, B, K), s);
   SQ_CHECK_HIP(hipGetLastError());
@@ -1654,18 +1657,21 @@ extern "C" int sqair_graph_capture(SqairHandle* h, const float* flat_params, con
                                    const float* noise, int T, int B, int t_offset, const SqairOutputs* out,
                                    void* workspace, int64_t workspace_bytes, void* stream) {
   if (!h) return -1;
-  if (sq_state_refusal(h, false, B, t_offset) != 0 || sq_smc_refusal(h, out) != 0) return -1;
+  if (sq_state_refusal(h, false, B, t_offset) != 0 || sq_smc_refusal(h, out) != 0 || sq_history_refusal(h, T, B, out) != 0) return -1;
   hipStream_t s = (hipStream_t)stream;
   if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
   if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
   if (h->opt_slot_chain) {  // one eager pass: the chain launches' op tables are uploaded outside the capture (sqair_chain.hip)
-    void* const state_out = h->state_out;   // (a carried state is imported but not exported, nor resampled: the capture leaves
-    const bool smc_on = h->smc_on;           //  the state, its source map and the SMC weights as they were)
+    void* const state_out = h->state_out;   // (a carried state is imported but not exported, resampled or pushed: the capture
+    const bool smc_on = h->smc_on;           //  leaves the state, its source map, the SMC weights and the history as they were)
+    const bool hist_on = h->hist_on;
     h->state_out = nullptr;
     h->smc_on = false;
+    h->hist_on = false;
     const int rc0 = forward_impl(h, flat_params, (const float*)packed, obs, noise, T, B, t_offset, out, (float*)workspace, workspace_bytes, s);
     h->state_out = state_out;
     h->smc_on = smc_on;
+    h->hist_on = hist_on;
     if (rc0 != 0) return rc0;
     SQ_CHECK_HIP(hipStreamSynchronize(s));
   }

@@ -250,6 +250,41 @@ struct SmcArgs {
 };
 int sq_launch_smc_resample(const SmcArgs& a, hipStream_t s);
 
+// Track history (sqair_set_history / sqair_history_trace).  The ring, 32-bit words:
+//   header [SQ_HIST_HDR]: word 0 = passes pushed so far (advanced by k_history_push), word 1 = its workgroups' arrival count
+//   trace scratch [L][R]: the ancestor rows of the last trace (k_history_walk -> k_history_gather / k_track_table)
+//   L slots of `slot_words`: parent [R] | t0 [R] | where [T][R][N][4] | presence [T][R][N] | obj_id [T][R][N] |
+//                            what [T][R][N][nw] (with the field) | log_w [T][R] (with the field)
+constexpr int SQ_HIST_HDR = 64;
+constexpr int SQ_HIST_PUSH_WORDS = 1024;   // words of a slot one workgroup of k_history_push copies
+constexpr int SQ_HIST_MAX_TRACKS = 1024;
+struct HistLayout {
+  int L, T, R, N, nw, K;
+  unsigned fields;
+  long long o_where, o_pres, o_id, o_what, o_lw;   // offsets inside a slot (parent at 0, t0 at R); -1: field absent
+  long long slot_words, scratch, slots, total;     // words; scratch / slots: offsets from the ring's base
+};
+struct HistPushArgs {
+  unsigned* ring;
+  HistLayout lay;
+  const float *where, *presence, *obj_id, *what, *lw;   // the pass's outputs
+  const int* src;       // the map the pass imported through, or NULL = identity
+  int have_in;          // 0: no state_in, every row started fresh
+  const int* t_row;     // [R]
+};
+int sq_launch_history_push(const HistPushArgs& a, hipStream_t s);
+struct HistTraceArgs {
+  unsigned* ring;
+  HistLayout lay;
+  const int* src_next;   // [R] or NULL
+  int lag, M;
+  float *where, *presence, *obj_id, *what, *log_w;
+  int *valid, *frame_index, *ancestor_row, *unique_ancestors;
+  int *track_id, *n_tracks;
+  float *track_present, *track_where;
+};
+int sq_launch_history_trace(const HistTraceArgs& a, hipStream_t s);
+
 // Generation modes (sqair_modules.py:157-170, :294-302).  Generation record of slot (r, k), 64 floats:
 //   [0:4] where ~ prior, [4:54] what ~ prior, [54] presence ~ Bernoulli(prior logit), [55] the posterior path's own
 //   propagation presence, [56] the posterior path's own discovery presence of step k

@@ -233,6 +233,206 @@ int sq_launch_smc_resample(const SmcArgs& a, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// track history (sqair_set_history / sqair_history_trace; the ring's layout: HistLayout in sqair_glue.h)
+// ------------------------------------------------------------------------------------------------
+// Header words: 0 = the slot the next push writes (0 .. L-1), 1 = slots filled so far (saturates at L), 2 = arrival count of the
+// running push's workgroups (0 between launches).  Position and fill level instead of one ever-growing count: nothing wraps,
+// however long the stream runs.
+//
+// k_history_push: one pass's rows into the slot at the head, SQ_HIST_PUSH_WORDS words per workgroup, 32-bit words copied as they
+// are.  Every workgroup reads the head before it copies; the last one to arrive (a device-scope counter) advances it, so no
+// workgroup can see the head of the next pass.  Launched after k_state_export and BEFORE k_smc_resample, which overwrites `src`.
+__global__ __launch_bounds__(256) void k_history_push(const HistPushArgs a, int nwg SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ unsigned s_head;
+  const HistLayout& y = a.lay;
+  const int tid = threadIdx.x, R = y.R;
+  if (tid == 0) s_head = __hip_atomic_load(&a.ring[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) % (unsigned)y.L;
+  __syncthreads();
+  const unsigned head = s_head;
+  unsigned* slot = a.ring + y.slots + (long long)head * y.slot_words;
+  const long long used = y.o_lw + ((y.fields & SQAIR_HIST_LOG_W) ? (long long)y.T * R : 0);
+  const long long w0 = (long long)blockIdx.x * SQ_HIST_PUSH_WORDS;
+  auto word = [](const float* p, long long i) { return reinterpret_cast<const unsigned*>(p)[i]; };
+#pragma unroll
+  for (int j = 0; j < SQ_HIST_PUSH_WORDS / 256; ++j) {
+    const long long w = w0 + j * 256 + tid;
+    if (w >= y.slot_words) break;
+    unsigned v = 0u;   // (the slot's padding)
+    if (w < R) {       // parent: the map as k_state_import read it
+      int p = !a.have_in ? -1 : (a.src != nullptr ? a.src[w] : (int)w);
+      if (p < 0 || p >= R) p = -1;
+      v = (unsigned)p;
+    } else if (w < y.o_where) v = (unsigned)a.t_row[w - R];
+    else if (w < y.o_pres) v = word(a.where, w - y.o_where);
+    else if (w < y.o_id) v = word(a.presence, w - y.o_pres);
+    else if (w < y.o_what) v = word(a.obj_id, w - y.o_id);
+    else if (w < y.o_lw) v = word(a.what, w - y.o_what);
+    else if (w < used) v = word(a.lw, w - y.o_lw);
+    slot[w] = v;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    __threadfence();
+    if (atomicAdd(&a.ring[2], 1u) == (unsigned)(nwg - 1)) {   // the last workgroup: every other one has read the head
+      const unsigned cnt = __hip_atomic_load(&a.ring[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&a.ring[2], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&a.ring[1], cnt < (unsigned)y.L ? cnt + 1u : (unsigned)y.L, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&a.ring[0], (head + 1u) % (unsigned)y.L, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+int sq_launch_history_push(const HistPushArgs& a, hipStream_t s) {
+  const int nwg = (int)((a.lay.slot_words + SQ_HIST_PUSH_WORDS - 1) / SQ_HIST_PUSH_WORDS);
+  SQ_LAUNCH(k_history_push, dim3(nwg), dim3(256), 0, s, a, nwg);
+  return 0;
+}
+
+// the slot of the pass j passes back from the newest (j < slots filled)
+__device__ inline const unsigned* sq_hist_slot(const unsigned* ring, const HistLayout& y, unsigned pos, int j) {
+  return ring + y.slots + (long long)((pos + (unsigned)(y.L - 1 - j)) % (unsigned)y.L) * y.slot_words;
+}
+// k_history_walk: one workgroup per lane, thread k = the lane's row k.  `lag` dependent 4-byte loads per thread: a = start row,
+// then a = parent_i[a] from the newest pass back; the ancestor rows go to the ring's scratch (the two kernels below read them)
+// and to the caller.  The distinct count of a lane: a row counts when no lower k of the lane holds the same ancestor.
+__global__ __launch_bounds__(256) void k_history_walk(const HistTraceArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ int s_a[SQ_MAX_K];
+  const HistLayout& y = a.lay;
+  const int b = blockIdx.x, k = threadIdx.x, K = y.K, R = y.R, L = y.L, r = b * K + k;
+  const unsigned pos = a.ring[0] % (unsigned)L;
+  const int cnt = (int)min(a.ring[1], (unsigned)L);
+  int* scratch = reinterpret_cast<int*>(a.ring + y.scratch);
+  int cur = -1;
+  if (k < K) {
+    cur = a.src_next != nullptr ? a.src_next[r] : r;
+    if (cur < 0 || cur >= R) cur = -1;
+  }
+  for (int j = 0; j < a.lag; ++j) {
+    const int i = a.lag - 1 - j;
+    if (j >= cnt) cur = -1;   // never pushed, or already overwritten
+    if (k < K) {
+      s_a[k] = cur;
+      scratch[(size_t)i * R + r] = cur;
+      if (a.ancestor_row != nullptr) a.ancestor_row[(size_t)i * R + r] = cur;
+    }
+    __syncthreads();
+    int first = 0;
+    if (k < K && cur >= 0) {
+      first = 1;
+      for (int q = 0; q < k; ++q)
+        if (s_a[q] == cur) { first = 0; break; }
+    }
+    const int n = __syncthreads_count(first);
+    if (k == 0 && a.unique_ancestors != nullptr) a.unique_ancestors[(size_t)i * (R / K) + b] = n;
+    if (cur >= 0) {
+      const int p = (int)sq_hist_slot(a.ring, y, pos, j)[cur];
+      cur = (p < 0 || p >= R) ? -1 : p;
+    }
+  }
+}
+// k_history_gather: workgroup (r, i) copies the T frames of pass i at the ancestor's row into frames i * T .. of row r
+__global__ __launch_bounds__(256) void k_history_gather(const HistTraceArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  const HistLayout& y = a.lay;
+  const int R = y.R, r = blockIdx.x % R, i = blockIdx.x / R, tid = threadIdx.x, T = y.T, N = y.N, nw = y.nw;
+  const int ar = reinterpret_cast<const int*>(a.ring + y.scratch)[(size_t)i * R + r];
+  const unsigned* sl = sq_hist_slot(a.ring, y, a.ring[0] % (unsigned)y.L, a.lag - 1 - i);
+  auto copy = [&](float* dst, long long off, int t, int width) {   // dst [F][R][width] <- slot section [T][R][width]
+    if (dst == nullptr) return;
+    unsigned* o = reinterpret_cast<unsigned*>(dst) + ((size_t)(i * T + t) * R + r) * width;
+    const unsigned* in = sl + off + ((size_t)t * R + (ar < 0 ? 0 : ar)) * width;
+    for (int e = tid; e < width; e += 256) o[e] = ar < 0 ? 0u : in[e];
+  };
+  for (int t = 0; t < T; ++t) {
+    copy(a.where, y.o_where, t, N * 4);
+    copy(a.presence, y.o_pres, t, N);
+    copy(a.obj_id, y.o_id, t, N);
+    copy(a.what, y.o_what, t, N * nw);
+    copy(a.log_w, y.o_lw, t, 1);
+    if (tid == 0) {
+      const size_t o = (size_t)(i * T + t) * R + r;
+      if (a.valid != nullptr) a.valid[o] = ar >= 0;
+      if (a.frame_index != nullptr) a.frame_index[o] = ar < 0 ? -1 : (int)sl[R + ar] + t;
+    }
+  }
+}
+// k_track_table: one workgroup per traced row.  The ids present in a valid frame of the row's path, ascending: repeated selection
+// of the smallest id above the last one chosen (an integer minimum over the F * N candidates: the order of the threads does not
+// matter), until none is left -- the first M are kept, all are counted.  Then one thread per (frame, track) looks the id up among
+// the frame's N slots.
+__global__ __launch_bounds__(256) void k_track_table(const HistTraceArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ int s_ids[SQ_HIST_MAX_TRACKS];
+  __shared__ int s_best;
+  const HistLayout& y = a.lay;
+  const int r = blockIdx.x, tid = threadIdx.x, R = y.R, T = y.T, N = y.N, M = a.M;
+  const int* anc = reinterpret_cast<const int*>(a.ring + y.scratch);
+  const unsigned pos = a.ring[0] % (unsigned)y.L;
+  constexpr int NONE = 0x7fffffff;
+  const int C = a.lag * T * N;
+  int last = -1, count = 0;
+  for (;;) {
+    if (tid == 0) s_best = NONE;
+    __syncthreads();
+    int loc = NONE;
+    for (int c = tid; c < C; c += 256) {
+      const int i = c / (T * N), t = (c / N) % T, n = c % N;
+      const int ar = anc[(size_t)i * R + r];
+      if (ar < 0) continue;
+      const float* sl = reinterpret_cast<const float*>(sq_hist_slot(a.ring, y, pos, a.lag - 1 - i));
+      const size_t o = ((size_t)t * R + ar) * N + n;
+      if (sl[y.o_pres + o] == 1.0f) {
+        const int id = (int)sl[y.o_id + o];
+        if (id > last && id < loc) loc = id;
+      }
+    }
+    if (loc != NONE) atomicMin(&s_best, loc);
+    __syncthreads();
+    const int best = s_best;
+    __syncthreads();
+    if (best == NONE) break;
+    if (count < M && tid == 0) s_ids[count] = best;
+    ++count;
+    last = best;
+  }
+  __syncthreads();
+  const int nm = count < M ? count : M;
+  if (a.track_id != nullptr)
+    for (int m = tid; m < M; m += 256) a.track_id[(size_t)r * M + m] = m < nm ? s_ids[m] : -1;
+  if (tid == 0 && a.n_tracks != nullptr) a.n_tracks[r] = count;
+  if (a.track_present == nullptr && a.track_where == nullptr) return;
+  const int FM = a.lag * T * M;
+  for (int e = tid; e < FM; e += 256) {
+    const int f = e / M, m = e % M, i = f / T, t = f % T;
+    float pr = 0.0f, wh[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    const int ar = anc[(size_t)i * R + r];
+    if (m < nm && ar >= 0) {
+      const float* sl = reinterpret_cast<const float*>(sq_hist_slot(a.ring, y, pos, a.lag - 1 - i));
+      const size_t o = ((size_t)t * R + ar) * N;
+      for (int n = 0; n < N; ++n)
+        if (sl[y.o_pres + o + n] == 1.0f && (int)sl[y.o_id + o + n] == s_ids[m]) {
+          pr = 1.0f;
+          for (int q = 0; q < 4; ++q) wh[q] = sl[y.o_where + (o + n) * 4 + q];
+          break;
+        }
+    }
+    const size_t oo = ((size_t)f * R + r) * M + m;
+    if (a.track_present != nullptr) a.track_present[oo] = pr;
+    if (a.track_where != nullptr)
+      for (int q = 0; q < 4; ++q) a.track_where[oo * 4 + q] = wh[q];
+  }
+}
+int sq_launch_history_trace(const HistTraceArgs& a, hipStream_t s) {
+  const HistLayout& y = a.lay;
+  SQ_LAUNCH(k_history_walk, dim3(y.R / y.K), dim3(256), 0, s, a);
+  if (a.where || a.presence || a.obj_id || a.what || a.log_w || a.valid || a.frame_index)
+    SQ_LAUNCH(k_history_gather, dim3(y.R * a.lag), dim3(256), 0, s, a);
+  if (a.track_id || a.n_tracks || a.track_present || a.track_where) SQ_LAUNCH(k_track_table, dim3(y.R), dim3(256), 0, s, a);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Spatial-transformer crop (reference: sqair/modules.py:170-227; Sonnet AffineGridWarper +
 // tf.contrib.resampler).  One workgroup per sequence b stages the frame in LDS
 // once and cuts the glimpses of all K particles of that sequence from it.  The `where` sample of

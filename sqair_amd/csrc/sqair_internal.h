@@ -85,6 +85,12 @@ struct SqairHandle {
   // SMC resampling of the carried state (sqair_set_smc): one k_smc_resample launch after the state export
   bool smc_on = false;
   SqairSmc smc = {};                 // (smc.src_rows == state_src and its B == state_B while smc_on)
+  // track history (sqair_set_history): one k_history_push launch after the state export, before the resampler
+  bool hist_on = false;
+  void* hist_ring = nullptr;
+  int64_t hist_bytes = 0;
+  int hist_L = 0, hist_T = 0;        // hist_T: frames per pass of the ring's slots, 0 until the first pass pushes
+  uint32_t hist_fields = 0;
   // generic capture slots (sqair_capture_begin / _end / _launch): any sequence of C-ABI calls as one HIP graph
   hipGraph_t cap_graph[4] = {nullptr, nullptr, nullptr, nullptr};
   hipGraphExec_t cap_exec[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -226,12 +232,17 @@ struct SqStateRes {
   const void* in; void* out; const int32_t* src;
   bool fresh;
   bool smc_on; SqairSmc smc;
+  bool hist_on = false;   // (the handle's inference passes only: a carried training call never pushes)
 };
 SQ_LOCAL SqStateRes sq_handle_state(const SqairHandle* h);
 SQ_LOCAL SqStateRes sq_carry_state(const SqairCarry* c);
 SQ_LOCAL int sq_smc_refusal(SqairHandle* h, const SqairOutputs* outp);   // -1 + error text: a pass with SMC on that does not bind the log weights
 SQ_LOCAL StateArgs sq_state_args(const SqairHandle* h, const SqStateRes& st, int R, float* rec, float* temporal, float* prior, float* last_id,
                                  int* t_row, float* fresh, int t0);
+// track history: -1 + error text for a pass with history on that the ring rules out (host only; fixes the ring's T on the first
+// pass); the push's arguments for a pass of T frames
+SQ_LOCAL int sq_history_refusal(SqairHandle* h, int T, int B, const SqairOutputs* outp);
+SQ_LOCAL HistPushArgs sq_history_push_args(const SqairHandle* h, const SqStateRes& st, const SqairOutputs& out, const int* t_row, int T, int B);
 SQ_LOCAL SmcArgs sq_smc_args(const SqairSmc& m, const float* lw, const int32_t* t_row, int T, int B, int K);
 // section A of a frame of the pass, and a frame of the forecast: the propagation-prior cell and its statistics (sqair_api.hip)
 SQ_LOCAL int sq_prior_step(SqairHandle* h, const float* packed, hipStream_t s, int M, const float* rec_prev, const float* prior_prev,

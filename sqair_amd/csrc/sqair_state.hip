@@ -1,5 +1,5 @@
 // libsqair_hip.so -- the carried model state on the native side of the C ABI (include/sqair_hip.h): the state blob and its
-// registration on a handle (sqair_set_state / sqair_set_smc), the refusals of the passes and carried training calls a state rules
+// registration on a handle (sqair_set_state / sqair_set_smc / sqair_set_history), the refusals of the passes and carried training calls a state rules
 // out, the settings one pass resolves them to (SqStateRes: the handle's, or a SqairCarry's), and the forecast that rolls the prior
 // forward from a state (sqair_forecast).  Host code only; the pass that imports / exports / resamples the state is
 // sq_forward_impl (sqair_api.hip), the kernels live in sqair_glue.hip.
@@ -15,6 +15,9 @@ int64_t sq_state_row_floats(const SqairHandle* h) {
   const int64_t snh = c.time_cell == CELL_LSTM ? 2 * nh : nh, psnh = c.prior_cell == CELL_LSTM ? 2 * nh : nh;
   return (N * (rec::W + snh + psnh) + 2 + 3) / 4 * 4;
 }
+static void sq_history_off(SqairHandle* h) {
+  h->hist_on = false; h->hist_ring = nullptr; h->hist_bytes = 0; h->hist_L = 0; h->hist_T = 0; h->hist_fields = 0;
+}
 extern "C" int64_t sqair_state_bytes(const SqairHandle* h, int B) {
   if (!h || B < 1) return -1;
   return (int64_t)B * h->cfg.k_particles * sq_state_row_floats(h) * 4;
@@ -24,6 +27,7 @@ extern "C" int sqair_set_state(SqairHandle* h, const void* state_in, void* state
   if (!state_in && !state_out && !src_rows) {
     h->state_on = false; h->state_in = nullptr; h->state_out = nullptr; h->state_src = nullptr; h->state_B = 0;
     h->smc_on = false; h->smc = SqairSmc{};   // (SMC resamples the carried state: off with it)
+    sq_history_off(h);                        // (the history records the carried rows: off with it)
     return 0;
   }
   if (h->cfg.sample_from_prior) return sq_no(h, "sqair_set_state: not with sample_from_prior (generation decides per frame on the host)");
@@ -34,6 +38,7 @@ extern "C" int sqair_set_state(SqairHandle* h, const void* state_in, void* state
   if (h->smc_on && (!state_in || src_rows != h->state_src || B != h->state_B)) {   // (what SMC was registered against is gone)
     h->smc_on = false; h->smc = SqairSmc{};
   }
+  if (h->hist_on && B != h->state_B) sq_history_off(h);   // (the ring was sized for the other B)
   h->state_on = true; h->state_in = state_in; h->state_out = state_out; h->state_src = src_rows; h->state_B = B;
   return 0;
 }
@@ -126,7 +131,7 @@ int sq_state_refusal(SqairHandle* h, bool train, int B, int t_offset) {
 }
 
 SqStateRes sq_handle_state(const SqairHandle* h) {
-  return SqStateRes{h->state_on, h->state_in, h->state_out, h->state_src, false, h->smc_on, h->smc};
+  return SqStateRes{h->state_on, h->state_in, h->state_out, h->state_src, false, h->smc_on, h->smc, h->state_on && h->hist_on};
 }
 SqStateRes sq_carry_state(const SqairCarry* c) {
   return SqStateRes{true, c->state_in, c->state_out, c->src_rows, true, c->smc != nullptr, c->smc ? *c->smc : SqairSmc{}};
@@ -144,6 +149,111 @@ StateArgs sq_state_args(const SqairHandle* h, const SqStateRes& st, int R, float
   a.R = R; a.n_rec = d.N * rec::W; a.n_tmp = d.N * d.snh; a.n_pri = d.N * d.psnh; a.row_words = (int)sq_state_row_floats(h);
   a.t0 = t0;
   return a;
+}
+
+// ------------------------------------------------------------------------------------------------
+// track history (include/sqair_hip.h: sqair_set_history / sqair_history_trace): the ring's layout, registration and refusals, the
+// argument blocks of k_history_push (launched by sq_forward_impl) and of the trace kernels
+// ------------------------------------------------------------------------------------------------
+static HistLayout sq_hist_layout(const SqairHandle* h, int L, int T, int B, uint32_t fields) {
+  const SqairConfig& c = h->cfg;
+  HistLayout y; memset(&y, 0, sizeof(y));
+  y.L = L; y.T = T; y.K = c.k_particles; y.R = B * c.k_particles; y.N = c.n_steps_per_image; y.nw = c.n_what; y.fields = fields;
+  const long long R = y.R, TRN = (long long)T * R * y.N;
+  y.o_where = 2 * R;   // (parent at 0, t0 at R)
+  y.o_pres = y.o_where + TRN * 4;
+  y.o_id = y.o_pres + TRN;
+  y.o_what = y.o_id + TRN;
+  y.o_lw = y.o_what + ((fields & SQAIR_HIST_WHAT) ? TRN * y.nw : 0);
+  y.slot_words = align64(y.o_lw + ((fields & SQAIR_HIST_LOG_W) ? (long long)T * R : 0));
+  y.scratch = SQ_HIST_HDR;
+  y.slots = align64(y.scratch + (long long)L * R);
+  y.total = y.slots + (long long)L * y.slot_words;
+  return y;
+}
+static bool sq_hist_fields_ok(uint32_t fields) {
+  return (fields & SQAIR_HIST_MANDATORY) == SQAIR_HIST_MANDATORY && (fields & ~SQAIR_HIST_ALL) == 0;
+}
+extern "C" int64_t sqair_history_bytes(const SqairHandle* h, int L, int T, int B, uint32_t fields) {
+  if (!h || L < 1 || T < 1 || B < 1 || !sq_hist_fields_ok(fields) || (int64_t)B * h->cfg.k_particles > INT32_MAX) return -1;
+  return sq_hist_layout(h, L, T, B, fields).total * 4;
+}
+extern "C" int sqair_set_history(SqairHandle* h, void* ring, int64_t ring_bytes, int L, uint32_t fields) {
+  if (!h) return -1;
+  if (!ring) {
+    sq_history_off(h);
+    return 0;
+  }
+  if (!h->state_on) return sq_no(h, "sqair_set_history: needs a carried state (sqair_set_state): the history records the rows it carries");
+  if (L < 1) return sq_no(h, "sqair_set_history: L must be >= 1");
+  if (!sq_hist_fields_ok(fields))
+    return sq_no(h, "sqair_set_history: fields must hold where, presence and obj_id (SQAIR_HIST_MANDATORY) and no bit outside SQAIR_HIST_ALL");
+  const int64_t need = sqair_history_bytes(h, L, 1, h->state_B, fields);
+  if (ring_bytes < need)
+    return sq_no(h, "sqair_set_history: ring_bytes " + std::to_string(ring_bytes) + " < sqair_history_bytes(h, " + std::to_string(L) +
+                    ", 1, " + std::to_string(h->state_B) + ", fields) = " + std::to_string(need));
+  h->hist_on = true; h->hist_ring = ring; h->hist_bytes = ring_bytes; h->hist_L = L; h->hist_T = 0; h->hist_fields = fields;
+  return 0;
+}
+// the refusal of a pass with history on (host only: before any HIP call).  The first pass fixes the T the ring's slots are laid
+// out for.
+int sq_history_refusal(SqairHandle* h, int T, int B, const SqairOutputs* outp) {
+  if (!h->state_on || !h->hist_on) return 0;
+  if (T < 1 || B != h->state_B) return 0;   // (the pass's own checks refuse these)
+  if (h->hist_T != 0 && T != h->hist_T)
+    return sq_no(h, "history (sqair_set_history): this ring's slots hold passes of T = " + std::to_string(h->hist_T) + " frames, a pass of T = " +
+                    std::to_string(T) + " cannot be pushed into it");
+  const int64_t need = sqair_history_bytes(h, h->hist_L, T, B, h->hist_fields);
+  if (h->hist_bytes < need)
+    return sq_no(h, "history (sqair_set_history): ring_bytes " + std::to_string(h->hist_bytes) + " < sqair_history_bytes(h, " +
+                    std::to_string(h->hist_L) + ", " + std::to_string(T) + ", " + std::to_string(B) + ", fields) = " + std::to_string(need));
+  const uint32_t f = h->hist_fields;
+  if (!outp || !outp->where || !outp->presence || !outp->obj_id || ((f & SQAIR_HIST_WHAT) && !outp->what) ||
+      ((f & SQAIR_HIST_LOG_W) && !outp->log_weights_per_timestep))
+    return sq_no(h, "history (sqair_set_history) records the pass's outputs: a pass with history on must bind where, presence, obj_id and "
+                    "the optional fields it was set with (what, log_weights_per_timestep)");
+  h->hist_T = T;
+  return 0;
+}
+HistPushArgs sq_history_push_args(const SqairHandle* h, const SqStateRes& st, const SqairOutputs& out, const int* t_row, int T, int B) {
+  HistPushArgs a; memset(&a, 0, sizeof(a));
+  a.ring = (unsigned*)h->hist_ring;
+  a.lay = sq_hist_layout(h, h->hist_L, T, B, h->hist_fields);
+  a.where = out.where; a.presence = out.presence; a.obj_id = out.obj_id; a.what = out.what; a.lw = out.log_weights_per_timestep;
+  a.src = st.src; a.have_in = st.in != nullptr; a.t_row = t_row;
+  return a;
+}
+extern "C" int sqair_history_trace(SqairHandle* h, void* ring, const int32_t* src_next, int lag, const SqairTraceOutputs* outp,
+                                   void* stream) {
+  if (!h) return -1;
+  if (!h->state_on || !h->hist_on) return sq_no(h, "sqair_history_trace: no history set (sqair_set_history)");
+  if (!ring || ring != h->hist_ring) return sq_no(h, "sqair_history_trace: ring must be the ring given to sqair_set_history");
+  if (lag < 1 || lag > h->hist_L)
+    return sq_no(h, "sqair_history_trace: lag = " + std::to_string(lag) + " must lie in [1, L = " + std::to_string(h->hist_L) + "]");
+  if (!outp) return sq_no(h, "sqair_history_trace: out must not be NULL");
+  const SqairTraceOutputs& o = *outp;
+  if (o.T < 1) return sq_no(h, "sqair_history_trace: out->T (frames per pass) must be >= 1");
+  if (h->hist_T != 0 && o.T != h->hist_T)
+    return sq_no(h, "sqair_history_trace: out->T = " + std::to_string(o.T) + " but the passes pushed have T = " + std::to_string(h->hist_T));
+  if (h->hist_bytes < sqair_history_bytes(h, h->hist_L, o.T, h->state_B, h->hist_fields))
+    return sq_no(h, "sqair_history_trace: the ring is too small for passes of out->T = " + std::to_string(o.T) + " frames");
+  if ((o.what && !(h->hist_fields & SQAIR_HIST_WHAT)) || (o.log_w && !(h->hist_fields & SQAIR_HIST_LOG_W)))
+    return sq_no(h, "sqair_history_trace: what / log_w asked of a ring that was set without the field");
+  const bool table = o.track_id || o.n_tracks || o.track_present || o.track_where;
+  if (table && (o.max_tracks < 1 || o.max_tracks > SQ_HIST_MAX_TRACKS))
+    return sq_no(h, "sqair_history_trace: max_tracks must lie in [1, " + std::to_string(SQ_HIST_MAX_TRACKS) + "] for the track table");
+  HistTraceArgs a; memset(&a, 0, sizeof(a));
+  a.ring = (unsigned*)ring;
+  a.lay = sq_hist_layout(h, h->hist_L, o.T, h->state_B, h->hist_fields);
+  if ((int64_t)a.lay.R * lag > INT32_MAX || (int64_t)lag * o.T * a.lay.N * (table ? o.max_tracks : 1) > INT32_MAX)
+    return sq_no(h, "sqair_history_trace: lag * rows (or lag * T * N * max_tracks) beyond 2^31");
+  a.src_next = src_next; a.lag = lag; a.M = table ? o.max_tracks : 1;
+  a.where = o.where; a.presence = o.presence; a.obj_id = o.obj_id; a.what = o.what; a.log_w = o.log_w;
+  a.valid = o.valid; a.frame_index = o.frame_index; a.ancestor_row = o.ancestor_row; a.unique_ancestors = o.unique_ancestors;
+  a.track_id = o.track_id; a.n_tracks = o.n_tracks; a.track_present = o.track_present; a.track_where = o.track_where;
+  sq_launch_history_trace(a, (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -27,6 +27,12 @@ discovery empty, and renders every frame.  Per particle it returns the sampled o
 predictive mean canvas and expected object count under the particles' weights.  It writes nothing the steps read: forecasting
 between steps leaves every step's results unchanged.
 
+With ``history=L`` the last L steps are kept in a ring on the device, written by one more kernel of the pass (include/sqair_hip.h:
+sqair_set_history), and ``tracks(lag)`` traces them on the device into trajectories (sqair_history_trace): as soon as a lane
+resamples, row r of this step no longer continues row r of the last one, so the track of an object is the path through the source
+maps -- the surviving particles' trajectories, the fixed-lag smoothing distribution of the filter -- and, because compaction moves
+objects between slots, a table keyed by object id.  No per-step copy to the host, no host-side genealogy.
+
 The stream takes over its core's handle: while it is open, every inference pass of that handle carries the state.  ``close()``
 hands the handle back.
 
@@ -52,7 +58,7 @@ FORECAST_NOISE_TAG = 1 << 63
 
 class SqairStream(object):
     def __init__(self, core, B, frames_per_step=1, outputs=DEFAULT_OUTPUTS, use_graph=True, seed=0, resample=None, ess_frac=0.5,
-                 state=None):
+                 state=None, history=None, history_fields=tuple(_capi.HISTORY_FIELDS)):
         if core.cfg.sample_from_prior:
             raise ValueError("SqairStream: generation modes (sample_from_prior) do not carry a state across calls")
         if resample not in (None, "systematic"):
@@ -71,6 +77,8 @@ class SqairStream(object):
         outputs = tuple(outputs)
         if "log_weights_per_timestep" not in outputs:   # (the running log-weight sums)
             outputs = outputs + ("log_weights_per_timestep",)
+        if history is not None:   # (checked before the handle is touched; the ring records these outputs of the pass)
+            outputs = outputs + tuple(f for f in CarriedState.check_history(history, history_fields, "SqairStream") if f not in outputs)
         self.outputs = outputs
         self.use_graph = bool(use_graph)
         self.seed = int(seed)
@@ -81,6 +89,7 @@ class SqairStream(object):
         if state is not None:   # hand-over: the first step continues every row of the given blob
             cs.adopt(state)
         self._graph = False
+        self._tr = {}               # tracks() buffers of the LAST (lag, start, max_tracks, table) only
         self._fc = {}               # forecast buffers of the LAST (F, outputs, summaries) only: workspace, noise, map, weights, outputs
         self._smc_uniforms = None   # registered with the caller's uniforms (True) or Philox (False)
         core.stream.synchronize()
@@ -88,12 +97,16 @@ class SqairStream(object):
                                             cs.state.numel() * 4, self.B), "sqair_set_state")
         if self.smc:
             self._set_smc(False)
+        if history is not None:
+            ring, nb, bits = cs.set_history(history, history_fields, self.T)
+            torch.cuda.current_stream(core.device).synchronize()   # (the ring's zeros are in place before a pass pushes into it)
+            core.check(core.lib.sqair_set_history(core.handle, ring.data_ptr(), nb, cs.history, bits), "sqair_set_history")
         core._graph_ready = False   # (the handle's graph is now this stream's)
 
-    # the carried state's, read-only (the last three: what the tests and tools look at)
-    state, log_weight_sum, log_z, log_evidence, ess, u, resampled, _src, _armed, _src_is_identity = (
+    # the carried state's, read-only (_src, _armed, _src_is_identity: what the tests and tools look at)
+    state, log_weight_sum, log_z, log_evidence, ess, u, resampled, _src, _armed, _src_is_identity, history, history_fields = (
         carried(n) for n in ("state", "log_weight_sum", "log_z", "log_evidence", "ess", "u", "resampled", "_src", "_armed",
-                             "_src_is_identity"))
+                             "_src_is_identity", "history", "history_fields"))
 
     def _set_smc(self, uniforms):
         """Registers the SMC buffers (sqair_set_smc), the lane uniforms read from ``_uniforms`` or drawn by Philox.  The pointers
@@ -192,15 +205,7 @@ class SqairStream(object):
                     core.check(lib.sqair_fill_noise(core.handle, fc["noise"].data_ptr(), F, self.B, self.B, 0,
                                                     (self.seed if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF,
                                                     FORECAST_NOISE_TAG | self.frame, core._stream()), "sqair_fill_noise")
-                if self.smc:   # (the resampler's map and weights are already indexed by next-step rows)
-                    src, lw = cs._src, cs.log_weight_sum
-                else:          # the pending host-side map, uploaded into the forecast's own buffer; the weights follow it
-                    m = cs.pending()
-                    src = fc["src"]
-                    src.copy_(torch.as_tensor(m.astype(np.int32)), non_blocking=True)
-                    keep = src >= 0
-                    lw = fc["log_w"]
-                    lw.copy_(torch.where(keep, cs.log_weight_sum[src.long().clamp_min(0)], torch.zeros_like(lw)))
+                src, lw = cs.next_rows(fc["src"], fc["log_w"])   # (the map and the weights of the rows the next step starts from)
                 out = fc["out"]
                 c_out = _capi.SqairForecastOutputs(**{n: t.data_ptr() for n, t in out.items()})
                 if summaries:
@@ -230,10 +235,77 @@ class SqairStream(object):
         return dict(ws=z(nb // 4), noise=z((F, R, 2, N, core.nzw)), src=z(R, torch.int32), log_w=z(R),
                     out={n: z(shapes[n]) for n in outputs})
 
+    # ---- track history ----------------------------------------------------------------------------------------------------
+    def tracks(self, lag=None, start="next", max_tracks=None, table=True):
+        """Traces every particle row's ancestral path back over the last ``lag`` steps (default: all ``history`` kept) on the
+        device: frames oldest -> newest, F = lag * frames_per_step.  ``start="next"``: from the rows the next ``step()`` would
+        start from (the pending source map; with SMC the map the resampler wrote: the equally weighted surviving set), as
+        ``forecast`` does; ``"last"``: from the rows of the last step's outputs.  Returns ``where`` [F, B*K, N, 4], ``presence``,
+        ``obj_id`` [F, B*K, N], with the fields kept ``what`` [F, B*K, N, n_what] and ``log_w`` [F, B*K] -- the values stored at the
+        ancestor's row, zero where the path has ended (a fresh row, a -1 start, a step not kept any more) --, ``valid`` and
+        ``frame_index`` [F, B*K] (the row's frame counter, -1 where invalid), ``ancestor_row`` [lag, B*K] and ``unique_ancestors``
+        [lag, B]: the distinct ancestors among a lane's K paths (how far back more than one hypothesis survives).  With ``table``
+        the tracks by object id: ``track_id`` [B*K, M] (ascending, -1 padded; M = ``max_tracks``, default 2 N), ``n_tracks`` [B*K]
+        (the true count; above M: truncated), ``track_present`` [F, B*K, M], ``track_where`` [F, B*K, M, 4].  With
+        ``start="next"`` also the particles' ``weights`` [B, K] (as ``forecast`` forms them) and ``best_row`` [B], the first row of
+        maximal weight per lane.  Copies, valid on the current stream; nothing the steps read is written.  One set of buffers is
+        kept, for the last (lag, start, max_tracks, table) asked for."""
+        core, cs = self.core, self.carried
+        if cs.ring is None:
+            raise ValueError("SqairStream.tracks: the stream keeps no history (SqairStream(..., history=L))")
+        lag = cs.history if lag is None else lag
+        if isinstance(lag, bool) or not isinstance(lag, (int, np.integer)) or not 1 <= lag <= cs.history:
+            raise ValueError("SqairStream.tracks: lag must be an integer in [1, history = {}]".format(cs.history))
+        if start not in ("next", "last"):
+            raise ValueError("SqairStream.tracks: start must be 'next' or 'last'")
+        M = 2 * core.N if max_tracks is None else max_tracks
+        if table and (isinstance(M, bool) or not isinstance(M, (int, np.integer)) or not 1 <= M <= 1024):
+            raise ValueError("SqairStream.tracks: max_tracks must be an integer in [1, 1024]")
+        lag, M = int(lag), int(M)
+        key = (lag, start, M if table else None, bool(table))
+        with torch.cuda.device(core.device):
+            core._join_in()
+            with core.on_stream():
+                tr = self._tr.get(key)
+                if tr is None:
+                    self._tr.clear()
+                    tr = self._tr[key] = self._track_buffers(lag, M, table)
+                src = None
+                if start == "next":
+                    src, lw = cs.next_rows(tr["src"], tr["log_w"])
+                c_out = _capi.SqairTraceOutputs(T=self.T, max_tracks=M, **{n: t.data_ptr() for n, t in tr["out"].items()})
+                core.check(core.lib.sqair_history_trace(core.handle, cs.ring.data_ptr(), None if src is None else src.data_ptr(),
+                                                        lag, C.byref(c_out), core._stream()), "sqair_history_trace")
+                res = {k: v.clone() for k, v in tr["out"].items()}
+                if start == "next":
+                    w = res["weights"] = torch.softmax(lw.reshape(self.B, self.K), -1)
+                    k = torch.arange(self.K, device=core.device)
+                    first = torch.where(w == w.max(-1, keepdim=True).values, k, self.K).min(-1).values % self.K
+                    res["best_row"] = (first + torch.arange(self.B, device=core.device) * self.K).to(torch.int32)
+            core._join_out()
+        return res
+
+    def _track_buffers(self, lag, M, table):
+        core = self.core
+        R, N, B, F = self.R, core.N, self.B, lag * self.T
+        i32 = torch.int32
+        shapes = dict(where=((F, R, N, 4), None), presence=((F, R, N), None), obj_id=((F, R, N), None), valid=((F, R), i32),
+                      frame_index=((F, R), i32), ancestor_row=((lag, R), i32), unique_ancestors=((lag, B), i32))
+        if "what" in self.history_fields:
+            shapes["what"] = ((F, R, N, core.nw), None)
+        if "log_weights_per_timestep" in self.history_fields:
+            shapes["log_w"] = ((F, R), None)
+        if table:
+            shapes.update(track_id=((R, M), i32), n_tracks=((R,), i32), track_present=((F, R, M), None),
+                          track_where=((F, R, M, 4), None))
+        z = lambda shp, dt=None: torch.zeros(shp, dtype=dt or torch.float32, device=core.device)
+        return dict(src=z(R, i32), log_w=z(R), out={n: z(*sd) for n, sd in shapes.items()})
+
     def close(self):
-        """Switches the carried state off on the core's handle (its passes start from the initial state again)."""
+        """Switches the history and the carried state off on the core's handle (its passes start from the initial state again)."""
         core = self.core
         if core.handle:
             core.stream.synchronize()
+            core.check(core.lib.sqair_set_history(core.handle, None, 0, 0, 0), "sqair_set_history")
             core.check(core.lib.sqair_set_state(core.handle, None, None, None, 0, 0), "sqair_set_state")
             core._graph_ready = False

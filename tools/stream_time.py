@@ -11,6 +11,13 @@ With --smc: the same step with in-graph SMC resampling (SqairStream(resample="sy
 at ess_frac 0.5 and 1.0 next to SMC off, at cfg-2's batch and for one camera with K = 5 particles:
 
     python tools/stream_time.py --smc [--out profiles/stream_time_smc.json]
+
+With --history: the price of the track history (SqairStream(history=64), include/sqair_hip.h: sqair_set_history).  Four streams at
+cfg-2's batch in ONE process -- plain, SMC, history, SMC + history --, timed in alternating blocks so that all four see the same
+machine, the same minutes.  The yardstick is the same run's SMC on - SMC off difference: the measured price of one dependent graph
+node; the push is one node too.  Also the time of tracks() at lag 10 and lag 64, and the ring's bytes:
+
+    python tools/stream_time.py --history [--out profiles/stream_history_time.json]
 """
 import argparse
 import json
@@ -67,16 +74,91 @@ def time_stream(B, K, N, steps, warmup, hw=(50, 50), resample=None, ess_frac=0.5
                 ms_per_frame_p90=float(np.percentile(ms, 90)), ms_per_frame_back_to_back=float(a.elapsed_time(b) / steps))
 
 
+def time_history(B, K, N, steps, warmup, L=64, rounds=10, hw=(50, 50)):
+    F = make_flags(k_particles=K, n_steps_per_image=N)
+    obs = torch.as_tensor(to_float(make_sequences(B, T=50, canvas=hw, seed=7)["imgs"])).cuda()
+    P = {k: np.asarray(v, dtype=np.float32) for k, v in
+         init_params(F, hw, seed=0, mean_img=obs.mean((0, 1)).cpu().numpy(), jitter=0.02).items()}
+    smc = dict(resample="systematic", ess_frac=0.5)
+    legs = dict(plain={}, smc=smc, history=dict(history=L), smc_history=dict(history=L, **smc))
+    streams = {}
+    for name, kw in legs.items():
+        core = SqairCore(F, hw)
+        core.set_params(P)
+        streams[name] = SqairStream(core, B, frames_per_step=1, use_graph=True, **kw)
+    block = max(steps // rounds, 1)
+    lat = {n: [] for n in legs}   # ms of one step, the host waiting for each (latency)
+    b2b = {n: [] for n in legs}   # ms per step of a block issued without waiting (throughput)
+    t = 0
+    for rnd in range(-1, rounds):  # (round -1: the warm-up, every stream captures its graph)
+        for name, st in streams.items():
+            core = st.core
+            with core.on_stream():
+                n = warmup if rnd < 0 else block
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+                for i in range(n):
+                    ev[i][0].record()
+                    st.step(obs[(t + i) % 50:(t + i) % 50 + 1])
+                    ev[i][1].record()
+                    core.stream.synchronize()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for i in range(n):
+                    st.step(obs[(t + i) % 50:(t + i) % 50 + 1])
+                b.record()
+                torch.cuda.synchronize()
+            if rnd >= 0:
+                lat[name] += [x.elapsed_time(y) for x, y in ev]
+                b2b[name].append(a.elapsed_time(b) / n)
+        t += block
+    med = {n: float(np.median(lat[n])) for n in legs}
+    thr = {n: float(np.median(b2b[n])) for n in legs}
+    res = dict(B=B, K=K, N=N, hw=list(hw), L=L, steps=block * rounds, rounds=rounds, warmup=warmup,
+               graph_nodes={n: st.core.graph_nodes() for n, st in streams.items()},
+               ring_bytes=int(streams["history"].carried.ring.numel() * 4), history_fields=list(streams["history"].history_fields),
+               ms_per_frame_median=med, ms_per_frame_p10={n: float(np.percentile(lat[n], 10)) for n in legs},
+               ms_per_frame_p90={n: float(np.percentile(lat[n], 90)) for n in legs}, ms_per_frame_back_to_back=thr)
+    for key, v in (("latency", med), ("back_to_back", thr)):
+        one_node = v["smc"] - v["plain"]            # the yardstick: one dependent node (the resampler) on this machine, this run
+        push = [v["history"] - v["plain"], v["smc_history"] - v["smc"]]
+        res["us_" + key] = dict(smc_node=1e3 * one_node, history_node_on_plain=1e3 * push[0], history_node_on_smc=1e3 * push[1],
+                                history_over_smc_node=[p / one_node if one_node > 0 else None for p in push])
+    # tracks(): the trace + the track table + the output copies, the ring full (warm-up + steps > L)
+    st = streams["smc_history"]
+    res["tracks_ms"] = {}
+    for lag in (10, L):
+        for start in ("next", "last"):
+            with st.core.on_stream():
+                for _ in range(5):
+                    st.tracks(lag=lag, start=start)
+                torch.cuda.synchronize()
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(50)]
+                for x, y in ev:
+                    x.record()
+                    st.tracks(lag=lag, start=start)
+                    y.record()
+                    st.core.stream.synchronize()
+            ms = [x.elapsed_time(y) for x, y in ev]
+            res["tracks_ms"]["lag{}_{}".format(lag, start)] = dict(median=float(np.median(ms)), p10=float(np.percentile(ms, 10)),
+                                                                   p90=float(np.percentile(ms, 90)))
+    for st in streams.values():
+        st.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--out", default=None)
     ap.add_argument("--smc", action="store_true", help="SMC resampling off / ess_frac 0.5 / 1.0 (profiles/stream_time_smc.json)")
+    ap.add_argument("--history", action="store_true", help="plain / SMC / history / SMC + history, alternating (profiles/stream_history_time.json)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     ov, _, _, _ = config_inputs(2)
-    if args.smc:
+    if args.history:
+        shapes = [dict(name="cfg2_batch_history", **time_history(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
+    elif args.smc:
         shapes = []
         for name, B, K in (("cfg2_batch", 32, ov["k_particles"]), ("one_camera_k5", 1, 5)):
             for resample, frac in ((None, 0.5), ("systematic", 0.5), ("systematic", 1.0)):
