@@ -395,6 +395,29 @@ int sqair_lstm_test(SqairHandle* h, const float* x, const float* hstate, const f
 /* adjoint of the element-wise cell: gate pre-activations [M, 4 nh], c_prev, d h', d c' -> d gates, d c_prev */
 int sqair_lstm_cell_bwd_test(SqairHandle* h, const float* gates, const float* c_prev, const float* d_h, const float* d_c,
                              float* d_gates, float* d_cprev, int M, void* stream);
+/* Slot compaction of ONE frame on raw device buffers (test helpers; reference: _choose_latents sqair/sqair_modules.py:514-582,
+ * compute_object_ids / select_present sqair/index.py:132-221) and its adjoint: the launches of the frame loop and of the backward
+ * sweep with the handle's dimensions, R = B * k_particles rows, then a stream synchronise.
+ * sqair_compact_test_layout: fills out[0:n] with the widths and columns of THIS build's buffers (the product and the wide library
+ * lay the slot record out differently) and returns the number of entries it knows (20):
+ *   0 record width W | 1 PRES | 2 ID | 3 WHERE | 4 WHAT | 5 LOGIT | 6 WHERE_LOC | 7 WHERE_SCALE | 8 WHAT_LOC | 9 WHAT_SCALE | 10 PROB |
+ *   11 temporal state width | 12 prior state width | 13 floats of `flat` | 14, 15 offsets of seq.temporal_init / seq.prior_init
+ *   in `flat` | 16 slots the build takes | 17 N | 18 n_what | 19 1 if the handle's dimensions have a specialised instantiation.
+ *   Widths are the kernels' own (n_hidden rounded up to 128 / 256 / 512; an LSTM state is [hidden | cell]); `flat` is the
+ *   parameter buffer in the kernels' own layout (sqair_debug_padded_count floats).
+ * sqair_compact_test: rec_p / rec_d / rec_prev [R][N][W], temporal_p [R][N][11], prior_p [R][N][12], last_id_prev [R] -> rec_next,
+ *   temporal_next, prior_next, last_id_next, src_out [R][N] (source slot 0..2N-1 of every merged slot) and whichever of the ten
+ *   per-slot outputs and num_steps_per_sample `out` names, at frame index t of tensors shaped [T][R][N][..].  Honours the
+ *   "specialised" option.
+ * sqair_compact_bwd_test: src [R][N] as the forward wrote it (refused, -1, unless every row names N distinct slots of [0, 2N));
+ *   d_rec_p / d_rec_d are accumulated into, d_temporal_p / d_prior_p [R][N][..] and d_new_temporal / d_new_prior [R][..] written. */
+int sqair_compact_test_layout(const SqairHandle* h, int32_t* out, int n);
+int sqair_compact_test(SqairHandle* h, const float* rec_p, const float* rec_d, const float* rec_prev, const float* temporal_p,
+                       const float* prior_p, const float* last_id_prev, const float* flat, float* rec_next, float* temporal_next,
+                       float* prior_next, float* last_id_next, int32_t* src_out, const SqairOutputs* out, int t, int B, void* stream);
+int sqair_compact_bwd_test(SqairHandle* h, const int32_t* src, const float* d_rec_next, const float* d_temporal_next,
+                           const float* d_prior_next, float* d_rec_p, float* d_rec_d, float* d_temporal_p, float* d_prior_p,
+                           float* d_new_temporal, float* d_new_prior, int B, void* stream);
 
 /* ---- adjoint (backward) building blocks of the training step (sqair_st_crop_bwd,
  * sqair_st_insert_ll_bwd, ...; the reference gets them from TF autodiff, sqair/model.py:160) ---------- */

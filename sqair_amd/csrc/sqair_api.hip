@@ -2044,6 +2044,38 @@ extern "C" int sqair_lstm_cell_bwd_test(SqairHandle* h, const float* gates, cons
   return 0;
 }
 
+// Slot compaction on raw device buffers (unit-test entry; its adjoint: sqair_compact_bwd_test in sqair_train.hip): the launch of the
+// frame loop with the handle's Dims, one frame.  The layout query tells a caller the widths and columns of THIS build's buffers, so that a
+// test hard-codes neither the product nor the wide record.
+extern "C" int sqair_compact_test_layout(const SqairHandle* h, int32_t* out, int n) {
+  if (!h || !out || n < 0) return -1;
+  const Dims d = make_dims(h->cfg, 1);
+  const int32_t v[20] = {rec::W, rec::PRES, rec::ID, rec::WHERE, rec::WHAT, rec::LOGIT, rec::WHERE_LOC, rec::WHERE_SCALE, rec::WHAT_LOC,
+                         rec::WHAT_SCALE, rec::PROB, d.snh, d.psnh, (int32_t)h->n_params, h->po.temporal_init, h->po.prior_init,
+                         SQ_MAXN, d.N, d.nw, sq_spec_ok(d) ? 1 : 0};
+  for (int i = 0; i < n && i < 20; ++i) out[i] = v[i];
+  return 20;
+}
+extern "C" int sqair_compact_test(SqairHandle* h, const float* rec_p, const float* rec_d, const float* rec_prev, const float* temporal_p,
+                                  const float* prior_p, const float* last_id_prev, const float* flat, float* rec_next,
+                                  float* temporal_next, float* prior_next, float* last_id_next, int32_t* src_out,
+                                  const SqairOutputs* out, int t, int B, void* stream) {
+  if (!h || !rec_p || !rec_d || !rec_prev || !temporal_p || !prior_p || !last_id_prev || !flat || !rec_next || !temporal_next ||
+      !prior_next || !last_id_next || !src_out || !out || t < 0 || B < 1) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  Dims d = make_dims(h->cfg, B);
+  d.spec = h->opt_specialised && sq_spec_ok(d) ? (h->opt_specialised_mask & SPEC_ALL) : 0;
+  CompactArgs ka; memset(&ka, 0, sizeof(ka));
+  ka.rec_p = rec_p; ka.rec_d = rec_d; ka.rec_prev = rec_prev; ka.temporal_p = temporal_p; ka.prior_p = prior_p;
+  ka.last_id_prev = last_id_prev; ka.last_id_next = last_id_next;
+  ka.rec_next = rec_next; ka.temporal_next = temporal_next; ka.prior_next = prior_next;
+  ka.flat = flat; ka.t = t; ka.out = *out; ka.src_out = src_out;
+  sq_launch_compact(ka, h->po, d, s);
+  SQ_CHECK_HIP(hipGetLastError());
+  SQ_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // host-only introspection of the packing plan (tests/test_pack_plan.py emulates the packed GEMMs on
 // the CPU from these tables to check the row / column maps without a GPU)

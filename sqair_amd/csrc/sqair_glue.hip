@@ -1650,6 +1650,13 @@ int sq_launch_compact(const CompactArgs& a, POff po, Dims d, hipStream_t s) {
 // glimpses sit in LDS, the canvas is built band by band over the slots' boxes (sqair_canvas.h), then
 // every thread finishes its pixels of the band: the canvas is written at most once, the frame read once.
 // ------------------------------------------------------------------------------------------------
+// One likelihood scale for every pixel: the pixels' common term -log sd - log sqrt(2 pi) is added ONCE, in double, to the fp32 sum
+// of -0.5 ((x - c) / sd)^2.  Added per pixel as an fp32 constant, its rounding error (up to half an ulp, the same for every pixel)
+// grew coherently with the pixel count: -6.9e-5 per frame at 32 x 40, -1.6e-4 at 50 x 50 on every particle row alike, which
+// log-mean-exp does not average away (tests/test_presence_paths.py: elbo_iwae 4.6 x as far from the fp64 oracle as the fp32 oracle).
+__device__ __forceinline__ float sq_add_ll_const(float sum, float sd, int n_pixels) {
+  return (float)((double)sum + (double)n_pixels * (-log((double)sd) - 0.91893853320467274178));
+}
 // LL = false (forecast, sq_launch_insert_canvas): canvas only -- no frame, no likelihood, no scalar outputs.
 template <int PF, int ROWS, bool LL = true>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_insert_loglik(const InsertArgs a, const Dims d, const int band_rows SQ_TLP) {
@@ -1674,7 +1681,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
   // a wavefront (64 consecutive pixels of a row) whose pixels are all outside every box skips the exponential -- most of a
   // 128 x 128 frame.  The value is the same sq_sigmoid(-10) either way.  (cfg-5: 111 -> 98 us.)
   const bool one_sd = a.std_fg == a.std_bg;
-  const float inv_sd = 1.0f / a.std_fg, lp0 = -logf(a.std_fg) - 0.91893853320467274178f;
+  const float inv_sd = 1.0f / a.std_fg;
   const float m_bg = sq_sigmoid(-10.0f);
   for (int yb0 = 0; yb0 < H; yb0 += band_rows) {
     const int yb1 = min(H, yb0 + band_rows) - 1, n = (yb1 - yb0 + 1) * W, pix0 = yb0 * W;
@@ -1697,7 +1704,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
         if constexpr (LL) {
           if (one_sd) {
             const float dd = (xv[q] - cv) * inv_sd;
-            ll += fmaf(-0.5f * dd, dd, lp0);
+            ll = fmaf(-0.5f * dd, dd, ll);   // (the pixels' common term -log sd - log sqrt(2 pi): once, below)
           } else {
             const float sd = m * a.std_fg + (1.0f - m) * a.std_bg;
             ll += sq_normal_lp(xv[q], cv, sd);
@@ -1713,7 +1720,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
   if ((tid & 63) == 0) red_s[tid >> 6] = ll;
   __syncthreads();
   if (tid == 0) {
-    const float dll = red_s[0] + red_s[1] + red_s[2] + red_s[3];
+    float dll = red_s[0] + red_s[1] + red_s[2] + red_s[3];
+    if (one_sd) dll = sq_add_ll_const(dll, a.std_fg, P);
     a.data_ll[frr] = dll;
     if (a.qz != nullptr) {
       const size_t tr = (size_t)a.t * d.R + frr;
@@ -1883,12 +1891,8 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(SQ_R
   }
   if constexpr (!LL) return;
   if (ONE_SD) {   // sum over pixels of -0.5 ((x - c) / sd)^2 - log sd - log sqrt(2 pi)
-    const float inv_sd = 1.0f / a.std_fg, lp0 = -logf(a.std_fg) - 0.91893853320467274178f;
-    const int nrows = (H - wave + WAVES - 1) / WAVES;
-    float cnt = 0.0f;
-#pragma unroll
-    for (int q = 0; q < CP; ++q) cnt += vw[q].x + vw[q].y;
-    ll = fmaf(-0.5f * inv_sd * inv_sd, ss.x + ss.y, lp0 * cnt * (float)nrows);
+    const float inv_sd = 1.0f / a.std_fg;
+    ll = -0.5f * inv_sd * inv_sd * (ss.x + ss.y);   // (the pixels' common term: once, by thread 0 below)
   }
   ll = sq_wave_sum(ll);
   if (lane == 0) red_s[wave] = ll;
@@ -1897,6 +1901,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(SQ_R
     float dll = red_s[0];
 #pragma unroll
     for (int w = 1; w < WAVES; ++w) dll += red_s[w];
+    if (ONE_SD) dll = sq_add_ll_const(dll, a.std_fg, P);
     a.data_ll[frr] = dll;
     if (a.qz != nullptr) {
       const size_t tr = (size_t)a.t * d.R + frr;

@@ -768,6 +768,36 @@ extern "C" int sqair_backward_carry(SqairHandle* h, const float* flat, const voi
 // sqair_elbo, sqair_backward = one training step up to the gradient all-reduce) and replays it as ONE hipGraphLaunch —
 // the step is ~3000 short dependent launches, so replay removes the host launch cost from the critical path.
 // ------------------------------------------------------------------------------------------------
+// the compaction adjoint on raw device buffers (unit-test entry; the forward: sqair_compact_test in sqair_api.hip)
+extern "C" int sqair_compact_bwd_test(SqairHandle* h, const int32_t* src, const float* d_rec_next, const float* d_temporal_next,
+                                      const float* d_prior_next, float* d_rec_p, float* d_rec_d, float* d_temporal_p, float* d_prior_p,
+                                      float* d_new_temporal, float* d_new_prior, int B, void* stream) {
+  if (!h || !src || !d_rec_next || !d_temporal_next || !d_prior_next || !d_rec_p || !d_rec_d || !d_temporal_p || !d_prior_p ||
+      !d_new_temporal || !d_new_prior || B < 1) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  const Dims d = make_dims(h->cfg, B);
+  // the kernel indexes LDS with `src`: refuse anything that is not N distinct slots of [0, 2N) per row (the forward's src_out is)
+  std::vector<int32_t> hs((size_t)d.R * d.N);
+  SQ_CHECK_HIP(hipMemcpyAsync(hs.data(), src, hs.size() * 4, hipMemcpyDeviceToHost, s));
+  SQ_CHECK_HIP(hipStreamSynchronize(s));
+  for (int r = 0; r < d.R; ++r) {
+    unsigned seen = 0;
+    for (int j = 0; j < d.N; ++j) {
+      const int32_t v = hs[(size_t)r * d.N + j];
+      if (v < 0 || v >= 2 * d.N || (seen >> v & 1u)) { sq_set_error(h, "sqair_compact_bwd_test: src is not a slot selection"); return -1; }
+      seen |= 1u << v;
+    }
+  }
+  CompactBwdArgs ka; memset(&ka, 0, sizeof(ka));
+  ka.src = src; ka.d_rec_next = d_rec_next; ka.d_temporal_next = d_temporal_next; ka.d_prior_next = d_prior_next;
+  ka.d_rec_p = d_rec_p; ka.d_rec_d = d_rec_d; ka.d_temporal_p = d_temporal_p; ka.d_prior_p = d_prior_p;
+  ka.d_new_temporal = d_new_temporal; ka.d_new_prior = d_new_prior;
+  sq_launch_compact_bwd(ka, h->po, d, s);
+  SQ_CHECK_HIP(hipGetLastError());
+  SQ_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
 extern "C" int sqair_capture_begin(SqairHandle* h, void* stream) {
   if (!h) return -1;
   SQ_CHECK_HIP(hipStreamBeginCapture((hipStream_t)stream, hipStreamCaptureModeThreadLocal));

@@ -200,3 +200,34 @@ def _fresh_bytes(lib, T, B):
     n = lib.sqair_workspace_bytes(h, T, B)
     lib.sqair_destroy(h)
     return n
+
+
+def test_compaction_test_entries_host_side():
+    """sqair_compact_test_layout / sqair_compact_test / sqair_compact_bwd_test (tests/test_compact_kernel.py drives them on the
+    GPU): exported by both builds under the unchanged ABI version, the layout query answers without a GPU with each build's own
+    record, and NULL arguments are refused before any HIP call."""
+    for path, W, pres, ident, slots in ((_capi.LIB_PATH, 168, 54, 165, 8), (_capi.WIDE_LIB_PATH, 416, 132, 409, 16)):
+        lib = _capi.lib(path)
+        for name in ("sqair_compact_test_layout", "sqair_compact_test", "sqair_compact_bwd_test"):
+            assert name in _capi.EXPORTED_SYMBOLS and hasattr(lib, name)
+        assert lib.sqair_abi_version() == _capi.ABI_VERSION == 2
+        for flags, snh, psnh, spec in ((dict(), 256, 256, path == _capi.LIB_PATH), (dict(time_transition="LSTM"), 512, 256, False),
+                                       (dict(n_units=5, prior_transition="LSTM"), 256, 512, False), (dict(n_units=2), 128, 128, False)):
+            F = make_flags(k_particles=5, n_steps_per_image=4, **flags)
+            cfg = make_config(F, (50, 50))
+            h = C.c_void_p()
+            assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
+            try:
+                buf = (C.c_int32 * 24)(*([-5] * 24))
+                assert lib.sqair_compact_test_layout(h, buf, 24) == 20
+                v = list(buf)
+                assert v[20:] == [-5] * 4 and v[:3] == [W, pres, ident] and v[16:19] == [slots, 4, 50]
+                assert v[11:13] == [snh, psnh] and v[19] == int(spec)
+                assert v[13] == lib.sqair_debug_padded_count(h, None) and 0 <= v[14] <= v[13] - snh and 0 <= v[15] <= v[13] - psnh
+                short = (C.c_int32 * 3)()
+                assert lib.sqair_compact_test_layout(h, short, 3) == 20 and list(short) == [W, pres, ident]
+                assert lib.sqair_compact_test_layout(h, None, 3) == -1 and lib.sqair_compact_test_layout(None, short, 3) == -1
+                assert lib.sqair_compact_test(h, *([None] * 13), 0, 1, None) == -1
+                assert lib.sqair_compact_bwd_test(h, *([None] * 10), 1, None) == -1
+            finally:
+                lib.sqair_destroy(h)

@@ -67,14 +67,12 @@ def _host(d):
     return {k: v.cpu().numpy() for k, v in d.items()}
 
 
-@pytest.mark.parametrize("case", sorted(CASES))
-def test_forecast_matches_the_fp64_rollout(case):
-    flags, hw, B, S, Fn = CASES[case]
-    F, P, obs, core = _setup(flags, hw, B, S)
+def _reference_rollout(F, P, obs, hw, B, S, Fn):
+    """CPU: the oracle over the S streamed frames and the fp64 rollout of Fn frames from its state, on the first of DRAWS noise
+    draws whose ORACLE margins (the posterior presences and the forecast's prior draws) are decision-stable.  Returns
+    (noise, forecast noise, reference rollout, the state it started from, margin)."""
     K, N, nzw = int(F.k_particles), int(F.n_steps_per_image), 4 + int(F.n_what) + 1
     R = B * K
-    if "n_what" in flags:
-        assert core.lib is _capi.lib(_capi.WIDE_LIB_PATH)
     orc = O.SqairOracle(P, O.make_cfg(F, hw), torch.float64)
     tiled = O.tile_input_for_iwae(torch.as_tensor(obs, dtype=torch.float64), K)
     rng = np.random.default_rng(23)
@@ -85,9 +83,20 @@ def test_forecast_matches_the_fp64_rollout(case):
         ref = forecast_ref(orc, state, fnoise)
         mg = min(float(presence_margins(seq, noise).min()), float(prior_margin(ref, fnoise).min()))
         if mg >= MARGIN:
-            break
-    else:
-        raise AssertionError("no decision-stable noise draw in {} attempts (last margin {:.2e})".format(DRAWS, mg))
+            return noise, fnoise, ref, state, mg
+    raise AssertionError("no decision-stable noise draw in {} attempts (last margin {:.2e})".format(DRAWS, mg))
+
+
+def _rollout_case(case, flags, hw, B, S, Fn, require=None):
+    """A stream over S frames, then a forecast of Fn frames against the fp64 rollout.  require(ref, state): a condition on the
+    REFERENCE rollout alone (what the case is meant to reach), checked before the HIP path runs."""
+    F, P, obs, core = _setup(flags, hw, B, S)
+    K = int(F.k_particles)
+    if "n_what" in flags:
+        assert core.lib is _capi.lib(_capi.WIDE_LIB_PATH)
+    noise, fnoise, ref, state, mg = _reference_rollout(F, P, obs, hw, B, S, Fn)
+    if require is not None:
+        require(ref, state)
     st = SqairStream(core, B, frames_per_step=S, use_graph=False)
     st.step(obs, noise=noise)
     got = _host(st.forecast(Fn, noise=fnoise))
@@ -103,6 +112,12 @@ def test_forecast_matches_the_fp64_rollout(case):
     lw = st.log_weight_sum.cpu().numpy().astype(np.float64).reshape(B, K)
     assert np.allclose(w, np.exp(lw - lw.max(1, keepdims=True)) / np.exp(lw - lw.max(1, keepdims=True)).sum(1, keepdims=True), rtol=1e-5)
     st.close()
+    return got, ref
+
+
+@pytest.mark.parametrize("case", sorted(CASES))
+def test_forecast_matches_the_fp64_rollout(case):
+    _rollout_case(case, *CASES[case])
 
 
 @pytest.mark.parametrize("prior", ["rnn", "rw", "guided"])

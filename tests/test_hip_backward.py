@@ -254,7 +254,7 @@ def test_rmsprop_step_matches_tf_semantics():
         lib.sqair_destroy(h)
 
 
-def _full_backward_case(K, N, T, B, hw, seed, flags=None, lib_path=None):
+def _full_backward_case(K, N, T, B, hw, seed, flags=None, lib_path=None, options=None):
     from sqair_amd.data import make_sequences, to_float
     from sqair_amd.model import Model, SqairCore
     from tests.hip_util import draw_noise, params32
@@ -262,12 +262,16 @@ def _full_backward_case(K, N, T, B, hw, seed, flags=None, lib_path=None):
     d = make_sequences(B, T=T, canvas=hw, n_objects=(1, 2), obj_size=max(2, min(28, min(hw) // 2)), seed=seed)
     obs = to_float(d["imgs"])
     P = params32(F, hw, 4, 0.05, obs.mean((0, 1)))
-    core = SqairCore(F, hw, lib_path=lib_path)
+    core = SqairCore(F, hw, lib_path=lib_path, options=options)
     core.set_params(P)
     names = ["log_weights_per_timestep", "discrete_log_prob", "presence", "prop_pres", "disc_pres"]
     m = Model(obs, None, core, K, outputs=names)
+    from tests import presence_patterns
     from tests.hip_util import stable_noise
     noise, ref, orc, _ = stable_noise(F, hw, P, obs, T, B * K, N, seed0=100, requires_grad=True, nzw=4 + int(F.n_what) + 1)
+    # which slot layouts the case reaches (tests/presence_patterns.py; the cases that REQUIRE some are in tests/test_presence_paths.py)
+    ref.pattern_counts = presence_patterns.count(presence_patterns.classify_outputs(ref.outputs, N))
+    print(presence_patterns.table(ref.pattern_counts))
     core.noise.copy_(torch.as_tensor(noise).reshape(core.noise.shape))
     core.forward(train=True)
     torch.cuda.synchronize()
@@ -276,6 +280,8 @@ def _full_backward_case(K, N, T, B, hw, seed, flags=None, lib_path=None):
     orc.make_target(ref).backward()
     core.backward()
     torch.cuda.synchronize()
+    if options and options.get("slot_chain"):
+        core.check_chain(train=True)   # (every launch of the in-launch slot chain completed: otherwise the tape means nothing)
     got = {k: v.cpu().numpy() for k, v in core.grads_by_name().items()}
     report = []
     for name, g in got.items():
@@ -329,7 +335,13 @@ def test_full_backward_degenerate_sizes(K, N, T, B):
 @pytest.mark.parametrize("K,N,T,B,hw", [(3, 3, 3, 3, (50, 50)), (5, 4, 4, 2, (50, 50))])
 def test_full_backward_matches_autograd(K, N, T, B, hw):
     """Gradient of the VIMCO target w.r.t. EVERY parameter through the whole recurrence (propagation + discovery +
-    compaction + decoder) against autograd through the fp64 oracle, same noise and identical presence decisions."""
+    compaction + decoder) against autograd through the fp64 oracle, same noise and identical presence decisions.
+
+    What "compaction" means here: at the initialisation's prop_step_bias = 5 a propagated object survives with p ~ 0.993, and these
+    two cases (27 and 40 (frame, row) cells) never drop one -- no cell with a survivor behind a dropped slot, 9 and 15 cells where
+    prop + disc > N.  They cover the compaction adjoint as the identity on the propagated slots plus truncation of the discoveries.
+    Real permutations (holes, holes with discoveries, rows that lose everything), forward and backward, are required and tested in
+    tests/test_presence_paths.py; every presence pattern of the kernels themselves in tests/test_compact_kernel.py."""
     report, ref, _ = _full_backward_case(K, N, T, B, hw, seed=11)
     assert float(ref.prop_pres.detach().sum()) > 0, "case must exercise propagation"
     _check_report(report)

@@ -12,6 +12,7 @@ from sqair_amd import _capi
 from sqair_amd.data import config_inputs, make_sequences, to_float
 from sqair_amd.flags import make_flags
 from sqair_amd.model import Model, SqairCore
+from tests import presence_patterns
 from tests.hip_util_cpu import fixture_params
 from tests.hip_util import (GOLDEN, MARGIN, MAX_DRAWS, draw_noise, params32, presence_margins, prior_presence_margins, rel_err,
                             run_hip, run_oracle, stable_noise)
@@ -39,7 +40,9 @@ def _record_parity(case, worst):
         pass
 
 
-def _check_against(m, ref_out, ref_model, names, T, tol=5e-4):
+def _check_against(m, ref_out, ref_model, names, T, tol=5e-4, scalar_bars=None):
+    # scalar_bars {name: absolute bar}: replaces REL * max(|ref|, 1) for that scalar where a case has MEASURED the fp32 rounding of the
+    # quantity on the oracle itself (tests/test_presence_paths.py); every other bar is the file's own
     # discrete decisions first: exact
     for k in ("presence", "prop_pres", "disc_pres", "obj_id", "num_steps_per_sample"):
         if k in ref_out:
@@ -61,7 +64,7 @@ def _check_against(m, ref_out, ref_model, names, T, tol=5e-4):
         assert rel_err(getattr(m, k).cpu().numpy(), ref_model[k]) < REL, k
     for k in ("elbo_vae", "elbo_iwae", "data_ll", "kl", "log_p_z", "log_q_z_given_x"):
         got, ref = float(getattr(m, k)), float(ref_model[k])
-        assert abs(got - ref) <= REL * max(abs(ref), 1.0), (k, got, ref)
+        assert abs(got - ref) <= (scalar_bars or {}).get(k, REL * max(abs(ref), 1.0)), (k, got, ref)
     return worst
 
 
@@ -91,20 +94,30 @@ def test_forward_matches_golden_fixture(name, options):
         assert abs(float(getattr(m, k)) - float(ref_model[k])) <= 1e-4 * max(1.0, abs(float(ref_model[k]))), k
 
 
-def _live_oracle_case(F, hw=(32, 40), T=3, B=3, tol=5e-4):
+def _live_oracle_inputs(F, hw, T, B):
+    """Frames, parameters and the decision-stable noise draw of a live-oracle case, with the oracle's result."""
     K, N = int(F.k_particles), int(F.n_steps_per_image)
     d = make_sequences(B, T=T, canvas=hw, n_objects=(1, 2), obj_size=20, seed=9)
     obs = to_float(d["imgs"])
     P = params32(F, hw, 5, 0.05, obs.mean((0, 1)))
     # the draw is chosen on the ORACLE's own decision margin (never on the HIP result); presence must then agree exactly
-    noise, ref, _, _ = stable_noise(F, hw, P, obs, T, B * K, N, nums=d["nums"])
-    m = run_hip(F, hw, P, obs, noise, nums=d["nums"])
+    noise, ref, _, margin = stable_noise(F, hw, P, obs, T, B * K, N, nums=d["nums"], nzw=4 + int(F.n_what) + 1)
+    # which slot layouts the case reaches (tests/presence_patterns.py; the cases that REQUIRE some are in tests/test_presence_paths.py)
+    counts = presence_patterns.count(presence_patterns.classify_outputs(ref.outputs, N))
+    print(presence_patterns.table(counts))
+    return dict(d=d, obs=obs, P=P, noise=noise, ref=ref, margin=margin, counts=counts)
+
+
+def _live_oracle_case(F, hw=(32, 40), T=3, B=3, tol=5e-4, options=None, inputs=None, scalar_bars=None):
+    x = inputs or _live_oracle_inputs(F, hw, T, B)
+    d, obs, P, noise, ref = x["d"], x["obs"], x["P"], x["noise"], x["ref"]
+    m = run_hip(F, hw, P, obs, noise, nums=d["nums"], options=options)
     assert np.array_equal(m.prop_pres.cpu().numpy(), ref.prop_pres.numpy())
     assert np.array_equal(m.disc_pres.cpu().numpy(), ref.disc_pres.numpy())
     ref_out = {k: v.numpy() for k, v in ref.outputs.items() if not k.startswith("_")}
     ref_model = {k: getattr(ref, k).numpy() for k in ("log_weights", "elbo_iwae_per_example", "elbo_vae", "elbo_iwae",
                                                       "data_ll", "kl", "log_p_z", "log_q_z_given_x")}
-    _check_against(m, ref_out, ref_model, list(ref_out), T, tol)
+    _check_against(m, ref_out, ref_model, list(ref_out), T, tol, scalar_bars)
     return m, ref
 
 

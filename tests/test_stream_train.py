@@ -116,7 +116,12 @@ def _stable(orc, frames, K, state, rng, F, R, T, grad):
 
 @pytest.mark.parametrize("case", sorted(ORACLE_CASES))
 def test_chunk_two_matches_the_fp64_oracle(case):
-    flags, path, smc = ORACLE_CASES[case]
+    _chunk_two_case(*ORACLE_CASES[case])
+
+
+def _chunk_two_case(flags, path, smc, require=None):
+    """require(out1, out2): a condition on the ORACLE's outputs of the two chunks (what the case is meant to reach), checked before
+    the device runs chunk 2."""
     B, T = 3, 3
     F, obs, P = _setup(flags, B, 2 * T, seed=23)
     K = int(F.k_particles)
@@ -142,6 +147,8 @@ def test_chunk_two_matches_the_fp64_oracle(case):
     assert (st2.t.numpy()[:(B - 1) * K] >= 1).all()                 # imported counters
     noise2, target, out2, _ = _stable(orc, obs[T:], K, st2, rng, F, R, T, grad=True)
     assert out2["prop_pres"][0].detach().numpy()[:(B - 1) * K].any()          # present objects propagated at the chunk's first frame
+    if require is not None:
+        require(out1, out2)
     for p in orc.P.values():
         p.grad = None
     target.backward()
