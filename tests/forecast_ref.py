@@ -10,6 +10,8 @@ import torch
 from oracle import sqair_oracle as O
 
 NAMES = ("what", "where", "presence", "presence_prob", "presence_logit", "obj_id", "canvas", "glimpse")
+# extras: the prior's statistics of every slot BEFORE the merge (the decisions' margins; which latent regime the rollout visits)
+EXTRAS = ("_prior_presence_prob", "_prior_where_scale", "_prior_what_scale", "_prior_logit", "_prior_prev_presence")
 
 
 def forecast_ref(orc, state, noise):
@@ -20,10 +22,11 @@ def forecast_ref(orc, state, noise):
     N, nw, dt = c.N, c.n_what, orc.dtype
     noise = torch.as_tensor(np.asarray(noise), dtype=dt)
     z, prior, prev_ids, last_id = state.z, state.prior, state.prev_ids, state.last_id
-    outs = {n: [] for n in NAMES + ("_prior_presence_prob",)}
+    outs = {n: [] for n in NAMES + EXTRAS}
     with torch.no_grad():
         for f in range(noise.shape[0]):
             eps = noise[f][:, 0]                                      # [B', N, nzw]
+            z_prev = z
             (where_loc, where_scale, what_loc, what_scale, logit), prior_new = orc.propagate_prior(z, prior)
             what = what_loc + what_scale * eps[..., 4:4 + nw]
             where = where_loc + where_scale * eps[..., 0:4]
@@ -43,6 +46,8 @@ def forecast_ref(orc, state, noise):
             for n, v in zip(NAMES, (what, where, pres, prob, logit, ids, canvas, glimpse)):
                 outs[n].append(v.squeeze(-1) if n in ("presence", "presence_prob", "presence_logit", "obj_id") else v)
             outs["_prior_presence_prob"].append(torch.sigmoid(prop[3]).squeeze(-1))
+            for n, v in zip(EXTRAS[1:], (where_scale, what_scale, prop[3], z_prev[2])):
+                outs[n].append(v)
     res = {n: torch.stack(v, 0) for n, v in outs.items()}
     res["_final"] = (z, prior, prev_ids, last_id)
     return res

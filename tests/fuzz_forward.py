@@ -1,7 +1,7 @@
 """Randomised configuration sweep of the forward pass against the live oracle (a checker script, not collected by pytest: it
 lives under tests/ because it calls the oracle).  On the GPU box:
 
-    python tests/fuzz_forward.py [n_cases] [seed] [--grad | --chain | --gen]
+    python tests/fuzz_forward.py [n_cases] [seed] [--grad | --chain | --gen] [--regime]
 
 Every case draws sizes (particles, slots, frames, sequences, frame shape, n_what, n_units), cells, priors and the boolean model
 flags at random inside the library's limits, a decision-stable noise draw on the ORACLE's margin (tests/hip_util.stable_noise),
@@ -11,6 +11,10 @@ the sizes are drawn inside what the in-launch slot chain takes (VanillaRNN slot 
 pass with `slot_chain` on must reproduce the launches bit for bit, eager and as a graph replay.  With --gen the generation
 modes (`sample_from_prior`, frames after a random `generate_after` drawn from the priors: seq.py:198-200,
 sqair_modules.py:157-170, 294-302) with a second noise tensor, the draw chosen on the oracle's posterior AND prior margins.
+With --regime (alone or with --grad) every case also draws a random subset of the "tight" parameter edits of
+tests/latent_regimes.py (EDITS: glimpses off the frame, the scale clamp, floored scales, saturated presence logits, a bright canvas,
+a floored prior) and prints which latent regimes the ORACLE reaches; the bars stay what they are, --grad's second bar included (the
+cases tests/test_regime_paths.py pins are the edits one by one and combined; this sweeps their combinations over the other flags).
 Round 5: 100 forward cases
 (seeds 1, 3) without a failure; 30 gradient cases (seed 2) with one beyond the tight bar, on parameters whose gradient is 3e-4 of
 the largest one, by exactly what fp32 autograd through the oracle misses the fp64 one (run_case's second bar).  Prints one
@@ -99,13 +103,30 @@ def run_gen_case(flags, hw, T, B, seed, rng):
     assert abs(float(m.elbo_iwae) - float(ref.elbo_iwae)) <= 1e-4 * max(1.0, abs(float(ref.elbo_iwae)))
 
 
-def run_case(flags, hw, T, B, seed, grad):
+def draw_edits(rng):
+    """A random subset (one to three) of the "tight" edits of tests/latent_regimes.py; the three edits of the discovery where bias
+    exclude one another."""
+    from tests import latent_regimes as LR
+    names = [n for n in sorted(LR.EDITS) if LR.EDITS[n][2] == "tight"]
+    picked, where_bias = [], ("magnify_off_frame", "minify_off_frame", "scale_clamp")
+    for n in rng.permutation(names)[:int(rng.integers(1, 4))]:
+        if n in where_bias and any(p in where_bias for p in picked):
+            continue
+        picked.append(str(n))
+    return tuple(picked)
+
+
+def run_case(flags, hw, T, B, seed, grad, edits=None):
     F = make_flags(**flags)
     K, N = int(F.k_particles), int(F.n_steps_per_image)
     if grad:
         from tests.test_hip_backward import _check_report, _full_backward_case
         extra = {k: v for k, v in flags.items() if k not in ("k_particles", "n_steps_per_image")}
-        report, _, _ = _full_backward_case(max(K, 2), N, T, B, hw, seed=seed, flags=extra)
+        report, ref, _ = _full_backward_case(max(K, 2), N, T, B, hw, seed=seed, flags=extra, edits=edits)
+        if edits:
+            from oracle import sqair_oracle as O
+            from tests import latent_regimes as LR
+            print("     " + LR.table(LR.counts_of(ref.outputs, O.make_cfg(make_flags(**dict(flags, k_particles=max(K, 2))), hw))))
         try:
             _check_report(report, ill_scale=True)
         except AssertionError:
@@ -121,7 +142,13 @@ def run_case(flags, hw, T, B, seed, grad):
     d = make_sequences(B, T=T, canvas=hw, n_objects=(0, 2), obj_size=max(2, min(20, min(hw) // 2)), seed=seed)
     obs = to_float(d["imgs"])
     P = params32(F, hw, seed, 0.05, obs.mean((0, 1)))
+    if edits:
+        from tests import latent_regimes as LR
+        P = LR.apply_edits(P, F, edits)
     noise, ref, _, _ = stable_noise(F, hw, P, obs, T, B * K, N, seed0=seed, nums=d["nums"], nzw=4 + int(F.n_what) + 1)
+    if edits:
+        from oracle import sqair_oracle as O
+        print("     " + LR.table(LR.counts_of(ref.outputs, O.make_cfg(F, hw))))
     m = run_hip(F, hw, P, obs, noise, nums=d["nums"])
     ref_out = {k: v.numpy() for k, v in ref.outputs.items() if not k.startswith("_")}
     ref_model = {k: getattr(ref, k).numpy() for k in ("log_weights", "elbo_iwae_per_example", "elbo_vae", "elbo_iwae",
@@ -131,7 +158,8 @@ def run_case(flags, hw, T, B, seed, grad):
 
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
-    grad, chain, gen = "--grad" in sys.argv, "--chain" in sys.argv, "--gen" in sys.argv
+    grad, chain, gen, regime = "--grad" in sys.argv, "--chain" in sys.argv, "--gen" in sys.argv, "--regime" in sys.argv
+    assert not (regime and (chain or gen)), "--regime goes with the forward sweep and with --grad"
     n, seed = (int(args[0]) if args else 30), (int(args[1]) if len(args) > 1 else 0)
     rng = np.random.default_rng(seed)
     failures = []
@@ -142,14 +170,15 @@ def main():
             B = int(rng.integers(1, 65))
             while B * flags["k_particles"] > 320:
                 B = max(1, B // 2)
-        tag = "case {:3d}: hw {} T {} B {} {}".format(i, hw, T, B, flags)
+        edits = draw_edits(rng) if regime else None
+        tag = "case {:3d}: hw {} T {} B {} {}{}".format(i, hw, T, B, flags, " edits {}".format(edits) if regime else "")
         try:
             if chain:
                 run_chain_case(flags, hw, T, B, seed * 1000 + i)
             elif gen:
                 run_gen_case(flags, hw, T, B, seed * 1000 + i, rng)
             else:
-                run_case(flags, hw, T, B, seed * 1000 + i, grad)
+                run_case(flags, hw, T, B, seed * 1000 + i, grad, edits)
             print("ok   " + tag, flush=True)
         except AssertionError as e:
             if "no decision-stable noise draw" in str(e):

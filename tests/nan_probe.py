@@ -1,6 +1,12 @@
 """Trains with the reference recipe (tools/train_demo.py's setting) and checks the gradient after EVERY step: at the first
 non-finite value prints which parameters are affected and the state of the forward pass that produced it.
-    python tests/nan_probe.py [steps] [flag=value ...]"""
+    python tests/nan_probe.py [steps] [flag=value ...]
+
+An ad-hoc training loop, not a test: it found the whole-gradient deviation at tiny glimpse scales (`sq_sigmoid_geo`) by getting
+there.  The latent values a training run drifts into -- tiny, clamped, magnified and minified glimpse scales, glimpses off the
+frame, floored standard deviations, saturated presence logits, a bright canvas -- are now pinned against the fp64 oracle without
+training: tests/latent_regimes.py moves the oracle there by editing a few heads, tests/test_latent_regimes.py (CPU) proves that it
+arrives, tests/test_regime_paths.py (-m gpu) holds the kernels to the suite's bars there."""
 import sys
 
 sys.path.insert(0, ".")

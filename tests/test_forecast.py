@@ -54,10 +54,13 @@ def _frames(hw, B, T, seed):
     return to_float(make_sequences(B, T=T, canvas=hw, seed=seed)["imgs"])
 
 
-def _setup(flags, hw, B, T, seed=19):
+def _setup(flags, hw, B, T, seed=19, edits=None):
     F = make_flags(**flags)
     obs = _frames(hw, B, T, seed)
     P = params32(F, hw, 3, 0.05, obs.mean((0, 1)))
+    if edits:   # names of tests/latent_regimes.EDITS (tests/test_regime_paths.py)
+        from tests import latent_regimes
+        P = latent_regimes.apply_edits(P, F, edits)
     core = SqairCore(F, hw)
     core.set_params(P)
     return F, P, obs, core
@@ -87,10 +90,10 @@ def _reference_rollout(F, P, obs, hw, B, S, Fn):
     raise AssertionError("no decision-stable noise draw in {} attempts (last margin {:.2e})".format(DRAWS, mg))
 
 
-def _rollout_case(case, flags, hw, B, S, Fn, require=None):
+def _rollout_case(case, flags, hw, B, S, Fn, require=None, edits=None):
     """A stream over S frames, then a forecast of Fn frames against the fp64 rollout.  require(ref, state): a condition on the
     REFERENCE rollout alone (what the case is meant to reach), checked before the HIP path runs."""
-    F, P, obs, core = _setup(flags, hw, B, S)
+    F, P, obs, core = _setup(flags, hw, B, S, edits=edits)
     K = int(F.k_particles)
     if "n_what" in flags:
         assert core.lib is _capi.lib(_capi.WIDE_LIB_PATH)

@@ -254,30 +254,44 @@ def test_rmsprop_step_matches_tf_semantics():
         lib.sqair_destroy(h)
 
 
-def _full_backward_case(K, N, T, B, hw, seed, flags=None, lib_path=None, options=None):
+def _full_backward_inputs(K, N, T, B, hw, seed, flags=None, edits=None, seed0=100):
+    """CPU: flags, frames, parameters (with the named tests/latent_regimes.EDITS, if any), the decision-stable noise draw and the
+    fp64 oracle's pass through it with autograd on (seed0: the first noise seed tried).  Returns (F, obs, P, noise, oracle model,
+    oracle)."""
     from sqair_amd.data import make_sequences, to_float
-    from sqair_amd.model import Model, SqairCore
-    from tests.hip_util import draw_noise, params32
+    from tests import presence_patterns
+    from tests.hip_util import params32, stable_noise
     F = make_flags(k_particles=K, n_steps_per_image=N, **(flags or {}))
     d = make_sequences(B, T=T, canvas=hw, n_objects=(1, 2), obj_size=max(2, min(28, min(hw) // 2)), seed=seed)
     obs = to_float(d["imgs"])
     P = params32(F, hw, 4, 0.05, obs.mean((0, 1)))
+    if edits:
+        from tests import latent_regimes
+        P = latent_regimes.apply_edits(P, F, edits)
+    noise, ref, orc, _ = stable_noise(F, hw, P, obs, T, B * K, N, seed0=seed0, requires_grad=True, nzw=4 + int(F.n_what) + 1)
+    # which slot layouts the case reaches (tests/presence_patterns.py; the cases that REQUIRE some are in tests/test_presence_paths.py)
+    ref.pattern_counts = presence_patterns.count(presence_patterns.classify_outputs(ref.outputs, N))
+    print(presence_patterns.table(ref.pattern_counts))
+    return F, obs, P, noise, ref, orc
+
+
+def _full_backward_case(K, N, T, B, hw, seed, flags=None, lib_path=None, options=None, edits=None, inputs=None):
+    """inputs: what `_full_backward_inputs` returned for the same arguments, its oracle not yet differentiated (a caller that has
+    looked at the oracle's outputs first)."""
+    from sqair_amd.model import Model, SqairCore
+    F, obs, P, noise, ref, orc = inputs or _full_backward_inputs(K, N, T, B, hw, seed, flags, edits)
     core = SqairCore(F, hw, lib_path=lib_path, options=options)
     core.set_params(P)
     names = ["log_weights_per_timestep", "discrete_log_prob", "presence", "prop_pres", "disc_pres"]
     m = Model(obs, None, core, K, outputs=names)
-    from tests import presence_patterns
-    from tests.hip_util import stable_noise
-    noise, ref, orc, _ = stable_noise(F, hw, P, obs, T, B * K, N, seed0=100, requires_grad=True, nzw=4 + int(F.n_what) + 1)
-    # which slot layouts the case reaches (tests/presence_patterns.py; the cases that REQUIRE some are in tests/test_presence_paths.py)
-    ref.pattern_counts = presence_patterns.count(presence_patterns.classify_outputs(ref.outputs, N))
-    print(presence_patterns.table(ref.pattern_counts))
     core.noise.copy_(torch.as_tensor(noise).reshape(core.noise.shape))
     core.forward(train=True)
     torch.cuda.synchronize()
     assert np.array_equal(core.out["prop_pres"].cpu().numpy(), ref.prop_pres.detach().numpy())
     assert np.array_equal(core.out["disc_pres"].cpu().numpy(), ref.disc_pres.detach().numpy())
-    orc.make_target(ref).backward()
+    if not getattr(ref, "differentiated", False):
+        orc.make_target(ref).backward()
+        ref.differentiated = True
     core.backward()
     torch.cuda.synchronize()
     if options and options.get("slot_chain"):

@@ -94,12 +94,16 @@ def test_forward_matches_golden_fixture(name, options):
         assert abs(float(getattr(m, k)) - float(ref_model[k])) <= 1e-4 * max(1.0, abs(float(ref_model[k]))), k
 
 
-def _live_oracle_inputs(F, hw, T, B):
-    """Frames, parameters and the decision-stable noise draw of a live-oracle case, with the oracle's result."""
+def _live_oracle_inputs(F, hw, T, B, edits=None):
+    """Frames, parameters and the decision-stable noise draw of a live-oracle case, with the oracle's result.  edits: names of
+    tests/latent_regimes.EDITS applied to the initialised parameters (tests/test_regime_paths.py)."""
     K, N = int(F.k_particles), int(F.n_steps_per_image)
     d = make_sequences(B, T=T, canvas=hw, n_objects=(1, 2), obj_size=20, seed=9)
     obs = to_float(d["imgs"])
     P = params32(F, hw, 5, 0.05, obs.mean((0, 1)))
+    if edits:
+        from tests import latent_regimes
+        P = latent_regimes.apply_edits(P, F, edits)
     # the draw is chosen on the ORACLE's own decision margin (never on the HIP result); presence must then agree exactly
     noise, ref, _, margin = stable_noise(F, hw, P, obs, T, B * K, N, nums=d["nums"], nzw=4 + int(F.n_what) + 1)
     # which slot layouts the case reaches (tests/presence_patterns.py; the cases that REQUIRE some are in tests/test_presence_paths.py)

@@ -48,12 +48,20 @@ def _scaled(got, want):
 
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_stream_matches_the_fp64_particle_filter(case):
-    flags, B, TS, frames, frac, caller = CASES[case]
+    _filter_case(case, *CASES[case])
+
+
+def _filter_case(case, flags, B, TS, frames, frac, caller, edits=None, require=None):
+    """edits: names of tests/latent_regimes.EDITS applied to the parameters; require(outputs, step): a condition on the ORACLE
+    filter's proposal of a step (what the case is meant to reach), checked before the device runs that step."""
     F = make_flags(**flags)
     K, N, nzw = int(F.k_particles), int(F.n_steps_per_image), 4 + int(F.n_what) + 1
     R = B * K
     obs = to_float(make_sequences(B, T=frames, canvas=HW, seed=19)["imgs"])
     P = params32(F, HW, 3, 0.05, obs.mean((0, 1)))
+    if edits:   # names of tests/latent_regimes.EDITS (tests/test_regime_paths.py)
+        from tests import latent_regimes
+        P = latent_regimes.apply_edits(P, F, edits)
     core = SqairCore(F, HW)
     core.set_params(P)
     if "n_what" in flags:
@@ -74,6 +82,8 @@ def test_stream_matches_the_fp64_particle_filter(case):
                 break
         else:
             raise AssertionError("no decision-stable noise draw in {} attempts at step {}".format(DRAWS, s))
+        if require is not None:
+            require(prop[0], s)
         lw0_ref, lz0_ref = pf.log_w.copy(), pf.log_z.copy()
         ref, rw = pf.commit(prop)
         lw0 = st.log_weight_sum.cpu().numpy()
@@ -157,3 +167,4 @@ def test_stream_matches_the_fp64_particle_filter(case):
         assert n["went"] == steps * B, n
     assert n["dec_skipped"] <= max(1, 0.2 * n["dec_checked"]), n
     st.close()
+    return n, worst

@@ -31,10 +31,13 @@ LSTM = dict(time_transition="LSTM", prior_transition="LSTM")
 OUTS = ("what", "where", "presence", "obj_id", "log_weights_per_timestep")
 
 
-def _setup(flags, B, T, seed=19, options=None):
+def _setup(flags, B, T, seed=19, options=None, edits=None):
     F = make_flags(learning_rate=0.0, **flags)   # (lr 0: the parameters are held, the optimiser step changes nothing)
     obs = to_float(make_sequences(B, T=T, canvas=HW, n_objects=(1, 2), obj_size=10, seed=seed)["imgs"])
     P = params32(F, HW, 3, 0.05, obs.mean((0, 1)))
+    if edits:   # names of tests/latent_regimes.EDITS (tests/test_regime_paths.py)
+        from tests import latent_regimes
+        P = latent_regimes.apply_edits(P, F, edits)
     return F, obs, P
 
 
@@ -119,11 +122,11 @@ def test_chunk_two_matches_the_fp64_oracle(case):
     _chunk_two_case(*ORACLE_CASES[case])
 
 
-def _chunk_two_case(flags, path, smc, require=None):
+def _chunk_two_case(flags, path, smc, require=None, edits=None):
     """require(out1, out2): a condition on the ORACLE's outputs of the two chunks (what the case is meant to reach), checked before
     the device runs chunk 2."""
     B, T = 3, 3
-    F, obs, P = _setup(flags, B, 2 * T, seed=23)
+    F, obs, P = _setup(flags, B, 2 * T, seed=23, edits=edits)
     K = int(F.k_particles)
     R = B * K
     core = _core(F, P)
