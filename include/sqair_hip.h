@@ -354,6 +354,40 @@ int sqair_forecast(SqairHandle* h, const float* flat_params, const void* packed,
                    int F, int B, const int32_t* src_rows /*NULL: the map of sqair_set_state*/,
                    const SqairForecastOutputs* out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- missing-frame steps: unobserved lanes coast on the prior, inside the pass ------------------------------------------------
+ * Cameras drop frames, lanes of a batch run at different rates, an object passes behind an occluder the caller knows about.  With
+ * a mask set, every following inference pass with a carried state reads observed[T, B] (device int32, nonzero = the lane has a
+ * frame) ON THE DEVICE, so one captured graph serves every pattern of present and missing lanes.  For an observed (frame, lane)
+ * nothing changes, bit for bit.  For an unobserved (frame t, lane b) each of the lane's K rows takes a COASTED frame, the
+ * particle filter's treatment of a missing observation -- propose from the transition prior, leave the weight alone, let time
+ * advance:
+ *   records and ids: what / where / presence / presence_logit / presence_prob / obj_id of frame t are exactly the frame
+ *       sqair_forecast would produce from the rows of t - 1 (the same device code: PropagatePrior, the draws from noise slot s = 0 of
+ *       the frame's ordinary noise -- s = 1 is not read --, compute_object_ids with nothing discovered, the N slots present-first
+ *       in a stable order); last_id does not move;
+ *   prior state: each slot's new prior-cell state travels with it, as in the forecast;
+ *   temporal state: HELD (no glimpse, no update) and carried with its slot through the same permutation -- the reference's merge,
+ *       select_present over [temporal_prev | init_temporal] with discovery absent; an LSTM state moves as [h | c];
+ *   the row's frame counter advances as for any frame: a coasted frame is time that passed;
+ *   log_weights_per_timestep = 0, so a coasted frame changes neither the accumulated log weights, nor the ESS, nor log_evidence;
+ *   canvas and glimpse are the decoder's render of the coasted records;
+ *   num_prop_steps_per_sample = num_steps_per_sample = the number of present slots, num_disc_steps_per_sample = 0, prop_pres = the
+ *       compacted presence, disc_pres = 0;
+ *   every other bound SqairOutputs buffer is written as 0 for that (frame, row): the posterior locs and scales, all *_log_prob,
+ *       disc_prob, prop_prob, step_log_prob, discrete_log_prob, data_ll_per_sample, kl_per_sample, log_q_z_given_x_per_sample,
+ *       log_p_z_per_sample.
+ * The frame of an unobserved lane influences no output and no state word, but it must be FINITE: the pass still computes on it
+ * (the posterior runs on every row; the step is bound by its dependent launches, not its rows).  Within a pass of T > 1 frames the
+ * mask is per frame: frame t + 1 of a lane reads the coasted frame t.  A pass with a mask has exactly T + 1 kernel nodes more
+ * (k_coast_step after each frame's compaction, k_coast_finish before the state export, the history push and the resampler, so the
+ * history records the coasted outputs and the resampler reads zero log weights); without one nothing is launched.
+ * The pointer is remembered by the handle and frozen into captured graphs, as the state's pointers are.  NULL observed: off.
+ * Refused (return -1, text in sqair_last_error, before any HIP call): no state set, T < 1, a B other than the state's, a
+ * configuration with sample_from_prior; at pass time: a pass whose T is not the T given here, and every training call
+ * (sqair_forward_train, sqair_forward_train_carry) while a mask is set -- training on gappy streams is out of scope.
+ * sqair_set_state switching the state off, or to another B, switches the mask off. */
+int sqair_set_observed(SqairHandle* h, const int32_t* observed /* device [T,B]; NULL: off */, int T, int B);
+
 /* ---- objective ---------------------------------------------------------------------------------
  * Fused IWAE / VIMCO reductions over [T,B,K] (reference: Model._build sqair/model.py:88-103,
  * targets.iwae / vimco_control_variate / vimco sqair/targets.py:38-75, make_target model.py:150-158,

@@ -151,6 +151,7 @@ _PROTOS = {
     "sqair_history_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32]),
     "sqair_set_history": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_uint32]),
     "sqair_history_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SqairTraceOutputs), C.c_void_p]),
+    "sqair_set_observed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "sqair_forecast_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
     "sqair_forecast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                  C.POINTER(SqairForecastOutputs), C.c_void_p, C.c_int64, C.c_void_p]),

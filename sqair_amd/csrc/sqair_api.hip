@@ -1005,7 +1005,9 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
                     int T, int B, int t_offset, const SqairOutputs* outp, float* wsbase, int64_t ws_bytes,
                     hipStream_t s, bool train, int parts, const SqStateRes* carry = nullptr) {
   const SqairConfig& c = h->cfg;
-  if (!carry && (sq_state_refusal(h, train, B, t_offset) != 0 || sq_smc_refusal(h, outp) != 0 || sq_history_refusal(h, T, B, outp) != 0)) return -1;
+  if (!carry && (sq_observed_refusal(h, train, T) != 0 || sq_state_refusal(h, train, B, t_offset) != 0 || sq_smc_refusal(h, outp) != 0 ||
+                 sq_history_refusal(h, T, B, outp) != 0))
+    return -1;
   const SqStateRes st = carry ? *carry : sq_handle_state(h);
   if (!flat || !packed || !obs || !noise || !outp || !wsbase || T < 1 || B < 1) {
     sq_set_error(h, "sqair_forward: null argument or bad T/B");
@@ -1334,6 +1336,15 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
       ka.flat = flat; ka.t = t; ka.out = out;
       ka.src_out = train ? w.src + (size_t)t * M : nullptr;
       sq_launch_compact(ka, po, d, s);
+      // missing-frame steps (sqair_set_observed): the rows of lanes without a frame take the prior's frame instead, from section A's
+      // statistics and prior states of this frame, their temporal states held
+      if (st.observed) {
+        CoastArgs ca; memset(&ca, 0, sizeof(ca));
+        ca.observed = st.observed; ca.t = t; ca.rec_prev = rec_prev; ca.pstats = pstats_t; ca.ps_ld = PS_LD; ca.prior_p = prior_p;
+        ca.temporal_prev = temporal_prev; ca.noise = nz; ca.last_id_prev = ka.last_id_prev; ca.last_id_next = ka.last_id_next;
+        ca.rec_next = rec_next; ca.prior_next = ka.prior_next; ca.temporal_next = ka.temporal_next; ca.out = out; ca.cfg = c;
+        sq_launch_coast_step(ca, d, s);
+      }
     }
   }
   if (!(parts & 4)) return 0;
@@ -1361,6 +1372,13 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
     ia.canvas = out.canvas; ia.data_ll = w.dll; ia.qz = w.qz; ia.pz = w.pz; ia.t = 0; ia.n_frames = T; ia.out = out;
     ia.std_fg = c.output_std; ia.std_bg = c.background_std;
     if (sq_launch_insert_loglik(ia, d, s) != 0) { sq_set_error(h, "sqair_forward: the decoder canvas launch failed (dynamic LDS limit)"); return -2; }
+  }
+  // missing-frame steps: the outputs H and J wrote for unobserved lanes become those of a coasted frame (log weight 0) -- before
+  // the history records them and the resampler reads them
+  if (st.observed) {
+    CoastFinishArgs fa; memset(&fa, 0, sizeof(fa));
+    fa.observed = st.observed; fa.rec = w.rec_m_all + (size_t)M * RW; fa.T = T; fa.out = out;
+    sq_launch_coast_finish(fa, d, s);
   }
   // final recurrent state (for state-level parity checks), in the caller's widths: [hidden | cell] halves without their padding
   const int unh = h->ucfg.n_hidden;
@@ -1406,7 +1424,7 @@ extern "C" int sqair_forward_train(SqairHandle* h, const float* flat_params, con
                                    const float* noise, int T, int B, int t_offset, const SqairOutputs* out,
                                    void* workspace, int64_t workspace_bytes, void* stream) {
   if (!h) return -1;
-  if (sq_state_refusal(h, true, B, t_offset) != 0) return -1;
+  if (sq_observed_refusal(h, true, T) != 0 || sq_state_refusal(h, true, B, t_offset) != 0) return -1;
   if (!sq_trainable_frame(h)) return -1;
   return sq_forward_impl(h, flat_params, (const float*)packed, obs, noise, T, B, t_offset, out, (float*)workspace,
                          workspace_bytes, (hipStream_t)stream, true, 7);
@@ -1418,7 +1436,7 @@ extern "C" int sqair_forward_train_carry(SqairHandle* h, const float* flat_param
                                          const float* noise, int T, int B, const SqairCarry* carry, const SqairOutputs* out,
                                          void* train_workspace, int64_t workspace_bytes, void* stream) {
   if (!h) return -1;
-  if (sq_carry_refusal(h, "sqair_forward_train_carry", B, carry, out) != 0) return -1;
+  if (sq_observed_refusal(h, true, T) != 0 || sq_carry_refusal(h, "sqair_forward_train_carry", B, carry, out) != 0) return -1;
   if (!out) {
     sq_set_error(h, "sqair_forward_train_carry: null argument");
     return -1;
@@ -1657,7 +1675,9 @@ extern "C" int sqair_graph_capture(SqairHandle* h, const float* flat_params, con
                                    const float* noise, int T, int B, int t_offset, const SqairOutputs* out,
                                    void* workspace, int64_t workspace_bytes, void* stream) {
   if (!h) return -1;
-  if (sq_state_refusal(h, false, B, t_offset) != 0 || sq_smc_refusal(h, out) != 0 || sq_history_refusal(h, T, B, out) != 0) return -1;
+  if (sq_observed_refusal(h, false, T) != 0 || sq_state_refusal(h, false, B, t_offset) != 0 || sq_smc_refusal(h, out) != 0 ||
+      sq_history_refusal(h, T, B, out) != 0)
+    return -1;
   hipStream_t s = (hipStream_t)stream;
   if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
   if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }

@@ -323,6 +323,33 @@ struct ForecastArgs {
   SqairConfig cfg;
 };
 int sq_launch_forecast_step(const ForecastArgs& a, Dims d, hipStream_t s);
+// Missing-frame steps (sqair_set_observed): the frame of an unobserved (frame t, lane b) is the forecast's frame from the rows of
+// t - 1 -- the same device function as k_forecast_step on section A's statistics of this frame -- with the temporal state of every
+// slot held and carried through the same permutation.  k_coast_step runs right after the frame's k_compact and overwrites what
+// that wrote for the rows of unobserved lanes; one wavefront per (row, slot), workgroups of observed lanes return at once.
+struct CoastArgs {
+  const int* observed;                 // [T][B] device, nonzero = the lane has a frame
+  int t;                               // frame inside the pass (and inside the outputs)
+  const float* rec_prev;               // records of frame t - 1 [R][N][rec::W]
+  const float* pstats; int ps_ld;      // section A's prior statistics of this frame
+  const float* prior_p;                // section A's new prior state of every slot [R][N][psnh]
+  const float* temporal_prev;          // temporal state of frame t - 1 [R][N][snh]: held
+  const float* noise;                  // noise of frame t [R][2][N][nzw] (slot s = 0 read)
+  const float* last_id_prev; float* last_id_next;
+  float* rec_next; float* prior_next; float* temporal_next;
+  SqairOutputs out;
+  SqairConfig cfg;
+};
+int sq_launch_coast_step(const CoastArgs& a, Dims d, hipStream_t s);
+// k_coast_finish: one launch of the epilogue, one workgroup per (row, frame): for unobserved lanes every per-row and per-slot output
+// the posterior path wrote becomes 0 (the log weight among them), the counts those of the coasted records.
+struct CoastFinishArgs {
+  const int* observed;                 // [T][B]
+  const float* rec;                    // merged records of frames 0..T-1 [T][R][N][rec::W]
+  int T;
+  SqairOutputs out;
+};
+int sq_launch_coast_finish(const CoastFinishArgs& a, Dims d, hipStream_t s);
 // Predictive summaries of a forecast: one workgroup per (frame, lane b); w = softmax of the lane's K log weights (NULL: uniform),
 // mean_canvas[f][b] = sum_k w_k canvas[f][b*K + k], expected_count[f][b] = sum_k w_k (present slots of particle k).  Every sum over k
 // runs in index order.

@@ -1414,62 +1414,138 @@ int sq_launch_generate_disc(const GenArgs& a, POff po, Dims d, hipStream_t s) {
 // to its destination.  (The N presences are drawn by each of the row's N wavefronts: a few loads, against a loop over the slots in
 // one wavefront whose dependent memory round trips made it the longest launch of a forecast frame, 11 us at cfg-2.)
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_forecast_step(const ForecastArgs a, const Dims d SQ_TLP) {
-  SQ_TL_SCOPE;
-  const int r = blockIdx.x, k = blockIdx.y, lane = threadIdx.x, N = d.N, nw = d.nw;
+// The frame of one (row r, slot k) for the wavefront that calls it, shared by the forecast and the missing-frame step of a pass
+// (k_coast_step) so that both execute the same instructions on the same inputs.  `o_*`: the six per-slot outputs, each optional;
+// f: the frame's index inside them.  Returns slot k's destination.
+struct PriorFrameOut { float *what, *where, *presence, *presence_prob, *presence_logit, *obj_id; };
+__device__ __forceinline__ int sq_prior_frame_slot(const SqairConfig& cfg, const Dims& d, int r, int k, int lane, const float* rec_prev,
+                                                   const float* pstats, int ps_ld, const float* prior_p, const float* noise,
+                                                   float* rec_next, float* prior_next, int f, const PriorFrameOut& out) {
+  const int N = d.N, nw = d.nw;
   float lg = 0.0f, pres = 0.0f;
   if (lane < N) {
     const size_t rk = (size_t)r * N + lane;
-    lg = sq_prior_logit(a.cfg, a.rec_prev + rk * rec::W, a.pstats + rk * a.ps_ld);
-    pres = a.noise[(((size_t)r * 2 + 0) * N + lane) * d.nzw + 4 + nw] < sq_sigmoid(lg) ? 1.0f : 0.0f;
+    lg = sq_prior_logit(cfg, rec_prev + rk * rec::W, pstats + rk * ps_ld);
+    pres = noise[(((size_t)r * 2 + 0) * N + lane) * d.nzw + 4 + nw] < sq_sigmoid(lg) ? 1.0f : 0.0f;
   }
   const unsigned long long all = (1ull << N) - 1ull;   // (N <= 16)
   const unsigned long long present = __ballot(lane < N && pres != 0.0f) & all;
   const unsigned long long below = (1ull << lane) - 1ull;
   const int dst_l = (pres != 0.0f) ? __popcll(present & below) : __popcll(present) + __popcll(~present & all & below);
-  {
-    const size_t rk = (size_t)r * N + k;
-    const float* rm = a.rec_prev + rk * rec::W;
-    const float* ps = a.pstats + rk * a.ps_ld;
-    const float* gn = a.noise + (((size_t)r * 2 + 0) * N + k) * d.nzw;
-    const int dst = __shfl(dst_l, k);
-    const float lgk = __shfl(lg, k), pk = __shfl(pres, k);
-    const float id = rm[rec::ID] * pk - (1.0f - pk);   // compute_object_ids of a propagated slot
-    float* rn = a.rec_next + ((size_t)r * N + dst) * rec::W;
-    const size_t o = ((size_t)a.f * d.R + r) * N + dst;
-    for (int i = lane; i < rec::W; i += 64) {
-      float v = 0.0f;
-      if (i < 4) {
-        v = sq_prior_where_sample(a.cfg, rm, ps, nw, i, gn[i]);
-        if (a.out.where) a.out.where[o * 4 + i] = v;
-      } else if (i < rec::WHAT + nw) {
-        v = sq_prior_what_sample(a.cfg, rm, ps, nw, i - rec::WHAT, gn[i]);
-        if (a.out.what) a.out.what[o * nw + (i - rec::WHAT)] = v;
-      } else if (i == rec::PRES) {
-        v = pk;
-      } else if (i == rec::LOGIT) {
-        v = lgk;
-      } else if (i == rec::PROB) {
-        v = sq_sigmoid(lgk);
-      } else if (i == rec::ID) {
-        v = id;
-      }
-      rn[i] = v;
+  const size_t rk = (size_t)r * N + k;
+  const float* rm = rec_prev + rk * rec::W;
+  const float* ps = pstats + rk * ps_ld;
+  const float* gn = noise + (((size_t)r * 2 + 0) * N + k) * d.nzw;
+  const int dst = __shfl(dst_l, k);
+  const float lgk = __shfl(lg, k), pk = __shfl(pres, k);
+  const float id = rm[rec::ID] * pk - (1.0f - pk);   // compute_object_ids of a propagated slot
+  float* rn = rec_next + ((size_t)r * N + dst) * rec::W;
+  const size_t o = ((size_t)f * d.R + r) * N + dst;
+  for (int i = lane; i < rec::W; i += 64) {
+    float v = 0.0f;
+    if (i < 4) {
+      v = sq_prior_where_sample(cfg, rm, ps, nw, i, gn[i]);
+      if (out.where) out.where[o * 4 + i] = v;
+    } else if (i < rec::WHAT + nw) {
+      v = sq_prior_what_sample(cfg, rm, ps, nw, i - rec::WHAT, gn[i]);
+      if (out.what) out.what[o * nw + (i - rec::WHAT)] = v;
+    } else if (i == rec::PRES) {
+      v = pk;
+    } else if (i == rec::LOGIT) {
+      v = lgk;
+    } else if (i == rec::PROB) {
+      v = sq_sigmoid(lgk);
+    } else if (i == rec::ID) {
+      v = id;
     }
-    if (lane == 0) {
-      if (a.out.presence) a.out.presence[o] = pk;
-      if (a.out.presence_prob) a.out.presence_prob[o] = sq_sigmoid(lgk);
-      if (a.out.presence_logit) a.out.presence_logit[o] = lgk;
-      if (a.out.obj_id) a.out.obj_id[o] = id;
-    }
-    typedef float cf4 __attribute__((ext_vector_type(4)));
-    const cf4* src = reinterpret_cast<const cf4*>(a.prior_p + rk * d.psnh);
-    cf4* dstp = reinterpret_cast<cf4*>(a.prior_next + ((size_t)r * N + dst) * d.psnh);
-    for (int i = lane; i < d.psnh / 4; i += 64) dstp[i] = src[i];
+    rn[i] = v;
   }
+  if (lane == 0) {
+    if (out.presence) out.presence[o] = pk;
+    if (out.presence_prob) out.presence_prob[o] = sq_sigmoid(lgk);
+    if (out.presence_logit) out.presence_logit[o] = lgk;
+    if (out.obj_id) out.obj_id[o] = id;
+  }
+  typedef float cf4 __attribute__((ext_vector_type(4)));
+  const cf4* src = reinterpret_cast<const cf4*>(prior_p + rk * d.psnh);
+  cf4* dstp = reinterpret_cast<cf4*>(prior_next + ((size_t)r * N + dst) * d.psnh);
+  for (int i = lane; i < d.psnh / 4; i += 64) dstp[i] = src[i];
+  return dst;
+}
+__global__ __launch_bounds__(64) void k_forecast_step(const ForecastArgs a, const Dims d SQ_TLP) {
+  SQ_TL_SCOPE;
+  const PriorFrameOut o = {a.out.what, a.out.where, a.out.presence, a.out.presence_prob, a.out.presence_logit, a.out.obj_id};
+  (void)sq_prior_frame_slot(a.cfg, d, blockIdx.x, blockIdx.y, threadIdx.x, a.rec_prev, a.pstats, a.ps_ld, a.prior_p, a.noise, a.rec_next,
+                            a.prior_next, a.f, o);
 }
 int sq_launch_forecast_step(const ForecastArgs& a, Dims d, hipStream_t s) {
   SQ_LAUNCH(k_forecast_step, dim3(d.R, d.N), dim3(64), 0, s, a, d);
+  return 0;
+}
+// ------------------------------------------------------------------------------------------------
+// Missing-frame steps (sqair_set_observed; CoastArgs in sqair_glue.h).  k_coast_step, after the frame's k_compact: the rows of an
+// unobserved lane take the forecast's frame (sq_prior_frame_slot: records, ids, compaction, prior state), the temporal state of
+// slot k is HELD -- no glimpse, no update -- and moves with its slot, last_id stays, and the posterior's locs and scales k_compact
+// wrote for the frame become 0.  One wavefront per (row, slot); the lane's flag is uniform per workgroup.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_coast_step(const CoastArgs a, const Dims d SQ_TLP) {
+  SQ_TL_SCOPE;
+  const int r = blockIdx.x, k = blockIdx.y, lane = threadIdx.x, N = d.N, nw = d.nw;
+  if (a.observed[(size_t)a.t * d.B + sq_div(r, d.k_mul)] != 0) return;   // (the row's lane: r / K)
+  const PriorFrameOut po = {a.out.what, a.out.where, a.out.presence, a.out.presence_prob, a.out.presence_logit, a.out.obj_id};
+  const int dst = sq_prior_frame_slot(a.cfg, d, r, k, lane, a.rec_prev, a.pstats, a.ps_ld, a.prior_p, a.noise, a.rec_next, a.prior_next,
+                                      a.t, po);
+  typedef float cf4 __attribute__((ext_vector_type(4)));
+  const cf4* src = reinterpret_cast<const cf4*>(a.temporal_prev + ((size_t)r * N + k) * d.snh);
+  cf4* dstp = reinterpret_cast<cf4*>(a.temporal_next + ((size_t)r * N + dst) * d.snh);
+  for (int i = lane; i < d.snh / 4; i += 64) dstp[i] = src[i];
+  if (k == 0 && lane == 0) a.last_id_next[r] = a.last_id_prev[r];
+  const size_t o = ((size_t)a.t * d.R + r) * N + dst;
+  for (int c = lane; c < nw; c += 64) {
+    if (a.out.what_loc) a.out.what_loc[o * nw + c] = 0.0f;
+    if (a.out.what_scale) a.out.what_scale[o * nw + c] = 0.0f;
+  }
+  if (lane < 4) {
+    if (a.out.where_loc) a.out.where_loc[o * 4 + lane] = 0.0f;
+    if (a.out.where_scale) a.out.where_scale[o * 4 + lane] = 0.0f;
+  }
+}
+int sq_launch_coast_step(const CoastArgs& a, Dims d, hipStream_t s) {
+  SQ_LAUNCH(k_coast_step, dim3(d.R, d.N), dim3(64), 0, s, a, d);
+  return 0;
+}
+// k_coast_finish (CoastFinishArgs): workgroup (row, frame) of an unobserved lane zeroes what the log-probability and decoder launches
+// wrote for it -- the frame's log weight among them: a coasted frame changes no particle weight -- and writes the counts of the
+// coasted records.  Runs before the state export, the history push and the resampler.
+__global__ __launch_bounds__(64) void k_coast_finish(const CoastFinishArgs a, const Dims d SQ_TLP) {
+  SQ_TL_SCOPE;
+  const int r = blockIdx.x, t = blockIdx.y, lane = threadIdx.x, N = d.N;
+  if (a.observed[(size_t)t * d.B + sq_div(r, d.k_mul)] != 0) return;
+  const size_t tr = (size_t)t * d.R + r;
+  const SqairOutputs& o = a.out;
+  float p = 0.0f;
+  if (lane < N) {
+    p = a.rec[(tr * N + lane) * rec::W + rec::PRES];
+    const size_t e = tr * N + lane;
+    auto zero = [e](float* q) { if (q) q[e] = 0.0f; };
+    zero(o.disc_what_log_prob); zero(o.disc_where_log_prob); zero(o.disc_what_prior_log_prob); zero(o.disc_where_prior_log_prob);
+    zero(o.prop_what_log_prob); zero(o.prop_where_log_prob); zero(o.prop_what_prior_log_prob); zero(o.prop_where_prior_log_prob);
+    zero(o.prop_prob); zero(o.disc_pres);
+    if (o.prop_pres) o.prop_pres[e] = p;
+  }
+  if (lane <= N && o.disc_prob) o.disc_prob[tr * (N + 1) + lane] = 0.0f;
+  const float n = (float)__popcll(__ballot(lane < N && p != 0.0f));
+  if (lane == 0) {
+    auto zero = [tr](float* q) { if (q) q[tr] = 0.0f; };
+    zero(o.step_log_prob); zero(o.disc_log_prob); zero(o.disc_prior_log_prob); zero(o.prop_log_prob); zero(o.prop_prior_log_prob);
+    zero(o.discrete_log_prob); zero(o.data_ll_per_sample); zero(o.kl_per_sample); zero(o.log_q_z_given_x_per_sample);
+    zero(o.log_p_z_per_sample); zero(o.log_weights_per_timestep); zero(o.num_disc_steps_per_sample);
+    if (o.num_prop_steps_per_sample) o.num_prop_steps_per_sample[tr] = n;
+    if (o.num_steps_per_sample) o.num_steps_per_sample[tr] = n;
+  }
+}
+int sq_launch_coast_finish(const CoastFinishArgs& a, Dims d, hipStream_t s) {
+  SQ_LAUNCH(k_coast_finish, dim3(d.R, a.T), dim3(64), 0, s, a, d);
   return 0;
 }
 // Predictive summaries (ForecastSummaryArgs): workgroup (b, f).  Thread 0 turns the lane's log weights into w_k (max, exp, sum, divide,

@@ -91,6 +91,9 @@ struct SqairHandle {
   int64_t hist_bytes = 0;
   int hist_L = 0, hist_T = 0;        // hist_T: frames per pass of the ring's slots, 0 until the first pass pushes
   uint32_t hist_fields = 0;
+  // missing-frame steps (sqair_set_observed): the passes' kernels read this device mask [observed_T][state_B]
+  const int32_t* observed = nullptr;
+  int observed_T = 0;
   // generic capture slots (sqair_capture_begin / _end / _launch): any sequence of C-ABI calls as one HIP graph
   hipGraph_t cap_graph[4] = {nullptr, nullptr, nullptr, nullptr};
   hipGraphExec_t cap_exec[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -233,6 +236,7 @@ struct SqStateRes {
   bool fresh;
   bool smc_on; SqairSmc smc;
   bool hist_on = false;   // (the handle's inference passes only: a carried training call never pushes)
+  const int32_t* observed = nullptr;   // (the same: the handle's device mask of sqair_set_observed, or NULL)
 };
 SQ_LOCAL SqStateRes sq_handle_state(const SqairHandle* h);
 SQ_LOCAL SqStateRes sq_carry_state(const SqairCarry* c);
@@ -242,6 +246,8 @@ SQ_LOCAL StateArgs sq_state_args(const SqairHandle* h, const SqStateRes& st, int
 // track history: -1 + error text for a pass with history on that the ring rules out (host only; fixes the ring's T on the first
 // pass); the push's arguments for a pass of T frames
 SQ_LOCAL int sq_history_refusal(SqairHandle* h, int T, int B, const SqairOutputs* outp);
+// missing-frame steps: -1 + error text for a training call, or a pass of another T, while a mask is set (host only)
+SQ_LOCAL int sq_observed_refusal(SqairHandle* h, bool train, int T);
 SQ_LOCAL HistPushArgs sq_history_push_args(const SqairHandle* h, const SqStateRes& st, const SqairOutputs& out, const int* t_row, int T, int B);
 SQ_LOCAL SmcArgs sq_smc_args(const SqairSmc& m, const float* lw, const int32_t* t_row, int T, int B, int K);
 // section A of a frame of the pass, and a frame of the forecast: the propagation-prior cell and its statistics (sqair_api.hip)

@@ -1,5 +1,5 @@
 // libsqair_hip.so -- the carried model state on the native side of the C ABI (include/sqair_hip.h): the state blob and its
-// registration on a handle (sqair_set_state / sqair_set_smc / sqair_set_history), the refusals of the passes and carried training calls a state rules
+// registration on a handle (sqair_set_state / sqair_set_smc / sqair_set_history / sqair_set_observed), the refusals of the passes and carried training calls a state rules
 // out, the settings one pass resolves them to (SqStateRes: the handle's, or a SqairCarry's), and the forecast that rolls the prior
 // forward from a state (sqair_forecast).  Host code only; the pass that imports / exports / resamples the state is
 // sq_forward_impl (sqair_api.hip), the kernels live in sqair_glue.hip.
@@ -15,6 +15,7 @@ int64_t sq_state_row_floats(const SqairHandle* h) {
   const int64_t snh = c.time_cell == CELL_LSTM ? 2 * nh : nh, psnh = c.prior_cell == CELL_LSTM ? 2 * nh : nh;
   return (N * (rec::W + snh + psnh) + 2 + 3) / 4 * 4;
 }
+static void sq_observed_off(SqairHandle* h) { h->observed = nullptr; h->observed_T = 0; }
 static void sq_history_off(SqairHandle* h) {
   h->hist_on = false; h->hist_ring = nullptr; h->hist_bytes = 0; h->hist_L = 0; h->hist_T = 0; h->hist_fields = 0;
 }
@@ -28,6 +29,7 @@ extern "C" int sqair_set_state(SqairHandle* h, const void* state_in, void* state
     h->state_on = false; h->state_in = nullptr; h->state_out = nullptr; h->state_src = nullptr; h->state_B = 0;
     h->smc_on = false; h->smc = SqairSmc{};   // (SMC resamples the carried state: off with it)
     sq_history_off(h);                        // (the history records the carried rows: off with it)
+    sq_observed_off(h);                       // (the mask is per lane of the carried batch: off with it)
     return 0;
   }
   if (h->cfg.sample_from_prior) return sq_no(h, "sqair_set_state: not with sample_from_prior (generation decides per frame on the host)");
@@ -39,7 +41,34 @@ extern "C" int sqair_set_state(SqairHandle* h, const void* state_in, void* state
     h->smc_on = false; h->smc = SqairSmc{};
   }
   if (h->hist_on && B != h->state_B) sq_history_off(h);   // (the ring was sized for the other B)
+  if (B != h->state_B) sq_observed_off(h);                // (and so was the mask)
   h->state_on = true; h->state_in = state_in; h->state_out = state_out; h->state_src = src_rows; h->state_B = B;
+  return 0;
+}
+// Missing-frame steps (include/sqair_hip.h: sqair_set_observed): the device mask the passes' k_coast_step / k_coast_finish read.
+extern "C" int sqair_set_observed(SqairHandle* h, const int32_t* observed, int T, int B) {
+  if (!h) return -1;
+  if (!observed) {
+    sq_observed_off(h);
+    return 0;
+  }
+  if (h->cfg.sample_from_prior) return sq_no(h, "sqair_set_observed: not with sample_from_prior (generation decides per frame on the host)");
+  if (!h->state_on) return sq_no(h, "sqair_set_observed: needs a carried state (sqair_set_state): an unobserved lane coasts on the state it carries");
+  if (T < 1) return sq_no(h, "sqair_set_observed: T must be >= 1");
+  if (B != h->state_B)
+    return sq_no(h, "sqair_set_observed: B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
+  h->observed = observed; h->observed_T = T;
+  return 0;
+}
+// the refusals of a call while a mask is set (host only: before any HIP call)
+int sq_observed_refusal(SqairHandle* h, bool train, int T) {
+  if (!h->observed) return 0;
+  if (train)
+    return sq_no(h, "a mask of observed lanes is set (sqair_set_observed): training on gappy streams is out of scope, switch the mask off "
+                    "before a training call");
+  if (T != h->observed_T)
+    return sq_no(h, "observed (sqair_set_observed): the mask was registered for passes of T = " + std::to_string(h->observed_T) +
+                    " frames, a pass of T = " + std::to_string(T) + " cannot read it");
   return 0;
 }
 // The fields of an SqairSmc that each of its three users checks, -1 + "<who>..." when one is off: ess_frac (in [0, 1]; `train`:
@@ -131,7 +160,8 @@ int sq_state_refusal(SqairHandle* h, bool train, int B, int t_offset) {
 }
 
 SqStateRes sq_handle_state(const SqairHandle* h) {
-  return SqStateRes{h->state_on, h->state_in, h->state_out, h->state_src, false, h->smc_on, h->smc, h->state_on && h->hist_on};
+  return SqStateRes{h->state_on, h->state_in, h->state_out, h->state_src, false, h->smc_on, h->smc, h->state_on && h->hist_on,
+                    h->state_on ? h->observed : nullptr};
 }
 SqStateRes sq_carry_state(const SqairCarry* c) {
   return SqStateRes{true, c->state_in, c->state_out, c->src_rows, true, c->smc != nullptr, c->smc ? *c->smc : SqairSmc{}};

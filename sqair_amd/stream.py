@@ -33,6 +33,12 @@ resamples, row r of this step no longer continues row r of the last one, so the 
 maps -- the surviving particles' trajectories, the fixed-lag smoothing distribution of the filter -- and, because compaction moves
 objects between slots, a table keyed by object id.  No per-step copy to the host, no host-side genealogy.
 
+With ``missing=True`` a step takes ``observed`` [T', B]: lanes without a frame -- a dropped frame, a slower camera, a known occluder --
+coast on the prior inside the pass (include/sqair_hip.h: sqair_set_observed).  Their particles are proposed from the transition
+prior, as ``forecast`` would, their temporal states held, their weights left alone, and time advances; the mask lives on the device,
+so the one captured graph serves every pattern of present and missing lanes.  Feeding a blank frame instead would let the inference
+network "see" an empty scene and kill the objects.
+
 The stream takes over its core's handle: while it is open, every inference pass of that handle carries the state.  ``close()``
 hands the handle back.
 
@@ -58,7 +64,7 @@ FORECAST_NOISE_TAG = 1 << 63
 
 class SqairStream(object):
     def __init__(self, core, B, frames_per_step=1, outputs=DEFAULT_OUTPUTS, use_graph=True, seed=0, resample=None, ess_frac=0.5,
-                 state=None, history=None, history_fields=tuple(_capi.HISTORY_FIELDS)):
+                 state=None, history=None, history_fields=tuple(_capi.HISTORY_FIELDS), missing=False):
         if core.cfg.sample_from_prior:
             raise ValueError("SqairStream: generation modes (sample_from_prior) do not carry a state across calls")
         if resample not in (None, "systematic"):
@@ -97,6 +103,13 @@ class SqairStream(object):
                                             cs.state.numel() * 4, self.B), "sqair_set_state")
         if self.smc:
             self._set_smc(False)
+        self.missing = bool(missing)
+        if self.missing:   # the device mask [T', B] the pass's kernels read: all observed until a step says otherwise
+            self._observed = torch.ones((self.T, self.B), dtype=torch.int32, device=core.device)
+            self._every_lane = torch.ones((self.T, self.B), dtype=torch.bool, device=core.device)   # what step() returns without a mask
+            self._observed_is_ones = True
+            torch.cuda.current_stream(core.device).synchronize()
+            core.check(core.lib.sqair_set_observed(core.handle, self._observed.data_ptr(), self.T, self.B), "sqair_set_observed")
         if history is not None:
             ring, nb, bits = cs.set_history(history, history_fields, self.T)
             torch.cuda.current_stream(core.device).synchronize()   # (the ring's zeros are in place before a pass pushes into it)
@@ -131,14 +144,42 @@ class SqairStream(object):
         self.carried.resample(src_rows)
 
     # ---- stepping ---------------------------------------------------------------------------------------------------------
-    def step(self, frames, noise=None, seed=None, uniforms=None):
+    def _check_observed(self, observed):
+        """``observed`` of a step as a bool tensor [T', B] (None: every lane has its frame)."""
+        if observed is None:
+            return None
+        if not self.missing:
+            raise ValueError("SqairStream.step: observed is for a stream with missing=True")
+        m = torch.as_tensor(observed)
+        if m.dtype != torch.bool:
+            raise ValueError("SqairStream.step: observed must be a bool array, dtype {} given".format(m.dtype))
+        if self.T == 1 and tuple(m.shape) == (self.B,):
+            m = m.reshape(1, self.B)
+        if tuple(m.shape) != (self.T, self.B):
+            raise ValueError("SqairStream.step: observed of shape {} given, [{}, {}] expected{}".format(
+                tuple(m.shape), self.T, self.B, " (or [{}])".format(self.B) if self.T == 1 else ""))
+        return m
+
+    @staticmethod
+    def _blank_unobserved(frames, observed):
+        """The frames of unobserved lanes as zeros: the pass still computes on them (include/sqair_hip.h: they must be finite)."""
+        return torch.where(observed.to(frames.device)[:, :, None, None], frames, 0.0)
+
+    def step(self, frames, noise=None, seed=None, uniforms=None, observed=None):
         """Consumes frames [T', B, H, W] (T' = frames_per_step); returns this step's per-frame outputs {name: [T', B*K, ...]}
         (copies, valid on the current stream).  ``noise`` [T', B*K, 2, N, 4 + n_what + 1]; default: the library's generator
         keyed by (``seed`` or the stream's seed, frame index).  With SMC on, also ``ess``, ``resampled``, ``log_evidence`` [B]
         and ``ancestors`` [B*K] (the next step's source map), device copies taken before anything is read on the host;
-        ``uniforms`` [B] in [0, 1): this step's systematic-resampling uniforms (default: Philox)."""
+        ``uniforms`` [B] in [0, 1): this step's systematic-resampling uniforms (default: Philox).  ``observed`` (streams with
+        ``missing=True``): bool [T', B], or [B] when T' = 1, False = the lane has no frame and coasts on the prior; its frame is
+        replaced by zeros, so it may hold anything, NaN included.  Default: every lane observed.  Returned among the outputs."""
+        observed = self._check_observed(observed)   # (before the core is touched)
         core, cs = self.core, self.carried
         frames, noise, uniforms = cs.check_inputs(self.T, frames, noise, uniforms, "stream")
+        if observed is not None:
+            if frames.is_cuda:   # (one upload at most: the blanking, the registered mask and the returned one share it)
+                observed = observed.to(frames.device)
+            frames = self._blank_unobserved(frames, observed)
         if self.smc:
             self._set_smc(uniforms is not None)
         lib = core.lib
@@ -146,6 +187,13 @@ class SqairStream(object):
             core._join_in()
             with core.on_stream():
                 cs.feed(frames, noise, uniforms, self.seed if seed is None else int(seed), self.frame)
+                if self.missing:   # (a mask that lives on the device, like the frames of a resident clip, costs no upload)
+                    if observed is not None:
+                        observed = observed.to(core.device, non_blocking=True)
+                        self._observed.copy_(observed)
+                    elif not self._observed_is_ones:
+                        self._observed.fill_(1)
+                    self._observed_is_ones = observed is None
                 if self.use_graph:
                     if not self._graph:
                         core.stream.synchronize()
@@ -155,6 +203,8 @@ class SqairStream(object):
                 else:
                     core.check(lib.sqair_forward(*core._args(0)), "sqair_forward")
                 out = {k: core.out[k].clone() for k in self.outputs}
+                if self.missing:
+                    out["observed"] = self._every_lane if observed is None else observed
                 if self.smc:   # (log_weight_sum is the resampler's accumulator)
                     out.update(ess=cs.ess.clone(), resampled=cs.resampled.clone(), log_evidence=cs.log_evidence.clone(),
                                ancestors=cs._src.clone())

@@ -18,6 +18,13 @@ machine, the same minutes.  The yardstick is the same run's SMC on - SMC off dif
 node; the push is one node too.  Also the time of tracks() at lag 10 and lag 64, and the ring's bytes:
 
     python tools/stream_time.py --history [--out profiles/stream_history_time.json]
+
+With --missing: the price of missing-frame steps (SqairStream(missing=True), include/sqair_hip.h: sqair_set_observed).  Streams at
+cfg-2's batch alternating in one process as with --history: plain, ``missing=True`` with every lane observed, ``missing=True`` with
+no lane observed -- and SMC on, for the yardstick: the same run's SMC on - SMC off difference is the price of one dependent node
+that day, and a one-frame pass with a mask has two nodes more.  The ratio is recorded, not gated on:
+
+    python tools/stream_time.py --missing [--out profiles/stream_missing_time.json]
 """
 import argparse
 import json
@@ -74,13 +81,15 @@ def time_stream(B, K, N, steps, warmup, hw=(50, 50), resample=None, ess_frac=0.5
                 ms_per_frame_p90=float(np.percentile(ms, 90)), ms_per_frame_back_to_back=float(a.elapsed_time(b) / steps))
 
 
-def time_history(B, K, N, steps, warmup, L=64, rounds=10, hw=(50, 50)):
+def alternating_streams(legs, B, K, N, steps, warmup, rounds, hw, step_kw=None):
+    """One stream per leg (name -> SqairStream keywords) in ONE process, timed in alternating blocks so that all of them see the
+    same machine, the same minutes.  step_kw: name -> keywords of every step() of that leg.  Returns (streams, the result's
+    common fields, median latency per leg, median back-to-back time per leg), times in ms per frame."""
     F = make_flags(k_particles=K, n_steps_per_image=N)
     obs = torch.as_tensor(to_float(make_sequences(B, T=50, canvas=hw, seed=7)["imgs"])).cuda()
     P = {k: np.asarray(v, dtype=np.float32) for k, v in
          init_params(F, hw, seed=0, mean_img=obs.mean((0, 1)).cpu().numpy(), jitter=0.02).items()}
-    smc = dict(resample="systematic", ess_frac=0.5)
-    legs = dict(plain={}, smc=smc, history=dict(history=L), smc_history=dict(history=L, **smc))
+    step_kw = step_kw or {}
     streams = {}
     for name, kw in legs.items():
         core = SqairCore(F, hw)
@@ -96,15 +105,16 @@ def time_history(B, K, N, steps, warmup, L=64, rounds=10, hw=(50, 50)):
             with core.on_stream():
                 n = warmup if rnd < 0 else block
                 ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+                kw = step_kw.get(name, {})
                 for i in range(n):
                     ev[i][0].record()
-                    st.step(obs[(t + i) % 50:(t + i) % 50 + 1])
+                    st.step(obs[(t + i) % 50:(t + i) % 50 + 1], **kw)
                     ev[i][1].record()
                     core.stream.synchronize()
                 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 a.record()
                 for i in range(n):
-                    st.step(obs[(t + i) % 50:(t + i) % 50 + 1])
+                    st.step(obs[(t + i) % 50:(t + i) % 50 + 1], **kw)
                 b.record()
                 torch.cuda.synchronize()
             if rnd >= 0:
@@ -113,11 +123,18 @@ def time_history(B, K, N, steps, warmup, L=64, rounds=10, hw=(50, 50)):
         t += block
     med = {n: float(np.median(lat[n])) for n in legs}
     thr = {n: float(np.median(b2b[n])) for n in legs}
-    res = dict(B=B, K=K, N=N, hw=list(hw), L=L, steps=block * rounds, rounds=rounds, warmup=warmup,
+    res = dict(B=B, K=K, N=N, hw=list(hw), steps=block * rounds, rounds=rounds, warmup=warmup,
                graph_nodes={n: st.core.graph_nodes() for n, st in streams.items()},
-               ring_bytes=int(streams["history"].carried.ring.numel() * 4), history_fields=list(streams["history"].history_fields),
                ms_per_frame_median=med, ms_per_frame_p10={n: float(np.percentile(lat[n], 10)) for n in legs},
                ms_per_frame_p90={n: float(np.percentile(lat[n], 90)) for n in legs}, ms_per_frame_back_to_back=thr)
+    return streams, res, med, thr
+
+
+def time_history(B, K, N, steps, warmup, L=64, rounds=10, hw=(50, 50)):
+    smc = dict(resample="systematic", ess_frac=0.5)
+    legs = dict(plain={}, smc=smc, history=dict(history=L), smc_history=dict(history=L, **smc))
+    streams, res, med, thr = alternating_streams(legs, B, K, N, steps, warmup, rounds, hw)
+    res.update(L=L, ring_bytes=int(streams["history"].carried.ring.numel() * 4), history_fields=list(streams["history"].history_fields))
     for key, v in (("latency", med), ("back_to_back", thr)):
         one_node = v["smc"] - v["plain"]            # the yardstick: one dependent node (the resampler) on this machine, this run
         push = [v["history"] - v["plain"], v["smc_history"] - v["smc"]]
@@ -146,6 +163,23 @@ def time_history(B, K, N, steps, warmup, L=64, rounds=10, hw=(50, 50)):
     return res
 
 
+def time_missing(B, K, N, steps, warmup, rounds=10, hw=(50, 50)):
+    legs = dict(plain={}, smc=dict(resample="systematic", ess_frac=0.5), missing_all_observed=dict(missing=True),
+                missing_none_observed=dict(missing=True))
+    # (the masks are resident on the device beforehand, as the frames are)
+    step_kw = dict(missing_all_observed=dict(observed=torch.ones(B, dtype=torch.bool).cuda()),
+                   missing_none_observed=dict(observed=torch.zeros(B, dtype=torch.bool).cuda()))
+    streams, res, med, thr = alternating_streams(legs, B, K, N, steps, warmup, rounds, hw, step_kw)
+    for key, v in (("latency", med), ("back_to_back", thr)):
+        one_node = v["smc"] - v["plain"]            # the yardstick: one dependent node (the resampler) on this machine, this run
+        added = {n: v[n] - v["plain"] for n in ("missing_all_observed", "missing_none_observed")}
+        res["us_" + key] = dict(smc_node=1e3 * one_node, **{n: 1e3 * a for n, a in added.items()},
+                                **{n + "_over_smc_node": (a / one_node if one_node > 0 else None) for n, a in added.items()})
+    for st in streams.values():
+        st.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=500)
@@ -153,10 +187,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--smc", action="store_true", help="SMC resampling off / ess_frac 0.5 / 1.0 (profiles/stream_time_smc.json)")
     ap.add_argument("--history", action="store_true", help="plain / SMC / history / SMC + history, alternating (profiles/stream_history_time.json)")
+    ap.add_argument("--missing", action="store_true", help="plain / SMC / a mask with every lane / with no lane observed, alternating (profiles/stream_missing_time.json)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     ov, _, _, _ = config_inputs(2)
-    if args.history:
+    if args.missing:
+        shapes = [dict(name="cfg2_batch_missing", **time_missing(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
+    elif args.history:
         shapes = [dict(name="cfg2_batch_history", **time_history(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
     elif args.smc:
         shapes = []
