@@ -384,7 +384,9 @@ int sqair_forecast(SqairHandle* h, const float* flat_params, const void* packed,
  * The pointer is remembered by the handle and frozen into captured graphs, as the state's pointers are.  NULL observed: off.
  * Refused (return -1, text in sqair_last_error, before any HIP call): no state set, T < 1, a B other than the state's, a
  * configuration with sample_from_prior; at pass time: a pass whose T is not the T given here, and every training call
- * (sqair_forward_train, sqair_forward_train_carry) while a mask is set -- training on gappy streams is out of scope.
+ * (sqair_forward_train, sqair_forward_train_carry) while a mask is set -- training on gappy streams is out of scope for THIS mask,
+ * which belongs to the handle's inference state: a carried training chunk takes its mask per call, sqair_forward_train_carry_masked /
+ * sqair_backward_carry_masked below ("training on gappy and ragged streams").
  * sqair_set_state switching the state off, or to another B, switches the mask off. */
 int sqair_set_observed(SqairHandle* h, const int32_t* observed /* device [T,B]; NULL: off */, int T, int B);
 
@@ -527,6 +529,51 @@ int sqair_backward_carry(SqairHandle* h, const float* flat_params, const void* p
                          const float* importance_weights, const float* vimco_signal, int T, int B, const SqairCarry* carry,
                          void* train_workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes,
                          float* flat_grad, void* stream);
+
+/* ---- training on gappy and ragged streams: a per-frame observed mask in a carried chunk ---------------------------------------
+ * A masked carried chunk is a carried chunk (SqairCarry, unchanged) plus a device mask observed[T', B] (int32, nonzero = the lane
+ * has a frame), read ON THE DEVICE by both calls: one captured graph serves every mask.  A dropped frame, a lane at a lower frame
+ * rate, and -- as a trailing run of zeros -- a lane whose clip ends inside the chunk (a ragged batch) are the same mechanism.
+ *   Forward.  An observed (frame, lane) is untouched, bit for bit.  An unobserved one coasts exactly as sqair_set_observed defines
+ *     for inference, by the same kernels: records / ids / prior state from the transition prior's draws, the temporal state held
+ *     and permuted, the frame counter advanced, log_weights_per_timestep = 0, every other bound output as the inference pass writes
+ *     it -- except discrete_log_prob.
+ *   discrete_log_prob of a coasted (frame t, row r).  The presences of a coasted frame are DRAWN FROM p_theta, so an unbiased
+ *     gradient of the chunk's bound needs their score term: the value is the sum over the N slots of
+ *         pres log sigmoid(l) + (1 - pres) log sigmoid(-l),
+ *     l the coasted logit (record t's presence_logit), pres the drawn presence; fp64, slots in index order.  Slots absent at t - 1
+ *     of the "rnn" prior contribute 0 to rounding (l = -88).  It is written only if the lane has an observed frame LATER IN THE SAME
+ *     CHUNK, else 0: a trailing run of unobserved frames influences no log weight of the chunk, its score term would be pure variance.
+ *   Target.  sqair_elbo on [T', B*K] unchanged, / T' (not / the number of observed frames): VIMCO over the chunk's log weights --
+ *     zero in coasted frames -- and the discrete log-probs above.
+ *   Gradient.  d target / d theta with the imported state constant, as sqair_backward_carry.  A coasted frame t of row r contributes
+ *     - the reparameterised draws: d what, d where of record t + 1 flow into the prior statistics of frame t (loc directly, raw scale
+ *       through eps softplus'), and with prop_prior_type rw / guided into record t (the 0.1 factors of the prior's draws); d logit /
+ *       d prob of the record into the logit;
+ *     - the score term: g_discrete_log_prob[t, r] (presence - sigmoid(l)) into the logit of each slot;
+ *     - d prior state of t + 1, through the inverse of the frame's present-first permutation, into the adjoint of the prior cell's
+ *       new state; d temporal state of t + 1 through the same inverse permutation into d temporal state of t (it was held);
+ *     - NOTHING from the posterior: its log-probabilities, its likelihood and its compaction are not part of a coasted frame, and
+ *       the adjoints of the inference network for that (frame, row) are exactly zero.
+ *   Consequences.  A chunk in which no lane is observed has target 0 and a gradient whose every entry is 0.  For one lane, a chunk
+ *     of T' frames observed only in its first s frames has s / T' times the gradient of the s-frame chunk on the same frames and noise.
+ *     SMC at chunk boundaries (ess_frac == 1) composes unchanged: the resampler reads zero log weights for coasted frames.
+ * The frames of unobserved lanes must be FINITE (the posterior still runs on every row) and influence nothing.
+ * Launches: the forward has T' + 1 kernel nodes more than sqair_forward_train_carry (k_coast_step per frame, k_coast_finish), the
+ * backward T' + 1 more than sqair_backward_carry (one masking launch after the objective's adjoint, k_coast_step_bwd per frame).
+ * NULL observed: the two calls ARE sqair_forward_train_carry / sqair_backward_carry, nothing more is launched.
+ * The backward must be given the mask the forward ran with, unchanged in between.
+ * Refused (return -1, text in sqair_last_error, before any HIP call): everything sqair_forward_train_carry / sqair_backward_carry
+ * refuse (sample_from_prior among it), and a handle with a sqair_set_observed mask set.  Out of scope: a mask for the plain
+ * sqair_forward_train, adaptive-ESS training, a history for training, a lane-sparse pass. */
+int sqair_forward_train_carry_masked(SqairHandle* h, const float* flat_params, const void* packed, const float* obs,
+                                     const float* noise, int T, int B, const SqairCarry* carry,
+                                     const int32_t* observed /* device [T,B]; NULL: no mask */, const SqairOutputs* out,
+                                     void* train_workspace, int64_t workspace_bytes, void* stream);
+int sqair_backward_carry_masked(SqairHandle* h, const float* flat_params, const void* packed, const float* obs, const float* noise,
+                                const float* importance_weights, const float* vimco_signal, int T, int B, const SqairCarry* carry,
+                                const int32_t* observed /* device [T,B]; NULL: no mask */, void* train_workspace,
+                                int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, float* flat_grad, void* stream);
 
 /* ---- workspace clearing.  By default every pass starts by zero-filling the caller's workspace (60 MB for inference,
  * 308 MB for the training tape at BASELINE configs[1]: ~1-2 % of a step), so that a workspace may hold garbage and may be

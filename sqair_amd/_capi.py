@@ -142,6 +142,10 @@ _PROTOS = {
                                                                 C.c_void_p, C.c_int64, C.c_void_p]),
     "sqair_backward_carry": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.POINTER(SqairCarry), C.c_void_p, C.c_int64,
                                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "sqair_forward_train_carry_masked": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.POINTER(SqairCarry), C.c_void_p,
+                                                                       C.POINTER(SqairOutputs), C.c_void_p, C.c_int64, C.c_void_p]),
+    "sqair_backward_carry_masked": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.POINTER(SqairCarry), C.c_void_p, C.c_void_p,
+                                                                 C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "sqair_set_generation_noise": (C.c_int, [C.c_void_p, C.c_void_p]),
     "sqair_state_bytes": (C.c_int64, [C.c_void_p, C.c_int]),
     "sqair_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),

@@ -16,6 +16,31 @@ def carried(name):
     return property(lambda self: getattr(self.carried, name))
 
 
+def check_observed(observed, missing, T, B, who, kind):
+    """``observed`` of a step of ``who`` (a ``kind``: "stream" / "trainer") as a bool tensor [T', B] (None: every lane has its
+    frame); [B] is taken when T' = 1."""
+    import torch
+    if observed is None:
+        return None
+    if not missing:
+        raise ValueError("{}.step: observed is for a {} with missing=True".format(who, kind))
+    m = torch.as_tensor(observed)
+    if m.dtype != torch.bool:
+        raise ValueError("{}.step: observed must be a bool array, dtype {} given".format(who, m.dtype))
+    if T == 1 and tuple(m.shape) == (B,):
+        m = m.reshape(1, B)
+    if tuple(m.shape) != (T, B):
+        raise ValueError("{}.step: observed of shape {} given, [{}, {}] expected{}".format(
+            who, tuple(m.shape), T, B, " (or [{}])".format(B) if T == 1 else ""))
+    return m
+
+
+def blank_unobserved(frames, observed):
+    """The frames of unobserved lanes as zeros: the pass still computes on them (include/sqair_hip.h: they must be finite)."""
+    import torch
+    return torch.where(observed.to(frames.device)[:, :, None, None], frames, 0.0)
+
+
 class SourceMap(object):
     """The pending source map of R = B * K particle rows (K per lane).  ``who``: the class the error texts name."""
 

@@ -1378,6 +1378,7 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
   if (st.observed) {
     CoastFinishArgs fa; memset(&fa, 0, sizeof(fa));
     fa.observed = st.observed; fa.rec = w.rec_m_all + (size_t)M * RW; fa.T = T; fa.out = out;
+    fa.train = train ? 1 : 0;   // (only a masked carried chunk trains with a mask: its coasted rows keep their score term)
     sq_launch_coast_finish(fa, d, s);
   }
   // final recurrent state (for state-level parity checks), in the caller's widths: [hidden | cell] halves without their padding
@@ -1442,6 +1443,24 @@ extern "C" int sqair_forward_train_carry(SqairHandle* h, const float* flat_param
     return -1;
   }
   const SqStateRes st = sq_carry_state(carry);
+  return sq_forward_impl(h, flat_params, (const float*)packed, obs, noise, T, B, 0, out, (float*)train_workspace, workspace_bytes,
+                         (hipStream_t)stream, true, 7, &st);
+}
+
+// Training forward of a masked carried chunk (include/sqair_hip.h: "training on gappy and ragged streams"): the carried chunk with
+// the mask of THIS call in the pass's settings -- never the handle's -- so k_coast_step / k_coast_finish run as in an inference pass
+// with sqair_set_observed, the latter in its training instantiation.  NULL observed: sqair_forward_train_carry.
+extern "C" int sqair_forward_train_carry_masked(SqairHandle* h, const float* flat_params, const void* packed, const float* obs,
+                                                const float* noise, int T, int B, const SqairCarry* carry, const int32_t* observed,
+                                                const SqairOutputs* out, void* train_workspace, int64_t workspace_bytes, void* stream) {
+  if (!h) return -1;
+  if (sq_observed_refusal(h, true, T) != 0 || sq_carry_refusal(h, "sqair_forward_train_carry_masked", B, carry, out) != 0) return -1;
+  if (!out) {
+    sq_set_error(h, "sqair_forward_train_carry_masked: null argument");
+    return -1;
+  }
+  SqStateRes st = sq_carry_state(carry);
+  st.observed = observed;
   return sq_forward_impl(h, flat_params, (const float*)packed, obs, noise, T, B, 0, out, (float*)train_workspace, workspace_bytes,
                          (hipStream_t)stream, true, 7, &st);
 }

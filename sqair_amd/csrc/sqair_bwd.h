@@ -23,6 +23,8 @@ struct CompactBwdArgs {
   float* d_temporal_p; float* d_prior_p;                     // [M][nh] (written: every propagation slot)
   float* d_new_temporal; float* d_new_prior;                 // [R][snh], [R][psnh]: per row, the gradient reaching the trainable
                                                              // initial states through this frame's newly discovered objects
+  const int* observed_t;          // a masked carried chunk: this frame's mask [B], or NULL.  The rows of an unobserved lane took the
+                                  // prior's frame (k_coast_step): nothing is routed for them, what is written is written as zeros
 };
 
 struct TailBwdArgs {

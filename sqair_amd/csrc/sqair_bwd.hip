@@ -1725,7 +1725,10 @@ __global__ __launch_bounds__(256) void k_compact_bwd(const CompactBwdArgs a, con
   __shared__ int inv_s[2 * SQ_MAXN];  // source slot -> destination (or -1)
   if (tid < 2 * N) inv_s[tid] = -1;
   __syncthreads();
-  if (tid < N) inv_s[a.src[(size_t)r * N + tid]] = tid;
+  // (a coasted row of a masked carried chunk: no source slot has a destination -- its merged slots came from the prior, whose
+  //  adjoint is k_coast_step_bwd's -- so the three jobs below add nothing and write zeros)
+  const bool coasted = a.observed_t != nullptr && a.observed_t[sq_div(r, d.k_mul)] == 0;
+  if (tid < N && !coasted) inv_s[a.src[(size_t)r * N + tid]] = tid;
   __syncthreads();
   typedef float cf4 __attribute__((ext_vector_type(4)));   // all gradient rows are 16-byte aligned: 16-byte units throughout
   const cf4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};

@@ -347,9 +347,34 @@ struct CoastFinishArgs {
   const int* observed;                 // [T][B]
   const float* rec;                    // merged records of frames 0..T-1 [T][R][N][rec::W]
   int T;
+  int train;                           // a masked carried training chunk: discrete_log_prob of a coasted row is its score term
   SqairOutputs out;
 };
 int sq_launch_coast_finish(const CoastFinishArgs& a, Dims d, hipStream_t s);
+// The adjoint of the coasted frames of a masked carried chunk (sqair_glue.hip: k_coast_mask_grads, k_coast_step_bwd).
+struct CoastMaskArgs {
+  const int* observed;                 // [T][B]
+  int T;
+  float* g_lw; float* g_dl;            // [T][R] the objective's adjoint: zeroed for coasted (frame, row)s
+  float* g_sc;                         // [T][R] out: the score term's coefficient of coasted (frame, row)s
+};
+int sq_launch_coast_mask_grads(const CoastMaskArgs& a, Dims d, hipStream_t s);
+struct CoastBwdArgs {
+  const int* observed;                 // [T][B]
+  int t;
+  const float* rec_prev;               // records of frame t - 1 [R][N][rec::W]
+  const float* pstats; int ps_ld;      // section A's prior statistics of this frame
+  const float* noise;                  // noise of frame t
+  const float* g_sc;                   // [R] this frame's score coefficients
+  const float* d_rec_next;             // gradient records of frame t [R][N][rec::W] (read at the slot's destination)
+  const float* d_prior_next; const float* d_temporal_next;   // d prior_m / d temporal_m of frame t + 1
+  float* d_rec_prev;                   // += gradient records of frame t - 1
+  float* d_pstats;                     // += [R][N][ps_ld]
+  float* d_prior_p;                    // =  [R][N][psnh]
+  float* d_temporal_prev;              // += d temporal_m of frame t
+  SqairConfig cfg;
+};
+int sq_launch_coast_step_bwd(const CoastBwdArgs& a, Dims d, hipStream_t s);
 // Predictive summaries of a forecast: one workgroup per (frame, lane b); w = softmax of the lane's K log weights (NULL: uniform),
 // mean_canvas[f][b] = sum_k w_k canvas[f][b*K + k], expected_count[f][b] = sum_k w_k (present slots of particle k).  Every sum over k
 // runs in index order.

@@ -1418,11 +1418,13 @@ int sq_launch_generate_disc(const GenArgs& a, POff po, Dims d, hipStream_t s) {
 // (k_coast_step) so that both execute the same instructions on the same inputs.  `o_*`: the six per-slot outputs, each optional;
 // f: the frame's index inside them.  Returns slot k's destination.
 struct PriorFrameOut { float *what, *where, *presence, *presence_prob, *presence_logit, *obj_id; };
-__device__ __forceinline__ int sq_prior_frame_slot(const SqairConfig& cfg, const Dims& d, int r, int k, int lane, const float* rec_prev,
-                                                   const float* pstats, int ps_ld, const float* prior_p, const float* noise,
-                                                   float* rec_next, float* prior_next, int f, const PriorFrameOut& out) {
+// The presence draws of a row's frame and the present-first permutation they give: lane j < N returns slot j's destination and
+// leaves its prior logit and drawn presence in lg / pres.  Shared with the adjoint of a coasted frame (k_coast_step_bwd), which
+// recomputes the permutation from the same inputs instead of keeping it on the tape.
+__device__ __forceinline__ int sq_prior_frame_draw(const SqairConfig& cfg, const Dims& d, int r, int lane, const float* rec_prev,
+                                                   const float* pstats, int ps_ld, const float* noise, float& lg, float& pres) {
   const int N = d.N, nw = d.nw;
-  float lg = 0.0f, pres = 0.0f;
+  lg = 0.0f; pres = 0.0f;
   if (lane < N) {
     const size_t rk = (size_t)r * N + lane;
     lg = sq_prior_logit(cfg, rec_prev + rk * rec::W, pstats + rk * ps_ld);
@@ -1431,7 +1433,14 @@ __device__ __forceinline__ int sq_prior_frame_slot(const SqairConfig& cfg, const
   const unsigned long long all = (1ull << N) - 1ull;   // (N <= 16)
   const unsigned long long present = __ballot(lane < N && pres != 0.0f) & all;
   const unsigned long long below = (1ull << lane) - 1ull;
-  const int dst_l = (pres != 0.0f) ? __popcll(present & below) : __popcll(present) + __popcll(~present & all & below);
+  return (pres != 0.0f) ? __popcll(present & below) : __popcll(present) + __popcll(~present & all & below);
+}
+__device__ __forceinline__ int sq_prior_frame_slot(const SqairConfig& cfg, const Dims& d, int r, int k, int lane, const float* rec_prev,
+                                                   const float* pstats, int ps_ld, const float* prior_p, const float* noise,
+                                                   float* rec_next, float* prior_next, int f, const PriorFrameOut& out) {
+  const int N = d.N, nw = d.nw;
+  float lg, pres;
+  const int dst_l = sq_prior_frame_draw(cfg, d, r, lane, rec_prev, pstats, ps_ld, noise, lg, pres);
   const size_t rk = (size_t)r * N + k;
   const float* rm = rec_prev + rk * rec::W;
   const float* ps = pstats + rk * ps_ld;
@@ -1517,6 +1526,17 @@ int sq_launch_coast_step(const CoastArgs& a, Dims d, hipStream_t s) {
 // k_coast_finish (CoastFinishArgs): workgroup (row, frame) of an unobserved lane zeroes what the log-probability and decoder launches
 // wrote for it -- the frame's log weight among them: a coasted frame changes no particle weight -- and writes the counts of the
 // coasted records.  Runs before the state export, the history push and the resampler.
+// Whether lane b has an observed frame after frame t of the T frames of the mask.
+__device__ __forceinline__ bool sq_later_observed(const int* observed, int t, int T, int B, int b) {
+  bool later = false;
+  for (int u = t + 1; u < T; ++u) later = later || observed[(size_t)u * B + b] != 0;
+  return later;
+}
+// TRAIN (a masked carried chunk, sqair_forward_train_carry_masked): discrete_log_prob of the coasted (frame, row) is the score term
+// of its presences, which were drawn from p_theta -- sum over the N slots of the Bernoulli log-probability of the drawn presence
+// under the coasted logit, in fp64, slots in index order -- when the lane has an observed frame later in the chunk, else 0: a
+// trailing run of unobserved frames reaches no log weight of the chunk.  The inference instantiation is the kernel as it was.
+template <bool TRAIN>
 __global__ __launch_bounds__(64) void k_coast_finish(const CoastFinishArgs a, const Dims d SQ_TLP) {
   SQ_TL_SCOPE;
   const int r = blockIdx.x, t = blockIdx.y, lane = threadIdx.x, N = d.N;
@@ -1538,14 +1558,101 @@ __global__ __launch_bounds__(64) void k_coast_finish(const CoastFinishArgs a, co
   if (lane == 0) {
     auto zero = [tr](float* q) { if (q) q[tr] = 0.0f; };
     zero(o.step_log_prob); zero(o.disc_log_prob); zero(o.disc_prior_log_prob); zero(o.prop_log_prob); zero(o.prop_prior_log_prob);
-    zero(o.discrete_log_prob); zero(o.data_ll_per_sample); zero(o.kl_per_sample); zero(o.log_q_z_given_x_per_sample);
+    if (!TRAIN) zero(o.discrete_log_prob);
+    zero(o.data_ll_per_sample); zero(o.kl_per_sample); zero(o.log_q_z_given_x_per_sample);
     zero(o.log_p_z_per_sample); zero(o.log_weights_per_timestep); zero(o.num_disc_steps_per_sample);
     if (o.num_prop_steps_per_sample) o.num_prop_steps_per_sample[tr] = n;
     if (o.num_steps_per_sample) o.num_steps_per_sample[tr] = n;
   }
+  if (TRAIN) {
+    double term = 0.0;
+    if (lane < N) {
+      const double l = (double)a.rec[(tr * N + lane) * rec::W + rec::LOGIT];
+      term = -(fmax(l, 0.0) - l * (double)p + log1p(exp(-fabs(l))));
+    }
+    double sum = 0.0;
+    for (int j = 0; j < N; ++j) sum += __shfl(term, j);
+    if (lane == 0 && o.discrete_log_prob)
+      o.discrete_log_prob[tr] = sq_later_observed(a.observed, t, a.T, d.B, sq_div(r, d.k_mul)) ? (float)sum : 0.0f;
+  }
 }
 int sq_launch_coast_finish(const CoastFinishArgs& a, Dims d, hipStream_t s) {
-  SQ_LAUNCH(k_coast_finish, dim3(d.R, a.T), dim3(64), 0, s, a, d);
+  if (a.train) SQ_LAUNCH(k_coast_finish<true>, dim3(d.R, a.T), dim3(64), 0, s, a, d);
+  else SQ_LAUNCH(k_coast_finish<false>, dim3(d.R, a.T), dim3(64), 0, s, a, d);
+  return 0;
+}
+// ------------------------------------------------------------------------------------------------
+// The adjoint of a masked carried chunk's coasted frames (include/sqair_hip.h: sqair_backward_carry_masked).
+// k_coast_mask_grads, once after the objective's adjoint: for a coasted (frame, row) the log weight is not in the target -- g_lw
+// becomes 0, and with it everything the log-probability and decoder adjoints (linear in g_lw and g_dl) send into the posterior --
+// and g_dl, the coefficient of the score term, moves aside into g_sc (times the "observed later" flag the forward applied).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_coast_mask_grads(const CoastMaskArgs a, const Dims d SQ_TLP) {
+  SQ_TL_SCOPE;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.T * d.R) return;
+  const int t = i / d.R, r = i - t * d.R, b = sq_div(r, d.k_mul);
+  if (a.observed[(size_t)t * d.B + b] != 0) return;   // (g_sc of observed rows: the zeros of the cleared scratch, never read)
+  a.g_sc[i] = sq_later_observed(a.observed, t, a.T, d.B, b) ? a.g_dl[i] : 0.0f;
+  a.g_lw[i] = 0.0f;
+  a.g_dl[i] = 0.0f;
+}
+int sq_launch_coast_mask_grads(const CoastMaskArgs& a, Dims d, hipStream_t s) {
+  SQ_LAUNCH(k_coast_mask_grads, dim3((a.T * d.R + 255) / 256), dim3(256), 0, s, a, d);
+  return 0;
+}
+// k_coast_step_bwd, frame t of the reverse sweep, between B^T and A^T: one wavefront per (row, slot k) as the forward, the mask word
+// uniform per workgroup, workgroups of observed lanes return at once.  Slot k went to `dst` of frame t + 1 (the forward's draw,
+// recomputed); this wavefront is the only writer of row (r, k) of each buffer in this launch, so += needs no atomic, and every
+// sum has one order:
+//   d what / d where of record t + 1  -> the prior statistics of frame t (loc; raw scale through eps softplus'), and with rw /
+//                                        guided into record t, the 0.1 factors of sq_prior_*_sample     (d_pstats +=, d_rec_prev +=)
+//   d LOGIT, d PROB of record t + 1, the score term g_sc (presence - sigmoid(logit))  -> the logit: statistics word 0 through
+//                                        the previous presence, and with rw / guided record t's logit  (d_pstats +=, d_rec_prev +=)
+//   d prior_m[t + 1][dst]             -> the adjoint of the prior cell's new state, which A^T consumes   (d_prior_p =, after the
+//                                        zeros k_compact_bwd wrote for the row)
+//   d temporal_m[t + 1][dst]          -> d temporal_m[t][k], the state was held                          (+=, after the sweep's
+//                                        first writers of the row: zeros for a coasted row)
+__global__ __launch_bounds__(64) void k_coast_step_bwd(const CoastBwdArgs a, const Dims d SQ_TLP) {
+  SQ_TL_SCOPE;
+  const int r = blockIdx.x, k = blockIdx.y, lane = threadIdx.x, N = d.N, nw = d.nw;
+  if (a.observed[(size_t)a.t * d.B + sq_div(r, d.k_mul)] != 0) return;
+  float lg, pres;
+  const int dst_l = sq_prior_frame_draw(a.cfg, d, r, lane, a.rec_prev, a.pstats, a.ps_ld, a.noise, lg, pres);
+  const int dst = __shfl(dst_l, k);
+  const float lgk = __shfl(lg, k), pk = __shfl(pres, k);
+  const size_t rk = (size_t)r * N + k, rd = (size_t)r * N + dst;
+  const float* rm = a.rec_prev + rk * rec::W;
+  const float* ps = a.pstats + rk * a.ps_ld;
+  const float* gn = a.noise + (((size_t)r * 2 + 0) * N + k) * d.nzw;
+  const float* dn = a.d_rec_next + rd * rec::W;
+  float* dp = a.d_rec_prev + rk * rec::W;
+  float* dps = a.d_pstats + rk * a.ps_ld;
+  const int type = a.cfg.prop_prior_type;
+  const float loc_c = type == 0 ? 1.0f : type == 1 ? 0.0f : 0.1f;
+  // where (i < 4) and what: record columns i, noise columns i, statistics loc 1 + i and raw scale 5 + nw + i (sq_prior_*_sample)
+  for (int i = lane; i < 4 + nw; i += 64) {
+    const float g = dn[i];
+    if (type != 1) dps[1 + i] += loc_c * g;
+    dps[5 + nw + i] += g * gn[i] * sq_sigmoid(ps[5 + nw + i]);
+    if (type != 0) dp[i] += g;
+  }
+  if (lane == 0) {
+    const float sg = sq_sigmoid(lgk);
+    const float dl = dn[rec::LOGIT] + dn[rec::PROB] * sg * (1.0f - sg) + a.g_sc[r] * (pk - sg);
+    dps[0] += dl * rm[rec::PRES] * (type != 0 ? 0.1f : 1.0f);
+    if (type != 0) dp[rec::LOGIT] += dl;
+  }
+  typedef float cf4 __attribute__((ext_vector_type(4)));
+  const cf4* pn = reinterpret_cast<const cf4*>(a.d_prior_next + rd * d.psnh);
+  cf4* pp = reinterpret_cast<cf4*>(a.d_prior_p + rk * d.psnh);
+  for (int i = lane; i < d.psnh / 4; i += 64) pp[i] = pn[i];
+  const cf4* tn = reinterpret_cast<const cf4*>(a.d_temporal_next + rd * d.snh);
+  cf4* tp = reinterpret_cast<cf4*>(a.d_temporal_prev + rk * d.snh);
+  for (int i = lane; i < d.snh / 4; i += 64) tp[i] = tp[i] + tn[i];
+}
+int sq_launch_coast_step_bwd(const CoastBwdArgs& a, Dims d, hipStream_t s) {
+  SQ_LAUNCH(k_coast_step_bwd, dim3(d.R, d.N), dim3(64), 0, s, a, d);
   return 0;
 }
 // Predictive summaries (ForecastSummaryArgs): workgroup (b, f).  Thread 0 turns the lane's log weights into w_k (max, exp, sum, divide,

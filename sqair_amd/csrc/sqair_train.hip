@@ -112,6 +112,7 @@ struct Dx {
 
 struct BwdSpace {
   float *g_lw, *g_dl;
+  float* g_sc;                                  // [T][R] a masked carried chunk: the score coefficients of coasted (frame, row)s
   float *d_rec_m, *d_rec_p, *d_rec_d;          // gradient records
   // d temporal / prior merged state, one buffer per frame boundary 0..T inside the part of the scratch that is cleared once
   // per pass (by frame parity they needed a clear per frame: 10 extra launches on the critical path)
@@ -161,7 +162,7 @@ static BwdSpace carve_bwd(const SqairHandle* h, int T, int B, float* base) {
     dst = base ? base + o : nullptr;
     o += align64(n);
   };
-  T_(b.g_lw, T * R); T_(b.g_dl, T * R);
+  T_(b.g_lw, T * R); T_(b.g_dl, T * R); T_(b.g_sc, T * R);
   T_(b.d_rec_m, (T + 1) * M * rec::W); T_(b.d_rec_p, MT * rec::W); T_(b.d_rec_d, MT * rec::W);
   const int64_t snh = c.time_cell == CELL_LSTM ? 2 * nh : nh, gw = sq_gate_width(c, c.time_cell);  // temporal state / gate widths
   const int64_t psnh = c.prior_cell == CELL_LSTM ? 2 * nh : nh, pgw = sq_gate_width(c, c.prior_cell);
@@ -223,9 +224,11 @@ struct SlotAdjPhase {
 
 // carried: after sqair_forward_train_carry -- each row's step-prior time is its counter plus the frame (w.t_row), and the frame-0
 // initial-state gradients take only the rows that started fresh (w.fresh); the imported rows are constants.
+// observed: the device mask [T][B] of a masked carried chunk (after sqair_forward_train_carry_masked with the same mask), or NULL.
+// With one the sweep has T + 1 launches more: k_coast_mask_grads after the objective, k_coast_step_bwd in every frame.
 static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, const float* obs, const float* noise,
                        const float* importance_weights, const float* vimco_signal, int T, int B, int t_offset, bool carried,
-                       void* train_workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes,
+                       const int32_t* observed, void* train_workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes,
                        float* flat_grad, void* stream) {
   if (!h || !flat || !packedv || !obs || !noise || !importance_weights || !vimco_signal || !train_workspace || !scratch || !flat_grad)
     return -1;
@@ -329,6 +332,13 @@ static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, c
 
   // ================= 0. objective =================
   sq_launch_elbo_bwd(importance_weights, vimco_signal, T, B, K, b.g_lw, b.g_dl, s);
+  // a masked carried chunk: the log weight of a coasted (frame, row) is not in the target, its discrete log-prob is the score term
+  // of the prior's presence draws.  J^T and H^T are linear in g_lw and g_dl: zeros there, zeros from them for those rows.
+  if (observed) {
+    CoastMaskArgs ma; memset(&ma, 0, sizeof(ma));
+    ma.observed = observed; ma.T = T; ma.g_lw = b.g_lw; ma.g_dl = b.g_dl; ma.g_sc = b.g_sc;
+    sq_launch_coast_mask_grads(ma, d, s);
+  }
 
   // ================= J^T. decoder branch, all frames =================
   {
@@ -385,6 +395,7 @@ static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, c
       ka.d_prior_next = b.d_pm(t + 1); ka.d_rec_p = d_rec_p_t; ka.d_rec_d = d_rec_d_t;
       ka.d_temporal_p = b.d_temporal_p; ka.d_prior_p = b.d_prior_p;
       ka.d_new_temporal = b.d_new_t + (size_t)t * R * snh; ka.d_new_prior = b.d_new_p + (size_t)t * R * psnh;
+      ka.observed_t = observed ? observed + (size_t)t * B : nullptr;
       sq_launch_compact_bwd(ka, po, d, s);
     }
     // ---- the lower part of a slot's adjoint, the same for both slot loops: glimpse encoder (WHAT_HEAD -> GENC1 -> GENC0 dX),
@@ -603,6 +614,17 @@ static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, c
       { Dx x(b.d_wb + (size_t)t * M * WB_LD, WB_LD); x.to(0, 128, d_hid1, 256).dact(hid1, 256, ACT_ELU); CK(rundx(L_WB2, x, M)); }
       { Dx x(d_hid1, 256); x.to(0, nh, d_tau + d.toff, snh).acc(); CK(rundx(L_TAU1, x, M)); }
     }
+    // ---- the coasted rows of a masked carried chunk: record t + 1, the prior state and the held temporal state back through the
+    //      frame's permutation (k_coast_step_bwd).  Here: after every first writer of d temporal_m[t] (E^T, D^T; zeros for these
+    //      rows), before A^T reads d_prior_p and the frame's d_pstats.
+    if (observed) {
+      CoastBwdArgs ca; memset(&ca, 0, sizeof(ca));
+      ca.observed = observed; ca.t = t; ca.rec_prev = rec_prev; ca.pstats = w.pstats + (size_t)t * M * PS_LD; ca.ps_ld = PS_LD;
+      ca.noise = nz; ca.g_sc = b.g_sc + (size_t)t * R; ca.d_rec_next = d_rec_next; ca.d_prior_next = b.d_pm(t + 1);
+      ca.d_temporal_next = b.d_tm(t + 1); ca.d_rec_prev = d_rec_prev; ca.d_pstats = b.d_pstats + (size_t)t * M * PS_LD;
+      ca.d_prior_p = b.d_prior_p; ca.d_temporal_prev = d_tau; ca.cfg = c;
+      sq_launch_coast_step_bwd(ca, d, s);
+    }
     // ---- A^T. prior cell
     float* d_pgru1 = b.d_pgru1 + (size_t)t * M * pgw;
     if (c.prior_cell == CELL_VANILLA) {
@@ -748,7 +770,7 @@ extern "C" int sqair_backward(SqairHandle* h, const float* flat, const void* pac
                               void* train_workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes,
                               float* flat_grad, void* stream) {
   if (h && sq_state_refusal(h, true, B, t_offset) != 0) return -1;
-  return sq_backward(h, flat, packedv, obs, noise, importance_weights, vimco_signal, T, B, t_offset, false, train_workspace,
+  return sq_backward(h, flat, packedv, obs, noise, importance_weights, vimco_signal, T, B, t_offset, false, nullptr, train_workspace,
                      workspace_bytes, scratch, scratch_bytes, flat_grad, stream);
 }
 // Backward of a carried chunk (include/sqair_hip.h: SqairCarry), after sqair_forward_train_carry and sqair_elbo.  The carry is
@@ -759,7 +781,19 @@ extern "C" int sqair_backward_carry(SqairHandle* h, const float* flat, const voi
                                     float* flat_grad, void* stream) {
   if (!h) return -1;
   if (sq_carry_refusal(h, "sqair_backward_carry", B, carry, nullptr) != 0) return -1;
-  return sq_backward(h, flat, packedv, obs, noise, importance_weights, vimco_signal, T, B, 0, true, train_workspace,
+  return sq_backward(h, flat, packedv, obs, noise, importance_weights, vimco_signal, T, B, 0, true, nullptr, train_workspace,
+                     workspace_bytes, scratch, scratch_bytes, flat_grad, stream);
+}
+// Backward of a masked carried chunk, after sqair_forward_train_carry_masked with the same mask (still holding the same words) and
+// sqair_elbo.  NULL observed: sqair_backward_carry.
+extern "C" int sqair_backward_carry_masked(SqairHandle* h, const float* flat, const void* packedv, const float* obs, const float* noise,
+                                           const float* importance_weights, const float* vimco_signal, int T, int B,
+                                           const SqairCarry* carry, const int32_t* observed, void* train_workspace,
+                                           int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, float* flat_grad,
+                                           void* stream) {
+  if (!h) return -1;
+  if (sq_observed_refusal(h, true, T) != 0 || sq_carry_refusal(h, "sqair_backward_carry_masked", B, carry, nullptr) != 0) return -1;
+  return sq_backward(h, flat, packedv, obs, noise, importance_weights, vimco_signal, T, B, 0, true, observed, train_workspace,
                      workspace_bytes, scratch, scratch_bytes, flat_grad, stream);
 }
 

@@ -353,47 +353,64 @@ class SqairCore(object):
             self.flat_grad = torch.zeros_like(self.flat)
 
     # ---- training with a carried state (include/sqair_hip.h: SqairCarry) --------------------------------------------------------
-    def forward_carry(self, carry):
+    def forward_carry(self, carry, observed=None):
         """forward(train=True) of a carried chunk: ``carry`` (a ``_capi.SqairCarry`` the caller keeps alive) names the blob the rows
-        start from, the blob frame T goes to and optionally the SMC resampler that ends the pass."""
+        start from, the blob frame T goes to and optionally the SMC resampler that ends the pass.  ``observed``: an int32 device
+        tensor [T, B] the caller keeps alive, nonzero = the lane has a frame -- a masked chunk (include/sqair_hip.h: "training on
+        gappy and ragged streams"); None: no mask."""
         with torch.cuda.device(self.device):
             self._join_in()
             self._train_buffers()
-            self._issue_carry(carry, backward=False)
+            self._issue_carry(carry, backward=False, observed=observed)
             self._join_out()
 
-    def backward_carry(self, carry):
-        """backward() of the chunk forward_carry(carry) ran: the imported rows are constants.  Returns ``self.flat_grad``."""
+    def backward_carry(self, carry, observed=None):
+        """backward() of the chunk forward_carry(carry, observed) ran: the imported rows are constants.  Returns ``self.flat_grad``."""
         assert getattr(self, "train_ws", None) is not None, "backward_carry() needs forward_carry() first"
         with torch.cuda.device(self.device):
             self._join_in()
-            self._issue_carry(carry, forward=False)
+            self._issue_carry(carry, forward=False, observed=observed)
             self._join_out()
         return self.flat_grad
 
-    def grad_step_carry(self, carry, use_graph=True):
-        """grad_step() of a carried chunk.  The first call for a (shape, carry) runs eagerly -- the chunk's one real step, which
-        advances the carried state -- and then captures the same calls without running them; later calls replay the graph."""
+    def grad_step_carry(self, carry, use_graph=True, observed=None):
+        """grad_step() of a carried chunk.  The first call for a (shape, carry, mask buffer) runs eagerly -- the chunk's one real
+        step, which advances the carried state -- and then captures the same calls without running them; later calls replay the
+        graph.  The mask is read on the device: one graph serves every content of the ``observed`` buffer."""
         if not use_graph:
-            self.forward_carry(carry)
-            return self.backward_carry(carry)
-        return self._graphed((self._shape, "carry", _carry_key(carry)), lambda: (self.forward_carry(carry), self.backward_carry(carry)),
-                             lambda: self._issue_carry(carry), replay_after_capture=False)
+            self.forward_carry(carry, observed)
+            return self.backward_carry(carry, observed)
+        key = (self._shape, "carry", _carry_key(carry), None if observed is None else observed.data_ptr())
+        return self._graphed(key, lambda: (self.forward_carry(carry, observed), self.backward_carry(carry, observed)),
+                             lambda: self._issue_carry(carry, observed=observed), replay_after_capture=False)
 
-    def _issue_carry(self, carry, forward=True, backward=True):
-        """The raw calls of a carried gradient evaluation (forward + ELBO, backward) on the core's stream: capturable."""
+    def _check_mask(self, observed):
+        if observed.dtype != torch.int32 or tuple(observed.shape) != (self.T, self.B) or not (observed.is_contiguous() and observed.is_cuda):
+            raise ValueError("observed must be a contiguous int32 device tensor [{}, {}]".format(self.T, self.B))
+        return observed.data_ptr()
+
+    def _issue_carry(self, carry, forward=True, backward=True, observed=None):
+        """The raw calls of a carried gradient evaluation (forward + ELBO, backward) on the core's stream: capturable.  With a
+        mask, the masked pair of calls."""
         ws, nb = self.train_ws.data_ptr(), self.train_ws.numel() * 4
+        mask = None if observed is None else self._check_mask(observed)
         if forward:
-            self.check(self.lib.sqair_forward_train_carry(
-                self.handle, self.flat.data_ptr(), self.packed.data_ptr(), self.obs.data_ptr(), self.noise.data_ptr(), self.T, self.B,
-                C.byref(carry), C.byref(self.c_out), ws, nb, self._stream()), "sqair_forward_train_carry")
+            head = (self.handle, self.flat.data_ptr(), self.packed.data_ptr(), self.obs.data_ptr(), self.noise.data_ptr(), self.T, self.B,
+                    C.byref(carry))
+            tail = (C.byref(self.c_out), ws, nb, self._stream())
+            if mask is None:
+                self.check(self.lib.sqair_forward_train_carry(*(head + tail)), "sqair_forward_train_carry")
+            else:
+                self.check(self.lib.sqair_forward_train_carry_masked(*(head + (mask,) + tail)), "sqair_forward_train_carry_masked")
             self._elbo()
         if backward:
-            self.check(self.lib.sqair_backward_carry(
-                self.handle, self.flat.data_ptr(), self.packed.data_ptr(), self.obs.data_ptr(), self.noise.data_ptr(),
-                self.importance_weights.data_ptr(), self.vimco_signal.data_ptr(), self.T, self.B, C.byref(carry), ws, nb,
-                self.bwd_scratch.data_ptr(), self.bwd_scratch.numel() * 4, self.flat_grad.data_ptr(), self._stream()),
-                "sqair_backward_carry")
+            head = (self.handle, self.flat.data_ptr(), self.packed.data_ptr(), self.obs.data_ptr(), self.noise.data_ptr(),
+                    self.importance_weights.data_ptr(), self.vimco_signal.data_ptr(), self.T, self.B, C.byref(carry))
+            tail = (ws, nb, self.bwd_scratch.data_ptr(), self.bwd_scratch.numel() * 4, self.flat_grad.data_ptr(), self._stream())
+            if mask is None:
+                self.check(self.lib.sqair_backward_carry(*(head + tail)), "sqair_backward_carry")
+            else:
+                self.check(self.lib.sqair_backward_carry_masked(*(head + (mask,) + tail)), "sqair_backward_carry_masked")
 
     def grads_by_name(self):
         """The last backward()'s gradients as a dict name -> tensor (reference variable shapes)."""

@@ -54,7 +54,7 @@ import numpy as np
 import torch
 
 from sqair_amd import _capi
-from sqair_amd.carried import CarriedState, carried
+from sqair_amd.carried import CarriedState, blank_unobserved, carried, check_observed
 
 DEFAULT_OUTPUTS = ("what", "where", "presence", "obj_id", "log_weights_per_timestep")
 FORECAST_OUTPUTS = ("what", "where", "presence", "presence_prob", "presence_logit", "obj_id", "canvas", "glimpse")
@@ -146,24 +146,9 @@ class SqairStream(object):
     # ---- stepping ---------------------------------------------------------------------------------------------------------
     def _check_observed(self, observed):
         """``observed`` of a step as a bool tensor [T', B] (None: every lane has its frame)."""
-        if observed is None:
-            return None
-        if not self.missing:
-            raise ValueError("SqairStream.step: observed is for a stream with missing=True")
-        m = torch.as_tensor(observed)
-        if m.dtype != torch.bool:
-            raise ValueError("SqairStream.step: observed must be a bool array, dtype {} given".format(m.dtype))
-        if self.T == 1 and tuple(m.shape) == (self.B,):
-            m = m.reshape(1, self.B)
-        if tuple(m.shape) != (self.T, self.B):
-            raise ValueError("SqairStream.step: observed of shape {} given, [{}, {}] expected{}".format(
-                tuple(m.shape), self.T, self.B, " (or [{}])".format(self.B) if self.T == 1 else ""))
-        return m
+        return check_observed(observed, self.missing, self.T, self.B, "SqairStream", "stream")
 
-    @staticmethod
-    def _blank_unobserved(frames, observed):
-        """The frames of unobserved lanes as zeros: the pass still computes on them (include/sqair_hip.h: they must be finite)."""
-        return torch.where(observed.to(frames.device)[:, :, None, None], frames, 0.0)
+    _blank_unobserved = staticmethod(blank_unobserved)
 
     def step(self, frames, noise=None, seed=None, uniforms=None, observed=None):
         """Consumes frames [T', B, H, W] (T' = frames_per_step); returns this step's per-frame outputs {name: [T', B*K, ...]}

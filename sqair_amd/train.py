@@ -13,7 +13,7 @@ import ctypes as C
 
 import numpy as np
 
-from .carried import CarriedState, carried
+from .carried import CarriedState, blank_unobserved, carried, check_observed
 
 
 def lr_schedule(F):
@@ -189,10 +189,16 @@ class StreamTrainer(object):
     step's source map) as in ``SqairStream``.  Default noise: the library's Philox keyed by (seed, index of the chunk's first frame,
     position in the global batch), so that data-parallel ranks draw what one GPU would.  ``state`` can be handed to
     ``SqairStream(core, B, state=...)`` of the same core and B.  The trainer takes no registration on the handle: close a
-    ``SqairStream`` of the same core before stepping."""
+    ``SqairStream`` of the same core before stepping.
+
+    ``missing=True``: a step takes ``observed`` [T', B] (include/sqair_hip.h: "training on gappy and ragged streams").  A lane
+    without a frame -- a dropped frame, a slower camera, or, as a trailing run, a clip that ends inside the chunk -- coasts on the
+    prior: its log weight is 0, its posterior gets no gradient, the prior is trained through the coasted draws and their score term.
+    The step then runs the masked pair of calls (T' + 1 launches more each way); the mask lives in one device buffer that the
+    captured graph reads, so every pattern replays the same graph.  On a data-parallel job the mask covers this rank's lanes."""
 
     def __init__(self, core_or_model, F, B, frames_per_step=1, seed=0, resample=None, use_graph=True, comm=None, collective=True,
-                 outputs=("what", "where", "presence", "obj_id")):
+                 outputs=("what", "where", "presence", "obj_id"), missing=False):
         core = getattr(core_or_model, "core", core_or_model)
         if core.cfg.sample_from_prior:
             raise ValueError("StreamTrainer: generation modes (sample_from_prior) do not carry a state")
@@ -216,6 +222,11 @@ class StreamTrainer(object):
         # the blob, the source map (host-side until a step uploads it; SMC: the resampler's) and the weights (sqair_amd/carried.py)
         self.carried = CarriedState(core, self.B, "StreamTrainer", self.smc)
         self._carries = {}      # SqairCarry (and its SqairSmc) per uniforms mode, kept alive while the trainer lives
+        self.missing = bool(missing)
+        if self.missing:   # the device mask [T', B] both masked calls read: all observed until a step says otherwise
+            import torch
+            self._observed = torch.ones((self.T, self.B), dtype=torch.int32, device=core.device)
+            self._observed_is_ones = True
         core.stream.synchronize()
 
     # the carried state's, read-only; ``ancestors`` (SMC): the source map of the next step, written by the resampler
@@ -247,16 +258,34 @@ class StreamTrainer(object):
         self.carried.resample(src_rows)
 
     # ---- stepping ------------------------------------------------------------------------------------------------------------
-    def step(self, frames, noise=None, seed=None, uniforms=None, global_batch=None, b0=0):
+    def _check_observed(self, observed):
+        return check_observed(observed, self.missing, self.T, self.B, "StreamTrainer", "trainer")
+
+    def step(self, frames, noise=None, seed=None, uniforms=None, global_batch=None, b0=0, observed=None):
         """One training step on the next chunk: frames [T', B, H, W]; ``noise`` [T', B*K, 2, N, 4 + n_what + 1] (default: Philox
         keyed by (``seed`` or the trainer's seed, the chunk's first frame, position in the global batch ``global_batch`` / ``b0``));
         ``uniforms`` [B] (SMC only: the resampler's uniforms; default Philox).  Asynchronous on the core's stream.  Returns the
-        flat gradient buffer after the optimiser step (on a multi-rank job the SUM over the ranks, as ``Trainer.step``)."""
+        flat gradient buffer after the optimiser step (on a multi-rank job the SUM over the ranks, as ``Trainer.step``).
+        ``observed`` (trainers with ``missing=True``): bool [T', B] of this rank's lanes, or [B] when T' = 1; False = the lane has no
+        frame there and coasts on the prior.  Its frame is replaced by zeros, so it may hold anything, NaN included.  Default:
+        every lane observed."""
+        observed = self._check_observed(observed)   # (before the core is touched)
         core, cs = self.core, self.carried
         frames, noise, uniforms = cs.check_inputs(self.T, frames, noise, uniforms, "trainer")
+        if observed is not None:
+            if frames.is_cuda:
+                observed = observed.to(frames.device)
+            frames = blank_unobserved(frames, observed)
         with core.on_stream():
             cs.feed(frames, noise, uniforms, self.seed if seed is None else int(seed), self.frame, global_batch=global_batch, b0=b0)
-            g = core.grad_step_carry(self._carry(uniforms is not None), use_graph=self.use_graph)
+            if self.missing:
+                if observed is not None:
+                    self._observed.copy_(observed.to(core.device, non_blocking=True))
+                elif not self._observed_is_ones:
+                    self._observed.fill_(1)
+                self._observed_is_ones = observed is None
+            g = core.grad_step_carry(self._carry(uniforms is not None), use_graph=self.use_graph,
+                                     observed=self._observed if self.missing else None)
             if not self.smc:
                 cs.log_weight_sum += core.out["log_weights_per_timestep"].sum(0)
             _finish_step(self, g)
