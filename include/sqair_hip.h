@@ -390,6 +390,75 @@ int sqair_forecast(SqairHandle* h, const float* flat_params, const void* packed,
  * sqair_set_state switching the state off, or to another B, switches the mask off. */
 int sqair_set_observed(SqairHandle* h, const int32_t* observed /* device [T,B]; NULL: off */, int T, int B);
 
+/* ---- lane estimates: one answer per lane from its K particles, inside the pass ----------------------------------------------
+ * A pass returns K particle rows per lane; a tracker's caller wants one answer per camera: how many objects, where (boxes in
+ * pixels), how sure.  With an estimate set, every following inference pass with a carried state ends with one more kernel,
+ * k_lane_estimate, one workgroup per (lane b, frame t): after k_coast_finish, the state export and the history push, and BEFORE the
+ * SMC resampler, which zeroes log_w and rewrites the source map.  No host round trip: one captured graph serves every step.  A
+ * pass with the estimate on has exactly one kernel node more; with it off nothing is launched and every other output, blob and
+ * accumulator is unchanged bit for bit.  Training passes never run it.
+ * For frame t of the pass and lane b, rows r = b*K + k:
+ * 1. Weights.  a_k(t) = log_w[r] + sum over t' <= t of log_weights_per_timestep[t', r], in frame order, in fp32: the resampler's
+ *    accumulation stopped at frame t.  m = max_k a_k, e_k = expf(a_k - m), S = sum e_k, w_k = e_k / S, ESS = S^2 / sum e_k^2, each
+ *    sum one thread's loop in index order -- the device code of the resampler and of the forecast's summaries, not a restatement.
+ *    weights[t,b,k] = w_k, ess[t,b] = ESS; with SMC on, ess[T-1, b] is the resampler's ess[b] bit for bit.  log_w is the carried
+ *    log weight of this pass's rows, as it stands when the pass runs (with SMC: smc->log_w); NULL means zeros.
+ * 2. Best row.  best_row[t,b] = b*K + the first k of maximal a_k (an exact compare: a_k is defined in fp32).
+ * 3. Count posterior.  n_k = the number of present slots (presence != 0) of row k; count_prob[t,b,c] = sum_k w_k [n_k = c] for
+ *    c = 0..N, expected_count[t,b] = sum_k w_k n_k, map_count[t,b] = the first c of maximal count_prob; k in index order.
+ * 4. The lane's objects are the best row's slots j (already present-first): presence, obj_id [t,b,N], where [t,b,N,4] and what
+ *    [t,b,N,n_what] are copies of the best row's 32-bit words, zero where the slot is absent.  box[t,b,j] = (y, x, h, w) in pixels
+ *    is the reference's stn_to_pixel_coords(to_coords(where), (H, W)) (sqair/modules.py:221-262):
+ *      (sx, sy, tx, ty) = to_coords(where) (sigmoid kept >= 1e-4, tanh), y = (H - 1) / 2 (ty - sy + 1), h = (H + 1) sy,
+ *      x = (W - 1) / 2 (tx - sx + 1), w = (W + 1) sx,
+ *    with the device to_coords of the crop and insert kernels: the box the decoder drew with.  Zero where absent.
+ * 5. Support and consensus box, by SPATIAL association -- not by id: obj_id is a per-row counter that agrees between two rows
+ *    only as far back as their common ancestor, and slots are not objects (compaction moves them).  For each present best-row
+ *    object j and each particle k:  m* = the first present slot of row k with maximal IoU(box[j], box of (k, m)).  Boxes are axis
+ *    aligned; IoU = intersection / union with overlap lengths min(y1 + h1, y2 + h2) - max(y1, y2) (x alike) clipped at 0; 0 when
+ *    the union is not positive, else exactly 1 for two boxes with the same four words.  Particle k AGREES on j when that IoU >=
+ *    iou_min.  support[t,b,j] = sum_k w_k [k agrees] (the best row always agrees with itself: its IoU is 1), box_mean[t,b,j] =
+ *    sum_k w_k [k agrees] box of (k, m*) / support; both zero where slot j is absent.  k in index order: the same bits on every
+ *    replay, eager or graph.  Matching is NOT one-to-one: two best-row objects may be matched by the same slot of a particle
+ *    (one-to-one, Hungarian, matching is out of scope).
+ * 6. mean_canvas[t,b] = sum_k w_k canvas[t, r], k in index order: only when asked for, and the pass must then bind out->canvas.
+ * 7. Non-finite lanes: the resampler's rule, bad values stay visible.  A lane whose S is not finite (some a_k NaN or +inf, or
+ *    every a_k -inf) gives NaN weights, ess, count_prob, expected_count, support, box_mean and mean_canvas, best_row = map_count
+ *    = -1 and zero objects (presence, obj_id, where, what, box).  Finite lanes of the same launch are unaffected.
+ * 8. Coasted (frame, lane)s (sqair_set_observed) need no special case: their records are the coasted ones, their log weight 0.
+ * Every pointer of SqairLaneEstimate is optional except best_row.  Pointers are remembered by the handle and frozen into captured
+ * graphs, as the state's are.  NULL est: off.  Refused (return -1, text in sqair_last_error, before any HIP call): no state set,
+ * T < 1, a B other than the state's, iou_min NaN or outside (0, 1], a NULL best_row, with SMC on a log_w other than smc->log_w;
+ * at pass time: a pass of another T, a NULL out->log_weights_per_timestep, mean_canvas without out->canvas, SMC on with another
+ * log_w.  The objects are read from the pass's own merged slot records, not from its SqairOutputs buffers: those need not be
+ * bound.  sqair_set_state switching the state off, or to another B, switches the estimate off.
+ * Out of scope: estimates for training passes, smoothed (lagged) estimates -- sqair_history_trace plus best_row serve those. */
+typedef struct SqairLaneEstimate {
+  float iou_min;             /* in (0, 1] */
+  const float* log_w;        /* [B*K] in: carried log weights of the pass's rows; NULL = zeros */
+  int32_t* best_row;         /* [T,B] required */
+  float* weights;            /* [T,B,K] */
+  float* ess;                /* [T,B] */
+  float* count_prob;         /* [T,B,N+1] */
+  float* expected_count;     /* [T,B] */
+  int32_t* map_count;        /* [T,B] */
+  float* presence;           /* [T,B,N] */
+  float* obj_id;             /* [T,B,N] */
+  float* where;              /* [T,B,N,4] */
+  float* what;               /* [T,B,N,n_what] */
+  float* box;                /* [T,B,N,4] (y, x, h, w) in pixels */
+  float* support;            /* [T,B,N] */
+  float* box_mean;           /* [T,B,N,4] */
+  float* mean_canvas;        /* [T,B,H,W] */
+} SqairLaneEstimate;
+int sqair_set_estimate(SqairHandle* h, const SqairLaneEstimate* est /* NULL: off */, int T, int B);
+/* Kernel-level check of the estimate (tests): the kernel above on caller buffers, no state and no pass, any K in 1..256 with the
+ * handle's N, n_what, H, W.  where [T,B*K,N,4], presence, obj_id [T,B*K,N], what [T,B*K,N,n_what] (or NULL), canvas [T,B*K,H,W]
+ * (or NULL), lw [T,B*K] standing for the pass's log_weights_per_timestep.  Refused (return -1, before any HIP call): a NULL where /
+ * presence / obj_id / lw / est, T, B or K out of range, what est refuses, est->what without what, est->mean_canvas without canvas. */
+int sqair_lane_estimate_test(SqairHandle* h, const float* where, const float* presence, const float* obj_id, const float* what,
+                             const float* canvas, const float* lw, int T, int B, int K, const SqairLaneEstimate* est, void* stream);
+
 /* ---- objective ---------------------------------------------------------------------------------
  * Fused IWAE / VIMCO reductions over [T,B,K] (reference: Model._build sqair/model.py:88-103,
  * targets.iwae / vimco_control_variate / vimco sqair/targets.py:38-75, make_target model.py:150-158,

@@ -64,6 +64,18 @@ class SqairForecastOutputs(C.Structure):
                                           "log_w", "mean_canvas", "expected_count")]
 
 
+# lane estimates (include/sqair_hip.h: sqair_set_estimate): the outputs of SqairLaneEstimate in declaration order; the two int32 ones
+ESTIMATE_FIELDS = ("best_row", "weights", "ess", "count_prob", "expected_count", "map_count", "presence", "obj_id", "where", "what",
+                   "box", "support", "box_mean", "mean_canvas")
+ESTIMATE_INT_FIELDS = ("best_row", "map_count")
+
+
+class SqairLaneEstimate(C.Structure):
+    """One answer per lane from its particles (include/sqair_hip.h: sqair_set_estimate); every pointer is a device address, all but
+    best_row optional."""
+    _fields_ = [("iou_min", C.c_float), ("log_w", C.c_void_p)] + [(n, C.c_void_p) for n in ESTIMATE_FIELDS]
+
+
 # track history (include/sqair_hip.h: sqair_set_history): the bit of each field a ring slot may hold; the first three are mandatory
 HISTORY_FIELDS = {"where": 1, "presence": 2, "obj_id": 4, "what": 8, "log_weights_per_timestep": 16}
 HISTORY_MANDATORY = ("where", "presence", "obj_id")
@@ -156,6 +168,8 @@ _PROTOS = {
     "sqair_set_history": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_uint32]),
     "sqair_history_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SqairTraceOutputs), C.c_void_p]),
     "sqair_set_observed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "sqair_set_estimate": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneEstimate), C.c_int, C.c_int]),
+    "sqair_lane_estimate_test": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int, C.POINTER(SqairLaneEstimate), C.c_void_p]),
     "sqair_forecast_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
     "sqair_forecast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                  C.POINTER(SqairForecastOutputs), C.c_void_p, C.c_int64, C.c_void_p]),
@@ -241,8 +255,8 @@ def lib(path=None, allow_stale=False):
             raise ImportError("{}: ABI version {} but this binding speaks {}; rebuild (python sqair_amd/csrc/build.py)".format(
                 os.path.basename(path), l.sqair_abi_version(), ABI_VERSION))
         for name, (res, args) in _PROTOS.items():
-            if allow_stale and name.startswith("sqair_debug") and not hasattr(l, name):
-                continue   # (tools/ab_libs.py: a build of an older revision has the same ABI version but may lack a newer debug query)
+            if allow_stale and not hasattr(l, name):
+                continue   # (tools/ab_libs.py: a build of an older revision has the same ABI version but may lack a newer entry point)
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args

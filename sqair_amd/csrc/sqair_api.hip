@@ -1006,7 +1006,7 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
                     hipStream_t s, bool train, int parts, const SqStateRes* carry = nullptr) {
   const SqairConfig& c = h->cfg;
   if (!carry && (sq_observed_refusal(h, train, T) != 0 || sq_state_refusal(h, train, B, t_offset) != 0 || sq_smc_refusal(h, outp) != 0 ||
-                 sq_history_refusal(h, T, B, outp) != 0))
+                 sq_history_refusal(h, T, B, outp) != 0 || sq_estimate_refusal(h, T, outp) != 0))
     return -1;
   const SqStateRes st = carry ? *carry : sq_handle_state(h);
   if (!flat || !packed || !obs || !noise || !outp || !wsbase || T < 1 || B < 1) {
@@ -1398,6 +1398,9 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
   // track history: this pass's rows, the map it imported through and its counters into the ring (sqair_set_history) -- before the
   // resampler overwrites that map
   if (st.hist_on) sq_launch_history_push(sq_history_push_args(h, st, out, w.t_row, T, B), s);
+  // lane estimates: one answer per (frame, lane) from this pass's rows and the log weights they carry (sqair_set_estimate) -- before
+  // the resampler zeroes those weights and rewrites the map
+  if (st.est_on) sq_launch_lane_estimate(sq_estimate_args(h, w.rec_m_all + (size_t)M * RW, out, T, B), s);
   // SMC: this pass's log weights -> ESS, evidence and the next pass's source map (sqair_set_smc / SqairCarry.smc)
   if (st.smc_on) sq_launch_smc_resample(sq_smc_args(st.smc, out.log_weights_per_timestep, w.t_row, T, B, K), s);
   SQ_CHECK_HIP(hipGetLastError());
@@ -1695,7 +1698,7 @@ extern "C" int sqair_graph_capture(SqairHandle* h, const float* flat_params, con
                                    void* workspace, int64_t workspace_bytes, void* stream) {
   if (!h) return -1;
   if (sq_observed_refusal(h, false, T) != 0 || sq_state_refusal(h, false, B, t_offset) != 0 || sq_smc_refusal(h, out) != 0 ||
-      sq_history_refusal(h, T, B, out) != 0)
+      sq_history_refusal(h, T, B, out) != 0 || sq_estimate_refusal(h, T, out) != 0)
     return -1;
   hipStream_t s = (hipStream_t)stream;
   if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
@@ -1703,14 +1706,16 @@ extern "C" int sqair_graph_capture(SqairHandle* h, const float* flat_params, con
   if (h->opt_slot_chain) {  // one eager pass: the chain launches' op tables are uploaded outside the capture (sqair_chain.hip)
     void* const state_out = h->state_out;   // (a carried state is imported but not exported, resampled or pushed: the capture
     const bool smc_on = h->smc_on;           //  leaves the state, its source map, the SMC weights and the history as they were)
-    const bool hist_on = h->hist_on;
+    const bool hist_on = h->hist_on, est_on = h->est_on;
     h->state_out = nullptr;
     h->smc_on = false;
     h->hist_on = false;
+    h->est_on = false;
     const int rc0 = forward_impl(h, flat_params, (const float*)packed, obs, noise, T, B, t_offset, out, (float*)workspace, workspace_bytes, s);
     h->state_out = state_out;
     h->smc_on = smc_on;
     h->hist_on = hist_on;
+    h->est_on = est_on;
     if (rc0 != 0) return rc0;
     SQ_CHECK_HIP(hipStreamSynchronize(s));
   }

@@ -254,6 +254,12 @@ __device__ __forceinline__ float sq_sigmoid(float x) { return __builtin_amdgcn_r
 // into 6e-5 pixels at the glimpse edge and the likelihood sums over ~400 pixels into 0.04 - 0.4 nats per frame: found as a
 // uniform few-percent deviation of whole gradients from the oracle in states with tiny scales (tests/nan_probe.py).
 __device__ __forceinline__ float sq_sigmoid_geo(float x) { return 1.0f / (1.0f + expf(-x)); }
+// to_coords of the spatial transformer (sqair/modules.py:220-227, with the clip of :205-206) for entry q of a `where`
+// (sx, sy, tx, ty): the scales are sigmoids kept at or above 1e-4, the shifts libm's tanh -- the expression the crops (sqair_crop_body.inc,
+// sqair_chain.hip) and the decoder's insert (sqair_canvas.h) evaluate in place, as a function for the lane estimate's boxes, so that
+// a box is the box the decoder drew with.  (Those kernels keep their own statement: routed through this function their code came out a
+// few instructions different, and they are hops of the slot loop whose code is not touched without a measurement.)
+__device__ __forceinline__ float sq_to_coord(float l, int q) { return (q & 2) ? tanhf(l) : fmaxf(sq_sigmoid_geo(l), 1e-4f); }
 __device__ __forceinline__ float sq_tanh(float x) {  // 1 - 2 / (e^{2x} + 1): saturates cleanly (e^{2x} = inf -> 1, 0 -> -1)
   return 1.0f - 2.0f * __builtin_amdgcn_rcpf(sq_exp(2.0f * x) + 1.0f);
 }

@@ -388,6 +388,23 @@ struct ForecastSummaryArgs {
 };
 int sq_launch_forecast_summary(const ForecastSummaryArgs& a, Dims d, hipStream_t s);
 
+// Lane estimates (sqair_set_estimate; include/sqair_hip.h states the semantics): k_lane_estimate, one workgroup per (lane b, frame t)
+// -- times a third grid dimension over pixel chunks when mean_canvas is asked for, each recomputing the weights.  The objects of
+// (frame t, row r, slot j) are read at a base + ((t * R + r) * N + j) * ld: the pass's merged records (every ld = rec::W) or, for the
+// kernel-level entry point, the caller's tensors (ld = 4, 1, 1, n_what).
+constexpr int SQ_EST_PIXELS = 1024;   // pixels of mean_canvas per workgroup of the third grid dimension
+struct LaneEstArgs {
+  const float* where; int where_ld;
+  const float* presence; int pres_ld;
+  const float* obj_id; int id_ld;
+  const float* what; int what_ld;      // NULL unless est.what is set
+  const float* canvas;                 // [T][R][H*W]; NULL unless est.mean_canvas is set
+  const float* lw;                     // the pass's log_weights_per_timestep [T][R]
+  SqairLaneEstimate est;               // iou_min, log_w and the outputs
+  int T, B, K, N, nw, H, W;
+};
+int sq_launch_lane_estimate(const LaneEstArgs& a, hipStream_t s);
+
 struct CompactArgs {
   const float* rec_p; const float* rec_d; const float* rec_prev;
   const float* temporal_p; const float* prior_p;

@@ -94,6 +94,10 @@ struct SqairHandle {
   // missing-frame steps (sqair_set_observed): the passes' kernels read this device mask [observed_T][state_B]
   const int32_t* observed = nullptr;
   int observed_T = 0;
+  // lane estimates (sqair_set_estimate): one k_lane_estimate launch after the history push, before the resampler
+  bool est_on = false;
+  SqairLaneEstimate est = {};
+  int est_T = 0;
   // generic capture slots (sqair_capture_begin / _end / _launch): any sequence of C-ABI calls as one HIP graph
   hipGraph_t cap_graph[4] = {nullptr, nullptr, nullptr, nullptr};
   hipGraphExec_t cap_exec[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -237,6 +241,7 @@ struct SqStateRes {
   bool smc_on; SqairSmc smc;
   bool hist_on = false;   // (the handle's inference passes only: a carried training call never pushes)
   const int32_t* observed = nullptr;   // (the same: the handle's device mask of sqair_set_observed, or NULL)
+  bool est_on = false;    // (the same: a carried training call never estimates)
 };
 SQ_LOCAL SqStateRes sq_handle_state(const SqairHandle* h);
 SQ_LOCAL SqStateRes sq_carry_state(const SqairCarry* c);
@@ -250,6 +255,10 @@ SQ_LOCAL int sq_history_refusal(SqairHandle* h, int T, int B, const SqairOutputs
 SQ_LOCAL int sq_observed_refusal(SqairHandle* h, bool train, int T);
 SQ_LOCAL HistPushArgs sq_history_push_args(const SqairHandle* h, const SqStateRes& st, const SqairOutputs& out, const int* t_row, int T, int B);
 SQ_LOCAL SmcArgs sq_smc_args(const SqairSmc& m, const float* lw, const int32_t* t_row, int T, int B, int K);
+// lane estimates: -1 + error text for a pass with the estimate on that it rules out (host only); the kernel's arguments for a pass
+// of T frames over the merged records `rec` [T][R][N][rec::W]
+SQ_LOCAL int sq_estimate_refusal(SqairHandle* h, int T, const SqairOutputs* outp);
+SQ_LOCAL LaneEstArgs sq_estimate_args(const SqairHandle* h, const float* rec, const SqairOutputs& out, int T, int B);
 // section A of a frame of the pass, and a frame of the forecast: the propagation-prior cell and its statistics (sqair_api.hip)
 SQ_LOCAL int sq_prior_step(SqairHandle* h, const float* packed, hipStream_t s, int M, const float* rec_prev, const float* prior_prev,
                            float* prior_p, float* pgz, float* pgrh, float* pgxh, float* pstats, float* o3, float* o1);

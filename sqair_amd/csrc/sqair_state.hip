@@ -16,6 +16,7 @@ int64_t sq_state_row_floats(const SqairHandle* h) {
   return (N * (rec::W + snh + psnh) + 2 + 3) / 4 * 4;
 }
 static void sq_observed_off(SqairHandle* h) { h->observed = nullptr; h->observed_T = 0; }
+static void sq_estimate_off(SqairHandle* h) { h->est_on = false; h->est = SqairLaneEstimate{}; h->est_T = 0; }
 static void sq_history_off(SqairHandle* h) {
   h->hist_on = false; h->hist_ring = nullptr; h->hist_bytes = 0; h->hist_L = 0; h->hist_T = 0; h->hist_fields = 0;
 }
@@ -30,6 +31,7 @@ extern "C" int sqair_set_state(SqairHandle* h, const void* state_in, void* state
     h->smc_on = false; h->smc = SqairSmc{};   // (SMC resamples the carried state: off with it)
     sq_history_off(h);                        // (the history records the carried rows: off with it)
     sq_observed_off(h);                       // (the mask is per lane of the carried batch: off with it)
+    sq_estimate_off(h);                       // (and so are the estimate's outputs)
     return 0;
   }
   if (h->cfg.sample_from_prior) return sq_no(h, "sqair_set_state: not with sample_from_prior (generation decides per frame on the host)");
@@ -42,6 +44,7 @@ extern "C" int sqair_set_state(SqairHandle* h, const void* state_in, void* state
   }
   if (h->hist_on && B != h->state_B) sq_history_off(h);   // (the ring was sized for the other B)
   if (B != h->state_B) sq_observed_off(h);                // (and so was the mask)
+  if (B != h->state_B) sq_estimate_off(h);                // (and the estimate's outputs)
   h->state_on = true; h->state_in = state_in; h->state_out = state_out; h->state_src = src_rows; h->state_B = B;
   return 0;
 }
@@ -125,6 +128,79 @@ extern "C" int sqair_smc_resample_test(SqairHandle* h, const float* lw, int T, i
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }
+// ------------------------------------------------------------------------------------------------
+// lane estimates (include/sqair_hip.h: sqair_set_estimate): registration, the refusals of a pass, the arguments of k_lane_estimate
+// (launched by sq_forward_impl) and the kernel-level entry point
+// ------------------------------------------------------------------------------------------------
+// what every user of an SqairLaneEstimate checks, -1 + "<who>..." when one is off
+static int sq_estimate_fields(SqairHandle* h, const std::string& who, const SqairLaneEstimate& e) {
+  if (!(e.iou_min > 0.0f && e.iou_min <= 1.0f)) return sq_no(h, who + "iou_min must lie in (0, 1]");   // (NaN fails both)
+  if (!e.best_row) return sq_no(h, who + "best_row must not be NULL");
+  return 0;
+}
+static int sq_estimate_smc_mismatch(SqairHandle* h, const std::string& who, const SqairLaneEstimate& e) {
+  if (!h->smc_on || e.log_w == h->smc.log_w) return 0;
+  return sq_no(h, who + "with SMC on (sqair_set_smc) log_w must be smc->log_w, the carried log weights of the pass's rows");
+}
+extern "C" int sqair_set_estimate(SqairHandle* h, const SqairLaneEstimate* est, int T, int B) {
+  if (!h) return -1;
+  if (!est) {
+    sq_estimate_off(h);
+    return 0;
+  }
+  const std::string who = "sqair_set_estimate: ";
+  if (!h->state_on) return sq_no(h, who + "needs a carried state (sqair_set_state): the estimate weighs the rows it carries");
+  if (T < 1) return sq_no(h, who + "T must be >= 1");
+  if (B != h->state_B)
+    return sq_no(h, who + "B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
+  if (sq_estimate_fields(h, who, *est) != 0 || sq_estimate_smc_mismatch(h, who, *est) != 0) return -1;
+  h->est_on = true; h->est = *est; h->est_T = T;
+  return 0;
+}
+// the refusal of a pass with the estimate on (host only: before any HIP call)
+int sq_estimate_refusal(SqairHandle* h, int T, const SqairOutputs* outp) {
+  if (!h->state_on || !h->est_on) return 0;
+  const std::string who = "lane estimate (sqair_set_estimate): ";
+  if (T != h->est_T)
+    return sq_no(h, who + "the outputs were registered for passes of T = " + std::to_string(h->est_T) + " frames, a pass of T = " +
+                    std::to_string(T) + " cannot fill them");
+  if (!outp || !outp->log_weights_per_timestep)
+    return sq_no(h, who + "the weights are formed from log_weights_per_timestep: a pass with the estimate on must bind that output");
+  if (h->est.mean_canvas && !outp->canvas) return sq_no(h, who + "mean_canvas averages the pass's canvases: the pass must bind out->canvas");
+  return sq_estimate_smc_mismatch(h, who, h->est);
+}
+LaneEstArgs sq_estimate_args(const SqairHandle* h, const float* rec, const SqairOutputs& out, int T, int B) {
+  const SqairConfig& c = h->cfg;
+  LaneEstArgs a; memset(&a, 0, sizeof(a));
+  a.where = rec + rec::WHERE; a.presence = rec + rec::PRES; a.obj_id = rec + rec::ID; a.what = rec + rec::WHAT;
+  a.where_ld = a.pres_ld = a.id_ld = a.what_ld = rec::W;
+  a.canvas = out.canvas; a.lw = out.log_weights_per_timestep; a.est = h->est;
+  a.T = T; a.B = B; a.K = c.k_particles; a.N = c.n_steps_per_image; a.nw = c.n_what; a.H = c.img_h; a.W = c.img_w;
+  return a;
+}
+// kernel-level check of the estimate (tests/test_estimate_kernel.py): k_lane_estimate on caller tensors, K given (1..SQ_MAX_K), no
+// state and no pass
+extern "C" int sqair_lane_estimate_test(SqairHandle* h, const float* where, const float* presence, const float* obj_id,
+                                        const float* what, const float* canvas, const float* lw, int T, int B, int K,
+                                        const SqairLaneEstimate* est, void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_lane_estimate_test: ";
+  const SqairConfig& c = h->cfg;
+  if (!where || !presence || !obj_id || !lw || !est || T < 1 || B < 1 || K < 1 || K > SQ_MAX_K || T > 65535 ||
+      (int64_t)B * K > INT32_MAX)
+    return sq_no(h, who + "null where / presence / obj_id / lw / est or bad T / B / K (1 <= K <= " + std::to_string(SQ_MAX_K) + ")");
+  if (sq_estimate_fields(h, who, *est) != 0) return -1;
+  if (est->what && !what) return sq_no(h, who + "est->what needs what");
+  if (est->mean_canvas && !canvas) return sq_no(h, who + "est->mean_canvas needs canvas");
+  LaneEstArgs a; memset(&a, 0, sizeof(a));
+  a.where = where; a.where_ld = 4; a.presence = presence; a.pres_ld = 1; a.obj_id = obj_id; a.id_ld = 1;
+  a.what = what; a.what_ld = c.n_what; a.canvas = canvas; a.lw = lw; a.est = *est;
+  a.T = T; a.B = B; a.K = K; a.N = c.n_steps_per_image; a.nw = c.n_what; a.H = c.img_h; a.W = c.img_w;
+  sq_launch_lane_estimate(a, (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 // the refusals of a carried training call (host only: before any HIP call)
 int sq_carry_refusal(SqairHandle* h, const char* fn, int B, const SqairCarry* carry, const SqairOutputs* out) {
   const std::string f = std::string(fn) + ": ";
@@ -161,7 +237,7 @@ int sq_state_refusal(SqairHandle* h, bool train, int B, int t_offset) {
 
 SqStateRes sq_handle_state(const SqairHandle* h) {
   return SqStateRes{h->state_on, h->state_in, h->state_out, h->state_src, false, h->smc_on, h->smc, h->state_on && h->hist_on,
-                    h->state_on ? h->observed : nullptr};
+                    h->state_on ? h->observed : nullptr, h->state_on && h->est_on};
 }
 SqStateRes sq_carry_state(const SqairCarry* c) {
   return SqStateRes{true, c->state_in, c->state_out, c->src_rows, true, c->smc != nullptr, c->smc ? *c->smc : SqairSmc{}};

@@ -39,6 +39,14 @@ prior, as ``forecast`` would, their temporal states held, their weights left alo
 so the one captured graph serves every pattern of present and missing lanes.  Feeding a blank frame instead would let the inference
 network "see" an empty scene and kill the objects.
 
+With ``estimate=True`` a step also returns ``out["lane"]``: one answer per lane and frame from the K particles, formed by one more
+kernel of the pass before the resampler zeroes the weights (include/sqair_hip.h: sqair_set_estimate, which states the semantics):
+the normalised ``weights`` [T', B, K] and ``ess`` [T', B] of the step's own rows, ``best_row``, the count posterior ``count_prob``
+[T', B, N + 1] with ``expected_count`` and ``map_count``, the best row's objects (``presence``, ``obj_id``, ``where``, ``what``) with
+their ``box`` [T', B, N, 4] = (y, x, h, w) in pixels, and per object the ``support`` -- the weight of the particles that hold a box
+of IoU >= ``estimate_iou`` with it -- and their weighted mean box ``box_mean``; with ``estimate_canvas`` the posterior mean
+reconstruction ``mean_canvas`` [T', B, H, W].
+
 The stream takes over its core's handle: while it is open, every inference pass of that handle carries the state.  ``close()``
 hands the handle back.
 
@@ -64,7 +72,8 @@ FORECAST_NOISE_TAG = 1 << 63
 
 class SqairStream(object):
     def __init__(self, core, B, frames_per_step=1, outputs=DEFAULT_OUTPUTS, use_graph=True, seed=0, resample=None, ess_frac=0.5,
-                 state=None, history=None, history_fields=tuple(_capi.HISTORY_FIELDS), missing=False):
+                 state=None, history=None, history_fields=tuple(_capi.HISTORY_FIELDS), missing=False, estimate=False,
+                 estimate_iou=0.5, estimate_canvas=False):
         if core.cfg.sample_from_prior:
             raise ValueError("SqairStream: generation modes (sample_from_prior) do not carry a state across calls")
         if resample not in (None, "systematic"):
@@ -72,6 +81,11 @@ class SqairStream(object):
         ess_frac = float(ess_frac)
         if resample is not None and not 0.0 <= ess_frac <= 1.0:   # (NaN fails too)
             raise ValueError("SqairStream: ess_frac must lie in [0, 1]")
+        estimate_iou = float(estimate_iou)
+        if estimate and not 0.0 < estimate_iou <= 1.0:   # (NaN fails too)
+            raise ValueError("SqairStream: estimate_iou must lie in (0, 1]")
+        if estimate_canvas and not estimate:
+            raise ValueError("SqairStream: estimate_canvas is for a stream with estimate=True")
         self.smc = resample is not None
         self.ess_frac = ess_frac
         self.core = core
@@ -85,6 +99,8 @@ class SqairStream(object):
             outputs = outputs + ("log_weights_per_timestep",)
         if history is not None:   # (checked before the handle is touched; the ring records these outputs of the pass)
             outputs = outputs + tuple(f for f in CarriedState.check_history(history, history_fields, "SqairStream") if f not in outputs)
+        if estimate_canvas and "canvas" not in outputs:   # (mean_canvas averages the pass's canvases)
+            outputs = outputs + ("canvas",)
         self.outputs = outputs
         self.use_graph = bool(use_graph)
         self.seed = int(seed)
@@ -110,6 +126,13 @@ class SqairStream(object):
             self._observed_is_ones = True
             torch.cuda.current_stream(core.device).synchronize()
             core.check(core.lib.sqair_set_observed(core.handle, self._observed.data_ptr(), self.T, self.B), "sqair_set_observed")
+        self.estimate = bool(estimate)
+        if self.estimate:   # after SMC: the estimate's log_w must be the resampler's accumulator
+            self._est = self._estimate_buffers(bool(estimate_canvas))
+            est = _capi.SqairLaneEstimate(iou_min=estimate_iou, log_w=cs.log_weight_sum.data_ptr(),
+                                          **{n: t.data_ptr() for n, t in self._est.items()})
+            torch.cuda.current_stream(core.device).synchronize()
+            core.check(core.lib.sqair_set_estimate(core.handle, C.byref(est), self.T, self.B), "sqair_set_estimate")
         if history is not None:
             ring, nb, bits = cs.set_history(history, history_fields, self.T)
             torch.cuda.current_stream(core.device).synchronize()   # (the ring's zeros are in place before a pass pushes into it)
@@ -131,6 +154,23 @@ class SqairStream(object):
         core.check(core.lib.sqair_set_smc(core.handle, C.byref(smc), self.B), "sqair_set_smc")
         self._smc_uniforms = uniforms
         self._graph = False
+
+    def _estimate_buffers(self, canvas):
+        """The device buffers k_lane_estimate writes (include/sqair_hip.h: SqairLaneEstimate), by field: views of ONE allocation
+        (``_est_flat``), so that a step copies them out with one launch instead of one per field."""
+        core = self.core
+        T, B, K, N = self.T, self.B, self.K, core.N
+        shapes = dict(best_row=(T, B), weights=(T, B, K), ess=(T, B), count_prob=(T, B, N + 1), expected_count=(T, B),
+                      map_count=(T, B), presence=(T, B, N), obj_id=(T, B, N), where=(T, B, N, 4), what=(T, B, N, core.nw),
+                      box=(T, B, N, 4), support=(T, B, N), box_mean=(T, B, N, 4))
+        if canvas:
+            shapes["mean_canvas"] = (T, B, core.H, core.W)
+        sizes = {n: int(np.prod(shp)) for n, shp in shapes.items()}
+        offs = dict(zip(sizes, np.cumsum([0] + [(s + 3) // 4 * 4 for s in sizes.values()]).tolist()))   # (16-byte aligned fields)
+        self._est_flat = torch.zeros(offs[list(sizes)[-1]] + sizes[list(sizes)[-1]], dtype=torch.float32, device=core.device)
+        self._est_views = lambda flat: {n: (flat[offs[n]:offs[n] + sizes[n]].view(torch.int32) if n in _capi.ESTIMATE_INT_FIELDS
+                                            else flat[offs[n]:offs[n] + sizes[n]]).view(shapes[n]) for n in shapes}
+        return self._est_views(self._est_flat)
 
     # ---- source map -------------------------------------------------------------------------------------------------------
     def reset(self, lanes):
@@ -157,7 +197,8 @@ class SqairStream(object):
         and ``ancestors`` [B*K] (the next step's source map), device copies taken before anything is read on the host;
         ``uniforms`` [B] in [0, 1): this step's systematic-resampling uniforms (default: Philox).  ``observed`` (streams with
         ``missing=True``): bool [T', B], or [B] when T' = 1, False = the lane has no frame and coasts on the prior; its frame is
-        replaced by zeros, so it may hold anything, NaN included.  Default: every lane observed.  Returned among the outputs."""
+        replaced by zeros, so it may hold anything, NaN included.  Default: every lane observed.  Returned among the outputs.
+        Streams with ``estimate=True`` add ``lane``: the per-lane answer {name: [T', B, ...]} of this step's rows."""
         observed = self._check_observed(observed)   # (before the core is touched)
         core, cs = self.core, self.carried
         frames, noise, uniforms = cs.check_inputs(self.T, frames, noise, uniforms, "stream")
@@ -190,6 +231,8 @@ class SqairStream(object):
                 out = {k: core.out[k].clone() for k in self.outputs}
                 if self.missing:
                     out["observed"] = self._every_lane if observed is None else observed
+                if self.estimate:
+                    out["lane"] = self._est_views(self._est_flat.clone())
                 if self.smc:   # (log_weight_sum is the resampler's accumulator)
                     out.update(ess=cs.ess.clone(), resampled=cs.resampled.clone(), log_evidence=cs.log_evidence.clone(),
                                ancestors=cs._src.clone())
@@ -337,10 +380,12 @@ class SqairStream(object):
         return dict(src=z(R, i32), log_w=z(R), out={n: z(*sd) for n, sd in shapes.items()})
 
     def close(self):
-        """Switches the history and the carried state off on the core's handle (its passes start from the initial state again)."""
+        """Switches the estimate, the history and the carried state off on the core's handle (its passes start from the initial
+        state again)."""
         core = self.core
         if core.handle:
             core.stream.synchronize()
+            core.check(core.lib.sqair_set_estimate(core.handle, None, 0, 0), "sqair_set_estimate")
             core.check(core.lib.sqair_set_history(core.handle, None, 0, 0, 0), "sqair_set_history")
             core.check(core.lib.sqair_set_state(core.handle, None, None, None, 0, 0), "sqair_set_state")
             core._graph_ready = False

@@ -25,6 +25,13 @@ no lane observed -- and SMC on, for the yardstick: the same run's SMC on - SMC o
 that day, and a one-frame pass with a mask has two nodes more.  The ratio is recorded, not gated on:
 
     python tools/stream_time.py --missing [--out profiles/stream_missing_time.json]
+
+With --estimate: the price of the lane estimate (SqairStream(estimate=True), include/sqair_hip.h: sqair_set_estimate).  Streams at
+cfg-2's batch alternating in one process as with --history: plain, SMC, estimate, SMC + estimate, estimate with the posterior mean
+reconstruction.  The estimate is one dependent node; the yardstick is the same run's SMC on - SMC off difference, the resampler's
+node that day.  The ratio is recorded, not gated on:
+
+    python tools/stream_time.py --estimate [--out profiles/stream_estimate_time.json]
 """
 import argparse
 import json
@@ -180,6 +187,23 @@ def time_missing(B, K, N, steps, warmup, rounds=10, hw=(50, 50)):
     return res
 
 
+def time_estimate(B, K, N, steps, warmup, rounds=10, hw=(50, 50)):
+    smc = dict(resample="systematic", ess_frac=0.5)
+    legs = dict(plain={}, smc=smc, estimate=dict(estimate=True), smc_estimate=dict(estimate=True, **smc),
+                canvas=dict(outputs=("what", "where", "presence", "obj_id", "log_weights_per_timestep", "canvas")),
+                estimate_canvas=dict(estimate=True, estimate_canvas=True))
+    streams, res, med, thr = alternating_streams(legs, B, K, N, steps, warmup, rounds, hw)
+    for key, v in (("latency", med), ("back_to_back", thr)):
+        one_node = v["smc"] - v["plain"]            # the yardstick: one dependent node (the resampler) on this machine, this run
+        added = dict(estimate_node_on_plain=v["estimate"] - v["plain"], estimate_node_on_smc=v["smc_estimate"] - v["smc"],
+                     estimate_canvas_on_canvas=v["estimate_canvas"] - v["canvas"])   # (both legs copy the canvases out)
+        res["us_" + key] = dict(smc_node=1e3 * one_node, **{n: 1e3 * a for n, a in added.items()},
+                                **{n + "_over_smc_node": (a / one_node if one_node > 0 else None) for n, a in added.items()})
+    for st in streams.values():
+        st.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=500)
@@ -188,10 +212,13 @@ def main():
     ap.add_argument("--smc", action="store_true", help="SMC resampling off / ess_frac 0.5 / 1.0 (profiles/stream_time_smc.json)")
     ap.add_argument("--history", action="store_true", help="plain / SMC / history / SMC + history, alternating (profiles/stream_history_time.json)")
     ap.add_argument("--missing", action="store_true", help="plain / SMC / a mask with every lane / with no lane observed, alternating (profiles/stream_missing_time.json)")
+    ap.add_argument("--estimate", action="store_true", help="plain / SMC / estimate / SMC + estimate / with mean_canvas, alternating (profiles/stream_estimate_time.json)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     ov, _, _, _ = config_inputs(2)
-    if args.missing:
+    if args.estimate:
+        shapes = [dict(name="cfg2_batch_estimate", **time_estimate(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
+    elif args.missing:
         shapes = [dict(name="cfg2_batch_missing", **time_missing(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
     elif args.history:
         shapes = [dict(name="cfg2_batch_history", **time_history(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
