@@ -354,6 +354,77 @@ int sqair_forecast(SqairHandle* h, const float* flat_params, const void* packed,
                    int F, int B, const int32_t* src_rows /*NULL: the map of sqair_set_state*/,
                    const SqairForecastOutputs* out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- object forecasts: fanned-out rollouts and one predictive answer per object of a lane -------------------------------------
+ * sqair_forecast draws ONE rollout per particle row and answers per row; with K = 1 the predictive "distribution" is a single draw.
+ * sqair_forecast_fan rolls every particle row forward S times inside one call, and, with `lane` set, turns the K*S rollouts of a
+ * lane into one answer per object of the lane: predicted box, spread and survival mass per horizon, and the predictive count
+ * distribution -- formed on the device, no host round trip, capturable like sqair_forecast, and with its promise: nothing but `out`,
+ * `lane` and the workspace is written.  sqair_forecast is the S = 1, lane = NULL case of the same code and keeps its bits.
+ * Fan-out.  R = B*K.  Rollout row q = r*S + s (r = b*K + k, s = 0..S-1) starts from exactly the row sqair_forecast starts row r
+ *   from: the blob through src_rows[r] (the registered map when NULL); -1 or an index outside [0, R) gives the fresh initial state
+ *   (the map is expanded into the workspace, src_fan[q] = src[q / S], the range rule applied against the blob's R).
+ *   noise is [F, R*S, 2, N, nzw]; the per-row outputs of SqairForecastOutputs are read with B' = R*S; out->log_w stays [R];
+ *   mean_canvas / expected_count stay [F, B, ...]: row q carries weight w_k / S (w = the lane's softmax as in sqair_forecast, the
+ *   division in fp32), the sums run over the lane's K*S rows q in index order.
+ * Lane forecast (SqairForecastLane; every pointer optional except best_row).  Per lane b:
+ * 1. Weights and best row: sqair_set_estimate's points 1-2 on out->log_w alone (no per-frame terms; NULL: uniform), the same device
+ *    helpers: weights[b,k] = w_k, best_row[b] = b*K + the first k of maximal log weight.
+ * 2. start_where / start_presence / start_obj_id [R,N,.]: the frame-0 (imported) records of every particle row, 32-bit words
+ *    copied.  The lane's objects are the best START row's slots j: presence, obj_id [B,N] copied words, box0 [B,N,4] = (y, x, h, w)
+ *    in pixels as sqair_set_estimate's point 4; zero where the slot is absent.  A fresh best row has no present slot: no objects.
+ * 3. Association, ONCE, on the start rows, by sqair_set_estimate's point 5: per object j and particle k, m* = the first present
+ *    slot of k's start row of maximal IoU with box0[j]; k is associated with j when that IoU >= iou_min (not one-to-one).
+ *    support[b,j] = sum_k w_k [k associated].  The obj_id word of slot m* is the id FOLLOWED in each of particle k's S rollouts: a
+ *    forecast discovers nothing, so a survivor keeps its id while compaction moves it between slots.
+ * 4. Per frame f and object j, over the rollouts q = (k, s) of the lane with k associated and a present slot of frame f whose obj_id
+ *    word equals the followed id (an exact compare; the first such slot), weight w_q = w_k / S:
+ *      alive[f,b,j]    = sum w_q                              (unnormalised: <= support, non-increasing in f)
+ *      box_mean[f,b,j] = sum w_q box_q / alive                (box_q: the pixel box of that slot)
+ *      box_std[f,b,j]  = sqrt(sum w_q (box_q - box_mean)^2 / alive)     (two passes in fp32: the mean first)
+ *    Where alive is 0 the box statistics are NaN (0 / 0: nothing to average, and the value stays visible).  An absent best-row slot
+ *    gives zeros in support, alive, box_mean, box_std.
+ * 5. count_prob[f,b,c] = sum_q w_q [rollout q holds c present slots at frame f], c = 0..N.
+ * 6. Every sum over rollouts is ONE thread's loop over q in index order (over k for support): fixed by (K, S) alone, no float
+ *    atomics, the same bits eager or replayed from a graph.
+ * 7. Non-finite lanes, sqair_set_estimate's point 7: a NaN or +inf log weight, or all of them -inf, gives NaN weights, support,
+ *    alive, box_mean, box_std and count_prob, best_row = -1 and no objects (presence, obj_id, box0 zero).
+ * Refused (return -1, text in sqair_last_error, before any HIP call): everything sqair_forecast refuses; S < 1; K*S >
+ * SQAIR_FORECAST_FAN_MAX (the rollouts of a lane are staged in LDS, one 16-byte box each); R*S*N beyond int32; workspace_bytes <
+ * sqair_forecast_fan_workspace_bytes(h, F, B, S) (>= sqair_forecast_workspace_bytes(h, F, B) at S = 1); with lane set: iou_min NaN or
+ * outside (0, 1], a NULL best_row. */
+#define SQAIR_FORECAST_FAN_MAX 1024
+typedef struct SqairForecastLane {
+  float iou_min;             /* in (0, 1] */
+  int32_t* best_row;         /* [B] required */
+  float* weights;            /* [B,K] */
+  float* start_where;        /* [R,N,4] */
+  float* start_presence;     /* [R,N] */
+  float* start_obj_id;       /* [R,N] */
+  float* obj_id;             /* [B,N] */
+  float* presence;           /* [B,N] */
+  float* box0;               /* [B,N,4] (y, x, h, w) in pixels */
+  float* support;            /* [B,N] */
+  float* alive;              /* [F,B,N] */
+  float* box_mean;           /* [F,B,N,4] */
+  float* box_std;            /* [F,B,N,4] */
+  float* count_prob;         /* [F,B,N+1] */
+} SqairForecastLane;
+int64_t sqair_forecast_fan_workspace_bytes(const SqairHandle* h, int F, int B, int S);
+int sqair_forecast_fan(SqairHandle* h, const float* flat_params, const void* packed, const float* noise /*[F,R*S,2,N,nzw]*/,
+                       int F, int B, int S, const int32_t* src_rows /*[R] or NULL: the map of sqair_set_state*/,
+                       const SqairForecastOutputs* out, const SqairForecastLane* lane /*NULL: none*/, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+/* Kernel-level check of the lane forecast (tests): the same kernels on caller tensors, no state and no forecast, any K in 1..256 and
+ * S with K*S <= SQAIR_FORECAST_FAN_MAX, the handle's N, H, W.  start_where [B*K,N,4], start_presence, start_obj_id [B*K,N]: the start
+ * rows; where [F,B*K*S,N,4], presence, obj_id [F,B*K*S,N]: the rollouts; log_w [B*K] or NULL.  scratch: device memory of
+ * sqair_forecast_lane_scratch_bytes(h, B, K) bytes (the weights, the association and the followed ids between the two launches).
+ * Refused (return -1, before any HIP call): a NULL start_* / where / presence / obj_id / lane / scratch, F, B, K or S out of range,
+ * what lane refuses, scratch_bytes too small. */
+int64_t sqair_forecast_lane_scratch_bytes(const SqairHandle* h, int B, int K);
+int sqair_forecast_lane_test(SqairHandle* h, const float* start_where, const float* start_presence, const float* start_obj_id,
+                             const float* where, const float* presence, const float* obj_id, const float* log_w, int F, int B, int K,
+                             int S, const SqairForecastLane* lane, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ---- missing-frame steps: unobserved lanes coast on the prior, inside the pass ------------------------------------------------
  * Cameras drop frames, lanes of a batch run at different rates, an object passes behind an occluder the caller knows about.  With
  * a mask set, every following inference pass with a carried state reads observed[T, B] (device int32, nonzero = the lane has a

@@ -64,6 +64,27 @@ class SqairForecastOutputs(C.Structure):
                                           "log_w", "mean_canvas", "expected_count")]
 
 
+# object forecasts (include/sqair_hip.h: sqair_forecast_fan): the outputs of SqairForecastLane in declaration order, with their shapes
+# in terms of F, B, K, N (R = B * K)
+FORECAST_LANE_FIELDS = ("best_row", "weights", "start_where", "start_presence", "start_obj_id", "obj_id", "presence", "box0", "support",
+                        "alive", "box_mean", "box_std", "count_prob")
+FORECAST_LANE_INT_FIELDS = ("best_row",)
+FORECAST_FAN_MAX = 1024
+
+
+def forecast_lane_shapes(F, B, K, N):
+    R = B * K
+    return dict(best_row=(B,), weights=(B, K), start_where=(R, N, 4), start_presence=(R, N), start_obj_id=(R, N), obj_id=(B, N),
+                presence=(B, N), box0=(B, N, 4), support=(B, N), alive=(F, B, N), box_mean=(F, B, N, 4), box_std=(F, B, N, 4),
+                count_prob=(F, B, N + 1))
+
+
+class SqairForecastLane(C.Structure):
+    """One predictive answer per object of a lane from its K * S rollouts (include/sqair_hip.h: sqair_forecast_fan); every pointer is
+    a device address, all but best_row optional."""
+    _fields_ = [("iou_min", C.c_float)] + [(n, C.c_void_p) for n in FORECAST_LANE_FIELDS]
+
+
 # lane estimates (include/sqair_hip.h: sqair_set_estimate): the outputs of SqairLaneEstimate in declaration order; the two int32 ones
 ESTIMATE_FIELDS = ("best_row", "weights", "ess", "count_prob", "expected_count", "map_count", "presence", "obj_id", "where", "what",
                    "box", "support", "box_mean", "mean_canvas")
@@ -173,6 +194,12 @@ _PROTOS = {
     "sqair_forecast_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
     "sqair_forecast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                  C.POINTER(SqairForecastOutputs), C.c_void_p, C.c_int64, C.c_void_p]),
+    "sqair_forecast_fan_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "sqair_forecast_fan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                     C.POINTER(SqairForecastOutputs), C.POINTER(SqairForecastLane), C.c_void_p, C.c_int64, C.c_void_p]),
+    "sqair_forecast_lane_scratch_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
+    "sqair_forecast_lane_test": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 4 + [C.POINTER(SqairForecastLane), C.c_void_p, C.c_int64,
+                                                                              C.c_void_p]),
     "sqair_fill_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]),
     "sqair_capture_begin": (C.c_int, [C.c_void_p, C.c_void_p]),
     "sqair_capture_end": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),

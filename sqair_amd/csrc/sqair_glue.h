@@ -405,6 +405,49 @@ struct LaneEstArgs {
 };
 int sq_launch_lane_estimate(const LaneEstArgs& a, hipStream_t s);
 
+// Object forecasts (sqair_forecast_fan; include/sqair_hip.h states the semantics).  Fan-out: rollout row q = r * S + s.
+// k_forecast_fan_src expands the source map, src_fan[q] = src[q / S] (NULL: q / S), an index outside [0, R) of the blob -> -1.
+int sq_launch_forecast_fan_src(const int* src, int* src_fan, int R, int S, hipStream_t s);
+// k_forecast_summary for S rollouts per particle: the lane's K*S rows in index order, row q weighing w_{q / S} / S.
+struct ForecastFanSummaryArgs {
+  const float* canvas;                 // [F][R*S][H*W]
+  const float* rec;                    // records of frames 0..F-1 [F][R*S][N][rec::W]
+  const float* log_w;                  // [R] or NULL
+  float* mean_canvas;                  // [F][B][H*W] or NULL
+  float* expected_count;               // [F][B] or NULL
+  int F, B, K, S, N, P;
+};
+int sq_launch_forecast_fan_summary(const ForecastFanSummaryArgs& a, hipStream_t s);
+// The lane forecast: k_forecast_lane_start, one workgroup per lane (weights, best start row, its objects, the K x N association and
+// the followed ids, left in `scratch`), then k_forecast_lane_frame, one workgroup per (lane, frame), thread = rollout.  Start row r
+// is read at base + ((r * row_step) * N + j) * ld -- frame 0 of the forecast's records (row_step = S, every ld = rec::W) or the
+// caller's tensors (row_step = 1, ld = 4, 1, 1); slot j of (frame f, rollout row q) at base + (((f * R * S) + q) * N + j) * ld.
+inline int64_t sq_al64(int64_t x) { return (x + 63) / 64 * 64; }
+struct ForecastLaneScratch { float* w; unsigned* fid; int* fm; int* bp; };   // [R], [R][N], [R][N], [B][N]
+inline int64_t sq_forecast_lane_scratch_words(int64_t B, int64_t K, int64_t N) { return sq_al64(B * K) + 2 * sq_al64(B * K * N) + sq_al64(B * N); }
+inline ForecastLaneScratch sq_forecast_lane_scratch(float* base, int64_t B, int64_t K, int64_t N) {
+  ForecastLaneScratch x;
+  x.w = base; base += sq_al64(B * K);
+  x.fid = (unsigned*)base; base += sq_al64(B * K * N);
+  x.fm = (int*)base; base += sq_al64(B * K * N);
+  x.bp = (int*)base;
+  return x;
+}
+struct ForecastLaneArgs {
+  const float* s_where; int s_where_ld;
+  const float* s_pres; int s_pres_ld;
+  const float* s_id; int s_id_ld;
+  int row_step;
+  const float* where; int where_ld;
+  const float* presence; int pres_ld;
+  const float* obj_id; int id_ld;
+  const float* log_w;                  // [R] or NULL
+  ForecastLaneScratch x;
+  SqairForecastLane lane;              // iou_min and the outputs
+  int F, B, K, S, N, H, W;
+};
+int sq_launch_forecast_lane(const ForecastLaneArgs& a, hipStream_t s);
+
 struct CompactArgs {
   const float* rec_p; const float* rec_d; const float* rec_prev;
   const float* temporal_p; const float* prior_p;

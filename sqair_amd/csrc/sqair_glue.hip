@@ -2583,3 +2583,266 @@ int sq_launch_lane_estimate(const LaneEstArgs& a, hipStream_t s) {
   else SQ_LAUNCH(k_lane_estimate<false>, dim3(a.B, a.T, nz), dim3(256), 0, s, a);
   return 0;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Object forecasts (sqair_forecast_fan; include/sqair_hip.h states the semantics; the argument blocks: sqair_glue.h).  Defined after
+// every other kernel of this code object: none of the kernels a pass runs moves.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_forecast_fan_src(const int* __restrict__ src, int* __restrict__ src_fan, const int R, const int S SQ_TLP) {
+  SQ_TL_SCOPE;
+  const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (q >= (long long)R * S) return;
+  const int r = (int)(q / S);
+  int sr = src != nullptr ? src[r] : r;
+  if (sr < 0 || sr >= R) sr = -1;   // (the import's range rule against the blob's R: the fanned-out import never reads outside it)
+  src_fan[q] = sr;
+}
+int sq_launch_forecast_fan_src(const int* src, int* src_fan, int R, int S, hipStream_t s) {
+  const long long n = (long long)R * S;
+  SQ_LAUNCH(k_forecast_fan_src, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, src_fan, R, S);
+  return 0;
+}
+// k_forecast_summary over S rollouts per particle: workgroup (b, f).  The lane's weights by the same helpers, then expanded to one
+// weight per rollout row, w_q = w_{q / S} / S, so that both sums are the loops of k_forecast_summary over the lane's K*S rows.
+__global__ __launch_bounds__(256) void k_forecast_fan_summary(const ForecastFanSummaryArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ float s_k[SQ_MAX_K];
+  __shared__ float s_w[SQAIR_FORECAST_FAN_MAX];
+  __shared__ float s_m;
+  const int b = blockIdx.x, f = blockIdx.y, tid = threadIdx.x, K = a.K, S = a.S, N = a.N, P = a.P, KS = K * S;
+  const size_t row0 = ((size_t)f * a.B + b) * KS;   // (frame f, rollout 0 of lane b)
+  if (tid < K) s_k[tid] = sq_lane_log_weight<true>(a.log_w, nullptr, 0, a.B * K, b * K + tid);
+  __syncthreads();
+  if (tid == 0) s_m = sq_lane_max(s_k, K);
+  __syncthreads();
+  if (tid < K) s_k[tid] = sq_lane_exp(s_k[tid], s_m);
+  __syncthreads();
+  if (tid == 0) {
+    float Sum, Q;
+    sq_lane_sums<false>(s_k, K, Sum, Q);
+    for (int k = 0; k < K; ++k) s_k[k] = s_k[k] / Sum;
+  }
+  __syncthreads();
+  for (int q = tid; q < KS; q += 256) s_w[q] = s_k[q / S] / (float)S;
+  __syncthreads();
+  if (tid == 0 && a.expected_count) {
+    float cnt = 0.0f;
+    for (int q = 0; q < KS; ++q) {
+      float n = 0.0f;
+      for (int j = 0; j < N; ++j) n += a.rec[((row0 + q) * N + j) * rec::W + rec::PRES];
+      cnt += s_w[q] * n;
+    }
+    a.expected_count[(size_t)f * a.B + b] = cnt;
+  }
+  if (!a.mean_canvas) return;
+  for (int p = tid; p < P; p += 256) a.mean_canvas[((size_t)f * a.B + b) * P + p] = sq_lane_mean_pixel(s_w, a.canvas, row0, P, p, KS);
+}
+int sq_launch_forecast_fan_summary(const ForecastFanSummaryArgs& a, hipStream_t s) {
+  SQ_LAUNCH(k_forecast_fan_summary, dim3(a.B, a.F), dim3(256), 0, s, a);
+  return 0;
+}
+
+// k_forecast_lane_start: workgroup = lane b.  The weights and the best row as k_lane_estimate forms them (the same helpers), the best
+// START row's objects and boxes, then thread k < K associates its particle's start row with them -- k_lane_estimate's rule, its
+// per-object registers statically indexed over the build's slot limit -- and leaves in the scratch, per (k, j), whether k is
+// associated and the obj_id word its rollouts are followed by.
+__global__ __launch_bounds__(256) void k_forecast_lane_start(const ForecastLaneArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ float s_a[SQ_MAX_K];        // a_k
+  __shared__ float s_w[SQ_MAX_K];        // e_k, then w_k
+  __shared__ unsigned char s_match[SQ_MAX_K * SQ_MAXN];
+  __shared__ SqBox s_bbox[SQ_MAXN];      // the best start row's boxes
+  __shared__ int s_bp[SQ_MAXN];          // ... and which of its slots are present
+  __shared__ float s_st[2];              // m, S
+  __shared__ int s_best;
+  const SqairForecastLane& o = a.lane;
+  const int b = blockIdx.x, tid = threadIdx.x, K = a.K, N = a.N, R = a.B * K, r = b * K + tid;
+  const float nan = __builtin_nanf("");
+  auto word = [](const float* p) { return *reinterpret_cast<const unsigned*>(p); };
+  auto put = [](float* p, unsigned v) { *reinterpret_cast<unsigned*>(p) = v; };
+  // ---- 1: weights and the best row
+  float acc = 0.0f;
+  if (tid < K) {
+    acc = sq_lane_log_weight<true>(a.log_w, nullptr, 0, R, r);
+    s_a[tid] = acc;
+  }
+  if (tid == 0) s_best = K;
+  __syncthreads();
+  if (tid == 0) s_st[0] = sq_lane_max(s_a, K);
+  __syncthreads();
+  if (tid < K) {
+    s_w[tid] = sq_lane_exp(acc, s_st[0]);
+    if (acc == s_st[0]) atomicMin(&s_best, tid);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float S, Q;
+    sq_lane_sums<false>(s_w, K, S, Q);
+    s_st[1] = S;
+    if (!isfinite(S)) s_best = -1;
+    o.best_row[b] = isfinite(S) ? b * K + s_best : -1;
+  }
+  __syncthreads();
+  const bool bad = s_best < 0;   // a non-finite lane: NaN weights, no objects
+  if (tid < K) {
+    const float w = s_w[tid] / s_st[1];
+    s_w[tid] = w;
+    a.x.w[r] = w;
+    if (o.weights) o.weights[r] = w;
+  }
+  // ---- 2: the start records of the lane's rows (words copied), the best start row's objects and their boxes
+  for (int i = tid; i < K * N; i += 256) {
+    const int k = i / N;
+    const size_t src = ((size_t)(b * K + k) * a.row_step) * N + (i - k * N), dst = (size_t)b * K * N + i;
+    if (o.start_presence) put(o.start_presence + dst, word(a.s_pres + src * a.s_pres_ld));
+    if (o.start_obj_id) put(o.start_obj_id + dst, word(a.s_id + src * a.s_id_ld));
+    if (o.start_where)
+      for (int c = 0; c < 4; ++c) put(o.start_where + dst * 4 + c, word(a.s_where + src * a.s_where_ld + c));
+  }
+  const size_t best0 = ((size_t)(b * K + (bad ? 0 : s_best)) * a.row_step) * N;   // (slot 0 of the best start row)
+  if (tid < N) {
+    const int j = tid;
+    const bool pj = !bad && a.s_pres[(best0 + j) * a.s_pres_ld] != 0.0f;
+    SqBox bx = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (pj) bx = sq_box_of_where(a.s_where + (best0 + j) * a.s_where_ld, a.H, a.W);
+    s_bp[j] = pj;
+    s_bbox[j] = bx;
+    const size_t e = (size_t)b * N + j;
+    a.x.bp[e] = pj;
+    if (o.presence) put(o.presence + e, pj ? word(a.s_pres + (best0 + j) * a.s_pres_ld) : 0u);
+    if (o.obj_id) put(o.obj_id + e, pj ? word(a.s_id + (best0 + j) * a.s_id_ld) : 0u);
+    if (o.box0) {
+      o.box0[e * 4 + 0] = bx.y; o.box0[e * 4 + 1] = bx.x; o.box0[e * 4 + 2] = bx.h; o.box0[e * 4 + 3] = bx.w;
+    }
+  }
+  __syncthreads();
+  // ---- 3: thread k's particle: per best-row object its first present start slot of maximal IoU, and that slot's id word
+  if (tid < K) {
+    float bi[SQ_MAXN];
+    int bm[SQ_MAXN];
+    unsigned bw[SQ_MAXN];
+#pragma unroll
+    for (int j = 0; j < SQ_MAXN; ++j) { bi[j] = -1.0f; bm[j] = 255; bw[j] = 0u; }
+    const size_t k0 = ((size_t)r * a.row_step) * N;
+    for (int m = 0; m < N; ++m) {
+      if (a.s_pres[(k0 + m) * a.s_pres_ld] == 0.0f) continue;
+      const SqBox bx = sq_box_of_where(a.s_where + (k0 + m) * a.s_where_ld, a.H, a.W);
+      const unsigned idw = word(a.s_id + (k0 + m) * a.s_id_ld);
+#pragma unroll
+      for (int j = 0; j < SQ_MAXN; ++j) {
+        if (j < N && s_bp[j]) {
+          const float v = sq_box_iou(s_bbox[j], bx);
+          if (v > bi[j]) { bi[j] = v; bm[j] = m; bw[j] = idw; }
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < SQ_MAXN; ++j)
+      if (j < N) {
+        const bool ok = bi[j] >= o.iou_min;
+        s_match[tid * N + j] = (unsigned char)(ok ? bm[j] : 255);
+        a.x.fm[(size_t)r * N + j] = ok;
+        a.x.fid[(size_t)r * N + j] = ok ? bw[j] : 0u;
+      }
+  }
+  __syncthreads();
+  if (tid < N && o.support) {
+    const int j = tid;
+    float sup = 0.0f;
+    for (int k = 0; k < K; ++k) {
+      if (s_match[k * N + j] == 255) continue;
+      sup += s_w[k];
+    }
+    o.support[(size_t)b * N + j] = s_bp[j] ? sup : (bad ? nan : 0.0f);
+  }
+}
+// k_forecast_lane_frame: workgroup (lane b, frame f), thread = rollout q of the lane (K*S <= SQAIR_FORECAST_FAN_MAX: up to four per
+// thread).  The rollouts' counts give count_prob; per object j each associated rollout looks its followed id up among its present
+// slots and stages that slot's pixel box in LDS (16 bytes per rollout), then threads c < 4 reduce coordinate c in two passes, each
+// ONE thread's loop over q in index order.  No per-thread arrays: nothing to spill.
+__global__ __launch_bounds__(256) void k_forecast_lane_frame(const ForecastLaneArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ float s_w[SQ_MAX_K];                       // w_k / S
+  __shared__ SqBox s_stage[SQAIR_FORECAST_FAN_MAX];     // the box followed in rollout q
+  __shared__ unsigned char s_hit[SQAIR_FORECAST_FAN_MAX];
+  __shared__ unsigned char s_n[SQAIR_FORECAST_FAN_MAX];
+  const SqairForecastLane& o = a.lane;
+  const int b = blockIdx.x, f = blockIdx.y, tid = threadIdx.x, K = a.K, S = a.S, N = a.N, KS = K * S;
+  const size_t fb = (size_t)f * a.B + b, row0 = fb * KS;   // (frame f, rollout 0 of lane b)
+  const bool bad = o.best_row[b] < 0;
+  const float nan = __builtin_nanf("");
+  if (tid < K) s_w[tid] = a.x.w[b * K + tid] / (float)S;
+  for (int q = tid; q < KS; q += 256) {
+    int n = 0;
+    for (int m = 0; m < N; ++m) n += a.presence[((row0 + q) * N + m) * a.pres_ld] != 0.0f ? 1 : 0;
+    s_n[q] = (unsigned char)n;
+  }
+  __syncthreads();
+  if (tid <= N && o.count_prob) {
+    float p = 0.0f;
+    for (int k = 0, q = 0; k < K; ++k) {
+      const float w = s_w[k];
+      for (int s = 0; s < S; ++s, ++q) p += s_n[q] == tid ? w : 0.0f;
+    }
+    o.count_prob[fb * (N + 1) + tid] = bad ? nan : p;
+  }
+  if (!o.alive && !o.box_mean && !o.box_std) return;
+  for (int j = 0; j < N; ++j) {   // (the loop and its branches are uniform over the workgroup)
+    const size_t e = fb * N + j;
+    if (!a.x.bp[b * N + j]) {     // absent: zero (a non-finite lane: NaN)
+      const float v = bad ? nan : 0.0f;
+      if (tid == 0 && o.alive) o.alive[e] = v;
+      if (tid < 4 && o.box_mean) o.box_mean[e * 4 + tid] = v;
+      if (tid < 4 && o.box_std) o.box_std[e * 4 + tid] = v;
+      continue;
+    }
+    for (int q = tid; q < KS; q += 256) {
+      const size_t kj = (size_t)(b * K + q / S) * N + j;
+      int hit = 0;
+      if (a.x.fm[kj]) {
+        const unsigned idw = a.x.fid[kj];
+        for (int m = 0; m < N && !hit; ++m) {
+          const size_t sl = (row0 + q) * N + m;
+          if (a.presence[sl * a.pres_ld] != 0.0f && *reinterpret_cast<const unsigned*>(a.obj_id + sl * a.id_ld) == idw) {
+            s_stage[q] = sq_box_of_where(a.where + sl * a.where_ld, a.H, a.W);
+            hit = 1;
+          }
+        }
+      }
+      s_hit[q] = (unsigned char)hit;
+    }
+    __syncthreads();
+    if (tid < 4) {
+      float al = 0.0f, sum = 0.0f;
+      for (int k = 0, q = 0; k < K; ++k) {
+        const float w = s_w[k];
+        for (int s = 0; s < S; ++s, ++q) {
+          if (!s_hit[q]) continue;
+          const SqBox& bx = s_stage[q];
+          al += w;
+          sum += w * (tid == 0 ? bx.y : tid == 1 ? bx.x : tid == 2 ? bx.h : bx.w);
+        }
+      }
+      const float mean = sum / al;
+      float var = 0.0f;
+      for (int k = 0, q = 0; k < K; ++k) {
+        const float w = s_w[k];
+        for (int s = 0; s < S; ++s, ++q) {
+          if (!s_hit[q]) continue;
+          const SqBox& bx = s_stage[q];
+          const float dv = (tid == 0 ? bx.y : tid == 1 ? bx.x : tid == 2 ? bx.h : bx.w) - mean;
+          var += w * (dv * dv);
+        }
+      }
+      if (tid == 0 && o.alive) o.alive[e] = al;
+      if (o.box_mean) o.box_mean[e * 4 + tid] = mean;
+      if (o.box_std) o.box_std[e * 4 + tid] = sqrtf(var / al);
+    }
+    __syncthreads();
+  }
+}
+int sq_launch_forecast_lane(const ForecastLaneArgs& a, hipStream_t s) {
+  SQ_LAUNCH(k_forecast_lane_start, dim3(a.B), dim3(256), 0, s, a);
+  SQ_LAUNCH(k_forecast_lane_frame, dim3(a.B, a.F), dim3(256), 0, s, a);
+  return 0;
+}

@@ -420,36 +420,79 @@ extern "C" int64_t sqair_forecast_workspace_bytes(const SqairHandle* h, int F, i
   if (!h || F < 1 || B < 1) return -1;
   return fc_carve(h, F, B, nullptr).total * 4;
 }
-extern "C" int sqair_forecast(SqairHandle* h, const float* flat_params, const void* packed_v, const float* noise, int F, int B,
-                              const int32_t* src_rows, const SqairForecastOutputs* outp, void* workspace, int64_t workspace_bytes,
-                              void* stream) {
+// The fan-out's workspace: the forecast's own for B * S lanes' worth of rows (the per-row kernels never look at lane structure),
+// then the expanded source map [R*S] and the lane forecast's scratch.
+static bool fc_fan_fits(const SqairHandle* h, int B, int S) {
+  return S >= 1 && (int64_t)h->cfg.k_particles * S <= SQAIR_FORECAST_FAN_MAX &&
+         (int64_t)B * h->cfg.k_particles * S * h->cfg.n_steps_per_image <= INT32_MAX;
+}
+extern "C" int64_t sqair_forecast_fan_workspace_bytes(const SqairHandle* h, int F, int B, int S) {
+  if (!h || F < 1 || B < 1 || !fc_fan_fits(h, B, S)) return -1;
+  const int64_t K = h->cfg.k_particles, N = h->cfg.n_steps_per_image;
+  return (fc_carve(h, F, B * S, nullptr).total + align64((int64_t)B * K * S) + sq_forecast_lane_scratch_words(B, K, N)) * 4;
+}
+extern "C" int64_t sqair_forecast_lane_scratch_bytes(const SqairHandle* h, int B, int K) {
+  if (!h || B < 1 || K < 1 || K > SQ_MAX_K) return -1;
+  return sq_forecast_lane_scratch_words(B, K, h->cfg.n_steps_per_image) * 4;
+}
+static int sq_forecast_lane_fields(SqairHandle* h, const std::string& who, const SqairForecastLane& l) {
+  if (!(l.iou_min > 0.0f && l.iou_min <= 1.0f)) return sq_no(h, who + "lane->iou_min must lie in (0, 1]");   // (NaN fails both)
+  if (!l.best_row) return sq_no(h, who + "lane->best_row must not be NULL");
+  return 0;
+}
+// sqair_forecast (fan = false: S = 1, no lane, its own workspace size) and sqair_forecast_fan: one body
+static int sq_forecast_impl(SqairHandle* h, const bool fan, const float* flat_params, const void* packed_v, const float* noise, int F,
+                            int B, int S, const int32_t* src_rows, const SqairForecastOutputs* outp, const SqairForecastLane* lane,
+                            void* workspace, int64_t workspace_bytes, void* stream) {
   if (!h) return -1;
   const SqairConfig& c = h->cfg;
-  if (c.sample_from_prior) return sq_no(h, "sqair_forecast: not with sample_from_prior (the forecast is the generation mode, from a carried state)");
-  if (!h->state_on || !h->state_in) return sq_no(h, "sqair_forecast: needs a carried state with state_in (sqair_set_state) to start from");
+  const std::string fn = fan ? "sqair_forecast_fan" : "sqair_forecast", who = fn + ": ";
+  if (c.sample_from_prior) return sq_no(h, who + "not with sample_from_prior (the forecast is the generation mode, from a carried state)");
+  if (!h->state_on || !h->state_in) return sq_no(h, who + "needs a carried state with state_in (sqair_set_state) to start from");
   if (B != h->state_B)
-    return sq_no(h, "sqair_forecast: B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
-  if (F < 1) return sq_no(h, "sqair_forecast: F must be >= 1");
-  if (!noise) return sq_no(h, "sqair_forecast: noise must not be NULL");
-  if (!flat_params || !packed_v || !outp || !workspace) return sq_no(h, "sqair_forecast: null parameters, packed buffer, outputs or workspace");
-  if (workspace_bytes < sqair_forecast_workspace_bytes(h, F, B))
-    return sq_no(h, "sqair_forecast: workspace_bytes " + std::to_string(workspace_bytes) + " < sqair_forecast_workspace_bytes(h, " +
-                    std::to_string(F) + ", " + std::to_string(B) + ") = " + std::to_string(sqair_forecast_workspace_bytes(h, F, B)));
+    return sq_no(h, who + "B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
+  if (F < 1) return sq_no(h, who + "F must be >= 1");
+  if (!noise) return sq_no(h, who + "noise must not be NULL");
+  if (!flat_params || !packed_v || !outp || !workspace) return sq_no(h, who + "null parameters, packed buffer, outputs or workspace");
+  if (fan) {
+    if (S < 1) return sq_no(h, who + "S must be >= 1");
+    if ((int64_t)c.k_particles * S > SQAIR_FORECAST_FAN_MAX)
+      return sq_no(h, who + "K * S = " + std::to_string((int64_t)c.k_particles * S) + " rollouts per lane, above SQAIR_FORECAST_FAN_MAX = " +
+                      std::to_string(SQAIR_FORECAST_FAN_MAX));
+    if (!fc_fan_fits(h, B, S)) return sq_no(h, who + "B * K * S * N slots do not fit int32");
+  }
+  const int64_t need = fan ? sqair_forecast_fan_workspace_bytes(h, F, B, S) : sqair_forecast_workspace_bytes(h, F, B);
+  if (workspace_bytes < need)
+    return sq_no(h, who + "workspace_bytes " + std::to_string(workspace_bytes) + " < " + fn + "_workspace_bytes(h, " +
+                    std::to_string(F) + ", " + std::to_string(B) + (fan ? ", " + std::to_string(S) : std::string()) + ") = " + std::to_string(need));
+  if (lane) {
+    if (sq_forecast_lane_fields(h, who, *lane) != 0) return -1;
+    if (F > 65535) return sq_no(h, who + "with lane set F must be <= 65535");
+  }
   const float* packed = (const float*)packed_v;
   const float* flat = sq_flat(h, flat_params, packed);
   sq_chain_reset(h);
   hipStream_t s = (hipStream_t)stream;
   const SqairForecastOutputs out = *outp;
-  const int nh = c.n_hidden, N = c.n_steps_per_image, K = c.k_particles, R = B * K, M = R * N, RW = rec::W;
+  // R: the rollout rows, q = r * S + s -- B * S lanes' worth of rows to every per-row kernel; only the import map, the summaries
+  // and the lane forecast know the lanes
+  const int nh = c.n_hidden, N = c.n_steps_per_image, K = c.k_particles, R = B * S * K, M = R * N, RW = rec::W;
   const int G2 = c.glimpse_size * c.glimpse_size;
-  const Dims d = make_dims(c, B);
+  const Dims d = make_dims(c, B * S);
   const int psnh = d.psnh;
   const POff po = h->po;
-  const FcWorkspace w = fc_carve(h, F, B, (float*)workspace);
+  const FcWorkspace w = fc_carve(h, F, B * S, (float*)workspace);
+  int* src_fan = (int*)((float*)workspace + w.total);                                  // [R] (fan only)
+  float* lane_scratch = (float*)workspace + w.total + align64((int64_t)R);             // (fan only)
   // prologue: the rows the next pass would start from (the pass's own k_init_state + k_state_import, into this workspace)
   sq_launch_init_state(w.rec, w.temporal, w.prior[0], w.last_id, w.disc_init_rec, w.prop_rnn_init, w.disc_rnn_init, w.rn_init_state,
                        w.w3_prop, w.w3_disc, (int)P(h, "prop.transform.l2.w"), (int)P(h, "disc.transform.l2.w"), flat, po, d, s);
-  const SqStateRes st = {true, h->state_in, nullptr, src_rows ? src_rows : h->state_src, false, false, SqairSmc{}};
+  const int32_t* src = src_rows ? src_rows : h->state_src;
+  if (S > 1) {   // (the map fanned out into the workspace; k_state_import then bounds it against R, which its -1s pass)
+    sq_launch_forecast_fan_src(src, src_fan, B * K, S, s);
+    src = src_fan;
+  }
+  const SqStateRes st = {true, h->state_in, nullptr, src, false, false, SqairSmc{}};
   sq_launch_state_import(sq_state_args(h, st, R, w.rec, w.temporal, w.prior[0], w.last_id, w.t_row, nullptr, 0), s);
   // per frame: the prior cell over all M slots (section A of the pass), then sampling + ids + compaction in one launch
   for (int f = 0; f < F; ++f) {
@@ -463,8 +506,17 @@ extern "C" int sqair_forecast(SqairHandle* h, const float* flat_params, const vo
     fa.f = f; fa.out = out; fa.cfg = c;
     sq_launch_forecast_step(fa, d, s);
   }
-  // decoder of all F frames (section J of the pass without the likelihood): three M = F*B'*N row GEMMs + the canvas-only insert
   const float* rec_all = w.rec + (size_t)M * RW;
+  if (lane) {   // the lane forecast needs only the records: frame 0 = the start rows (S copies of each), frames 1..F the rollouts
+    ForecastLaneArgs la; memset(&la, 0, sizeof(la));
+    la.s_where = w.rec + rec::WHERE; la.s_pres = w.rec + rec::PRES; la.s_id = w.rec + rec::ID;
+    la.where = rec_all + rec::WHERE; la.presence = rec_all + rec::PRES; la.obj_id = rec_all + rec::ID;
+    la.s_where_ld = la.s_pres_ld = la.s_id_ld = la.where_ld = la.pres_ld = la.id_ld = RW;
+    la.row_step = S; la.log_w = out.log_w; la.x = sq_forecast_lane_scratch(lane_scratch, B, K, N); la.lane = *lane;
+    la.F = F; la.B = B; la.K = K; la.S = S; la.N = N; la.H = c.img_h; la.W = c.img_w;
+    sq_launch_forecast_lane(la, s);
+  }
+  // decoder of all F frames (section J of the pass without the likelihood): three M = F*B'*N row GEMMs + the canvas-only insert
   float* canvas = out.canvas ? out.canvas : w.canvas;
   const bool want_canvas = out.canvas || out.mean_canvas;
   if (want_canvas || out.glimpse) {
@@ -481,11 +533,53 @@ extern "C" int sqair_forecast(SqairHandle* h, const float* flat_params, const vo
     }
   }
   if (out.mean_canvas || out.expected_count) {
-    ForecastSummaryArgs sa; memset(&sa, 0, sizeof(sa));
-    sa.canvas = canvas; sa.rec = rec_all; sa.log_w = out.log_w; sa.mean_canvas = out.mean_canvas; sa.expected_count = out.expected_count;
-    sa.F = F;
-    sq_launch_forecast_summary(sa, d, s);
+    if (S == 1) {
+      ForecastSummaryArgs sa; memset(&sa, 0, sizeof(sa));
+      sa.canvas = canvas; sa.rec = rec_all; sa.log_w = out.log_w; sa.mean_canvas = out.mean_canvas; sa.expected_count = out.expected_count;
+      sa.F = F;
+      sq_launch_forecast_summary(sa, d, s);
+    } else {
+      ForecastFanSummaryArgs sa; memset(&sa, 0, sizeof(sa));
+      sa.canvas = canvas; sa.rec = rec_all; sa.log_w = out.log_w; sa.mean_canvas = out.mean_canvas; sa.expected_count = out.expected_count;
+      sa.F = F; sa.B = B; sa.K = K; sa.S = S; sa.N = N; sa.P = c.img_h * c.img_w;
+      sq_launch_forecast_fan_summary(sa, s);
+    }
   }
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+extern "C" int sqair_forecast(SqairHandle* h, const float* flat_params, const void* packed_v, const float* noise, int F, int B,
+                              const int32_t* src_rows, const SqairForecastOutputs* outp, void* workspace, int64_t workspace_bytes,
+                              void* stream) {
+  return sq_forecast_impl(h, false, flat_params, packed_v, noise, F, B, 1, src_rows, outp, nullptr, workspace, workspace_bytes, stream);
+}
+extern "C" int sqair_forecast_fan(SqairHandle* h, const float* flat_params, const void* packed_v, const float* noise, int F, int B, int S,
+                                  const int32_t* src_rows, const SqairForecastOutputs* outp, const SqairForecastLane* lane,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+  return sq_forecast_impl(h, true, flat_params, packed_v, noise, F, B, S, src_rows, outp, lane, workspace, workspace_bytes, stream);
+}
+// kernel-level check of the lane forecast (tests/test_forecast_lane_kernel.py): the two kernels on caller tensors, K and S given
+extern "C" int sqair_forecast_lane_test(SqairHandle* h, const float* start_where, const float* start_presence, const float* start_obj_id,
+                                        const float* where, const float* presence, const float* obj_id, const float* log_w, int F, int B,
+                                        int K, int S, const SqairForecastLane* lane, void* scratch, int64_t scratch_bytes, void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_forecast_lane_test: ";
+  const SqairConfig& c = h->cfg;
+  if (!start_where || !start_presence || !start_obj_id || !where || !presence || !obj_id || !lane || !scratch)
+    return sq_no(h, who + "null start_where / start_presence / start_obj_id / where / presence / obj_id / lane / scratch");
+  if (F < 1 || F > 65535 || B < 1 || K < 1 || K > SQ_MAX_K || S < 1 || (int64_t)K * S > SQAIR_FORECAST_FAN_MAX ||
+      (int64_t)B * K * S * c.n_steps_per_image > INT32_MAX)
+    return sq_no(h, who + "bad F / B / K / S (1 <= K <= " + std::to_string(SQ_MAX_K) + ", K * S <= " + std::to_string(SQAIR_FORECAST_FAN_MAX) + ")");
+  if (sq_forecast_lane_fields(h, who, *lane) != 0) return -1;
+  if (scratch_bytes < sqair_forecast_lane_scratch_bytes(h, B, K))
+    return sq_no(h, who + "scratch_bytes " + std::to_string(scratch_bytes) + " < sqair_forecast_lane_scratch_bytes(h, " + std::to_string(B) +
+                    ", " + std::to_string(K) + ") = " + std::to_string(sqair_forecast_lane_scratch_bytes(h, B, K)));
+  ForecastLaneArgs la; memset(&la, 0, sizeof(la));
+  la.s_where = start_where; la.s_pres = start_presence; la.s_id = start_obj_id; la.where = where; la.presence = presence; la.obj_id = obj_id;
+  la.s_where_ld = la.where_ld = 4; la.s_pres_ld = la.s_id_ld = la.pres_ld = la.id_ld = 1;
+  la.row_step = 1; la.log_w = log_w; la.x = sq_forecast_lane_scratch((float*)scratch, B, K, c.n_steps_per_image); la.lane = *lane;
+  la.F = F; la.B = B; la.K = K; la.S = S; la.N = c.n_steps_per_image; la.H = c.img_h; la.W = c.img_w;
+  sq_launch_forecast_lane(la, (hipStream_t)stream);
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }

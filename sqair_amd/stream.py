@@ -112,7 +112,7 @@ class SqairStream(object):
             cs.adopt(state)
         self._graph = False
         self._tr = {}               # tracks() buffers of the LAST (lag, start, max_tracks, table) only
-        self._fc = {}               # forecast buffers of the LAST (F, outputs, summaries) only: workspace, noise, map, weights, outputs
+        self._fc = {}               # forecast buffers of the LAST (F, outputs, summaries, samples, lane) only: workspace, noise, map, weights, outputs
         self._smc_uniforms = None   # registered with the caller's uniforms (True) or Philox (False)
         core.stream.synchronize()
         core.check(core.lib.sqair_set_state(core.handle, cs.state.data_ptr(), cs.state.data_ptr(), cs._src.data_ptr(),
@@ -243,7 +243,7 @@ class SqairStream(object):
         return out
 
     # ---- forecasting ------------------------------------------------------------------------------------------------------
-    def forecast(self, F, noise=None, seed=None, outputs=FORECAST_OUTPUTS, summaries=True):
+    def forecast(self, F, noise=None, seed=None, outputs=FORECAST_OUTPUTS, summaries=True, samples=1, lane=False, lane_iou=0.5):
         """Rolls the generative prior F frames forward from the rows the next ``step()`` would start from -- the state blob through
         the pending source map (a reset or resample armed since the last step, else identity; with SMC the map the resampler
         wrote) -- and returns {name: [F, B*K, ...]} for ``outputs`` (of FORECAST_OUTPUTS).  With ``summaries`` also the lanes'
@@ -252,54 +252,76 @@ class SqairStream(object):
         [F, B*K, 2, N, 4 + n_what + 1] (slot s = 0 is read); default: the library's Philox keyed by (``seed`` or the stream's
         seed, FORECAST_NOISE_TAG | frames consumed), apart from every step's draws.  Copies, valid on the current stream.  Nothing
         the steps read is written.  The stream keeps one set of forecast buffers (workspace, noise, outputs), for the last
-        (F, outputs, summaries) asked for: repeating a shape reuses them, another shape frees them and allocates its own."""
-        F = int(F)
+        (F, outputs, summaries, samples, lane) asked for: repeating a shape reuses them, another shape frees them and allocates its own.
+        ``samples`` = S rolls every particle row forward S times in the one call (include/sqair_hip.h: sqair_forecast_fan): the per-row
+        results become [F, B*K*S, ...], rollout s of row r at r*S + s (``noise`` likewise), each weighing w_k / S in the summaries.
+        ``lane=True`` adds ``lane``: one predictive answer per object of each lane from its K*S rollouts, {name: tensor} for
+        ``best_row`` [B], ``weights`` [B, K], ``start_where`` / ``start_presence`` / ``start_obj_id`` [B*K, N, .] (the rows the rollouts
+        start from), the best start row's objects ``obj_id``, ``presence`` [B, N] and ``box0`` [B, N, 4] (y, x, h, w in pixels),
+        ``support`` [B, N], and per horizon ``alive`` [F, B, N] (the weight of the rollouts in which the object still lives),
+        ``box_mean`` / ``box_std`` [F, B, N, 4] over those rollouts (NaN where none is left) and ``count_prob`` [F, B, N + 1];
+        ``lane_iou``: the association threshold on the start rows, as a stream's ``estimate_iou``."""
+        F, S, lane, lane_iou = int(F), int(samples), bool(lane), float(lane_iou)
         if F < 1:
             raise ValueError("SqairStream.forecast: F must be >= 1")
+        if S < 1 or self.K * S > _capi.FORECAST_FAN_MAX:
+            raise ValueError("SqairStream.forecast: samples must be >= 1 with K * samples <= {}".format(_capi.FORECAST_FAN_MAX))
+        if lane and not 0.0 < lane_iou <= 1.0:   # (NaN fails too)
+            raise ValueError("SqairStream.forecast: lane_iou must lie in (0, 1]")
         outputs = tuple(outputs)
         bad = [n for n in outputs if n not in FORECAST_OUTPUTS]
         if bad:
             raise ValueError("SqairStream.forecast: unknown outputs {} (choose from {})".format(bad, FORECAST_OUTPUTS))
         core, cs = self.core, self.carried
         lib, dev = core.lib, core.device
-        R, N, nzw = self.R, core.N, core.nzw
+        R, N, nzw = self.R * S, core.N, core.nzw
         if noise is not None:
             noise = torch.as_tensor(noise, dtype=torch.float32)
             if noise.numel() != F * R * 2 * N * nzw:
                 raise ValueError("SqairStream.forecast: noise of shape {} given, [{}, {}, 2, {}, {}] expected".format(
                     tuple(noise.shape), F, R, N, nzw))
-        key = (F, outputs, bool(summaries))
+        key = (F, outputs, bool(summaries), S, lane)
         with torch.cuda.device(dev):
             core._join_in()
             with core.on_stream():
                 fc = self._fc.get(key)
                 if fc is None:   # (another shape: the previous buffers are released first -- a growing horizon does not pile up)
                     self._fc.clear()
-                    fc = self._forecast_buffers(F, outputs, summaries)
+                    fc = self._forecast_buffers(F, outputs, summaries, S, lane)
                     self._fc[key] = fc
                 if noise is not None:
                     fc["noise"].copy_(noise.reshape(fc["noise"].shape), non_blocking=True)
                 else:
-                    core.check(lib.sqair_fill_noise(core.handle, fc["noise"].data_ptr(), F, self.B, self.B, 0,
+                    core.check(lib.sqair_fill_noise(core.handle, fc["noise"].data_ptr(), F, self.B * S, self.B * S, 0,
                                                     (self.seed if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF,
                                                     FORECAST_NOISE_TAG | self.frame, core._stream()), "sqair_fill_noise")
                 src, lw = cs.next_rows(fc["src"], fc["log_w"])   # (the map and the weights of the rows the next step starts from)
                 out = fc["out"]
                 c_out = _capi.SqairForecastOutputs(**{n: t.data_ptr() for n, t in out.items()})
-                if summaries:
+                if summaries or lane:
                     c_out.log_w = lw.data_ptr()
-                core.check(lib.sqair_forecast(core.handle, core.flat.data_ptr(), core.packed.data_ptr(), fc["noise"].data_ptr(), F,
-                                              self.B, src.data_ptr(), C.byref(c_out), fc["ws"].data_ptr(), fc["ws"].numel() * 4,
-                                              core._stream()), "sqair_forecast")
+                if S == 1 and not lane:
+                    core.check(lib.sqair_forecast(core.handle, core.flat.data_ptr(), core.packed.data_ptr(), fc["noise"].data_ptr(), F,
+                                                  self.B, src.data_ptr(), C.byref(c_out), fc["ws"].data_ptr(), fc["ws"].numel() * 4,
+                                                  core._stream()), "sqair_forecast")
+                else:
+                    c_lane = None
+                    if lane:
+                        c_lane = C.byref(_capi.SqairForecastLane(iou_min=lane_iou, **{n: t.data_ptr() for n, t in fc["lane"].items()}))
+                    core.check(lib.sqair_forecast_fan(core.handle, core.flat.data_ptr(), core.packed.data_ptr(), fc["noise"].data_ptr(),
+                                                      F, self.B, S, src.data_ptr(), C.byref(c_out), c_lane, fc["ws"].data_ptr(),
+                                                      fc["ws"].numel() * 4, core._stream()), "sqair_forecast_fan")
                 res = {k: v.clone() for k, v in out.items()}
+                if lane:   # (views of one allocation: one copy, not one per field)
+                    res["lane"] = fc["lane_views"](fc["lane_flat"].clone())
                 if summaries:
                     res["weights"] = torch.softmax(lw.reshape(self.B, self.K), -1)
             core._join_out()
         return res
 
-    def _forecast_buffers(self, F, outputs, summaries):
+    def _forecast_buffers(self, F, outputs, summaries, S=1, lane=False):
         core = self.core
-        R, N, B = self.R, core.N, self.B
+        R, N, B = self.R * S, core.N, self.B
         shapes = dict(what=(F, R, N, core.nw), where=(F, R, N, 4), presence=(F, R, N), presence_prob=(F, R, N),
                       presence_logit=(F, R, N), obj_id=(F, R, N), canvas=(F, R, core.H, core.W),
                       glimpse=(F, R, N, core.G, core.G))
@@ -307,11 +329,23 @@ class SqairStream(object):
             shapes.update(mean_canvas=(F, B, core.H, core.W), expected_count=(F, B))
             outputs = outputs + ("mean_canvas", "expected_count")
         z = lambda shp, dt=torch.float32: torch.zeros(shp, dtype=dt, device=core.device)
-        nb = core.lib.sqair_forecast_workspace_bytes(core.handle, F, B)
+        if S == 1 and not lane:
+            nb = core.lib.sqair_forecast_workspace_bytes(core.handle, F, B)
+        else:
+            nb = core.lib.sqair_forecast_fan_workspace_bytes(core.handle, F, B, S)
         if nb < 0:
             raise RuntimeError("sqair_forecast_workspace_bytes failed")
-        return dict(ws=z(nb // 4), noise=z((F, R, 2, N, core.nzw)), src=z(R, torch.int32), log_w=z(R),
-                    out={n: z(shapes[n]) for n in outputs})
+        fc = dict(ws=z(nb // 4), noise=z((F, R, 2, N, core.nzw)), src=z(self.R, torch.int32), log_w=z(self.R),
+                  out={n: z(shapes[n]) for n in outputs})
+        if lane:   # the fields of SqairForecastLane as views of ONE allocation, 16-byte aligned
+            lshapes = _capi.forecast_lane_shapes(F, B, self.K, N)
+            sizes = {n: int(np.prod(shp)) for n, shp in lshapes.items()}
+            offs = dict(zip(sizes, np.cumsum([0] + [(s + 3) // 4 * 4 for s in sizes.values()]).tolist()))
+            fc["lane_flat"] = z(offs[list(sizes)[-1]] + sizes[list(sizes)[-1]])
+            fc["lane_views"] = lambda flat: {n: (flat[offs[n]:offs[n] + sizes[n]].view(torch.int32) if n in _capi.FORECAST_LANE_INT_FIELDS
+                                                 else flat[offs[n]:offs[n] + sizes[n]]).view(lshapes[n]) for n in lshapes}
+            fc["lane"] = fc["lane_views"](fc["lane_flat"])
+        return fc
 
     # ---- track history ----------------------------------------------------------------------------------------------------
     def tracks(self, lag=None, start="next", max_tracks=None, table=True):
