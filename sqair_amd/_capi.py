@@ -91,6 +91,16 @@ ESTIMATE_FIELDS = ("best_row", "weights", "ess", "count_prob", "expected_count",
 ESTIMATE_INT_FIELDS = ("best_row", "map_count")
 
 
+def estimate_shapes(T, B, K, N, nw, canvas_hw=None):
+    """The outputs' shapes for passes of T frames; ``canvas_hw``: (H, W) when mean_canvas is asked for."""
+    shapes = dict(best_row=(T, B), weights=(T, B, K), ess=(T, B), count_prob=(T, B, N + 1), expected_count=(T, B), map_count=(T, B),
+                  presence=(T, B, N), obj_id=(T, B, N), where=(T, B, N, 4), what=(T, B, N, nw), box=(T, B, N, 4), support=(T, B, N),
+                  box_mean=(T, B, N, 4))
+    if canvas_hw is not None:
+        shapes["mean_canvas"] = (T, B) + tuple(canvas_hw)
+    return shapes
+
+
 class SqairLaneEstimate(C.Structure):
     """One answer per lane from its particles (include/sqair_hip.h: sqair_set_estimate); every pointer is a device address, all but
     best_row optional."""

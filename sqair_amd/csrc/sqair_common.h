@@ -117,7 +117,7 @@ void sq_set_error(SqairHandle* h, const std::string& msg);
 int sq_allow_big_lds(const void* kernel, int bytes);
 
 // Philox4x32-10 (Salmon et al., SC'11): counter (c0..c3), key (k0, k1) -> four independent 32-bit words.  The device generator of
-// sqair_fill_noise (sqair_train.hip) and of the SMC resampler's uniforms (k_smc_resample, sqair_glue.hip).
+// sqair_fill_noise (sqair_train.hip) and of the SMC resampler's uniforms (k_smc_resample, sqair_lane.hip).
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
                                               unsigned out[4]) {
 #pragma unroll

@@ -1,4 +1,4 @@
-// Launchers of the non-GEMM kernels (sqair_glue.hip).
+// Launchers of the non-GEMM kernels (sqair_glue.hip; the kernels of the per-lane answers: sqair_lane.hip).
 #pragma once
 #include "sqair_common.h"
 
@@ -375,28 +375,34 @@ struct CoastBwdArgs {
   SqairConfig cfg;
 };
 int sq_launch_coast_step_bwd(const CoastBwdArgs& a, Dims d, hipStream_t s);
-// Predictive summaries of a forecast: one workgroup per (frame, lane b); w = softmax of the lane's K log weights (NULL: uniform),
-// mean_canvas[f][b] = sum_k w_k canvas[f][b*K + k], expected_count[f][b] = sum_k w_k (present slots of particle k).  Every sum over k
-// runs in index order.
+// Predictive summaries of a forecast of S rollouts per particle (rollout row q = r * S + s; S = 1: the plain forecast): one workgroup
+// per (frame, lane b); w = softmax of the lane's K log weights (NULL: uniform), row q weighing w_{q / S} / S;
+// mean_canvas[f][b] = sum_q w_q canvas[f][b*K*S + q], expected_count[f][b] = sum_q w_q (present slots of row q).  Every sum over q runs
+// in index order.
 struct ForecastSummaryArgs {
-  const float* canvas;                 // [F][R][H*W]
-  const float* rec;                    // records of frames 0..F-1 [F][R][N][rec::W]
+  const float* canvas;                 // [F][R*S][H*W]
+  const float* rec;                    // records of frames 0..F-1 [F][R*S][N][rec::W]
   const float* log_w;                  // [R] or NULL
   float* mean_canvas;                  // [F][B][H*W] or NULL
   float* expected_count;               // [F][B] or NULL
-  int F;
+  int F, B, K, S, N, P;
 };
-int sq_launch_forecast_summary(const ForecastSummaryArgs& a, Dims d, hipStream_t s);
+int sq_launch_forecast_summary(const ForecastSummaryArgs& a, hipStream_t s);
 
-// Lane estimates (sqair_set_estimate; include/sqair_hip.h states the semantics): k_lane_estimate, one workgroup per (lane b, frame t)
-// -- times a third grid dimension over pixel chunks when mean_canvas is asked for, each recomputing the weights.  The objects of
-// (frame t, row r, slot j) are read at a base + ((t * R + r) * N + j) * ld: the pass's merged records (every ld = rec::W) or, for the
-// kernel-level entry point, the caller's tensors (ld = 4, 1, 1, n_what).
-constexpr int SQ_EST_PIXELS = 1024;   // pixels of mean_canvas per workgroup of the third grid dimension
-struct LaneEstArgs {
+// The kernels of the per-lane answers (sqair_lane.hip) read the objects of a row through a view: slot j of row r at
+// base + ((r * row_step) * N + j) * ld -- a pass's or a forecast's records (every ld = rec::W) or a caller's tensors (ld = 4, 1, 1).
+struct LaneRows {
   const float* where; int where_ld;
   const float* presence; int pres_ld;
   const float* obj_id; int id_ld;
+  int row_step;
+};
+// Lane estimates (sqair_set_estimate; include/sqair_hip.h states the semantics): k_lane_estimate, one workgroup per (lane b, frame t)
+// -- times a third grid dimension over pixel chunks when mean_canvas is asked for, each recomputing the weights.  `rows`: row
+// t * R + r is row r of frame t (row_step = 1); `what` at what + ((t * R + r) * N + j) * what_ld.
+constexpr int SQ_EST_PIXELS = 1024;   // pixels of mean_canvas per workgroup of the third grid dimension
+struct LaneEstArgs {
+  LaneRows rows;
   const float* what; int what_ld;      // NULL unless est.what is set
   const float* canvas;                 // [T][R][H*W]; NULL unless est.mean_canvas is set
   const float* lw;                     // the pass's log_weights_per_timestep [T][R]
@@ -408,20 +414,10 @@ int sq_launch_lane_estimate(const LaneEstArgs& a, hipStream_t s);
 // Object forecasts (sqair_forecast_fan; include/sqair_hip.h states the semantics).  Fan-out: rollout row q = r * S + s.
 // k_forecast_fan_src expands the source map, src_fan[q] = src[q / S] (NULL: q / S), an index outside [0, R) of the blob -> -1.
 int sq_launch_forecast_fan_src(const int* src, int* src_fan, int R, int S, hipStream_t s);
-// k_forecast_summary for S rollouts per particle: the lane's K*S rows in index order, row q weighing w_{q / S} / S.
-struct ForecastFanSummaryArgs {
-  const float* canvas;                 // [F][R*S][H*W]
-  const float* rec;                    // records of frames 0..F-1 [F][R*S][N][rec::W]
-  const float* log_w;                  // [R] or NULL
-  float* mean_canvas;                  // [F][B][H*W] or NULL
-  float* expected_count;               // [F][B] or NULL
-  int F, B, K, S, N, P;
-};
-int sq_launch_forecast_fan_summary(const ForecastFanSummaryArgs& a, hipStream_t s);
 // The lane forecast: k_forecast_lane_start, one workgroup per lane (weights, best start row, its objects, the K x N association and
 // the followed ids, left in `scratch`), then k_forecast_lane_frame, one workgroup per (lane, frame), thread = rollout.  Start row r
-// is read at base + ((r * row_step) * N + j) * ld -- frame 0 of the forecast's records (row_step = S, every ld = rec::W) or the
-// caller's tensors (row_step = 1, ld = 4, 1, 1); slot j of (frame f, rollout row q) at base + (((f * R * S) + q) * N + j) * ld.
+// is row r of the view `start` -- frame 0 of the forecast's records (row_step = S) or the caller's tensors (row_step = 1); slot j of
+// (frame f, rollout row q) at base + (((f * R * S) + q) * N + j) * ld.
 inline int64_t sq_al64(int64_t x) { return (x + 63) / 64 * 64; }
 struct ForecastLaneScratch { float* w; unsigned* fid; int* fm; int* bp; };   // [R], [R][N], [R][N], [B][N]
 inline int64_t sq_forecast_lane_scratch_words(int64_t B, int64_t K, int64_t N) { return sq_al64(B * K) + 2 * sq_al64(B * K * N) + sq_al64(B * N); }
@@ -434,10 +430,7 @@ inline ForecastLaneScratch sq_forecast_lane_scratch(float* base, int64_t B, int6
   return x;
 }
 struct ForecastLaneArgs {
-  const float* s_where; int s_where_ld;
-  const float* s_pres; int s_pres_ld;
-  const float* s_id; int s_id_ld;
-  int row_step;
+  LaneRows start;
   const float* where; int where_ld;
   const float* presence; int pres_ld;
   const float* obj_id; int id_ld;

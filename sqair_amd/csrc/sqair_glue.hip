@@ -149,113 +149,6 @@ int sq_launch_state_export(const StateArgs& a, hipStream_t s) {
   return 0;
 }
 
-// k_smc_resample (sqair_set_smc; SmcArgs in sqair_glue.h): the last launch of a pass with SMC on, after k_state_export.  Lane b's
-// log weights a_k = log_w + this pass's per-frame log weights (frame order) -> ESS and the evidence, then either a systematic
-// resampling written as the next pass's source map (k_state_import gathers the chosen rows out of the blob k_state_export just
-// wrote) or the identity map with the weights carried on.  Every lane-wide sum (max, S, sum e^2, the prefix c) is one thread's
-// loop in index order: the same bits on every replay, and K <= 256 adds are nothing next to the pass.
-// The weights of a lane's K particles, one statement of each step for the three kernels that form them (k_smc_resample below,
-// k_forecast_summary, k_lane_estimate): a_k accumulated in frame order, m = max a_k, e_k = expf(a_k - m), S = sum e_k and
-// Q = sum e_k^2 as ONE thread's loops in index order, ESS = S^2 / Q.  A NaN or +inf a_k, or every a_k at -inf, makes S non-finite.
-template <bool MAY_BE_NULL>   // log_w == NULL: zeros (the resampler's is never NULL)
-__device__ __forceinline__ float sq_lane_log_weight(const float* log_w, const float* lw, int n_frames, int R, int r) {
-  float acc = MAY_BE_NULL && !log_w ? 0.0f : log_w[r];
-  for (int t = 0; t < n_frames; ++t) acc += lw[(size_t)t * R + r];
-  return acc;
-}
-__device__ __forceinline__ float sq_lane_max(const float* a, int K) {
-  float m = a[0];
-  for (int i = 1; i < K; ++i) m = fmaxf(m, a[i]);
-  return m;
-}
-__device__ __forceinline__ float sq_lane_exp(float a, float m) { return expf(a - m); }
-template <bool PREFIX>   // PREFIX: e_k is replaced by the inclusive prefix sum c_k (the resampler searches it)
-__device__ __forceinline__ void sq_lane_sums(float* e, int K, float& S, float& Q) {
-  float c = 0.0f, q = 0.0f;
-  for (int i = 0; i < K; ++i) {
-    const float v = e[i];
-    c += v;
-    q += v * v;
-    if (PREFIX) e[i] = c;
-  }
-  S = c;
-  Q = q;
-}
-__device__ __forceinline__ float sq_lane_ess(float S, float Q) { return S * S / Q; }
-// sum_k w_k canvas[row0 + k][p], k in index order
-__device__ __forceinline__ float sq_lane_mean_pixel(const float* w, const float* __restrict__ canvas, size_t row0, int P, int p, int K) {
-  float acc = 0.0f;
-  for (int k = 0; k < K; ++k) acc += w[k] * canvas[(row0 + k) * P + p];
-  return acc;
-}
-constexpr unsigned SQ_SMC_PHILOX_TAG = 0x534D4352u;   // ("SMCR") counter word 1: never an element index of sqair_fill_noise
-__global__ __launch_bounds__(256) void k_smc_resample(const SmcArgs a SQ_TLP) {
-  SQ_TL_SCOPE;
-  __shared__ float s_a[SQ_MAX_K];   // a_k
-  __shared__ float s_c[SQ_MAX_K];   // e_k, then the inclusive prefix c_k
-  __shared__ float s_st[3];         // m, S, u
-  __shared__ int s_do;
-  const int b = blockIdx.x, k = threadIdx.x, K = a.K, R = a.B * K, r = b * K + k;
-  float acc = 0.0f;
-  if (k < K) {
-    acc = sq_lane_log_weight<false>(a.log_w, a.lw, a.T, R, r);
-    s_a[k] = acc;
-  }
-  __syncthreads();
-  if (k == 0) s_st[0] = sq_lane_max(s_a, K);
-  __syncthreads();
-  if (k < K) s_c[k] = sq_lane_exp(acc, s_st[0]);
-  __syncthreads();
-  if (k == 0) {
-    const float m = s_st[0];
-    float c, q;
-    sq_lane_sums<true>(s_c, K, c, q);
-    const float ess = sq_lane_ess(c, q), lse = m + logf(c / (float)K);
-    const float lz = a.log_z[b];
-    a.log_evidence[b] = lz + lse;
-    a.ess[b] = ess;
-    // (a NaN or infinite a_k, or every a_k at -inf, gives a non-finite ESS: such a lane never resamples, whatever ess_frac, so
-    //  the identity map and the carried a_k keep the bad values where the caller can see them)
-    const int go = isfinite(ess) && (a.ess_frac == 1.0f || ess < a.ess_frac * (float)K);
-    float u;   // (drawn whether or not the lane resamples: u_out always holds this pass's u)
-    if (a.uniforms != nullptr) {
-      u = a.uniforms[b];
-    } else {
-      const unsigned ctr = (unsigned)(a.t_row[b * K] + a.T);   // (the lane's frame counter after the pass)
-      unsigned w[4];
-      philox4x32_10((unsigned)b, SQ_SMC_PHILOX_TAG, ctr, 0u, (unsigned)a.seed, (unsigned)(a.seed >> 32), w);
-      u = (float)(w[0] >> 8) * (1.0f / 16777216.0f);   // [0, 1), 24 bits
-    }
-    if (a.u_out != nullptr) a.u_out[b] = u;
-    if (go) a.log_z[b] = lz + lse;
-    a.resampled[b] = go;
-    s_st[1] = c; s_st[2] = u; s_do = go;
-  }
-  __syncthreads();
-  if (k >= K) return;
-  if (s_do) {
-    // output k: the smallest i with c_i > (k + u) S / K.  If none (fp32 rounding of (k + u) S / K up to S = c_{K-1}: k = K - 1
-    // and u near 1), the smallest i with c_i >= S, i.e. the last particle of positive weight, never a zero-weight one after it.
-    // The predicate is monotone in i and true at K - 1; below S it is c_i > thr alone.
-    const float thr = ((float)k + s_st[2]) * s_st[1] / (float)K, S = s_st[1];
-    int lo = 0, hi = K - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (s_c[mid] > thr || s_c[mid] >= S) hi = mid;
-      else lo = mid + 1;
-    }
-    a.src[r] = b * K + lo;
-    a.log_w[r] = 0.0f;
-  } else {
-    a.src[r] = r;
-    a.log_w[r] = acc;
-  }
-}
-int sq_launch_smc_resample(const SmcArgs& a, hipStream_t s) {
-  SQ_LAUNCH(k_smc_resample, dim3(a.B), dim3(256), 0, s, a);
-  return 0;
-}
-
 // ------------------------------------------------------------------------------------------------
 // track history (sqair_set_history / sqair_history_trace; the ring's layout: HistLayout in sqair_glue.h)
 // ------------------------------------------------------------------------------------------------
@@ -1679,42 +1572,6 @@ int sq_launch_coast_step_bwd(const CoastBwdArgs& a, Dims d, hipStream_t s) {
   SQ_LAUNCH(k_coast_step_bwd, dim3(d.R, d.N), dim3(64), 0, s, a, d);
   return 0;
 }
-// Predictive summaries (ForecastSummaryArgs): workgroup (b, f).  The lane's log weights become w_k by the lane-weight helpers above
-// (max, sum and divide are thread 0's loops in index order); a NaN or +inf weight, or all of them -inf, makes S -- and so every
-// w_k -- NaN.
-__global__ __launch_bounds__(256) void k_forecast_summary(const ForecastSummaryArgs a, const Dims d SQ_TLP) {
-  SQ_TL_SCOPE;
-  __shared__ float s_w[SQ_MAX_K];
-  __shared__ float s_m;
-  const int b = blockIdx.x, f = blockIdx.y, tid = threadIdx.x, K = d.K, N = d.N, P = d.H * d.W;
-  const size_t row0 = (size_t)f * d.R + (size_t)b * K;   // (frame f, particle 0 of lane b)
-  if (tid < K) s_w[tid] = sq_lane_log_weight<true>(a.log_w, nullptr, 0, d.R, b * K + tid);
-  __syncthreads();
-  if (tid == 0) s_m = sq_lane_max(s_w, K);
-  __syncthreads();
-  if (tid < K) s_w[tid] = sq_lane_exp(s_w[tid], s_m);
-  __syncthreads();
-  if (tid == 0) {
-    float S, Q;
-    sq_lane_sums<false>(s_w, K, S, Q);
-    float cnt = 0.0f;
-    for (int k = 0; k < K; ++k) {
-      const float w = s_w[k] / S;
-      s_w[k] = w;
-      float n = 0.0f;
-      for (int j = 0; j < N; ++j) n += a.rec[((row0 + k) * N + j) * rec::W + rec::PRES];
-      cnt += w * n;
-    }
-    if (a.expected_count) a.expected_count[(size_t)f * d.B + b] = cnt;
-  }
-  __syncthreads();
-  if (!a.mean_canvas) return;
-  for (int p = tid; p < P; p += 256) a.mean_canvas[((size_t)f * d.B + b) * P + p] = sq_lane_mean_pixel(s_w, a.canvas, row0, P, p, K);
-}
-int sq_launch_forecast_summary(const ForecastSummaryArgs& a, Dims d, hipStream_t s) {
-  SQ_LAUNCH(k_forecast_summary, dim3(d.B, a.F), dim3(256), 0, s, a, d);
-  return 0;
-}
 
 // ------------------------------------------------------------------------------------------------
 // Slot compaction (reference: SQAIRTimestep._choose_latents sqair/sqair_modules.py:514-582,
@@ -2383,466 +2240,5 @@ int sq_launch_elbo(const float* log_w_t, const float* disc_lp_t, int T, int B, i
   }
   SQ_LAUNCH(k_elbo, dim3(1), dim3(1024), 0, s, log_w_t, disc_lp_t, T, B, K, log_weights, elbo_per_ex, iw,
                      signal, scalars, m, n_means, reinforce, means_out);
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Lane estimates (sqair_set_estimate; LaneEstArgs in sqair_glue.h; the semantics: include/sqair_hip.h, points 1-8)
-// ------------------------------------------------------------------------------------------------
-struct SqBox { float y, x, h, w; };
-// stn_to_pixel_coords(to_coords(where), (H, W)) (sqair/modules.py:221-262), with the to_coords of the crop and insert kernels
-__device__ __forceinline__ SqBox sq_box_of_where(const float* __restrict__ wl, int H, int W) {
-  const float sx = sq_to_coord(wl[0], 0), sy = sq_to_coord(wl[1], 1), tx = sq_to_coord(wl[2], 2), ty = sq_to_coord(wl[3], 3);
-  SqBox o;
-  o.y = 0.5f * (float)(H - 1) * (ty - sy + 1.0f);
-  o.x = 0.5f * (float)(W - 1) * (tx - sx + 1.0f);
-  o.h = (float)(H + 1) * sy;
-  o.w = (float)(W + 1) * sx;
-  return o;
-}
-// axis-aligned intersection over union; 0 when the union is not positive, exactly 1 for the same four words (positive area)
-__device__ __forceinline__ float sq_box_iou(const SqBox& p, const SqBox& q) {
-  const float oy = fmaxf(fminf(p.y + p.h, q.y + q.h) - fmaxf(p.y, q.y), 0.0f);
-  const float ox = fmaxf(fminf(p.x + p.w, q.x + q.w) - fmaxf(p.x, q.x), 0.0f);
-  const float inter = oy * ox, uni = p.h * p.w + q.h * q.w - inter;
-  if (!(uni > 0.0f)) return 0.0f;
-  if (p.y == q.y && p.x == q.x && p.h == q.h && p.w == q.w) return 1.0f;
-  return inter / uni;
-}
-// k_lane_estimate: workgroup (lane b, frame t, pixel chunk z).  Every workgroup forms the lane's weights at frame t (the helpers the
-// resampler runs on); chunk z = 0 also gives the lane's answer:
-//   thread k < K   its particle: n_k, and against the <= N best-row boxes in LDS the first present slot of maximal IoU per
-//                  best-row object j -- kept in registers (statically indexed: the j loop is unrolled over the build's slot limit)
-//                  and left as a K x N table of bytes (the slot, or 255: no agreement);
-//   per object j   the K matched boxes are recomputed by their threads into a 4 KB stage (K x N boxes would be 64 KB), then
-//                  threads c < 4 reduce coordinate c, and the support, over k in index order.
-// Every sum over k is one thread's loop in index order; nothing is accumulated with atomics (the first maximal k is an integer
-// atomicMin in LDS).  CANVAS: the instantiation that also averages the canvases (est.mean_canvas set); the other one carries none of it.
-template <bool CANVAS>
-__global__ __launch_bounds__(256) void k_lane_estimate(const LaneEstArgs a SQ_TLP) {
-  SQ_TL_SCOPE;
-  __shared__ float s_a[SQ_MAX_K];        // a_k
-  __shared__ float s_w[SQ_MAX_K];        // e_k, then w_k
-  __shared__ SqBox s_stage[SQ_MAX_K];    // the boxes matched to the current best-row object
-  __shared__ unsigned char s_match[SQ_MAX_K * SQ_MAXN];
-  __shared__ unsigned char s_n[SQ_MAX_K];
-  __shared__ SqBox s_bbox[SQ_MAXN];      // the best row's boxes
-  __shared__ int s_bp[SQ_MAXN];          // ... and which of its slots are present
-  __shared__ float s_cp[SQ_MAXN + 1];
-  __shared__ float s_st[2];              // m, S
-  __shared__ int s_best;
-  const SqairLaneEstimate& o = a.est;
-  const int b = blockIdx.x, t = blockIdx.y, tid = threadIdx.x, K = a.K, N = a.N, R = a.B * K, r = b * K + tid;
-  const bool lead = blockIdx.z == 0;
-  const size_t tb = (size_t)t * a.B + b, row0 = (size_t)t * R + (size_t)b * K;   // (frame t, particle 0 of lane b)
-  const float nan = __builtin_nanf("");
-  // ---- 1, 2: weights and the best row
-  float acc = 0.0f;
-  if (tid < K) {
-    acc = sq_lane_log_weight<true>(o.log_w, a.lw, t + 1, R, r);
-    s_a[tid] = acc;
-  }
-  if (tid == 0) s_best = K;
-  __syncthreads();
-  if (tid == 0) s_st[0] = sq_lane_max(s_a, K);
-  __syncthreads();
-  if (tid < K) {
-    s_w[tid] = sq_lane_exp(acc, s_st[0]);
-    if (acc == s_st[0]) atomicMin(&s_best, tid);
-  }
-  __syncthreads();
-  if (tid == 0) {
-    float S, Q;
-    sq_lane_sums<false>(s_w, K, S, Q);
-    s_st[1] = S;
-    if (!isfinite(S)) s_best = -1;
-    if (lead) {
-      if (o.ess) o.ess[tb] = sq_lane_ess(S, Q);
-      o.best_row[tb] = isfinite(S) ? b * K + s_best : -1;
-    }
-  }
-  __syncthreads();
-  const bool bad = s_best < 0;   // a non-finite lane: NaN weights, no objects
-  if (tid < K) {
-    const float w = s_w[tid] / s_st[1];
-    s_w[tid] = w;
-    if (lead && o.weights) o.weights[tb * K + tid] = w;
-  }
-  if (lead) {
-    // ---- 4: the best row's slots -> the lane's objects and their boxes
-    const size_t best0 = (row0 + (bad ? 0 : s_best)) * N;   // (slot 0 of the best row)
-    auto word = [](const float* p) { return *reinterpret_cast<const unsigned*>(p); };
-    auto put = [](float* p, unsigned v) { *reinterpret_cast<unsigned*>(p) = v; };
-    if (tid < N) {
-      const int j = tid;
-      const bool pj = !bad && a.presence[(best0 + j) * a.pres_ld] != 0.0f;
-      SqBox bx = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (pj) bx = sq_box_of_where(a.where + (best0 + j) * a.where_ld, a.H, a.W);
-      s_bp[j] = pj;
-      s_bbox[j] = bx;
-      const size_t e = tb * N + j;
-      if (o.presence) put(o.presence + e, pj ? word(a.presence + (best0 + j) * a.pres_ld) : 0u);
-      if (o.obj_id) put(o.obj_id + e, pj ? word(a.obj_id + (best0 + j) * a.id_ld) : 0u);
-      if (o.where)
-        for (int q = 0; q < 4; ++q) put(o.where + e * 4 + q, pj ? word(a.where + (best0 + j) * a.where_ld + q) : 0u);
-      if (o.box) {
-        o.box[e * 4 + 0] = bx.y; o.box[e * 4 + 1] = bx.x; o.box[e * 4 + 2] = bx.h; o.box[e * 4 + 3] = bx.w;
-      }
-    }
-    __syncthreads();
-    if (o.what)
-      for (int i = tid; i < N * a.nw; i += 256) {
-        const int j = i / a.nw, q = i - j * a.nw;
-        put(o.what + tb * N * a.nw + i, s_bp[j] ? word(a.what + (best0 + j) * a.what_ld + q) : 0u);
-      }
-    // ---- 3, 5: thread k's particle: its count, and per best-row object its first present slot of maximal IoU
-    if (tid < K) {
-      float bi[SQ_MAXN];
-      int bm[SQ_MAXN];
-#pragma unroll
-      for (int j = 0; j < SQ_MAXN; ++j) { bi[j] = -1.0f; bm[j] = 255; }
-      int n = 0;
-      const size_t k0 = (row0 + tid) * N;
-      for (int m = 0; m < N; ++m) {
-        if (a.presence[(k0 + m) * a.pres_ld] == 0.0f) continue;
-        ++n;
-        const SqBox bx = sq_box_of_where(a.where + (k0 + m) * a.where_ld, a.H, a.W);
-#pragma unroll
-        for (int j = 0; j < SQ_MAXN; ++j) {
-          if (j < N && s_bp[j]) {
-            const float v = sq_box_iou(s_bbox[j], bx);
-            if (v > bi[j]) { bi[j] = v; bm[j] = m; }
-          }
-        }
-      }
-      s_n[tid] = (unsigned char)n;
-#pragma unroll
-      for (int j = 0; j < SQ_MAXN; ++j)
-        if (j < N) s_match[tid * N + j] = (unsigned char)(bi[j] >= o.iou_min ? bm[j] : 255);
-    }
-    __syncthreads();
-    // ---- 3: the count posterior (thread c), the expected count (thread N + 1), the first maximal count (thread 0)
-    if (tid <= N) {
-      float p = 0.0f;
-      for (int k = 0; k < K; ++k) p += s_n[k] == tid ? s_w[k] : 0.0f;
-      if (bad) p = nan;
-      s_cp[tid] = p;
-      if (o.count_prob) o.count_prob[tb * (N + 1) + tid] = p;
-    } else if (tid == N + 1 && o.expected_count) {
-      float cnt = 0.0f;
-      for (int k = 0; k < K; ++k) cnt += s_w[k] * (float)s_n[k];
-      o.expected_count[tb] = cnt;
-    }
-    __syncthreads();
-    if (tid == 0 && o.map_count) {
-      int best_c = 0;
-      for (int c = 1; c <= N; ++c)
-        if (s_cp[c] > s_cp[best_c]) best_c = c;
-      o.map_count[tb] = bad ? -1 : best_c;
-    }
-    // ---- 5: support and consensus box of every best-row object (the loop and its branches are uniform over the workgroup)
-    if (o.support || o.box_mean) {
-      for (int j = 0; j < N; ++j) {
-        const size_t e = tb * N + j;
-        if (!s_bp[j]) {   // absent: zero (a non-finite lane: NaN)
-          const float v = bad ? nan : 0.0f;
-          if (tid == 0 && o.support) o.support[e] = v;
-          if (tid < 4 && o.box_mean) o.box_mean[e * 4 + tid] = v;
-          continue;
-        }
-        const int mt = tid < K ? s_match[tid * N + j] : 255;
-        if (mt != 255) s_stage[tid] = sq_box_of_where(a.where + ((row0 + tid) * N + mt) * a.where_ld, a.H, a.W);
-        __syncthreads();
-        if (tid < 4) {
-          float sup = 0.0f, sum = 0.0f;
-          for (int k = 0; k < K; ++k) {
-            if (s_match[k * N + j] == 255) continue;
-            const float w = s_w[k];
-            const SqBox& bx = s_stage[k];
-            sup += w;
-            sum += w * (tid == 0 ? bx.y : tid == 1 ? bx.x : tid == 2 ? bx.h : bx.w);
-          }
-          if (tid == 0 && o.support) o.support[e] = sup;
-          if (o.box_mean) o.box_mean[e * 4 + tid] = sum / sup;
-        }
-        __syncthreads();
-      }
-    }
-  }
-  // ---- 6: the posterior mean reconstruction, this workgroup's chunk of pixels
-  if (CANVAS) {
-    __syncthreads();   // (w_k of every particle)
-    const int P = a.H * a.W, p0 = blockIdx.z * SQ_EST_PIXELS;
-    for (int p = p0 + tid; p < min(p0 + SQ_EST_PIXELS, P); p += 256)
-      o.mean_canvas[tb * P + p] = sq_lane_mean_pixel(s_w, a.canvas, row0, P, p, K);
-  }
-}
-int sq_launch_lane_estimate(const LaneEstArgs& a, hipStream_t s) {
-  const int P = a.H * a.W, nz = a.est.mean_canvas ? (P + SQ_EST_PIXELS - 1) / SQ_EST_PIXELS : 1;
-  if (a.est.mean_canvas) SQ_LAUNCH(k_lane_estimate<true>, dim3(a.B, a.T, nz), dim3(256), 0, s, a);
-  else SQ_LAUNCH(k_lane_estimate<false>, dim3(a.B, a.T, nz), dim3(256), 0, s, a);
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Object forecasts (sqair_forecast_fan; include/sqair_hip.h states the semantics; the argument blocks: sqair_glue.h).  Defined after
-// every other kernel of this code object: none of the kernels a pass runs moves.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_forecast_fan_src(const int* __restrict__ src, int* __restrict__ src_fan, const int R, const int S SQ_TLP) {
-  SQ_TL_SCOPE;
-  const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (q >= (long long)R * S) return;
-  const int r = (int)(q / S);
-  int sr = src != nullptr ? src[r] : r;
-  if (sr < 0 || sr >= R) sr = -1;   // (the import's range rule against the blob's R: the fanned-out import never reads outside it)
-  src_fan[q] = sr;
-}
-int sq_launch_forecast_fan_src(const int* src, int* src_fan, int R, int S, hipStream_t s) {
-  const long long n = (long long)R * S;
-  SQ_LAUNCH(k_forecast_fan_src, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, src_fan, R, S);
-  return 0;
-}
-// k_forecast_summary over S rollouts per particle: workgroup (b, f).  The lane's weights by the same helpers, then expanded to one
-// weight per rollout row, w_q = w_{q / S} / S, so that both sums are the loops of k_forecast_summary over the lane's K*S rows.
-__global__ __launch_bounds__(256) void k_forecast_fan_summary(const ForecastFanSummaryArgs a SQ_TLP) {
-  SQ_TL_SCOPE;
-  __shared__ float s_k[SQ_MAX_K];
-  __shared__ float s_w[SQAIR_FORECAST_FAN_MAX];
-  __shared__ float s_m;
-  const int b = blockIdx.x, f = blockIdx.y, tid = threadIdx.x, K = a.K, S = a.S, N = a.N, P = a.P, KS = K * S;
-  const size_t row0 = ((size_t)f * a.B + b) * KS;   // (frame f, rollout 0 of lane b)
-  if (tid < K) s_k[tid] = sq_lane_log_weight<true>(a.log_w, nullptr, 0, a.B * K, b * K + tid);
-  __syncthreads();
-  if (tid == 0) s_m = sq_lane_max(s_k, K);
-  __syncthreads();
-  if (tid < K) s_k[tid] = sq_lane_exp(s_k[tid], s_m);
-  __syncthreads();
-  if (tid == 0) {
-    float Sum, Q;
-    sq_lane_sums<false>(s_k, K, Sum, Q);
-    for (int k = 0; k < K; ++k) s_k[k] = s_k[k] / Sum;
-  }
-  __syncthreads();
-  for (int q = tid; q < KS; q += 256) s_w[q] = s_k[q / S] / (float)S;
-  __syncthreads();
-  if (tid == 0 && a.expected_count) {
-    float cnt = 0.0f;
-    for (int q = 0; q < KS; ++q) {
-      float n = 0.0f;
-      for (int j = 0; j < N; ++j) n += a.rec[((row0 + q) * N + j) * rec::W + rec::PRES];
-      cnt += s_w[q] * n;
-    }
-    a.expected_count[(size_t)f * a.B + b] = cnt;
-  }
-  if (!a.mean_canvas) return;
-  for (int p = tid; p < P; p += 256) a.mean_canvas[((size_t)f * a.B + b) * P + p] = sq_lane_mean_pixel(s_w, a.canvas, row0, P, p, KS);
-}
-int sq_launch_forecast_fan_summary(const ForecastFanSummaryArgs& a, hipStream_t s) {
-  SQ_LAUNCH(k_forecast_fan_summary, dim3(a.B, a.F), dim3(256), 0, s, a);
-  return 0;
-}
-
-// k_forecast_lane_start: workgroup = lane b.  The weights and the best row as k_lane_estimate forms them (the same helpers), the best
-// START row's objects and boxes, then thread k < K associates its particle's start row with them -- k_lane_estimate's rule, its
-// per-object registers statically indexed over the build's slot limit -- and leaves in the scratch, per (k, j), whether k is
-// associated and the obj_id word its rollouts are followed by.
-__global__ __launch_bounds__(256) void k_forecast_lane_start(const ForecastLaneArgs a SQ_TLP) {
-  SQ_TL_SCOPE;
-  __shared__ float s_a[SQ_MAX_K];        // a_k
-  __shared__ float s_w[SQ_MAX_K];        // e_k, then w_k
-  __shared__ unsigned char s_match[SQ_MAX_K * SQ_MAXN];
-  __shared__ SqBox s_bbox[SQ_MAXN];      // the best start row's boxes
-  __shared__ int s_bp[SQ_MAXN];          // ... and which of its slots are present
-  __shared__ float s_st[2];              // m, S
-  __shared__ int s_best;
-  const SqairForecastLane& o = a.lane;
-  const int b = blockIdx.x, tid = threadIdx.x, K = a.K, N = a.N, R = a.B * K, r = b * K + tid;
-  const float nan = __builtin_nanf("");
-  auto word = [](const float* p) { return *reinterpret_cast<const unsigned*>(p); };
-  auto put = [](float* p, unsigned v) { *reinterpret_cast<unsigned*>(p) = v; };
-  // ---- 1: weights and the best row
-  float acc = 0.0f;
-  if (tid < K) {
-    acc = sq_lane_log_weight<true>(a.log_w, nullptr, 0, R, r);
-    s_a[tid] = acc;
-  }
-  if (tid == 0) s_best = K;
-  __syncthreads();
-  if (tid == 0) s_st[0] = sq_lane_max(s_a, K);
-  __syncthreads();
-  if (tid < K) {
-    s_w[tid] = sq_lane_exp(acc, s_st[0]);
-    if (acc == s_st[0]) atomicMin(&s_best, tid);
-  }
-  __syncthreads();
-  if (tid == 0) {
-    float S, Q;
-    sq_lane_sums<false>(s_w, K, S, Q);
-    s_st[1] = S;
-    if (!isfinite(S)) s_best = -1;
-    o.best_row[b] = isfinite(S) ? b * K + s_best : -1;
-  }
-  __syncthreads();
-  const bool bad = s_best < 0;   // a non-finite lane: NaN weights, no objects
-  if (tid < K) {
-    const float w = s_w[tid] / s_st[1];
-    s_w[tid] = w;
-    a.x.w[r] = w;
-    if (o.weights) o.weights[r] = w;
-  }
-  // ---- 2: the start records of the lane's rows (words copied), the best start row's objects and their boxes
-  for (int i = tid; i < K * N; i += 256) {
-    const int k = i / N;
-    const size_t src = ((size_t)(b * K + k) * a.row_step) * N + (i - k * N), dst = (size_t)b * K * N + i;
-    if (o.start_presence) put(o.start_presence + dst, word(a.s_pres + src * a.s_pres_ld));
-    if (o.start_obj_id) put(o.start_obj_id + dst, word(a.s_id + src * a.s_id_ld));
-    if (o.start_where)
-      for (int c = 0; c < 4; ++c) put(o.start_where + dst * 4 + c, word(a.s_where + src * a.s_where_ld + c));
-  }
-  const size_t best0 = ((size_t)(b * K + (bad ? 0 : s_best)) * a.row_step) * N;   // (slot 0 of the best start row)
-  if (tid < N) {
-    const int j = tid;
-    const bool pj = !bad && a.s_pres[(best0 + j) * a.s_pres_ld] != 0.0f;
-    SqBox bx = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (pj) bx = sq_box_of_where(a.s_where + (best0 + j) * a.s_where_ld, a.H, a.W);
-    s_bp[j] = pj;
-    s_bbox[j] = bx;
-    const size_t e = (size_t)b * N + j;
-    a.x.bp[e] = pj;
-    if (o.presence) put(o.presence + e, pj ? word(a.s_pres + (best0 + j) * a.s_pres_ld) : 0u);
-    if (o.obj_id) put(o.obj_id + e, pj ? word(a.s_id + (best0 + j) * a.s_id_ld) : 0u);
-    if (o.box0) {
-      o.box0[e * 4 + 0] = bx.y; o.box0[e * 4 + 1] = bx.x; o.box0[e * 4 + 2] = bx.h; o.box0[e * 4 + 3] = bx.w;
-    }
-  }
-  __syncthreads();
-  // ---- 3: thread k's particle: per best-row object its first present start slot of maximal IoU, and that slot's id word
-  if (tid < K) {
-    float bi[SQ_MAXN];
-    int bm[SQ_MAXN];
-    unsigned bw[SQ_MAXN];
-#pragma unroll
-    for (int j = 0; j < SQ_MAXN; ++j) { bi[j] = -1.0f; bm[j] = 255; bw[j] = 0u; }
-    const size_t k0 = ((size_t)r * a.row_step) * N;
-    for (int m = 0; m < N; ++m) {
-      if (a.s_pres[(k0 + m) * a.s_pres_ld] == 0.0f) continue;
-      const SqBox bx = sq_box_of_where(a.s_where + (k0 + m) * a.s_where_ld, a.H, a.W);
-      const unsigned idw = word(a.s_id + (k0 + m) * a.s_id_ld);
-#pragma unroll
-      for (int j = 0; j < SQ_MAXN; ++j) {
-        if (j < N && s_bp[j]) {
-          const float v = sq_box_iou(s_bbox[j], bx);
-          if (v > bi[j]) { bi[j] = v; bm[j] = m; bw[j] = idw; }
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < SQ_MAXN; ++j)
-      if (j < N) {
-        const bool ok = bi[j] >= o.iou_min;
-        s_match[tid * N + j] = (unsigned char)(ok ? bm[j] : 255);
-        a.x.fm[(size_t)r * N + j] = ok;
-        a.x.fid[(size_t)r * N + j] = ok ? bw[j] : 0u;
-      }
-  }
-  __syncthreads();
-  if (tid < N && o.support) {
-    const int j = tid;
-    float sup = 0.0f;
-    for (int k = 0; k < K; ++k) {
-      if (s_match[k * N + j] == 255) continue;
-      sup += s_w[k];
-    }
-    o.support[(size_t)b * N + j] = s_bp[j] ? sup : (bad ? nan : 0.0f);
-  }
-}
-// k_forecast_lane_frame: workgroup (lane b, frame f), thread = rollout q of the lane (K*S <= SQAIR_FORECAST_FAN_MAX: up to four per
-// thread).  The rollouts' counts give count_prob; per object j each associated rollout looks its followed id up among its present
-// slots and stages that slot's pixel box in LDS (16 bytes per rollout), then threads c < 4 reduce coordinate c in two passes, each
-// ONE thread's loop over q in index order.  No per-thread arrays: nothing to spill.
-__global__ __launch_bounds__(256) void k_forecast_lane_frame(const ForecastLaneArgs a SQ_TLP) {
-  SQ_TL_SCOPE;
-  __shared__ float s_w[SQ_MAX_K];                       // w_k / S
-  __shared__ SqBox s_stage[SQAIR_FORECAST_FAN_MAX];     // the box followed in rollout q
-  __shared__ unsigned char s_hit[SQAIR_FORECAST_FAN_MAX];
-  __shared__ unsigned char s_n[SQAIR_FORECAST_FAN_MAX];
-  const SqairForecastLane& o = a.lane;
-  const int b = blockIdx.x, f = blockIdx.y, tid = threadIdx.x, K = a.K, S = a.S, N = a.N, KS = K * S;
-  const size_t fb = (size_t)f * a.B + b, row0 = fb * KS;   // (frame f, rollout 0 of lane b)
-  const bool bad = o.best_row[b] < 0;
-  const float nan = __builtin_nanf("");
-  if (tid < K) s_w[tid] = a.x.w[b * K + tid] / (float)S;
-  for (int q = tid; q < KS; q += 256) {
-    int n = 0;
-    for (int m = 0; m < N; ++m) n += a.presence[((row0 + q) * N + m) * a.pres_ld] != 0.0f ? 1 : 0;
-    s_n[q] = (unsigned char)n;
-  }
-  __syncthreads();
-  if (tid <= N && o.count_prob) {
-    float p = 0.0f;
-    for (int k = 0, q = 0; k < K; ++k) {
-      const float w = s_w[k];
-      for (int s = 0; s < S; ++s, ++q) p += s_n[q] == tid ? w : 0.0f;
-    }
-    o.count_prob[fb * (N + 1) + tid] = bad ? nan : p;
-  }
-  if (!o.alive && !o.box_mean && !o.box_std) return;
-  for (int j = 0; j < N; ++j) {   // (the loop and its branches are uniform over the workgroup)
-    const size_t e = fb * N + j;
-    if (!a.x.bp[b * N + j]) {     // absent: zero (a non-finite lane: NaN)
-      const float v = bad ? nan : 0.0f;
-      if (tid == 0 && o.alive) o.alive[e] = v;
-      if (tid < 4 && o.box_mean) o.box_mean[e * 4 + tid] = v;
-      if (tid < 4 && o.box_std) o.box_std[e * 4 + tid] = v;
-      continue;
-    }
-    for (int q = tid; q < KS; q += 256) {
-      const size_t kj = (size_t)(b * K + q / S) * N + j;
-      int hit = 0;
-      if (a.x.fm[kj]) {
-        const unsigned idw = a.x.fid[kj];
-        for (int m = 0; m < N && !hit; ++m) {
-          const size_t sl = (row0 + q) * N + m;
-          if (a.presence[sl * a.pres_ld] != 0.0f && *reinterpret_cast<const unsigned*>(a.obj_id + sl * a.id_ld) == idw) {
-            s_stage[q] = sq_box_of_where(a.where + sl * a.where_ld, a.H, a.W);
-            hit = 1;
-          }
-        }
-      }
-      s_hit[q] = (unsigned char)hit;
-    }
-    __syncthreads();
-    if (tid < 4) {
-      float al = 0.0f, sum = 0.0f;
-      for (int k = 0, q = 0; k < K; ++k) {
-        const float w = s_w[k];
-        for (int s = 0; s < S; ++s, ++q) {
-          if (!s_hit[q]) continue;
-          const SqBox& bx = s_stage[q];
-          al += w;
-          sum += w * (tid == 0 ? bx.y : tid == 1 ? bx.x : tid == 2 ? bx.h : bx.w);
-        }
-      }
-      const float mean = sum / al;
-      float var = 0.0f;
-      for (int k = 0, q = 0; k < K; ++k) {
-        const float w = s_w[k];
-        for (int s = 0; s < S; ++s, ++q) {
-          if (!s_hit[q]) continue;
-          const SqBox& bx = s_stage[q];
-          const float dv = (tid == 0 ? bx.y : tid == 1 ? bx.x : tid == 2 ? bx.h : bx.w) - mean;
-          var += w * (dv * dv);
-        }
-      }
-      if (tid == 0 && o.alive) o.alive[e] = al;
-      if (o.box_mean) o.box_mean[e * 4 + tid] = mean;
-      if (o.box_std) o.box_std[e * 4 + tid] = sqrtf(var / al);
-    }
-    __syncthreads();
-  }
-}
-int sq_launch_forecast_lane(const ForecastLaneArgs& a, hipStream_t s) {
-  SQ_LAUNCH(k_forecast_lane_start, dim3(a.B), dim3(256), 0, s, a);
-  SQ_LAUNCH(k_forecast_lane_frame, dim3(a.B, a.F), dim3(256), 0, s, a);
   return 0;
 }

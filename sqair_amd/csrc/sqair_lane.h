@@ -1,0 +1,175 @@
+// Device functions of the per-lane answers (sqair_lane.hip): what turns a lane's K particle rows into one answer -- the weights, the
+// best row's objects, the association of every particle with them -- stated once for the kernels that need it.
+#pragma once
+#include "sqair_glue.h"
+
+// The weights of a lane's K particles: a_k accumulated in frame order, m = max a_k, e_k = expf(a_k - m), S = sum e_k and
+// Q = sum e_k^2 as ONE thread's loops in index order, ESS = S^2 / Q.  A NaN or +inf a_k, or every a_k at -inf, makes S non-finite.
+template <bool MAY_BE_NULL>   // log_w == NULL: zeros (the resampler's is never NULL)
+__device__ __forceinline__ float sq_lane_log_weight(const float* log_w, const float* lw, int n_frames, int R, int r) {
+  float acc = MAY_BE_NULL && !log_w ? 0.0f : log_w[r];
+  for (int t = 0; t < n_frames; ++t) acc += lw[(size_t)t * R + r];
+  return acc;
+}
+__device__ __forceinline__ float sq_lane_max(const float* a, int K) {
+  float m = a[0];
+  for (int i = 1; i < K; ++i) m = fmaxf(m, a[i]);
+  return m;
+}
+__device__ __forceinline__ float sq_lane_exp(float a, float m) { return expf(a - m); }
+template <bool PREFIX>   // PREFIX: e_k is replaced by the inclusive prefix sum c_k (the resampler searches it)
+__device__ __forceinline__ void sq_lane_sums(float* e, int K, float& S, float& Q) {
+  float c = 0.0f, q = 0.0f;
+  for (int i = 0; i < K; ++i) {
+    const float v = e[i];
+    c += v;
+    q += v * v;
+    if (PREFIX) e[i] = c;
+  }
+  S = c;
+  Q = q;
+}
+__device__ __forceinline__ float sq_lane_ess(float S, float Q) { return S * S / Q; }
+// sum_k w_k canvas[row0 + k][p], k in index order
+__device__ __forceinline__ float sq_lane_mean_pixel(const float* w, const float* __restrict__ canvas, size_t row0, int P, int p, int K) {
+  float acc = 0.0f;
+  for (int k = 0; k < K; ++k) acc += w[k] * canvas[(row0 + k) * P + p];
+  return acc;
+}
+// The sequence over a workgroup of >= K threads, thread k < K holding a_k (`acc`).  Leaves in s_w[0..K), behind a barrier,
+//   PREFIX   the inclusive prefix sums c_k of e_k (nothing is divided; st.best is not formed);
+//   else     w_k = e_k / S, and in st.best the first k of maximal a_k (an integer atomicMin in LDS) -- or -1 for a non-finite
+//            lane (S not finite): NaN weights, no best row, no objects;
+// and in `st` m, S and Q.
+struct SqLaneStats { float m, S, Q; int best; };
+template <bool PREFIX>
+__device__ __forceinline__ void sq_lane_weights(const float acc, const int K, float* s_w, SqLaneStats& st) {
+  const int k = threadIdx.x;
+  if (k < K) s_w[k] = acc;
+  if (k == 0) st.best = K;
+  __syncthreads();
+  if (k == 0) st.m = sq_lane_max(s_w, K);
+  __syncthreads();
+  if (k < K) {
+    s_w[k] = sq_lane_exp(acc, st.m);
+    if (!PREFIX && acc == st.m) atomicMin(&st.best, k);
+  }
+  __syncthreads();
+  if (k == 0) {
+    sq_lane_sums<PREFIX>(s_w, K, st.S, st.Q);
+    if (!PREFIX && !isfinite(st.S)) st.best = -1;
+  }
+  __syncthreads();
+  if (PREFIX) return;
+  if (k < K) s_w[k] = s_w[k] / st.S;
+  __syncthreads();
+}
+
+// 32-bit words copied as they are
+__device__ __forceinline__ unsigned sq_word(const float* p) { return *reinterpret_cast<const unsigned*>(p); }
+__device__ __forceinline__ void sq_put(float* p, unsigned v) { *reinterpret_cast<unsigned*>(p) = v; }
+
+// slot 0 of row `row` of a view, in slots
+__device__ __forceinline__ size_t sq_lane_slot(const LaneRows& v, size_t row, int N) { return row * v.row_step * N; }
+
+struct SqBox { float y, x, h, w; };
+__device__ __forceinline__ float sq_box_coord(const SqBox& b, int c) { return c == 0 ? b.y : c == 1 ? b.x : c == 2 ? b.h : b.w; }
+// stn_to_pixel_coords(to_coords(where), (H, W)) (sqair/modules.py:221-262), with the to_coords of the crop and insert kernels
+__device__ __forceinline__ SqBox sq_box_of_where(const float* __restrict__ wl, int H, int W) {
+  const float sx = sq_to_coord(wl[0], 0), sy = sq_to_coord(wl[1], 1), tx = sq_to_coord(wl[2], 2), ty = sq_to_coord(wl[3], 3);
+  SqBox o;
+  o.y = 0.5f * (float)(H - 1) * (ty - sy + 1.0f);
+  o.x = 0.5f * (float)(W - 1) * (tx - sx + 1.0f);
+  o.h = (float)(H + 1) * sy;
+  o.w = (float)(W + 1) * sx;
+  return o;
+}
+// axis-aligned intersection over union; 0 when the union is not positive, exactly 1 for the same four words (positive area)
+__device__ __forceinline__ float sq_box_iou(const SqBox& p, const SqBox& q) {
+  const float oy = fmaxf(fminf(p.y + p.h, q.y + q.h) - fmaxf(p.y, q.y), 0.0f);
+  const float ox = fmaxf(fminf(p.x + p.w, q.x + q.w) - fmaxf(p.x, q.x), 0.0f);
+  const float inter = oy * ox, uni = p.h * p.w + q.h * q.w - inter;
+  if (!(uni > 0.0f)) return 0.0f;
+  if (p.y == q.y && p.x == q.x && p.h == q.h && p.w == q.w) return 1.0f;
+  return inter / uni;
+}
+
+// The best row's objects: thread j < N takes slot j of row `best` of the view (LaneRows, sqair_glue.h) -- absent in a non-finite lane
+// (`bad`) -- into s_bp[j] / s_bbox[j] and, where bound, its words and its pixel box into element e0 + j of the outputs.  Ends on a
+// barrier.
+struct SqBestOut { float* presence; float* obj_id; float* where; float* box; };   // [.., N], [.., N], [.., N, 4], [.., N, 4] or NULL
+__device__ __forceinline__ void sq_lane_best_objects(const LaneRows& v, const size_t best, const bool bad, const int N, const int H,
+                                                     const int W, const size_t e0, const SqBestOut& o, int* s_bp, SqBox* s_bbox) {
+  const int j = threadIdx.x;
+  if (j < N) {
+    const size_t sl = sq_lane_slot(v, best, N) + j;
+    const bool pj = !bad && v.presence[sl * v.pres_ld] != 0.0f;
+    SqBox bx = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (pj) bx = sq_box_of_where(v.where + sl * v.where_ld, H, W);
+    s_bp[j] = pj;
+    s_bbox[j] = bx;
+    const size_t e = e0 + j;
+    if (o.presence) sq_put(o.presence + e, pj ? sq_word(v.presence + sl * v.pres_ld) : 0u);
+    if (o.obj_id) sq_put(o.obj_id + e, pj ? sq_word(v.obj_id + sl * v.id_ld) : 0u);
+    if (o.where)
+      for (int q = 0; q < 4; ++q) sq_put(o.where + e * 4 + q, pj ? sq_word(v.where + sl * v.where_ld + q) : 0u);
+    if (o.box) {
+      o.box[e * 4 + 0] = bx.y; o.box[e * 4 + 1] = bx.x; o.box[e * 4 + 2] = bx.h; o.box[e * 4 + 3] = bx.w;
+    }
+  }
+  __syncthreads();
+}
+
+// The association of ONE particle (the calling thread's row `row` of the view) with the best row's objects: per object j the first
+// present slot of maximal IoU, kept in registers -- statically indexed: the j loops are unrolled over the build's slot limit -- and
+// left in match[0..N) as a byte (the slot, or 255: below iou_min or no best-row object j).  WITH_ID: fm[j] says whether j is
+// matched and fid[j] is the obj_id word of the matched slot (0 otherwise).  Returns the row's number of present slots.
+template <bool WITH_ID>
+__device__ __forceinline__ int sq_lane_associate(const LaneRows& v, const size_t row, const int N, const int H, const int W,
+                                                 const float iou_min, const int* s_bp, const SqBox* s_bbox, unsigned char* match,
+                                                 int* fm, unsigned* fid) {
+  float bi[SQ_MAXN];
+  int bm[SQ_MAXN];
+  unsigned bw[SQ_MAXN];
+#pragma unroll
+  for (int j = 0; j < SQ_MAXN; ++j) { bi[j] = -1.0f; bm[j] = 255; bw[j] = 0u; }
+  int n = 0;
+  const size_t k0 = sq_lane_slot(v, row, N);
+  for (int m = 0; m < N; ++m) {
+    if (v.presence[(k0 + m) * v.pres_ld] == 0.0f) continue;
+    ++n;
+    const SqBox bx = sq_box_of_where(v.where + (k0 + m) * v.where_ld, H, W);
+    const unsigned idw = WITH_ID ? sq_word(v.obj_id + (k0 + m) * v.id_ld) : 0u;
+#pragma unroll
+    for (int j = 0; j < SQ_MAXN; ++j) {
+      if (j < N && s_bp[j]) {
+        const float iou = sq_box_iou(s_bbox[j], bx);
+        if (iou > bi[j]) { bi[j] = iou; bm[j] = m; bw[j] = idw; }
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < SQ_MAXN; ++j)
+    if (j < N) {
+      const bool ok = bi[j] >= iou_min;
+      match[j] = (unsigned char)(ok ? bm[j] : 255);
+      if (WITH_ID) { fm[j] = ok; fid[j] = ok ? bw[j] : 0u; }
+    }
+  return n;
+}
+
+// Thread c < 4, coordinate c of the boxes staged for the lane's K * S rows q = k * S + s: al = sum of w_k and sum = sum of
+// w_k * coordinate over the rows with hit(q), ONE thread's loop over q in index order.
+template <class Hit>
+__device__ __forceinline__ void sq_lane_box_sum(const float* s_w, const SqBox* s_stage, const int K, const int S, const int c, Hit hit,
+                                                float& al, float& sum) {
+  al = 0.0f; sum = 0.0f;
+  for (int k = 0, q = 0; k < K; ++k) {
+    const float w = s_w[k];
+    for (int s = 0; s < S; ++s, ++q) {
+      if (!hit(q)) continue;
+      al += w;
+      sum += w * sq_box_coord(s_stage[q], c);
+    }
+  }
+}

@@ -1,0 +1,352 @@
+// The per-lane answers: the kernels that turn a lane's K particle rows into one answer per lane -- the SMC resampler, the forecast
+// summaries, the lane estimate and the lane forecast.  None of them is a hop of the frame loop (once per pass or per call, on B
+// workgroups), and they are a translation unit -- a code object -- of their own so that work on them moves no kernel of the pass
+// (DESIGN.md section 3h).  Their compositions are the device functions of sqair_lane.h.  Every lane-wide sum is one thread's loop in
+// index order: the same bits on every replay, and K <= 256 adds are nothing next to the pass.
+#include "sqair_lane.h"
+
+// ------------------------------------------------------------------------------------------------
+// k_smc_resample (sqair_set_smc; SmcArgs in sqair_glue.h): the last launch of a pass with SMC on, after k_state_export.  Lane b's
+// log weights a_k = log_w + this pass's per-frame log weights (frame order) -> ESS and the evidence, then either a systematic
+// resampling written as the next pass's source map (k_state_import gathers the chosen rows out of the blob k_state_export just
+// wrote) or the identity map with the weights carried on.
+// ------------------------------------------------------------------------------------------------
+constexpr unsigned SQ_SMC_PHILOX_TAG = 0x534D4352u;   // ("SMCR") counter word 1: never an element index of sqair_fill_noise
+__global__ __launch_bounds__(256) void k_smc_resample(const SmcArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ float s_c[SQ_MAX_K];   // a_k, e_k, then the inclusive prefix c_k
+  __shared__ SqLaneStats s_st;
+  __shared__ float s_u;
+  __shared__ int s_do;
+  const int b = blockIdx.x, k = threadIdx.x, K = a.K, R = a.B * K, r = b * K + k;
+  const float acc = k < K ? sq_lane_log_weight<false>(a.log_w, a.lw, a.T, R, r) : 0.0f;
+  sq_lane_weights<true>(acc, K, s_c, s_st);
+  if (k == 0) {
+    const float m = s_st.m, c = s_st.S;
+    const float ess = sq_lane_ess(c, s_st.Q), lse = m + logf(c / (float)K);
+    const float lz = a.log_z[b];
+    a.log_evidence[b] = lz + lse;
+    a.ess[b] = ess;
+    // (a NaN or infinite a_k, or every a_k at -inf, gives a non-finite ESS: such a lane never resamples, whatever ess_frac, so
+    //  the identity map and the carried a_k keep the bad values where the caller can see them)
+    const int go = isfinite(ess) && (a.ess_frac == 1.0f || ess < a.ess_frac * (float)K);
+    float u;   // (drawn whether or not the lane resamples: u_out always holds this pass's u)
+    if (a.uniforms != nullptr) {
+      u = a.uniforms[b];
+    } else {
+      const unsigned ctr = (unsigned)(a.t_row[b * K] + a.T);   // (the lane's frame counter after the pass)
+      unsigned w[4];
+      philox4x32_10((unsigned)b, SQ_SMC_PHILOX_TAG, ctr, 0u, (unsigned)a.seed, (unsigned)(a.seed >> 32), w);
+      u = (float)(w[0] >> 8) * (1.0f / 16777216.0f);   // [0, 1), 24 bits
+    }
+    if (a.u_out != nullptr) a.u_out[b] = u;
+    if (go) a.log_z[b] = lz + lse;
+    a.resampled[b] = go;
+    s_u = u; s_do = go;
+  }
+  __syncthreads();
+  if (k >= K) return;
+  if (s_do) {
+    // output k: the smallest i with c_i > (k + u) S / K.  If none (fp32 rounding of (k + u) S / K up to S = c_{K-1}: k = K - 1
+    // and u near 1), the smallest i with c_i >= S, i.e. the last particle of positive weight, never a zero-weight one after it.
+    // The predicate is monotone in i and true at K - 1; below S it is c_i > thr alone.
+    const float thr = ((float)k + s_u) * s_st.S / (float)K, S = s_st.S;
+    int lo = 0, hi = K - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (s_c[mid] > thr || s_c[mid] >= S) hi = mid;
+      else lo = mid + 1;
+    }
+    a.src[r] = b * K + lo;
+    a.log_w[r] = 0.0f;
+  } else {
+    a.src[r] = r;
+    a.log_w[r] = acc;
+  }
+}
+int sq_launch_smc_resample(const SmcArgs& a, hipStream_t s) {
+  SQ_LAUNCH(k_smc_resample, dim3(a.B), dim3(256), 0, s, a);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Forecasts (sqair_forecast, sqair_forecast_fan; include/sqair_hip.h states the semantics; the argument blocks: sqair_glue.h)
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_forecast_fan_src(const int* __restrict__ src, int* __restrict__ src_fan, const int R, const int S SQ_TLP) {
+  SQ_TL_SCOPE;
+  const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (q >= (long long)R * S) return;
+  const int r = (int)(q / S);
+  int sr = src != nullptr ? src[r] : r;
+  if (sr < 0 || sr >= R) sr = -1;   // (the import's range rule against the blob's R: the fanned-out import never reads outside it)
+  src_fan[q] = sr;
+}
+int sq_launch_forecast_fan_src(const int* src, int* src_fan, int R, int S, hipStream_t s) {
+  const long long n = (long long)R * S;
+  SQ_LAUNCH(k_forecast_fan_src, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, src_fan, R, S);
+  return 0;
+}
+// Predictive summaries (ForecastSummaryArgs): workgroup (b, f).  The lane's weights, expanded to one weight per rollout row,
+// w_q = w_{q / S} / S (S = 1: w_q = w_k, the division by 1.0f is exact), then both sums as loops over the lane's K*S rows.  A NaN or
+// +inf weight, or all of them -inf, makes S -- and so every w_q -- NaN.
+__global__ __launch_bounds__(256) void k_forecast_summary(const ForecastSummaryArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ float s_k[SQ_MAX_K];
+  __shared__ float s_w[SQAIR_FORECAST_FAN_MAX];
+  __shared__ SqLaneStats s_st;
+  const int b = blockIdx.x, f = blockIdx.y, tid = threadIdx.x, K = a.K, S = a.S, N = a.N, P = a.P, KS = K * S;
+  const size_t row0 = ((size_t)f * a.B + b) * KS;   // (frame f, rollout 0 of lane b)
+  sq_lane_weights<false>(tid < K ? sq_lane_log_weight<true>(a.log_w, nullptr, 0, a.B * K, b * K + tid) : 0.0f, K, s_k, s_st);
+  for (int q = tid; q < KS; q += 256) s_w[q] = s_k[q / S] / (float)S;
+  __syncthreads();
+  if (tid == 0 && a.expected_count) {
+    float cnt = 0.0f;
+    for (int q = 0; q < KS; ++q) {
+      float n = 0.0f;
+      for (int j = 0; j < N; ++j) n += a.rec[((row0 + q) * N + j) * rec::W + rec::PRES];
+      cnt += s_w[q] * n;
+    }
+    a.expected_count[(size_t)f * a.B + b] = cnt;
+  }
+  if (!a.mean_canvas) return;
+  for (int p = tid; p < P; p += 256) a.mean_canvas[((size_t)f * a.B + b) * P + p] = sq_lane_mean_pixel(s_w, a.canvas, row0, P, p, KS);
+}
+int sq_launch_forecast_summary(const ForecastSummaryArgs& a, hipStream_t s) {
+  SQ_LAUNCH(k_forecast_summary, dim3(a.B, a.F), dim3(256), 0, s, a);
+  return 0;
+}
+
+// k_forecast_lane_start: workgroup = lane b.  The weights and the best row, the best START row's objects and boxes, then thread
+// k < K associates its particle's start row with them and leaves in the scratch, per (k, j), whether k is associated and the obj_id
+// word its rollouts are followed by -- every step k_lane_estimate's, by the same functions.
+__global__ __launch_bounds__(256) void k_forecast_lane_start(const ForecastLaneArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ float s_w[SQ_MAX_K];        // a_k, e_k, then w_k
+  __shared__ unsigned char s_match[SQ_MAX_K * SQ_MAXN];
+  __shared__ SqBox s_bbox[SQ_MAXN];      // the best start row's boxes
+  __shared__ int s_bp[SQ_MAXN];          // ... and which of its slots are present
+  __shared__ SqLaneStats s_st;
+  const SqairForecastLane& o = a.lane;
+  const LaneRows& v = a.start;
+  const int b = blockIdx.x, tid = threadIdx.x, K = a.K, N = a.N, R = a.B * K, r = b * K + tid;
+  // ---- 1: weights and the best row
+  sq_lane_weights<false>(tid < K ? sq_lane_log_weight<true>(a.log_w, nullptr, 0, R, r) : 0.0f, K, s_w, s_st);
+  const bool bad = s_st.best < 0;
+  if (tid == 0) o.best_row[b] = bad ? -1 : b * K + s_st.best;
+  if (tid < K) {
+    a.x.w[r] = s_w[tid];
+    if (o.weights) o.weights[r] = s_w[tid];
+  }
+  // ---- 2: the start records of the lane's rows (words copied), the best start row's objects and their boxes
+  for (int i = tid; i < K * N; i += 256) {
+    const int k = i / N;
+    const size_t src = sq_lane_slot(v, (size_t)(b * K + k), N) + (i - k * N), dst = (size_t)b * K * N + i;
+    if (o.start_presence) sq_put(o.start_presence + dst, sq_word(v.presence + src * v.pres_ld));
+    if (o.start_obj_id) sq_put(o.start_obj_id + dst, sq_word(v.obj_id + src * v.id_ld));
+    if (o.start_where)
+      for (int c = 0; c < 4; ++c) sq_put(o.start_where + dst * 4 + c, sq_word(v.where + src * v.where_ld + c));
+  }
+  sq_lane_best_objects(v, (size_t)(b * K + (bad ? 0 : s_st.best)), bad, N, a.H, a.W, (size_t)b * N,
+                       SqBestOut{o.presence, o.obj_id, nullptr, o.box0}, s_bp, s_bbox);
+  if (tid < N) a.x.bp[(size_t)b * N + tid] = s_bp[tid];
+  // ---- 3: thread k's particle: per best-row object its first present start slot of maximal IoU, and that slot's id word
+  if (tid < K)
+    sq_lane_associate<true>(v, (size_t)r, N, a.H, a.W, o.iou_min, s_bp, s_bbox, s_match + tid * N, a.x.fm + (size_t)r * N,
+                            a.x.fid + (size_t)r * N);
+  __syncthreads();
+  if (tid < N && o.support) {
+    const int j = tid;
+    float sup = 0.0f;
+    for (int k = 0; k < K; ++k) {
+      if (s_match[k * N + j] == 255) continue;
+      sup += s_w[k];
+    }
+    o.support[(size_t)b * N + j] = s_bp[j] ? sup : (bad ? __builtin_nanf("") : 0.0f);
+  }
+}
+// k_forecast_lane_frame: workgroup (lane b, frame f), thread = rollout q of the lane (K*S <= SQAIR_FORECAST_FAN_MAX: up to four per
+// thread).  The rollouts' counts give count_prob; per object j each associated rollout looks its followed id up among its present
+// slots and stages that slot's pixel box in LDS (16 bytes per rollout), then threads c < 4 reduce coordinate c in two passes, each
+// ONE thread's loop over q in index order.  No per-thread arrays: nothing to spill.
+__global__ __launch_bounds__(256) void k_forecast_lane_frame(const ForecastLaneArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ float s_w[SQ_MAX_K];                       // w_k / S
+  __shared__ SqBox s_stage[SQAIR_FORECAST_FAN_MAX];     // the box followed in rollout q
+  __shared__ unsigned char s_hit[SQAIR_FORECAST_FAN_MAX];
+  __shared__ unsigned char s_n[SQAIR_FORECAST_FAN_MAX];
+  const SqairForecastLane& o = a.lane;
+  const int b = blockIdx.x, f = blockIdx.y, tid = threadIdx.x, K = a.K, S = a.S, N = a.N, KS = K * S;
+  const size_t fb = (size_t)f * a.B + b, row0 = fb * KS;   // (frame f, rollout 0 of lane b)
+  const bool bad = o.best_row[b] < 0;
+  const float nan = __builtin_nanf("");
+  if (tid < K) s_w[tid] = a.x.w[b * K + tid] / (float)S;
+  for (int q = tid; q < KS; q += 256) {
+    int n = 0;
+    for (int m = 0; m < N; ++m) n += a.presence[((row0 + q) * N + m) * a.pres_ld] != 0.0f ? 1 : 0;
+    s_n[q] = (unsigned char)n;
+  }
+  __syncthreads();
+  if (tid <= N && o.count_prob) {
+    float p = 0.0f;
+    for (int k = 0, q = 0; k < K; ++k) {
+      const float w = s_w[k];
+      for (int s = 0; s < S; ++s, ++q) p += s_n[q] == tid ? w : 0.0f;
+    }
+    o.count_prob[fb * (N + 1) + tid] = bad ? nan : p;
+  }
+  if (!o.alive && !o.box_mean && !o.box_std) return;
+  for (int j = 0; j < N; ++j) {   // (the loop and its branches are uniform over the workgroup)
+    const size_t e = fb * N + j;
+    if (!a.x.bp[b * N + j]) {     // absent: zero (a non-finite lane: NaN)
+      const float v = bad ? nan : 0.0f;
+      if (tid == 0 && o.alive) o.alive[e] = v;
+      if (tid < 4 && o.box_mean) o.box_mean[e * 4 + tid] = v;
+      if (tid < 4 && o.box_std) o.box_std[e * 4 + tid] = v;
+      continue;
+    }
+    for (int q = tid; q < KS; q += 256) {
+      const size_t kj = (size_t)(b * K + q / S) * N + j;
+      int hit = 0;
+      if (a.x.fm[kj]) {
+        const unsigned idw = a.x.fid[kj];
+        for (int m = 0; m < N && !hit; ++m) {
+          const size_t sl = (row0 + q) * N + m;
+          if (a.presence[sl * a.pres_ld] != 0.0f && sq_word(a.obj_id + sl * a.id_ld) == idw) {
+            s_stage[q] = sq_box_of_where(a.where + sl * a.where_ld, a.H, a.W);
+            hit = 1;
+          }
+        }
+      }
+      s_hit[q] = (unsigned char)hit;
+    }
+    __syncthreads();
+    if (tid < 4) {
+      float al, sum;
+      sq_lane_box_sum(s_w, s_stage, K, S, tid, [&](int q) { return s_hit[q] != 0; }, al, sum);
+      const float mean = sum / al;
+      float var = 0.0f;
+      for (int k = 0, q = 0; k < K; ++k) {
+        const float w = s_w[k];
+        for (int s = 0; s < S; ++s, ++q) {
+          if (!s_hit[q]) continue;
+          const float dv = sq_box_coord(s_stage[q], tid) - mean;
+          var += w * (dv * dv);
+        }
+      }
+      if (tid == 0 && o.alive) o.alive[e] = al;
+      if (o.box_mean) o.box_mean[e * 4 + tid] = mean;
+      if (o.box_std) o.box_std[e * 4 + tid] = sqrtf(var / al);
+    }
+    __syncthreads();
+  }
+}
+int sq_launch_forecast_lane(const ForecastLaneArgs& a, hipStream_t s) {
+  SQ_LAUNCH(k_forecast_lane_start, dim3(a.B), dim3(256), 0, s, a);
+  SQ_LAUNCH(k_forecast_lane_frame, dim3(a.B, a.F), dim3(256), 0, s, a);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Lane estimates (sqair_set_estimate; LaneEstArgs in sqair_glue.h; the semantics: include/sqair_hip.h, points 1-8)
+// ------------------------------------------------------------------------------------------------
+// k_lane_estimate: workgroup (lane b, frame t, pixel chunk z).  Every workgroup forms the lane's weights at frame t; chunk z = 0 also
+// gives the lane's answer:
+//   thread k < K   its particle: n_k, and its association with the <= N best-row boxes in LDS, left as a K x N table of bytes;
+//   per object j   the K matched boxes are recomputed by their threads into a 4 KB stage (K x N boxes would be 64 KB), then
+//                  threads c < 4 reduce coordinate c, and the support, over k in index order.
+// Nothing is accumulated with atomics.  CANVAS: the instantiation that also averages the canvases (est.mean_canvas set); the other
+// one carries none of it.
+template <bool CANVAS>
+__global__ __launch_bounds__(256) void k_lane_estimate(const LaneEstArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ float s_w[SQ_MAX_K];        // a_k, e_k, then w_k
+  __shared__ SqBox s_stage[SQ_MAX_K];    // the boxes matched to the current best-row object
+  __shared__ unsigned char s_match[SQ_MAX_K * SQ_MAXN];
+  __shared__ unsigned char s_n[SQ_MAX_K];
+  __shared__ SqBox s_bbox[SQ_MAXN];      // the best row's boxes
+  __shared__ int s_bp[SQ_MAXN];          // ... and which of its slots are present
+  __shared__ float s_cp[SQ_MAXN + 1];
+  __shared__ SqLaneStats s_st;
+  const SqairLaneEstimate& o = a.est;
+  const LaneRows& v = a.rows;
+  const int b = blockIdx.x, t = blockIdx.y, tid = threadIdx.x, K = a.K, N = a.N, R = a.B * K, r = b * K + tid;
+  const bool lead = blockIdx.z == 0;
+  const size_t tb = (size_t)t * a.B + b, row0 = (size_t)t * R + (size_t)b * K;   // (frame t, particle 0 of lane b)
+  const float nan = __builtin_nanf("");
+  // ---- 1, 2: weights and the best row
+  sq_lane_weights<false>(tid < K ? sq_lane_log_weight<true>(o.log_w, a.lw, t + 1, R, r) : 0.0f, K, s_w, s_st);
+  const bool bad = s_st.best < 0;
+  if (lead) {
+    if (tid == 0) {
+      if (o.ess) o.ess[tb] = sq_lane_ess(s_st.S, s_st.Q);
+      o.best_row[tb] = bad ? -1 : b * K + s_st.best;
+    }
+    if (tid < K && o.weights) o.weights[tb * K + tid] = s_w[tid];
+    // ---- 4: the best row's slots -> the lane's objects and their boxes
+    const size_t best = row0 + (bad ? 0 : s_st.best);
+    sq_lane_best_objects(v, best, bad, N, a.H, a.W, tb * N, SqBestOut{o.presence, o.obj_id, o.where, o.box}, s_bp, s_bbox);
+    if (o.what)
+      for (int i = tid; i < N * a.nw; i += 256) {
+        const int j = i / a.nw, q = i - j * a.nw;
+        sq_put(o.what + tb * N * a.nw + i, s_bp[j] ? sq_word(a.what + (best * N + j) * a.what_ld + q) : 0u);
+      }
+    // ---- 3, 5: thread k's particle: its count, and per best-row object its first present slot of maximal IoU
+    if (tid < K)
+      s_n[tid] = (unsigned char)sq_lane_associate<false>(v, row0 + tid, N, a.H, a.W, o.iou_min, s_bp, s_bbox, s_match + tid * N,
+                                                         nullptr, nullptr);
+    __syncthreads();
+    // ---- 3: the count posterior (thread c), the expected count (thread N + 1), the first maximal count (thread 0)
+    if (tid <= N) {
+      float p = 0.0f;
+      for (int k = 0; k < K; ++k) p += s_n[k] == tid ? s_w[k] : 0.0f;
+      if (bad) p = nan;
+      s_cp[tid] = p;
+      if (o.count_prob) o.count_prob[tb * (N + 1) + tid] = p;
+    } else if (tid == N + 1 && o.expected_count) {
+      float cnt = 0.0f;
+      for (int k = 0; k < K; ++k) cnt += s_w[k] * (float)s_n[k];
+      o.expected_count[tb] = cnt;
+    }
+    __syncthreads();
+    if (tid == 0 && o.map_count) {
+      int best_c = 0;
+      for (int c = 1; c <= N; ++c)
+        if (s_cp[c] > s_cp[best_c]) best_c = c;
+      o.map_count[tb] = bad ? -1 : best_c;
+    }
+    // ---- 5: support and consensus box of every best-row object (the loop and its branches are uniform over the workgroup)
+    if (o.support || o.box_mean) {
+      for (int j = 0; j < N; ++j) {
+        const size_t e = tb * N + j;
+        if (!s_bp[j]) {   // absent: zero (a non-finite lane: NaN)
+          const float z = bad ? nan : 0.0f;
+          if (tid == 0 && o.support) o.support[e] = z;
+          if (tid < 4 && o.box_mean) o.box_mean[e * 4 + tid] = z;
+          continue;
+        }
+        const int mt = tid < K ? s_match[tid * N + j] : 255;
+        if (mt != 255) s_stage[tid] = sq_box_of_where(v.where + (sq_lane_slot(v, row0 + tid, N) + mt) * v.where_ld, a.H, a.W);
+        __syncthreads();
+        if (tid < 4) {
+          float sup, sum;
+          sq_lane_box_sum(s_w, s_stage, K, 1, tid, [&](int k) { return s_match[k * N + j] != 255; }, sup, sum);
+          if (tid == 0 && o.support) o.support[e] = sup;
+          if (o.box_mean) o.box_mean[e * 4 + tid] = sum / sup;
+        }
+        __syncthreads();
+      }
+    }
+  }
+  // ---- 6: the posterior mean reconstruction, this workgroup's chunk of pixels
+  if (CANVAS) {
+    const int P = a.H * a.W, p0 = blockIdx.z * SQ_EST_PIXELS;
+    for (int p = p0 + tid; p < min(p0 + SQ_EST_PIXELS, P); p += 256)
+      o.mean_canvas[tb * P + p] = sq_lane_mean_pixel(s_w, a.canvas, row0, P, p, K);
+  }
+}
+int sq_launch_lane_estimate(const LaneEstArgs& a, hipStream_t s) {
+  const int P = a.H * a.W, nz = a.est.mean_canvas ? (P + SQ_EST_PIXELS - 1) / SQ_EST_PIXELS : 1;
+  if (a.est.mean_canvas) SQ_LAUNCH(k_lane_estimate<true>, dim3(a.B, a.T, nz), dim3(256), 0, s, a);
+  else SQ_LAUNCH(k_lane_estimate<false>, dim3(a.B, a.T, nz), dim3(256), 0, s, a);
+  return 0;
+}

@@ -2,7 +2,7 @@
 // registration on a handle (sqair_set_state / sqair_set_smc / sqair_set_history / sqair_set_observed), the refusals of the passes and carried training calls a state rules
 // out, the settings one pass resolves them to (SqStateRes: the handle's, or a SqairCarry's), and the forecast that rolls the prior
 // forward from a state (sqair_forecast).  Host code only; the pass that imports / exports / resamples the state is
-// sq_forward_impl (sqair_api.hip), the kernels live in sqair_glue.hip.
+// sq_forward_impl (sqair_api.hip), the kernels live in sqair_glue.hip and sqair_lane.hip.
 #include "sqair_internal.h"
 #include "sqair_chain.h"
 
@@ -172,8 +172,8 @@ int sq_estimate_refusal(SqairHandle* h, int T, const SqairOutputs* outp) {
 LaneEstArgs sq_estimate_args(const SqairHandle* h, const float* rec, const SqairOutputs& out, int T, int B) {
   const SqairConfig& c = h->cfg;
   LaneEstArgs a; memset(&a, 0, sizeof(a));
-  a.where = rec + rec::WHERE; a.presence = rec + rec::PRES; a.obj_id = rec + rec::ID; a.what = rec + rec::WHAT;
-  a.where_ld = a.pres_ld = a.id_ld = a.what_ld = rec::W;
+  a.rows = LaneRows{rec + rec::WHERE, rec::W, rec + rec::PRES, rec::W, rec + rec::ID, rec::W, 1};
+  a.what = rec + rec::WHAT; a.what_ld = rec::W;
   a.canvas = out.canvas; a.lw = out.log_weights_per_timestep; a.est = h->est;
   a.T = T; a.B = B; a.K = c.k_particles; a.N = c.n_steps_per_image; a.nw = c.n_what; a.H = c.img_h; a.W = c.img_w;
   return a;
@@ -193,7 +193,7 @@ extern "C" int sqair_lane_estimate_test(SqairHandle* h, const float* where, cons
   if (est->what && !what) return sq_no(h, who + "est->what needs what");
   if (est->mean_canvas && !canvas) return sq_no(h, who + "est->mean_canvas needs canvas");
   LaneEstArgs a; memset(&a, 0, sizeof(a));
-  a.where = where; a.where_ld = 4; a.presence = presence; a.pres_ld = 1; a.obj_id = obj_id; a.id_ld = 1;
+  a.rows = LaneRows{where, 4, presence, 1, obj_id, 1, 1};
   a.what = what; a.what_ld = c.n_what; a.canvas = canvas; a.lw = lw; a.est = *est;
   a.T = T; a.B = B; a.K = K; a.N = c.n_steps_per_image; a.nw = c.n_what; a.H = c.img_h; a.W = c.img_w;
   sq_launch_lane_estimate(a, (hipStream_t)stream);
@@ -509,10 +509,10 @@ static int sq_forecast_impl(SqairHandle* h, const bool fan, const float* flat_pa
   const float* rec_all = w.rec + (size_t)M * RW;
   if (lane) {   // the lane forecast needs only the records: frame 0 = the start rows (S copies of each), frames 1..F the rollouts
     ForecastLaneArgs la; memset(&la, 0, sizeof(la));
-    la.s_where = w.rec + rec::WHERE; la.s_pres = w.rec + rec::PRES; la.s_id = w.rec + rec::ID;
+    la.start = LaneRows{w.rec + rec::WHERE, RW, w.rec + rec::PRES, RW, w.rec + rec::ID, RW, S};
     la.where = rec_all + rec::WHERE; la.presence = rec_all + rec::PRES; la.obj_id = rec_all + rec::ID;
-    la.s_where_ld = la.s_pres_ld = la.s_id_ld = la.where_ld = la.pres_ld = la.id_ld = RW;
-    la.row_step = S; la.log_w = out.log_w; la.x = sq_forecast_lane_scratch(lane_scratch, B, K, N); la.lane = *lane;
+    la.where_ld = la.pres_ld = la.id_ld = RW;
+    la.log_w = out.log_w; la.x = sq_forecast_lane_scratch(lane_scratch, B, K, N); la.lane = *lane;
     la.F = F; la.B = B; la.K = K; la.S = S; la.N = N; la.H = c.img_h; la.W = c.img_w;
     sq_launch_forecast_lane(la, s);
   }
@@ -533,17 +533,10 @@ static int sq_forecast_impl(SqairHandle* h, const bool fan, const float* flat_pa
     }
   }
   if (out.mean_canvas || out.expected_count) {
-    if (S == 1) {
-      ForecastSummaryArgs sa; memset(&sa, 0, sizeof(sa));
-      sa.canvas = canvas; sa.rec = rec_all; sa.log_w = out.log_w; sa.mean_canvas = out.mean_canvas; sa.expected_count = out.expected_count;
-      sa.F = F;
-      sq_launch_forecast_summary(sa, d, s);
-    } else {
-      ForecastFanSummaryArgs sa; memset(&sa, 0, sizeof(sa));
-      sa.canvas = canvas; sa.rec = rec_all; sa.log_w = out.log_w; sa.mean_canvas = out.mean_canvas; sa.expected_count = out.expected_count;
-      sa.F = F; sa.B = B; sa.K = K; sa.S = S; sa.N = N; sa.P = c.img_h * c.img_w;
-      sq_launch_forecast_fan_summary(sa, s);
-    }
+    ForecastSummaryArgs sa; memset(&sa, 0, sizeof(sa));
+    sa.canvas = canvas; sa.rec = rec_all; sa.log_w = out.log_w; sa.mean_canvas = out.mean_canvas; sa.expected_count = out.expected_count;
+    sa.F = F; sa.B = B; sa.K = K; sa.S = S; sa.N = N; sa.P = c.img_h * c.img_w;
+    sq_launch_forecast_summary(sa, s);
   }
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
@@ -575,9 +568,9 @@ extern "C" int sqair_forecast_lane_test(SqairHandle* h, const float* start_where
     return sq_no(h, who + "scratch_bytes " + std::to_string(scratch_bytes) + " < sqair_forecast_lane_scratch_bytes(h, " + std::to_string(B) +
                     ", " + std::to_string(K) + ") = " + std::to_string(sqair_forecast_lane_scratch_bytes(h, B, K)));
   ForecastLaneArgs la; memset(&la, 0, sizeof(la));
-  la.s_where = start_where; la.s_pres = start_presence; la.s_id = start_obj_id; la.where = where; la.presence = presence; la.obj_id = obj_id;
-  la.s_where_ld = la.where_ld = 4; la.s_pres_ld = la.s_id_ld = la.pres_ld = la.id_ld = 1;
-  la.row_step = 1; la.log_w = log_w; la.x = sq_forecast_lane_scratch((float*)scratch, B, K, c.n_steps_per_image); la.lane = *lane;
+  la.start = LaneRows{start_where, 4, start_presence, 1, start_obj_id, 1, 1};
+  la.where = where; la.where_ld = 4; la.presence = presence; la.pres_ld = 1; la.obj_id = obj_id; la.id_ld = 1;
+  la.log_w = log_w; la.x = sq_forecast_lane_scratch((float*)scratch, B, K, c.n_steps_per_image); la.lane = *lane;
   la.F = F; la.B = B; la.K = K; la.S = S; la.N = c.n_steps_per_image; la.H = c.img_h; la.W = c.img_w;
   sq_launch_forecast_lane(la, (hipStream_t)stream);
   SQ_CHECK_HIP(hipGetLastError());

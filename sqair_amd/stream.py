@@ -70,6 +70,16 @@ FORECAST_OUTPUTS = ("what", "where", "presence", "presence_prob", "presence_logi
 FORECAST_NOISE_TAG = 1 << 63
 
 
+def _field_views(shapes, int_fields, device):
+    """The fields {name: shape} as views of ONE float32 allocation, each 16-byte aligned (``int_fields``: viewed as int32), so that
+    they are copied out with one launch instead of one per field.  Returns (flat, views): views(flat or a clone of it) -> {name: view}."""
+    sizes = {n: int(np.prod(shp)) for n, shp in shapes.items()}
+    offs = dict(zip(sizes, np.cumsum([0] + [(s + 3) // 4 * 4 for s in sizes.values()]).tolist()))
+    flat = torch.zeros(offs[list(sizes)[-1]] + sizes[list(sizes)[-1]], dtype=torch.float32, device=device)
+    return flat, lambda flat: {n: (flat[offs[n]:offs[n] + sizes[n]].view(torch.int32) if n in int_fields
+                                   else flat[offs[n]:offs[n] + sizes[n]]).view(shapes[n]) for n in shapes}
+
+
 class SqairStream(object):
     def __init__(self, core, B, frames_per_step=1, outputs=DEFAULT_OUTPUTS, use_graph=True, seed=0, resample=None, ess_frac=0.5,
                  state=None, history=None, history_fields=tuple(_capi.HISTORY_FIELDS), missing=False, estimate=False,
@@ -159,17 +169,8 @@ class SqairStream(object):
         """The device buffers k_lane_estimate writes (include/sqair_hip.h: SqairLaneEstimate), by field: views of ONE allocation
         (``_est_flat``), so that a step copies them out with one launch instead of one per field."""
         core = self.core
-        T, B, K, N = self.T, self.B, self.K, core.N
-        shapes = dict(best_row=(T, B), weights=(T, B, K), ess=(T, B), count_prob=(T, B, N + 1), expected_count=(T, B),
-                      map_count=(T, B), presence=(T, B, N), obj_id=(T, B, N), where=(T, B, N, 4), what=(T, B, N, core.nw),
-                      box=(T, B, N, 4), support=(T, B, N), box_mean=(T, B, N, 4))
-        if canvas:
-            shapes["mean_canvas"] = (T, B, core.H, core.W)
-        sizes = {n: int(np.prod(shp)) for n, shp in shapes.items()}
-        offs = dict(zip(sizes, np.cumsum([0] + [(s + 3) // 4 * 4 for s in sizes.values()]).tolist()))   # (16-byte aligned fields)
-        self._est_flat = torch.zeros(offs[list(sizes)[-1]] + sizes[list(sizes)[-1]], dtype=torch.float32, device=core.device)
-        self._est_views = lambda flat: {n: (flat[offs[n]:offs[n] + sizes[n]].view(torch.int32) if n in _capi.ESTIMATE_INT_FIELDS
-                                            else flat[offs[n]:offs[n] + sizes[n]]).view(shapes[n]) for n in shapes}
+        shapes = _capi.estimate_shapes(self.T, self.B, self.K, core.N, core.nw, (core.H, core.W) if canvas else None)
+        self._est_flat, self._est_views = _field_views(shapes, _capi.ESTIMATE_INT_FIELDS, core.device)
         return self._est_views(self._est_flat)
 
     # ---- source map -------------------------------------------------------------------------------------------------------
@@ -337,13 +338,9 @@ class SqairStream(object):
             raise RuntimeError("sqair_forecast_workspace_bytes failed")
         fc = dict(ws=z(nb // 4), noise=z((F, R, 2, N, core.nzw)), src=z(self.R, torch.int32), log_w=z(self.R),
                   out={n: z(shapes[n]) for n in outputs})
-        if lane:   # the fields of SqairForecastLane as views of ONE allocation, 16-byte aligned
-            lshapes = _capi.forecast_lane_shapes(F, B, self.K, N)
-            sizes = {n: int(np.prod(shp)) for n, shp in lshapes.items()}
-            offs = dict(zip(sizes, np.cumsum([0] + [(s + 3) // 4 * 4 for s in sizes.values()]).tolist()))
-            fc["lane_flat"] = z(offs[list(sizes)[-1]] + sizes[list(sizes)[-1]])
-            fc["lane_views"] = lambda flat: {n: (flat[offs[n]:offs[n] + sizes[n]].view(torch.int32) if n in _capi.FORECAST_LANE_INT_FIELDS
-                                                 else flat[offs[n]:offs[n] + sizes[n]]).view(lshapes[n]) for n in lshapes}
+        if lane:   # the fields of SqairForecastLane as views of ONE allocation
+            fc["lane_flat"], fc["lane_views"] = _field_views(_capi.forecast_lane_shapes(F, B, self.K, N), _capi.FORECAST_LANE_INT_FIELDS,
+                                                             core.device)
             fc["lane"] = fc["lane_views"](fc["lane_flat"])
         return fc
 
