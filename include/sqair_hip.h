@@ -316,6 +316,69 @@ typedef struct SqairTraceOutputs {
 } SqairTraceOutputs;
 int sqair_history_trace(SqairHandle* h, void* ring, const int32_t* src_next, int lag, const SqairTraceOutputs* out,
                         void* stream);
+/* ---- lane tracks: one smoothed trajectory per object of a lane ---------------------------------------------------------------
+ * sqair_history_trace answers per particle row: K ancestral paths per lane.  sqair_history_trace_lane runs the same trace and then
+ * turns the K traced paths of a lane into one answer per object of the lane -- where it was, frame by frame, with the weight of the
+ * particles that agree and their spread: the backward-looking twin of the lane forecast (SqairForecastLane), by the same device
+ * functions, so that between the same two steps both list the same objects in the same order and past and future join into one
+ * trajectory per object.  R = B*K, F = lag*T, frames oldest -> newest.  Row r of traced frame f is the trace's gathered row: its
+ * ancestor's stored words (zero where invalid) plus valid[f, r].  log_w [R] (NULL: uniform) weighs the traced rows: with src_next
+ * the weights of the rows the next pass would start from.  Per lane b:
+ * 1. Weights and best row: sqair_forecast_fan's point 1 on log_w, the same device helpers: weights[b,k] = w_k, best_row[b] = b*K +
+ *    the first k of maximal log weight.
+ * 2. The lane's objects are the slots j of the best row's NEWEST traced frame (f = F-1): presence, obj_id [B,N] copied words,
+ *    box0 [B,N,4] = (y, x, h, w) in pixels; all zero where the slot is absent or where that frame of the best row is invalid.
+ * 3. Association, ONCE, on frame F-1, by sqair_set_estimate's point 5: per object j and particle k, m* = the first present slot of
+ *    k's row of maximal IoU with box0[j]; k is associated with j when that IoU >= iou_min, and the obj_id word of slot m* is the id
+ *    FOLLOWED back along k's path.  A particle whose frame F-1 is invalid is associated with nothing.
+ *    support[b,j] = sum_k w_k [k associated].
+ * 4. Per frame f and object j, over the particles k that are associated, valid at f, and hold a present slot of their row at f
+ *    whose obj_id word equals the followed id (an exact compare; the first such slot):
+ *      alive[f,b,j]    = sum w_k             (unnormalised; alive[F-1] is support bit for bit)
+ *      box_mean[f,b,j] = sum w_k box_k / alive
+ *      box_std[f,b,j]  = sqrt(sum w_k (box_k - box_mean)^2 / alive)      (two passes in fp32, as the forecast's)
+ *    Where alive is 0 (an object born inside the window, at older frames) the box statistics are NaN.  An absent object gives zeros.
+ * 5. count_prob[f,b,c] = sum_k w_k [k valid at f and holds c present slots], c = 0..N;  valid_mass[f,b] = sum_k w_k [k valid at f].
+ *    Both are left UNNORMALISED: count_prob[f,b,:] sums to valid_mass[f,b], not to 1 -- the mass of the paths that reach back to f.
+ * 6. first_frame[b,j] (int32): the oldest f from which the best row's own path holds the id word obj_id[b,j] present in every
+ *    frame up to F-1; -1 for an absent object.
+ * 7. Every sum over particles is ONE thread's loop over k in index order: no float atomics, the same bits eager or replayed.
+ *    Non-finite lanes follow sqair_forecast_fan's point 7: NaN weights, support, alive, box_mean, box_std, count_prob and
+ *    valid_mass, best_row = -1 and no objects (presence, obj_id, box0 zero, first_frame -1).
+ * 8. Writes only `out`, `lane`, the scratch (sqair_trace_lane_scratch_bytes(h, B, K) bytes of device memory) and the ring's trace
+ *    scratch: capturable, and it interleaves with passes as sqair_history_trace does.  Two launches on top of the trace's.
+ * Every pointer of SqairTraceLane is optional except best_row.
+ * Refused (return -1, text in sqair_last_error, before any HIP call): everything sqair_history_trace refuses; a NULL lane or
+ * best_row; iou_min NaN or outside (0, 1]; K > 256; lag * T > 65535; a NULL scratch or scratch_bytes too small; a NULL out->where,
+ * out->presence, out->obj_id or out->valid (the lane kernels read the gathered rows).
+ * Out of scope: objects that left the scene before frame F-1 are not part of the answer -- the per-row track table (track_id ...)
+ * serves them; anchoring departed objects at their last present frame is a later step. */
+typedef struct SqairTraceLane {
+  float iou_min;             /* in (0, 1] */
+  int32_t* best_row;         /* [B] required */
+  float* weights;            /* [B,K] */
+  float* obj_id;             /* [B,N] */
+  float* presence;           /* [B,N] */
+  float* box0;               /* [B,N,4] (y, x, h, w) in pixels, at frame F-1 */
+  float* support;            /* [B,N] */
+  int32_t* first_frame;      /* [B,N] */
+  float* alive;              /* [F,B,N] */
+  float* box_mean;           /* [F,B,N,4] */
+  float* box_std;            /* [F,B,N,4] */
+  float* count_prob;         /* [F,B,N+1] unnormalised */
+  float* valid_mass;         /* [F,B] */
+} SqairTraceLane;
+int64_t sqair_trace_lane_scratch_bytes(const SqairHandle* h, int B, int K);   /* -1: bad arguments (K outside 1..256) */
+int sqair_history_trace_lane(SqairHandle* h, void* ring, const int32_t* src_next, int lag, const SqairTraceOutputs* out,
+                             const float* log_w /*[R] or NULL: uniform*/, const SqairTraceLane* lane, void* scratch,
+                             int64_t scratch_bytes, void* stream);
+/* Kernel-level check of the lane tracks (tests): the two lane kernels on caller tensors, no ring and no trace, any K in 1..256, the
+ * handle's N, H, W.  where [F,B*K,N,4], presence, obj_id [F,B*K,N]: the traced rows, frames oldest -> newest; valid [F,B*K] int32;
+ * log_w [B*K] or NULL.  Refused (return -1, before any HIP call): a NULL where / presence / obj_id / valid / lane / scratch, F (1 ..
+ * 65535), B or K out of range, what lane refuses, scratch_bytes < sqair_trace_lane_scratch_bytes(h, B, K). */
+int sqair_track_lane_test(SqairHandle* h, const float* where, const float* presence, const float* obj_id, const int32_t* valid,
+                          const float* log_w, int F, int B, int K, const SqairTraceLane* lane, void* scratch, int64_t scratch_bytes,
+                          void* stream);
 
 /* ---- forecasting: the generative prior rolled forward from a carried state ------------------------------------------------
  * A forecast of F frames starts from the rows the NEXT pass would start from: state_in of sqair_set_state gathered through a source
@@ -503,7 +566,8 @@ int sqair_set_observed(SqairHandle* h, const int32_t* observed /* device [T,B]; 
  * at pass time: a pass of another T, a NULL out->log_weights_per_timestep, mean_canvas without out->canvas, SMC on with another
  * log_w.  The objects are read from the pass's own merged slot records, not from its SqairOutputs buffers: those need not be
  * bound.  sqair_set_state switching the state off, or to another B, switches the estimate off.
- * Out of scope: estimates for training passes, smoothed (lagged) estimates -- sqair_history_trace plus best_row serve those. */
+ * Out of scope: estimates for training passes.  Smoothed (lagged) estimates are sqair_history_trace_lane's: one trajectory per object
+ * of a lane from the K traced paths. */
 typedef struct SqairLaneEstimate {
   float iou_min;             /* in (0, 1] */
   const float* log_w;        /* [B*K] in: carried log weights of the pass's rows; NULL = zeros */

@@ -119,6 +119,24 @@ class SqairTraceOutputs(C.Structure):
     _fields_ = [("T", C.c_int32), ("max_tracks", C.c_int32)] + [(n, C.c_void_p) for n in TRACE_FIELDS]
 
 
+# lane tracks (include/sqair_hip.h: sqair_history_trace_lane): the outputs of SqairTraceLane in declaration order, with their shapes
+# in terms of F = lag * T, B, K, N
+TRACK_LANE_FIELDS = ("best_row", "weights", "obj_id", "presence", "box0", "support", "first_frame", "alive", "box_mean", "box_std",
+                     "count_prob", "valid_mass")
+TRACK_LANE_INT_FIELDS = ("best_row", "first_frame")
+
+
+def track_lane_shapes(F, B, K, N):
+    return dict(best_row=(B,), weights=(B, K), obj_id=(B, N), presence=(B, N), box0=(B, N, 4), support=(B, N), first_frame=(B, N),
+                alive=(F, B, N), box_mean=(F, B, N, 4), box_std=(F, B, N, 4), count_prob=(F, B, N + 1), valid_mass=(F, B))
+
+
+class SqairTraceLane(C.Structure):
+    """One smoothed trajectory per object of a lane from its K traced paths (include/sqair_hip.h: sqair_history_trace_lane); every
+    pointer is a device address, all but best_row optional."""
+    _fields_ = [("iou_min", C.c_float)] + [(n, C.c_void_p) for n in TRACK_LANE_FIELDS]
+
+
 _PROTOS = {
     "sqair_abi_version": (C.c_int, []),
     "sqair_build_id": (C.c_char_p, []),
@@ -198,6 +216,10 @@ _PROTOS = {
     "sqair_history_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32]),
     "sqair_set_history": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_uint32]),
     "sqair_history_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SqairTraceOutputs), C.c_void_p]),
+    "sqair_trace_lane_scratch_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
+    "sqair_history_trace_lane": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SqairTraceOutputs), C.c_void_p,
+                                           C.POINTER(SqairTraceLane), C.c_void_p, C.c_int64, C.c_void_p]),
+    "sqair_track_lane_test": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 3 + [C.POINTER(SqairTraceLane), C.c_void_p, C.c_int64, C.c_void_p]),
     "sqair_set_observed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "sqair_set_estimate": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneEstimate), C.c_int, C.c_int]),
     "sqair_lane_estimate_test": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int, C.POINTER(SqairLaneEstimate), C.c_void_p]),

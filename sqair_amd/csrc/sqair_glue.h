@@ -440,6 +440,17 @@ struct ForecastLaneArgs {
   int F, B, K, S, N, H, W;
 };
 int sq_launch_forecast_lane(const ForecastLaneArgs& a, hipStream_t s);
+// Lane tracks (sqair_history_trace_lane; include/sqair_hip.h states the semantics): the lane forecast's two kernel bodies run backwards
+// in time over the K traced paths of a lane.  `f` is the forecast's block with S = 1: where / presence / obj_id = the traced rows
+// [F][R][N] (ld = 4, 1, 1), `start` = the view of their frame F - 1, `lane` = the outputs the two answers share (start_* NULL), the
+// same scratch.  What the tracks add: the rows' `valid` mask and the two outputs the forecast has no counterpart of.
+struct TrackLaneArgs {
+  ForecastLaneArgs f;
+  const int* valid;                    // [F][R]
+  int* first_frame;                    // [B][N] or NULL
+  float* valid_mass;                   // [F][B] or NULL
+};
+int sq_launch_track_lane(const TrackLaneArgs& a, hipStream_t s);
 
 struct CompactArgs {
   const float* rec_p; const float* rec_d; const float* rec_prev;

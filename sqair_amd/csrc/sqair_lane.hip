@@ -1,6 +1,6 @@
 // The per-lane answers: the kernels that turn a lane's K particle rows into one answer per lane -- the SMC resampler, the forecast
-// summaries, the lane estimate and the lane forecast.  None of them is a hop of the frame loop (once per pass or per call, on B
-// workgroups), and they are a translation unit -- a code object -- of their own so that work on them moves no kernel of the pass
+// summaries, the lane estimate, the lane forecast and the lane tracks.  None of them is a hop of the frame loop (once per pass or
+// per call, on B workgroups), and they are a translation unit -- a code object -- of their own so that work on them moves no kernel of the pass
 // (DESIGN.md section 3h).  Their compositions are the device functions of sqair_lane.h.  Every lane-wide sum is one thread's loop in
 // index order: the same bits on every replay, and K <= 256 adds are nothing next to the pass.
 #include "sqair_lane.h"
@@ -116,11 +116,15 @@ int sq_launch_forecast_summary(const ForecastSummaryArgs& a, hipStream_t s) {
   return 0;
 }
 
-// k_forecast_lane_start: workgroup = lane b.  The weights and the best row, the best START row's objects and boxes, then thread
-// k < K associates its particle's start row with them and leaves in the scratch, per (k, j), whether k is associated and the obj_id
-// word its rollouts are followed by -- every step k_lane_estimate's, by the same functions.
-__global__ __launch_bounds__(256) void k_forecast_lane_start(const ForecastLaneArgs a SQ_TLP) {
-  SQ_TL_SCOPE;
+// The start body of the lane forecast and of the lane tracks: workgroup = lane b.  The weights and the best row, the best START
+// row's objects and boxes, then thread k < K associates its particle's start row with them and leaves in the scratch, per (k, j),
+// whether k is associated and the obj_id word it is followed by -- every step k_lane_estimate's, by the same functions.  TRACK: the
+// start rows are the newest traced frame and carry a mask, `valid` [R]: an invalid row holds no objects and is associated with
+// nothing.  Returns, for the kernel's own epilogue, the lane's best particle (-1: a non-finite lane) and, to thread j < N, whether
+// best-row slot j is present.
+struct SqLaneStart { int best; int present; };
+template <bool TRACK>
+__device__ __forceinline__ SqLaneStart sq_lane_start(const ForecastLaneArgs& a, const int* __restrict__ valid) {
   __shared__ float s_w[SQ_MAX_K];        // a_k, e_k, then w_k
   __shared__ unsigned char s_match[SQ_MAX_K * SQ_MAXN];
   __shared__ SqBox s_bbox[SQ_MAXN];      // the best start row's boxes
@@ -138,21 +142,28 @@ __global__ __launch_bounds__(256) void k_forecast_lane_start(const ForecastLaneA
     if (o.weights) o.weights[r] = s_w[tid];
   }
   // ---- 2: the start records of the lane's rows (words copied), the best start row's objects and their boxes
-  for (int i = tid; i < K * N; i += 256) {
-    const int k = i / N;
-    const size_t src = sq_lane_slot(v, (size_t)(b * K + k), N) + (i - k * N), dst = (size_t)b * K * N + i;
-    if (o.start_presence) sq_put(o.start_presence + dst, sq_word(v.presence + src * v.pres_ld));
-    if (o.start_obj_id) sq_put(o.start_obj_id + dst, sq_word(v.obj_id + src * v.id_ld));
-    if (o.start_where)
-      for (int c = 0; c < 4; ++c) sq_put(o.start_where + dst * 4 + c, sq_word(v.where + src * v.where_ld + c));
-  }
-  sq_lane_best_objects(v, (size_t)(b * K + (bad ? 0 : s_st.best)), bad, N, a.H, a.W, (size_t)b * N,
-                       SqBestOut{o.presence, o.obj_id, nullptr, o.box0}, s_bp, s_bbox);
+  if (!TRACK)
+    for (int i = tid; i < K * N; i += 256) {
+      const int k = i / N;
+      const size_t src = sq_lane_slot(v, (size_t)(b * K + k), N) + (i - k * N), dst = (size_t)b * K * N + i;
+      if (o.start_presence) sq_put(o.start_presence + dst, sq_word(v.presence + src * v.pres_ld));
+      if (o.start_obj_id) sq_put(o.start_obj_id + dst, sq_word(v.obj_id + src * v.id_ld));
+      if (o.start_where)
+        for (int c = 0; c < 4; ++c) sq_put(o.start_where + dst * 4 + c, sq_word(v.where + src * v.where_ld + c));
+    }
+  const size_t best = (size_t)(b * K + (bad ? 0 : s_st.best));
+  sq_lane_best_objects(v, best, bad || (TRACK && !valid[best]), N, a.H, a.W, (size_t)b * N, SqBestOut{o.presence, o.obj_id, nullptr, o.box0},
+                       s_bp, s_bbox);
   if (tid < N) a.x.bp[(size_t)b * N + tid] = s_bp[tid];
   // ---- 3: thread k's particle: per best-row object its first present start slot of maximal IoU, and that slot's id word
-  if (tid < K)
-    sq_lane_associate<true>(v, (size_t)r, N, a.H, a.W, o.iou_min, s_bp, s_bbox, s_match + tid * N, a.x.fm + (size_t)r * N,
-                            a.x.fid + (size_t)r * N);
+  if (tid < K) {
+    if (TRACK && !valid[r]) {
+      for (int j = 0; j < N; ++j) { s_match[tid * N + j] = 255; a.x.fm[(size_t)r * N + j] = 0; a.x.fid[(size_t)r * N + j] = 0u; }
+    } else {
+      sq_lane_associate<true>(v, (size_t)r, N, a.H, a.W, o.iou_min, s_bp, s_bbox, s_match + tid * N, a.x.fm + (size_t)r * N,
+                              a.x.fid + (size_t)r * N);
+    }
+  }
   __syncthreads();
   if (tid < N && o.support) {
     const int j = tid;
@@ -163,13 +174,20 @@ __global__ __launch_bounds__(256) void k_forecast_lane_start(const ForecastLaneA
     }
     o.support[(size_t)b * N + j] = s_bp[j] ? sup : (bad ? __builtin_nanf("") : 0.0f);
   }
+  return SqLaneStart{bad ? -1 : s_st.best, tid < N ? s_bp[tid] : 0};
 }
-// k_forecast_lane_frame: workgroup (lane b, frame f), thread = rollout q of the lane (K*S <= SQAIR_FORECAST_FAN_MAX: up to four per
+__global__ __launch_bounds__(256) void k_forecast_lane_start(const ForecastLaneArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  sq_lane_start<false>(a, nullptr);
+}
+// The frame body of both: workgroup (lane b, frame f), thread = rollout q of the lane (K*S <= SQAIR_FORECAST_FAN_MAX: up to four per
 // thread).  The rollouts' counts give count_prob; per object j each associated rollout looks its followed id up among its present
 // slots and stages that slot's pixel box in LDS (16 bytes per rollout), then threads c < 4 reduce coordinate c in two passes, each
-// ONE thread's loop over q in index order.  No per-thread arrays: nothing to spill.
-__global__ __launch_bounds__(256) void k_forecast_lane_frame(const ForecastLaneArgs a SQ_TLP) {
-  SQ_TL_SCOPE;
+// ONE thread's loop over q in index order.  No per-thread arrays: nothing to spill.  TRACK (S = 1: rollout q = particle k's traced
+// row of frame f): a row with valid[q] == 0 counts nowhere -- not in count_prob, not as a hit -- and valid_mass is the weight left.
+template <bool TRACK>
+__device__ __forceinline__ void sq_lane_frame(const ForecastLaneArgs& a, const int* __restrict__ valid, float* valid_mass) {
+  constexpr unsigned char INVALID = 255;                // (a count is at most N <= 16)
   __shared__ float s_w[SQ_MAX_K];                       // w_k / S
   __shared__ SqBox s_stage[SQAIR_FORECAST_FAN_MAX];     // the box followed in rollout q
   __shared__ unsigned char s_hit[SQAIR_FORECAST_FAN_MAX];
@@ -183,7 +201,7 @@ __global__ __launch_bounds__(256) void k_forecast_lane_frame(const ForecastLaneA
   for (int q = tid; q < KS; q += 256) {
     int n = 0;
     for (int m = 0; m < N; ++m) n += a.presence[((row0 + q) * N + m) * a.pres_ld] != 0.0f ? 1 : 0;
-    s_n[q] = (unsigned char)n;
+    s_n[q] = TRACK && !valid[row0 + q] ? INVALID : (unsigned char)n;
   }
   __syncthreads();
   if (tid <= N && o.count_prob) {
@@ -193,6 +211,11 @@ __global__ __launch_bounds__(256) void k_forecast_lane_frame(const ForecastLaneA
       for (int s = 0; s < S; ++s, ++q) p += s_n[q] == tid ? w : 0.0f;
     }
     o.count_prob[fb * (N + 1) + tid] = bad ? nan : p;
+  }
+  if (TRACK && tid == N + 1 && valid_mass) {
+    float p = 0.0f;
+    for (int k = 0; k < K; ++k) p += s_n[k] != INVALID ? s_w[k] : 0.0f;
+    valid_mass[fb] = bad ? nan : p;
   }
   if (!o.alive && !o.box_mean && !o.box_std) return;
   for (int j = 0; j < N; ++j) {   // (the loop and its branches are uniform over the workgroup)
@@ -207,7 +230,7 @@ __global__ __launch_bounds__(256) void k_forecast_lane_frame(const ForecastLaneA
     for (int q = tid; q < KS; q += 256) {
       const size_t kj = (size_t)(b * K + q / S) * N + j;
       int hit = 0;
-      if (a.x.fm[kj]) {
+      if (a.x.fm[kj] && !(TRACK && s_n[q] == INVALID)) {
         const unsigned idw = a.x.fid[kj];
         for (int m = 0; m < N && !hit; ++m) {
           const size_t sl = (row0 + q) * N + m;
@@ -240,9 +263,55 @@ __global__ __launch_bounds__(256) void k_forecast_lane_frame(const ForecastLaneA
     __syncthreads();
   }
 }
+__global__ __launch_bounds__(256) void k_forecast_lane_frame(const ForecastLaneArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  sq_lane_frame<false>(a, nullptr, nullptr);
+}
 int sq_launch_forecast_lane(const ForecastLaneArgs& a, hipStream_t s) {
   SQ_LAUNCH(k_forecast_lane_start, dim3(a.B), dim3(256), 0, s, a);
   SQ_LAUNCH(k_forecast_lane_frame, dim3(a.B, a.F), dim3(256), 0, s, a);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Lane tracks (sqair_history_trace_lane; TrackLaneArgs in sqair_glue.h; the semantics: include/sqair_hip.h, points 1-8): the lane
+// forecast's bodies over the traced rows, frame F - 1 standing where the forecast's start rows stand.
+// ------------------------------------------------------------------------------------------------
+// k_track_lane_start: workgroup = lane b.  After the shared body, thread j < N walks the best row's own path back from frame F - 1
+// for as long as it is valid and holds object j's id word in a present slot: first_frame.
+__global__ __launch_bounds__(256) void k_track_lane_start(const TrackLaneArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  const ForecastLaneArgs& g = a.f;
+  const int b = blockIdx.x, j = threadIdx.x, N = g.N;
+  const size_t R = (size_t)g.B * g.K;
+  const SqLaneStart st = sq_lane_start<true>(g, a.valid + (size_t)(g.F - 1) * R);
+  if (j >= N || !a.first_frame) return;
+  int first = -1;
+  if (st.present) {
+    const size_t best = (size_t)b * g.K + st.best;
+    const unsigned idw = sq_word(g.obj_id + (((size_t)(g.F - 1) * R + best) * N + j) * g.id_ld);
+    for (int f = g.F - 1; f >= 0; --f) {
+      const size_t row = (size_t)f * R + best;
+      if (!a.valid[row]) break;
+      bool has = false;
+      for (int m = 0; m < N && !has; ++m) {
+        const size_t sl = row * N + m;
+        has = g.presence[sl * g.pres_ld] != 0.0f && sq_word(g.obj_id + sl * g.id_ld) == idw;
+      }
+      if (!has) break;
+      first = f;
+    }
+  }
+  a.first_frame[(size_t)b * N + j] = first;
+}
+// k_track_lane_frame: workgroup (lane b, frame f), thread k = the lane's traced row k of frame f
+__global__ __launch_bounds__(256) void k_track_lane_frame(const TrackLaneArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  sq_lane_frame<true>(a.f, a.valid, a.valid_mass);
+}
+int sq_launch_track_lane(const TrackLaneArgs& a, hipStream_t s) {
+  SQ_LAUNCH(k_track_lane_start, dim3(a.f.B), dim3(256), 0, s, a);
+  SQ_LAUNCH(k_track_lane_frame, dim3(a.f.B, a.f.F), dim3(256), 0, s, a);
   return 0;
 }
 

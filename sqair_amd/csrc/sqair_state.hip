@@ -329,35 +329,113 @@ HistPushArgs sq_history_push_args(const SqairHandle* h, const SqStateRes& st, co
   a.src = st.src; a.have_in = st.in != nullptr; a.t_row = t_row;
   return a;
 }
-extern "C" int sqair_history_trace(SqairHandle* h, void* ring, const int32_t* src_next, int lag, const SqairTraceOutputs* outp,
-                                   void* stream) {
-  if (!h) return -1;
-  if (!h->state_on || !h->hist_on) return sq_no(h, "sqair_history_trace: no history set (sqair_set_history)");
-  if (!ring || ring != h->hist_ring) return sq_no(h, "sqair_history_trace: ring must be the ring given to sqair_set_history");
+// the refusals of a trace and its argument block (host only): sqair_history_trace and sqair_history_trace_lane, one body
+static int sq_history_trace_args(SqairHandle* h, const std::string& who, void* ring, const int32_t* src_next, int lag,
+                                 const SqairTraceOutputs* outp, HistTraceArgs& a) {
+  if (!h->state_on || !h->hist_on) return sq_no(h, who + "no history set (sqair_set_history)");
+  if (!ring || ring != h->hist_ring) return sq_no(h, who + "ring must be the ring given to sqair_set_history");
   if (lag < 1 || lag > h->hist_L)
-    return sq_no(h, "sqair_history_trace: lag = " + std::to_string(lag) + " must lie in [1, L = " + std::to_string(h->hist_L) + "]");
-  if (!outp) return sq_no(h, "sqair_history_trace: out must not be NULL");
+    return sq_no(h, who + "lag = " + std::to_string(lag) + " must lie in [1, L = " + std::to_string(h->hist_L) + "]");
+  if (!outp) return sq_no(h, who + "out must not be NULL");
   const SqairTraceOutputs& o = *outp;
-  if (o.T < 1) return sq_no(h, "sqair_history_trace: out->T (frames per pass) must be >= 1");
+  if (o.T < 1) return sq_no(h, who + "out->T (frames per pass) must be >= 1");
   if (h->hist_T != 0 && o.T != h->hist_T)
-    return sq_no(h, "sqair_history_trace: out->T = " + std::to_string(o.T) + " but the passes pushed have T = " + std::to_string(h->hist_T));
+    return sq_no(h, who + "out->T = " + std::to_string(o.T) + " but the passes pushed have T = " + std::to_string(h->hist_T));
   if (h->hist_bytes < sqair_history_bytes(h, h->hist_L, o.T, h->state_B, h->hist_fields))
-    return sq_no(h, "sqair_history_trace: the ring is too small for passes of out->T = " + std::to_string(o.T) + " frames");
+    return sq_no(h, who + "the ring is too small for passes of out->T = " + std::to_string(o.T) + " frames");
   if ((o.what && !(h->hist_fields & SQAIR_HIST_WHAT)) || (o.log_w && !(h->hist_fields & SQAIR_HIST_LOG_W)))
-    return sq_no(h, "sqair_history_trace: what / log_w asked of a ring that was set without the field");
+    return sq_no(h, who + "what / log_w asked of a ring that was set without the field");
   const bool table = o.track_id || o.n_tracks || o.track_present || o.track_where;
   if (table && (o.max_tracks < 1 || o.max_tracks > SQ_HIST_MAX_TRACKS))
-    return sq_no(h, "sqair_history_trace: max_tracks must lie in [1, " + std::to_string(SQ_HIST_MAX_TRACKS) + "] for the track table");
-  HistTraceArgs a; memset(&a, 0, sizeof(a));
+    return sq_no(h, who + "max_tracks must lie in [1, " + std::to_string(SQ_HIST_MAX_TRACKS) + "] for the track table");
+  memset(&a, 0, sizeof(a));
   a.ring = (unsigned*)ring;
   a.lay = sq_hist_layout(h, h->hist_L, o.T, h->state_B, h->hist_fields);
   if ((int64_t)a.lay.R * lag > INT32_MAX || (int64_t)lag * o.T * a.lay.N * (table ? o.max_tracks : 1) > INT32_MAX)
-    return sq_no(h, "sqair_history_trace: lag * rows (or lag * T * N * max_tracks) beyond 2^31");
+    return sq_no(h, who + "lag * rows (or lag * T * N * max_tracks) beyond 2^31");
   a.src_next = src_next; a.lag = lag; a.M = table ? o.max_tracks : 1;
   a.where = o.where; a.presence = o.presence; a.obj_id = o.obj_id; a.what = o.what; a.log_w = o.log_w;
   a.valid = o.valid; a.frame_index = o.frame_index; a.ancestor_row = o.ancestor_row; a.unique_ancestors = o.unique_ancestors;
   a.track_id = o.track_id; a.n_tracks = o.n_tracks; a.track_present = o.track_present; a.track_where = o.track_where;
+  return 0;
+}
+extern "C" int sqair_history_trace(SqairHandle* h, void* ring, const int32_t* src_next, int lag, const SqairTraceOutputs* outp,
+                                   void* stream) {
+  if (!h) return -1;
+  HistTraceArgs a;
+  if (sq_history_trace_args(h, "sqair_history_trace: ", ring, src_next, lag, outp, a) != 0) return -1;
   sq_launch_history_trace(a, (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// lane tracks (include/sqair_hip.h: sqair_history_trace_lane): the trace, then the lane forecast's kernels run backwards over the
+// traced rows (TrackLaneArgs)
+// ------------------------------------------------------------------------------------------------
+extern "C" int64_t sqair_trace_lane_scratch_bytes(const SqairHandle* h, int B, int K) {
+  return sqair_forecast_lane_scratch_bytes(h, B, K);   // (the same weights, association and followed ids between the two launches)
+}
+static int sq_trace_lane_fields(SqairHandle* h, const std::string& who, const SqairTraceLane* l, int F, int B, int K, const void* scratch,
+                                int64_t scratch_bytes) {
+  if (!l) return sq_no(h, who + "lane must not be NULL");
+  if (!(l->iou_min > 0.0f && l->iou_min <= 1.0f)) return sq_no(h, who + "lane->iou_min must lie in (0, 1]");   // (NaN fails both)
+  if (!l->best_row) return sq_no(h, who + "lane->best_row must not be NULL");
+  if (K > SQ_MAX_K) return sq_no(h, who + "K = " + std::to_string(K) + " particles per lane, above " + std::to_string(SQ_MAX_K));
+  if (F > 65535) return sq_no(h, who + "F = " + std::to_string(F) + " traced frames, above 65535");
+  const int64_t need = sqair_trace_lane_scratch_bytes(h, B, K);
+  if (!scratch || scratch_bytes < need)
+    return sq_no(h, who + "scratch is NULL or scratch_bytes " + std::to_string(scratch_bytes) + " < sqair_trace_lane_scratch_bytes(h, " +
+                    std::to_string(B) + ", " + std::to_string(K) + ") = " + std::to_string(need));
+  return 0;
+}
+static TrackLaneArgs sq_track_lane_args(const SqairHandle* h, const float* where, const float* presence, const float* obj_id,
+                                        const int32_t* valid, const float* log_w, int F, int B, int K, const SqairTraceLane& l,
+                                        void* scratch) {
+  const SqairConfig& c = h->cfg;
+  const int N = c.n_steps_per_image;
+  const size_t last = (size_t)(F - 1) * B * K * N;   // slot 0 of row 0 of the newest frame
+  TrackLaneArgs a; memset(&a, 0, sizeof(a));
+  ForecastLaneArgs& g = a.f;
+  g.start = LaneRows{where + last * 4, 4, presence + last, 1, obj_id + last, 1, 1};
+  g.where = where; g.where_ld = 4; g.presence = presence; g.pres_ld = 1; g.obj_id = obj_id; g.id_ld = 1;
+  g.log_w = log_w; g.x = sq_forecast_lane_scratch((float*)scratch, B, K, N);
+  g.lane.iou_min = l.iou_min; g.lane.best_row = l.best_row; g.lane.weights = l.weights; g.lane.obj_id = l.obj_id;
+  g.lane.presence = l.presence; g.lane.box0 = l.box0; g.lane.support = l.support; g.lane.alive = l.alive; g.lane.box_mean = l.box_mean;
+  g.lane.box_std = l.box_std; g.lane.count_prob = l.count_prob;
+  g.F = F; g.B = B; g.K = K; g.S = 1; g.N = N; g.H = c.img_h; g.W = c.img_w;
+  a.valid = valid; a.first_frame = l.first_frame; a.valid_mass = l.valid_mass;
+  return a;
+}
+extern "C" int sqair_history_trace_lane(SqairHandle* h, void* ring, const int32_t* src_next, int lag, const SqairTraceOutputs* outp,
+                                        const float* log_w, const SqairTraceLane* lane, void* scratch, int64_t scratch_bytes,
+                                        void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_history_trace_lane: ";
+  HistTraceArgs a;
+  if (sq_history_trace_args(h, who, ring, src_next, lag, outp, a) != 0) return -1;
+  const int F = lag * outp->T, B = h->state_B, K = h->cfg.k_particles;
+  if (sq_trace_lane_fields(h, who, lane, F, B, K, scratch, scratch_bytes) != 0) return -1;
+  if (!outp->where || !outp->presence || !outp->obj_id || !outp->valid)
+    return sq_no(h, who + "the lane kernels read the gathered rows: out->where, out->presence, out->obj_id and out->valid must be bound");
+  sq_launch_history_trace(a, (hipStream_t)stream);
+  sq_launch_track_lane(sq_track_lane_args(h, outp->where, outp->presence, outp->obj_id, outp->valid, log_w, F, B, K, *lane, scratch),
+                       (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+// kernel-level check of the lane tracks (tests/test_track_lane_kernel.py): the two kernels on caller tensors, K given, no ring
+extern "C" int sqair_track_lane_test(SqairHandle* h, const float* where, const float* presence, const float* obj_id, const int32_t* valid,
+                                     const float* log_w, int F, int B, int K, const SqairTraceLane* lane, void* scratch,
+                                     int64_t scratch_bytes, void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_track_lane_test: ";
+  if (!where || !presence || !obj_id || !valid || !lane || !scratch)
+    return sq_no(h, who + "null where / presence / obj_id / valid / lane / scratch");
+  if (F < 1 || F > 65535 || B < 1 || K < 1 || K > SQ_MAX_K || (int64_t)F * B * K * h->cfg.n_steps_per_image > INT32_MAX)
+    return sq_no(h, who + "bad F / B / K (1 <= F <= 65535, 1 <= K <= " + std::to_string(SQ_MAX_K) + ", F * B * K * N within int32)");
+  if (sq_trace_lane_fields(h, who, lane, F, B, K, scratch, scratch_bytes) != 0) return -1;
+  sq_launch_track_lane(sq_track_lane_args(h, where, presence, obj_id, valid, log_w, F, B, K, *lane, scratch), (hipStream_t)stream);
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }

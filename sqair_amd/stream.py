@@ -121,7 +121,7 @@ class SqairStream(object):
         if state is not None:   # hand-over: the first step continues every row of the given blob
             cs.adopt(state)
         self._graph = False
-        self._tr = {}               # tracks() buffers of the LAST (lag, start, max_tracks, table) only
+        self._tr = {}               # tracks() buffers of the LAST (lag, start, max_tracks, table, lane, lane_iou) only
         self._fc = {}               # forecast buffers of the LAST (F, outputs, summaries, samples, lane) only: workspace, noise, map, weights, outputs
         self._smc_uniforms = None   # registered with the caller's uniforms (True) or Philox (False)
         core.stream.synchronize()
@@ -345,7 +345,7 @@ class SqairStream(object):
         return fc
 
     # ---- track history ----------------------------------------------------------------------------------------------------
-    def tracks(self, lag=None, start="next", max_tracks=None, table=True):
+    def tracks(self, lag=None, start="next", max_tracks=None, table=True, lane=False, lane_iou=0.5):
         """Traces every particle row's ancestral path back over the last ``lag`` steps (default: all ``history`` kept) on the
         device: frames oldest -> newest, F = lag * frames_per_step.  ``start="next"``: from the rows the next ``step()`` would
         start from (the pending source map; with SMC the map the resampler wrote: the equally weighted surviving set), as
@@ -358,7 +358,15 @@ class SqairStream(object):
         (the true count; above M: truncated), ``track_present`` [F, B*K, M], ``track_where`` [F, B*K, M, 4].  With
         ``start="next"`` also the particles' ``weights`` [B, K] (as ``forecast`` forms them) and ``best_row`` [B], the first row of
         maximal weight per lane.  Copies, valid on the current stream; nothing the steps read is written.  One set of buffers is
-        kept, for the last (lag, start, max_tracks, table) asked for."""
+        kept, for the last (lag, start, max_tracks, table, lane, lane_iou) asked for.
+        ``lane=True`` (needs ``start="next"``) adds ``lane``: one smoothed trajectory per object of each lane from its K traced paths
+        (include/sqair_hip.h: sqair_history_trace_lane), the backward-looking twin of ``forecast(lane=True)``, weighed by the weights
+        ``forecast`` would use: ``best_row`` [B], ``weights`` [B, K], the objects of the best row's newest frame ``obj_id``,
+        ``presence`` [B, N], ``box0`` [B, N, 4] and ``support`` [B, N] -- the same objects in the same order as the lane forecast taken
+        between the same two steps --, ``first_frame`` [B, N] (the oldest frame the best row's own path holds the object from), and
+        per traced frame ``alive`` [F, B, N] (the weight of the particles whose path holds the object there), ``box_mean`` /
+        ``box_std`` [F, B, N, 4] over them (NaN where none does), ``count_prob`` [F, B, N + 1] and ``valid_mass`` [F, B] (the weight of
+        the paths that reach back to the frame: ``count_prob`` sums to it, not to 1); ``lane_iou``: the association threshold."""
         core, cs = self.core, self.carried
         if cs.ring is None:
             raise ValueError("SqairStream.tracks: the stream keeps no history (SqairStream(..., history=L))")
@@ -370,22 +378,37 @@ class SqairStream(object):
         M = 2 * core.N if max_tracks is None else max_tracks
         if table and (isinstance(M, bool) or not isinstance(M, (int, np.integer)) or not 1 <= M <= 1024):
             raise ValueError("SqairStream.tracks: max_tracks must be an integer in [1, 1024]")
+        lane, lane_iou = bool(lane), float(lane_iou)
+        if lane and start != "next":
+            raise ValueError("SqairStream.tracks: lane=True requires start='next': the lane answer is weighed by the weights of the rows "
+                             "the next step starts from, as forecast()'s is")
+        if lane and not 0.0 < lane_iou <= 1.0:   # (NaN fails too)
+            raise ValueError("SqairStream.tracks: lane_iou must lie in (0, 1]")
         lag, M = int(lag), int(M)
-        key = (lag, start, M if table else None, bool(table))
+        key = (lag, start, M if table else None, bool(table), lane, lane_iou if lane else None)
         with torch.cuda.device(core.device):
             core._join_in()
             with core.on_stream():
                 tr = self._tr.get(key)
                 if tr is None:
                     self._tr.clear()
-                    tr = self._tr[key] = self._track_buffers(lag, M, table)
+                    tr = self._tr[key] = self._track_buffers(lag, M, table, lane)
                 src = None
                 if start == "next":
                     src, lw = cs.next_rows(tr["src"], tr["log_w"])
                 c_out = _capi.SqairTraceOutputs(T=self.T, max_tracks=M, **{n: t.data_ptr() for n, t in tr["out"].items()})
-                core.check(core.lib.sqair_history_trace(core.handle, cs.ring.data_ptr(), None if src is None else src.data_ptr(),
-                                                        lag, C.byref(c_out), core._stream()), "sqair_history_trace")
+                if lane:
+                    c_lane = _capi.SqairTraceLane(iou_min=lane_iou, **{n: t.data_ptr() for n, t in tr["lane"].items()})
+                    core.check(core.lib.sqair_history_trace_lane(core.handle, cs.ring.data_ptr(), src.data_ptr(), lag, C.byref(c_out),
+                                                                 lw.data_ptr(), C.byref(c_lane), tr["lane_scratch"].data_ptr(),
+                                                                 tr["lane_scratch"].numel() * 4, core._stream()),
+                               "sqair_history_trace_lane")
+                else:
+                    core.check(core.lib.sqair_history_trace(core.handle, cs.ring.data_ptr(), None if src is None else src.data_ptr(),
+                                                            lag, C.byref(c_out), core._stream()), "sqair_history_trace")
                 res = {k: v.clone() for k, v in tr["out"].items()}
+                if lane:   # (views of one allocation: one copy, not one per field)
+                    res["lane"] = tr["lane_views"](tr["lane_flat"].clone())
                 if start == "next":
                     w = res["weights"] = torch.softmax(lw.reshape(self.B, self.K), -1)
                     k = torch.arange(self.K, device=core.device)
@@ -394,7 +417,7 @@ class SqairStream(object):
             core._join_out()
         return res
 
-    def _track_buffers(self, lag, M, table):
+    def _track_buffers(self, lag, M, table, lane=False):
         core = self.core
         R, N, B, F = self.R, core.N, self.B, lag * self.T
         i32 = torch.int32
@@ -408,7 +431,16 @@ class SqairStream(object):
             shapes.update(track_id=((R, M), i32), n_tracks=((R,), i32), track_present=((F, R, M), None),
                           track_where=((F, R, M, 4), None))
         z = lambda shp, dt=None: torch.zeros(shp, dtype=dt or torch.float32, device=core.device)
-        return dict(src=z(R, i32), log_w=z(R), out={n: z(*sd) for n, sd in shapes.items()})
+        tr = dict(src=z(R, i32), log_w=z(R), out={n: z(*sd) for n, sd in shapes.items()})
+        if lane:   # the fields of SqairTraceLane as views of ONE allocation, and the scratch between the two lane launches
+            tr["lane_flat"], tr["lane_views"] = _field_views(_capi.track_lane_shapes(F, B, self.K, N), _capi.TRACK_LANE_INT_FIELDS,
+                                                             core.device)
+            tr["lane"] = tr["lane_views"](tr["lane_flat"])
+            nb = core.lib.sqair_trace_lane_scratch_bytes(core.handle, B, self.K)
+            if nb < 0:
+                raise RuntimeError("sqair_trace_lane_scratch_bytes failed")
+            tr["lane_scratch"] = z(nb // 4)
+        return tr
 
     def close(self):
         """Switches the estimate, the history and the carried state off on the core's handle (its passes start from the initial

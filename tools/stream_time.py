@@ -19,6 +19,11 @@ node; the push is one node too.  Also the time of tracks() at lag 10 and lag 64,
 
     python tools/stream_time.py --history [--out profiles/stream_history_time.json]
 
+With --history --lane: the price of the lane tracks (SqairStream.tracks(lag, lane=True), include/sqair_hip.h:
+sqair_history_trace_lane) against the plain tracks(lag) of the same run, lag 10 and 64 at cfg-2's batch, alternating in one process.
+
+    python tools/stream_time.py --history --lane [--out profiles/track_lane_time.json]
+
 With --missing: the price of missing-frame steps (SqairStream(missing=True), include/sqair_hip.h: sqair_set_observed).  Streams at
 cfg-2's batch alternating in one process as with --history: plain, ``missing=True`` with every lane observed, ``missing=True`` with
 no lane observed -- and SMC on, for the yardstick: the same run's SMC on - SMC off difference is the price of one dependent node
@@ -170,6 +175,39 @@ def time_history(B, K, N, steps, warmup, L=64, rounds=10, hw=(50, 50)):
     return res
 
 
+def time_track_lane(B, K, N, warmup, L=64, rounds=10, block=10, hw=(50, 50)):
+    """The price of the lane tracks: tracks(lag, lane=True) against plain tracks(lag) (the trace, no table in either), lag 10 and L,
+    the ring full.  Two SMC + history streams fed the same frames in ONE process -- a stream keeps one set of tracks() buffers, so
+    each leg has its own -- called in alternating blocks, every call waited for (latency)."""
+    smc = dict(resample="systematic", ess_frac=0.5, history=L)
+    legs = dict(tracks=smc, tracks_lane=dict(smc))
+    streams, res, _, _ = alternating_streams(legs, B, K, N, max(L, rounds), warmup, rounds, hw)
+    res = dict(B=B, K=K, N=N, hw=list(hw), L=L, rounds=rounds, calls_per_leg=rounds * block, ms={}, lane_minus_plain_us={},
+               lane_over_plain={})
+    calls = dict(tracks=lambda st, lag: st.tracks(lag=lag, table=False), tracks_lane=lambda st, lag: st.tracks(lag=lag, table=False, lane=True))
+    for lag in (10, L):
+        ms = {n: [] for n in legs}
+        for rnd in range(-1, rounds):   # (round -1: the warm-up, every leg allocates its buffers)
+            for name, st in streams.items():
+                with st.core.on_stream():
+                    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(block)]
+                    for x, y in ev:
+                        x.record()
+                        calls[name](st, lag)
+                        y.record()
+                        st.core.stream.synchronize()
+                if rnd >= 0:
+                    ms[name] += [x.elapsed_time(y) for x, y in ev]
+        med = {n: float(np.median(v)) for n, v in ms.items()}
+        key = "lag{}".format(lag)
+        res["ms"][key] = {n: dict(median=med[n], p10=float(np.percentile(v, 10)), p90=float(np.percentile(v, 90))) for n, v in ms.items()}
+        res["lane_minus_plain_us"][key] = 1e3 * (med["tracks_lane"] - med["tracks"])
+        res["lane_over_plain"][key] = med["tracks_lane"] / med["tracks"]
+    for st in streams.values():
+        st.close()
+    return res
+
+
 def time_missing(B, K, N, steps, warmup, rounds=10, hw=(50, 50)):
     legs = dict(plain={}, smc=dict(resample="systematic", ess_frac=0.5), missing_all_observed=dict(missing=True),
                 missing_none_observed=dict(missing=True))
@@ -211,6 +249,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--smc", action="store_true", help="SMC resampling off / ess_frac 0.5 / 1.0 (profiles/stream_time_smc.json)")
     ap.add_argument("--history", action="store_true", help="plain / SMC / history / SMC + history, alternating (profiles/stream_history_time.json)")
+    ap.add_argument("--lane", action="store_true", help="with --history: tracks(lag, lane=True) against tracks(lag), alternating (profiles/track_lane_time.json)")
     ap.add_argument("--missing", action="store_true", help="plain / SMC / a mask with every lane / with no lane observed, alternating (profiles/stream_missing_time.json)")
     ap.add_argument("--estimate", action="store_true", help="plain / SMC / estimate / SMC + estimate / with mean_canvas, alternating (profiles/stream_estimate_time.json)")
     args = ap.parse_args()
@@ -220,6 +259,8 @@ def main():
         shapes = [dict(name="cfg2_batch_estimate", **time_estimate(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
     elif args.missing:
         shapes = [dict(name="cfg2_batch_missing", **time_missing(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
+    elif args.history and args.lane:
+        shapes = [dict(name="cfg2_batch_track_lane", **time_track_lane(32, ov["k_particles"], ov["n_steps_per_image"], args.warmup))]
     elif args.history:
         shapes = [dict(name="cfg2_batch_history", **time_history(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
     elif args.smc:
