@@ -594,6 +594,56 @@ int sqair_set_estimate(SqairHandle* h, const SqairLaneEstimate* est /* NULL: off
 int sqair_lane_estimate_test(SqairHandle* h, const float* where, const float* presence, const float* obj_id, const float* what,
                              const float* canvas, const float* lw, int T, int B, int K, const SqairLaneEstimate* est, void* stream);
 
+/* ---- object layers: per-object appearance, coverage and pixel owners of a lane, inside the pass --------------------------------
+ * The estimate says how many objects a lane holds and where; the layers say which pixels each of them occupies and what it looks
+ * like there: the object's segmentation and its appearance on the frame.  The decoder draws the canvas as a sum over slots of
+ * inverse-warped glimpses plus a written-to mask; the layers are that sum taken apart per object of the lane.  With layers set, every
+ * following inference pass with a carried state and an estimate runs one more kernel, k_lane_layers, directly after
+ * k_lane_estimate and BEFORE the SMC resampler, which zeroes the weights.  A pass with layers on has exactly one kernel node more;
+ * with layers off nothing is launched and every other output, blob and accumulator is unchanged bit for bit.  Training passes never
+ * run it.  It reads the pass's own decoded glimpses and merged slot records: neither needs to be bound as an output.
+ * For frame t of the pass, row r and slot m with where logits wl, presence p and decoded glimpse g [G, G], two images [H, W]:
+ *   V(r, m) = p * (inverse spatial transformer of g),  O(r, m) = p * (inverse spatial transformer of a glimpse of ones)
+ * -- what the decoder adds into its canvas and its written-to mask for that slot, by the decoder's own device functions
+ * (sq_canvas_coord, sq_canvas_tap, the to_coords of the crop and insert kernels); a pixel outside the slot's box receives exactly 0.
+ * For lane b, rows r = b*K + k:
+ * 1. Shared quantities.  The weights w_k, the best row, the best row's objects j and the association of every particle with them are
+ *    sqair_set_estimate's points 1, 2, 4 and 5, computed by the same device functions, with the estimate's iou_min and log_w.
+ * 2. match[t,b,k,j] (int32) = the slot m* of particle k associated with best-row object j; -1 when k does not agree on j, when j is
+ *    absent, or when the lane is non-finite.  It is the table the estimate builds for its support: with it a caller gathers any
+ *    per-row output per object of the lane.
+ * 3. For each present j, A_j = {k : match[t,b,k,j] >= 0} and s_j = sum over A_j of w_k -- the estimate's support, summed in the same
+ *    order.  layer[t,b,j] = sum over A_j of w_k V(b*K + k, match[t,b,k,j]) / s_j, cover[t,b,j] the same with O: [H, W] in fp32, k in
+ *    index order, one thread per pixel, no float atomics: the same bits on every replay, eager or graph.  Absent j: zeros.  The best
+ *    row always agrees with itself, so s_j >= w_best > 0: a convex combination.
+ * 4. owner[t,b,y,x] (int32) = the first present j of maximal cover[t,b,j,y,x] if that maximum is >= cover_min, else -1
+ *    (background).  A NaN never wins.
+ * 5. Non-finite lanes follow the estimate's rule 7: layer and cover are NaN, match and owner -1; finite lanes of the same launch
+ *    are unaffected.
+ * 6. Coasted (frame, lane)s need no special case: the decoder ran on their coasted records.
+ * 7. Consequence.  At K = 1, layer[j] = V(best, j), so sum_j layer[j] + mean_img * sigmoid(-10 + 20 sum_j cover[j]) is the pass's own
+ *    canvas of that row.
+ * Every pointer of SqairLaneLayers is optional, at least one must be set; owner needs no cover bound.  Pointers are remembered by the
+ * handle and frozen into captured graphs.  NULL lay: off.  Refused (return -1, text in sqair_last_error, before any HIP call): no
+ * estimate set (sqair_set_estimate), a T other than the estimate's, a B other than the state's, cover_min NaN or outside (0, 1], all
+ * four pointers NULL; at pass time: a pass of another T.  sqair_set_estimate switching the estimate off or to another T, and
+ * sqair_set_state switching the state off or to another B, switch the layers off.
+ * Out of scope: layers of forecasts and of lane tracks, per-particle-row layers, one-to-one matching, layers for training passes. */
+typedef struct SqairLaneLayers {
+  float cover_min;           /* in (0, 1] */
+  int32_t* match;            /* [T,B,K,N] */
+  float* layer;              /* [T,B,N,H,W] */
+  float* cover;              /* [T,B,N,H,W] */
+  int32_t* owner;            /* [T,B,H,W] */
+} SqairLaneLayers;
+int sqair_set_layers(SqairHandle* h, const SqairLaneLayers* lay /* NULL: off */, int T, int B);
+/* Kernel-level check of the layers (tests): the kernel above on caller buffers, no state and no pass, any K in 1..256 with the
+ * handle's N, G, H, W.  glimpse [T,B*K,N,G,G], where [T,B*K,N,4], presence [T,B*K,N], lw [T,B*K] standing for the pass's
+ * log_weights_per_timestep, log_w [B*K] or NULL (zeros).  Refused (return -1, before any HIP call): a NULL glimpse / where / presence
+ * / lw / lay, T, B or K out of range, iou_min NaN or outside (0, 1], what sqair_set_layers refuses for lay. */
+int sqair_lane_layers_test(SqairHandle* h, const float* glimpse, const float* where, const float* presence, const float* lw,
+                           const float* log_w, float iou_min, int T, int B, int K, const SqairLaneLayers* lay, void* stream);
+
 /* ---- objective ---------------------------------------------------------------------------------
  * Fused IWAE / VIMCO reductions over [T,B,K] (reference: Model._build sqair/model.py:88-103,
  * targets.iwae / vimco_control_variate / vimco sqair/targets.py:38-75, make_target model.py:150-158,

@@ -107,6 +107,23 @@ class SqairLaneEstimate(C.Structure):
     _fields_ = [("iou_min", C.c_float), ("log_w", C.c_void_p)] + [(n, C.c_void_p) for n in ESTIMATE_FIELDS]
 
 
+# object layers (include/sqair_hip.h: sqair_set_layers): the outputs of SqairLaneLayers in declaration order; the two int32 ones
+LAYERS_FIELDS = ("match", "layer", "cover", "owner")
+LAYERS_INT_FIELDS = ("match", "owner")
+
+
+def layers_shapes(T, B, K, N, hw):
+    """The outputs' shapes for passes of T frames over frames of ``hw`` = (H, W)."""
+    hw = tuple(hw)
+    return dict(match=(T, B, K, N), layer=(T, B, N) + hw, cover=(T, B, N) + hw, owner=(T, B) + hw)
+
+
+class SqairLaneLayers(C.Structure):
+    """Per-object appearance, coverage and pixel owners of a lane (include/sqair_hip.h: sqair_set_layers); every pointer is a
+    device address, each optional, at least one set."""
+    _fields_ = [("cover_min", C.c_float)] + [(n, C.c_void_p) for n in LAYERS_FIELDS]
+
+
 # track history (include/sqair_hip.h: sqair_set_history): the bit of each field a ring slot may hold; the first three are mandatory
 HISTORY_FIELDS = {"where": 1, "presence": 2, "obj_id": 4, "what": 8, "log_weights_per_timestep": 16}
 HISTORY_MANDATORY = ("where", "presence", "obj_id")
@@ -223,6 +240,8 @@ _PROTOS = {
     "sqair_set_observed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "sqair_set_estimate": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneEstimate), C.c_int, C.c_int]),
     "sqair_lane_estimate_test": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int, C.POINTER(SqairLaneEstimate), C.c_void_p]),
+    "sqair_set_layers": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneLayers), C.c_int, C.c_int]),
+    "sqair_lane_layers_test": (C.c_int, [C.c_void_p] * 6 + [C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(SqairLaneLayers), C.c_void_p]),
     "sqair_forecast_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
     "sqair_forecast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                  C.POINTER(SqairForecastOutputs), C.c_void_p, C.c_int64, C.c_void_p]),

@@ -1401,6 +1401,13 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
   // lane estimates: one answer per (frame, lane) from this pass's rows and the log weights they carry (sqair_set_estimate) -- before
   // the resampler zeroes those weights and rewrites the map
   if (st.est_on) sq_launch_lane_estimate(sq_estimate_args(h, w.rec_m_all + (size_t)M * RW, out, T, B), s);
+  // object layers: the decoder's sum over slots taken apart per object of the lane (sqair_set_layers), from the glimpses section J
+  // decoded -- the caller's buffer or the workspace's -- by the estimate's weights and association
+  if (st.lay_on &&
+      sq_launch_lane_layers(sq_layers_args(h, w.rec_m_all + (size_t)M * RW, (out.glimpse && !train) ? out.glimpse : w.glimpse, out, T, B), s) != 0) {
+    sq_set_error(h, "sqair_forward: the object layers launch failed (dynamic LDS limit)");
+    return -2;
+  }
   // SMC: this pass's log weights -> ESS, evidence and the next pass's source map (sqair_set_smc / SqairCarry.smc)
   if (st.smc_on) sq_launch_smc_resample(sq_smc_args(st.smc, out.log_weights_per_timestep, w.t_row, T, B, K), s);
   SQ_CHECK_HIP(hipGetLastError());

@@ -410,6 +410,21 @@ struct LaneEstArgs {
   int T, B, K, N, nw, H, W;
 };
 int sq_launch_lane_estimate(const LaneEstArgs& a, hipStream_t s);
+// Object layers (sqair_set_layers; include/sqair_hip.h states the semantics): k_lane_layers, one workgroup per (lane b, frame t,
+// tile of SQ_LAYER_TILE consecutive pixels), each recomputing the lane's weights and association; a thread holds SQ_LAYER_PX pixels
+// of every image in registers, so any frame size is a matter of the grid alone.  `rows` as LaneEstArgs' (obj_id is not read);
+// glimpse (g) of slot m of row r of frame t at glimpse + (((t * R + r) * N + m) * G * G.
+constexpr int SQ_LAYER_PX = 4, SQ_LAYER_TILE = 256 * SQ_LAYER_PX;
+struct LaneLayerArgs {
+  LaneRows rows;
+  const float* glimpse;                // [T][R][N][G*G]
+  const float* lw;                     // the pass's log_weights_per_timestep [T][R]
+  const float* log_w;                  // the estimate's: [R] or NULL = zeros
+  float iou_min;                       // the estimate's
+  SqairLaneLayers lay;                 // cover_min and the outputs
+  int T, B, K, N, G, H, W;
+};
+int sq_launch_lane_layers(const LaneLayerArgs& a, hipStream_t s);   // -2: the kernel's LDS (two glimpses) does not fit
 
 // Object forecasts (sqair_forecast_fan; include/sqair_hip.h states the semantics).  Fan-out: rollout row q = r * S + s.
 // k_forecast_fan_src expands the source map, src_fan[q] = src[q / S] (NULL: q / S), an index outside [0, R) of the blob -> -1.

@@ -1,9 +1,10 @@
 // The per-lane answers: the kernels that turn a lane's K particle rows into one answer per lane -- the SMC resampler, the forecast
-// summaries, the lane estimate, the lane forecast and the lane tracks.  None of them is a hop of the frame loop (once per pass or
+// summaries, the lane estimate, the object layers, the lane forecast and the lane tracks.  None of them is a hop of the frame loop (once per pass or
 // per call, on B workgroups), and they are a translation unit -- a code object -- of their own so that work on them moves no kernel of the pass
 // (DESIGN.md section 3h).  Their compositions are the device functions of sqair_lane.h.  Every lane-wide sum is one thread's loop in
 // index order: the same bits on every replay, and K <= 256 adds are nothing next to the pass.
 #include "sqair_lane.h"
+#include "sqair_canvas.h"
 
 // ------------------------------------------------------------------------------------------------
 // k_smc_resample (sqair_set_smc; SmcArgs in sqair_glue.h): the last launch of a pass with SMC on, after k_state_export.  Lane b's
@@ -417,5 +418,153 @@ int sq_launch_lane_estimate(const LaneEstArgs& a, hipStream_t s) {
   const int P = a.H * a.W, nz = a.est.mean_canvas ? (P + SQ_EST_PIXELS - 1) / SQ_EST_PIXELS : 1;
   if (a.est.mean_canvas) SQ_LAUNCH(k_lane_estimate<true>, dim3(a.B, a.T, nz), dim3(256), 0, s, a);
   else SQ_LAUNCH(k_lane_estimate<false>, dim3(a.B, a.T, nz), dim3(256), 0, s, a);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Object layers (sqair_set_layers; LaneLayerArgs in sqair_glue.h; the semantics: include/sqair_hip.h, points 1-7)
+// ------------------------------------------------------------------------------------------------
+// k_lane_layers: workgroup (lane b, frame t, tile z of SQ_LAYER_TILE consecutive pixels), thread = SQ_LAYER_PX pixels of the tile,
+// 256 apart, whose sums it keeps in registers.  Every workgroup repeats the estimate's prologue -- weights, best objects, thread k's
+// association into the K x N byte table -- and turns the table into one 64-bit mask per (object, wave): the particles that agree on
+// an object are then the set bits, walked in index order by every thread alike.  The matched glimpses pass through two LDS buffers:
+// while the taps of pair (j, k) read one, the LDS-DMA of the next pair's G^2 floats and threads 0..4's transform coefficients and
+// presence of it fill the other; one barrier per pair.  A pair whose box misses the tile's rows (or the frame's columns) is skipped
+// by a test on the box ends that is uniform over the workgroup -- the coordinate grows with the pixel index, and a pixel outside the
+// box adds exactly 0 either way.  Nothing is accumulated with atomics.
+struct SqLayerPairs { int j, wv; unsigned long long m; };   // the walk's position: object, wave word, bits left in it
+__device__ __forceinline__ bool sq_layer_next(const unsigned long long (*s_agree)[4], const int N, SqLayerPairs& it, int& k) {
+  for (;;) {
+    if (it.m) {
+      k = 64 * it.wv + __ffsll(it.m) - 1;
+      it.m &= it.m - 1;
+      return true;
+    }
+    if (++it.wv == 4) {
+      it.wv = 0;
+      if (++it.j >= N) return false;
+    }
+    it.m = s_agree[it.j][it.wv];
+  }
+}
+__global__ __launch_bounds__(256) void k_lane_layers(const LaneLayerArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  extern __shared__ __align__(16) float s_gl[];   // [2][G * G]: the glimpse of the pair at work, and of the next one
+  __shared__ float s_w[SQ_MAX_K];                 // a_k, e_k, then w_k
+  __shared__ unsigned char s_match[SQ_MAX_K * SQ_MAXN];
+  __shared__ unsigned long long s_agree[SQ_MAXN][4];
+  __shared__ SqBox s_bbox[SQ_MAXN];
+  __shared__ int s_bp[SQ_MAXN];
+  __shared__ float s_co[2][8];                    // sx, sy, tx, ty, presence of the two staged pairs
+  __shared__ SqLaneStats s_st;
+  constexpr int PX = SQ_LAYER_PX;
+  const SqairLaneLayers& o = a.lay;
+  const LaneRows& v = a.rows;
+  const int b = blockIdx.x, t = blockIdx.y, tid = threadIdx.x, K = a.K, N = a.N, G = a.G, H = a.H, W = a.W, R = a.B * K;
+  const int G2 = G * G, P = H * W;
+  const size_t tb = (size_t)t * a.B + b, row0 = (size_t)t * R + (size_t)b * K;   // (frame t, particle 0 of lane b)
+  const float nan = __builtin_nanf("");
+  // ---- the estimate's points 1, 2, 4, 5: weights, best row, its objects, thread k's association
+  sq_lane_weights<false>(tid < K ? sq_lane_log_weight<true>(a.log_w, a.lw, t + 1, R, b * K + tid) : 0.0f, K, s_w, s_st);
+  const bool bad = s_st.best < 0;
+  sq_lane_best_objects(v, row0 + (bad ? 0 : s_st.best), bad, N, H, W, 0, SqBestOut{nullptr, nullptr, nullptr, nullptr}, s_bp, s_bbox);
+  if (tid < K) sq_lane_associate<false>(v, row0 + tid, N, H, W, a.iou_min, s_bp, s_bbox, s_match + tid * N, nullptr, nullptr);
+  __syncthreads();
+  if (blockIdx.z == 0 && o.match)
+    for (int i = tid; i < K * N; i += 256) o.match[tb * K * N + i] = s_match[i] == 255 ? -1 : (int)s_match[i];
+  if (!o.layer && !o.cover && !o.owner) return;
+  for (int j = 0; j < N; ++j) {   // (an absent object, and every object of a non-finite lane: no bit)
+    const unsigned long long m = __ballot(tid < K && s_match[tid * N + j] != 255);
+    if ((tid & 63) == 0) s_agree[j][tid >> 6] = m;
+  }
+  // ---- this thread's pixels, the tile's rows
+  const int p0 = blockIdx.z * SQ_LAYER_TILE, ya = p0 / W, yb = (min(p0 + SQ_LAYER_TILE, P) - 1) / W;
+  int px[PX], py[PX], own[PX];
+  float top[PX];
+#pragma unroll
+  for (int u = 0; u < PX; ++u) {
+    const int p = min(p0 + tid + 256 * u, P - 1);   // (clamped: a pixel beyond the frame is computed and not written)
+    py[u] = p / W;
+    px[u] = p - py[u] * W;
+    own[u] = -1;
+    top[u] = -__builtin_inff();
+  }
+  // pair (j, k) into buffer `buf`: the glimpse by LDS-DMA, its coefficients and presence by threads 0..4 -- all in place by the next barrier
+  auto stage = [&](const int j, const int k, const int buf) {
+    const int m = s_match[k * N + j];
+    const size_t sl = sq_lane_slot(v, row0 + k, N) + m;
+    sq_wave_stage(s_gl + buf * G2, a.glimpse + ((row0 + k) * N + m) * G2, G2, tid & 63, tid >> 6, 4);
+    if (tid < 4) s_co[buf][tid] = sq_to_coord(v.where[sl * v.where_ld + tid], tid);
+    else if (tid == 4) s_co[buf][4] = v.presence[sl * v.pres_ld];
+  };
+  __syncthreads();
+  SqLayerPairs it = {-1, 3, 0ull};
+  int nk = 0, cur = 0;
+  bool more = sq_layer_next(s_agree, N, it, nk);
+  int nj = it.j;
+  if (more) stage(nj, nk, 0);
+  __syncthreads();
+  for (int j = 0; j < N; ++j) {   // (the loops and their branches are uniform over the workgroup)
+    float lay[PX], cov[PX];
+    if (!s_bp[j]) {   // absent: zero (a non-finite lane: NaN)
+#pragma unroll
+      for (int u = 0; u < PX; ++u) lay[u] = cov[u] = bad ? nan : 0.0f;
+    } else {
+#pragma unroll
+      for (int u = 0; u < PX; ++u) lay[u] = cov[u] = 0.0f;
+      float sup = 0.0f;
+      while (more && nj == j) {
+        const int k = nk;
+        more = sq_layer_next(s_agree, N, it, nk);
+        nj = it.j;
+        if (more) stage(nj, nk, cur ^ 1);
+        const float* gk = s_gl + cur * G2;
+        const float sx = s_co[cur][0], sy = s_co[cur][1], tx = s_co[cur][2], ty = s_co[cur][3], pk = s_co[cur][4], wk = s_w[k];
+        sup += wk;
+        const bool hit = sq_canvas_coord(yb, H, sy, ty, G) > -1.0f && sq_canvas_coord(ya, H, sy, ty, G) < (float)G &&
+                         sq_canvas_coord(W - 1, W, sx, tx, G) > -1.0f && sq_canvas_coord(0, W, sx, tx, G) < (float)G;
+        if (hit) {
+#pragma unroll
+          for (int u = 0; u < PX; ++u) {
+            const float xg = sq_canvas_coord(px[u], W, sx, tx, G), yg = sq_canvas_coord(py[u], H, sy, ty, G);
+            if (sq_canvas_inside(xg, G) && sq_canvas_inside(yg, G)) {
+              float val, on;
+              sq_canvas_tap(gk, xg, yg, G, val, on);
+              lay[u] += wk * (val * pk);
+              cov[u] += wk * (on * pk);
+            }
+          }
+        }
+        __syncthreads();
+        cur ^= 1;
+      }
+#pragma unroll
+      for (int u = 0; u < PX; ++u) {
+        lay[u] /= sup;
+        cov[u] /= sup;
+        if (cov[u] > top[u]) { top[u] = cov[u]; own[u] = j; }   // (the first of equal covers stays; a NaN never wins)
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < PX; ++u) {
+      const int p = p0 + tid + 256 * u;
+      if (p >= P) continue;
+      if (o.layer) o.layer[(tb * N + j) * P + p] = lay[u];
+      if (o.cover) o.cover[(tb * N + j) * P + p] = cov[u];
+    }
+  }
+  if (o.owner) {
+#pragma unroll
+    for (int u = 0; u < PX; ++u) {
+      const int p = p0 + tid + 256 * u;
+      if (p < P) o.owner[tb * P + p] = top[u] >= o.cover_min ? own[u] : -1;
+    }
+  }
+}
+int sq_launch_lane_layers(const LaneLayerArgs& a, hipStream_t s) {
+  const int P = a.H * a.W, lds = 2 * a.G * a.G * (int)sizeof(float);
+  const int nz = (a.lay.layer || a.lay.cover || a.lay.owner) ? (P + SQ_LAYER_TILE - 1) / SQ_LAYER_TILE : 1;
+  if (lds > 32 * 1024 && sq_allow_big_lds((const void*)k_lane_layers, 150 * 1024) != 0) return -2;
+  SQ_LAUNCH(k_lane_layers, dim3(a.B, a.T, nz), dim3(256), lds, s, a);
   return 0;
 }

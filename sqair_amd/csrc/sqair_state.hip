@@ -16,7 +16,11 @@ int64_t sq_state_row_floats(const SqairHandle* h) {
   return (N * (rec::W + snh + psnh) + 2 + 3) / 4 * 4;
 }
 static void sq_observed_off(SqairHandle* h) { h->observed = nullptr; h->observed_T = 0; }
-static void sq_estimate_off(SqairHandle* h) { h->est_on = false; h->est = SqairLaneEstimate{}; h->est_T = 0; }
+static void sq_layers_off(SqairHandle* h) { h->lay_on = false; h->lay = SqairLaneLayers{}; }
+static void sq_estimate_off(SqairHandle* h) {
+  h->est_on = false; h->est = SqairLaneEstimate{}; h->est_T = 0;
+  sq_layers_off(h);                           // (the layers share the estimate's weights and association: off with it)
+}
 static void sq_history_off(SqairHandle* h) {
   h->hist_on = false; h->hist_ring = nullptr; h->hist_bytes = 0; h->hist_L = 0; h->hist_T = 0; h->hist_fields = 0;
 }
@@ -154,6 +158,7 @@ extern "C" int sqair_set_estimate(SqairHandle* h, const SqairLaneEstimate* est, 
   if (B != h->state_B)
     return sq_no(h, who + "B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
   if (sq_estimate_fields(h, who, *est) != 0 || sq_estimate_smc_mismatch(h, who, *est) != 0) return -1;
+  if (T != h->est_T) sq_layers_off(h);   // (the layers' outputs were sized for the other T)
   h->est_on = true; h->est = *est; h->est_T = T;
   return 0;
 }
@@ -200,6 +205,60 @@ extern "C" int sqair_lane_estimate_test(SqairHandle* h, const float* where, cons
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }
+// ------------------------------------------------------------------------------------------------
+// object layers (include/sqair_hip.h: sqair_set_layers): registration, the arguments of k_lane_layers (launched by sq_forward_impl
+// directly after k_lane_estimate) and the kernel-level entry point
+// ------------------------------------------------------------------------------------------------
+// what every user of an SqairLaneLayers checks, -1 + "<who>..." when one is off
+static int sq_layers_fields(SqairHandle* h, const std::string& who, const SqairLaneLayers& l) {
+  if (!(l.cover_min > 0.0f && l.cover_min <= 1.0f)) return sq_no(h, who + "cover_min must lie in (0, 1]");   // (NaN fails both)
+  if (!l.match && !l.layer && !l.cover && !l.owner) return sq_no(h, who + "at least one of match, layer, cover and owner must be set");
+  return 0;
+}
+extern "C" int sqair_set_layers(SqairHandle* h, const SqairLaneLayers* lay, int T, int B) {
+  if (!h) return -1;
+  if (!lay) {
+    sq_layers_off(h);
+    return 0;
+  }
+  const std::string who = "sqair_set_layers: ";
+  if (!h->state_on || !h->est_on)
+    return sq_no(h, who + "needs an estimate (sqair_set_estimate): the layers weigh and associate the particles as it does");
+  if (T != h->est_T)
+    return sq_no(h, who + "T = " + std::to_string(T) + " but the estimate set by sqair_set_estimate is for T = " + std::to_string(h->est_T));
+  if (B != h->state_B)
+    return sq_no(h, who + "B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
+  if (sq_layers_fields(h, who, *lay) != 0) return -1;
+  h->lay_on = true; h->lay = *lay;
+  return 0;
+}
+LaneLayerArgs sq_layers_args(const SqairHandle* h, const float* rec, const float* glimpse, const SqairOutputs& out, int T, int B) {
+  const SqairConfig& c = h->cfg;
+  LaneLayerArgs a; memset(&a, 0, sizeof(a));
+  a.rows = LaneRows{rec + rec::WHERE, rec::W, rec + rec::PRES, rec::W, nullptr, 0, 1};
+  a.glimpse = glimpse; a.lw = out.log_weights_per_timestep; a.log_w = h->est.log_w; a.iou_min = h->est.iou_min; a.lay = h->lay;
+  a.T = T; a.B = B; a.K = c.k_particles; a.N = c.n_steps_per_image; a.G = c.glimpse_size; a.H = c.img_h; a.W = c.img_w;
+  return a;
+}
+// kernel-level check of the layers (tests/test_layers_kernel.py): k_lane_layers on caller tensors, K given (1..SQ_MAX_K), no state
+// and no pass
+extern "C" int sqair_lane_layers_test(SqairHandle* h, const float* glimpse, const float* where, const float* presence, const float* lw,
+                                      const float* log_w, float iou_min, int T, int B, int K, const SqairLaneLayers* lay, void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_lane_layers_test: ";
+  const SqairConfig& c = h->cfg;
+  if (!glimpse || !where || !presence || !lw || !lay || T < 1 || B < 1 || K < 1 || K > SQ_MAX_K || T > 65535 || (int64_t)B * K > INT32_MAX)
+    return sq_no(h, who + "null glimpse / where / presence / lw / lay or bad T / B / K (1 <= K <= " + std::to_string(SQ_MAX_K) + ")");
+  if (!(iou_min > 0.0f && iou_min <= 1.0f)) return sq_no(h, who + "iou_min must lie in (0, 1]");
+  if (sq_layers_fields(h, who, *lay) != 0) return -1;
+  LaneLayerArgs a; memset(&a, 0, sizeof(a));
+  a.rows = LaneRows{where, 4, presence, 1, nullptr, 0, 1};
+  a.glimpse = glimpse; a.lw = lw; a.log_w = log_w; a.iou_min = iou_min; a.lay = *lay;
+  a.T = T; a.B = B; a.K = K; a.N = c.n_steps_per_image; a.G = c.glimpse_size; a.H = c.img_h; a.W = c.img_w;
+  if (sq_launch_lane_layers(a, (hipStream_t)stream) != 0) { sq_set_error(h, who + "the launch failed (dynamic LDS limit)"); return -2; }
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
 
 // the refusals of a carried training call (host only: before any HIP call)
 int sq_carry_refusal(SqairHandle* h, const char* fn, int B, const SqairCarry* carry, const SqairOutputs* out) {
@@ -237,7 +296,7 @@ int sq_state_refusal(SqairHandle* h, bool train, int B, int t_offset) {
 
 SqStateRes sq_handle_state(const SqairHandle* h) {
   return SqStateRes{h->state_on, h->state_in, h->state_out, h->state_src, false, h->smc_on, h->smc, h->state_on && h->hist_on,
-                    h->state_on ? h->observed : nullptr, h->state_on && h->est_on};
+                    h->state_on ? h->observed : nullptr, h->state_on && h->est_on, h->state_on && h->est_on && h->lay_on};
 }
 SqStateRes sq_carry_state(const SqairCarry* c) {
   return SqStateRes{true, c->state_in, c->state_out, c->src_rows, true, c->smc != nullptr, c->smc ? *c->smc : SqairSmc{}};

@@ -47,6 +47,12 @@ their ``box`` [T', B, N, 4] = (y, x, h, w) in pixels, and per object the ``suppo
 of IoU >= ``estimate_iou`` with it -- and their weighted mean box ``box_mean``; with ``estimate_canvas`` the posterior mean
 reconstruction ``mean_canvas`` [T', B, H, W].
 
+With ``estimate_layers=True`` (a stream with ``estimate=True``) ``out["lane"]`` also says which pixels each object of the lane
+occupies, by one more kernel of the pass directly after the estimate's (include/sqair_hip.h: sqair_set_layers, which states the
+semantics): ``match`` [T', B, K, N] -- the slot of particle k associated with object j, -1 where it does not agree -- and, over the
+particles that agree, the weighted mean of what the decoder drew for the object: its appearance ``layer`` and its coverage ``cover``
+[T', B, N, H, W]; ``owner`` [T', B, H, W] is the object of largest coverage at a pixel, -1 (background) below ``layers_cover_min``.
+
 The stream takes over its core's handle: while it is open, every inference pass of that handle carries the state.  ``close()``
 hands the handle back.
 
@@ -83,7 +89,7 @@ def _field_views(shapes, int_fields, device):
 class SqairStream(object):
     def __init__(self, core, B, frames_per_step=1, outputs=DEFAULT_OUTPUTS, use_graph=True, seed=0, resample=None, ess_frac=0.5,
                  state=None, history=None, history_fields=tuple(_capi.HISTORY_FIELDS), missing=False, estimate=False,
-                 estimate_iou=0.5, estimate_canvas=False):
+                 estimate_iou=0.5, estimate_canvas=False, estimate_layers=False, layers_cover_min=0.5):
         if core.cfg.sample_from_prior:
             raise ValueError("SqairStream: generation modes (sample_from_prior) do not carry a state across calls")
         if resample not in (None, "systematic"):
@@ -96,6 +102,11 @@ class SqairStream(object):
             raise ValueError("SqairStream: estimate_iou must lie in (0, 1]")
         if estimate_canvas and not estimate:
             raise ValueError("SqairStream: estimate_canvas is for a stream with estimate=True")
+        if estimate_layers and not estimate:
+            raise ValueError("SqairStream: estimate_layers is for a stream with estimate=True")
+        layers_cover_min = float(layers_cover_min)
+        if estimate_layers and not 0.0 < layers_cover_min <= 1.0:   # (NaN fails too)
+            raise ValueError("SqairStream: layers_cover_min must lie in (0, 1]")
         self.smc = resample is not None
         self.ess_frac = ess_frac
         self.core = core
@@ -138,11 +149,14 @@ class SqairStream(object):
             core.check(core.lib.sqair_set_observed(core.handle, self._observed.data_ptr(), self.T, self.B), "sqair_set_observed")
         self.estimate = bool(estimate)
         if self.estimate:   # after SMC: the estimate's log_w must be the resampler's accumulator
-            self._est = self._estimate_buffers(bool(estimate_canvas))
+            self._est = self._estimate_buffers(bool(estimate_canvas), bool(estimate_layers))
             est = _capi.SqairLaneEstimate(iou_min=estimate_iou, log_w=cs.log_weight_sum.data_ptr(),
-                                          **{n: t.data_ptr() for n, t in self._est.items()})
+                                          **{n: t.data_ptr() for n, t in self._est.items() if n in _capi.ESTIMATE_FIELDS})
             torch.cuda.current_stream(core.device).synchronize()
             core.check(core.lib.sqair_set_estimate(core.handle, C.byref(est), self.T, self.B), "sqair_set_estimate")
+            if estimate_layers:
+                lay = _capi.SqairLaneLayers(cover_min=layers_cover_min, **{n: self._est[n].data_ptr() for n in _capi.LAYERS_FIELDS})
+                core.check(core.lib.sqair_set_layers(core.handle, C.byref(lay), self.T, self.B), "sqair_set_layers")
         if history is not None:
             ring, nb, bits = cs.set_history(history, history_fields, self.T)
             torch.cuda.current_stream(core.device).synchronize()   # (the ring's zeros are in place before a pass pushes into it)
@@ -165,12 +179,16 @@ class SqairStream(object):
         self._smc_uniforms = uniforms
         self._graph = False
 
-    def _estimate_buffers(self, canvas):
-        """The device buffers k_lane_estimate writes (include/sqair_hip.h: SqairLaneEstimate), by field: views of ONE allocation
-        (``_est_flat``), so that a step copies them out with one launch instead of one per field."""
+    def _estimate_buffers(self, canvas, layers=False):
+        """The device buffers k_lane_estimate -- and, with ``layers``, k_lane_layers -- writes (include/sqair_hip.h: SqairLaneEstimate,
+        SqairLaneLayers), by field: views of ONE allocation (``_est_flat``), so that a step copies them out with one launch instead
+        of one per field."""
         core = self.core
         shapes = _capi.estimate_shapes(self.T, self.B, self.K, core.N, core.nw, (core.H, core.W) if canvas else None)
-        self._est_flat, self._est_views = _field_views(shapes, _capi.ESTIMATE_INT_FIELDS, core.device)
+        if layers:
+            shapes.update(_capi.layers_shapes(self.T, self.B, self.K, core.N, (core.H, core.W)))
+        self._est_flat, self._est_views = _field_views(shapes, _capi.ESTIMATE_INT_FIELDS + (_capi.LAYERS_INT_FIELDS if layers else ()),
+                                                       core.device)
         return self._est_views(self._est_flat)
 
     # ---- source map -------------------------------------------------------------------------------------------------------

@@ -37,6 +37,13 @@ reconstruction.  The estimate is one dependent node; the yardstick is the same r
 node that day.  The ratio is recorded, not gated on:
 
     python tools/stream_time.py --estimate [--out profiles/stream_estimate_time.json]
+
+With --layers: the price of the object layers (SqairStream(estimate=True, estimate_layers=True), include/sqair_hip.h:
+sqair_set_layers).  Streams at cfg-2's batch alternating in one process as with --history: plain, SMC, estimate, SMC + estimate,
+layers, SMC + layers.  The layers are one dependent node after the estimate's -- and a larger copy out of the step: layer and cover
+are 2 N H W floats per lane; next to them the estimate's node and the resampler's node of the same run.  Recorded, not gated on:
+
+    python tools/stream_time.py --layers [--out profiles/stream_layers_time.json]
 """
 import argparse
 import json
@@ -242,6 +249,24 @@ def time_estimate(B, K, N, steps, warmup, rounds=10, hw=(50, 50)):
     return res
 
 
+def time_layers(B, K, N, steps, warmup, rounds=10, hw=(50, 50)):
+    smc = dict(resample="systematic", ess_frac=0.5)
+    lay = dict(estimate=True, estimate_layers=True)
+    legs = dict(plain={}, smc=smc, estimate=dict(estimate=True), smc_estimate=dict(estimate=True, **smc), layers=lay,
+                smc_layers=dict(lay, **smc))
+    streams, res, med, thr = alternating_streams(legs, B, K, N, steps, warmup, rounds, hw)
+    res["lane_bytes_per_step"] = {n: int(streams[n]._est_flat.numel() * 4) for n in ("estimate", "layers")}
+    for key, v in (("latency", med), ("back_to_back", thr)):
+        one_node = v["smc"] - v["plain"]            # the yardstick: one dependent node (the resampler) on this machine, this run
+        added = dict(estimate_node_on_plain=v["estimate"] - v["plain"], estimate_node_on_smc=v["smc_estimate"] - v["smc"],
+                     layers_node_on_estimate=v["layers"] - v["estimate"], layers_node_on_smc_estimate=v["smc_layers"] - v["smc_estimate"])
+        res["us_" + key] = dict(smc_node=1e3 * one_node, **{n: 1e3 * a for n, a in added.items()},
+                                **{n + "_over_smc_node": (a / one_node if one_node > 0 else None) for n, a in added.items()})
+    for st in streams.values():
+        st.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=500)
@@ -252,10 +277,13 @@ def main():
     ap.add_argument("--lane", action="store_true", help="with --history: tracks(lag, lane=True) against tracks(lag), alternating (profiles/track_lane_time.json)")
     ap.add_argument("--missing", action="store_true", help="plain / SMC / a mask with every lane / with no lane observed, alternating (profiles/stream_missing_time.json)")
     ap.add_argument("--estimate", action="store_true", help="plain / SMC / estimate / SMC + estimate / with mean_canvas, alternating (profiles/stream_estimate_time.json)")
+    ap.add_argument("--layers", action="store_true", help="plain / SMC / estimate / SMC + estimate / layers / SMC + layers, alternating (profiles/stream_layers_time.json)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     ov, _, _, _ = config_inputs(2)
-    if args.estimate:
+    if args.layers:
+        shapes = [dict(name="cfg2_batch_layers", **time_layers(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
+    elif args.estimate:
         shapes = [dict(name="cfg2_batch_estimate", **time_estimate(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
     elif args.missing:
         shapes = [dict(name="cfg2_batch_missing", **time_missing(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
