@@ -725,11 +725,13 @@ int sqair_st_insert_loglik_bwd(SqairHandle* h, const float* glimpse, const float
  * from the importance weights and the learning signal sqair_elbo returned. */
 int sqair_elbo_bwd(SqairHandle* h, const float* importance_weights, const float* vimco_signal, int T, int B,
                    float* g_log_w_t, float* g_disc_lp_t, void* stream);
-/* Decoder branch of sqair_backward (first slice of the training step).  Call after sqair_forward (with
- * SqairOutputs.glimpse == NULL so the decoded glimpses stay in the workspace) and sqair_elbo on the same
- * workspace.  Writes the gradients of the VIMCO target w.r.t. dec.mean_img, dec.l{0,1,2}.{w,b}, dec.output_scale
- * into flat_grad (flat-parameter layout; other entries untouched) and, optionally, the seed gradients on the
- * merged latents d_rec [T, B'*N, 64] (record order: where 0:4, what 4:54). */
+/* Decoder branch of sqair_backward on its own (unit-test entry: the same host function and kernels as the full pass).
+ * Call after sqair_forward (with SqairOutputs.glimpse == NULL so the decoded glimpses stay in the workspace) and
+ * sqair_elbo on the same inference workspace.  Writes the gradients of the VIMCO target w.r.t. dec.mean_img,
+ * dec.l{0,1,2}.{w,b}, dec.output_scale into flat_grad (flat-parameter layout; other entries untouched) and, optionally,
+ * the seed gradients on the merged latents d_rec [T, B'*N, 64] (record order: where 0:4, what 4:54).  Refuses (-1) padded
+ * configurations, the wide build, frames that cannot be trained and H * W that is not a multiple of 4.  `scratch`:
+ * sqair_backward_scratch_bytes (query it: the size is the entry's own business). */
 int64_t sqair_backward_scratch_bytes(const SqairHandle* h, int T, int B);
 int sqair_backward_decoder(SqairHandle* h, const float* flat_params, const void* packed, const float* obs,
                            const float* importance_weights, const float* vimco_signal, int T, int B,
@@ -929,8 +931,9 @@ int sqair_add_l2_grad(SqairHandle* h, const float* flat_params, float* flat_grad
  * g = grad_scale * flat_grad (grad_scale = 1/world after the data-parallel all-reduce(sum)). */
 int sqair_rmsprop_step(SqairHandle* h, float* flat_params, const float* flat_grad, float* ms, float* mom, int64_t n,
                        float lr, float decay, float momentum, float epsilon, float grad_scale, void* stream);
-/* Dense layer backward on the MFMA path (test helper): y = act(x W + b) forward; given dy returns dx [M,K],
- * dw [K,N] (reference [in,out] layout) and db [N]. */
+/* Dense layer backward on the kernels of the training step (test helper): y = act(x W + b) forward; given dy returns
+ * dx [M,K], dw [K,N] (reference [in,out] layout) and db [N].  dw / db take the route sqair_backward gives a block: the
+ * grouped weight-gradient kernel, or a launch of their own when x's rows are not 16-byte aligned (Kdim % 4 != 0). */
 int sqair_linear_bwd_test(SqairHandle* h, const float* x, const float* w, const float* y, const float* dy, float* dx,
                           float* dw, float* db, int M, int Kdim, int Ndim, int act, void* scratch,
                           int64_t scratch_bytes, void* stream);

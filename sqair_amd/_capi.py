@@ -266,6 +266,7 @@ _PROTOS = {
     "sqair_debug_dense_log": (C.c_int, [C.c_void_p, C.c_int]),
     "sqair_debug_dense_log_entry": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "sqair_debug_specialised_launches": (C.c_int64, []),
+    "sqair_debug_wgrad_launches": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sqair_debug_layers": (C.c_int, [C.c_void_p]),
     "sqair_debug_padded_count": (C.c_int64, [C.c_void_p, C.POINTER(C.c_int)]),
     "sqair_debug_layer": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),

@@ -22,6 +22,7 @@
 
 #include "sqair_internal.h"
 #include "sqair_chain.h"
+#include "sqair_bwd.h"
 
 void sq_set_error(SqairHandle* h, const std::string& msg) {
   if (h) h->err = msg;
@@ -550,6 +551,7 @@ static void build_plan(SqairHandle* h) {
 // gradient of a z-record segment comes out in record order.  Built from the forward plan element by element.
 static void build_plan_T(SqairHandle* h) {
   for (int id = 0; id < L_COUNT; ++id) {
+    if (id == L_WHAT_HEAD_I || id == L_PROP_HEADS_I) continue;   // forward-only packs: no dX reads them, layersT[id] stays empty
     const PackedLayer& L = h->layers[id];
     PackedLayer& T = h->layersT[id];
     T.kc = L.nt;            // reduction over the (padded) forward outputs
@@ -2080,9 +2082,6 @@ extern "C" int sqair_lstm_test(SqairHandle* h, const float* x, const float* hsta
   return 0;
 }
 
-int sq_launch_lstm_cell_bwd(const float* gates, int g_ld, const float* c_prev, int c_ld, const float* d_h, int dh_ld, const float* d_c,
-                            int dc_ld, float* d_gates, int dg_ld, float* d_cprev, int dcp_ld, int rows, int nh, hipStream_t s,
-                            float* d_gates2 = nullptr, int dg2_ld = 0);
 // adjoint of the element-wise LSTM cell: gates [M, 4 nh] (pre-activations i, j, f, o), c_prev, d h', d c' -> d gates, d c_prev
 extern "C" int sqair_lstm_cell_bwd_test(SqairHandle* h, const float* gates, const float* c_prev, const float* d_h, const float* d_c,
                                         float* d_gates, float* d_cprev, int M, void* stream) {
@@ -2133,6 +2132,13 @@ extern "C" int sqair_compact_test(SqairHandle* h, const float* rec_p, const floa
 // ------------------------------------------------------------------------------------------------
 // launches of specialised instantiations (sqair_glue.h) issued or captured by this process so far: lets a test see which path a pass took
 extern "C" int64_t sqair_debug_specialised_launches(void) { return (int64_t)sq_spec_launches(); }
+// the same for the weight gradients: blocks that went through the grouped kernel, and launches of their own (sqair_bwd.h)
+extern "C" int sqair_debug_wgrad_launches(int64_t* grouped_blocks, int64_t* own_launches) {
+  if (!grouped_blocks || !own_launches) return -1;
+  *grouped_blocks = (int64_t)sq_wgrad_grouped_blocks();
+  *own_launches = (int64_t)sq_wgrad_own_launches();
+  return 0;
+}
 extern "C" int sqair_debug_layers(const SqairHandle* h) { return h ? (int)L_COUNT : -1; }
 // padded inventory: total floats of the padded flat buffer; u2i (optional, n = sqair_param_count entries): where element j of the
 // caller's flat buffer lives in it
@@ -2159,20 +2165,10 @@ extern "C" int sqair_debug_plan(const SqairHandle* h, int id, int* widx, int* bi
 }
 
 // ------------------------------------------------------------------------------------------------
-// dense-layer backward through the MFMA kernels (unit-test entry): y = act(x W + b) was computed forward;
-// given dL/dy returns dL/dx (k_linear on the transposed pack), dL/dW and dL/db (k_wgrad).
+// dense-layer backward through the kernels of the training step (unit-test entry): y = act(x W + b) was computed forward;
+// given dL/dy returns dL/dx (k_linear on the transposed pack, the route of the decoder layers), dL/dW and dL/db (routed as
+// sqair_backward routes a block: the grouped kernel, or k_wgrad2 on its own for operands the grouped kernel declines).
 // ------------------------------------------------------------------------------------------------
-int sq_launch_wgrad(const float* A, int lda, const float* dY, int ldy, float* dW, int ldw, float* db, int M, int Kdim,
-                    int Ndim, int accumulate, hipStream_t s, const int* rowmap = nullptr, const float* alpha_ptr = nullptr);
-int sq_launch_insert_bwd_frames(const float* glimpse, const float* rec, int rec_ld, const float* img, const float* mean_img,
-                                const float* g_ll, float* d_glimpse, float* d_rec, int d_rec_ld, float* d_mean_rows,
-                                float std_fg, float std_bg, int T, Dims d, hipStream_t s, const float* scale = nullptr,
-                                float* d_scale = nullptr);
-int sq_launch_reduce_rows(const float* rows, float* out, int R, int P, int accumulate, hipStream_t s);
-int sq_launch_elbo_bwd(const float* iw, const float* sig, int T, int B, int K, float* g_lw, float* g_dl, hipStream_t s);
-int sq_launch_dot_scale(const float* a, const float* b, int64_t n, const float* scale, float* out, hipStream_t s);
-int sq_launch_dact(const float* d_out, const float* out, float* d_pre, int64_t n, int act, hipStream_t s);
-
 extern "C" int sqair_linear_bwd_test(SqairHandle* h, const float* x, const float* wmat, const float* y, const float* dy,
                                      float* dx, float* dw, float* db, int M, int Kdim, int Ndim, int act, void* scratch,
                                      int64_t scratch_bytes, void* stream) {
@@ -2183,7 +2179,7 @@ extern "C" int sqair_linear_bwd_test(SqairHandle* h, const float* x, const float
   adhoc_layer(h, Ndim, Kdim, &L);
   const int64_t nel = (int64_t)L.nt * L.kc * 256, nb = L.nt * 16;
   const int npad = (Ndim + 3) & ~3;
-  if (scratch_bytes < (2 * nel + nb + 256 + (int64_t)M * npad + (int64_t)M * Ndim) * 4) {
+  if (scratch_bytes < (2 * nel + nb + 256 + (int64_t)M * npad) * 4) {
     sq_set_error(h, "sqair_linear_bwd_test: scratch too small");
     return -1;
   }
@@ -2200,128 +2196,23 @@ extern "C" int sqair_linear_bwd_test(SqairHandle* h, const float* x, const float
   float* d_w = (float*)scratch + nel;
   float* d_b = d_w + nel;
   float* d_zero = d_b + nb;
-  float* d_dpre_pad = d_zero + 256;
-  float* d_dpre = d_dpre_pad + (int64_t)M * npad;
+  float* d_dpre = d_zero + 256;          // [M][npad], 16-byte aligned rows
   SQ_CHECK_HIP(hipMemcpyAsync(d_idx, idx.data(), nel * 4, hipMemcpyHostToDevice, s));
   SQ_CHECK_HIP(hipMemsetAsync(d_b, 0, (nb + 256 + (size_t)M * npad) * 4, s));
+  SQ_CHECK_HIP(hipMemsetAsync(dw, 0, (size_t)Kdim * Ndim * 4, s));   // (the weight-gradient kernels accumulate with atomics)
+  SQ_CHECK_HIP(hipMemsetAsync(db, 0, (size_t)Ndim * 4, s));
   SQ_CHECK_HIP(hipStreamSynchronize(s));
   sq_launch_pack(wmat, d_w, d_idx, nel, s);
-  sq_launch_dact(dy, y, d_dpre, (int64_t)M * Ndim, act, s);
-  sq_launch_wgrad(x, Kdim, d_dpre, Ndim, dw, Ndim, db, M, Kdim, Ndim, 0, s);
-  SQ_CHECK_HIP(hipMemcpy2DAsync(d_dpre_pad, (size_t)npad * 4, d_dpre, (size_t)Ndim * 4, (size_t)Ndim * 4, M,
-                                hipMemcpyDeviceToDevice, s));
+  sq_launch_dact2(dy, Ndim, y, Ndim, d_dpre, npad, M, Ndim, act, act, 1 << 30, 0, s);
+  WgradBatch wbatch;
+  if (!wbatch.add(x, Kdim, d_dpre, npad, dw, Ndim, M, Kdim, Ndim, nullptr, nullptr, db, nullptr))
+    sq_launch_wgrad_acc(x, Kdim, d_dpre, npad, dw, Ndim, M, Kdim, Ndim, s, nullptr, nullptr, db, nullptr);
+  if (wbatch.flush(s) != 0) { sq_set_error(h, "sqair_linear_bwd_test: the grouped weight-gradient launch failed"); return -2; }
   Lin l;
-  l.seg(d_dpre_pad, npad, Ndim).out(dx, Kdim).act(ACT_NONE);
+  l.seg(d_dpre, npad, Ndim).out(dx, Kdim).act(ACT_NONE);
   l.a.wp = d_w; l.a.wzero = d_zero; l.a.bias = d_b; l.a.M = M; l.a.N = Kdim;
   if (sq_launch_linear(l.a, L, s) != 0) { sq_set_error(h, "sqair_linear_bwd_test: A-operand contract violated"); return -5; }
   SQ_CHECK_HIP(hipGetLastError());
   SQ_CHECK_HIP(hipStreamSynchronize(s));
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// sqair_backward, decoder branch (first slice of the training step).
-// Must follow sqair_forward + sqair_elbo on the same workspace (it reads the merged records, decoder activations
-// and glimpses of all T frames the forward pass left there).  Computes
-//   dL/d(log w_t) from the VIMCO target  ->  insert / log-likelihood adjoint of all T frames  ->  three dense
-//   layers backward (dX through the transposed packs, dW / db through k_wgrad over M = T*B'*N rows)
-// and writes the gradients of every decoder parameter (dec.mean_img, dec.l0-2.{w,b}, dec.output_scale) into
-// flat_grad (other entries untouched) plus the seed gradients on the merged latents d_rec [T, B'*N, 64] (record
-// order: where 0:4, what 4:54) that the recurrent part of the backward pass will consume.
-// ------------------------------------------------------------------------------------------------
-extern "C" int64_t sqair_backward_scratch_bytes(const SqairHandle* h, int T, int B) {
-  if (!h || T < 1 || B < 1) return -1;
-  const SqairConfig& c = h->cfg;
-  const int64_t R = (int64_t)B * c.k_particles, M = R * c.n_steps_per_image, MT = M * T;
-  const int64_t G2 = c.glimpse_size * c.glimpse_size, P_ = c.img_h * c.img_w, nh = c.n_hidden;
-  return (2 * align64(T * R) + align64(MT * G2) + align64(T * R * P_) + 2 * align64(MT * (nh > G2 ? nh : G2)) +
-          align64(MT * 64) + 1024) * 4;
-}
-
-extern "C" int sqair_backward_decoder(SqairHandle* h, const float* flat, const void* packedv, const float* obs,
-                                      const float* importance_weights, const float* vimco_signal, int T, int B,
-                                      void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes,
-                                      float* flat_grad, float* d_rec_out, void* stream) {
-  if (!h || !flat || !packedv || !obs || !importance_weights || !vimco_signal || !workspace || !scratch || !flat_grad) return -1;
-  if (workspace_bytes < sqair_workspace_bytes(h, T, B) || scratch_bytes < sqair_backward_scratch_bytes(h, T, B)) {
-    sq_set_error(h, "sqair_backward_decoder: workspace / scratch too small");
-    return -1;
-  }
-  if (!sq_unit_frame_ok(h) || !sq_trainable_frame(h)) return -1;
-  if (h->padded || rec::ZWP != 64) {
-    sq_set_error(h, "sqair_backward_decoder (a partial adjoint kept for unit tests) writes in the product build's own shapes: use sqair_backward in the wide build or with an n_hidden that is padded");
-    return -1;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const float* packed = (const float*)packedv;
-  const SqairConfig& c = h->cfg;
-  const int nh = c.n_hidden, nw = c.n_what, N = c.n_steps_per_image, K = c.k_particles;
-  const int R = B * K, M = R * N, MT = M * T, G2 = c.glimpse_size * c.glimpse_size, P_ = c.img_h * c.img_w;
-  Dims d = make_dims(c, B);
-  Workspace w = carve(h, T, B, (float*)workspace);
-  const PackedLayout pl = packed_layout(h);
-  const int RW = rec::W;
-  // scratch carve
-  float* sc = (float*)scratch;
-  const int64_t big = (int64_t)MT * (nh > G2 ? nh : G2);
-  float* g_lw = sc; sc += align64((int64_t)T * R);  // every carve 256-byte aligned (GEMM A-operand contract)
-  float* g_dl = sc; sc += align64((int64_t)T * R);
-  float* d_gl = sc; sc += align64((int64_t)MT * G2);
-  float* d_mean_rows = sc; sc += align64((int64_t)T * R * P_);
-  float* bufa = sc; sc += align64(big);
-  float* bufb = sc; sc += align64(big);
-  float* d_rec = sc; sc += align64((int64_t)MT * 64);
-  const float* rec_all = w.rec_m_all + (size_t)M * RW;
-  const float* gl = w.glimpse;  // forward wrote the decoded glimpses here unless the caller asked for the output tensor
-  sq_launch_elbo_bwd(importance_weights, vimco_signal, T, B, K, g_lw, g_dl, s);
-  SQ_CHECK_HIP(hipMemsetAsync(d_rec, 0, (size_t)MT * 64 * 4, s));
-  if (sq_launch_insert_bwd_frames(gl, rec_all, RW, obs, flat + h->po.dec_mean_img, g_lw, d_gl, d_rec + rec::WHERE, 64, d_mean_rows,
-                                  c.output_std, c.background_std, T, d, s) != 0) {
-    sq_set_error(h, "the decoder canvas adjoint launch failed (dynamic LDS limit)");
-    return -2;
-  }
-  sq_launch_reduce_rows(d_mean_rows, flat_grad + h->po.dec_mean_img, T * R, P_, 0, s);
-  // ---- DEC2: glimpse = scale * (dec_b W2 + b2)
-  const float* scale = flat + h->po.dec_output_scale;
-  sq_launch_dot_scale(d_gl, gl, (int64_t)MT * G2, scale, flat_grad + h->po.dec_output_scale, s);
-  sq_launch_wgrad(w.dec_b, nh, d_gl, G2, flat_grad + P(h, "dec.l2.w"), G2, flat_grad + P(h, "dec.l2.b"), MT, nh, G2, 0, s,
-                  nullptr, scale);
-  auto dx = [&](LayerId id, const float* dpre, int ld, int width, float* outp, int out_ld, const float* scale_ptr) -> int {
-    const PackedLayer& LT = h->layersT[id];
-    Lin l;
-    l.seg(dpre, ld, width).out(outp, out_ld).act(ACT_NONE);
-    l.a.scale_ptr = scale_ptr;
-    l.a.wp = packed + pl.w + LT.w_off; l.a.wzero = packed + pl.w; l.a.bias = packed + pl.b + LT.b_off;
-    l.a.M = MT; l.a.N = LT.N;
-    return sq_launch_linear(l.a, LT, s);
-  };
-  if (dx(L_DEC2, d_gl, G2, G2, bufa, nh, scale) != 0) { sq_set_error(h, "backward: DEC2 dX contract"); return -5; }
-  sq_launch_dact(bufa, w.dec_b, bufb, (int64_t)MT * nh, ACT_ELU, s);            // bufb = dPre of layer 1
-  sq_launch_wgrad(w.dec_a, nh, bufb, nh, flat_grad + P(h, "dec.l1.w"), nh, flat_grad + P(h, "dec.l1.b"), MT, nh, nh, 0, s);
-  if (dx(L_DEC1, bufb, nh, nh, bufa, nh, nullptr) != 0) { sq_set_error(h, "backward: DEC1 dX contract"); return -5; }
-  sq_launch_dact(bufa, w.dec_a, bufb, (int64_t)MT * nh, ACT_ELU, s);            // bufb = dPre of layer 0
-  // layer 0 reads the z-record: positions 4..53 are `what` -> rows 0..nw-1 of dec.l0.w
-  {
-    std::vector<int> rm(rec::ZW, -1);
-    for (int i = 0; i < nw; ++i) rm[rec::WHAT + i] = i;
-    int* d_rm = (int*)sc;  // 1024-float tail of the scratch
-    SQ_CHECK_HIP(hipMemcpyAsync(d_rm, rm.data(), rec::ZW * 4, hipMemcpyHostToDevice, s));
-    SQ_CHECK_HIP(hipStreamSynchronize(s));
-    sq_launch_wgrad(rec_all, RW, bufb, nh, flat_grad + P(h, "dec.l0.w"), nh, flat_grad + P(h, "dec.l0.b"), MT, rec::ZW, nh, 0, s,
-                    d_rm, nullptr);
-  }
-  // d what of the merged records: accumulate onto the d where the insert adjoint already wrote (disjoint columns)
-  {
-    const PackedLayer& LT = h->layersT[L_DEC0];
-    Lin l;
-    l.seg(bufb, nh, nh).out(bufa, 64).act(ACT_NONE);
-    l.a.wp = packed + pl.w + LT.w_off; l.a.wzero = packed + pl.w; l.a.bias = packed + pl.b + LT.b_off;
-    l.a.M = MT; l.a.N = LT.N;
-    l.a.add = d_rec; l.a.add_ld = 64; l.a.add_n = 64;
-    if (sq_launch_linear(l.a, LT, s) != 0) { sq_set_error(h, "backward: DEC0 dX contract"); return -5; }
-    SQ_CHECK_HIP(hipMemcpyAsync(d_rec, bufa, (size_t)MT * 64 * 4, hipMemcpyDeviceToDevice, s));
-  }
-  if (d_rec_out) SQ_CHECK_HIP(hipMemcpyAsync(d_rec_out, d_rec, (size_t)MT * 64 * 4, hipMemcpyDeviceToDevice, s));
-  SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -82,15 +82,11 @@ int sq_launch_latent_sum_bwd(const float* d_c, const float* rec_p, const float* 
 int sq_launch_sum_slots(const float* d_rnn, float* d_pre_d, float* d_pre_disc, int B, int K, int N, int nh, hipStream_t s);
 int sq_launch_particle_sum(const float* in, float* out, int B, int K, int nh, hipStream_t s);
 int sq_launch_axpy2d(const float* x, int x_ld, float* y, int y_ld, int rows, int cols, int acc, hipStream_t s);
-int sq_launch_wgrad(const float* A, int lda, const float* dY, int ldy, float* dW, int ldw, float* db, int M, int Kdim,
-                    int Ndim, int accumulate, hipStream_t s, const int* rowmap = nullptr, const float* alpha_ptr = nullptr);
 int sq_launch_insert_bwd_frames(const float* glimpse, const float* rec, int rec_ld, const float* img, const float* mean_img,
                                 const float* g_ll, float* d_glimpse, float* d_rec, int d_rec_ld, float* d_mean_rows,
                                 float std_fg, float std_bg, int T, Dims d, hipStream_t s, const float* scale = nullptr,
                                 float* d_scale = nullptr);   // scale / d_scale: the output scale's gradient in the same launch
-int sq_launch_reduce_rows(const float* rows, float* out, int R, int P, int accumulate, hipStream_t s);
 int sq_launch_elbo_bwd(const float* iw, const float* sig, int T, int B, int K, float* g_lw, float* g_dl, hipStream_t s);
-int sq_launch_dot_scale(const float* a, const float* b, int64_t n, const float* scale, float* out, hipStream_t s);
 int sq_launch_reduce_rows_atomic(const float* rows, float* out, int R, int P, hipStream_t s);
 int sq_launch_wgrad_acc(const float* A, int lda, const float* dY, int ldy, float* dW, int ldw, int M, int Kdim, int Ndim,
                         hipStream_t s, const int* rowmap, const float* alpha_ptr, float* db_a, float* db_b);
@@ -109,6 +105,11 @@ constexpr int SQ_WG_MAXD = 96;
 // begin[x][i]: position in XCD x's queue where block i starts (i = nd: the queue's length; beyond: INT_MAX).  Workgroup b of the
 // launch is entry b / 8 of the queue of XCD b % 8 (workgroups are handed to the XCDs round-robin).
 struct WgGroup { WgDesc d[SQ_WG_MAXD]; int begin[8][SQ_WG_MAXD + 8]; int nd; };
+// which weight-gradient route ran: blocks flushed through k_wgrad_group / calls of sq_launch_wgrad_acc that went on to launch
+// (k_wgrad2 or, for large aligned blocks -- reachable in the knob build only --, k_wgrad3; counted before the launch itself),
+// issued or captured by this process so far (sqair_debug_wgrad_launches: lets a test see the route a block took)
+long long sq_wgrad_grouped_blocks();
+long long sq_wgrad_own_launches();
 struct WgradBatch {
   std::vector<WgDesc> blocks;
   bool add(const float* A, int lda, const float* dY, int ldy, float* dW, int ldw, int M, int Kdim, int Ndim, const int* rowmap,

@@ -8,8 +8,10 @@
 //                         log-likelihood (reference forward: sqair/modules.py:435-467, sqair/seq.py:271-274)
 //   k_elbo_bwd            d(VIMCO target)/d(log w_t), d/d(discrete log prob_t) (sqair/targets.py:62-75,
 //                         sqair/model.py:150-158)
-//   k_wgrad               dW += A^T dY, db += colsum(dY) on the fp32 matrix cores, written in the reference's
-//                         [in, out] layout straight into the flat gradient buffer
+//   k_wgrad_group         dW += A^T dY, db += colsum(dY) on the fp32 matrix cores, written in the reference's
+//                         [in, out] layout straight into the flat gradient buffer: every block of a pass in one launch
+//                         (WgradBatch); k_wgrad2 as its own launch for blocks whose operands are not 16-byte aligned,
+//                         k_wgrad3 in the knob build (sqair_linear_bwd_test drives the first two)
 #include "sqair_glue.h"
 #include "sqair_bwd.h"
 #include "sqair_canvas.h"
@@ -17,6 +19,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <atomic>
 #include <climits>
 #include <vector>
 
@@ -719,15 +722,7 @@ static size_t insert_bwd_lds(const Dims& d, int& band_rows) {
     if ((d).W > SQ_CANVAS_WIDE) SQ_LAUNCH((k_insert_loglik_bwd<SQ_CANVAS_PF_BWD_W, SQ_CANVAS_ROWS_BWD_W>), grid, dim3(256), shm, s, a, d, band_rows); \
     else SQ_LAUNCH((k_insert_loglik_bwd<SQ_CANVAS_PF_BWD, SQ_CANVAS_ROWS_BWD>), grid, dim3(256), shm, s, a, d, band_rows);            \
   } while (0)
-__global__ void k_reduce_rows(const float* __restrict__ rows, float* __restrict__ out, int R, int P, int accumulate SQ_TLP) {
-  SQ_TL_SCOPE;
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= P) return;
-  float acc = accumulate ? out[p] : 0.0f;
-  for (int r = 0; r < R; ++r) acc += rows[(size_t)r * P + p];
-  out[p] = acc;
-}
-// row-chunked variant for the training step: out[p] += sum over this block's rows (float atomics, out pre-zeroed)
+// column sums of rows[R][P]: out[p] += sum over this block's rows (float atomics, out pre-zeroed)
 __global__ void k_reduce_rows_atomic(const float* __restrict__ rows, float* __restrict__ out, int R, int P, int rows_per_block SQ_TLP) {
   SQ_TL_SCOPE;
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -760,9 +755,10 @@ extern "C" int sqair_st_insert_loglik_bwd(SqairHandle* h, const float* glimpse, 
     if (shm == 0) return -2;
     SQ_LAUNCH_INSERT_BWD(dim3(d.R, 1), shm, (hipStream_t)stream, a, d, band_rows);
   }
-  if (d_mean_img)   // (NULL: the per-row contributions stay in `scratch`, [R, H * W]; what tools/time_insert.py times)
-    SQ_LAUNCH(k_reduce_rows, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)scratch,
-                       d_mean_img, d.R, P, 0);
+  if (d_mean_img) {  // (NULL: the per-row contributions stay in `scratch`, [R, H * W]; what tools/time_insert.py times)
+    if (hipMemsetAsync(d_mean_img, 0, (size_t)P * 4, (hipStream_t)stream) != hipSuccess) return -2;
+    sq_launch_reduce_rows_atomic((const float*)scratch, d_mean_img, d.R, P, (hipStream_t)stream);
+  }
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -790,78 +786,6 @@ extern "C" int sqair_elbo_bwd(SqairHandle* h, const float* importance_weights, c
   SQ_LAUNCH(k_elbo_bwd, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, importance_weights,
                      vimco_signal, T, B, c.k_particles, g_log_w_t, g_disc_lp_t);
   return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Weight gradient of a dense layer on the fp32 matrix cores: dW[k][n] (+)= sum_m A[m][k] dY[m][n], reference
-// layout [in, out] with leading dimension ldw; db[n] (+)= sum_m dY[m][n].  One workgroup per 16(k) x 16(n) tile, its
-// 4 waves split the M rows (chunks of 4 rows per MFMA: A^T fragment lane l = A[m0 + (l>>4)][k0 + (l&15)],
-// dY fragment lane l = dY[m0 + (l>>4)][n0 + (l&15)] — both coalesced 64-byte row pieces), LDS reduce.
-// M is large when the tape of a whole step is reduced at once (T*N*B' = 6400 rows), which is how the training
-// step uses it: one launch per layer per step, off the critical path.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_wgrad(const float* __restrict__ A, int lda, const float* __restrict__ dY, int ldy,
-                                               float* __restrict__ dW, int ldw, float* __restrict__ db, int M, int Kdim,
-                                               int Ndim, int accumulate, const int* __restrict__ rowmap,
-                                               const float* __restrict__ alpha_ptr SQ_TLP) {
-  SQ_TL_SCOPE;
-  __shared__ float red[4 * 256];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int k0 = blockIdx.x * 16, n0 = blockIdx.y * 16;
-  const int kk = min(k0 + (lane & 15), Kdim - 1), nn = min(n0 + (lane & 15), Ndim - 1);
-  const int mq = lane >> 4;
-  f32x4_b acc = {0.0f, 0.0f, 0.0f, 0.0f};
-  float bsum = 0.0f;
-  for (int m0 = wave * 4; m0 < M; m0 += 16 * 4) {  // 4 MFMAs (16 rows) per wave per trip, loads issued together
-    float av[4], bv[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int m = m0 + q * 16 + mq;
-      const int mc = min(m, M - 1);
-      const float x = A[(size_t)mc * lda + kk], y = dY[(size_t)mc * ldy + nn];
-      av[q] = m < M ? x : 0.0f;
-      bv[q] = m < M ? y : 0.0f;
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q], bv[q], acc, 0, 0, 0);
-      bsum += bv[q];
-    }
-  }
-  // acc[i] of lane l = dW tile [row k = 4*(l>>4) + i][col n = l & 15]
-  float* r = red + wave * 256;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) r[(4 * mq + i) * 16 + (lane & 15)] = acc[i];
-  __syncthreads();
-  const float alpha = alpha_ptr != nullptr ? alpha_ptr[0] : 1.0f;
-  const float v = (red[tid] + red[256 + tid] + red[512 + tid] + red[768 + tid]) * alpha;
-  const int k = k0 + (tid >> 4), n = n0 + (tid & 15);
-  if (k < Kdim && n < Ndim) {
-    const int row = rowmap != nullptr ? rowmap[k] : k;  // A-segment position -> row of the reference matrix (-1: none)
-    if (row >= 0) {
-      float* p = dW + (size_t)row * ldw + n;
-      *p = accumulate ? *p + v : v;
-    }
-  }
-  if (db != nullptr && blockIdx.x == 0) {
-    // column sums: lanes with the same (l & 15) across mq and waves
-    bsum += __shfl_xor(bsum, 16, 64);
-    bsum += __shfl_xor(bsum, 32, 64);
-    __syncthreads();
-    if (lane < 16) red[wave * 16 + lane] = bsum;
-    __syncthreads();
-    if (tid < 16 && n0 + tid < Ndim) {
-      const float s = (red[tid] + red[16 + tid] + red[32 + tid] + red[48 + tid]) * alpha;
-      db[n0 + tid] = accumulate ? db[n0 + tid] + s : s;
-    }
-  }
-}
-
-int sq_launch_wgrad(const float* A, int lda, const float* dY, int ldy, float* dW, int ldw, float* db, int M, int Kdim,
-                    int Ndim, int accumulate, hipStream_t s, const int* rowmap, const float* alpha_ptr) {
-  SQ_LAUNCH(k_wgrad, dim3((Kdim + 15) / 16, (Ndim + 15) / 16), dim3(256), 0, s, A, lda, dY, ldy, dW, ldw, db, M,
-                     Kdim, Ndim, accumulate, rowmap, alpha_ptr);
-  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1013,6 +937,9 @@ static bool wgrad3_operands_ok(const float* A, int lda, const float* dY, int ldy
 static bool wgrad3_eligible(const float* A, int lda, const float* dY, int ldy, int M, int Kdim, int Ndim) {
   return wgrad3_operands_ok(A, lda, dY, ldy, Kdim, Ndim) && Kdim % 4 == 0 && Ndim % 4 == 0 && Kdim >= 48 && Ndim >= 48 && M >= 256;
 }
+static std::atomic<long long> g_wgrad_grouped{0}, g_wgrad_own{0};
+long long sq_wgrad_grouped_blocks() { return g_wgrad_grouped.load(); }
+long long sq_wgrad_own_launches() { return g_wgrad_own.load(); }
 static const size_t WG3_LDS = (4 * 4096 + 256) * sizeof(float);
 static const size_t WG1_LDS = SQ_WGRAD_GROUP_WAVES * (4096 + 64) * sizeof(float);  // k_wgrad_group: a tile + its column sums per wave
 bool WgradBatch::add(const float* A, int lda, const float* dY, int ldy, float* dW, int ldw, int M, int Kdim, int Ndim, const int* rowmap,
@@ -1092,6 +1019,7 @@ int WgradBatch::flush(hipStream_t s) {
                 g.d[i].Ndim, g.d[i].n_tiles, g.d[i].zc, g.d[i].m_per_wg, (double)g.d[i].Kdim * g.d[i].Ndim / (4096.0 * g.d[i].n_tiles));
     }
     SQ_LAUNCH(k_wgrad_group, dim3(grid), dim3(64 * SQ_WGRAD_GROUP_WAVES), WG1_LDS, s, g);
+    g_wgrad_grouped += nd;
   }
   blocks.clear();
   return 0;
@@ -1101,6 +1029,7 @@ int sq_launch_wgrad_acc(const float* A, int lda, const float* dY, int ldy, float
   static const int skip = SQ_KNOB_INT("SQAIR_WGRAD3", 1) < 0;  // measurement knob (knob builds only): no weight gradients at all
   const int wg3_target = 512;
   if (skip) return 0;
+  ++g_wgrad_own;
   if (wgrad3_eligible(A, lda, dY, ldy, M, Kdim, Ndim)) {
     const int kt = (Kdim + 63) / 64, nt = (Ndim + 63) / 64;
     int zc = wg3_target / (kt * nt);
@@ -1140,10 +1069,6 @@ int sq_launch_insert_bwd_frames(const float* glimpse, const float* rec, int rec_
   SQ_LAUNCH_INSERT_BWD(dim3(d.R, T), shm, s, a, d, band_rows);
   return 0;
 }
-int sq_launch_reduce_rows(const float* rows, float* out, int R, int P, int accumulate, hipStream_t s) {
-  SQ_LAUNCH(k_reduce_rows, dim3((P + 255) / 256), dim3(256), 0, s, rows, out, R, P, accumulate);
-  return 0;
-}
 int sq_launch_reduce_rows_atomic(const float* rows, float* out, int R, int P, hipStream_t s) {
   const int rpb = 32;
   SQ_LAUNCH(k_reduce_rows_atomic, dim3((P + 255) / 256, (R + rpb - 1) / rpb), dim3(256), 0, s, rows, out, R, P, rpb);
@@ -1152,51 +1077,6 @@ int sq_launch_reduce_rows_atomic(const float* rows, float* out, int R, int P, hi
 int sq_launch_elbo_bwd(const float* iw, const float* sig, int T, int B, int K, float* g_lw, float* g_dl, hipStream_t s) {
   const int n = T * B * K;
   SQ_LAUNCH(k_elbo_bwd, dim3((n + 255) / 256), dim3(256), 0, s, iw, sig, T, B, K, g_lw, g_dl);
-  return 0;
-}
-
-// d(output_scale) = sum(d_glimpse * glimpse) / scale   (glimpse = scale * raw; modules.py:144-147)
-__global__ void k_dot_scale(const float* __restrict__ a, const float* __restrict__ b, int64_t n, const float* __restrict__ scale,
-                            float* __restrict__ out SQ_TLP) {
-  SQ_TL_SCOPE;
-  __shared__ float red[16];
-  float acc = 0.0f;
-  for (int64_t i = threadIdx.x; i < n; i += 1024) acc += a[i] * b[i];
-  acc = sq_wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.0f;
-    for (int i = 0; i < 16; ++i) t += red[i];
-    out[0] = t / scale[0];
-  }
-}
-int sq_launch_dot_scale(const float* a, const float* b, int64_t n, const float* scale, float* out, hipStream_t s) {
-  SQ_LAUNCH(k_dot_scale, dim3(1), dim3(1024), 0, s, a, b, n, scale, out);
-  return 0;
-}
-
-// Elementwise adjoint of the fused activation epilogue: dPre = dOut * act'(.) expressed through the saved OUTPUT
-// (elu: out > 0 ? 1 : out + 1; tanh: 1 - out^2; sigmoid: out (1 - out); softplus(x) + c: 1 - exp(-(out - c))).
-__global__ void k_dact(const float* __restrict__ d_out, const float* __restrict__ out, float* __restrict__ d_pre, int64_t n,
-                       int act SQ_TLP) {
-  SQ_TL_SCOPE;
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float o = out[i];
-  float g = d_out[i];
-  switch (act) {
-    case ACT_ELU: g *= o > 0.0f ? 1.0f : o + 1.0f; break;
-    case ACT_TANH: g *= 1.0f - o * o; break;
-    case ACT_SIGMOID: g *= o * (1.0f - o); break;
-    case ACT_SOFTPLUS_MIN: g *= 1.0f - expf(-(o - 1e-2f)); break;
-    default: break;
-  }
-  d_pre[i] = g;
-}
-
-int sq_launch_dact(const float* d_out, const float* out, float* d_pre, int64_t n, int act, hipStream_t s) {
-  SQ_LAUNCH(k_dact, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_out, out, d_pre, n, act);
   return 0;
 }
 

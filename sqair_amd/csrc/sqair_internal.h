@@ -114,14 +114,6 @@ int sq_state_refusal(SqairHandle* h, bool train, int B, int t_offset);   // -1 +
 // (forward only, else NULL) is checked for the log weights SMC resamples on
 int sq_carry_refusal(SqairHandle* h, const char* fn, int B, const SqairCarry* carry, const SqairOutputs* out);
 bool sq_trainable_frame(SqairHandle* h);                   // false + error text when the handle's frames cannot be trained
-// The partial adjoint kept for unit tests (sqair_backward_decoder) takes the caller's frames as they are, and the full adjoint
-// kernels stage frames in 16-byte units: it wants H * W to be a multiple of 4 (the full passes stage other frames through a
-// padded copy; the per-kernel entry points sqair_st_*_bwd read frames word by word and take any size).
-inline bool sq_unit_frame_ok(SqairHandle* h) {
-  if (((h->cfg.img_h * h->cfg.img_w) & 3) == 0) return true;
-  sq_set_error(h, "this unit entry point needs H * W to be a multiple of 4 (use sqair_forward_train / sqair_backward for other frame sizes)");
-  return false;
-}
 int64_t P(const SqairHandle* h, const std::string& name);  // flat offset of a parameter (aborts on unknown names)
 int PC(const SqairHandle* h, const std::string& name);      // its number of columns
 

@@ -207,6 +207,85 @@ extern "C" int64_t sqair_backward_bytes(const SqairHandle* h, int T, int B) {
 
 #define CK(x) do { int _r = (x); if (_r != 0) { sq_set_error(h, std::string("sqair_backward: ") + #x); return _r; } } while (0)
 
+// dX through the transposed pack: out[M][K of the forward layer] (+)= dpre[M][N] W^T.  Single-segment layers write
+// exactly their true input width; multi-segment layers write all 16 * kc padded columns (the caller splits them).
+static int sq_dx(SqairHandle* h, const char* who, const float* packed, LayerId id, const float* dpre, int ld, int Mrows, float* outp,
+                 int out_ld, bool acc, const float* scale_ptr, hipStream_t s) {
+  const PackedLayout pl = packed_layout(h);
+  const PackedLayer& LT = h->layersT[id];
+  const PackedLayer& LF = h->layers[id];
+  Lin l;
+  l.seg(dpre, ld, LF.N).out(outp, out_ld).act(ACT_NONE);
+  l.a.scale_ptr = scale_ptr;
+  l.a.wp = packed + pl.w + LT.w_off; l.a.wzero = packed + pl.w; l.a.bias = packed + pl.b + LT.b_off;
+  l.a.M = Mrows; l.a.N = LF.seg_width.size() == 1 ? LF.seg_width[0] : LT.N;
+  if (acc) { l.a.add = outp; l.a.add_ld = out_ld; l.a.add_n = l.a.N; }
+  const int rc = sq_launch_linear(l.a, LT, s);
+  if (rc != 0) sq_set_error(h, std::string(who) + ": A-operand contract violated in dX of layer " + std::to_string((int)id));
+  return rc;
+}
+// batched weight + bias gradients of one layer over `rows` uses: every block joins the grouped launch at the end of the pass
+// (its operands must then stay as they are until wbatch.flush), or is launched on its own when the grouped kernel does not take it
+static void sq_wgrad_layer(const SqairHandle* h, const float* packed, LayerId id, const std::vector<std::pair<const float*, int>>& segs,
+                           const float* dY, int ldy, int rows, WgradBatch& wbatch, float* flat_grad, hipStream_t s) {
+  const int* rm_dev = (const int*)packed + packed_layout(h).rm;
+  // the bias gradient of a column block rides on the first weight-gradient launch of that block
+  std::vector<char> bias_done(h->bg[id].size(), 0);
+  for (const auto& e : h->wg[id]) {
+    float *dba = nullptr, *dbb = nullptr;
+    for (size_t bi = 0; bi < h->bg[id].size(); ++bi) {
+      const auto& be = h->bg[id][bi];
+      if (!bias_done[bi] && be.n0 == e.n0 && be.ncols == e.ncols) {
+        if (!be.a.empty()) dba = flat_grad + P(h, be.a) + be.col0;
+        if (!be.b.empty()) dbb = flat_grad + P(h, be.b) + be.col0;
+        bias_done[bi] = 1;
+      }
+    }
+    if (wbatch.add(segs[e.seg].first, segs[e.seg].second, dY + e.n0, ldy, flat_grad + P(h, e.w) + e.col0, PC(h, e.w), rows,
+                   h->layers[id].seg_width[e.seg], e.ncols, rm_dev + e.rm_off, nullptr, dba, dbb))
+      continue;
+    sq_launch_wgrad_acc(segs[e.seg].first, segs[e.seg].second, dY + e.n0, ldy, flat_grad + P(h, e.w) + e.col0, PC(h, e.w), rows,
+                        h->layers[id].seg_width[e.seg], e.ncols, s, rm_dev + e.rm_off, nullptr, dba, dbb);
+  }
+  for (size_t bi = 0; bi < h->bg[id].size(); ++bi)
+    if (!bias_done[bi]) {  // (no weight block with the same column range: plain column sums)
+      const auto& e = h->bg[id][bi];
+      if (!e.a.empty()) sq_launch_colsum(dY + e.n0, ldy, rows, e.ncols, flat_grad + P(h, e.a) + e.col0, 1, s);
+      if (!e.b.empty()) sq_launch_colsum(dY + e.n0, ldy, rows, e.ncols, flat_grad + P(h, e.b) + e.col0, 1, s);
+    }
+}
+
+// J^T: the decoder branch of all T frames (they are off the recurrence) -- the adjoint of the canvas and its log-likelihood, then
+// the three dense layers.  Reads the merged records rec_all [T][M][rec::W], the decoded glimpses, the decoder's two hidden
+// activations and the frames; accumulates the gradients of dec.* into flat_grad (mean image, output scale and the blocks the
+// grouped kernel declines at once, the other blocks when the caller flushes wbatch) and the seed gradients of the merged
+// latents into d_rec (row stride d_rec_ld: where from the canvas, what from layer 0's dX).  d_gl, d_mean_rows and the three
+// buffers are written in full; bufb and bufc stay operands of wbatch until its flush.  `who`: the entry point, for error texts.
+static int sq_decoder_adjoint(SqairHandle* h, const char* who, const float* flat, const float* packed, const float* obs, int T, const Dims& d,
+                              const float* rec_all, const float* glimpse, const float* dec_a, const float* dec_b, const float* g_lw,
+                              float* d_gl, float* d_mean_rows, float* bufa, float* bufb, float* bufc, float* d_rec, int d_rec_ld,
+                              WgradBatch& wbatch, float* flat_grad, hipStream_t s) {
+  const SqairConfig& c = h->cfg;
+  const POff& po = h->po;
+  const int nh = c.n_hidden, MT = d.R * d.N * T, G2 = d.G * d.G, RW = rec::W;
+  const float* scale = flat + po.dec_output_scale;
+  int rc = sq_launch_insert_bwd_frames(glimpse, rec_all, RW, obs, flat + po.dec_mean_img, g_lw, d_gl, d_rec + rec::WHERE, d_rec_ld, d_mean_rows,
+                                       c.output_std, c.background_std, T, d, s, scale, flat_grad + po.dec_output_scale);
+  if (rc != 0) { sq_set_error(h, std::string(who) + ": the decoder canvas adjoint launch failed (dynamic LDS limit)"); return rc; }
+  sq_launch_reduce_rows_atomic(d_mean_rows, flat_grad + po.dec_mean_img, T * d.R, d.H * d.W, s);
+  if (!wbatch.add(dec_b, nh, d_gl, G2, flat_grad + P(h, "dec.l2.w"), G2, MT, nh, G2, nullptr, scale, flat_grad + P(h, "dec.l2.b"), nullptr))
+    sq_launch_wgrad_acc(dec_b, nh, d_gl, G2, flat_grad + P(h, "dec.l2.w"), G2, MT, nh, G2, s, nullptr, scale,
+                        flat_grad + P(h, "dec.l2.b"), nullptr);
+  if ((rc = sq_dx(h, who, packed, L_DEC2, d_gl, G2, MT, bufa, nh, false, scale, s)) != 0) return rc;
+  sq_launch_dact2(bufa, nh, dec_b, nh, bufb, nh, MT, nh, ACT_ELU, ACT_ELU, 1 << 30, 0, s);
+  sq_wgrad_layer(h, packed, L_DEC1, {{dec_a, nh}}, bufb, nh, MT, wbatch, flat_grad, s);
+  if ((rc = sq_dx(h, who, packed, L_DEC1, bufb, nh, MT, bufa, nh, false, nullptr, s)) != 0) return rc;
+  sq_launch_dact2(bufa, nh, dec_a, nh, bufc, nh, MT, nh, ACT_ELU, ACT_ELU, 1 << 30, 0, s);
+  sq_wgrad_layer(h, packed, L_DEC0, {{rec_all, RW}}, bufc, nh, MT, wbatch, flat_grad, s);
+  if ((rc = sq_dx(h, who, packed, L_DEC0, bufc, nh, MT, d_rec, d_rec_ld, true, nullptr, s)) != 0) return rc;
+  return 0;
+}
+
 // What the two slot loops of the reverse sweep differ in -- propagation (tape phase 0) and discovery (phase 1) -- filled once per
 // frame; the lower part of the slot adjoint (sqair_backward: slot_adjoint) is the same code for both.
 struct SlotAdjPhase {
@@ -254,7 +333,6 @@ static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, c
   if ((P_ & 3) != 0) { d.P4 = (P_ + 3) / 4 * 4; obs = w.obs_p; }
   const int PL = d.P4;
   const int pre_ld = h->layers[L_PRE].nt * 16;
-  const int* rm_dev = (const int*)packed + pl.rm;
 
   if ((reinterpret_cast<uintptr_t>(flat_grad) & 15) != 0) {
     sq_set_error(h, "sqair_backward: flat_grad must be 16-byte aligned");
@@ -274,22 +352,6 @@ static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, c
   }
 #endif
 
-  // dX through the transposed pack: out[M][K of the forward layer] (+)= dpre[M][N] W^T.  Single-segment layers write
-  // exactly their true input width; multi-segment layers write all 16 * kc padded columns (the caller splits them).
-  auto dx = [&](LayerId id, const float* dpre, int ld, int Mrows, float* outp, int out_ld, bool acc,
-                const float* scale_ptr = nullptr) -> int {
-    const PackedLayer& LT = h->layersT[id];
-    const PackedLayer& LF = h->layers[id];
-    Lin l;
-    l.seg(dpre, ld, LF.N).out(outp, out_ld).act(ACT_NONE);
-    l.a.scale_ptr = scale_ptr;
-    l.a.wp = packed + pl.w + LT.w_off; l.a.wzero = packed + pl.w; l.a.bias = packed + pl.b + LT.b_off;
-    l.a.M = Mrows; l.a.N = LF.seg_width.size() == 1 ? LF.seg_width[0] : LT.N;
-    if (acc) { l.a.add = outp; l.a.add_ld = out_ld; l.a.add_n = l.a.N; }
-    const int rc = sq_launch_linear(l.a, LT, s);
-    if (rc != 0) sq_set_error(h, "sqair_backward: A-operand contract violated in dX of layer " + std::to_string((int)id));
-    return rc;
-  };
   auto rundx = [&](LayerId id, Dx& dxa, int Mrows, const float* scale_ptr = nullptr) -> int {
     const PackedLayer& LT = h->layersT[id];
     dxa.a.width = h->layers[id].N; dxa.a.wp = packed + pl.w + LT.w_off; dxa.a.wzero = packed + pl.w;
@@ -298,34 +360,10 @@ static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, c
     if (rc != 0) sq_set_error(h, "sqair_backward: A-operand contract violated in dX of layer " + std::to_string((int)id));
     return rc;
   };
-  // batched weight + bias gradients of one layer over `rows` uses
-  // `defer`: the block joins the grouped launch at the end of the pass (its operands must then stay as they are until there)
   WgradBatch wbatch;
-  auto wgrad = [&](LayerId id, std::vector<std::pair<const float*, int>> segs, const float* dY, int ldy, int rows, bool defer = true) {
-    // the bias gradient of a column block rides on the first weight-gradient launch of that block
-    std::vector<char> bias_done(h->bg[id].size(), 0);
-    for (const auto& e : h->wg[id]) {
-      float *dba = nullptr, *dbb = nullptr;
-      for (size_t bi = 0; bi < h->bg[id].size(); ++bi) {
-        const auto& be = h->bg[id][bi];
-        if (!bias_done[bi] && be.n0 == e.n0 && be.ncols == e.ncols) {
-          if (!be.a.empty()) dba = flat_grad + P(h, be.a) + be.col0;
-          if (!be.b.empty()) dbb = flat_grad + P(h, be.b) + be.col0;
-          bias_done[bi] = 1;
-        }
-      }
-      if (defer && wbatch.add(segs[e.seg].first, segs[e.seg].second, dY + e.n0, ldy, flat_grad + P(h, e.w) + e.col0, PC(h, e.w), rows,
-                              h->layers[id].seg_width[e.seg], e.ncols, rm_dev + e.rm_off, nullptr, dba, dbb))
-        continue;
-      sq_launch_wgrad_acc(segs[e.seg].first, segs[e.seg].second, dY + e.n0, ldy, flat_grad + P(h, e.w) + e.col0, PC(h, e.w), rows,
-                          h->layers[id].seg_width[e.seg], e.ncols, s, rm_dev + e.rm_off, nullptr, dba, dbb);
-    }
-    for (size_t bi = 0; bi < h->bg[id].size(); ++bi)
-      if (!bias_done[bi]) {  // (no weight block with the same column range: plain column sums)
-        const auto& e = h->bg[id][bi];
-        if (!e.a.empty()) sq_launch_colsum(dY + e.n0, ldy, rows, e.ncols, flat_grad + P(h, e.a) + e.col0, 1, s);
-        if (!e.b.empty()) sq_launch_colsum(dY + e.n0, ldy, rows, e.ncols, flat_grad + P(h, e.b) + e.col0, 1, s);
-      }
+  // (kept as a lambda: the ~45 calls below differ only in the layer, its operands and the row count)
+  auto wgrad = [&](LayerId id, std::vector<std::pair<const float*, int>> segs, const float* dY, int ldy, int rows) {
+    sq_wgrad_layer(h, packed, id, segs, dY, ldy, rows, wbatch, flat_grad, s);
   };
   auto slotp = [&](float* base, int W, int t, int ph, int k) { return base + (((size_t)(ph * T + t) * R * N) + k) * W; };
   auto cslotp = [&](const float* base, int W, int t, int ph, int k) { return base + (((size_t)(ph * T + t) * R * N) + k) * W; };
@@ -342,23 +380,9 @@ static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, c
 
   // ================= J^T. decoder branch, all frames =================
   {
-    const float* rec_all = w.rec_m_all + (size_t)M * RW;
-    float* d_rec_all = b.d_rec_m + (size_t)M * RW;
-    const float* gl = w.glimpse;
-    const float* scale = flat + po.dec_output_scale;
-    CK(sq_launch_insert_bwd_frames(gl, rec_all, RW, obs, flat + po.dec_mean_img, b.g_lw, b.d_gl, d_rec_all + rec::WHERE, RW,
-                                   b.d_mean_rows, c.output_std, c.background_std, T, d, s, scale, flat_grad + po.dec_output_scale));
-    sq_launch_reduce_rows_atomic(b.d_mean_rows, flat_grad + po.dec_mean_img, T * R, P_, s);
-    if (!wbatch.add(w.dec_b, nh, b.d_gl, G2, flat_grad + P(h, "dec.l2.w"), G2, MT, nh, G2, nullptr, scale, flat_grad + P(h, "dec.l2.b"), nullptr))
-      sq_launch_wgrad_acc(w.dec_b, nh, b.d_gl, G2, flat_grad + P(h, "dec.l2.w"), G2, MT, nh, G2, s, nullptr, scale,
-                          flat_grad + P(h, "dec.l2.b"), nullptr);
-    CK(dx(L_DEC2, b.d_gl, G2, MT, b.bufa, nh, false, scale));
-    sq_launch_dact2(b.bufa, nh, w.dec_b, nh, b.bufb, nh, MT, nh, ACT_ELU, ACT_ELU, 1 << 30, 0, s);
-    wgrad(L_DEC1, {{w.dec_a, nh}}, b.bufb, nh, MT);
-    CK(dx(L_DEC1, b.bufb, nh, MT, b.bufa, nh, false));
-    sq_launch_dact2(b.bufa, nh, w.dec_a, nh, b.bufc, nh, MT, nh, ACT_ELU, ACT_ELU, 1 << 30, 0, s);
-    wgrad(L_DEC0, {{rec_all, RW}}, b.bufc, nh, MT);
-    CK(dx(L_DEC0, b.bufc, nh, MT, d_rec_all, RW, true));
+    const int rc = sq_decoder_adjoint(h, "sqair_backward", flat, packed, obs, T, d, w.rec_m_all + (size_t)M * RW, w.glimpse, w.dec_a, w.dec_b,
+                                      b.g_lw, b.d_gl, b.d_mean_rows, b.bufa, b.bufb, b.bufc, b.d_rec_m + (size_t)M * RW, RW, wbatch, flat_grad, s);
+    if (rc != 0) return rc;   // (the error text is the failing launch's)
   }
   // ================= H^T. log-probabilities, all frames =================
   {
@@ -795,6 +819,70 @@ extern "C" int sqair_backward_carry_masked(SqairHandle* h, const float* flat, co
   if (sq_observed_refusal(h, true, T) != 0 || sq_carry_refusal(h, "sqair_backward_carry_masked", B, carry, nullptr) != 0) return -1;
   return sq_backward(h, flat, packedv, obs, noise, importance_weights, vimco_signal, T, B, 0, true, observed, train_workspace,
                      workspace_bytes, scratch, scratch_bytes, flat_grad, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The decoder branch on its own (unit-test entry): sq_decoder_adjoint after sqair_forward + sqair_elbo on the INFERENCE
+// workspace, which keeps the merged records, the decoder's activations and the glimpses of all T frames.  The gradients of
+// the eight decoder parameters are zeroed first (every kernel of the branch accumulates with atomics), the other entries of
+// flat_grad are left alone.  Takes the caller's frames and flat buffers as they are: no padded configurations, no wide
+// record, H * W a multiple of 4 (sqair_backward stages other frames through a padded copy).
+// ------------------------------------------------------------------------------------------------
+struct DecSpace { float *g_lw, *g_dl, *d_gl, *d_mean_rows, *bufa, *bufb, *bufc, *d_rec; int64_t total; };
+static DecSpace carve_dec(const SqairHandle* h, int T, int B, float* base) {
+  const SqairConfig& c = h->cfg;
+  const int64_t R = (int64_t)B * c.k_particles, MT = R * c.n_steps_per_image * T;
+  const int64_t G2 = c.glimpse_size * c.glimpse_size, P_ = c.img_h * c.img_w, nh = c.n_hidden;
+  DecSpace b;
+  int64_t o = 0;
+  auto T_ = [&](float*& dst, int64_t n) { dst = base ? base + o : nullptr; o += align64(n); };  // 256-byte aligned (GEMM A-operand contract)
+  T_(b.g_lw, T * R); T_(b.g_dl, T * R); T_(b.d_gl, MT * G2); T_(b.d_mean_rows, T * R * P_);
+  T_(b.bufa, MT * nh); T_(b.bufb, MT * nh); T_(b.bufc, MT * nh); T_(b.d_rec, MT * 64);
+  b.total = o;
+  return b;
+}
+extern "C" int64_t sqair_backward_scratch_bytes(const SqairHandle* h, int T, int B) {
+  if (!h || T < 1 || B < 1) return -1;
+  return carve_dec(h, T, B, nullptr).total * 4;
+}
+extern "C" int sqair_backward_decoder(SqairHandle* h, const float* flat, const void* packedv, const float* obs,
+                                      const float* importance_weights, const float* vimco_signal, int T, int B,
+                                      void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes,
+                                      float* flat_grad, float* d_rec_out, void* stream) {
+  if (!h || !flat || !packedv || !obs || !importance_weights || !vimco_signal || !workspace || !scratch || !flat_grad) return -1;
+  if (workspace_bytes < sqair_workspace_bytes(h, T, B) || scratch_bytes < sqair_backward_scratch_bytes(h, T, B)) {
+    sq_set_error(h, "sqair_backward_decoder: workspace / scratch too small");
+    return -1;
+  }
+  if (((h->cfg.img_h * h->cfg.img_w) & 3) != 0) {
+    sq_set_error(h, "this unit entry point needs H * W to be a multiple of 4 (use sqair_forward_train / sqair_backward for other frame sizes)");
+    return -1;
+  }
+  if (!sq_trainable_frame(h)) return -1;
+  if (h->padded || rec::ZWP != 64) {
+    sq_set_error(h, "sqair_backward_decoder (a partial adjoint kept for unit tests) writes in the product build's own shapes: use sqair_backward in the wide build or with an n_hidden that is padded");
+    return -1;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const SqairConfig& c = h->cfg;
+  const Dims d = make_dims(c, B);
+  const int64_t M = (int64_t)d.R * d.N, MT = M * T;
+  const Workspace w = sq_carve(h, T, B, (float*)workspace, false);
+  const DecSpace b = carve_dec(h, T, B, (float*)scratch);
+  for (const char* name : {"dec.mean_img", "dec.l0.w", "dec.l0.b", "dec.l1.w", "dec.l1.b", "dec.l2.w", "dec.l2.b", "dec.output_scale"}) {
+    const ParamEntry& e = h->params[h->pidx.at(name)];
+    SQ_CHECK_HIP(hipMemsetAsync(flat_grad + e.off, 0, (size_t)e.numel * 4, s));
+  }
+  SQ_CHECK_HIP(hipMemsetAsync(b.d_rec, 0, (size_t)MT * 64 * 4, s));
+  sq_launch_elbo_bwd(importance_weights, vimco_signal, T, B, c.k_particles, b.g_lw, b.g_dl, s);
+  WgradBatch wbatch;
+  const int rc = sq_decoder_adjoint(h, "sqair_backward_decoder", flat, (const float*)packedv, obs, T, d, w.rec_m_all + (size_t)M * rec::W, w.glimpse, w.dec_a,
+                                    w.dec_b, b.g_lw, b.d_gl, b.d_mean_rows, b.bufa, b.bufb, b.bufc, b.d_rec, 64, wbatch, flat_grad, s);
+  if (rc != 0) return rc;
+  if (wbatch.flush(s) != 0) { sq_set_error(h, "sqair_backward_decoder: the grouped weight-gradient launch failed"); return -2; }
+  if (d_rec_out) SQ_CHECK_HIP(hipMemcpyAsync(d_rec_out, b.d_rec, (size_t)MT * 64 * 4, hipMemcpyDeviceToDevice, s));
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------

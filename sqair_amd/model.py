@@ -420,16 +420,19 @@ class SqairCore(object):
             out[name] = self.flat_grad[o:o + n].reshape(shape)
         return out
 
-    def backward_decoder(self):
-        """Decoder branch of the backward pass (first slice of the training step, see include/sqair_hip.h):
-        gradients of the VIMCO target w.r.t. the decoder parameters as a dict name -> tensor, plus the seed
-        gradients on the merged latents.  Requires a preceding forward() whose outputs did not request `glimpse`."""
+    def backward_decoder(self, flat_grad=None):
+        """Decoder branch of the backward pass on its own (a unit-test entry that runs the full pass's decoder adjoint, see
+        include/sqair_hip.h): gradients of the VIMCO target w.r.t. the decoder parameters as a dict name -> tensor, plus the
+        seed gradients on the merged latents.  Requires a preceding forward() whose outputs did not request `glimpse`.
+        `flat_grad`: the caller's flat gradient buffer (the entry overwrites the dec.* ranges and leaves the rest), default zeros."""
         assert "glimpse" not in self.out, "bind(outputs=...) without 'glimpse' so that the glimpses stay in the workspace"
         R, M = self.B * self.K, self.B * self.K * self.N
         with torch.cuda.device(self.device):
             nb = self.lib.sqair_backward_scratch_bytes(self.handle, self.T, self.B)
             scratch = torch.empty(nb // 4, dtype=torch.float32, device=self.device)
-            flat_grad = torch.zeros_like(self.flat)
+            if flat_grad is None:
+                flat_grad = torch.zeros_like(self.flat)
+            assert flat_grad.shape == self.flat.shape and flat_grad.dtype == torch.float32 and flat_grad.is_contiguous()
             d_rec = torch.zeros(self.T, M, 64, dtype=torch.float32, device=self.device)
             self._join_in()
             self.check(self.lib.sqair_backward_decoder(

@@ -231,3 +231,26 @@ def test_compaction_test_entries_host_side():
                 assert lib.sqair_compact_bwd_test(h, *([None] * 10), 1, None) == -1
             finally:
                 lib.sqair_destroy(h)
+
+
+def test_backward_decoder_refusals_host_side():
+    """sqair_backward_decoder (the decoder adjoint of the training step as a unit entry) says no before any HIP call to what it
+    does not serve -- an n_hidden that is padded, a frame whose H * W is not a multiple of 4 -- and its scratch size answers
+    without a GPU."""
+    lib = _capi.lib()
+    T, B = 3, 4
+    buf = (C.c_float * 16)()     # stands for every device buffer: a refusal comes before anything is read
+    for flags, hw, msg in ((dict(n_units=5), (50, 50), b"an n_hidden that is padded"), (dict(), (37, 41), b"needs H * W to be a multiple of 4")):
+        cfg = make_config(make_flags(k_particles=2, n_steps_per_image=3, **flags), hw)
+        h = C.c_void_p()
+        assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
+        try:
+            nb = lib.sqair_backward_scratch_bytes(h, T, B)
+            assert nb > 0 and lib.sqair_backward_scratch_bytes(h, 0, B) == -1
+            rc = lib.sqair_backward_decoder(h, buf, buf, buf, buf, buf, T, B, buf, lib.sqair_workspace_bytes(h, T, B), buf, nb, buf, None,
+                                            None)
+            assert rc == -1 and msg in lib.sqair_last_error(h), lib.sqair_last_error(h)
+            assert lib.sqair_backward_decoder(h, buf, buf, buf, buf, buf, T, B, buf, lib.sqair_workspace_bytes(h, T, B), buf, nb - 4, buf,
+                                              None, None) == -1 and b"too small" in lib.sqair_last_error(h)
+        finally:
+            lib.sqair_destroy(h)

@@ -169,11 +169,24 @@ def test_elbo_reinforce_signal(K):
         lib.sqair_destroy(h)
 
 
+def _wgrad_launches(lib):
+    """(blocks flushed through k_wgrad_group, own launches of sq_launch_wgrad_acc) by this process so far."""
+    grouped, own = C.c_int64(-1), C.c_int64(-1)
+    assert lib.sqair_debug_wgrad_launches(C.byref(grouped), C.byref(own)) == 0
+    return grouped.value, own.value
+
+
 @pytest.mark.parametrize("M,K,N,act", [(160, 256, 256, 1), (640, 400, 256, 1), (6400, 56, 256, 1), (160, 311, 128, 2),
-                                       (37, 54, 109, 0), (160, 256, 100, 4), (33, 128, 400, 3)])
+                                       (37, 54, 109, 0), (160, 256, 100, 4), (33, 128, 400, 3), (37, 56, 112, 1),
+                                       (160, 576, 256, 1)])
 def test_linear_backward_mfma(M, K, N, act):
+    """One dense layer backward on the kernels the training step runs: dx through k_linear on the transposed pack, dw / db routed as
+    sqair_backward routes a block.  K % 4 != 0 (311, 54: x's rows are not 16-byte aligned) goes to k_wgrad2 as its own launch,
+    every other shape to k_wgrad_group: 6400 rows are five M-chunks that meet through atomics, 37 rows a partial 16-row step,
+    K = 56 less than one 64-wide tile, 576 x 256 = 36 tiles dealt in two groups."""
     lib, h, F = _handle(2, 3, (50, 50))
     try:
+        before = _wgrad_launches(lib)
         rng = np.random.default_rng(M + K)
         x = rng.standard_normal((M, K)).astype(np.float32)
         w = (rng.standard_normal((K, N)) / np.sqrt(K)).astype(np.float32)
@@ -193,6 +206,8 @@ def test_linear_backward_mfma(M, K, N, act):
                                        dw.data_ptr(), db.data_ptr(), M, K, N, act, scratch.data_ptr(), scratch.numel() * 4,
                                        stream())
         assert rc == 0, lib.sqair_last_error(h)
+        grouped, own = (a - b for a, b in zip(_wgrad_launches(lib), before))
+        assert (grouped, own) == ((0, 1) if K % 4 else (1, 0))
         assert rel_err(dx.cpu().numpy(), x64.grad.numpy()) < 2e-5
         assert rel_err(dw.cpu().numpy(), w64.grad.numpy()) < 2e-5 * max(1.0, np.sqrt(M / 160.0))
         assert rel_err(db.cpu().numpy(), b64.grad.numpy()) < 2e-5 * max(1.0, np.sqrt(M / 160.0))
@@ -222,7 +237,15 @@ def test_backward_decoder_branch_matches_autograd(K, N, T, B, hw):
     assert np.array_equal(m.prop_pres.cpu().numpy(), ref.prop_pres.detach().numpy())
     assert np.array_equal(m.disc_pres.cpu().numpy(), ref.disc_pres.detach().numpy())
     orc.make_target(ref).backward()
-    grads, d_rec = core.backward_decoder()
+    # the caller's gradient buffer arrives full of a sentinel: the entry overwrites the eight dec.* ranges and nothing else
+    flat_grad = torch.full_like(core.flat, 7.25)
+    grads, d_rec = core.backward_decoder(flat_grad=flat_grad)
+    assert sorted(grads) == ["dec.l0.b", "dec.l0.w", "dec.l1.b", "dec.l1.w", "dec.l2.b", "dec.l2.w", "dec.mean_img", "dec.output_scale"]
+    other = torch.ones(flat_grad.numel(), dtype=torch.bool)
+    for name, (o, shape) in core.offsets.items():
+        if name.startswith("dec."):
+            other[o:o + (int(np.prod(shape)) if len(shape) else 1)] = False
+    assert other.sum() > 0 and bool((flat_grad.cpu()[other] == 7.25).all())
     for name, g in grads.items():
         want = orc.P[name].grad.numpy()
         got = g.cpu().numpy().reshape(want.shape)
