@@ -938,6 +938,88 @@ int sqair_linear_bwd_test(SqairHandle* h, const float* x, const float* w, const 
                           float* dw, float* db, int M, int Kdim, int Ndim, int act, void* scratch,
                           int64_t scratch_bytes, void* stream);
 
+/* ---- the dense family's operand contract and the routed dX launcher, one launch each (test helpers) ------------------------
+ * Both entries hand the caller's operand pointers, pitches and divisors to the launcher UNCHANGED (no staging copy): the caller
+ * owns alignment (segment / dpre base on 16 bytes, pitch a multiple of 4 floats -- otherwise the launcher refuses, -5, and
+ * nothing is launched), the readable and finite round_up(width, 4) floats of every operand row, and ceil(M / rdiv) rows behind a
+ * row divisor.  Only the weights are packed into `scratch`.  Errors carry the entry's name (sqair_last_error). */
+typedef struct SqairDenseSeg {
+  const float* p;          /* row r of the layer reads p + (r / rdiv) * ld */
+  int32_t ld;              /* 0 = one broadcast row */
+  int32_t width;           /* inputs taken from this segment */
+  int32_t rdiv;            /* >= 1 */
+} SqairDenseSeg;
+/* out[m, n] = act(sum_i x_i[m / rdiv_i] W_i + b + (n < add_n ? add[m / add_rdiv, n] : 0))[n] * scale * *scale_ptr, n < N; act = act_a
+ * for n < act_split, act_b otherwise (codes of sqair_linear_test).  w: dense row-major [sum(width), N], segment after segment;
+ * b [N] or NULL; add / scale_ptr NULL = none; out_ld >= N.  scratch >= 4 * (2 * nt * kc * 256 + 32 * nt + 256) bytes with
+ * kc = sum_i ceil(width_i / 16), nt = ceil(N / 16). */
+typedef struct SqairDenseContract {
+  int32_t nseg;            /* 1..4 */
+  SqairDenseSeg seg[4];
+  const float* w;
+  const float* b;
+  const float* add;
+  int32_t add_ld, add_n, add_rdiv;
+  int32_t act_a, act_b, act_split;
+  float scale;
+  const float* scale_ptr;
+  float* out;
+  int32_t out_ld, M, N;
+  void* scratch;
+  int64_t scratch_bytes;
+} SqairDenseContract;
+int sqair_linear_contract_test(SqairHandle* h, const SqairDenseContract* c, void* stream);
+
+/* The routed dX GEMM of the training step: v = dpre [M, width] (pitch ld) W^T * *scale_ptr for the forward matrix w [Kdim, width];
+ * columns [n0, n1) of v (n0 a multiple of 16) go to range i: dst[m, n - n0] = dact(v + add[m, n - n0], saved[m, n - n0]) and the same
+ * to dst2; add may be dst (accumulate); saved = the producing layer's saved OUTPUT, its activation act_a for n - n0 < act_split,
+ * act_b otherwise; every pointer but dst optional.  gru.mode 1 / 2: the GRU gate adjoints in the epilogue instead (one range
+ * [0, nh) without saved): mode 1, g = v: dpre1[:, 0:nh] = g (hc - h) z (1 - z), dpre1[:, 2nh:3nh] = g z (1 - hc^2), d_h (+)= g (1 - z)
+ * with z = g0, hc = g1, h = hprev; dup[:, 0:nh] and dup[:, dup_h_off:] (dup_h_off >= 0) receive second copies of the two; mode 2,
+ * g = v: dpre1[:, nh:2nh] = dup = g h r (1 - r), d_h += g r with r = g0.  Returns the launcher's code: -5 (alignment, pitch, a range
+ * start off 16 columns, nranges outside 1..3), -6 (a GRU block with a saved pointer, with more than the one range [0, nh), or
+ * deeper than the build's instantiations: width > 256 on the product library).
+ * scratch >= 4 * (2 * nt * kc * 256 + 256) bytes with kc = ceil(width / 16), nt = ceil(Kdim / 16). */
+typedef struct SqairDxRange {
+  int32_t n0, n1;
+  float* dst; int32_t dst_ld;
+  float* dst2; int32_t dst2_ld;
+  const float* add; int32_t add_ld;
+  const float* saved; int32_t saved_ld;
+  int32_t act_a, act_b, act_split;
+} SqairDxRange;
+typedef struct SqairDxGru {
+  int32_t mode;
+  const float* g0; int32_t g0_ld;
+  const float* g1; int32_t g1_ld;
+  const float* hprev; int32_t h_ld;
+  float* dpre1; int32_t dp_ld;
+  float* d_h; int32_t dh_ld, acc_dh;
+  float* dup; int32_t dup_ld, dup_h_off;
+  int32_t nh;
+} SqairDxGru;
+typedef struct SqairDxTest {
+  const float* dpre; int32_t ld, width, M;
+  const float* w; int32_t Kdim;
+  const float* scale_ptr;
+  int32_t nranges;
+  SqairDxRange r[3];
+  SqairDxGru gru;
+  void* scratch;
+  int64_t scratch_bytes;
+} SqairDxTest;
+int sqair_linear_dx_test(SqairHandle* h, const SqairDxTest* t, void* stream);
+
+/* Which kernel family the two dense launchers chose, counted on the host per process (launches issued or captured so far), at the
+ * point of the choice: out[0:n] receives the first n of the SQAIR_DENSE_ROUTES counts below, the return value is their number.
+ *   forward (sq_launch_linear):  0 split-K (k_linear) | 1 32 x 32 tiles (k_linear_t2) | 2 k_linear_rows | 3 k_linear_mt |
+ *                                4 k_linear_lds | k_linear_big with wave tile 5 2 x 2 | 6 3 x 2 | 7 3 x 3 | 8 4 x 2
+ *   dX (sq_launch_linear_dx):    k_linear_dx<NCH> with NCH = 9 1 | 10 2 | 11 3 | 12 4 | 13 5 | 14 6 | 15 7 | 16 8 | 17 9 | 18 12 |
+ *                                19 18 | 20 32 x 32 tiles (k_linear_dx_t2) | 21 GRU mode 1 | 22 GRU mode 2
+ * A refused launch (-5, -6) and an empty one count nothing. */
+#define SQAIR_DENSE_ROUTES 23
+int sqair_debug_dense_routes(int64_t* out, int n);
+
 #ifdef __cplusplus
 }
 #endif

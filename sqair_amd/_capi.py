@@ -154,6 +154,53 @@ class SqairTraceLane(C.Structure):
     _fields_ = [("iou_min", C.c_float)] + [(n, C.c_void_p) for n in TRACK_LANE_FIELDS]
 
 
+class SqairDenseSeg(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("ld", C.c_int32), ("width", C.c_int32), ("rdiv", C.c_int32)]
+
+
+class SqairDenseContract(C.Structure):
+    """One dense launch with everything the operand contract can say (include/sqair_hip.h: sqair_linear_contract_test); device
+    addresses, handed to the launcher unchanged."""
+    _fields_ = [("nseg", C.c_int32), ("seg", SqairDenseSeg * 4), ("w", C.c_void_p), ("b", C.c_void_p), ("add", C.c_void_p),
+                ("add_ld", C.c_int32), ("add_n", C.c_int32), ("add_rdiv", C.c_int32), ("act_a", C.c_int32), ("act_b", C.c_int32),
+                ("act_split", C.c_int32), ("scale", C.c_float), ("scale_ptr", C.c_void_p), ("out", C.c_void_p), ("out_ld", C.c_int32),
+                ("M", C.c_int32), ("N", C.c_int32), ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64)]
+
+
+class SqairDxRange(C.Structure):
+    _fields_ = [("n0", C.c_int32), ("n1", C.c_int32), ("dst", C.c_void_p), ("dst_ld", C.c_int32), ("dst2", C.c_void_p),
+                ("dst2_ld", C.c_int32), ("add", C.c_void_p), ("add_ld", C.c_int32), ("saved", C.c_void_p), ("saved_ld", C.c_int32),
+                ("act_a", C.c_int32), ("act_b", C.c_int32), ("act_split", C.c_int32)]
+
+
+class SqairDxGru(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("g0", C.c_void_p), ("g0_ld", C.c_int32), ("g1", C.c_void_p), ("g1_ld", C.c_int32),
+                ("hprev", C.c_void_p), ("h_ld", C.c_int32), ("dpre1", C.c_void_p), ("dp_ld", C.c_int32), ("d_h", C.c_void_p),
+                ("dh_ld", C.c_int32), ("acc_dh", C.c_int32), ("dup", C.c_void_p), ("dup_ld", C.c_int32), ("dup_h_off", C.c_int32),
+                ("nh", C.c_int32)]
+
+
+class SqairDxTest(C.Structure):
+    """One launch of the routed dX GEMM (include/sqair_hip.h: sqair_linear_dx_test); device addresses, handed on unchanged."""
+    _fields_ = [("dpre", C.c_void_p), ("ld", C.c_int32), ("width", C.c_int32), ("M", C.c_int32), ("w", C.c_void_p),
+                ("Kdim", C.c_int32), ("scale_ptr", C.c_void_p), ("nranges", C.c_int32), ("r", SqairDxRange * 3), ("gru", SqairDxGru),
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64)]
+
+
+# sqair_debug_dense_routes: the families of the two dense launchers, in the order include/sqair_hip.h documents
+DENSE_ROUTES = ("fwd_splitk", "fwd_t2", "fwd_rows", "fwd_mt", "fwd_lds", "fwd_big_2x2", "fwd_big_3x2", "fwd_big_3x3", "fwd_big_4x2",
+                "dx_nch1", "dx_nch2", "dx_nch3", "dx_nch4", "dx_nch5", "dx_nch6", "dx_nch7", "dx_nch8", "dx_nch9", "dx_nch12", "dx_nch18",
+                "dx_t2", "dx_gru1", "dx_gru2")
+
+
+def dense_routes(library=None):
+    """{family: launches of it this process has issued or captured so far} for the two dense launchers."""
+    v = (C.c_int64 * len(DENSE_ROUTES))()
+    n = (library or lib()).sqair_debug_dense_routes(v, len(DENSE_ROUTES))
+    assert n == len(DENSE_ROUTES), "the library counts {} dense routes, this binding names {}".format(n, len(DENSE_ROUTES))
+    return dict(zip(DENSE_ROUTES, (int(x) for x in v)))
+
+
 _PROTOS = {
     "sqair_abi_version": (C.c_int, []),
     "sqair_build_id": (C.c_char_p, []),
@@ -259,6 +306,9 @@ _PROTOS = {
     "sqair_rmsprop_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
                                      C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "sqair_linear_bwd_test": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 4 + [C.c_void_p, C.c_int64, C.c_void_p]),
+    "sqair_linear_contract_test": (C.c_int, [C.c_void_p, C.POINTER(SqairDenseContract), C.c_void_p]),
+    "sqair_linear_dx_test": (C.c_int, [C.c_void_p, C.POINTER(SqairDxTest), C.c_void_p]),
+    "sqair_debug_dense_routes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
     "sqair_debug_linear_time": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_void_p]),
     "sqair_debug_linear_graph_time": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -275,7 +325,8 @@ _PROTOS = {
                                    C.POINTER(C.c_int)]),
 }
 
-EXPORTED_SYMBOLS = [n for n in _PROTOS if not n.startswith("sqair_debug")]
+# what include/sqair_hip.h declares: everything but the measurement helpers -- and the one read-out among them that it documents
+EXPORTED_SYMBOLS = [n for n in _PROTOS if not n.startswith("sqair_debug") or n == "sqair_debug_dense_routes"]
 
 TIMELINE_LIB_PATH = os.path.join(_HERE, "libsqair_hip_timeline.so")
 # the same sources compiled with -DSQAIR_WIDE: the rest of the reference's flag range (n_what up to 128, up to 16 object slots,

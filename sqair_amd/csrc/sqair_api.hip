@@ -23,6 +23,7 @@
 #include "sqair_internal.h"
 #include "sqair_chain.h"
 #include "sqair_bwd.h"
+#include "sqair_dx.h"
 
 void sq_set_error(SqairHandle* h, const std::string& msg) {
   if (h) h->err = msg;
@@ -1852,6 +1853,19 @@ static void adhoc_fill(std::vector<int>& idx, int kc, int cbase, int n0, int nco
   }
 }
 
+// the same for the TRANSPOSED layer of a dense forward matrix W [Kdim, Ndim] at flat offset 0: Kdim output columns, reduction over
+// the Ndim forward outputs, `kc` = ceil(Ndim / 16) chunks
+static void adhoc_fill_transposed(std::vector<int>& idx, int kc, int Kdim, int Ndim) {
+  for (int j = 0; j < Kdim; ++j) {       // output column j of the transposed layer = input j of the forward layer
+    const int tile = j / 16, ln = j % 16;
+    for (int kk = 0; kk < Ndim; ++kk) {  // reduction index = forward output kk
+      const int cch = kk / 16, kin = kk % 16;
+      const int lane = (kin / 4) * 16 + ln, comp = kin % 4;
+      idx[(((int64_t)tile * kc + cch) * 64 + lane) * 4 + comp] = j * Ndim + kk;  // W[j][kk]
+    }
+  }
+}
+
 extern "C" int sqair_linear_test(SqairHandle* h, const float* x, const float* wmat, const float* b, float* y, int M,
                                  int Kdim, int Ndim, int act, void* scratch, int64_t scratch_bytes, void* stream) {
   if (!h || !x || !wmat || !y || !scratch) return -1;
@@ -2184,14 +2198,7 @@ extern "C" int sqair_linear_bwd_test(SqairHandle* h, const float* x, const float
     return -1;
   }
   std::vector<int> idx(nel, -1);
-  for (int j = 0; j < Kdim; ++j) {       // output column j of the transposed layer = input k of the forward layer
-    const int tile = j / 16, ln = j % 16;
-    for (int kk = 0; kk < Ndim; ++kk) {  // reduction index = forward output n
-      const int cch = kk / 16, kin = kk % 16;
-      const int lane = (kin / 4) * 16 + ln, comp = kin % 4;
-      idx[(((int64_t)tile * L.kc + cch) * 64 + lane) * 4 + comp] = j * Ndim + kk;  // W[j][kk]
-    }
-  }
+  adhoc_fill_transposed(idx, L.kc, Kdim, Ndim);
   int* d_idx = (int*)scratch;
   float* d_w = (float*)scratch + nel;
   float* d_b = d_w + nel;
@@ -2215,4 +2222,97 @@ extern "C" int sqair_linear_bwd_test(SqairHandle* h, const float* x, const float
   SQ_CHECK_HIP(hipGetLastError());
   SQ_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The dense family's operand contract, one launch (unit-test entry): everything a Lin can say -- segments with pitches, widths and
+// row divisors, a broadcast segment, the addend, the split activation, both scales, a padded output pitch -- goes to
+// sq_launch_linear as the caller gave it.  Only the weights are packed here, the ad-hoc way of sqair_gru_test.
+// ------------------------------------------------------------------------------------------------
+extern "C" int sqair_linear_contract_test(SqairHandle* h, const SqairDenseContract* c, void* stream) {
+  if (!h || !c || !c->w || !c->out || !c->scratch || c->nseg < 1 || c->nseg > 4 || c->M < 1 || c->N < 1 || c->out_ld < c->N) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  PackedLayer L;
+  L.kc = 0; L.nt = (c->N + 15) / 16; L.N = c->N; L.w_off = 0; L.b_off = 0;
+  for (int i = 0; i < c->nseg; ++i) {
+    if (c->seg[i].width < 1) { sq_set_error(h, "sqair_linear_contract_test: a segment without inputs"); return -1; }
+    L.seg_width.push_back(c->seg[i].width);
+    L.kc += (c->seg[i].width + 15) / 16;
+  }
+  const int64_t nel = (int64_t)L.nt * L.kc * 256, nb = L.nt * 16;
+  if (c->scratch_bytes < (2 * nel + 2 * nb + 256) * 4) { sq_set_error(h, "sqair_linear_contract_test: scratch too small"); return -1; }
+  std::vector<int> idx(nel, -1), bidx(nb, -1);
+  for (int i = 0, cbase = 0, k0 = 0; i < c->nseg; ++i) {
+    adhoc_fill(idx, L.kc, cbase, 0, c->N, c->seg[i].width, (int64_t)k0 * c->N, c->N, 0);
+    cbase += (c->seg[i].width + 15) / 16;
+    k0 += c->seg[i].width;
+  }
+  for (int n = 0; n < c->N; ++n) bidx[n] = c->b ? n : -1;
+  int* d_idx = (int*)c->scratch;
+  float* d_w = (float*)c->scratch + nel;
+  float* d_b = d_w + nel;
+  int* d_bidx = (int*)(d_b + nb);
+  float* d_zero = (float*)(d_bidx + nb);
+  SQ_CHECK_HIP(hipMemcpyAsync(d_idx, idx.data(), nel * 4, hipMemcpyHostToDevice, s));
+  SQ_CHECK_HIP(hipMemcpyAsync(d_bidx, bidx.data(), nb * 4, hipMemcpyHostToDevice, s));
+  SQ_CHECK_HIP(hipMemsetAsync(d_zero, 0, 256 * 4, s));
+  SQ_CHECK_HIP(hipStreamSynchronize(s));
+  sq_launch_pack(c->w, d_w, d_idx, nel, s);
+  if (c->b) sq_launch_pack(c->b, d_b, d_bidx, nb, s);
+  else SQ_CHECK_HIP(hipMemsetAsync(d_b, 0, nb * 4, s));
+  Lin l;
+  for (int i = 0; i < c->nseg; ++i) l.seg(c->seg[i].p, c->seg[i].ld, c->seg[i].width, c->seg[i].rdiv);
+  if (c->add) l.add(c->add, c->add_ld, c->add_n, c->add_rdiv);
+  l.out(c->out, c->out_ld).act2(c->act_a, c->act_b, c->act_split);
+  l.a.scale = c->scale; l.a.scale_ptr = c->scale_ptr;
+  l.a.wp = d_w; l.a.wzero = d_zero; l.a.bias = d_b; l.a.M = c->M; l.a.N = c->N;
+  const int rc = sq_launch_linear(l.a, L, s);
+  if (rc != 0) { sq_set_error(h, "sqair_linear_contract_test: A-operand contract violated"); return rc; }
+  SQ_CHECK_HIP(hipGetLastError());
+  SQ_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+// The routed dX GEMM, one launch (unit-test entry): dpre, the ranges and the GRU block reach sq_launch_linear_dx as given; the
+// forward matrix w [Kdim, width] is packed transposed, as sqair_linear_bwd_test packs it.
+extern "C" int sqair_linear_dx_test(SqairHandle* h, const SqairDxTest* t, void* stream) {
+  if (!h || !t || !t->dpre || !t->w || !t->scratch || t->M < 1 || t->width < 1 || t->Kdim < 1) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  const int kc = (t->width + 15) / 16, nt = (t->Kdim + 15) / 16;
+  const int64_t nel = (int64_t)nt * kc * 256;
+  if (t->scratch_bytes < (2 * nel + 256) * 4) { sq_set_error(h, "sqair_linear_dx_test: scratch too small"); return -1; }
+  std::vector<int> idx(nel, -1);
+  adhoc_fill_transposed(idx, kc, t->Kdim, t->width);
+  int* d_idx = (int*)t->scratch;
+  float* d_w = (float*)t->scratch + nel;
+  float* d_zero = d_w + nel;
+  SQ_CHECK_HIP(hipMemcpyAsync(d_idx, idx.data(), nel * 4, hipMemcpyHostToDevice, s));
+  SQ_CHECK_HIP(hipMemsetAsync(d_zero, 0, 256 * 4, s));
+  SQ_CHECK_HIP(hipStreamSynchronize(s));
+  sq_launch_pack(t->w, d_w, d_idx, nel, s);
+  DxArgs a; memset(&a, 0, sizeof(a));
+  a.dpre = t->dpre; a.ld = t->ld; a.width = t->width; a.wp = d_w; a.wzero = d_zero; a.scale_ptr = t->scale_ptr; a.M = t->M;
+  a.nranges = t->nranges;
+  for (int i = 0; i < 3 && i < t->nranges; ++i) {
+    const SqairDxRange& r = t->r[i];
+    a.r[i] = DxRange{r.n0, r.n1, r.dst, r.dst_ld, r.dst2, r.dst2_ld, r.add, r.add_ld, r.saved, r.saved_ld, r.act_a, r.act_b, r.act_split};
+  }
+  const SqairDxGru& g = t->gru;
+  a.gru = DxGru{g.mode, g.g0, g.g0_ld, g.g1, g.g1_ld, g.hprev, g.h_ld, g.dpre1, g.dp_ld, g.d_h, g.dh_ld, g.acc_dh, g.dup, g.dup_ld,
+                g.dup_h_off, g.nh};
+  const int rc = sq_launch_linear_dx(a, kc, nt, s);
+  if (rc == -5) { sq_set_error(h, "sqair_linear_dx_test: operand contract violated (alignment, pitch, range start or range count)"); return rc; }
+  if (rc == -6) { sq_set_error(h, "sqair_linear_dx_test: the GRU epilogue takes one range [0, nh) without a saved output, at most 16 K chunks on the product build"); return rc; }
+  if (rc != 0) { sq_set_error(h, "sqair_linear_dx_test: launch refused"); return rc; }
+  SQ_CHECK_HIP(hipGetLastError());
+  SQ_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+// the routes the two dense launchers took (sqair_common.h: DenseRoute, in the order sqair_hip.h documents)
+extern "C" int sqair_debug_dense_routes(int64_t* out, int n) {
+  static_assert(DR_COUNT == SQAIR_DENSE_ROUTES, "sqair_hip.h documents every route");
+  if (!out || n < 0) return -1;
+  for (int i = 0; i < n && i < DR_COUNT; ++i) out[i] = (int64_t)sq_dense_route_hits(i);
+  return DR_COUNT;
 }

@@ -130,6 +130,16 @@ __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
+// Which kernel family a dense launcher chose, counted on the host per process at the point of the choice (launches issued or
+// captured so far; sqair_debug_dense_routes: lets a test see the route a launch took).  The order is the C-ABI's (sqair_hip.h).
+enum DenseRoute {
+  DR_SPLITK = 0, DR_T2, DR_ROWS, DR_MT, DR_LDS, DR_BIG22, DR_BIG32, DR_BIG33, DR_BIG42,
+  DR_DX_NCH1, DR_DX_NCH2, DR_DX_NCH3, DR_DX_NCH4, DR_DX_NCH5, DR_DX_NCH6, DR_DX_NCH7, DR_DX_NCH8, DR_DX_NCH9, DR_DX_NCH12, DR_DX_NCH18,
+  DR_DX_T2, DR_DX_GRU1, DR_DX_GRU2, DR_COUNT
+};
+void sq_dense_route_hit(int route);
+long long sq_dense_route_hits(int route);
+
 // launchers (sqair_linear.hip)
 int sq_launch_linear(const LinArgs& a, const PackedLayer& L, hipStream_t s);
 int sq_launch_pack(const float* flat, float* packed_w, const int* idx, int64_t n, hipStream_t s);

@@ -22,6 +22,7 @@
 #include <type_traits>
 #include "sqair_common.h"
 #include "sqair_lin_device.h"
+#include <atomic>
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -919,6 +920,10 @@ static void launch_nch(const LinArgs& a, const PackedLayer& L, hipStream_t s) {
   }
 }
 
+static std::atomic<long long> g_dense_route[DR_COUNT];
+void sq_dense_route_hit(int route) { ++g_dense_route[route]; }
+long long sq_dense_route_hits(int route) { return route >= 0 && route < DR_COUNT ? g_dense_route[route].load() : -1; }
+
 static unsigned rmul_of(int rdiv) { return rdiv <= 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)rdiv) + 1u; }
 
 int sq_launch_linear(const LinArgs& a_in, const PackedLayer& L, hipStream_t s) {
@@ -956,6 +961,7 @@ int sq_launch_linear(const LinArgs& a_in, const PackedLayer& L, hipStream_t s) {
     // (all of them accumulate in the same order: the tile shape never changes a result)
     if (L.kc <= 4) {  // K <= 64: one block of loads, nothing to pipeline
       const dim3 grid_r(L.nt, (mt + 3) / 4);
+      sq_dense_route_hit(DR_ROWS);
       SQ_LAUNCH(k_linear_rows<4>, grid_r, dim3(256), 0, s, a, L.kc, L.nt);
       return 0;
     }
@@ -968,7 +974,7 @@ int sq_launch_linear(const LinArgs& a_in, const PackedLayer& L, hipStream_t s) {
     static const int big = SQ_KNOB_INT("SQAIR_BIG", 2);  // measurement knob: 0 = off
     if (big > 0 && L.nt >= 4) {
 #ifdef SQAIR_KNOBS
-      if (const char* e = SQ_KNOB_STR("SQAIR_BIG_SHAPE")) {   // "TMW,TNW": forced tile (measurement)
+      if (const char* e = SQ_KNOB_STR("SQAIR_BIG_SHAPE")) {   // "TMW,TNW": forced tile (measurement; not among the counted routes)
         const int tm = e[0] - '0', tn = e[2] - '0';
 #define SQ_BIG_CASE(A, B) if (tm == A && tn == B) { launch_big<A, B>(a, L, s); return 0; }
         SQ_BIG_CASE(1, 2) SQ_BIG_CASE(1, 3) SQ_BIG_CASE(1, 4)
@@ -978,19 +984,21 @@ int sq_launch_linear(const LinArgs& a_in, const PackedLayer& L, hipStream_t s) {
       }
 #endif
       switch (pick_big_shape(a.M, L.nt, L.kc, a.act_a != ACT_NONE)) {
-        case 22: launch_big<2, 2>(a, L, s); break;
-        case 32: launch_big<3, 2>(a, L, s); break;
-        case 33: launch_big<3, 3>(a, L, s); break;
-        default: launch_big<4, 2>(a, L, s); break;
+        case 22: sq_dense_route_hit(DR_BIG22); launch_big<2, 2>(a, L, s); break;
+        case 32: sq_dense_route_hit(DR_BIG32); launch_big<3, 2>(a, L, s); break;
+        case 33: sq_dense_route_hit(DR_BIG33); launch_big<3, 3>(a, L, s); break;
+        default: sq_dense_route_hit(DR_BIG42); launch_big<4, 2>(a, L, s); break;
       }
       return 0;
     }
     static const int lds_wgs = SQ_KNOB_INT("SQAIR_LDS_WGS", 512);  // measurement knob
     if (((a.M + 127) / 128) * ((L.nt + 3) / 4) >= lds_wgs) {
+      sq_dense_route_hit(DR_LDS);
       SQ_LAUNCH((k_linear_lds<2>), dim3((L.nt + 3) / 4, (a.M + 127) / 128), dim3(256), 0, s, a, L.kc, L.nt);
       return 0;
     }
     const MtShape sh = pick_mt_shape(a.M, L.nt, L.kc);
+    sq_dense_route_hit(DR_MT);
     if (sh.nt >= 2) launch_mt<4, 1, 2>(a, L, mt, sh.coal != 0, s);
     else launch_mt<4, 1, 1>(a, L, mt, sh.coal != 0, s);
     return 0;
@@ -1002,9 +1010,11 @@ int sq_launch_linear(const LinArgs& a_in, const PackedLayer& L, hipStream_t s) {
   // 16 x 16 tile is as fast or faster (640 x 362 x 1152 13.6 / 13.2, 640 x 312 x 768 8.6 / 9.5) and keeps those layers
   static const int t2_rows = SQ_KNOB_INT("SQAIR_T2_ROWS", 512), t2_kc = SQ_KNOB_INT("SQAIR_T2_KC", 40);  // measurement knobs
   if (a.M >= t2_rows && L.nt >= 4 && L.kc >= t2_kc) {
+    sq_dense_route_hit(DR_T2);
     launch_t2_any(a, L, s);
     return 0;
   }
+  sq_dense_route_hit(DR_SPLITK);
   switch (per_wave) {
     case 1: launch_nch<1>(a, L, s); break;
     case 2: launch_nch<2>(a, L, s); break;

@@ -161,12 +161,14 @@ int sq_launch_linear_dx(const DxArgs& a, int kc, int nt, hipStream_t s) {
   if (a.gru.mode != 0) {  // GRU gate adjoints in the epilogue: one range [0, nh), K = nh or the what-head width (<= 16 chunks)
     if (a.nranges != 1 || a.r[0].n0 != 0 || a.r[0].n1 != a.gru.nh || a.r[0].saved != nullptr) return -6;
 #define SQ_DXG(NCH, G) SQ_LAUNCH((k_linear_dx<NCH, G>), g, dim3(256), 0, s, a.dpre, a.wp, a.ld, a.width, a.M, kc, a.wzero, a)
+#ifndef SQAIR_WIDE
+    if (per_wave > 4) return -6;
+#endif
+    sq_dense_route_hit(a.gru.mode == 1 ? DR_DX_GRU1 : DR_DX_GRU2);
 #ifdef SQAIR_WIDE
     // (the wide build: K up to 5 x 128 head columns / 512 hidden units -- deeper instantiations of the same kernel)
     if (per_wave > 8) { if (a.gru.mode == 1) SQ_DXG(18, 1); else SQ_DXG(18, 2); return 0; }
     if (per_wave > 4) { if (a.gru.mode == 1) SQ_DXG(8, 1); else SQ_DXG(8, 2); return 0; }
-#else
-    if (per_wave > 4) return -6;
 #endif
     if (a.gru.mode == 1) SQ_DXG(4, 1); else SQ_DXG(4, 2);
 #undef SQ_DXG
@@ -176,11 +178,13 @@ int sq_launch_linear_dx(const DxArgs& a, int kc, int nt, hipStream_t s) {
   static const int t2_rows = SQ_KNOB_INT("SQAIR_T2_ROWS", 512), t2_kc = SQ_KNOB_INT("SQAIR_T2_KC", 40);  // measurement knobs
   if (a.M >= t2_rows && nt >= 4 && kc >= t2_kc) {
     const dim3 g2((nt + 1) / 2, (a.M + 31) / 32);
+    sq_dense_route_hit(DR_DX_T2);
 #define SQ_DXT2(NB, NW) SQ_LAUNCH((k_linear_dx_t2<NB, NW>), g2, dim3(64 * NW), 0, s, a, kc, nt)
     if (per_wave <= 2) SQ_DXT2(2, 4); else if (per_wave <= 3 || per_wave == 5 || per_wave == 6) SQ_DXT2(3, 4); else SQ_DXT2(4, 4);
 #undef SQ_DXT2
     return 0;
   }
+  sq_dense_route_hit(per_wave <= 9 ? DR_DX_NCH1 + per_wave - 1 : (per_wave <= 12 ? DR_DX_NCH12 : DR_DX_NCH18));
   switch (per_wave) {
     case 1: SQ_LAUNCH(k_linear_dx<1>, g, dim3(256), 0, s, a.dpre, a.wp, a.ld, a.width, a.M, kc, a.wzero, a); break;
     case 2: SQ_LAUNCH(k_linear_dx<2>, g, dim3(256), 0, s, a.dpre, a.wp, a.ld, a.width, a.M, kc, a.wzero, a); break;

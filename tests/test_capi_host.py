@@ -254,3 +254,30 @@ def test_backward_decoder_refusals_host_side():
                                               None, None) == -1 and b"too small" in lib.sqair_last_error(h)
         finally:
             lib.sqair_destroy(h)
+
+
+def test_dense_test_structs_have_the_header_layout(repo_root, tmp_path):
+    """The descriptions of sqair_linear_contract_test / sqair_linear_dx_test are passed by address: the ctypes mirrors must have
+    the size and the field offsets a C compiler gives the header's structs."""
+    import shutil
+    import subprocess
+    structs = {"SqairDenseSeg": _capi.SqairDenseSeg, "SqairDenseContract": _capi.SqairDenseContract, "SqairDxRange": _capi.SqairDxRange,
+               "SqairDxGru": _capi.SqairDxGru, "SqairDxTest": _capi.SqairDxTest}
+    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "sqair_hip.h"', "int main(void) {"]
+    for name, cls in structs.items():
+        lines.append('  printf("{0} %zu\\n", sizeof({0}));'.format(name))
+        for field, _ in cls._fields_:
+            lines.append('  printf("{0}.{1} %zu\\n", offsetof({0}, {1}));'.format(name, field))
+    lines += ["  return 0;", "}"]
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines))
+    gcc = shutil.which("gcc")
+    assert gcc, "gcc is part of the image"
+    subprocess.check_call([gcc, "-std=c99", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(repo_root, "include"),
+                           str(src), "-o", str(tmp_path / "layout")])
+    got = dict(l.split() for l in subprocess.run([str(tmp_path / "layout")], capture_output=True, text=True, check=True).stdout.splitlines())
+    for name, cls in structs.items():
+        assert int(got[name]) == C.sizeof(cls), name
+        for field, _ in cls._fields_:
+            assert int(got[name + "." + field]) == getattr(cls, field).offset, (name, field)
+    assert len(_capi.DENSE_ROUTES) == int(re.search(r"#define SQAIR_DENSE_ROUTES (\d+)", open(os.path.join(repo_root, "include", "sqair_hip.h")).read()).group(1))
