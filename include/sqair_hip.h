@@ -644,6 +644,75 @@ int sqair_set_layers(SqairHandle* h, const SqairLaneLayers* lay /* NULL: off */,
 int sqair_lane_layers_test(SqairHandle* h, const float* glimpse, const float* where, const float* presence, const float* lw,
                            const float* log_w, float iou_min, int T, int B, int K, const SqairLaneLayers* lay, void* stream);
 
+/* ---- stream scoring: CLEAR-MOT events of the lane answer against ground-truth boxes, inside the pass ---------------------------
+ * The estimate, the layers, the lane tracks and the lane forecasts say what the filter believes; the score says whether the lane
+ * answer follows the objects of the scene and whether obj_id stays on them.  The lane's obj_id is the best row's, and ids agree
+ * between rows only back to their common ancestor: a switch of the best row can switch the identity the caller sees -- an identity
+ * switch below.  With a score set, every following inference pass with a carried state and an estimate runs one more kernel,
+ * k_lane_score, one workgroup per lane looping over the pass's frames in order: after k_lane_estimate (and after k_lane_layers if
+ * on) and BEFORE the SMC resampler.  A pass with the score on has exactly one kernel node more; with the score off nothing is
+ * launched and every other output, blob and accumulator is unchanged bit for bit.  Training passes never run it.  The kernel reads
+ * the estimate's own output buffers box, presence, obj_id and map_count -- they must be bound -- and does not read the records again.
+ * Inputs per pass, on the device, read by the kernel so that one captured graph serves every pattern: truth_box [T,B,G,4] fp32
+ * (y, x, h, w) in pixels, the convention of the estimate's box; truth_present [T,B,G] int32 -- truth identity IS the slot g: an
+ * object keeps its slot for its life; truth_valid [T,B] int32, 0 = this (frame, lane) has no truth: it is not scored and leaves the
+ * memory and the accumulators untouched.  G in 1..16 is chosen when the score is set.
+ * For lane b and the frames t of the pass in order with truth_valid[t,b] != 0:
+ * 0. Non-finite lanes.  The estimate's non-finite lane (map_count == -1) counts one frames_invalid and nothing else changes.  For
+ *    such a frame, and for a frame without truth, the per-frame outputs are -1 (truth_match, tp, fn, fp, idsw) and 0 (match_iou).
+ * 1. Candidates: present truth g (truth_present != 0) x present lane object j (presence != 0).  Holes are allowed on both sides:
+ *    nothing is assumed present-first.  IoU(g, j) is the estimate's (point 5 above: the same device function, sq_box_iou, on the
+ *    fp32 words).
+ * 2. Keep.  last_id[b,g] is the identity memory: the obj_id WORD (the 32 bits of the float, read as int32) of the lane object truth
+ *    g was last matched with, -1 = none yet; a negative word (a negative id: the model makes none) is stored as it is and then
+ *    reads as no memory.  For g in index order with last_id[b,g] >= 0: the first unclaimed present j whose obj_id word equals
+ *    last_id[b,g] and whose IoU(g, j) >= iou_min is matched with g and claimed.
+ * 3. Rest: greedy one-to-one.  Repeat: among unmatched present g and unclaimed present j with IoU >= iou_min take the pair of
+ *    maximal IoU, ties to the smallest g, then the smallest j; stop when no such pair is left.  A NaN never wins.
+ * 4. Events.  tp[t,b] = matched pairs, fn[t,b] = present truths unmatched, fp[t,b] = present lane objects unclaimed.  For each
+ *    matched g in index order with id = the obj_id word of its j: idsw[t,b] += [last_id[b,g] >= 0 and last_id[b,g] != id], then
+ *    last_id[b,g] = id; unmatched g keep their memory.  match_iou[t,b,g] = the pair's IoU (0 unmatched), truth_match[t,b,g] = j
+ *    (-1 unmatched or absent).  With n_truth = the number of present truths: count_hit += [map_count == n_truth], count_abs_err
+ *    += |map_count - n_truth|.
+ * 5. Accumulators persist across passes and are updated in place -- read, added to, written by one thread -- so a replayed graph
+ *    accumulates as eager calls do.  counts [B,9] int64: frames (scored), frames_invalid, truth, tp, fn, fp, idsw, count_hit,
+ *    count_abs_err.  iou_sum [B] fp64 += match_iou[t,b,g] converted to fp64, g in index order, frames in order, from one thread:
+ *    no float atomics, the same bits eager and graph.  The caller zeroes counts and iou_sum and sets last_id to -1 to start.
+ * 6. Coasted (frame, lane)s (sqair_set_observed) need no case of their own: they are scored when their truth is valid.
+ * Pointers are remembered by the handle and frozen into captured graphs.  NULL score: off.  Refused (return -1, text in
+ * sqair_last_error, before any HIP call): no estimate set (sqair_set_estimate); an estimate without box, presence, obj_id or
+ * map_count; a T other than the estimate's, a B other than the state's; G outside 1..16; iou_min NaN or outside (0, 1]; a NULL
+ * truth_box, truth_present, truth_valid, counts, iou_sum or last_id (the per-frame outputs are optional); at pass time: a pass
+ * of another T.  sqair_set_estimate switching the estimate off, to another T or to one without the four fields, and
+ * sqair_set_state switching the state off or to another B, switch the score off.
+ * Out of scope: optimal (Hungarian) assignment -- step 3 is greedy; IDF1 and mostly-tracked / mostly-lost statistics; scoring per
+ * particle row; scoring of forecasts or lane tracks; training passes. */
+#define SQAIR_SCORE_MAX_TRUTH 16
+#define SQAIR_SCORE_COUNTS 9
+typedef struct SqairLaneScore {
+  float iou_min;                  /* in (0, 1] */
+  int32_t G;                      /* truth slots per lane, 1..16 */
+  const float* truth_box;         /* [T,B,G,4] in */
+  const int32_t* truth_present;   /* [T,B,G] in */
+  const int32_t* truth_valid;     /* [T,B] in */
+  int64_t* counts;                /* [B,9] in/out */
+  double* iou_sum;                /* [B] in/out */
+  int32_t* last_id;               /* [B,G] in/out */
+  int32_t* truth_match;           /* [T,B,G] */
+  float* match_iou;               /* [T,B,G] */
+  int32_t* tp;                    /* [T,B] */
+  int32_t* fn;                    /* [T,B] */
+  int32_t* fp;                    /* [T,B] */
+  int32_t* idsw;                  /* [T,B] */
+} SqairLaneScore;
+int sqair_set_score(SqairHandle* h, const SqairLaneScore* score /* NULL: off */, int T, int B);
+/* Kernel-level check of the score (tests): the kernel above on caller buffers, no state and no pass, with the handle's N and any G
+ * in 1..16.  box [T,B,N,4], presence, obj_id [T,B,N] and map_count [T,B] stand for the estimate's outputs.  Refused (return -1,
+ * before any HIP call): a NULL box / presence / obj_id / map_count / score, T or B out of range, what sqair_set_score refuses for
+ * score. */
+int sqair_lane_score_test(SqairHandle* h, const float* box, const float* presence, const float* obj_id, const int32_t* map_count,
+                          int T, int B, const SqairLaneScore* score, void* stream);
+
 /* ---- objective ---------------------------------------------------------------------------------
  * Fused IWAE / VIMCO reductions over [T,B,K] (reference: Model._build sqair/model.py:88-103,
  * targets.iwae / vimco_control_variate / vimco sqair/targets.py:38-75, make_target model.py:150-158,

@@ -124,6 +124,26 @@ class SqairLaneLayers(C.Structure):
     _fields_ = [("cover_min", C.c_float)] + [(n, C.c_void_p) for n in LAYERS_FIELDS]
 
 
+# stream scoring (include/sqair_hip.h: sqair_set_score): the per-frame outputs of SqairLaneScore in declaration order and the int32
+# ones among them; the inputs and accumulators before them; the columns of ``counts``
+SCORE_FIELDS = ("truth_match", "match_iou", "tp", "fn", "fp", "idsw")
+SCORE_INT_FIELDS = ("truth_match", "tp", "fn", "fp", "idsw")
+SCORE_INPUTS = ("truth_box", "truth_present", "truth_valid", "counts", "iou_sum", "last_id")
+SCORE_COUNTS = ("frames", "frames_invalid", "truth", "tp", "fn", "fp", "idsw", "count_hit", "count_abs_err")
+SCORE_MAX_TRUTH = 16
+
+
+def score_shapes(T, B, G):
+    """The per-frame outputs' shapes for passes of T frames and G truth slots per lane."""
+    return dict(truth_match=(T, B, G), match_iou=(T, B, G), tp=(T, B), fn=(T, B), fp=(T, B), idsw=(T, B))
+
+
+class SqairLaneScore(C.Structure):
+    """CLEAR-MOT scoring of the lane answer against ground-truth boxes (include/sqair_hip.h: sqair_set_score); every pointer is a
+    device address, the per-frame outputs (SCORE_FIELDS) optional."""
+    _fields_ = [("iou_min", C.c_float), ("G", C.c_int32)] + [(n, C.c_void_p) for n in SCORE_INPUTS + SCORE_FIELDS]
+
+
 # track history (include/sqair_hip.h: sqair_set_history): the bit of each field a ring slot may hold; the first three are mandatory
 HISTORY_FIELDS = {"where": 1, "presence": 2, "obj_id": 4, "what": 8, "log_weights_per_timestep": 16}
 HISTORY_MANDATORY = ("where", "presence", "obj_id")
@@ -289,6 +309,8 @@ _PROTOS = {
     "sqair_lane_estimate_test": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int, C.POINTER(SqairLaneEstimate), C.c_void_p]),
     "sqair_set_layers": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneLayers), C.c_int, C.c_int]),
     "sqair_lane_layers_test": (C.c_int, [C.c_void_p] * 6 + [C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(SqairLaneLayers), C.c_void_p]),
+    "sqair_set_score": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneScore), C.c_int, C.c_int]),
+    "sqair_lane_score_test": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.POINTER(SqairLaneScore), C.c_void_p]),
     "sqair_forecast_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
     "sqair_forecast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                  C.POINTER(SqairForecastOutputs), C.c_void_p, C.c_int64, C.c_void_p]),

@@ -1411,6 +1411,8 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
     sq_set_error(h, "sqair_forward: the object layers launch failed (dynamic LDS limit)");
     return -2;
   }
+  // stream scoring: the lane answer the estimate just wrote against the caller's ground truth (sqair_set_score), accumulated in place
+  if (st.score_on) sq_launch_lane_score(sq_score_args(h, T, B), s);
   // SMC: this pass's log weights -> ESS, evidence and the next pass's source map (sqair_set_smc / SqairCarry.smc)
   if (st.smc_on) sq_launch_smc_resample(sq_smc_args(st.smc, out.log_weights_per_timestep, w.t_row, T, B, K), s);
   SQ_CHECK_HIP(hipGetLastError());

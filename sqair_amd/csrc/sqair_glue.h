@@ -425,6 +425,18 @@ struct LaneLayerArgs {
   int T, B, K, N, G, H, W;
 };
 int sq_launch_lane_layers(const LaneLayerArgs& a, hipStream_t s);   // -2: the kernel's LDS (two glimpses) does not fit
+// Stream scoring (sqair_set_score; include/sqair_hip.h states the semantics): k_lane_score, one workgroup per lane b looping over the
+// pass's frames in order.  box / presence / obj_id [T][B][N] and map_count [T][B] are the estimate's outputs (or a test's buffers).
+constexpr int SQ_SCORE_MAXG = 16;
+struct LaneScoreArgs {
+  const float* box;                    // [T][B][N][4]
+  const float* presence;               // [T][B][N]
+  const float* obj_id;                 // [T][B][N]
+  const int32_t* map_count;            // [T][B]
+  SqairLaneScore sc;                   // iou_min, G, the truth, the accumulators and the per-frame outputs
+  int T, B, N;
+};
+int sq_launch_lane_score(const LaneScoreArgs& a, hipStream_t s);
 
 // Object forecasts (sqair_forecast_fan; include/sqair_hip.h states the semantics).  Fan-out: rollout row q = r * S + s.
 // k_forecast_fan_src expands the source map, src_fan[q] = src[q / S] (NULL: q / S), an index outside [0, R) of the blob -> -1.

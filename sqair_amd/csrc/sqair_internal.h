@@ -101,6 +101,9 @@ struct SqairHandle {
   // object layers (sqair_set_layers): one k_lane_layers launch directly after the estimate's; needs the estimate, T = est_T
   bool lay_on = false;
   SqairLaneLayers lay = {};
+  // stream scoring (sqair_set_score): one k_lane_score launch after the estimate's and the layers'; needs the estimate, T = est_T
+  bool score_on = false;
+  SqairLaneScore score = {};
   // generic capture slots (sqair_capture_begin / _end / _launch): any sequence of C-ABI calls as one HIP graph
   hipGraph_t cap_graph[4] = {nullptr, nullptr, nullptr, nullptr};
   hipGraphExec_t cap_exec[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -238,6 +241,7 @@ struct SqStateRes {
   const int32_t* observed = nullptr;   // (the same: the handle's device mask of sqair_set_observed, or NULL)
   bool est_on = false;    // (the same: a carried training call never estimates)
   bool lay_on = false;    // (the same; only ever with est_on)
+  bool score_on = false;  // (the same; only ever with est_on)
 };
 SQ_LOCAL SqStateRes sq_handle_state(const SqairHandle* h);
 SQ_LOCAL SqStateRes sq_carry_state(const SqairCarry* c);
@@ -258,6 +262,8 @@ SQ_LOCAL LaneEstArgs sq_estimate_args(const SqairHandle* h, const float* rec, co
 // object layers: the kernel's arguments for a pass of T frames over the merged records `rec` and the decoded glimpses `glimpse`
 // [T][R][N][G*G] (a pass of another T is the estimate's to refuse: the layers are only ever registered for the estimate's T)
 SQ_LOCAL LaneLayerArgs sq_layers_args(const SqairHandle* h, const float* rec, const float* glimpse, const SqairOutputs& out, int T, int B);
+// stream scoring: the kernel's arguments for a pass of T frames -- the estimate's own output buffers and the registered score
+SQ_LOCAL LaneScoreArgs sq_score_args(const SqairHandle* h, int T, int B);
 // section A of a frame of the pass, and a frame of the forecast: the propagation-prior cell and its statistics (sqair_api.hip)
 SQ_LOCAL int sq_prior_step(SqairHandle* h, const float* packed, hipStream_t s, int M, const float* rec_prev, const float* prior_prev,
                            float* prior_p, float* pgz, float* pgrh, float* pgxh, float* pstats, float* o3, float* o1);

@@ -173,3 +173,42 @@ __device__ __forceinline__ void sq_lane_box_sum(const float* s_w, const SqBox* s
     }
   }
 }
+
+// Keep + greedy one-to-one assignment of rows g < G to columns j < N over an IoU table in LDS, iou[g * ld + j] -- ONE thread's walk,
+// every array in LDS, nothing indexed in registers.  A pair is eligible when its entry >= iou_min: the caller stores a value below
+// every threshold (-1) for a pair that is no candidate, and a NaN never passes.
+//   keep   (keep_id != NULL) for g in index order with keep_id[g] >= 0: the first unclaimed j with col_id[j] == keep_id[g] and an
+//          eligible entry is matched with g;
+//   rest   repeat: the eligible pair of maximal entry among unmatched g and unclaimed j, ties to the smallest g, then the smallest
+//          j (a row-major scan with a strict compare); stop when none is left.
+// Leaves row_match[g] = j or -1 and col_claim[j] = 1 or 0; returns the number of pairs.  Greedy, not optimal (Hungarian) assignment.
+__device__ __forceinline__ int sq_assign_keep_greedy(const float* iou, const int ld, const int G, const int N, const float iou_min,
+                                                     const int* keep_id, const int* col_id, int* row_match, int* col_claim) {
+  int n = 0;
+  for (int g = 0; g < G; ++g) row_match[g] = -1;
+  for (int j = 0; j < N; ++j) col_claim[j] = 0;
+  if (keep_id)
+    for (int g = 0; g < G; ++g) {
+      const int id = keep_id[g];
+      if (id < 0) continue;
+      for (int j = 0; j < N; ++j)
+        if (!col_claim[j] && col_id[j] == id && iou[g * ld + j] >= iou_min) {
+          row_match[g] = j; col_claim[j] = 1; ++n;
+          break;
+        }
+    }
+  for (;;) {
+    float top = -1.0f;
+    int tg = -1, tj = -1;
+    for (int g = 0; g < G; ++g) {
+      if (row_match[g] >= 0) continue;
+      for (int j = 0; j < N; ++j) {
+        const float v = iou[g * ld + j];
+        if (!col_claim[j] && v >= iou_min && v > top) { top = v; tg = g; tj = j; }
+      }
+    }
+    if (tg < 0) break;
+    row_match[tg] = tj; col_claim[tj] = 1; ++n;
+  }
+  return n;
+}

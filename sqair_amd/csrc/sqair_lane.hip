@@ -1,5 +1,5 @@
 // The per-lane answers: the kernels that turn a lane's K particle rows into one answer per lane -- the SMC resampler, the forecast
-// summaries, the lane estimate, the object layers, the lane forecast and the lane tracks.  None of them is a hop of the frame loop (once per pass or
+// summaries, the lane estimate, the object layers, the stream score, the lane forecast and the lane tracks.  None of them is a hop of the frame loop (once per pass or
 // per call, on B workgroups), and they are a translation unit -- a code object -- of their own so that work on them moves no kernel of the pass
 // (DESIGN.md section 3h).  Their compositions are the device functions of sqair_lane.h.  Every lane-wide sum is one thread's loop in
 // index order: the same bits on every replay, and K <= 256 adds are nothing next to the pass.
@@ -566,5 +566,103 @@ int sq_launch_lane_layers(const LaneLayerArgs& a, hipStream_t s) {
   const int nz = (a.lay.layer || a.lay.cover || a.lay.owner) ? (P + SQ_LAYER_TILE - 1) / SQ_LAYER_TILE : 1;
   if (lds > 32 * 1024 && sq_allow_big_lds((const void*)k_lane_layers, 150 * 1024) != 0) return -2;
   SQ_LAUNCH(k_lane_layers, dim3(a.B, a.T, nz), dim3(256), lds, s, a);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Stream scoring (sqair_set_score; LaneScoreArgs in sqair_glue.h; the semantics: include/sqair_hip.h, points 0-6)
+// ------------------------------------------------------------------------------------------------
+// k_lane_score: workgroup = lane b, looping over the pass's frames in order -- the identity memory makes frame t depend on frame
+// t - 1.  Per frame thread i < G * N fills entry (g, j) = (i / N, i % N) of the IoU table in LDS (-1 for a pair that is no
+// candidate), thread 0 walks the tables (sq_assign_keep_greedy) and counts the events, threads g < G write the per-frame outputs.
+// The memory stays in LDS over the frames; thread 0 keeps the counters in registers and adds them to the accumulators once, in
+// place.  Every branch around a barrier depends on truth_valid[t, b] and map_count[t, b] alone: uniform over the workgroup.
+__global__ __launch_bounds__(256) void k_lane_score(const LaneScoreArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ float s_iou[SQ_SCORE_MAXG * SQ_MAXN];
+  __shared__ int s_last[SQ_SCORE_MAXG], s_tpres[SQ_SCORE_MAXG], s_gm[SQ_SCORE_MAXG];
+  __shared__ int s_id[SQ_MAXN], s_lpres[SQ_MAXN], s_claim[SQ_MAXN];
+  const SqairLaneScore& o = a.sc;
+  const int b = blockIdx.x, tid = threadIdx.x, G = o.G, N = a.N;
+  if (tid < G) s_last[tid] = o.last_id[(size_t)b * G + tid];
+  long long c_frames = 0, c_invalid = 0, c_truth = 0, c_tp = 0, c_fn = 0, c_fp = 0, c_idsw = 0, c_hit = 0, c_err = 0;
+  double iou_sum = tid == 0 ? o.iou_sum[b] : 0.0;
+  for (int t = 0; t < a.T; ++t) {
+    const size_t tb = (size_t)t * a.B + b;
+    const bool valid = o.truth_valid[tb] != 0;
+    const int mc = a.map_count[tb];
+    __syncthreads();   // (the memory is loaded; the last frame's readers are done with the tables)
+    if (!valid || mc == -1) {   // no truth, or a non-finite lane: nothing is scored
+      if (tid == 0) {
+        if (valid) ++c_invalid;
+        if (o.tp) o.tp[tb] = -1;
+        if (o.fn) o.fn[tb] = -1;
+        if (o.fp) o.fp[tb] = -1;
+        if (o.idsw) o.idsw[tb] = -1;
+      }
+      if (tid < G) {
+        if (o.truth_match) o.truth_match[tb * G + tid] = -1;
+        if (o.match_iou) o.match_iou[tb * G + tid] = 0.0f;
+      }
+      continue;
+    }
+    // ---- 1: the candidates' IoU
+    if (tid < G * N) {
+      const int g = tid / N, j = tid - g * N;
+      float v = -1.0f;
+      if (o.truth_present[tb * G + g] != 0 && a.presence[tb * N + j] != 0.0f) {
+        const float* p = o.truth_box + (tb * G + g) * 4;
+        const float* q = a.box + (tb * N + j) * 4;
+        v = sq_box_iou(SqBox{p[0], p[1], p[2], p[3]}, SqBox{q[0], q[1], q[2], q[3]});
+      }
+      s_iou[tid] = v;
+    }
+    if (tid < G) s_tpres[tid] = o.truth_present[tb * G + tid] != 0;
+    if (tid < N) {
+      s_lpres[tid] = a.presence[tb * N + tid] != 0.0f;
+      s_id[tid] = (int)sq_word(a.obj_id + tb * N + tid);
+    }
+    __syncthreads();
+    // ---- 2, 3, 4: the assignment and the events, one thread
+    if (tid == 0) {
+      sq_assign_keep_greedy(s_iou, N, G, N, o.iou_min, s_last, s_id, s_gm, s_claim);
+      int n_truth = 0, tp = 0, fn = 0, fp = 0, sw = 0;
+      for (int g = 0; g < G; ++g) {
+        if (!s_tpres[g]) continue;
+        ++n_truth;
+        const int j = s_gm[g];
+        if (j < 0) { ++fn; continue; }
+        ++tp;
+        const int id = s_id[j], last = s_last[g];
+        sw += last >= 0 && last != id;
+        s_last[g] = id;
+        iou_sum += (double)s_iou[g * N + j];
+      }
+      for (int j = 0; j < N; ++j) fp += s_lpres[j] && !s_claim[j];
+      ++c_frames; c_truth += n_truth; c_tp += tp; c_fn += fn; c_fp += fp; c_idsw += sw;
+      c_hit += mc == n_truth; c_err += mc > n_truth ? mc - n_truth : n_truth - mc;
+      if (o.tp) o.tp[tb] = tp;
+      if (o.fn) o.fn[tb] = fn;
+      if (o.fp) o.fp[tb] = fp;
+      if (o.idsw) o.idsw[tb] = sw;
+    }
+    __syncthreads();
+    if (tid < G) {
+      const int j = s_gm[tid];
+      if (o.truth_match) o.truth_match[tb * G + tid] = j;
+      if (o.match_iou) o.match_iou[tb * G + tid] = j >= 0 ? s_iou[tid * N + j] : 0.0f;
+    }
+  }
+  __syncthreads();
+  if (tid < G) o.last_id[(size_t)b * G + tid] = s_last[tid];
+  if (tid == 0) {
+    int64_t* c = o.counts + (size_t)b * SQAIR_SCORE_COUNTS;
+    c[0] += c_frames; c[1] += c_invalid; c[2] += c_truth; c[3] += c_tp; c[4] += c_fn; c[5] += c_fp; c[6] += c_idsw; c[7] += c_hit;
+    c[8] += c_err;
+    o.iou_sum[b] = iou_sum;
+  }
+}
+int sq_launch_lane_score(const LaneScoreArgs& a, hipStream_t s) {
+  SQ_LAUNCH(k_lane_score, dim3(a.B), dim3(256), 0, s, a);
   return 0;
 }

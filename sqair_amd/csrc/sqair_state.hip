@@ -17,9 +17,11 @@ int64_t sq_state_row_floats(const SqairHandle* h) {
 }
 static void sq_observed_off(SqairHandle* h) { h->observed = nullptr; h->observed_T = 0; }
 static void sq_layers_off(SqairHandle* h) { h->lay_on = false; h->lay = SqairLaneLayers{}; }
+static void sq_score_off(SqairHandle* h) { h->score_on = false; h->score = SqairLaneScore{}; }
 static void sq_estimate_off(SqairHandle* h) {
   h->est_on = false; h->est = SqairLaneEstimate{}; h->est_T = 0;
   sq_layers_off(h);                           // (the layers share the estimate's weights and association: off with it)
+  sq_score_off(h);                            // (the score reads the estimate's outputs: off with it)
 }
 static void sq_history_off(SqairHandle* h) {
   h->hist_on = false; h->hist_ring = nullptr; h->hist_bytes = 0; h->hist_L = 0; h->hist_T = 0; h->hist_fields = 0;
@@ -146,6 +148,7 @@ static int sq_estimate_smc_mismatch(SqairHandle* h, const std::string& who, cons
   if (!h->smc_on || e.log_w == h->smc.log_w) return 0;
   return sq_no(h, who + "with SMC on (sqair_set_smc) log_w must be smc->log_w, the carried log weights of the pass's rows");
 }
+static bool sq_estimate_scorable(const SqairLaneEstimate& e) { return e.box && e.presence && e.obj_id && e.map_count; }
 extern "C" int sqair_set_estimate(SqairHandle* h, const SqairLaneEstimate* est, int T, int B) {
   if (!h) return -1;
   if (!est) {
@@ -159,6 +162,7 @@ extern "C" int sqair_set_estimate(SqairHandle* h, const SqairLaneEstimate* est, 
     return sq_no(h, who + "B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
   if (sq_estimate_fields(h, who, *est) != 0 || sq_estimate_smc_mismatch(h, who, *est) != 0) return -1;
   if (T != h->est_T) sq_layers_off(h);   // (the layers' outputs were sized for the other T)
+  if (T != h->est_T || !sq_estimate_scorable(*est)) sq_score_off(h);   // (and the score's; it reads these four outputs)
   h->est_on = true; h->est = *est; h->est_T = T;
   return 0;
 }
@@ -259,6 +263,58 @@ extern "C" int sqair_lane_layers_test(SqairHandle* h, const float* glimpse, cons
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }
+// ------------------------------------------------------------------------------------------------
+// stream scoring (include/sqair_hip.h: sqair_set_score): registration, the arguments of k_lane_score (launched by sq_forward_impl
+// after the estimate's and the layers' kernels, before the resampler) and the kernel-level entry point
+// ------------------------------------------------------------------------------------------------
+// what every user of an SqairLaneScore checks, -1 + "<who>..." when one is off
+static int sq_score_fields(SqairHandle* h, const std::string& who, const SqairLaneScore& c) {
+  if (c.G < 1 || c.G > SQ_SCORE_MAXG) return sq_no(h, who + "G = " + std::to_string(c.G) + " must lie in 1.." + std::to_string(SQ_SCORE_MAXG));
+  if (!(c.iou_min > 0.0f && c.iou_min <= 1.0f)) return sq_no(h, who + "iou_min must lie in (0, 1]");   // (NaN fails both)
+  if (!c.truth_box || !c.truth_present || !c.truth_valid || !c.counts || !c.iou_sum || !c.last_id)
+    return sq_no(h, who + "truth_box, truth_present, truth_valid, counts, iou_sum and last_id must not be NULL");
+  return 0;
+}
+extern "C" int sqair_set_score(SqairHandle* h, const SqairLaneScore* score, int T, int B) {
+  if (!h) return -1;
+  if (!score) {
+    sq_score_off(h);
+    return 0;
+  }
+  const std::string who = "sqair_set_score: ";
+  if (!h->state_on || !h->est_on)
+    return sq_no(h, who + "needs an estimate (sqair_set_estimate): the score reads the lane answer it writes");
+  if (!sq_estimate_scorable(h->est))
+    return sq_no(h, who + "the estimate (sqair_set_estimate) must bind box, presence, obj_id and map_count: the score reads them");
+  if (T != h->est_T)
+    return sq_no(h, who + "T = " + std::to_string(T) + " but the estimate set by sqair_set_estimate is for T = " + std::to_string(h->est_T));
+  if (B != h->state_B)
+    return sq_no(h, who + "B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
+  if (sq_score_fields(h, who, *score) != 0) return -1;
+  h->score_on = true; h->score = *score;
+  return 0;
+}
+LaneScoreArgs sq_score_args(const SqairHandle* h, int T, int B) {
+  LaneScoreArgs a; memset(&a, 0, sizeof(a));
+  a.box = h->est.box; a.presence = h->est.presence; a.obj_id = h->est.obj_id; a.map_count = h->est.map_count; a.sc = h->score;
+  a.T = T; a.B = B; a.N = h->cfg.n_steps_per_image;
+  return a;
+}
+// kernel-level check of the score (tests/test_score_kernel.py): k_lane_score on caller tensors, no state and no pass
+extern "C" int sqair_lane_score_test(SqairHandle* h, const float* box, const float* presence, const float* obj_id, const int32_t* map_count,
+                                     int T, int B, const SqairLaneScore* score, void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_lane_score_test: ";
+  if (!box || !presence || !obj_id || !map_count || !score || T < 1 || B < 1 || T > 65535)
+    return sq_no(h, who + "null box / presence / obj_id / map_count / score or bad T / B");
+  if (sq_score_fields(h, who, *score) != 0) return -1;
+  LaneScoreArgs a; memset(&a, 0, sizeof(a));
+  a.box = box; a.presence = presence; a.obj_id = obj_id; a.map_count = map_count; a.sc = *score;
+  a.T = T; a.B = B; a.N = h->cfg.n_steps_per_image;
+  sq_launch_lane_score(a, (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
 
 // the refusals of a carried training call (host only: before any HIP call)
 int sq_carry_refusal(SqairHandle* h, const char* fn, int B, const SqairCarry* carry, const SqairOutputs* out) {
@@ -296,7 +352,8 @@ int sq_state_refusal(SqairHandle* h, bool train, int B, int t_offset) {
 
 SqStateRes sq_handle_state(const SqairHandle* h) {
   return SqStateRes{h->state_on, h->state_in, h->state_out, h->state_src, false, h->smc_on, h->smc, h->state_on && h->hist_on,
-                    h->state_on ? h->observed : nullptr, h->state_on && h->est_on, h->state_on && h->est_on && h->lay_on};
+                    h->state_on ? h->observed : nullptr, h->state_on && h->est_on, h->state_on && h->est_on && h->lay_on,
+                    h->state_on && h->est_on && h->score_on};
 }
 SqStateRes sq_carry_state(const SqairCarry* c) {
   return SqStateRes{true, c->state_in, c->state_out, c->src_rows, true, c->smc != nullptr, c->smc ? *c->smc : SqairSmc{}};

@@ -53,6 +53,17 @@ semantics): ``match`` [T', B, K, N] -- the slot of particle k associated with ob
 particles that agree, the weighted mean of what the decoder drew for the object: its appearance ``layer`` and its coverage ``cover``
 [T', B, N, H, W]; ``owner`` [T', B, H, W] is the object of largest coverage at a pixel, -1 (background) below ``layers_cover_min``.
 
+With ``score=True`` (a stream with ``estimate=True``) the lane answer is scored against ground-truth boxes inside the pass, by one more
+kernel after the estimate's and the layers' (include/sqair_hip.h: sqair_set_score, which states the semantics): a step takes
+``truth=dict(box=[T', B, G, 4], present=[T', B, G], valid=[T', B] or None)`` -- (y, x, h, w) in pixels as ``make_sequences``'s
+``coords``, G = ``score_truth`` slots per lane, an object keeping its slot for its life -- copied into stream-owned device buffers
+the way ``observed`` is; a step without ``truth`` scores nothing.  Present truths and present lane objects of IoU >= ``score_iou``
+are matched one to one (an object's last identity first, then greedily by IoU) and the CLEAR-MOT events counted on the device:
+``out["lane"]`` gains ``truth_match``, ``match_iou`` [T', B, G] and ``tp``, ``fn``, ``fp``, ``idsw`` [T', B] (-1 where nothing was scored),
+and ``score()`` reads the accumulators: per lane ``frames``, ``frames_invalid``, ``truth``, ``tp``, ``fn``, ``fp``, ``idsw``,
+``count_hit``, ``count_abs_err`` and ``iou_sum``, pooled ``mota``, ``motp`` and ``count_accuracy``.  ``reset(lanes)`` also forgets
+those lanes' identities (a new clip has new ones) and keeps their counters.
+
 The stream takes over its core's handle: while it is open, every inference pass of that handle carries the state.  ``close()``
 hands the handle back.
 
@@ -89,7 +100,8 @@ def _field_views(shapes, int_fields, device):
 class SqairStream(object):
     def __init__(self, core, B, frames_per_step=1, outputs=DEFAULT_OUTPUTS, use_graph=True, seed=0, resample=None, ess_frac=0.5,
                  state=None, history=None, history_fields=tuple(_capi.HISTORY_FIELDS), missing=False, estimate=False,
-                 estimate_iou=0.5, estimate_canvas=False, estimate_layers=False, layers_cover_min=0.5):
+                 estimate_iou=0.5, estimate_canvas=False, estimate_layers=False, layers_cover_min=0.5, score=False, score_iou=0.5,
+                 score_truth=None):
         if core.cfg.sample_from_prior:
             raise ValueError("SqairStream: generation modes (sample_from_prior) do not carry a state across calls")
         if resample not in (None, "systematic"):
@@ -107,6 +119,14 @@ class SqairStream(object):
         layers_cover_min = float(layers_cover_min)
         if estimate_layers and not 0.0 < layers_cover_min <= 1.0:   # (NaN fails too)
             raise ValueError("SqairStream: layers_cover_min must lie in (0, 1]")
+        if score and not estimate:
+            raise ValueError("SqairStream: score is for a stream with estimate=True")
+        score_iou = float(score_iou)
+        if score and not 0.0 < score_iou <= 1.0:   # (NaN fails too)
+            raise ValueError("SqairStream: score_iou must lie in (0, 1]")
+        if score and score_truth is not None and (isinstance(score_truth, bool) or not isinstance(score_truth, (int, np.integer)) or
+                                                  not 1 <= score_truth <= _capi.SCORE_MAX_TRUTH):
+            raise ValueError("SqairStream: score_truth must be an integer in [1, {}]".format(_capi.SCORE_MAX_TRUTH))
         self.smc = resample is not None
         self.ess_frac = ess_frac
         self.core = core
@@ -148,8 +168,10 @@ class SqairStream(object):
             torch.cuda.current_stream(core.device).synchronize()
             core.check(core.lib.sqair_set_observed(core.handle, self._observed.data_ptr(), self.T, self.B), "sqair_set_observed")
         self.estimate = bool(estimate)
+        self.scored = bool(score)
+        self.G = (core.N if score_truth is None else int(score_truth)) if self.scored else 0   # truth slots per lane
         if self.estimate:   # after SMC: the estimate's log_w must be the resampler's accumulator
-            self._est = self._estimate_buffers(bool(estimate_canvas), bool(estimate_layers))
+            self._est = self._estimate_buffers(bool(estimate_canvas), bool(estimate_layers), self.G)
             est = _capi.SqairLaneEstimate(iou_min=estimate_iou, log_w=cs.log_weight_sum.data_ptr(),
                                           **{n: t.data_ptr() for n, t in self._est.items() if n in _capi.ESTIMATE_FIELDS})
             torch.cuda.current_stream(core.device).synchronize()
@@ -157,6 +179,16 @@ class SqairStream(object):
             if estimate_layers:
                 lay = _capi.SqairLaneLayers(cover_min=layers_cover_min, **{n: self._est[n].data_ptr() for n in _capi.LAYERS_FIELDS})
                 core.check(core.lib.sqair_set_layers(core.handle, C.byref(lay), self.T, self.B), "sqair_set_layers")
+            if self.scored:   # the truth of a step, the accumulators and the identity memory: the stream's own device buffers
+                z = lambda shp, dt: torch.zeros(shp, dtype=dt, device=core.device)
+                self._score = dict(truth_box=z((self.T, self.B, self.G, 4), torch.float32), truth_present=z((self.T, self.B, self.G), torch.int32),
+                                   truth_valid=z((self.T, self.B), torch.int32), counts=z((self.B, len(_capi.SCORE_COUNTS)), torch.int64),
+                                   iou_sum=z((self.B,), torch.float64), last_id=z((self.B, self.G), torch.int32) - 1)
+                self._score_valid_is_zero = True
+                sc = _capi.SqairLaneScore(iou_min=score_iou, G=self.G, **{n: t.data_ptr() for n, t in self._score.items()},
+                                          **{n: self._est[n].data_ptr() for n in _capi.SCORE_FIELDS})
+                torch.cuda.current_stream(core.device).synchronize()
+                core.check(core.lib.sqair_set_score(core.handle, C.byref(sc), self.T, self.B), "sqair_set_score")
         if history is not None:
             ring, nb, bits = cs.set_history(history, history_fields, self.T)
             torch.cuda.current_stream(core.device).synchronize()   # (the ring's zeros are in place before a pass pushes into it)
@@ -179,22 +211,31 @@ class SqairStream(object):
         self._smc_uniforms = uniforms
         self._graph = False
 
-    def _estimate_buffers(self, canvas, layers=False):
-        """The device buffers k_lane_estimate -- and, with ``layers``, k_lane_layers -- writes (include/sqair_hip.h: SqairLaneEstimate,
-        SqairLaneLayers), by field: views of ONE allocation (``_est_flat``), so that a step copies them out with one launch instead
-        of one per field."""
+    def _estimate_buffers(self, canvas, layers=False, score_truth=0):
+        """The device buffers k_lane_estimate -- and, with ``layers``, k_lane_layers, with ``score_truth`` = G > 0, k_lane_score's
+        per-frame outputs -- writes (include/sqair_hip.h: SqairLaneEstimate, SqairLaneLayers, SqairLaneScore), by field: views of ONE
+        allocation (``_est_flat``), so that a step copies them out with one launch instead of one per field."""
         core = self.core
         shapes = _capi.estimate_shapes(self.T, self.B, self.K, core.N, core.nw, (core.H, core.W) if canvas else None)
         if layers:
             shapes.update(_capi.layers_shapes(self.T, self.B, self.K, core.N, (core.H, core.W)))
-        self._est_flat, self._est_views = _field_views(shapes, _capi.ESTIMATE_INT_FIELDS + (_capi.LAYERS_INT_FIELDS if layers else ()),
-                                                       core.device)
+        if score_truth:
+            shapes.update(_capi.score_shapes(self.T, self.B, score_truth))
+        ints = _capi.ESTIMATE_INT_FIELDS + (_capi.LAYERS_INT_FIELDS if layers else ()) + (_capi.SCORE_INT_FIELDS if score_truth else ())
+        self._est_flat, self._est_views = _field_views(shapes, ints, core.device)
         return self._est_views(self._est_flat)
 
     # ---- source map -------------------------------------------------------------------------------------------------------
     def reset(self, lanes):
-        """Lanes (sequences, in [0, B)) whose next step starts a new clip: their K particle rows start fresh, counter 0."""
+        """Lanes (sequences, in [0, B)) whose next step starts a new clip: their K particle rows start fresh, counter 0.  A scored
+        stream also forgets those lanes' identities (``last_id``: a new clip has new ones); their counters stay."""
         self.carried.reset(lanes)
+        if self.scored:
+            lanes = sorted(set(self.carried.check_lanes(lanes)))
+            if lanes:
+                with self.carried._on_core_stream():
+                    for j in lanes:
+                        self._score["last_id"][j].fill_(-1)
 
     def resample(self, src_rows):
         """Row r of the next step continues row src_rows[r] (-1: starts fresh); e.g. SMC resampling of the particles of each
@@ -209,7 +250,29 @@ class SqairStream(object):
 
     _blank_unobserved = staticmethod(blank_unobserved)
 
-    def step(self, frames, noise=None, seed=None, uniforms=None, observed=None):
+    def _check_truth(self, truth):
+        """``truth`` of a step as (box float32 [T', B, G, 4], present int32 [T', B, G], valid int32 [T', B]) (None: no truth)."""
+        if truth is None:
+            return None
+        fn = "SqairStream.step: "
+        if not self.scored:
+            raise ValueError(fn + "truth is for a stream with score=True")
+        if not isinstance(truth, dict) or "box" not in truth or "present" not in truth or set(truth) - {"box", "present", "valid"}:
+            raise ValueError(fn + "truth must be a dict with box, present and optionally valid")
+        T, B, G = self.T, self.B, self.G
+        box = torch.as_tensor(truth["box"]).to(torch.float32)
+        present = torch.as_tensor(truth["present"])
+        valid = truth.get("valid")
+        valid = torch.ones((T, B), dtype=torch.int32) if valid is None else torch.as_tensor(valid)
+        if T == 1 and box.dim() == 3:
+            box, present, valid = box[None], present[None], (valid[None] if valid.dim() == 1 else valid)
+        for name, t, shp in (("box", box, (T, B, G, 4)), ("present", present, (T, B, G)), ("valid", valid, (T, B))):
+            if tuple(t.shape) != shp:
+                raise ValueError(fn + "truth[{!r}] of shape {} given, {} expected".format(name, tuple(t.shape), list(shp)))
+        as_mask = lambda m: m if m.dtype == torch.int32 else (m != 0).to(torch.int32)   # (the kernel tests != 0: int32 goes as it is)
+        return box, as_mask(present), as_mask(valid)
+
+    def step(self, frames, noise=None, seed=None, uniforms=None, observed=None, truth=None):
         """Consumes frames [T', B, H, W] (T' = frames_per_step); returns this step's per-frame outputs {name: [T', B*K, ...]}
         (copies, valid on the current stream).  ``noise`` [T', B*K, 2, N, 4 + n_what + 1]; default: the library's generator
         keyed by (``seed`` or the stream's seed, frame index).  With SMC on, also ``ess``, ``resampled``, ``log_evidence`` [B]
@@ -217,8 +280,11 @@ class SqairStream(object):
         ``uniforms`` [B] in [0, 1): this step's systematic-resampling uniforms (default: Philox).  ``observed`` (streams with
         ``missing=True``): bool [T', B], or [B] when T' = 1, False = the lane has no frame and coasts on the prior; its frame is
         replaced by zeros, so it may hold anything, NaN included.  Default: every lane observed.  Returned among the outputs.
-        Streams with ``estimate=True`` add ``lane``: the per-lane answer {name: [T', B, ...]} of this step's rows."""
+        Streams with ``estimate=True`` add ``lane``: the per-lane answer {name: [T', B, ...]} of this step's rows.  ``truth``
+        (streams with ``score=True``): dict(box=[T', B, G, 4] (y, x, h, w) in pixels, present=[T', B, G], valid=[T', B] or None = all),
+        with [B, ...] accepted when T' = 1; the step's lane answer is scored against it.  Default: nothing is scored."""
         observed = self._check_observed(observed)   # (before the core is touched)
+        truth = self._check_truth(truth)
         core, cs = self.core, self.carried
         frames, noise, uniforms = cs.check_inputs(self.T, frames, noise, uniforms, "stream")
         if observed is not None:
@@ -239,6 +305,13 @@ class SqairStream(object):
                     elif not self._observed_is_ones:
                         self._observed.fill_(1)
                     self._observed_is_ones = observed is None
+                if self.scored:   # (as the mask: the kernel reads the stream's own buffers, so one graph serves every step)
+                    if truth is not None:
+                        for n, t in zip(("truth_box", "truth_present", "truth_valid"), truth):
+                            self._score[n].copy_(t, non_blocking=True)
+                    elif not self._score_valid_is_zero:
+                        self._score["truth_valid"].zero_()
+                    self._score_valid_is_zero = truth is None
                 if self.use_graph:
                     if not self._graph:
                         core.stream.synchronize()
@@ -260,6 +333,34 @@ class SqairStream(object):
             core._join_out()
         self.frame += self.T
         return out
+
+    # ---- scoring ----------------------------------------------------------------------------------------------------------
+    def score(self, reset=False):
+        """The score so far (include/sqair_hip.h: sqair_set_score): per lane the int64 counters ``frames``, ``frames_invalid``,
+        ``truth``, ``tp``, ``fn``, ``fp``, ``idsw``, ``count_hit``, ``count_abs_err`` [B] and the fp64 ``iou_sum`` [B] (host tensors), and
+        pooled over the lanes ``mota`` = 1 - (fn + fp + idsw) / truth, ``motp`` = iou_sum / tp and ``count_accuracy`` = count_hit /
+        frames, each NaN where its denominator is 0.  ``reset``: the counters and ``iou_sum`` start again from zero afterwards; the
+        identity memory stays (``reset(lanes)`` clears that)."""
+        if not self.scored:
+            raise ValueError("SqairStream.score: the stream keeps no score (SqairStream(..., estimate=True, score=True))")
+        core = self.core
+        with torch.cuda.device(core.device):
+            core._join_in()
+            with core.on_stream():
+                counts, iou_sum = self._score["counts"].clone(), self._score["iou_sum"].clone()
+                if reset:
+                    self._score["counts"].zero_()
+                    self._score["iou_sum"].zero_()
+            core._join_out()
+            counts, iou_sum = counts.cpu(), iou_sum.cpu()
+        res = {n: counts[:, i].clone() for i, n in enumerate(_capi.SCORE_COUNTS)}
+        res["iou_sum"] = iou_sum
+        tot = {n: int(v.sum()) for n, v in res.items() if n != "iou_sum"}
+        div = lambda a, b: float(a) / b if b else float("nan")
+        res["mota"] = 1.0 - div(tot["fn"] + tot["fp"] + tot["idsw"], tot["truth"])
+        res["motp"] = div(float(iou_sum.sum()), tot["tp"])
+        res["count_accuracy"] = div(tot["count_hit"], tot["frames"])
+        return res
 
     # ---- forecasting ------------------------------------------------------------------------------------------------------
     def forecast(self, F, noise=None, seed=None, outputs=FORECAST_OUTPUTS, summaries=True, samples=1, lane=False, lane_iou=0.5):

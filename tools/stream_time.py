@@ -44,6 +44,15 @@ layers, SMC + layers.  The layers are one dependent node after the estimate's --
 are 2 N H W floats per lane; next to them the estimate's node and the resampler's node of the same run.  Recorded, not gated on:
 
     python tools/stream_time.py --layers [--out profiles/stream_layers_time.json]
+
+With --score: the price of stream scoring (SqairStream(estimate=True, score=True), include/sqair_hip.h: sqair_set_score).  Streams at
+cfg-2's batch alternating in one process as with --history: plain, SMC, estimate, SMC + estimate, score, SMC + score; the scored legs
+are fed a truth that is resident on the device (G = N boxes per lane, all present, every frame valid), as the frames are.  The score
+is one dependent node after the estimate's, three small copies of the truth into the stream's buffers and six more small fields in
+the step's copy of the per-lane answer; next to it the estimate's node and the resampler's node of the same run.  Recorded, not
+gated on:
+
+    python tools/stream_time.py --score [--out profiles/stream_score_time.json]
 """
 import argparse
 import json
@@ -267,6 +276,29 @@ def time_layers(B, K, N, steps, warmup, rounds=10, hw=(50, 50)):
     return res
 
 
+def time_score(B, K, N, steps, warmup, rounds=10, hw=(50, 50)):
+    smc = dict(resample="systematic", ess_frac=0.5)
+    sc = dict(estimate=True, score=True, score_truth=N)
+    legs = dict(plain={}, smc=smc, estimate=dict(estimate=True), smc_estimate=dict(estimate=True, **smc), score=sc, smc_score=dict(sc, **smc))
+    rng = np.random.default_rng(3)
+    box = np.concatenate([rng.uniform(-5, 35, (1, B, N, 2)), rng.uniform(8, 28, (1, B, N, 2))], -1).astype(np.float32)
+    truth = dict(box=torch.as_tensor(box).cuda(), present=torch.ones((1, B, N), dtype=torch.int32).cuda(),
+                 valid=torch.ones((1, B), dtype=torch.int32).cuda())
+    step_kw = dict(score=dict(truth=truth), smc_score=dict(truth=truth))
+    streams, res, med, thr = alternating_streams(legs, B, K, N, steps, warmup, rounds, hw, step_kw)
+    res["lane_bytes_per_step"] = {n: int(streams[n]._est_flat.numel() * 4) for n in ("estimate", "score")}
+    res["score"] = {n: (v.sum().item() if torch.is_tensor(v) else v) for n, v in streams["smc_score"].score().items()}   # (over the lanes)
+    for key, v in (("latency", med), ("back_to_back", thr)):
+        one_node = v["smc"] - v["plain"]            # the yardstick: one dependent node (the resampler) on this machine, this run
+        added = dict(estimate_node_on_plain=v["estimate"] - v["plain"], estimate_node_on_smc=v["smc_estimate"] - v["smc"],
+                     score_node_on_estimate=v["score"] - v["estimate"], score_node_on_smc_estimate=v["smc_score"] - v["smc_estimate"])
+        res["us_" + key] = dict(smc_node=1e3 * one_node, **{n: 1e3 * a for n, a in added.items()},
+                                **{n + "_over_smc_node": (a / one_node if one_node > 0 else None) for n, a in added.items()})
+    for st in streams.values():
+        st.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=500)
@@ -278,10 +310,13 @@ def main():
     ap.add_argument("--missing", action="store_true", help="plain / SMC / a mask with every lane / with no lane observed, alternating (profiles/stream_missing_time.json)")
     ap.add_argument("--estimate", action="store_true", help="plain / SMC / estimate / SMC + estimate / with mean_canvas, alternating (profiles/stream_estimate_time.json)")
     ap.add_argument("--layers", action="store_true", help="plain / SMC / estimate / SMC + estimate / layers / SMC + layers, alternating (profiles/stream_layers_time.json)")
+    ap.add_argument("--score", action="store_true", help="plain / SMC / estimate / SMC + estimate / score / SMC + score, alternating (profiles/stream_score_time.json)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     ov, _, _, _ = config_inputs(2)
-    if args.layers:
+    if args.score:
+        shapes = [dict(name="cfg2_batch_score", **time_score(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
+    elif args.layers:
         shapes = [dict(name="cfg2_batch_layers", **time_layers(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
     elif args.estimate:
         shapes = [dict(name="cfg2_batch_estimate", **time_estimate(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
