@@ -265,7 +265,9 @@ int sqair_smc_resample_test(SqairHandle* h, const float* lw, int T, int B, int K
  * with unknown bits, ring_bytes < sqair_history_bytes(h, L, 1, B of the state, fields); at pass time: a B other than the
  * state's, ring_bytes < sqair_history_bytes for the pass's T, a T other than the ring's earlier passes', a NULL output among the
  * fields.  NULL ring: off.  sqair_set_state switching the state off switches history off too.  Training passes
- * (sqair_forward_train*, sqair_forward_train_carry) never push: a history for training on streams is out of scope. */
+ * (sqair_forward_train*, sqair_forward_train_carry) never push: a history for training on streams is out of scope.
+ * The ring's T is fixed by the first pass that none of the pass-time refusals -- the history's own or another registration's, the
+ * estimate's for instance -- turns away: a refused pass leaves the handle, the ring's T included, as it was. */
 #define SQAIR_HIST_WHERE    1u
 #define SQAIR_HIST_PRESENCE 2u
 #define SQAIR_HIST_OBJ_ID   4u

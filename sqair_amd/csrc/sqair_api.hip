@@ -1001,17 +1001,13 @@ struct SlotPhase {
   bool fuse;                          // the slot's tail rides in the next slot's VanillaRNN launch (k_rnn_tail)
 };
 
-// parts: 1 = prologue (workspace clear, initial state, input encoder), 2 = the frame loop, 4 = epilogue (log-probabilities,
-// decoder, final state copies).  carry: the settings of a carried training call (refused or not by its entry point); NULL =
-// the handle's carried state, if any.
-int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, const float* obs, const float* noise,
-                    int T, int B, int t_offset, const SqairOutputs* outp, float* wsbase, int64_t ws_bytes,
-                    hipStream_t s, bool train, int parts, const SqStateRes* carry = nullptr) {
+// The pass: prologue (workspace clear, initial state, input encoder), the frame loop, epilogue (log-probabilities, decoder, final
+// state copies, the carried state's writers).  st: the settings its entry point resolved (sq_resolve_pass / sq_carry_state), already
+// past their refusals; the pass reads no registration field of the handle.
+SQ_LOCAL int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, const float* obs, const float* noise,
+                             int T, int B, int t_offset, const SqairOutputs* outp, float* wsbase, int64_t ws_bytes,
+                             hipStream_t s, bool train, const SqStateRes& st) {
   const SqairConfig& c = h->cfg;
-  if (!carry && (sq_observed_refusal(h, train, T) != 0 || sq_state_refusal(h, train, B, t_offset) != 0 || sq_smc_refusal(h, outp) != 0 ||
-                 sq_history_refusal(h, T, B, outp) != 0 || sq_estimate_refusal(h, T, outp) != 0))
-    return -1;
-  const SqStateRes st = carry ? *carry : sq_handle_state(h);
   if (!flat || !packed || !obs || !noise || !outp || !wsbase || T < 1 || B < 1) {
     sq_set_error(h, "sqair_forward: null argument or bad T/B");
     return -1;
@@ -1054,7 +1050,7 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
   // The GEMM A-operand contract wants every float it may touch to be finite (padding meets zero weights, but
   // 0 * NaN = NaN) and slot records are read as 56-wide segments before all their fields are written in a frame:
   // clear the caller's (garbage) workspace once per pass
-  if (parts & 1) {
+  {
     // (clear_each_pass = false: the caller cleared this workspace once with sqair_clear_workspace and reuses it with the
     //  same T and B -- every buffer is then either rewritten by the pass or holds finite values / zeros it never overwrites)
     if (h->clear_each_pass) sq_zero_fill(wsbase, w.clear_n, s);
@@ -1106,7 +1102,7 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
   if (w.chain && !(fuse_prop && fuse_disc)) { sq_set_error(h, "slot chain: tail fusion off"); return -3; }
   const bool fw = sq_what_fusion(h, train, w.chain);   // the what sample in the producing layer's epilogue (sqair_glue.h: WhatArgs)
   TailArgs pending_tail; memset(&pending_tail, 0, sizeof(pending_tail));
-  for (int t = 0; (parts & 2) && t < T; ++t) {
+  for (int t = 0; t < T; ++t) {
     const int pp = t & 1, pn = pp ^ 1;
     const float* img = obs + (size_t)t * B * PL;
     const float* nz = noise + (size_t)t * R * 2 * N * nzw;
@@ -1350,7 +1346,6 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
       }
     }
   }
-  if (!(parts & 4)) return 0;
   // ---- H. log-probabilities of all T frames in one launch (grid R x T) ----
   {
     LogprobArgs la; memset(&la, 0, sizeof(la));
@@ -1418,11 +1413,6 @@ int sq_forward_impl(SqairHandle* h, const float* flat, const float* packed, cons
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }
-static int forward_impl(SqairHandle* h, const float* flat, const float* packed, const float* obs, const float* noise,
-                        int T, int B, int t_offset, const SqairOutputs* outp, float* wsbase, int64_t ws_bytes,
-                        hipStream_t s) {
-  return sq_forward_impl(h, flat, packed, obs, noise, T, B, t_offset, outp, wsbase, ws_bytes, s, false, 7);
-}
 
 // Training-mode forward pass: identical launch sequence and results, but every intermediate the backward pass needs
 // is kept in the (larger) workspace; sqair_backward consumes it.
@@ -1440,10 +1430,11 @@ extern "C" int sqair_forward_train(SqairHandle* h, const float* flat_params, con
                                    const float* noise, int T, int B, int t_offset, const SqairOutputs* out,
                                    void* workspace, int64_t workspace_bytes, void* stream) {
   if (!h) return -1;
-  if (sq_observed_refusal(h, true, T) != 0 || sq_state_refusal(h, true, B, t_offset) != 0) return -1;
+  SqStateRes st;
+  if (sq_resolve_pass(h, true, T, B, t_offset, out, &st) != 0) return -1;
   if (!sq_trainable_frame(h)) return -1;
   return sq_forward_impl(h, flat_params, (const float*)packed, obs, noise, T, B, t_offset, out, (float*)workspace,
-                         workspace_bytes, (hipStream_t)stream, true, 7);
+                         workspace_bytes, (hipStream_t)stream, true, st);
 }
 // Training forward of a carried chunk (include/sqair_hip.h: SqairCarry): the pass of sqair_forward_train with the state import /
 // export / SMC settings of the carry instead of the handle's; every row's counter and fresh / imported flag stay in the workspace
@@ -1459,7 +1450,7 @@ extern "C" int sqair_forward_train_carry(SqairHandle* h, const float* flat_param
   }
   const SqStateRes st = sq_carry_state(carry);
   return sq_forward_impl(h, flat_params, (const float*)packed, obs, noise, T, B, 0, out, (float*)train_workspace, workspace_bytes,
-                         (hipStream_t)stream, true, 7, &st);
+                         (hipStream_t)stream, true, st);
 }
 
 // Training forward of a masked carried chunk (include/sqair_hip.h: "training on gappy and ragged streams"): the carried chunk with
@@ -1477,7 +1468,7 @@ extern "C" int sqair_forward_train_carry_masked(SqairHandle* h, const float* fla
   SqStateRes st = sq_carry_state(carry);
   st.observed = observed;
   return sq_forward_impl(h, flat_params, (const float*)packed, obs, noise, T, B, 0, out, (float*)train_workspace, workspace_bytes,
-                         (hipStream_t)stream, true, 7, &st);
+                         (hipStream_t)stream, true, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1697,58 +1688,72 @@ extern "C" int sqair_check_scales(SqairHandle* h, void* workspace, int T, int B,
   return 0;
 }
 
+// Capture on this stream, scoped: on every way out that did not hand_over() the graph and its executable, the destructor ends a
+// capture still open (a stream left capturing fails every later call on it) and destroys what was made, the two timing events of
+// the measurement helpers included.  (sqair_capture_begin / _end are paired by the caller and do not use this.)
+struct SqCapture {
+  hipStream_t s;
+  bool open = false;
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  explicit SqCapture(hipStream_t stream) : s(stream) {}
+  SqCapture(const SqCapture&) = delete;
+  hipError_t begin() { const hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal); open = e == hipSuccess; return e; }
+  hipError_t end() { open = false; return hipStreamEndCapture(s, &graph); }
+  hipError_t instantiate() { return hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0); }
+  hipError_t events() { const hipError_t e = hipEventCreate(&ev[0]); return e != hipSuccess ? e : hipEventCreate(&ev[1]); }
+  void hand_over(hipGraph_t* g, hipGraphExec_t* x) { *g = graph; *x = exec; graph = nullptr; exec = nullptr; }
+  ~SqCapture() {
+    if (open) (void)hipStreamEndCapture(s, &graph);
+    if (exec) (void)hipGraphExecDestroy(exec);
+    if (graph) (void)hipGraphDestroy(graph);
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+  }
+};
+
 extern "C" int sqair_forward(SqairHandle* h, const float* flat_params, const void* packed, const float* obs,
                              const float* noise, int T, int B, int t_offset, const SqairOutputs* out, void* workspace,
                              int64_t workspace_bytes, void* stream) {
   if (!h) return -1;
-  return forward_impl(h, flat_params, (const float*)packed, obs, noise, T, B, t_offset, out, (float*)workspace,
-                      workspace_bytes, (hipStream_t)stream);
+  SqStateRes st;
+  if (sq_resolve_pass(h, false, T, B, t_offset, out, &st) != 0) return -1;
+  return sq_forward_impl(h, flat_params, (const float*)packed, obs, noise, T, B, t_offset, out, (float*)workspace, workspace_bytes,
+                         (hipStream_t)stream, false, st);
 }
 
 extern "C" int sqair_graph_capture(SqairHandle* h, const float* flat_params, const void* packed, const float* obs,
                                    const float* noise, int T, int B, int t_offset, const SqairOutputs* out,
                                    void* workspace, int64_t workspace_bytes, void* stream) {
   if (!h) return -1;
-  if (sq_observed_refusal(h, false, T) != 0 || sq_state_refusal(h, false, B, t_offset) != 0 || sq_smc_refusal(h, out) != 0 ||
-      sq_history_refusal(h, T, B, out) != 0 || sq_estimate_refusal(h, T, out) != 0)
-    return -1;
+  SqStateRes st;
+  if (sq_resolve_pass(h, false, T, B, t_offset, out, &st) != 0) return -1;
   hipStream_t s = (hipStream_t)stream;
   if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
   if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
-  if (h->opt_slot_chain) {  // one eager pass: the chain launches' op tables are uploaded outside the capture (sqair_chain.hip)
-    void* const state_out = h->state_out;   // (a carried state is imported but not exported, resampled or pushed: the capture
-    const bool smc_on = h->smc_on;           //  leaves the state, its source map, the SMC weights and the history as they were)
-    const bool hist_on = h->hist_on, est_on = h->est_on;
-    h->state_out = nullptr;
-    h->smc_on = false;
-    h->hist_on = false;
-    h->est_on = false;
-    const int rc0 = forward_impl(h, flat_params, (const float*)packed, obs, noise, T, B, t_offset, out, (float*)workspace, workspace_bytes, s);
-    h->state_out = state_out;
-    h->smc_on = smc_on;
-    h->hist_on = hist_on;
-    h->est_on = est_on;
+  if (h->opt_slot_chain) {
+    // one eager pass: the chain launches' op tables are uploaded outside the capture (sqair_chain.hip).  It reads what the pass
+    // reads and writes nothing but the workspace and the outputs: the capture leaves state, map, weights, history and score as they were
+    const int rc0 = sq_forward_impl(h, flat_params, (const float*)packed, obs, noise, T, B, t_offset, out, (float*)workspace,
+                                    workspace_bytes, s, false, sq_without_effects(st));
     if (rc0 != 0) return rc0;
     SQ_CHECK_HIP(hipStreamSynchronize(s));
   }
-  SQ_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-  int rc = forward_impl(h, flat_params, (const float*)packed, obs, noise, T, B, t_offset, out, (float*)workspace,
-                        workspace_bytes, s);
-  hipGraph_t g = nullptr;
-  hipError_t e = hipStreamEndCapture(s, &g);
-  if (rc != 0) {
-    if (g) (void)hipGraphDestroy(g);
-    return rc;
-  }
+  SqCapture cap(s);
+  SQ_CHECK_HIP(cap.begin());
+  const int rc = sq_forward_impl(h, flat_params, (const float*)packed, obs, noise, T, B, t_offset, out, (float*)workspace,
+                                 workspace_bytes, s, false, st);
+  const hipError_t e = cap.end();
+  if (rc != 0) return rc;
   if (e != hipSuccess) {
     sq_set_error(h, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
     return -2;
   }
-  h->graph = g;
   size_t nn = 0;
-  SQ_CHECK_HIP(hipGraphGetNodes(g, nullptr, &nn));
+  SQ_CHECK_HIP(hipGraphGetNodes(cap.graph, nullptr, &nn));
+  SQ_CHECK_HIP(cap.instantiate());
   h->graph_nodes = (int)nn;
-  SQ_CHECK_HIP(hipGraphInstantiate(&h->graph_exec, g, nullptr, nullptr, 0));
+  cap.hand_over(&h->graph, &h->graph_exec);
   return 0;
 }
 
@@ -1868,8 +1873,11 @@ static void adhoc_fill_transposed(std::vector<int>& idx, int kc, int Kdim, int N
   }
 }
 
-extern "C" int sqair_linear_test(SqairHandle* h, const float* x, const float* wmat, const float* b, float* y, int M,
-                                 int Kdim, int Ndim, int act, void* scratch, int64_t scratch_bytes, void* stream) {
+// What the dense unit entry points time after their one checked launch: nothing (sqair_linear_test), the launch `reps` times back to
+// back (sqair_debug_linear_time), or `nodes` launches, dependent or not, as one HIP graph replayed `reps` times (..._graph_time)
+struct LinearTiming { int reps = 0, nodes = 0; bool dependent = false; };
+static int sq_linear_test(SqairHandle* h, const float* x, const float* wmat, const float* b, float* y, int M, int Kdim, int Ndim, int act,
+                          void* scratch, int64_t scratch_bytes, const LinearTiming& tm, float* us_out, void* stream) {
   if (!h || !x || !wmat || !y || !scratch) return -1;
   hipStream_t s = (hipStream_t)stream;
   PackedLayer L;
@@ -1900,17 +1908,19 @@ extern "C" int sqair_linear_test(SqairHandle* h, const float* x, const float* wm
   if (sq_launch_linear(l.a, L, s) != 0) { sq_set_error(h, "sqair_linear_test: A-operand contract violated"); return -5; }
   SQ_CHECK_HIP(hipGetLastError());
   SQ_CHECK_HIP(hipStreamSynchronize(s));
-  if (h->debug_reps > 0 && h->debug_graph_nodes > 0) {
-    // sqair_debug_linear_graph_time: `nodes` launches of this layer captured as ONE HIP graph -- the same launch over and over
-    // (no data dependence), or (dependent) every launch reading what the previous one wrote -- and the graph replayed
-    // `reps` times between two HIP events: time per graph NODE (kernel + the dependent-dispatch boundary), on whatever build
-    // of the library this is.  The figure bench.py's timeline calls the SLOT of a dense launch, measured without the stamps.
+  if (tm.reps < 1) return 0;
+  SqCapture cap(s);   // (the events of both timed modes; the graph of the second)
+  float ms = 0.0f;
+  if (tm.nodes > 0) {
+    // `nodes` launches of this layer captured as ONE HIP graph -- the same launch over and over (no data dependence), or
+    // (dependent) every launch reading what the previous one wrote -- and the graph replayed `reps` times between two HIP events:
+    // time per graph NODE (kernel + the dependent-dispatch boundary), on whatever build of the library this is.  The figure
+    // bench.py's timeline calls the SLOT of a dense launch, measured without the stamps.
     // dependent: every launch reads what the previous one wrote -- IN PLACE, input columns [0, K) and output columns [0, N) of
     // one buffer of pitch max(K, N) behind the other scratch (a race between the workgroups of a row tile: the values mean
     // nothing, tanh keeps them finite; what is timed is a launch whose operand comes out of the previous launch's stores)
     Lin l2;
-    const bool dep = h->debug_graph_dependent;
-    if (dep) {
+    if (tm.dependent) {
       const int ldz = (std::max(kpad, Ndim) + 3) & ~3;
       float* d_z = d_x + (size_t)M * kpad;
       if (scratch_bytes < (2 * nel + 2 * nb + 256 + (int64_t)M * kpad + (int64_t)M * ldz + 16) * 4) { sq_set_error(h, "sqair_debug_linear_graph_time: scratch too small"); return -1; }
@@ -1919,53 +1929,36 @@ extern "C" int sqair_linear_test(SqairHandle* h, const float* x, const float* wm
       l2.seg(d_z, ldz, Kdim).out(d_z, ldz).act(act);
       l2.a.wp = d_w; l2.a.wzero = d_zero; l2.a.bias = d_b; l2.a.M = M; l2.a.N = Ndim;
     }
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
-    SQ_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    for (int i = 0; i < h->debug_graph_nodes; ++i) sq_launch_linear(dep ? l2.a : l.a, L, s);
-    SQ_CHECK_HIP(hipStreamEndCapture(s, &g));
-    SQ_CHECK_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-    hipEvent_t ea, eb;
-    SQ_CHECK_HIP(hipEventCreate(&ea));
-    SQ_CHECK_HIP(hipEventCreate(&eb));
-    for (int i = 0; i < 2; ++i) SQ_CHECK_HIP(hipGraphLaunch(ge, s));
-    (void)hipEventRecord(ea, s);
-    for (int i = 0; i < h->debug_reps; ++i) SQ_CHECK_HIP(hipGraphLaunch(ge, s));
-    (void)hipEventRecord(eb, s);
-    SQ_CHECK_HIP(hipStreamSynchronize(s));
-    float ms = 0.0f;
-    SQ_CHECK_HIP(hipEventElapsedTime(&ms, ea, eb));
-    h->debug_us = ms * 1e3f / ((float)h->debug_reps * (float)h->debug_graph_nodes);
-    (void)hipEventDestroy(ea);
-    (void)hipEventDestroy(eb);
-    (void)hipGraphExecDestroy(ge);
-    (void)hipGraphDestroy(g);
-  } else if (h->debug_reps > 0) {  // sqair_debug_linear_time: the same launch `reps` times back to back between two events
-    hipEvent_t ea, eb;
-    SQ_CHECK_HIP(hipEventCreate(&ea));
-    SQ_CHECK_HIP(hipEventCreate(&eb));
+    SQ_CHECK_HIP(cap.begin());
+    for (int i = 0; i < tm.nodes; ++i)   // (a failed launch: cap ends the capture on the way out)
+      if (sq_launch_linear(tm.dependent ? l2.a : l.a, L, s) != 0) { sq_set_error(h, "sqair_debug_linear_graph_time: A-operand contract violated inside the capture"); return -5; }
+    SQ_CHECK_HIP(cap.end());
+    SQ_CHECK_HIP(cap.instantiate());
+    SQ_CHECK_HIP(cap.events());
+    for (int i = 0; i < 2; ++i) SQ_CHECK_HIP(hipGraphLaunch(cap.exec, s));
+    (void)hipEventRecord(cap.ev[0], s);
+    for (int i = 0; i < tm.reps; ++i) SQ_CHECK_HIP(hipGraphLaunch(cap.exec, s));
+  } else {  // the same launch `reps` times back to back between two events
+    SQ_CHECK_HIP(cap.events());
     for (int i = 0; i < 3; ++i) sq_launch_linear(l.a, L, s);
-    (void)hipEventRecord(ea, s);
-    for (int i = 0; i < h->debug_reps; ++i) sq_launch_linear(l.a, L, s);
-    (void)hipEventRecord(eb, s);
-    SQ_CHECK_HIP(hipStreamSynchronize(s));
-    float ms = 0.0f;
-    SQ_CHECK_HIP(hipEventElapsedTime(&ms, ea, eb));
-    h->debug_us = ms * 1e3f / (float)h->debug_reps;
-    (void)hipEventDestroy(ea);
-    (void)hipEventDestroy(eb);
+    (void)hipEventRecord(cap.ev[0], s);
+    for (int i = 0; i < tm.reps; ++i) sq_launch_linear(l.a, L, s);
   }
+  (void)hipEventRecord(cap.ev[1], s);
+  SQ_CHECK_HIP(hipStreamSynchronize(s));
+  SQ_CHECK_HIP(hipEventElapsedTime(&ms, cap.ev[0], cap.ev[1]));
+  *us_out = ms * 1e3f / ((float)tm.reps * (float)std::max(tm.nodes, 1));
   return 0;
+}
+extern "C" int sqair_linear_test(SqairHandle* h, const float* x, const float* wmat, const float* b, float* y, int M,
+                                 int Kdim, int Ndim, int act, void* scratch, int64_t scratch_bytes, void* stream) {
+  return sq_linear_test(h, x, wmat, b, y, M, Kdim, Ndim, act, scratch, scratch_bytes, LinearTiming{}, nullptr, stream);
 }
 // measurement helper (tools/time_linear.py): average time of one dense launch of the given shape, launches back to back
 extern "C" int sqair_debug_linear_time(SqairHandle* h, const float* x, const float* wmat, const float* b, float* y, int M, int Kdim,
                                        int Ndim, int act, void* scratch, int64_t scratch_bytes, int reps, float* us_out, void* stream) {
   if (!h || !us_out || reps < 1) return -1;
-  h->debug_reps = reps;
-  const int rc = sqair_linear_test(h, x, wmat, b, y, M, Kdim, Ndim, act, scratch, scratch_bytes, stream);
-  h->debug_reps = 0;
-  *us_out = h->debug_us;
-  return rc;
+  return sq_linear_test(h, x, wmat, b, y, M, Kdim, Ndim, act, scratch, scratch_bytes, LinearTiming{reps, 0, false}, us_out, stream);
 }
 
 // measurement helper (tools/dense_graph_time.py): the dense launches of the passes issued between (on = 1) and the read-out.
@@ -1987,11 +1980,8 @@ extern "C" int sqair_debug_linear_graph_time(SqairHandle* h, const float* x, con
                                              int Ndim, int act, void* scratch, int64_t scratch_bytes, int nodes, int replays,
                                              int dependent, float* us_out, void* stream) {
   if (!h || !us_out || nodes < 1 || replays < 1) return -1;
-  h->debug_reps = replays; h->debug_graph_nodes = nodes; h->debug_graph_dependent = dependent != 0;
-  const int rc = sqair_linear_test(h, x, wmat, b, y, M, Kdim, Ndim, act, scratch, scratch_bytes, stream);
-  h->debug_reps = 0; h->debug_graph_nodes = 0;
-  *us_out = h->debug_us;
-  return rc;
+  return sq_linear_test(h, x, wmat, b, y, M, Kdim, Ndim, act, scratch, scratch_bytes, LinearTiming{replays, nodes, dependent != 0},
+                        us_out, stream);
 }
 
 extern "C" int sqair_gru_test(SqairHandle* h, const float* x, const float* hstate, const float* gru_flat, float* h_out,

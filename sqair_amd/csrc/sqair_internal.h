@@ -59,12 +59,8 @@ struct SqairHandle {
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;
   int graph_nodes = 0;
-  int debug_reps = 0;       // sqair_debug_linear_time
-  int debug_graph_nodes = 0;           // sqair_debug_linear_graph_time: launches per captured graph
-  bool debug_graph_dependent = false;  // ... chained through two buffers (K == N) instead of repeated
   bool dense_log_on = false;           // sqair_debug_dense_log: {layer id, rows, K (padded to 16 per segment), N} of every dense launch
   std::vector<int> dense_log;          // of the passes issued while it was on (host side only: nothing changes on the device)
-  float debug_us = 0.0f;
   bool opt_what_fusion = true;  // sqair_set_option("what_fusion"): the what sample of a slot inside the layer that produces its operands (bit-identical)
   bool opt_specialised = true;  // sqair_set_option("specialised"): the slot loop's per-row kernels in their instantiations for the shipped dimensions (bit-identical)
   int opt_specialised_mask = 3;    // sqair_set_option("specialised_mask"): which of them (SPEC_* bits, sqair_glue.h); a measurement aid
@@ -230,34 +226,36 @@ Workspace sq_carve(const SqairHandle* h, int T, int B, float* base, bool train);
 
 // ---- carried model state (sqair_state.hip) ----
 int64_t sq_state_row_floats(const SqairHandle* h);   // floats of one particle row of the state blob
-// The carried-state settings of one pass, resolved once: the handle's (sqair_set_state / sqair_set_smc: inference passes) or
-// a carried training call's (SqairCarry).  `fresh`: k_state_import records each row's fresh / imported flag for the backward.
+// The carried-state settings of one pass, resolved once per call and passed by value: the handle's (sq_resolve_pass; all off for
+// a training pass) or a carried training call's (sq_carry_state).  The pass reads these, never the handle's registration fields,
+// and nothing between resolution and return writes those.  `fresh`: k_state_import records each row's fresh / imported flag for
+// the backward.  lay_on and score_on are only ever set with est_on: whoever clears est_on clears them explicitly with it.
 struct SqStateRes {
   bool on;
   const void* in; void* out; const int32_t* src;
   bool fresh;
   bool smc_on; SqairSmc smc;
   bool hist_on = false;   // (the handle's inference passes only: a carried training call never pushes)
-  const int32_t* observed = nullptr;   // (the same: the handle's device mask of sqair_set_observed, or NULL)
-  bool est_on = false;    // (the same: a carried training call never estimates)
+  const int32_t* observed = nullptr;   // (the handle's device mask of sqair_set_observed, a masked carried chunk's own, or NULL)
+  bool est_on = false;    // (the handle's inference passes only: a carried training call never estimates)
   bool lay_on = false;    // (the same; only ever with est_on)
   bool score_on = false;  // (the same; only ever with est_on)
 };
-SQ_LOCAL SqStateRes sq_handle_state(const SqairHandle* h);
+// The refusals of a pass on the handle's settings -- observed mask, state, SMC, history, estimate, in this order (-1 + error text,
+// before any HIP call) -- then the settings in *st.  The only place that fixes the history ring's T: a refused call changes nothing.
+SQ_LOCAL int sq_resolve_pass(SqairHandle* h, bool train, int T, int B, int t_offset, const SqairOutputs* out, SqStateRes* st);
+// `st` for a pass that changes nothing outside its workspace and outputs (a capture's eager pre-pass): what it reads stays (the rows
+// imported through the map, the mask), what it writes goes (export, history push, estimate, layers, score, resampler).
+SQ_LOCAL SqStateRes sq_without_effects(SqStateRes st);
 SQ_LOCAL SqStateRes sq_carry_state(const SqairCarry* c);
-SQ_LOCAL int sq_smc_refusal(SqairHandle* h, const SqairOutputs* outp);   // -1 + error text: a pass with SMC on that does not bind the log weights
 SQ_LOCAL StateArgs sq_state_args(const SqairHandle* h, const SqStateRes& st, int R, float* rec, float* temporal, float* prior, float* last_id,
                                  int* t_row, float* fresh, int t0);
-// track history: -1 + error text for a pass with history on that the ring rules out (host only; fixes the ring's T on the first
-// pass); the push's arguments for a pass of T frames
-SQ_LOCAL int sq_history_refusal(SqairHandle* h, int T, int B, const SqairOutputs* outp);
 // missing-frame steps: -1 + error text for a training call, or a pass of another T, while a mask is set (host only)
 SQ_LOCAL int sq_observed_refusal(SqairHandle* h, bool train, int T);
+// track history: the push's arguments for a pass of T frames
 SQ_LOCAL HistPushArgs sq_history_push_args(const SqairHandle* h, const SqStateRes& st, const SqairOutputs& out, const int* t_row, int T, int B);
 SQ_LOCAL SmcArgs sq_smc_args(const SqairSmc& m, const float* lw, const int32_t* t_row, int T, int B, int K);
-// lane estimates: -1 + error text for a pass with the estimate on that it rules out (host only); the kernel's arguments for a pass
-// of T frames over the merged records `rec` [T][R][N][rec::W]
-SQ_LOCAL int sq_estimate_refusal(SqairHandle* h, int T, const SqairOutputs* outp);
+// lane estimates: the kernel's arguments for a pass of T frames over the merged records `rec` [T][R][N][rec::W]
 SQ_LOCAL LaneEstArgs sq_estimate_args(const SqairHandle* h, const float* rec, const SqairOutputs& out, int T, int B);
 // object layers: the kernel's arguments for a pass of T frames over the merged records `rec` and the decoded glimpses `glimpse`
 // [T][R][N][G*G] (a pass of another T is the estimate's to refuse: the layers are only ever registered for the estimate's T)

@@ -1,8 +1,8 @@
 // libsqair_hip.so -- the carried model state on the native side of the C ABI (include/sqair_hip.h): the state blob and its
-// registration on a handle (sqair_set_state / sqair_set_smc / sqair_set_history / sqair_set_observed), the refusals of the passes and carried training calls a state rules
-// out, the settings one pass resolves them to (SqStateRes: the handle's, or a SqairCarry's), and the forecast that rolls the prior
-// forward from a state (sqair_forecast).  Host code only; the pass that imports / exports / resamples the state is
-// sq_forward_impl (sqair_api.hip), the kernels live in sqair_glue.hip and sqair_lane.hip.
+// registration on a handle (sqair_set_state / _smc / _history / _observed / _estimate / _layers / _score), the one resolution of a call
+// (sq_resolve_pass: the refusals of a pass, each free of side effects, then the handle's settings by value as an SqStateRes;
+// sq_carry_state: a SqairCarry's), and the forecast that rolls the prior forward from a state (sqair_forecast).  Host code only; the
+// pass, sq_forward_impl (sqair_api.hip), reads the SqStateRes it is given; the kernels live in sqair_glue.hip and sqair_lane.hip.
 #include "sqair_internal.h"
 #include "sqair_chain.h"
 
@@ -14,6 +14,15 @@ int64_t sq_state_row_floats(const SqairHandle* h) {
   const int64_t N = c.n_steps_per_image, nh = c.n_hidden;
   const int64_t snh = c.time_cell == CELL_LSTM ? 2 * nh : nh, psnh = c.prior_cell == CELL_LSTM ? 2 * nh : nh;
   return (N * (rec::W + snh + psnh) + 2 + 3) / 4 * 4;
+}
+// -1 + "<who>B = ... but the state ..." when a call's B is not the registered state's; likewise T against the estimate's
+static int sq_state_b_mismatch(SqairHandle* h, const std::string& who, int B) {
+  if (B == h->state_B) return 0;
+  return sq_no(h, who + "B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
+}
+static int sq_estimate_t_mismatch(SqairHandle* h, const std::string& who, int T) {
+  if (T == h->est_T) return 0;
+  return sq_no(h, who + "T = " + std::to_string(T) + " but the estimate set by sqair_set_estimate is for T = " + std::to_string(h->est_T));
 }
 static void sq_observed_off(SqairHandle* h) { h->observed = nullptr; h->observed_T = 0; }
 static void sq_layers_off(SqairHandle* h) { h->lay_on = false; h->lay = SqairLaneLayers{}; }
@@ -64,8 +73,7 @@ extern "C" int sqair_set_observed(SqairHandle* h, const int32_t* observed, int T
   if (h->cfg.sample_from_prior) return sq_no(h, "sqair_set_observed: not with sample_from_prior (generation decides per frame on the host)");
   if (!h->state_on) return sq_no(h, "sqair_set_observed: needs a carried state (sqair_set_state): an unobserved lane coasts on the state it carries");
   if (T < 1) return sq_no(h, "sqair_set_observed: T must be >= 1");
-  if (B != h->state_B)
-    return sq_no(h, "sqair_set_observed: B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
+  if (sq_state_b_mismatch(h, "sqair_set_observed: ", B) != 0) return -1;
   h->observed = observed; h->observed_T = T;
   return 0;
 }
@@ -101,13 +109,12 @@ extern "C" int sqair_set_smc(SqairHandle* h, const SqairSmc* smc, int B) {
     return sq_no(h, "sqair_set_smc: needs a carried state with state_in and a source map (sqair_set_state) to resample");
   if (smc->src_rows != h->state_src) return sq_no(h, "sqair_set_smc: src_rows must be the source map given to sqair_set_state");
   if (sq_smc_fields(h, "sqair_set_smc: ", *smc, false, true, "log_w, log_z, log_evidence, ess and resampled") != 0) return -1;
-  if (B != h->state_B)
-    return sq_no(h, "sqair_set_smc: B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
+  if (sq_state_b_mismatch(h, "sqair_set_smc: ", B) != 0) return -1;
   h->smc_on = true; h->smc = *smc;
   return 0;
 }
 // the refusal of a pass with SMC on (host only: before any HIP call)
-int sq_smc_refusal(SqairHandle* h, const SqairOutputs* outp) {
+static int sq_smc_refusal(SqairHandle* h, const SqairOutputs* outp) {
   if (!h->smc_on || (outp && outp->log_weights_per_timestep)) return 0;
   return sq_no(h, "SMC (sqair_set_smc) resamples on log_weights_per_timestep: a pass with SMC on must bind that output");
 }
@@ -158,8 +165,7 @@ extern "C" int sqair_set_estimate(SqairHandle* h, const SqairLaneEstimate* est, 
   const std::string who = "sqair_set_estimate: ";
   if (!h->state_on) return sq_no(h, who + "needs a carried state (sqair_set_state): the estimate weighs the rows it carries");
   if (T < 1) return sq_no(h, who + "T must be >= 1");
-  if (B != h->state_B)
-    return sq_no(h, who + "B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
+  if (sq_state_b_mismatch(h, who, B) != 0) return -1;
   if (sq_estimate_fields(h, who, *est) != 0 || sq_estimate_smc_mismatch(h, who, *est) != 0) return -1;
   if (T != h->est_T) sq_layers_off(h);   // (the layers' outputs were sized for the other T)
   if (T != h->est_T || !sq_estimate_scorable(*est)) sq_score_off(h);   // (and the score's; it reads these four outputs)
@@ -167,7 +173,7 @@ extern "C" int sqair_set_estimate(SqairHandle* h, const SqairLaneEstimate* est, 
   return 0;
 }
 // the refusal of a pass with the estimate on (host only: before any HIP call)
-int sq_estimate_refusal(SqairHandle* h, int T, const SqairOutputs* outp) {
+static int sq_estimate_refusal(SqairHandle* h, int T, const SqairOutputs* outp) {
   if (!h->state_on || !h->est_on) return 0;
   const std::string who = "lane estimate (sqair_set_estimate): ";
   if (T != h->est_T)
@@ -228,10 +234,8 @@ extern "C" int sqair_set_layers(SqairHandle* h, const SqairLaneLayers* lay, int 
   const std::string who = "sqair_set_layers: ";
   if (!h->state_on || !h->est_on)
     return sq_no(h, who + "needs an estimate (sqair_set_estimate): the layers weigh and associate the particles as it does");
-  if (T != h->est_T)
-    return sq_no(h, who + "T = " + std::to_string(T) + " but the estimate set by sqair_set_estimate is for T = " + std::to_string(h->est_T));
-  if (B != h->state_B)
-    return sq_no(h, who + "B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
+  if (sq_estimate_t_mismatch(h, who, T) != 0) return -1;
+  if (sq_state_b_mismatch(h, who, B) != 0) return -1;
   if (sq_layers_fields(h, who, *lay) != 0) return -1;
   h->lay_on = true; h->lay = *lay;
   return 0;
@@ -286,10 +290,8 @@ extern "C" int sqair_set_score(SqairHandle* h, const SqairLaneScore* score, int 
     return sq_no(h, who + "needs an estimate (sqair_set_estimate): the score reads the lane answer it writes");
   if (!sq_estimate_scorable(h->est))
     return sq_no(h, who + "the estimate (sqair_set_estimate) must bind box, presence, obj_id and map_count: the score reads them");
-  if (T != h->est_T)
-    return sq_no(h, who + "T = " + std::to_string(T) + " but the estimate set by sqair_set_estimate is for T = " + std::to_string(h->est_T));
-  if (B != h->state_B)
-    return sq_no(h, who + "B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
+  if (sq_estimate_t_mismatch(h, who, T) != 0) return -1;
+  if (sq_state_b_mismatch(h, who, B) != 0) return -1;
   if (sq_score_fields(h, who, *score) != 0) return -1;
   h->score_on = true; h->score = *score;
   return 0;
@@ -345,16 +347,9 @@ int sq_state_refusal(SqairHandle* h, bool train, int B, int t_offset) {
   if (h->cfg.sample_from_prior) return sq_no(h, "a carried state (sqair_set_state) does not combine with sample_from_prior");
   if (h->state_in && t_offset != 0)
     return sq_no(h, "with state_in set (sqair_set_state) t_offset must be 0: the state's frame counter is the time index");
-  if (B != h->state_B)
-    return sq_no(h, "B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
-  return 0;
+  return sq_state_b_mismatch(h, "", B);
 }
 
-SqStateRes sq_handle_state(const SqairHandle* h) {
-  return SqStateRes{h->state_on, h->state_in, h->state_out, h->state_src, false, h->smc_on, h->smc, h->state_on && h->hist_on,
-                    h->state_on ? h->observed : nullptr, h->state_on && h->est_on, h->state_on && h->est_on && h->lay_on,
-                    h->state_on && h->est_on && h->score_on};
-}
 SqStateRes sq_carry_state(const SqairCarry* c) {
   return SqStateRes{true, c->state_in, c->state_out, c->src_rows, true, c->smc != nullptr, c->smc ? *c->smc : SqairSmc{}};
 }
@@ -417,9 +412,8 @@ extern "C" int sqair_set_history(SqairHandle* h, void* ring, int64_t ring_bytes,
   h->hist_on = true; h->hist_ring = ring; h->hist_bytes = ring_bytes; h->hist_L = L; h->hist_T = 0; h->hist_fields = fields;
   return 0;
 }
-// the refusal of a pass with history on (host only: before any HIP call).  The first pass fixes the T the ring's slots are laid
-// out for.
-int sq_history_refusal(SqairHandle* h, int T, int B, const SqairOutputs* outp) {
+// the refusal of a pass with history on (host only: before any HIP call; sq_resolve_pass fixes the ring's T)
+static int sq_history_refusal(SqairHandle* h, int T, int B, const SqairOutputs* outp) {
   if (!h->state_on || !h->hist_on) return 0;
   if (T < 1 || B != h->state_B) return 0;   // (the pass's own checks refuse these)
   if (h->hist_T != 0 && T != h->hist_T)
@@ -434,8 +428,22 @@ int sq_history_refusal(SqairHandle* h, int T, int B, const SqairOutputs* outp) {
       ((f & SQAIR_HIST_LOG_W) && !outp->log_weights_per_timestep))
     return sq_no(h, "history (sqair_set_history) records the pass's outputs: a pass with history on must bind where, presence, obj_id and "
                     "the optional fields it was set with (what, log_weights_per_timestep)");
-  h->hist_T = T;
   return 0;
+}
+int sq_resolve_pass(SqairHandle* h, bool train, int T, int B, int t_offset, const SqairOutputs* out, SqStateRes* st) {
+  if (sq_observed_refusal(h, train, T) != 0 || sq_state_refusal(h, train, B, t_offset) != 0 || sq_smc_refusal(h, out) != 0 ||
+      sq_history_refusal(h, T, B, out) != 0 || sq_estimate_refusal(h, T, out) != 0)
+    return -1;
+  const bool on = h->state_on, est = on && h->est_on;
+  *st = SqStateRes{on, h->state_in, h->state_out, h->state_src, false, h->smc_on, h->smc, on && h->hist_on,
+                   on ? h->observed : nullptr, est, est && h->lay_on, est && h->score_on};
+  if (st->hist_on && T >= 1) h->hist_T = T;   // (T < 1 is the pass's own to refuse)
+  return 0;
+}
+SqStateRes sq_without_effects(SqStateRes st) {
+  st.out = nullptr; st.smc_on = false; st.smc = SqairSmc{};
+  st.hist_on = st.est_on = st.lay_on = st.score_on = false;
+  return st;
 }
 HistPushArgs sq_history_push_args(const SqairHandle* h, const SqStateRes& st, const SqairOutputs& out, const int* t_row, int T, int B) {
   HistPushArgs a; memset(&a, 0, sizeof(a));
@@ -643,8 +651,7 @@ static int sq_forecast_impl(SqairHandle* h, const bool fan, const float* flat_pa
   const std::string fn = fan ? "sqair_forecast_fan" : "sqair_forecast", who = fn + ": ";
   if (c.sample_from_prior) return sq_no(h, who + "not with sample_from_prior (the forecast is the generation mode, from a carried state)");
   if (!h->state_on || !h->state_in) return sq_no(h, who + "needs a carried state with state_in (sqair_set_state) to start from");
-  if (B != h->state_B)
-    return sq_no(h, who + "B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
+  if (sq_state_b_mismatch(h, who, B) != 0) return -1;
   if (F < 1) return sq_no(h, who + "F must be >= 1");
   if (!noise) return sq_no(h, who + "noise must not be NULL");
   if (!flat_params || !packed_v || !outp || !workspace) return sq_no(h, who + "null parameters, packed buffer, outputs or workspace");

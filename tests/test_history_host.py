@@ -145,6 +145,27 @@ def test_pass_time_refusals_before_any_hip_call():
         lib.sqair_destroy(h)
 
 
+def test_a_refused_pass_leaves_the_handle_unchanged():
+    """A pass the history would take and the estimate refuses must not fix the ring's frames per pass: the next pass, of the
+    estimate's T, gets past every refusal to the pass's own argument check."""
+    lib, h = _handle(k_particles=2, n_steps_per_image=3)
+    try:
+        B = 4
+        _state(lib, h, B)
+        assert lib.sqair_set_history(h, DUMMY, BIG, 8, ALL) == 0
+        est = _capi.SqairLaneEstimate(iou_min=0.5, log_w=0x2000, best_row=0x3000)
+        assert lib.sqair_set_estimate(h, C.byref(est), 1, B) == 0
+        every = [n for n, _ in _capi.SqairOutputs._fields_]
+        assert lib.sqair_forward(*_fwd_args(h, B, T=3, bind=every)) == -1
+        assert "sqair_set_estimate" in _err(lib, h) and "registered for passes of T = 1" in _err(lib, h)
+        args = _fwd_args(h, B, T=1, bind=every)
+        assert lib.sqair_forward(*(args[:9] + (None,) + args[10:])) == -1      # (a NULL workspace)
+        assert _err(lib, h) == "sqair_forward: null argument or bad T/B", _err(lib, h)
+        assert "ring" not in _err(lib, h)
+    finally:
+        lib.sqair_destroy(h)
+
+
 def test_training_passes_stay_refused_with_a_history_set():
     lib, h = _handle(k_particles=2, n_steps_per_image=3)
     try:
