@@ -1081,6 +1081,102 @@ typedef struct SqairDxTest {
 } SqairDxTest;
 int sqair_linear_dx_test(SqairHandle* h, const SqairDxTest* t, void* stream);
 
+/* ---- the element-wise adjoints of the slot loop, one launch each (test helpers) -----------------------------------------------
+ * The kernels that sit between the dX GEMMs in the reverse sweep of sqair_backward, on caller-owned device buffers that reach the
+ * pass's own launchers UNCHANGED.  The dimensions (R = B * k_particles rows, N slots, n_what, n_hidden, the frame, the glimpse), the
+ * record layout and every parameter offset (steps predictors, scale offsets, Cholesky factor) are the handle's, derived by the
+ * expressions the pass uses; the caller chooses mode, slot, B, the pitches and which optional outputs exist.  `flat` / `flat_grad`
+ * are parameter buffers in the kernels' own layout (sqair_debug_padded_count floats: the caller's layout unless n_hidden is
+ * padded); records are [R][N][W] with the columns sqair_compact_test_layout reports; noise is one frame's [R][2][N][4 + n_what + 1]
+ * (phase 0 propagation, 1 discovery).  A refusal (-1: a NULL required pointer, a slot outside [0, N), a pitch below the width, a
+ * frame that cannot be trained) carries the entry's name in sqair_last_error and launches nothing; otherwise the launcher's code,
+ * after a stream synchronise.
+ *
+ * sqair_slot_tail_bwd_test (k_slot_tail_bwd): presence logit -> steps predictor -> `what` sample; reads d_rec_new[LOGIT, WHAT,
+ *   WHAT_LOC, WHAT_SCALE] of the slot, the previous presence (discovery: the record of slot - 1, 1 for slot 0; propagation:
+ *   rec_prev), s1h [R][n_hidden / 2] the saved hidden activations, enc [R][2 n_what] = (loc, scale) of the glimpse encoder, and in
+ *   propagation hraw [R][5 n_what] (what-head loc, raw scale, three raw gates) and rec_prev[WHAT].  Writes d_s1pre (and the copy
+ *   d_s1pre2, optional), d_raw_out [R][dr_ld] (one float per row), d_rec_new[WHAT] (the sample's total gradient), d_enc [R][2 n_what]
+ *   (enc_pre 1, discovery: the scale half as the gradient of the head's pre-activation), and in propagation d_hraw [R][5 n_what] and
+ *   d_rec_prev[WHAT] += .  rec_prev, d_rec_prev, hraw and d_hraw are required in propagation only. */
+typedef struct SqairSlotTailBwdTest {
+  int32_t is_disc, slot, B, enc_pre;
+  const float* rec_prev; const float* rec_new;
+  float* d_rec_new; float* d_rec_prev;
+  const float* s1h; int32_t s1h_ld;
+  const float* hraw; int32_t h_ld;
+  const float* enc; int32_t enc_ld;
+  const float* noise;
+  const float* flat;
+  float* d_s1pre; int32_t ds_ld;
+  float* d_s1pre2; int32_t ds2_ld;
+  float* d_raw_out; int32_t dr_ld;
+  float* d_enc; int32_t de_ld;
+  float* d_hraw; int32_t dh_ld;
+} SqairSlotTailBwdTest;
+int sqair_slot_tail_bwd_test(SqairHandle* h, const SqairSlotTailBwdTest* t, void* stream);
+
+/* sqair_crop_chain_bwd_test (k_crop_chain_bwd): d glimpse -> d where -> the where sample's adjoint.  mode 1 (crop #1 of
+ *   propagation): ALL N slots in one launch (`slot` ignored), where logits = rec_prev[WHERE] + 0.1 wb; row r, slot k reads g_out row
+ *   r * g_row_mul + g_row_add + k and mask row r * mask_row_mul + mask_row_add + k (both multipliers >= N); writes d_wb
+ *   [R * N][wb_ld] and d_rec_prev[WHERE] += .  mode 2 / 3 (crop #2 of propagation / discovery): one slot, where = rec_new[WHERE];
+ *   reads d_rec_new[WHERE, WHERE_LOC, WHERE_SCALE], tp [R][8] the saved transform output, the phase's noise; writes d_tp [R][8],
+ *   d_rec_new[WHERE] (the sample's total gradient) and, mode 2, d_rec_prev[WHERE] += .  mask (optional, [rows][G * G]) multiplies the
+ *   glimpse; then d_mask += , and with mask_dact 1 the sum is written times mask (1 - mask).  d_t2 (optional, modes 2 / 3): the
+ *   adjoint of the transform's output layer in the same launch, d_t2[r][j] = (sum_o d_tp[r][o] w3[j][o]) elu'(t2[r][j]) with w3
+ *   [n_hidden][8] and t2 the saved hidden activations.  img: [B] frames, each padded with zeros to a multiple of 4 floats. */
+typedef struct SqairCropChainBwdTest {
+  int32_t mode, slot, B, mask_dact;
+  const float* img;
+  const float* rec_prev; const float* rec_new;
+  float* d_rec_prev; float* d_rec_new;
+  const float* wb; int32_t wb_ld;
+  float* d_wb;
+  const float* mask; int32_t mask_row_mul, mask_row_add;
+  float* d_mask;
+  const float* g_out; int32_t g_row_mul, g_row_add;
+  const float* tp; int32_t tp_ld;
+  float* d_tp; int32_t dtp_ld;
+  const float* noise;
+  const float* flat;
+  const float* w3;
+  const float* t2; int32_t t2_ld;
+  float* d_t2; int32_t dt2_ld;
+} SqairCropChainBwdTest;
+int sqair_crop_chain_bwd_test(SqairHandle* h, const SqairCropChainBwdTest* t, void* stream);
+
+/* sqair_where_param_grads_test (k_where_param_grads): the batched reduction over all T * R * N (frame, row, slot) uses into the ten
+ *   entries of prop.cholesky_scale and the two transform.scale_offset scalars, ADDED onto flat_grad.  d_tp [2 phases][T * R * N][tp_ld]
+ *   (columns 4:8 are summed); d_rec_p / rec_p [T][R][N][W] (d where total, where_scale); noise [T][R][2][N][4 + n_what + 1]. */
+typedef struct SqairWhereParamGradsTest {
+  int32_t T, B;
+  const float* d_tp; int32_t tp_ld;
+  const float* d_rec_p; const float* rec_p;
+  const float* noise;
+  float* flat_grad;
+} SqairWhereParamGradsTest;
+int sqair_where_param_grads_test(SqairHandle* h, const SqairWhereParamGradsTest* t, void* stream);
+
+/* sqair_gru_gates_bwd_test (k_gru_bwd_a, then k_gru_bwd_b): the gate adjoints of the slot RNN's GRU over `rows` rows of n_hidden
+ *   units.  Stage A from d_hn = d h': dpre1[:, 0:nh] = d(z pre-activation), dpre1[:, 2nh:3nh] = d(candidate pre-activation), d_h (+)=
+ *   the direct part (accumulate_dh 1 adds); dup_z (optional) receives the first at column 0 and the second at dup_h_off (>= 0).
+ *   Stage B from d_rh = d(r h): dpre1[:, nh:2nh] = d(r pre-activation) (copy: dup_r, optional), d_h += d_rh r.  z, r, hc: the saved
+ *   gate OUTPUTS; hprev with h_ld 0 is one broadcast row. */
+typedef struct SqairGruGatesBwdTest {
+  int32_t rows, accumulate_dh;
+  const float* d_hn; int32_t dhn_ld;
+  const float* z; int32_t z_ld;
+  const float* r; int32_t r_ld;
+  const float* hc; int32_t hc_ld;
+  const float* hprev; int32_t h_ld;
+  const float* d_rh; int32_t drh_ld;
+  float* dpre1; int32_t dp_ld;
+  float* d_h; int32_t dh_ld;
+  float* dup_z; int32_t dupz_ld, dup_h_off;
+  float* dup_r; int32_t dupr_ld;
+} SqairGruGatesBwdTest;
+int sqair_gru_gates_bwd_test(SqairHandle* h, const SqairGruGatesBwdTest* t, void* stream);
+
 /* Which kernel family the two dense launchers chose, counted on the host per process (launches issued or captured so far), at the
  * point of the choice: out[0:n] receives the first n of the SQAIR_DENSE_ROUTES counts below, the return value is their number.
  *   forward (sq_launch_linear):  0 split-K (k_linear) | 1 32 x 32 tiles (k_linear_t2) | 2 k_linear_rows | 3 k_linear_mt |

@@ -207,6 +207,38 @@ class SqairDxTest(C.Structure):
                 ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64)]
 
 
+def _fields(spec):
+    """'p name' = device address, 'i name' = int32; in the header's order."""
+    return [(s.split()[1], C.c_void_p if s.split()[0] == "p" else C.c_int32) for s in spec]
+
+
+class SqairSlotTailBwdTest(C.Structure):
+    """One launch of the slot-tail adjoint (include/sqair_hip.h: sqair_slot_tail_bwd_test); device addresses, handed on unchanged."""
+    _fields_ = _fields(["i is_disc", "i slot", "i B", "i enc_pre", "p rec_prev", "p rec_new", "p d_rec_new", "p d_rec_prev", "p s1h",
+                        "i s1h_ld", "p hraw", "i h_ld", "p enc", "i enc_ld", "p noise", "p flat", "p d_s1pre", "i ds_ld", "p d_s1pre2",
+                        "i ds2_ld", "p d_raw_out", "i dr_ld", "p d_enc", "i de_ld", "p d_hraw", "i dh_ld"])
+
+
+class SqairCropChainBwdTest(C.Structure):
+    """One launch of the crop adjoint of the recurrence (include/sqair_hip.h: sqair_crop_chain_bwd_test)."""
+    _fields_ = _fields(["i mode", "i slot", "i B", "i mask_dact", "p img", "p rec_prev", "p rec_new", "p d_rec_prev", "p d_rec_new", "p wb",
+                        "i wb_ld", "p d_wb", "p mask", "i mask_row_mul", "i mask_row_add", "p d_mask", "p g_out", "i g_row_mul",
+                        "i g_row_add", "p tp", "i tp_ld", "p d_tp", "i dtp_ld", "p noise", "p flat", "p w3", "p t2", "i t2_ld", "p d_t2",
+                        "i dt2_ld"])
+
+
+class SqairWhereParamGradsTest(C.Structure):
+    """The batched where-parameter reduction (include/sqair_hip.h: sqair_where_param_grads_test)."""
+    _fields_ = _fields(["i T", "i B", "p d_tp", "i tp_ld", "p d_rec_p", "p rec_p", "p noise", "p flat_grad"])
+
+
+class SqairGruGatesBwdTest(C.Structure):
+    """Both stages of the slot RNN's GRU gate adjoints (include/sqair_hip.h: sqair_gru_gates_bwd_test)."""
+    _fields_ = _fields(["i rows", "i accumulate_dh", "p d_hn", "i dhn_ld", "p z", "i z_ld", "p r", "i r_ld", "p hc", "i hc_ld", "p hprev",
+                        "i h_ld", "p d_rh", "i drh_ld", "p dpre1", "i dp_ld", "p d_h", "i dh_ld", "p dup_z", "i dupz_ld", "i dup_h_off",
+                        "p dup_r", "i dupr_ld"])
+
+
 # sqair_debug_dense_routes: the families of the two dense launchers, in the order include/sqair_hip.h documents
 DENSE_ROUTES = ("fwd_splitk", "fwd_t2", "fwd_rows", "fwd_mt", "fwd_lds", "fwd_big_2x2", "fwd_big_3x2", "fwd_big_3x3", "fwd_big_4x2",
                 "dx_nch1", "dx_nch2", "dx_nch3", "dx_nch4", "dx_nch5", "dx_nch6", "dx_nch7", "dx_nch8", "dx_nch9", "dx_nch12", "dx_nch18",
@@ -330,6 +362,10 @@ _PROTOS = {
     "sqair_linear_bwd_test": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 4 + [C.c_void_p, C.c_int64, C.c_void_p]),
     "sqair_linear_contract_test": (C.c_int, [C.c_void_p, C.POINTER(SqairDenseContract), C.c_void_p]),
     "sqair_linear_dx_test": (C.c_int, [C.c_void_p, C.POINTER(SqairDxTest), C.c_void_p]),
+    "sqair_slot_tail_bwd_test": (C.c_int, [C.c_void_p, C.POINTER(SqairSlotTailBwdTest), C.c_void_p]),
+    "sqair_crop_chain_bwd_test": (C.c_int, [C.c_void_p, C.POINTER(SqairCropChainBwdTest), C.c_void_p]),
+    "sqair_where_param_grads_test": (C.c_int, [C.c_void_p, C.POINTER(SqairWhereParamGradsTest), C.c_void_p]),
+    "sqair_gru_gates_bwd_test": (C.c_int, [C.c_void_p, C.POINTER(SqairGruGatesBwdTest), C.c_void_p]),
     "sqair_debug_dense_routes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
     "sqair_debug_linear_time": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_void_p]),

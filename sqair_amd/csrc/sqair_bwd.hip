@@ -1776,7 +1776,7 @@ __global__ __launch_bounds__(256) void k_slot_tail_bwd(const TailBwdArgs a, cons
     w2_ = a.flat[a.w2_off + tid];
   }
   {
-    const int sh = 31 - __clz(nsp);   // nsp = nh / 2 is 64 or 128 (sqair_create)
+    const int sh = 31 - __clz(nsp);   // nsp = nh / 2 is 64, 128 or -- wide build, n_hidden 512 -- 256: a power of two (sqair_create)
 #pragma unroll
     for (int q = 0; q < WU; ++q) {
       const int e = 4 * (tid + 256 * q);
@@ -1938,7 +1938,10 @@ __global__ __launch_bounds__(256) void k_crop_chain_bwd(const CropChainBwdArgs a
 #pragma unroll
     for (int q = 0; q < 4; ++q)
       if (tid + 256 * q < n4) d4[tid + 256 * q] = fv[q];
-    for (int base = 1024; base < n4; base += 1024) {   // frames beyond 4096 pixels
+    // frames beyond 4096 pixels.  NOT REACHED as launched: sq_launch_crop_chain_bwd gives this instantiation frames of at most
+    // SQ_CROP_STAGE_MAX_PIXELS = 4096 pixels, so n4 = P4 / 4 <= 1024 and the loop's condition is false on entry; larger frames
+    // take the LDS-DMA instantiation.  Kept: it is what makes the instantiation correct on its own
+    for (int base = 1024; base < n4; base += 1024) {
       f32x4_b v[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) v[q] = s4[min(base + tid + 256 * q, n4 - 1)];

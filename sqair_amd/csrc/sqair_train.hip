@@ -301,6 +301,26 @@ struct SlotAdjPhase {
   bool d_r_every_slot;                 // d_r[k & 1] holds a contribution in the last slot too (propagation: the temporal cell's gate dX)
 };
 
+// The host expressions of the slot loop's element-wise adjoint launches that the pass shares with their unit entries (sqair_*_bwd_test
+// at the end of this file): both call these, so an entry cannot drift from the pass.
+// Dims of a training pass over B sequences: frames whose H * W is not a multiple of 4 are read from a zero-padded copy
+static Dims sq_train_dims(const SqairHandle* h, int B) {
+  Dims d = make_dims(h->cfg, B);
+  const int P_ = h->cfg.img_h * h->cfg.img_w;
+  if ((P_ & 3) != 0) d.P4 = (P_ + 3) / 4 * 4;
+  return d;
+}
+// the steps predictor a slot tail reads: output layer {w, b} and the first `what` row of its hidden layer ([in, nh/2] layout;
+// inputs [hidden nh | what] in discovery, [hidden nh | temporal nh | what] in propagation)
+static void sq_tail_param_offsets(const SqairHandle* h, bool is_disc, TailBwdArgs* ta) {
+  const int nh = h->cfg.n_hidden, nsp = nh / 2;
+  ta->w2_off = is_disc ? h->po.disc_steps_l1_w : h->po.prop_steps_l1_w;
+  ta->b2_off = is_disc ? h->po.disc_steps_l1_b : h->po.prop_steps_l1_b;
+  ta->wwhat_off = is_disc ? (int)P(h, "disc.steps.l0.w") + nh * nsp : (int)P(h, "prop.steps.l0.w") + 2 * nh * nsp;
+}
+// slots one crop-adjoint launch covers: crop #1 takes the frame's N slots at once (grid.y), the slot loops one
+static int sq_crop_bwd_slots(int mode, const Dims& d) { return mode == CROP_PROP1 ? d.N : 1; }
+
 // carried: after sqair_forward_train_carry -- each row's step-prior time is its counter plus the frame (w.t_row), and the frame-0
 // initial-state gradients take only the rows that started fresh (w.fresh); the imported rows are constants.
 // observed: the device mask [T][B] of a masked carried chunk (after sqair_forward_train_carry_masked with the same mask), or NULL.
@@ -322,7 +342,7 @@ static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, c
   const int nh = c.n_hidden, nw = c.n_what, N = c.n_steps_per_image, K = c.k_particles;
   const int R = B * K, M = R * N, MT = M * T, G2 = c.glimpse_size * c.glimpse_size, P_ = c.img_h * c.img_w;
   const int nzw = 4 + nw + 1, RW = rec::W, nsp = nh / 2;
-  Dims d = make_dims(c, B);
+  const Dims d = sq_train_dims(h, B);
   const int snh = d.snh, gw = sq_gate_width(c, c.time_cell), psnh = d.psnh, pgw = sq_gate_width(c, c.prior_cell);
   const int rw = sq_rnn_width(c);  // slot-RNN pre-activation width; d_pre columns [rnn rw | T1 nh | S1 nsp | GRU z, r]
   const POff po = h->po;
@@ -330,7 +350,7 @@ static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, c
   const BwdSpace b = carve_bwd(h, T, B, (float*)scratch);
   const PackedLayout pl = packed_layout(h);
   // (frames whose H * W is not a multiple of 4: the zero-padded copy the forward pass left in the training workspace)
-  if ((P_ & 3) != 0) { d.P4 = (P_ + 3) / 4 * 4; obs = w.obs_p; }
+  if ((P_ & 3) != 0) obs = w.obs_p;
   const int PL = d.P4;
   const int pre_ld = h->layers[L_PRE].nt * 16;
 
@@ -446,7 +466,7 @@ static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, c
       ca.slot = k; ca.img = img; ca.rec_prev = rec_prev; ca.rec_new = sp.rec; ca.d_rec_prev = d_rec_prev; ca.d_rec_new = sp.d_rec;
       ca.g_out = b.d_g; ca.g_row_mul = 1; ca.tp = cslotp(w.tp, TP_LD, t, sp.ph, k); ca.tp_ld = tpl; ca.d_tp = d_tp; ca.dtp_ld = tpl;
       ca.noise = nz; ca.flat = flat; ca.flat_grad = flat_grad; ca.w3 = sp.w3; ca.t2 = t2; ca.t2_ld = rl; ca.d_t2 = d_t2; ca.dt2_ld = rl;
-      CK(sq_launch_crop_chain_bwd(ca, po, d, 1, s));
+      CK(sq_launch_crop_chain_bwd(ca, po, d, sq_crop_bwd_slots(ca.mode, d), s));
       { Dx x(d_t2, rl); x.to(0, nh, d_t1, t1l).dact(t1, t1l, ACT_ELU).dup(d_pre_k ? d_pre_k + rw : nullptr, sp.d_pre_ld); CK(rundx(sp.t2, x, R)); }
       // d h_k = T1^T + what d_r[k & 1] holds (the next slot's RNN; in propagation also the temporal cell's gate GEMM)
       const bool d_r_in = k < N - 1 || sp.d_r_every_slot;
@@ -501,8 +521,8 @@ static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, c
         ta.is_disc = 1; ta.slot = j; ta.rec_prev = rec_prev; ta.rec_new = rec_d_t; ta.d_rec_new = d_rec_d_t;
         ta.d_rec_prev = d_rec_prev; ta.s1h = cslotp(w.s1h, S1_LD, t, 1, j); ta.s1h_ld = s1l; ta.enc = enc; ta.enc_ld = el;
         ta.noise = nz; ta.d_s1pre = d_t1 + nh; ta.ds_ld = t1l; ta.d_enc = d_enc3; ta.de_ld = el; ta.enc_pre = 1; ta.d_raw_out = slotp(b.d_raw, 1, t, 1, j); ta.dr_ld = N; ta.flat = flat;
-        ta.flat_grad = flat_grad; ta.w2_off = po.disc_steps_l1_w; ta.b2_off = po.disc_steps_l1_b;
-        ta.wwhat_off = (int)P(h, "disc.steps.l0.w") + nh * nsp;
+        ta.flat_grad = flat_grad;
+        sq_tail_param_offsets(h, true, &ta);
         CK(sq_launch_slot_tail_bwd(ta, d, s));
       }
       CropChainBwdArgs ca; memset(&ca, 0, sizeof(ca));
@@ -554,8 +574,8 @@ static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, c
         ta.hraw = cslotp(w.hraw, HRAW_LD, t, 0, k); ta.h_ld = hl; ta.enc = enc; ta.enc_ld = el; ta.noise = nz;
         ta.d_s1pre = d_t1 + nh; ta.ds_ld = t1l; ta.d_s1pre2 = d_pre_k + rw + nh; ta.ds2_ld = pre_rld;
         ta.d_enc = b.d_enc; ta.de_ld = ENC_LD; ta.d_hraw = d_hraw; ta.dh_ld = hl; ta.d_raw_out = slotp(b.d_raw, 1, t, 0, k); ta.dr_ld = N;
-        ta.flat = flat; ta.flat_grad = flat_grad; ta.w2_off = po.prop_steps_l1_w; ta.b2_off = po.prop_steps_l1_b;
-        ta.wwhat_off = (int)P(h, "prop.steps.l0.w") + 2 * nh * nsp;
+        ta.flat = flat; ta.flat_grad = flat_grad;
+        sq_tail_param_offsets(h, false, &ta);
         CK(sq_launch_slot_tail_bwd(ta, d, s));
       }
       // heads -> d tau'_k (the new HIDDEN state), + what the compaction sent back for this slot's new temporal state
@@ -625,7 +645,7 @@ static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, c
       ca.wb_ld = WB_LD; ca.d_wb = b.d_wb + (size_t)t * M * WB_LD; ca.mask = c.masked_glimpse ? mask : nullptr; ca.mask_row_mul = N;
       ca.d_mask = d_mask_t; ca.g_out = b.d_g1; ca.g_row_mul = N; ca.flat = flat; ca.flat_grad = flat_grad;
       ca.mask_dact = 1;  // the frame's last contribution to d mask: the sigmoid's adjoint rides on its write (d_mask_t IS d_maskpre)
-      CK(sq_launch_crop_chain_bwd(ca, po, d, N, s));
+      CK(sq_launch_crop_chain_bwd(ca, po, d, sq_crop_bwd_slots(ca.mode, d), s));
     }
     // ---- B^T. mask MLP and where-bias MLP
     {
@@ -915,6 +935,116 @@ extern "C" int sqair_compact_bwd_test(SqairHandle* h, const int32_t* src, const 
   ka.d_rec_p = d_rec_p; ka.d_rec_d = d_rec_d; ka.d_temporal_p = d_temporal_p; ka.d_prior_p = d_prior_p;
   ka.d_new_temporal = d_new_temporal; ka.d_new_prior = d_new_prior;
   sq_launch_compact_bwd(ka, h->po, d, s);
+  SQ_CHECK_HIP(hipGetLastError());
+  SQ_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The element-wise adjoints of the slot loop on raw device buffers (unit-test entries, tests/test_slot_adjoint_kernels.py): the
+// caller's pointers and pitches reach the launchers of the reverse sweep unchanged; Dims, POff and the parameter offsets are the
+// handle's, through the helpers sq_backward itself calls (sq_train_dims, sq_tail_param_offsets, sq_crop_bwd_slots).
+// ------------------------------------------------------------------------------------------------
+static int sq_refuse(SqairHandle* h, const char* who, const std::string& why) {
+  sq_set_error(h, std::string(who) + ": " + why);
+  return -1;
+}
+extern "C" int sqair_slot_tail_bwd_test(SqairHandle* h, const SqairSlotTailBwdTest* t, void* stream) {
+  static const char* who = "sqair_slot_tail_bwd_test";
+  if (!h) return -1;
+  if (!t) return sq_refuse(h, who, "no description");
+  if (t->B < 1) return sq_refuse(h, who, "B < 1");
+  const Dims d = sq_train_dims(h, t->B);
+  const int nsp = d.nh / 2;
+  const bool disc = t->is_disc != 0;
+  if (t->slot < 0 || t->slot >= d.N) return sq_refuse(h, who, "slot outside [0, N)");
+  if (!t->rec_new || !t->d_rec_new || !t->s1h || !t->enc || !t->noise || !t->flat || !t->d_s1pre || !t->d_raw_out || !t->d_enc)
+    return sq_refuse(h, who, "a required pointer is NULL");
+  if (!disc && (!t->rec_prev || !t->d_rec_prev || !t->hraw || !t->d_hraw))
+    return sq_refuse(h, who, "propagation needs rec_prev, d_rec_prev, hraw and d_hraw");
+  if (t->s1h_ld < nsp || t->ds_ld < nsp || (t->d_s1pre2 && t->ds2_ld < nsp) || t->enc_ld < 2 * d.nw || t->de_ld < 2 * d.nw || t->dr_ld < 1 ||
+      (!disc && (t->h_ld < 5 * d.nw || t->dh_ld < 5 * d.nw)))
+    return sq_refuse(h, who, "a pitch is smaller than the width");
+  hipStream_t s = (hipStream_t)stream;
+  TailBwdArgs ta; memset(&ta, 0, sizeof(ta));
+  ta.is_disc = disc ? 1 : 0; ta.slot = t->slot; ta.rec_prev = t->rec_prev; ta.rec_new = t->rec_new; ta.d_rec_new = t->d_rec_new;
+  ta.d_rec_prev = t->d_rec_prev; ta.s1h = t->s1h; ta.s1h_ld = t->s1h_ld; ta.hraw = t->hraw; ta.h_ld = t->h_ld; ta.enc = t->enc;
+  ta.enc_ld = t->enc_ld; ta.noise = t->noise; ta.d_s1pre = t->d_s1pre; ta.ds_ld = t->ds_ld; ta.d_s1pre2 = t->d_s1pre2; ta.ds2_ld = t->ds2_ld;
+  ta.enc_pre = t->enc_pre; ta.d_raw_out = t->d_raw_out; ta.dr_ld = t->dr_ld; ta.d_enc = t->d_enc; ta.de_ld = t->de_ld;
+  ta.d_hraw = t->d_hraw; ta.dh_ld = t->dh_ld; ta.flat = t->flat;
+  sq_tail_param_offsets(h, disc, &ta);
+  const int rc = sq_launch_slot_tail_bwd(ta, d, s);
+  if (rc != 0) { sq_set_error(h, std::string(who) + ": launch refused (dynamic LDS limit)"); return rc; }
+  SQ_CHECK_HIP(hipGetLastError());
+  SQ_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int sqair_crop_chain_bwd_test(SqairHandle* h, const SqairCropChainBwdTest* t, void* stream) {
+  static const char* who = "sqair_crop_chain_bwd_test";
+  if (!h) return -1;
+  if (!t) return sq_refuse(h, who, "no description");
+  if (t->B < 1) return sq_refuse(h, who, "B < 1");
+  if (t->mode != CROP_PROP1 && t->mode != CROP_PROP2 && t->mode != CROP_DISC) return sq_refuse(h, who, "mode is not 1, 2 or 3");
+  const Dims d = sq_train_dims(h, t->B);
+  const bool p1 = t->mode == CROP_PROP1;
+  const int nslots = sq_crop_bwd_slots(t->mode, d);
+  if (!p1 && (t->slot < 0 || t->slot >= d.N)) return sq_refuse(h, who, "slot outside [0, N)");
+  if (!t->img || !t->g_out || !t->flat || !t->d_rec_prev) return sq_refuse(h, who, "a required pointer is NULL");
+  if (p1 && (!t->rec_prev || !t->wb || !t->d_wb)) return sq_refuse(h, who, "mode 1 needs rec_prev, wb and d_wb");
+  if (!p1 && (!t->rec_new || !t->d_rec_new || !t->tp || !t->d_tp || !t->noise))
+    return sq_refuse(h, who, "modes 2 and 3 need rec_new, d_rec_new, tp, d_tp and noise");
+  if (t->mask && !t->d_mask) return sq_refuse(h, who, "a mask needs d_mask");
+  if (t->d_t2 && !p1 && (!t->w3 || !t->t2)) return sq_refuse(h, who, "d_t2 needs w3 and t2");
+  if ((p1 && t->wb_ld < 4) || (!p1 && (t->tp_ld < 8 || t->dtp_ld < 8)) || (t->d_t2 && !p1 && (t->t2_ld < d.nh || t->dt2_ld < d.nh)) ||
+      t->g_row_mul < nslots || t->g_row_add < 0 || (t->mask && (t->mask_row_mul < nslots || t->mask_row_add < 0)))
+    return sq_refuse(h, who, "a pitch is smaller than the width");
+  if (!sq_trainable_frame(h)) return sq_refuse(h, who, std::string(sqair_last_error(h)));
+  hipStream_t s = (hipStream_t)stream;
+  CropChainBwdArgs ca; memset(&ca, 0, sizeof(ca));
+  ca.mode = t->mode; ca.slot = t->slot; ca.img = t->img; ca.rec_prev = t->rec_prev; ca.rec_new = t->rec_new; ca.d_rec_prev = t->d_rec_prev;
+  ca.d_rec_new = t->d_rec_new; ca.wb = t->wb; ca.wb_ld = t->wb_ld; ca.d_wb = t->d_wb; ca.mask = t->mask; ca.mask_row_mul = t->mask_row_mul;
+  ca.mask_row_add = t->mask_row_add; ca.d_mask = t->d_mask; ca.mask_dact = t->mask_dact; ca.g_out = t->g_out; ca.g_row_mul = t->g_row_mul;
+  ca.g_row_add = t->g_row_add; ca.tp = t->tp; ca.tp_ld = t->tp_ld; ca.d_tp = t->d_tp; ca.dtp_ld = t->dtp_ld; ca.noise = t->noise;
+  ca.flat = t->flat; ca.w3 = t->w3; ca.t2 = t->t2; ca.t2_ld = t->t2_ld; ca.d_t2 = t->d_t2; ca.dt2_ld = t->dt2_ld;
+  const int rc = sq_launch_crop_chain_bwd(ca, h->po, d, nslots, s);
+  if (rc != 0) { sq_set_error(h, std::string(who) + ": launch refused (frame alignment or dynamic LDS limit)"); return rc; }
+  SQ_CHECK_HIP(hipGetLastError());
+  SQ_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int sqair_where_param_grads_test(SqairHandle* h, const SqairWhereParamGradsTest* t, void* stream) {
+  static const char* who = "sqair_where_param_grads_test";
+  if (!h) return -1;
+  if (!t) return sq_refuse(h, who, "no description");
+  if (t->T < 1 || t->B < 1) return sq_refuse(h, who, "T < 1 or B < 1");
+  if (!t->d_tp || !t->d_rec_p || !t->rec_p || !t->noise || !t->flat_grad) return sq_refuse(h, who, "a required pointer is NULL");
+  if (t->tp_ld < 8) return sq_refuse(h, who, "a pitch is smaller than the width");
+  const Dims d = sq_train_dims(h, t->B);
+  if ((int64_t)t->T * d.R * d.N > (int64_t)1 << 24) return sq_refuse(h, who, "more than 2^24 (frame, row, slot) rows");
+  hipStream_t s = (hipStream_t)stream;
+  sq_launch_where_param_grads(t->d_tp, t->tp_ld, t->d_rec_p, t->rec_p, t->noise, t->T, d, t->flat_grad, h->po, s);
+  SQ_CHECK_HIP(hipGetLastError());
+  SQ_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int sqair_gru_gates_bwd_test(SqairHandle* h, const SqairGruGatesBwdTest* t, void* stream) {
+  static const char* who = "sqair_gru_gates_bwd_test";
+  if (!h) return -1;
+  if (!t) return sq_refuse(h, who, "no description");
+  const int nh = h->cfg.n_hidden;
+  if (t->rows < 1 || (int64_t)t->rows * nh > (int64_t)1 << 30) return sq_refuse(h, who, "rows outside [1, 2^30 / n_hidden]");
+  if (!t->d_hn || !t->z || !t->r || !t->hc || !t->hprev || !t->d_rh || !t->dpre1 || !t->d_h) return sq_refuse(h, who, "a required pointer is NULL");
+  if (t->dhn_ld < nh || t->z_ld < nh || t->r_ld < nh || t->hc_ld < nh || (t->h_ld != 0 && t->h_ld < nh) || t->drh_ld < nh || t->dp_ld < 3 * nh ||
+      t->dh_ld < nh || (t->dup_z && t->dupz_ld < (t->dup_h_off >= 0 ? t->dup_h_off + nh : nh)) || (t->dup_r && t->dupr_ld < nh))
+    return sq_refuse(h, who, "a pitch is smaller than the width");
+  hipStream_t s = (hipStream_t)stream;
+  sq_launch_gru_bwd_a(t->d_hn, t->dhn_ld, t->z, t->z_ld, t->hc, t->hc_ld, t->hprev, t->h_ld, t->dpre1, t->dp_ld, t->d_h, t->dh_ld, t->rows, nh,
+                      t->accumulate_dh, s, t->dup_z, t->dupz_ld, t->dup_h_off);
+  sq_launch_gru_bwd_b(t->d_rh, t->drh_ld, t->r, t->r_ld, t->hprev, t->h_ld, t->dpre1, t->dp_ld, t->d_h, t->dh_ld, t->rows, nh, s, t->dup_r,
+                      t->dupr_ld);
   SQ_CHECK_HIP(hipGetLastError());
   SQ_CHECK_HIP(hipStreamSynchronize(s));
   return 0;

@@ -1,0 +1,327 @@
+"""Reference for the element-wise adjoints of the slot loop (k_slot_tail_bwd, k_crop_chain_bwd, k_where_param_grads, k_gru_bwd_a / _b).
+
+Every piece is the FORWARD computation, restated on the oracle's own functions (oracle/sqair_oracle.py: to_coords, st_crop /
+bilinear_gather, softplus, elu, fill_triangular, the gru definition, the gated `what` mixture of propagation_core); every adjoint is
+autograd of sum(upstream * output).  No derivative is written down here.  The same functions run in float64 (the reference) and in
+float32 (what an honest fp32 implementation loses: the tolerance of tests/test_slot_adjoint_kernels.py is a multiple of it).
+
+The kernels read SAVED activations (the tape of the forward pass: outputs of ELU, sigmoid, tanh, softplus), not pre-activations.  A
+piece therefore takes the tape values and inverts the activation to obtain the leaf it differentiates with respect to; kernel and
+reference are given the same fp32 tape.  tests/test_slot_adjoint_ref.py pins all of it on the CPU: against SqairOracle.discovery_core /
+propagation_core, against central differences, and the Cholesky index order against oracle.fill_triangular.
+
+The metric and the sentinel helpers at the end are shared with the GPU tests (and meant for the unit tests of k_logprob_bwd to come)."""
+import numpy as np
+import torch
+
+from oracle import sqair_oracle as O
+
+MIN_STD = 1e-2          # oracle.make_cfg: min_std; the where scales add the same constant (propagation_core / discovery_core)
+GATE_SCALE = 0.9999     # propagation_core: gates = sigmoid(.) * 0.9999
+WHERE_BIAS_SCALE = 0.1  # propagation_core: where_bias = MLP(.) * 0.1
+
+
+def T(x, dtype):
+    return torch.as_tensor(np.asarray(x), dtype=dtype)
+
+
+def leaf(x, dtype):
+    return T(x, dtype).clone().requires_grad_(True)
+
+
+# ---- inverses of the saved activations (forward functions, evaluated in the piece's dtype)
+def inv_elu(y):
+    return torch.where(y > 0, y, torch.log1p(torch.clamp(y, max=0.0)))
+
+
+def inv_softplus(s):
+    return s + torch.log(-torch.expm1(-s))
+
+
+def logit(p):
+    return torch.log(p) - torch.log1p(-p)
+
+
+def adjoints(outputs, upstream, leaves):
+    """d sum(upstream * output) / d leaf for every leaf (zeros where a leaf does not reach the outputs)."""
+    obj = None
+    for k, up in upstream.items():
+        term = (up * outputs[k]).sum()
+        obj = term if obj is None else obj + term
+    grads = torch.autograd.grad(obj, list(leaves.values()), allow_unused=True)
+    return {k: (torch.zeros_like(v) if g is None else g).detach() for (k, v), g in zip(leaves.items(), grads)}
+
+
+# ------------------------------------------------------------------------------------------------
+# slot tail: `what` sample (gated mixture in propagation), steps predictor on it, presence logit
+# ------------------------------------------------------------------------------------------------
+def tail_forward(lv, c):
+    """lv: leaves; c: constants.  Returns what, what_loc, what_scale, logit (the record fields the upstream gradients arrive in).
+    lv: enc_loc [R, nw]; enc_scale [R, nw] or (enc_pre) enc_raw; s1_rest [R, nsp] = the hidden pre-activation of the steps predictor
+    without the `what` rows' part; bump [R, nw] zeros added to the sample (its gradient is the sample's total gradient);
+    propagation: hraw [R, 5 nw] = what-head (loc, raw scale) and the three raw gates, what_tm1 [R, nw].
+    c: eps [R, nw], w_what [nw, nsp], w2 [nsp], b2 scalar, prev [R] previous presence, is_disc."""
+    nw = c["eps"].shape[-1]
+    loc2 = lv["enc_loc"]
+    scale2 = O.softplus(lv["enc_raw"]) + MIN_STD if "enc_raw" in lv else lv["enc_scale"]     # gaussian_head
+    if c["is_disc"]:
+        what_loc, what_scale = loc2, scale2
+    else:
+        h = lv["hraw"]
+        t_loc, t_scale = h[..., :nw], O.softplus(h[..., nw:2 * nw]) + MIN_STD                # gaussian_head("prop.what_head")
+        gates = torch.sigmoid(h[..., 2 * nw:]) * GATE_SCALE
+        fg, ig, tg = gates[..., :nw], gates[..., nw:2 * nw], gates[..., 2 * nw:]
+        what_loc = fg * lv["what_tm1"] + (1.0 - ig) * loc2 + (1.0 - tg) * t_loc
+        what_scale = (1.0 - ig) * scale2 + (1.0 - tg) * t_scale
+    what = what_loc + what_scale * c["eps"] + lv["bump"]
+    hidden = O.elu(lv["s1_rest"] + what @ c["w_what"])                                       # mlp_1hidden_out, the `what` rows apart
+    raw = hidden @ c["w2"] + c["b2"]
+    prev = c["prev"]
+    return dict(what=what, what_loc=what_loc, what_scale=what_scale, logit=prev * raw + (prev - 1.0) * 88.0, raw=raw, hidden=hidden)
+
+
+def tail_leaves(tape, c, dtype, enc_pre):
+    """Leaves from the fp32 tape: s1h (the saved hidden ACTIVATIONS), enc (loc, scale), hraw, what_tm1."""
+    nw = c["eps"].shape[-1]
+    enc = T(tape["enc"], dtype)
+    lv = dict(enc_loc=leaf(enc[..., :nw], dtype), bump=leaf(np.zeros(enc[..., :nw].shape), dtype))
+    if enc_pre:
+        lv["enc_raw"] = inv_softplus(enc[..., nw:] - MIN_STD).detach().requires_grad_(True)
+    else:
+        lv["enc_scale"] = leaf(enc[..., nw:], dtype)
+    if not c["is_disc"]:
+        lv["hraw"] = leaf(tape["hraw"], dtype)
+        lv["what_tm1"] = leaf(tape["what_tm1"], dtype)
+    # the rest of the hidden pre-activation is whatever makes the hidden layer reproduce the saved activations
+    lv["s1_rest"] = leaf(np.zeros(np.asarray(tape["s1h"]).shape), dtype)
+    with torch.no_grad():
+        part = tail_forward(lv, c)["what"] @ c["w_what"]
+        lv["s1_rest"] = (inv_elu(T(tape["s1h"], dtype)) - part).requires_grad_(True)
+    return lv
+
+
+def tail_adjoint(tape, consts, upstream, dtype, enc_pre=False):
+    """upstream: what, what_loc, what_scale [R, nw], logit [R].  Returns the kernel's outputs by name."""
+    c = {k: (v if isinstance(v, (bool, int)) else T(v, dtype)) for k, v in consts.items()}
+    lv = tail_leaves(tape, c, dtype, enc_pre)
+    out = tail_forward(lv, c)
+    raw_leaf = out["raw"]
+    up = {k: T(v, dtype) for k, v in upstream.items()}
+    g = adjoints(out, up, dict(lv, _raw=raw_leaf))
+    res = dict(d_s1pre=g["s1_rest"], d_raw=g["_raw"], d_what=g["bump"],
+               d_enc=torch.cat([g["enc_loc"], g["enc_raw" if enc_pre else "enc_scale"]], -1))
+    if not c["is_disc"]:
+        res.update(d_hraw=g["hraw"], d_what_tm1=g["what_tm1"])
+    return {k: v.numpy() for k, v in res.items()}
+
+
+# ------------------------------------------------------------------------------------------------
+# crop chain: where sample -> spatial transformer (-> mask) -> glimpse
+# ------------------------------------------------------------------------------------------------
+def sampling_coords(where_logits, H, W, G):
+    """The source-pixel coordinates st_crop samples at: x [.., G], y [.., G] (st_crop's own expressions)."""
+    sx, sy, tx, ty = O.to_coords(where_logits)
+    g = torch.linspace(-1.0, 1.0, G, dtype=where_logits.dtype)
+    x = 0.5 * (W - 1) * (sx[..., None] * g + tx[..., None] + 1.0)
+    y = 0.5 * (H - 1) * (sy[..., None] * g + ty[..., None] + 1.0)
+    return x, y
+
+
+def kink_margin(where_logits, H, W, G):
+    """Per row: the distance of the closest sampling coordinate to an integer pixel coordinate (where bilinear sampling has its
+    kink and fp32 may take other taps than fp64)."""
+    x, y = sampling_coords(T(where_logits, torch.float64), H, W, G)
+    both = torch.cat([x, y], -1)
+    return (both - torch.round(both)).abs().min(-1).values.numpy()
+
+
+def where_scale_of(raw, offset, is_disc):
+    """propagation_core / discovery_core: scale = softplus(raw + scale_offset [- 1 in propagation]) + 1e-2."""
+    return O.softplus(raw + offset - (0.0 if is_disc else 1.0)) + MIN_STD
+
+
+def where_tril(cholesky, scale):
+    """SqairOracle.where_tril without the object: L = T * scale[:, None] + diag(scale), T = fill_triangular(cholesky_scale, 4)."""
+    Tm = O.fill_triangular(cholesky, 4)
+    return Tm[None] * scale[..., :, None] + torch.diag_embed(scale)
+
+
+def crop_forward(lv, c):
+    """mode 1 (crop #1 of propagation): where logits = where_tm1 + 0.1 wb, rows [M, 4].
+    mode 2 / 3: where = loc + L eps (propagation: loc = where_tm1 + tp[:4], L from the Cholesky factor) or loc + scale eps (discovery:
+    loc = tp[:4]); sampled at the SAVED fp32 where (c['where_saved'], a constant shift of rounding size).
+    tp is a leaf, or with t2pre the transform's output layer elu(t2pre) @ w3 + (the constant that reproduces the saved tp).
+    Returns glimpse [M, G2] (masked), where, where_loc, where_scale, mask."""
+    img, G, mode = c["img"], c["G"], c["mode"]
+    out = {}
+    if mode == 1:
+        wl = lv["where_tm1"] + WHERE_BIAS_SCALE * lv["wb"]
+    else:
+        tp = lv["tp"] if "tp" in lv else O.elu(lv["t2pre"]) @ c["w3"] + c["tp_const"]
+        is_disc = mode == 3
+        scale = where_scale_of(tp[..., 4:], c["scale_offset"], is_disc)
+        if is_disc:
+            loc = tp[..., :4]
+            where = loc + scale * c["eps"]
+        else:
+            loc = lv["where_tm1"] + tp[..., :4]
+            where = loc + (where_tril(c["cholesky"], scale) @ c["eps"].unsqueeze(-1)).squeeze(-1)
+        where = where + lv["bump"]
+        out.update(where=where, where_loc=loc, where_scale=scale, tp=tp)
+        wl = where + (c["where_saved"] - where).detach() if "where_saved" in c else where
+    glimpse = O.st_crop(img, wl, G).reshape(wl.shape[0], G * G)
+    if "maskpre" in lv or "mask" in lv:
+        mask = torch.sigmoid(lv["maskpre"]) if "maskpre" in lv else lv["mask"]
+        glimpse = glimpse * mask
+        out["mask"] = mask
+    out["glimpse"] = glimpse
+    out["where_logits"] = wl
+    return out
+
+
+def crop_adjoint(tape, consts, upstream, dtype, fuse_t3=False, mask_dact=False):
+    """tape: where_tm1 [M, 4], wb (mode 1), tp [M, 8] and where [M, 4] (modes 2 / 3), mask [M, G2] or None, t2 [M, nh] (fused).
+    upstream: glimpse [M, G2]; where, where_loc, where_scale [M, 4] (modes 2 / 3); mask [M, G2] = what d_mask already holds."""
+    c = {k: (v if isinstance(v, (bool, int)) else T(v, dtype)) for k, v in consts.items()}
+    mode = c["mode"]
+    lv = {}
+    if mode != 3:
+        lv["where_tm1"] = leaf(tape["where_tm1"], dtype)
+    if mode == 1:
+        lv["wb"] = leaf(tape["wb"], dtype)
+    else:
+        lv["bump"] = leaf(np.zeros(np.asarray(tape["tp"])[..., :4].shape), dtype)
+        c["where_saved"] = T(tape["where"], dtype)
+        if fuse_t3:
+            lv["t2pre"] = inv_elu(T(tape["t2"], dtype)).requires_grad_(True)
+            with torch.no_grad():
+                c["tp_const"] = T(tape["tp"], dtype) - O.elu(lv["t2pre"]) @ c["w3"]
+        else:
+            lv["tp"] = leaf(tape["tp"], dtype)
+    if tape.get("mask") is not None:
+        if mask_dact:
+            lv["maskpre"] = logit(T(tape["mask"], dtype)).requires_grad_(True)
+        else:
+            lv["mask"] = leaf(tape["mask"], dtype)
+    out = crop_forward(lv, c)
+    leaves = dict(lv)
+    if fuse_t3:
+        leaves["_tp"] = out["tp"]
+    g = adjoints(out, {k: T(v, dtype) for k, v in upstream.items() if k in out}, leaves)
+    res = {}
+    if mode == 1:
+        res.update(d_where_tm1=g["where_tm1"], d_wb=g["wb"])
+    else:
+        res.update(d_tp=g["_tp"] if fuse_t3 else g["tp"], d_where=g["bump"])
+        if mode == 2:
+            res["d_where_tm1"] = g["where_tm1"]
+        if fuse_t3:
+            res["d_t2"] = g["t2pre"]
+    if tape.get("mask") is not None:
+        res["d_mask"] = g["maskpre" if mask_dact else "mask"]
+    return {k: v.numpy() for k, v in res.items()}
+
+
+# ------------------------------------------------------------------------------------------------
+# where parameters: Cholesky factor of the propagation where posterior, both scale offsets
+# ------------------------------------------------------------------------------------------------
+def where_param_adjoint(d_where, scale, eps, d_raw_p, d_raw_d, dtype, with_abs=False):
+    """All [rows, 4].  Forward, per use: where = loc + where_tril(scale) eps with the SAVED scale, and the raw scale + scale_offset
+    of each phase.  Returns the twelve gradients [cholesky 10 | prop offset | disc offset] (and the sums of the absolute terms)."""
+    def twelve(d_where, scale, eps, d_raw_p, d_raw_d):
+        ch = leaf(np.zeros(10), dtype)
+        off_p, off_d = leaf(np.zeros(()), dtype), leaf(np.zeros(()), dtype)
+        sc = T(scale, dtype)
+        out = dict(where=(where_tril(ch, sc) @ T(eps, dtype).unsqueeze(-1)).squeeze(-1), raw_p=torch.zeros_like(sc) + off_p,
+                   raw_d=torch.zeros_like(sc) + off_d)
+        g = adjoints(out, dict(where=T(d_where, dtype), raw_p=T(d_raw_p, dtype), raw_d=T(d_raw_d, dtype)), dict(ch=ch, p=off_p, d=off_d))
+        return torch.cat([g["ch"], g["p"].reshape(1), g["d"].reshape(1)]).numpy()
+    got = twelve(d_where, scale, eps, d_raw_p, d_raw_d)
+    if not with_abs:
+        return got
+    # the sums of the absolute terms: the same (multilinear) map on the absolute values of its operands
+    return got, twelve(*[np.abs(np.asarray(a, np.float64)) for a in (d_where, scale, eps, d_raw_p, d_raw_d)])
+
+
+# ------------------------------------------------------------------------------------------------
+# GRU gates (oracle.gru: z, r = sigmoid(.), hc = tanh(. + (r h) U_h), h' = (1 - z) h + z hc)
+# ------------------------------------------------------------------------------------------------
+def gru_forward(lv):
+    """The two element-wise pieces around the candidate's recurrent GEMM: h' from (az, ah, h) and r h from (ar, h)."""
+    z, r, hc = torch.sigmoid(lv["az"]), torch.sigmoid(lv["ar"]), torch.tanh(lv["ah"])
+    return dict(h_new=(1.0 - z) * lv["h"] + z * hc, rh=r * lv["h"])
+
+
+def gru_adjoint(tape, upstream, dtype):
+    """tape: z, r, hc [rows, nh] the saved gate OUTPUTS, h [rows, nh] or [1, nh] (broadcast); upstream: h_new = d h', rh = d(r h).
+    Returns d_az, d_ar, d_ah, and d_h split into stage A's part (from h') and stage B's (from r h)."""
+    lv = dict(az=logit(T(tape["z"], dtype)).requires_grad_(True), ar=logit(T(tape["r"], dtype)).requires_grad_(True),
+              ah=torch.atanh(T(tape["hc"], dtype)).requires_grad_(True))
+    h = T(tape["h"], dtype)
+    lv["h"] = (h.expand_as(lv["az"]) if h.shape[0] == 1 else h).clone().requires_grad_(True)
+    out = gru_forward(lv)
+    ga = adjoints(out, dict(h_new=T(upstream["h_new"], dtype)), lv)
+    gb = adjoints(out, dict(rh=T(upstream["rh"], dtype)), lv)
+    return {k: v.numpy() for k, v in dict(d_az=ga["az"], d_ah=ga["ah"], d_ar=gb["ar"], d_h_a=ga["h"], d_h_b=gb["h"]).items()}
+
+
+# ------------------------------------------------------------------------------------------------
+# metric, bars, sentinels
+# ------------------------------------------------------------------------------------------------
+ULP32 = float(2.0 ** -23)
+
+
+def row_scaled_error(got, ref, scale=None):
+    """max over elements of |got - ref| / (largest |ref| of the element's row) (rows = all leading axes); `scale` replaces the row
+    maximum (the reduced scalars: the sum of the absolute terms).  A row whose scale is 0 must be reproduced exactly."""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    den = np.abs(ref).max(-1, keepdims=True) if scale is None else np.asarray(scale, np.float64)
+    diff = np.abs(got - ref)
+    if not np.all(np.isfinite(got)):
+        return float("inf")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        e = np.where(diff == 0, 0.0, diff / den)
+    return float(e.max()) if e.size else 0.0
+
+
+def bar_from_fp32(err32):
+    """8 x the error of the same reference evaluated in fp32; 8 ulp of the row scale where that is exactly zero."""
+    return 8.0 * err32 if err32 > 0 else 8.0 * ULP32
+
+
+def distinct_words(n, start):
+    """n float32 words with consecutive bit patterns from 1.0f + start: finite, normal, pairwise distinct (sentinels)."""
+    assert start + n < (0x7F000000 - 0x3F800000)
+    return (np.arange(start, start + n, dtype=np.uint32) + np.uint32(0x3F800000)).view(np.float32)
+
+
+class Pitched:
+    """A [rows, width] operand inside a [rows + 2 guard rows, ld] buffer whose every other word is NaN (inputs: a kernel that reads
+    its padding poisons its result) or a distinct sentinel (outputs: compared bit for bit afterwards)."""
+
+    def __init__(self, rows, width, ld, data=None, nan=True, start=0, offset=0):
+        assert ld >= offset + width
+        self.rows, self.width, self.ld, self.offset = rows, width, ld, offset
+        n = (rows + 2) * ld
+        self.host = np.full(n, np.nan, np.float32) if nan else distinct_words(n, start).copy()
+        self.host = self.host.reshape(rows + 2, ld)
+        if data is not None:
+            self.host[1:1 + rows, offset:offset + width] = np.asarray(data, np.float32).reshape(rows, width)
+        self.before = self.host.copy()
+
+    def view(self, a=None):
+        a = self.host if a is None else a
+        return a[1:1 + self.rows, self.offset:self.offset + self.width]
+
+    def first_word(self):
+        """Index (in floats) of element [0, 0] of the operand inside the buffer."""
+        return self.ld + self.offset
+
+    def untouched(self, after, written=None):
+        """True if every word outside the operand (and outside `written`, a boolean [rows, width] of the words the kernel owns) has
+        the bits it had before."""
+        own = np.zeros(self.host.shape, bool)
+        own[1:1 + self.rows, self.offset:self.offset + self.width] = True if written is None else written
+        a, b = np.asarray(after, np.float32).reshape(self.host.shape).view(np.uint32), self.before.view(np.uint32)
+        return bool(np.array_equal(a[~own], b[~own]))

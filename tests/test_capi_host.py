@@ -256,13 +256,95 @@ def test_backward_decoder_refusals_host_side():
             lib.sqair_destroy(h)
 
 
+def _all_set(cls, buf, **over):
+    """A description whose every pointer is `buf` and every int a value the entry accepts, then `over`."""
+    t = cls()
+    for name, typ in cls._fields_:
+        setattr(t, name, C.addressof(buf) if typ is C.c_void_p else 1024)
+    for k, v in over.items():
+        setattr(t, k, v)
+    return t
+
+
+def test_slot_adjoint_test_entries_refuse_host_side():
+    """sqair_slot_tail_bwd_test / sqair_crop_chain_bwd_test / sqair_where_param_grads_test / sqair_gru_gates_bwd_test
+    (tests/test_slot_adjoint_kernels.py drives them on the GPU): exported by both builds under the unchanged ABI version, and a NULL
+    required pointer, a slot out of range, a pitch below the width and a frame that cannot be trained are refused with the entry's
+    name in the error text before any HIP call (`buf` stands for every device buffer: nothing reads it)."""
+    buf = (C.c_float * 16)()
+    for path in (_capi.LIB_PATH, _capi.WIDE_LIB_PATH):
+        lib = _capi.lib(path)
+        assert lib.sqair_abi_version() == _capi.ABI_VERSION == 2
+        cfg = make_config(make_flags(k_particles=2, n_steps_per_image=3), (50, 50))
+        h = C.c_void_p()
+        assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
+        big = C.c_void_p()
+        assert lib.sqair_create(C.byref(make_config(make_flags(k_particles=2, n_steps_per_image=3), (200, 200))), C.byref(big)) == 0
+        try:
+            def refused(fn, cls, handle=h, **over):
+                name = fn.encode()
+                assert fn in _capi.EXPORTED_SYMBOLS
+                rc = getattr(lib, fn)(handle, C.byref(_all_set(cls, buf, **over)), None)
+                err = lib.sqair_last_error(handle)
+                assert rc == -1 and err.startswith(name + b": "), (fn, over, rc, err)
+                return err
+            for fn in ("sqair_slot_tail_bwd_test", "sqair_crop_chain_bwd_test", "sqair_where_param_grads_test", "sqair_gru_gates_bwd_test"):
+                assert getattr(lib, fn)(None, None, None) == -1
+                assert getattr(lib, fn)(h, None, None) == -1 and lib.sqair_last_error(h).startswith(fn.encode())
+            S, K, W, G = _capi.SqairSlotTailBwdTest, _capi.SqairCropChainBwdTest, _capi.SqairWhereParamGradsTest, _capi.SqairGruGatesBwdTest
+            tail = dict(is_disc=0, slot=1, B=2, enc_pre=0)
+            for p in ("rec_new", "d_rec_new", "s1h", "enc", "noise", "flat", "d_s1pre", "d_raw_out", "d_enc"):
+                assert b"NULL" in refused("sqair_slot_tail_bwd_test", S, **dict(tail, **{p: None}))
+            for p in ("rec_prev", "d_rec_prev", "hraw", "d_hraw"):
+                assert b"propagation needs" in refused("sqair_slot_tail_bwd_test", S, **dict(tail, **{p: None}))
+            for slot in (-1, 3):
+                assert b"slot" in refused("sqair_slot_tail_bwd_test", S, **dict(tail, slot=slot))
+            assert b"B < 1" in refused("sqair_slot_tail_bwd_test", S, **dict(tail, B=0))
+            for ld, v in (("s1h_ld", 127), ("ds_ld", 127), ("ds2_ld", 127), ("enc_ld", 99), ("de_ld", 99), ("dr_ld", 0), ("h_ld", 249),
+                          ("dh_ld", 249)):
+                assert b"pitch" in refused("sqair_slot_tail_bwd_test", S, **dict(tail, **{ld: v}))
+            crop = dict(mode=2, slot=0, B=2, mask_dact=0, g_row_add=0, mask_row_add=0)
+            for p in ("img", "g_out", "flat", "d_rec_prev", "rec_new", "d_rec_new", "tp", "d_tp", "noise", "d_mask", "w3", "t2"):
+                refused("sqair_crop_chain_bwd_test", K, **dict(crop, **{p: None}))
+            for p in ("rec_prev", "wb", "d_wb"):
+                refused("sqair_crop_chain_bwd_test", K, **dict(crop, mode=1, **{p: None}))
+            for mode in (0, 4):
+                assert b"mode" in refused("sqair_crop_chain_bwd_test", K, **dict(crop, mode=mode))
+            for slot in (-1, 3):
+                assert b"slot" in refused("sqair_crop_chain_bwd_test", K, **dict(crop, slot=slot))
+            for ld, v in (("tp_ld", 7), ("dtp_ld", 7), ("t2_ld", 255), ("dt2_ld", 255), ("g_row_mul", 0), ("mask_row_mul", 0)):
+                assert b"pitch" in refused("sqair_crop_chain_bwd_test", K, **dict(crop, **{ld: v}))
+            for ld, v in (("wb_ld", 3), ("g_row_mul", 2), ("mask_row_mul", 2)):   # crop #1 covers the N = 3 slots of a row
+                assert b"pitch" in refused("sqair_crop_chain_bwd_test", K, **dict(crop, mode=1, **{ld: v}))
+            assert b"200 x 200" in refused("sqair_crop_chain_bwd_test", K, handle=big, **crop)   # a frame the crop adjoint cannot stage
+            wpg = dict(T=2, B=2, tp_ld=8)
+            for p in ("d_tp", "d_rec_p", "rec_p", "noise", "flat_grad"):
+                assert b"NULL" in refused("sqair_where_param_grads_test", W, **dict(wpg, **{p: None}))
+            assert b"pitch" in refused("sqair_where_param_grads_test", W, **dict(wpg, tp_ld=7))
+            assert b"T < 1" in refused("sqair_where_param_grads_test", W, **dict(wpg, T=0))
+            gru = dict(rows=4, accumulate_dh=0, dup_h_off=-1, h_ld=0)
+            for p in ("d_hn", "z", "r", "hc", "hprev", "d_rh", "dpre1", "d_h"):
+                assert b"NULL" in refused("sqair_gru_gates_bwd_test", G, **dict(gru, **{p: None}))
+            for ld, v in (("dhn_ld", 255), ("z_ld", 255), ("r_ld", 255), ("hc_ld", 255), ("h_ld", 255), ("drh_ld", 255), ("dp_ld", 767),
+                          ("dh_ld", 255), ("dupz_ld", 255), ("dupr_ld", 255)):
+                assert b"pitch" in refused("sqair_gru_gates_bwd_test", G, **dict(gru, **{ld: v}))
+            assert b"pitch" in refused("sqair_gru_gates_bwd_test", G, **dict(gru, dup_h_off=512, dupz_ld=767))
+            assert b"rows" in refused("sqair_gru_gates_bwd_test", G, **dict(gru, rows=0))
+        finally:
+            lib.sqair_destroy(h)
+            lib.sqair_destroy(big)
+
+
 def test_dense_test_structs_have_the_header_layout(repo_root, tmp_path):
     """The descriptions of sqair_linear_contract_test / sqair_linear_dx_test are passed by address: the ctypes mirrors must have
     the size and the field offsets a C compiler gives the header's structs."""
     import shutil
     import subprocess
     structs = {"SqairDenseSeg": _capi.SqairDenseSeg, "SqairDenseContract": _capi.SqairDenseContract, "SqairDxRange": _capi.SqairDxRange,
-               "SqairDxGru": _capi.SqairDxGru, "SqairDxTest": _capi.SqairDxTest}
+               "SqairDxGru": _capi.SqairDxGru, "SqairDxTest": _capi.SqairDxTest,
+               # the slot loop's element-wise adjoints (sqair_slot_tail_bwd_test and its three neighbours)
+               "SqairSlotTailBwdTest": _capi.SqairSlotTailBwdTest, "SqairCropChainBwdTest": _capi.SqairCropChainBwdTest,
+               "SqairWhereParamGradsTest": _capi.SqairWhereParamGradsTest, "SqairGruGatesBwdTest": _capi.SqairGruGatesBwdTest}
     lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "sqair_hip.h"', "int main(void) {"]
     for name, cls in structs.items():
         lines.append('  printf("{0} %zu\\n", sizeof({0}));'.format(name))

@@ -1,0 +1,297 @@
+"""The float64 reference of the slot loop's adjoint kernels (tests/slot_adjoint_ref.py), pinned without a GPU:
+every forward piece reproduces the oracle's discovery_core / propagation_core on the same inputs, autograd agrees with central
+differences, the inverted activations reproduce the tape, and the Cholesky gradient lands where oracle.fill_triangular says."""
+import contextlib
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import sqair_oracle as O
+from sqair_amd.flags import make_flags
+from sqair_amd.params import init_params
+from tests import slot_adjoint_ref as R
+
+F64 = torch.float64
+HW, G, NW, NH, B = (14, 17), 6, 7, 128, 5
+
+
+@contextlib.contextmanager
+def recorded():
+    """Every call of oracle.linear (its output) and oracle.mlp2_hidden (its input), by layer name, in call order."""
+    rec = {}
+    lin, mlp = O.linear, O.mlp2_hidden
+
+    def linear(P, name, x):
+        y = lin(P, name, x)
+        rec.setdefault(name, []).append(y)
+        return y
+
+    def mlp2_hidden(P, name, x):
+        rec.setdefault(name + ":in", []).append(x)
+        return mlp(P, name, x)
+    O.linear, O.mlp2_hidden = linear, mlp2_hidden
+    try:
+        yield rec
+    finally:
+        O.linear, O.mlp2_hidden = lin, mlp
+
+
+@pytest.fixture(scope="module")
+def model():
+    F = make_flags(n_units=NH // 32, n_what=NW, glimpse_size=G, n_steps_per_image=2, k_particles=1)
+    P = init_params(F, HW, seed=5, jitter=0.3)
+    P["prop.cholesky_scale"] = np.linspace(-0.6, 0.7, 10)
+    orc = O.SqairOracle(P, O.make_cfg(F, HW), F64)
+    rng = np.random.default_rng(11)
+    t = lambda *s: torch.as_tensor(rng.standard_normal(s))
+    x = dict(img=torch.as_tensor(rng.uniform(size=(B,) + HW)), what_tm1=t(B, NW), where_tm1=t(B, 4) * 0.5,
+             pres_tm1=torch.as_tensor([[1.0], [0.0], [1.0], [1.0], [0.0]]), logit_tm1=t(B, 1), temporal=t(B, NH) * 0.5,
+             what_km1=t(B, NW), where_km1=t(B, 4), pres_km1=torch.ones(B, 1), hidden=t(B, NH) * 0.5, eps_where=t(B, 4), eps_what=t(B, NW),
+             u=torch.as_tensor(rng.uniform(size=(B, 1))), cond=t(B, NH))
+    return orc, x
+
+
+def _close(a, b, tol=1e-12):
+    a, b = a.detach().numpy(), b.detach().numpy()
+    assert a.shape == b.shape and np.abs(a - b).max() <= tol * max(1.0, np.abs(b).max()), np.abs(a - b).max()
+
+
+def test_propagation_pieces_reproduce_the_oracle(model):
+    orc, x = model
+    P = orc.P
+    with recorded() as rec:
+        out, _ = orc.propagation_core(x["img"], (x["what_tm1"], x["where_tm1"], x["pres_tm1"], x["logit_tm1"]), x["temporal"],
+                                      (x["what_km1"], x["where_km1"], x["pres_km1"], x["hidden"]), x["eps_where"], x["eps_what"], x["u"])
+    zeros4, zerosw = torch.zeros(B, 4, dtype=F64), torch.zeros(B, NW, dtype=F64)
+    enc = rec["enc.what_head"][1]
+    # crop #1: where_tm1 + 0.1 where-bias MLP output, masked
+    c1 = R.crop_forward(dict(where_tm1=x["where_tm1"], wb=rec["prop.where_bias.l1"][0], maskpre=rec["enc.mask.l1"][0]),
+                        dict(img=x["img"], G=G, mode=1))
+    _close(c1["glimpse"], rec["enc.glimpse:in"][0])
+    # crop #2 and the where sample, from the transform's output and through its output layer
+    consts = dict(img=x["img"], G=G, mode=2, scale_offset=P["prop.transform.scale_offset"], cholesky=P["prop.cholesky_scale"], eps=x["eps_where"])
+    for lv in (dict(tp=rec["prop.transform.l2"][0]),
+               dict(t2pre=rec["prop.transform.l1"][0])):
+        cc = dict(consts, w3=P["prop.transform.l2.w"], tp_const=P["prop.transform.l2.b"])
+        c2 = R.crop_forward(dict(lv, where_tm1=x["where_tm1"], bump=zeros4, maskpre=rec["enc.mask.l1"][1]), cc)
+        _close(c2["where"], out["where"]); _close(c2["where_loc"], out["where_loc"]); _close(c2["where_scale"], out["where_scale"])
+        _close(c2["glimpse"], rec["enc.glimpse:in"][1])
+    # the tail: gated mixture, sample, steps predictor, presence logit
+    w0 = P["prop.steps.l0.w"]
+    tc = dict(eps=x["eps_what"], w_what=w0[2 * NH:], w2=P["prop.steps.l1.w"][:, 0], b2=P["prop.steps.l1.b"][0], prev=x["pres_tm1"][:, 0], is_disc=False)
+    assert w0.shape[0] == 2 * NH + NW
+    lv = dict(enc_loc=enc[:, :NW], enc_raw=enc[:, NW:], hraw=torch.cat([rec["prop.what_head"][0], rec["prop.gates"][0]], -1),
+              what_tm1=x["what_tm1"], bump=zerosw, s1_rest=rec["prop.steps.l0"][0] - out["what"] @ w0[2 * NH:])
+    t = R.tail_forward(lv, tc)
+    for k in ("what", "what_loc", "what_scale"):
+        _close(t[k], out[k])
+    _close(t["logit"], out["presence_logit"][:, 0]); _close(t["raw"], rec["prop.steps.l1"][0][:, 0])
+    lv2 = dict(lv, enc_scale=O.softplus(enc[:, NW:]) + 1e-2)
+    del lv2["enc_raw"]
+    _close(R.tail_forward(lv2, tc)["what"], out["what"])
+
+
+def test_discovery_pieces_reproduce_the_oracle(model):
+    orc, x = model
+    P = orc.P
+    with recorded() as rec:
+        out, _ = orc.discovery_core(x["img"], x["cond"], (x["what_km1"], x["where_km1"], x["pres_tm1"], x["hidden"]), x["eps_where"],
+                                    x["eps_what"], x["u"])
+    cc = dict(img=x["img"], G=G, mode=3, scale_offset=P["disc.transform.scale_offset"], eps=x["eps_where"])
+    c3 = R.crop_forward(dict(tp=rec["disc.transform.l2"][0], bump=torch.zeros(B, 4, dtype=F64)), cc)
+    _close(c3["where"], out["where"]); _close(c3["where_loc"], out["where_loc"]); _close(c3["where_scale"], out["where_scale"])
+    _close(c3["glimpse"], rec["enc.glimpse:in"][0])
+    w0 = P["disc.steps.l0.w"]
+    assert w0.shape[0] == NH + NW
+    enc = rec["enc.what_head"][0]
+    tc = dict(eps=x["eps_what"], w_what=w0[NH:], w2=P["disc.steps.l1.w"][:, 0], b2=P["disc.steps.l1.b"][0], prev=x["pres_tm1"][:, 0], is_disc=True)
+    t = R.tail_forward(dict(enc_loc=enc[:, :NW], enc_raw=enc[:, NW:], bump=torch.zeros(B, NW, dtype=F64),
+                            s1_rest=rec["disc.steps.l0"][0] - out["what"] @ w0[NH:]), tc)
+    for k in ("what", "what_loc", "what_scale"):
+        _close(t[k], out[k])
+    _close(t["logit"], out["presence_logit"][:, 0])
+
+
+def test_gru_pieces_are_the_oracle_gru():
+    """h' and r h of the two element-wise pieces with the candidate's GEMM between them are oracle.gru; the adjoints the pieces give,
+    chained through that GEMM the way the pass chains them, are the gradient of oracle.gru with respect to the state."""
+    rng = np.random.default_rng(3)
+    nx, nh, rows = 9, 16, 6
+    P = {"g." + k: torch.as_tensor(rng.standard_normal(s) * 0.4) for k, s in
+         dict(wz=(nx, nh), uz=(nh, nh), bz=(nh,), wr=(nx, nh), ur=(nh, nh), br=(nh,), wh=(nx, nh), uh=(nh, nh), bh=(nh,)).items()}
+    xin, up = torch.as_tensor(rng.standard_normal((rows, nx))), torch.as_tensor(rng.standard_normal((rows, nh)))
+    h = torch.as_tensor(rng.standard_normal((rows, nh))).requires_grad_(True)
+    want = O.gru(P, "g", xin, h)
+    g_want, = torch.autograd.grad((up * want).sum(), h)
+    with torch.no_grad():
+        az = xin @ P["g.wz"] + h @ P["g.uz"] + P["g.bz"]
+        ar = xin @ P["g.wr"] + h @ P["g.ur"] + P["g.br"]
+        rh = torch.sigmoid(ar) * h
+        ah = xin @ P["g.wh"] + rh @ P["g.uh"] + P["g.bh"]
+        pieces = R.gru_forward(dict(az=az, ar=ar, ah=ah, h=h))
+    _close(pieces["h_new"], want); _close(pieces["rh"], rh)
+    tape = dict(z=torch.sigmoid(az).numpy(), r=torch.sigmoid(ar).numpy(), hc=torch.tanh(ah).numpy(), h=h.detach().numpy())
+    a = R.gru_adjoint(tape, dict(h_new=up.numpy(), rh=np.zeros((rows, nh))), F64)
+    d_rh = a["d_ah"] @ P["g.uh"].numpy().T
+    b = R.gru_adjoint(tape, dict(h_new=up.numpy(), rh=d_rh), F64)
+    total = b["d_h_a"] + b["d_h_b"] + b["d_az"] @ P["g.uz"].numpy().T + b["d_ar"] @ P["g.ur"].numpy().T
+    assert np.abs(total - g_want.numpy()).max() <= 1e-11 * np.abs(g_want.numpy()).max()
+
+
+def _fd(fn, x0, rng, h=1e-6, probes=6):
+    """Central differences of the scalar fn along random directions of the dict of arrays x0; returns [(fd, direction)]."""
+    res = []
+    for _ in range(probes):
+        v = {k: rng.standard_normal(a.shape) for k, a in x0.items()}
+        up = fn({k: a + h * v[k] for k, a in x0.items()})
+        dn = fn({k: a - h * v[k] for k, a in x0.items()})
+        res.append(((up - dn) / (2 * h), v))
+    return res
+
+
+def _stable_where(rng, rows, H, W, G_, scale=0.7):
+    """where logits whose every sampling coordinate is at least 1e-3 pixel from an integer (redrawn per row)."""
+    w = rng.standard_normal((rows, 4)) * scale
+    for _ in range(50):
+        bad = R.kink_margin(w, H, W, G_) < 1e-3
+        if not bad.any():
+            return w
+        w[bad] = rng.standard_normal((int(bad.sum()), 4)) * scale
+    raise AssertionError("no stable where draw")
+
+
+@pytest.mark.parametrize("is_disc,enc_pre", [(False, False), (True, True), (True, False)])
+def test_tail_adjoint_agrees_with_central_differences(is_disc, enc_pre):
+    rng = np.random.default_rng(7)
+    rows, nw, nsp = 4, 5, 8
+    consts = dict(eps=rng.standard_normal((rows, nw)), w_what=rng.standard_normal((nw, nsp)) * 0.5, w2=rng.standard_normal(nsp),
+                  b2=np.float64(0.3), prev=np.array([1.0, 0.0, 1.0, 1.0]), is_disc=is_disc)
+    x0 = dict(enc_loc=rng.standard_normal((rows, nw)), enc_raw=rng.standard_normal((rows, nw)), s1_rest=rng.standard_normal((rows, nsp)))
+    if not is_disc:
+        x0.update(hraw=rng.standard_normal((rows, 5 * nw)), what_tm1=rng.standard_normal((rows, nw)))
+    up = dict(what=rng.standard_normal((rows, nw)), what_loc=rng.standard_normal((rows, nw)), what_scale=rng.standard_normal((rows, nw)),
+              logit=rng.standard_normal(rows))
+    c = {k: (v if isinstance(v, bool) else torch.as_tensor(v)) for k, v in consts.items()}
+
+    def forward(x):
+        lv = {k: torch.as_tensor(v) for k, v in x.items()}
+        lv["bump"] = torch.zeros(rows, nw, dtype=F64)
+        return R.tail_forward(lv, c)
+
+    def objective(x):
+        o = forward(x)
+        return float(sum((torch.as_tensor(up[k]) * o[k]).sum() for k in up))
+    o = forward(x0)
+    enc_scale = (O.softplus(torch.as_tensor(x0["enc_raw"])) + 1e-2).numpy()
+    tape = dict(s1h=o["hidden"].numpy(), enc=np.concatenate([x0["enc_loc"], enc_scale], -1), hraw=x0.get("hraw"), what_tm1=x0.get("what_tm1"))
+    g = R.tail_adjoint(tape, consts, up, F64, enc_pre=enc_pre)
+    for fd, v in _fd(objective, x0, rng):
+        d_enc_scale = g["d_enc"][:, nw:] if enc_pre else g["d_enc"][:, nw:] * torch.sigmoid(torch.as_tensor(x0["enc_raw"])).numpy()
+        an = (g["d_s1pre"] * v["s1_rest"]).sum() + (g["d_enc"][:, :nw] * v["enc_loc"]).sum() + (d_enc_scale * v["enc_raw"]).sum()
+        if not is_disc:
+            an += (g["d_hraw"] * v["hraw"]).sum() + (g["d_what_tm1"] * v["what_tm1"]).sum()
+        assert abs(fd - an) <= 1e-7 * max(1.0, abs(an)), (fd, an)
+    # d_raw is the presence logit's upstream times the previous presence; the sample's total gradient includes the predictor's path
+    assert np.array_equal(g["d_raw"], up["logit"] * consts["prev"])
+    assert np.abs(g["d_what"] - up["what"]).max() > 1e-3 and np.array_equal((g["d_what"] - up["what"])[1], np.zeros(nw))
+
+
+@pytest.mark.parametrize("mode,fuse,dact", [(1, False, True), (1, False, False), (2, True, False), (2, False, True), (3, True, False)])
+def test_crop_adjoint_agrees_with_central_differences(mode, fuse, dact):
+    rng = np.random.default_rng(13 + mode)
+    rows, H, W, G_, nh = 5, 11, 13, 5, 12
+    where = _stable_where(rng, rows, H, W, G_)
+    where[0] = [2.0, 2.0, 2.5, -2.5]      # a glimpse mostly outside the frame
+    where[0] = where[0] if R.kink_margin(where[:1], H, W, G_)[0] >= 1e-3 else where[0] + 0.0123
+    consts = dict(img=rng.uniform(size=(rows, H, W)), G=G_, mode=mode, scale_offset=np.float64(-0.4), cholesky=np.linspace(-0.5, 0.6, 10),
+                  eps=rng.standard_normal((rows, 4)), w3=rng.standard_normal((nh, 8)) * 0.3)
+    mask = rng.uniform(0.05, 0.95, size=(rows, G_ * G_)) if mode != 3 else None
+    tape = dict(mask=mask)
+    if mode == 1:
+        tape.update(wb=rng.standard_normal((rows, 4)), where_tm1=None)
+        tape["where_tm1"] = where - 0.1 * tape["wb"]
+    else:
+        t2 = np.where(rng.uniform(size=(rows, nh)) < 0.5, rng.uniform(0.1, 2, size=(rows, nh)), -rng.uniform(0.05, 0.9, size=(rows, nh)))
+        tp = rng.standard_normal((rows, 8))
+        # where_tm1 (mode 2) chosen so that the sample lands on the stable where logits
+        cc = {k: (v if isinstance(v, int) else torch.as_tensor(v)) for k, v in consts.items()}
+        o = R.crop_forward(dict(tp=torch.as_tensor(tp), where_tm1=torch.zeros(rows, 4, dtype=F64), bump=torch.zeros(rows, 4, dtype=F64)), cc)
+        shift = where - o["where"].numpy()
+        if mode == 2:
+            tape["where_tm1"] = shift
+        else:
+            tp[:, :4] += shift
+        tape.update(tp=tp, t2=t2, where=where)
+    up = dict(glimpse=rng.standard_normal((rows, G_ * G_)), where=rng.standard_normal((rows, 4)), where_loc=rng.standard_normal((rows, 4)),
+              where_scale=rng.standard_normal((rows, 4)), mask=rng.standard_normal((rows, G_ * G_)))
+    g = R.crop_adjoint(tape, consts, up, F64, fuse_t3=fuse, mask_dact=dact)
+    # the same objective as a function of plain arrays
+    names = [k for k in ("where_tm1", "wb", "tp", "mask") if tape.get(k) is not None and not (k == "tp" and fuse)]
+    x0 = {k: np.asarray(tape[k], np.float64) for k in names}
+    if fuse:
+        x0["t2pre"] = R.inv_elu(torch.as_tensor(t2)).numpy()
+        tp_const = tp - O.elu(torch.as_tensor(x0["t2pre"])).numpy() @ consts["w3"]
+    if mask is not None and dact:
+        x0["maskpre"] = R.logit(torch.as_tensor(x0.pop("mask"))).numpy()
+
+    def objective(x):
+        cc = {k: (v if isinstance(v, int) else torch.as_tensor(v)) for k, v in consts.items()}
+        if fuse:
+            cc["tp_const"] = torch.as_tensor(tp_const)
+        lv = {k: torch.as_tensor(v) for k, v in x.items()}
+        if mode != 1:
+            lv["bump"] = torch.zeros(rows, 4, dtype=F64)
+        o = R.crop_forward(lv, cc)
+        return float(sum((torch.as_tensor(up[k]) * o[k]).sum() for k in up if k in o))
+    key = dict(where_tm1="d_where_tm1", wb="d_wb", tp="d_tp", t2pre="d_t2", mask="d_mask", maskpre="d_mask")
+    for fd, v in _fd(objective, x0, rng, h=1e-5):
+        an = sum((g[key[k]] * v[k]).sum() for k in x0)
+        assert abs(fd - an) <= 2e-6 * max(1.0, abs(an)), (fd, an)
+    if mode != 1:
+        assert np.abs(g["d_where"] - up["where"]).max() > 1e-3        # the crop's part is in the sample's total gradient
+
+
+def test_where_parameters_and_the_cholesky_order():
+    rng = np.random.default_rng(2)
+    rows = 37
+    d_where, eps, d_p, d_d = (rng.standard_normal((rows, 4)) for _ in range(4))
+    scale = rng.uniform(0.02, 1.5, size=(rows, 4))
+    got, tot = R.where_param_adjoint(d_where, scale, eps, d_p, d_d, F64, with_abs=True)
+    assert got.shape == tot.shape == (12,) and np.all(tot >= np.abs(got))
+    assert abs(got[10] - d_p.sum()) <= 1e-12 * tot[10] and abs(got[11] - d_d.sum()) <= 1e-12 * tot[11]
+    # central differences on the Cholesky vector
+    def objective(ch):
+        L = R.where_tril(torch.as_tensor(ch), torch.as_tensor(scale))
+        return float((torch.as_tensor(d_where) * (L @ torch.as_tensor(eps).unsqueeze(-1)).squeeze(-1)).sum())
+    for q in range(10):
+        e = np.zeros(10); e[q] = 1e-6
+        assert abs((objective(e) - objective(-e)) / 2e-6 - got[q]) <= 1e-8 * tot[q]
+    # one-hot: entry q of the vector is element (i, j) of fill_triangular's matrix, and nothing else
+    order = O.fill_triangular(torch.arange(1.0, 11.0, dtype=F64), 4).numpy()
+    assert order.tolist() == [[5, 0, 0, 0], [9, 10, 0, 0], [8, 7, 6, 0], [4, 3, 2, 1]]      # tfd.fill_triangular, n = 4
+    for i in range(4):
+        for j in range(i + 1):
+            dw, ee = np.zeros((1, 4)), np.zeros((1, 4))
+            dw[0, i], ee[0, j] = 2.0, 3.0
+            g = R.where_param_adjoint(dw, np.full((1, 4), 0.5), ee, np.zeros((1, 4)), np.zeros((1, 4)), F64)
+            want = np.zeros(12); want[int(order[i, j]) - 1] = 2.0 * 0.5 * 3.0
+            assert np.array_equal(g, want), (i, j, g)
+
+
+def test_inverted_activations_reproduce_the_tape_and_the_metric():
+    x = torch.linspace(-12, 12, 97, dtype=F64)
+    for act, inv in ((O.elu, R.inv_elu), (torch.sigmoid, R.logit), (torch.tanh, torch.atanh), (lambda v: O.softplus(v), R.inv_softplus)):
+        y = act(x).to(torch.float32).to(F64)           # the fp32 tape
+        assert torch.equal(act(inv(y)).to(torch.float32), y.to(torch.float32))
+    ref = np.array([[1.0, -4.0, 0.0], [0.0, 0.0, 0.0]])
+    assert R.row_scaled_error(ref, ref) == 0.0
+    assert R.row_scaled_error(ref + np.array([[0.0, 0.0, 0.4], [0, 0, 0]]), ref) == pytest.approx(0.1)
+    assert R.row_scaled_error(ref + np.array([[0.0, 0.0, 0.0], [0, 1e-30, 0]]), ref) == float("inf")   # a zero row is exact or wrong
+    assert R.row_scaled_error(np.array([1.0, 2.0]), np.array([1.5, 2.0]), scale=np.array([5.0, 5.0])) == pytest.approx(0.1)
+    assert R.bar_from_fp32(0.0) == 8 * 2.0 ** -23 and R.bar_from_fp32(1e-6) == 8e-6
+    p = R.Pitched(3, 4, 7, data=np.ones((3, 4)), nan=False, start=10, offset=2)
+    after = p.host.copy(); after[1:4, 2:6] = 5.0
+    assert p.untouched(after) and np.array_equal(p.view(after), np.full((3, 4), 5.0, np.float32))
+    after[0, 0] = 0.0
+    assert not p.untouched(after)
