@@ -714,6 +714,93 @@ int sqair_set_score(SqairHandle* h, const SqairLaneScore* score /* NULL: off */,
  * score. */
 int sqair_lane_score_test(SqairHandle* h, const float* box, const float* presence, const float* obj_id, const int32_t* map_count,
                           int T, int B, const SqairLaneScore* score, void* stream);
+/* Forecasts and lane tracks are scored by sqair_lane_traj_score, next. */
+
+/* ---- trajectory scoring: a lane forecast or a lane track table against the truth's trajectories ------------------------------
+ * The score above checks the lane's answer about the present.  sqair_lane_traj_score checks the two answers that reach over time --
+ * the lane forecast (SqairForecastLane, the future) and the lane tracks (SqairTraceLane, the past) -- against ground-truth boxes, on
+ * the device: does the predicted box land on the object f frames on, is alive / support an honest survival probability, how far is the
+ * smoothed box from where the object was.  Both tables list the same objects in the same layout, so one scorer serves both.  It is a
+ * stand-alone, capturable call: neither registered on the handle nor part of a pass; it runs after sqair_forecast_fan or
+ * sqair_history_trace_lane on the table either of them wrote (or on a caller's tensors: it is its own kernel-level entry), one launch
+ * of k_lane_traj_score.  The handle gives N and the error text only; it reads the table and the truth and writes only `score`.
+ * The table (SqairLaneTraj, read-only) holds the fields SqairForecastLane and SqairTraceLane share: best_row [B], presence, obj_id,
+ * support [B,N], box0 [B,N,4], alive [F,B,N], box_mean [F,B,N,4], count_prob [F,B,N+1], and valid_mass [F,B] (NULL: mass 1 everywhere,
+ * the forecast's case).  The truth (SqairTrajTruth): G in 1..16 slots per lane, truth identity IS the slot g as in sqair_set_score;
+ * the ANCHOR -- anchor_box [B,G,4], anchor_present [B,G], anchor_valid [B] -- is the truth at the frame the table's objects are read
+ * from, the last stepped frame (frame F-1 of lane tracks, the frame before f = 0 of a forecast); truth_box [F,B,G,4], truth_present
+ * [F,B,G], truth_valid [F,B] are the truth at the table's frames.  Boxes are fp32 (y, x, h, w) in pixels, masks int32 (nonzero = set).
+ * For each lane b:
+ * 0. Lane not scored.  anchor_valid[b] == 0: the lane is untouched -- no accumulator changes, the per-call outputs are -1 (integers)
+ *    and 0 (floats).  A valid anchor on a non-finite lane (best_row[b] == -1) counts one calls_invalid and changes nothing else; the
+ *    per-call outputs are -1 and 0 as well.
+ * 1. Link, once per call.  Candidates: anchor-present truth g x present lane object j (presence != 0); holes are allowed on both
+ *    sides.  IoU(g, j) = sq_box_iou(anchor_box[b,g], box0[b,j]), the estimate's device function on the fp32 words.  The assignment is
+ *    sq_assign_keep_greedy, the score's device function, unchanged (points 2 and 3 above: keep, then greedy one-to-one, ties to the
+ *    smallest g, then the smallest j; a NaN never wins), with iou_min, and with keep_id[b,g] against the obj_id words when keep_id is
+ *    given (a scorer's last_id: the truth stays with the identity it was last matched with).  link[b,g] = j or -1, link_iou[b,g] =
+ *    the pair's IoU (0 unlinked).  lane_counts[b,:] += (calls, calls_invalid, anchor_truth, linked): calls = 1 for a scored lane,
+ *    anchor_truth = the anchor-present truths, linked = those with link >= 0.
+ * 2. Per frame f that is scored -- truth_valid[f,b] != 0 and valid_mass[f,b] > 0 (a NULL valid_mass counts as positive) -- and each g
+ *    with j = link[b,g] >= 0:  p_alive[f,b,g] = p = alive[f,b,j] / support[b,j], an fp32 division; y = [truth_present[f,b,g] != 0];
+ *    brier = (p - y)^2 in fp32.
+ *      state 1, a pair: y and alive[f,b,j] > 0.  pair_iou[f,b,g] = sq_box_iou(truth_box[f,b,g], box_mean[f,b,j]); centre_err[f,b,g] =
+ *               the Euclidean distance in pixels between the two box centres (y + h/2, x + w/2), in fp32; hits += [pair_iou >= iou_min].
+ *      state 2, lost: y and alive[f,b,j] not positive -- the filter's paths do not hold a living object; a NaN box_mean is never read.
+ *      state 0, gone: not y.  Only the Brier term counts.
+ *    An unlinked g, or a frame that is not scored, gives state[f,b,g] = -1 and zeros (p_alive, pair_iou, centre_err).
+ * 3. Count, per scored frame.  count_map[f,b] = the first argmax of count_prob[f,b,:] (-1 for a frame not scored); n_truth = the
+ *    number of present truths of the frame, linked or not; count_hit += [count_map == n_truth], count_abs_err += |count_map - n_truth|.
+ * 4. Accumulators, per (frame, lane): counts[f,b,:] int64 = (frames, pairs, hits, lost, gone, count_hit, count_abs_err); sums[f,b,:]
+ *    fp64 = (iou_sum, centre_err_sum, brier_sum): each fp32 value converted to fp64 and added to the cell, g in index order.  They are
+ *    updated in place: one thread owns each cell (f, b) -- it reads, adds and writes; no float atomics -- so a replayed graph
+ *    accumulates the bits eager calls do.  The caller zeroes counts, sums and lane_counts to start.
+ * 5. Refused (return -1, text in sqair_last_error, before any HIP call): a NULL table, truth or score; a NULL best_row, presence,
+ *    support, box0, alive, box_mean, count_prob, anchor_box, anchor_present, anchor_valid, truth_box, truth_present, truth_valid,
+ *    counts, sums or lane_counts (obj_id, valid_mass, keep_id and the per-call outputs are optional); F outside 1..65535 or B < 1; G
+ *    outside 1..16; iou_min NaN or outside (0, 1]; a keep_id without a table obj_id.
+ * 6. Out of scope: optimal (Hungarian) assignment -- the link is greedy; calibration of box_std; trajectory scoring per particle
+ *    row; truth for departed objects (the tables list the objects of the last stepped frame only); a truth ring kept by the stream --
+ *    the caller brings the truth of the table's frames. */
+#define SQAIR_TRAJ_COUNTS 7
+#define SQAIR_TRAJ_SUMS 3
+#define SQAIR_TRAJ_LANE_COUNTS 4
+typedef struct SqairLaneTraj {
+  const int32_t* best_row;        /* [B] */
+  const float* presence;          /* [B,N] */
+  const float* obj_id;            /* [B,N]; NULL allowed without keep_id */
+  const float* support;           /* [B,N] */
+  const float* box0;              /* [B,N,4] */
+  const float* alive;             /* [F,B,N] */
+  const float* box_mean;          /* [F,B,N,4] */
+  const float* count_prob;        /* [F,B,N+1] */
+  const float* valid_mass;        /* [F,B]; NULL = 1 everywhere */
+} SqairLaneTraj;
+typedef struct SqairTrajTruth {
+  int32_t G;                      /* truth slots per lane, 1..16 */
+  const float* anchor_box;        /* [B,G,4] */
+  const int32_t* anchor_present;  /* [B,G] */
+  const int32_t* anchor_valid;    /* [B] */
+  const float* truth_box;         /* [F,B,G,4] */
+  const int32_t* truth_present;   /* [F,B,G] */
+  const int32_t* truth_valid;     /* [F,B] */
+  const int32_t* keep_id;         /* [B,G]; NULL = no keep */
+} SqairTrajTruth;
+typedef struct SqairTrajScore {
+  float iou_min;                  /* in (0, 1] */
+  int64_t* counts;                /* [F,B,7] in/out */
+  double* sums;                   /* [F,B,3] in/out */
+  int64_t* lane_counts;           /* [B,4] in/out */
+  int32_t* link;                  /* [B,G] */
+  float* link_iou;                /* [B,G] */
+  int32_t* state;                 /* [F,B,G] */
+  float* p_alive;                 /* [F,B,G] */
+  float* pair_iou;                /* [F,B,G] */
+  float* centre_err;              /* [F,B,G] */
+  int32_t* count_map;             /* [F,B] */
+} SqairTrajScore;
+int sqair_lane_traj_score(SqairHandle* h, const SqairLaneTraj* table, const SqairTrajTruth* truth, const SqairTrajScore* score, int F,
+                          int B, void* stream);
 
 /* ---- objective ---------------------------------------------------------------------------------
  * Fused IWAE / VIMCO reductions over [T,B,K] (reference: Model._build sqair/model.py:88-103,

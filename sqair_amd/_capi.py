@@ -144,6 +144,41 @@ class SqairLaneScore(C.Structure):
     _fields_ = [("iou_min", C.c_float), ("G", C.c_int32)] + [(n, C.c_void_p) for n in SCORE_INPUTS + SCORE_FIELDS]
 
 
+# trajectory scoring (include/sqair_hip.h: sqair_lane_traj_score): the three structs' pointer fields in declaration order, the int32
+# ones among the per-call outputs, the columns of ``counts`` [F, B, .], ``sums`` [F, B, .] and ``lane_counts`` [B, .]
+TRAJ_TABLE_FIELDS = ("best_row", "presence", "obj_id", "support", "box0", "alive", "box_mean", "count_prob", "valid_mass")
+TRAJ_TABLE_OPTIONAL = ("obj_id", "valid_mass")
+TRAJ_TRUTH_FIELDS = ("anchor_box", "anchor_present", "anchor_valid", "truth_box", "truth_present", "truth_valid", "keep_id")
+TRAJ_ACCUMULATORS = ("counts", "sums", "lane_counts")
+TRAJ_FIELDS = ("link", "link_iou", "state", "p_alive", "pair_iou", "centre_err", "count_map")
+TRAJ_INT_FIELDS = ("link", "state", "count_map")
+TRAJ_COUNTS = ("frames", "pairs", "hits", "lost", "gone", "count_hit", "count_abs_err")
+TRAJ_SUMS = ("iou_sum", "centre_err_sum", "brier_sum")
+TRAJ_LANE_COUNTS = ("calls", "calls_invalid", "anchor_truth", "linked")
+
+
+def traj_shapes(F, B, G):
+    """The per-call outputs' shapes for a table of F frames and G truth slots per lane."""
+    return dict(link=(B, G), link_iou=(B, G), state=(F, B, G), p_alive=(F, B, G), pair_iou=(F, B, G), centre_err=(F, B, G),
+                count_map=(F, B))
+
+
+class SqairLaneTraj(C.Structure):
+    """The table a lane forecast or a lane trace wrote, as the trajectory score reads it (include/sqair_hip.h:
+    sqair_lane_traj_score); device addresses, obj_id and valid_mass optional."""
+    _fields_ = [(n, C.c_void_p) for n in TRAJ_TABLE_FIELDS]
+
+
+class SqairTrajTruth(C.Structure):
+    """The truth of a trajectory score: the anchor and the table's frames; device addresses, keep_id optional."""
+    _fields_ = [("G", C.c_int32)] + [(n, C.c_void_p) for n in TRAJ_TRUTH_FIELDS]
+
+
+class SqairTrajScore(C.Structure):
+    """The accumulators (required) and the per-call outputs (TRAJ_FIELDS, optional) of a trajectory score; device addresses."""
+    _fields_ = [("iou_min", C.c_float)] + [(n, C.c_void_p) for n in TRAJ_ACCUMULATORS + TRAJ_FIELDS]
+
+
 # track history (include/sqair_hip.h: sqair_set_history): the bit of each field a ring slot may hold; the first three are mandatory
 HISTORY_FIELDS = {"where": 1, "presence": 2, "obj_id": 4, "what": 8, "log_weights_per_timestep": 16}
 HISTORY_MANDATORY = ("where", "presence", "obj_id")
@@ -343,6 +378,8 @@ _PROTOS = {
     "sqair_lane_layers_test": (C.c_int, [C.c_void_p] * 6 + [C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(SqairLaneLayers), C.c_void_p]),
     "sqair_set_score": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneScore), C.c_int, C.c_int]),
     "sqair_lane_score_test": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.POINTER(SqairLaneScore), C.c_void_p]),
+    "sqair_lane_traj_score": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneTraj), C.POINTER(SqairTrajTruth), C.POINTER(SqairTrajScore),
+                                        C.c_int, C.c_int, C.c_void_p]),
     "sqair_forecast_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
     "sqair_forecast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                  C.POINTER(SqairForecastOutputs), C.c_void_p, C.c_int64, C.c_void_p]),

@@ -437,6 +437,16 @@ struct LaneScoreArgs {
   int T, B, N;
 };
 int sq_launch_lane_score(const LaneScoreArgs& a, hipStream_t s);
+// Trajectory scoring (sqair_lane_traj_score; include/sqair_hip.h states the semantics): k_lane_traj_score, grid (lane b, chunk of
+// SQ_TRAJ_FRAMES frames): every workgroup recomputes its lane's link, then thread = frame, looping over the truth slots.
+constexpr int SQ_TRAJ_FRAMES = 256;
+struct LaneTrajScoreArgs {
+  SqairLaneTraj tab;                   // the lane forecast's or the lane tracks' table (or a test's buffers)
+  SqairTrajTruth tr;                   // G, the anchor, the truth of the table's frames, keep_id
+  SqairTrajScore sc;                   // iou_min, the accumulators and the per-call outputs
+  int F, B, N;
+};
+int sq_launch_lane_traj_score(const LaneTrajScoreArgs& a, hipStream_t s);
 
 // Object forecasts (sqair_forecast_fan; include/sqair_hip.h states the semantics).  Fan-out: rollout row q = r * S + s.
 // k_forecast_fan_src expands the source map, src_fan[q] = src[q / S] (NULL: q / S), an index outside [0, R) of the blob -> -1.

@@ -1,5 +1,5 @@
 // The per-lane answers: the kernels that turn a lane's K particle rows into one answer per lane -- the SMC resampler, the forecast
-// summaries, the lane estimate, the object layers, the stream score, the lane forecast and the lane tracks.  None of them is a hop of the frame loop (once per pass or
+// summaries, the lane estimate, the object layers, the stream score, the lane forecast, the lane tracks and the trajectory score of those two.  None of them is a hop of the frame loop (once per pass or
 // per call, on B workgroups), and they are a translation unit -- a code object -- of their own so that work on them moves no kernel of the pass
 // (DESIGN.md section 3h).  Their compositions are the device functions of sqair_lane.h.  Every lane-wide sum is one thread's loop in
 // index order: the same bits on every replay, and K <= 256 adds are nothing next to the pass.
@@ -664,5 +664,120 @@ __global__ __launch_bounds__(256) void k_lane_score(const LaneScoreArgs a SQ_TLP
 }
 int sq_launch_lane_score(const LaneScoreArgs& a, hipStream_t s) {
   SQ_LAUNCH(k_lane_score, dim3(a.B), dim3(256), 0, s, a);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Trajectory scoring (sqair_lane_traj_score; LaneTrajScoreArgs in sqair_glue.h; the semantics: include/sqair_hip.h, points 0-6)
+// ------------------------------------------------------------------------------------------------
+// k_lane_traj_score: grid (lane b, chunk z of SQ_TRAJ_FRAMES frames).  Every workgroup recomputes its lane's link -- thread i < G * N
+// fills entry (g, j) = (i / N, i % N) of the IoU table in LDS (-1 for a pair that is no candidate; every pair of a lane that is not
+// scored), thread 0 walks it (sq_assign_keep_greedy) -- and chunk 0 alone writes lane_counts and the [B, G] outputs.  Then thread =
+// frame f = z * SQ_TRAJ_FRAMES + tid, looping over the truth slots with the link read from LDS: it owns the cells (f, b) of counts
+// and sums.  The barriers are met by every thread: what differs between lanes is what the threads store around them.
+__global__ __launch_bounds__(256) void k_lane_traj_score(const LaneTrajScoreArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ float s_iou[SQ_SCORE_MAXG * SQ_MAXN];
+  __shared__ int s_keep[SQ_SCORE_MAXG], s_gm[SQ_SCORE_MAXG], s_apres[SQ_SCORE_MAXG];
+  __shared__ int s_id[SQ_MAXN], s_claim[SQ_MAXN];
+  const SqairLaneTraj& t = a.tab;
+  const SqairTrajTruth& u = a.tr;
+  const SqairTrajScore& o = a.sc;
+  const int b = blockIdx.x, tid = threadIdx.x, G = u.G, N = a.N;
+  const bool anchored = u.anchor_valid[b] != 0;
+  const bool lane_on = anchored && t.best_row[b] != -1;   // (a non-finite lane has no objects to link)
+  // ---- 1: the link
+  if (tid < G * N) {
+    const int g = tid / N, j = tid - g * N;
+    float v = -1.0f;
+    if (lane_on && u.anchor_present[(size_t)b * G + g] != 0 && t.presence[(size_t)b * N + j] != 0.0f) {
+      const float* p = u.anchor_box + ((size_t)b * G + g) * 4;
+      const float* q = t.box0 + ((size_t)b * N + j) * 4;
+      v = sq_box_iou(SqBox{p[0], p[1], p[2], p[3]}, SqBox{q[0], q[1], q[2], q[3]});
+    }
+    s_iou[tid] = v;
+  }
+  if (tid < G) {
+    s_apres[tid] = lane_on && u.anchor_present[(size_t)b * G + tid] != 0;
+    s_keep[tid] = u.keep_id ? u.keep_id[(size_t)b * G + tid] : -1;
+  }
+  if (tid < N) s_id[tid] = t.obj_id ? (int)sq_word(t.obj_id + (size_t)b * N + tid) : 0;
+  __syncthreads();
+  if (tid == 0) sq_assign_keep_greedy(s_iou, N, G, N, o.iou_min, u.keep_id ? s_keep : nullptr, s_id, s_gm, s_claim);
+  __syncthreads();
+  if (blockIdx.y == 0) {
+    if (tid < G) {
+      const int j = s_gm[tid];
+      if (o.link) o.link[(size_t)b * G + tid] = j;
+      if (o.link_iou) o.link_iou[(size_t)b * G + tid] = j >= 0 ? s_iou[tid * N + j] : 0.0f;
+    }
+    if (tid == 0 && anchored) {
+      int64_t* c = o.lane_counts + (size_t)b * SQAIR_TRAJ_LANE_COUNTS;
+      if (!lane_on) {
+        c[1] += 1;
+      } else {
+        int n_anchor = 0, n_link = 0;
+        for (int g = 0; g < G; ++g) { n_anchor += s_apres[g]; n_link += s_gm[g] >= 0; }
+        c[0] += 1; c[2] += n_anchor; c[3] += n_link;
+      }
+    }
+  }
+  // ---- 2, 3, 4: one frame per thread
+  const int f = blockIdx.y * SQ_TRAJ_FRAMES + tid;
+  if (f >= a.F) return;   // (past the last barrier)
+  const size_t fb = (size_t)f * a.B + b;
+  const bool on = lane_on && u.truth_valid[fb] != 0 && (!t.valid_mass || t.valid_mass[fb] > 0.0f);
+  long long c_pairs = 0, c_hits = 0, c_lost = 0, c_gone = 0;
+  double* sum = o.sums + fb * SQAIR_TRAJ_SUMS;
+  double iou_sum = 0.0, err_sum = 0.0, brier_sum = 0.0;
+  if (on) { iou_sum = sum[0]; err_sum = sum[1]; brier_sum = sum[2]; }
+  int n_truth = 0;
+  for (int g = 0; g < G; ++g) {
+    const int j = s_gm[g];
+    const bool y = on && u.truth_present[fb * G + g] != 0;
+    n_truth += y;
+    int st = -1;
+    float p = 0.0f, iou = 0.0f, err = 0.0f;
+    if (on && j >= 0) {
+      const float al = t.alive[fb * N + j];
+      p = al / t.support[(size_t)b * N + j];
+      const float d = p - (y ? 1.0f : 0.0f);
+      brier_sum += (double)(d * d);
+      if (!y) {
+        st = 0; ++c_gone;
+      } else if (al > 0.0f) {
+        st = 1; ++c_pairs;
+        const float* tb = u.truth_box + (fb * G + g) * 4;
+        const float* q = t.box_mean + (fb * N + j) * 4;
+        iou = sq_box_iou(SqBox{tb[0], tb[1], tb[2], tb[3]}, SqBox{q[0], q[1], q[2], q[3]});
+        const float dy = (tb[0] + 0.5f * tb[2]) - (q[0] + 0.5f * q[2]), dx = (tb[1] + 0.5f * tb[3]) - (q[1] + 0.5f * q[3]);
+        err = sqrtf(dy * dy + dx * dx);
+        c_hits += iou >= o.iou_min;
+        iou_sum += (double)iou; err_sum += (double)err;
+      } else {
+        st = 2; ++c_lost;   // (box_mean is NaN there: not read)
+      }
+    }
+    if (o.state) o.state[fb * G + g] = st;
+    if (o.p_alive) o.p_alive[fb * G + g] = p;
+    if (o.pair_iou) o.pair_iou[fb * G + g] = iou;
+    if (o.centre_err) o.centre_err[fb * G + g] = err;
+  }
+  int cm = -1;
+  if (on) {
+    const float* cp = t.count_prob + fb * (N + 1);
+    float top = cp[0];
+    cm = 0;
+    for (int c = 1; c <= N; ++c)
+      if (cp[c] > top) { top = cp[c]; cm = c; }
+    int64_t* c = o.counts + fb * SQAIR_TRAJ_COUNTS;
+    c[0] += 1; c[1] += c_pairs; c[2] += c_hits; c[3] += c_lost; c[4] += c_gone; c[5] += cm == n_truth;
+    c[6] += cm > n_truth ? cm - n_truth : n_truth - cm;
+    sum[0] = iou_sum; sum[1] = err_sum; sum[2] = brier_sum;
+  }
+  if (o.count_map) o.count_map[fb] = cm;
+}
+int sq_launch_lane_traj_score(const LaneTrajScoreArgs& a, hipStream_t s) {
+  SQ_LAUNCH(k_lane_traj_score, dim3(a.B, (a.F + SQ_TRAJ_FRAMES - 1) / SQ_TRAJ_FRAMES), dim3(256), 0, s, a);
   return 0;
 }

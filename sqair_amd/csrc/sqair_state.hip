@@ -317,6 +317,30 @@ extern "C" int sqair_lane_score_test(SqairHandle* h, const float* box, const flo
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }
+// trajectory scoring (include/sqair_hip.h: sqair_lane_traj_score): a stand-alone call on the table a lane forecast or a lane trace
+// wrote -- or on a test's tensors --, nothing registered on the handle, which gives N and the error text
+extern "C" int sqair_lane_traj_score(SqairHandle* h, const SqairLaneTraj* table, const SqairTrajTruth* truth, const SqairTrajScore* score,
+                                     int F, int B, void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_lane_traj_score: ";
+  if (!table || !truth || !score) return sq_no(h, who + "table, truth and score must not be NULL");
+  if (F < 1 || F > 65535 || B < 1) return sq_no(h, who + "F = " + std::to_string(F) + " must lie in 1..65535 and B = " + std::to_string(B) + " must be >= 1");
+  if (truth->G < 1 || truth->G > SQ_SCORE_MAXG)
+    return sq_no(h, who + "G = " + std::to_string(truth->G) + " must lie in 1.." + std::to_string(SQ_SCORE_MAXG));
+  if (!(score->iou_min > 0.0f && score->iou_min <= 1.0f)) return sq_no(h, who + "iou_min must lie in (0, 1]");   // (NaN fails both)
+  if (!table->best_row || !table->presence || !table->support || !table->box0 || !table->alive || !table->box_mean || !table->count_prob)
+    return sq_no(h, who + "the table's best_row, presence, support, box0, alive, box_mean and count_prob must not be NULL");
+  if (!truth->anchor_box || !truth->anchor_present || !truth->anchor_valid || !truth->truth_box || !truth->truth_present || !truth->truth_valid)
+    return sq_no(h, who + "anchor_box, anchor_present, anchor_valid, truth_box, truth_present and truth_valid must not be NULL");
+  if (!score->counts || !score->sums || !score->lane_counts) return sq_no(h, who + "counts, sums and lane_counts must not be NULL");
+  if (truth->keep_id && !table->obj_id) return sq_no(h, who + "keep_id needs the table's obj_id: the identities it is compared with");
+  LaneTrajScoreArgs a; memset(&a, 0, sizeof(a));
+  a.tab = *table; a.tr = *truth; a.sc = *score;
+  a.F = F; a.B = B; a.N = h->cfg.n_steps_per_image;
+  sq_launch_lane_traj_score(a, (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
 
 // the refusals of a carried training call (host only: before any HIP call)
 int sq_carry_refusal(SqairHandle* h, const char* fn, int B, const SqairCarry* carry, const SqairOutputs* out) {

@@ -64,6 +64,13 @@ and ``score()`` reads the accumulators: per lane ``frames``, ``frames_invalid``,
 ``count_hit``, ``count_abs_err`` and ``iou_sum``, pooled ``mota``, ``motp`` and ``count_accuracy``.  ``reset(lanes)`` also forgets
 those lanes' identities (a new clip has new ones) and keeps their counters.
 
+``forecast(..., lane=True, truth=...)`` and ``tracks(..., lane=True, truth=...)`` score the two answers that reach over time -- the
+lane forecast and the lane tracks -- against the truth's trajectories with one more launch after the call's own (include/sqair_hip.h:
+sqair_lane_traj_score, which states the semantics): truth and lane objects are linked once, at the last stepped frame, and every
+horizon or traced frame then gives displacement error, IoU, the Brier term of ``alive / support`` as a survival probability and the
+count's hit, accumulated on the device per (frame, lane); ``trajectory_score(kind)`` reads the sums and pools them into curves over
+the horizon (``ade``, ``fde``, ``mean_iou``, ``hit_rate``, ``brier``, ``count_accuracy``) without a lane table ever visiting the host.
+
 The stream takes over its core's handle: while it is open, every inference pass of that handle carries the state.  ``close()``
 hands the handle back.
 
@@ -154,6 +161,7 @@ class SqairStream(object):
         self._graph = False
         self._tr = {}               # tracks() buffers of the LAST (lag, start, max_tracks, table, lane, lane_iou) only
         self._fc = {}               # forecast buffers of the LAST (F, outputs, summaries, samples, lane) only: workspace, noise, map, weights, outputs
+        self._traj = {}             # trajectory scores by kind ("forecast", "tracks"): accumulators and outputs of the LAST (F, G, truth_iou)
         self._smc_uniforms = None   # registered with the caller's uniforms (True) or Philox (False)
         core.stream.synchronize()
         core.check(core.lib.sqair_set_state(core.handle, cs.state.data_ptr(), cs.state.data_ptr(), cs._src.data_ptr(),
@@ -362,8 +370,123 @@ class SqairStream(object):
         res["count_accuracy"] = div(tot["count_hit"], tot["frames"])
         return res
 
+    # ---- trajectory scoring ------------------------------------------------------------------------------------------------
+    def _check_traj_truth(self, fn, truth, lane, F, default_anchor, link_ids, truth_iou):
+        """``truth`` of ``forecast`` / ``tracks`` as {name: tensor} in the C ABI's names and dtypes plus ``G`` and ``iou_min`` (None: no
+        truth); everything is checked here, before the core is touched."""
+        if truth is None:
+            if link_ids:
+                raise ValueError(fn + "link_ids is for a call with truth")
+            return None
+        if not lane:
+            raise ValueError(fn + "truth is for a call with lane=True: the lane table is what is scored")
+        names = {"box", "present", "valid", "anchor_box", "anchor_present", "anchor_valid"}
+        if not isinstance(truth, dict) or "box" not in truth or "present" not in truth or set(truth) - names:
+            raise ValueError(fn + "truth must be a dict with box, present and optionally valid, anchor_box, anchor_present, anchor_valid")
+        truth_iou = float(truth_iou)
+        if not 0.0 < truth_iou <= 1.0:   # (NaN fails too)
+            raise ValueError(fn + "truth_iou must lie in (0, 1]")
+        B = self.B
+        box = torch.as_tensor(truth["box"]).to(torch.float32)
+        present = torch.as_tensor(truth["present"])
+        if box.dim() != 4 or not 1 <= box.shape[2] <= _capi.SCORE_MAX_TRUTH:
+            raise ValueError(fn + "truth['box'] of shape {} given, [{}, {}, G, 4] with G in [1, {}] expected".format(
+                tuple(box.shape), F, B, _capi.SCORE_MAX_TRUTH))
+        G = int(box.shape[2])
+        def shaped(items):
+            for name, t, shp in items:
+                if tuple(t.shape) != shp:
+                    raise ValueError(fn + "truth[{!r}] of shape {} given, {} expected".format(name, tuple(t.shape), list(shp)))
+        given = truth.get("valid") is not None
+        valid = torch.as_tensor(truth["valid"]) if given else torch.ones((F, B), dtype=torch.int32)
+        shaped((("box", box, (F, B, G, 4)), ("present", present, (F, B, G)), ("valid", valid, (F, B))))
+        if (truth.get("anchor_box") is None) != (truth.get("anchor_present") is None):
+            raise ValueError(fn + "truth['anchor_box'] and truth['anchor_present'] come together")
+        a_valid = truth.get("anchor_valid")
+        if truth.get("anchor_box") is None:
+            if not default_anchor:
+                raise ValueError(fn + "a forecast's truth needs anchor_box and anchor_present: the truth at the last stepped frame, "
+                                      "which is none of the forecast's frames")
+            a_box, a_present = box[-1], present[-1]   # (a trace's newest frame is the last stepped one)
+            if a_valid is None and given:
+                a_valid = valid[-1]
+        else:
+            a_box, a_present = torch.as_tensor(truth["anchor_box"]).to(torch.float32), torch.as_tensor(truth["anchor_present"])
+        a_valid = torch.ones((B,), dtype=torch.int32) if a_valid is None else torch.as_tensor(a_valid)
+        shaped((("anchor_box", a_box, (B, G, 4)), ("anchor_present", a_present, (B, G)), ("anchor_valid", a_valid, (B,))))
+        if link_ids and not (self.scored and G == self.G):
+            raise ValueError(fn + "link_ids is for a stream with score=True and the same G: it keeps a truth with the identity the "
+                                  "stream's score last matched it with")
+        as_mask = lambda m: m if m.dtype == torch.int32 else (m != 0).to(torch.int32)
+        return dict(G=G, iou_min=truth_iou, truth_box=box, truth_present=as_mask(present), truth_valid=as_mask(valid), anchor_box=a_box,
+                    anchor_present=as_mask(a_present), anchor_valid=as_mask(a_valid))
+
+    def _traj_score(self, kind, table, F, truth, link_ids):
+        """Scores the lane table a forecast or a trace has just written (``table``: its device buffers by field) against ``truth``
+        (of _check_traj_truth) with one launch on the core's stream (include/sqair_hip.h: sqair_lane_traj_score); returns the
+        per-call outputs, copies.  The accumulators of ``kind`` are kept for the last (F, G, truth_iou) scored."""
+        core = self.core
+        G, key = truth["G"], (F, truth["G"], truth["iou_min"])
+        ts = self._traj.get(kind)
+        if ts is None or ts["key"] != key:   # (another F, G or threshold: the old sums would not mean the same)
+            z = lambda shp, dt: torch.zeros(shp, dtype=dt, device=core.device)
+            ts = self._traj[kind] = dict(key=key, counts=z((F, self.B, len(_capi.TRAJ_COUNTS)), torch.int64),
+                                         sums=z((F, self.B, len(_capi.TRAJ_SUMS)), torch.float64),
+                                         lane_counts=z((self.B, len(_capi.TRAJ_LANE_COUNTS)), torch.int64))
+            ts["flat"], ts["views"] = _field_views(_capi.traj_shapes(F, self.B, G), _capi.TRAJ_INT_FIELDS, core.device)
+            ts["out"] = ts["views"](ts["flat"])
+        dev = {n: truth[n].to(core.device, non_blocking=True).contiguous() for n in _capi.TRAJ_TRUTH_FIELDS if n != "keep_id"}
+        c_tab = _capi.SqairLaneTraj(**{n: table[n].data_ptr() for n in _capi.TRAJ_TABLE_FIELDS if n in table})
+        c_truth = _capi.SqairTrajTruth(G=G, keep_id=self._score["last_id"].data_ptr() if link_ids else None,
+                                       **{n: t.data_ptr() for n, t in dev.items()})
+        c_score = _capi.SqairTrajScore(iou_min=truth["iou_min"], **{n: ts[n].data_ptr() for n in _capi.TRAJ_ACCUMULATORS},
+                                       **{n: t.data_ptr() for n, t in ts["out"].items()})
+        core.check(core.lib.sqair_lane_traj_score(core.handle, C.byref(c_tab), C.byref(c_truth), C.byref(c_score), F, self.B,
+                                                  core._stream()), "sqair_lane_traj_score")
+        return ts["views"](ts["flat"].clone())
+
+    def trajectory_score(self, kind, reset=False):
+        """The trajectory score so far of ``kind`` = "forecast" or "tracks" (include/sqair_hip.h: sqair_lane_traj_score): what the
+        calls with ``truth`` have accumulated.  Per (frame or horizon f, lane) the int64 counters ``frames``, ``pairs``, ``hits``,
+        ``lost``, ``gone``, ``count_hit``, ``count_abs_err`` [F, B] and the fp64 ``iou_sum``, ``centre_err_sum``, ``brier_sum`` [F, B]; per
+        lane ``calls``, ``calls_invalid``, ``anchor_truth``, ``linked`` [B] (host tensors).  Pooled over the lanes, per f, NaN where the
+        denominator is 0: ``ade`` = centre_err_sum / pairs (``fde`` = its last entry), ``mean_iou`` = iou_sum / pairs, ``hit_rate`` =
+        hits / (pairs + lost), ``brier`` = brier_sum / (pairs + lost + gone), ``count_accuracy`` = count_hit / frames [F] (float64), and
+        ``link_rate`` = linked / anchor_truth.  The accumulators belong to (kind, F, G, truth_iou): a call with truth of another F, G
+        or threshold starts fresh ones and drops the old.  ``reset``: they start again from zero afterwards."""
+        if kind not in ("forecast", "tracks"):
+            raise ValueError("SqairStream.trajectory_score: kind must be 'forecast' or 'tracks'")
+        ts = self._traj.get(kind)
+        if ts is None:
+            raise ValueError("SqairStream.trajectory_score: no {} call has been scored yet ({}(..., lane=True, truth=...))".format(kind, kind))
+        core = self.core
+        with torch.cuda.device(core.device):
+            core._join_in()
+            with core.on_stream():
+                acc = {n: ts[n].clone() for n in _capi.TRAJ_ACCUMULATORS}
+                if reset:
+                    for n in _capi.TRAJ_ACCUMULATORS:
+                        ts[n].zero_()
+            core._join_out()
+            acc = {n: t.cpu() for n, t in acc.items()}
+        res = {n: acc["counts"][..., i].clone() for i, n in enumerate(_capi.TRAJ_COUNTS)}
+        res.update({n: acc["sums"][..., i].clone() for i, n in enumerate(_capi.TRAJ_SUMS)})
+        res.update({n: acc["lane_counts"][:, i].clone() for i, n in enumerate(_capi.TRAJ_LANE_COUNTS)})
+        tot = {n: res[n].sum(1).to(torch.float64) for n in _capi.TRAJ_COUNTS + _capi.TRAJ_SUMS}
+        div = lambda a, b: torch.where(b > 0, a / torch.where(b > 0, b, torch.ones_like(b)), torch.full_like(b, float("nan")))
+        res["ade"] = div(tot["centre_err_sum"], tot["pairs"])
+        res["fde"] = float(res["ade"][-1])
+        res["mean_iou"] = div(tot["iou_sum"], tot["pairs"])
+        res["hit_rate"] = div(tot["hits"], tot["pairs"] + tot["lost"])
+        res["brier"] = div(tot["brier_sum"], tot["pairs"] + tot["lost"] + tot["gone"])
+        res["count_accuracy"] = div(tot["count_hit"], tot["frames"])
+        linked, anchors = int(res["linked"].sum()), int(res["anchor_truth"].sum())
+        res["link_rate"] = float(linked) / anchors if anchors else float("nan")
+        return res
+
     # ---- forecasting ------------------------------------------------------------------------------------------------------
-    def forecast(self, F, noise=None, seed=None, outputs=FORECAST_OUTPUTS, summaries=True, samples=1, lane=False, lane_iou=0.5):
+    def forecast(self, F, noise=None, seed=None, outputs=FORECAST_OUTPUTS, summaries=True, samples=1, lane=False, lane_iou=0.5,
+                 truth=None, link_ids=False, truth_iou=0.5):
         """Rolls the generative prior F frames forward from the rows the next ``step()`` would start from -- the state blob through
         the pending source map (a reset or resample armed since the last step, else identity; with SMC the map the resampler
         wrote) -- and returns {name: [F, B*K, ...]} for ``outputs`` (of FORECAST_OUTPUTS).  With ``summaries`` also the lanes'
@@ -380,7 +503,16 @@ class SqairStream(object):
         start from), the best start row's objects ``obj_id``, ``presence`` [B, N] and ``box0`` [B, N, 4] (y, x, h, w in pixels),
         ``support`` [B, N], and per horizon ``alive`` [F, B, N] (the weight of the rollouts in which the object still lives),
         ``box_mean`` / ``box_std`` [F, B, N, 4] over those rollouts (NaN where none is left) and ``count_prob`` [F, B, N + 1];
-        ``lane_iou``: the association threshold on the start rows, as a stream's ``estimate_iou``."""
+        ``lane_iou``: the association threshold on the start rows, as a stream's ``estimate_iou``.
+        ``truth`` (with ``lane=True``) scores the lane forecast against ground-truth boxes on the device, one more launch after the
+        forecast's (include/sqair_hip.h: sqair_lane_traj_score, which states the semantics): dict(box=[F, B, G, 4] (y, x, h, w) in
+        pixels, present=[F, B, G], valid=[F, B] or None = all -- the truth at the forecast's frames --, anchor_box=[B, G, 4],
+        anchor_present=[B, G], anchor_valid=[B] or None = all -- the truth at the last stepped frame, required: truth and lane objects
+        are linked there, by IoU >= ``truth_iou``); G in [1, 16] comes from the shapes, tensors already on the device are used where
+        they are.  ``res["lane"]["score"]`` holds ``link``, ``link_iou`` [B, G], ``state``, ``p_alive``, ``pair_iou``, ``centre_err`` [F, B, G]
+        and ``count_map`` [F, B]; ``trajectory_score("forecast")`` reads what the calls have accumulated.  ``link_ids=True`` (a stream
+        with ``score=True`` and the same G) keeps each truth with the identity the stream's score last matched it with.  Without
+        ``truth`` nothing is launched, and with it every other output is unchanged bit for bit."""
         F, S, lane, lane_iou = int(F), int(samples), bool(lane), float(lane_iou)
         if F < 1:
             raise ValueError("SqairStream.forecast: F must be >= 1")
@@ -392,6 +524,7 @@ class SqairStream(object):
         bad = [n for n in outputs if n not in FORECAST_OUTPUTS]
         if bad:
             raise ValueError("SqairStream.forecast: unknown outputs {} (choose from {})".format(bad, FORECAST_OUTPUTS))
+        truth = self._check_traj_truth("SqairStream.forecast: ", truth, lane, F, False, link_ids, truth_iou)
         core, cs = self.core, self.carried
         lib, dev = core.lib, core.device
         R, N, nzw = self.R * S, core.N, core.nzw
@@ -432,8 +565,11 @@ class SqairStream(object):
                                                       F, self.B, S, src.data_ptr(), C.byref(c_out), c_lane, fc["ws"].data_ptr(),
                                                       fc["ws"].numel() * 4, core._stream()), "sqair_forecast_fan")
                 res = {k: v.clone() for k, v in out.items()}
+                score = None if truth is None else self._traj_score("forecast", fc["lane"], F, truth, link_ids)
                 if lane:   # (views of one allocation: one copy, not one per field)
                     res["lane"] = fc["lane_views"](fc["lane_flat"].clone())
+                    if score is not None:
+                        res["lane"]["score"] = score
                 if summaries:
                     res["weights"] = torch.softmax(lw.reshape(self.B, self.K), -1)
             core._join_out()
@@ -464,7 +600,8 @@ class SqairStream(object):
         return fc
 
     # ---- track history ----------------------------------------------------------------------------------------------------
-    def tracks(self, lag=None, start="next", max_tracks=None, table=True, lane=False, lane_iou=0.5):
+    def tracks(self, lag=None, start="next", max_tracks=None, table=True, lane=False, lane_iou=0.5, truth=None, link_ids=False,
+               truth_iou=0.5):
         """Traces every particle row's ancestral path back over the last ``lag`` steps (default: all ``history`` kept) on the
         device: frames oldest -> newest, F = lag * frames_per_step.  ``start="next"``: from the rows the next ``step()`` would
         start from (the pending source map; with SMC the map the resampler wrote: the equally weighted surviving set), as
@@ -485,7 +622,11 @@ class SqairStream(object):
         between the same two steps --, ``first_frame`` [B, N] (the oldest frame the best row's own path holds the object from), and
         per traced frame ``alive`` [F, B, N] (the weight of the particles whose path holds the object there), ``box_mean`` /
         ``box_std`` [F, B, N, 4] over them (NaN where none does), ``count_prob`` [F, B, N + 1] and ``valid_mass`` [F, B] (the weight of
-        the paths that reach back to the frame: ``count_prob`` sums to it, not to 1); ``lane_iou``: the association threshold."""
+        the paths that reach back to the frame: ``count_prob`` sums to it, not to 1); ``lane_iou``: the association threshold.
+        ``truth``, ``link_ids``, ``truth_iou`` (with ``lane=True``): the lane tracks scored against ground-truth boxes as ``forecast``'s
+        lane answer is, ``truth["box"]`` [F, B, G, 4] and ``truth["present"]`` [F, B, G] being the truth at the traced frames; the anchor
+        defaults to their frame F - 1 (and ``anchor_valid`` to ``valid[F - 1]``), the last stepped frame; frames no path reaches back to
+        (``valid_mass`` 0) are not scored.  ``res["lane"]["score"]`` and ``trajectory_score("tracks")`` as there."""
         core, cs = self.core, self.carried
         if cs.ring is None:
             raise ValueError("SqairStream.tracks: the stream keeps no history (SqairStream(..., history=L))")
@@ -504,6 +645,7 @@ class SqairStream(object):
         if lane and not 0.0 < lane_iou <= 1.0:   # (NaN fails too)
             raise ValueError("SqairStream.tracks: lane_iou must lie in (0, 1]")
         lag, M = int(lag), int(M)
+        truth = self._check_traj_truth("SqairStream.tracks: ", truth, lane, lag * self.T, True, link_ids, truth_iou)
         key = (lag, start, M if table else None, bool(table), lane, lane_iou if lane else None)
         with torch.cuda.device(core.device):
             core._join_in()
@@ -526,8 +668,11 @@ class SqairStream(object):
                     core.check(core.lib.sqair_history_trace(core.handle, cs.ring.data_ptr(), None if src is None else src.data_ptr(),
                                                             lag, C.byref(c_out), core._stream()), "sqair_history_trace")
                 res = {k: v.clone() for k, v in tr["out"].items()}
+                score = None if truth is None else self._traj_score("tracks", tr["lane"], lag * self.T, truth, link_ids)
                 if lane:   # (views of one allocation: one copy, not one per field)
                     res["lane"] = tr["lane_views"](tr["lane_flat"].clone())
+                    if score is not None:
+                        res["lane"]["score"] = score
                 if start == "next":
                     w = res["weights"] = torch.softmax(lw.reshape(self.B, self.K), -1)
                     k = torch.arange(self.K, device=core.device)
