@@ -802,6 +802,94 @@ typedef struct SqairTrajScore {
 int sqair_lane_traj_score(SqairHandle* h, const SqairLaneTraj* table, const SqairTrajTruth* truth, const SqairTrajScore* score, int F,
                           int B, void* stream);
 
+/* ---- lane identities: stable per-lane track ids, formed inside the pass --------------------------------------------------------
+ * The lane's obj_id is the best row's per-row counter: a switch of the best row switches the identity the caller sees although the
+ * object did not move (the score's idsw counts exactly that), and an object the filter drops for a few frames comes back under a
+ * fresh id.  With an identity set, every following inference pass with a carried state and an estimate runs one more kernel,
+ * k_lane_identity, one workgroup per lane looping over the pass's frames in order: after k_lane_estimate (and after k_lane_layers if
+ * on), BEFORE k_lane_score if on and BEFORE the SMC resampler.  It keeps a table of M tracks per lane on the device and links the
+ * lane's objects to them frame by frame, so one captured graph serves every step.  A pass with the identity on has exactly one kernel
+ * node more; with it off nothing is launched and every other output, blob and accumulator is unchanged bit for bit.  Training passes
+ * never run it.  The kernel reads the estimate's own output buffers box, presence, obj_id, best_row (and what, when trk_what is
+ * given) -- they must be bound -- and does not read the records again.
+ * The memory, per lane b and entry e < M: trk_id (-1 = free; the other fields of a free entry are whatever they last held and are
+ * never read), trk_word (the obj_id WORD -- the 32 bits of the float, read as int32 -- last seen on the track), trk_age (frames since
+ * it was last seen), trk_len (frames it was seen in), trk_box (its last box, the estimate's four words), trk_what (its last what,
+ * n_what words); next_id[b], the next fresh id of the lane.  The caller starts with trk_id = -1 and everything else 0.
+ * For lane b and the frames t of the pass in order:
+ * 0. Non-finite lane (best_row[t,b] == -1): lane_id, how and track_len are -1, frames_invalid += 1, the memory is untouched -- no
+ *    ageing.
+ * 1. Table.  For every entry e < M and slot j < N: IoU(e, j) = sq_box_iou(trk_box[e], box[t,b,j]) on the fp32 words (the estimate's
+ *    point 5), or -1 when e is free (trk_id < 0) or j is absent (presence == 0).
+ * 2. Link by position, the same lineage first: ONE call of sq_assign_keep_greedy, the device function of the score's points 2
+ *    and 3, as it stands -- rows are the entries, columns the slots, keep_id[e] = trk_word[e] for live entries and -1 for free
+ *    ones, col_id[j] = the obj_id word of slot j, a pair is eligible at IoU >= iou_min; keep, then greedy one-to-one, ties to the
+ *    smallest e, then the smallest j; a NaN never passes.  For a matched pair how = 1 (kept) when trk_word[e] equals the word of j,
+ *    else how = 2 (bridged: the caller would have lost the identity).
+ * 3. Nothing else is done in the position link.
+ * 4. Re-identification, only when reid_dist > 0.  For each still unmatched present j in index order, over the unclaimed live
+ *    entries e: centres are (y + 0.5 h, x + 0.5 w), dc2 the squared centre distance, r = reid_dist * (trk_age[e] + 1); e is
+ *    eligible when dc2 <= r * r and, with trk_what given, dw <= reid_what, where dw = (sum over c in index order of fmaf(d, d, acc),
+ *    d = what[t,b,j,c] - trk_what[e][c]) / n_what in fp32, one thread's loop per pair.  A NaN never passes.  The eligible e of
+ *    minimal dw is taken -- without trk_what the one of minimal dc2 --, ties to the smallest e; it is claimed and how = 3
+ *    (re-identified).  Greedy in j on purpose: simple and reproducible.
+ * 5. Update.  For a matched e (steps 2 and 4): trk_box, trk_word and trk_what become the 32-bit words of j, trk_age = 0,
+ *    trk_len += 1; lane_id[t,b,j] = trk_id[e], track_len[t,b,j] = trk_len[e].
+ * 6. Births, the remaining present j in index order: the first free entry, or if there is none the unclaimed live entry of largest
+ *    trk_age, ties to the smallest e, which is evicted (ended += 1) -- M >= N guarantees that one exists.  trk_id = next_id[b],
+ *    next_id[b] += 1, trk_len = 1, trk_age = 0, the words of j as in 5, how = 0 (born).  An entry freed or born in this frame is not
+ *    a candidate of step 4 of the same frame: a birth follows every link.
+ * 7. Ageing.  Every live entry neither matched nor born in this frame: trk_age += 1, and if that exceeds max_age the entry is freed
+ *    (trk_id = -1) and ended += 1.
+ * 8. Counters, counts [B,8] int64: frames, frames_invalid, objects (present slots seen), kept, bridged, reidentified, born (one count
+ *    per value of how), ended.  Absent slots j give lane_id = how = track_len = -1.
+ * 9. Coasted (frame, lane)s (sqair_set_observed) need no case of their own.
+ * The memory and the counters are read, updated and written by the one workgroup of the lane, in place: a replayed graph leaves the
+ * bits of eager calls, and two passes of three frames leave the bits of one pass of six.  A reset of a lane is the caller's: it frees
+ * the entries (trk_id = -1) and keeps next_id, so an id is never reused within a lane.
+ * lane_id is required, how and track_len are optional.  Pointers are remembered by the handle and frozen into captured graphs.  NULL
+ * id: off.  Refused (return -1, text in sqair_last_error, before any HIP call): no estimate set (sqair_set_estimate); an estimate
+ * without box, presence, obj_id or best_row; trk_what given while the estimate binds no what; a T other than the estimate's, a B
+ * other than the state's; M outside N..16; iou_min outside (0, 1]; reid_dist negative; reid_what not in (0, +inf]; max_age < 0; any
+ * NaN among the scalars; a NULL trk_id, trk_word, trk_age, trk_len, trk_box, next_id, counts or lane_id; at pass time: a pass of
+ * another T.  sqair_set_estimate switching the estimate off, to another T or to one without those fields, and sqair_set_state
+ * switching the state off or to another B, switch the identity off.
+ * sqair_set_score_ids(h, 1) makes k_lane_score read the identity's lane_id words where it reads the estimate's obj_id (the kernel
+ * treats the id as a 32-bit word: only the pointer the launcher passes changes); refused unless both the score and the identity are
+ * set; the identity or the score going off puts it back to 0.
+ * Out of scope: carrying lane_id into the object lists of lane tracks and lane forecasts; optimal (Hungarian) assignment; a motion
+ * model for the unseen track; identities across lanes; training passes. */
+#define SQAIR_IDENT_MAX_TRACKS 16
+#define SQAIR_IDENT_COUNTS 8
+typedef struct SqairLaneIdentity {
+  float iou_min;        /* in (0, 1]: the position gate of the link */
+  float reid_dist;      /* >= 0, pixels per frame: how far a centre may have moved per frame unseen; 0 = re-identification off */
+  float reid_what;      /* in (0, +inf]: largest mean squared difference of what; +inf = rank by it, gate nothing */
+  int32_t M;            /* track entries per lane, N..16 */
+  int32_t max_age;      /* >= 0: frames a track may go unseen before it ends */
+  /* memory, in/out, persists across passes; the caller starts with trk_id = -1, everything else 0 */
+  int32_t* trk_id;      /* [B,M]  -1 = free */
+  int32_t* trk_word;    /* [B,M]  the obj_id WORD last seen on the track */
+  int32_t* trk_age;     /* [B,M]  frames since it was last seen */
+  int32_t* trk_len;     /* [B,M]  frames it was seen in */
+  float*   trk_box;     /* [B,M,4] its last box, the estimate's words */
+  float*   trk_what;    /* [B,M,n_what] its last what, or NULL: no appearance, step 4 ranks by distance */
+  int32_t* next_id;     /* [B]    the next fresh id of the lane */
+  int64_t* counts;      /* [B,8]  frames, frames_invalid, objects, kept, bridged, reidentified, born, ended */
+  /* per frame, out */
+  int32_t* lane_id;     /* [T,B,N] required; -1 where slot j is absent */
+  int32_t* how;         /* [T,B,N] 0 born, 1 kept (same obj_id word), 2 bridged (another word), 3 re-identified; -1 absent */
+  int32_t* track_len;   /* [T,B,N] */
+} SqairLaneIdentity;
+int sqair_set_identity(SqairHandle* h, const SqairLaneIdentity* id /* NULL: off */, int T, int B);
+/* Kernel-level check of the identity (tests): the kernel above on caller buffers, no state and no pass, with the handle's N and
+ * n_what.  box [T,B,N,4], presence, obj_id [T,B,N], what [T,B,N,n_what] (or NULL) and best_row [T,B] stand for the estimate's outputs.
+ * Refused (return -1, before any HIP call): a NULL box / presence / obj_id / best_row / id, T or B out of range, id->trk_what without
+ * what, what sqair_set_identity refuses for id. */
+int sqair_lane_identity_test(SqairHandle* h, const float* box, const float* presence, const float* obj_id, const float* what /* or NULL */,
+                             const int32_t* best_row, int T, int B, const SqairLaneIdentity* id, void* stream);
+int sqair_set_score_ids(SqairHandle* h, int lane_ids /* 0: the estimate's obj_id (default); 1: the identity's lane_id */);
+
 /* ---- objective ---------------------------------------------------------------------------------
  * Fused IWAE / VIMCO reductions over [T,B,K] (reference: Model._build sqair/model.py:88-103,
  * targets.iwae / vimco_control_variate / vimco sqair/targets.py:38-75, make_target model.py:150-158,

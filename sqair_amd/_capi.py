@@ -144,6 +144,34 @@ class SqairLaneScore(C.Structure):
     _fields_ = [("iou_min", C.c_float), ("G", C.c_int32)] + [(n, C.c_void_p) for n in SCORE_INPUTS + SCORE_FIELDS]
 
 
+# lane identities (include/sqair_hip.h: sqair_set_identity): the scalars, the memory and the per-frame outputs of SqairLaneIdentity
+# in declaration order (all outputs int32); the names the outputs have in a step's ``lane`` dict; the columns of ``counts``
+IDENT_SCALARS = (("iou_min", C.c_float), ("reid_dist", C.c_float), ("reid_what", C.c_float), ("M", C.c_int32), ("max_age", C.c_int32))
+IDENT_MEMORY = ("trk_id", "trk_word", "trk_age", "trk_len", "trk_box", "trk_what", "next_id", "counts")
+IDENT_FIELDS = ("lane_id", "how", "track_len")
+IDENT_LANE_NAMES = dict(lane_id="lane_id", how="id_how", track_len="track_len")
+IDENT_COUNTS = ("frames", "frames_invalid", "objects", "kept", "bridged", "reidentified", "born", "ended")
+IDENT_MAX_TRACKS = 16
+
+
+def identity_shapes(T, B, N):
+    """The per-frame outputs' shapes for passes of T frames, by their names in a step's ``lane`` dict."""
+    return {IDENT_LANE_NAMES[n]: (T, B, N) for n in IDENT_FIELDS}
+
+
+def identity_memory_shapes(B, M, nw):
+    """The memory's and the counters' shapes for M track entries per lane; every array int32 but trk_box, trk_what (float32) and
+    counts (int64)."""
+    return dict(trk_id=(B, M), trk_word=(B, M), trk_age=(B, M), trk_len=(B, M), trk_box=(B, M, 4), trk_what=(B, M, nw), next_id=(B,),
+                counts=(B, len(IDENT_COUNTS)))
+
+
+class SqairLaneIdentity(C.Structure):
+    """Stable per-lane track ids (include/sqair_hip.h: sqair_set_identity); every pointer is a device address, trk_what, how and
+    track_len optional."""
+    _fields_ = list(IDENT_SCALARS) + [(n, C.c_void_p) for n in IDENT_MEMORY + IDENT_FIELDS]
+
+
 # trajectory scoring (include/sqair_hip.h: sqair_lane_traj_score): the three structs' pointer fields in declaration order, the int32
 # ones among the per-call outputs, the columns of ``counts`` [F, B, .], ``sums`` [F, B, .] and ``lane_counts`` [B, .]
 TRAJ_TABLE_FIELDS = ("best_row", "presence", "obj_id", "support", "box0", "alive", "box_mean", "count_prob", "valid_mass")
@@ -378,6 +406,9 @@ _PROTOS = {
     "sqair_lane_layers_test": (C.c_int, [C.c_void_p] * 6 + [C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(SqairLaneLayers), C.c_void_p]),
     "sqair_set_score": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneScore), C.c_int, C.c_int]),
     "sqair_lane_score_test": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.POINTER(SqairLaneScore), C.c_void_p]),
+    "sqair_set_identity": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneIdentity), C.c_int, C.c_int]),
+    "sqair_lane_identity_test": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.POINTER(SqairLaneIdentity), C.c_void_p]),
+    "sqair_set_score_ids": (C.c_int, [C.c_void_p, C.c_int]),
     "sqair_lane_traj_score": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneTraj), C.POINTER(SqairTrajTruth), C.POINTER(SqairTrajScore),
                                         C.c_int, C.c_int, C.c_void_p]),
     "sqair_forecast_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),

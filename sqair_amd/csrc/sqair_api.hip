@@ -1406,6 +1406,9 @@ SQ_LOCAL int sq_forward_impl(SqairHandle* h, const float* flat, const float* pac
     sq_set_error(h, "sqair_forward: the object layers launch failed (dynamic LDS limit)");
     return -2;
   }
+  // lane identities: the lane's objects linked to the lane's track table (sqair_set_identity), updated in place -- before the score,
+  // which may read the ids it writes (sqair_set_score_ids)
+  if (st.ident_on) sq_launch_lane_identity(sq_identity_args(h, T, B), s);
   // stream scoring: the lane answer the estimate just wrote against the caller's ground truth (sqair_set_score), accumulated in place
   if (st.score_on) sq_launch_lane_score(sq_score_args(h, T, B), s);
   // SMC: this pass's log weights -> ESS, evidence and the next pass's source map (sqair_set_smc / SqairCarry.smc)

@@ -437,6 +437,20 @@ struct LaneScoreArgs {
   int T, B, N;
 };
 int sq_launch_lane_score(const LaneScoreArgs& a, hipStream_t s);
+// Lane identities (sqair_set_identity; include/sqair_hip.h states the semantics): k_lane_identity, one workgroup per lane b looping
+// over the pass's frames in order, the track table in LDS across them.  box / presence / obj_id [T][B][N], what [T][B][N][nw] and
+// best_row [T][B] are the estimate's outputs (or a test's buffers); what is read only when id.trk_what is set.
+constexpr int SQ_IDENT_MAXM = 16;
+struct LaneIdentArgs {
+  const float* box;                    // [T][B][N][4]
+  const float* presence;               // [T][B][N]
+  const float* obj_id;                 // [T][B][N]
+  const float* what;                   // [T][B][N][nw]; NULL unless id.trk_what is set
+  const int32_t* best_row;             // [T][B]
+  SqairLaneIdentity id;                // the scalars, the memory, the counters and the per-frame outputs
+  int T, B, N, nw;
+};
+int sq_launch_lane_identity(const LaneIdentArgs& a, hipStream_t s);
 // Trajectory scoring (sqair_lane_traj_score; include/sqair_hip.h states the semantics): k_lane_traj_score, grid (lane b, chunk of
 // SQ_TRAJ_FRAMES frames): every workgroup recomputes its lane's link, then thread = frame, looping over the truth slots.
 constexpr int SQ_TRAJ_FRAMES = 256;

@@ -100,6 +100,11 @@ struct SqairHandle {
   // stream scoring (sqair_set_score): one k_lane_score launch after the estimate's and the layers'; needs the estimate, T = est_T
   bool score_on = false;
   SqairLaneScore score = {};
+  // lane identities (sqair_set_identity): one k_lane_identity launch after the layers', before the score's; needs the estimate,
+  // T = est_T.  score_ids (sqair_set_score_ids): the score reads the identity's lane_id for obj_id; only ever with both on
+  bool ident_on = false;
+  SqairLaneIdentity ident = {};
+  bool score_ids = false;
   // generic capture slots (sqair_capture_begin / _end / _launch): any sequence of C-ABI calls as one HIP graph
   hipGraph_t cap_graph[4] = {nullptr, nullptr, nullptr, nullptr};
   hipGraphExec_t cap_exec[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -229,7 +234,7 @@ int64_t sq_state_row_floats(const SqairHandle* h);   // floats of one particle r
 // The carried-state settings of one pass, resolved once per call and passed by value: the handle's (sq_resolve_pass; all off for
 // a training pass) or a carried training call's (sq_carry_state).  The pass reads these, never the handle's registration fields,
 // and nothing between resolution and return writes those.  `fresh`: k_state_import records each row's fresh / imported flag for
-// the backward.  lay_on and score_on are only ever set with est_on: whoever clears est_on clears them explicitly with it.
+// the backward.  lay_on, ident_on and score_on are only ever set with est_on: whoever clears est_on clears them explicitly with it.
 struct SqStateRes {
   bool on;
   const void* in; void* out; const int32_t* src;
@@ -240,12 +245,13 @@ struct SqStateRes {
   bool est_on = false;    // (the handle's inference passes only: a carried training call never estimates)
   bool lay_on = false;    // (the same; only ever with est_on)
   bool score_on = false;  // (the same; only ever with est_on)
+  bool ident_on = false;  // (the same; only ever with est_on)
 };
 // The refusals of a pass on the handle's settings -- observed mask, state, SMC, history, estimate, in this order (-1 + error text,
 // before any HIP call) -- then the settings in *st.  The only place that fixes the history ring's T: a refused call changes nothing.
 SQ_LOCAL int sq_resolve_pass(SqairHandle* h, bool train, int T, int B, int t_offset, const SqairOutputs* out, SqStateRes* st);
 // `st` for a pass that changes nothing outside its workspace and outputs (a capture's eager pre-pass): what it reads stays (the rows
-// imported through the map, the mask), what it writes goes (export, history push, estimate, layers, score, resampler).
+// imported through the map, the mask), what it writes goes (export, history push, estimate, layers, identity, score, resampler).
 SQ_LOCAL SqStateRes sq_without_effects(SqStateRes st);
 SQ_LOCAL SqStateRes sq_carry_state(const SqairCarry* c);
 SQ_LOCAL StateArgs sq_state_args(const SqairHandle* h, const SqStateRes& st, int R, float* rec, float* temporal, float* prior, float* last_id,
@@ -262,6 +268,8 @@ SQ_LOCAL LaneEstArgs sq_estimate_args(const SqairHandle* h, const float* rec, co
 SQ_LOCAL LaneLayerArgs sq_layers_args(const SqairHandle* h, const float* rec, const float* glimpse, const SqairOutputs& out, int T, int B);
 // stream scoring: the kernel's arguments for a pass of T frames -- the estimate's own output buffers and the registered score
 SQ_LOCAL LaneScoreArgs sq_score_args(const SqairHandle* h, int T, int B);
+// lane identities: the kernel's arguments for a pass of T frames -- the estimate's own output buffers and the registered identity
+SQ_LOCAL LaneIdentArgs sq_identity_args(const SqairHandle* h, int T, int B);
 // section A of a frame of the pass, and a frame of the forecast: the propagation-prior cell and its statistics (sqair_api.hip)
 SQ_LOCAL int sq_prior_step(SqairHandle* h, const float* packed, hipStream_t s, int M, const float* rec_prev, const float* prior_prev,
                            float* prior_p, float* pgz, float* pgrh, float* pgxh, float* pstats, float* o3, float* o1);

@@ -1,5 +1,5 @@
 // The per-lane answers: the kernels that turn a lane's K particle rows into one answer per lane -- the SMC resampler, the forecast
-// summaries, the lane estimate, the object layers, the stream score, the lane forecast, the lane tracks and the trajectory score of those two.  None of them is a hop of the frame loop (once per pass or
+// summaries, the lane estimate, the object layers, the stream score, the lane identities, the lane forecast, the lane tracks and the trajectory score of those two.  None of them is a hop of the frame loop (once per pass or
 // per call, on B workgroups), and they are a translation unit -- a code object -- of their own so that work on them moves no kernel of the pass
 // (DESIGN.md section 3h).  Their compositions are the device functions of sqair_lane.h.  Every lane-wide sum is one thread's loop in
 // index order: the same bits on every replay, and K <= 256 adds are nothing next to the pass.
@@ -664,6 +664,170 @@ __global__ __launch_bounds__(256) void k_lane_score(const LaneScoreArgs a SQ_TLP
 }
 int sq_launch_lane_score(const LaneScoreArgs& a, hipStream_t s) {
   SQ_LAUNCH(k_lane_score, dim3(a.B), dim3(256), 0, s, a);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Lane identities (sqair_set_identity; LaneIdentArgs in sqair_glue.h; the semantics: include/sqair_hip.h, points 0-9)
+// ------------------------------------------------------------------------------------------------
+// k_lane_identity: workgroup = lane b, looping over the pass's frames in order -- the track table makes frame t depend on frame
+// t - 1 -- with the table (ids, words, ages, lengths, boxes, what vectors) in LDS across them.  Per frame thread i < M * N fills entry
+// (e, j) = (i / N, i % N) of the IoU table (-1 for a pair that is no candidate) and, when re-identification is on, of the dc2 and dw
+// tables: the loop over n_what per pair is the parallel part.  Thread 0 walks the tables -- sq_assign_keep_greedy, then the
+// re-identification, the births and the ageing -- and leaves per slot j its entry and how it got there; then threads j < N write
+// the outputs and the workgroup copies the words of every seen slot into its entry.  Every array is in LDS, nothing is indexed in
+// registers.  Every branch around a barrier depends on best_row[t, b] and the struct's scalars alone: uniform over the workgroup.
+__global__ __launch_bounds__(256) void k_lane_identity(const LaneIdentArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ float s_iou[SQ_IDENT_MAXM * SQ_MAXN], s_dc2[SQ_IDENT_MAXM * SQ_MAXN], s_dw[SQ_IDENT_MAXM * SQ_MAXN];
+  __shared__ float s_tbox[SQ_IDENT_MAXM * 4], s_twhat[SQ_IDENT_MAXM * SQ_MAX_NWHAT];
+  __shared__ int s_tid[SQ_IDENT_MAXM], s_word[SQ_IDENT_MAXM], s_age[SQ_IDENT_MAXM], s_len[SQ_IDENT_MAXM];
+  __shared__ int s_keep[SQ_IDENT_MAXM], s_em[SQ_IDENT_MAXM];                       // keep_id of the walk; the slot an entry took
+  __shared__ int s_jid[SQ_MAXN], s_pres[SQ_MAXN], s_claim[SQ_MAXN], s_je[SQ_MAXN], s_how[SQ_MAXN];   // per slot: word, present, entry, how
+  const SqairLaneIdentity& o = a.id;
+  const int b = blockIdx.x, tid = threadIdx.x, M = o.M, N = a.N, nw = a.nw;
+  const bool reid = o.reid_dist > 0.0f, app = o.trk_what != nullptr;
+  if (tid < M) {
+    const size_t e = (size_t)b * M + tid;
+    s_tid[tid] = o.trk_id[e]; s_word[tid] = o.trk_word[e]; s_age[tid] = o.trk_age[e]; s_len[tid] = o.trk_len[e];
+  }
+  if (tid < M * 4) s_tbox[tid] = o.trk_box[(size_t)b * M * 4 + tid];
+  if (app)
+    for (int i = tid; i < M * nw; i += 256) s_twhat[i] = o.trk_what[(size_t)b * M * nw + i];
+  int next = tid == 0 ? o.next_id[b] : 0;
+  long long c_frames = 0, c_invalid = 0, c_obj = 0, c_kept = 0, c_bridged = 0, c_reid = 0, c_born = 0, c_ended = 0;
+  for (int t = 0; t < a.T; ++t) {
+    const size_t tb = (size_t)t * a.B + b;
+    const bool bad = a.best_row[tb] == -1;
+    __syncthreads();   // (the memory is loaded, or the last frame's words are in it; its readers are done with the tables)
+    if (bad) {   // a non-finite lane: no outputs, no ageing
+      if (tid == 0) ++c_invalid;
+      if (tid < N) {
+        o.lane_id[tb * N + tid] = -1;
+        if (o.how) o.how[tb * N + tid] = -1;
+        if (o.track_len) o.track_len[tb * N + tid] = -1;
+      }
+      continue;
+    }
+    // ---- 1 (and 4's tables): entry e against slot j
+    if (tid < M * N) {
+      const int e = tid / N, j = tid - e * N;
+      float v = -1.0f, dc2 = 0.0f, dw = 0.0f;
+      if (s_tid[e] >= 0 && a.presence[tb * N + j] != 0.0f) {
+        const float* q = a.box + (tb * N + j) * 4;
+        const SqBox p = {s_tbox[e * 4 + 0], s_tbox[e * 4 + 1], s_tbox[e * 4 + 2], s_tbox[e * 4 + 3]}, bx = {q[0], q[1], q[2], q[3]};
+        v = sq_box_iou(p, bx);
+        if (reid) {
+          const float dy = fmaf(0.5f, bx.h, bx.y) - fmaf(0.5f, p.h, p.y), dx = fmaf(0.5f, bx.w, bx.x) - fmaf(0.5f, p.w, p.x);
+          dc2 = fmaf(dy, dy, dx * dx);
+          if (app) {
+            const float* wj = a.what + (tb * N + j) * nw;
+            float acc = 0.0f;
+            for (int c = 0; c < nw; ++c) {
+              const float d = wj[c] - s_twhat[e * nw + c];
+              acc = fmaf(d, d, acc);
+            }
+            dw = acc / (float)nw;
+          }
+        }
+      }
+      s_iou[tid] = v; s_dc2[tid] = dc2; s_dw[tid] = dw;
+    }
+    if (tid < M) s_keep[tid] = s_tid[tid] >= 0 ? s_word[tid] : -1;
+    if (tid < N) {
+      s_pres[tid] = a.presence[tb * N + tid] != 0.0f;
+      s_jid[tid] = (int)sq_word(a.obj_id + tb * N + tid);
+    }
+    __syncthreads();
+    // ---- 2 .. 8: the links, the births and the ageing, one thread
+    if (tid == 0) {
+      sq_assign_keep_greedy(s_iou, N, M, N, o.iou_min, s_keep, s_jid, s_em, s_claim);
+      for (int j = 0; j < N; ++j) { s_je[j] = -1; s_how[j] = -1; }
+      for (int e = 0; e < M; ++e) {
+        const int j = s_em[e];
+        if (j < 0) continue;
+        s_je[j] = e;
+        s_how[j] = s_word[e] == s_jid[j] ? 1 : 2;
+      }
+      if (reid)
+        for (int j = 0; j < N; ++j) {
+          if (!s_pres[j] || s_je[j] >= 0) continue;
+          int be = -1;
+          float bk = 0.0f;
+          for (int e = 0; e < M; ++e) {
+            if (s_tid[e] < 0 || s_em[e] >= 0) continue;
+            const float r = o.reid_dist * (float)(s_age[e] + 1);
+            if (!(s_dc2[e * N + j] <= r * r)) continue;
+            if (app && !(s_dw[e * N + j] <= o.reid_what)) continue;
+            const float key = app ? s_dw[e * N + j] : s_dc2[e * N + j];
+            if (be < 0 || key < bk) { be = e; bk = key; }
+          }
+          if (be < 0) continue;
+          s_em[be] = j; s_je[j] = be; s_how[j] = 3;
+        }
+      for (int j = 0; j < N; ++j) {   // 5: the matched entries
+        const int e = s_je[j];
+        if (e < 0) continue;
+        s_word[e] = s_jid[j]; s_age[e] = 0; s_len[e] += 1;
+      }
+      for (int j = 0; j < N; ++j) {   // 6: births
+        if (!s_pres[j] || s_je[j] >= 0) continue;
+        int be = -1;
+        for (int e = 0; e < M && be < 0; ++e)
+          if (s_tid[e] < 0) be = e;
+        if (be < 0) {
+          for (int e = 0; e < M; ++e)
+            if (s_em[e] < 0 && (be < 0 || s_age[e] > s_age[be])) be = e;
+          ++c_ended;
+        }
+        s_tid[be] = next++; s_word[be] = s_jid[j]; s_age[be] = 0; s_len[be] = 1;
+        s_em[be] = j; s_je[j] = be; s_how[j] = 0;
+      }
+      for (int e = 0; e < M; ++e) {   // 7: ageing
+        if (s_tid[e] < 0 || s_em[e] >= 0) continue;
+        s_age[e] += 1;
+        if (s_age[e] > o.max_age) { s_tid[e] = -1; ++c_ended; }
+      }
+      ++c_frames;
+      for (int j = 0; j < N; ++j) {
+        const int hw = s_how[j];
+        c_obj += s_pres[j]; c_born += hw == 0; c_kept += hw == 1; c_bridged += hw == 2; c_reid += hw == 3;
+      }
+    }
+    __syncthreads();
+    // ---- 5, 6: the outputs, and the words of every seen slot into its entry
+    if (tid < N) {
+      const int e = s_je[tid];
+      o.lane_id[tb * N + tid] = e >= 0 ? s_tid[e] : -1;
+      if (o.how) o.how[tb * N + tid] = s_how[tid];
+      if (o.track_len) o.track_len[tb * N + tid] = e >= 0 ? s_len[e] : -1;
+    }
+    if (tid < N * 4) {
+      const int j = tid >> 2, e = s_je[j];
+      if (e >= 0) sq_put(s_tbox + e * 4 + (tid & 3), sq_word(a.box + (tb * N + j) * 4 + (tid & 3)));
+    }
+    if (app)
+      for (int i = tid; i < N * nw; i += 256) {
+        const int j = i / nw, e = s_je[j];
+        if (e >= 0) sq_put(s_twhat + e * nw + (i - j * nw), sq_word(a.what + tb * N * nw + i));
+      }
+  }
+  __syncthreads();
+  if (tid < M) {
+    const size_t e = (size_t)b * M + tid;
+    o.trk_id[e] = s_tid[tid]; o.trk_word[e] = s_word[tid]; o.trk_age[e] = s_age[tid]; o.trk_len[e] = s_len[tid];
+  }
+  if (tid < M * 4) sq_put(o.trk_box + (size_t)b * M * 4 + tid, sq_word(s_tbox + tid));
+  if (app)
+    for (int i = tid; i < M * nw; i += 256) sq_put(o.trk_what + (size_t)b * M * nw + i, sq_word(s_twhat + i));
+  if (tid == 0) {
+    o.next_id[b] = next;
+    int64_t* c = o.counts + (size_t)b * SQAIR_IDENT_COUNTS;
+    c[0] += c_frames; c[1] += c_invalid; c[2] += c_obj; c[3] += c_kept; c[4] += c_bridged; c[5] += c_reid; c[6] += c_born; c[7] += c_ended;
+  }
+}
+int sq_launch_lane_identity(const LaneIdentArgs& a, hipStream_t s) {
+  SQ_LAUNCH(k_lane_identity, dim3(a.B), dim3(256), 0, s, a);
   return 0;
 }
 

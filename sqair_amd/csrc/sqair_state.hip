@@ -1,5 +1,5 @@
 // libsqair_hip.so -- the carried model state on the native side of the C ABI (include/sqair_hip.h): the state blob and its
-// registration on a handle (sqair_set_state / _smc / _history / _observed / _estimate / _layers / _score), the one resolution of a call
+// registration on a handle (sqair_set_state / _smc / _history / _observed / _estimate / _layers / _score / _identity), the one resolution of a call
 // (sq_resolve_pass: the refusals of a pass, each free of side effects, then the handle's settings by value as an SqStateRes;
 // sq_carry_state: a SqairCarry's), and the forecast that rolls the prior forward from a state (sqair_forecast).  Host code only; the
 // pass, sq_forward_impl (sqair_api.hip), reads the SqStateRes it is given; the kernels live in sqair_glue.hip and sqair_lane.hip.
@@ -26,11 +26,14 @@ static int sq_estimate_t_mismatch(SqairHandle* h, const std::string& who, int T)
 }
 static void sq_observed_off(SqairHandle* h) { h->observed = nullptr; h->observed_T = 0; }
 static void sq_layers_off(SqairHandle* h) { h->lay_on = false; h->lay = SqairLaneLayers{}; }
-static void sq_score_off(SqairHandle* h) { h->score_on = false; h->score = SqairLaneScore{}; }
+// (the score reads the identity's ids only while both are on: either going off puts score_ids back to 0)
+static void sq_score_off(SqairHandle* h) { h->score_on = false; h->score = SqairLaneScore{}; h->score_ids = false; }
+static void sq_identity_off(SqairHandle* h) { h->ident_on = false; h->ident = SqairLaneIdentity{}; h->score_ids = false; }
 static void sq_estimate_off(SqairHandle* h) {
   h->est_on = false; h->est = SqairLaneEstimate{}; h->est_T = 0;
   sq_layers_off(h);                           // (the layers share the estimate's weights and association: off with it)
   sq_score_off(h);                            // (the score reads the estimate's outputs: off with it)
+  sq_identity_off(h);                         // (and so does the identity)
 }
 static void sq_history_off(SqairHandle* h) {
   h->hist_on = false; h->hist_ring = nullptr; h->hist_bytes = 0; h->hist_L = 0; h->hist_T = 0; h->hist_fields = 0;
@@ -156,6 +159,10 @@ static int sq_estimate_smc_mismatch(SqairHandle* h, const std::string& who, cons
   return sq_no(h, who + "with SMC on (sqair_set_smc) log_w must be smc->log_w, the carried log weights of the pass's rows");
 }
 static bool sq_estimate_scorable(const SqairLaneEstimate& e) { return e.box && e.presence && e.obj_id && e.map_count; }
+// (best_row is never NULL in a registered estimate; `what`: the identity keeps an appearance, trk_what, and reads the estimate's)
+static bool sq_estimate_identifiable(const SqairLaneEstimate& e, bool what) {
+  return e.box && e.presence && e.obj_id && e.best_row && (!what || e.what);
+}
 extern "C" int sqair_set_estimate(SqairHandle* h, const SqairLaneEstimate* est, int T, int B) {
   if (!h) return -1;
   if (!est) {
@@ -169,6 +176,7 @@ extern "C" int sqair_set_estimate(SqairHandle* h, const SqairLaneEstimate* est, 
   if (sq_estimate_fields(h, who, *est) != 0 || sq_estimate_smc_mismatch(h, who, *est) != 0) return -1;
   if (T != h->est_T) sq_layers_off(h);   // (the layers' outputs were sized for the other T)
   if (T != h->est_T || !sq_estimate_scorable(*est)) sq_score_off(h);   // (and the score's; it reads these four outputs)
+  if (T != h->est_T || !sq_estimate_identifiable(*est, h->ident.trk_what != nullptr)) sq_identity_off(h);   // (and the identity's)
   h->est_on = true; h->est = *est; h->est_T = T;
   return 0;
 }
@@ -299,6 +307,8 @@ extern "C" int sqair_set_score(SqairHandle* h, const SqairLaneScore* score, int 
 LaneScoreArgs sq_score_args(const SqairHandle* h, int T, int B) {
   LaneScoreArgs a; memset(&a, 0, sizeof(a));
   a.box = h->est.box; a.presence = h->est.presence; a.obj_id = h->est.obj_id; a.map_count = h->est.map_count; a.sc = h->score;
+  // (sqair_set_score_ids: the kernel takes the id as a 32-bit word, so the identity's int32 lane_id stands where obj_id stands)
+  if (h->score_ids && h->ident_on) a.obj_id = reinterpret_cast<const float*>(h->ident.lane_id);
   a.T = T; a.B = B; a.N = h->cfg.n_steps_per_image;
   return a;
 }
@@ -314,6 +324,73 @@ extern "C" int sqair_lane_score_test(SqairHandle* h, const float* box, const flo
   a.box = box; a.presence = presence; a.obj_id = obj_id; a.map_count = map_count; a.sc = *score;
   a.T = T; a.B = B; a.N = h->cfg.n_steps_per_image;
   sq_launch_lane_score(a, (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+// ------------------------------------------------------------------------------------------------
+// lane identities (include/sqair_hip.h: sqair_set_identity): registration, the arguments of k_lane_identity (launched by
+// sq_forward_impl after the estimate's and the layers' kernels, before the score's and the resampler) and the kernel-level entry point
+// ------------------------------------------------------------------------------------------------
+// what every user of an SqairLaneIdentity checks, -1 + "<who>..." when one is off
+static int sq_identity_fields(SqairHandle* h, const std::string& who, const SqairLaneIdentity& c) {
+  const int N = h->cfg.n_steps_per_image;
+  if (c.M < N || c.M > SQ_IDENT_MAXM)
+    return sq_no(h, who + "M = " + std::to_string(c.M) + " must lie in N = " + std::to_string(N) + ".." + std::to_string(SQ_IDENT_MAXM));
+  if (!(c.iou_min > 0.0f && c.iou_min <= 1.0f)) return sq_no(h, who + "iou_min must lie in (0, 1]");   // (NaN fails both)
+  if (!(c.reid_dist >= 0.0f)) return sq_no(h, who + "reid_dist must be >= 0");                          // (NaN fails)
+  if (!(c.reid_what > 0.0f)) return sq_no(h, who + "reid_what must lie in (0, +inf]");                  // (NaN fails)
+  if (c.max_age < 0) return sq_no(h, who + "max_age must be >= 0");
+  if (!c.trk_id || !c.trk_word || !c.trk_age || !c.trk_len || !c.trk_box || !c.next_id || !c.counts || !c.lane_id)
+    return sq_no(h, who + "trk_id, trk_word, trk_age, trk_len, trk_box, next_id, counts and lane_id must not be NULL");
+  return 0;
+}
+extern "C" int sqair_set_identity(SqairHandle* h, const SqairLaneIdentity* id, int T, int B) {
+  if (!h) return -1;
+  if (!id) {
+    sq_identity_off(h);
+    return 0;
+  }
+  const std::string who = "sqair_set_identity: ";
+  if (!h->state_on || !h->est_on)
+    return sq_no(h, who + "needs an estimate (sqair_set_estimate): the identity links the lane answer it writes");
+  if (!sq_estimate_identifiable(h->est, false))
+    return sq_no(h, who + "the estimate (sqair_set_estimate) must bind box, presence, obj_id and best_row: the identity reads them");
+  if (id->trk_what && !h->est.what)
+    return sq_no(h, who + "trk_what needs the estimate (sqair_set_estimate) to bind what: the appearance it remembers");
+  if (sq_estimate_t_mismatch(h, who, T) != 0) return -1;
+  if (sq_state_b_mismatch(h, who, B) != 0) return -1;
+  if (sq_identity_fields(h, who, *id) != 0) return -1;
+  h->ident_on = true; h->ident = *id;
+  return 0;
+}
+extern "C" int sqair_set_score_ids(SqairHandle* h, int lane_ids) {
+  if (!h) return -1;
+  if (lane_ids && !(h->state_on && h->est_on && h->score_on && h->ident_on))
+    return sq_no(h, "sqair_set_score_ids: needs both a score (sqair_set_score) and an identity (sqair_set_identity): the score reads "
+                    "the lane_id the identity writes");
+  h->score_ids = lane_ids != 0;
+  return 0;
+}
+LaneIdentArgs sq_identity_args(const SqairHandle* h, int T, int B) {
+  LaneIdentArgs a; memset(&a, 0, sizeof(a));
+  a.box = h->est.box; a.presence = h->est.presence; a.obj_id = h->est.obj_id; a.best_row = h->est.best_row;
+  a.what = h->ident.trk_what ? h->est.what : nullptr; a.id = h->ident;
+  a.T = T; a.B = B; a.N = h->cfg.n_steps_per_image; a.nw = h->cfg.n_what;
+  return a;
+}
+// kernel-level check of the identity (tests/test_identity_kernel.py): k_lane_identity on caller tensors, no state and no pass
+extern "C" int sqair_lane_identity_test(SqairHandle* h, const float* box, const float* presence, const float* obj_id, const float* what,
+                                        const int32_t* best_row, int T, int B, const SqairLaneIdentity* id, void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_lane_identity_test: ";
+  if (!box || !presence || !obj_id || !best_row || !id || T < 1 || B < 1 || T > 65535)
+    return sq_no(h, who + "null box / presence / obj_id / best_row / id or bad T / B");
+  if (sq_identity_fields(h, who, *id) != 0) return -1;
+  if (id->trk_what && !what) return sq_no(h, who + "id->trk_what needs what");
+  LaneIdentArgs a; memset(&a, 0, sizeof(a));
+  a.box = box; a.presence = presence; a.obj_id = obj_id; a.best_row = best_row; a.what = id->trk_what ? what : nullptr; a.id = *id;
+  a.T = T; a.B = B; a.N = h->cfg.n_steps_per_image; a.nw = h->cfg.n_what;
+  sq_launch_lane_identity(a, (hipStream_t)stream);
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -460,13 +537,13 @@ int sq_resolve_pass(SqairHandle* h, bool train, int T, int B, int t_offset, cons
     return -1;
   const bool on = h->state_on, est = on && h->est_on;
   *st = SqStateRes{on, h->state_in, h->state_out, h->state_src, false, h->smc_on, h->smc, on && h->hist_on,
-                   on ? h->observed : nullptr, est, est && h->lay_on, est && h->score_on};
+                   on ? h->observed : nullptr, est, est && h->lay_on, est && h->score_on, est && h->ident_on};
   if (st->hist_on && T >= 1) h->hist_T = T;   // (T < 1 is the pass's own to refuse)
   return 0;
 }
 SqStateRes sq_without_effects(SqStateRes st) {
   st.out = nullptr; st.smc_on = false; st.smc = SqairSmc{};
-  st.hist_on = st.est_on = st.lay_on = st.score_on = false;
+  st.hist_on = st.est_on = st.lay_on = st.score_on = st.ident_on = false;
   return st;
 }
 HistPushArgs sq_history_push_args(const SqairHandle* h, const SqStateRes& st, const SqairOutputs& out, const int* t_row, int T, int B) {

@@ -64,6 +64,19 @@ and ``score()`` reads the accumulators: per lane ``frames``, ``frames_invalid``,
 ``count_hit``, ``count_abs_err`` and ``iou_sum``, pooled ``mota``, ``motp`` and ``count_accuracy``.  ``reset(lanes)`` also forgets
 those lanes' identities (a new clip has new ones) and keeps their counters.
 
+With ``identity=True`` (a stream with ``estimate=True``) every object of the lane answer carries a track id that stays on it for as
+long as the tracker can tell it is the same object, formed by one more kernel of the pass after the estimate's and the layers' and
+before the score's (include/sqair_hip.h: sqair_set_identity, which states the semantics).  ``obj_id`` is the best row's per-row
+counter and changes when the best row switches; ``lane_id`` does not: a table of ``identity_tracks`` (default min(16, 2 N)) tracks
+per lane is kept on the device, and each frame's objects are linked to it by position (IoU >= ``identity_iou``, the same obj_id
+first), then -- ``identity_reid_dist`` > 0 -- an object that was dropped for up to ``identity_max_age`` frames is re-identified when
+its centre lies within ``identity_reid_dist`` pixels per frame unseen and, with ``identity_appearance``, its ``what`` within
+``identity_reid_what`` of the track's (the nearest appearance wins), else it is born under a fresh id.  ``out["lane"]`` gains
+``lane_id``, ``id_how`` (0 born, 1 kept, 2 bridged -- the obj_id changed under it --, 3 re-identified) and ``track_len`` [T', B, N]
+int32, -1 where the slot is absent; ``identities()`` reads the counters and the table.  ``reset(lanes)`` frees those lanes' tracks;
+ids are never reused within a lane.  ``score_ids="lane"`` (with ``score=True``) makes the score count its identity switches on
+``lane_id`` instead of ``obj_id``.
+
 ``forecast(..., lane=True, truth=...)`` and ``tracks(..., lane=True, truth=...)`` score the two answers that reach over time -- the
 lane forecast and the lane tracks -- against the truth's trajectories with one more launch after the call's own (include/sqair_hip.h:
 sqair_lane_traj_score, which states the semantics): truth and lane objects are linked once, at the last stepped frame, and every
@@ -108,7 +121,8 @@ class SqairStream(object):
     def __init__(self, core, B, frames_per_step=1, outputs=DEFAULT_OUTPUTS, use_graph=True, seed=0, resample=None, ess_frac=0.5,
                  state=None, history=None, history_fields=tuple(_capi.HISTORY_FIELDS), missing=False, estimate=False,
                  estimate_iou=0.5, estimate_canvas=False, estimate_layers=False, layers_cover_min=0.5, score=False, score_iou=0.5,
-                 score_truth=None):
+                 score_truth=None, identity=False, identity_iou=0.3, identity_tracks=None, identity_max_age=10, identity_reid_dist=4.0,
+                 identity_reid_what=float("inf"), identity_appearance=True, score_ids="row"):
         if core.cfg.sample_from_prior:
             raise ValueError("SqairStream: generation modes (sample_from_prior) do not carry a state across calls")
         if resample not in (None, "systematic"):
@@ -134,6 +148,24 @@ class SqairStream(object):
         if score and score_truth is not None and (isinstance(score_truth, bool) or not isinstance(score_truth, (int, np.integer)) or
                                                   not 1 <= score_truth <= _capi.SCORE_MAX_TRUTH):
             raise ValueError("SqairStream: score_truth must be an integer in [1, {}]".format(_capi.SCORE_MAX_TRUTH))
+        if identity and not estimate:
+            raise ValueError("SqairStream: identity is for a stream with estimate=True")
+        identity_iou, identity_reid_dist, identity_reid_what = float(identity_iou), float(identity_reid_dist), float(identity_reid_what)
+        if identity and not 0.0 < identity_iou <= 1.0:   # (NaN fails too)
+            raise ValueError("SqairStream: identity_iou must lie in (0, 1]")
+        if identity and identity_tracks is not None and (isinstance(identity_tracks, bool) or not isinstance(identity_tracks, (int, np.integer)) or
+                                                         not 1 <= identity_tracks <= _capi.IDENT_MAX_TRACKS):
+            raise ValueError("SqairStream: identity_tracks must be an integer in [n_steps_per_image, {}]".format(_capi.IDENT_MAX_TRACKS))
+        if identity and (isinstance(identity_max_age, bool) or not isinstance(identity_max_age, (int, np.integer)) or identity_max_age < 0):
+            raise ValueError("SqairStream: identity_max_age must be an integer >= 0")
+        if identity and not identity_reid_dist >= 0.0:   # (NaN fails too)
+            raise ValueError("SqairStream: identity_reid_dist must be >= 0")
+        if identity and not identity_reid_what > 0.0:   # (NaN fails too)
+            raise ValueError("SqairStream: identity_reid_what must lie in (0, +inf]")
+        if score_ids not in ("row", "lane"):
+            raise ValueError("SqairStream: score_ids must be 'row' or 'lane'")
+        if score_ids == "lane" and not (score and identity):
+            raise ValueError("SqairStream: score_ids='lane' is for a stream with score=True and identity=True")
         self.smc = resample is not None
         self.ess_frac = ess_frac
         self.core = core
@@ -142,6 +174,10 @@ class SqairStream(object):
         self.T = int(frames_per_step)
         if self.B < 1 or self.T < 1:
             raise ValueError("SqairStream: B and frames_per_step must be >= 1")
+        self.identified = bool(identity)
+        self.M = (min(_capi.IDENT_MAX_TRACKS, 2 * core.N) if identity_tracks is None else int(identity_tracks)) if self.identified else 0   # track entries per lane
+        if self.identified and not core.N <= self.M:   # (the last check that needs the core's N: still before the handle is touched)
+            raise ValueError("SqairStream: identity_tracks must be an integer in [n_steps_per_image, {}]".format(_capi.IDENT_MAX_TRACKS))
         outputs = tuple(outputs)
         if "log_weights_per_timestep" not in outputs:   # (the running log-weight sums)
             outputs = outputs + ("log_weights_per_timestep",)
@@ -179,7 +215,7 @@ class SqairStream(object):
         self.scored = bool(score)
         self.G = (core.N if score_truth is None else int(score_truth)) if self.scored else 0   # truth slots per lane
         if self.estimate:   # after SMC: the estimate's log_w must be the resampler's accumulator
-            self._est = self._estimate_buffers(bool(estimate_canvas), bool(estimate_layers), self.G)
+            self._est = self._estimate_buffers(bool(estimate_canvas), bool(estimate_layers), self.G, self.identified)
             est = _capi.SqairLaneEstimate(iou_min=estimate_iou, log_w=cs.log_weight_sum.data_ptr(),
                                           **{n: t.data_ptr() for n, t in self._est.items() if n in _capi.ESTIMATE_FIELDS})
             torch.cuda.current_stream(core.device).synchronize()
@@ -197,6 +233,21 @@ class SqairStream(object):
                                           **{n: self._est[n].data_ptr() for n in _capi.SCORE_FIELDS})
                 torch.cuda.current_stream(core.device).synchronize()
                 core.check(core.lib.sqair_set_score(core.handle, C.byref(sc), self.T, self.B), "sqair_set_score")
+            if self.identified:   # the track table of every lane and the counters: the stream's own device buffers
+                shapes = _capi.identity_memory_shapes(self.B, self.M, core.nw)
+                if not identity_appearance:
+                    del shapes["trk_what"]
+                floats = ("trk_box", "trk_what")
+                self._ident = {n: torch.zeros(shp, dtype=torch.float32 if n in floats else torch.int64 if n == "counts" else torch.int32,
+                                              device=core.device) for n, shp in shapes.items()}
+                self._ident["trk_id"].fill_(-1)
+                idt = _capi.SqairLaneIdentity(iou_min=identity_iou, reid_dist=identity_reid_dist, reid_what=identity_reid_what, M=self.M,
+                                              max_age=int(identity_max_age), **{n: t.data_ptr() for n, t in self._ident.items()},
+                                              **{n: self._est[_capi.IDENT_LANE_NAMES[n]].data_ptr() for n in _capi.IDENT_FIELDS})
+                torch.cuda.current_stream(core.device).synchronize()
+                core.check(core.lib.sqair_set_identity(core.handle, C.byref(idt), self.T, self.B), "sqair_set_identity")
+                if score_ids == "lane":
+                    core.check(core.lib.sqair_set_score_ids(core.handle, 1), "sqair_set_score_ids")
         if history is not None:
             ring, nb, bits = cs.set_history(history, history_fields, self.T)
             torch.cuda.current_stream(core.device).synchronize()   # (the ring's zeros are in place before a pass pushes into it)
@@ -219,10 +270,11 @@ class SqairStream(object):
         self._smc_uniforms = uniforms
         self._graph = False
 
-    def _estimate_buffers(self, canvas, layers=False, score_truth=0):
+    def _estimate_buffers(self, canvas, layers=False, score_truth=0, identity=False):
         """The device buffers k_lane_estimate -- and, with ``layers``, k_lane_layers, with ``score_truth`` = G > 0, k_lane_score's
-        per-frame outputs -- writes (include/sqair_hip.h: SqairLaneEstimate, SqairLaneLayers, SqairLaneScore), by field: views of ONE
-        allocation (``_est_flat``), so that a step copies them out with one launch instead of one per field."""
+        per-frame outputs, with ``identity`` k_lane_identity's -- writes (include/sqair_hip.h: SqairLaneEstimate, SqairLaneLayers,
+        SqairLaneScore, SqairLaneIdentity), by field: views of ONE allocation (``_est_flat``), so that a step copies them out with one
+        launch instead of one per field."""
         core = self.core
         shapes = _capi.estimate_shapes(self.T, self.B, self.K, core.N, core.nw, (core.H, core.W) if canvas else None)
         if layers:
@@ -230,20 +282,28 @@ class SqairStream(object):
         if score_truth:
             shapes.update(_capi.score_shapes(self.T, self.B, score_truth))
         ints = _capi.ESTIMATE_INT_FIELDS + (_capi.LAYERS_INT_FIELDS if layers else ()) + (_capi.SCORE_INT_FIELDS if score_truth else ())
+        if identity:
+            shapes.update(_capi.identity_shapes(self.T, self.B, core.N))
+            ints = ints + tuple(_capi.IDENT_LANE_NAMES[n] for n in _capi.IDENT_FIELDS)
         self._est_flat, self._est_views = _field_views(shapes, ints, core.device)
         return self._est_views(self._est_flat)
 
     # ---- source map -------------------------------------------------------------------------------------------------------
     def reset(self, lanes):
         """Lanes (sequences, in [0, B)) whose next step starts a new clip: their K particle rows start fresh, counter 0.  A scored
-        stream also forgets those lanes' identities (``last_id``: a new clip has new ones); their counters stay."""
+        stream also forgets those lanes' identities (``last_id``: a new clip has new ones); their counters stay.  A stream with
+        ``identity=True`` frees those lanes' track entries (``trk_id`` = -1) and keeps their ``next_id``: an id is never reused within
+        a lane."""
         self.carried.reset(lanes)
-        if self.scored:
+        if self.scored or self.identified:
             lanes = sorted(set(self.carried.check_lanes(lanes)))
             if lanes:
                 with self.carried._on_core_stream():
                     for j in lanes:
-                        self._score["last_id"][j].fill_(-1)
+                        if self.scored:
+                            self._score["last_id"][j].fill_(-1)
+                        if self.identified:
+                            self._ident["trk_id"][j].fill_(-1)
 
     def resample(self, src_rows):
         """Row r of the next step continues row src_rows[r] (-1: starts fresh); e.g. SMC resampling of the particles of each
@@ -368,6 +428,31 @@ class SqairStream(object):
         res["mota"] = 1.0 - div(tot["fn"] + tot["fp"] + tot["idsw"], tot["truth"])
         res["motp"] = div(float(iou_sum.sum()), tot["tp"])
         res["count_accuracy"] = div(tot["count_hit"], tot["frames"])
+        return res
+
+    # ---- lane identities --------------------------------------------------------------------------------------------------
+    def identities(self):
+        """The identities so far (include/sqair_hip.h: sqair_set_identity): per lane the int64 counters ``frames``, ``frames_invalid``,
+        ``objects``, ``kept``, ``bridged``, ``reidentified``, ``born``, ``ended`` [B] and ``next_id`` [B]; pooled over the lanes
+        ``bridged_rate`` = bridged / objects and ``reidentified_rate`` = reidentified / objects (NaN without objects); and the track
+        table ``trk_id``, ``trk_age``, ``trk_len`` [B, M] and ``trk_box`` [B, M, 4] (host tensors): the entries with ``trk_id`` >= 0 and
+        ``trk_age`` > 0 are the tracks remembered but currently unseen."""
+        if not self.identified:
+            raise ValueError("SqairStream.identities: the stream keeps no identities (SqairStream(..., estimate=True, identity=True))")
+        core = self.core
+        with torch.cuda.device(core.device):
+            core._join_in()
+            with core.on_stream():
+                got = {n: self._ident[n].clone() for n in ("counts", "next_id", "trk_id", "trk_age", "trk_len", "trk_box")}
+            core._join_out()
+            got = {n: v.cpu() for n, v in got.items()}
+        counts = got.pop("counts")
+        res = {n: counts[:, i].clone() for i, n in enumerate(_capi.IDENT_COUNTS)}
+        tot = {n: int(v.sum()) for n, v in res.items()}
+        div = lambda a, b: float(a) / b if b else float("nan")
+        res.update(got)
+        res["bridged_rate"] = div(tot["bridged"], tot["objects"])
+        res["reidentified_rate"] = div(tot["reidentified"], tot["objects"])
         return res
 
     # ---- trajectory scoring ------------------------------------------------------------------------------------------------

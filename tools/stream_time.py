@@ -53,6 +53,13 @@ the step's copy of the per-lane answer; next to it the estimate's node and the r
 gated on:
 
     python tools/stream_time.py --score [--out profiles/stream_score_time.json]
+
+With --identity: the price of lane identities (SqairStream(estimate=True, identity=True), include/sqair_hip.h: sqair_set_identity).
+Streams at cfg-2's batch alternating in one process as with --history: plain, SMC, estimate, identity, SMC + estimate, SMC + identity,
+score, score + identity (score_ids="lane"); the scored legs are fed a device-resident truth as with --score.  The identity's node is
+reported next to the estimate's and the resampler's node of the same run.
+
+    python tools/stream_time.py --identity [--out profiles/stream_identity_time.json]
 """
 import argparse
 import json
@@ -299,6 +306,33 @@ def time_score(B, K, N, steps, warmup, rounds=10, hw=(50, 50)):
     return res
 
 
+def time_identity(B, K, N, steps, warmup, rounds=10, hw=(50, 50)):
+    smc = dict(resample="systematic", ess_frac=0.5)
+    idt = dict(estimate=True, identity=True)
+    sc = dict(estimate=True, score=True, score_truth=N)
+    legs = dict(plain={}, smc=smc, estimate=dict(estimate=True), identity=idt, smc_estimate=dict(estimate=True, **smc),
+                smc_identity=dict(idt, **smc), score=sc, score_identity=dict(sc, identity=True, score_ids="lane"))
+    rng = np.random.default_rng(3)
+    box = np.concatenate([rng.uniform(-5, 35, (1, B, N, 2)), rng.uniform(8, 28, (1, B, N, 2))], -1).astype(np.float32)
+    truth = dict(box=torch.as_tensor(box).cuda(), present=torch.ones((1, B, N), dtype=torch.int32).cuda(),
+                 valid=torch.ones((1, B), dtype=torch.int32).cuda())
+    step_kw = dict(score=dict(truth=truth), score_identity=dict(truth=truth))
+    streams, res, med, thr = alternating_streams(legs, B, K, N, steps, warmup, rounds, hw, step_kw)
+    res["lane_bytes_per_step"] = {n: int(streams[n]._est_flat.numel() * 4) for n in ("estimate", "identity")}
+    res["identities"] = {n: (int(v.sum()) if torch.is_tensor(v) and v.dim() == 1 else v) for n, v in streams["smc_identity"].identities().items()
+                         if not n.startswith("trk_")}   # (over the lanes)
+    for key, v in (("latency", med), ("back_to_back", thr)):
+        one_node = v["smc"] - v["plain"]            # the yardstick: one dependent node (the resampler) on this machine, this run
+        added = dict(estimate_node_on_plain=v["estimate"] - v["plain"], estimate_node_on_smc=v["smc_estimate"] - v["smc"],
+                     identity_node_on_estimate=v["identity"] - v["estimate"], identity_node_on_smc_estimate=v["smc_identity"] - v["smc_estimate"],
+                     identity_node_on_score=v["score_identity"] - v["score"])
+        res["us_" + key] = dict(smc_node=1e3 * one_node, **{n: 1e3 * a for n, a in added.items()},
+                                **{n + "_over_smc_node": (a / one_node if one_node > 0 else None) for n, a in added.items()})
+    for st in streams.values():
+        st.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=500)
@@ -311,10 +345,13 @@ def main():
     ap.add_argument("--estimate", action="store_true", help="plain / SMC / estimate / SMC + estimate / with mean_canvas, alternating (profiles/stream_estimate_time.json)")
     ap.add_argument("--layers", action="store_true", help="plain / SMC / estimate / SMC + estimate / layers / SMC + layers, alternating (profiles/stream_layers_time.json)")
     ap.add_argument("--score", action="store_true", help="plain / SMC / estimate / SMC + estimate / score / SMC + score, alternating (profiles/stream_score_time.json)")
+    ap.add_argument("--identity", action="store_true", help="plain / SMC / estimate / identity / SMC + estimate / SMC + identity / score / score + identity, alternating (profiles/stream_identity_time.json)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     ov, _, _, _ = config_inputs(2)
-    if args.score:
+    if args.identity:
+        shapes = [dict(name="cfg2_batch_identity", **time_identity(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
+    elif args.score:
         shapes = [dict(name="cfg2_batch_score", **time_score(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
     elif args.layers:
         shapes = [dict(name="cfg2_batch_layers", **time_layers(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
