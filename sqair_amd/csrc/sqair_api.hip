@@ -1,6 +1,6 @@
 // libsqair_hip.so — handle, parameter inventory, weight packing plan, and the launch sequence of the
 // SQAIR forward pass.  Host code only; kernels live in sqair_linear.hip / sqair_glue.hip; the carried state and the forecast in
-// sqair_state.hip.
+// sqair_state.hip, the lane answers in sqair_lane_api.hip.
 //
 // The launch sequence of one frame restates SQAIRTimestep + AIRDecoder (reference:
 // sqair/sqair_modules.py:446-582, sqair/core.py:164-359, sqair/propagate.py:68-184,
@@ -1395,22 +1395,13 @@ SQ_LOCAL int sq_forward_impl(SqairHandle* h, const float* flat, const float* pac
   if (st.on && st.out) sq_launch_state_export(state_at(T, T), s);
   // track history: this pass's rows, the map it imported through and its counters into the ring (sqair_set_history) -- before the
   // resampler overwrites that map
-  if (st.hist_on) sq_launch_history_push(sq_history_push_args(h, st, out, w.t_row, T, B), s);
-  // lane estimates: one answer per (frame, lane) from this pass's rows and the log weights they carry (sqair_set_estimate) -- before
-  // the resampler zeroes those weights and rewrites the map
-  if (st.est_on) sq_launch_lane_estimate(sq_estimate_args(h, w.rec_m_all + (size_t)M * RW, out, T, B), s);
-  // object layers: the decoder's sum over slots taken apart per object of the lane (sqair_set_layers), from the glimpses section J
-  // decoded -- the caller's buffer or the workspace's -- by the estimate's weights and association
-  if (st.lay_on &&
-      sq_launch_lane_layers(sq_layers_args(h, w.rec_m_all + (size_t)M * RW, (out.glimpse && !train) ? out.glimpse : w.glimpse, out, T, B), s) != 0) {
-    sq_set_error(h, "sqair_forward: the object layers launch failed (dynamic LDS limit)");
-    return -2;
+  if (st.hist.on) sq_launch_history_push(sq_history_push_args(h, st, out, w.t_row, T, B), s);
+  // the lane answers (sqair_lane_api.hip): estimate -> layers -> identity -> score over this pass's merged records and the glimpses
+  // section J decoded (the caller's buffer or the workspace's) -- before the resampler zeroes the weights and rewrites the map
+  {
+    const int rc = sq_launch_lane_answers(h, st.lane, w.rec_m_all + (size_t)M * RW, (out.glimpse && !train) ? out.glimpse : w.glimpse, out, T, B, s);
+    if (rc != 0) return rc;
   }
-  // lane identities: the lane's objects linked to the lane's track table (sqair_set_identity), updated in place -- before the score,
-  // which may read the ids it writes (sqair_set_score_ids)
-  if (st.ident_on) sq_launch_lane_identity(sq_identity_args(h, T, B), s);
-  // stream scoring: the lane answer the estimate just wrote against the caller's ground truth (sqair_set_score), accumulated in place
-  if (st.score_on) sq_launch_lane_score(sq_score_args(h, T, B), s);
   // SMC: this pass's log weights -> ESS, evidence and the next pass's source map (sqair_set_smc / SqairCarry.smc)
   if (st.smc_on) sq_launch_smc_resample(sq_smc_args(st.smc, out.log_weights_per_timestep, w.t_row, T, B, K), s);
   SQ_CHECK_HIP(hipGetLastError());

@@ -1,5 +1,5 @@
-// Internal declarations shared by sqair_api.hip (handle, plan, forward pass), sqair_state.hip (carried state, forecast) and
-// sqair_train.hip (backward pass).
+// Internal declarations shared by sqair_api.hip (handle, plan, forward pass), sqair_state.hip (carried state, forecast),
+// sqair_lane_api.hip (lane answers) and sqair_train.hip (backward pass).
 #pragma once
 #include <cstdio>
 #include <cstring>
@@ -20,6 +20,32 @@ enum LayerId {
   L_DISC_S1, L_DEC0, L_DEC1, L_DEC2, L_PROP_RNN2, L_DISC_RNN2,
   L_WHAT_HEAD_I, L_PROP_HEADS_I,   // forward-only packs with interleaved output columns (what fusion, sqair_glue.h: WhatArgs)
   L_COUNT
+};
+
+// The track history's ring as registered (sqair_set_history), by value: on the handle, and in the settings a pass resolves.
+struct SqHistRing {
+  bool on = false;
+  void* ring = nullptr;
+  int64_t bytes = 0;
+  int L = 0;
+  uint32_t fields = 0;
+};
+// The lane answers of a pass, by value: on the handle as registered, and in the settings a pass resolves (SqStateRes).  One
+// launch each after the history push, before the resampler, in this order (sq_launch_lane_answers): the estimate
+// (k_lane_estimate; T: the frames per pass its outputs were sized for), then its followers, which read what it writes and are
+// only ever on with it and for its T -- the layers (k_lane_layers), the identity (k_lane_identity) and the score (k_lane_score).
+// score_ids: the score reads the identity's lane_id for obj_id; only ever with both on.  All off is SqLaneSet{}.
+struct SqLaneSet {
+  bool est_on = false;
+  SqairLaneEstimate est = {};
+  int est_T = 0;
+  bool lay_on = false;
+  SqairLaneLayers lay = {};
+  bool ident_on = false;
+  SqairLaneIdentity ident = {};
+  bool score_on = false;
+  SqairLaneScore score = {};
+  bool score_ids = false;
 };
 
 struct SqairHandle {
@@ -82,29 +108,13 @@ struct SqairHandle {
   bool smc_on = false;
   SqairSmc smc = {};                 // (smc.src_rows == state_src and its B == state_B while smc_on)
   // track history (sqair_set_history): one k_history_push launch after the state export, before the resampler
-  bool hist_on = false;
-  void* hist_ring = nullptr;
-  int64_t hist_bytes = 0;
-  int hist_L = 0, hist_T = 0;        // hist_T: frames per pass of the ring's slots, 0 until the first pass pushes
-  uint32_t hist_fields = 0;
+  SqHistRing hist;
+  int hist_T = 0;                    // frames per pass of the ring's slots, 0 until the first pass pushes
   // missing-frame steps (sqair_set_observed): the passes' kernels read this device mask [observed_T][state_B]
   const int32_t* observed = nullptr;
   int observed_T = 0;
-  // lane estimates (sqair_set_estimate): one k_lane_estimate launch after the history push, before the resampler
-  bool est_on = false;
-  SqairLaneEstimate est = {};
-  int est_T = 0;
-  // object layers (sqair_set_layers): one k_lane_layers launch directly after the estimate's; needs the estimate, T = est_T
-  bool lay_on = false;
-  SqairLaneLayers lay = {};
-  // stream scoring (sqair_set_score): one k_lane_score launch after the estimate's and the layers'; needs the estimate, T = est_T
-  bool score_on = false;
-  SqairLaneScore score = {};
-  // lane identities (sqair_set_identity): one k_lane_identity launch after the layers', before the score's; needs the estimate,
-  // T = est_T.  score_ids (sqair_set_score_ids): the score reads the identity's lane_id for obj_id; only ever with both on
-  bool ident_on = false;
-  SqairLaneIdentity ident = {};
-  bool score_ids = false;
+  // the lane answers (sqair_set_estimate / _layers / _identity / _score / _score_ids; sqair_lane_api.hip)
+  SqLaneSet lane;
   // generic capture slots (sqair_capture_begin / _end / _launch): any sequence of C-ABI calls as one HIP graph
   hipGraph_t cap_graph[4] = {nullptr, nullptr, nullptr, nullptr};
   hipGraphExec_t cap_exec[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -229,47 +239,55 @@ Workspace sq_carve(const SqairHandle* h, int T, int B, float* base, bool train);
 // table carry it: the older ones (sq_carve, sq_run, sq_state_refusal, ...) were exported before and stay so, the table unchanged.
 #define SQ_LOCAL __attribute__((visibility("hidden")))
 
+static inline int sq_no(SqairHandle* h, const std::string& why) { sq_set_error(h, why); return -1; }   // a refusal: -1 + error text
+// -1 + "<who><name> must lie in (0, 1]" unless it does: an IoU or coverage threshold (NaN fails both comparisons)
+static inline int sq_unit_refusal(SqairHandle* h, const std::string& who, const char* name, float v) {
+  return v > 0.0f && v <= 1.0f ? 0 : sq_no(h, who + name + " must lie in (0, 1]");
+}
+
 // ---- carried model state (sqair_state.hip) ----
 int64_t sq_state_row_floats(const SqairHandle* h);   // floats of one particle row of the state blob
 // The carried-state settings of one pass, resolved once per call and passed by value: the handle's (sq_resolve_pass; all off for
-// a training pass) or a carried training call's (sq_carry_state).  The pass reads these, never the handle's registration fields,
-// and nothing between resolution and return writes those.  `fresh`: k_state_import records each row's fresh / imported flag for
-// the backward.  lay_on, ident_on and score_on are only ever set with est_on: whoever clears est_on clears them explicitly with it.
+// a training pass) or a carried training call's (sq_carry_state).  The pass and the argument builders it calls read these, never
+// the handle's registration fields (of the handle only cfg and the error text), and nothing between resolution and return writes
+// those.  `fresh`: k_state_import records each row's fresh / imported flag for the backward.  hist, observed and lane: the
+// handle's inference passes only -- a carried training call never pushes, coasts on the handle's mask or answers per lane.
 struct SqStateRes {
-  bool on;
-  const void* in; void* out; const int32_t* src;
-  bool fresh;
-  bool smc_on; SqairSmc smc;
-  bool hist_on = false;   // (the handle's inference passes only: a carried training call never pushes)
+  bool on = false;
+  const void* in = nullptr;
+  void* out = nullptr;
+  const int32_t* src = nullptr;
+  bool fresh = false;
+  bool smc_on = false;
+  SqairSmc smc = {};
   const int32_t* observed = nullptr;   // (the handle's device mask of sqair_set_observed, a masked carried chunk's own, or NULL)
-  bool est_on = false;    // (the handle's inference passes only: a carried training call never estimates)
-  bool lay_on = false;    // (the same; only ever with est_on)
-  bool score_on = false;  // (the same; only ever with est_on)
-  bool ident_on = false;  // (the same; only ever with est_on)
+  SqHistRing hist;
+  SqLaneSet lane;
 };
 // The refusals of a pass on the handle's settings -- observed mask, state, SMC, history, estimate, in this order (-1 + error text,
 // before any HIP call) -- then the settings in *st.  The only place that fixes the history ring's T: a refused call changes nothing.
 SQ_LOCAL int sq_resolve_pass(SqairHandle* h, bool train, int T, int B, int t_offset, const SqairOutputs* out, SqStateRes* st);
 // `st` for a pass that changes nothing outside its workspace and outputs (a capture's eager pre-pass): what it reads stays (the rows
-// imported through the map, the mask), what it writes goes (export, history push, estimate, layers, identity, score, resampler).
+// imported through the map, the mask), what it writes goes (export, history push, the lane answers, resampler).
 SQ_LOCAL SqStateRes sq_without_effects(SqStateRes st);
 SQ_LOCAL SqStateRes sq_carry_state(const SqairCarry* c);
 SQ_LOCAL StateArgs sq_state_args(const SqairHandle* h, const SqStateRes& st, int R, float* rec, float* temporal, float* prior, float* last_id,
                                  int* t_row, float* fresh, int t0);
+// -1 + "<who>B = ... but the state ..." when a call's B is not the registered state's
+SQ_LOCAL int sq_state_b_mismatch(SqairHandle* h, const std::string& who, int B);
 // missing-frame steps: -1 + error text for a training call, or a pass of another T, while a mask is set (host only)
 SQ_LOCAL int sq_observed_refusal(SqairHandle* h, bool train, int T);
-// track history: the push's arguments for a pass of T frames
+// track history: the push's arguments for a pass of T frames into the ring of `st` (of `h` only cfg)
 SQ_LOCAL HistPushArgs sq_history_push_args(const SqairHandle* h, const SqStateRes& st, const SqairOutputs& out, const int* t_row, int T, int B);
 SQ_LOCAL SmcArgs sq_smc_args(const SqairSmc& m, const float* lw, const int32_t* t_row, int T, int B, int K);
-// lane estimates: the kernel's arguments for a pass of T frames over the merged records `rec` [T][R][N][rec::W]
-SQ_LOCAL LaneEstArgs sq_estimate_args(const SqairHandle* h, const float* rec, const SqairOutputs& out, int T, int B);
-// object layers: the kernel's arguments for a pass of T frames over the merged records `rec` and the decoded glimpses `glimpse`
-// [T][R][N][G*G] (a pass of another T is the estimate's to refuse: the layers are only ever registered for the estimate's T)
-SQ_LOCAL LaneLayerArgs sq_layers_args(const SqairHandle* h, const float* rec, const float* glimpse, const SqairOutputs& out, int T, int B);
-// stream scoring: the kernel's arguments for a pass of T frames -- the estimate's own output buffers and the registered score
-SQ_LOCAL LaneScoreArgs sq_score_args(const SqairHandle* h, int T, int B);
-// lane identities: the kernel's arguments for a pass of T frames -- the estimate's own output buffers and the registered identity
-SQ_LOCAL LaneIdentArgs sq_identity_args(const SqairHandle* h, int T, int B);
+// ---- lane answers (sqair_lane_api.hip) ----
+// the refusal of a pass with the estimate on (host only: before any HIP call; sq_resolve_pass calls it last)
+SQ_LOCAL int sq_estimate_refusal(SqairHandle* h, int T, const SqairOutputs* outp);
+// The lane launches of a pass of T frames, `l` as resolved: estimate -> layers -> identity -> score over the merged records `rec`
+// [T][R][N][rec::W], the decoded glimpses `glimpse` [T][R][N][G*G] and the pass's outputs.  0, or -2 + error text when the layers'
+// launch fails (dynamic LDS limit).  Of `h` only cfg and the error text.
+SQ_LOCAL int sq_launch_lane_answers(SqairHandle* h, const SqLaneSet& l, const float* rec, const float* glimpse, const SqairOutputs& out,
+                                    int T, int B, hipStream_t s);
 // section A of a frame of the pass, and a frame of the forecast: the propagation-prior cell and its statistics (sqair_api.hip)
 SQ_LOCAL int sq_prior_step(SqairHandle* h, const float* packed, hipStream_t s, int M, const float* rec_prev, const float* prior_prev,
                            float* prior_p, float* pgz, float* pgrh, float* pgxh, float* pstats, float* o3, float* o1);

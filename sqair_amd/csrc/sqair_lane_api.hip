@@ -1,0 +1,301 @@
+// libsqair_hip.so -- the lane answers on the native side of the C ABI (include/sqair_hip.h): the estimate and its followers, the
+// layers, the identity and the score.  Their registration on a handle as one block (SqLaneSet, sqair_internal.h: sqair_set_estimate
+// / _layers / _score / _identity / _score_ids), the estimate's refusal of a pass, ONE builder per kernel's arguments -- called by the
+// pass and by the kernel-level entry point alike --, the pass's launch sequence (sq_launch_lane_answers, called by sq_forward_impl
+// with the block sq_resolve_pass resolved) and the stand-alone entry points (sqair_lane_*_test, sqair_lane_traj_score).  Host code
+// only: the kernels and their launchers live in sqair_lane.hip, which work here does not move.  A further follower is one member
+// of SqLaneSet, its registration and builder here, and one line of sq_launch_lane_answers.
+#include "sqair_internal.h"
+
+// ------------------------------------------------------------------------------------------------
+// what every user of one of the public structs checks, -1 + "<who>..." when a field is off
+// ------------------------------------------------------------------------------------------------
+static int sq_truth_slots_refusal(SqairHandle* h, const std::string& who, int G) {
+  if (G >= 1 && G <= SQ_SCORE_MAXG) return 0;
+  return sq_no(h, who + "G = " + std::to_string(G) + " must lie in 1.." + std::to_string(SQ_SCORE_MAXG));
+}
+static int sq_estimate_fields(SqairHandle* h, const std::string& who, const SqairLaneEstimate& e) {
+  if (sq_unit_refusal(h, who, "iou_min", e.iou_min) != 0) return -1;
+  if (!e.best_row) return sq_no(h, who + "best_row must not be NULL");
+  return 0;
+}
+static int sq_layers_fields(SqairHandle* h, const std::string& who, const SqairLaneLayers& l) {
+  if (sq_unit_refusal(h, who, "cover_min", l.cover_min) != 0) return -1;
+  if (!l.match && !l.layer && !l.cover && !l.owner) return sq_no(h, who + "at least one of match, layer, cover and owner must be set");
+  return 0;
+}
+static int sq_score_fields(SqairHandle* h, const std::string& who, const SqairLaneScore& c) {
+  if (sq_truth_slots_refusal(h, who, c.G) != 0 || sq_unit_refusal(h, who, "iou_min", c.iou_min) != 0) return -1;
+  if (!c.truth_box || !c.truth_present || !c.truth_valid || !c.counts || !c.iou_sum || !c.last_id)
+    return sq_no(h, who + "truth_box, truth_present, truth_valid, counts, iou_sum and last_id must not be NULL");
+  return 0;
+}
+static int sq_identity_fields(SqairHandle* h, const std::string& who, const SqairLaneIdentity& c) {
+  const int N = h->cfg.n_steps_per_image;
+  if (c.M < N || c.M > SQ_IDENT_MAXM)
+    return sq_no(h, who + "M = " + std::to_string(c.M) + " must lie in N = " + std::to_string(N) + ".." + std::to_string(SQ_IDENT_MAXM));
+  if (sq_unit_refusal(h, who, "iou_min", c.iou_min) != 0) return -1;
+  if (!(c.reid_dist >= 0.0f)) return sq_no(h, who + "reid_dist must be >= 0");                          // (NaN fails)
+  if (!(c.reid_what > 0.0f)) return sq_no(h, who + "reid_what must lie in (0, +inf]");                  // (NaN fails)
+  if (c.max_age < 0) return sq_no(h, who + "max_age must be >= 0");
+  if (!c.trk_id || !c.trk_word || !c.trk_age || !c.trk_len || !c.trk_box || !c.next_id || !c.counts || !c.lane_id)
+    return sq_no(h, who + "trk_id, trk_word, trk_age, trk_len, trk_box, next_id, counts and lane_id must not be NULL");
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// registration: the handle's block, h->lane.  Switching the estimate off is h->lane = SqLaneSet{}: its followers go with it
+// ------------------------------------------------------------------------------------------------
+static void sq_layers_off(SqLaneSet& l) { l.lay_on = false; l.lay = SqairLaneLayers{}; }
+// (the score reads the identity's ids only while both are on: either going off puts score_ids back to 0)
+static void sq_score_off(SqLaneSet& l) { l.score_on = false; l.score = SqairLaneScore{}; l.score_ids = false; }
+static void sq_identity_off(SqLaneSet& l) { l.ident_on = false; l.ident = SqairLaneIdentity{}; l.score_ids = false; }
+// what the followers need of the estimate they read (best_row is never NULL in a registered estimate; `what`: the identity keeps an
+// appearance, trk_what, and reads the estimate's)
+static bool sq_estimate_scorable(const SqairLaneEstimate& e) { return e.box && e.presence && e.obj_id && e.map_count; }
+static bool sq_estimate_identifiable(const SqairLaneEstimate& e, bool what) {
+  return e.box && e.presence && e.obj_id && e.best_row && (!what || e.what);
+}
+static int sq_estimate_smc_mismatch(SqairHandle* h, const std::string& who, const SqairLaneEstimate& e) {
+  if (!h->smc_on || e.log_w == h->smc.log_w) return 0;
+  return sq_no(h, who + "with SMC on (sqair_set_smc) log_w must be smc->log_w, the carried log weights of the pass's rows");
+}
+// what every follower's registration checks after its own needs of the estimate: the estimate's T, the state's B
+static int sq_follower_shape_refusal(SqairHandle* h, const std::string& who, int T, int B) {
+  if (T != h->lane.est_T)
+    return sq_no(h, who + "T = " + std::to_string(T) + " but the estimate set by sqair_set_estimate is for T = " + std::to_string(h->lane.est_T));
+  return sq_state_b_mismatch(h, who, B);
+}
+extern "C" int sqair_set_estimate(SqairHandle* h, const SqairLaneEstimate* est, int T, int B) {
+  if (!h) return -1;
+  if (!est) {
+    h->lane = SqLaneSet{};
+    return 0;
+  }
+  const std::string who = "sqair_set_estimate: ";
+  if (!h->state_on) return sq_no(h, who + "needs a carried state (sqair_set_state): the estimate weighs the rows it carries");
+  if (T < 1) return sq_no(h, who + "T must be >= 1");
+  if (sq_state_b_mismatch(h, who, B) != 0) return -1;
+  if (sq_estimate_fields(h, who, *est) != 0 || sq_estimate_smc_mismatch(h, who, *est) != 0) return -1;
+  // a re-registered estimate drops the followers it can no longer feed: outputs sized for the other T, outputs they read gone
+  SqLaneSet& l = h->lane;
+  if (T != l.est_T) sq_layers_off(l);
+  if (T != l.est_T || !sq_estimate_scorable(*est)) sq_score_off(l);
+  if (T != l.est_T || !sq_estimate_identifiable(*est, l.ident.trk_what != nullptr)) sq_identity_off(l);
+  l.est_on = true; l.est = *est; l.est_T = T;
+  return 0;
+}
+int sq_estimate_refusal(SqairHandle* h, int T, const SqairOutputs* outp) {
+  if (!h->state_on || !h->lane.est_on) return 0;
+  const std::string who = "lane estimate (sqair_set_estimate): ";
+  if (T != h->lane.est_T)
+    return sq_no(h, who + "the outputs were registered for passes of T = " + std::to_string(h->lane.est_T) + " frames, a pass of T = " +
+                    std::to_string(T) + " cannot fill them");
+  if (!outp || !outp->log_weights_per_timestep)
+    return sq_no(h, who + "the weights are formed from log_weights_per_timestep: a pass with the estimate on must bind that output");
+  if (h->lane.est.mean_canvas && !outp->canvas) return sq_no(h, who + "mean_canvas averages the pass's canvases: the pass must bind out->canvas");
+  return sq_estimate_smc_mismatch(h, who, h->lane.est);
+}
+extern "C" int sqair_set_layers(SqairHandle* h, const SqairLaneLayers* lay, int T, int B) {
+  if (!h) return -1;
+  if (!lay) {
+    sq_layers_off(h->lane);
+    return 0;
+  }
+  const std::string who = "sqair_set_layers: ";
+  if (!h->state_on || !h->lane.est_on)
+    return sq_no(h, who + "needs an estimate (sqair_set_estimate): the layers weigh and associate the particles as it does");
+  if (sq_follower_shape_refusal(h, who, T, B) != 0 || sq_layers_fields(h, who, *lay) != 0) return -1;
+  h->lane.lay_on = true; h->lane.lay = *lay;
+  return 0;
+}
+extern "C" int sqair_set_score(SqairHandle* h, const SqairLaneScore* score, int T, int B) {
+  if (!h) return -1;
+  if (!score) {
+    sq_score_off(h->lane);
+    return 0;
+  }
+  const std::string who = "sqair_set_score: ";
+  if (!h->state_on || !h->lane.est_on)
+    return sq_no(h, who + "needs an estimate (sqair_set_estimate): the score reads the lane answer it writes");
+  if (!sq_estimate_scorable(h->lane.est))
+    return sq_no(h, who + "the estimate (sqair_set_estimate) must bind box, presence, obj_id and map_count: the score reads them");
+  if (sq_follower_shape_refusal(h, who, T, B) != 0 || sq_score_fields(h, who, *score) != 0) return -1;
+  h->lane.score_on = true; h->lane.score = *score;
+  return 0;
+}
+extern "C" int sqair_set_identity(SqairHandle* h, const SqairLaneIdentity* id, int T, int B) {
+  if (!h) return -1;
+  if (!id) {
+    sq_identity_off(h->lane);
+    return 0;
+  }
+  const std::string who = "sqair_set_identity: ";
+  if (!h->state_on || !h->lane.est_on)
+    return sq_no(h, who + "needs an estimate (sqair_set_estimate): the identity links the lane answer it writes");
+  if (!sq_estimate_identifiable(h->lane.est, false))
+    return sq_no(h, who + "the estimate (sqair_set_estimate) must bind box, presence, obj_id and best_row: the identity reads them");
+  if (id->trk_what && !h->lane.est.what)
+    return sq_no(h, who + "trk_what needs the estimate (sqair_set_estimate) to bind what: the appearance it remembers");
+  if (sq_follower_shape_refusal(h, who, T, B) != 0 || sq_identity_fields(h, who, *id) != 0) return -1;
+  h->lane.ident_on = true; h->lane.ident = *id;
+  return 0;
+}
+extern "C" int sqair_set_score_ids(SqairHandle* h, int lane_ids) {
+  if (!h) return -1;
+  if (lane_ids && !(h->state_on && h->lane.est_on && h->lane.score_on && h->lane.ident_on))
+    return sq_no(h, "sqair_set_score_ids: needs both a score (sqair_set_score) and an identity (sqair_set_identity): the score reads "
+                    "the lane_id the identity writes");
+  h->lane.score_ids = lane_ids != 0;
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the kernels' arguments, one builder each: the pass (sq_launch_lane_answers) and the kernel-level entry points both call these
+// ------------------------------------------------------------------------------------------------
+static LaneEstArgs sq_estimate_args(const SqairConfig& c, const LaneRows& rows, const float* what, int what_ld, const float* canvas,
+                                    const float* lw, const SqairLaneEstimate& est, int T, int B, int K) {
+  LaneEstArgs a; memset(&a, 0, sizeof(a));
+  a.rows = rows;
+  a.what = what; a.what_ld = what_ld; a.canvas = canvas; a.lw = lw; a.est = est;
+  a.T = T; a.B = B; a.K = K; a.N = c.n_steps_per_image; a.nw = c.n_what; a.H = c.img_h; a.W = c.img_w;
+  return a;
+}
+static LaneLayerArgs sq_layers_args(const SqairConfig& c, const LaneRows& rows, const float* glimpse, const float* lw, const float* log_w,
+                                    float iou_min, const SqairLaneLayers& lay, int T, int B, int K) {
+  LaneLayerArgs a; memset(&a, 0, sizeof(a));
+  a.rows = rows;
+  a.glimpse = glimpse; a.lw = lw; a.log_w = log_w; a.iou_min = iou_min; a.lay = lay;
+  a.T = T; a.B = B; a.K = K; a.N = c.n_steps_per_image; a.G = c.glimpse_size; a.H = c.img_h; a.W = c.img_w;
+  return a;
+}
+// (`what` is read only by an identity that keeps an appearance, trk_what)
+static LaneIdentArgs sq_identity_args(const SqairConfig& c, const float* box, const float* presence, const float* obj_id, const float* what,
+                                      const int32_t* best_row, const SqairLaneIdentity& id, int T, int B) {
+  LaneIdentArgs a; memset(&a, 0, sizeof(a));
+  a.box = box; a.presence = presence; a.obj_id = obj_id; a.best_row = best_row; a.what = id.trk_what ? what : nullptr; a.id = id;
+  a.T = T; a.B = B; a.N = c.n_steps_per_image; a.nw = c.n_what;
+  return a;
+}
+static LaneScoreArgs sq_score_args(const SqairConfig& c, const float* box, const float* presence, const float* obj_id,
+                                   const int32_t* map_count, const SqairLaneScore& score, int T, int B) {
+  LaneScoreArgs a; memset(&a, 0, sizeof(a));
+  a.box = box; a.presence = presence; a.obj_id = obj_id; a.map_count = map_count; a.sc = score;
+  a.T = T; a.B = B; a.N = c.n_steps_per_image;
+  return a;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the pass: every lane launch, in the one order they have.  The estimate comes before the resampler zeroes the weights it reads
+// and rewrites the map; the followers read the estimate's own output buffers, the identity before the score, which may read the
+// ids it writes.  `l` is the pass's resolved copy: nothing here reads the handle's registration
+// ------------------------------------------------------------------------------------------------
+int sq_launch_lane_answers(SqairHandle* h, const SqLaneSet& l, const float* rec, const float* glimpse, const SqairOutputs& out, int T, int B,
+                           hipStream_t s) {
+  if (!l.est_on) return 0;   // (no follower without it)
+  const SqairConfig& c = h->cfg;
+  const int K = c.k_particles;
+  const SqairLaneEstimate& e = l.est;
+  const float* lw = out.log_weights_per_timestep;
+  // lane estimates: one answer per (frame, lane) from this pass's rows and the log weights they carry (sqair_set_estimate)
+  sq_launch_lane_estimate(sq_estimate_args(c, LaneRows{rec + rec::WHERE, rec::W, rec + rec::PRES, rec::W, rec + rec::ID, rec::W, 1},
+                                           rec + rec::WHAT, rec::W, out.canvas, lw, e, T, B, K), s);
+  // object layers: the decoder's sum over slots taken apart per object of the lane (sqair_set_layers), by the estimate's weights
+  // and association
+  if (l.lay_on &&
+      sq_launch_lane_layers(sq_layers_args(c, LaneRows{rec + rec::WHERE, rec::W, rec + rec::PRES, rec::W, nullptr, 0, 1}, glimpse, lw,
+                                           e.log_w, e.iou_min, l.lay, T, B, K), s) != 0) {
+    sq_set_error(h, "sqair_forward: the object layers launch failed (dynamic LDS limit)");
+    return -2;
+  }
+  // lane identities: the lane's objects linked to the lane's track table (sqair_set_identity), updated in place
+  if (l.ident_on) sq_launch_lane_identity(sq_identity_args(c, e.box, e.presence, e.obj_id, e.what, e.best_row, l.ident, T, B), s);
+  // stream scoring: the lane answer against the caller's ground truth (sqair_set_score), accumulated in place.  sqair_set_score_ids:
+  // the kernel takes the id as a 32-bit word, so the identity's int32 lane_id stands where obj_id stands
+  if (l.score_on) {
+    const float* ids = (l.ident_on && l.score_ids) ? reinterpret_cast<const float*>(l.ident.lane_id) : e.obj_id;
+    sq_launch_lane_score(sq_score_args(c, e.box, e.presence, ids, e.map_count, l.score, T, B), s);
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// kernel-level checks (tests/test_{estimate,layers,score,identity}_kernel.py): one kernel on caller tensors, no state and no pass;
+// K, where there is one, is given (1..SQ_MAX_K)
+// ------------------------------------------------------------------------------------------------
+extern "C" int sqair_lane_estimate_test(SqairHandle* h, const float* where, const float* presence, const float* obj_id,
+                                        const float* what, const float* canvas, const float* lw, int T, int B, int K,
+                                        const SqairLaneEstimate* est, void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_lane_estimate_test: ";
+  if (!where || !presence || !obj_id || !lw || !est || T < 1 || B < 1 || K < 1 || K > SQ_MAX_K || T > 65535 ||
+      (int64_t)B * K > INT32_MAX)
+    return sq_no(h, who + "null where / presence / obj_id / lw / est or bad T / B / K (1 <= K <= " + std::to_string(SQ_MAX_K) + ")");
+  if (sq_estimate_fields(h, who, *est) != 0) return -1;
+  if (est->what && !what) return sq_no(h, who + "est->what needs what");
+  if (est->mean_canvas && !canvas) return sq_no(h, who + "est->mean_canvas needs canvas");
+  sq_launch_lane_estimate(sq_estimate_args(h->cfg, LaneRows{where, 4, presence, 1, obj_id, 1, 1}, what, h->cfg.n_what, canvas, lw, *est,
+                                           T, B, K), (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+extern "C" int sqair_lane_layers_test(SqairHandle* h, const float* glimpse, const float* where, const float* presence, const float* lw,
+                                      const float* log_w, float iou_min, int T, int B, int K, const SqairLaneLayers* lay, void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_lane_layers_test: ";
+  if (!glimpse || !where || !presence || !lw || !lay || T < 1 || B < 1 || K < 1 || K > SQ_MAX_K || T > 65535 || (int64_t)B * K > INT32_MAX)
+    return sq_no(h, who + "null glimpse / where / presence / lw / lay or bad T / B / K (1 <= K <= " + std::to_string(SQ_MAX_K) + ")");
+  if (sq_unit_refusal(h, who, "iou_min", iou_min) != 0 || sq_layers_fields(h, who, *lay) != 0) return -1;
+  if (sq_launch_lane_layers(sq_layers_args(h->cfg, LaneRows{where, 4, presence, 1, nullptr, 0, 1}, glimpse, lw, log_w, iou_min, *lay,
+                                           T, B, K), (hipStream_t)stream) != 0) {
+    sq_set_error(h, who + "the launch failed (dynamic LDS limit)");
+    return -2;
+  }
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+extern "C" int sqair_lane_score_test(SqairHandle* h, const float* box, const float* presence, const float* obj_id, const int32_t* map_count,
+                                     int T, int B, const SqairLaneScore* score, void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_lane_score_test: ";
+  if (!box || !presence || !obj_id || !map_count || !score || T < 1 || B < 1 || T > 65535)
+    return sq_no(h, who + "null box / presence / obj_id / map_count / score or bad T / B");
+  if (sq_score_fields(h, who, *score) != 0) return -1;
+  sq_launch_lane_score(sq_score_args(h->cfg, box, presence, obj_id, map_count, *score, T, B), (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+extern "C" int sqair_lane_identity_test(SqairHandle* h, const float* box, const float* presence, const float* obj_id, const float* what,
+                                        const int32_t* best_row, int T, int B, const SqairLaneIdentity* id, void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_lane_identity_test: ";
+  if (!box || !presence || !obj_id || !best_row || !id || T < 1 || B < 1 || T > 65535)
+    return sq_no(h, who + "null box / presence / obj_id / best_row / id or bad T / B");
+  if (sq_identity_fields(h, who, *id) != 0) return -1;
+  if (id->trk_what && !what) return sq_no(h, who + "id->trk_what needs what");
+  sq_launch_lane_identity(sq_identity_args(h->cfg, box, presence, obj_id, what, best_row, *id, T, B), (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+// trajectory scoring (include/sqair_hip.h: sqair_lane_traj_score): a stand-alone call on the table a lane forecast or a lane trace
+// wrote -- or on a test's tensors --, nothing registered on the handle, which gives N and the error text
+extern "C" int sqair_lane_traj_score(SqairHandle* h, const SqairLaneTraj* table, const SqairTrajTruth* truth, const SqairTrajScore* score,
+                                     int F, int B, void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_lane_traj_score: ";
+  if (!table || !truth || !score) return sq_no(h, who + "table, truth and score must not be NULL");
+  if (F < 1 || F > 65535 || B < 1) return sq_no(h, who + "F = " + std::to_string(F) + " must lie in 1..65535 and B = " + std::to_string(B) + " must be >= 1");
+  if (sq_truth_slots_refusal(h, who, truth->G) != 0 || sq_unit_refusal(h, who, "iou_min", score->iou_min) != 0) return -1;
+  if (!table->best_row || !table->presence || !table->support || !table->box0 || !table->alive || !table->box_mean || !table->count_prob)
+    return sq_no(h, who + "the table's best_row, presence, support, box0, alive, box_mean and count_prob must not be NULL");
+  if (!truth->anchor_box || !truth->anchor_present || !truth->anchor_valid || !truth->truth_box || !truth->truth_present || !truth->truth_valid)
+    return sq_no(h, who + "anchor_box, anchor_present, anchor_valid, truth_box, truth_present and truth_valid must not be NULL");
+  if (!score->counts || !score->sums || !score->lane_counts) return sq_no(h, who + "counts, sums and lane_counts must not be NULL");
+  if (truth->keep_id && !table->obj_id) return sq_no(h, who + "keep_id needs the table's obj_id: the identities it is compared with");
+  LaneTrajScoreArgs a; memset(&a, 0, sizeof(a));
+  a.tab = *table; a.tr = *truth; a.sc = *score;
+  a.F = F; a.B = B; a.N = h->cfg.n_steps_per_image;
+  sq_launch_lane_traj_score(a, (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}

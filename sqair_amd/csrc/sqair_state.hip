@@ -1,12 +1,12 @@
 // libsqair_hip.so -- the carried model state on the native side of the C ABI (include/sqair_hip.h): the state blob and its
-// registration on a handle (sqair_set_state / _smc / _history / _observed / _estimate / _layers / _score / _identity), the one resolution of a call
-// (sq_resolve_pass: the refusals of a pass, each free of side effects, then the handle's settings by value as an SqStateRes;
-// sq_carry_state: a SqairCarry's), and the forecast that rolls the prior forward from a state (sqair_forecast).  Host code only; the
-// pass, sq_forward_impl (sqair_api.hip), reads the SqStateRes it is given; the kernels live in sqair_glue.hip and sqair_lane.hip.
+// registration on a handle (sqair_set_state / _smc / _history / _observed), the one resolution of a call (sq_resolve_pass: the
+// refusals of a pass, each free of side effects, then the handle's settings by value as an SqStateRes; sq_carry_state: a
+// SqairCarry's), the traces of the history ring and the forecast that rolls the prior forward from a state (sqair_forecast), each
+// with its lane table.  Host code only; the pass, sq_forward_impl (sqair_api.hip), reads the SqStateRes it is given and nothing
+// of the registration; the lane answers a state carries along (estimate, layers, identity, score) are registered and launched in
+// sqair_lane_api.hip; the kernels live in sqair_glue.hip and sqair_lane.hip.
 #include "sqair_internal.h"
 #include "sqair_chain.h"
-
-static int sq_no(SqairHandle* h, const std::string& why) { sq_set_error(h, why); return -1; }   // a refusal: -1 + error text
 
 // carried model state: one blob row per particle row (StateArgs, sqair_glue.h), 4-word aligned
 int64_t sq_state_row_floats(const SqairHandle* h) {
@@ -15,29 +15,12 @@ int64_t sq_state_row_floats(const SqairHandle* h) {
   const int64_t snh = c.time_cell == CELL_LSTM ? 2 * nh : nh, psnh = c.prior_cell == CELL_LSTM ? 2 * nh : nh;
   return (N * (rec::W + snh + psnh) + 2 + 3) / 4 * 4;
 }
-// -1 + "<who>B = ... but the state ..." when a call's B is not the registered state's; likewise T against the estimate's
-static int sq_state_b_mismatch(SqairHandle* h, const std::string& who, int B) {
+int sq_state_b_mismatch(SqairHandle* h, const std::string& who, int B) {
   if (B == h->state_B) return 0;
   return sq_no(h, who + "B = " + std::to_string(B) + " but the state set by sqair_set_state is for B = " + std::to_string(h->state_B));
 }
-static int sq_estimate_t_mismatch(SqairHandle* h, const std::string& who, int T) {
-  if (T == h->est_T) return 0;
-  return sq_no(h, who + "T = " + std::to_string(T) + " but the estimate set by sqair_set_estimate is for T = " + std::to_string(h->est_T));
-}
 static void sq_observed_off(SqairHandle* h) { h->observed = nullptr; h->observed_T = 0; }
-static void sq_layers_off(SqairHandle* h) { h->lay_on = false; h->lay = SqairLaneLayers{}; }
-// (the score reads the identity's ids only while both are on: either going off puts score_ids back to 0)
-static void sq_score_off(SqairHandle* h) { h->score_on = false; h->score = SqairLaneScore{}; h->score_ids = false; }
-static void sq_identity_off(SqairHandle* h) { h->ident_on = false; h->ident = SqairLaneIdentity{}; h->score_ids = false; }
-static void sq_estimate_off(SqairHandle* h) {
-  h->est_on = false; h->est = SqairLaneEstimate{}; h->est_T = 0;
-  sq_layers_off(h);                           // (the layers share the estimate's weights and association: off with it)
-  sq_score_off(h);                            // (the score reads the estimate's outputs: off with it)
-  sq_identity_off(h);                         // (and so does the identity)
-}
-static void sq_history_off(SqairHandle* h) {
-  h->hist_on = false; h->hist_ring = nullptr; h->hist_bytes = 0; h->hist_L = 0; h->hist_T = 0; h->hist_fields = 0;
-}
+static void sq_history_off(SqairHandle* h) { h->hist = SqHistRing{}; h->hist_T = 0; }
 extern "C" int64_t sqair_state_bytes(const SqairHandle* h, int B) {
   if (!h || B < 1) return -1;
   return (int64_t)B * h->cfg.k_particles * sq_state_row_floats(h) * 4;
@@ -49,7 +32,7 @@ extern "C" int sqair_set_state(SqairHandle* h, const void* state_in, void* state
     h->smc_on = false; h->smc = SqairSmc{};   // (SMC resamples the carried state: off with it)
     sq_history_off(h);                        // (the history records the carried rows: off with it)
     sq_observed_off(h);                       // (the mask is per lane of the carried batch: off with it)
-    sq_estimate_off(h);                       // (and so are the estimate's outputs)
+    h->lane = SqLaneSet{};                    // (and so are the lane answers' outputs)
     return 0;
   }
   if (h->cfg.sample_from_prior) return sq_no(h, "sqair_set_state: not with sample_from_prior (generation decides per frame on the host)");
@@ -60,9 +43,9 @@ extern "C" int sqair_set_state(SqairHandle* h, const void* state_in, void* state
   if (h->smc_on && (!state_in || src_rows != h->state_src || B != h->state_B)) {   // (what SMC was registered against is gone)
     h->smc_on = false; h->smc = SqairSmc{};
   }
-  if (h->hist_on && B != h->state_B) sq_history_off(h);   // (the ring was sized for the other B)
+  if (h->hist.on && B != h->state_B) sq_history_off(h);   // (the ring was sized for the other B)
   if (B != h->state_B) sq_observed_off(h);                // (and so was the mask)
-  if (B != h->state_B) sq_estimate_off(h);                // (and the estimate's outputs)
+  if (B != h->state_B) h->lane = SqLaneSet{};             // (and the lane answers' outputs)
   h->state_on = true; h->state_in = state_in; h->state_out = state_out; h->state_src = src_rows; h->state_B = B;
   return 0;
 }
@@ -144,281 +127,6 @@ extern "C" int sqair_smc_resample_test(SqairHandle* h, const float* lw, int T, i
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }
-// ------------------------------------------------------------------------------------------------
-// lane estimates (include/sqair_hip.h: sqair_set_estimate): registration, the refusals of a pass, the arguments of k_lane_estimate
-// (launched by sq_forward_impl) and the kernel-level entry point
-// ------------------------------------------------------------------------------------------------
-// what every user of an SqairLaneEstimate checks, -1 + "<who>..." when one is off
-static int sq_estimate_fields(SqairHandle* h, const std::string& who, const SqairLaneEstimate& e) {
-  if (!(e.iou_min > 0.0f && e.iou_min <= 1.0f)) return sq_no(h, who + "iou_min must lie in (0, 1]");   // (NaN fails both)
-  if (!e.best_row) return sq_no(h, who + "best_row must not be NULL");
-  return 0;
-}
-static int sq_estimate_smc_mismatch(SqairHandle* h, const std::string& who, const SqairLaneEstimate& e) {
-  if (!h->smc_on || e.log_w == h->smc.log_w) return 0;
-  return sq_no(h, who + "with SMC on (sqair_set_smc) log_w must be smc->log_w, the carried log weights of the pass's rows");
-}
-static bool sq_estimate_scorable(const SqairLaneEstimate& e) { return e.box && e.presence && e.obj_id && e.map_count; }
-// (best_row is never NULL in a registered estimate; `what`: the identity keeps an appearance, trk_what, and reads the estimate's)
-static bool sq_estimate_identifiable(const SqairLaneEstimate& e, bool what) {
-  return e.box && e.presence && e.obj_id && e.best_row && (!what || e.what);
-}
-extern "C" int sqair_set_estimate(SqairHandle* h, const SqairLaneEstimate* est, int T, int B) {
-  if (!h) return -1;
-  if (!est) {
-    sq_estimate_off(h);
-    return 0;
-  }
-  const std::string who = "sqair_set_estimate: ";
-  if (!h->state_on) return sq_no(h, who + "needs a carried state (sqair_set_state): the estimate weighs the rows it carries");
-  if (T < 1) return sq_no(h, who + "T must be >= 1");
-  if (sq_state_b_mismatch(h, who, B) != 0) return -1;
-  if (sq_estimate_fields(h, who, *est) != 0 || sq_estimate_smc_mismatch(h, who, *est) != 0) return -1;
-  if (T != h->est_T) sq_layers_off(h);   // (the layers' outputs were sized for the other T)
-  if (T != h->est_T || !sq_estimate_scorable(*est)) sq_score_off(h);   // (and the score's; it reads these four outputs)
-  if (T != h->est_T || !sq_estimate_identifiable(*est, h->ident.trk_what != nullptr)) sq_identity_off(h);   // (and the identity's)
-  h->est_on = true; h->est = *est; h->est_T = T;
-  return 0;
-}
-// the refusal of a pass with the estimate on (host only: before any HIP call)
-static int sq_estimate_refusal(SqairHandle* h, int T, const SqairOutputs* outp) {
-  if (!h->state_on || !h->est_on) return 0;
-  const std::string who = "lane estimate (sqair_set_estimate): ";
-  if (T != h->est_T)
-    return sq_no(h, who + "the outputs were registered for passes of T = " + std::to_string(h->est_T) + " frames, a pass of T = " +
-                    std::to_string(T) + " cannot fill them");
-  if (!outp || !outp->log_weights_per_timestep)
-    return sq_no(h, who + "the weights are formed from log_weights_per_timestep: a pass with the estimate on must bind that output");
-  if (h->est.mean_canvas && !outp->canvas) return sq_no(h, who + "mean_canvas averages the pass's canvases: the pass must bind out->canvas");
-  return sq_estimate_smc_mismatch(h, who, h->est);
-}
-LaneEstArgs sq_estimate_args(const SqairHandle* h, const float* rec, const SqairOutputs& out, int T, int B) {
-  const SqairConfig& c = h->cfg;
-  LaneEstArgs a; memset(&a, 0, sizeof(a));
-  a.rows = LaneRows{rec + rec::WHERE, rec::W, rec + rec::PRES, rec::W, rec + rec::ID, rec::W, 1};
-  a.what = rec + rec::WHAT; a.what_ld = rec::W;
-  a.canvas = out.canvas; a.lw = out.log_weights_per_timestep; a.est = h->est;
-  a.T = T; a.B = B; a.K = c.k_particles; a.N = c.n_steps_per_image; a.nw = c.n_what; a.H = c.img_h; a.W = c.img_w;
-  return a;
-}
-// kernel-level check of the estimate (tests/test_estimate_kernel.py): k_lane_estimate on caller tensors, K given (1..SQ_MAX_K), no
-// state and no pass
-extern "C" int sqair_lane_estimate_test(SqairHandle* h, const float* where, const float* presence, const float* obj_id,
-                                        const float* what, const float* canvas, const float* lw, int T, int B, int K,
-                                        const SqairLaneEstimate* est, void* stream) {
-  if (!h) return -1;
-  const std::string who = "sqair_lane_estimate_test: ";
-  const SqairConfig& c = h->cfg;
-  if (!where || !presence || !obj_id || !lw || !est || T < 1 || B < 1 || K < 1 || K > SQ_MAX_K || T > 65535 ||
-      (int64_t)B * K > INT32_MAX)
-    return sq_no(h, who + "null where / presence / obj_id / lw / est or bad T / B / K (1 <= K <= " + std::to_string(SQ_MAX_K) + ")");
-  if (sq_estimate_fields(h, who, *est) != 0) return -1;
-  if (est->what && !what) return sq_no(h, who + "est->what needs what");
-  if (est->mean_canvas && !canvas) return sq_no(h, who + "est->mean_canvas needs canvas");
-  LaneEstArgs a; memset(&a, 0, sizeof(a));
-  a.rows = LaneRows{where, 4, presence, 1, obj_id, 1, 1};
-  a.what = what; a.what_ld = c.n_what; a.canvas = canvas; a.lw = lw; a.est = *est;
-  a.T = T; a.B = B; a.K = K; a.N = c.n_steps_per_image; a.nw = c.n_what; a.H = c.img_h; a.W = c.img_w;
-  sq_launch_lane_estimate(a, (hipStream_t)stream);
-  SQ_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-// ------------------------------------------------------------------------------------------------
-// object layers (include/sqair_hip.h: sqair_set_layers): registration, the arguments of k_lane_layers (launched by sq_forward_impl
-// directly after k_lane_estimate) and the kernel-level entry point
-// ------------------------------------------------------------------------------------------------
-// what every user of an SqairLaneLayers checks, -1 + "<who>..." when one is off
-static int sq_layers_fields(SqairHandle* h, const std::string& who, const SqairLaneLayers& l) {
-  if (!(l.cover_min > 0.0f && l.cover_min <= 1.0f)) return sq_no(h, who + "cover_min must lie in (0, 1]");   // (NaN fails both)
-  if (!l.match && !l.layer && !l.cover && !l.owner) return sq_no(h, who + "at least one of match, layer, cover and owner must be set");
-  return 0;
-}
-extern "C" int sqair_set_layers(SqairHandle* h, const SqairLaneLayers* lay, int T, int B) {
-  if (!h) return -1;
-  if (!lay) {
-    sq_layers_off(h);
-    return 0;
-  }
-  const std::string who = "sqair_set_layers: ";
-  if (!h->state_on || !h->est_on)
-    return sq_no(h, who + "needs an estimate (sqair_set_estimate): the layers weigh and associate the particles as it does");
-  if (sq_estimate_t_mismatch(h, who, T) != 0) return -1;
-  if (sq_state_b_mismatch(h, who, B) != 0) return -1;
-  if (sq_layers_fields(h, who, *lay) != 0) return -1;
-  h->lay_on = true; h->lay = *lay;
-  return 0;
-}
-LaneLayerArgs sq_layers_args(const SqairHandle* h, const float* rec, const float* glimpse, const SqairOutputs& out, int T, int B) {
-  const SqairConfig& c = h->cfg;
-  LaneLayerArgs a; memset(&a, 0, sizeof(a));
-  a.rows = LaneRows{rec + rec::WHERE, rec::W, rec + rec::PRES, rec::W, nullptr, 0, 1};
-  a.glimpse = glimpse; a.lw = out.log_weights_per_timestep; a.log_w = h->est.log_w; a.iou_min = h->est.iou_min; a.lay = h->lay;
-  a.T = T; a.B = B; a.K = c.k_particles; a.N = c.n_steps_per_image; a.G = c.glimpse_size; a.H = c.img_h; a.W = c.img_w;
-  return a;
-}
-// kernel-level check of the layers (tests/test_layers_kernel.py): k_lane_layers on caller tensors, K given (1..SQ_MAX_K), no state
-// and no pass
-extern "C" int sqair_lane_layers_test(SqairHandle* h, const float* glimpse, const float* where, const float* presence, const float* lw,
-                                      const float* log_w, float iou_min, int T, int B, int K, const SqairLaneLayers* lay, void* stream) {
-  if (!h) return -1;
-  const std::string who = "sqair_lane_layers_test: ";
-  const SqairConfig& c = h->cfg;
-  if (!glimpse || !where || !presence || !lw || !lay || T < 1 || B < 1 || K < 1 || K > SQ_MAX_K || T > 65535 || (int64_t)B * K > INT32_MAX)
-    return sq_no(h, who + "null glimpse / where / presence / lw / lay or bad T / B / K (1 <= K <= " + std::to_string(SQ_MAX_K) + ")");
-  if (!(iou_min > 0.0f && iou_min <= 1.0f)) return sq_no(h, who + "iou_min must lie in (0, 1]");
-  if (sq_layers_fields(h, who, *lay) != 0) return -1;
-  LaneLayerArgs a; memset(&a, 0, sizeof(a));
-  a.rows = LaneRows{where, 4, presence, 1, nullptr, 0, 1};
-  a.glimpse = glimpse; a.lw = lw; a.log_w = log_w; a.iou_min = iou_min; a.lay = *lay;
-  a.T = T; a.B = B; a.K = K; a.N = c.n_steps_per_image; a.G = c.glimpse_size; a.H = c.img_h; a.W = c.img_w;
-  if (sq_launch_lane_layers(a, (hipStream_t)stream) != 0) { sq_set_error(h, who + "the launch failed (dynamic LDS limit)"); return -2; }
-  SQ_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-// ------------------------------------------------------------------------------------------------
-// stream scoring (include/sqair_hip.h: sqair_set_score): registration, the arguments of k_lane_score (launched by sq_forward_impl
-// after the estimate's and the layers' kernels, before the resampler) and the kernel-level entry point
-// ------------------------------------------------------------------------------------------------
-// what every user of an SqairLaneScore checks, -1 + "<who>..." when one is off
-static int sq_score_fields(SqairHandle* h, const std::string& who, const SqairLaneScore& c) {
-  if (c.G < 1 || c.G > SQ_SCORE_MAXG) return sq_no(h, who + "G = " + std::to_string(c.G) + " must lie in 1.." + std::to_string(SQ_SCORE_MAXG));
-  if (!(c.iou_min > 0.0f && c.iou_min <= 1.0f)) return sq_no(h, who + "iou_min must lie in (0, 1]");   // (NaN fails both)
-  if (!c.truth_box || !c.truth_present || !c.truth_valid || !c.counts || !c.iou_sum || !c.last_id)
-    return sq_no(h, who + "truth_box, truth_present, truth_valid, counts, iou_sum and last_id must not be NULL");
-  return 0;
-}
-extern "C" int sqair_set_score(SqairHandle* h, const SqairLaneScore* score, int T, int B) {
-  if (!h) return -1;
-  if (!score) {
-    sq_score_off(h);
-    return 0;
-  }
-  const std::string who = "sqair_set_score: ";
-  if (!h->state_on || !h->est_on)
-    return sq_no(h, who + "needs an estimate (sqair_set_estimate): the score reads the lane answer it writes");
-  if (!sq_estimate_scorable(h->est))
-    return sq_no(h, who + "the estimate (sqair_set_estimate) must bind box, presence, obj_id and map_count: the score reads them");
-  if (sq_estimate_t_mismatch(h, who, T) != 0) return -1;
-  if (sq_state_b_mismatch(h, who, B) != 0) return -1;
-  if (sq_score_fields(h, who, *score) != 0) return -1;
-  h->score_on = true; h->score = *score;
-  return 0;
-}
-LaneScoreArgs sq_score_args(const SqairHandle* h, int T, int B) {
-  LaneScoreArgs a; memset(&a, 0, sizeof(a));
-  a.box = h->est.box; a.presence = h->est.presence; a.obj_id = h->est.obj_id; a.map_count = h->est.map_count; a.sc = h->score;
-  // (sqair_set_score_ids: the kernel takes the id as a 32-bit word, so the identity's int32 lane_id stands where obj_id stands)
-  if (h->score_ids && h->ident_on) a.obj_id = reinterpret_cast<const float*>(h->ident.lane_id);
-  a.T = T; a.B = B; a.N = h->cfg.n_steps_per_image;
-  return a;
-}
-// kernel-level check of the score (tests/test_score_kernel.py): k_lane_score on caller tensors, no state and no pass
-extern "C" int sqair_lane_score_test(SqairHandle* h, const float* box, const float* presence, const float* obj_id, const int32_t* map_count,
-                                     int T, int B, const SqairLaneScore* score, void* stream) {
-  if (!h) return -1;
-  const std::string who = "sqair_lane_score_test: ";
-  if (!box || !presence || !obj_id || !map_count || !score || T < 1 || B < 1 || T > 65535)
-    return sq_no(h, who + "null box / presence / obj_id / map_count / score or bad T / B");
-  if (sq_score_fields(h, who, *score) != 0) return -1;
-  LaneScoreArgs a; memset(&a, 0, sizeof(a));
-  a.box = box; a.presence = presence; a.obj_id = obj_id; a.map_count = map_count; a.sc = *score;
-  a.T = T; a.B = B; a.N = h->cfg.n_steps_per_image;
-  sq_launch_lane_score(a, (hipStream_t)stream);
-  SQ_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-// ------------------------------------------------------------------------------------------------
-// lane identities (include/sqair_hip.h: sqair_set_identity): registration, the arguments of k_lane_identity (launched by
-// sq_forward_impl after the estimate's and the layers' kernels, before the score's and the resampler) and the kernel-level entry point
-// ------------------------------------------------------------------------------------------------
-// what every user of an SqairLaneIdentity checks, -1 + "<who>..." when one is off
-static int sq_identity_fields(SqairHandle* h, const std::string& who, const SqairLaneIdentity& c) {
-  const int N = h->cfg.n_steps_per_image;
-  if (c.M < N || c.M > SQ_IDENT_MAXM)
-    return sq_no(h, who + "M = " + std::to_string(c.M) + " must lie in N = " + std::to_string(N) + ".." + std::to_string(SQ_IDENT_MAXM));
-  if (!(c.iou_min > 0.0f && c.iou_min <= 1.0f)) return sq_no(h, who + "iou_min must lie in (0, 1]");   // (NaN fails both)
-  if (!(c.reid_dist >= 0.0f)) return sq_no(h, who + "reid_dist must be >= 0");                          // (NaN fails)
-  if (!(c.reid_what > 0.0f)) return sq_no(h, who + "reid_what must lie in (0, +inf]");                  // (NaN fails)
-  if (c.max_age < 0) return sq_no(h, who + "max_age must be >= 0");
-  if (!c.trk_id || !c.trk_word || !c.trk_age || !c.trk_len || !c.trk_box || !c.next_id || !c.counts || !c.lane_id)
-    return sq_no(h, who + "trk_id, trk_word, trk_age, trk_len, trk_box, next_id, counts and lane_id must not be NULL");
-  return 0;
-}
-extern "C" int sqair_set_identity(SqairHandle* h, const SqairLaneIdentity* id, int T, int B) {
-  if (!h) return -1;
-  if (!id) {
-    sq_identity_off(h);
-    return 0;
-  }
-  const std::string who = "sqair_set_identity: ";
-  if (!h->state_on || !h->est_on)
-    return sq_no(h, who + "needs an estimate (sqair_set_estimate): the identity links the lane answer it writes");
-  if (!sq_estimate_identifiable(h->est, false))
-    return sq_no(h, who + "the estimate (sqair_set_estimate) must bind box, presence, obj_id and best_row: the identity reads them");
-  if (id->trk_what && !h->est.what)
-    return sq_no(h, who + "trk_what needs the estimate (sqair_set_estimate) to bind what: the appearance it remembers");
-  if (sq_estimate_t_mismatch(h, who, T) != 0) return -1;
-  if (sq_state_b_mismatch(h, who, B) != 0) return -1;
-  if (sq_identity_fields(h, who, *id) != 0) return -1;
-  h->ident_on = true; h->ident = *id;
-  return 0;
-}
-extern "C" int sqair_set_score_ids(SqairHandle* h, int lane_ids) {
-  if (!h) return -1;
-  if (lane_ids && !(h->state_on && h->est_on && h->score_on && h->ident_on))
-    return sq_no(h, "sqair_set_score_ids: needs both a score (sqair_set_score) and an identity (sqair_set_identity): the score reads "
-                    "the lane_id the identity writes");
-  h->score_ids = lane_ids != 0;
-  return 0;
-}
-LaneIdentArgs sq_identity_args(const SqairHandle* h, int T, int B) {
-  LaneIdentArgs a; memset(&a, 0, sizeof(a));
-  a.box = h->est.box; a.presence = h->est.presence; a.obj_id = h->est.obj_id; a.best_row = h->est.best_row;
-  a.what = h->ident.trk_what ? h->est.what : nullptr; a.id = h->ident;
-  a.T = T; a.B = B; a.N = h->cfg.n_steps_per_image; a.nw = h->cfg.n_what;
-  return a;
-}
-// kernel-level check of the identity (tests/test_identity_kernel.py): k_lane_identity on caller tensors, no state and no pass
-extern "C" int sqair_lane_identity_test(SqairHandle* h, const float* box, const float* presence, const float* obj_id, const float* what,
-                                        const int32_t* best_row, int T, int B, const SqairLaneIdentity* id, void* stream) {
-  if (!h) return -1;
-  const std::string who = "sqair_lane_identity_test: ";
-  if (!box || !presence || !obj_id || !best_row || !id || T < 1 || B < 1 || T > 65535)
-    return sq_no(h, who + "null box / presence / obj_id / best_row / id or bad T / B");
-  if (sq_identity_fields(h, who, *id) != 0) return -1;
-  if (id->trk_what && !what) return sq_no(h, who + "id->trk_what needs what");
-  LaneIdentArgs a; memset(&a, 0, sizeof(a));
-  a.box = box; a.presence = presence; a.obj_id = obj_id; a.best_row = best_row; a.what = id->trk_what ? what : nullptr; a.id = *id;
-  a.T = T; a.B = B; a.N = h->cfg.n_steps_per_image; a.nw = h->cfg.n_what;
-  sq_launch_lane_identity(a, (hipStream_t)stream);
-  SQ_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-// trajectory scoring (include/sqair_hip.h: sqair_lane_traj_score): a stand-alone call on the table a lane forecast or a lane trace
-// wrote -- or on a test's tensors --, nothing registered on the handle, which gives N and the error text
-extern "C" int sqair_lane_traj_score(SqairHandle* h, const SqairLaneTraj* table, const SqairTrajTruth* truth, const SqairTrajScore* score,
-                                     int F, int B, void* stream) {
-  if (!h) return -1;
-  const std::string who = "sqair_lane_traj_score: ";
-  if (!table || !truth || !score) return sq_no(h, who + "table, truth and score must not be NULL");
-  if (F < 1 || F > 65535 || B < 1) return sq_no(h, who + "F = " + std::to_string(F) + " must lie in 1..65535 and B = " + std::to_string(B) + " must be >= 1");
-  if (truth->G < 1 || truth->G > SQ_SCORE_MAXG)
-    return sq_no(h, who + "G = " + std::to_string(truth->G) + " must lie in 1.." + std::to_string(SQ_SCORE_MAXG));
-  if (!(score->iou_min > 0.0f && score->iou_min <= 1.0f)) return sq_no(h, who + "iou_min must lie in (0, 1]");   // (NaN fails both)
-  if (!table->best_row || !table->presence || !table->support || !table->box0 || !table->alive || !table->box_mean || !table->count_prob)
-    return sq_no(h, who + "the table's best_row, presence, support, box0, alive, box_mean and count_prob must not be NULL");
-  if (!truth->anchor_box || !truth->anchor_present || !truth->anchor_valid || !truth->truth_box || !truth->truth_present || !truth->truth_valid)
-    return sq_no(h, who + "anchor_box, anchor_present, anchor_valid, truth_box, truth_present and truth_valid must not be NULL");
-  if (!score->counts || !score->sums || !score->lane_counts) return sq_no(h, who + "counts, sums and lane_counts must not be NULL");
-  if (truth->keep_id && !table->obj_id) return sq_no(h, who + "keep_id needs the table's obj_id: the identities it is compared with");
-  LaneTrajScoreArgs a; memset(&a, 0, sizeof(a));
-  a.tab = *table; a.tr = *truth; a.sc = *score;
-  a.F = F; a.B = B; a.N = h->cfg.n_steps_per_image;
-  sq_launch_lane_traj_score(a, (hipStream_t)stream);
-  SQ_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
 // the refusals of a carried training call (host only: before any HIP call)
 int sq_carry_refusal(SqairHandle* h, const char* fn, int B, const SqairCarry* carry, const SqairOutputs* out) {
   const std::string f = std::string(fn) + ": ";
@@ -452,7 +160,11 @@ int sq_state_refusal(SqairHandle* h, bool train, int B, int t_offset) {
 }
 
 SqStateRes sq_carry_state(const SqairCarry* c) {
-  return SqStateRes{true, c->state_in, c->state_out, c->src_rows, true, c->smc != nullptr, c->smc ? *c->smc : SqairSmc{}};
+  SqStateRes st;
+  st.on = true; st.in = c->state_in; st.out = c->state_out; st.src = c->src_rows;
+  st.fresh = true;
+  if (c->smc) { st.smc_on = true; st.smc = *c->smc; }
+  return st;
 }
 // k_state_import's / k_state_export's arguments: the frame's records, states, last ids and row counters `t_row` (and, for the
 // import of a training pass, its fresh / imported flags, else NULL) against the blobs and source map of `st`
@@ -510,21 +222,21 @@ extern "C" int sqair_set_history(SqairHandle* h, void* ring, int64_t ring_bytes,
   if (ring_bytes < need)
     return sq_no(h, "sqair_set_history: ring_bytes " + std::to_string(ring_bytes) + " < sqair_history_bytes(h, " + std::to_string(L) +
                     ", 1, " + std::to_string(h->state_B) + ", fields) = " + std::to_string(need));
-  h->hist_on = true; h->hist_ring = ring; h->hist_bytes = ring_bytes; h->hist_L = L; h->hist_T = 0; h->hist_fields = fields;
+  h->hist.on = true; h->hist.ring = ring; h->hist.bytes = ring_bytes; h->hist.L = L; h->hist_T = 0; h->hist.fields = fields;
   return 0;
 }
 // the refusal of a pass with history on (host only: before any HIP call; sq_resolve_pass fixes the ring's T)
 static int sq_history_refusal(SqairHandle* h, int T, int B, const SqairOutputs* outp) {
-  if (!h->state_on || !h->hist_on) return 0;
+  if (!h->state_on || !h->hist.on) return 0;
   if (T < 1 || B != h->state_B) return 0;   // (the pass's own checks refuse these)
   if (h->hist_T != 0 && T != h->hist_T)
     return sq_no(h, "history (sqair_set_history): this ring's slots hold passes of T = " + std::to_string(h->hist_T) + " frames, a pass of T = " +
                     std::to_string(T) + " cannot be pushed into it");
-  const int64_t need = sqair_history_bytes(h, h->hist_L, T, B, h->hist_fields);
-  if (h->hist_bytes < need)
-    return sq_no(h, "history (sqair_set_history): ring_bytes " + std::to_string(h->hist_bytes) + " < sqair_history_bytes(h, " +
-                    std::to_string(h->hist_L) + ", " + std::to_string(T) + ", " + std::to_string(B) + ", fields) = " + std::to_string(need));
-  const uint32_t f = h->hist_fields;
+  const int64_t need = sqair_history_bytes(h, h->hist.L, T, B, h->hist.fields);
+  if (h->hist.bytes < need)
+    return sq_no(h, "history (sqair_set_history): ring_bytes " + std::to_string(h->hist.bytes) + " < sqair_history_bytes(h, " +
+                    std::to_string(h->hist.L) + ", " + std::to_string(T) + ", " + std::to_string(B) + ", fields) = " + std::to_string(need));
+  const uint32_t f = h->hist.fields;
   if (!outp || !outp->where || !outp->presence || !outp->obj_id || ((f & SQAIR_HIST_WHAT) && !outp->what) ||
       ((f & SQAIR_HIST_LOG_W) && !outp->log_weights_per_timestep))
     return sq_no(h, "history (sqair_set_history) records the pass's outputs: a pass with history on must bind where, presence, obj_id and "
@@ -535,21 +247,26 @@ int sq_resolve_pass(SqairHandle* h, bool train, int T, int B, int t_offset, cons
   if (sq_observed_refusal(h, train, T) != 0 || sq_state_refusal(h, train, B, t_offset) != 0 || sq_smc_refusal(h, out) != 0 ||
       sq_history_refusal(h, T, B, out) != 0 || sq_estimate_refusal(h, T, out) != 0)
     return -1;
-  const bool on = h->state_on, est = on && h->est_on;
-  *st = SqStateRes{on, h->state_in, h->state_out, h->state_src, false, h->smc_on, h->smc, on && h->hist_on,
-                   on ? h->observed : nullptr, est, est && h->lay_on, est && h->score_on, est && h->ident_on};
-  if (st->hist_on && T >= 1) h->hist_T = T;   // (T < 1 is the pass's own to refuse)
+  SqStateRes r;
+  r.on = h->state_on; r.in = h->state_in; r.out = h->state_out; r.src = h->state_src;
+  r.smc_on = h->smc_on; r.smc = h->smc;
+  if (r.on) {   // (what rides on the carried state: all off without one)
+    r.observed = h->observed; r.hist = h->hist; r.lane = h->lane;
+  }
+  *st = r;
+  if (r.hist.on && T >= 1) h->hist_T = T;   // (T < 1 is the pass's own to refuse)
   return 0;
 }
 SqStateRes sq_without_effects(SqStateRes st) {
   st.out = nullptr; st.smc_on = false; st.smc = SqairSmc{};
-  st.hist_on = st.est_on = st.lay_on = st.score_on = st.ident_on = false;
+  st.hist = SqHistRing{};
+  st.lane = SqLaneSet{};
   return st;
 }
 HistPushArgs sq_history_push_args(const SqairHandle* h, const SqStateRes& st, const SqairOutputs& out, const int* t_row, int T, int B) {
   HistPushArgs a; memset(&a, 0, sizeof(a));
-  a.ring = (unsigned*)h->hist_ring;
-  a.lay = sq_hist_layout(h, h->hist_L, T, B, h->hist_fields);
+  a.ring = (unsigned*)st.hist.ring;
+  a.lay = sq_hist_layout(h, st.hist.L, T, B, st.hist.fields);
   a.where = out.where; a.presence = out.presence; a.obj_id = out.obj_id; a.what = out.what; a.lw = out.log_weights_per_timestep;
   a.src = st.src; a.have_in = st.in != nullptr; a.t_row = t_row;
   return a;
@@ -557,25 +274,25 @@ HistPushArgs sq_history_push_args(const SqairHandle* h, const SqStateRes& st, co
 // the refusals of a trace and its argument block (host only): sqair_history_trace and sqair_history_trace_lane, one body
 static int sq_history_trace_args(SqairHandle* h, const std::string& who, void* ring, const int32_t* src_next, int lag,
                                  const SqairTraceOutputs* outp, HistTraceArgs& a) {
-  if (!h->state_on || !h->hist_on) return sq_no(h, who + "no history set (sqair_set_history)");
-  if (!ring || ring != h->hist_ring) return sq_no(h, who + "ring must be the ring given to sqair_set_history");
-  if (lag < 1 || lag > h->hist_L)
-    return sq_no(h, who + "lag = " + std::to_string(lag) + " must lie in [1, L = " + std::to_string(h->hist_L) + "]");
+  if (!h->state_on || !h->hist.on) return sq_no(h, who + "no history set (sqair_set_history)");
+  if (!ring || ring != h->hist.ring) return sq_no(h, who + "ring must be the ring given to sqair_set_history");
+  if (lag < 1 || lag > h->hist.L)
+    return sq_no(h, who + "lag = " + std::to_string(lag) + " must lie in [1, L = " + std::to_string(h->hist.L) + "]");
   if (!outp) return sq_no(h, who + "out must not be NULL");
   const SqairTraceOutputs& o = *outp;
   if (o.T < 1) return sq_no(h, who + "out->T (frames per pass) must be >= 1");
   if (h->hist_T != 0 && o.T != h->hist_T)
     return sq_no(h, who + "out->T = " + std::to_string(o.T) + " but the passes pushed have T = " + std::to_string(h->hist_T));
-  if (h->hist_bytes < sqair_history_bytes(h, h->hist_L, o.T, h->state_B, h->hist_fields))
+  if (h->hist.bytes < sqair_history_bytes(h, h->hist.L, o.T, h->state_B, h->hist.fields))
     return sq_no(h, who + "the ring is too small for passes of out->T = " + std::to_string(o.T) + " frames");
-  if ((o.what && !(h->hist_fields & SQAIR_HIST_WHAT)) || (o.log_w && !(h->hist_fields & SQAIR_HIST_LOG_W)))
+  if ((o.what && !(h->hist.fields & SQAIR_HIST_WHAT)) || (o.log_w && !(h->hist.fields & SQAIR_HIST_LOG_W)))
     return sq_no(h, who + "what / log_w asked of a ring that was set without the field");
   const bool table = o.track_id || o.n_tracks || o.track_present || o.track_where;
   if (table && (o.max_tracks < 1 || o.max_tracks > SQ_HIST_MAX_TRACKS))
     return sq_no(h, who + "max_tracks must lie in [1, " + std::to_string(SQ_HIST_MAX_TRACKS) + "] for the track table");
   memset(&a, 0, sizeof(a));
   a.ring = (unsigned*)ring;
-  a.lay = sq_hist_layout(h, h->hist_L, o.T, h->state_B, h->hist_fields);
+  a.lay = sq_hist_layout(h, h->hist.L, o.T, h->state_B, h->hist.fields);
   if ((int64_t)a.lay.R * lag > INT32_MAX || (int64_t)lag * o.T * a.lay.N * (table ? o.max_tracks : 1) > INT32_MAX)
     return sq_no(h, who + "lag * rows (or lag * T * N * max_tracks) beyond 2^31");
   a.src_next = src_next; a.lag = lag; a.M = table ? o.max_tracks : 1;
@@ -604,7 +321,7 @@ extern "C" int64_t sqair_trace_lane_scratch_bytes(const SqairHandle* h, int B, i
 static int sq_trace_lane_fields(SqairHandle* h, const std::string& who, const SqairTraceLane* l, int F, int B, int K, const void* scratch,
                                 int64_t scratch_bytes) {
   if (!l) return sq_no(h, who + "lane must not be NULL");
-  if (!(l->iou_min > 0.0f && l->iou_min <= 1.0f)) return sq_no(h, who + "lane->iou_min must lie in (0, 1]");   // (NaN fails both)
+  if (sq_unit_refusal(h, who, "lane->iou_min", l->iou_min) != 0) return -1;
   if (!l->best_row) return sq_no(h, who + "lane->best_row must not be NULL");
   if (K > SQ_MAX_K) return sq_no(h, who + "K = " + std::to_string(K) + " particles per lane, above " + std::to_string(SQ_MAX_K));
   if (F > 65535) return sq_no(h, who + "F = " + std::to_string(F) + " traced frames, above 65535");
@@ -739,7 +456,7 @@ extern "C" int64_t sqair_forecast_lane_scratch_bytes(const SqairHandle* h, int B
   return sq_forecast_lane_scratch_words(B, K, h->cfg.n_steps_per_image) * 4;
 }
 static int sq_forecast_lane_fields(SqairHandle* h, const std::string& who, const SqairForecastLane& l) {
-  if (!(l.iou_min > 0.0f && l.iou_min <= 1.0f)) return sq_no(h, who + "lane->iou_min must lie in (0, 1]");   // (NaN fails both)
+  if (sq_unit_refusal(h, who, "lane->iou_min", l.iou_min) != 0) return -1;
   if (!l.best_row) return sq_no(h, who + "lane->best_row must not be NULL");
   return 0;
 }
@@ -794,7 +511,8 @@ static int sq_forecast_impl(SqairHandle* h, const bool fan, const float* flat_pa
     sq_launch_forecast_fan_src(src, src_fan, B * K, S, s);
     src = src_fan;
   }
-  const SqStateRes st = {true, h->state_in, nullptr, src, false, false, SqairSmc{}};
+  SqStateRes st;   // (an import only: nothing exported, pushed or resampled)
+  st.on = true; st.in = h->state_in; st.src = src;
   sq_launch_state_import(sq_state_args(h, st, R, w.rec, w.temporal, w.prior[0], w.last_id, w.t_row, nullptr, 0), s);
   // per frame: the prior cell over all M slots (section A of the pass), then sampling + ids + compaction in one launch
   for (int f = 0; f < F; ++f) {

@@ -1,0 +1,402 @@
+"""The lane answers of a stream, host side: what ``SqairStream`` (sqair_amd/stream.py) says per lane instead of per particle row.
+``LaneAnswers`` is the resident stack a step fills -- the estimate and its followers, each one more kernel of the pass
+(include/sqair_hip.h states the semantics; sqair_amd/csrc/sqair_lane_api.hip registers and launches them as one block) --,
+``TrajScores`` the per-call trajectory scores of ``forecast`` and ``tracks``.  The stream owns one of each and keeps its public surface.
+
+``estimate=True``: a step also returns ``out["lane"]``, one answer per lane and frame from the K particles, formed before the
+resampler zeroes the weights (sqair_set_estimate): the normalised ``weights`` [T', B, K] and ``ess`` [T', B] of the step's own rows,
+``best_row``, the count posterior ``count_prob`` [T', B, N + 1] with ``expected_count`` and ``map_count``, the best row's objects
+(``presence``, ``obj_id``, ``where``, ``what``) with their ``box`` [T', B, N, 4] = (y, x, h, w) in pixels, and per object the
+``support`` -- the weight of the particles that hold a box of IoU >= ``estimate_iou`` with it -- and their weighted mean box
+``box_mean``; with ``estimate_canvas`` the posterior mean reconstruction ``mean_canvas`` [T', B, H, W].
+
+``estimate_layers=True``: ``out["lane"]`` also says which pixels each object of the lane occupies (sqair_set_layers): ``match``
+[T', B, K, N] -- the slot of particle k associated with object j, -1 where it does not agree -- and, over the particles that agree,
+the weighted mean of what the decoder drew for the object: its appearance ``layer`` and its coverage ``cover`` [T', B, N, H, W];
+``owner`` [T', B, H, W] is the object of largest coverage at a pixel, -1 (background) below ``layers_cover_min``.
+
+``score=True``: the lane answer is scored against ground-truth boxes inside the pass (sqair_set_score): a step takes
+``truth=dict(box=[T', B, G, 4], present=[T', B, G], valid=[T', B] or None)`` -- (y, x, h, w) in pixels as ``make_sequences``'s
+``coords``, G = ``score_truth`` slots per lane, an object keeping its slot for its life -- copied into stream-owned device buffers
+the way ``observed`` is; a step without ``truth`` scores nothing.  Present truths and present lane objects of IoU >= ``score_iou``
+are matched one to one (an object's last identity first, then greedily by IoU) and the CLEAR-MOT events counted on the device:
+``out["lane"]`` gains ``truth_match``, ``match_iou`` [T', B, G] and ``tp``, ``fn``, ``fp``, ``idsw`` [T', B] (-1 where nothing was
+scored), and ``score()`` reads the accumulators.  ``reset(lanes)`` also forgets those lanes' identities (a new clip has new ones)
+and keeps their counters.
+
+``identity=True``: every object of the lane answer carries a track id that stays on it for as long as the tracker can tell it is the
+same object (sqair_set_identity), formed after the layers and before the score.  ``obj_id`` is the best row's per-row counter and
+changes when the best row switches; ``lane_id`` does not: a table of ``identity_tracks`` (default min(16, 2 N)) tracks per lane is
+kept on the device, and each frame's objects are linked to it by position (IoU >= ``identity_iou``, the same obj_id first), then --
+``identity_reid_dist`` > 0 -- an object that was dropped for up to ``identity_max_age`` frames is re-identified when its centre lies
+within ``identity_reid_dist`` pixels per frame unseen and, with ``identity_appearance``, its ``what`` within ``identity_reid_what``
+of the track's (the nearest appearance wins), else it is born under a fresh id.  ``out["lane"]`` gains ``lane_id``, ``id_how``
+(0 born, 1 kept, 2 bridged -- the obj_id changed under it --, 3 re-identified) and ``track_len`` [T', B, N] int32, -1 where the slot
+is absent; ``identities()`` reads the counters and the table.  ``reset(lanes)`` frees those lanes' tracks; ids are never reused
+within a lane.  ``score_ids="lane"`` (with ``score=True``) makes the score count its identity switches on ``lane_id`` instead of
+``obj_id``.
+
+``forecast(..., lane=True, truth=...)`` and ``tracks(..., lane=True, truth=...)`` score the two answers that reach over time -- the
+lane forecast and the lane tracks -- against the truth's trajectories with one more launch after the call's own
+(sqair_lane_traj_score): truth and lane objects are linked once, at the last stepped frame, and every horizon or traced frame then
+gives displacement error, IoU, the Brier term of ``alive / support`` as a survival probability and the count's hit, accumulated on
+the device per (frame, lane); ``trajectory_score(kind)`` reads the sums and pools them into curves over the horizon without a lane
+table ever visiting the host."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from sqair_amd import _capi
+
+
+def lane_answer(name, of="lane"):
+    """A read-only attribute of a stream class that is attribute ``name`` of its ``of`` object (what the tests and tools look at)."""
+    return property(lambda self: getattr(getattr(self, of), name))
+
+
+# ---- shared checks and the read-back ---------------------------------------------------------------------------------------------
+def is_int_in(v, lo, hi=None):
+    """``v`` is an integer (no bool, no float) with lo <= v (<= hi)."""
+    return not isinstance(v, bool) and isinstance(v, (int, np.integer)) and lo <= v and (hi is None or v <= hi)
+
+
+def check_unit(who, name, v):
+    """Raises unless the threshold ``v`` lies in (0, 1] (NaN fails too)."""
+    if not 0.0 < v <= 1.0:
+        raise ValueError("{}{} must lie in (0, 1]".format(who, name))
+
+
+def as_mask(m):
+    """A truth mask as int32 (the kernels test != 0: int32 goes as it is)."""
+    return m if m.dtype == torch.int32 else (m != 0).to(torch.int32)
+
+
+def check_shapes(fn, items):
+    """Raises for the first of ``items`` = (name, tensor, shape) of a ``truth`` dict that has another shape."""
+    for name, t, shp in items:
+        if tuple(t.shape) != shp:
+            raise ValueError(fn + "truth[{!r}] of shape {} given, {} expected".format(name, tuple(t.shape), list(shp)))
+
+
+def read_back(core, tensors, zero=False):
+    """Host copies of the device tensors {name: tensor}, cloned on the core's stream (joined with the caller's on the way in and
+    out); ``zero``: they start again from zero afterwards."""
+    with torch.cuda.device(core.device):
+        core._join_in()
+        with core.on_stream():
+            got = {n: t.clone() for n, t in tensors.items()}
+            if zero:
+                for t in tensors.values():
+                    t.zero_()
+        core._join_out()
+        return {n: t.cpu() for n, t in got.items()}
+
+
+def _columns(table, names):
+    """The last axis of an accumulator table by name, copies."""
+    return {n: table[..., i].clone() for i, n in enumerate(names)}
+
+
+def _ratio(a, b):
+    return float(a) / b if b else float("nan")
+
+
+def field_views(shapes, int_fields, device):
+    """The fields {name: shape} as views of ONE float32 allocation, each 16-byte aligned (``int_fields``: viewed as int32), so that
+    they are copied out with one launch instead of one per field.  Returns (flat, views): views(flat or a clone of it) -> {name: view}."""
+    sizes = {n: int(np.prod(shp)) for n, shp in shapes.items()}
+    offs = dict(zip(sizes, np.cumsum([0] + [(s + 3) // 4 * 4 for s in sizes.values()]).tolist()))
+    flat = torch.zeros(offs[list(sizes)[-1]] + sizes[list(sizes)[-1]], dtype=torch.float32, device=device)
+    return flat, lambda flat: {n: (flat[offs[n]:offs[n] + sizes[n]].view(torch.int32) if n in int_fields
+                                   else flat[offs[n]:offs[n] + sizes[n]]).view(shapes[n]) for n in shapes}
+
+
+# ---- the resident stack: estimate, layers, identity, score -----------------------------------------------------------------------
+class LaneAnswers(object):
+    """The lane answers a stream's steps fill.  The constructor only checks its keyword group (no core, no device: it runs before the
+    stream touches either); ``register`` allocates the buffers and registers them on the core's handle.  ``flat`` / ``views``: ONE
+    allocation and its views by field, ``est`` (field_views) -- everything a step copies out as ``out["lane"]``; ``score_buf`` and
+    ``ident_buf``: the score's truth, accumulators and identity memory, the identity's track table and counters."""
+
+    def __init__(self, who, estimate, estimate_iou, estimate_canvas, estimate_layers, layers_cover_min, score, score_iou, score_truth,
+                 identity, identity_iou, identity_tracks, identity_max_age, identity_reid_dist, identity_reid_what, identity_appearance,
+                 score_ids):
+        self.step_fn, who = who + ".step: ", who + ": "
+
+        def bad(why):
+            raise ValueError(who + why)
+        self.estimate_iou = float(estimate_iou)
+        if estimate:
+            check_unit(who, "estimate_iou", self.estimate_iou)
+        if estimate_canvas and not estimate:
+            bad("estimate_canvas is for a stream with estimate=True")
+        if estimate_layers and not estimate:
+            bad("estimate_layers is for a stream with estimate=True")
+        self.cover_min = float(layers_cover_min)
+        if estimate_layers:
+            check_unit(who, "layers_cover_min", self.cover_min)
+        if score and not estimate:
+            bad("score is for a stream with estimate=True")
+        self.score_iou = float(score_iou)
+        if score:
+            check_unit(who, "score_iou", self.score_iou)
+        if score and score_truth is not None and not is_int_in(score_truth, 1, _capi.SCORE_MAX_TRUTH):
+            bad("score_truth must be an integer in [1, {}]".format(_capi.SCORE_MAX_TRUTH))
+        if identity and not estimate:
+            bad("identity is for a stream with estimate=True")
+        self.identity_iou, self.reid_dist, self.reid_what = float(identity_iou), float(identity_reid_dist), float(identity_reid_what)
+        if identity:
+            check_unit(who, "identity_iou", self.identity_iou)
+        self._tracks_text = "identity_tracks must be an integer in [n_steps_per_image, {}]".format(_capi.IDENT_MAX_TRACKS)
+        if identity and identity_tracks is not None and not is_int_in(identity_tracks, 1, _capi.IDENT_MAX_TRACKS):
+            bad(self._tracks_text)
+        if identity and not is_int_in(identity_max_age, 0):
+            bad("identity_max_age must be an integer >= 0")
+        if identity and not self.reid_dist >= 0.0:   # (NaN fails too)
+            bad("identity_reid_dist must be >= 0")
+        if identity and not self.reid_what > 0.0:   # (NaN fails too)
+            bad("identity_reid_what must lie in (0, +inf]")
+        if score_ids not in ("row", "lane"):
+            bad("score_ids must be 'row' or 'lane'")
+        if score_ids == "lane" and not (score and identity):
+            bad("score_ids='lane' is for a stream with score=True and identity=True")
+        self.who = who
+        self.estimate, self.canvas, self.layers = bool(estimate), bool(estimate_canvas), bool(estimate_layers)
+        self.scored, self.identified, self.appearance = bool(score), bool(identity), bool(identity_appearance)
+        self._truth_slots, self._tracks, self.max_age, self.score_ids = score_truth, identity_tracks, identity_max_age, score_ids
+        self.G = self.M = 0   # truth slots, track entries per lane (size)
+
+    def size(self, core):
+        """``G`` and ``M`` for the core's N slots: the last check, and the only one that needs the core (its handle is not touched)."""
+        if self.scored:
+            self.G = core.N if self._truth_slots is None else int(self._truth_slots)
+        if self.identified:
+            self.M = min(_capi.IDENT_MAX_TRACKS, 2 * core.N) if self._tracks is None else int(self._tracks)
+            if not core.N <= self.M:
+                raise ValueError(self.who + self._tracks_text)
+
+    def register(self, core, log_w, T, B):
+        """Allocates the buffers and registers them on the handle: the estimate (``log_w``: the carried log weights -- after SMC, so
+        that they are the resampler's accumulator), then layers, score, identity, score_ids."""
+        self.core, self.T, self.B = core, T, B
+        if not self.estimate:
+            return
+        lib, h, G, K, N = core.lib, core.handle, self.G, core.K, core.N
+        shapes = _capi.estimate_shapes(T, B, K, N, core.nw, (core.H, core.W) if self.canvas else None)
+        ints = _capi.ESTIMATE_INT_FIELDS
+        if self.layers:
+            shapes.update(_capi.layers_shapes(T, B, K, N, (core.H, core.W)))
+            ints = ints + _capi.LAYERS_INT_FIELDS
+        if self.scored:
+            shapes.update(_capi.score_shapes(T, B, G))
+            ints = ints + _capi.SCORE_INT_FIELDS
+        if self.identified:
+            shapes.update(_capi.identity_shapes(T, B, N))
+            ints = ints + tuple(_capi.IDENT_LANE_NAMES[n] for n in _capi.IDENT_FIELDS)
+        self.flat, self.views = field_views(shapes, ints, core.device)
+        est = self.est = self.views(self.flat)
+        z = lambda shp, dt: torch.zeros(shp, dtype=dt, device=core.device)
+        sync = torch.cuda.current_stream(core.device).synchronize   # (a buffer's initial values are in place before a pass reads it)
+        c_est = _capi.SqairLaneEstimate(iou_min=self.estimate_iou, log_w=log_w.data_ptr(),
+                                        **{n: t.data_ptr() for n, t in est.items() if n in _capi.ESTIMATE_FIELDS})
+        sync()
+        core.check(lib.sqair_set_estimate(h, C.byref(c_est), T, B), "sqair_set_estimate")
+        if self.layers:
+            lay = _capi.SqairLaneLayers(cover_min=self.cover_min, **{n: est[n].data_ptr() for n in _capi.LAYERS_FIELDS})
+            core.check(lib.sqair_set_layers(h, C.byref(lay), T, B), "sqair_set_layers")
+        if self.scored:   # the truth of a step, the accumulators and the identity memory
+            self.score_buf = dict(truth_box=z((T, B, G, 4), torch.float32), truth_present=z((T, B, G), torch.int32),
+                                  truth_valid=z((T, B), torch.int32), counts=z((B, len(_capi.SCORE_COUNTS)), torch.int64),
+                                  iou_sum=z((B,), torch.float64), last_id=z((B, G), torch.int32) - 1)
+            self._valid_is_zero = True
+            sc = _capi.SqairLaneScore(iou_min=self.score_iou, G=G, **{n: t.data_ptr() for n, t in self.score_buf.items()},
+                                      **{n: est[n].data_ptr() for n in _capi.SCORE_FIELDS})
+            sync()
+            core.check(lib.sqair_set_score(h, C.byref(sc), T, B), "sqair_set_score")
+        if self.identified:   # the track table of every lane and the counters
+            shapes = _capi.identity_memory_shapes(B, self.M, core.nw)
+            if not self.appearance:
+                del shapes["trk_what"]
+            dtype = lambda n: torch.float32 if n in ("trk_box", "trk_what") else torch.int64 if n == "counts" else torch.int32
+            self.ident_buf = {n: z(shp, dtype(n)) for n, shp in shapes.items()}
+            self.ident_buf["trk_id"].fill_(-1)
+            idt = _capi.SqairLaneIdentity(iou_min=self.identity_iou, reid_dist=self.reid_dist, reid_what=self.reid_what, M=self.M,
+                                          max_age=int(self.max_age), **{n: t.data_ptr() for n, t in self.ident_buf.items()},
+                                          **{n: est[_capi.IDENT_LANE_NAMES[n]].data_ptr() for n in _capi.IDENT_FIELDS})
+            sync()
+            core.check(lib.sqair_set_identity(h, C.byref(idt), T, B), "sqair_set_identity")
+            if self.score_ids == "lane":
+                core.check(lib.sqair_set_score_ids(h, 1), "sqair_set_score_ids")
+
+    # ---- per step ------------------------------------------------------------------------------------------------------------
+    def check_truth(self, truth):
+        """``truth`` of a step as (box float32 [T', B, G, 4], present int32 [T', B, G], valid int32 [T', B]) (None: no truth)."""
+        if truth is None:
+            return None
+        fn = self.step_fn
+        if not self.scored:
+            raise ValueError(fn + "truth is for a stream with score=True")
+        if not isinstance(truth, dict) or "box" not in truth or "present" not in truth or set(truth) - {"box", "present", "valid"}:
+            raise ValueError(fn + "truth must be a dict with box, present and optionally valid")
+        T, B, G = self.T, self.B, self.G
+        box = torch.as_tensor(truth["box"]).to(torch.float32)
+        present = torch.as_tensor(truth["present"])
+        valid = truth.get("valid")
+        valid = torch.ones((T, B), dtype=torch.int32) if valid is None else torch.as_tensor(valid)
+        if T == 1 and box.dim() == 3:
+            box, present, valid = box[None], present[None], (valid[None] if valid.dim() == 1 else valid)
+        check_shapes(fn, (("box", box, (T, B, G, 4)), ("present", present, (T, B, G)), ("valid", valid, (T, B))))
+        return box, as_mask(present), as_mask(valid)
+
+    def feed_truth(self, truth):
+        """A step's checked truth into the score's own buffers, on the current stream (as the mask of a stream with missing frames:
+        the kernel reads the stream's buffers, so one graph serves every step); without one ``truth_valid`` is zeroed once."""
+        if not self.scored:
+            return
+        if truth is not None:
+            for n, t in zip(("truth_box", "truth_present", "truth_valid"), truth):
+                self.score_buf[n].copy_(t, non_blocking=True)
+        elif not self._valid_is_zero:
+            self.score_buf["truth_valid"].zero_()
+        self._valid_is_zero = truth is None
+
+    def copy_out(self):
+        """``out["lane"]`` of the step just run: views of one clone."""
+        return self.views(self.flat.clone())
+
+    def reset(self, lanes, on_core_stream):
+        """The follow-ups of a stream's ``reset(lanes)`` (``lanes`` checked and distinct; ``on_core_stream``: the carried state's context):
+        the score forgets those lanes' identities (``last_id``) and keeps their counters; the identity frees their track entries
+        (``trk_id`` = -1) and keeps their ``next_id``."""
+        if lanes and (self.scored or self.identified):
+            with on_core_stream():
+                for j in lanes:
+                    if self.scored:
+                        self.score_buf["last_id"][j].fill_(-1)
+                    if self.identified:
+                        self.ident_buf["trk_id"][j].fill_(-1)
+
+    # ---- read-outs -----------------------------------------------------------------------------------------------------------
+    def score(self, reset=False):
+        if not self.scored:
+            raise ValueError("SqairStream.score: the stream keeps no score (SqairStream(..., estimate=True, score=True))")
+        got = read_back(self.core, {n: self.score_buf[n] for n in ("counts", "iou_sum")}, zero=reset)
+        res = _columns(got["counts"], _capi.SCORE_COUNTS)
+        tot = {n: int(v.sum()) for n, v in res.items()}
+        res["iou_sum"] = got["iou_sum"]
+        res["mota"] = 1.0 - _ratio(tot["fn"] + tot["fp"] + tot["idsw"], tot["truth"])
+        res["motp"] = _ratio(float(got["iou_sum"].sum()), tot["tp"])
+        res["count_accuracy"] = _ratio(tot["count_hit"], tot["frames"])
+        return res
+
+    def identities(self):
+        if not self.identified:
+            raise ValueError("SqairStream.identities: the stream keeps no identities (SqairStream(..., estimate=True, identity=True))")
+        got = read_back(self.core, {n: self.ident_buf[n] for n in ("counts", "next_id", "trk_id", "trk_age", "trk_len", "trk_box")})
+        res = _columns(got.pop("counts"), _capi.IDENT_COUNTS)
+        tot = {n: int(v.sum()) for n, v in res.items()}
+        res.update(got)
+        res["bridged_rate"] = _ratio(tot["bridged"], tot["objects"])
+        res["reidentified_rate"] = _ratio(tot["reidentified"], tot["objects"])
+        return res
+
+
+# ---- the per-call trajectory scores of forecast() and tracks() -------------------------------------------------------------------
+class TrajScores(object):
+    """``acc``: by kind ("forecast", "tracks") the accumulators and per-call outputs of the LAST (F, G, truth_iou) scored.  ``lane``:
+    the stream's LaneAnswers (``link_ids`` keeps a truth with the identity its score last matched it with)."""
+
+    def __init__(self, core, B, lane):
+        self.core, self.B, self.lane, self.acc = core, B, lane, {}
+
+    def check_truth(self, fn, truth, lane, F, default_anchor, link_ids, truth_iou):
+        """``truth`` of ``forecast`` / ``tracks`` as {name: tensor} in the C ABI's names and dtypes plus ``G`` and ``iou_min`` (None: no
+        truth); everything is checked here, before the core is touched."""
+        if truth is None:
+            if link_ids:
+                raise ValueError(fn + "link_ids is for a call with truth")
+            return None
+        if not lane:
+            raise ValueError(fn + "truth is for a call with lane=True: the lane table is what is scored")
+        names = {"box", "present", "valid", "anchor_box", "anchor_present", "anchor_valid"}
+        if not isinstance(truth, dict) or "box" not in truth or "present" not in truth or set(truth) - names:
+            raise ValueError(fn + "truth must be a dict with box, present and optionally valid, anchor_box, anchor_present, anchor_valid")
+        truth_iou = float(truth_iou)
+        check_unit(fn, "truth_iou", truth_iou)
+        B = self.B
+        box = torch.as_tensor(truth["box"]).to(torch.float32)
+        present = torch.as_tensor(truth["present"])
+        if box.dim() != 4 or not 1 <= box.shape[2] <= _capi.SCORE_MAX_TRUTH:
+            raise ValueError(fn + "truth['box'] of shape {} given, [{}, {}, G, 4] with G in [1, {}] expected".format(
+                tuple(box.shape), F, B, _capi.SCORE_MAX_TRUTH))
+        G = int(box.shape[2])
+        given = truth.get("valid") is not None
+        valid = torch.as_tensor(truth["valid"]) if given else torch.ones((F, B), dtype=torch.int32)
+        check_shapes(fn, (("box", box, (F, B, G, 4)), ("present", present, (F, B, G)), ("valid", valid, (F, B))))
+        if (truth.get("anchor_box") is None) != (truth.get("anchor_present") is None):
+            raise ValueError(fn + "truth['anchor_box'] and truth['anchor_present'] come together")
+        a_valid = truth.get("anchor_valid")
+        if truth.get("anchor_box") is None:
+            if not default_anchor:
+                raise ValueError(fn + "a forecast's truth needs anchor_box and anchor_present: the truth at the last stepped frame, "
+                                      "which is none of the forecast's frames")
+            a_box, a_present = box[-1], present[-1]   # (a trace's newest frame is the last stepped one)
+            if a_valid is None and given:
+                a_valid = valid[-1]
+        else:
+            a_box, a_present = torch.as_tensor(truth["anchor_box"]).to(torch.float32), torch.as_tensor(truth["anchor_present"])
+        a_valid = torch.ones((B,), dtype=torch.int32) if a_valid is None else torch.as_tensor(a_valid)
+        check_shapes(fn, (("anchor_box", a_box, (B, G, 4)), ("anchor_present", a_present, (B, G)), ("anchor_valid", a_valid, (B,))))
+        if link_ids and not (self.lane.scored and G == self.lane.G):
+            raise ValueError(fn + "link_ids is for a stream with score=True and the same G: it keeps a truth with the identity the "
+                                  "stream's score last matched it with")
+        return dict(G=G, iou_min=truth_iou, truth_box=box, truth_present=as_mask(present), truth_valid=as_mask(valid), anchor_box=a_box,
+                    anchor_present=as_mask(a_present), anchor_valid=as_mask(a_valid))
+
+    def launch(self, kind, table, F, truth, link_ids):
+        """Scores the lane table a forecast or a trace has just written (``table``: its device buffers by field) against ``truth``
+        (of check_truth) with one launch on the core's stream (include/sqair_hip.h: sqair_lane_traj_score); returns the per-call
+        outputs, copies.  The accumulators of ``kind`` are kept for the last (F, G, truth_iou) scored."""
+        core, B = self.core, self.B
+        G, key = truth["G"], (F, truth["G"], truth["iou_min"])
+        ts = self.acc.get(kind)
+        if ts is None or ts["key"] != key:   # (another F, G or threshold: the old sums would not mean the same)
+            z = lambda shp, dt: torch.zeros(shp, dtype=dt, device=core.device)
+            ts = self.acc[kind] = dict(key=key, counts=z((F, B, len(_capi.TRAJ_COUNTS)), torch.int64),
+                                       sums=z((F, B, len(_capi.TRAJ_SUMS)), torch.float64),
+                                       lane_counts=z((B, len(_capi.TRAJ_LANE_COUNTS)), torch.int64))
+            ts["flat"], ts["views"] = field_views(_capi.traj_shapes(F, B, G), _capi.TRAJ_INT_FIELDS, core.device)
+            ts["out"] = ts["views"](ts["flat"])
+        dev = {n: truth[n].to(core.device, non_blocking=True).contiguous() for n in _capi.TRAJ_TRUTH_FIELDS if n != "keep_id"}
+        c_tab = _capi.SqairLaneTraj(**{n: table[n].data_ptr() for n in _capi.TRAJ_TABLE_FIELDS if n in table})
+        c_truth = _capi.SqairTrajTruth(G=G, keep_id=self.lane.score_buf["last_id"].data_ptr() if link_ids else None,
+                                       **{n: t.data_ptr() for n, t in dev.items()})
+        c_score = _capi.SqairTrajScore(iou_min=truth["iou_min"], **{n: ts[n].data_ptr() for n in _capi.TRAJ_ACCUMULATORS},
+                                       **{n: t.data_ptr() for n, t in ts["out"].items()})
+        core.check(core.lib.sqair_lane_traj_score(core.handle, C.byref(c_tab), C.byref(c_truth), C.byref(c_score), F, B,
+                                                  core._stream()), "sqair_lane_traj_score")
+        return ts["views"](ts["flat"].clone())
+
+    def read(self, kind, reset=False):
+        if kind not in ("forecast", "tracks"):
+            raise ValueError("SqairStream.trajectory_score: kind must be 'forecast' or 'tracks'")
+        ts = self.acc.get(kind)
+        if ts is None:
+            raise ValueError("SqairStream.trajectory_score: no {} call has been scored yet ({}(..., lane=True, truth=...))".format(kind, kind))
+        acc = read_back(self.core, {n: ts[n] for n in _capi.TRAJ_ACCUMULATORS}, zero=reset)
+        res = _columns(acc["counts"], _capi.TRAJ_COUNTS)
+        res.update(_columns(acc["sums"], _capi.TRAJ_SUMS))
+        res.update(_columns(acc["lane_counts"], _capi.TRAJ_LANE_COUNTS))
+        tot = {n: res[n].sum(1).to(torch.float64) for n in _capi.TRAJ_COUNTS + _capi.TRAJ_SUMS}
+        div = lambda a, b: torch.where(b > 0, a / torch.where(b > 0, b, torch.ones_like(b)), torch.full_like(b, float("nan")))
+        res["ade"] = div(tot["centre_err_sum"], tot["pairs"])
+        res["fde"] = float(res["ade"][-1])
+        res["mean_iou"] = div(tot["iou_sum"], tot["pairs"])
+        res["hit_rate"] = div(tot["hits"], tot["pairs"] + tot["lost"])
+        res["brier"] = div(tot["brier_sum"], tot["pairs"] + tot["lost"] + tot["gone"])
+        res["count_accuracy"] = div(tot["count_hit"], tot["frames"])
+        res["link_rate"] = _ratio(int(res["linked"].sum()), int(res["anchor_truth"].sum()))
+        return res

@@ -12,6 +12,7 @@ import torch
 
 from sqair_amd import _capi
 from sqair_amd.flags import make_flags
+from sqair_amd.lane import TrajScores
 from sqair_amd.model import make_config
 from sqair_amd.stream import SqairStream
 
@@ -165,10 +166,11 @@ def test_refusals_before_any_hip_call(path):
 def _stream(scored=False, G=0, B=3, K=2, T=1):
     """A stream's argument checks without a device: the attributes they read, and a core and a carried state that fail when touched."""
     st = SqairStream.__new__(SqairStream)
-    st.B, st.K, st.T, st.R, st.scored, st.G = B, K, T, B * K, scored, G
+    st.B, st.K, st.T, st.R = B, K, T, B * K
     st.core = types.SimpleNamespace(N=3)
     st.carried = types.SimpleNamespace(ring=object(), history=8)
-    st._traj = {}
+    st.lane = types.SimpleNamespace(scored=scored, G=G)
+    st.traj = TrajScores(st.core, B, st.lane)
     return st
 
 
