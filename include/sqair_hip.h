@@ -687,8 +687,9 @@ int sqair_lane_layers_test(SqairHandle* h, const float* glimpse, const float* wh
  * truth_box, truth_present, truth_valid, counts, iou_sum or last_id (the per-frame outputs are optional); at pass time: a pass
  * of another T.  sqair_set_estimate switching the estimate off, to another T or to one without the four fields, and
  * sqair_set_state switching the state off or to another B, switch the score off.
- * Out of scope: optimal (Hungarian) assignment -- step 3 is greedy; IDF1 and mostly-tracked / mostly-lost statistics; scoring per
- * particle row; scoring of forecasts or lane tracks; training passes. */
+ * Out of scope: optimal (Hungarian) assignment per frame -- step 3 is greedy (IDF1 and the mostly-tracked / mostly-lost statistics,
+ * with the optimal assignment over a clip they need, are sqair_set_idf's, below); scoring per particle row;
+ * scoring of forecasts or lane tracks; training passes. */
 #define SQAIR_SCORE_MAX_TRUTH 16
 #define SQAIR_SCORE_COUNTS 9
 typedef struct SqairLaneScore {
@@ -889,6 +890,92 @@ int sqair_set_identity(SqairHandle* h, const SqairLaneIdentity* id /* NULL: off 
 int sqair_lane_identity_test(SqairHandle* h, const float* box, const float* presence, const float* obj_id, const float* what /* or NULL */,
                              const int32_t* best_row, int T, int B, const SqairLaneIdentity* id, void* stream);
 int sqair_set_score_ids(SqairHandle* h, int lane_ids /* 0: the estimate's obj_id (default); 1: the identity's lane_id */);
+
+/* ---- IDF1 scoring: does an identity stay on an object over its life -- global identity assignment, solved on the device ---------
+ * The score's idsw counts the moments an identity changes on a greedy per-frame match; it cannot say for how long the wrong id then
+ * stays, and gives no credit for an object re-identified under its old id.  The identity measures of Ristani et al. (IDF1, IDP, IDR)
+ * and the trajectory statistics (mostly tracked / partly tracked / mostly lost, fragmentations) can: they need, per lane, how many
+ * frames every truth identity overlapped every predicted identity, and a maximum-weight one-to-one assignment over that table.  With
+ * an IDF set, every following inference pass with a carried state, an estimate and a score runs one more kernel, k_lane_idf, one
+ * workgroup per lane looping over the pass's frames in order: after k_lane_score and BEFORE the SMC resampler.  A pass with the IDF on
+ * has exactly one kernel node more; with it off nothing is launched and every other output, blob and accumulator is unchanged bit for
+ * bit.  Training passes, and a capture's eager pre-pass without effects, never run it.  sqair_lane_idf_solve, a stand-alone capturable
+ * call (one launch of k_lane_idf_solve, one wavefront per lane), solves the assignment when the caller reads the score or a clip ends.
+ * Everything after the IoU threshold is integer arithmetic: graph replay, eager calls and split passes agree exactly.
+ * 1. Units.  A CLIP of lane b runs from the start, or from the last close of lane b, to the next close.  Truth identity IS the slot g,
+ *    as in the score.  Predicted identity is the 32-bit id WORD k_lane_score is handed for the same pass: the obj_id word, or lane_id
+ *    when sqair_set_score_ids(h, 1) is in force.  The inputs are the score's own truth_box, truth_present, truth_valid, iou_min and G,
+ *    and the score's per-frame output truth_match, which must be bound.
+ * 2. Table, per lane, persistent on the device, updated in place by the lane's one workgroup, no atomics; P in 1..64 columns:
+ *    col_id [B,P] the id word of a column, -1 = free (the other words of a free column are whatever they last held and are never
+ *    read); overlap [B,G,P] frames in which truth g and column p overlapped; row_frames [B,G] frames truth g was present; col_frames
+ *    [B,P] frames the column's id was present; extra_frames [B] object-frames without a column; matched [B,G] frames the score matched
+ *    truth g; frag [B,G] fragmentations of truth g; trk_state [B,G] bit 0 = tracked at g's last present frame, bit 1 = ever tracked;
+ *    frames [B] frames accumulated in the open clip.  All int32.  The caller starts with col_id = -1 and everything else 0.
+ * 3. Per scored (frame, lane) -- truth_valid[t,b] != 0 and the estimate's lane finite (map_count != -1); every other frame touches
+ *    nothing, exactly as in the score -- frames[b] += 1 and:
+ *    a. Columns.  For the present lane objects j (presence != 0) in index order: the column whose col_id equals j's id word is j's; a
+ *       non-negative word that is in no column takes the first free column (its col_frames and overlap start at 0).  An object is
+ *       UNKEYED -- extra_frames += 1 -- when its word is negative, when no column is free, or when an earlier j of the same frame
+ *       holds the same word (ids are distinct within a frame, so each cell has one writer: the later j counts as unkeyed).  A frame
+ *       with at least one unkeyed object adds 1 to totals.overflow_ids, at once.
+ *    b. col_frames[col(j)] += 1 for every keyed j.
+ *    c. row_frames[g] += 1 for every present truth g (truth_present != 0).
+ *    d. overlap[g, col(j)] += 1 for EVERY pair (present g, keyed j) with sq_box_iou(truth_box[t,b,g], box[t,b,j]) >= iou_min -- the
+ *       score's device function on the same fp32 words; all pairs, not only the score's matches: that is the IDF1 definition.
+ *    e. matched[g] += [truth_match[t,b,g] >= 0] for every present g.
+ *    f. For every present g: if g is matched now, was ever tracked (bit 1) and was not tracked at its previous present frame (bit 0),
+ *       frag[g] += 1; then bit 0 = matched now, bit 1 |= matched now.
+ * 4. Solve, per lane.  IDTP = the maximum over one-to-one assignments of truth rows to columns of the sum of overlap[g, p];
+ *    unassigned rows and columns are allowed (the dummy-node formulation of the paper), free columns count nothing.  IDFN = sum_g
+ *    row_frames - IDTP, IDFP = sum_p col_frames (used columns) + extra_frames - IDTP.  A truth with row_frames > 0 is a trajectory;
+ *    with m = matched and n = row_frames it is mostly tracked (MT) if 5 m >= 4 n, mostly lost (ML) if 5 m < n, partly tracked (PT)
+ *    otherwise.  The clip's twelve figures, in the order of totals: clips (1 for a clip with frames > 0), frames, trajectories, idtp,
+ *    idfn, idfp, mt, pt, ml, frag (sum_g frag), ids (columns used), overflow_ids (always 0 here: 3a has counted it in totals).
+ *    assign[b,g] = the id word of the column assigned to truth g when their overlap is positive, else -1; optimal assignments tie,
+ *    the figures do not.  The assignment is sq_assign_optimal_i32 (csrc/sqair_lane.h): shortest augmenting paths with integer
+ *    potentials, rows inserted in index order, exact for weights below 2^30, which the frames of a clip never reach.
+ * 5. Totals and close.  totals [B,12] int64, in/out, the caller zeroes them.  Without `close` the solve writes the open clip's figures
+ *    to open [B,12] int64 and assign [B,G] (each optional) and changes nothing else.  For a lane with close[b] != 0 it also adds the
+ *    figures to totals[b] and frees the table: col_id = -1 for every column, row_frames, matched, frag, trk_state, extra_frames and
+ *    frames = 0; overlap and col_frames of a freed column stay as they are and are never read.
+ * Pointers are remembered by the handle and frozen into captured graphs.  NULL idf: off.  sqair_set_idf is refused (return -1, text
+ * in sqair_last_error, before any HIP call) with no score set (sqair_set_score); with a score that binds no truth_match; for a T other
+ * than the estimate's or a B other than the state's; for P outside 1..64; for a NULL col_id, overlap, row_frames, col_frames,
+ * extra_frames, matched, frag, trk_state, frames or totals.  The IDF goes off with the score: everything that switches the score off
+ * switches it off, and so does sqair_set_score registering a score without truth_match or with another G.
+ * Out of scope: optimal per-frame matching inside k_lane_score or k_lane_identity (the device function is shaped for it); truth
+ * identities other than the slot; HOTA; IDF1 per particle row, or for forecasts and lane tracks; identities across lanes; training
+ * passes; more than 64 predicted ids per clip -- reported through overflow_ids, not solved. */
+#define SQAIR_IDF_MAX_IDS 64
+#define SQAIR_IDF_TOTALS 12
+typedef struct SqairLaneIdf {
+  int32_t P;                      /* id columns per lane, 1..64 */
+  /* the table, in/out, persists across passes; the caller starts with col_id = -1, everything else 0 */
+  int32_t* col_id;                /* [B,P]   the id word of the column, -1 = free */
+  int32_t* overlap;               /* [B,G,P] */
+  int32_t* row_frames;            /* [B,G] */
+  int32_t* col_frames;            /* [B,P] */
+  int32_t* extra_frames;          /* [B] */
+  int32_t* matched;               /* [B,G] */
+  int32_t* frag;                  /* [B,G] */
+  int32_t* trk_state;             /* [B,G] */
+  int32_t* frames;                /* [B] */
+  int64_t* totals;                /* [B,12] in/out: clips, frames, trajectories, idtp, idfn, idfp, mt, pt, ml, frag, ids, overflow_ids */
+} SqairLaneIdf;
+int sqair_set_idf(SqairHandle* h, const SqairLaneIdf* idf /* NULL: off */, int T, int B);
+/* Kernel-level check of the accumulation (tests): k_lane_idf on caller buffers, no state and no pass, with the handle's N and any G
+ * in 1..16.  box [T,B,N,4], presence, ids [T,B,N] (32-bit words) and map_count [T,B] stand for the estimate's outputs, score for the
+ * registered score: its truth_box, truth_present, truth_valid, iou_min, G and truth_match [T,B,G] are read, nothing of it is written.
+ * Refused (return -1, before any HIP call): a NULL box / presence / ids / map_count / score / idf, T or B out of range, G or iou_min
+ * out of range, a NULL truth_box, truth_present, truth_valid or truth_match, what sqair_set_idf refuses for idf. */
+int sqair_lane_idf_test(SqairHandle* h, const float* box, const float* presence, const float* ids, const int32_t* map_count, int T, int B,
+                        const SqairLaneScore* score, const SqairLaneIdf* idf, void* stream);
+/* The solve (points 4 and 5): stand-alone and capturable -- nothing is registered on the handle and no pass runs it.  It takes the
+ * caller's tensors, so the tests call the kernel through it as it stands.  The handle gives the error text only.  Refused (return -1, before any HIP call): a
+ * NULL idf, G outside 1..16, B < 1, what sqair_set_idf refuses for idf. */
+int sqair_lane_idf_solve(SqairHandle* h, const SqairLaneIdf* idf, int G, int B, const int32_t* close /* device [B] or NULL */,
+                         int64_t* open /* [B,12] or NULL */, int32_t* assign /* [B,G] or NULL */, void* stream);
 
 /* ---- objective ---------------------------------------------------------------------------------
  * Fused IWAE / VIMCO reductions over [T,B,K] (reference: Model._build sqair/model.py:88-103,

@@ -144,6 +144,25 @@ class SqairLaneScore(C.Structure):
     _fields_ = [("iou_min", C.c_float), ("G", C.c_int32)] + [(n, C.c_void_p) for n in SCORE_INPUTS + SCORE_FIELDS]
 
 
+# IDF1 scoring (include/sqair_hip.h: sqair_set_idf): the table's fields of SqairLaneIdf in declaration order (all int32) with their
+# shapes, then ``totals`` (int64) and its columns -- the twelve figures of a clip
+IDF_TABLE = ("col_id", "overlap", "row_frames", "col_frames", "extra_frames", "matched", "frag", "trk_state", "frames")
+IDF_TOTALS = ("clips", "frames", "trajectories", "idtp", "idfn", "idfp", "mt", "pt", "ml", "frag", "ids", "overflow_ids")
+IDF_MAX_IDS = 64
+
+
+def idf_shapes(B, G, P):
+    """The table's shapes for G truth slots and P id columns per lane (int32), and ``totals`` (int64)."""
+    return dict(col_id=(B, P), overlap=(B, G, P), row_frames=(B, G), col_frames=(B, P), extra_frames=(B,), matched=(B, G), frag=(B, G),
+                trk_state=(B, G), frames=(B,), totals=(B, len(IDF_TOTALS)))
+
+
+class SqairLaneIdf(C.Structure):
+    """The identity overlap table of a clip per lane and the totals over closed clips (include/sqair_hip.h: sqair_set_idf); every
+    pointer is a device address, none optional."""
+    _fields_ = [("P", C.c_int32)] + [(n, C.c_void_p) for n in IDF_TABLE + ("totals",)]
+
+
 # lane identities (include/sqair_hip.h: sqair_set_identity): the scalars, the memory and the per-frame outputs of SqairLaneIdentity
 # in declaration order (all outputs int32); the names the outputs have in a step's ``lane`` dict; the columns of ``counts``
 IDENT_SCALARS = (("iou_min", C.c_float), ("reid_dist", C.c_float), ("reid_what", C.c_float), ("M", C.c_int32), ("max_age", C.c_int32))
@@ -409,6 +428,9 @@ _PROTOS = {
     "sqair_set_identity": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneIdentity), C.c_int, C.c_int]),
     "sqair_lane_identity_test": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.POINTER(SqairLaneIdentity), C.c_void_p]),
     "sqair_set_score_ids": (C.c_int, [C.c_void_p, C.c_int]),
+    "sqair_set_idf": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneIdf), C.c_int, C.c_int]),
+    "sqair_lane_idf_test": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.POINTER(SqairLaneScore), C.POINTER(SqairLaneIdf), C.c_void_p]),
+    "sqair_lane_idf_solve": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneIdf), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqair_lane_traj_score": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneTraj), C.POINTER(SqairTrajTruth), C.POINTER(SqairTrajScore),
                                         C.c_int, C.c_int, C.c_void_p]),
     "sqair_forecast_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),

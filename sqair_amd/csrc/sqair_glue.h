@@ -461,6 +461,30 @@ struct LaneTrajScoreArgs {
   int F, B, N;
 };
 int sq_launch_lane_traj_score(const LaneTrajScoreArgs& a, hipStream_t s);
+// IDF1 scoring (sqair_set_idf; include/sqair_hip.h states the semantics): k_lane_idf, one workgroup per lane b looping over the pass's
+// frames in order with the lane's table in LDS across them.  box / presence / ids [T][B][N] and map_count [T][B] are the words
+// k_lane_score was handed (or a test's buffers); of `sc` the truth, iou_min, G and truth_match are read.
+constexpr int SQ_IDF_MAXP = 64;
+struct LaneIdfArgs {
+  const float* box;                    // [T][B][N][4]
+  const float* presence;               // [T][B][N]
+  const float* ids;                    // [T][B][N] 32-bit id words
+  const int32_t* map_count;            // [T][B]
+  SqairLaneScore sc;                   // read-only here
+  SqairLaneIdf idf;                    // P, the table and totals
+  int T, B, N;
+};
+int sq_launch_lane_idf(const LaneIdfArgs& a, hipStream_t s);
+// The solve (sqair_lane_idf_solve): k_lane_idf_solve, one wavefront per lane b: the table to LDS, sq_assign_optimal_i32, the clip's
+// figures; for the lanes of `close` the figures into totals and the table freed.
+struct LaneIdfSolveArgs {
+  SqairLaneIdf idf;
+  const int32_t* close;                // [B] or NULL
+  int64_t* open;                       // [B][SQAIR_IDF_TOTALS] or NULL
+  int32_t* assign;                     // [B][G] or NULL
+  int G, B;
+};
+int sq_launch_lane_idf_solve(const LaneIdfSolveArgs& a, hipStream_t s);
 
 // Object forecasts (sqair_forecast_fan; include/sqair_hip.h states the semantics).  Fan-out: rollout row q = r * S + s.
 // k_forecast_fan_src expands the source map, src_fan[q] = src[q / S] (NULL: q / S), an index outside [0, R) of the blob -> -1.

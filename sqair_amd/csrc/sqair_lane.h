@@ -181,7 +181,9 @@ __device__ __forceinline__ void sq_lane_box_sum(const float* s_w, const SqBox* s
 //          eligible entry is matched with g;
 //   rest   repeat: the eligible pair of maximal entry among unmatched g and unclaimed j, ties to the smallest g, then the smallest
 //          j (a row-major scan with a strict compare); stop when none is left.
-// Leaves row_match[g] = j or -1 and col_claim[j] = 1 or 0; returns the number of pairs.  Greedy, not optimal (Hungarian) assignment.
+// Leaves row_match[g] = j or -1 and col_claim[j] = 1 or 0; returns the number of pairs.  Greedy, not optimal: the
+// optimal (Hungarian) assignment is sq_assign_optimal_i32, below, over an int32 table and a whole wavefront's work; the per-frame
+// matches of the score, the identity and the trajectory score stay greedy.
 __device__ __forceinline__ int sq_assign_keep_greedy(const float* iou, const int ld, const int G, const int N, const float iou_min,
                                                      const int* keep_id, const int* col_id, int* row_match, int* col_claim) {
   int n = 0;
@@ -211,4 +213,84 @@ __device__ __forceinline__ int sq_assign_keep_greedy(const float* iou, const int
     row_match[tg] = tj; col_claim[tj] = 1; ++n;
   }
   return n;
+}
+
+// Maximum-weight one-to-one assignment of rows g < G to columns p < P over an int32 table in LDS, w[g * ld + p], for ONE wavefront:
+// all 64 lanes call it together, lane p owns column p (P <= 64, G <= 64).  Rows and columns may stay unassigned -- every row g has a
+// private dummy column of weight 0, owned by lane g, so a pair of negative weight is never taken --: the optimum is the maximum over
+// all partial assignments of the sum of the weights.  Shortest augmenting paths with integer potentials (Hungarian / Jonker-
+// Volgenant), rows inserted in index order, O(G^2) wave steps: a step relaxes every unvisited column from the row just reached (one
+// column per lane, in registers: the potential, the row assigned to it and that row's potential, the distance, the way back) and
+// takes the wave-wide arg-min of the distances, a butterfly of shuffles over (distance, column) keys, ties to the smallest column, the
+// real ones before the dummies; then the path is flipped from its free end, one column per step, the owners exchanging rows by
+// shuffle.  Nothing is indexed in registers, no barrier is used: the only LDS written is row_to_col, once.  Exact for |weights| below
+// 2^30 (the potentials and distances are 64-bit sums of at most G weights; nothing is refused at run time for it).
+// Leaves row_to_col[g] = p or -1 (LDS, visible to the wave after the call) and returns the optimum in every lane.
+__device__ __forceinline__ long long sq_wave_min_i64(long long v) {
+  for (int m = 32; m >= 1; m >>= 1) {
+    const long long o = __shfl_xor(v, m, 64);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+__device__ __forceinline__ long long sq_wave_sum_i64(long long v) {
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+__device__ __forceinline__ long long sq_assign_optimal_i32(const int* w, const int ld, const int G, const int P, int* row_to_col) {
+  constexpr long long FAR = 1ll << 60, NO_KEY = 0x7fffffffffffffffll;
+  const int L = threadIdx.x & 63;
+  const bool hasA = L < P, hasB = L < G;   // slot A: column L; slot B: the dummy column of row L, number 64 + L
+  long long vA = 0, vB = 0, uA = 0, uB = 0;   // the column's potential; the potential of the row assigned to it
+  int pA = -1, pB = -1;                        // the row assigned to the column, -1 = free
+  for (int i = 0; i < G; ++i) {
+    long long dA = FAR, dB = FAR, u_root = 0, u0 = 0;
+    bool usedA = !hasA, usedB = !hasB;
+    int wayA = -1, wayB = -1, j0 = -1, i0 = i;   // (column -1: the root, row i)
+    for (int step = 0; step <= i + 1; ++step) {   // (a path visits at most the i assigned columns and a free one)
+      long long key = NO_KEY;
+      if (!usedA) {
+        const long long cur = -(long long)w[i0 * ld + L] - u0 - vA;
+        if (cur < dA) { dA = cur; wayA = j0; }
+        key = dA * 256 + L;
+      }
+      if (!usedB) {
+        if (i0 == L && -u0 - vB < dB) { dB = -u0 - vB; wayB = j0; }
+        if (dB < FAR) {
+          const long long kb = dB * 256 + (64 + L);
+          key = kb < key ? kb : key;
+        }
+      }
+      key = sq_wave_min_i64(key);   // (row i's own dummy is free and reachable: there always is one)
+      const long long delta = key >> 8;   // (the floor: a distance is negative until the row's potential has absorbed its best weight)
+      j0 = (int)(key & 255);
+      u_root += delta;
+      if (usedA) { uA += delta; vA -= delta; } else if (dA < FAR) dA -= delta;
+      if (usedB) { uB += delta; vB -= delta; } else if (dB < FAR) dB -= delta;
+      if (j0 == L) usedA = true;
+      if (j0 == 64 + L) usedB = true;
+      const bool dummy = j0 >= 64;
+      i0 = __shfl(dummy ? pB : pA, j0 & 63, 64);
+      u0 = __shfl(dummy ? uB : uA, j0 & 63, 64);
+      if (i0 < 0) break;   // a free column: the path ends
+    }
+    for (int step = 0; step <= i + 1; ++step) {   // flip the path: column j0 takes the row of the column before it, the first one the root's
+      const bool dummy = j0 >= 64;
+      const int j1 = __shfl(dummy ? wayB : wayA, j0 & 63, 64);
+      int pr = i;
+      long long ur = u_root;
+      if (j1 >= 0) {
+        const bool d1 = j1 >= 64;
+        pr = __shfl(d1 ? pB : pA, j1 & 63, 64);
+        ur = __shfl(d1 ? uB : uA, j1 & 63, 64);
+      }
+      if (j0 == L) { pA = pr; uA = ur; }
+      if (j0 == 64 + L) { pB = pr; uB = ur; }
+      if (j1 < 0) break;
+      j0 = j1;
+    }
+  }
+  if (hasA && pA >= 0) row_to_col[pA] = L;
+  if (hasB && pB >= 0) row_to_col[pB] = -1;
+  return sq_wave_sum_i64(hasA && pA >= 0 ? (long long)w[pA * ld + L] : 0ll);
 }

@@ -945,3 +945,146 @@ int sq_launch_lane_traj_score(const LaneTrajScoreArgs& a, hipStream_t s) {
   SQ_LAUNCH(k_lane_traj_score, dim3(a.B, (a.F + SQ_TRAJ_FRAMES - 1) / SQ_TRAJ_FRAMES), dim3(256), 0, s, a);
   return 0;
 }
+
+// ------------------------------------------------------------------------------------------------
+// IDF1 scoring (sqair_set_idf; LaneIdfArgs / LaneIdfSolveArgs in sqair_glue.h; the semantics: include/sqair_hip.h, points 1-5)
+// ------------------------------------------------------------------------------------------------
+// k_lane_idf: workgroup = lane b, looping over the pass's frames in order with the lane's table in LDS across them (a free column
+// loads as zeros: its stale words are never read).  Per scored frame thread 0 finds or makes the column of every present lane
+// object (at most N * P compares) and counts the column, the unkeyed objects and the frame; threads g < G count their truth's
+// presence, match and fragmentation; then thread i < G * N computes the IoU of pair (g, j) = (i / N, i % N) on the words the score
+// read and increments its own cell of the overlap table -- the columns of a frame are distinct, so every cell has one writer.
+// Everything is in LDS, nothing is indexed in registers.  Every branch around a barrier depends on truth_valid[t, b] and
+// map_count[t, b] alone: uniform over the workgroup.
+__global__ __launch_bounds__(256) void k_lane_idf(const LaneIdfArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ int s_ov[SQ_SCORE_MAXG * SQ_IDF_MAXP];
+  __shared__ int s_cid[SQ_IDF_MAXP], s_cfr[SQ_IDF_MAXP];
+  __shared__ int s_rfr[SQ_SCORE_MAXG], s_mat[SQ_SCORE_MAXG], s_frag[SQ_SCORE_MAXG], s_st[SQ_SCORE_MAXG];
+  __shared__ int s_jcol[SQ_MAXN];
+  const SqairLaneScore& o = a.sc;
+  const SqairLaneIdf& f = a.idf;
+  const int b = blockIdx.x, tid = threadIdx.x, G = o.G, N = a.N, P = f.P;
+  if (tid < P) {
+    s_cid[tid] = f.col_id[(size_t)b * P + tid];
+    s_cfr[tid] = s_cid[tid] >= 0 ? f.col_frames[(size_t)b * P + tid] : 0;
+  }
+  if (tid < G) {
+    const size_t e = (size_t)b * G + tid;
+    s_rfr[tid] = f.row_frames[e]; s_mat[tid] = f.matched[e]; s_frag[tid] = f.frag[e]; s_st[tid] = f.trk_state[e];
+  }
+  for (int i = tid; i < G * P; i += 256) s_ov[i] = f.col_id[(size_t)b * P + i % P] >= 0 ? f.overlap[(size_t)b * G * P + i] : 0;
+  int c_extra = 0, c_frames = 0, c_over = 0;   // (thread 0's)
+  for (int t = 0; t < a.T; ++t) {
+    const size_t tb = (size_t)t * a.B + b;
+    if (o.truth_valid[tb] == 0 || a.map_count[tb] == -1) continue;   // no truth, or a non-finite lane: nothing is touched
+    __syncthreads();   // (the table is loaded; the last frame's increments are in it)
+    // ---- a, b: the columns of the frame's objects, one thread
+    if (tid == 0) {
+      int unkeyed = 0;
+      for (int j = 0; j < N; ++j) {
+        s_jcol[j] = -1;
+        if (a.presence[tb * N + j] == 0.0f) continue;
+        const int word = (int)sq_word(a.ids + tb * N + j);
+        int col = -1, free_col = -1;
+        if (word >= 0) {
+          for (int p = 0; p < P; ++p) {
+            const int id = s_cid[p];
+            if (id == word) { col = p; break; }
+            if (id < 0 && free_col < 0) free_col = p;
+          }
+          if (col >= 0) {
+            for (int jj = 0; jj < j; ++jj)
+              if (s_jcol[jj] == col) col = -2;   // an earlier object of the frame holds the word
+          } else if (free_col >= 0) {
+            col = free_col;
+            s_cid[col] = word; s_cfr[col] = 0;
+            for (int g = 0; g < G; ++g) s_ov[g * P + col] = 0;
+          }
+        }
+        if (col >= 0) { s_jcol[j] = col; s_cfr[col] += 1; }
+        else ++unkeyed;
+      }
+      c_extra += unkeyed; c_over += unkeyed > 0; ++c_frames;
+    }
+    // ---- c, e, f: the truth's counters, thread g
+    if (tid < G && o.truth_present[tb * G + tid] != 0) {
+      const int m = o.truth_match[tb * G + tid] >= 0, st = s_st[tid];
+      s_rfr[tid] += 1; s_mat[tid] += m;
+      s_frag[tid] += m && (st & 2) && !(st & 1);
+      s_st[tid] = (st & 2) | (m ? 3 : 0);
+    }
+    __syncthreads();
+    // ---- d: every overlapping pair
+    if (tid < G * N) {
+      const int g = tid / N, j = tid - g * N, col = s_jcol[j];
+      if (col >= 0 && o.truth_present[tb * G + g] != 0) {
+        const float* p = o.truth_box + (tb * G + g) * 4;
+        const float* q = a.box + (tb * N + j) * 4;
+        if (sq_box_iou(SqBox{p[0], p[1], p[2], p[3]}, SqBox{q[0], q[1], q[2], q[3]}) >= o.iou_min) s_ov[g * P + col] += 1;
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < P) { f.col_id[(size_t)b * P + tid] = s_cid[tid]; f.col_frames[(size_t)b * P + tid] = s_cfr[tid]; }
+  if (tid < G) {
+    const size_t e = (size_t)b * G + tid;
+    f.row_frames[e] = s_rfr[tid]; f.matched[e] = s_mat[tid]; f.frag[e] = s_frag[tid]; f.trk_state[e] = s_st[tid];
+  }
+  for (int i = tid; i < G * P; i += 256) f.overlap[(size_t)b * G * P + i] = s_ov[i];
+  if (tid == 0) {
+    f.extra_frames[b] += c_extra; f.frames[b] += c_frames;
+    f.totals[(size_t)b * SQAIR_IDF_TOTALS + 11] += c_over;
+  }
+}
+int sq_launch_lane_idf(const LaneIdfArgs& a, hipStream_t s) {
+  SQ_LAUNCH(k_lane_idf, dim3(a.B), dim3(256), 0, s, a);
+  return 0;
+}
+
+// k_lane_idf_solve: workgroup = lane b, ONE wavefront.  The lane's overlap table to LDS (a free column as zeros), the optimal
+// assignment (sq_assign_optimal_i32, lane p owning column p), then the clip's twelve figures as wave sums -- lane g < G brings its
+// truth's counters, lane p < P its column's --, written by lane 0; a closed lane's figures go into totals and its table is freed,
+// every lane storing over the words it read itself.
+__global__ __launch_bounds__(64) void k_lane_idf_solve(const LaneIdfSolveArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ int s_w[SQ_SCORE_MAXG * SQ_IDF_MAXP];
+  __shared__ int s_r2c[SQ_SCORE_MAXG];
+  const SqairLaneIdf& f = a.idf;
+  const int b = blockIdx.x, L = threadIdx.x, G = a.G, P = f.P;
+  const int cid = L < P ? f.col_id[(size_t)b * P + L] : -1;
+  for (int i = L; i < G * P; i += 64) s_w[i] = f.col_id[(size_t)b * P + i % P] >= 0 ? f.overlap[(size_t)b * G * P + i] : 0;
+  __syncthreads();
+  const long long idtp = sq_assign_optimal_i32(s_w, P, G, P, s_r2c);
+  __syncthreads();
+  const size_t e = (size_t)b * G + L;
+  const int rf = L < G ? f.row_frames[e] : 0, m = L < G ? f.matched[e] : 0;
+  const bool traj = rf > 0, mt = traj && 5ll * m >= 4ll * rf, ml = traj && 5ll * m < rf;
+  const long long n_row = sq_wave_sum_i64(rf), n_col = sq_wave_sum_i64(cid >= 0 ? f.col_frames[(size_t)b * P + L] : 0);
+  const long long n_traj = sq_wave_sum_i64(traj), n_mt = sq_wave_sum_i64(mt), n_ml = sq_wave_sum_i64(ml);
+  const long long n_frag = sq_wave_sum_i64(L < G ? f.frag[e] : 0), n_ids = sq_wave_sum_i64(cid >= 0);
+  const bool closed = a.close && a.close[b] != 0;
+  if (L < G && a.assign) {
+    const int p = s_r2c[L];
+    a.assign[e] = p >= 0 && s_w[L * P + p] > 0 ? f.col_id[(size_t)b * P + p] : -1;
+  }
+  if (L == 0) {
+    const long long frames = f.frames[b], extra = f.extra_frames[b];
+    const long long fig[SQAIR_IDF_TOTALS] = {frames > 0, frames, n_traj, idtp, n_row - idtp, n_col + extra - idtp, n_mt,
+                                             n_traj - n_mt - n_ml, n_ml, n_frag, n_ids, 0};
+#pragma unroll
+    for (int k = 0; k < SQAIR_IDF_TOTALS; ++k) {
+      if (a.open) a.open[(size_t)b * SQAIR_IDF_TOTALS + k] = fig[k];
+      if (closed) f.totals[(size_t)b * SQAIR_IDF_TOTALS + k] += fig[k];
+    }
+    if (closed) { f.frames[b] = 0; f.extra_frames[b] = 0; }
+  }
+  if (!closed) return;
+  __syncthreads();   // (assign has read the ids of the columns before they are freed)
+  if (L < P) f.col_id[(size_t)b * P + L] = -1;
+  if (L < G) { f.row_frames[e] = 0; f.matched[e] = 0; f.frag[e] = 0; f.trk_state[e] = 0; }
+}
+int sq_launch_lane_idf_solve(const LaneIdfSolveArgs& a, hipStream_t s) {
+  SQ_LAUNCH(k_lane_idf_solve, dim3(a.B), dim3(64), 0, s, a);
+  return 0;
+}

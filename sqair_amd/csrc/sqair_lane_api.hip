@@ -1,8 +1,9 @@
 // libsqair_hip.so -- the lane answers on the native side of the C ABI (include/sqair_hip.h): the estimate and its followers, the
-// layers, the identity and the score.  Their registration on a handle as one block (SqLaneSet, sqair_internal.h: sqair_set_estimate
-// / _layers / _score / _identity / _score_ids), the estimate's refusal of a pass, ONE builder per kernel's arguments -- called by the
+// layers, the identity, the score and the IDF1 table.  Their registration on a handle as one block (SqLaneSet, sqair_internal.h:
+// sqair_set_estimate / _layers / _score / _identity / _score_ids / _idf), the estimate's refusal of a pass, ONE builder per kernel's arguments -- called by the
 // pass and by the kernel-level entry point alike --, the pass's launch sequence (sq_launch_lane_answers, called by sq_forward_impl
-// with the block sq_resolve_pass resolved) and the stand-alone entry points (sqair_lane_*_test, sqair_lane_traj_score).  Host code
+// with the block sq_resolve_pass resolved) and the stand-alone entry points (sqair_lane_*_test, sqair_lane_traj_score,
+// sqair_lane_idf_solve).  Host code
 // only: the kernels and their launchers live in sqair_lane.hip, which work here does not move.  A further follower is one member
 // of SqLaneSet, its registration and builder here, and one line of sq_launch_lane_answers.
 #include "sqair_internal.h"
@@ -30,6 +31,14 @@ static int sq_score_fields(SqairHandle* h, const std::string& who, const SqairLa
     return sq_no(h, who + "truth_box, truth_present, truth_valid, counts, iou_sum and last_id must not be NULL");
   return 0;
 }
+static int sq_idf_fields(SqairHandle* h, const std::string& who, const SqairLaneIdf& c) {
+  if (c.P < 1 || c.P > SQ_IDF_MAXP)
+    return sq_no(h, who + "P = " + std::to_string(c.P) + " must lie in 1.." + std::to_string(SQ_IDF_MAXP));
+  if (!c.col_id || !c.overlap || !c.row_frames || !c.col_frames || !c.extra_frames || !c.matched || !c.frag || !c.trk_state || !c.frames ||
+      !c.totals)
+    return sq_no(h, who + "col_id, overlap, row_frames, col_frames, extra_frames, matched, frag, trk_state, frames and totals must not be NULL");
+  return 0;
+}
 static int sq_identity_fields(SqairHandle* h, const std::string& who, const SqairLaneIdentity& c) {
   const int N = h->cfg.n_steps_per_image;
   if (c.M < N || c.M > SQ_IDENT_MAXM)
@@ -48,7 +57,9 @@ static int sq_identity_fields(SqairHandle* h, const std::string& who, const Sqai
 // ------------------------------------------------------------------------------------------------
 static void sq_layers_off(SqLaneSet& l) { l.lay_on = false; l.lay = SqairLaneLayers{}; }
 // (the score reads the identity's ids only while both are on: either going off puts score_ids back to 0)
-static void sq_score_off(SqLaneSet& l) { l.score_on = false; l.score = SqairLaneScore{}; l.score_ids = false; }
+// (and the IDF reads the score's truth and its truth_match: it goes off with it)
+static void sq_idf_off(SqLaneSet& l) { l.idf_on = false; l.idf = SqairLaneIdf{}; }
+static void sq_score_off(SqLaneSet& l) { l.score_on = false; l.score = SqairLaneScore{}; l.score_ids = false; sq_idf_off(l); }
 static void sq_identity_off(SqLaneSet& l) { l.ident_on = false; l.ident = SqairLaneIdentity{}; l.score_ids = false; }
 // what the followers need of the estimate they read (best_row is never NULL in a registered estimate; `what`: the identity keeps an
 // appearance, trk_what, and reads the estimate's)
@@ -121,7 +132,24 @@ extern "C" int sqair_set_score(SqairHandle* h, const SqairLaneScore* score, int 
   if (!sq_estimate_scorable(h->lane.est))
     return sq_no(h, who + "the estimate (sqair_set_estimate) must bind box, presence, obj_id and map_count: the score reads them");
   if (sq_follower_shape_refusal(h, who, T, B) != 0 || sq_score_fields(h, who, *score) != 0) return -1;
+  // a re-registered score drops the IDF it can no longer feed: a table sized for the other G, the output it reads gone
+  if (h->lane.score_on && (!score->truth_match || score->G != h->lane.score.G)) sq_idf_off(h->lane);
   h->lane.score_on = true; h->lane.score = *score;
+  return 0;
+}
+extern "C" int sqair_set_idf(SqairHandle* h, const SqairLaneIdf* idf, int T, int B) {
+  if (!h) return -1;
+  if (!idf) {
+    sq_idf_off(h->lane);
+    return 0;
+  }
+  const std::string who = "sqair_set_idf: ";
+  if (!h->state_on || !h->lane.est_on || !h->lane.score_on)
+    return sq_no(h, who + "needs a score (sqair_set_score): the table is keyed by the truth and the id words the score reads");
+  if (!h->lane.score.truth_match)
+    return sq_no(h, who + "the score (sqair_set_score) must bind truth_match: the trajectory statistics read the score's matches");
+  if (sq_follower_shape_refusal(h, who, T, B) != 0 || sq_idf_fields(h, who, *idf) != 0) return -1;
+  h->lane.idf_on = true; h->lane.idf = *idf;
   return 0;
 }
 extern "C" int sqair_set_identity(SqairHandle* h, const SqairLaneIdentity* id, int T, int B) {
@@ -184,11 +212,19 @@ static LaneScoreArgs sq_score_args(const SqairConfig& c, const float* box, const
   a.T = T; a.B = B; a.N = c.n_steps_per_image;
   return a;
 }
+// (`ids`: the id words the score is handed for the same frames; of `score` the truth, iou_min, G and truth_match are read)
+static LaneIdfArgs sq_idf_args(const SqairConfig& c, const float* box, const float* presence, const float* ids, const int32_t* map_count,
+                               const SqairLaneScore& score, const SqairLaneIdf& idf, int T, int B) {
+  LaneIdfArgs a; memset(&a, 0, sizeof(a));
+  a.box = box; a.presence = presence; a.ids = ids; a.map_count = map_count; a.sc = score; a.idf = idf;
+  a.T = T; a.B = B; a.N = c.n_steps_per_image;
+  return a;
+}
 
 // ------------------------------------------------------------------------------------------------
 // the pass: every lane launch, in the one order they have.  The estimate comes before the resampler zeroes the weights it reads
 // and rewrites the map; the followers read the estimate's own output buffers, the identity before the score, which may read the
-// ids it writes.  `l` is the pass's resolved copy: nothing here reads the handle's registration
+// ids it writes, the IDF1 table after the score, whose matches and id words it reads.  `l` is the pass's resolved copy: nothing here reads the handle's registration
 // ------------------------------------------------------------------------------------------------
 int sq_launch_lane_answers(SqairHandle* h, const SqLaneSet& l, const float* rec, const float* glimpse, const SqairOutputs& out, int T, int B,
                            hipStream_t s) {
@@ -215,12 +251,14 @@ int sq_launch_lane_answers(SqairHandle* h, const SqLaneSet& l, const float* rec,
   if (l.score_on) {
     const float* ids = (l.ident_on && l.score_ids) ? reinterpret_cast<const float*>(l.ident.lane_id) : e.obj_id;
     sq_launch_lane_score(sq_score_args(c, e.box, e.presence, ids, e.map_count, l.score, T, B), s);
+    // IDF1 scoring: the clip's identity overlap table (sqair_set_idf), accumulated in place on the words the score just read
+    if (l.idf_on) sq_launch_lane_idf(sq_idf_args(c, e.box, e.presence, ids, e.map_count, l.score, l.idf, T, B), s);
   }
   return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
-// kernel-level checks (tests/test_{estimate,layers,score,identity}_kernel.py): one kernel on caller tensors, no state and no pass;
+// kernel-level checks (tests/test_{estimate,layers,score,identity,idf}_kernel.py): one kernel on caller tensors, no state and no pass;
 // K, where there is one, is given (1..SQ_MAX_K)
 // ------------------------------------------------------------------------------------------------
 extern "C" int sqair_lane_estimate_test(SqairHandle* h, const float* where, const float* presence, const float* obj_id,
@@ -274,6 +312,35 @@ extern "C" int sqair_lane_identity_test(SqairHandle* h, const float* box, const 
   if (sq_identity_fields(h, who, *id) != 0) return -1;
   if (id->trk_what && !what) return sq_no(h, who + "id->trk_what needs what");
   sq_launch_lane_identity(sq_identity_args(h->cfg, box, presence, obj_id, what, best_row, *id, T, B), (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+extern "C" int sqair_lane_idf_test(SqairHandle* h, const float* box, const float* presence, const float* ids, const int32_t* map_count,
+                                   int T, int B, const SqairLaneScore* score, const SqairLaneIdf* idf, void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_lane_idf_test: ";
+  if (!box || !presence || !ids || !map_count || !score || !idf || T < 1 || B < 1 || T > 65535)
+    return sq_no(h, who + "null box / presence / ids / map_count / score / idf or bad T / B");
+  if (sq_truth_slots_refusal(h, who, score->G) != 0 || sq_unit_refusal(h, who, "iou_min", score->iou_min) != 0) return -1;
+  if (!score->truth_box || !score->truth_present || !score->truth_valid || !score->truth_match)
+    return sq_no(h, who + "the score's truth_box, truth_present, truth_valid and truth_match must not be NULL");
+  if (sq_idf_fields(h, who, *idf) != 0) return -1;
+  sq_launch_lane_idf(sq_idf_args(h->cfg, box, presence, ids, map_count, *score, *idf, T, B), (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+// the IDF1 solve (include/sqair_hip.h: sqair_lane_idf_solve): a stand-alone call on the table the passes -- or a test -- filled, nothing
+// registered on the handle, which gives the error text
+extern "C" int sqair_lane_idf_solve(SqairHandle* h, const SqairLaneIdf* idf, int G, int B, const int32_t* close, int64_t* open,
+                                    int32_t* assign, void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_lane_idf_solve: ";
+  if (!idf) return sq_no(h, who + "idf must not be NULL");
+  if (B < 1) return sq_no(h, who + "B = " + std::to_string(B) + " must be >= 1");
+  if (sq_truth_slots_refusal(h, who, G) != 0 || sq_idf_fields(h, who, *idf) != 0) return -1;
+  LaneIdfSolveArgs a; memset(&a, 0, sizeof(a));
+  a.idf = *idf; a.close = close; a.open = open; a.assign = assign; a.G = G; a.B = B;
+  sq_launch_lane_idf_solve(a, (hipStream_t)stream);
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }

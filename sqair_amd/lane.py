@@ -36,6 +36,14 @@ is absent; ``identities()`` reads the counters and the table.  ``reset(lanes)`` 
 within a lane.  ``score_ids="lane"`` (with ``score=True``) makes the score count its identity switches on ``lane_id`` instead of
 ``obj_id``.
 
+``score_idf=True`` (with ``score=True``): the score's idsw counts the moments an identity changes, not for how long the wrong id then
+stays.  The stream then also keeps, per lane and on the device, how many frames of the open clip every truth overlapped (IoU >=
+``score_iou``) every predicted id -- the id words the score reads: ``obj_id``, or ``lane_id`` with ``score_ids="lane"`` --, up to
+``score_idf_ids`` ids per clip, one more kernel of the pass after the score's (sqair_set_idf); ``idf_score()`` solves the maximum-weight
+one-to-one assignment of truths to ids on the device (sqair_lane_idf_solve) and returns IDF1, IDP, IDR, mostly tracked / partly
+tracked / mostly lost and the fragmentations.  ``reset(lanes)`` closes those lanes' clips -- their figures go into the totals and
+their tables are freed -- before it forgets their identities: a new clip has new truth identities.
+
 ``forecast(..., lane=True, truth=...)`` and ``tracks(..., lane=True, truth=...)`` score the two answers that reach over time -- the
 lane forecast and the lane tracks -- against the truth's trajectories with one more launch after the call's own
 (sqair_lane_traj_score): truth and lane objects are linked once, at the last stepped frame, and every horizon or traced frame then
@@ -119,11 +127,12 @@ class LaneAnswers(object):
     """The lane answers a stream's steps fill.  The constructor only checks its keyword group (no core, no device: it runs before the
     stream touches either); ``register`` allocates the buffers and registers them on the core's handle.  ``flat`` / ``views``: ONE
     allocation and its views by field, ``est`` (field_views) -- everything a step copies out as ``out["lane"]``; ``score_buf`` and
-    ``ident_buf``: the score's truth, accumulators and identity memory, the identity's track table and counters."""
+    ``ident_buf``: the score's truth, accumulators and identity memory, the identity's track table and counters; ``idf_buf``: the
+    IDF1 table of every lane's open clip and the totals over the closed ones."""
 
     def __init__(self, who, estimate, estimate_iou, estimate_canvas, estimate_layers, layers_cover_min, score, score_iou, score_truth,
                  identity, identity_iou, identity_tracks, identity_max_age, identity_reid_dist, identity_reid_what, identity_appearance,
-                 score_ids):
+                 score_ids, score_idf=False, score_idf_ids=32):
         self.step_fn, who = who + ".step: ", who + ": "
 
         def bad(why):
@@ -163,6 +172,11 @@ class LaneAnswers(object):
             bad("score_ids must be 'row' or 'lane'")
         if score_ids == "lane" and not (score and identity):
             bad("score_ids='lane' is for a stream with score=True and identity=True")
+        if score_idf and not score:
+            bad("score_idf is for a stream with score=True")
+        if score_idf and not is_int_in(score_idf_ids, 1, _capi.IDF_MAX_IDS):
+            bad("score_idf_ids must be an integer in [1, {}]".format(_capi.IDF_MAX_IDS))
+        self.idf, self.P = bool(score_idf), int(score_idf_ids) if score_idf else 0
         self.who = who
         self.estimate, self.canvas, self.layers = bool(estimate), bool(estimate_canvas), bool(estimate_layers)
         self.scored, self.identified, self.appearance = bool(score), bool(identity), bool(identity_appearance)
@@ -230,6 +244,13 @@ class LaneAnswers(object):
             core.check(lib.sqair_set_identity(h, C.byref(idt), T, B), "sqair_set_identity")
             if self.score_ids == "lane":
                 core.check(lib.sqair_set_score_ids(h, 1), "sqair_set_score_ids")
+        if self.idf:   # the overlap table of every lane's open clip, the totals over the closed ones, and what a solve writes
+            self.idf_buf = {n: z(shp, torch.int64 if n == "totals" else torch.int32) for n, shp in _capi.idf_shapes(B, G, self.P).items()}
+            self.idf_buf["col_id"].fill_(-1)
+            self._idf_c = _capi.SqairLaneIdf(P=self.P, **{n: t.data_ptr() for n, t in self.idf_buf.items()})
+            self._idf_out = dict(open=z((B, len(_capi.IDF_TOTALS)), torch.int64), assign=z((B, G), torch.int32), close=z((B,), torch.int32))
+            sync()
+            core.check(lib.sqair_set_idf(h, C.byref(self._idf_c), T, B), "sqair_set_idf")
 
     # ---- per step ------------------------------------------------------------------------------------------------------------
     def check_truth(self, truth):
@@ -270,9 +291,15 @@ class LaneAnswers(object):
     def reset(self, lanes, on_core_stream):
         """The follow-ups of a stream's ``reset(lanes)`` (``lanes`` checked and distinct; ``on_core_stream``: the carried state's context):
         the score forgets those lanes' identities (``last_id``) and keeps their counters; the identity frees their track entries
-        (``trk_id`` = -1) and keeps their ``next_id``."""
+        (``trk_id`` = -1) and keeps their ``next_id``.  Before either, a stream with ``score_idf`` closes those lanes' clips: one solve
+        with their mask, their figures into the totals, their tables freed."""
         if lanes and (self.scored or self.identified):
             with on_core_stream():
+                if self.idf:
+                    close = self._idf_out["close"]
+                    close.zero_()
+                    close[torch.as_tensor(lanes, device=close.device)] = 1
+                    self._solve(close)
                 for j in lanes:
                     if self.scored:
                         self.score_buf["last_id"][j].fill_(-1)
@@ -290,6 +317,42 @@ class LaneAnswers(object):
         res["mota"] = 1.0 - _ratio(tot["fn"] + tot["fp"] + tot["idsw"], tot["truth"])
         res["motp"] = _ratio(float(got["iou_sum"].sum()), tot["tp"])
         res["count_accuracy"] = _ratio(tot["count_hit"], tot["frames"])
+        return res
+
+    def _solve(self, close=None):
+        """One solve on the current stream (include/sqair_hip.h: sqair_lane_idf_solve) into ``_idf_out``; ``close``: the device mask
+        [B] of the lanes whose clip ends."""
+        core, o = self.core, self._idf_out
+        core.check(core.lib.sqair_lane_idf_solve(core.handle, C.byref(self._idf_c), self.G, self.B,
+                                                 None if close is None else close.data_ptr(), o["open"].data_ptr(), o["assign"].data_ptr(),
+                                                 core._stream()), "sqair_lane_idf_solve")
+
+    def idf_score(self, reset=False):
+        if not self.idf:
+            raise ValueError("SqairStream.idf_score: the stream keeps no IDF1 table (SqairStream(..., estimate=True, score=True, "
+                             "score_idf=True))")
+        core, buf = self.core, self.idf_buf
+        with torch.cuda.device(core.device):
+            core._join_in()
+            with core.on_stream():
+                self._solve()
+                got = {n: t.clone() for n, t in (("totals", buf["totals"]), ("open", self._idf_out["open"]), ("assign", self._idf_out["assign"]))}
+                if reset:   # the totals from zero, every table free (what a close leaves, without counting the clip)
+                    buf["col_id"].fill_(-1)
+                    for n in ("totals", "row_frames", "matched", "frag", "trk_state", "extra_frames", "frames"):
+                        buf[n].zero_()
+            core._join_out()
+        got = {n: t.cpu() for n, t in got.items()}
+        res = _columns(got["totals"] + got["open"], _capi.IDF_TOTALS)
+        tot = {n: int(v.sum()) for n, v in res.items()}
+        res["assign"] = got["assign"]
+        res["idf1"] = _ratio(2 * tot["idtp"], 2 * tot["idtp"] + tot["idfp"] + tot["idfn"])
+        res["idp"] = _ratio(tot["idtp"], tot["idtp"] + tot["idfp"])
+        res["idr"] = _ratio(tot["idtp"], tot["idtp"] + tot["idfn"])
+        res["mt_rate"] = _ratio(tot["mt"], tot["trajectories"])
+        res["ml_rate"] = _ratio(tot["ml"], tot["trajectories"])
+        res["frag_per_lane"], res["frag"] = res["frag"], tot["frag"]
+        res["exact"] = tot["overflow_ids"] == 0
         return res
 
     def identities(self):

@@ -41,7 +41,8 @@ network "see" an empty scene and kill the objects.
 
 With ``estimate=True`` a step also returns ``out["lane"]``: one answer per lane and frame from the K particles, and its followers
 say more about it, each one more kernel of the pass -- ``estimate_layers`` which pixels each object occupies, ``identity`` a track id
-that stays on an object, ``score`` the CLEAR-MOT events against a step's ``truth`` (``score()``, ``identities()``); ``forecast`` and
+that stays on an object, ``score`` the CLEAR-MOT events against a step's ``truth`` (``score()``, ``identities()``), ``score_idf`` the identity overlap table
+IDF1 is solved from (``idf_score()``); ``forecast`` and
 ``tracks`` with ``lane=True, truth=...`` score the lane forecast and the lane tracks (``trajectory_score(kind)``).  sqair_amd/lane.py
 holds all of it and says what each returns.
 
@@ -73,7 +74,7 @@ class SqairStream(object):
                  state=None, history=None, history_fields=tuple(_capi.HISTORY_FIELDS), missing=False, estimate=False,
                  estimate_iou=0.5, estimate_canvas=False, estimate_layers=False, layers_cover_min=0.5, score=False, score_iou=0.5,
                  score_truth=None, identity=False, identity_iou=0.3, identity_tracks=None, identity_max_age=10, identity_reid_dist=4.0,
-                 identity_reid_what=float("inf"), identity_appearance=True, score_ids="row"):
+                 identity_reid_what=float("inf"), identity_appearance=True, score_ids="row", score_idf=False, score_idf_ids=32):
         if core.cfg.sample_from_prior:
             raise ValueError("SqairStream: generation modes (sample_from_prior) do not carry a state across calls")
         if resample not in (None, "systematic"):
@@ -83,7 +84,7 @@ class SqairStream(object):
             raise ValueError("SqairStream: ess_frac must lie in [0, 1]")
         la = self.lane = LaneAnswers("SqairStream", estimate, estimate_iou, estimate_canvas, estimate_layers, layers_cover_min, score,
                                      score_iou, score_truth, identity, identity_iou, identity_tracks, identity_max_age,
-                                     identity_reid_dist, identity_reid_what, identity_appearance, score_ids)   # (checks only)
+                                     identity_reid_dist, identity_reid_what, identity_appearance, score_ids, score_idf, score_idf_ids)   # (checks only)
         self.smc = resample is not None
         self.ess_frac = ess_frac
         self.core = core
@@ -138,8 +139,8 @@ class SqairStream(object):
         carried(n) for n in ("state", "log_weight_sum", "log_z", "log_evidence", "ess", "u", "resampled", "_src", "_armed",
                              "_src_is_identity", "history", "history_fields"))
     # the lane answers', likewise
-    estimate, scored, identified, G, M, _est_flat, _est_views, _est, _score, _ident = (
-        lane_answer(n) for n in ("estimate", "scored", "identified", "G", "M", "flat", "views", "est", "score_buf", "ident_buf"))
+    estimate, scored, identified, G, M, _est_flat, _est_views, _est, _score, _ident, _idf = (
+        lane_answer(n) for n in ("estimate", "scored", "identified", "G", "M", "flat", "views", "est", "score_buf", "ident_buf", "idf_buf"))
     _traj = lane_answer("acc", of="traj")
 
     def _set_smc(self, uniforms):
@@ -158,7 +159,8 @@ class SqairStream(object):
         """Lanes (sequences, in [0, B)) whose next step starts a new clip: their K particle rows start fresh, counter 0.  A scored
         stream also forgets those lanes' identities (``last_id``: a new clip has new ones); their counters stay.  A stream with
         ``identity=True`` frees those lanes' track entries (``trk_id`` = -1) and keeps their ``next_id``: an id is never reused within
-        a lane."""
+        a lane.  A stream with ``score_idf=True`` first closes those lanes' clips (one solve on the device): their IDF1 figures go
+        into the totals and their tables are freed -- a new clip has new truth identities."""
         self.carried.reset(lanes)
         self.lane.reset(sorted(set(self.carried.check_lanes(lanes))), self.carried._on_core_stream)
 
@@ -239,6 +241,17 @@ class SqairStream(object):
         frames, each NaN where its denominator is 0.  ``reset``: the counters and ``iou_sum`` start again from zero afterwards; the
         identity memory stays (``reset(lanes)`` clears that)."""
         return self.lane.score(reset)
+
+    def idf_score(self, reset=False):
+        """The identity measures so far (include/sqair_hip.h: sqair_set_idf): one solve on the device, nothing closed.  Per lane, the
+        totals over the closed clips plus the open clip, the int64 figures ``clips``, ``frames``, ``trajectories``, ``idtp``, ``idfn``,
+        ``idfp``, ``mt``, ``pt``, ``ml``, ``frag_per_lane``, ``ids``, ``overflow_ids`` [B] (host tensors);
+        ``assign`` [B, G] int32, the id word assigned to each truth of the open clip (-1: none; optimal assignments tie); pooled over the
+        lanes ``idf1`` = 2 idtp / (2 idtp + idfp + idfn), ``idp`` = idtp / (idtp + idfp), ``idr`` = idtp / (idtp + idfn), ``mt_rate`` =
+        mt / trajectories, ``ml_rate`` = ml / trajectories, each NaN where its denominator is 0, ``frag`` the fragmentations and
+        ``exact``: no frame held an object without a column (``overflow_ids`` == 0: more than ``score_idf_ids`` ids in a clip, a
+        negative id word).  ``reset``: the totals start again from zero and every table is freed afterwards."""
+        return self.lane.idf_score(reset)
 
     # ---- lane identities --------------------------------------------------------------------------------------------------
     def identities(self):

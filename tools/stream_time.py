@@ -60,6 +60,14 @@ score, score + identity (score_ids="lane"); the scored legs are fed a device-res
 reported next to the estimate's and the resampler's node of the same run.
 
     python tools/stream_time.py --identity [--out profiles/stream_identity_time.json]
+
+With --idf: the price of IDF1 scoring (SqairStream(estimate=True, score=True, score_idf=True, score_idf_ids=32), include/sqair_hip.h:
+sqair_set_idf).  Streams at cfg-2's batch alternating in one process as with --history: plain, SMC, estimate, SMC + estimate, score,
+SMC + score, score + IDF, SMC + score + IDF; the scored legs are fed a device-resident truth as with --score.  The IDF's node is reported
+next to the score's and the resampler's node of the same run, and the median time of ``idf_score()`` -- the solve, its three copies
+and the host's pooling -- is measured separately.  Recorded, not gated on:
+
+    python tools/stream_time.py --idf [--out profiles/stream_idf_time.json]
 """
 import argparse
 import json
@@ -333,6 +341,45 @@ def time_identity(B, K, N, steps, warmup, rounds=10, hw=(50, 50)):
     return res
 
 
+def time_idf(B, K, N, steps, warmup, rounds=10, hw=(50, 50), P=32):
+    smc = dict(resample="systematic", ess_frac=0.5)
+    sc = dict(estimate=True, score=True, score_truth=N)
+    idf = dict(sc, score_idf=True, score_idf_ids=P)
+    legs = dict(plain={}, smc=smc, estimate=dict(estimate=True), smc_estimate=dict(estimate=True, **smc), score=sc, smc_score=dict(sc, **smc),
+                score_idf=idf, smc_score_idf=dict(idf, **smc))
+    rng = np.random.default_rng(3)
+    box = np.concatenate([rng.uniform(-5, 35, (1, B, N, 2)), rng.uniform(8, 28, (1, B, N, 2))], -1).astype(np.float32)
+    truth = dict(box=torch.as_tensor(box).cuda(), present=torch.ones((1, B, N), dtype=torch.int32).cuda(),
+                 valid=torch.ones((1, B), dtype=torch.int32).cuda())
+    step_kw = {n: dict(truth=truth) for n in ("score", "smc_score", "score_idf", "smc_score_idf")}
+    streams, res, med, thr = alternating_streams(legs, B, K, N, steps, warmup, rounds, hw, step_kw)
+    res["P"] = P
+    st = streams["smc_score_idf"]
+    with st.core.on_stream():   # idf_score(): the solve, the copies and the pooling, every call waited for
+        for _ in range(5):
+            st.idf_score()
+        torch.cuda.synchronize()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(100)]
+        for x, y in ev:
+            x.record()
+            got = st.idf_score()
+            y.record()
+            st.core.stream.synchronize()
+    ms = [x.elapsed_time(y) for x, y in ev]
+    res["idf_score_ms"] = dict(median=float(np.median(ms)), p10=float(np.percentile(ms, 10)), p90=float(np.percentile(ms, 90)))
+    res["idf_score"] = {n: (int(v.sum()) if torch.is_tensor(v) else v) for n, v in got.items() if n != "assign"}   # (over the lanes)
+    for key, v in (("latency", med), ("back_to_back", thr)):
+        one_node = v["smc"] - v["plain"]            # the yardstick: one dependent node (the resampler) on this machine, this run
+        added = dict(estimate_node_on_plain=v["estimate"] - v["plain"], score_node_on_estimate=v["score"] - v["estimate"],
+                     score_node_on_smc_estimate=v["smc_score"] - v["smc_estimate"], idf_node_on_score=v["score_idf"] - v["score"],
+                     idf_node_on_smc_score=v["smc_score_idf"] - v["smc_score"])
+        res["us_" + key] = dict(smc_node=1e3 * one_node, **{n: 1e3 * a for n, a in added.items()},
+                                **{n + "_over_smc_node": (a / one_node if one_node > 0 else None) for n, a in added.items()})
+    for st in streams.values():
+        st.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=500)
@@ -346,10 +393,13 @@ def main():
     ap.add_argument("--layers", action="store_true", help="plain / SMC / estimate / SMC + estimate / layers / SMC + layers, alternating (profiles/stream_layers_time.json)")
     ap.add_argument("--score", action="store_true", help="plain / SMC / estimate / SMC + estimate / score / SMC + score, alternating (profiles/stream_score_time.json)")
     ap.add_argument("--identity", action="store_true", help="plain / SMC / estimate / identity / SMC + estimate / SMC + identity / score / score + identity, alternating (profiles/stream_identity_time.json)")
+    ap.add_argument("--idf", action="store_true", help="score and score + IDF, each with and without SMC, alternating; idf_score() apart (profiles/stream_idf_time.json)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     ov, _, _, _ = config_inputs(2)
-    if args.identity:
+    if args.idf:
+        shapes = [dict(name="cfg2_batch_idf", **time_idf(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
+    elif args.identity:
         shapes = [dict(name="cfg2_batch_identity", **time_identity(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
     elif args.score:
         shapes = [dict(name="cfg2_batch_score", **time_score(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
