@@ -1439,6 +1439,64 @@ typedef struct SqairGruGatesBwdTest {
 } SqairGruGatesBwdTest;
 int sqair_gru_gates_bwd_test(SqairHandle* h, const SqairGruGatesBwdTest* t, void* stream);
 
+/* ---- the log-probability kernels, one launch each (test helpers) -----------------------------------------------------------------
+ * k_logprob (section H of the forward pass) and its adjoint k_logprob_bwd (H^T, the head of sqair_backward's reverse sweep), under
+ * the rules of the slot-loop entries above: caller-owned device buffers reach the two launchers UNCHANGED; dimensions, SqairConfig,
+ * record layout and every parameter offset are the handle's; the caller chooses B, T, the pstats pitch, the time source (t_row [R]
+ * per-row frame counters, or NULL: t_global / t_global0; frame f of row r has time t_row[r] + f) and which optional outputs exist.
+ * A refusal (-1: a NULL required pointer, B < 1, T < 1, ps_ld < 9 + 2 n_what or so large that the row no longer fits 150 KB of LDS,
+ * for the adjoint a frame that cannot be trained) carries the entry's name in sqair_last_error and launches nothing; otherwise the
+ * launcher's code, after a stream synchronise.  R = B * k_particles, M = R * N; records [frames][R][N][W] (columns:
+ * sqair_compact_test_layout); pstats [T][M][ps_ld] = the prior's raw statistics [logit | where_loc 4 | what_loc n_what |
+ * where_scale 4 | what_scale n_what]; spre [T][R][128] the where prior's conditioning pre-activation without the expected-steps
+ * row (required with rec_where_prior only); flat / flat_grad in the kernels' own layout (sqair_debug_padded_count floats).
+ *
+ * sqair_logprob_test (k_logprob, gen = NULL: the generation modes stay with sqair_forward).  READS, per (frame, row): of rec_p
+ *   WHERE, WHAT[0:n_what], PRES, LOGIT, WHERE_LOC, WHERE_SCALE, WHAT_LOC, WHAT_SCALE; of rec_d the same without LOGIT, plus PROB; of
+ *   rec_prev [T][R][N][W] (frame f: the merged records of f - 1) PRES, and under rw / guided only WHERE, WHAT, LOGIT;
+ *   pstats columns [0, 9 + 2 n_what) (the loc columns 1 .. 4 + n_what not under rw); spre and the where-prior parameters
+ *   (disc.rn.i2h, .h2h, .readout, .init_sample, row 4 + n_hidden of disc.rn.cond.w) with rec_where_prior; disc.steps_prior.*,
+ *   disc.step_prior_bias and (where the time is > 0) disc.step_prior_timestep_bias with the categorical step prior;
+ *   prop.cholesky_scale.  The row's records and statistics are staged whole, so every other word of them may hold anything, NaN
+ *   included; the fields of an ABSENT slot are read and multiplied by the zero mask: they must be finite.  WRITES qz, pz, disc_lp
+ *   [T][R] at frame f, and of `out` (optional, as every pointer in it) at frame t + f: the eight per-slot log-probs, prop_prob,
+ *   prop_pres, disc_pres [..][N], disc_prob [..][N + 1], prop / disc (prior) log-probs, step_log_prob, discrete_log_prob and the
+ *   two step counts; nothing else of `out` is touched. */
+typedef struct SqairLogprobTest {
+  int32_t B, T, t, t_global;
+  const int32_t* t_row;
+  const float* rec_p; const float* rec_d; const float* rec_prev;
+  const float* pstats; int32_t ps_ld;
+  const float* spre;
+  const float* flat;
+  float* qz; float* pz; float* disc_lp;
+  const SqairOutputs* out;
+} SqairLogprobTest;
+int sqair_logprob_test(SqairHandle* h, const SqairLogprobTest* t, void* stream);
+
+/* sqair_logprob_bwd_test (k_logprob_bwd): the adjoint of sum over (frame, row) of g_lw (pz - qz) + g_dl disc_lp.  READS what
+ *   k_logprob reads, with two differences: rec_m is [T + 1][R][N][W] (frame f reads rec_m[f]; only its z segment WHERE .. LOGIT is
+ *   staged, frame T not at all), and all fifteen small-parameter segments are staged whatever the flags (an unused one may hold NaN).
+ *   g_lw, g_dl [T][R].  ACCUMULATES (+=, float atomics, exact zeros skipped): d_rec_p in WHERE, WHAT[0:n_what], LOGIT, WHERE_LOC,
+ *   WHERE_SCALE, WHAT_LOC, WHAT_SCALE; d_rec_d in the same columns (its LOGIT holds the gradient of logit(PROB) through the
+ *   number-of-steps posterior); d_rec_m[f] in LOGIT (rw / guided: also of slots absent at f - 1, through the expected number of
+ *   steps) and WHERE / WHAT[0:n_what] (rw / guided), frame T untouched; flat_grad inside the fifteen segments prop.cholesky_scale,
+ *   disc.rn.{readout, i2h, h2h}.{w, b}, row 4 + n_hidden of disc.rn.cond.w, disc.rn.init_sample, disc.steps_prior.{l0, l1}.{w, b},
+ *   disc.step_prior_bias, disc.step_prior_timestep_bias and nowhere else.  WRITES (=): d_pstats [T][M][ps_ld] over the full pitch,
+ *   zeros outside the used columns (rw: the loc columns are zeros too); d_spre [T][R][128], zeros without rec_where_prior.  Masks
+ *   multiply, they do not select: an absent slot's fields must be finite. */
+typedef struct SqairLogprobBwdTest {
+  int32_t B, T, t_global0, ps_ld;
+  const int32_t* t_row;
+  const float* rec_p; const float* rec_d; const float* rec_m;
+  const float* pstats; const float* spre;
+  const float* g_lw; const float* g_dl;
+  float* d_rec_p; float* d_rec_d; float* d_rec_m;
+  float* d_pstats; float* d_spre;
+  const float* flat; float* flat_grad;
+} SqairLogprobBwdTest;
+int sqair_logprob_bwd_test(SqairHandle* h, const SqairLogprobBwdTest* t, void* stream);
+
 /* Which kernel family the two dense launchers chose, counted on the host per process (launches issued or captured so far), at the
  * point of the choice: out[0:n] receives the first n of the SQAIR_DENSE_ROUTES counts below, the return value is their number.
  *   forward (sq_launch_linear):  0 split-K (k_linear) | 1 32 x 32 tiles (k_linear_t2) | 2 k_linear_rows | 3 k_linear_mt |

@@ -321,6 +321,18 @@ class SqairGruGatesBwdTest(C.Structure):
                         "p dup_r", "i dupr_ld"])
 
 
+class SqairLogprobTest(C.Structure):
+    """One launch of k_logprob over T frames (include/sqair_hip.h: sqair_logprob_test); device addresses, handed on unchanged."""
+    _fields_ = _fields(["i B", "i T", "i t", "i t_global", "p t_row", "p rec_p", "p rec_d", "p rec_prev", "p pstats", "i ps_ld", "p spre",
+                        "p flat", "p qz", "p pz", "p disc_lp", "p out"])   # out: the address of a SqairOutputs, or NULL
+
+
+class SqairLogprobBwdTest(C.Structure):
+    """One launch of k_logprob_bwd over T frames (include/sqair_hip.h: sqair_logprob_bwd_test)."""
+    _fields_ = _fields(["i B", "i T", "i t_global0", "i ps_ld", "p t_row", "p rec_p", "p rec_d", "p rec_m", "p pstats", "p spre", "p g_lw",
+                        "p g_dl", "p d_rec_p", "p d_rec_d", "p d_rec_m", "p d_pstats", "p d_spre", "p flat", "p flat_grad"])
+
+
 # sqair_debug_dense_routes: the families of the two dense launchers, in the order include/sqair_hip.h documents
 DENSE_ROUTES = ("fwd_splitk", "fwd_t2", "fwd_rows", "fwd_mt", "fwd_lds", "fwd_big_2x2", "fwd_big_3x2", "fwd_big_3x3", "fwd_big_4x2",
                 "dx_nch1", "dx_nch2", "dx_nch3", "dx_nch4", "dx_nch5", "dx_nch6", "dx_nch7", "dx_nch8", "dx_nch9", "dx_nch12", "dx_nch18",
@@ -456,6 +468,8 @@ _PROTOS = {
     "sqair_crop_chain_bwd_test": (C.c_int, [C.c_void_p, C.POINTER(SqairCropChainBwdTest), C.c_void_p]),
     "sqair_where_param_grads_test": (C.c_int, [C.c_void_p, C.POINTER(SqairWhereParamGradsTest), C.c_void_p]),
     "sqair_gru_gates_bwd_test": (C.c_int, [C.c_void_p, C.POINTER(SqairGruGatesBwdTest), C.c_void_p]),
+    "sqair_logprob_test": (C.c_int, [C.c_void_p, C.POINTER(SqairLogprobTest), C.c_void_p]),
+    "sqair_logprob_bwd_test": (C.c_int, [C.c_void_p, C.POINTER(SqairLogprobBwdTest), C.c_void_p]),
     "sqair_debug_dense_routes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
     "sqair_debug_linear_time": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_void_p]),

@@ -1340,6 +1340,9 @@ __global__ __launch_bounds__(256) void k_logprob_bwd(const LogprobBwdArgs a, con
   float d_e = 0.0f;
   if (lane < N) {
     // q_num = log J_n, J from p_j = sigmoid(logit_j): d log J_n / d logit_j = (1 - p_j) for j < n, -p_n for j = n < N
+    // (the gradient of the UNCLIPPED logarithm.  Below k_logprob's clip J_n < 1e-16 the reference's clip_preserve passes the gradient
+    // of J_n straight through the clip, d J_n / 1e-16, where this is d J_n / J_n: different by design, and out of reach -- J_n is the
+    // probability of the count that was sampled.  tests/test_logprob_kernels.py keeps J_n >= 1e-12 and does not test below the clip.)
     const int j = lane;
     const float coef = -gw + gd;
     const float pj = rd_s[j * RW + rec::PROB];

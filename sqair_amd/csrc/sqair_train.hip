@@ -1050,6 +1050,71 @@ extern "C" int sqair_gru_gates_bwd_test(SqairHandle* h, const SqairGruGatesBwdTe
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The log-probability kernels on raw device buffers (unit-test entries, tests/test_logprob_kernels.py): k_logprob as section H of
+// the forward pass launches it, k_logprob_bwd as H^T of sq_backward does.  The caller's pointers, the pstats pitch and the time
+// source reach sq_launch_logprob / sq_launch_logprob_bwd unchanged; Dims, POff and SqairConfig are the handle's.
+// ------------------------------------------------------------------------------------------------
+extern "C" int sqair_logprob_test(SqairHandle* h, const SqairLogprobTest* t, void* stream) {
+  static const char* who = "sqair_logprob_test";
+  if (!h) return -1;
+  if (!t) return sq_refuse(h, who, "no description");
+  if (t->B < 1) return sq_refuse(h, who, "B < 1");
+  if (t->T < 1) return sq_refuse(h, who, "T < 1");
+  if (t->t < 0) return sq_refuse(h, who, "t < 0");
+  if (!t->rec_p || !t->rec_d || !t->rec_prev || !t->pstats || !t->flat || !t->qz || !t->pz || !t->disc_lp)
+    return sq_refuse(h, who, "a required pointer is NULL");
+  if (h->cfg.rec_where_prior && !t->spre) return sq_refuse(h, who, "a required pointer is NULL (spre: the recurrent where prior reads it)");
+  const Dims d = make_dims(h->cfg, t->B);
+  if (t->ps_ld < 9 + 2 * d.nw) return sq_refuse(h, who, "a pitch is smaller than the width");
+  // (the launcher's own expression: what the kernel stages per row)
+  const size_t shm = ((size_t)3 * d.N * rec::W + (size_t)d.N * t->ps_ld + 128 + 128 + 516 + 20 + 40 + 4 + 20 + 11 * (d.N + 1) + 2 * (d.N + 1) + 16) *
+                     sizeof(float);
+  if (shm > 150 * 1024) return sq_refuse(h, who, "a pitch asks for more than 150 KB of LDS");
+  hipStream_t s = (hipStream_t)stream;
+  LogprobArgs la; memset(&la, 0, sizeof(la));
+  la.rec_p = t->rec_p; la.rec_d = t->rec_d; la.rec_prev = t->rec_prev; la.pstats = t->pstats; la.ps_ld = t->ps_ld; la.spre = t->spre;
+  la.flat = t->flat; la.t_global = t->t_global; la.t_row = t->t_row; la.t = t->t; la.n_frames = t->T; la.qz = t->qz; la.pz = t->pz;
+  la.disc_lp = t->disc_lp; la.gen = nullptr; la.cfg = h->cfg;
+  if (t->out) la.out = *t->out;
+  const int rc = sq_launch_logprob(la, h->po, d, s);
+  if (rc != 0) { sq_set_error(h, std::string(who) + ": launch refused (dynamic LDS limit)"); return rc; }
+  SQ_CHECK_HIP(hipGetLastError());
+  SQ_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int sqair_logprob_bwd_test(SqairHandle* h, const SqairLogprobBwdTest* t, void* stream) {
+  static const char* who = "sqair_logprob_bwd_test";
+  if (!h) return -1;
+  if (!t) return sq_refuse(h, who, "no description");
+  if (t->B < 1) return sq_refuse(h, who, "B < 1");
+  if (t->T < 1) return sq_refuse(h, who, "T < 1");
+  if (!t->rec_p || !t->rec_d || !t->rec_m || !t->pstats || !t->g_lw || !t->g_dl || !t->d_rec_p || !t->d_rec_d || !t->d_rec_m || !t->d_pstats ||
+      !t->d_spre || !t->flat || !t->flat_grad)
+    return sq_refuse(h, who, "a required pointer is NULL");
+  if (h->cfg.rec_where_prior && !t->spre) return sq_refuse(h, who, "a required pointer is NULL (spre: the recurrent where prior reads it)");
+  const Dims d = sq_train_dims(h, t->B);
+  if (t->ps_ld < 9 + 2 * d.nw) return sq_refuse(h, who, "a pitch is smaller than the width");
+  {  // (sq_launch_logprob_bwd's own expression: the row's records, statistics and small parameters with their gradients)
+    const size_t small = 738 + 13 * (size_t)(d.N + 1);
+    const size_t shm = (4 * (size_t)d.N * rec::W + 2 * (size_t)d.N * rec::ZW + 2 * (size_t)d.N * t->ps_ld + 2 * small) * sizeof(float);
+    if (shm > 150 * 1024) return sq_refuse(h, who, "a pitch asks for more than 150 KB of LDS");
+  }
+  if (!sq_trainable_frame(h)) return sq_refuse(h, who, std::string(sqair_last_error(h)));
+  hipStream_t s = (hipStream_t)stream;
+  LogprobBwdArgs la; memset(&la, 0, sizeof(la));
+  la.rec_p = t->rec_p; la.rec_d = t->rec_d; la.rec_m = t->rec_m; la.pstats = t->pstats; la.ps_ld = t->ps_ld; la.spre = t->spre;
+  la.g_lw = t->g_lw; la.g_dl = t->g_dl; la.d_rec_p = t->d_rec_p; la.d_rec_d = t->d_rec_d; la.d_rec_m = t->d_rec_m;
+  la.d_pstats = t->d_pstats; la.d_spre = t->d_spre; la.flat = t->flat; la.flat_grad = t->flat_grad; la.t_global0 = t->t_global0;
+  la.t_row = t->t_row; la.cfg = h->cfg;
+  const int rc = sq_launch_logprob_bwd(la, h->po, d, t->T, s);
+  if (rc != 0) { sq_set_error(h, std::string(who) + ": launch refused (dynamic LDS limit)"); return rc; }
+  SQ_CHECK_HIP(hipGetLastError());
+  SQ_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
 extern "C" int sqair_capture_begin(SqairHandle* h, void* stream) {
   if (!h) return -1;
   SQ_CHECK_HIP(hipStreamBeginCapture((hipStream_t)stream, hipStreamCaptureModeThreadLocal));

@@ -10,7 +10,8 @@ piece therefore takes the tape values and inverts the activation to obtain the l
 reference are given the same fp32 tape.  tests/test_slot_adjoint_ref.py pins all of it on the CPU: against SqairOracle.discovery_core /
 propagation_core, against central differences, and the Cholesky index order against oracle.fill_triangular.
 
-The metric and the sentinel helpers at the end are shared with the GPU tests (and meant for the unit tests of k_logprob_bwd to come)."""
+The metric and the sentinel helpers at the end are shared with the GPU tests, those of the log-probability kernels included
+(tests/logprob_ref.py, tests/test_logprob_kernels.py)."""
 import numpy as np
 import torch
 

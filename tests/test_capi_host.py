@@ -270,7 +270,9 @@ def test_slot_adjoint_test_entries_refuse_host_side():
     """sqair_slot_tail_bwd_test / sqair_crop_chain_bwd_test / sqair_where_param_grads_test / sqair_gru_gates_bwd_test
     (tests/test_slot_adjoint_kernels.py drives them on the GPU): exported by both builds under the unchanged ABI version, and a NULL
     required pointer, a slot out of range, a pitch below the width and a frame that cannot be trained are refused with the entry's
-    name in the error text before any HIP call (`buf` stands for every device buffer: nothing reads it)."""
+    name in the error text before any HIP call (`buf` stands for every device buffer: nothing reads it).  The same for
+    sqair_logprob_test / sqair_logprob_bwd_test (tests/test_logprob_kernels.py): a NULL required pointer, B < 1, T < 1, a pstats pitch
+    below 9 + 2 n_what or beyond the LDS."""
     buf = (C.c_float * 16)()
     for path in (_capi.LIB_PATH, _capi.WIDE_LIB_PATH):
         lib = _capi.lib(path)
@@ -330,6 +332,25 @@ def test_slot_adjoint_test_entries_refuse_host_side():
                 assert b"pitch" in refused("sqair_gru_gates_bwd_test", G, **dict(gru, **{ld: v}))
             assert b"pitch" in refused("sqair_gru_gates_bwd_test", G, **dict(gru, dup_h_off=512, dupz_ld=767))
             assert b"rows" in refused("sqair_gru_gates_bwd_test", G, **dict(gru, rows=0))
+            # the log-probability kernels' entries (tests/test_logprob_kernels.py): the same rules
+            for fn in ("sqair_logprob_test", "sqair_logprob_bwd_test"):
+                assert getattr(lib, fn)(None, None, None) == -1
+                assert getattr(lib, fn)(h, None, None) == -1 and lib.sqair_last_error(h).startswith(fn.encode())
+            LF, LB = _capi.SqairLogprobTest, _capi.SqairLogprobBwdTest
+            fwd = dict(B=2, T=3, t=2, t_global=0, ps_ld=112)
+            for p in ("rec_p", "rec_d", "rec_prev", "pstats", "spre", "flat", "qz", "pz", "disc_lp"):
+                assert b"NULL" in refused("sqair_logprob_test", LF, **dict(fwd, **{p: None}))
+            bwd = dict(B=2, T=3, t_global0=0, ps_ld=112)
+            for p in ("rec_p", "rec_d", "rec_m", "pstats", "spre", "g_lw", "g_dl", "d_rec_p", "d_rec_d", "d_rec_m", "d_pstats", "d_spre", "flat",
+                      "flat_grad"):
+                assert b"NULL" in refused("sqair_logprob_bwd_test", LB, **dict(bwd, **{p: None}))
+            for fn, cls, ok in (("sqair_logprob_test", LF, fwd), ("sqair_logprob_bwd_test", LB, bwd)):
+                assert b"B < 1" in refused(fn, cls, **dict(ok, B=0))
+                assert b"T < 1" in refused(fn, cls, **dict(ok, T=0))
+                assert b"pitch" in refused(fn, cls, **dict(ok, ps_ld=9 + 2 * 50 - 1))        # below [logit | 4 + n_what | 4 + n_what]
+                assert b"LDS" in refused(fn, cls, **dict(ok, ps_ld=1 << 20))                  # a row that no longer fits the LDS
+            assert b"t < 0" in refused("sqair_logprob_test", LF, **dict(fwd, t=-1))
+            assert b"200 x 200" in refused("sqair_logprob_bwd_test", LB, handle=big, **bwd)  # a configuration that cannot be trained
         finally:
             lib.sqair_destroy(h)
             lib.sqair_destroy(big)
@@ -344,7 +365,9 @@ def test_dense_test_structs_have_the_header_layout(repo_root, tmp_path):
                "SqairDxGru": _capi.SqairDxGru, "SqairDxTest": _capi.SqairDxTest,
                # the slot loop's element-wise adjoints (sqair_slot_tail_bwd_test and its three neighbours)
                "SqairSlotTailBwdTest": _capi.SqairSlotTailBwdTest, "SqairCropChainBwdTest": _capi.SqairCropChainBwdTest,
-               "SqairWhereParamGradsTest": _capi.SqairWhereParamGradsTest, "SqairGruGatesBwdTest": _capi.SqairGruGatesBwdTest}
+               "SqairWhereParamGradsTest": _capi.SqairWhereParamGradsTest, "SqairGruGatesBwdTest": _capi.SqairGruGatesBwdTest,
+               # the log-probability kernels (sqair_logprob_test, sqair_logprob_bwd_test)
+               "SqairLogprobTest": _capi.SqairLogprobTest, "SqairLogprobBwdTest": _capi.SqairLogprobBwdTest}
     lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "sqair_hip.h"', "int main(void) {"]
     for name, cls in structs.items():
         lines.append('  printf("{0} %zu\\n", sizeof({0}));'.format(name))
