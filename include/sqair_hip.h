@@ -1000,8 +1000,8 @@ int sqair_st_crop(SqairHandle* h, const float* img, const float* where_logits, c
 int sqair_st_insert_loglik(SqairHandle* h, const float* glimpse, const float* where_logits,
                            const float* presence, const float* img, const float* mean_img,
                            float* canvas, float* data_ll, int B, void* stream);
-/* y = act(x W + b) on the packed MFMA path with an ad-hoc pack of W [K,N] (test helper):
- * act 0 none, 1 elu, 2 tanh, 3 sigmoid, 4 softplus+0.01. */
+/* y = act(x W + b) on the packed MFMA path, W [K,N] packed by the planner that packs the handle's layers (test helper; so
+ * are the packs of the test helpers below): act 0 none, 1 elu, 2 tanh, 3 sigmoid, 4 softplus+0.01. */
 int sqair_linear_test(SqairHandle* h, const float* x, const float* w, const float* b, float* y, int M,
                       int Kdim, int Ndim, int act, void* scratch, int64_t scratch_bytes, void* stream);
 /* snt.GRU step through the two fused MFMA launches the forward pass uses:

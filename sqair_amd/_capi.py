@@ -485,6 +485,7 @@ _PROTOS = {
                                     C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "sqair_debug_plan": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                    C.POINTER(C.c_int)]),
+    "sqair_debug_plan_t": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
 }
 
 # what include/sqair_hip.h declares: everything but the measurement helpers -- and the one read-out among them that it documents

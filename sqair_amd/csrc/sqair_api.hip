@@ -1,6 +1,7 @@
 // libsqair_hip.so — handle, parameter inventory, weight packing plan, and the launch sequence of the
 // SQAIR forward pass.  Host code only; kernels live in sqair_linear.hip / sqair_glue.hip; the carried state and the forecast in
-// sqair_state.hip, the lane answers in sqair_lane_api.hip.
+// sqair_state.hip, the lane answers in sqair_lane_api.hip, the packed layout and its planners in sqair_pack.hip, the dense
+// family's unit-test and measurement entries in sqair_dense_test.hip.
 //
 // The launch sequence of one frame restates SQAIRTimestep + AIRDecoder (reference:
 // sqair/sqair_modules.py:446-582, sqair/core.py:164-359, sqair/propagate.py:68-184,
@@ -215,12 +216,6 @@ static void build_inventory(SqairHandle* h) {
 // ------------------------------------------------------------------------------------------------
 // packing plan: for every packed weight element the index of its source in the flat buffer
 // ------------------------------------------------------------------------------------------------
-typedef std::vector<int> RowMap;  // per segment position: source row or -1
-static RowMap rm_range(int start, int n) {
-  RowMap r(n);
-  for (int i = 0; i < n; ++i) r[i] = start + i;
-  return r;
-}
 static RowMap rm_none(int n) { return RowMap(n, -1); }
 // z-record segment (rec::ZW wide): where rows, what rows, presence row (-1 = unused)
 static RowMap rm_zrec(int nw, int where0, int what0, int pres_row) {
@@ -242,63 +237,27 @@ struct ColBlock {
   std::string bias_a, bias_b;  // bias vector names ("" = none); element col0 + j
 };
 
+// The names resolved to flat offsets, the (column block, segment) entries of the weight-gradient scatter recorded (sqair_train.hip),
+// and the layer appended to the plan in the one packed layout (sqair_pack.h).
 static void build_layer(SqairHandle* h, LayerId id, const std::vector<int>& seg_width, const std::vector<ColBlock>& blocks) {
-  PackedLayer& L = h->layers[id];
-  L.seg_width = seg_width;
-  L.kc = 0;
-  for (int w : seg_width) L.kc += (w + 15) / 16;
-  L.N = 0;
-  for (const ColBlock& b : blocks) L.N += b.ncols;
-  L.nt = (L.N + 15) / 16;
-  L.w_off = h->packed_w;
-  L.b_off = h->packed_b;
-  const int64_t nel = (int64_t)L.nt * L.kc * 256;
-  h->widx.resize(h->packed_w + nel, -1);
-  h->bidx_a.resize(h->packed_b + L.nt * 16, -1);
-  h->bidx_b.resize(h->packed_b + L.nt * 16, -1);
+  std::vector<PackBlock> pb;
   int n0 = 0;
   for (const ColBlock& b : blocks) {
-    if ((int)b.seg.size() != (int)seg_width.size()) {
-      fprintf(stderr, "sqair: layer %d: segment count mismatch\n", (int)id);
-      abort();
+    PackBlock q{b.ncols, b.col0};
+    for (size_t sgi = 0; sgi < b.seg.size(); ++sgi) {
+      const SegSrc& src = b.seg[sgi];
+      if (src.w.empty()) { q.seg.push_back({}); continue; }
+      h->wg[id].push_back({n0, b.ncols, b.col0, (int)sgi, src.w, (int64_t)h->rm_pool.size()});
+      h->rm_pool.insert(h->rm_pool.end(), src.rows.begin(), src.rows.end());
+      q.seg.push_back({P(h, src.w), PC(h, src.w), src.rows});
     }
-    for (size_t sgi = 0; sgi < seg_width.size(); ++sgi)
-      if (!b.seg[sgi].w.empty()) {
-        h->wg[id].push_back({n0, b.ncols, b.col0, (int)sgi, b.seg[sgi].w, (int64_t)h->rm_pool.size()});
-        h->rm_pool.insert(h->rm_pool.end(), b.seg[sgi].rows.begin(), b.seg[sgi].rows.end());
-      }
     if (!b.bias_a.empty() || !b.bias_b.empty()) h->bg[id].push_back({n0, b.ncols, b.col0, b.bias_a, b.bias_b});
-    for (int j = 0; j < b.ncols; ++j) {
-      const int n = n0 + j;
-      const int tile = n / 16, ln = n % 16;
-      if (!b.bias_a.empty()) h->bidx_a[L.b_off + n] = (int)(P(h, b.bias_a) + b.col0 + j);
-      if (!b.bias_b.empty()) h->bidx_b[L.b_off + n] = (int)(P(h, b.bias_b) + b.col0 + j);
-      int cbase = 0;
-      for (size_t s = 0; s < seg_width.size(); ++s) {
-        const SegSrc& src = b.seg[s];
-        const int nch = (seg_width[s] + 15) / 16;
-        if (!src.w.empty()) {
-          if ((int)src.rows.size() != seg_width[s]) {
-            fprintf(stderr, "sqair: layer %d seg %zu: rowmap %zu != width %d\n", (int)id, s, src.rows.size(), seg_width[s]);
-            abort();
-          }
-          const int64_t woff = P(h, src.w);
-          const int ldw = PC(h, src.w);
-          for (int k = 0; k < seg_width[s]; ++k) {
-            if (src.rows[k] < 0) continue;
-            const int c = cbase + k / 16, kin = k % 16;
-            const int lane = (kin / 4) * 16 + ln, comp = kin % 4;
-            h->widx[L.w_off + (((int64_t)tile * L.kc + c) * 64 + lane) * 4 + comp] =
-                (int)(woff + (int64_t)src.rows[k] * ldw + b.col0 + j);
-          }
-        }
-        cbase += nch;
-      }
-    }
+    if (!b.bias_a.empty()) q.bias_a = P(h, b.bias_a);
+    if (!b.bias_b.empty()) q.bias_b = P(h, b.bias_b);
+    pb.push_back(q);
     n0 += b.ncols;
   }
-  h->packed_w += nel;
-  h->packed_b += L.nt * 16;
+  h->layers[id] = sq_plan_layer(h->plan, (int)id, seg_width, pb);
 }
 
 static ColBlock cb1(int ncols, int col0, const std::string& w, const RowMap& rows, const std::string& ba = "",
@@ -314,8 +273,7 @@ static ColBlock cb1(int ncols, int col0, const std::string& w, const RowMap& row
 
 static void build_plan(SqairHandle* h) {
   const SqairConfig& c = h->cfg;
-  h->packed_w = 256;  // leading zero block: one K-chunk of zero weights for the ragged tail of the chunk loop
-  h->widx.assign(256, -1);
+  h->plan = PackPlan();   // (starts with the leading zero block)
   const int P_ = c.img_h * c.img_w, nh = c.n_hidden, nw = c.n_what;
   const int G2 = c.glimpse_size * c.glimpse_size, nsp = nh / 2;
   auto simple = [&](LayerId id, const std::string& name, int fin, int fout, int row0 = 0, bool bias = true) {
@@ -548,34 +506,11 @@ static void build_plan(SqairHandle* h) {
   simple(L_DEC2, "dec.l2", nh, G2);
 }
 
-// Transposed packs for the backward pass: dA_cat [M, 16 kc] = dPre [M, N] W^T with the same zero padding, so the
-// gradient of a z-record segment comes out in record order.  Built from the forward plan element by element.
+// Transposed packs for the backward pass (sq_plan_layer_T), behind the forward layers in the same plan.
 static void build_plan_T(SqairHandle* h) {
-  for (int id = 0; id < L_COUNT; ++id) {
-    if (id == L_WHAT_HEAD_I || id == L_PROP_HEADS_I) continue;   // forward-only packs: no dX reads them, layersT[id] stays empty
-    const PackedLayer& L = h->layers[id];
-    PackedLayer& T = h->layersT[id];
-    T.kc = L.nt;            // reduction over the (padded) forward outputs
-    T.nt = L.kc;            // one output tile per forward K-chunk
-    T.N = L.kc * 16;
-    T.seg_width = {L.N};
-    T.w_off = h->packed_w;
-    T.b_off = h->packed_b;
-    const int64_t nel = (int64_t)T.nt * T.kc * 256;
-    h->widx.resize(h->packed_w + nel, -1);
-    h->bidx_a.resize(h->packed_b + T.nt * 16, -1);
-    h->bidx_b.resize(h->packed_b + T.nt * 16, -1);
-    for (int k = 0; k < L.kc * 16; ++k)
-      for (int n = 0; n < L.nt * 16; ++n) {
-        const int64_t f = L.w_off + ((((int64_t)(n / 16) * L.kc + k / 16) * 64) + ((k % 16) / 4) * 16 + n % 16) * 4 + k % 4;
-        const int src = h->widx[f];
-        if (src < 0) continue;
-        const int64_t t = T.w_off + ((((int64_t)(k / 16) * T.kc + n / 16) * 64) + ((n % 16) / 4) * 16 + k % 16) * 4 + n % 4;
-        h->widx[t] = src;
-      }
-    h->packed_w += nel;
-    h->packed_b += T.nt * 16;
-  }
+  for (int id = 0; id < L_COUNT; ++id)
+    if (id != L_WHAT_HEAD_I && id != L_PROP_HEADS_I)   // forward-only packs: no dX reads them, layersT[id] stays empty
+      h->layersT[id] = sq_plan_layer_T(h->plan, h->plan, h->layers[id]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -710,9 +645,9 @@ extern "C" int sqair_pack_params(SqairHandle* h, const float* flat, void* packed
   if (h->padded && h->plan_uploaded_ptr != packed)
     SQ_CHECK_HIP(hipMemcpyAsync(ibase + pl.um, h->u2i.data(), h->u2i.size() * 4, hipMemcpyHostToDevice, s));
   if (h->plan_uploaded_ptr != packed) {
-    SQ_CHECK_HIP(hipMemcpyAsync(ibase + pl.wi, h->widx.data(), h->packed_w * 4, hipMemcpyHostToDevice, s));
-    SQ_CHECK_HIP(hipMemcpyAsync(ibase + pl.ba, h->bidx_a.data(), h->packed_b * 4, hipMemcpyHostToDevice, s));
-    SQ_CHECK_HIP(hipMemcpyAsync(ibase + pl.bb, h->bidx_b.data(), h->packed_b * 4, hipMemcpyHostToDevice, s));
+    SQ_CHECK_HIP(hipMemcpyAsync(ibase + pl.wi, h->plan.widx.data(), h->plan.packed_w() * 4, hipMemcpyHostToDevice, s));
+    SQ_CHECK_HIP(hipMemcpyAsync(ibase + pl.ba, h->plan.bidx_a.data(), h->plan.packed_b() * 4, hipMemcpyHostToDevice, s));
+    SQ_CHECK_HIP(hipMemcpyAsync(ibase + pl.bb, h->plan.bidx_b.data(), h->plan.packed_b() * 4, hipMemcpyHostToDevice, s));
     SQ_CHECK_HIP(hipMemcpyAsync(ibase + pl.rm, h->rm_pool.data(), h->rm_pool.size() * 4, hipMemcpyHostToDevice, s));
     SQ_CHECK_HIP(hipStreamSynchronize(s));
     h->plan_uploaded_ptr = packed;
@@ -723,8 +658,8 @@ extern "C" int sqair_pack_params(SqairHandle* h, const float* flat, void* packed
               (const int*)(ibase + pl.um), h->n_uparams);
     flat = base + pl.fi;
   }
-  sq_launch_pack(flat, base + pl.w, ibase + pl.wi, h->packed_w, s);
-  sq_launch_pack_bias(flat, base + pl.b, ibase + pl.ba, ibase + pl.bb, h->packed_b, s);
+  sq_launch_pack(flat, base + pl.w, ibase + pl.wi, h->plan.packed_w(), s);
+  sq_launch_pack_bias(flat, base + pl.b, ibase + pl.ba, ibase + pl.bb, h->plan.packed_b(), s);
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -1682,30 +1617,6 @@ extern "C" int sqair_check_scales(SqairHandle* h, void* workspace, int T, int B,
   return 0;
 }
 
-// Capture on this stream, scoped: on every way out that did not hand_over() the graph and its executable, the destructor ends a
-// capture still open (a stream left capturing fails every later call on it) and destroys what was made, the two timing events of
-// the measurement helpers included.  (sqair_capture_begin / _end are paired by the caller and do not use this.)
-struct SqCapture {
-  hipStream_t s;
-  bool open = false;
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  explicit SqCapture(hipStream_t stream) : s(stream) {}
-  SqCapture(const SqCapture&) = delete;
-  hipError_t begin() { const hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal); open = e == hipSuccess; return e; }
-  hipError_t end() { open = false; return hipStreamEndCapture(s, &graph); }
-  hipError_t instantiate() { return hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0); }
-  hipError_t events() { const hipError_t e = hipEventCreate(&ev[0]); return e != hipSuccess ? e : hipEventCreate(&ev[1]); }
-  void hand_over(hipGraph_t* g, hipGraphExec_t* x) { *g = graph; *x = exec; graph = nullptr; exec = nullptr; }
-  ~SqCapture() {
-    if (open) (void)hipStreamEndCapture(s, &graph);
-    if (exec) (void)hipGraphExecDestroy(exec);
-    if (graph) (void)hipGraphDestroy(graph);
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-  }
-};
-
 extern "C" int sqair_forward(SqairHandle* h, const float* flat_params, const void* packed, const float* obs,
                              const float* noise, int T, int B, int t_offset, const SqairOutputs* out, void* workspace,
                              int64_t workspace_bytes, void* stream) {
@@ -1829,271 +1740,6 @@ extern "C" int sqair_st_insert_loglik(SqairHandle* h, const float* glimpse, cons
   return 0;
 }
 
-// ad-hoc pack of a dense [K,N] matrix on the host plan path: scratch = [idx int32 | packed w | packed b | bidx]
-static int adhoc_layer(SqairHandle* h, int Kdim, int Ndim, PackedLayer* L) {
-  L->seg_width = {Kdim};
-  L->kc = (Kdim + 15) / 16;
-  L->nt = (Ndim + 15) / 16;
-  L->N = Ndim;
-  L->w_off = 0;
-  L->b_off = 0;
-  (void)h;
-  return 0;
-}
-
-// fills idx for a dense [K, N] row-major matrix located at flat offset `woff`, columns col0..col0+ncols of a
-// matrix with leading dimension ldw, into packed columns n0.. of a layer with `kc` chunks, segment chunk base cbase
-static void adhoc_fill(std::vector<int>& idx, int kc, int cbase, int n0, int ncols, int Kdim, int64_t woff, int ldw, int col0) {
-  for (int j = 0; j < ncols; ++j) {
-    const int n = n0 + j, tile = n / 16, ln = n % 16;
-    for (int k = 0; k < Kdim; ++k) {
-      const int cch = cbase + k / 16, kin = k % 16;
-      const int lane = (kin / 4) * 16 + ln, comp = kin % 4;
-      idx[(((int64_t)tile * kc + cch) * 64 + lane) * 4 + comp] = (int)(woff + (int64_t)k * ldw + col0 + j);
-    }
-  }
-}
-
-// the same for the TRANSPOSED layer of a dense forward matrix W [Kdim, Ndim] at flat offset 0: Kdim output columns, reduction over
-// the Ndim forward outputs, `kc` = ceil(Ndim / 16) chunks
-static void adhoc_fill_transposed(std::vector<int>& idx, int kc, int Kdim, int Ndim) {
-  for (int j = 0; j < Kdim; ++j) {       // output column j of the transposed layer = input j of the forward layer
-    const int tile = j / 16, ln = j % 16;
-    for (int kk = 0; kk < Ndim; ++kk) {  // reduction index = forward output kk
-      const int cch = kk / 16, kin = kk % 16;
-      const int lane = (kin / 4) * 16 + ln, comp = kin % 4;
-      idx[(((int64_t)tile * kc + cch) * 64 + lane) * 4 + comp] = j * Ndim + kk;  // W[j][kk]
-    }
-  }
-}
-
-// What the dense unit entry points time after their one checked launch: nothing (sqair_linear_test), the launch `reps` times back to
-// back (sqair_debug_linear_time), or `nodes` launches, dependent or not, as one HIP graph replayed `reps` times (..._graph_time)
-struct LinearTiming { int reps = 0, nodes = 0; bool dependent = false; };
-static int sq_linear_test(SqairHandle* h, const float* x, const float* wmat, const float* b, float* y, int M, int Kdim, int Ndim, int act,
-                          void* scratch, int64_t scratch_bytes, const LinearTiming& tm, float* us_out, void* stream) {
-  if (!h || !x || !wmat || !y || !scratch) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  PackedLayer L;
-  adhoc_layer(h, Kdim, Ndim, &L);
-  const int64_t nel = (int64_t)L.nt * L.kc * 256, nb = L.nt * 16;
-  const int kpad = (Kdim + 3) & ~3;
-  if (scratch_bytes < (2 * nel + 2 * nb + 256 + (int64_t)M * kpad) * 4) { sq_set_error(h, "sqair_linear_test: scratch too small"); return -1; }
-  std::vector<int> idx(nel, -1), bidx(nb, -1);
-  adhoc_fill(idx, L.kc, 0, 0, Ndim, Kdim, 0, Ndim, 0);
-  for (int n = 0; n < Ndim; ++n) bidx[n] = b ? n : -1;
-  int* d_idx = (int*)scratch;
-  float* d_w = (float*)scratch + nel;
-  float* d_b = d_w + nel;
-  int* d_bidx = (int*)(d_b + nb);
-  float* d_zero = (float*)(d_bidx + nb);
-  float* d_x = d_zero + 256;  // A-operand contract: rows padded to a multiple of 4 floats, finite
-  SQ_CHECK_HIP(hipMemcpyAsync(d_idx, idx.data(), nel * 4, hipMemcpyHostToDevice, s));
-  SQ_CHECK_HIP(hipMemcpyAsync(d_bidx, bidx.data(), nb * 4, hipMemcpyHostToDevice, s));
-  SQ_CHECK_HIP(hipMemsetAsync(d_zero, 0, (256 + (size_t)M * kpad) * 4, s));
-  SQ_CHECK_HIP(hipMemcpy2DAsync(d_x, (size_t)kpad * 4, x, (size_t)Kdim * 4, (size_t)Kdim * 4, M, hipMemcpyDeviceToDevice, s));
-  SQ_CHECK_HIP(hipStreamSynchronize(s));
-  sq_launch_pack(wmat, d_w, d_idx, nel, s);
-  if (b) sq_launch_pack(b, d_b, d_bidx, nb, s);
-  else SQ_CHECK_HIP(hipMemsetAsync(d_b, 0, nb * 4, s));
-  Lin l;
-  l.seg(d_x, kpad, Kdim).out(y, Ndim).act(act);
-  l.a.wp = d_w; l.a.wzero = d_zero; l.a.bias = d_b; l.a.M = M; l.a.N = Ndim;
-  if (sq_launch_linear(l.a, L, s) != 0) { sq_set_error(h, "sqair_linear_test: A-operand contract violated"); return -5; }
-  SQ_CHECK_HIP(hipGetLastError());
-  SQ_CHECK_HIP(hipStreamSynchronize(s));
-  if (tm.reps < 1) return 0;
-  SqCapture cap(s);   // (the events of both timed modes; the graph of the second)
-  float ms = 0.0f;
-  if (tm.nodes > 0) {
-    // `nodes` launches of this layer captured as ONE HIP graph -- the same launch over and over (no data dependence), or
-    // (dependent) every launch reading what the previous one wrote -- and the graph replayed `reps` times between two HIP events:
-    // time per graph NODE (kernel + the dependent-dispatch boundary), on whatever build of the library this is.  The figure
-    // bench.py's timeline calls the SLOT of a dense launch, measured without the stamps.
-    // dependent: every launch reads what the previous one wrote -- IN PLACE, input columns [0, K) and output columns [0, N) of
-    // one buffer of pitch max(K, N) behind the other scratch (a race between the workgroups of a row tile: the values mean
-    // nothing, tanh keeps them finite; what is timed is a launch whose operand comes out of the previous launch's stores)
-    Lin l2;
-    if (tm.dependent) {
-      const int ldz = (std::max(kpad, Ndim) + 3) & ~3;
-      float* d_z = d_x + (size_t)M * kpad;
-      if (scratch_bytes < (2 * nel + 2 * nb + 256 + (int64_t)M * kpad + (int64_t)M * ldz + 16) * 4) { sq_set_error(h, "sqair_debug_linear_graph_time: scratch too small"); return -1; }
-      SQ_CHECK_HIP(hipMemsetAsync(d_z, 0, ((size_t)M * ldz + 16) * 4, s));
-      SQ_CHECK_HIP(hipMemcpy2DAsync(d_z, (size_t)ldz * 4, x, (size_t)Kdim * 4, (size_t)Kdim * 4, M, hipMemcpyDeviceToDevice, s));
-      l2.seg(d_z, ldz, Kdim).out(d_z, ldz).act(act);
-      l2.a.wp = d_w; l2.a.wzero = d_zero; l2.a.bias = d_b; l2.a.M = M; l2.a.N = Ndim;
-    }
-    SQ_CHECK_HIP(cap.begin());
-    for (int i = 0; i < tm.nodes; ++i)   // (a failed launch: cap ends the capture on the way out)
-      if (sq_launch_linear(tm.dependent ? l2.a : l.a, L, s) != 0) { sq_set_error(h, "sqair_debug_linear_graph_time: A-operand contract violated inside the capture"); return -5; }
-    SQ_CHECK_HIP(cap.end());
-    SQ_CHECK_HIP(cap.instantiate());
-    SQ_CHECK_HIP(cap.events());
-    for (int i = 0; i < 2; ++i) SQ_CHECK_HIP(hipGraphLaunch(cap.exec, s));
-    (void)hipEventRecord(cap.ev[0], s);
-    for (int i = 0; i < tm.reps; ++i) SQ_CHECK_HIP(hipGraphLaunch(cap.exec, s));
-  } else {  // the same launch `reps` times back to back between two events
-    SQ_CHECK_HIP(cap.events());
-    for (int i = 0; i < 3; ++i) sq_launch_linear(l.a, L, s);
-    (void)hipEventRecord(cap.ev[0], s);
-    for (int i = 0; i < tm.reps; ++i) sq_launch_linear(l.a, L, s);
-  }
-  (void)hipEventRecord(cap.ev[1], s);
-  SQ_CHECK_HIP(hipStreamSynchronize(s));
-  SQ_CHECK_HIP(hipEventElapsedTime(&ms, cap.ev[0], cap.ev[1]));
-  *us_out = ms * 1e3f / ((float)tm.reps * (float)std::max(tm.nodes, 1));
-  return 0;
-}
-extern "C" int sqair_linear_test(SqairHandle* h, const float* x, const float* wmat, const float* b, float* y, int M,
-                                 int Kdim, int Ndim, int act, void* scratch, int64_t scratch_bytes, void* stream) {
-  return sq_linear_test(h, x, wmat, b, y, M, Kdim, Ndim, act, scratch, scratch_bytes, LinearTiming{}, nullptr, stream);
-}
-// measurement helper (tools/time_linear.py): average time of one dense launch of the given shape, launches back to back
-extern "C" int sqair_debug_linear_time(SqairHandle* h, const float* x, const float* wmat, const float* b, float* y, int M, int Kdim,
-                                       int Ndim, int act, void* scratch, int64_t scratch_bytes, int reps, float* us_out, void* stream) {
-  if (!h || !us_out || reps < 1) return -1;
-  return sq_linear_test(h, x, wmat, b, y, M, Kdim, Ndim, act, scratch, scratch_bytes, LinearTiming{reps, 0, false}, us_out, stream);
-}
-
-// measurement helper (tools/dense_graph_time.py): the dense launches of the passes issued between (on = 1) and the read-out.
-// entry i -> {layer id (-1 - id: the VanillaRNN layer with the slot tail fused in front), rows, K padded, N}; returns the count.
-extern "C" int sqair_debug_dense_log(SqairHandle* h, int on) {
-  if (!h) return -1;
-  if (on) h->dense_log.clear();
-  h->dense_log_on = on != 0;
-  return (int)(h->dense_log.size() / 4);
-}
-extern "C" int sqair_debug_dense_log_entry(const SqairHandle* h, int i, int* out4) {
-  if (!h || !out4 || i < 0 || (size_t)i * 4 + 3 >= h->dense_log.size()) return -1;
-  for (int q = 0; q < 4; ++q) out4[q] = h->dense_log[(size_t)i * 4 + q];
-  return 0;
-}
-// measurement helper (tools/dense_graph_time.py): time per NODE of a HIP graph of `nodes` launches of one dense layer -- the same
-// launch again and again, or (dependent != 0) each reading what the previous one wrote -- replayed `replays` times between HIP events
-extern "C" int sqair_debug_linear_graph_time(SqairHandle* h, const float* x, const float* wmat, const float* b, float* y, int M, int Kdim,
-                                             int Ndim, int act, void* scratch, int64_t scratch_bytes, int nodes, int replays,
-                                             int dependent, float* us_out, void* stream) {
-  if (!h || !us_out || nodes < 1 || replays < 1) return -1;
-  return sq_linear_test(h, x, wmat, b, y, M, Kdim, Ndim, act, scratch, scratch_bytes, LinearTiming{replays, nodes, dependent != 0},
-                        us_out, stream);
-}
-
-extern "C" int sqair_gru_test(SqairHandle* h, const float* x, const float* hstate, const float* gru_flat, float* h_out,
-                              int M, int Kx, void* scratch, int64_t scratch_bytes, void* stream) {
-  if (!h || !x || !hstate || !gru_flat || !h_out || !scratch) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  const int nh = h->cfg.n_hidden;
-  // gru_flat: for g in (z, r, h): w_g [Kx,nh], u_g [nh,nh], b_g [nh]  (the order add_gru() lays them out)
-  const int64_t gs = (int64_t)Kx * nh + (int64_t)nh * nh + nh;
-  PackedLayer L1, L2;
-  L1.seg_width = {Kx, nh};
-  L1.kc = (Kx + 15) / 16 + (nh + 15) / 16;
-  L1.nt = 3 * nh / 16; L1.N = 3 * nh; L1.w_off = 0; L1.b_off = 0;
-  adhoc_layer(h, nh, nh, &L2);
-  const int64_t n1 = (int64_t)L1.nt * L1.kc * 256, n2 = (int64_t)L2.nt * L2.kc * 256, nb1 = L1.nt * 16, nb2 = L2.nt * 16;
-  const int kpad = (Kx + 3) & ~3;
-  const int64_t need = (2 * n1 + 2 * n2 + 2 * nb1 + nb2 + 3 * (int64_t)M * nh + 256 + (int64_t)M * kpad) * 4;
-  if (scratch_bytes < need) { sq_set_error(h, "sqair_gru_test: scratch too small"); return -1; }
-  std::vector<int> i1(n1, -1), i2(n2, -1), b1(nb1, -1);
-  const int xc = (Kx + 15) / 16;
-  for (int g = 0; g < 3; ++g) {
-    adhoc_fill(i1, L1.kc, 0, g * nh, nh, Kx, g * gs, nh, 0);
-    if (g < 2) adhoc_fill(i1, L1.kc, xc, g * nh, nh, nh, g * gs + (int64_t)Kx * nh, nh, 0);
-    for (int n = 0; n < nh; ++n) b1[g * nh + n] = (int)(g * gs + (int64_t)Kx * nh + (int64_t)nh * nh + n);
-  }
-  adhoc_fill(i2, L2.kc, 0, 0, nh, nh, 2 * gs + (int64_t)Kx * nh, nh, 0);
-  float* f = (float*)scratch;
-  int* d_i1 = (int*)f; f += n1;
-  float* d_w1 = f; f += n1;
-  int* d_i2 = (int*)f; f += n2;
-  float* d_w2 = f; f += n2;
-  int* d_b1i = (int*)f; f += nb1;
-  float* d_b1 = f; f += nb1;
-  float* d_b2 = f; f += nb2;
-  float* d_z = f; f += (int64_t)M * nh;
-  float* d_rh = f; f += (int64_t)M * nh;
-  float* d_xh = f; f += (int64_t)M * nh;
-  float* d_zero = f; f += 256;
-  float* d_x = f; f += (int64_t)M * kpad;
-  SQ_CHECK_HIP(hipMemsetAsync(d_zero, 0, (256 + (size_t)M * kpad) * 4, s));
-  SQ_CHECK_HIP(hipMemcpy2DAsync(d_x, (size_t)kpad * 4, x, (size_t)Kx * 4, (size_t)Kx * 4, M, hipMemcpyDeviceToDevice, s));
-  SQ_CHECK_HIP(hipMemcpyAsync(d_i1, i1.data(), n1 * 4, hipMemcpyHostToDevice, s));
-  SQ_CHECK_HIP(hipMemcpyAsync(d_i2, i2.data(), n2 * 4, hipMemcpyHostToDevice, s));
-  SQ_CHECK_HIP(hipMemcpyAsync(d_b1i, b1.data(), nb1 * 4, hipMemcpyHostToDevice, s));
-  SQ_CHECK_HIP(hipStreamSynchronize(s));
-  sq_launch_pack(gru_flat, d_w1, d_i1, n1, s);
-  sq_launch_pack(gru_flat, d_w2, d_i2, n2, s);
-  sq_launch_pack(gru_flat, d_b1, d_b1i, nb1, s);
-  SQ_CHECK_HIP(hipMemsetAsync(d_b2, 0, nb2 * 4, s));
-  Lin g1;
-  g1.seg(d_x, kpad, Kx).seg(hstate, nh, nh).out(d_z, nh).gru1(hstate, nh, d_rh, nh, d_xh, nh, nh);
-  g1.a.wp = d_w1; g1.a.wzero = d_zero; g1.a.bias = d_b1; g1.a.M = M; g1.a.N = 3 * nh;
-  if (sq_launch_linear(g1.a, L1, s) != 0) { sq_set_error(h, "sqair_gru_test: A-operand contract violated"); return -5; }
-  Lin g2;
-  g2.seg(d_rh, nh, nh).add(d_xh, nh, nh).out(h_out, nh).gru2(hstate, nh, d_z, nh, nh);
-  g2.a.wp = d_w2; g2.a.wzero = d_zero; g2.a.bias = d_b2; g2.a.M = M; g2.a.N = nh;
-  sq_launch_linear(g2.a, L2, s);
-  SQ_CHECK_HIP(hipGetLastError());
-  SQ_CHECK_HIP(hipStreamSynchronize(s));
-  return 0;
-}
-
-// snt.LSTM step through the launches the forward pass uses: one gate GEMM over [x | h] + the element-wise cell kernel
-extern "C" int sqair_lstm_test(SqairHandle* h, const float* x, const float* hstate, const float* cstate, const float* lstm_flat,
-                               float* state_out, int M, int Kx, void* scratch, int64_t scratch_bytes, void* stream) {
-  if (!h || !x || !hstate || !cstate || !lstm_flat || !state_out || !scratch) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  const int nh = h->cfg.n_hidden;
-  // lstm_flat: w_gates [(Kx + nh), 4 nh] then b_gates [4 nh] (the order of the reference's LSTM variables)
-  PackedLayer L;
-  L.seg_width = {Kx, nh};
-  L.kc = (Kx + 15) / 16 + (nh + 15) / 16;
-  L.nt = 4 * nh / 16; L.N = 4 * nh; L.w_off = 0; L.b_off = 0;
-  const int64_t nel = (int64_t)L.nt * L.kc * 256, nb = L.nt * 16;
-  const int kpad = (Kx + 3) & ~3;
-  const int64_t need = (2 * nel + 2 * nb + 256 + (int64_t)M * kpad + (int64_t)M * 4 * nh) * 4;
-  if (scratch_bytes < need) { sq_set_error(h, "sqair_lstm_test: scratch too small"); return -1; }
-  std::vector<int> idx(nel, -1), bidx(nb, -1);
-  adhoc_fill(idx, L.kc, 0, 0, 4 * nh, Kx, 0, 4 * nh, 0);
-  adhoc_fill(idx, L.kc, (Kx + 15) / 16, 0, 4 * nh, nh, (int64_t)Kx * 4 * nh, 4 * nh, 0);
-  for (int n = 0; n < 4 * nh; ++n) bidx[n] = (int)((int64_t)(Kx + nh) * 4 * nh + n);
-  float* f = (float*)scratch;
-  int* d_idx = (int*)f; f += nel;
-  float* d_w = f; f += nel;
-  int* d_bidx = (int*)f; f += nb;
-  float* d_b = f; f += nb;
-  float* d_zero = f; f += 256;
-  float* d_x = f; f += (int64_t)M * kpad;
-  float* d_g = f;
-  SQ_CHECK_HIP(hipMemsetAsync(d_zero, 0, (256 + (size_t)M * kpad) * 4, s));
-  SQ_CHECK_HIP(hipMemcpy2DAsync(d_x, (size_t)kpad * 4, x, (size_t)Kx * 4, (size_t)Kx * 4, M, hipMemcpyDeviceToDevice, s));
-  SQ_CHECK_HIP(hipMemcpyAsync(d_idx, idx.data(), nel * 4, hipMemcpyHostToDevice, s));
-  SQ_CHECK_HIP(hipMemcpyAsync(d_bidx, bidx.data(), nb * 4, hipMemcpyHostToDevice, s));
-  SQ_CHECK_HIP(hipStreamSynchronize(s));
-  sq_launch_pack(lstm_flat, d_w, d_idx, nel, s);
-  sq_launch_pack(lstm_flat, d_b, d_bidx, nb, s);
-  Lin g;
-  g.seg(d_x, kpad, Kx).seg(hstate, nh, nh).out(d_g, 4 * nh);
-  g.a.wp = d_w; g.a.wzero = d_zero; g.a.bias = d_b; g.a.M = M; g.a.N = 4 * nh;
-  if (sq_launch_linear(g.a, L, s) != 0) { sq_set_error(h, "sqair_lstm_test: A-operand contract violated"); return -5; }
-  sq_launch_lstm_cell(d_g, 4 * nh, cstate, nh, state_out, 2 * nh, M, nh, s);
-  SQ_CHECK_HIP(hipGetLastError());
-  SQ_CHECK_HIP(hipStreamSynchronize(s));
-  return 0;
-}
-
-// adjoint of the element-wise LSTM cell: gates [M, 4 nh] (pre-activations i, j, f, o), c_prev, d h', d c' -> d gates, d c_prev
-extern "C" int sqair_lstm_cell_bwd_test(SqairHandle* h, const float* gates, const float* c_prev, const float* d_h, const float* d_c,
-                                        float* d_gates, float* d_cprev, int M, void* stream) {
-  if (!h || !gates || !c_prev || !d_h || !d_c || !d_gates || !d_cprev) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  const int nh = h->cfg.n_hidden;
-  sq_launch_lstm_cell_bwd(gates, 4 * nh, c_prev, nh, d_h, nh, d_c, nh, d_gates, 4 * nh, d_cprev, nh, M, nh, s);
-  SQ_CHECK_HIP(hipGetLastError());
-  SQ_CHECK_HIP(hipStreamSynchronize(s));
-  return 0;
-}
-
 // Slot compaction on raw device buffers (unit-test entry; its adjoint: sqair_compact_bwd_test in sqair_train.hip): the launch of the
 // frame loop with the handle's Dims, one frame.  The layout query tells a caller the widths and columns of THIS build's buffers, so that a
 // test hard-codes neither the product nor the wide record.
@@ -2158,147 +1804,16 @@ extern "C" int sqair_debug_layer(const SqairHandle* h, int id, int* kc, int* nt,
 extern "C" int sqair_debug_plan(const SqairHandle* h, int id, int* widx, int* bidx_a, int* bidx_b) {
   if (!h || id < 0 || id >= L_COUNT) return -1;
   const PackedLayer& L = h->layers[id];
-  memcpy(widx, h->widx.data() + L.w_off, (size_t)L.nt * L.kc * 256 * sizeof(int));
-  memcpy(bidx_a, h->bidx_a.data() + L.b_off, (size_t)L.nt * 16 * sizeof(int));
-  memcpy(bidx_b, h->bidx_b.data() + L.b_off, (size_t)L.nt * 16 * sizeof(int));
+  memcpy(widx, h->plan.widx.data() + L.w_off, (size_t)L.nt * L.kc * 256 * sizeof(int));
+  memcpy(bidx_a, h->plan.bidx_a.data() + L.b_off, (size_t)L.nt * 16 * sizeof(int));
+  memcpy(bidx_b, h->plan.bidx_b.data() + L.b_off, (size_t)L.nt * 16 * sizeof(int));
   return 0;
 }
-
-// ------------------------------------------------------------------------------------------------
-// dense-layer backward through the kernels of the training step (unit-test entry): y = act(x W + b) was computed forward;
-// given dL/dy returns dL/dx (k_linear on the transposed pack, the route of the decoder layers), dL/dW and dL/db (routed as
-// sqair_backward routes a block: the grouped kernel, or k_wgrad2 on its own for operands the grouped kernel declines).
-// ------------------------------------------------------------------------------------------------
-extern "C" int sqair_linear_bwd_test(SqairHandle* h, const float* x, const float* wmat, const float* y, const float* dy,
-                                     float* dx, float* dw, float* db, int M, int Kdim, int Ndim, int act, void* scratch,
-                                     int64_t scratch_bytes, void* stream) {
-  if (!h || !x || !wmat || !y || !dy || !dx || !dw || !db || !scratch) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  // transposed layer: K' = Ndim inputs (dpre), N' = Kdim outputs (dx)
-  PackedLayer L;
-  adhoc_layer(h, Ndim, Kdim, &L);
-  const int64_t nel = (int64_t)L.nt * L.kc * 256, nb = L.nt * 16;
-  const int npad = (Ndim + 3) & ~3;
-  if (scratch_bytes < (2 * nel + nb + 256 + (int64_t)M * npad) * 4) {
-    sq_set_error(h, "sqair_linear_bwd_test: scratch too small");
-    return -1;
-  }
-  std::vector<int> idx(nel, -1);
-  adhoc_fill_transposed(idx, L.kc, Kdim, Ndim);
-  int* d_idx = (int*)scratch;
-  float* d_w = (float*)scratch + nel;
-  float* d_b = d_w + nel;
-  float* d_zero = d_b + nb;
-  float* d_dpre = d_zero + 256;          // [M][npad], 16-byte aligned rows
-  SQ_CHECK_HIP(hipMemcpyAsync(d_idx, idx.data(), nel * 4, hipMemcpyHostToDevice, s));
-  SQ_CHECK_HIP(hipMemsetAsync(d_b, 0, (nb + 256 + (size_t)M * npad) * 4, s));
-  SQ_CHECK_HIP(hipMemsetAsync(dw, 0, (size_t)Kdim * Ndim * 4, s));   // (the weight-gradient kernels accumulate with atomics)
-  SQ_CHECK_HIP(hipMemsetAsync(db, 0, (size_t)Ndim * 4, s));
-  SQ_CHECK_HIP(hipStreamSynchronize(s));
-  sq_launch_pack(wmat, d_w, d_idx, nel, s);
-  sq_launch_dact2(dy, Ndim, y, Ndim, d_dpre, npad, M, Ndim, act, act, 1 << 30, 0, s);
-  WgradBatch wbatch;
-  if (!wbatch.add(x, Kdim, d_dpre, npad, dw, Ndim, M, Kdim, Ndim, nullptr, nullptr, db, nullptr))
-    sq_launch_wgrad_acc(x, Kdim, d_dpre, npad, dw, Ndim, M, Kdim, Ndim, s, nullptr, nullptr, db, nullptr);
-  if (wbatch.flush(s) != 0) { sq_set_error(h, "sqair_linear_bwd_test: the grouped weight-gradient launch failed"); return -2; }
-  Lin l;
-  l.seg(d_dpre, npad, Ndim).out(dx, Kdim).act(ACT_NONE);
-  l.a.wp = d_w; l.a.wzero = d_zero; l.a.bias = d_b; l.a.M = M; l.a.N = Kdim;
-  if (sq_launch_linear(l.a, L, s) != 0) { sq_set_error(h, "sqair_linear_bwd_test: A-operand contract violated"); return -5; }
-  SQ_CHECK_HIP(hipGetLastError());
-  SQ_CHECK_HIP(hipStreamSynchronize(s));
+// the transposed pack of layer id (dX = dY W^T): widx [kc*nt*256], nt tiles of kc chunks with kc, nt as sqair_debug_layer reports them
+// for the forward layer, swapped; -1 for a layer without one (the forward-only interleaved layers)
+extern "C" int sqair_debug_plan_t(const SqairHandle* h, int id, int* widx) {
+  if (!h || !widx || id < 0 || id >= L_COUNT || h->layersT[id].seg_width.empty()) return -1;
+  const PackedLayer& T = h->layersT[id];
+  memcpy(widx, h->plan.widx.data() + T.w_off, (size_t)T.nt * T.kc * 256 * sizeof(int));
   return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// The dense family's operand contract, one launch (unit-test entry): everything a Lin can say -- segments with pitches, widths and
-// row divisors, a broadcast segment, the addend, the split activation, both scales, a padded output pitch -- goes to
-// sq_launch_linear as the caller gave it.  Only the weights are packed here, the ad-hoc way of sqair_gru_test.
-// ------------------------------------------------------------------------------------------------
-extern "C" int sqair_linear_contract_test(SqairHandle* h, const SqairDenseContract* c, void* stream) {
-  if (!h || !c || !c->w || !c->out || !c->scratch || c->nseg < 1 || c->nseg > 4 || c->M < 1 || c->N < 1 || c->out_ld < c->N) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  PackedLayer L;
-  L.kc = 0; L.nt = (c->N + 15) / 16; L.N = c->N; L.w_off = 0; L.b_off = 0;
-  for (int i = 0; i < c->nseg; ++i) {
-    if (c->seg[i].width < 1) { sq_set_error(h, "sqair_linear_contract_test: a segment without inputs"); return -1; }
-    L.seg_width.push_back(c->seg[i].width);
-    L.kc += (c->seg[i].width + 15) / 16;
-  }
-  const int64_t nel = (int64_t)L.nt * L.kc * 256, nb = L.nt * 16;
-  if (c->scratch_bytes < (2 * nel + 2 * nb + 256) * 4) { sq_set_error(h, "sqair_linear_contract_test: scratch too small"); return -1; }
-  std::vector<int> idx(nel, -1), bidx(nb, -1);
-  for (int i = 0, cbase = 0, k0 = 0; i < c->nseg; ++i) {
-    adhoc_fill(idx, L.kc, cbase, 0, c->N, c->seg[i].width, (int64_t)k0 * c->N, c->N, 0);
-    cbase += (c->seg[i].width + 15) / 16;
-    k0 += c->seg[i].width;
-  }
-  for (int n = 0; n < c->N; ++n) bidx[n] = c->b ? n : -1;
-  int* d_idx = (int*)c->scratch;
-  float* d_w = (float*)c->scratch + nel;
-  float* d_b = d_w + nel;
-  int* d_bidx = (int*)(d_b + nb);
-  float* d_zero = (float*)(d_bidx + nb);
-  SQ_CHECK_HIP(hipMemcpyAsync(d_idx, idx.data(), nel * 4, hipMemcpyHostToDevice, s));
-  SQ_CHECK_HIP(hipMemcpyAsync(d_bidx, bidx.data(), nb * 4, hipMemcpyHostToDevice, s));
-  SQ_CHECK_HIP(hipMemsetAsync(d_zero, 0, 256 * 4, s));
-  SQ_CHECK_HIP(hipStreamSynchronize(s));
-  sq_launch_pack(c->w, d_w, d_idx, nel, s);
-  if (c->b) sq_launch_pack(c->b, d_b, d_bidx, nb, s);
-  else SQ_CHECK_HIP(hipMemsetAsync(d_b, 0, nb * 4, s));
-  Lin l;
-  for (int i = 0; i < c->nseg; ++i) l.seg(c->seg[i].p, c->seg[i].ld, c->seg[i].width, c->seg[i].rdiv);
-  if (c->add) l.add(c->add, c->add_ld, c->add_n, c->add_rdiv);
-  l.out(c->out, c->out_ld).act2(c->act_a, c->act_b, c->act_split);
-  l.a.scale = c->scale; l.a.scale_ptr = c->scale_ptr;
-  l.a.wp = d_w; l.a.wzero = d_zero; l.a.bias = d_b; l.a.M = c->M; l.a.N = c->N;
-  const int rc = sq_launch_linear(l.a, L, s);
-  if (rc != 0) { sq_set_error(h, "sqair_linear_contract_test: A-operand contract violated"); return rc; }
-  SQ_CHECK_HIP(hipGetLastError());
-  SQ_CHECK_HIP(hipStreamSynchronize(s));
-  return 0;
-}
-
-// The routed dX GEMM, one launch (unit-test entry): dpre, the ranges and the GRU block reach sq_launch_linear_dx as given; the
-// forward matrix w [Kdim, width] is packed transposed, as sqair_linear_bwd_test packs it.
-extern "C" int sqair_linear_dx_test(SqairHandle* h, const SqairDxTest* t, void* stream) {
-  if (!h || !t || !t->dpre || !t->w || !t->scratch || t->M < 1 || t->width < 1 || t->Kdim < 1) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  const int kc = (t->width + 15) / 16, nt = (t->Kdim + 15) / 16;
-  const int64_t nel = (int64_t)nt * kc * 256;
-  if (t->scratch_bytes < (2 * nel + 256) * 4) { sq_set_error(h, "sqair_linear_dx_test: scratch too small"); return -1; }
-  std::vector<int> idx(nel, -1);
-  adhoc_fill_transposed(idx, kc, t->Kdim, t->width);
-  int* d_idx = (int*)t->scratch;
-  float* d_w = (float*)t->scratch + nel;
-  float* d_zero = d_w + nel;
-  SQ_CHECK_HIP(hipMemcpyAsync(d_idx, idx.data(), nel * 4, hipMemcpyHostToDevice, s));
-  SQ_CHECK_HIP(hipMemsetAsync(d_zero, 0, 256 * 4, s));
-  SQ_CHECK_HIP(hipStreamSynchronize(s));
-  sq_launch_pack(t->w, d_w, d_idx, nel, s);
-  DxArgs a; memset(&a, 0, sizeof(a));
-  a.dpre = t->dpre; a.ld = t->ld; a.width = t->width; a.wp = d_w; a.wzero = d_zero; a.scale_ptr = t->scale_ptr; a.M = t->M;
-  a.nranges = t->nranges;
-  for (int i = 0; i < 3 && i < t->nranges; ++i) {
-    const SqairDxRange& r = t->r[i];
-    a.r[i] = DxRange{r.n0, r.n1, r.dst, r.dst_ld, r.dst2, r.dst2_ld, r.add, r.add_ld, r.saved, r.saved_ld, r.act_a, r.act_b, r.act_split};
-  }
-  const SqairDxGru& g = t->gru;
-  a.gru = DxGru{g.mode, g.g0, g.g0_ld, g.g1, g.g1_ld, g.hprev, g.h_ld, g.dpre1, g.dp_ld, g.d_h, g.dh_ld, g.acc_dh, g.dup, g.dup_ld,
-                g.dup_h_off, g.nh};
-  const int rc = sq_launch_linear_dx(a, kc, nt, s);
-  if (rc == -5) { sq_set_error(h, "sqair_linear_dx_test: operand contract violated (alignment, pitch, range start or range count)"); return rc; }
-  if (rc == -6) { sq_set_error(h, "sqair_linear_dx_test: the GRU epilogue takes one range [0, nh) without a saved output, at most 16 K chunks on the product build"); return rc; }
-  if (rc != 0) { sq_set_error(h, "sqair_linear_dx_test: launch refused"); return rc; }
-  SQ_CHECK_HIP(hipGetLastError());
-  SQ_CHECK_HIP(hipStreamSynchronize(s));
-  return 0;
-}
-
-// the routes the two dense launchers took (sqair_common.h: DenseRoute, in the order sqair_hip.h documents)
-extern "C" int sqair_debug_dense_routes(int64_t* out, int n) {
-  static_assert(DR_COUNT == SQAIR_DENSE_ROUTES, "sqair_hip.h documents every route");
-  if (!out || n < 0) return -1;
-  for (int i = 0; i < n && i < DR_COUNT; ++i) out[i] = (int64_t)sq_dense_route_hits(i);
-  return DR_COUNT;
 }

@@ -109,6 +109,10 @@ struct PackedLayer {
   std::vector<int> seg_width;  // true widths per segment
 };
 
+// A helper shared between translation units that stays out of the library's dynamic symbol table.  Only helpers newer than that
+// table carry it: the older ones (sq_carve, sq_run, sq_state_refusal, ...) were exported before and stay so, the table unchanged.
+#define SQ_LOCAL __attribute__((visibility("hidden")))
+
 struct SqairHandle;
 void sq_set_error(SqairHandle* h, const std::string& msg);
 // Raises a kernel's dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) on the CURRENT device, once per

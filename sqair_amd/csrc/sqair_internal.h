@@ -1,11 +1,12 @@
 // Internal declarations shared by sqair_api.hip (handle, plan, forward pass), sqair_state.hip (carried state, forecast),
-// sqair_lane_api.hip (lane answers) and sqair_train.hip (backward pass).
+// sqair_lane_api.hip (lane answers), sqair_train.hip (backward pass) and sqair_dense_test.hip (the dense unit-test entries).
 #pragma once
 #include <cstdio>
 #include <cstring>
 #include <map>
 
 #include "sqair_glue.h"
+#include "sqair_pack.h"
 
 struct ParamEntry {
   std::string name;
@@ -79,9 +80,7 @@ struct SqairHandle {
   std::vector<WgEntry> wg[L_COUNT];
   std::vector<BgEntry> bg[L_COUNT];
   std::vector<int> rm_pool;
-  std::vector<int> widx;            // per packed weight element: index into flat params or -1
-  std::vector<int> bidx_a, bidx_b;  // per packed bias element
-  int64_t packed_w = 0, packed_b = 0;
+  PackPlan plan;                    // index tables of layers[] then layersT[] (sqair_pack.h)
   bool plan_uploaded_to = false;
   const void* plan_uploaded_ptr = nullptr;
   // graph
@@ -142,11 +141,11 @@ struct PackedLayout {
 inline PackedLayout packed_layout(const SqairHandle* h) {
   PackedLayout p;
   p.w = 0;
-  p.b = align64(p.w + h->packed_w);
-  p.wi = align64(p.b + h->packed_b);
-  p.ba = align64(p.wi + h->packed_w);
-  p.bb = align64(p.ba + h->packed_b);
-  p.rm = align64(p.bb + h->packed_b);
+  p.b = align64(p.w + h->plan.packed_w());
+  p.wi = align64(p.b + h->plan.packed_b());
+  p.ba = align64(p.wi + h->plan.packed_w());
+  p.bb = align64(p.ba + h->plan.packed_b());
+  p.rm = align64(p.bb + h->plan.packed_b());
   p.fi = align64(p.rm + (int64_t)h->rm_pool.size());
   p.um = align64(p.fi + (h->padded ? h->n_params : 0));
   p.total = align64(p.um + (h->padded ? h->n_uparams : 0));
@@ -238,10 +237,6 @@ struct Workspace {
 };
 Workspace sq_carve(const SqairHandle* h, int T, int B, float* base, bool train);
 
-// A helper shared between translation units that stays out of the library's dynamic symbol table.  Only helpers newer than that
-// table carry it: the older ones (sq_carve, sq_run, sq_state_refusal, ...) were exported before and stay so, the table unchanged.
-#define SQ_LOCAL __attribute__((visibility("hidden")))
-
 static inline int sq_no(SqairHandle* h, const std::string& why) { sq_set_error(h, why); return -1; }   // a refusal: -1 + error text
 // -1 + "<who><name> must lie in (0, 1]" unless it does: an IoU or coverage threshold (NaN fails both comparisons)
 static inline int sq_unit_refusal(SqairHandle* h, const std::string& who, const char* name, float v) {
@@ -294,6 +289,30 @@ SQ_LOCAL int sq_launch_lane_answers(SqairHandle* h, const SqLaneSet& l, const fl
 // section A of a frame of the pass, and a frame of the forecast: the propagation-prior cell and its statistics (sqair_api.hip)
 SQ_LOCAL int sq_prior_step(SqairHandle* h, const float* packed, hipStream_t s, int M, const float* rec_prev, const float* prior_prev,
                            float* prior_p, float* pgz, float* pgrh, float* pgxh, float* pstats, float* o3, float* o1);
+
+// Capture on this stream, scoped: on every way out that did not hand_over() the graph and its executable, the destructor ends a
+// capture still open (a stream left capturing fails every later call on it) and destroys what was made, the two timing events of
+// the measurement helpers included.  (sqair_capture_begin / _end are paired by the caller and do not use this.)
+struct SqCapture {
+  hipStream_t s;
+  bool open = false;
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  explicit SqCapture(hipStream_t stream) : s(stream) {}
+  SqCapture(const SqCapture&) = delete;
+  hipError_t begin() { const hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal); open = e == hipSuccess; return e; }
+  hipError_t end() { open = false; return hipStreamEndCapture(s, &graph); }
+  hipError_t instantiate() { return hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0); }
+  hipError_t events() { const hipError_t e = hipEventCreate(&ev[0]); return e != hipSuccess ? e : hipEventCreate(&ev[1]); }
+  void hand_over(hipGraph_t* g, hipGraphExec_t* x) { *g = graph; *x = exec; graph = nullptr; exec = nullptr; }
+  ~SqCapture() {
+    if (open) (void)hipStreamEndCapture(s, &graph);
+    if (exec) (void)hipGraphExecDestroy(exec);
+    if (graph) (void)hipGraphDestroy(graph);
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+  }
+};
 
 // zero fill as a kernel (not a memset node: see sqair_train.hip); p 16-byte aligned
 void sq_zero_fill(float* p, int64_t n, hipStream_t s);

@@ -26,6 +26,8 @@ def test_library_loads_and_exports_header_symbols(repo_root):
     for n in names:
         assert hasattr(lib, n), "missing export " + n
     assert set(names) == set(_capi.EXPORTED_SYMBOLS), "ctypes prototypes and header disagree"
+    # a host-only read-out of the plan: a measurement helper, bound and exported but not in the header
+    assert "sqair_debug_plan_t" in _capi._PROTOS and hasattr(lib, "sqair_debug_plan_t") and "sqair_debug_plan_t" not in names
     assert lib.sqair_abi_version() == _capi.ABI_VERSION == 2
     assert lib.sqair_build_flags() == b"product"
 

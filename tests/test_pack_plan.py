@@ -221,3 +221,43 @@ def test_interleaved_forward_packs_hold_the_same_columns(plan):
                 col = full[:, 16 * t + 5 * e + g]
                 assert np.array_equal(col, ref[:, g * NW + c]) if c < NW else not col.any()
         assert not full[:, 16 * t + 15].any()
+
+
+def _unpacked(widx, kc, nt):
+    """An index table in the MFMA fragment order -> [16 kc, 16 nt] (row k, column n), the indices themselves."""
+    W = np.empty((kc * 16, nt * 16), dtype=np.int32)
+    t = widx.reshape(nt, kc, 64, 4)
+    for lane in range(64):
+        for comp in range(4):
+            W[np.ix_(np.arange(kc) * 16 + 4 * (lane >> 4) + comp, np.arange(nt) * 16 + (lane & 15))] = t[:, :, lane, comp].T
+    return W
+
+
+@pytest.mark.parametrize("flags", [dict(), dict(transition="LSTM", time_transition="LSTM", prior_transition="LSTM"),
+                                   dict(transition="GRU", time_transition="LSTM", prior_transition="LSTM")])
+def test_transposed_plan_is_the_forward_plan_transposed(flags):
+    """The packs of the dX GEMMs (dX = dY W^T): for every layer the transposed table, unpacked, holds index for index the
+    flat-parameter indices of the forward table, unpacked and transposed -- the zero padding included.  The two interleaved
+    forward-only layers have no transposed pack."""
+    p = Plan(**flags)
+    try:
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        filled = 0
+        for lid, name in enumerate(LAYERS):
+            kc, nt, n, nseg = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+            assert p.lib.sqair_debug_layer(p.h, lid, C.byref(kc), C.byref(nt), C.byref(n), C.byref(nseg), (C.c_int * 4)()) == 0
+            kc, nt = kc.value, nt.value
+            fwd, ba, bb, tr = (np.full(m, -7, dtype=np.int32) for m in (nt * kc * 256, nt * 16, nt * 16, nt * kc * 256))
+            assert p.lib.sqair_debug_plan(p.h, lid, ip(fwd), ip(ba), ip(bb)) == 0
+            if name.endswith("_I"):
+                assert p.lib.sqair_debug_plan_t(p.h, lid, ip(tr)) == -1 and (tr == -7).all(), name
+                continue
+            assert p.lib.sqair_debug_plan_t(p.h, lid, ip(tr)) == 0, name
+            F = _unpacked(fwd, kc, nt)
+            assert F.min() >= -1, name
+            assert np.array_equal(_unpacked(tr, nt, kc), F.T), name
+            filled += int((F >= 0).sum())
+        assert filled > 0
+        assert p.lib.sqair_debug_plan_t(p.h, len(LAYERS), ip(tr)) == -1 and p.lib.sqair_debug_plan_t(p.h, 0, None) == -1
+    finally:
+        p.lib.sqair_destroy(p.h)
