@@ -1180,7 +1180,8 @@ int sqair_clear_workspace(SqairHandle* h, void* workspace, int64_t workspace_byt
  *                 sqair/core.py:226-229, :336-359) in the epilogue of the dense layer that produces its operands -- the glimpse
  *                 encoder's Gaussian head of a discovery slot, the temporal cell's heads of a propagation slot -- instead of in
  *                 the slot tail (csrc/sqair_glue.h: WhatArgs).  Results are bit-identical either way; re-capture graphs after
- *                 changing it.  (Training passes and the slot chain always derive the sample in the tail.)
+ *                 changing it.  (Training passes, the slot chain, and passes of so many particle rows -- 6000 -- that the dense
+ *                 layers leave the split-K kernel always derive the sample in the tail: the option then changes nothing.)
  *   "specialised" (default 1): when the handle's dimensions are the shipped model family's (50 x 50 frames, 20 x 20 glimpses,
  *                 4 slots, n_what 50, n_hidden 256, GRU temporal and prior cells), the crops of the slot loop and the
  *                 compaction run in instantiations that have those dimensions and the launch's mode compiled in
@@ -1438,6 +1439,97 @@ typedef struct SqairGruGatesBwdTest {
   float* dup_r; int32_t dupr_ld;
 } SqairGruGatesBwdTest;
 int sqair_gru_gates_bwd_test(SqairHandle* h, const SqairGruGatesBwdTest* t, void* stream);
+
+/* ---- the forward kernels of the slot loop, one launch each (test helpers) ----------------------------------------------------------
+ * k_crop_row, k_slot_tail, k_rnn_tail and k_linear_what under the rules of the adjoint entries above: caller-owned device buffers reach the
+ * pass's own launchers UNCHANGED, through the argument builder and launch helpers the pass calls; dimensions, record layout and
+ * parameter offsets are the handle's; a refusal is -1, names the entry in sqair_last_error and launches nothing; otherwise the
+ * launcher's code, after a stream synchronise.  `flat` as above; `packed` is sqair_pack_params' output for these parameters.
+ * Records [R][N][W], noise one frame's [R][2][N][4 + n_what + 1] (phase 0 propagation, 1 discovery), R = B * k_particles.
+ *
+ * sqair_slot_crop_test (k_crop_row; mode 1 = crop #1 of propagation, ALL N slots of a row in one launch, `slot` ignored; mode 2 / 3 =
+ *   crop #2 of a propagation / discovery slot).  One workgroup per (row, slot); with B a multiple of 8 workgroup i serves row
+ *   ((i / 8 / K) * 8 + i % 8) * K + (i / 8) % K, else row i.  specialised 0: the generic instantiation; 1: the instantiation with the
+ *   shipped family's dimensions compiled in, where the handle has them, the frame is staged, modes 1 / 2 have a mask, mode 3 none,
+ *   and modes 2 / 3 come with t2 -- otherwise the generic one all the same.  Frames up to 4096 pixels are staged in LDS.
+ *   READS  img [B] frames at a pitch of H * W rounded up to 4 floats: the H * W pixels of frame r / K, not the padding; mask
+ *          (optional) row r * mask_row_mul + mask_row_add (+ slot in mode 1), G * G floats.
+ *          mode 1: rec_prev(r, slot)[WHERE], wb [(r * N + slot)][4]; where logits = rec_prev[WHERE] + 0.1 wb.
+ *          modes 2 / 3: noise[r][phase][slot][0 : 4] (phase 0 / 1); tp [R][loc 4 | raw scale 4], or with t2 [R][n_hidden] (16-byte
+ *          aligned rows) the transform's output layer w3 = {w [n_hidden][8], b [8]} (16-byte aligned) evaluated in the launch;
+ *          of flat disc.transform.scale_offset (mode 3) / prop.transform.scale_offset and the ten prop.cholesky_scale (mode 2);
+ *          mode 2 also rec_prev(r, slot)[WHERE].  mode 3: loc = tp[0:4], scale = softplus(raw + offset) + 1e-2, where = loc +
+ *          scale eps.  mode 2: loc = rec_prev[WHERE] + tp[0:4], scale = softplus(raw + offset - 1) + 1e-2, where = loc + L eps with
+ *          L = fill_triangular(cholesky) * scale[:, None] + diag(scale).
+ *   WRITES out row r * out_row_mul + out_row_add (+ slot in mode 1): the G x G glimpse (times the mask); modes 2 / 3:
+ *          rec_new(r, slot)[WHERE, WHERE_LOC, WHERE_SCALE]; with t2 and tp_out: tp_out [R][8] = the output layer's result.  Nothing
+ *          else: no other column or slot of a record, no other row of out / tp_out.  rec_prev is never written. */
+typedef struct SqairSlotCropTest {
+  int32_t mode, slot, B, specialised;
+  const float* img;
+  const float* rec_prev; float* rec_new;
+  const float* wb; int32_t wb_ld;
+  const float* tp; int32_t tp_ld;
+  const float* t2; int32_t t2_ld;
+  const float* w3;
+  const float* noise;
+  const float* flat;
+  const float* mask; int32_t mask_row_mul, mask_row_add;
+  float* out; int32_t out_row_mul, out_row_add;
+  float* tp_out; int32_t tp_out_ld;
+} SqairSlotCropTest;
+int sqair_slot_crop_test(SqairHandle* h, const SqairSlotCropTest* t, void* stream);
+
+/* sqair_slot_tail_test.  Without the RNN block (out NULL): k_slot_tail<what_done>, one workgroup per 16 rows.  Per row r (a ragged
+ *   last tile re-reads row R - 1 and stores nothing for it):
+ *   READS  noise[r][phase][slot][4 + n_what] (the uniform u); the previous presence -- propagation: rec_prev(r, slot)[PRES];
+ *          discovery: rec_new(r, slot - 1)[PRES], slot 0: none, it is 1 -- ; s1p [R][n_hidden / 2]; of `packed` the phase's *_S1 pack
+ *          (the `what` rows of steps.l0.w); of `flat` steps.l1.w [n_hidden / 2] and steps.l1.b.
+ *          what_done 0: enc [R][loc n_what | scale n_what], noise[..][4 : 4 + n_what]; propagation also hraw [R][5 n_what] (what-head
+ *          loc, raw scale, raw forget / input / temporal gate) and rec_prev(r, slot)[WHAT].
+ *          what_done 1 (product library only): rec_new(r, slot)[WHAT] instead; enc, hraw, the `what` noise and rec_prev[WHAT] are
+ *          NOT read (they may be NULL or hold NaN).
+ *   WRITES rec_new(r, slot)[PRES, LOGIT, PROB]; what_done 0: also [WHAT, WHAT_LOC, WHAT_SCALE][0 : n_what]; s1h_out [R][n_hidden / 2]
+ *          (optional) = elu(s1p + what W).  No other column of the record, no other slot, no row beyond R.
+ *   A row whose previous presence is 0 gets logit = 0 * raw - 88 = -88 exactly (raw must be finite), presence 0, prob = sigmoid(-88);
+ *   its sample and s1h_out are written like any other row's.  presence = (u < prob) * previous presence.
+ * With the RNN block (out set; product library, VanillaRNN slot cell, n_hidden 128 / 256, option tail_fusion on, slot + 1 < N):
+ *   k_rnn_tail = the same tail inside the NEXT slot's layer, out [R][n_hidden] = tanh([z | hid] W + b + add) on the phase's
+ *   L_PROP_RNN / L_DISC_RNN pack, z = rec_new(r, slot)[WHERE .. LOGIT] with the fresh tail results.  Every workgroup (16 rows x 16
+ *   or 32 columns) re-derives the tail of its rows and additionally READS rec_new(r, slot)[WHERE] (written by the slot's crop; must
+ *   be finite), hid [R][n_hidden] (16-byte aligned rows), add [R][n_hidden], the pack and its bias.  Only the column-tile-0
+ *   workgroups WRITE the record and s1h_out (exactly what k_slot_tail writes); all write their tile of `out`. */
+typedef struct SqairSlotTailTest {
+  int32_t is_disc, slot, B, what_done;
+  const float* hraw; int32_t h_ld;
+  const float* enc; int32_t enc_ld;
+  const float* rec_prev; float* rec_new;
+  const float* noise;
+  const float* s1p; int32_t s1p_ld;
+  float* s1h_out; int32_t s1h_ld;
+  const float* flat; const float* packed;
+  const float* hid; int32_t hid_ld;      /* the optional RNN block */
+  const float* add; int32_t add_ld;
+  float* out; int32_t out_ld;
+} SqairSlotTailTest;
+int sqair_slot_tail_test(SqairHandle* h, const SqairSlotTailTest* t, void* stream);
+
+/* sqair_linear_what_test (k_linear_what<n_hidden / 64, mode> on the L_WHAT_HEAD_I / L_PROP_HEADS_I pack; M = B * k_particles rows;
+ *   refused on the wide library and where n_hidden is neither 128 nor 256).  One workgroup per 16 rows x 16 interleaved columns.
+ *   READS  x [M][n_hidden] (16-byte aligned rows, x_ld a multiple of 4), the pack and its bias, noise[r][phase][slot][4 : 4 + n_what]
+ *          (phase 1 for mode 0, 0 for mode 1); mode 1 also enc [M][loc n_what | scale n_what] and rec_prev(r, slot)[WHAT].
+ *   WRITES rec_new(r, slot)[WHAT, WHAT_LOC, WHAT_SCALE][0 : n_what] and nothing else: mode 0 (discovery) loc = x W_loc + b,
+ *          scale = softplus(x W_scale + b) + 1e-2; mode 1 (propagation) the gated mixture of the tail; what = loc + scale eps.
+ *   The result has the bits of the plain head layer (L_WHAT_HEAD / L_PROP_HEADS) on the split-K kernel followed by the tail. */
+typedef struct SqairLinearWhatTest {
+  int32_t mode, slot, B;
+  const float* x; int32_t x_ld;
+  const float* noise;
+  const float* enc; int32_t enc_ld;
+  const float* rec_prev; float* rec_new;
+  const float* packed;
+} SqairLinearWhatTest;
+int sqair_linear_what_test(SqairHandle* h, const SqairLinearWhatTest* t, void* stream);
 
 /* ---- the log-probability kernels, one launch each (test helpers) -----------------------------------------------------------------
  * k_logprob (section H of the forward pass) and its adjoint k_logprob_bwd (H^T, the head of sqair_backward's reverse sweep), under

@@ -333,6 +333,25 @@ class SqairLogprobBwdTest(C.Structure):
                         "p g_dl", "p d_rec_p", "p d_rec_d", "p d_rec_m", "p d_pstats", "p d_spre", "p flat", "p flat_grad"])
 
 
+class SqairSlotCropTest(C.Structure):
+    """One launch of a crop of the slot loop with its where sample (include/sqair_hip.h: sqair_slot_crop_test)."""
+    _fields_ = _fields(["i mode", "i slot", "i B", "i specialised", "p img", "p rec_prev", "p rec_new", "p wb", "i wb_ld", "p tp", "i tp_ld",
+                        "p t2", "i t2_ld", "p w3", "p noise", "p flat", "p mask", "i mask_row_mul", "i mask_row_add", "p out",
+                        "i out_row_mul", "i out_row_add", "p tp_out", "i tp_out_ld"])
+
+
+class SqairSlotTailTest(C.Structure):
+    """One launch of a slot's tail, alone or inside the next slot's RNN layer (include/sqair_hip.h: sqair_slot_tail_test)."""
+    _fields_ = _fields(["i is_disc", "i slot", "i B", "i what_done", "p hraw", "i h_ld", "p enc", "i enc_ld", "p rec_prev", "p rec_new",
+                        "p noise", "p s1p", "i s1p_ld", "p s1h_out", "i s1h_ld", "p flat", "p packed", "p hid", "i hid_ld", "p add",
+                        "i add_ld", "p out", "i out_ld"])
+
+
+class SqairLinearWhatTest(C.Structure):
+    """One launch of a head layer with the what sample in its epilogue (include/sqair_hip.h: sqair_linear_what_test)."""
+    _fields_ = _fields(["i mode", "i slot", "i B", "p x", "i x_ld", "p noise", "p enc", "i enc_ld", "p rec_prev", "p rec_new", "p packed"])
+
+
 # sqair_debug_dense_routes: the families of the two dense launchers, in the order include/sqair_hip.h documents
 DENSE_ROUTES = ("fwd_splitk", "fwd_t2", "fwd_rows", "fwd_mt", "fwd_lds", "fwd_big_2x2", "fwd_big_3x2", "fwd_big_3x3", "fwd_big_4x2",
                 "dx_nch1", "dx_nch2", "dx_nch3", "dx_nch4", "dx_nch5", "dx_nch6", "dx_nch7", "dx_nch8", "dx_nch9", "dx_nch12", "dx_nch18",
@@ -469,6 +488,9 @@ _PROTOS = {
     "sqair_where_param_grads_test": (C.c_int, [C.c_void_p, C.POINTER(SqairWhereParamGradsTest), C.c_void_p]),
     "sqair_gru_gates_bwd_test": (C.c_int, [C.c_void_p, C.POINTER(SqairGruGatesBwdTest), C.c_void_p]),
     "sqair_logprob_test": (C.c_int, [C.c_void_p, C.POINTER(SqairLogprobTest), C.c_void_p]),
+    "sqair_slot_crop_test": (C.c_int, [C.c_void_p, C.POINTER(SqairSlotCropTest), C.c_void_p]),
+    "sqair_slot_tail_test": (C.c_int, [C.c_void_p, C.POINTER(SqairSlotTailTest), C.c_void_p]),
+    "sqair_linear_what_test": (C.c_int, [C.c_void_p, C.POINTER(SqairLinearWhatTest), C.c_void_p]),
     "sqair_logprob_bwd_test": (C.c_int, [C.c_void_p, C.POINTER(SqairLogprobBwdTest), C.c_void_p]),
     "sqair_debug_dense_routes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
     "sqair_debug_linear_time": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -808,13 +808,13 @@ int sq_run(SqairHandle* h, Lin& l, LayerId id, int M, const float* packed, hipSt
 
 // The tail of slot k fused into slot k + 1's VanillaRNN layer (k_rnn_tail, sqair_glue.hip): possible when the layer is exactly
 // [z-record (56 -> 4 chunks) | hidden state (nh)] -> nh with nh in {128, 256}.
-static bool can_fuse_tail(const SqairHandle* h, LayerId id) {
+SQ_LOCAL bool sq_can_fuse_tail(const SqairHandle* h, LayerId id) {
   const PackedLayer& L = h->layers[id];
   const int nh = h->cfg.n_hidden;
   return h->cfg.rnn_cell == RNN_VANILLA && (nh == 128 || nh == 256) && L.seg_width.size() == 2 && L.seg_width[0] == rec::ZW &&
          L.seg_width[1] == nh && L.kc == 4 + nh / 16 && L.nt == nh / 16 && L.N == nh && h->opt_tail_fusion;
 }
-static int run_rnn_tail(SqairHandle* h, const TailArgs& ta, Dims d, LayerId id, const float* hid, int hid_ld, const float* add, int add_ld,
+SQ_LOCAL int sq_run_rnn_tail(SqairHandle* h, const TailArgs& ta, Dims d, LayerId id, const float* hid, int hid_ld, const float* add, int add_ld,
                         float* out, int out_ld, const float* packed, hipStream_t s) {
   const PackedLayer& L = h->layers[id];
   const PackedLayout pl = packed_layout(h);
@@ -833,17 +833,21 @@ static int run_rnn_tail(SqairHandle* h, const TailArgs& ta, Dims d, LayerId id, 
 // A slot's what sample in the epilogue of the layer that produces its operands (WhatArgs, sqair_glue.h): the glimpse encoder's
 // Gaussian head of a discovery slot (mode 0, pack L_WHAT_HEAD_I) / the temporal cell's heads of a propagation slot (mode 1, pack
 // L_PROP_HEADS_I).  Inference passes of the product build on the launch path; the slot's tail then runs with `what_done`.
-static bool sq_what_fusion(const SqairHandle* h, bool train, bool chain) {
+// Only at row counts where the two plain layers it replaces (L_WHAT_HEAD, L_PROP_HEADS: R rows each) run on the split-K kernel:
+// k_linear_what is that kernel's GEMM, and from sq_linear_leaves_split_k on the plain layers are summed in another order (and
+// faster) -- fused, a pass of 6000 rows differed from the training pass and from what_fusion = 0 in the last bits.
+static bool sq_what_fusion(const SqairHandle* h, bool train, bool chain, int R) {
 #ifdef SQAIR_WIDE
-  (void)h; (void)train; (void)chain;
+  (void)h; (void)train; (void)chain; (void)R;
   return false;
 #else
+  if (sq_linear_leaves_split_k(R, h->layers[L_WHAT_HEAD]) || sq_linear_leaves_split_k(R, h->layers[L_PROP_HEADS])) return false;
   // (not in training passes: the layer would also have to write its own output to the tape for the adjoint -- scattered 4-byte stores
   //  in the reference column order -- and the step was slower with it, 7.38 against 7.35 ms)
   return h->opt_what_fusion && !train && !chain && (h->cfg.n_hidden == 128 || h->cfg.n_hidden == 256);
 #endif
 }
-static int run_what(SqairHandle* h, int mode, const float* x, int x_ld, int M, int slot, const float* noise, const float* enc, int enc_ld,
+SQ_LOCAL int sq_run_what(SqairHandle* h, int mode, const float* x, int x_ld, int M, int slot, const float* noise, const float* enc, int enc_ld,
                     const float* rec_prev, float* rec_new, const float* packed, hipStream_t s) {
   const LayerId id = mode == 0 ? L_WHAT_HEAD_I : L_PROP_HEADS_I;
   const PackedLayer& L = h->layers[id];
@@ -856,6 +860,48 @@ static int run_what(SqairHandle* h, int mode, const float* x, int x_ld, int M, i
   const int rc = sq_launch_linear_what(a, s);
   if (rc != 0) sq_set_error(h, "internal: k_linear_what launch rejected (layer " + std::to_string((int)id) + ")");
   return rc;
+}
+
+// The arguments of a slot's tail (sqair_glue.h: TailArgs) from its operands `io`: the phase's *_S1 pack of the `what` rows of steps.l0
+// and the offsets of steps.l1 in the flat parameters.  The pass (slot_tail below) and sqair_slot_tail_test both build them here.
+SQ_LOCAL TailArgs sq_tail_args(const SqairHandle* h, const TailOperands& io, const float* flat, const float* packed) {
+  const bool disc = io.is_disc != 0;
+  const PackedLayout pl = packed_layout(h);
+  TailArgs ta; memset(&ta, 0, sizeof(ta));
+  ta.is_disc = disc ? 1 : 0; ta.slot = io.slot; ta.hraw = io.hraw; ta.h_ld = io.h_ld; ta.enc = io.enc; ta.enc_ld = io.enc_ld;
+  ta.rec_prev = io.rec_prev; ta.rec_new = io.rec_new; ta.noise = io.noise; ta.s1p = io.s1p; ta.s1p_ld = io.s1p_ld;
+  ta.wp = packed + pl.w + h->layers[disc ? L_DISC_S1 : L_PROP_S1].w_off; ta.flat = flat;
+  ta.w2_off = disc ? h->po.disc_steps_l1_w : h->po.prop_steps_l1_w; ta.b2_off = disc ? h->po.disc_steps_l1_b : h->po.prop_steps_l1_b;
+  ta.s1h_out = io.s1h_out; ta.s1h_ld = io.s1h_out ? io.s1h_ld : 0;
+  ta.what_done = io.what_done ? 1 : 0;
+  return ta;
+}
+
+// The arguments of a crop of the slot loop (sqair_glue.h: CropArgs) from its operands: what the mode does not read stays NULL
+// whatever the caller holds there -- crop #1 (CROP_PROP1) reads rec_prev and wb and no transform, noise or new record; crop #2
+// reads the transform's output `tp`, or with `t2` its input and output layer `w3` (then, and only then, tp_out is written), the
+// previous record in propagation only.  The pass (sections C, E, G below) and sqair_slot_crop_test both build them here.
+SQ_LOCAL CropArgs sq_crop_args(const CropOperands& o) {
+  CropArgs ca; memset(&ca, 0, sizeof(ca));
+  ca.mode = o.mode; ca.img = o.img; ca.mask = o.mask; ca.mask_row_mul = o.mask_row_mul; ca.mask_row_add = o.mask_row_add;
+  ca.out = o.out; ca.out_row_mul = o.out_row_mul; ca.out_row_add = o.out_row_add; ca.flat = o.flat;
+  if (o.mode == CROP_PROP1) { ca.rec_prev = o.rec_prev; ca.wb = o.wb; ca.wb_ld = o.wb_ld; return ca; }
+  ca.slot = o.slot; ca.rec_new = o.rec_new; ca.noise = o.noise;
+  if (o.mode == CROP_PROP2) ca.rec_prev = o.rec_prev;
+  if (o.t2) { ca.t2 = o.t2; ca.t2_ld = o.t2_ld; ca.w3 = o.w3; ca.tp_out = o.tp_out; ca.tp_out_ld = o.tp_out ? o.tp_out_ld : 0; }
+  else { ca.tp = o.tp; ca.tp_ld = o.tp_ld; }
+  return ca;
+}
+// slots a crop launch covers (the grid's y): crop #1 all N of a row, crop #2 its one
+SQ_LOCAL int sq_crop_slots(int mode, const Dims& d) { return mode == CROP_PROP1 ? d.N : 1; }
+// Dims of the pass's launches for B sequences: frames whose H * W is not a multiple of 4 are read from a zero-padded copy of pitch P4
+// (made once in the prologue), and `spec` says which of the slot loop's kernels run in their specialised instantiations (sqair_glue.h)
+SQ_LOCAL Dims sq_pass_dims(const SqairHandle* h, int B, int spec_mask) {
+  Dims d = make_dims(h->cfg, B);
+  const int P_ = h->cfg.img_h * h->cfg.img_w;
+  if ((P_ & 3) != 0) d.P4 = (P_ + 3) / 4 * 4;
+  d.spec = spec_mask && sq_spec_ok(d) ? (spec_mask & SPEC_ALL) : 0;
+  return d;
 }
 
 static int emit_crop(SqairHandle* h, const CropArgs& ca, POff po, Dims d, int nslots, hipStream_t s) {
@@ -876,7 +922,7 @@ static bool sq_chain_on(const SqairHandle* h, int T, int B) {
 #else
   const SqairConfig& c = h->cfg;
   return h->opt_slot_chain && c.rnn_cell == RNN_VANILLA && c.time_cell == CELL_GRU && !c.sample_from_prior &&
-         c.n_hidden == 256 && can_fuse_tail(h, L_PROP_RNN) && can_fuse_tail(h, L_DISC_RNN) && B * c.k_particles <= 320 && 2 * T <= SQ_CHAIN_MAX_LAUNCHES;
+         c.n_hidden == 256 && sq_can_fuse_tail(h, L_PROP_RNN) && sq_can_fuse_tail(h, L_DISC_RNN) && B * c.k_particles <= 320 && 2 * T <= SQ_CHAIN_MAX_LAUNCHES;
 #endif
 }
 
@@ -925,14 +971,13 @@ int sq_prior_step(SqairHandle* h, const float* packed, hipStream_t s, int M, con
 // frame; the slot step itself (sq_forward_impl: slot_front, slot_tail) is the same code for both.
 struct SlotPhase {
   int ph;                             // tape phase
-  LayerId rnn, rnn2, t1, t2, s1;
+  LayerId rnn, rnn2, t1, t2;
   const float *init_rec, *rnn_init;   // slot 0's previous record and RNN state ([hidden | cell] with an LSTM slot RNN)
   float* rec;                         // the frame's records of this phase
   const float* pre;                   // hoisted slot-RNN pre-activations: slot k at pre + k * pre_step, row stride pre_ld
   int pre_step, pre_ld;
   const float* pre_t1;                // T1's hoisted addend, laid out like `pre` (propagation), or none
   const float* w3;                    // the transform's output layer (crop #2)
-  int w2_off, b2_off;                 // the steps predictor's output layer (slot tail)
   bool fuse;                          // the slot's tail rides in the next slot's VanillaRNN launch (k_rnn_tail)
 };
 
@@ -961,20 +1006,18 @@ SQ_LOCAL int sq_forward_impl(SqairHandle* h, const float* flat, const float* pac
   const int nh = c.n_hidden, nw = c.n_what, N = c.n_steps_per_image, K = c.k_particles;
   const int R = B * K, M = R * N, G2 = c.glimpse_size * c.glimpse_size, P_ = c.img_h * c.img_w;
   const int nzw = 4 + nw + 1;
-  Dims d = make_dims(c, B);
+  const Dims d = sq_pass_dims(h, B, h->opt_specialised ? h->opt_specialised_mask : 0);
   const POff po = h->po;
   const Workspace w = sq_carve(h, T, B, wsbase, train);
   // Frames are GEMM A operands (the input encoder) and 16-byte staging units (crop adjoint): their rows must start 16-byte
   // aligned.  H * W not a multiple of 4 (the reference takes any frame size): the pass works on a zero-padded copy with pitch
   // P4 = H * W rounded up to 4, made once in the prologue; otherwise on the caller's buffer as it is.
   const float* const obs_user = obs;
-  if ((P_ & 3) != 0) { d.P4 = (P_ + 3) / 4 * 4; obs = w.obs_p; }
-  d.spec = h->opt_specialised && sq_spec_ok(d) ? (h->opt_specialised_mask & SPEC_ALL) : 0;   // (sqair_glue.h: the slot loop's kernels with this family's dimensions compiled in)
+  if ((P_ & 3) != 0) obs = w.obs_p;   // (d.P4, and d.spec -- the slot loop's kernels with this family's dimensions compiled in: sq_pass_dims)
   const int PL = d.P4;
   const int pre_ld = h->layers[L_PRE].nt * 16;
   const int RW = rec::W, snh = d.snh, psnh = d.psnh;
   const int rw = sq_rnn_width(c);  // slot-RNN pre-activation width; pre columns: [rnn rw | T1 nh | S1 nh/2 | GRU z, r]
-  const PackedLayout pl = packed_layout(h);
   // the carried state's rows of frame t of the pass (k_state_import: t = 0, k_state_export: t = T)
   auto state_at = [&](int t, int t0) {
     return sq_state_args(h, st, R, w.rec_m_all + (size_t)t * M * RW, w.state(w.temporal_m, t, w.snh), w.state(w.prior_m, t, w.psnh),
@@ -1033,9 +1076,9 @@ SQ_LOCAL int sq_forward_impl(SqairHandle* h, const float* flat, const float* pac
 #define SQAIR_TAIL_FUSION_ROWS_DEFAULT 560
 #endif
   static const int tail_rows = SQ_KNOB_INT("SQAIR_TAIL_FUSION_ROWS", SQAIR_TAIL_FUSION_ROWS_DEFAULT);
-  const bool fuse_prop = d.R <= tail_rows && can_fuse_tail(h, L_PROP_RNN), fuse_disc = d.R <= tail_rows && can_fuse_tail(h, L_DISC_RNN);
+  const bool fuse_prop = d.R <= tail_rows && sq_can_fuse_tail(h, L_PROP_RNN), fuse_disc = d.R <= tail_rows && sq_can_fuse_tail(h, L_DISC_RNN);
   if (w.chain && !(fuse_prop && fuse_disc)) { sq_set_error(h, "slot chain: tail fusion off"); return -3; }
-  const bool fw = sq_what_fusion(h, train, w.chain);   // the what sample in the producing layer's epilogue (sqair_glue.h: WhatArgs)
+  const bool fw = sq_what_fusion(h, train, w.chain, R);   // the what sample in the producing layer's epilogue (sqair_glue.h: WhatArgs)
   TailArgs pending_tail; memset(&pending_tail, 0, sizeof(pending_tail));
   for (int t = 0; t < T; ++t) {
     const int pp = t & 1, pn = pp ^ 1;
@@ -1079,10 +1122,10 @@ SQ_LOCAL int sq_forward_impl(SqairHandle* h, const float* flat, const float* pac
     }
     // ---- C. crop #1 at where_{t-1} + bias, masked, encoded -> loc1 (core.py:293-294) ----
     {
-      CropArgs ca; memset(&ca, 0, sizeof(ca));
-      ca.mode = CROP_PROP1; ca.img = img; ca.mask = c.masked_glimpse ? mask : nullptr; ca.mask_row_mul = N;
-      ca.out = g1; ca.out_row_mul = N; ca.rec_prev = rec_prev; ca.wb = wb; ca.wb_ld = WB_LD; ca.flat = flat;
-      emit_crop(h, ca, po, d, N, s);
+      CropOperands co; memset(&co, 0, sizeof(co));
+      co.mode = CROP_PROP1; co.img = img; co.mask = c.masked_glimpse ? mask : nullptr; co.mask_row_mul = N;
+      co.out = g1; co.out_row_mul = N; co.rec_prev = rec_prev; co.wb = wb; co.wb_ld = WB_LD; co.flat = flat;
+      emit_crop(h, sq_crop_args(co), po, d, sq_crop_slots(CROP_PROP1, d), s);
       Lin a; a.seg(g1, G2, G2).out(pea, nh).act(ACT_ELU); RUN(a, L_GENC0, M);
       Lin b; b.seg(pea, nh, nh).out(peb, nh).act(ACT_ELU); RUN(b, L_GENC1, M);
       Lin l; l.seg(peb, nh, nh).out(m1, M1_LD); RUN(l, L_WHAT_LOC, M);
@@ -1096,13 +1139,13 @@ SQ_LOCAL int sq_forward_impl(SqairHandle* h, const float* flat, const float* pac
       }
     }
     // ---- the slot step of both slot loops ----
-    const SlotPhase prop = {0, L_PROP_RNN, L_PROP_RNN2, L_PROP_T1, L_PROP_T2, L_PROP_S1, w.zero_rec, w.prop_rnn_init, rec_p_t,
-                            w.pre, pre_ld, N * pre_ld, w.pre + rw, w.w3_prop, po.prop_steps_l1_w, po.prop_steps_l1_b, fuse_prop};
-    const SlotPhase disc = {1, L_DISC_RNN, L_DISC_RNN2, L_DISC_T1, L_DISC_T2, L_DISC_S1, w.disc_init_rec, w.disc_rnn_init, rec_d_t,
-                            w.pre_d, 0, rw, nullptr, w.w3_disc, po.disc_steps_l1_w, po.disc_steps_l1_b, fuse_disc};
-    // slot RNN -> T1 -> T2 -> crop #2 (`ca` arrives with the phase's own fields) -> glimpse encoder (the what head unless the
+    const SlotPhase prop = {0, L_PROP_RNN, L_PROP_RNN2, L_PROP_T1, L_PROP_T2, w.zero_rec, w.prop_rnn_init, rec_p_t,
+                            w.pre, pre_ld, N * pre_ld, w.pre + rw, w.w3_prop, fuse_prop};
+    const SlotPhase disc = {1, L_DISC_RNN, L_DISC_RNN2, L_DISC_T1, L_DISC_T2, w.disc_init_rec, w.disc_rnn_init, rec_d_t,
+                            w.pre_d, 0, rw, nullptr, w.w3_disc, fuse_disc};
+    // slot RNN -> T1 -> T2 -> crop #2 (`co` arrives with the phase's own fields) -> glimpse encoder (the what head unless the
     // slot's what sample is fused into its own launch)
-    auto slot_front = [&](const SlotPhase& sp, int k, CropArgs ca, bool what_head) -> int {
+    auto slot_front = [&](const SlotPhase& sp, int k, CropOperands co, bool what_head) -> int {
       const int rl = w.sld(nh), t1l = w.sld(T1_LD);
       const float* pre_k = sp.pre + (size_t)k * sp.pre_step;
       float* r_k = w.rslot(t, sp.ph, k);
@@ -1132,7 +1175,7 @@ SQ_LOCAL int sq_forward_impl(SqairHandle* h, const float* flat, const float* pac
         b2.a.o1 = g3 + 2 * nh; b2.a.o1_ld = g3l;
         RUN(b2, sp.rnn2, R);
       } else if (k > 0 && sp.fuse) {  // the previous slot's tail rides in this launch
-        const int rc = run_rnn_tail(h, pending_tail, d, sp.rnn, w.rslot(t, sp.ph, k - 1), rl, pre_k, sp.pre_ld, r_k, rl, packed, s);
+        const int rc = sq_run_rnn_tail(h, pending_tail, d, sp.rnn, w.rslot(t, sp.ph, k - 1), rl, pre_k, sp.pre_ld, r_k, rl, packed, s);
         if (rc != 0) return rc;
       } else {  // (VanillaRNN: rw == nh)
         a.add(pre_k, sp.pre_ld, nh).out(r_k, rl).act(ACT_TANH);
@@ -1143,10 +1186,10 @@ SQ_LOCAL int sq_forward_impl(SqairHandle* h, const float* flat, const float* pac
       if (sp.pre_t1) b.add(sp.pre_t1 + (size_t)k * sp.pre_step, sp.pre_ld, nh + nh / 2);
       RUN(b, sp.t1, R);
       Lin cc; cc.seg(t1, t1l, nh).out(t2, rl).act(ACT_ELU); RUN(cc, sp.t2, R);
-      ca.img = img; ca.out = g2; ca.out_row_mul = w.tape ? N : 1; ca.rec_new = sp.rec; ca.t2 = t2; ca.t2_ld = rl; ca.w3 = sp.w3;
-      ca.noise = nz; ca.flat = flat; ca.slot = k;
-      if (train) { ca.tp_out = w.slot(w.tp, TP_LD, t, sp.ph, k); ca.tp_out_ld = w.sld(TP_LD); }
-      emit_crop(h, ca, po, d, 1, s);
+      co.img = img; co.out = g2; co.out_row_mul = w.tape ? N : 1; co.rec_new = sp.rec; co.t2 = t2; co.t2_ld = rl; co.w3 = sp.w3;
+      co.noise = nz; co.flat = flat; co.slot = k;
+      if (train) { co.tp_out = w.slot(w.tp, TP_LD, t, sp.ph, k); co.tp_out_ld = w.sld(TP_LD); }
+      emit_crop(h, sq_crop_args(co), po, d, sq_crop_slots(co.mode, d), s);
       // (three dependent slot layers, one launch each: a single multi-layer launch with in-launch hand-offs was built and
       //  measured slower twice in round 1 -- tools/xcd_team.hip, DESIGN.md section 8 -- and left the library)
       Lin ea; ea.seg(g2, w.sld(G2), G2).out(e1, rl).act(ACT_ELU); RUN(ea, L_GENC0, R);
@@ -1159,12 +1202,12 @@ SQ_LOCAL int sq_forward_impl(SqairHandle* h, const float* flat, const float* pac
     };
     // the slot's tail (sqair_glue.h: TailArgs): launched now, or handed to the next slot's RNN launch
     auto slot_tail = [&](const SlotPhase& sp, int k, const float* hraw, int h_ld) {
-      TailArgs ta; memset(&ta, 0, sizeof(ta));
-      ta.is_disc = sp.ph; ta.slot = k; ta.hraw = hraw; ta.h_ld = h_ld; ta.enc = w.slot(w.enc, ENC_LD, t, sp.ph, k); ta.enc_ld = w.sld(ENC_LD);
-      ta.rec_prev = rec_prev; ta.rec_new = sp.rec; ta.noise = nz; ta.s1p = w.slot(w.t1, T1_LD, t, sp.ph, k) + nh; ta.s1p_ld = w.sld(T1_LD);
-      ta.wp = packed + pl.w + h->layers[sp.s1].w_off; ta.flat = flat; ta.w2_off = sp.w2_off; ta.b2_off = sp.b2_off;
-      if (train) { ta.s1h_out = w.slot(w.s1h, S1_LD, t, sp.ph, k); ta.s1h_ld = w.sld(S1_LD); }
-      ta.what_done = fw ? 1 : 0;
+      TailOperands io; memset(&io, 0, sizeof(io));
+      io.is_disc = sp.ph; io.slot = k; io.hraw = hraw; io.h_ld = h_ld; io.enc = w.slot(w.enc, ENC_LD, t, sp.ph, k); io.enc_ld = w.sld(ENC_LD);
+      io.rec_prev = rec_prev; io.rec_new = sp.rec; io.noise = nz; io.s1p = w.slot(w.t1, T1_LD, t, sp.ph, k) + nh; io.s1p_ld = w.sld(T1_LD);
+      if (train) { io.s1h_out = w.slot(w.s1h, S1_LD, t, sp.ph, k); io.s1h_ld = w.sld(S1_LD); }
+      io.what_done = fw ? 1 : 0;
+      const TailArgs ta = sq_tail_args(h, io, flat, packed);
       if (sp.fuse && k + 1 < N) pending_tail = ta;  // computed inside the next slot's RNN launch
       else emit_tail(h, ta, d, s);
     };
@@ -1173,9 +1216,9 @@ SQ_LOCAL int sq_forward_impl(SqairHandle* h, const float* flat, const float* pac
     if (w.chain) sq_chain_begin(h, d, po, wsbase, ws_bytes);
     for (int k = 0; k < N; ++k) {
       {
-        CropArgs ca; memset(&ca, 0, sizeof(ca));
-        ca.mode = CROP_PROP2; ca.mask = c.masked_glimpse ? mask : nullptr; ca.mask_row_mul = N; ca.mask_row_add = k; ca.rec_prev = rec_prev;
-        const int rc = slot_front(prop, k, ca, true);
+        CropOperands co; memset(&co, 0, sizeof(co));
+        co.mode = CROP_PROP2; co.mask = c.masked_glimpse ? mask : nullptr; co.mask_row_mul = N; co.mask_row_add = k; co.rec_prev = rec_prev;
+        const int rc = slot_front(prop, k, co, true);
         if (rc != 0) return rc;
       }
       const float* pre_k = w.pre + (size_t)k * pre_ld;
@@ -1213,7 +1256,7 @@ SQ_LOCAL int sq_forward_impl(SqairHandle* h, const float* flat, const float* pac
       }
       // the heads on the slot's new temporal state (snh == nh unless the temporal cell is an LSTM): the what sample in the
       // layer's own launch, or the raw heads for the tail
-      if (fw) { const int rc = run_what(h, 1, temporal_p + (size_t)k * snh, N * snh, R, k, nz, enc, el, rec_prev, rec_p_t, packed, s); if (rc != 0) return rc; }
+      if (fw) { const int rc = sq_run_what(h, 1, temporal_p + (size_t)k * snh, N * snh, R, k, nz, enc, el, rec_prev, rec_p_t, packed, s); if (rc != 0) return rc; }
       else { Lin hd; hd.seg(temporal_p + (size_t)k * snh, N * snh, nh).out(hraw, hl); RUN(hd, L_PROP_HEADS, R); }
       slot_tail(prop, k, hraw, hl);
     }
@@ -1244,13 +1287,13 @@ SQ_LOCAL int sq_forward_impl(SqairHandle* h, const float* flat, const float* pac
     if (w.chain) sq_chain_begin(h, d, po, wsbase, ws_bytes);
     for (int j = 0; j < N; ++j) {
       {
-        CropArgs ca; memset(&ca, 0, sizeof(ca));
-        ca.mode = CROP_DISC;
-        const int rc = slot_front(disc, j, ca, !fw);
+        CropOperands co; memset(&co, 0, sizeof(co));
+        co.mode = CROP_DISC;
+        const int rc = slot_front(disc, j, co, !fw);
         if (rc != 0) return rc;
       }
       if (fw) {   // the Gaussian head writes the slot's what sample itself (`enc` has no other reader in a discovery slot)
-        const int rc = run_what(h, 0, w.slot(w.e2, nh, t, 1, j), w.sld(nh), R, j, nz, nullptr, 0, nullptr, rec_d_t, packed, s);
+        const int rc = sq_run_what(h, 0, w.slot(w.e2, nh, t, 1, j), w.sld(nh), R, j, nz, nullptr, 0, nullptr, rec_d_t, packed, s);
         if (rc != 0) return rc;
       }
       slot_tail(disc, j, nullptr, 0);

@@ -146,6 +146,7 @@ long long sq_dense_route_hits(int route);
 
 // launchers (sqair_linear.hip)
 int sq_launch_linear(const LinArgs& a, const PackedLayer& L, hipStream_t s);
+bool sq_linear_leaves_split_k(int M, const PackedLayer& L);   // M rows of L go to the throughput kernels, not to split-K
 int sq_launch_pack(const float* flat, float* packed_w, const int* idx, int64_t n, hipStream_t s);
 int sq_launch_pack_bias(const float* flat, float* packed_b, const int* idxa, const int* idxb, int64_t n,
                         hipStream_t s);

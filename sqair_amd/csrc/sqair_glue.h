@@ -179,7 +179,11 @@ struct TailArgs {
 // (L_WHAT_HEAD_I, L_PROP_HEADS_I).  The element-wise work is then done ONCE per element by the lanes of one launch instead of
 // by every one of the 16 column-tile workgroups of the next slot's fused RNN + tail launch, whose per-workgroup instruction
 // stream is what that launch waits for (timing ablation: -2.8 % of the cfg-2 forward step).  Same arithmetic on the same
-// operands: results are bit-identical to the tail deriving the sample (tests/test_hip_forward.py).
+// operands: results are bit-identical to the tail deriving the sample from the plain layer's output AS LONG AS THAT LAYER RUNS ON THE
+// SPLIT-K KERNEL (k_linear_what is its GEMM: four per-wave partial sums, reduced in wave order).  The pass therefore takes the
+// fusion only below the row count at which sq_launch_linear hands the plain layers to the throughput kernels, which sum the K
+// chunks in sequence (sq_linear_leaves_split_k: 6000 rows; sq_what_fusion, sqair_api.hip; tests/test_hip_forward.py,
+// tests/test_slot_forward_kernels.py).
 struct WhatArgs {
   int mode;                          // 0: discovery (pairs loc, scale); 1: propagation (t_loc, t_scale, forget, input, temporal gate)
   const float* x; int x_ld;          // A operand [M][K = 16 kc] (one segment, 16-byte aligned rows)

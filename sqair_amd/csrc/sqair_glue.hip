@@ -879,7 +879,7 @@ int sq_launch_rnn_tail(const TailArgs& ta, Dims d, const float* hid, int hid_ld,
                        int add_ld, float* out, int out_ld, int n_out, hipStream_t s) {
 #ifdef SQAIR_WIDE
   (void)ta; (void)d; (void)hid; (void)hid_ld; (void)wp; (void)bias; (void)add; (void)add_ld; (void)out; (void)out_ld; (void)n_out; (void)s;
-  return -1;   // (the wide build never fuses the tail: can_fuse_tail, sqair_api.hip)
+  return -1;   // (the wide build never fuses the tail: sq_can_fuse_tail, sqair_api.hip)
 #else
   const int nt = (n_out + 15) / 16, mt = (d.R + 15) / 16;
   // More 16 x 16 tiles than CUs (from 272 particle rows on at n_hidden 256: cfg-4's 320): the launch would run in two rounds of

@@ -89,7 +89,8 @@ struct SqairHandle {
   int graph_nodes = 0;
   bool dense_log_on = false;           // sqair_debug_dense_log: {layer id, rows, K (padded to 16 per segment), N} of every dense launch
   std::vector<int> dense_log;          // of the passes issued while it was on (host side only: nothing changes on the device)
-  bool opt_what_fusion = true;  // sqair_set_option("what_fusion"): the what sample of a slot inside the layer that produces its operands (bit-identical)
+  bool opt_what_fusion = true;  // sqair_set_option("what_fusion"): the what sample of a slot inside the layer that produces its operands (bit-identical;
+                                // taken while the layers it replaces run on the split-K kernel: sq_what_fusion, sqair_api.hip)
   bool opt_specialised = true;  // sqair_set_option("specialised"): the slot loop's per-row kernels in their instantiations for the shipped dimensions (bit-identical)
   int opt_specialised_mask = 3;    // sqair_set_option("specialised_mask"): which of them (SPEC_* bits, sqair_glue.h); a measurement aid
   bool opt_tail_fusion = true;  // sqair_set_option("tail_fusion"): the tail of slot k inside slot k + 1's RNN launch (bit-identical either way)
@@ -286,6 +287,43 @@ SQ_LOCAL int sq_estimate_refusal(SqairHandle* h, int T, const SqairOutputs* outp
 // launch fails (dynamic LDS limit).  Of `h` only cfg and the error text.
 SQ_LOCAL int sq_launch_lane_answers(SqairHandle* h, const SqLaneSet& l, const float* rec, const float* glimpse, const SqairOutputs& out,
                                     int T, int B, hipStream_t s);
+// ---- the slot step's argument builders and launch helpers (sqair_api.hip), shared by the pass and by the forward unit entries
+// (sqair_slot_crop_test, sqair_slot_tail_test, sqair_linear_what_test: sqair_train.hip) ----
+// What a slot's tail takes from its caller; sq_tail_args adds what the handle resolves (the *_S1 pack, the steps.l1 offsets).
+struct TailOperands {
+  int is_disc, slot, what_done;
+  const float* hraw; int h_ld;
+  const float* enc; int enc_ld;
+  const float* rec_prev; float* rec_new;
+  const float* noise;
+  const float* s1p; int s1p_ld;
+  float* s1h_out; int s1h_ld;
+};
+// What a crop of the slot loop takes from its caller (the fields of CropArgs, sqair_glue.h); sq_crop_args keeps what the mode reads.
+struct CropOperands {
+  int mode, slot;
+  const float* img;
+  const float* mask; int mask_row_mul, mask_row_add;
+  float* out; int out_row_mul, out_row_add;
+  const float* rec_prev; float* rec_new;
+  const float* wb; int wb_ld;
+  const float* tp; int tp_ld;
+  const float* t2; int t2_ld;
+  const float* w3;
+  const float* noise; const float* flat;
+  float* tp_out; int tp_out_ld;
+};
+SQ_LOCAL CropArgs sq_crop_args(const CropOperands& o);
+SQ_LOCAL int sq_crop_slots(int mode, const Dims& d);
+SQ_LOCAL Dims sq_pass_dims(const SqairHandle* h, int B, int spec_mask);
+SQ_LOCAL TailArgs sq_tail_args(const SqairHandle* h, const TailOperands& io, const float* flat, const float* packed);
+// the tail of slot ta.slot can ride in the next slot's VanillaRNN layer `id` (L_PROP_RNN / L_DISC_RNN): k_rnn_tail serves it
+SQ_LOCAL bool sq_can_fuse_tail(const SqairHandle* h, LayerId id);
+SQ_LOCAL int sq_run_rnn_tail(SqairHandle* h, const TailArgs& ta, Dims d, LayerId id, const float* hid, int hid_ld, const float* add, int add_ld,
+                             float* out, int out_ld, const float* packed, hipStream_t s);
+// k_linear_what on the handle's L_WHAT_HEAD_I (mode 0) / L_PROP_HEADS_I (mode 1) pack
+SQ_LOCAL int sq_run_what(SqairHandle* h, int mode, const float* x, int x_ld, int M, int slot, const float* noise, const float* enc, int enc_ld,
+                         const float* rec_prev, float* rec_new, const float* packed, hipStream_t s);
 // section A of a frame of the pass, and a frame of the forecast: the propagation-prior cell and its statistics (sqair_api.hip)
 SQ_LOCAL int sq_prior_step(SqairHandle* h, const float* packed, hipStream_t s, int M, const float* rec_prev, const float* prior_prev,
                            float* prior_p, float* pgz, float* pgrh, float* pgxh, float* pstats, float* o3, float* o1);

@@ -926,6 +926,23 @@ long long sq_dense_route_hits(int route) { return route >= 0 && route < DR_COUNT
 
 static unsigned rmul_of(int rdiv) { return rdiv <= 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)rdiv) + 1u; }
 
+#ifndef SQAIR_MT_ROWS_DEFAULT
+#define SQAIR_MT_ROWS_DEFAULT 6000
+#endif
+// Whether a launch of M rows of layer L leaves the split-K kernel for the throughput variants (the comments inside sq_launch_linear
+// say why and where).  Those sum a column's K chunks in sequence, the split-K kernel in four per-wave partial sums: the last bits of
+// a result differ between the two families.  Whoever promises the split-K kernel's bits from another launch (sq_what_fusion,
+// sqair_api.hip) asks here, so that the numbers exist once.
+bool sq_linear_leaves_split_k(int M, const PackedLayer& L) {
+  static const int mt_rows = SQ_KNOB_INT("SQAIR_MT_ROWS", SQAIR_MT_ROWS_DEFAULT);  // measurement knob (tools/build_rev.sh WT <name> -D...)
+  // just below 2048 rows only the WIDE layers go to the LDS-tiled kernel (its 128 x 64 tiles then still number ~200):
+  // tools/time_linear.py, back to back, 1920 x 362 x 1152 35.7 -> 33.2 us, 1920 x 312 x 768 21.2 -> 19.2 (every 256 / 400-column
+  // layer would be twice as slow; at 1280 rows 362 x 1152 gains back to back, 24.3 -> 21.1, but not in the pass, and
+  // 312 x 768 loses, 14.7 -> 18.4).  cfg-4 (1920 rows per frame): forward 6.13 -> 6.07 ms, training 14.16 -> 14.12.
+  const bool mid_wide = L.kc > 4 && M >= 1792 && L.nt >= 48;
+  return M >= mt_rows || mid_wide;
+}
+
 int sq_launch_linear(const LinArgs& a_in, const PackedLayer& L, hipStream_t s) {
   LinArgs a = a_in;
   for (int i = 0; i < a.nseg; ++i) a.seg[i].rmul = rmul_of(a.seg[i].rdiv);
@@ -948,16 +965,7 @@ int sq_launch_linear(const LinArgs& a_in, const PackedLayer& L, hipStream_t s) {
   // 2560 x 256 x 256 in 8.4 us (the LDS-tiled kernel's best tile 11.1), 5120 x 256 x 256 in 15.2 (15.1).
   // Also tried for the 2048+ row launches and dropped: the split-K structure with a 32 x 32 and with a 64 x 64 workgroup tile
   // (half / a quarter of the operand bytes per output tile): 22 - 25 us against 16 - 17 us on 5120 x 256 x 256, back to back.
-#ifndef SQAIR_MT_ROWS_DEFAULT
-#define SQAIR_MT_ROWS_DEFAULT 6000
-#endif
-  static const int mt_rows = SQ_KNOB_INT("SQAIR_MT_ROWS", SQAIR_MT_ROWS_DEFAULT);  // measurement knob (tools/build_rev.sh WT <name> -D...)
-  // just below 2048 rows only the WIDE layers go to the LDS-tiled kernel (its 128 x 64 tiles then still number ~200):
-  // tools/time_linear.py, back to back, 1920 x 362 x 1152 35.7 -> 33.2 us, 1920 x 312 x 768 21.2 -> 19.2 (every 256 / 400-column
-  // layer would be twice as slow; at 1280 rows 362 x 1152 gains back to back, 24.3 -> 21.1, but not in the pass, and
-  // 312 x 768 loses, 14.7 -> 18.4).  cfg-4 (1920 rows per frame): forward 6.13 -> 6.07 ms, training 14.16 -> 14.12.
-  const bool mid_wide = L.kc > 4 && a.M >= 1792 && L.nt >= 48;
-  if (a.M >= mt_rows || mid_wide) {
+  if (sq_linear_leaves_split_k(a.M, L)) {
     // (all of them accumulate in the same order: the tile shape never changes a result)
     if (L.kc <= 4) {  // K <= 64: one block of loads, nothing to pipeline
       const dim3 grid_r(L.nt, (mt + 3) / 4);

@@ -1115,6 +1115,111 @@ extern "C" int sqair_logprob_bwd_test(SqairHandle* h, const SqairLogprobBwdTest*
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The forward kernels of the slot loop on raw device buffers (unit-test entries, tests/test_slot_forward_kernels.py): k_crop_row,
+// k_slot_tail, k_rnn_tail and k_linear_what through the argument builders and the launch helpers the pass itself calls (sq_pass_dims,
+// sq_crop_args, sq_tail_args, sq_run_rnn_tail, sq_run_what: sqair_api.hip), so that what a test launches is what a pass launches.
+// ------------------------------------------------------------------------------------------------
+extern "C" int sqair_slot_crop_test(SqairHandle* h, const SqairSlotCropTest* t, void* stream) {
+  static const char* who = "sqair_slot_crop_test";
+  if (!h) return -1;
+  if (!t) return sq_refuse(h, who, "no description");
+  if (t->B < 1) return sq_refuse(h, who, "B < 1");
+  if (t->mode != CROP_PROP1 && t->mode != CROP_PROP2 && t->mode != CROP_DISC) return sq_refuse(h, who, "mode is not 1, 2 or 3");
+  const Dims d = sq_pass_dims(h, t->B, t->specialised ? SPEC_CROP : 0);
+  const bool p1 = t->mode == CROP_PROP1;
+  const int nslots = sq_crop_slots(t->mode, d);
+  if (!p1 && (t->slot < 0 || t->slot >= d.N)) return sq_refuse(h, who, "slot outside [0, N)");
+  if (!t->img || !t->out || !t->flat) return sq_refuse(h, who, "a required pointer is NULL");
+  if (p1 && (!t->rec_prev || !t->wb)) return sq_refuse(h, who, "mode 1 needs rec_prev and wb");
+  if (!p1 && (!t->rec_new || !t->noise)) return sq_refuse(h, who, "modes 2 and 3 need rec_new and noise");
+  if (t->mode == CROP_PROP2 && !t->rec_prev) return sq_refuse(h, who, "mode 2 needs rec_prev");
+  if (!p1 && (t->tp != nullptr) == (t->t2 != nullptr)) return sq_refuse(h, who, "modes 2 and 3 need exactly one of tp and t2");
+  if (!p1 && t->t2 && !t->w3) return sq_refuse(h, who, "t2 needs w3");
+  if (!p1 && t->tp_out && !t->t2) return sq_refuse(h, who, "tp_out needs t2 (the launch writes it from its own output layer)");
+  if ((p1 && t->wb_ld < 4) || (!p1 && t->tp && t->tp_ld < 8) || (!p1 && t->t2 && t->t2_ld < d.nh) || (!p1 && t->tp_out && t->tp_out_ld < 8) ||
+      t->out_row_mul < nslots || t->out_row_add < 0 || (t->mask && (t->mask_row_mul < nslots || t->mask_row_add < 0)))
+    return sq_refuse(h, who, "a pitch is smaller than the width");
+  if (!p1 && t->t2 && ((reinterpret_cast<uintptr_t>(t->t2) & 15) != 0 || (t->t2_ld & 3) != 0 || (reinterpret_cast<uintptr_t>(t->w3) & 15) != 0))
+    return sq_refuse(h, who, "t2 / w3 are not 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  CropOperands co; memset(&co, 0, sizeof(co));
+  co.mode = t->mode; co.slot = t->slot; co.img = t->img; co.mask = t->mask; co.mask_row_mul = t->mask_row_mul; co.mask_row_add = t->mask_row_add;
+  co.out = t->out; co.out_row_mul = t->out_row_mul; co.out_row_add = t->out_row_add; co.rec_prev = t->rec_prev; co.rec_new = t->rec_new;
+  co.wb = t->wb; co.wb_ld = t->wb_ld; co.tp = t->tp; co.tp_ld = t->tp_ld; co.t2 = t->t2; co.t2_ld = t->t2_ld; co.w3 = t->w3; co.noise = t->noise;
+  co.flat = t->flat; co.tp_out = t->tp_out; co.tp_out_ld = t->tp_out_ld;
+  const int rc = sq_launch_crop(sq_crop_args(co), h->po, d, nslots, s);
+  if (rc != 0) { sq_set_error(h, std::string(who) + ": launch refused"); return rc; }
+  SQ_CHECK_HIP(hipGetLastError());
+  SQ_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int sqair_slot_tail_test(SqairHandle* h, const SqairSlotTailTest* t, void* stream) {
+  static const char* who = "sqair_slot_tail_test";
+  if (!h) return -1;
+  if (!t) return sq_refuse(h, who, "no description");
+  if (t->B < 1) return sq_refuse(h, who, "B < 1");
+  const Dims d = make_dims(h->cfg, t->B);
+  const int nsp = d.nh / 2;
+  const bool disc = t->is_disc != 0, wd = t->what_done != 0, rnn = t->out != nullptr;
+  if (t->slot < 0 || t->slot >= d.N) return sq_refuse(h, who, "slot outside [0, N)");
+#ifdef SQAIR_WIDE
+  if (wd) return sq_refuse(h, who, "what_done: the wide library has no what fusion");
+#endif
+  if (!t->rec_new || !t->noise || !t->s1p || !t->flat || !t->packed) return sq_refuse(h, who, "a required pointer is NULL");
+  if (!wd && !t->enc) return sq_refuse(h, who, "a required pointer is NULL (enc: read unless what_done)");
+  if (!disc && (!t->rec_prev || (!wd && !t->hraw))) return sq_refuse(h, who, "propagation needs rec_prev and, unless what_done, hraw");
+  if (t->s1p_ld < nsp || (t->s1h_out && t->s1h_ld < nsp) || (!wd && t->enc_ld < 2 * d.nw) || (!disc && !wd && t->h_ld < 5 * d.nw))
+    return sq_refuse(h, who, "a pitch is smaller than the width");
+  if (rnn) {
+    const LayerId id = disc ? L_DISC_RNN : L_PROP_RNN;
+    if (!sq_can_fuse_tail(h, id)) return sq_refuse(h, who, "the RNN block needs a configuration whose tail can ride in the next slot's layer");
+    if (t->slot + 1 >= d.N) return sq_refuse(h, who, "the RNN block is the NEXT slot's layer: slot + 1 outside [0, N)");
+    if (!t->hid || !t->add) return sq_refuse(h, who, "the RNN block needs hid and add");
+    if (t->hid_ld < d.nh || t->add_ld < d.nh || t->out_ld < d.nh) return sq_refuse(h, who, "a pitch is smaller than the width");
+    if ((reinterpret_cast<uintptr_t>(t->hid) & 15) != 0 || (t->hid_ld & 3) != 0) return sq_refuse(h, who, "hid is not a 16-byte aligned A operand");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  TailOperands io; memset(&io, 0, sizeof(io));
+  io.is_disc = disc ? 1 : 0; io.slot = t->slot; io.what_done = wd ? 1 : 0; io.hraw = t->hraw; io.h_ld = t->h_ld; io.enc = t->enc; io.enc_ld = t->enc_ld;
+  io.rec_prev = t->rec_prev; io.rec_new = t->rec_new; io.noise = t->noise; io.s1p = t->s1p; io.s1p_ld = t->s1p_ld;
+  io.s1h_out = t->s1h_out; io.s1h_ld = t->s1h_ld;
+  const TailArgs ta = sq_tail_args(h, io, t->flat, t->packed);
+  const int rc = rnn ? sq_run_rnn_tail(h, ta, d, disc ? L_DISC_RNN : L_PROP_RNN, t->hid, t->hid_ld, t->add, t->add_ld, t->out, t->out_ld, t->packed, s)
+                     : sq_launch_slot_tail(ta, d, s);
+  if (rc != 0) { sq_set_error(h, std::string(who) + ": launch refused"); return rc; }
+  SQ_CHECK_HIP(hipGetLastError());
+  SQ_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int sqair_linear_what_test(SqairHandle* h, const SqairLinearWhatTest* t, void* stream) {
+  static const char* who = "sqair_linear_what_test";
+  if (!h) return -1;
+  if (!t) return sq_refuse(h, who, "no description");
+#ifdef SQAIR_WIDE
+  return sq_refuse(h, who, "the wide library has no what fusion");
+#else
+  const SqairConfig& c = h->cfg;
+  if (c.n_hidden != 128 && c.n_hidden != 256) return sq_refuse(h, who, "n_hidden is neither 128 nor 256");
+  if (t->B < 1) return sq_refuse(h, who, "B < 1");
+  if (t->mode != 0 && t->mode != 1) return sq_refuse(h, who, "mode is not 0 or 1");
+  if (t->slot < 0 || t->slot >= c.n_steps_per_image) return sq_refuse(h, who, "slot outside [0, N)");
+  if (!t->x || !t->noise || !t->rec_new || !t->packed) return sq_refuse(h, who, "a required pointer is NULL");
+  if (t->mode == 1 && (!t->enc || !t->rec_prev)) return sq_refuse(h, who, "mode 1 needs enc and rec_prev");
+  if (t->x_ld < c.n_hidden || (t->mode == 1 && t->enc_ld < 2 * c.n_what)) return sq_refuse(h, who, "a pitch is smaller than the width");
+  if ((int64_t)t->B * c.k_particles > (int64_t)1 << 24) return sq_refuse(h, who, "more than 2^24 rows");
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = sq_run_what(h, t->mode, t->x, t->x_ld, t->B * c.k_particles, t->slot, t->noise, t->enc, t->enc_ld, t->rec_prev, t->rec_new,
+                             t->packed, s);
+  if (rc != 0) { sq_set_error(h, std::string(who) + ": launch refused (x is not a 16-byte aligned A operand)"); return rc; }
+  SQ_CHECK_HIP(hipGetLastError());
+  SQ_CHECK_HIP(hipStreamSynchronize(s));
+  return 0;
+#endif
+}
+
 extern "C" int sqair_capture_begin(SqairHandle* h, void* stream) {
   if (!h) return -1;
   SQ_CHECK_HIP(hipStreamBeginCapture((hipStream_t)stream, hipStreamCaptureModeThreadLocal));

@@ -20,6 +20,12 @@ from oracle import sqair_oracle as O
 MIN_STD = 1e-2          # oracle.make_cfg: min_std; the where scales add the same constant (propagation_core / discovery_core)
 GATE_SCALE = 0.9999     # propagation_core: gates = sigmoid(.) * 0.9999
 WHERE_BIAS_SCALE = 0.1  # propagation_core: where_bias = MLP(.) * 0.1
+ABSENT_LOGIT = 88.0     # steps_logit: prev * logit + (prev - 1) * 88
+
+
+def gates_of(raw):
+    """propagation_core: the three gates (forget | input | temporal) from their raw pre-activations."""
+    return torch.sigmoid(raw) * GATE_SCALE
 
 
 def T(x, dtype):
@@ -70,7 +76,7 @@ def tail_forward(lv, c):
     else:
         h = lv["hraw"]
         t_loc, t_scale = h[..., :nw], O.softplus(h[..., nw:2 * nw]) + MIN_STD                # gaussian_head("prop.what_head")
-        gates = torch.sigmoid(h[..., 2 * nw:]) * GATE_SCALE
+        gates = gates_of(h[..., 2 * nw:])
         fg, ig, tg = gates[..., :nw], gates[..., nw:2 * nw], gates[..., 2 * nw:]
         what_loc = fg * lv["what_tm1"] + (1.0 - ig) * loc2 + (1.0 - tg) * t_loc
         what_scale = (1.0 - ig) * scale2 + (1.0 - tg) * t_scale
@@ -78,7 +84,7 @@ def tail_forward(lv, c):
     hidden = O.elu(lv["s1_rest"] + what @ c["w_what"])                                       # mlp_1hidden_out, the `what` rows apart
     raw = hidden @ c["w2"] + c["b2"]
     prev = c["prev"]
-    return dict(what=what, what_loc=what_loc, what_scale=what_scale, logit=prev * raw + (prev - 1.0) * 88.0, raw=raw, hidden=hidden)
+    return dict(what=what, what_loc=what_loc, what_scale=what_scale, logit=prev * raw + (prev - 1.0) * ABSENT_LOGIT, raw=raw, hidden=hidden)
 
 
 def tail_leaves(tape, c, dtype, enc_pre):

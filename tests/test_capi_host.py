@@ -358,6 +358,103 @@ def test_slot_adjoint_test_entries_refuse_host_side():
             lib.sqair_destroy(big)
 
 
+def test_slot_forward_test_entries_refuse_host_side():
+    """sqair_slot_crop_test / sqair_slot_tail_test / sqair_linear_what_test (tests/test_slot_forward_kernels.py drives them on the
+    GPU): exported by both builds under the unchanged ABI version; a NULL required pointer, a mode or slot out of range, B < 1, a pitch
+    below the width, an operand that is not 16-byte aligned, tp together with t2, tp_out without t2, the RNN block where the tail
+    cannot ride in the next slot's layer (the wide library, a GRU slot cell, the last slot), what_done and the whole of
+    sqair_linear_what_test on the wide library are refused with the entry's name in the error text before any HIP call (`buf` stands
+    for every device buffer: nothing reads it)."""
+    buf = (C.c_float * 16)()
+    CR, TL, WH = _capi.SqairSlotCropTest, _capi.SqairSlotTailTest, _capi.SqairLinearWhatTest
+    for path in (_capi.LIB_PATH, _capi.WIDE_LIB_PATH):
+        wide = path == _capi.WIDE_LIB_PATH
+        lib = _capi.lib(path)
+        assert lib.sqair_abi_version() == _capi.ABI_VERSION == 2
+        h, gru = C.c_void_p(), C.c_void_p()
+        assert lib.sqair_create(C.byref(make_config(make_flags(k_particles=2, n_steps_per_image=3), (50, 50))), C.byref(h)) == 0
+        assert lib.sqair_create(C.byref(make_config(make_flags(k_particles=2, n_steps_per_image=3, transition="GRU"), (50, 50))), C.byref(gru)) == 0
+        try:
+            def call(fn, cls, handle=h, **over):
+                assert fn in _capi.EXPORTED_SYMBOLS
+                return getattr(lib, fn)(handle, C.byref(_all_set(cls, buf, **over)), None), lib.sqair_last_error(handle)
+
+            def refused(fn, cls, handle=h, **over):
+                rc, err = call(fn, cls, handle, **over)
+                assert rc == -1 and err.startswith(fn.encode() + b": "), (fn, over, rc, err)
+                return err
+            for fn in ("sqair_slot_crop_test", "sqair_slot_tail_test", "sqair_linear_what_test"):
+                assert getattr(lib, fn)(None, None, None) == -1
+                assert getattr(lib, fn)(h, None, None) == -1 and lib.sqair_last_error(h).startswith(fn.encode())
+            # the crop: mode 2 with t2 (so tp NULL) is a description the entry accepts up to the launch
+            crop = dict(mode=2, slot=1, B=2, specialised=0, tp=None, out_row_add=0, mask_row_add=0)
+            for p in ("img", "out", "flat", "rec_new", "noise", "rec_prev", "w3"):
+                refused("sqair_slot_crop_test", CR, **dict(crop, **{p: None}))
+            for p in ("rec_prev", "wb"):
+                assert b"mode 1" in refused("sqair_slot_crop_test", CR, **dict(crop, mode=1, **{p: None}))
+            for mode in (0, 4):
+                assert b"mode" in refused("sqair_slot_crop_test", CR, **dict(crop, mode=mode))
+            for slot in (-1, 3):
+                assert b"slot" in refused("sqair_slot_crop_test", CR, **dict(crop, slot=slot))
+            assert b"B < 1" in refused("sqair_slot_crop_test", CR, **dict(crop, B=0))
+            assert b"exactly one" in refused("sqair_slot_crop_test", CR, **dict(crop, tp=C.addressof(buf)))
+            assert b"exactly one" in refused("sqair_slot_crop_test", CR, **dict(crop, t2=None))
+            assert b"tp_out needs t2" in refused("sqair_slot_crop_test", CR, **dict(crop, tp=C.addressof(buf), t2=None))
+            for ld, v in (("t2_ld", 255), ("tp_out_ld", 7), ("out_row_mul", 0), ("out_row_add", -1), ("mask_row_mul", 0), ("mask_row_add", -1)):
+                assert b"pitch" in refused("sqair_slot_crop_test", CR, **dict(crop, **{ld: v}))
+            assert b"pitch" in refused("sqair_slot_crop_test", CR, **dict(crop, tp=C.addressof(buf), t2=None, tp_out=None, tp_ld=7))
+            for ld, v in (("wb_ld", 3), ("out_row_mul", 2), ("mask_row_mul", 2)):   # crop #1 covers the N = 3 slots of a row
+                assert b"pitch" in refused("sqair_slot_crop_test", CR, **dict(crop, mode=1, **{ld: v}))
+            assert b"aligned" in refused("sqair_slot_crop_test", CR, **dict(crop, t2=C.addressof(buf) + 4))
+            assert b"aligned" in refused("sqair_slot_crop_test", CR, **dict(crop, w3=C.addressof(buf) + 8))
+            assert b"aligned" in refused("sqair_slot_crop_test", CR, **dict(crop, t2_ld=1026))
+            # the tail, without the RNN block
+            tail = dict(is_disc=0, slot=1, B=2, what_done=0, out=None)
+            for p in ("rec_new", "noise", "s1p", "flat", "packed", "enc"):
+                assert b"NULL" in refused("sqair_slot_tail_test", TL, **dict(tail, **{p: None}))
+            for p in ("rec_prev", "hraw"):
+                assert b"propagation needs" in refused("sqair_slot_tail_test", TL, **dict(tail, **{p: None}))
+            for slot in (-1, 3):
+                assert b"slot" in refused("sqair_slot_tail_test", TL, **dict(tail, slot=slot))
+            assert b"B < 1" in refused("sqair_slot_tail_test", TL, **dict(tail, B=0))
+            for ld, v in (("s1p_ld", 127), ("s1h_ld", 127), ("enc_ld", 99), ("h_ld", 249)):
+                assert b"pitch" in refused("sqair_slot_tail_test", TL, **dict(tail, **{ld: v}))
+            rnn = dict(tail, slot=0, out=C.addressof(buf))
+            if wide:
+                assert b"what_done" in refused("sqair_slot_tail_test", TL, **dict(tail, what_done=1))
+                assert b"RNN block" in refused("sqair_slot_tail_test", TL, **rnn)
+            else:
+                assert b"RNN block" in refused("sqair_slot_tail_test", TL, handle=gru, **rnn)          # a GRU slot cell: no fused tail
+                assert b"slot + 1" in refused("sqair_slot_tail_test", TL, **dict(rnn, slot=2))           # the last slot has no next layer
+                for p in ("hid", "add"):
+                    assert b"RNN block needs" in refused("sqair_slot_tail_test", TL, **dict(rnn, **{p: None}))
+                for ld in ("hid_ld", "add_ld", "out_ld"):
+                    assert b"pitch" in refused("sqair_slot_tail_test", TL, **dict(rnn, **{ld: 255}))
+                assert b"aligned" in refused("sqair_slot_tail_test", TL, **dict(rnn, hid=C.addressof(buf) + 4))
+                assert b"aligned" in refused("sqair_slot_tail_test", TL, **dict(rnn, hid_ld=1026))
+            # the head layer with the what sample in its epilogue
+            what = dict(mode=1, slot=1, B=2)
+            if wide:
+                assert b"wide library" in refused("sqair_linear_what_test", WH, **what)
+            else:
+                for p in ("x", "noise", "rec_new", "packed"):
+                    assert b"NULL" in refused("sqair_linear_what_test", WH, **dict(what, **{p: None}))
+                for p in ("enc", "rec_prev"):
+                    assert b"mode 1" in refused("sqair_linear_what_test", WH, **dict(what, **{p: None}))
+                for mode in (-1, 2):
+                    assert b"mode" in refused("sqair_linear_what_test", WH, **dict(what, mode=mode))
+                for slot in (-1, 3):
+                    assert b"slot" in refused("sqair_linear_what_test", WH, **dict(what, slot=slot))
+                assert b"B < 1" in refused("sqair_linear_what_test", WH, **dict(what, B=0))
+                for ld, v in (("x_ld", 255), ("enc_ld", 99)):
+                    assert b"pitch" in refused("sqair_linear_what_test", WH, **dict(what, **{ld: v}))
+                rc, err = call("sqair_linear_what_test", WH, **dict(what, x_ld=1026))                   # the launcher's own refusal: its code
+                assert rc == -5 and err.startswith(b"sqair_linear_what_test: "), (rc, err)
+        finally:
+            lib.sqair_destroy(h)
+            lib.sqair_destroy(gru)
+
+
 def test_dense_test_structs_have_the_header_layout(repo_root, tmp_path):
     """The descriptions of sqair_linear_contract_test / sqair_linear_dx_test are passed by address: the ctypes mirrors must have
     the size and the field offsets a C compiler gives the header's structs."""
@@ -369,7 +466,10 @@ def test_dense_test_structs_have_the_header_layout(repo_root, tmp_path):
                "SqairSlotTailBwdTest": _capi.SqairSlotTailBwdTest, "SqairCropChainBwdTest": _capi.SqairCropChainBwdTest,
                "SqairWhereParamGradsTest": _capi.SqairWhereParamGradsTest, "SqairGruGatesBwdTest": _capi.SqairGruGatesBwdTest,
                # the log-probability kernels (sqair_logprob_test, sqair_logprob_bwd_test)
-               "SqairLogprobTest": _capi.SqairLogprobTest, "SqairLogprobBwdTest": _capi.SqairLogprobBwdTest}
+               "SqairLogprobTest": _capi.SqairLogprobTest, "SqairLogprobBwdTest": _capi.SqairLogprobBwdTest,
+               # the slot loop's forward kernels (sqair_slot_crop_test, sqair_slot_tail_test, sqair_linear_what_test)
+               "SqairSlotCropTest": _capi.SqairSlotCropTest, "SqairSlotTailTest": _capi.SqairSlotTailTest,
+               "SqairLinearWhatTest": _capi.SqairLinearWhatTest}
     lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "sqair_hip.h"', "int main(void) {"]
     for name, cls in structs.items():
         lines.append('  printf("{0} %zu\\n", sizeof({0}));'.format(name))

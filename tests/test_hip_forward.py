@@ -2,6 +2,7 @@
 
 Bar (BASELINE.json north_star): ELBO / log p(x) terms within 1e-4 relative of the oracle on identical
 inputs, parameters and noise, with identical presence decisions (checked exactly)."""
+import ctypes as C
 import os
 
 import numpy as np
@@ -470,11 +471,14 @@ def test_tail_fused_into_the_next_rnn_layer_is_bitwise_identical(K, N, T, B, n_u
     (4, 2, 2, 3, (50, 50), dict(time_transition="LSTM")),                  # LSTM temporal cell: heads on the hidden half of [h | c]
     (4, 2, 2, 2, (50, 50), dict(time_transition="VanillaRNN", transition="GRU")),   # un-fused tails after a GRU slot cell
     (6, 2, 3, 3, (50, 50), dict(sample_from_prior=True, generate_after=1)),         # generation modes read the same records
-    (5, 3, 8, 2, (72, 64), dict(masked_glimpse=False, prop_prior_type="rw"))])      # eight slots, a frame beyond the staged crop
+    (5, 3, 8, 2, (72, 64), dict(masked_glimpse=False, prop_prior_type="rw")),       # eight slots, a frame beyond the staged crop
+    (94, 64, 2, 2, (50, 50), {})])                                         # 6016 rows: the plain head layers leave the split-K kernel
 def test_what_fusion_is_bit_identical(B, K, N, T, hw, flags):
     """The what sample of a slot computed in the epilogue of the layer that produces its operands (option what_fusion, default
     on for inference passes: sqair_glue.h WhatArgs, packs L_WHAT_HEAD_I / L_PROP_HEADS_I) against the slot tail deriving it:
-    the same arithmetic on the same operands -- every output bit for bit, eager and as a graph replay."""
+    the same arithmetic on the same operands -- every output bit for bit, eager and as a graph replay.  From 6000 particle rows on the
+    plain head layers run on the throughput kernels, whose sums k_linear_what's split-K GEMM does not reproduce: the pass then does not
+    take the fusion (sq_what_fusion, sqair_api.hip) and its dense launch log is the log of a pass with the option off."""
     from sqair_amd.model import Model, SqairCore
     F = make_flags(k_particles=K, n_steps_per_image=N, **flags)
     d = make_sequences(B, T=T, canvas=hw, seed=13)
@@ -488,12 +492,20 @@ def test_what_fusion_is_bit_identical(B, K, N, T, hw, flags):
         core = SqairCore(F, hw, options={"what_fusion": int(fusion)})
         core.set_params(P)
         m = Model(obs, None, core, K, presence=d["nums"])
+        if not use_graph:
+            assert core.lib.sqair_debug_dense_log(core.handle, 1) == 0
         m.run(noise=noise, use_graph=use_graph, gen_noise=gen_noise if flags.get("sample_from_prior") else None)
         torch.cuda.synchronize()
+        if not use_graph:   # {layer id, rows, K, N} of every dense launch of the eager pass
+            e = (C.c_int * 4)()
+            for i in range(core.lib.sqair_debug_dense_log(core.handle, 0)):
+                assert core.lib.sqair_debug_dense_log_entry(core.handle, i, e) == 0
+                launches[fusion].append(tuple(e))
         out = {k: v.detach().cpu().numpy().copy() for k, v in core.out.items()}
         out["log_weights"] = core.log_weights.cpu().numpy().copy()
         return out, core.lib.sqair_graph_nodes(core.handle) if use_graph else 0
 
+    launches = {False: [], True: []}
     ref, _ = run(False, False)
     assert float(ref["presence"].sum()) > 0
     for use_graph in (False, True):
@@ -502,6 +514,8 @@ def test_what_fusion_is_bit_identical(B, K, N, T, hw, flags):
             assert np.array_equal(v, got[k], equal_nan=True), (k, use_graph)
     _, nodes_off = run(False, True)
     assert nodes == nodes_off, "the fusion replaces launches one for one"
+    assert len(launches[True]) == len(launches[False]) > 0
+    assert (launches[True] == launches[False]) == (B * K >= 6000), "the fusion is taken below 6000 particle rows and only there"
     # (a training pass does not take the fusion: its results equal the inference pass's all the same)
     core = SqairCore(F, hw)
     core.set_params(P)
