@@ -561,10 +561,10 @@ extern "C" int sqair_create(const SqairConfig* cfg, SqairHandle** out) {
   h->cfg = *cfg;
   // (128, 256 or 512: the slot-tail adjoint indexes its LDS copy of steps.l0 with shifts -- n_hidden / 2 a power of two)
   h->cfg.n_hidden = cfg->n_hidden <= 128 ? 128 : (cfg->n_hidden <= 256 ? 256 : 512);
-  {  // the log-probability adjoint stages a row's 2N records, their gradients and the prior statistics in LDS (k_logprob_bwd)
-    const int64_t N = cfg->n_steps_per_image;
-    const int64_t lds = (4 * N * rec::W + 2 * N * rec::ZW + 2 * N * PS_LD + 2 * (800 + 13 * (N + 1))) * 4;
-    if (lds > 150 * 1024) { delete h; return -1; }   // (only the wide build can get here: n_steps_per_image 15, 16 with its 416-float record)
+  // the log-probability adjoint stages a row's 2N records, their gradients and the prior statistics in LDS (k_logprob_bwd)
+  if (sq_logprob_bwd_lds_bytes(make_dims(h->cfg, 1), PS_LD) > 150 * 1024) {   // (only the wide build can get here: n_steps_per_image
+    delete h;                                                                  // 15, 16 with its 416-float record)
+    return -1;
   }
   build_inventory(h);
   // GRU candidate matrices are bare [nh, nh] parameters: give build_plan's simple() a ".w" alias
@@ -1780,38 +1780,6 @@ extern "C" int sqair_st_insert_loglik(SqairHandle* h, const float* glimpse, cons
   ia.canvas = canvas; ia.data_ll = data_ll; ia.std_fg = c.output_std; ia.std_bg = c.background_std;
   if (sq_launch_insert_loglik(ia, d, (hipStream_t)stream) != 0) { sq_set_error(h, "sqair_st_insert_loglik: launch failed (dynamic LDS limit)"); return -2; }
   SQ_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-// Slot compaction on raw device buffers (unit-test entry; its adjoint: sqair_compact_bwd_test in sqair_train.hip): the launch of the
-// frame loop with the handle's Dims, one frame.  The layout query tells a caller the widths and columns of THIS build's buffers, so that a
-// test hard-codes neither the product nor the wide record.
-extern "C" int sqair_compact_test_layout(const SqairHandle* h, int32_t* out, int n) {
-  if (!h || !out || n < 0) return -1;
-  const Dims d = make_dims(h->cfg, 1);
-  const int32_t v[20] = {rec::W, rec::PRES, rec::ID, rec::WHERE, rec::WHAT, rec::LOGIT, rec::WHERE_LOC, rec::WHERE_SCALE, rec::WHAT_LOC,
-                         rec::WHAT_SCALE, rec::PROB, d.snh, d.psnh, (int32_t)h->n_params, h->po.temporal_init, h->po.prior_init,
-                         SQ_MAXN, d.N, d.nw, sq_spec_ok(d) ? 1 : 0};
-  for (int i = 0; i < n && i < 20; ++i) out[i] = v[i];
-  return 20;
-}
-extern "C" int sqair_compact_test(SqairHandle* h, const float* rec_p, const float* rec_d, const float* rec_prev, const float* temporal_p,
-                                  const float* prior_p, const float* last_id_prev, const float* flat, float* rec_next,
-                                  float* temporal_next, float* prior_next, float* last_id_next, int32_t* src_out,
-                                  const SqairOutputs* out, int t, int B, void* stream) {
-  if (!h || !rec_p || !rec_d || !rec_prev || !temporal_p || !prior_p || !last_id_prev || !flat || !rec_next || !temporal_next ||
-      !prior_next || !last_id_next || !src_out || !out || t < 0 || B < 1) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  Dims d = make_dims(h->cfg, B);
-  d.spec = h->opt_specialised && sq_spec_ok(d) ? (h->opt_specialised_mask & SPEC_ALL) : 0;
-  CompactArgs ka; memset(&ka, 0, sizeof(ka));
-  ka.rec_p = rec_p; ka.rec_d = rec_d; ka.rec_prev = rec_prev; ka.temporal_p = temporal_p; ka.prior_p = prior_p;
-  ka.last_id_prev = last_id_prev; ka.last_id_next = last_id_next;
-  ka.rec_next = rec_next; ka.temporal_next = temporal_next; ka.prior_next = prior_next;
-  ka.flat = flat; ka.t = t; ka.out = *out; ka.src_out = src_out;
-  sq_launch_compact(ka, h->po, d, s);
-  SQ_CHECK_HIP(hipGetLastError());
-  SQ_CHECK_HIP(hipStreamSynchronize(s));
   return 0;
 }
 

@@ -63,6 +63,8 @@ struct CropChainBwdArgs {
 };
 
 int sq_launch_logprob_bwd(const LogprobBwdArgs& a, POff po, Dims d, int T, hipStream_t s);
+// k_logprob_bwd's dynamic LDS at a pstats pitch: a row's records, statistics and small parameters with their gradients
+size_t sq_logprob_bwd_lds_bytes(const Dims& d, int ps_ld);
 int sq_launch_compact_bwd(const CompactBwdArgs& a, POff po, Dims d, hipStream_t s);
 int sq_launch_slot_tail_bwd(const TailBwdArgs& a, Dims d, hipStream_t s);
 int sq_launch_crop_chain_bwd(const CropChainBwdArgs& a, POff po, Dims d, int nslots, hipStream_t s);

@@ -1525,10 +1525,10 @@ __global__ __launch_bounds__(256) void k_logprob_bwd(const LogprobBwdArgs a, con
       }
 }
 
-int sq_launch_logprob_bwd(const LogprobBwdArgs& a, POff po, Dims d, int T, hipStream_t s) {
-  // compact layout of the small parameters (flat offset, length) -> LDS offset
-  SmallParamTab tab = {};
-  POff cp = po;
+// compact layout of the small parameters (flat offset, length) -> LDS offset: the table, the offsets in it (cp) and its length
+static int sq_small_param_layout(const POff& po, const Dims& d, SmallParamTab& tab, POff& cp) {
+  tab = {};
+  cp = po;
   int o = 0;
   auto seg = [&](int src, int len) {
     tab.src[tab.n] = src; tab.len[tab.n] = len; tab.dst[tab.n] = o;
@@ -1553,9 +1553,20 @@ int sq_launch_logprob_bwd(const LogprobBwdArgs& a, POff po, Dims d, int T, hipSt
   cp.step_prior_bias = seg(po.step_prior_bias, N1);
   cp.step_prior_tbias = seg(po.step_prior_tbias, N1);
   cp.cholesky = seg(po.cholesky, 10);
-  if (o > SQ_SMALL_MAX) return -1;
   tab.total = o;
-  const size_t shm = (4 * (size_t)d.N * rec::W + 2 * (size_t)d.N * rec::ZW + 2 * (size_t)d.N * a.ps_ld + 2 * (size_t)o) * sizeof(float);
+  return o;
+}
+size_t sq_logprob_bwd_lds_bytes(const Dims& d, int ps_ld) {
+  SmallParamTab tab;
+  POff cp;
+  const size_t small = (size_t)sq_small_param_layout(POff{}, d, tab, cp);
+  return (4 * (size_t)d.N * rec::W + 2 * (size_t)d.N * rec::ZW + 2 * (size_t)d.N * ps_ld + 2 * small) * sizeof(float);
+}
+int sq_launch_logprob_bwd(const LogprobBwdArgs& a, POff po, Dims d, int T, hipStream_t s) {
+  SmallParamTab tab;
+  POff cp;
+  if (sq_small_param_layout(po, d, tab, cp) > SQ_SMALL_MAX) return -1;
+  const size_t shm = sq_logprob_bwd_lds_bytes(d, a.ps_ld);
   if (shm > 150 * 1024) return -1;   // (sqair_create has checked this configuration against sq_logprob_bwd_lds_bytes)
   if (shm > 48 * 1024 && sq_allow_big_lds((const void*)k_logprob_bwd, 150 * 1024) != 0) return -2;
   SQ_LAUNCH(k_logprob_bwd, dim3(d.R, T), dim3(256), shm, s, a, cp, tab, d);

@@ -216,6 +216,7 @@ struct LogprobArgs {
   SqairConfig cfg;
 };
 int sq_launch_logprob(const LogprobArgs& a, POff po, Dims d, hipStream_t s);
+size_t sq_logprob_lds_bytes(const Dims& d, int ps_ld);   // k_logprob's dynamic LDS at a pstats pitch: what it stages per row
 
 // Carried model state (sqair_set_state).  One blob row per particle row r, 32-bit words:
 //   [N * rec::W slot records | N * snh temporal state | N * psnh prior state | last_id | frame counter (int32) | zero padding]

@@ -1196,9 +1196,12 @@ __global__ __launch_bounds__(64 * SQ_LOGPROB_WAVES) void k_logprob(const Logprob
   if (a.out.num_prop_steps_per_sample) a.out.num_prop_steps_per_sample[tr] = n_prop;
   if (a.out.num_disc_steps_per_sample) a.out.num_disc_steps_per_sample[tr] = n_disc;
 }
+size_t sq_logprob_lds_bytes(const Dims& d, int ps_ld) {
+  return ((size_t)3 * d.N * rec::W + (size_t)d.N * ps_ld + 128 + 128 + 516 + 20 + 40 + 4 + 20 + 11 * (d.N + 1) + 2 * (d.N + 1) + 16) *
+         sizeof(float);
+}
 int sq_launch_logprob(const LogprobArgs& a, POff po, Dims d, hipStream_t s) {
-  const size_t shm = ((size_t)3 * d.N * rec::W + (size_t)d.N * a.ps_ld + 128 + 128 + 516 + 20 + 40 + 4 + 20 +
-                      11 * (d.N + 1) + 2 * (d.N + 1) + 16) * sizeof(float);
+  const size_t shm = sq_logprob_lds_bytes(d, a.ps_ld);
   if (shm > 48 * 1024 && sq_allow_big_lds((const void*)k_logprob, 150 * 1024) != 0) return -2;
   SQ_LAUNCH(k_logprob, dim3(d.R, a.n_frames), dim3(64 * SQ_LOGPROB_WAVES), shm, s, a, po, d);
   return 0;

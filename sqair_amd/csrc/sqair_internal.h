@@ -1,5 +1,5 @@
 // Internal declarations shared by sqair_api.hip (handle, plan, forward pass), sqair_state.hip (carried state, forecast),
-// sqair_lane_api.hip (lane answers), sqair_train.hip (backward pass) and sqair_dense_test.hip (the dense unit-test entries).
+// sqair_lane_api.hip (lane answers), sqair_train.hip (backward pass), sqair_dense_test.hip and sqair_unit_test.hip (the unit-test entries).
 #pragma once
 #include <cstdio>
 #include <cstring>
@@ -239,6 +239,7 @@ struct Workspace {
 Workspace sq_carve(const SqairHandle* h, int T, int B, float* base, bool train);
 
 static inline int sq_no(SqairHandle* h, const std::string& why) { sq_set_error(h, why); return -1; }   // a refusal: -1 + error text
+static inline int sq_refuse(SqairHandle* h, const char* who, const std::string& why) { return sq_no(h, std::string(who) + ": " + why); }
 // -1 + "<who><name> must lie in (0, 1]" unless it does: an IoU or coverage threshold (NaN fails both comparisons)
 static inline int sq_unit_refusal(SqairHandle* h, const std::string& who, const char* name, float v) {
   return v > 0.0f && v <= 1.0f ? 0 : sq_no(h, who + name + " must lie in (0, 1]");
@@ -288,7 +289,7 @@ SQ_LOCAL int sq_estimate_refusal(SqairHandle* h, int T, const SqairOutputs* outp
 SQ_LOCAL int sq_launch_lane_answers(SqairHandle* h, const SqLaneSet& l, const float* rec, const float* glimpse, const SqairOutputs& out,
                                     int T, int B, hipStream_t s);
 // ---- the slot step's argument builders and launch helpers (sqair_api.hip), shared by the pass and by the forward unit entries
-// (sqair_slot_crop_test, sqair_slot_tail_test, sqair_linear_what_test: sqair_train.hip) ----
+// (sqair_slot_crop_test, sqair_slot_tail_test, sqair_linear_what_test: sqair_unit_test.hip) ----
 // What a slot's tail takes from its caller; sq_tail_args adds what the handle resolves (the *_S1 pack, the steps.l1 offsets).
 struct TailOperands {
   int is_disc, slot, what_done;
@@ -324,6 +325,11 @@ SQ_LOCAL int sq_run_rnn_tail(SqairHandle* h, const TailArgs& ta, Dims d, LayerId
 // k_linear_what on the handle's L_WHAT_HEAD_I (mode 0) / L_PROP_HEADS_I (mode 1) pack
 SQ_LOCAL int sq_run_what(SqairHandle* h, int mode, const float* x, int x_ld, int M, int slot, const float* noise, const float* enc, int enc_ld,
                          const float* rec_prev, float* rec_new, const float* packed, hipStream_t s);
+// what the training pass shares with the adjoint unit entries (sqair_train.hip): the Dims of a training pass over B sequences, and
+// the steps predictor's offsets a slot-tail adjoint reads
+struct TailBwdArgs;
+SQ_LOCAL Dims sq_train_dims(const SqairHandle* h, int B);
+SQ_LOCAL void sq_tail_param_offsets(const SqairHandle* h, bool is_disc, TailBwdArgs* ta);
 // section A of a frame of the pass, and a frame of the forecast: the propagation-prior cell and its statistics (sqair_api.hip)
 SQ_LOCAL int sq_prior_step(SqairHandle* h, const float* packed, hipStream_t s, int M, const float* rec_prev, const float* prior_prev,
                            float* prior_p, float* pgz, float* pgrh, float* pgxh, float* pstats, float* o3, float* o1);

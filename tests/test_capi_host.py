@@ -159,6 +159,20 @@ def test_limits_of_both_builds():
                 l.sqair_destroy(h)
 
 
+def test_accepted_slot_counts_of_both_builds():
+    """n_steps_per_image 1 .. 17: the product build takes up to its 8 slots; the wide build up to 14 -- at 15 and 16 a row of
+    k_logprob_bwd (sq_logprob_bwd_lds_bytes at the workspace's pstats pitch) no longer fits 150 KB of LDS.  The two sets are what
+    the library accepted when sqair_create still carried its own copy of that size, with 800 where the small parameters take 738."""
+    h = C.c_void_p()
+    for path, accepted in ((_capi.LIB_PATH, range(1, 9)), (_capi.WIDE_LIB_PATH, range(1, 15))):
+        l = _capi.lib(path)
+        for N in range(1, 18):
+            rc = l.sqair_create(C.byref(make_config(make_flags(n_steps_per_image=N), (50, 50))), C.byref(h))
+            assert (rc == 0) == (N in accepted), (l.sqair_build_flags(), N, rc)
+            if rc == 0:
+                l.sqair_destroy(h)
+
+
 def test_run_time_options_host_side():
     """sqair_set_option without a GPU: the in-launch slot chain lays the inference workspace out like the training tape for the
     configurations it serves (shipped cells, n_hidden 256, up to 320 particle rows) and leaves the others alone; the wide build

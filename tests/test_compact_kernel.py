@@ -19,13 +19,12 @@ from sqair_amd import _capi
 from sqair_amd.flags import make_flags
 from sqair_amd.model import make_config
 from tests.hip_util import stream
+from tests.kernel_unit import LAYOUT
 
 pytestmark = pytest.mark.gpu
 
 LSTM = dict(time_transition="LSTM", prior_transition="LSTM")
 HIDDEN = ("what", "what_loc", "what_scale", "where", "where_loc", "where_scale", "presence_prob", "presence", "presence_logit", "obj_id")
-LAYOUT = ("W", "PRES", "ID", "WHERE", "WHAT", "LOGIT", "WHERE_LOC", "WHERE_SCALE", "WHAT_LOC", "WHAT_SCALE", "PROB", "snh", "psnh",
-          "n_flat", "temporal_init", "prior_init", "max_slots", "N", "nw", "spec_ok")
 
 
 class _Handle:

@@ -22,8 +22,6 @@ float32 from the float64 GEMM result rounded to float32, and four times that eva
 No element is excluded from a comparison.  With SQAIR_PARITY_DIR set every case appends its family, largest error, bar and their
 ratio to dense_contract_parity.json there (the copy under profiles/ is such a file); without it nothing is written."""
 import ctypes as C
-import json
-import os
 
 import numpy as np
 import pytest
@@ -32,34 +30,26 @@ import torch
 from sqair_amd import _capi
 from sqair_amd.flags import make_flags
 from sqair_amd.model import make_config
-from tests.hip_util import stream
+from tests.hip_util import dev as _dev, stream
+from tests.kernel_unit import F64, bits as _bits, merge_parity
 
 pytestmark = pytest.mark.gpu
 
 NONE, ELU, TANH, SIGMOID, SOFTPLUS_MIN = range(5)
-PARITY_DIR_ENV = "SQAIR_PARITY_DIR"
-F64 = np.float64
 
 
 def _record(case, **figures):
-    where = os.environ.get(PARITY_DIR_ENV)
-    if not where:
-        return
-    path = os.path.join(where, "dense_contract_parity.json")
-    try:
-        os.makedirs(where, exist_ok=True)
-        data = json.load(open(path)) if os.path.exists(path) else {
-            "note": "per case of tests/test_dense_contract.py: the kernel family the launcher chose, the largest error against the "
-                    "float64 reference, the bar and err / bar.  Forward errors are absolute; dX errors are relative to the "
-                    "destination's largest reference value; GRU destinations add `f32_formula_err` (the same formulas in numpy "
-                    "float32 from the rounded float64 GEMM result) and `allowance` = 4 x that, which is part of their bar.",
-            "cases": {}}
+    def update(data):
         data["build_id"] = _capi.build_id()
         data["device"] = torch.cuda.get_device_name(0)
         data["cases"][case] = figures
-        json.dump(data, open(path, "w"), indent=1, sort_keys=True)
-    except OSError:
-        pass
+
+    merge_parity("dense_contract_parity.json", lambda: {
+        "note": "per case of tests/test_dense_contract.py: the kernel family the launcher chose, the largest error against the "
+                "float64 reference, the bar and err / bar.  Forward errors are absolute; dX errors are relative to the "
+                "destination's largest reference value; GRU destinations add `f32_formula_err` (the same formulas in numpy "
+                "float32 from the rounded float64 GEMM result) and `allowance` = 4 x that, which is part of their bar.",
+        "cases": {}}, update)
 
 
 @pytest.fixture(scope="module")
@@ -72,18 +62,10 @@ def handle():
     lib.sqair_destroy(h)
 
 
-def _dev(x):
-    return torch.as_tensor(np.ascontiguousarray(x)).cuda()
-
-
 def _took(before):
     """The routes counted since `before`, as {family: launches}."""
     after = _capi.dense_routes()
     return {k: after[k] - before[k] for k in after if after[k] != before[k]}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
 
 
 def _act64(v, act):

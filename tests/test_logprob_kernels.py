@@ -29,8 +29,6 @@ over that kernel's cases.  Presences and step counts are exact.  With SQAIR_PARI
 there (profiles/logprob_parity.json is such a file)."""
 import ctypes as C
 import itertools
-import json
-import os
 
 import numpy as np
 import pytest
@@ -38,18 +36,15 @@ import torch
 
 from oracle import sqair_oracle as O
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
-from sqair_amd.params import param_spec
+from tests import kernel_unit as U
 from tests import logprob_ref as LR
 from tests import slot_adjoint_ref as R
+from tests.hip_util import stream
+from tests.kernel_unit import F32, F64, Buf
+from tests.kernel_unit import f32 as _f32, mixed as _mixed
 
 pytestmark = pytest.mark.gpu
 
-PARITY_DIR_ENV = "SQAIR_PARITY_DIR"
-LAYOUT = ("W", "PRES", "ID", "WHERE", "WHAT", "LOGIT", "WHERE_LOC", "WHERE_SCALE", "WHAT_LOC", "WHAT_SCALE", "PROB", "snh", "psnh",
-          "n_flat", "temporal_init", "prior_init", "max_slots", "N", "nw", "spec_ok")
-F32, F64 = np.float32, np.float64
 HW, T_FRAMES, OUT_T0, OUT_FRAMES = (50, 50), 3, 2, 6           # the forward's outputs: frames 2 .. 4 of tensors 6 frames tall
 JOINT_MIN = 1e-12
 FLAG_COMBOS = list(itertools.product(("rnn", "rw", "guided"), (True, False), ("cat", "geom")))
@@ -85,97 +80,43 @@ for _i, (_N, _nw, _nu, _c) in enumerate([(3, 64, 16, ("rnn", True, "cat")), (3, 
 
 
 # ------------------------------------------------------------------------------------------------ handles
-_open = {}
+class _Handle(U.Handle):
+    """The handle of a case, with the oracle's configuration and the small parameters' segments of the flat buffer."""
 
-
-class _Handle:
     def __init__(self, case):
         c = CASES[case]
-        self.lib = _capi.lib(_capi.WIDE_LIB_PATH if c["wide"] else _capi.LIB_PATH)
-        self.F = make_flags(k_particles=c["K"], n_steps_per_image=c["N"], n_what=c["nw"], n_units=c["n_units"], **c["flags"])
-        self.cfg = make_config(self.F, HW)
+        U.Handle.__init__(self, case, c["wide"], HW, c["N"], c["K"], dict(c["flags"], n_what=c["nw"], n_units=c["n_units"]))
         self.ocfg = O.make_cfg(self.F, HW)
-        self.h = C.c_void_p()
-        assert self.lib.sqair_create(C.byref(self.cfg), C.byref(self.h)) == 0, case
-        buf = (C.c_int32 * 20)()
-        assert self.lib.sqair_compact_test_layout(self.h, buf, 20) == 20
-        self.L = dict(zip(LAYOUT, [int(v) for v in buf]))
-        self.N, self.nw, self.nh = c["N"], c["nw"], 32 * c["n_units"]
-        assert self.L["N"] == self.N and self.L["nw"] == self.nw and int(self.cfg.n_hidden) == self.nh
-        # n_hidden is not padded in these configurations: the kernels' parameter layout is the caller's
-        assert self.L["n_flat"] == self.lib.sqair_param_count(self.h) == self.lib.sqair_debug_padded_count(self.h, None)
-        off = {}
-        for i in range(self.lib.sqair_param_entries(self.h)):
-            cname, coff, cnum = C.c_char_p(), C.c_int64(), C.c_int64()
-            assert self.lib.sqair_param_entry(self.h, i, C.byref(cname), C.byref(coff), C.byref(cnum)) == 0
-            off[cname.value.decode()] = (int(coff.value), int(cnum.value))
-        shapes = {name: tuple(shape) for name, shape, _, _ in param_spec(self.F, HW)}
+        assert self.nw == c["nw"] and self.nh == 32 * c["n_units"]
         self.seg = {}                  # small parameter -> (first word in flat, shape)
         for name in LR.SMALL_PARAMS:
             if name.endswith(":e"):    # the expected-steps row of disc.rn.cond.w [4 + n_hidden + 1, 128]
-                o, n = off["disc.rn.cond.w"]
-                assert n == (4 + self.nh + 1) * 128 and shapes["disc.rn.cond.w"] == (4 + self.nh + 1, 128)
+                o, n = self.off["disc.rn.cond.w"]
+                assert n == (4 + self.nh + 1) * 128 and self.shapes["disc.rn.cond.w"] == (4 + self.nh + 1, 128)
                 self.seg[name] = (o + (4 + self.nh) * 128, (128,))
             else:
-                o, n = off[name]
-                assert n == int(np.prod(shapes[name]))
-                self.seg[name] = (o, shapes[name])
-
-    def check(self, rc, what):
-        assert rc == 0, (what, rc, self.lib.sqair_last_error(self.h))
+                o, n = self.off[name]
+                assert n == int(np.prod(self.shapes[name]))
+                self.seg[name] = (o, self.shapes[name])
 
 
 def handle(case):
-    if case not in _open:
-        _open[case] = _Handle(case)
-    return _open[case]
+    return U.handle(case, _Handle)
 
 
-def close_handles():
-    for hd in _open.values():
-        hd.lib.sqair_destroy(hd.h)
-    _open.clear()
+close_handles = U.close
+PARITY = U.Parity("logprob_parity.json",
+                  "per case of tests/test_logprob_kernels.py and output: the kernel's largest scaled error against the float64 "
+                  "reference, the bar (8 x the worst error of the same reference in float32 over the kernel's cases), the float32 "
+                  "reference's own error in this case; `bars`: per kernel and output the float32 figure the bar comes from; "
+                  "`worst_ratio`: per kernel the largest err / bar", worst_ratio=True)
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _close_handles():
     yield
     close_handles()
-    _write_parity()
-
-
-# ------------------------------------------------------------------------------------------------ figures
-_figures = {}
-
-
-def _write_parity():
-    where = os.environ.get(PARITY_DIR_ENV)
-    if not where or not _figures:
-        return
-    try:
-        os.makedirs(where, exist_ok=True)
-        path = os.path.join(where, "logprob_parity.json")
-        data = json.load(open(path)) if os.path.exists(path) else {
-            "note": "per case of tests/test_logprob_kernels.py and output: the kernel's largest scaled error against the float64 "
-                    "reference, the bar (8 x the worst error of the same reference in float32 over the kernel's cases), the float32 "
-                    "reference's own error in this case; `bars`: per kernel and output the float32 figure the bar comes from; "
-                    "`worst_ratio`: per kernel the largest err / bar",
-            "build_id": _capi.build_id(), "bars": {}, "cases": {}, "worst_ratio": {}}
-        for kernel, cases in _figures.items():
-            data["cases"].setdefault(kernel, {}).update(cases)
-            data["bars"][kernel] = {k: dict(fp32_reference_worst=v, bar=R.bar_from_fp32(v)) for k, v in worst32(kernel).items()}
-            data["worst_ratio"][kernel] = max(o["ratio"] for c in data["cases"][kernel].values() for o in c.values())
-        json.dump(data, open(path, "w"), indent=1, sort_keys=True)
-    except OSError:
-        pass
-
-
-def _mixed(rng, shape, lo=-2.0, hi=1.0):
-    return (rng.standard_normal(shape) * 10.0 ** rng.uniform(lo, hi, size=shape)).astype(F32)
-
-
-def _f32(x):
-    return np.asarray(x, F64).astype(F32)
+    PARITY.write(worst32)
 
 
 # ------------------------------------------------------------------------------------------------ the cases (no GPU needed)
@@ -371,23 +312,16 @@ def build_case(case):
                 fwd_exact={k: f64[k] for k in LR.EXACT}, fwd_err32=errors({k: f32[k] for k in fn}, fref, fsc), joint_min=float(joint_n.min()))
 
 
-_case_cache = {}
+_cases = U.Cases(lambda _: {k: build_case(k) for k in CASES})
 
 
 def cases():
-    if not _case_cache:
-        for k in CASES:
-            _case_cache[k] = build_case(k)
-    return _case_cache
+    return _cases("all")
 
 
 def worst32(kernel):
     """Per output: the worst error of the fp32 reference over all cases of the kernel."""
-    worst = {}
-    for c in cases().values():
-        for name, e in c["err32" if kernel == "logprob_bwd" else "fwd_err32"].items():
-            worst[name] = max(worst.get(name, 0.0), e)
-    return worst
+    return U.worst32(cases(), "err32" if kernel == "logprob_bwd" else "fwd_err32")
 
 
 def mutated_errors(case, mutate):
@@ -401,35 +335,6 @@ def mutated_errors(case, mutate):
 
 
 # ------------------------------------------------------------------------------------------------ on the GPU
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-class Buf:
-    """A host array, its device copy, and which of its words the kernel owns."""
-
-    def __init__(self, host, owned=None):
-        self.before = np.ascontiguousarray(host)
-        self.t = dev(self.before)
-        self.owned = np.zeros(self.before.shape, bool) if owned is None else owned
-
-    def ptr(self, word=0):
-        return self.t.data_ptr() + 4 * int(word)
-
-    def after(self):
-        return self.t.cpu().numpy()
-
-    def check_untouched(self, name):
-        a, b = self.after().view(np.uint32), self.before.view(np.uint32)
-        bad = (a != b) & ~self.owned
-        assert not bad.any(), "{}: {} words outside the kernel's outputs changed (first at {})".format(name, int(bad.sum()),
-                                                                                                        np.argwhere(bad)[0].tolist())
-
-
 def _inputs(case, c, hd):
     """The device inputs both kernels share: records (rec_m's frame T NaN), pstats at its pitch inside guard rows, spre, the
     parameters (NaN but the ones in use), the per-row counters."""
@@ -449,16 +354,8 @@ def _inputs(case, c, hd):
 
 
 def _finish(kernel, case, got, ref, scales, err32, worst):
-    assert set(got) == set(ref)
-    over = []
-    for k in sorted(got):
-        assert got[k].shape == ref[k].shape, (k, got[k].shape, ref[k].shape)               # every row is compared
-        err, bar = R.row_scaled_error(got[k], ref[k], scales.get(k)), R.bar_from_fp32(worst[k])
-        _figures.setdefault(kernel, {}).setdefault(case, {})[k] = dict(err=err, bar=bar, fp32_reference_err=err32[k], ratio=err / bar)
-        print("{} {} {}: err {:.3e} bar {:.3e} (fp32 reference here {:.3e})".format(kernel, case, k, err, bar, err32[k]))
-        if not err <= bar:
-            over.append((k, err, bar))
-    assert not over, "outputs over their bar (name, err, bar): {}".format(over)
+    assert set(got) == set(ref)                                                            # (row_scaled_error: every row is compared)
+    U.judge(PARITY, kernel, case, got, lambda k: R.row_scaled_error(got[k], ref[k], scales.get(k)), err32, worst)
 
 
 @pytest.mark.parametrize("case", sorted(CASES))

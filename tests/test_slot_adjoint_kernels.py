@@ -25,8 +25,6 @@ copy under profiles/ is such a file).
 A glimpse wholly outside the frame does not exist under to_coords (the shift is a tanh: the glimpse's centre is inside the frame);
 the cases put saturated shifts and large scales in their first rows, which leaves most of those glimpses outside."""
 import ctypes as C
-import json
-import os
 
 import numpy as np
 import pytest
@@ -34,17 +32,14 @@ import torch
 
 from oracle import sqair_oracle as O
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
+from tests import kernel_unit as U
 from tests import slot_adjoint_ref as R
 from tests.hip_util import stream
+from tests.kernel_unit import CHOLESKY, F32, F64, SCALE_OFFSET, Buf, pitched, records
+from tests.kernel_unit import f32 as _f32, image as _image, mixed as _mixed
 
 pytestmark = pytest.mark.gpu
 
-PARITY_DIR_ENV = "SQAIR_PARITY_DIR"
-LAYOUT = ("W", "PRES", "ID", "WHERE", "WHAT", "LOGIT", "WHERE_LOC", "WHERE_SCALE", "WHAT_LOC", "WHAT_SCALE", "PROB", "snh", "psnh",
-          "n_flat", "temporal_init", "prior_init", "max_slots", "N", "nw", "spec_ok")
-F32, F64 = np.float32, np.float64
 KINK = 1e-3
 
 
@@ -65,164 +60,34 @@ HANDLES = {   # name: (wide, (H, W), N, K, flags)
     "c_50x50_g36": (False, (50, 50), 3, 3, dict(glimpse_size=36)),
     "c_50x50_512_wide": (True, (50, 50), 3, 3, dict(n_units=16)),
 }
-_open = {}
-
-
-class _Handle:
-    def __init__(self, name):
-        wide, hw, N, K, flags = HANDLES[name]
-        self.name, self.hw, self.N, self.K = name, hw, N, K
-        self.lib = _capi.lib(_capi.WIDE_LIB_PATH if wide else _capi.LIB_PATH)
-        self.F = make_flags(k_particles=K, n_steps_per_image=N, **flags)
-        self.cfg = make_config(self.F, hw)
-        self.h = C.c_void_p()
-        assert self.lib.sqair_create(C.byref(self.cfg), C.byref(self.h)) == 0, name
-        buf = (C.c_int32 * 20)()
-        assert self.lib.sqair_compact_test_layout(self.h, buf, 20) == 20
-        self.L = dict(zip(LAYOUT, [int(v) for v in buf]))
-        self.nw, self.nh, self.G = int(self.cfg.n_what), int(self.cfg.n_hidden), int(self.cfg.glimpse_size)
-        self.nzw = self.lib.sqair_noise_width(self.h)
-        assert self.L["N"] == N and self.L["nw"] == self.nw and self.nzw == 4 + self.nw + 1
-        # n_hidden is not padded in these configurations: the kernels' parameter layout is the caller's
-        assert self.L["n_flat"] == self.lib.sqair_param_count(self.h) == self.lib.sqair_debug_padded_count(self.h, None)
-        self.off = {}
-        for i in range(self.lib.sqair_param_entries(self.h)):
-            cname, coff, cnum = C.c_char_p(), C.c_int64(), C.c_int64()
-            assert self.lib.sqair_param_entry(self.h, i, C.byref(cname), C.byref(coff), C.byref(cnum)) == 0
-            self.off[cname.value.decode()] = (int(coff.value), int(cnum.value))
-
-    def check(self, rc, what):
-        assert rc == 0, (what, rc, self.lib.sqair_last_error(self.h))
 
 
 def handle(name):
-    if name not in _open:
-        _open[name] = _Handle(name)
-    return _open[name]
+    return U.handle(name, lambda n: U.Handle(n, *HANDLES[n]))
+
+
+PARITY = U.Parity("slot_adjoint_parity.json",
+                  "per case of tests/test_slot_adjoint_kernels.py and output: the kernel's largest row-scaled error against float64 "
+                  "autograd, the bar (8 x the worst error of the same reference in float32 over the kernel's cases), the float32 "
+                  "reference's own error in this case; `bars`: per kernel and output the float32 figure the bar comes from")
+_cases = U.Cases(lambda kernel: {k: BUILD[kernel](*v) for k, v in CASES[kernel].items()})
+
+
+def _worst32(kernel):
+    """Per output: the worst row-scaled error of the fp32 reference over all cases of the kernel."""
+    return U.worst32(_cases(kernel))
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _close_handles():
     yield
-    for hd in _open.values():
-        hd.lib.sqair_destroy(hd.h)
-    _open.clear()
-    _write_parity()
+    U.close()
+    PARITY.write(_worst32)
 
 
-# ------------------------------------------------------------------------------------------------ figures
-_figures = {}
-
-
-def _record(kernel, case, output, err, bar, err32):
-    _figures.setdefault(kernel, {}).setdefault(case, {})[output] = dict(err=err, bar=bar, fp32_reference_err=err32,
-                                                                        ratio=err / bar if bar > 0 else None)
-
-
-def _write_parity():
-    where = os.environ.get(PARITY_DIR_ENV)
-    if not where or not _figures:
-        return
-    try:
-        os.makedirs(where, exist_ok=True)
-        path = os.path.join(where, "slot_adjoint_parity.json")
-        data = json.load(open(path)) if os.path.exists(path) else {
-            "note": "per case of tests/test_slot_adjoint_kernels.py and output: the kernel's largest row-scaled error against float64 "
-                    "autograd, the bar (8 x the worst error of the same reference in float32 over the kernel's cases), the float32 "
-                    "reference's own error in this case; `bars`: per kernel and output the float32 figure the bar comes from",
-            "build_id": _capi.build_id(), "bars": {}, "cases": {}}
-        for kernel, cases in _figures.items():
-            data["cases"].setdefault(kernel, {}).update(cases)
-            data["bars"][kernel] = {k: dict(fp32_reference_worst=v, bar=R.bar_from_fp32(v)) for k, v in _worst32(kernel).items()}
-        json.dump(data, open(path, "w"), indent=1, sort_keys=True)
-    except OSError:
-        pass
-
-
-def _mixed(rng, shape):
-    """Upstream gradients: mixed sign, magnitudes over three decades."""
-    return (rng.standard_normal(shape) * 10.0 ** rng.uniform(-2, 1, size=shape)).astype(F32)
-
-
-def _f32(x):
-    return np.asarray(x, F64).astype(F32)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-class Buf:
-    """A host array, its device copy, and which of its words the kernel owns."""
-
-    def __init__(self, host, owned=None):
-        self.before = np.ascontiguousarray(host, F32)
-        self.t = dev(self.before)
-        self.owned = np.zeros(self.before.shape, bool) if owned is None else owned
-
-    def ptr(self, word=0):
-        return self.t.data_ptr() + 4 * int(word)
-
-    def after(self):
-        return self.t.cpu().numpy()
-
-    def check_untouched(self, name):
-        a, b = self.after().view(np.uint32), self.before.view(np.uint32)
-        bad = (a != b) & ~self.owned
-        assert not bad.any(), "{}: {} words outside the kernel's outputs changed (first at {})".format(name, int(bad.sum()),
-                                                                                                        np.argwhere(bad)[0].tolist())
-
-
-def pitched(rows, width, ld, data=None, out=False, start=0, offset=0, owned_cols=None):
-    """(Buf, pointer of element [0, 0]) of a [rows, width] operand at pitch ld with guard rows; inputs padded with NaN, outputs
-    with distinct words."""
-    p = R.Pitched(rows, width, ld, data=data, nan=not out, start=start, offset=offset)
-    owned = np.zeros(p.host.shape, bool)
-    if out:
-        v = owned[1:1 + rows, offset:offset + width]
-        v[:, :] = True if owned_cols is None else owned_cols[None, :]
-    b = Buf(p.host, owned)
-    b.p = p
-    return b, b.ptr(p.first_word())
-
-
-def records(R_, N, W, fill):
-    """[R, N, W] records: NaN (inputs) or distinct words (gradient records)."""
-    if fill == "nan":
-        return np.full((R_, N, W), np.nan, F32)
-    return R.distinct_words(R_ * N * W, fill).reshape(R_, N, W).copy()
-
-
-def _compare(kernel, case, name, got, ref64, err32_worst, scale=None, err32_case=None):
-    err = R.row_scaled_error(got, ref64, scale)
-    bar = R.bar_from_fp32(err32_worst[name])
-    _record(kernel, case, name, err, bar, err32_case)
-    print("{} {} {}: err {:.3e} bar {:.3e} (fp32 reference here {:.3e})".format(kernel, case, name, err, bar,
-                                                                              -1.0 if err32_case is None else err32_case))
-    return err, bar, name
-
-
-def _assert_within(results):
-    over = [(n, e, b) for e, b, n in results if not e <= b]
-    assert not over, "outputs over their bar (name, err, bar): {}".format(over)
-
-
-_case_cache = {}
-
-
-def _cases(kernel):
-    if kernel not in _case_cache:
-        _case_cache[kernel] = {k: BUILD[kernel](*v) for k, v in CASES[kernel].items()}
-    return _case_cache[kernel]
-
-
-def _worst32(kernel):
-    """Per output: the worst row-scaled error of the fp32 reference over all cases of the kernel."""
-    worst = {}
-    for c in _cases(kernel).values():
-        for name, e in c["err32"].items():
-            worst[name] = max(worst.get(name, 0.0), e)
-    return worst
+def _judge(kernel, case, got, c, scales=None):
+    assert set(got) == set(c["ref"])
+    U.judge(PARITY, kernel, case, got, lambda k: R.row_scaled_error(got[k], c["ref"][k], (scales or {}).get(k)), c["err32"], _worst32(kernel))
 
 
 # ------------------------------------------------------------------------------------------------ slot tail
@@ -368,14 +233,12 @@ def run_tail(case_name, c):
         assert np.array_equal(view("d_s1pre2").view(np.uint32), view("d_s1pre").view(np.uint32)), "d_s1pre2 is not a copy of d_s1pre"
     if enc_pre:
         got["d_enc_scale_pre"] = got.pop("d_enc_scale")
-    worst = _worst32("slot_tail")
-    assert set(got) == set(c["ref"])
-    return [_compare("slot_tail", case_name, k, got[k], c["ref"][k], worst, scale=c["scales"].get(k), err32_case=c["err32"][k]) for k in sorted(got)]
+    _judge("slot_tail", case_name, got, c, c["scales"])
 
 
 @pytest.mark.parametrize("case", sorted(TAIL_CASES))
 def test_slot_tail_adjoint(case):
-    _assert_within(run_tail(case, _cases("slot_tail")[case]))
+    run_tail(case, _cases("slot_tail")[case])
 
 
 # ------------------------------------------------------------------------------------------------ crop chain
@@ -396,9 +259,6 @@ CROP_CASES.update({
     "c_50x50_512_wide disc slot2 fused": ("c_50x50_512_wide", 3, 3, 2, 0, 1, 9),
     "c_50x50_512_wide prop1 mask+dact": ("c_50x50_512_wide", 3, 1, 0, 2, 0, 10),
 })
-CHOLESKY = np.linspace(-0.55, 0.65, 10).astype(F32)
-SCALE_OFFSET = {2: F32(-0.7), 3: F32(0.4)}
-
 
 def _draw_where(rng, rows, H, W, G):
     """Where logits per row, redrawn until the reference's kink margin holds; the first rows saturate the shift / take a large
@@ -421,18 +281,6 @@ def _draw_where(rng, rows, H, W, G):
         fresh[keep_special] = w[bad][keep_special] + rng.uniform(-0.05, 0.05, size=(int(keep_special.sum()), 4)).astype(F32)
         w[bad] = fresh
     raise AssertionError("no kink-free where draw")
-
-
-def _image(rng, B_, H, W):
-    """Frames in [0, 1] with structure at the scale of a glimpse pixel and above (a few random plane waves) and 10 % white noise."""
-    yy, xx = np.meshgrid(np.arange(H) / H, np.arange(W) / W, indexing="ij")
-    img = np.zeros((B_, H, W))
-    for b in range(B_):
-        for _ in range(6):
-            fy, fx, ph = rng.uniform(-4, 4), rng.uniform(-4, 4), rng.uniform(0, 2 * np.pi)
-            img[b] += rng.uniform(0.3, 1.0) * np.sin(2 * np.pi * (fy * yy + fx * xx) + ph)
-    img = 0.5 + 0.45 * img / np.abs(img).max((1, 2), keepdims=True)
-    return _f32(np.clip(0.9 * img + 0.1 * rng.uniform(size=img.shape), 0.0, 1.0))
 
 
 def build_crop(hname, B_, mode, slot, mask_mode, fuse, seed):
@@ -594,16 +442,15 @@ def run_crop(case_name, c):
             got["d_t2"] = view("d_t2")
     if mask_mode:
         got["d_mask"] = B["d_mask"].after()[midx]
-    worst = _worst32("crop_chain")
-    assert set(got) == set(c["ref"]) and all(v.shape[0] == rows for v in got.values())
-    return [_compare("crop_chain", case_name, k, got[k], c["ref"][k], worst, err32_case=c["err32"][k]) for k in sorted(got)]
+    assert all(v.shape[0] == rows for v in got.values())
+    _judge("crop_chain", case_name, got, c)
 
 
 @pytest.mark.parametrize("case", sorted(CROP_CASES))
 def test_crop_chain_adjoint(case):
     c = _cases("crop_chain")[case]
     print("{}: {:.0%} of the rows' where draws passed the kink margin first time".format(case, c["first_pass"]))
-    _assert_within(run_crop(case, c))
+    run_crop(case, c)
 
 
 def test_crop_chain_instantiation_boundary():
@@ -666,8 +513,7 @@ def test_where_param_grads(case):
     hname, T_, R_ = c["args"]
     got = _run_wpg(handle(hname), T_, R_, c["x"], c["content"])
     assert c["rows"] == {"T1 R1 N1": 1, "T1 R37 N1": 37, "T3 R700 N4": 8400}[case]      # (8400: beyond the launch's 8192 threads)
-    _assert_within([_compare("where_param_grads", case, "twelve", got, c["ref"]["twelve"], _worst32("where_param_grads"), scale=c["scale"],
-                             err32_case=c["err32"]["twelve"])])
+    _judge("where_param_grads", case, dict(twelve=got), c, dict(twelve=c["scale"]))
 
 
 def test_where_param_grads_cholesky_order():
@@ -762,12 +608,11 @@ def test_gru_gate_adjoints(case):
     d = view("dpre1")
     got = dict(d_az=d[:, :nh], d_ar=d[:, nh:2 * nh], d_ah=d[:, 2 * nh:], d_h=view("d_h"))
     if dup:
-        bits = lambda a: np.ascontiguousarray(a).view(np.uint32)
+        bits = U.bits
         assert np.array_equal(bits(view("dup_z")[:, :nh]), bits(got["d_az"])) and np.array_equal(bits(view("dup_r")), bits(got["d_ar"]))
         if dup == 2:
             assert np.array_equal(bits(view("dup_z")[:, 2 * nh:]), bits(got["d_ah"]))
-    worst = _worst32("gru_gates")
-    _assert_within([_compare("gru_gates", case, k, got[k], c["ref"][k], worst, err32_case=c["err32"][k]) for k in sorted(got)])
+    _judge("gru_gates", case, got, c)
 
 
 CASES = dict(slot_tail=TAIL_CASES, crop_chain=CROP_CASES, where_param_grads=WPG_CASES, gru_gates=GRU_CASES)

@@ -32,8 +32,6 @@ crop cases put saturated shifts with large scales in their first rows, which lea
 
 With SQAIR_PARITY_DIR set the figures go to slot_forward_parity.json there (the copy under profiles/ is such a file)."""
 import ctypes as C
-import json
-import os
 
 import numpy as np
 import pytest
@@ -41,18 +39,15 @@ import torch
 
 from oracle import sqair_oracle as O
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
-from sqair_amd.params import param_spec
+from tests import kernel_unit as U
 from tests import slot_adjoint_ref as R
 from tests import slot_forward_ref as SF
+from tests.hip_util import dev, stream
+from tests.kernel_unit import CHOLESKY, F32, F64, SCALE_OFFSET, Buf, pitched
+from tests.kernel_unit import bits as _bits, f32 as _f32, image as _image, records as _sentinel_records
 
 pytestmark = pytest.mark.gpu
 
-PARITY_DIR_ENV = "SQAIR_PARITY_DIR"
-LAYOUT = ("W", "PRES", "ID", "WHERE", "WHAT", "LOGIT", "WHERE_LOC", "WHERE_SCALE", "WHAT_LOC", "WHAT_SCALE", "PROB", "snh", "psnh",
-          "n_flat", "temporal_init", "prior_init", "max_slots", "N", "nw", "spec_ok")
-F32, F64 = np.float32, np.float64
 T64, T32 = torch.float64, torch.float32
 U_MARGIN = 1e-3
 U_MAX = float(np.nextafter(F32(1.0), F32(0.0)))
@@ -77,140 +72,24 @@ HANDLES = {   # name: (wide, (H, W), N, K, flags)
     "k_257x5_g12": (False, (257, 5), 3, 1, dict(glimpse_size=12)),
     "k_50x50_512_wide": (True, (50, 50), 3, 3, dict(n_units=16)),
 }
-_open = {}
-
-
-class _Handle:
-    def __init__(self, name):
-        wide, hw, N, K, flags = HANDLES[name]
-        self.name, self.hw, self.N, self.K, self.wide = name, hw, N, K, wide
-        self.lib = _capi.lib(_capi.WIDE_LIB_PATH if wide else _capi.LIB_PATH)
-        self.F = make_flags(k_particles=K, n_steps_per_image=N, **flags)
-        self.cfg = make_config(self.F, hw)
-        self.h = C.c_void_p()
-        assert self.lib.sqair_create(C.byref(self.cfg), C.byref(self.h)) == 0, name
-        buf = (C.c_int32 * 20)()
-        assert self.lib.sqair_compact_test_layout(self.h, buf, 20) == 20
-        self.L = dict(zip(LAYOUT, [int(v) for v in buf]))
-        self.nw, self.nh, self.G = int(self.cfg.n_what), int(self.cfg.n_hidden), int(self.cfg.glimpse_size)
-        self.nzw = self.lib.sqair_noise_width(self.h)
-        assert self.L["N"] == N and self.L["nw"] == self.nw and self.nzw == 4 + self.nw + 1
-        # n_hidden is not padded in these configurations: the kernels' parameter layout is the caller's
-        assert self.L["n_flat"] == self.lib.sqair_param_count(self.h) == self.lib.sqair_debug_padded_count(self.h, None)
-        self.off = {}
-        for i in range(self.lib.sqair_param_entries(self.h)):
-            cname, coff, cnum = C.c_char_p(), C.c_int64(), C.c_int64()
-            assert self.lib.sqair_param_entry(self.h, i, C.byref(cname), C.byref(coff), C.byref(cnum)) == 0
-            self.off[cname.value.decode()] = (int(coff.value), int(cnum.value))
-        self.shapes = {n: tuple(s) for n, s, _, _ in param_spec(self.F, hw)}    # the oracle's shapes
-        self.packed = None
-
-    def check(self, rc, what):
-        assert rc == 0, (what, rc, self.lib.sqair_last_error(self.h))
-
-    def flat_of(self, P):
-        """The flat parameter buffer: NaN but for the parameters of P (which may hold NaN rows themselves)."""
-        flat = np.full(self.L["n_flat"], np.nan, F32)
-        for name, v in P.items():
-            o, n = self.off[name]
-            assert tuple(np.shape(v)) == self.shapes[name] and n == int(np.prod(self.shapes[name], dtype=np.int64)), name
-            flat[o:o + n] = np.asarray(v, F32).reshape(-1)
-        return flat
-
-    def pack(self, flat_buf):
-        if self.packed is None:
-            self.packed = torch.zeros(self.lib.sqair_packed_bytes(self.h) // 4, dtype=torch.float32, device="cuda")
-        self.check(self.lib.sqair_pack_params(self.h, flat_buf.ptr(), self.packed.data_ptr(), _stream()), "sqair_pack_params")
-        torch.cuda.synchronize()
-        return self.packed.data_ptr()
 
 
 def handle(name):
-    if name not in _open:
-        _open[name] = _Handle(name)
-    return _open[name]
+    return U.handle(name, lambda n: U.Handle(n, *HANDLES[n]))
 
 
-def close_handles():
-    for hd in _open.values():
-        hd.lib.sqair_destroy(hd.h)
-    _open.clear()
+close_handles = U.close
+PARITY = U.Parity("slot_forward_parity.json",
+                  "per case of tests/test_slot_forward_kernels.py and output: the kernel's largest row-scaled error against the float64 "
+                  "reference, the bar (8 x the worst error of the same reference in float32 over the kernel's cases), the float32 "
+                  "reference's own error in this case; `bars`: per kernel and output the float32 figure the bar comes from")
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _close_handles():
     yield
     close_handles()
-    _write_parity()
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-# ------------------------------------------------------------------------------------------------ figures
-_figures = {}
-
-
-def _write_parity():
-    where = os.environ.get(PARITY_DIR_ENV)
-    if not where or not _figures:
-        return
-    try:
-        os.makedirs(where, exist_ok=True)
-        path = os.path.join(where, "slot_forward_parity.json")
-        data = json.load(open(path)) if os.path.exists(path) else {
-            "note": "per case of tests/test_slot_forward_kernels.py and output: the kernel's largest row-scaled error against the float64 "
-                    "reference, the bar (8 x the worst error of the same reference in float32 over the kernel's cases), the float32 "
-                    "reference's own error in this case; `bars`: per kernel and output the float32 figure the bar comes from",
-            "build_id": _capi.build_id(), "bars": {}, "cases": {}}
-        for kernel, cs in _figures.items():
-            data["cases"].setdefault(kernel, {}).update(cs)
-            data["bars"][kernel] = {k: dict(fp32_reference_worst=v, bar=R.bar_from_fp32(v)) for k, v in worst32(kernel).items()}
-        json.dump(data, open(path, "w"), indent=1, sort_keys=True)
-    except OSError:
-        pass
-
-
-def _f32(x):
-    return np.asarray(x, F64).astype(F32)
-
-
-class Buf:
-    """A host array, its device copy, and which of its words the kernel owns."""
-
-    def __init__(self, host, owned=None):
-        self.before = np.ascontiguousarray(host, F32)
-        self.t = torch.from_numpy(self.before.copy()).cuda()
-        self.owned = np.zeros(self.before.shape, bool) if owned is None else owned
-
-    def ptr(self, word=0):
-        return self.t.data_ptr() + 4 * int(word)
-
-    def after(self):
-        return self.t.cpu().numpy()
-
-    def check_untouched(self, name):
-        a, b = self.after().view(np.uint32), self.before.view(np.uint32)
-        bad = (a != b) & ~self.owned
-        assert not bad.any(), "{}: {} words outside the kernel's outputs changed (first at {})".format(name, int(bad.sum()),
-                                                                                                        np.argwhere(bad)[0].tolist())
-
-
-def pitched(rows, width, ld, data=None, out=False, start=0, offset=0):
-    """(Buf, pointer of element [0, 0]) of a [rows, width] operand at pitch ld with guard rows; inputs padded with NaN, outputs with
-    distinct words."""
-    p = R.Pitched(rows, width, ld, data=data, nan=not out, start=start, offset=offset)
-    owned = np.zeros(p.host.shape, bool)
-    if out:
-        owned[1:1 + rows, offset:offset + width] = True
-    b = Buf(p.host, owned)
-    b.p = p
-    return b, b.ptr(p.first_word())
-
-
-def _sentinel_records(R_, N, W, start):
-    return R.distinct_words(R_ * N * W, start).reshape(R_, N, W).copy()
+    PARITY.write(worst32)
 
 
 # ------------------------------------------------------------------------------------------------ errors, bars
@@ -235,24 +114,16 @@ def errors(got, ref):
     return e
 
 
-_case_cache = {}
+_cases = U.Cases(lambda kernel: {k: BUILD[kernel](*v) for k, v in CASES[kernel].items()})
 
 
 def cases(kernel=None):
-    if kernel is None:
-        return {k: cases(k) for k in CASES}
-    if kernel not in _case_cache:
-        _case_cache[kernel] = {k: BUILD[kernel](*v) for k, v in CASES[kernel].items()}
-    return _case_cache[kernel]
+    return {k: _cases(k) for k in CASES} if kernel is None else _cases(kernel)
 
 
 def worst32(kernel):
     """Per output: the worst error of the float32 reference over all cases of the kernel."""
-    worst = {}
-    for c in cases(kernel).values():
-        for name, e in c["err32"].items():
-            worst[name] = max(worst.get(name, 0.0), e)
-    return worst
+    return U.worst32(cases(kernel))
 
 
 def mutated_errors(kernel, case, mistake):
@@ -272,17 +143,9 @@ def _finish(kernel, inp):
 
 
 def _judge(kernel, case, got, c):
-    """Every output under its bar (all of them measured and recorded first)."""
-    e, w = errors(got, c["ref"]), worst32(kernel)
-    over = []
-    for k in sorted(e):
-        bar = 0.0 if k == "pres" else R.bar_from_fp32(w[k])
-        _figures.setdefault(kernel, {}).setdefault(case, {})[k] = dict(err=e[k], bar=bar, fp32_reference_err=c["err32"][k],
-                                                                         ratio=e[k] / bar if bar > 0 else None)
-        print("{} {} {}: err {:.3e} bar {:.3e} (fp32 reference here {:.3e})".format(kernel, case, k, e[k], bar, c["err32"][k]))
-        if not e[k] <= bar:
-            over.append((k, e[k], bar))
-    assert not over, "outputs over their bar (name, err, bar): {}".format(over)
+    """Every output under its bar (all of them measured and recorded first); presences are exact."""
+    e = errors(got, c["ref"])
+    U.judge(PARITY, kernel, case, e, e.get, c["err32"], worst32(kernel), exact=("pres",))
 
 
 # ------------------------------------------------------------------------------------------------ the tail family: inputs
@@ -469,7 +332,7 @@ def run_tail(c, what_done_from=None):
         B["hid"], t.hid = pitched(R_, nh, nh + 8, inp["hid"]); t.hid_ld = nh + 8
         B["add"], t.add = pitched(R_, nh, nh + 3, inp["add"]); t.add_ld = nh + 3
         B["out"], t.out = pitched(R_, nh, nh + 12, out=True, start=at); t.out_ld = nh + 12
-    hd.check(hd.lib.sqair_slot_tail_test(hd.h, C.byref(t), _stream()), "sqair_slot_tail_test")
+    hd.check(hd.lib.sqair_slot_tail_test(hd.h, C.byref(t), stream()), "sqair_slot_tail_test")
     for name, b in B.items():
         b.check_untouched(name)
     rn = B["rec_new"].after()
@@ -524,10 +387,6 @@ def test_rnn_tail(case):
     _judge("rnn_tail", case, run_tail(c), c)
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)
-
-
 def _plain_layer(hd, x, w, b, M, N_, act_b=0, act_split=1 << 30, add=None):
     """out [M, N_] = act(x w + b (+ add)) through sqair_linear_contract_test: the dense launcher on the same operands."""
     kc, nt = sum((k + 15) // 16 for k in [s.shape[1] for s in x]), (N_ + 15) // 16
@@ -545,7 +404,7 @@ def _plain_layer(hd, x, w, b, M, N_, act_b=0, act_split=1 << 30, add=None):
     c.act_a, c.act_b, c.act_split, c.scale = (2 if add is not None else 0), act_b, act_split, 1.0
     c.out, c.out_ld, c.M, c.N = out.data_ptr(), N_, M, N_
     c.scratch, c.scratch_bytes = scratch.data_ptr(), scratch.numel() * 4
-    hd.check(hd.lib.sqair_linear_contract_test(hd.h, C.byref(c), _stream()), "sqair_linear_contract_test")
+    hd.check(hd.lib.sqair_linear_contract_test(hd.h, C.byref(c), stream()), "sqair_linear_contract_test")
     return out
 
 
@@ -573,7 +432,6 @@ def test_rnn_tail_is_the_tail_and_then_the_plain_layer(case):
     z = np.zeros((R_, ZW), F32)
     z[:] = alone["rec_new"][:, slot, L["WHERE"]:L["WHERE"] + ZW]
     z[:, L["WHAT"] - L["WHERE"] + nw:L["PRES"] - L["WHERE"]] = 0.0                 # (what columns beyond n_what: zero in the kernel's tile)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, F32)).cuda()
     out = _plain_layer(hd, [dev(z), dev(inp["hid"])], np.concatenate([wz, inp["P"][core + ".rnn.h2h.w"]], 0), np.zeros(nh, F32), R_, nh,
                        add=dev(inp["add"]))
     assert np.array_equal(_bits(fused["out"]), _bits(out.cpu().numpy())), "the layer's output differs"
@@ -671,7 +529,7 @@ def run_what(c):
     if mode == 1:
         t.rec_prev = B["rec_prev"].ptr()
         B["enc"], t.enc = pitched(M, 2 * nw, 2 * nw + 5, inp["enc"]); t.enc_ld = 2 * nw + 5
-    hd.check(hd.lib.sqair_linear_what_test(hd.h, C.byref(t), _stream()), "sqair_linear_what_test")
+    hd.check(hd.lib.sqair_linear_what_test(hd.h, C.byref(t), stream()), "sqair_linear_what_test")
     for name, b in B.items():
         b.check_untouched(name)
     rn = B["rec_new"].after()
@@ -707,7 +565,6 @@ def test_linear_what_then_the_tail_is_the_plain_head_then_the_tail(case):
         rec_prev[:, slot, hd.L["PRES"]] = prev
     noise = inp["noise"].copy()
     noise[:, 1 - mode, slot, 4 + nw] = _f32(rng.uniform(size=M))
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, F32)).cuda()
     x = dev(inp["x"])
     if mode == 0:    # L_WHAT_HEAD: loc | softplus(raw) + 1e-2 (activation code 4 from column n_what on)
         enc = _plain_layer(hd, [x], P["enc.what_head.w"], P["enc.what_head.b"], M, 2 * nw, act_b=4, act_split=nw).cpu().numpy()
@@ -728,8 +585,6 @@ def test_linear_what_then_the_tail_is_the_plain_head_then_the_tail(case):
 
 
 # ------------------------------------------------------------------------------------------------ crop
-CHOLESKY = np.linspace(-0.55, 0.65, 10).astype(F32)
-SCALE_OFFSET = {2: F32(-0.7), 3: F32(0.4)}
 SPECIAL_WHERE = np.array([[2.0, 1.5, 12.0, -12.0], [3.0, 3.0, -2.5, 2.5], [-12.0, -10.0, 0.3, -0.2], [-1.0, 2.0, 4.0, 0.3]], F32)
 CROP_CASES = {}   # name: (handle, B, mode, slot, mask, fused, tp_out, specialised, seed)
 for _i, (_h, _B) in enumerate([("k_50x50", 8), ("k_37x41_g12", 8), ("k_64x64_g28", 7), ("k_72x64_128", 8), ("k_3x250", 7), ("k_257x5_g12", 7),
@@ -751,18 +606,6 @@ CROP_CASES.update({
 SPEC_PAIRS = ("k_50x50 prop1 mask", "k_50x50 prop2 s1 mask fused", "k_50x50 disc s1 fused tp_out")
 for _k in SPEC_PAIRS:
     CROP_CASES[_k + " specialised"] = CROP_CASES[_k][:7] + (1,) + CROP_CASES[_k][8:]
-
-
-def _image(rng, B_, H, W):
-    """Frames in [0, 1]: a few random plane waves and 10 % white noise."""
-    yy, xx = np.meshgrid(np.arange(H) / H, np.arange(W) / W, indexing="ij")
-    img = np.zeros((B_, H, W))
-    for b in range(B_):
-        for _ in range(6):
-            fy, fx, ph = rng.uniform(-4, 4), rng.uniform(-4, 4), rng.uniform(0, 2 * np.pi)
-            img[b] += rng.uniform(0.3, 1.0) * np.sin(2 * np.pi * (fy * yy + fx * xx) + ph)
-    img = 0.5 + 0.45 * img / np.abs(img).max((1, 2), keepdims=True)
-    return _f32(np.clip(0.9 * img + 0.1 * rng.uniform(size=img.shape), 0.0, 1.0))
 
 
 def _where_targets(rng, rows):
@@ -888,7 +731,7 @@ def run_crop(c):
                 B["tp_out"], t.tp_out = pitched(R_, 8, 11, out=True, start=inp["rec_new"].size + B["out"].before.size); t.tp_out_ld = 11
         else:
             B["tp"], t.tp = pitched(R_, 8, 9, inp["tp"]); t.tp_ld = 9
-    hd.check(hd.lib.sqair_slot_crop_test(hd.h, C.byref(t), _stream()), "sqair_slot_crop_test")
+    hd.check(hd.lib.sqair_slot_crop_test(hd.h, C.byref(t), stream()), "sqair_slot_crop_test")
     for name, b in B.items():
         b.check_untouched(name)
     got = dict(glimpse=B["out"].after()[orow])
