@@ -688,7 +688,8 @@ int sqair_lane_layers_test(SqairHandle* h, const float* glimpse, const float* wh
  * of another T.  sqair_set_estimate switching the estimate off, to another T or to one without the four fields, and
  * sqair_set_state switching the state off or to another B, switch the score off.
  * Out of scope: optimal (Hungarian) assignment per frame -- step 3 is greedy (IDF1 and the mostly-tracked / mostly-lost statistics,
- * with the optimal assignment over a clip they need, are sqair_set_idf's, below); scoring per particle row;
+ * with the optimal assignment over a clip they need, are sqair_set_idf's, below) here: step 3 as keep + optimal is
+ * sqair_set_lane_match's, below; scoring per particle row;
  * scoring of forecasts or lane tracks; training passes. */
 #define SQAIR_SCORE_MAX_TRUTH 16
 #define SQAIR_SCORE_COUNTS 9
@@ -760,7 +761,8 @@ int sqair_lane_score_test(SqairHandle* h, const float* box, const float* presenc
  *    support, box0, alive, box_mean, count_prob, anchor_box, anchor_present, anchor_valid, truth_box, truth_present, truth_valid,
  *    counts, sums or lane_counts (obj_id, valid_mass, keep_id and the per-call outputs are optional); F outside 1..65535 or B < 1; G
  *    outside 1..16; iou_min NaN or outside (0, 1]; a keep_id without a table obj_id.
- * 6. Out of scope: optimal (Hungarian) assignment -- the link is greedy; calibration of box_std; trajectory scoring per particle
+ * 6. Out of scope: optimal (Hungarian) assignment -- the link is greedy here; the link as keep + optimal is sqair_set_lane_match's,
+ *    below; calibration of box_std; trajectory scoring per particle
  *    row; truth for departed objects (the tables list the objects of the last stepped frame only); a truth ring kept by the stream --
  *    the caller brings the truth of the table's frames. */
 #define SQAIR_TRAJ_COUNTS 7
@@ -858,8 +860,9 @@ int sqair_lane_traj_score(SqairHandle* h, const SqairLaneTraj* table, const Sqai
  * sqair_set_score_ids(h, 1) makes k_lane_score read the identity's lane_id words where it reads the estimate's obj_id (the kernel
  * treats the id as a 32-bit word: only the pointer the launcher passes changes); refused unless both the score and the identity are
  * set; the identity or the score going off puts it back to 0.
- * Out of scope: carrying lane_id into the object lists of lane tracks and lane forecasts; optimal (Hungarian) assignment; a motion
- * model for the unseen track; identities across lanes; training passes. */
+ * Out of scope: carrying lane_id into the object lists of lane tracks and lane forecasts; optimal (Hungarian) assignment (here: step 2
+ * as keep + optimal is sqair_set_lane_match's, below; step 4 stays as it is); a motion model for the unseen track; identities across
+ * lanes; training passes. */
 #define SQAIR_IDENT_MAX_TRACKS 16
 #define SQAIR_IDENT_COUNTS 8
 typedef struct SqairLaneIdentity {
@@ -944,7 +947,8 @@ int sqair_set_score_ids(SqairHandle* h, int lane_ids /* 0: the estimate's obj_id
  * than the estimate's or a B other than the state's; for P outside 1..64; for a NULL col_id, overlap, row_frames, col_frames,
  * extra_frames, matched, frag, trk_state, frames or totals.  The IDF goes off with the score: everything that switches the score off
  * switches it off, and so does sqair_set_score registering a score without truth_match or with another G.
- * Out of scope: optimal per-frame matching inside k_lane_score or k_lane_identity (the device function is shaped for it); truth
+ * Out of scope: optimal per-frame matching inside k_lane_score or k_lane_identity (the device function is shaped for it:
+ * sqair_set_lane_match, below, is that change); truth
  * identities other than the slot; HOTA; IDF1 per particle row, or for forecasts and lane tracks; identities across lanes; training
  * passes; more than 64 predicted ids per clip -- reported through overflow_ids, not solved. */
 #define SQAIR_IDF_MAX_IDS 64
@@ -976,6 +980,44 @@ int sqair_lane_idf_test(SqairHandle* h, const float* box, const float* presence,
  * NULL idf, G outside 1..16, B < 1, what sqair_set_idf refuses for idf. */
 int sqair_lane_idf_solve(SqairHandle* h, const SqairLaneIdf* idf, int G, int B, const int32_t* close /* device [B] or NULL */,
                          int64_t* open /* [B,12] or NULL */, int32_t* assign /* [B,G] or NULL */, void* stream);
+
+/* ---- per-frame matching: keep + optimal where the lane block matches keep + greedy --------------------------------------------
+ * The lane block makes three per-frame correspondences, each by keep + greedy: truth x lane object in the stream score (its points 2
+ * and 3), track entry x lane object in the lane identities (their step 2), truth x lane object at the anchor of the trajectory score
+ * (its point 1).  Greedy is not what CLEAR-MOT defines: it keeps the still-valid correspondences of the last frame and solves the
+ * rest as an assignment problem.  With iou_min = 0.5 and the IoU table [[0.60, 0.54], [0.54, 0.08]] greedy takes (0, 0) and leaves
+ * truth 1 with nothing eligible -- tp 1, fn 1, fp 1 where two pairs exist.  sqair_set_lane_match selects, for each of the three, which
+ * of the two a launch uses; this paragraph is the one definition of the optimal mode.
+ * 1. Values.  score, identity, traj_link: 0 = keep + greedy (the default: every output, blob, accumulator and graph node count is what
+ *    it is without this call), 1 = keep + optimal.  score selects the mode of the stream score's kernel, identity that of step 2 of the
+ *    identity's kernel (re-identification, births and ageing are untouched), traj_link that of the link of sqair_lane_traj_score.
+ * 2. Keep.  Exactly the greedy mode's keep (the score's point 2), unchanged in meaning: rows in index order, the first unclaimed
+ *    eligible column carrying the remembered id word.  A kept pair is never given up, even where that costs a pair: that is
+ *    CLEAR-MOT's rule, and it keeps idsw comparable between the modes.
+ * 3. Rest: the objective.  Among the rows still unmatched and the columns still unclaimed, the one-to-one assignment of eligible
+ *    pairs (IoU >= iou_min; a NaN never passes; an absent row or column has no eligible pair) that maximises first the NUMBER of
+ *    pairs, then the sum of q(g, j) over the pairs.  q = __float2int_rn(IoU * 1048576.0f): the fp32 IoU the greedy mode compares, in
+ *    units of 2^-20, rounded to nearest even.
+ * 4. Weights.  The wavefront builds an int32 table in LDS: 2^25 + q for an eligible pair of an unmatched row and an unclaimed
+ *    column, -1 for every other pair.  IoU <= 1 gives q <= 2^20, at most 16 pairs give a sum of q of at most 2^24 < 2^25: one pair
+ *    more outweighs every sum of q.  Every weight stays below 2^30, the exact range of sq_assign_optimal_i32 (the IDF1 solve's device
+ *    function, called on the table as it stands), and a pair of weight -1 is never taken.  The function is sq_assign_keep_optimal
+ *    (csrc/sqair_lane.h), one wavefront's work where the greedy mode is one thread's walk.
+ * 5. Ties.  As in the IDF1 solve, optimal assignments tie: among equally optimal ones the result is whatever sq_assign_optimal_i32
+ *    returns.  That is deterministic -- the same bits eager, graph-replayed and in split passes -- and is not restated as a rule.
+ * 6. What follows.  Everything after the assignment is the greedy mode's code on the new pairs: the score's events, last_id,
+ *    match_iou, truth_match and accumulators; the identity's how, updates, re-identification, births and ageing; the trajectory
+ *    score's link, link_iou, lane_counts and every per-frame figure read through the link.  The IDF table's matched and frag (and
+ *    with them MT / PT / ML) read the score's truth_match and so follow the score's mode; its overlap table and IDTP do not depend
+ *    on it.  tp of a frame in the optimal mode is never below the greedy mode's on the same memory.
+ * 7. A plain setting of the handle: it needs no registration, survives sqair_set_estimate / _score / _identity / _state switching
+ *    things on and off, and is read when a pass or a stand-alone call is issued -- a captured graph freezes it, as it freezes
+ *    pointers.  The kernel-level entries sqair_lane_score_test, sqair_lane_identity_test and sqair_lane_idf_test honour it (the
+ *    last reads only truth_match, whatever mode wrote it).  The node count of a pass does not depend on it.
+ * Refused (return -1, text in sqair_last_error, before any HIP call): a NULL handle; a value other than 0 or 1 -- nothing is changed
+ * then.  Not offered: a stated tie-break among optimal assignments; optimal re-identification (the identity's step 4); matching per
+ * particle row; HOTA; training passes. */
+int sqair_set_lane_match(SqairHandle* h, int score, int identity, int traj_link);
 
 /* ---- objective ---------------------------------------------------------------------------------
  * Fused IWAE / VIMCO reductions over [T,B,K] (reference: Model._build sqair/model.py:88-103,

@@ -459,6 +459,7 @@ _PROTOS = {
     "sqair_set_identity": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneIdentity), C.c_int, C.c_int]),
     "sqair_lane_identity_test": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.POINTER(SqairLaneIdentity), C.c_void_p]),
     "sqair_set_score_ids": (C.c_int, [C.c_void_p, C.c_int]),
+    "sqair_set_lane_match": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "sqair_set_idf": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneIdf), C.c_int, C.c_int]),
     "sqair_lane_idf_test": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.POINTER(SqairLaneScore), C.POINTER(SqairLaneIdf), C.c_void_p]),
     "sqair_lane_idf_solve": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneIdf), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -440,6 +440,7 @@ struct LaneScoreArgs {
   const int32_t* map_count;            // [T][B]
   SqairLaneScore sc;                   // iou_min, G, the truth, the accumulators and the per-frame outputs
   int T, B, N;
+  int match;                           // sqair_set_lane_match's score: 0 = keep + greedy (k_lane_score), 1 = keep + optimal (k_lane_score_opt)
 };
 int sq_launch_lane_score(const LaneScoreArgs& a, hipStream_t s);
 // Lane identities (sqair_set_identity; include/sqair_hip.h states the semantics): k_lane_identity, one workgroup per lane b looping
@@ -454,6 +455,7 @@ struct LaneIdentArgs {
   const int32_t* best_row;             // [T][B]
   SqairLaneIdentity id;                // the scalars, the memory, the counters and the per-frame outputs
   int T, B, N, nw;
+  int match;                           // sqair_set_lane_match's identity, step 2: 0 = k_lane_identity, 1 = k_lane_identity_opt
 };
 int sq_launch_lane_identity(const LaneIdentArgs& a, hipStream_t s);
 // Trajectory scoring (sqair_lane_traj_score; include/sqair_hip.h states the semantics): k_lane_traj_score, grid (lane b, chunk of
@@ -464,6 +466,7 @@ struct LaneTrajScoreArgs {
   SqairTrajTruth tr;                   // G, the anchor, the truth of the table's frames, keep_id
   SqairTrajScore sc;                   // iou_min, the accumulators and the per-call outputs
   int F, B, N;
+  int match;                           // sqair_set_lane_match's traj_link: 0 = k_lane_traj_score, 1 = k_lane_traj_score_opt
 };
 int sq_launch_lane_traj_score(const LaneTrajScoreArgs& a, hipStream_t s);
 // IDF1 scoring (sqair_set_idf; include/sqair_hip.h states the semantics): k_lane_idf, one workgroup per lane b looping over the pass's

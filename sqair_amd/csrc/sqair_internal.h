@@ -50,6 +50,9 @@ struct SqLaneSet {
   bool score_ids = false;
   bool idf_on = false;
   SqairLaneIdf idf = {};
+  // sqair_set_lane_match's score and identity, 0 = keep + greedy, 1 = keep + optimal: no registration -- the setting lives on the
+  // handle (SqairHandle::match_*) and sq_resolve_pass copies it into the pass's resolved block, which is what the launches read
+  int score_match = 0, ident_match = 0;
 };
 
 struct SqairHandle {
@@ -118,6 +121,8 @@ struct SqairHandle {
   int observed_T = 0;
   // the lane answers (sqair_set_estimate / _layers / _identity / _score / _score_ids / _idf; sqair_lane_api.hip)
   SqLaneSet lane;
+  // per-frame matching of the lane block (sqair_set_lane_match): a plain setting, untouched by the registrations above
+  int match_score = 0, match_ident = 0, match_traj = 0;
   // generic capture slots (sqair_capture_begin / _end / _launch): any sequence of C-ABI calls as one HIP graph
   hipGraph_t cap_graph[4] = {nullptr, nullptr, nullptr, nullptr};
   hipGraphExec_t cap_exec[4] = {nullptr, nullptr, nullptr, nullptr};

@@ -183,7 +183,8 @@ __device__ __forceinline__ void sq_lane_box_sum(const float* s_w, const SqBox* s
 //          j (a row-major scan with a strict compare); stop when none is left.
 // Leaves row_match[g] = j or -1 and col_claim[j] = 1 or 0; returns the number of pairs.  Greedy, not optimal: the
 // optimal (Hungarian) assignment is sq_assign_optimal_i32, below, over an int32 table and a whole wavefront's work; the per-frame
-// matches of the score, the identity and the trajectory score stay greedy.
+// matches of the score, the identity and the trajectory score stay greedy unless sqair_set_lane_match asks for
+// sq_assign_keep_optimal, further below.
 __device__ __forceinline__ int sq_assign_keep_greedy(const float* iou, const int ld, const int G, const int N, const float iou_min,
                                                      const int* keep_id, const int* col_id, int* row_match, int* col_claim) {
   int n = 0;
@@ -293,4 +294,63 @@ __device__ __forceinline__ long long sq_assign_optimal_i32(const int* w, const i
   if (hasA && pA >= 0) row_to_col[pA] = L;
   if (hasB && pB >= 0) row_to_col[pB] = -1;
   return sq_wave_sum_i64(hasA && pA >= 0 ? (long long)w[pA * ld + L] : 0ll);
+}
+
+// Keep + optimal one-to-one assignment (sqair_set_lane_match): sq_assign_keep_greedy's contract -- the same IoU table in LDS, the same
+// eligibility (entry >= iou_min; -1 marks a non-candidate; a NaN never passes), the same keep_id / col_id, the same row_match /
+// col_claim and return value -- for ONE whole wavefront: all 64 lanes call it together (wave 0 of a 256-thread workgroup; the branch
+// around the call is wave-uniform).  `w` is G * N ints of LDS of the caller's, the function's own table.
+//   keep   lane 0's walk, exactly the greedy function's keep step: a kept pair is never given up, even where that costs a pair;
+//   rest   among the unmatched rows and unclaimed columns the one-to-one assignment of eligible pairs that maximises first the
+//          number of pairs, then the sum of q(g, j) = __float2int_rn(iou * 1048576.0f), the IoU in units of 2^-20.  The wave builds
+//          the int32 table -- weight 2^25 + q for an eligible pair of an unmatched row and an unclaimed column, -1 for every other
+//          pair -- and calls sq_assign_optimal_i32 on it.  An IoU is at most 1, so q <= 2^20; an assignment has at most 16 pairs
+//          (G <= 16), so its sum of q is at most 2^24 < 2^25: one pair more outweighs any sum of q, which is cardinality first.
+//          Every weight is at most 2^25 + 2^20 < 2^30, the solver's exact range, and a pair of weight -1 is never taken (a row's
+//          dummy column weighs 0).  The number of new pairs is the optimum >> 25 for the same reason.
+// Among equally optimal assignments the result is whatever sq_assign_optimal_i32 returns: deterministic, not restated as a rule.
+// LDS ordering inside the wave: lane 0's keep stores, the table, and the solver's row_to_col are each read by other lanes of the
+// same wavefront.  A wavefront's LDS instructions execute in program order, so no wait is needed; sq_wave_lds_order only keeps the
+// compiler from moving a lane's loads across another lane's stores (a wavefront-scope fence pair around a wave barrier, neither of
+// which is an instruction).  No array is indexed in registers (a lane holds its own row's kept column, one scalar), no scratch, no
+// atomics.
+__device__ __forceinline__ void sq_wave_lds_order() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ int sq_assign_keep_optimal(const float* iou, const int ld, const int G, const int N, const float iou_min,
+                                                      const int* keep_id, const int* col_id, int* row_match, int* col_claim, int* w) {
+  const int L = threadIdx.x & 63;
+  int n = 0;
+  if (L == 0) {
+    for (int g = 0; g < G; ++g) row_match[g] = -1;
+    for (int j = 0; j < N; ++j) col_claim[j] = 0;
+    if (keep_id)
+      for (int g = 0; g < G; ++g) {
+        const int id = keep_id[g];
+        if (id < 0) continue;
+        for (int j = 0; j < N; ++j)
+          if (!col_claim[j] && col_id[j] == id && iou[g * ld + j] >= iou_min) {
+            row_match[g] = j; col_claim[j] = 1; ++n;
+            break;
+          }
+      }
+  }
+  sq_wave_lds_order();
+  const int kept = L < G ? row_match[L] : -1;   // (the solver leaves -1 in the row of a kept pair: every weight of it is -1)
+  for (int i = L; i < G * N; i += 64) {
+    const int g = i / N, j = i - g * N;
+    const float v = iou[g * ld + j];
+    w[i] = (row_match[g] < 0 && !col_claim[j] && v >= iou_min) ? (1 << 25) + __float2int_rn(v * 1048576.0f) : -1;
+  }
+  sq_wave_lds_order();
+  const long long opt = sq_assign_optimal_i32(w, N, G, N, row_match);
+  sq_wave_lds_order();
+  if (L < G) {
+    if (kept >= 0) row_match[L] = kept;
+    else if (row_match[L] >= 0) col_claim[row_match[L]] = 1;
+  }
+  sq_wave_lds_order();
+  return __shfl(n, 0, 64) + (int)(opt >> 25);
 }

@@ -577,8 +577,10 @@ int sq_launch_lane_layers(const LaneLayerArgs& a, hipStream_t s) {
 // candidate), thread 0 walks the tables (sq_assign_keep_greedy) and counts the events, threads g < G write the per-frame outputs.
 // The memory stays in LDS over the frames; thread 0 keeps the counters in registers and adds them to the accumulators once, in
 // place.  Every branch around a barrier depends on truth_valid[t, b] and map_count[t, b] alone: uniform over the workgroup.
-__global__ __launch_bounds__(256) void k_lane_score(const LaneScoreArgs a SQ_TLP) {
-  SQ_TL_SCOPE;
+// OPT (sqair_set_lane_match, score = 1): wave 0 makes the assignment (sq_assign_keep_optimal, its int32 table in LDS) where thread 0
+// walks the greedy one; everything after it is the same code reading s_gm / s_claim.  OPT = false is k_lane_score as it always was.
+template <bool OPT>
+__device__ __forceinline__ void sq_lane_score_frames(const LaneScoreArgs& a) {
   __shared__ float s_iou[SQ_SCORE_MAXG * SQ_MAXN];
   __shared__ int s_last[SQ_SCORE_MAXG], s_tpres[SQ_SCORE_MAXG], s_gm[SQ_SCORE_MAXG];
   __shared__ int s_id[SQ_MAXN], s_lpres[SQ_MAXN], s_claim[SQ_MAXN];
@@ -624,8 +626,12 @@ __global__ __launch_bounds__(256) void k_lane_score(const LaneScoreArgs a SQ_TLP
     }
     __syncthreads();
     // ---- 2, 3, 4: the assignment and the events, one thread
+    if constexpr (OPT) {
+      __shared__ int s_w[SQ_SCORE_MAXG * SQ_MAXN];
+      if (tid < 64) sq_assign_keep_optimal(s_iou, N, G, N, o.iou_min, s_last, s_id, s_gm, s_claim, s_w);
+    }
     if (tid == 0) {
-      sq_assign_keep_greedy(s_iou, N, G, N, o.iou_min, s_last, s_id, s_gm, s_claim);
+      if constexpr (!OPT) sq_assign_keep_greedy(s_iou, N, G, N, o.iou_min, s_last, s_id, s_gm, s_claim);
       int n_truth = 0, tp = 0, fn = 0, fp = 0, sw = 0;
       for (int g = 0; g < G; ++g) {
         if (!s_tpres[g]) continue;
@@ -662,8 +668,17 @@ __global__ __launch_bounds__(256) void k_lane_score(const LaneScoreArgs a SQ_TLP
     o.iou_sum[b] = iou_sum;
   }
 }
+__global__ __launch_bounds__(256) void k_lane_score(const LaneScoreArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  sq_lane_score_frames<false>(a);
+}
+__global__ __launch_bounds__(256) void k_lane_score_opt(const LaneScoreArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  sq_lane_score_frames<true>(a);
+}
 int sq_launch_lane_score(const LaneScoreArgs& a, hipStream_t s) {
-  SQ_LAUNCH(k_lane_score, dim3(a.B), dim3(256), 0, s, a);
+  if (a.match) SQ_LAUNCH(k_lane_score_opt, dim3(a.B), dim3(256), 0, s, a);
+  else SQ_LAUNCH(k_lane_score, dim3(a.B), dim3(256), 0, s, a);
   return 0;
 }
 
@@ -677,8 +692,11 @@ int sq_launch_lane_score(const LaneScoreArgs& a, hipStream_t s) {
 // re-identification, the births and the ageing -- and leaves per slot j its entry and how it got there; then threads j < N write
 // the outputs and the workgroup copies the words of every seen slot into its entry.  Every array is in LDS, nothing is indexed in
 // registers.  Every branch around a barrier depends on best_row[t, b] and the struct's scalars alone: uniform over the workgroup.
-__global__ __launch_bounds__(256) void k_lane_identity(const LaneIdentArgs a SQ_TLP) {
-  SQ_TL_SCOPE;
+// OPT (sqair_set_lane_match, identity = 1): wave 0 makes step 2's assignment (sq_assign_keep_optimal) where thread 0 walks the
+// greedy one; the re-identification, the births and the ageing are thread 0's walk either way.  OPT = false is k_lane_identity as
+// it always was.
+template <bool OPT>
+__device__ __forceinline__ void sq_lane_identity_frames(const LaneIdentArgs& a) {
   __shared__ float s_iou[SQ_IDENT_MAXM * SQ_MAXN], s_dc2[SQ_IDENT_MAXM * SQ_MAXN], s_dw[SQ_IDENT_MAXM * SQ_MAXN];
   __shared__ float s_tbox[SQ_IDENT_MAXM * 4], s_twhat[SQ_IDENT_MAXM * SQ_MAX_NWHAT];
   __shared__ int s_tid[SQ_IDENT_MAXM], s_word[SQ_IDENT_MAXM], s_age[SQ_IDENT_MAXM], s_len[SQ_IDENT_MAXM];
@@ -740,8 +758,12 @@ __global__ __launch_bounds__(256) void k_lane_identity(const LaneIdentArgs a SQ_
     }
     __syncthreads();
     // ---- 2 .. 8: the links, the births and the ageing, one thread
+    if constexpr (OPT) {
+      __shared__ int s_w[SQ_IDENT_MAXM * SQ_MAXN];
+      if (tid < 64) sq_assign_keep_optimal(s_iou, N, M, N, o.iou_min, s_keep, s_jid, s_em, s_claim, s_w);
+    }
     if (tid == 0) {
-      sq_assign_keep_greedy(s_iou, N, M, N, o.iou_min, s_keep, s_jid, s_em, s_claim);
+      if constexpr (!OPT) sq_assign_keep_greedy(s_iou, N, M, N, o.iou_min, s_keep, s_jid, s_em, s_claim);
       for (int j = 0; j < N; ++j) { s_je[j] = -1; s_how[j] = -1; }
       for (int e = 0; e < M; ++e) {
         const int j = s_em[e];
@@ -826,8 +848,17 @@ __global__ __launch_bounds__(256) void k_lane_identity(const LaneIdentArgs a SQ_
     c[0] += c_frames; c[1] += c_invalid; c[2] += c_obj; c[3] += c_kept; c[4] += c_bridged; c[5] += c_reid; c[6] += c_born; c[7] += c_ended;
   }
 }
+__global__ __launch_bounds__(256) void k_lane_identity(const LaneIdentArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  sq_lane_identity_frames<false>(a);
+}
+__global__ __launch_bounds__(256) void k_lane_identity_opt(const LaneIdentArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  sq_lane_identity_frames<true>(a);
+}
 int sq_launch_lane_identity(const LaneIdentArgs& a, hipStream_t s) {
-  SQ_LAUNCH(k_lane_identity, dim3(a.B), dim3(256), 0, s, a);
+  if (a.match) SQ_LAUNCH(k_lane_identity_opt, dim3(a.B), dim3(256), 0, s, a);
+  else SQ_LAUNCH(k_lane_identity, dim3(a.B), dim3(256), 0, s, a);
   return 0;
 }
 
@@ -839,8 +870,10 @@ int sq_launch_lane_identity(const LaneIdentArgs& a, hipStream_t s) {
 // scored), thread 0 walks it (sq_assign_keep_greedy) -- and chunk 0 alone writes lane_counts and the [B, G] outputs.  Then thread =
 // frame f = z * SQ_TRAJ_FRAMES + tid, looping over the truth slots with the link read from LDS: it owns the cells (f, b) of counts
 // and sums.  The barriers are met by every thread: what differs between lanes is what the threads store around them.
-__global__ __launch_bounds__(256) void k_lane_traj_score(const LaneTrajScoreArgs a SQ_TLP) {
-  SQ_TL_SCOPE;
+// OPT (sqair_set_lane_match, traj_link = 1): wave 0 makes the link (sq_assign_keep_optimal) where thread 0 walks the greedy one.
+// OPT = false is k_lane_traj_score as it always was.
+template <bool OPT>
+__device__ __forceinline__ void sq_lane_traj_score_frames(const LaneTrajScoreArgs& a) {
   __shared__ float s_iou[SQ_SCORE_MAXG * SQ_MAXN];
   __shared__ int s_keep[SQ_SCORE_MAXG], s_gm[SQ_SCORE_MAXG], s_apres[SQ_SCORE_MAXG];
   __shared__ int s_id[SQ_MAXN], s_claim[SQ_MAXN];
@@ -867,7 +900,12 @@ __global__ __launch_bounds__(256) void k_lane_traj_score(const LaneTrajScoreArgs
   }
   if (tid < N) s_id[tid] = t.obj_id ? (int)sq_word(t.obj_id + (size_t)b * N + tid) : 0;
   __syncthreads();
-  if (tid == 0) sq_assign_keep_greedy(s_iou, N, G, N, o.iou_min, u.keep_id ? s_keep : nullptr, s_id, s_gm, s_claim);
+  if constexpr (OPT) {
+    __shared__ int s_w[SQ_SCORE_MAXG * SQ_MAXN];
+    if (tid < 64) sq_assign_keep_optimal(s_iou, N, G, N, o.iou_min, u.keep_id ? s_keep : nullptr, s_id, s_gm, s_claim, s_w);
+  } else {
+    if (tid == 0) sq_assign_keep_greedy(s_iou, N, G, N, o.iou_min, u.keep_id ? s_keep : nullptr, s_id, s_gm, s_claim);
+  }
   __syncthreads();
   if (blockIdx.y == 0) {
     if (tid < G) {
@@ -941,8 +979,18 @@ __global__ __launch_bounds__(256) void k_lane_traj_score(const LaneTrajScoreArgs
   }
   if (o.count_map) o.count_map[fb] = cm;
 }
+__global__ __launch_bounds__(256) void k_lane_traj_score(const LaneTrajScoreArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  sq_lane_traj_score_frames<false>(a);
+}
+__global__ __launch_bounds__(256) void k_lane_traj_score_opt(const LaneTrajScoreArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  sq_lane_traj_score_frames<true>(a);
+}
 int sq_launch_lane_traj_score(const LaneTrajScoreArgs& a, hipStream_t s) {
-  SQ_LAUNCH(k_lane_traj_score, dim3(a.B, (a.F + SQ_TRAJ_FRAMES - 1) / SQ_TRAJ_FRAMES), dim3(256), 0, s, a);
+  const dim3 grid(a.B, (a.F + SQ_TRAJ_FRAMES - 1) / SQ_TRAJ_FRAMES);
+  if (a.match) SQ_LAUNCH(k_lane_traj_score_opt, grid, dim3(256), 0, s, a);
+  else SQ_LAUNCH(k_lane_traj_score, grid, dim3(256), 0, s, a);
   return 0;
 }
 

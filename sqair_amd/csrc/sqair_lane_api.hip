@@ -169,6 +169,19 @@ extern "C" int sqair_set_identity(SqairHandle* h, const SqairLaneIdentity* id, i
   h->lane.ident_on = true; h->lane.ident = *id;
   return 0;
 }
+// per-frame matching (include/sqair_hip.h: sqair_set_lane_match): a plain setting of the handle, no registration; the pass reads it
+// through its resolved block (sq_resolve_pass), the stand-alone entry points read it at their launch
+extern "C" int sqair_set_lane_match(SqairHandle* h, int score, int identity, int traj_link) {
+  if (!h) return -1;
+  const int v[3] = {score, identity, traj_link};
+  const char* name[3] = {"score", "identity", "traj_link"};
+  for (int i = 0; i < 3; ++i)
+    if (v[i] != 0 && v[i] != 1)
+      return sq_no(h, std::string("sqair_set_lane_match: ") + name[i] + " = " + std::to_string(v[i]) +
+                          " must be 0 (keep + greedy) or 1 (keep + optimal)");
+  h->match_score = score; h->match_ident = identity; h->match_traj = traj_link;
+  return 0;
+}
 extern "C" int sqair_set_score_ids(SqairHandle* h, int lane_ids) {
   if (!h) return -1;
   if (lane_ids && !(h->state_on && h->lane.est_on && h->lane.score_on && h->lane.ident_on))
@@ -199,17 +212,17 @@ static LaneLayerArgs sq_layers_args(const SqairConfig& c, const LaneRows& rows, 
 }
 // (`what` is read only by an identity that keeps an appearance, trk_what)
 static LaneIdentArgs sq_identity_args(const SqairConfig& c, const float* box, const float* presence, const float* obj_id, const float* what,
-                                      const int32_t* best_row, const SqairLaneIdentity& id, int T, int B) {
+                                      const int32_t* best_row, const SqairLaneIdentity& id, int T, int B, int match) {
   LaneIdentArgs a; memset(&a, 0, sizeof(a));
   a.box = box; a.presence = presence; a.obj_id = obj_id; a.best_row = best_row; a.what = id.trk_what ? what : nullptr; a.id = id;
-  a.T = T; a.B = B; a.N = c.n_steps_per_image; a.nw = c.n_what;
+  a.T = T; a.B = B; a.N = c.n_steps_per_image; a.nw = c.n_what; a.match = match;
   return a;
 }
 static LaneScoreArgs sq_score_args(const SqairConfig& c, const float* box, const float* presence, const float* obj_id,
-                                   const int32_t* map_count, const SqairLaneScore& score, int T, int B) {
+                                   const int32_t* map_count, const SqairLaneScore& score, int T, int B, int match) {
   LaneScoreArgs a; memset(&a, 0, sizeof(a));
   a.box = box; a.presence = presence; a.obj_id = obj_id; a.map_count = map_count; a.sc = score;
-  a.T = T; a.B = B; a.N = c.n_steps_per_image;
+  a.T = T; a.B = B; a.N = c.n_steps_per_image; a.match = match;
   return a;
 }
 // (`ids`: the id words the score is handed for the same frames; of `score` the truth, iou_min, G and truth_match are read)
@@ -245,12 +258,12 @@ int sq_launch_lane_answers(SqairHandle* h, const SqLaneSet& l, const float* rec,
     return -2;
   }
   // lane identities: the lane's objects linked to the lane's track table (sqair_set_identity), updated in place
-  if (l.ident_on) sq_launch_lane_identity(sq_identity_args(c, e.box, e.presence, e.obj_id, e.what, e.best_row, l.ident, T, B), s);
+  if (l.ident_on) sq_launch_lane_identity(sq_identity_args(c, e.box, e.presence, e.obj_id, e.what, e.best_row, l.ident, T, B, l.ident_match), s);
   // stream scoring: the lane answer against the caller's ground truth (sqair_set_score), accumulated in place.  sqair_set_score_ids:
   // the kernel takes the id as a 32-bit word, so the identity's int32 lane_id stands where obj_id stands
   if (l.score_on) {
     const float* ids = (l.ident_on && l.score_ids) ? reinterpret_cast<const float*>(l.ident.lane_id) : e.obj_id;
-    sq_launch_lane_score(sq_score_args(c, e.box, e.presence, ids, e.map_count, l.score, T, B), s);
+    sq_launch_lane_score(sq_score_args(c, e.box, e.presence, ids, e.map_count, l.score, T, B, l.score_match), s);
     // IDF1 scoring: the clip's identity overlap table (sqair_set_idf), accumulated in place on the words the score just read
     if (l.idf_on) sq_launch_lane_idf(sq_idf_args(c, e.box, e.presence, ids, e.map_count, l.score, l.idf, T, B), s);
   }
@@ -299,7 +312,7 @@ extern "C" int sqair_lane_score_test(SqairHandle* h, const float* box, const flo
   if (!box || !presence || !obj_id || !map_count || !score || T < 1 || B < 1 || T > 65535)
     return sq_no(h, who + "null box / presence / obj_id / map_count / score or bad T / B");
   if (sq_score_fields(h, who, *score) != 0) return -1;
-  sq_launch_lane_score(sq_score_args(h->cfg, box, presence, obj_id, map_count, *score, T, B), (hipStream_t)stream);
+  sq_launch_lane_score(sq_score_args(h->cfg, box, presence, obj_id, map_count, *score, T, B, h->match_score), (hipStream_t)stream);
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -311,7 +324,7 @@ extern "C" int sqair_lane_identity_test(SqairHandle* h, const float* box, const 
     return sq_no(h, who + "null box / presence / obj_id / best_row / id or bad T / B");
   if (sq_identity_fields(h, who, *id) != 0) return -1;
   if (id->trk_what && !what) return sq_no(h, who + "id->trk_what needs what");
-  sq_launch_lane_identity(sq_identity_args(h->cfg, box, presence, obj_id, what, best_row, *id, T, B), (hipStream_t)stream);
+  sq_launch_lane_identity(sq_identity_args(h->cfg, box, presence, obj_id, what, best_row, *id, T, B, h->match_ident), (hipStream_t)stream);
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -361,7 +374,7 @@ extern "C" int sqair_lane_traj_score(SqairHandle* h, const SqairLaneTraj* table,
   if (truth->keep_id && !table->obj_id) return sq_no(h, who + "keep_id needs the table's obj_id: the identities it is compared with");
   LaneTrajScoreArgs a; memset(&a, 0, sizeof(a));
   a.tab = *table; a.tr = *truth; a.sc = *score;
-  a.F = F; a.B = B; a.N = h->cfg.n_steps_per_image;
+  a.F = F; a.B = B; a.N = h->cfg.n_steps_per_image; a.match = h->match_traj;
   sq_launch_lane_traj_score(a, (hipStream_t)stream);
   SQ_CHECK_HIP(hipGetLastError());
   return 0;

@@ -252,6 +252,7 @@ int sq_resolve_pass(SqairHandle* h, bool train, int T, int B, int t_offset, cons
   r.smc_on = h->smc_on; r.smc = h->smc;
   if (r.on) {   // (what rides on the carried state: all off without one)
     r.observed = h->observed; r.hist = h->hist; r.lane = h->lane;
+    r.lane.score_match = h->match_score; r.lane.ident_match = h->match_ident;   // (sqair_set_lane_match: read here, at launch time)
   }
   *st = r;
   if (r.hist.on && T >= 1) h->hist_T = T;   // (T < 1 is the pass's own to refuse)

@@ -19,7 +19,8 @@ the weighted mean of what the decoder drew for the object: its appearance ``laye
 ``truth=dict(box=[T', B, G, 4], present=[T', B, G], valid=[T', B] or None)`` -- (y, x, h, w) in pixels as ``make_sequences``'s
 ``coords``, G = ``score_truth`` slots per lane, an object keeping its slot for its life -- copied into stream-owned device buffers
 the way ``observed`` is; a step without ``truth`` scores nothing.  Present truths and present lane objects of IoU >= ``score_iou``
-are matched one to one (an object's last identity first, then greedily by IoU) and the CLEAR-MOT events counted on the device:
+are matched one to one (an object's last identity first, then greedily by IoU -- or, with ``score_match="optimal"``, as many pairs as
+possible and among those the largest total IoU, CLEAR-MOT's own rule: sqair_set_lane_match) and the CLEAR-MOT events counted on the device:
 ``out["lane"]`` gains ``truth_match``, ``match_iou`` [T', B, G] and ``tp``, ``fn``, ``fp``, ``idsw`` [T', B] (-1 where nothing was
 scored), and ``score()`` reads the accumulators.  ``reset(lanes)`` also forgets those lanes' identities (a new clip has new ones)
 and keeps their counters.
@@ -34,7 +35,8 @@ of the track's (the nearest appearance wins), else it is born under a fresh id. 
 (0 born, 1 kept, 2 bridged -- the obj_id changed under it --, 3 re-identified) and ``track_len`` [T', B, N] int32, -1 where the slot
 is absent; ``identities()`` reads the counters and the table.  ``reset(lanes)`` frees those lanes' tracks; ids are never reused
 within a lane.  ``score_ids="lane"`` (with ``score=True``) makes the score count its identity switches on ``lane_id`` instead of
-``obj_id``.
+``obj_id``.  ``identity_match="optimal"`` makes the position link keep + optimal where it is keep + greedy (sqair_set_lane_match);
+re-identification, births and ageing are the same either way.
 
 ``score_idf=True`` (with ``score=True``): the score's idsw counts the moments an identity changes, not for how long the wrong id then
 stays.  The stream then also keeps, per lane and on the device, how many frames of the open clip every truth overlapped (IoU >=
@@ -47,7 +49,7 @@ their tables are freed -- before it forgets their identities: a new clip has new
 ``forecast(..., lane=True, truth=...)`` and ``tracks(..., lane=True, truth=...)`` score the two answers that reach over time -- the
 lane forecast and the lane tracks -- against the truth's trajectories with one more launch after the call's own
 (sqair_lane_traj_score): truth and lane objects are linked once, at the last stepped frame, and every horizon or traced frame then
-gives displacement error, IoU, the Brier term of ``alive / support`` as a survival probability and the count's hit, accumulated on
+(``link_match="optimal"``: by keep + optimal, sqair_set_lane_match) gives displacement error, IoU, the Brier term of ``alive / support`` as a survival probability and the count's hit, accumulated on
 the device per (frame, lane); ``trajectory_score(kind)`` reads the sums and pools them into curves over the horizon without a lane
 table ever visiting the host."""
 from __future__ import annotations
@@ -58,6 +60,9 @@ import numpy as np
 import torch
 
 from sqair_amd import _capi
+
+
+MATCH_MODES = ("greedy", "optimal")   # the values of sqair_set_lane_match, by index (include/sqair_hip.h)
 
 
 def lane_answer(name, of="lane"):
@@ -132,7 +137,7 @@ class LaneAnswers(object):
 
     def __init__(self, who, estimate, estimate_iou, estimate_canvas, estimate_layers, layers_cover_min, score, score_iou, score_truth,
                  identity, identity_iou, identity_tracks, identity_max_age, identity_reid_dist, identity_reid_what, identity_appearance,
-                 score_ids, score_idf=False, score_idf_ids=32):
+                 score_ids, score_idf=False, score_idf_ids=32, score_match="greedy", identity_match="greedy"):
         self.step_fn, who = who + ".step: ", who + ": "
 
         def bad(why):
@@ -176,6 +181,13 @@ class LaneAnswers(object):
             bad("score_idf is for a stream with score=True")
         if score_idf and not is_int_in(score_idf_ids, 1, _capi.IDF_MAX_IDS):
             bad("score_idf_ids must be an integer in [1, {}]".format(_capi.IDF_MAX_IDS))
+        for name, v, flag, needs in (("score_match", score_match, score, "score=True"),
+                                     ("identity_match", identity_match, identity, "identity=True")):
+            if v not in MATCH_MODES:
+                bad("{} must be 'greedy' or 'optimal'".format(name))
+            if v == "optimal" and not flag:
+                bad("{}='optimal' is for a stream with {}".format(name, needs))
+        self.score_match, self.identity_match = MATCH_MODES.index(score_match), MATCH_MODES.index(identity_match)
         self.idf, self.P = bool(score_idf), int(score_idf_ids) if score_idf else 0
         self.who = who
         self.estimate, self.canvas, self.layers = bool(estimate), bool(estimate_canvas), bool(estimate_layers)
@@ -194,8 +206,10 @@ class LaneAnswers(object):
 
     def register(self, core, log_w, T, B):
         """Allocates the buffers and registers them on the handle: the estimate (``log_w``: the carried log weights -- after SMC, so
-        that they are the resampler's accumulator), then layers, score, identity, score_ids."""
+        that they are the resampler's accumulator), then layers, score, identity, score_ids; first of all the matching modes, a
+        plain setting of the handle that the passes read (sqair_set_lane_match; its traj_link is ``TrajScores.launch``'s, per call)."""
         self.core, self.T, self.B = core, T, B
+        core.check(core.lib.sqair_set_lane_match(core.handle, self.score_match, self.identity_match, 0), "sqair_set_lane_match")
         if not self.estimate:
             return
         lib, h, G, K, N = core.lib, core.handle, self.G, core.K, core.N
@@ -369,18 +383,22 @@ class LaneAnswers(object):
 
 # ---- the per-call trajectory scores of forecast() and tracks() -------------------------------------------------------------------
 class TrajScores(object):
-    """``acc``: by kind ("forecast", "tracks") the accumulators and per-call outputs of the LAST (F, G, truth_iou) scored.  ``lane``:
+    """``acc``: by kind ("forecast", "tracks") the accumulators and per-call outputs of the LAST (F, G, truth_iou, link_match) scored.  ``lane``:
     the stream's LaneAnswers (``link_ids`` keeps a truth with the identity its score last matched it with)."""
 
     def __init__(self, core, B, lane):
         self.core, self.B, self.lane, self.acc = core, B, lane, {}
 
-    def check_truth(self, fn, truth, lane, F, default_anchor, link_ids, truth_iou):
+    def check_truth(self, fn, truth, lane, F, default_anchor, link_ids, truth_iou, link_match="greedy"):
         """``truth`` of ``forecast`` / ``tracks`` as {name: tensor} in the C ABI's names and dtypes plus ``G`` and ``iou_min`` (None: no
-        truth); everything is checked here, before the core is touched."""
+        truth); everything is checked here, ``link_match`` too, before the core is touched."""
+        if link_match not in MATCH_MODES:
+            raise ValueError(fn + "link_match must be 'greedy' or 'optimal'")
         if truth is None:
             if link_ids:
                 raise ValueError(fn + "link_ids is for a call with truth")
+            if link_match == "optimal":
+                raise ValueError(fn + "link_match='optimal' is for a call with truth")
             return None
         if not lane:
             raise ValueError(fn + "truth is for a call with lane=True: the lane table is what is scored")
@@ -419,14 +437,15 @@ class TrajScores(object):
         return dict(G=G, iou_min=truth_iou, truth_box=box, truth_present=as_mask(present), truth_valid=as_mask(valid), anchor_box=a_box,
                     anchor_present=as_mask(a_present), anchor_valid=as_mask(a_valid))
 
-    def launch(self, kind, table, F, truth, link_ids):
+    def launch(self, kind, table, F, truth, link_ids, link_match="greedy"):
         """Scores the lane table a forecast or a trace has just written (``table``: its device buffers by field) against ``truth``
         (of check_truth) with one launch on the core's stream (include/sqair_hip.h: sqair_lane_traj_score); returns the per-call
-        outputs, copies.  The accumulators of ``kind`` are kept for the last (F, G, truth_iou) scored."""
+        outputs, copies.  The accumulators of ``kind`` are kept for the last (F, G, truth_iou, link_match) scored."""
         core, B = self.core, self.B
-        G, key = truth["G"], (F, truth["G"], truth["iou_min"])
+        match = MATCH_MODES.index(link_match)
+        G, key = truth["G"], (F, truth["G"], truth["iou_min"], match)
         ts = self.acc.get(kind)
-        if ts is None or ts["key"] != key:   # (another F, G or threshold: the old sums would not mean the same)
+        if ts is None or ts["key"] != key:   # (another F, G, threshold or matching: the old sums would not mean the same)
             z = lambda shp, dt: torch.zeros(shp, dtype=dt, device=core.device)
             ts = self.acc[kind] = dict(key=key, counts=z((F, B, len(_capi.TRAJ_COUNTS)), torch.int64),
                                        sums=z((F, B, len(_capi.TRAJ_SUMS)), torch.float64),
@@ -439,6 +458,9 @@ class TrajScores(object):
                                        **{n: t.data_ptr() for n, t in dev.items()})
         c_score = _capi.SqairTrajScore(iou_min=truth["iou_min"], **{n: ts[n].data_ptr() for n in _capi.TRAJ_ACCUMULATORS},
                                        **{n: t.data_ptr() for n, t in ts["out"].items()})
+        # (the link's mode is the call's; the score's and the identity's stay the stream's: the handle holds all three)
+        core.check(core.lib.sqair_set_lane_match(core.handle, self.lane.score_match, self.lane.identity_match, match),
+                   "sqair_set_lane_match")
         core.check(core.lib.sqair_lane_traj_score(core.handle, C.byref(c_tab), C.byref(c_truth), C.byref(c_score), F, B,
                                                   core._stream()), "sqair_lane_traj_score")
         return ts["views"](ts["flat"].clone())

@@ -41,7 +41,8 @@ network "see" an empty scene and kill the objects.
 
 With ``estimate=True`` a step also returns ``out["lane"]``: one answer per lane and frame from the K particles, and its followers
 say more about it, each one more kernel of the pass -- ``estimate_layers`` which pixels each object occupies, ``identity`` a track id
-that stays on an object, ``score`` the CLEAR-MOT events against a step's ``truth`` (``score()``, ``identities()``), ``score_idf`` the identity overlap table
+that stays on an object, ``score`` the CLEAR-MOT events against a step's ``truth`` (``score()``, ``identities()``; ``score_match`` / ``identity_match`` =
+"optimal": their per-frame matching as keep + optimal, sqair_set_lane_match), ``score_idf`` the identity overlap table
 IDF1 is solved from (``idf_score()``); ``forecast`` and
 ``tracks`` with ``lane=True, truth=...`` score the lane forecast and the lane tracks (``trajectory_score(kind)``).  sqair_amd/lane.py
 holds all of it and says what each returns.
@@ -74,7 +75,8 @@ class SqairStream(object):
                  state=None, history=None, history_fields=tuple(_capi.HISTORY_FIELDS), missing=False, estimate=False,
                  estimate_iou=0.5, estimate_canvas=False, estimate_layers=False, layers_cover_min=0.5, score=False, score_iou=0.5,
                  score_truth=None, identity=False, identity_iou=0.3, identity_tracks=None, identity_max_age=10, identity_reid_dist=4.0,
-                 identity_reid_what=float("inf"), identity_appearance=True, score_ids="row", score_idf=False, score_idf_ids=32):
+                 identity_reid_what=float("inf"), identity_appearance=True, score_ids="row", score_idf=False, score_idf_ids=32,
+                 score_match="greedy", identity_match="greedy"):
         if core.cfg.sample_from_prior:
             raise ValueError("SqairStream: generation modes (sample_from_prior) do not carry a state across calls")
         if resample not in (None, "systematic"):
@@ -84,7 +86,8 @@ class SqairStream(object):
             raise ValueError("SqairStream: ess_frac must lie in [0, 1]")
         la = self.lane = LaneAnswers("SqairStream", estimate, estimate_iou, estimate_canvas, estimate_layers, layers_cover_min, score,
                                      score_iou, score_truth, identity, identity_iou, identity_tracks, identity_max_age,
-                                     identity_reid_dist, identity_reid_what, identity_appearance, score_ids, score_idf, score_idf_ids)   # (checks only)
+                                     identity_reid_dist, identity_reid_what, identity_appearance, score_ids, score_idf, score_idf_ids,
+                                     score_match, identity_match)   # (checks only)
         self.smc = resample is not None
         self.ess_frac = ess_frac
         self.core = core
@@ -263,8 +266,8 @@ class SqairStream(object):
         return self.lane.identities()
 
     # ---- trajectory scoring ------------------------------------------------------------------------------------------------
-    def _check_traj_truth(self, fn, truth, lane, F, default_anchor, link_ids, truth_iou):
-        return self.traj.check_truth(fn, truth, lane, F, default_anchor, link_ids, truth_iou)
+    def _check_traj_truth(self, fn, truth, lane, F, default_anchor, link_ids, truth_iou, link_match="greedy"):
+        return self.traj.check_truth(fn, truth, lane, F, default_anchor, link_ids, truth_iou, link_match)
 
     def trajectory_score(self, kind, reset=False):
         """The trajectory score so far of ``kind`` = "forecast" or "tracks" (include/sqair_hip.h: sqair_lane_traj_score): what the
@@ -273,13 +276,13 @@ class SqairStream(object):
         lane ``calls``, ``calls_invalid``, ``anchor_truth``, ``linked`` [B] (host tensors).  Pooled over the lanes, per f, NaN where the
         denominator is 0: ``ade`` = centre_err_sum / pairs (``fde`` = its last entry), ``mean_iou`` = iou_sum / pairs, ``hit_rate`` =
         hits / (pairs + lost), ``brier`` = brier_sum / (pairs + lost + gone), ``count_accuracy`` = count_hit / frames [F] (float64), and
-        ``link_rate`` = linked / anchor_truth.  The accumulators belong to (kind, F, G, truth_iou): a call with truth of another F, G
-        or threshold starts fresh ones and drops the old.  ``reset``: they start again from zero afterwards."""
+        ``link_rate`` = linked / anchor_truth.  The accumulators belong to (kind, F, G, truth_iou, link_match): a call with truth of another F, G,
+        threshold or matching starts fresh ones and drops the old.  ``reset``: they start again from zero afterwards."""
         return self.traj.read(kind, reset)
 
     # ---- forecasting ------------------------------------------------------------------------------------------------------
     def forecast(self, F, noise=None, seed=None, outputs=FORECAST_OUTPUTS, summaries=True, samples=1, lane=False, lane_iou=0.5,
-                 truth=None, link_ids=False, truth_iou=0.5):
+                 truth=None, link_ids=False, truth_iou=0.5, link_match="greedy"):
         """Rolls the generative prior F frames forward from the rows the next ``step()`` would start from -- the state blob through
         the pending source map (a reset or resample armed since the last step, else identity; with SMC the map the resampler
         wrote) -- and returns {name: [F, B*K, ...]} for ``outputs`` (of FORECAST_OUTPUTS).  With ``summaries`` also the lanes'
@@ -304,7 +307,8 @@ class SqairStream(object):
         are linked there, by IoU >= ``truth_iou``); G in [1, 16] comes from the shapes, tensors already on the device are used where
         they are.  ``res["lane"]["score"]`` holds ``link``, ``link_iou`` [B, G], ``state``, ``p_alive``, ``pair_iou``, ``centre_err`` [F, B, G]
         and ``count_map`` [F, B]; ``trajectory_score("forecast")`` reads what the calls have accumulated.  ``link_ids=True`` (a stream
-        with ``score=True`` and the same G) keeps each truth with the identity the stream's score last matched it with.  Without
+        with ``score=True`` and the same G) keeps each truth with the identity the stream's score last matched it with;
+        ``link_match="optimal"`` links by keep + optimal where the default is keep + greedy (sqair_set_lane_match).  Without
         ``truth`` nothing is launched, and with it every other output is unchanged bit for bit."""
         F, S, lane, lane_iou = int(F), int(samples), bool(lane), float(lane_iou)
         if F < 1:
@@ -317,7 +321,7 @@ class SqairStream(object):
         bad = [n for n in outputs if n not in FORECAST_OUTPUTS]
         if bad:
             raise ValueError("SqairStream.forecast: unknown outputs {} (choose from {})".format(bad, FORECAST_OUTPUTS))
-        truth = self._check_traj_truth("SqairStream.forecast: ", truth, lane, F, False, link_ids, truth_iou)
+        truth = self._check_traj_truth("SqairStream.forecast: ", truth, lane, F, False, link_ids, truth_iou, link_match)
         core, cs = self.core, self.carried
         lib, dev = core.lib, core.device
         R, N, nzw = self.R * S, core.N, core.nzw
@@ -358,7 +362,7 @@ class SqairStream(object):
                                                       F, self.B, S, src.data_ptr(), C.byref(c_out), c_lane, fc["ws"].data_ptr(),
                                                       fc["ws"].numel() * 4, core._stream()), "sqair_forecast_fan")
                 res = {k: v.clone() for k, v in out.items()}
-                score = None if truth is None else self.traj.launch("forecast", fc["lane"], F, truth, link_ids)
+                score = None if truth is None else self.traj.launch("forecast", fc["lane"], F, truth, link_ids, link_match)
                 if lane:   # (views of one allocation: one copy, not one per field)
                     res["lane"] = fc["lane_views"](fc["lane_flat"].clone())
                     if score is not None:
@@ -394,7 +398,7 @@ class SqairStream(object):
 
     # ---- track history ----------------------------------------------------------------------------------------------------
     def tracks(self, lag=None, start="next", max_tracks=None, table=True, lane=False, lane_iou=0.5, truth=None, link_ids=False,
-               truth_iou=0.5):
+               truth_iou=0.5, link_match="greedy"):
         """Traces every particle row's ancestral path back over the last ``lag`` steps (default: all ``history`` kept) on the
         device: frames oldest -> newest, F = lag * frames_per_step.  ``start="next"``: from the rows the next ``step()`` would
         start from (the pending source map; with SMC the map the resampler wrote: the equally weighted surviving set), as
@@ -438,7 +442,7 @@ class SqairStream(object):
         if lane:
             check_unit("SqairStream.tracks: ", "lane_iou", lane_iou)
         lag, M = int(lag), int(M)
-        truth = self._check_traj_truth("SqairStream.tracks: ", truth, lane, lag * self.T, True, link_ids, truth_iou)
+        truth = self._check_traj_truth("SqairStream.tracks: ", truth, lane, lag * self.T, True, link_ids, truth_iou, link_match)
         key = (lag, start, M if table else None, bool(table), lane, lane_iou if lane else None)
         with torch.cuda.device(core.device):
             core._join_in()
@@ -461,7 +465,7 @@ class SqairStream(object):
                     core.check(core.lib.sqair_history_trace(core.handle, cs.ring.data_ptr(), None if src is None else src.data_ptr(),
                                                             lag, C.byref(c_out), core._stream()), "sqair_history_trace")
                 res = {k: v.clone() for k, v in tr["out"].items()}
-                score = None if truth is None else self.traj.launch("tracks", tr["lane"], lag * self.T, truth, link_ids)
+                score = None if truth is None else self.traj.launch("tracks", tr["lane"], lag * self.T, truth, link_ids, link_match)
                 if lane:   # (views of one allocation: one copy, not one per field)
                     res["lane"] = tr["lane_views"](tr["lane_flat"].clone())
                     if score is not None:
@@ -508,4 +512,5 @@ class SqairStream(object):
             core.check(core.lib.sqair_set_estimate(core.handle, None, 0, 0), "sqair_set_estimate")
             core.check(core.lib.sqair_set_history(core.handle, None, 0, 0, 0), "sqair_set_history")
             core.check(core.lib.sqair_set_state(core.handle, None, None, None, 0, 0), "sqair_set_state")
+            core.check(core.lib.sqair_set_lane_match(core.handle, 0, 0, 0), "sqair_set_lane_match")   # (a plain setting: nothing above resets it)
             core._graph_ready = False

@@ -68,6 +68,14 @@ next to the score's and the resampler's node of the same run, and the median tim
 and the host's pooling -- is measured separately.  Recorded, not gated on:
 
     python tools/stream_time.py --idf [--out profiles/stream_idf_time.json]
+
+With --match: the price of keep + optimal per-frame matching (SqairStream(score_match="optimal" / identity_match="optimal"),
+include/sqair_hip.h: sqair_set_lane_match) -- a wavefront's solve where the greedy mode is one thread's walk, in the same one node.
+Streams at cfg-2's batch alternating in one process as with --history, all with SMC and the estimate: SMC, SMC + estimate, score greedy,
+score optimal, identity greedy, identity optimal; the scored legs are fed a device-resident truth of overlapping boxes.  The difference
+optimal - greedy is reported next to the resampler's node of the same run.  Recorded, not gated on:
+
+    python tools/stream_time.py --match [--out profiles/stream_match_time.json]
 """
 import argparse
 import json
@@ -380,6 +388,39 @@ def time_idf(B, K, N, steps, warmup, rounds=10, hw=(50, 50), P=32):
     return res
 
 
+def time_match(B, K, N, steps, warmup, rounds=10, hw=(50, 50)):
+    smc = dict(resample="systematic", ess_frac=0.5)
+    est = dict(estimate=True, **smc)
+    sc = dict(est, score=True, score_truth=N)
+    idt = dict(est, identity=True)
+    legs = dict(plain={}, smc=smc, smc_estimate=est, score_greedy=sc, score_optimal=dict(sc, score_match="optimal"), identity_greedy=idt,
+                identity_optimal=dict(idt, identity_match="optimal"))
+    rng = np.random.default_rng(3)     # a crowd: the truths of a lane overlap each other
+    centre = rng.uniform(5, 25, (1, B, 1, 2))
+    box = np.concatenate([centre + rng.normal(0.0, 3.0, (1, B, N, 2)), rng.uniform(16, 24, (1, B, N, 2))], -1).astype(np.float32)
+    truth = dict(box=torch.as_tensor(box).cuda(), present=torch.ones((1, B, N), dtype=torch.int32).cuda(),
+                 valid=torch.ones((1, B), dtype=torch.int32).cuda())
+    step_kw = dict(score_greedy=dict(truth=truth), score_optimal=dict(truth=truth))
+    streams, res, med, thr = alternating_streams(legs, B, K, N, steps, warmup, rounds, hw, step_kw)
+    res["score"] = {m: {n: (v.sum().item() if torch.is_tensor(v) else v) for n, v in streams["score_" + m].score().items()}
+                    for m in ("greedy", "optimal")}   # (over the lanes)
+    res["identities"] = {m: {n: (int(v.sum()) if torch.is_tensor(v) and v.dim() == 1 else v)
+                             for n, v in streams["identity_" + m].identities().items() if not n.startswith("trk_")}
+                         for m in ("greedy", "optimal")}
+    for key, v in (("latency", med), ("back_to_back", thr)):
+        one_node = v["smc"] - v["plain"]            # the yardstick: one dependent node (the resampler) on this machine, this run
+        added = dict(score_node_greedy=v["score_greedy"] - v["smc_estimate"], score_node_optimal=v["score_optimal"] - v["smc_estimate"],
+                     identity_node_greedy=v["identity_greedy"] - v["smc_estimate"],
+                     identity_node_optimal=v["identity_optimal"] - v["smc_estimate"],
+                     score_optimal_minus_greedy=v["score_optimal"] - v["score_greedy"],
+                     identity_optimal_minus_greedy=v["identity_optimal"] - v["identity_greedy"])
+        res["us_" + key] = dict(smc_node=1e3 * one_node, **{n: 1e3 * a for n, a in added.items()},
+                                **{n + "_over_smc_node": (a / one_node if one_node > 0 else None) for n, a in added.items()})
+    for st in streams.values():
+        st.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=500)
@@ -394,10 +435,13 @@ def main():
     ap.add_argument("--score", action="store_true", help="plain / SMC / estimate / SMC + estimate / score / SMC + score, alternating (profiles/stream_score_time.json)")
     ap.add_argument("--identity", action="store_true", help="plain / SMC / estimate / identity / SMC + estimate / SMC + identity / score / score + identity, alternating (profiles/stream_identity_time.json)")
     ap.add_argument("--idf", action="store_true", help="score and score + IDF, each with and without SMC, alternating; idf_score() apart (profiles/stream_idf_time.json)")
+    ap.add_argument("--match", action="store_true", help="score and identity, greedy and optimal, with SMC and the estimate, alternating (profiles/stream_match_time.json)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     ov, _, _, _ = config_inputs(2)
-    if args.idf:
+    if args.match:
+        shapes = [dict(name="cfg2_batch_match", **time_match(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
+    elif args.idf:
         shapes = [dict(name="cfg2_batch_idf", **time_idf(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
     elif args.identity:
         shapes = [dict(name="cfg2_batch_identity", **time_identity(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
