@@ -1637,8 +1637,9 @@ int sqair_logprob_bwd_test(SqairHandle* h, const SqairLogprobBwdTest* t, void* s
  *                                4 k_linear_lds | k_linear_big with wave tile 5 2 x 2 | 6 3 x 2 | 7 3 x 3 | 8 4 x 2
  *   dX (sq_launch_linear_dx):    k_linear_dx<NCH> with NCH = 9 1 | 10 2 | 11 3 | 12 4 | 13 5 | 14 6 | 15 7 | 16 8 | 17 9 | 18 12 |
  *                                19 18 | 20 32 x 32 tiles (k_linear_dx_t2) | 21 GRU mode 1 | 22 GRU mode 2
+ *   forward, added later:        23 one-round strip (k_linear_strip; the split-K kernel's bits)
  * A refused launch (-5, -6) and an empty one count nothing. */
-#define SQAIR_DENSE_ROUTES 23
+#define SQAIR_DENSE_ROUTES 24
 int sqair_debug_dense_routes(int64_t* out, int n);
 
 #ifdef __cplusplus

@@ -355,7 +355,7 @@ class SqairLinearWhatTest(C.Structure):
 # sqair_debug_dense_routes: the families of the two dense launchers, in the order include/sqair_hip.h documents
 DENSE_ROUTES = ("fwd_splitk", "fwd_t2", "fwd_rows", "fwd_mt", "fwd_lds", "fwd_big_2x2", "fwd_big_3x2", "fwd_big_3x3", "fwd_big_4x2",
                 "dx_nch1", "dx_nch2", "dx_nch3", "dx_nch4", "dx_nch5", "dx_nch6", "dx_nch7", "dx_nch8", "dx_nch9", "dx_nch12", "dx_nch18",
-                "dx_t2", "dx_gru1", "dx_gru2")
+                "dx_t2", "dx_gru1", "dx_gru2", "fwd_strip")
 
 
 def dense_routes(library=None):

@@ -23,7 +23,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 SOURCES = ["sqair_api.hip", "sqair_state.hip", "sqair_linear.hip", "sqair_glue.hip", "sqair_bwd.hip", "sqair_train.hip", "sqair_linear_dx.hip", "sqair_chain.hip",
-           "sqair_lane.hip", "sqair_lane_api.hip", "sqair_pack.hip", "sqair_dense_test.hip", "sqair_unit_test.hip"]
+           "sqair_lane.hip", "sqair_lane_api.hip", "sqair_pack.hip", "sqair_dense_test.hip", "sqair_unit_test.hip",
+           "sqair_linear_strip.hip"]   # (last: the code objects of the other units keep their order in the binary)
 OUT = os.path.join(os.path.dirname(HERE), "libsqair_hip.so")
 OUT_TIMELINE = os.path.join(os.path.dirname(HERE), "libsqair_hip_timeline.so")
 OUT_KNOBS = os.path.join(ROOT, "tools", "bin", "libsqair_hip_knobs.so")

@@ -139,9 +139,11 @@ __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned
 enum DenseRoute {
   DR_SPLITK = 0, DR_T2, DR_ROWS, DR_MT, DR_LDS, DR_BIG22, DR_BIG32, DR_BIG33, DR_BIG42,
   DR_DX_NCH1, DR_DX_NCH2, DR_DX_NCH3, DR_DX_NCH4, DR_DX_NCH5, DR_DX_NCH6, DR_DX_NCH7, DR_DX_NCH8, DR_DX_NCH9, DR_DX_NCH12, DR_DX_NCH18,
-  DR_DX_T2, DR_DX_GRU1, DR_DX_GRU2, DR_COUNT
+  DR_DX_T2, DR_DX_GRU1, DR_DX_GRU2, DR_STRIP, DR_COUNT
 };
 void sq_dense_route_hit(int route);
+// sqair_linear_strip.hip: the one-round strip kernel's launch of a dense layer, if it takes it (*taken); else nothing happened
+SQ_LOCAL int sq_launch_linear_strip(const LinArgs& a, const PackedLayer& L, hipStream_t s, bool* taken);
 long long sq_dense_route_hits(int route);
 
 // launchers (sqair_linear.hip)

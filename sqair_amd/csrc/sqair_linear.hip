@@ -933,6 +933,9 @@ static unsigned rmul_of(int rdiv) { return rdiv <= 1 ? 0u : (unsigned)((1ull << 
 // say why and where).  Those sum a column's K chunks in sequence, the split-K kernel in four per-wave partial sums: the last bits of
 // a result differ between the two families.  Whoever promises the split-K kernel's bits from another launch (sq_what_fusion,
 // sqair_api.hip) asks here, so that the numbers exist once.
+// (The strip kernel -- DR_STRIP, sqair_linear_strip.hip -- is INSIDE the split-K family in this sense: same chunks per wave, same
+// accumulators, same order of the final sum, bit-identical results.  A launch that goes there has not left split-K: this predicate,
+// sq_what_fusion's and the slot chain are unaffected by it.)
 bool sq_linear_leaves_split_k(int M, const PackedLayer& L) {
   static const int mt_rows = SQ_KNOB_INT("SQAIR_MT_ROWS", SQAIR_MT_ROWS_DEFAULT);  // measurement knob (tools/build_rev.sh WT <name> -D...)
   // just below 2048 rows only the WIDE layers go to the LDS-tiled kernel (its 128 x 64 tiles then still number ~200):
@@ -1021,6 +1024,17 @@ int sq_launch_linear(const LinArgs& a_in, const PackedLayer& L, hipStream_t s) {
     sq_dense_route_hit(DR_T2);
     launch_t2_any(a, L, s);
     return 0;
+  }
+  // the widest once-per-frame layer on all slots (640 x 362 x 1152 at cfg-2: 2880 of these workgroups on 256 CUs): one round of
+  // workgroups, each with its rows of A resident in LDS and a strip of column tiles (sqair_linear_strip.hip).  Same bits as k_linear.
+  // The shapes it takes and the ones it was measured on and leaves here: there, and DESIGN.md section 6.
+  {
+    bool taken = false;
+    const int rc = sq_launch_linear_strip(a, L, s, &taken);
+    if (taken) {
+      if (rc == 0) sq_dense_route_hit(DR_STRIP);
+      return rc;
+    }
   }
   sq_dense_route_hit(DR_SPLITK);
   switch (per_wave) {

@@ -15,6 +15,10 @@
 // but cutting that chain with 8 or 16 waves per tile (one block each) is SLOWER (12.1 -> 30.9 us): every extra load in flight
 // lengthens the round trips; the memory system's delivery to scattered 64-byte row pieces is the limit.
 // Included twice by sqair_linear.hip / sqair_linear_dx.hip with SQ_T2_NAME / SQ_T2_DX set.
+// Below kc = 40 the forward launcher does not come here: the widest of those launches (640 x 362 x 1152) goes to the one-round strip
+// kernel of sqair_linear_strip.hip -- A resident in LDS, coalesced; B two chunks ahead behind UNCONDITIONAL loads (the `if` around
+// SQ_T2_ISSUE below makes hipcc wait vmcnt(0) at the next use: the round trip per block this header describes) -- the others stay
+// on k_linear.
 
 // operand fetch of one block of NB chunks starting at this wave's chunk index `BASE` into register set SET
 #define SQ_T2_ISSUE(SET, BASE)                                                                                     \
