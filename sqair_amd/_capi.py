@@ -1,4 +1,7 @@
-"""ctypes binding of libsqair_hip.so (C-ABI declared in include/sqair_hip.h).
+"""ctypes binding of libsqair_hip.so, made from the C header at import: include/sqair_hip.h is the one statement of the C-ABI
+(sqair_amd/_abi.py parses it), so the header travels with the package and an import without it fails.  What is written here is what
+the header does not state in code: the shapes, which fields of a struct are inputs and which outputs, the column names of the counter
+tables, the names a step's ``lane`` dict uses.
 
 The library is built in-tree by ``__graft_entry__.build()`` / ``sqair_amd/csrc/build.py``.  There is
 no CPU fallback: if the shared object is missing the import of the HIP path fails loudly.
@@ -8,68 +11,44 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+from sqair_amd import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsqair_hip.so")
 
-OUTPUT_FIELDS = [
-    "what", "what_loc", "what_scale", "where", "where_loc", "where_scale", "presence_prob", "presence",
-    "presence_logit", "obj_id", "step_log_prob", "canvas", "glimpse", "disc_what_log_prob",
-    "disc_where_log_prob", "disc_what_prior_log_prob", "disc_where_prior_log_prob", "disc_log_prob",
-    "disc_prior_log_prob", "disc_prob", "prop_what_log_prob", "prop_where_log_prob",
-    "prop_what_prior_log_prob", "prop_where_prior_log_prob", "prop_log_prob", "prop_prior_log_prob",
-    "prop_prob", "discrete_log_prob", "num_prop_steps_per_sample", "num_disc_steps_per_sample",
-    "num_steps_per_sample", "prop_pres", "disc_pres", "data_ll_per_sample", "kl_per_sample",
-    "log_q_z_given_x_per_sample", "log_p_z_per_sample", "log_weights_per_timestep",
-    "final_temporal_state", "final_prior_state", "final_last_used_id",
-]
+_HEADER = _abi.header()
+_K = _HEADER.constants
+# SqairLogprobTest.out: the address of a SqairOutputs, set as an integer like the device addresses beside it
+_STRUCTS, _HEADER_PROTOS = _abi.bind(_HEADER, addresses={("SqairLogprobTest", "out")})
+globals().update(_STRUCTS)   # SqairConfig, SqairOutputs, SqairSmc, ...: one ctypes.Structure per struct of the header
+field_dtype = _abi.field_dtype
+
+
+def _pointers(struct, after=None, without=()):
+    """The pointer fields of a struct in declaration order (``after``: those behind that field), but for ``without``."""
+    names = [f.name for f in _HEADER.structs[struct] if f.pointer_depth]
+    return tuple(n for n in names[names.index(after) + 1 if after else 0:] if n not in without)
+
+
+def _int32(struct, names):
+    """Those of the struct's fields ``names`` that the header types int32_t*."""
+    return tuple(n for n in names if field_dtype(struct, n) == "int32")
+
+
+def _counted(constant, *names):
+    """The column names of a counter table, as many as the header's constant says."""
+    assert len(names) == _K[constant], "{} is {} in the header, this binding names {} columns".format(constant, _K[constant], len(names))
+    return names
+
+
+OUTPUT_FIELDS = [f.name for f in _HEADER.structs["SqairOutputs"]]
 N_REFERENCE_OUTPUTS = 38  # the TensorArrays of reference sqair/seq.py:121-177
-
-
-class SqairConfig(C.Structure):
-    _fields_ = [
-        ("img_h", C.c_int32), ("img_w", C.c_int32), ("glimpse_size", C.c_int32),
-        ("n_steps_per_image", C.c_int32), ("n_what", C.c_int32), ("n_hidden", C.c_int32),
-        ("k_particles", C.c_int32), ("prop_prior_type", C.c_int32), ("disc_prior_type", C.c_int32),
-        ("masked_glimpse", C.c_int32), ("rec_where_prior", C.c_int32),
-        ("prop_prior_step_bias", C.c_float), ("step_success_prob", C.c_float), ("output_std", C.c_float),
-        ("background_std", C.c_float), ("where_prior_mean", C.c_float * 4),
-        ("sample_from_prior", C.c_int32), ("generate_after", C.c_int32), ("time_cell", C.c_int32), ("prior_cell", C.c_int32), ("rnn_cell", C.c_int32),
-    ]
-
-
-class SqairOutputs(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in OUTPUT_FIELDS]
-
-
-class SqairSmc(C.Structure):
-    """SMC resampling of a carried state (include/sqair_hip.h: sqair_set_smc); every pointer is a device address."""
-    _fields_ = [
-        ("ess_frac", C.c_float), ("seed", C.c_uint64), ("uniforms", C.c_void_p), ("log_w", C.c_void_p), ("log_z", C.c_void_p),
-        ("log_evidence", C.c_void_p), ("ess", C.c_void_p), ("u_out", C.c_void_p), ("resampled", C.c_void_p),
-        ("src_rows", C.c_void_p),
-    ]
-
-
-class SqairCarry(C.Structure):
-    """A carried training chunk (include/sqair_hip.h: sqair_forward_train_carry / sqair_backward_carry); device addresses."""
-    _fields_ = [
-        ("state_in", C.c_void_p), ("state_out", C.c_void_p), ("src_rows", C.c_void_p), ("state_bytes", C.c_int64),
-        ("B", C.c_int32), ("smc", C.POINTER(SqairSmc)),
-    ]
-
-
-class SqairForecastOutputs(C.Structure):
-    """Outputs of sqair_forecast (include/sqair_hip.h); every pointer is a device address or None."""
-    _fields_ = [(n, C.c_void_p) for n in ("what", "where", "presence", "presence_prob", "presence_logit", "obj_id", "canvas", "glimpse",
-                                          "log_w", "mean_canvas", "expected_count")]
-
 
 # object forecasts (include/sqair_hip.h: sqair_forecast_fan): the outputs of SqairForecastLane in declaration order, with their shapes
 # in terms of F, B, K, N (R = B * K)
-FORECAST_LANE_FIELDS = ("best_row", "weights", "start_where", "start_presence", "start_obj_id", "obj_id", "presence", "box0", "support",
-                        "alive", "box_mean", "box_std", "count_prob")
-FORECAST_LANE_INT_FIELDS = ("best_row",)
-FORECAST_FAN_MAX = 1024
+FORECAST_LANE_FIELDS = _pointers("SqairForecastLane")
+FORECAST_LANE_INT_FIELDS = _int32("SqairForecastLane", FORECAST_LANE_FIELDS)
+FORECAST_FAN_MAX = _K["SQAIR_FORECAST_FAN_MAX"]
 
 
 def forecast_lane_shapes(F, B, K, N):
@@ -79,16 +58,9 @@ def forecast_lane_shapes(F, B, K, N):
                 count_prob=(F, B, N + 1))
 
 
-class SqairForecastLane(C.Structure):
-    """One predictive answer per object of a lane from its K * S rollouts (include/sqair_hip.h: sqair_forecast_fan); every pointer is
-    a device address, all but best_row optional."""
-    _fields_ = [("iou_min", C.c_float)] + [(n, C.c_void_p) for n in FORECAST_LANE_FIELDS]
-
-
-# lane estimates (include/sqair_hip.h: sqair_set_estimate): the outputs of SqairLaneEstimate in declaration order; the two int32 ones
-ESTIMATE_FIELDS = ("best_row", "weights", "ess", "count_prob", "expected_count", "map_count", "presence", "obj_id", "where", "what",
-                   "box", "support", "box_mean", "mean_canvas")
-ESTIMATE_INT_FIELDS = ("best_row", "map_count")
+# lane estimates (include/sqair_hip.h: sqair_set_estimate): the outputs of SqairLaneEstimate in declaration order; the int32 ones
+ESTIMATE_FIELDS = _pointers("SqairLaneEstimate", after="log_w")
+ESTIMATE_INT_FIELDS = _int32("SqairLaneEstimate", ESTIMATE_FIELDS)
 
 
 def estimate_shapes(T, B, K, N, nw, canvas_hw=None):
@@ -101,15 +73,9 @@ def estimate_shapes(T, B, K, N, nw, canvas_hw=None):
     return shapes
 
 
-class SqairLaneEstimate(C.Structure):
-    """One answer per lane from its particles (include/sqair_hip.h: sqair_set_estimate); every pointer is a device address, all but
-    best_row optional."""
-    _fields_ = [("iou_min", C.c_float), ("log_w", C.c_void_p)] + [(n, C.c_void_p) for n in ESTIMATE_FIELDS]
-
-
-# object layers (include/sqair_hip.h: sqair_set_layers): the outputs of SqairLaneLayers in declaration order; the two int32 ones
-LAYERS_FIELDS = ("match", "layer", "cover", "owner")
-LAYERS_INT_FIELDS = ("match", "owner")
+# object layers (include/sqair_hip.h: sqair_set_layers): the outputs of SqairLaneLayers in declaration order; the int32 ones
+LAYERS_FIELDS = _pointers("SqairLaneLayers")
+LAYERS_INT_FIELDS = _int32("SqairLaneLayers", LAYERS_FIELDS)
 
 
 def layers_shapes(T, B, K, N, hw):
@@ -118,19 +84,13 @@ def layers_shapes(T, B, K, N, hw):
     return dict(match=(T, B, K, N), layer=(T, B, N) + hw, cover=(T, B, N) + hw, owner=(T, B) + hw)
 
 
-class SqairLaneLayers(C.Structure):
-    """Per-object appearance, coverage and pixel owners of a lane (include/sqair_hip.h: sqair_set_layers); every pointer is a
-    device address, each optional, at least one set."""
-    _fields_ = [("cover_min", C.c_float)] + [(n, C.c_void_p) for n in LAYERS_FIELDS]
-
-
-# stream scoring (include/sqair_hip.h: sqair_set_score): the per-frame outputs of SqairLaneScore in declaration order and the int32
-# ones among them; the inputs and accumulators before them; the columns of ``counts``
-SCORE_FIELDS = ("truth_match", "match_iou", "tp", "fn", "fp", "idsw")
-SCORE_INT_FIELDS = ("truth_match", "tp", "fn", "fp", "idsw")
+# stream scoring (include/sqair_hip.h: sqair_set_score): the inputs and accumulators of SqairLaneScore; the per-frame outputs, the
+# rest of its pointers, and the int32 ones among them; the columns of ``counts``
 SCORE_INPUTS = ("truth_box", "truth_present", "truth_valid", "counts", "iou_sum", "last_id")
-SCORE_COUNTS = ("frames", "frames_invalid", "truth", "tp", "fn", "fp", "idsw", "count_hit", "count_abs_err")
-SCORE_MAX_TRUTH = 16
+SCORE_FIELDS = _pointers("SqairLaneScore", without=SCORE_INPUTS)
+SCORE_INT_FIELDS = _int32("SqairLaneScore", SCORE_FIELDS)
+SCORE_COUNTS = _counted("SQAIR_SCORE_COUNTS", "frames", "frames_invalid", "truth", "tp", "fn", "fp", "idsw", "count_hit", "count_abs_err")
+SCORE_MAX_TRUTH = _K["SQAIR_SCORE_MAX_TRUTH"]
 
 
 def score_shapes(T, B, G):
@@ -138,39 +98,29 @@ def score_shapes(T, B, G):
     return dict(truth_match=(T, B, G), match_iou=(T, B, G), tp=(T, B), fn=(T, B), fp=(T, B), idsw=(T, B))
 
 
-class SqairLaneScore(C.Structure):
-    """CLEAR-MOT scoring of the lane answer against ground-truth boxes (include/sqair_hip.h: sqair_set_score); every pointer is a
-    device address, the per-frame outputs (SCORE_FIELDS) optional."""
-    _fields_ = [("iou_min", C.c_float), ("G", C.c_int32)] + [(n, C.c_void_p) for n in SCORE_INPUTS + SCORE_FIELDS]
-
-
-# IDF1 scoring (include/sqair_hip.h: sqair_set_idf): the table's fields of SqairLaneIdf in declaration order (all int32) with their
-# shapes, then ``totals`` (int64) and its columns -- the twelve figures of a clip
-IDF_TABLE = ("col_id", "overlap", "row_frames", "col_frames", "extra_frames", "matched", "frag", "trk_state", "frames")
-IDF_TOTALS = ("clips", "frames", "trajectories", "idtp", "idfn", "idfp", "mt", "pt", "ml", "frag", "ids", "overflow_ids")
-IDF_MAX_IDS = 64
+# IDF1 scoring (include/sqair_hip.h: sqair_set_idf): the table's fields of SqairLaneIdf in declaration order with their shapes, then
+# ``totals`` and its columns -- the twelve figures of a clip
+IDF_TABLE = _pointers("SqairLaneIdf", without=("totals",))
+IDF_TOTALS = _counted("SQAIR_IDF_TOTALS", "clips", "frames", "trajectories", "idtp", "idfn", "idfp", "mt", "pt", "ml", "frag", "ids",
+                      "overflow_ids")
+IDF_MAX_IDS = _K["SQAIR_IDF_MAX_IDS"]
 
 
 def idf_shapes(B, G, P):
-    """The table's shapes for G truth slots and P id columns per lane (int32), and ``totals`` (int64)."""
+    """The table's shapes for G truth slots and P id columns per lane, and ``totals``."""
     return dict(col_id=(B, P), overlap=(B, G, P), row_frames=(B, G), col_frames=(B, P), extra_frames=(B,), matched=(B, G), frag=(B, G),
                 trk_state=(B, G), frames=(B,), totals=(B, len(IDF_TOTALS)))
 
 
-class SqairLaneIdf(C.Structure):
-    """The identity overlap table of a clip per lane and the totals over closed clips (include/sqair_hip.h: sqair_set_idf); every
-    pointer is a device address, none optional."""
-    _fields_ = [("P", C.c_int32)] + [(n, C.c_void_p) for n in IDF_TABLE + ("totals",)]
-
-
-# lane identities (include/sqair_hip.h: sqair_set_identity): the scalars, the memory and the per-frame outputs of SqairLaneIdentity
-# in declaration order (all outputs int32); the names the outputs have in a step's ``lane`` dict; the columns of ``counts``
-IDENT_SCALARS = (("iou_min", C.c_float), ("reid_dist", C.c_float), ("reid_what", C.c_float), ("M", C.c_int32), ("max_age", C.c_int32))
-IDENT_MEMORY = ("trk_id", "trk_word", "trk_age", "trk_len", "trk_box", "trk_what", "next_id", "counts")
-IDENT_FIELDS = ("lane_id", "how", "track_len")
+# lane identities (include/sqair_hip.h: sqair_set_identity): the names the per-frame outputs of SqairLaneIdentity have in a step's
+# ``lane`` dict; the scalars before them and the memory, the rest of its pointers; the columns of ``counts``
 IDENT_LANE_NAMES = dict(lane_id="lane_id", how="id_how", track_len="track_len")
-IDENT_COUNTS = ("frames", "frames_invalid", "objects", "kept", "bridged", "reidentified", "born", "ended")
-IDENT_MAX_TRACKS = 16
+IDENT_FIELDS = tuple(IDENT_LANE_NAMES)
+IDENT_INT_FIELDS = _int32("SqairLaneIdentity", IDENT_FIELDS)
+IDENT_SCALARS = tuple((n, t) for n, t in _STRUCTS["SqairLaneIdentity"]._fields_ if t is not C.c_void_p)
+IDENT_MEMORY = _pointers("SqairLaneIdentity", without=IDENT_FIELDS)
+IDENT_COUNTS = _counted("SQAIR_IDENT_COUNTS", "frames", "frames_invalid", "objects", "kept", "bridged", "reidentified", "born", "ended")
+IDENT_MAX_TRACKS = _K["SQAIR_IDENT_MAX_TRACKS"]
 
 
 def identity_shapes(T, B, N):
@@ -179,29 +129,23 @@ def identity_shapes(T, B, N):
 
 
 def identity_memory_shapes(B, M, nw):
-    """The memory's and the counters' shapes for M track entries per lane; every array int32 but trk_box, trk_what (float32) and
-    counts (int64)."""
+    """The memory's and the counters' shapes for M track entries per lane."""
     return dict(trk_id=(B, M), trk_word=(B, M), trk_age=(B, M), trk_len=(B, M), trk_box=(B, M, 4), trk_what=(B, M, nw), next_id=(B,),
                 counts=(B, len(IDENT_COUNTS)))
 
 
-class SqairLaneIdentity(C.Structure):
-    """Stable per-lane track ids (include/sqair_hip.h: sqair_set_identity); every pointer is a device address, trk_what, how and
-    track_len optional."""
-    _fields_ = list(IDENT_SCALARS) + [(n, C.c_void_p) for n in IDENT_MEMORY + IDENT_FIELDS]
-
-
-# trajectory scoring (include/sqair_hip.h: sqair_lane_traj_score): the three structs' pointer fields in declaration order, the int32
-# ones among the per-call outputs, the columns of ``counts`` [F, B, .], ``sums`` [F, B, .] and ``lane_counts`` [B, .]
-TRAJ_TABLE_FIELDS = ("best_row", "presence", "obj_id", "support", "box0", "alive", "box_mean", "count_prob", "valid_mass")
+# trajectory scoring (include/sqair_hip.h: sqair_lane_traj_score): the three structs' pointer fields in declaration order -- of
+# SqairTrajScore the accumulators, then the per-call outputs and the int32 ones among them --, the columns of ``counts`` [F, B, .],
+# ``sums`` [F, B, .] and ``lane_counts`` [B, .]
+TRAJ_TABLE_FIELDS = _pointers("SqairLaneTraj")
 TRAJ_TABLE_OPTIONAL = ("obj_id", "valid_mass")
-TRAJ_TRUTH_FIELDS = ("anchor_box", "anchor_present", "anchor_valid", "truth_box", "truth_present", "truth_valid", "keep_id")
+TRAJ_TRUTH_FIELDS = _pointers("SqairTrajTruth")
 TRAJ_ACCUMULATORS = ("counts", "sums", "lane_counts")
-TRAJ_FIELDS = ("link", "link_iou", "state", "p_alive", "pair_iou", "centre_err", "count_map")
-TRAJ_INT_FIELDS = ("link", "state", "count_map")
-TRAJ_COUNTS = ("frames", "pairs", "hits", "lost", "gone", "count_hit", "count_abs_err")
-TRAJ_SUMS = ("iou_sum", "centre_err_sum", "brier_sum")
-TRAJ_LANE_COUNTS = ("calls", "calls_invalid", "anchor_truth", "linked")
+TRAJ_FIELDS = _pointers("SqairTrajScore", without=TRAJ_ACCUMULATORS)
+TRAJ_INT_FIELDS = _int32("SqairTrajScore", TRAJ_FIELDS)
+TRAJ_COUNTS = _counted("SQAIR_TRAJ_COUNTS", "frames", "pairs", "hits", "lost", "gone", "count_hit", "count_abs_err")
+TRAJ_SUMS = _counted("SQAIR_TRAJ_SUMS", "iou_sum", "centre_err_sum", "brier_sum")
+TRAJ_LANE_COUNTS = _counted("SQAIR_TRAJ_LANE_COUNTS", "calls", "calls_invalid", "anchor_truth", "linked")
 
 
 def traj_shapes(F, B, G):
@@ -210,39 +154,17 @@ def traj_shapes(F, B, G):
                 count_map=(F, B))
 
 
-class SqairLaneTraj(C.Structure):
-    """The table a lane forecast or a lane trace wrote, as the trajectory score reads it (include/sqair_hip.h:
-    sqair_lane_traj_score); device addresses, obj_id and valid_mass optional."""
-    _fields_ = [(n, C.c_void_p) for n in TRAJ_TABLE_FIELDS]
-
-
-class SqairTrajTruth(C.Structure):
-    """The truth of a trajectory score: the anchor and the table's frames; device addresses, keep_id optional."""
-    _fields_ = [("G", C.c_int32)] + [(n, C.c_void_p) for n in TRAJ_TRUTH_FIELDS]
-
-
-class SqairTrajScore(C.Structure):
-    """The accumulators (required) and the per-call outputs (TRAJ_FIELDS, optional) of a trajectory score; device addresses."""
-    _fields_ = [("iou_min", C.c_float)] + [(n, C.c_void_p) for n in TRAJ_ACCUMULATORS + TRAJ_FIELDS]
-
-
-# track history (include/sqair_hip.h: sqair_set_history): the bit of each field a ring slot may hold; the first three are mandatory
-HISTORY_FIELDS = {"where": 1, "presence": 2, "obj_id": 4, "what": 8, "log_weights_per_timestep": 16}
+# track history (include/sqair_hip.h: sqair_set_history): the bit of each output a ring slot may hold; the first three are mandatory
+HISTORY_FIELDS = {n: _K["SQAIR_HIST_" + bit] for n, bit in (("where", "WHERE"), ("presence", "PRESENCE"), ("obj_id", "OBJ_ID"),
+                                                            ("what", "WHAT"), ("log_weights_per_timestep", "LOG_W"))}
 HISTORY_MANDATORY = ("where", "presence", "obj_id")
-TRACE_FIELDS = ("where", "presence", "obj_id", "what", "log_w", "valid", "frame_index", "ancestor_row", "unique_ancestors", "track_id",
-                "n_tracks", "track_present", "track_where")
-
-
-class SqairTraceOutputs(C.Structure):
-    """Outputs of sqair_history_trace (include/sqair_hip.h); T = frames per pass, every pointer a device address or None."""
-    _fields_ = [("T", C.c_int32), ("max_tracks", C.c_int32)] + [(n, C.c_void_p) for n in TRACE_FIELDS]
-
+assert sum(HISTORY_FIELDS[n] for n in HISTORY_MANDATORY) == _K["SQAIR_HIST_MANDATORY"] and sum(HISTORY_FIELDS.values()) == _K["SQAIR_HIST_ALL"]
+TRACE_FIELDS = _pointers("SqairTraceOutputs")
 
 # lane tracks (include/sqair_hip.h: sqair_history_trace_lane): the outputs of SqairTraceLane in declaration order, with their shapes
 # in terms of F = lag * T, B, K, N
-TRACK_LANE_FIELDS = ("best_row", "weights", "obj_id", "presence", "box0", "support", "first_frame", "alive", "box_mean", "box_std",
-                     "count_prob", "valid_mass")
-TRACK_LANE_INT_FIELDS = ("best_row", "first_frame")
+TRACK_LANE_FIELDS = _pointers("SqairTraceLane")
+TRACK_LANE_INT_FIELDS = _int32("SqairTraceLane", TRACK_LANE_FIELDS)
 
 
 def track_lane_shapes(F, B, K, N):
@@ -250,112 +172,10 @@ def track_lane_shapes(F, B, K, N):
                 alive=(F, B, N), box_mean=(F, B, N, 4), box_std=(F, B, N, 4), count_prob=(F, B, N + 1), valid_mass=(F, B))
 
 
-class SqairTraceLane(C.Structure):
-    """One smoothed trajectory per object of a lane from its K traced paths (include/sqair_hip.h: sqair_history_trace_lane); every
-    pointer is a device address, all but best_row optional."""
-    _fields_ = [("iou_min", C.c_float)] + [(n, C.c_void_p) for n in TRACK_LANE_FIELDS]
-
-
-class SqairDenseSeg(C.Structure):
-    _fields_ = [("p", C.c_void_p), ("ld", C.c_int32), ("width", C.c_int32), ("rdiv", C.c_int32)]
-
-
-class SqairDenseContract(C.Structure):
-    """One dense launch with everything the operand contract can say (include/sqair_hip.h: sqair_linear_contract_test); device
-    addresses, handed to the launcher unchanged."""
-    _fields_ = [("nseg", C.c_int32), ("seg", SqairDenseSeg * 4), ("w", C.c_void_p), ("b", C.c_void_p), ("add", C.c_void_p),
-                ("add_ld", C.c_int32), ("add_n", C.c_int32), ("add_rdiv", C.c_int32), ("act_a", C.c_int32), ("act_b", C.c_int32),
-                ("act_split", C.c_int32), ("scale", C.c_float), ("scale_ptr", C.c_void_p), ("out", C.c_void_p), ("out_ld", C.c_int32),
-                ("M", C.c_int32), ("N", C.c_int32), ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64)]
-
-
-class SqairDxRange(C.Structure):
-    _fields_ = [("n0", C.c_int32), ("n1", C.c_int32), ("dst", C.c_void_p), ("dst_ld", C.c_int32), ("dst2", C.c_void_p),
-                ("dst2_ld", C.c_int32), ("add", C.c_void_p), ("add_ld", C.c_int32), ("saved", C.c_void_p), ("saved_ld", C.c_int32),
-                ("act_a", C.c_int32), ("act_b", C.c_int32), ("act_split", C.c_int32)]
-
-
-class SqairDxGru(C.Structure):
-    _fields_ = [("mode", C.c_int32), ("g0", C.c_void_p), ("g0_ld", C.c_int32), ("g1", C.c_void_p), ("g1_ld", C.c_int32),
-                ("hprev", C.c_void_p), ("h_ld", C.c_int32), ("dpre1", C.c_void_p), ("dp_ld", C.c_int32), ("d_h", C.c_void_p),
-                ("dh_ld", C.c_int32), ("acc_dh", C.c_int32), ("dup", C.c_void_p), ("dup_ld", C.c_int32), ("dup_h_off", C.c_int32),
-                ("nh", C.c_int32)]
-
-
-class SqairDxTest(C.Structure):
-    """One launch of the routed dX GEMM (include/sqair_hip.h: sqair_linear_dx_test); device addresses, handed on unchanged."""
-    _fields_ = [("dpre", C.c_void_p), ("ld", C.c_int32), ("width", C.c_int32), ("M", C.c_int32), ("w", C.c_void_p),
-                ("Kdim", C.c_int32), ("scale_ptr", C.c_void_p), ("nranges", C.c_int32), ("r", SqairDxRange * 3), ("gru", SqairDxGru),
-                ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64)]
-
-
-def _fields(spec):
-    """'p name' = device address, 'i name' = int32; in the header's order."""
-    return [(s.split()[1], C.c_void_p if s.split()[0] == "p" else C.c_int32) for s in spec]
-
-
-class SqairSlotTailBwdTest(C.Structure):
-    """One launch of the slot-tail adjoint (include/sqair_hip.h: sqair_slot_tail_bwd_test); device addresses, handed on unchanged."""
-    _fields_ = _fields(["i is_disc", "i slot", "i B", "i enc_pre", "p rec_prev", "p rec_new", "p d_rec_new", "p d_rec_prev", "p s1h",
-                        "i s1h_ld", "p hraw", "i h_ld", "p enc", "i enc_ld", "p noise", "p flat", "p d_s1pre", "i ds_ld", "p d_s1pre2",
-                        "i ds2_ld", "p d_raw_out", "i dr_ld", "p d_enc", "i de_ld", "p d_hraw", "i dh_ld"])
-
-
-class SqairCropChainBwdTest(C.Structure):
-    """One launch of the crop adjoint of the recurrence (include/sqair_hip.h: sqair_crop_chain_bwd_test)."""
-    _fields_ = _fields(["i mode", "i slot", "i B", "i mask_dact", "p img", "p rec_prev", "p rec_new", "p d_rec_prev", "p d_rec_new", "p wb",
-                        "i wb_ld", "p d_wb", "p mask", "i mask_row_mul", "i mask_row_add", "p d_mask", "p g_out", "i g_row_mul",
-                        "i g_row_add", "p tp", "i tp_ld", "p d_tp", "i dtp_ld", "p noise", "p flat", "p w3", "p t2", "i t2_ld", "p d_t2",
-                        "i dt2_ld"])
-
-
-class SqairWhereParamGradsTest(C.Structure):
-    """The batched where-parameter reduction (include/sqair_hip.h: sqair_where_param_grads_test)."""
-    _fields_ = _fields(["i T", "i B", "p d_tp", "i tp_ld", "p d_rec_p", "p rec_p", "p noise", "p flat_grad"])
-
-
-class SqairGruGatesBwdTest(C.Structure):
-    """Both stages of the slot RNN's GRU gate adjoints (include/sqair_hip.h: sqair_gru_gates_bwd_test)."""
-    _fields_ = _fields(["i rows", "i accumulate_dh", "p d_hn", "i dhn_ld", "p z", "i z_ld", "p r", "i r_ld", "p hc", "i hc_ld", "p hprev",
-                        "i h_ld", "p d_rh", "i drh_ld", "p dpre1", "i dp_ld", "p d_h", "i dh_ld", "p dup_z", "i dupz_ld", "i dup_h_off",
-                        "p dup_r", "i dupr_ld"])
-
-
-class SqairLogprobTest(C.Structure):
-    """One launch of k_logprob over T frames (include/sqair_hip.h: sqair_logprob_test); device addresses, handed on unchanged."""
-    _fields_ = _fields(["i B", "i T", "i t", "i t_global", "p t_row", "p rec_p", "p rec_d", "p rec_prev", "p pstats", "i ps_ld", "p spre",
-                        "p flat", "p qz", "p pz", "p disc_lp", "p out"])   # out: the address of a SqairOutputs, or NULL
-
-
-class SqairLogprobBwdTest(C.Structure):
-    """One launch of k_logprob_bwd over T frames (include/sqair_hip.h: sqair_logprob_bwd_test)."""
-    _fields_ = _fields(["i B", "i T", "i t_global0", "i ps_ld", "p t_row", "p rec_p", "p rec_d", "p rec_m", "p pstats", "p spre", "p g_lw",
-                        "p g_dl", "p d_rec_p", "p d_rec_d", "p d_rec_m", "p d_pstats", "p d_spre", "p flat", "p flat_grad"])
-
-
-class SqairSlotCropTest(C.Structure):
-    """One launch of a crop of the slot loop with its where sample (include/sqair_hip.h: sqair_slot_crop_test)."""
-    _fields_ = _fields(["i mode", "i slot", "i B", "i specialised", "p img", "p rec_prev", "p rec_new", "p wb", "i wb_ld", "p tp", "i tp_ld",
-                        "p t2", "i t2_ld", "p w3", "p noise", "p flat", "p mask", "i mask_row_mul", "i mask_row_add", "p out",
-                        "i out_row_mul", "i out_row_add", "p tp_out", "i tp_out_ld"])
-
-
-class SqairSlotTailTest(C.Structure):
-    """One launch of a slot's tail, alone or inside the next slot's RNN layer (include/sqair_hip.h: sqair_slot_tail_test)."""
-    _fields_ = _fields(["i is_disc", "i slot", "i B", "i what_done", "p hraw", "i h_ld", "p enc", "i enc_ld", "p rec_prev", "p rec_new",
-                        "p noise", "p s1p", "i s1p_ld", "p s1h_out", "i s1h_ld", "p flat", "p packed", "p hid", "i hid_ld", "p add",
-                        "i add_ld", "p out", "i out_ld"])
-
-
-class SqairLinearWhatTest(C.Structure):
-    """One launch of a head layer with the what sample in its epilogue (include/sqair_hip.h: sqair_linear_what_test)."""
-    _fields_ = _fields(["i mode", "i slot", "i B", "p x", "i x_ld", "p noise", "p enc", "i enc_ld", "p rec_prev", "p rec_new", "p packed"])
-
-
 # sqair_debug_dense_routes: the families of the two dense launchers, in the order include/sqair_hip.h documents
-DENSE_ROUTES = ("fwd_splitk", "fwd_t2", "fwd_rows", "fwd_mt", "fwd_lds", "fwd_big_2x2", "fwd_big_3x2", "fwd_big_3x3", "fwd_big_4x2",
-                "dx_nch1", "dx_nch2", "dx_nch3", "dx_nch4", "dx_nch5", "dx_nch6", "dx_nch7", "dx_nch8", "dx_nch9", "dx_nch12", "dx_nch18",
-                "dx_t2", "dx_gru1", "dx_gru2", "fwd_strip")
+DENSE_ROUTES = _counted("SQAIR_DENSE_ROUTES", "fwd_splitk", "fwd_t2", "fwd_rows", "fwd_mt", "fwd_lds", "fwd_big_2x2", "fwd_big_3x2",
+                        "fwd_big_3x3", "fwd_big_4x2", "dx_nch1", "dx_nch2", "dx_nch3", "dx_nch4", "dx_nch5", "dx_nch6", "dx_nch7", "dx_nch8",
+                        "dx_nch9", "dx_nch12", "dx_nch18", "dx_t2", "dx_gru1", "dx_gru2", "fwd_strip")
 
 
 def dense_routes(library=None):
@@ -366,134 +186,10 @@ def dense_routes(library=None):
     return dict(zip(DENSE_ROUTES, (int(x) for x in v)))
 
 
-_PROTOS = {
-    "sqair_abi_version": (C.c_int, []),
-    "sqair_build_id": (C.c_char_p, []),
-    "sqair_build_flags": (C.c_char_p, []),
-    "sqair_create": (C.c_int, [C.POINTER(SqairConfig), C.POINTER(C.c_void_p)]),
-    "sqair_destroy": (C.c_int, [C.c_void_p]),
-    "sqair_last_error": (C.c_char_p, [C.c_void_p]),
-    "sqair_param_count": (C.c_int64, [C.c_void_p]),
-    "sqair_param_entries": (C.c_int, [C.c_void_p]),
-    "sqair_param_entry": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64),
-                                    C.POINTER(C.c_int64)]),
-    "sqair_packed_bytes": (C.c_int64, [C.c_void_p]),
-    "sqair_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
-    "sqair_noise_width": (C.c_int, [C.c_void_p]),
-    "sqair_pack_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "sqair_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                C.c_int, C.POINTER(SqairOutputs), C.c_void_p, C.c_int64, C.c_void_p]),
-    "sqair_train_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
-    "sqair_forward_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                      C.c_int, C.POINTER(SqairOutputs), C.c_void_p, C.c_int64, C.c_void_p]),
-    "sqair_graph_capture": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                      C.c_int, C.c_int, C.POINTER(SqairOutputs), C.c_void_p, C.c_int64,
-                                      C.c_void_p]),
-    "sqair_graph_launch": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "sqair_graph_nodes": (C.c_int, [C.c_void_p]),
-    "sqair_elbo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                             C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p,
-                             C.c_void_p]),
-    "sqair_st_crop": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "sqair_st_insert_loglik": (C.c_int, [C.c_void_p] * 8 + [C.c_int, C.c_void_p]),
-    "sqair_linear_test": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                    C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
-    "sqair_gru_test": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                 C.c_void_p, C.c_int64, C.c_void_p]),
-    "sqair_set_workspace_clearing": (C.c_int, [C.c_void_p, C.c_int]),
-    "sqair_clear_workspace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "sqair_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
-    "sqair_chain_status": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "sqair_check_scales": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "sqair_check_finite": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_void_p, C.c_void_p]),
-    "sqair_timeline_available": (C.c_int, []),
-    "sqair_timeline_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
-    "sqair_timeline_count": (C.c_int, [C.c_void_p]),
-    "sqair_timeline_end": (C.c_int, [C.c_void_p]),
-    "sqair_timeline_record": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int),
-                                        C.POINTER(C.c_int)]),
-    "sqair_lstm_test": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
-    "sqair_lstm_cell_bwd_test": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_void_p]),
-    "sqair_compact_test_layout": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
-    "sqair_compact_test": (C.c_int, [C.c_void_p] * 13 + [C.POINTER(SqairOutputs), C.c_int, C.c_int, C.c_void_p]),
-    "sqair_compact_bwd_test": (C.c_int, [C.c_void_p] * 11 + [C.c_int, C.c_void_p]),
-    "sqair_get_config":(C.c_int, [C.c_void_p, C.POINTER(SqairConfig)]),
-    "sqair_st_crop_bwd": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_void_p]),
-    "sqair_st_insert_loglik_bwd": (C.c_int, [C.c_void_p] * 11 + [C.c_int64, C.c_int, C.c_void_p]),
-    "sqair_elbo_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                 C.c_void_p]),
-    "sqair_backward_scratch_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
-    "sqair_backward_decoder": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                         C.c_void_p, C.c_void_p, C.c_void_p]),
-    "sqair_backward_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
-    "sqair_backward": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                 C.c_void_p, C.c_void_p]),
-    "sqair_forward_train_carry": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.POINTER(SqairCarry), C.POINTER(SqairOutputs),
-                                                                C.c_void_p, C.c_int64, C.c_void_p]),
-    "sqair_backward_carry": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.POINTER(SqairCarry), C.c_void_p, C.c_int64,
-                                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "sqair_forward_train_carry_masked": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.POINTER(SqairCarry), C.c_void_p,
-                                                                       C.POINTER(SqairOutputs), C.c_void_p, C.c_int64, C.c_void_p]),
-    "sqair_backward_carry_masked": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.POINTER(SqairCarry), C.c_void_p, C.c_void_p,
-                                                                 C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "sqair_set_generation_noise": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "sqair_state_bytes": (C.c_int64, [C.c_void_p, C.c_int]),
-    "sqair_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),
-    "sqair_set_smc": (C.c_int, [C.c_void_p, C.POINTER(SqairSmc), C.c_int]),
-    "sqair_smc_resample_test": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(SqairSmc),
-                                         C.c_void_p]),
-    "sqair_history_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32]),
-    "sqair_set_history": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_uint32]),
-    "sqair_history_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SqairTraceOutputs), C.c_void_p]),
-    "sqair_trace_lane_scratch_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
-    "sqair_history_trace_lane": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SqairTraceOutputs), C.c_void_p,
-                                           C.POINTER(SqairTraceLane), C.c_void_p, C.c_int64, C.c_void_p]),
-    "sqair_track_lane_test": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 3 + [C.POINTER(SqairTraceLane), C.c_void_p, C.c_int64, C.c_void_p]),
-    "sqair_set_observed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
-    "sqair_set_estimate": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneEstimate), C.c_int, C.c_int]),
-    "sqair_lane_estimate_test": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int, C.POINTER(SqairLaneEstimate), C.c_void_p]),
-    "sqair_set_layers": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneLayers), C.c_int, C.c_int]),
-    "sqair_lane_layers_test": (C.c_int, [C.c_void_p] * 6 + [C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(SqairLaneLayers), C.c_void_p]),
-    "sqair_set_score": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneScore), C.c_int, C.c_int]),
-    "sqair_lane_score_test": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.POINTER(SqairLaneScore), C.c_void_p]),
-    "sqair_set_identity": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneIdentity), C.c_int, C.c_int]),
-    "sqair_lane_identity_test": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.POINTER(SqairLaneIdentity), C.c_void_p]),
-    "sqair_set_score_ids": (C.c_int, [C.c_void_p, C.c_int]),
-    "sqair_set_lane_match": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "sqair_set_idf": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneIdf), C.c_int, C.c_int]),
-    "sqair_lane_idf_test": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.POINTER(SqairLaneScore), C.POINTER(SqairLaneIdf), C.c_void_p]),
-    "sqair_lane_idf_solve": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneIdf), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "sqair_lane_traj_score": (C.c_int, [C.c_void_p, C.POINTER(SqairLaneTraj), C.POINTER(SqairTrajTruth), C.POINTER(SqairTrajScore),
-                                        C.c_int, C.c_int, C.c_void_p]),
-    "sqair_forecast_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
-    "sqair_forecast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
-                                 C.POINTER(SqairForecastOutputs), C.c_void_p, C.c_int64, C.c_void_p]),
-    "sqair_forecast_fan_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "sqair_forecast_fan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                     C.POINTER(SqairForecastOutputs), C.POINTER(SqairForecastLane), C.c_void_p, C.c_int64, C.c_void_p]),
-    "sqair_forecast_lane_scratch_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
-    "sqair_forecast_lane_test": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 4 + [C.POINTER(SqairForecastLane), C.c_void_p, C.c_int64,
-                                                                              C.c_void_p]),
-    "sqair_fill_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]),
-    "sqair_capture_begin": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "sqair_capture_end": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
-    "sqair_capture_launch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
-    "sqair_add_l2_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
-    "sqair_rmsprop_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
-                                     C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
-    "sqair_linear_bwd_test": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 4 + [C.c_void_p, C.c_int64, C.c_void_p]),
-    "sqair_linear_contract_test": (C.c_int, [C.c_void_p, C.POINTER(SqairDenseContract), C.c_void_p]),
-    "sqair_linear_dx_test": (C.c_int, [C.c_void_p, C.POINTER(SqairDxTest), C.c_void_p]),
-    "sqair_slot_tail_bwd_test": (C.c_int, [C.c_void_p, C.POINTER(SqairSlotTailBwdTest), C.c_void_p]),
-    "sqair_crop_chain_bwd_test": (C.c_int, [C.c_void_p, C.POINTER(SqairCropChainBwdTest), C.c_void_p]),
-    "sqair_where_param_grads_test": (C.c_int, [C.c_void_p, C.POINTER(SqairWhereParamGradsTest), C.c_void_p]),
-    "sqair_gru_gates_bwd_test": (C.c_int, [C.c_void_p, C.POINTER(SqairGruGatesBwdTest), C.c_void_p]),
-    "sqair_logprob_test": (C.c_int, [C.c_void_p, C.POINTER(SqairLogprobTest), C.c_void_p]),
-    "sqair_slot_crop_test": (C.c_int, [C.c_void_p, C.POINTER(SqairSlotCropTest), C.c_void_p]),
-    "sqair_slot_tail_test": (C.c_int, [C.c_void_p, C.POINTER(SqairSlotTailTest), C.c_void_p]),
-    "sqair_linear_what_test": (C.c_int, [C.c_void_p, C.POINTER(SqairLinearWhatTest), C.c_void_p]),
-    "sqair_logprob_bwd_test": (C.c_int, [C.c_void_p, C.POINTER(SqairLogprobBwdTest), C.c_void_p]),
-    "sqair_debug_dense_routes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
+# what include/sqair_hip.h declares: everything but the measurement helpers -- and the one read-out among them that it documents
+EXPORTED_SYMBOLS = list(_HEADER_PROTOS)
+# the measurement helpers the header deliberately does not declare, typed by hand
+_PROTOS = dict(_HEADER_PROTOS, **{
     "sqair_debug_linear_time": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_void_p]),
     "sqair_debug_linear_graph_time": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -509,10 +205,7 @@ _PROTOS = {
     "sqair_debug_plan": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                    C.POINTER(C.c_int)]),
     "sqair_debug_plan_t": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
-}
-
-# what include/sqair_hip.h declares: everything but the measurement helpers -- and the one read-out among them that it documents
-EXPORTED_SYMBOLS = [n for n in _PROTOS if not n.startswith("sqair_debug") or n == "sqair_debug_dense_routes"]
+})
 
 TIMELINE_LIB_PATH = os.path.join(_HERE, "libsqair_hip_timeline.so")
 # the same sources compiled with -DSQAIR_WIDE: the rest of the reference's flag range (n_what up to 128, up to 16 object slots,
@@ -529,7 +222,7 @@ def lib_path_for(n_what, n_steps_per_image, n_hidden):
               n_hidden <= PRODUCT_LIMITS["n_hidden"])
     return LIB_PATH if inside else WIDE_LIB_PATH
 
-ABI_VERSION = 2
+ABI_VERSION = _K["SQAIR_ABI_VERSION"]
 _VARIANT_OF = {"libsqair_hip.so": "product", "libsqair_hip_timeline.so": "timeline", "libsqair_hip_knobs.so": "knobs",
                "libsqair_hip_wide.so": "wide"}
 
@@ -579,8 +272,8 @@ def lib(path=None, allow_stale=False):
         got = l.sqair_build_id().decode()
         try:
             want = source_id()
-        except (OSError, ImportError):   # a binary-only deployment (no csrc/ -- ModuleNotFoundError --, its .hip files stripped, or no
-            # include/ beside the package): nothing to compare with
+        except (OSError, ImportError):   # a binary-only deployment (no csrc/ -- ModuleNotFoundError -- or its .hip files stripped; the
+            # header is there, or this module would not have imported): nothing to compare with
             want = None
             if not allow_stale:
                 import warnings

@@ -127,6 +127,12 @@ def field_views(shapes, int_fields, device):
                                    else flat[offs[n]:offs[n] + sizes[n]]).view(shapes[n]) for n in shapes}
 
 
+def zeros_of(owner, shapes, device):
+    """{name: zeros of its shape} for pointer fields of the struct ``owner`` of include/sqair_hip.h (or pointer parameters of the
+    function ``owner``), each in the element type the header declares it with."""
+    return {n: torch.zeros(shp, dtype=getattr(torch, _capi.field_dtype(owner, n)), device=device) for n, shp in shapes.items()}
+
+
 # ---- the resident stack: estimate, layers, identity, score -----------------------------------------------------------------------
 class LaneAnswers(object):
     """The lane answers a stream's steps fill.  The constructor only checks its keyword group (no core, no device: it runs before the
@@ -223,10 +229,9 @@ class LaneAnswers(object):
             ints = ints + _capi.SCORE_INT_FIELDS
         if self.identified:
             shapes.update(_capi.identity_shapes(T, B, N))
-            ints = ints + tuple(_capi.IDENT_LANE_NAMES[n] for n in _capi.IDENT_FIELDS)
+            ints = ints + tuple(_capi.IDENT_LANE_NAMES[n] for n in _capi.IDENT_INT_FIELDS)
         self.flat, self.views = field_views(shapes, ints, core.device)
         est = self.est = self.views(self.flat)
-        z = lambda shp, dt: torch.zeros(shp, dtype=dt, device=core.device)
         sync = torch.cuda.current_stream(core.device).synchronize   # (a buffer's initial values are in place before a pass reads it)
         c_est = _capi.SqairLaneEstimate(iou_min=self.estimate_iou, log_w=log_w.data_ptr(),
                                         **{n: t.data_ptr() for n, t in est.items() if n in _capi.ESTIMATE_FIELDS})
@@ -236,9 +241,9 @@ class LaneAnswers(object):
             lay = _capi.SqairLaneLayers(cover_min=self.cover_min, **{n: est[n].data_ptr() for n in _capi.LAYERS_FIELDS})
             core.check(lib.sqair_set_layers(h, C.byref(lay), T, B), "sqair_set_layers")
         if self.scored:   # the truth of a step, the accumulators and the identity memory
-            self.score_buf = dict(truth_box=z((T, B, G, 4), torch.float32), truth_present=z((T, B, G), torch.int32),
-                                  truth_valid=z((T, B), torch.int32), counts=z((B, len(_capi.SCORE_COUNTS)), torch.int64),
-                                  iou_sum=z((B,), torch.float64), last_id=z((B, G), torch.int32) - 1)
+            self.score_buf = zeros_of("SqairLaneScore", dict(truth_box=(T, B, G, 4), truth_present=(T, B, G), truth_valid=(T, B),
+                                                             counts=(B, len(_capi.SCORE_COUNTS)), iou_sum=(B,), last_id=(B, G)), core.device)
+            self.score_buf["last_id"].fill_(-1)
             self._valid_is_zero = True
             sc = _capi.SqairLaneScore(iou_min=self.score_iou, G=G, **{n: t.data_ptr() for n, t in self.score_buf.items()},
                                       **{n: est[n].data_ptr() for n in _capi.SCORE_FIELDS})
@@ -248,8 +253,7 @@ class LaneAnswers(object):
             shapes = _capi.identity_memory_shapes(B, self.M, core.nw)
             if not self.appearance:
                 del shapes["trk_what"]
-            dtype = lambda n: torch.float32 if n in ("trk_box", "trk_what") else torch.int64 if n == "counts" else torch.int32
-            self.ident_buf = {n: z(shp, dtype(n)) for n, shp in shapes.items()}
+            self.ident_buf = zeros_of("SqairLaneIdentity", shapes, core.device)
             self.ident_buf["trk_id"].fill_(-1)
             idt = _capi.SqairLaneIdentity(iou_min=self.identity_iou, reid_dist=self.reid_dist, reid_what=self.reid_what, M=self.M,
                                           max_age=int(self.max_age), **{n: t.data_ptr() for n, t in self.ident_buf.items()},
@@ -259,10 +263,10 @@ class LaneAnswers(object):
             if self.score_ids == "lane":
                 core.check(lib.sqair_set_score_ids(h, 1), "sqair_set_score_ids")
         if self.idf:   # the overlap table of every lane's open clip, the totals over the closed ones, and what a solve writes
-            self.idf_buf = {n: z(shp, torch.int64 if n == "totals" else torch.int32) for n, shp in _capi.idf_shapes(B, G, self.P).items()}
+            self.idf_buf = zeros_of("SqairLaneIdf", _capi.idf_shapes(B, G, self.P), core.device)
             self.idf_buf["col_id"].fill_(-1)
             self._idf_c = _capi.SqairLaneIdf(P=self.P, **{n: t.data_ptr() for n, t in self.idf_buf.items()})
-            self._idf_out = dict(open=z((B, len(_capi.IDF_TOTALS)), torch.int64), assign=z((B, G), torch.int32), close=z((B,), torch.int32))
+            self._idf_out = zeros_of("sqair_lane_idf_solve", dict(open=(B, len(_capi.IDF_TOTALS)), assign=(B, G), close=(B,)), core.device)
             sync()
             core.check(lib.sqair_set_idf(h, C.byref(self._idf_c), T, B), "sqair_set_idf")
 
@@ -446,10 +450,8 @@ class TrajScores(object):
         G, key = truth["G"], (F, truth["G"], truth["iou_min"], match)
         ts = self.acc.get(kind)
         if ts is None or ts["key"] != key:   # (another F, G, threshold or matching: the old sums would not mean the same)
-            z = lambda shp, dt: torch.zeros(shp, dtype=dt, device=core.device)
-            ts = self.acc[kind] = dict(key=key, counts=z((F, B, len(_capi.TRAJ_COUNTS)), torch.int64),
-                                       sums=z((F, B, len(_capi.TRAJ_SUMS)), torch.float64),
-                                       lane_counts=z((B, len(_capi.TRAJ_LANE_COUNTS)), torch.int64))
+            ts = self.acc[kind] = dict(zeros_of("SqairTrajScore", dict(counts=(F, B, len(_capi.TRAJ_COUNTS)), sums=(F, B, len(_capi.TRAJ_SUMS)),
+                                                                       lane_counts=(B, len(_capi.TRAJ_LANE_COUNTS))), core.device), key=key)
             ts["flat"], ts["views"] = field_views(_capi.traj_shapes(F, B, G), _capi.TRAJ_INT_FIELDS, core.device)
             ts["out"] = ts["views"](ts["flat"])
         dev = {n: truth[n].to(core.device, non_blocking=True).contiguous() for n in _capi.TRAJ_TRUTH_FIELDS if n != "keep_id"}

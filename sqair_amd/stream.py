@@ -62,7 +62,7 @@ import torch
 
 from sqair_amd import _capi
 from sqair_amd.carried import CarriedState, blank_unobserved, carried, check_observed
-from sqair_amd.lane import LaneAnswers, TrajScores, check_unit, field_views, is_int_in, lane_answer
+from sqair_amd.lane import LaneAnswers, TrajScores, check_unit, field_views, is_int_in, lane_answer, zeros_of
 
 DEFAULT_OUTPUTS = ("what", "where", "presence", "obj_id", "log_weights_per_timestep")
 FORECAST_OUTPUTS = ("what", "where", "presence", "presence_prob", "presence_logit", "obj_id", "canvas", "glimpse")
@@ -389,7 +389,7 @@ class SqairStream(object):
         if nb < 0:
             raise RuntimeError("sqair_forecast_workspace_bytes failed")
         fc = dict(ws=z(nb // 4), noise=z((F, R, 2, N, core.nzw)), src=z(self.R, torch.int32), log_w=z(self.R),
-                  out={n: z(shapes[n]) for n in outputs})
+                  out=zeros_of("SqairForecastOutputs", {n: shapes[n] for n in outputs}, core.device))
         if lane:   # the fields of SqairForecastLane as views of ONE allocation
             fc["lane_flat"], fc["lane_views"] = field_views(_capi.forecast_lane_shapes(F, B, self.K, N), _capi.FORECAST_LANE_INT_FIELDS,
                                                              core.device)
@@ -481,18 +481,16 @@ class SqairStream(object):
     def _track_buffers(self, lag, M, table, lane=False):
         core = self.core
         R, N, B, F = self.R, core.N, self.B, lag * self.T
-        i32 = torch.int32
-        shapes = dict(where=((F, R, N, 4), None), presence=((F, R, N), None), obj_id=((F, R, N), None), valid=((F, R), i32),
-                      frame_index=((F, R), i32), ancestor_row=((lag, R), i32), unique_ancestors=((lag, B), i32))
+        shapes = dict(where=(F, R, N, 4), presence=(F, R, N), obj_id=(F, R, N), valid=(F, R), frame_index=(F, R), ancestor_row=(lag, R),
+                      unique_ancestors=(lag, B))
         if "what" in self.history_fields:
-            shapes["what"] = ((F, R, N, core.nw), None)
+            shapes["what"] = (F, R, N, core.nw)
         if "log_weights_per_timestep" in self.history_fields:
-            shapes["log_w"] = ((F, R), None)
+            shapes["log_w"] = (F, R)
         if table:
-            shapes.update(track_id=((R, M), i32), n_tracks=((R,), i32), track_present=((F, R, M), None),
-                          track_where=((F, R, M, 4), None))
-        z = lambda shp, dt=None: torch.zeros(shp, dtype=dt or torch.float32, device=core.device)
-        tr = dict(src=z(R, i32), log_w=z(R), out={n: z(*sd) for n, sd in shapes.items()})
+            shapes.update(track_id=(R, M), n_tracks=(R,), track_present=(F, R, M), track_where=(F, R, M, 4))
+        z = lambda shp, dt=torch.float32: torch.zeros(shp, dtype=dt, device=core.device)
+        tr = dict(src=z(R, torch.int32), log_w=z(R), out=zeros_of("SqairTraceOutputs", shapes, core.device))
         if lane:   # the fields of SqairTraceLane as views of ONE allocation, and the scratch between the two lane launches
             tr["lane_flat"], tr["lane_views"] = field_views(_capi.track_lane_shapes(F, B, self.K, N), _capi.TRACK_LANE_INT_FIELDS,
                                                              core.device)

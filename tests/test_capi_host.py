@@ -1,5 +1,6 @@
 """Host-side checks that need no GPU: the C-ABI library loads, exports every symbol include/sqair_hip.h
-declares, and its parameter table agrees with the Python inventory."""
+declares, its parameter table agrees with the Python inventory, and the binding made from the header (sqair_amd/_abi.py) is what a C
+compiler reads in it."""
 import ctypes as C
 import os
 import re
@@ -7,7 +8,7 @@ import re
 import numpy as np
 import pytest
 
-from sqair_amd import _capi
+from sqair_amd import _abi, _capi
 from sqair_amd.flags import make_flags
 from sqair_amd.model import make_config
 from sqair_amd.params import param_offsets, param_spec
@@ -469,36 +470,195 @@ def test_slot_forward_test_entries_refuse_host_side():
             lib.sqair_destroy(gru)
 
 
-def test_dense_test_structs_have_the_header_layout(repo_root, tmp_path):
-    """The descriptions of sqair_linear_contract_test / sqair_linear_dx_test are passed by address: the ctypes mirrors must have
-    the size and the field offsets a C compiler gives the header's structs."""
+# ---- the binding is read from the header (sqair_amd/_abi.py): gcc judges what the parser read --------------------------------------
+def _gcc(tmp_path, name, lines, repo_root, run=True):
+    """Compiles (and runs) a generated C file against the header; returns what it printed, or the compiler's exit status."""
     import shutil
     import subprocess
-    structs = {"SqairDenseSeg": _capi.SqairDenseSeg, "SqairDenseContract": _capi.SqairDenseContract, "SqairDxRange": _capi.SqairDxRange,
-               "SqairDxGru": _capi.SqairDxGru, "SqairDxTest": _capi.SqairDxTest,
-               # the slot loop's element-wise adjoints (sqair_slot_tail_bwd_test and its three neighbours)
-               "SqairSlotTailBwdTest": _capi.SqairSlotTailBwdTest, "SqairCropChainBwdTest": _capi.SqairCropChainBwdTest,
-               "SqairWhereParamGradsTest": _capi.SqairWhereParamGradsTest, "SqairGruGatesBwdTest": _capi.SqairGruGatesBwdTest,
-               # the log-probability kernels (sqair_logprob_test, sqair_logprob_bwd_test)
-               "SqairLogprobTest": _capi.SqairLogprobTest, "SqairLogprobBwdTest": _capi.SqairLogprobBwdTest,
-               # the slot loop's forward kernels (sqair_slot_crop_test, sqair_slot_tail_test, sqair_linear_what_test)
-               "SqairSlotCropTest": _capi.SqairSlotCropTest, "SqairSlotTailTest": _capi.SqairSlotTailTest,
-               "SqairLinearWhatTest": _capi.SqairLinearWhatTest}
-    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "sqair_hip.h"', "int main(void) {"]
-    for name, cls in structs.items():
-        lines.append('  printf("{0} %zu\\n", sizeof({0}));'.format(name))
-        for field, _ in cls._fields_:
-            lines.append('  printf("{0}.{1} %zu\\n", offsetof({0}, {1}));'.format(name, field))
-    lines += ["  return 0;", "}"]
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
+    src = tmp_path / (name + ".c")
+    src.write_text("\n".join(lines) + "\n")
     gcc = shutil.which("gcc")
     assert gcc, "gcc is part of the image"
-    subprocess.check_call([gcc, "-std=c99", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(repo_root, "include"),
-                           str(src), "-o", str(tmp_path / "layout")])
-    got = dict(l.split() for l in subprocess.run([str(tmp_path / "layout")], capture_output=True, text=True, check=True).stdout.splitlines())
-    for name, cls in structs.items():
-        assert int(got[name]) == C.sizeof(cls), name
-        for field, _ in cls._fields_:
-            assert int(got[name + "." + field]) == getattr(cls, field).offset, (name, field)
-    assert len(_capi.DENSE_ROUTES) == int(re.search(r"#define SQAIR_DENSE_ROUTES (\d+)", open(os.path.join(repo_root, "include", "sqair_hip.h")).read()).group(1))
+    cmd = [gcc, "-std=gnu11", "-I" + os.path.join(repo_root, "include"), str(src)]
+    if not run:
+        return subprocess.run(cmd + ["-fsyntax-only"], capture_output=True, text=True).returncode
+    subprocess.check_call(cmd + ["-o", str(tmp_path / name)])
+    return subprocess.run([str(tmp_path / name)], capture_output=True, text=True, check=True).stdout
+
+
+def test_every_struct_has_the_header_layout(repo_root, tmp_path):
+    """Every struct of the header is passed by address: the ctypes classes made from the parse must have the size, the field offsets
+    and the field sizes a C compiler gives the header's structs.  The struct list is the header's, not a list kept here."""
+    structs = _abi.header().structs
+    assert len(structs) >= 30 and {"SqairConfig", "SqairOutputs", "SqairSmc", "SqairCarry", "SqairDenseContract", "SqairDxTest",
+                                   "SqairLogprobBwdTest", "SqairLinearWhatTest"} <= set(structs)
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(repo_root, "include", "sqair_hip.h")).read(), flags=re.S)
+    assert list(structs) == re.findall(r"^\}\s*(\w+)\s*;", txt, flags=re.M)   # (every struct closes at the start of a line)
+    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "sqair_hip.h"', "int main(void) {"]
+    for name, fields in structs.items():
+        lines.append('  printf("{0} %zu\\n", sizeof({0}));'.format(name))
+        for f in fields:
+            lines.append('  printf("{0}.{1} %zu %zu\\n", offsetof({0}, {1}), sizeof((({0}*)0)->{1}));'.format(name, f.name))
+    got = {l.split()[0]: [int(v) for v in l.split()[1:]] for l in _gcc(tmp_path, "layout", lines + ["  return 0;", "}"], repo_root).splitlines()}
+    for name, fields in structs.items():
+        cls = getattr(_capi, name)
+        assert issubclass(cls, C.Structure) and [n for n, _ in cls._fields_] == [f.name for f in fields], name
+        assert got[name] == [C.sizeof(cls)], name
+        for f in fields:
+            assert got[name + "." + f.name] == [getattr(cls, f.name).offset, getattr(cls, f.name).size], (name, f.name)
+    # the forms a field takes
+    assert _capi.SqairCarry.smc.offset == 40 and dict(_capi.SqairCarry._fields_)["smc"] is C.POINTER(_capi.SqairSmc)
+    assert dict(_capi.SqairLogprobTest._fields_)["out"] is C.c_void_p          # an address set as an integer
+    assert dict(_capi.SqairConfig._fields_)["where_prior_mean"] is C.c_float * 4
+    assert dict(_capi.SqairDxTest._fields_)["gru"] is _capi.SqairDxGru and dict(_capi.SqairDxTest._fields_)["r"] is _capi.SqairDxRange * 3
+    assert len(_capi.DENSE_ROUTES) == int(re.search(r"#define SQAIR_DENSE_ROUTES (\d+)", txt).group(1))
+
+
+def test_every_prototype_reads_as_the_compiler_reads_it(repo_root, tmp_path):
+    """One _Static_assert per function of the header: the type of the function is the return type and the parameters printed back
+    from the parse, const-ness, base type and pointer depth.  Nothing is linked or run.  The mapping to ctypes is then a table: one
+    function of each kind."""
+    functions = _abi.header().functions
+    assert sorted(functions) == _header_functions(repo_root) and len(functions) >= 103
+
+    def claim(name, ret, params):
+        return '_Static_assert(__builtin_types_compatible_p(__typeof__(&{0}), {1} (*)({2})), "{0}");'.format(
+            name, _abi.spell(ret), ", ".join(_abi.spell(p) for p in params) or "void")
+    head = ['#include "sqair_hip.h"']
+    assert _gcc(tmp_path, "protos", head + [claim(n, *f) for n, f in functions.items()], repo_root, run=False) == 0
+    # (the claim can fail: one const dropped, one depth off)
+    ret, params = functions["sqair_elbo"]
+    assert _abi.spell(params[10]) == "const float* const*"
+    for wrong in (params[10]._replace(pointer_const=()), params[10]._replace(pointer_depth=1, pointer_const=())):
+        assert _gcc(tmp_path, "wrong", head + [claim("sqair_elbo", ret, params[:10] + [wrong] + params[11:])], repo_root, run=False) != 0
+    P, V, I = C.POINTER, C.c_void_p, C.c_int
+    for name, want in (("sqair_create", (I, [P(_capi.SqairConfig), V])), ("sqair_last_error", (C.c_char_p, [V])),
+                       ("sqair_set_option", (I, [V, C.c_char_p, I])), ("sqair_history_bytes", (C.c_int64, [V, I, I, I, C.c_uint32])),
+                       ("sqair_forward_train_carry", (I, [V] * 5 + [I, I, P(_capi.SqairCarry), P(_capi.SqairOutputs), V, C.c_int64, V])),
+                       ("sqair_fill_noise", (I, [V, V, I, I, I, I, C.c_uint64, C.c_uint64, V]))):
+        assert _capi._PROTOS[name] == want, name
+        fn = getattr(_capi.lib(), name)
+        assert fn.restype is want[0] and list(fn.argtypes) == want[1], name
+
+
+_EVERY_CONSTRUCT = """/* a comment
+ * over lines, with a ; and a { in it */
+#ifndef SQAIR_T_H
+#define SQAIR_T_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define SQAIR_N 3u
+#define SQAIR_M 12   /* trailing */
+typedef struct SqairHandle SqairHandle;
+typedef struct SqairIn {
+  int32_t a, b;      /* two declarators */
+  float m[4];
+  const float* p; float*  q;
+} SqairIn;
+typedef struct {
+  SqairIn in; SqairIn two[2];
+  const SqairIn* ref;
+  int64_t* n; double* d; uint64_t seed; uint32_t bits; char tag; void* any;
+} SqairOut;
+int sqair_version(void);
+const char* sqair_name(const SqairHandle* h);
+int64_t sqair_run(SqairHandle** out, const SqairOut* o /* NULL: off */,
+                  const float* const* rows, const char* name, int n, float x, void* stream);
+#ifdef __cplusplus
+}
+#endif
+#endif /* SQAIR_T_H */
+"""
+
+
+def test_the_parser_reads_the_subset_and_refuses_the_rest(tmp_path):
+    F, P = _abi.Field, _abi.Param
+
+    def parse(text):
+        (tmp_path / "t.h").write_text(text)
+        return _abi.parse_header(str(tmp_path / "t.h"))
+    got = parse(_EVERY_CONSTRUCT)
+    assert got.constants == {"SQAIR_N": 3, "SQAIR_M": 12}
+    assert list(got.structs.items()) == [
+        ("SqairIn", [F("a", "int32_t", False, 0, None), F("b", "int32_t", False, 0, None), F("m", "float", False, 0, 4),
+                     F("p", "float", True, 1, None), F("q", "float", False, 1, None)]),
+        ("SqairOut", [F("in", "SqairIn", False, 0, None), F("two", "SqairIn", False, 0, 2), F("ref", "SqairIn", True, 1, None),
+                      F("n", "int64_t", False, 1, None), F("d", "double", False, 1, None), F("seed", "uint64_t", False, 0, None),
+                      F("bits", "uint32_t", False, 0, None), F("tag", "char", False, 0, None), F("any", "void", False, 1, None)])]
+    assert list(got.functions.items()) == [
+        ("sqair_version", (P("", "int", False, 0), [])),
+        ("sqair_name", (P("", "char", True, 1), [P("h", "SqairHandle", True, 1)])),
+        ("sqair_run", (P("", "int64_t", False, 0), [P("out", "SqairHandle", False, 2), P("o", "SqairOut", True, 1),
+                                                    P("rows", "float", True, 2, (0,)), P("name", "char", True, 1), P("n", "int", False, 0),
+                                                    P("x", "float", False, 0), P("stream", "void", False, 1)]))]
+    classes, protos = _abi.bind(got)
+    assert [t for _, t in classes["SqairOut"]._fields_] == [classes["SqairIn"], classes["SqairIn"] * 2, C.POINTER(classes["SqairIn"]),
+                                                           C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_char, C.c_void_p]
+    assert protos["sqair_run"] == (C.c_int64, [C.c_void_p, C.POINTER(classes["SqairOut"]), C.c_void_p, C.c_char_p, C.c_int, C.c_float,
+                                               C.c_void_p])
+    assert protos["sqair_name"] == (C.c_char_p, [C.c_void_p]) and protos["sqair_version"] == (C.c_int, [])
+    # what the subset leaves out fails, and the message names the text
+    for text, named in (("typedef struct S { int32_t a : 3; } S;", "int32_t a : 3"),
+                        ("typedef union U { int32_t a; float b; } U;", "typedef union U { int32_t a"),
+                        ("typedef enum { SQAIR_A, SQAIR_B } E;", "typedef enum { SQAIR_A, SQAIR_B } E"),
+                        ("typedef struct S { void (*fn)(int); } S;", "void (*fn)(int)"),
+                        ("typedef struct S { size_t n; } S;", "size_t n"),
+                        ("int sqair_f(unsigned n);", "unsigned n"),
+                        ("int sqair_f(SqairLater* p);", "SqairLater* p"),
+                        ("void sqair_f(int n);", "void sqair_f(int n);"),
+                        ("typedef struct S { int32_t* a, b; } S;", "int32_t* a, b"),
+                        ("typedef struct S { float*** p; } S;", "float*** p"),
+                        ("#define SQAIR_X (1 << 3)", "#define SQAIR_X (1 << 3)"),
+                        ("#define SQAIR_X 0x10", "0x10"),
+                        ("typedef struct S { int32_t a;", "typedef struct S { int32_t a"),
+                        ("int sqair_f(int n); /* no end", "/* no end"),
+                        ("int sqair_f(int n);\n}", "}")):
+        with pytest.raises(_abi.HeaderError) as e:
+            parse(text)
+        assert named in str(e.value), (text, str(e.value))
+
+
+def test_importing_the_binding_without_the_header_says_why(tmp_path, monkeypatch):
+    monkeypatch.setattr(_abi, "HEADER_PATH", str(tmp_path / "include" / "sqair_hip.h"))
+    _abi.header.cache_clear()
+    try:
+        with pytest.raises(ImportError, match="read from the C header, and the header ships with the library"):
+            _abi.header()
+    finally:
+        monkeypatch.undo()
+        _abi.header.cache_clear()
+    assert _abi.header() is _abi.header() and "SqairConfig" in _abi.header().structs   # parsed once per process
+
+
+# the *_INT_FIELDS tuples as they were written by hand before the binding was read from the header: the recorded result to reproduce
+_INT_FIELDS_BEFORE = dict(FORECAST_LANE_INT_FIELDS=("best_row",), ESTIMATE_INT_FIELDS=("best_row", "map_count"),
+                          LAYERS_INT_FIELDS=("match", "owner"), SCORE_INT_FIELDS=("truth_match", "tp", "fn", "fp", "idsw"),
+                          TRAJ_INT_FIELDS=("link", "state", "count_map"), TRACK_LANE_INT_FIELDS=("best_row", "first_frame"))
+
+
+def test_buffer_element_types_are_the_headers(repo_root):
+    """What the allocation code asks the binding -- the element type of a struct's pointer field -- against the header text read by
+    this test's own regex."""
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(repo_root, "include", "sqair_hip.h")).read(), flags=re.S)
+    names = {"float": "float32", "int32_t": "int32", "int64_t": "int64", "double": "float64"}
+    for struct, fields in (("SqairLaneScore", ("truth_box", "truth_present", "truth_valid", "counts", "iou_sum", "last_id", "match_iou", "tp")),
+                           ("SqairLaneIdentity", ("trk_id", "trk_box", "trk_what", "next_id", "counts", "lane_id")),
+                           ("SqairLaneIdf", ("col_id", "overlap", "frames", "totals")),
+                           ("SqairTrajScore", ("counts", "sums", "lane_counts", "link", "link_iou")),
+                           ("SqairTraceOutputs", ("where", "log_w", "valid", "ancestor_row", "track_id", "track_where"))):
+        body = re.search(r"typedef struct {0} \{{(.*?)\}} {0};".format(struct), txt, flags=re.S).group(1)
+        for f in fields:
+            assert _capi.field_dtype(struct, f) == names[re.search(r"(\w+)\s*\*\s*{}\s*;".format(f), body).group(1)], (struct, f)
+    assert re.search(r"double\* iou_sum", txt) and _capi.field_dtype("SqairLaneScore", "iou_sum") == "float64"
+    assert re.search(r"int64_t\* counts", txt) and _capi.field_dtype("SqairLaneScore", "counts") == "int64"
+    assert re.search(r"int32_t\* truth_present", txt) and _capi.field_dtype("SqairLaneScore", "truth_present") == "int32"
+    assert re.search(r"float\*\s+trk_box", txt) and _capi.field_dtype("SqairLaneIdentity", "trk_box") == "float32"
+    assert re.search(r"int64_t\* open\b", txt) and _capi.field_dtype("sqair_lane_idf_solve", "open") == "int64"   # a parameter
+    for scalar in (("SqairLaneScore", "G"), ("SqairCarry", "smc"), ("SqairCarry", "state_in")):   # no array of a device type
+        with pytest.raises(KeyError):
+            _capi.field_dtype(*scalar)
+    for name, before in _INT_FIELDS_BEFORE.items():
+        assert getattr(_capi, name) == before, name
+    assert _capi.IDENT_INT_FIELDS == _capi.IDENT_FIELDS == ("lane_id", "how", "track_len")
