@@ -2,7 +2,6 @@
 declares, its parameter table agrees with the Python inventory, and the binding made from the header (sqair_amd/_abi.py) is what a C
 compiler reads in it."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
@@ -12,17 +11,12 @@ from sqair_amd import _abi, _capi
 from sqair_amd.flags import make_flags
 from sqair_amd.model import make_config
 from sqair_amd.params import param_offsets, param_spec
+from tests.abi_host import code, constant, fields as header_fields, functions, gcc as _gcc, handle, prototype
 
 
-def _header_functions(repo_root):
-    txt = open(os.path.join(repo_root, "include", "sqair_hip.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(sqair_[a-z_0-9]+)\s*\(", txt)))
-
-
-def test_library_loads_and_exports_header_symbols(repo_root):
+def test_library_loads_and_exports_header_symbols():
     lib = _capi.lib()
-    names = _header_functions(repo_root)
+    names = functions()
     assert len(names) >= 18
     for n in names:
         assert hasattr(lib, n), "missing export " + n
@@ -61,14 +55,10 @@ def test_build_id_is_compiled_in_and_a_stale_binary_is_refused(tmp_path):
                                        (3, (50, 50), "GRU/GRU/GRU"), (3, (50, 50), "VanillaRNN/VanillaRNN/LSTM"),
                                        (4, (50, 50), "VanillaRNN/LSTM/VanillaRNN")])
 def test_param_table_matches_python_spec(N, hw, cell):
-    lib = _capi.lib()
     cs = cell.split("/") + ["GRU", "VanillaRNN"][len(cell.split("/")) - 1:]
-    F = make_flags(n_steps_per_image=N, time_transition=cs[0], prior_transition=cs[1], transition=cs[2])
-    cfg = make_config(F, hw)
-    h = C.c_void_p()
-    assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-    try:
-        spec = param_spec(F, hw)
+    flags = dict(n_steps_per_image=N, time_transition=cs[0], prior_transition=cs[1], transition=cs[2])
+    with handle(hw=hw, **flags) as (lib, h):
+        spec = param_spec(make_flags(**flags), hw)
         off, total = param_offsets(spec)
         assert lib.sqair_param_count(h) == total
         assert lib.sqair_param_entries(h) == len(spec)
@@ -83,8 +73,6 @@ def test_param_table_matches_python_spec(N, hw, cell):
         assert lib.sqair_packed_bytes(h) > total * 4
         assert lib.sqair_workspace_bytes(h, 10, 32) > 0
         assert lib.sqair_noise_width(h) == 55
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_create_rejects_bad_config():
@@ -126,10 +114,8 @@ def test_wide_library_accepts_the_rest_of_the_flag_range(flags):
     assert path == _capi.WIDE_LIB_PATH
     h = C.c_void_p()
     assert _capi.lib().sqair_create(C.byref(cfg), C.byref(h)) != 0
-    lib = _capi.lib(path)
-    assert lib.sqair_build_flags() == b"wide" and lib.sqair_abi_version() == _capi.ABI_VERSION
-    assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-    try:
+    with handle(path, **flags) as (lib, h):
+        assert lib.sqair_build_flags() == b"wide" and lib.sqair_abi_version() == _capi.ABI_VERSION
         spec = param_spec(F, (50, 50))
         off, total = param_offsets(spec)
         assert lib.sqair_param_count(h) == total and lib.sqair_param_entries(h) == len(spec)
@@ -139,8 +125,6 @@ def test_wide_library_accepts_the_rest_of_the_flag_range(flags):
             assert (cname.value.decode(), coff.value, cnum.value) == (name, off[name][0], int(np.prod(shape)) if len(shape) else 1)
         assert lib.sqair_noise_width(h) == 4 + int(F.n_what) + 1
         assert lib.sqair_workspace_bytes(h, 3, 2) > 0 and lib.sqair_backward_bytes(h, 3, 2) > 0
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_limits_of_both_builds():
@@ -178,45 +162,24 @@ def test_run_time_options_host_side():
     """sqair_set_option without a GPU: the in-launch slot chain lays the inference workspace out like the training tape for the
     configurations it serves (shipped cells, n_hidden 256, up to 320 particle rows) and leaves the others alone; the wide build
     refuses it; vi_target takes 0 / 1."""
-    lib = _capi.lib()
-
-    def handle(library, **flags):
-        F = make_flags(k_particles=5, n_steps_per_image=4, **flags)
-        cfg = make_config(F, (50, 50))
-        h = C.c_void_p()
-        assert library.sqair_create(C.byref(cfg), C.byref(h)) == 0
-        return h
-    h = handle(lib)
-    base = lib.sqair_workspace_bytes(h, 10, 32)
-    train = lib.sqair_train_workspace_bytes(h, 10, 32)
-    assert lib.sqair_set_option(h, b"slot_chain", 1) == 0
-    on = lib.sqair_workspace_bytes(h, 10, 32)
-    assert on > 5 * base and on >= train          # per-slot buffers kept apart + the launches' control blocks
-    assert lib.sqair_workspace_bytes(h, 10, 256) == _fresh_bytes(lib, 10, 256)   # 1280 rows: the chain keeps out
-    assert lib.sqair_set_option(h, b"slot_chain", 0) == 0
-    assert lib.sqair_workspace_bytes(h, 10, 32) == base
-    assert lib.sqair_set_option(h, b"vi_target", 1) == 0 and lib.sqair_set_option(h, b"vi_target", 0) == 0
-    assert lib.sqair_set_option(h, b"vi_target", 7) == -2 and b"vi_target" in lib.sqair_last_error(h)
-    lib.sqair_destroy(h)
-    h = handle(lib, time_transition="LSTM")
-    base = lib.sqair_workspace_bytes(h, 10, 32)
-    assert lib.sqair_set_option(h, b"slot_chain", 1) == 0
-    assert lib.sqair_workspace_bytes(h, 10, 32) == base      # LSTM temporal cell: one launch per op
-    lib.sqair_destroy(h)
-    wide = _capi.lib(_capi.WIDE_LIB_PATH)
-    h = handle(wide)
-    assert wide.sqair_set_option(h, b"slot_chain", 1) == -2 and b"wide build" in wide.sqair_last_error(h)
-    wide.sqair_destroy(h)
-
-
-def _fresh_bytes(lib, T, B):
-    F = make_flags(k_particles=5, n_steps_per_image=4)
-    cfg = make_config(F, (50, 50))
-    h = C.c_void_p()
-    assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-    n = lib.sqair_workspace_bytes(h, T, B)
-    lib.sqair_destroy(h)
-    return n
+    K5 = dict(k_particles=5, n_steps_per_image=4)
+    with handle(**K5) as (lib, h), handle(**K5) as (_, fresh):
+        base = lib.sqair_workspace_bytes(h, 10, 32)
+        train = lib.sqair_train_workspace_bytes(h, 10, 32)
+        assert lib.sqair_set_option(h, b"slot_chain", 1) == 0
+        on = lib.sqair_workspace_bytes(h, 10, 32)
+        assert on > 5 * base and on >= train          # per-slot buffers kept apart + the launches' control blocks
+        assert lib.sqair_workspace_bytes(h, 10, 256) == lib.sqair_workspace_bytes(fresh, 10, 256)   # 1280 rows: the chain keeps out
+        assert lib.sqair_set_option(h, b"slot_chain", 0) == 0
+        assert lib.sqair_workspace_bytes(h, 10, 32) == base
+        assert lib.sqair_set_option(h, b"vi_target", 1) == 0 and lib.sqair_set_option(h, b"vi_target", 0) == 0
+        assert lib.sqair_set_option(h, b"vi_target", 7) == -2 and b"vi_target" in lib.sqair_last_error(h)
+    with handle(time_transition="LSTM", **K5) as (lib, h):
+        base = lib.sqair_workspace_bytes(h, 10, 32)
+        assert lib.sqair_set_option(h, b"slot_chain", 1) == 0
+        assert lib.sqair_workspace_bytes(h, 10, 32) == base      # LSTM temporal cell: one launch per op
+    with handle(_capi.WIDE_LIB_PATH, **K5) as (wide, h):
+        assert wide.sqair_set_option(h, b"slot_chain", 1) == -2 and b"wide build" in wide.sqair_last_error(h)
 
 
 def test_compaction_test_entries_host_side():
@@ -230,11 +193,7 @@ def test_compaction_test_entries_host_side():
         assert lib.sqair_abi_version() == _capi.ABI_VERSION == 2
         for flags, snh, psnh, spec in ((dict(), 256, 256, path == _capi.LIB_PATH), (dict(time_transition="LSTM"), 512, 256, False),
                                        (dict(n_units=5, prior_transition="LSTM"), 256, 512, False), (dict(n_units=2), 128, 128, False)):
-            F = make_flags(k_particles=5, n_steps_per_image=4, **flags)
-            cfg = make_config(F, (50, 50))
-            h = C.c_void_p()
-            assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-            try:
+            with handle(path, k_particles=5, n_steps_per_image=4, **flags) as (_, h):
                 buf = (C.c_int32 * 24)(*([-5] * 24))
                 assert lib.sqair_compact_test_layout(h, buf, 24) == 20
                 v = list(buf)
@@ -246,31 +205,23 @@ def test_compaction_test_entries_host_side():
                 assert lib.sqair_compact_test_layout(h, None, 3) == -1 and lib.sqair_compact_test_layout(None, short, 3) == -1
                 assert lib.sqair_compact_test(h, *([None] * 13), 0, 1, None) == -1
                 assert lib.sqair_compact_bwd_test(h, *([None] * 10), 1, None) == -1
-            finally:
-                lib.sqair_destroy(h)
 
 
 def test_backward_decoder_refusals_host_side():
     """sqair_backward_decoder (the decoder adjoint of the training step as a unit entry) says no before any HIP call to what it
     does not serve -- an n_hidden that is padded, a frame whose H * W is not a multiple of 4 -- and its scratch size answers
     without a GPU."""
-    lib = _capi.lib()
     T, B = 3, 4
     buf = (C.c_float * 16)()     # stands for every device buffer: a refusal comes before anything is read
     for flags, hw, msg in ((dict(n_units=5), (50, 50), b"an n_hidden that is padded"), (dict(), (37, 41), b"needs H * W to be a multiple of 4")):
-        cfg = make_config(make_flags(k_particles=2, n_steps_per_image=3, **flags), hw)
-        h = C.c_void_p()
-        assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-        try:
-            nb = lib.sqair_backward_scratch_bytes(h, T, B)
+        with handle(hw=hw, k_particles=2, n_steps_per_image=3, **flags) as (lib, h):
+            nb =lib.sqair_backward_scratch_bytes(h, T, B)
             assert nb > 0 and lib.sqair_backward_scratch_bytes(h, 0, B) == -1
             rc = lib.sqair_backward_decoder(h, buf, buf, buf, buf, buf, T, B, buf, lib.sqair_workspace_bytes(h, T, B), buf, nb, buf, None,
                                             None)
             assert rc == -1 and msg in lib.sqair_last_error(h), lib.sqair_last_error(h)
             assert lib.sqair_backward_decoder(h, buf, buf, buf, buf, buf, T, B, buf, lib.sqair_workspace_bytes(h, T, B), buf, nb - 4, buf,
                                               None, None) == -1 and b"too small" in lib.sqair_last_error(h)
-        finally:
-            lib.sqair_destroy(h)
 
 
 def _all_set(cls, buf, **over):
@@ -292,14 +243,10 @@ def test_slot_adjoint_test_entries_refuse_host_side():
     below 9 + 2 n_what or beyond the LDS."""
     buf = (C.c_float * 16)()
     for path in (_capi.LIB_PATH, _capi.WIDE_LIB_PATH):
-        lib = _capi.lib(path)
-        assert lib.sqair_abi_version() == _capi.ABI_VERSION == 2
-        cfg = make_config(make_flags(k_particles=2, n_steps_per_image=3), (50, 50))
-        h = C.c_void_p()
-        assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-        big = C.c_void_p()
-        assert lib.sqair_create(C.byref(make_config(make_flags(k_particles=2, n_steps_per_image=3), (200, 200))), C.byref(big)) == 0
-        try:
+        K2 = dict(k_particles=2, n_steps_per_image=3)
+        with handle(path, **K2) as (lib, h), handle(path, hw=(200, 200), **K2) as (_, big):
+            assert lib.sqair_abi_version() == _capi.ABI_VERSION == 2
+
             def refused(fn, cls, handle=h, **over):
                 name = fn.encode()
                 assert fn in _capi.EXPORTED_SYMBOLS
@@ -368,9 +315,6 @@ def test_slot_adjoint_test_entries_refuse_host_side():
                 assert b"LDS" in refused(fn, cls, **dict(ok, ps_ld=1 << 20))                  # a row that no longer fits the LDS
             assert b"t < 0" in refused("sqair_logprob_test", LF, **dict(fwd, t=-1))
             assert b"200 x 200" in refused("sqair_logprob_bwd_test", LB, handle=big, **bwd)  # a configuration that cannot be trained
-        finally:
-            lib.sqair_destroy(h)
-            lib.sqair_destroy(big)
 
 
 def test_slot_forward_test_entries_refuse_host_side():
@@ -384,12 +328,10 @@ def test_slot_forward_test_entries_refuse_host_side():
     CR, TL, WH = _capi.SqairSlotCropTest, _capi.SqairSlotTailTest, _capi.SqairLinearWhatTest
     for path in (_capi.LIB_PATH, _capi.WIDE_LIB_PATH):
         wide = path == _capi.WIDE_LIB_PATH
-        lib = _capi.lib(path)
-        assert lib.sqair_abi_version() == _capi.ABI_VERSION == 2
-        h, gru = C.c_void_p(), C.c_void_p()
-        assert lib.sqair_create(C.byref(make_config(make_flags(k_particles=2, n_steps_per_image=3), (50, 50))), C.byref(h)) == 0
-        assert lib.sqair_create(C.byref(make_config(make_flags(k_particles=2, n_steps_per_image=3, transition="GRU"), (50, 50))), C.byref(gru)) == 0
-        try:
+        K2 = dict(k_particles=2, n_steps_per_image=3)
+        with handle(path, **K2) as (lib, h), handle(path, transition="GRU", **K2) as (_, gru):
+            assert lib.sqair_abi_version() == _capi.ABI_VERSION == 2
+
             def call(fn, cls, handle=h, **over):
                 assert fn in _capi.EXPORTED_SYMBOLS
                 return getattr(lib, fn)(handle, C.byref(_all_set(cls, buf, **over)), None), lib.sqair_last_error(handle)
@@ -465,41 +407,24 @@ def test_slot_forward_test_entries_refuse_host_side():
                     assert b"pitch" in refused("sqair_linear_what_test", WH, **dict(what, **{ld: v}))
                 rc, err = call("sqair_linear_what_test", WH, **dict(what, x_ld=1026))                   # the launcher's own refusal: its code
                 assert rc == -5 and err.startswith(b"sqair_linear_what_test: "), (rc, err)
-        finally:
-            lib.sqair_destroy(h)
-            lib.sqair_destroy(gru)
 
 
-# ---- the binding is read from the header (sqair_amd/_abi.py): gcc judges what the parser read --------------------------------------
-def _gcc(tmp_path, name, lines, repo_root, run=True):
-    """Compiles (and runs) a generated C file against the header; returns what it printed, or the compiler's exit status."""
-    import shutil
-    import subprocess
-    src = tmp_path / (name + ".c")
-    src.write_text("\n".join(lines) + "\n")
-    gcc = shutil.which("gcc")
-    assert gcc, "gcc is part of the image"
-    cmd = [gcc, "-std=gnu11", "-I" + os.path.join(repo_root, "include"), str(src)]
-    if not run:
-        return subprocess.run(cmd + ["-fsyntax-only"], capture_output=True, text=True).returncode
-    subprocess.check_call(cmd + ["-o", str(tmp_path / name)])
-    return subprocess.run([str(tmp_path / name)], capture_output=True, text=True, check=True).stdout
-
-
-def test_every_struct_has_the_header_layout(repo_root, tmp_path):
+# ---- the binding is read from the header (sqair_amd/_abi.py): gcc (tests/abi_host.py) judges what the parser read -------------------
+def test_every_struct_has_the_header_layout(tmp_path):
     """Every struct of the header is passed by address: the ctypes classes made from the parse must have the size, the field offsets
     and the field sizes a C compiler gives the header's structs.  The struct list is the header's, not a list kept here."""
     structs = _abi.header().structs
     assert len(structs) >= 30 and {"SqairConfig", "SqairOutputs", "SqairSmc", "SqairCarry", "SqairDenseContract", "SqairDxTest",
                                    "SqairLogprobBwdTest", "SqairLinearWhatTest"} <= set(structs)
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(repo_root, "include", "sqair_hip.h")).read(), flags=re.S)
-    assert list(structs) == re.findall(r"^\}\s*(\w+)\s*;", txt, flags=re.M)   # (every struct closes at the start of a line)
+    # the parse skipped none and kept the order: every closing brace of the header is a parsed struct's or the extern "C" guard's
+    closes = [code().index("}} {};".format(name)) for name in structs]
+    assert code().count("}") == len(structs) + 1 and closes == sorted(closes)
     lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "sqair_hip.h"', "int main(void) {"]
     for name, fields in structs.items():
         lines.append('  printf("{0} %zu\\n", sizeof({0}));'.format(name))
         for f in fields:
             lines.append('  printf("{0}.{1} %zu %zu\\n", offsetof({0}, {1}), sizeof((({0}*)0)->{1}));'.format(name, f.name))
-    got = {l.split()[0]: [int(v) for v in l.split()[1:]] for l in _gcc(tmp_path, "layout", lines + ["  return 0;", "}"], repo_root).splitlines()}
+    got = {l.split()[0]: [int(v) for v in l.split()[1:]] for l in _gcc(tmp_path, "layout", lines + ["  return 0;", "}"]).splitlines()}
     for name, fields in structs.items():
         cls = getattr(_capi, name)
         assert issubclass(cls, C.Structure) and [n for n, _ in cls._fields_] == [f.name for f in fields], name
@@ -511,26 +436,27 @@ def test_every_struct_has_the_header_layout(repo_root, tmp_path):
     assert dict(_capi.SqairLogprobTest._fields_)["out"] is C.c_void_p          # an address set as an integer
     assert dict(_capi.SqairConfig._fields_)["where_prior_mean"] is C.c_float * 4
     assert dict(_capi.SqairDxTest._fields_)["gru"] is _capi.SqairDxGru and dict(_capi.SqairDxTest._fields_)["r"] is _capi.SqairDxRange * 3
-    assert len(_capi.DENSE_ROUTES) == int(re.search(r"#define SQAIR_DENSE_ROUTES (\d+)", txt).group(1))
+    assert len(_capi.DENSE_ROUTES) == constant("SQAIR_DENSE_ROUTES")
 
 
-def test_every_prototype_reads_as_the_compiler_reads_it(repo_root, tmp_path):
+def test_every_prototype_reads_as_the_compiler_reads_it(tmp_path):
     """One _Static_assert per function of the header: the type of the function is the return type and the parameters printed back
     from the parse, const-ness, base type and pointer depth.  Nothing is linked or run.  The mapping to ctypes is then a table: one
     function of each kind."""
     functions = _abi.header().functions
-    assert sorted(functions) == _header_functions(repo_root) and len(functions) >= 103
+    # the parse skipped none: every parenthesis of the header opens the parameters of a parsed function
+    assert code().count("(") == len(functions) >= 103 and all(name + "(" in code() for name in functions)
 
     def claim(name, ret, params):
         return '_Static_assert(__builtin_types_compatible_p(__typeof__(&{0}), {1} (*)({2})), "{0}");'.format(
             name, _abi.spell(ret), ", ".join(_abi.spell(p) for p in params) or "void")
     head = ['#include "sqair_hip.h"']
-    assert _gcc(tmp_path, "protos", head + [claim(n, *f) for n, f in functions.items()], repo_root, run=False) == 0
+    assert _gcc(tmp_path, "protos", head + [claim(n, *f) for n, f in functions.items()], run=False) == 0
     # (the claim can fail: one const dropped, one depth off)
     ret, params = functions["sqair_elbo"]
     assert _abi.spell(params[10]) == "const float* const*"
     for wrong in (params[10]._replace(pointer_const=()), params[10]._replace(pointer_depth=1, pointer_const=())):
-        assert _gcc(tmp_path, "wrong", head + [claim("sqair_elbo", ret, params[:10] + [wrong] + params[11:])], repo_root, run=False) != 0
+        assert _gcc(tmp_path, "wrong", head + [claim("sqair_elbo", ret, params[:10] + [wrong] + params[11:])], run=False) != 0
     P, V, I = C.POINTER, C.c_void_p, C.c_int
     for name, want in (("sqair_create", (I, [P(_capi.SqairConfig), V])), ("sqair_last_error", (C.c_char_p, [V])),
                        ("sqair_set_option", (I, [V, C.c_char_p, I])), ("sqair_history_bytes", (C.c_int64, [V, I, I, I, C.c_uint32])),
@@ -638,24 +564,25 @@ _INT_FIELDS_BEFORE = dict(FORECAST_LANE_INT_FIELDS=("best_row",), ESTIMATE_INT_F
                           TRAJ_INT_FIELDS=("link", "state", "count_map"), TRACK_LANE_INT_FIELDS=("best_row", "first_frame"))
 
 
-def test_buffer_element_types_are_the_headers(repo_root):
-    """What the allocation code asks the binding -- the element type of a struct's pointer field -- against the header text read by
-    this test's own regex."""
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(repo_root, "include", "sqair_hip.h")).read(), flags=re.S)
-    names = {"float": "float32", "int32_t": "int32", "int64_t": "int64", "double": "float64"}
+def test_buffer_element_types_are_the_headers():
+    """What the allocation code asks the binding -- the element type of a struct's pointer field -- against the field's type as the
+    header spells it, and for a few against the words of the header's text."""
+    txt = " ".join(code().split())      # (runs of blanks as one)
+    names = {"float*": "float32", "const float*": "float32", "int32_t*": "int32", "const int32_t*": "int32", "int64_t*": "int64",
+             "double*": "float64"}
     for struct, fields in (("SqairLaneScore", ("truth_box", "truth_present", "truth_valid", "counts", "iou_sum", "last_id", "match_iou", "tp")),
                            ("SqairLaneIdentity", ("trk_id", "trk_box", "trk_what", "next_id", "counts", "lane_id")),
                            ("SqairLaneIdf", ("col_id", "overlap", "frames", "totals")),
                            ("SqairTrajScore", ("counts", "sums", "lane_counts", "link", "link_iou")),
                            ("SqairTraceOutputs", ("where", "log_w", "valid", "ancestor_row", "track_id", "track_where"))):
-        body = re.search(r"typedef struct {0} \{{(.*?)\}} {0};".format(struct), txt, flags=re.S).group(1)
+        spelled = {n: ty for ty, n in header_fields(struct)}
         for f in fields:
-            assert _capi.field_dtype(struct, f) == names[re.search(r"(\w+)\s*\*\s*{}\s*;".format(f), body).group(1)], (struct, f)
-    assert re.search(r"double\* iou_sum", txt) and _capi.field_dtype("SqairLaneScore", "iou_sum") == "float64"
-    assert re.search(r"int64_t\* counts", txt) and _capi.field_dtype("SqairLaneScore", "counts") == "int64"
-    assert re.search(r"int32_t\* truth_present", txt) and _capi.field_dtype("SqairLaneScore", "truth_present") == "int32"
-    assert re.search(r"float\*\s+trk_box", txt) and _capi.field_dtype("SqairLaneIdentity", "trk_box") == "float32"
-    assert re.search(r"int64_t\* open\b", txt) and _capi.field_dtype("sqair_lane_idf_solve", "open") == "int64"   # a parameter
+            assert _capi.field_dtype(struct, f) == names[spelled[f]], (struct, f)
+    assert "double* iou_sum;" in txt and _capi.field_dtype("SqairLaneScore", "iou_sum") == "float64"
+    assert "int64_t* counts;" in txt and _capi.field_dtype("SqairLaneScore", "counts") == "int64"
+    assert "int32_t* truth_present;" in txt and _capi.field_dtype("SqairLaneScore", "truth_present") == "int32"
+    assert "float* trk_box" in txt and _capi.field_dtype("SqairLaneIdentity", "trk_box") == "float32"
+    assert "int64_t* open," in prototype("sqair_lane_idf_solve") and _capi.field_dtype("sqair_lane_idf_solve", "open") == "int64"   # a parameter
     for scalar in (("SqairLaneScore", "G"), ("SqairCarry", "smc"), ("SqairCarry", "state_in")):   # no array of a device type
         with pytest.raises(KeyError):
             _capi.field_dtype(*scalar)

@@ -2,88 +2,46 @@
 declared, the header's paragraph carries the semantics, every refusal is made before any HIP call (dummy device pointers are
 enough), the estimate goes off with the state -- and the argument errors of SqairStream(estimate=...)."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
 from sqair_amd.stream import SqairStream
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DUMMY = C.c_void_p(0x1000)     # never dereferenced: the calls below are refused first
-BIG = 1 << 50
-
-
-def _handle(path=None, hw=(50, 50), **flags):
-    lib = _capi.lib(path)
-    cfg = make_config(make_flags(**flags), hw)
-    h = C.c_void_p()
-    assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-    return lib, h
-
-
-def _err(lib, h):
-    return lib.sqair_last_error(h).decode()
-
-
-def _state(lib, h, B):
-    assert lib.sqair_set_state(h, DUMMY, DUMMY, DUMMY, lib.sqair_state_bytes(h, B), B) == 0
-
-
-def _est(iou_min=0.5, log_w=0x2000, best_row=0x3000, **kw):
-    return _capi.SqairLaneEstimate(iou_min=iou_min, log_w=log_w, best_row=best_row, **kw)
-
-
-def _smc(log_w=0x2000):
-    return _capi.SqairSmc(ess_frac=0.5, seed=0, uniforms=None, log_w=log_w, log_z=0x1000, log_evidence=0x1000, ess=0x1000, u_out=None,
-                          resampled=0x1000, src_rows=0x1000)
-
-
-def _fwd_args(h, B, T=1, bind=("log_weights_per_timestep",)):
-    out = _capi.SqairOutputs(**{k: 0x1000 for k in bind})
-    return (h, DUMMY, DUMMY, DUMMY, DUMMY, T, B, 0, C.byref(out), DUMMY, BIG, DUMMY)
+from tests.abi_host import (DUMMY, LIBS, constant, err as _err, estimate as _est, fields as header_fields, fwd_args as _fwd_args, handle,
+                            paragraph, phrases, prototype, set_state as _state, smc as _smc, stated_once)
 
 
 def test_the_symbols_are_exported_and_declared_and_the_abi_is_unchanged():
-    hdr = open(os.path.join(ROOT, "include", "sqair_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     for path in (None, _capi.WIDE_LIB_PATH, _capi.TIMELINE_LIB_PATH):
         lib = _capi.lib(path)
         assert hasattr(lib, "sqair_set_estimate") and hasattr(lib, "sqair_lane_estimate_test") and lib.sqair_abi_version() == 2
     assert "sqair_set_estimate" in _capi.EXPORTED_SYMBOLS and "sqair_lane_estimate_test" in _capi.EXPORTED_SYMBOLS
-    assert re.search(r"\bint\s+sqair_set_estimate\s*\(\s*SqairHandle\*\s*h,\s*const SqairLaneEstimate\*\s*est\s*,\s*int T,\s*int B\)", code)
-    assert re.search(r"\bint\s+sqair_lane_estimate_test\s*\(\s*SqairHandle\*\s*h,\s*const float\*\s*where,\s*const float\*\s*presence,"
-                     r"\s*const float\*\s*obj_id,\s*const float\*\s*what,\s*const float\*\s*canvas,\s*const float\*\s*lw,\s*int T,"
-                     r"\s*int B,\s*int K,\s*const SqairLaneEstimate\*\s*est,\s*void\*\s*stream\)", code)
-    assert _capi.ABI_VERSION == 2 and re.search(r"#define SQAIR_ABI_VERSION 2\b", hdr)
+    assert prototype("sqair_set_estimate") == "int sqair_set_estimate(SqairHandle* h, const SqairLaneEstimate* est, int T, int B)"
+    assert prototype("sqair_lane_estimate_test") == ("int sqair_lane_estimate_test(SqairHandle* h, const float* where, const float* presence, "
+                                                     "const float* obj_id, const float* what, const float* canvas, const float* lw, int T, "
+                                                     "int B, int K, const SqairLaneEstimate* est, void* stream)")
+    assert _capi.ABI_VERSION == 2 == constant("SQAIR_ABI_VERSION")
     # the binding's struct mirrors the header's, field for field and in order
-    body = re.search(r"typedef struct SqairLaneEstimate \{(.*?)\} SqairLaneEstimate;", code, flags=re.S).group(1)
-    fields = re.findall(r"(const float\*|float\*|int32_t\*|float)\s+(\w+);", body)
+    fields = header_fields("SqairLaneEstimate")
     assert [n for _, n in fields] == [n for n, _ in _capi.SqairLaneEstimate._fields_]
     assert [n for ty, n in fields if ty == "int32_t*"] == list(_capi.ESTIMATE_INT_FIELDS)
     assert [n for _, n in fields][2:] == list(_capi.ESTIMATE_FIELDS)
 
 
 def test_the_header_states_the_semantics_once():
-    hdr = open(os.path.join(ROOT, "include", "sqair_hip.h")).read()
-    doc = hdr[hdr.index("lane estimates: one answer per lane"):hdr.index("typedef struct SqairLaneEstimate")]
-    doc = re.sub(r"\s*\n \*\s*", " ", doc)   # (the comment's line breaks)
-    for word in ("k_lane_estimate", "BEFORE the", "exactly one kernel node more", "Training passes never run it",
-                 "in frame order, in fp32", "index order", "bit for bit", "NULL means zeros", "the first k of maximal a_k",
-                 "count_prob[t,b,c] = sum_k w_k [n_k = c]", "the first c of maximal count_prob", "stn_to_pixel_coords(to_coords(where), (H, W))",
-                 "modules.py:221-262", "SPATIAL association", "not by id", "the first present slot of row k with maximal IoU",
-                 "0 when the union is not positive", "iou_min", "NOT one-to-one", "mean_canvas[t,b] = sum_k w_k canvas[t, r]",
-                 "out->canvas", "Non-finite lanes", "best_row = map_count = -1", "zero objects", "Coasted", "Refused"):
-        assert word in doc, word
-    assert hdr.count("lane estimates: one answer per lane") == 1
+    doc = paragraph("lane estimates: one answer per lane", "typedef struct SqairLaneEstimate")
+    phrases(doc, ("k_lane_estimate", "BEFORE the", "exactly one kernel node more", "Training passes never run it",
+                  "in frame order, in fp32", "index order", "bit for bit", "NULL means zeros", "the first k of maximal a_k",
+                  "count_prob[t,b,c] = sum_k w_k [n_k = c]", "the first c of maximal count_prob",
+                  "stn_to_pixel_coords(to_coords(where), (H, W))", "modules.py:221-262", "SPATIAL association", "not by id",
+                  "the first present slot of row k with maximal IoU", "0 when the union is not positive", "iou_min", "NOT one-to-one",
+                  "mean_canvas[t,b] = sum_k w_k canvas[t, r]", "out->canvas", "Non-finite lanes", "best_row = map_count = -1", "zero objects",
+                  "Coasted", "Refused"))
+    stated_once("lane estimates: one answer per lane")
 
 
 def test_set_estimate_refusals_before_any_hip_call():
-    lib, h = _handle(k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(k_particles=2, n_steps_per_image=3) as (lib, h):
         B = 4
         assert lib.sqair_set_estimate(None, C.byref(_est()), 1, B) == -1
         assert lib.sqair_set_estimate(h, C.byref(_est()), 1, B) == -1 and "carried state" in _err(lib, h)      # no state set
@@ -103,13 +61,10 @@ def test_set_estimate_refusals_before_any_hip_call():
             assert lib.sqair_set_estimate(h, C.byref(_est(log_w=other)), 1, B) == -1 and "smc->log_w" in _err(lib, h)
         assert lib.sqair_set_estimate(h, C.byref(_est(log_w=0x2000)), 1, B) == 0
         assert lib.sqair_set_estimate(h, None, 0, 0) == 0       # NULL: off
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_pass_time_refusals_before_any_hip_call():
-    lib, h = _handle(k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(k_particles=2, n_steps_per_image=3) as (lib, h):
         B = 4
         _state(lib, h, B)
         assert lib.sqair_set_estimate(h, C.byref(_est()), 2, B) == 0
@@ -128,13 +83,10 @@ def test_pass_time_refusals_before_any_hip_call():
         assert lib.sqair_set_estimate(h, C.byref(_est(log_w=0x2000)), 2, B) == 0
         assert lib.sqair_set_smc(h, C.byref(_smc(log_w=0x2100)), B) == 0
         assert lib.sqair_forward(*_fwd_args(h, B, T=2)) == -1 and "sqair_set_estimate" in _err(lib, h) and "smc->log_w" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_the_state_going_off_or_to_another_b_takes_the_estimate_with_it():
-    lib, h = _handle(k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(k_particles=2, n_steps_per_image=3) as (lib, h):
         B = 4
         # a pass of the registered B, another T and a NULL parameter pointer: the estimate refuses it while it is on; once it is
         # off the pass gets to its own argument check, which comes next -- still on the host
@@ -155,27 +107,21 @@ def test_the_state_going_off_or_to_another_b_takes_the_estimate_with_it():
         _state(lib, h, B + 1)              # another B: off
         assert gone(B + 1)
         assert lib.sqair_set_estimate(h, C.byref(_est()), 2, B) == -1 and "B = 4" in _err(lib, h) and "B = 5" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_training_calls_never_estimate():
     """A training pass with the handle's state on is the state's to refuse; a carried training call does not look at the handle's
     estimate at all (there is none without a state)."""
-    lib, h = _handle(k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(k_particles=2, n_steps_per_image=3) as (lib, h):
         B = 4
         _state(lib, h, B)
         assert lib.sqair_set_estimate(h, C.byref(_est()), 2, B) == 0
         assert lib.sqair_forward_train(*_fwd_args(h, B, T=2)) == -1 and "carried state" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
-@pytest.mark.parametrize("path", [None, _capi.WIDE_LIB_PATH])
+@pytest.mark.parametrize("path", LIBS)
 def test_kernel_entry_point_refusals_before_any_hip_call(path):
-    lib, h = _handle(path, k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(path, k_particles=2, n_steps_per_image=3) as (lib, h):
         good = dict(where=DUMMY, presence=DUMMY, obj_id=DUMMY, what=DUMMY, canvas=DUMMY, lw=DUMMY, T=1, B=3, K=5)
         order = ("where", "presence", "obj_id", "what", "canvas", "lw", "T", "B", "K")
         call = lambda est, **kw: lib.sqair_lane_estimate_test(h, *[dict(good, **kw)[k] for k in order],
@@ -190,8 +136,6 @@ def test_kernel_entry_point_refusals_before_any_hip_call(path):
         assert call(_est(best_row=None)) == -1 and "best_row" in _err(lib, h)
         assert call(_est(what=0x4000), what=None) == -1 and "est->what needs what" in _err(lib, h)
         assert call(_est(mean_canvas=0x4000), canvas=None) == -1 and "est->mean_canvas needs canvas" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_stream_argument_errors():

@@ -19,10 +19,9 @@ import pytest
 import torch
 
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
 from tests import estimate_check as EC
 from tests import estimate_ref as E
+from tests.abi_host import open_handle
 
 pytestmark = pytest.mark.gpu
 
@@ -105,11 +104,7 @@ _handles = {}
 def _handle(wide, N, hw):
     key = (wide, N, hw)
     if key not in _handles:
-        lib = _capi.lib(_capi.WIDE_LIB_PATH if wide else None)
-        cfg = make_config(make_flags(k_particles=2, n_steps_per_image=N, n_what=N_WHAT), hw)
-        h = C.c_void_p()
-        assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-        _handles[key] = (lib, h)
+        _handles[key] = open_handle(_capi.WIDE_LIB_PATH if wide else None, hw, k_particles=2, n_steps_per_image=N, n_what=N_WHAT)
     return _handles[key]
 
 

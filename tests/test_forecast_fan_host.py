@@ -1,54 +1,38 @@
 """No GPU: the C-ABI of the object forecasts (include/sqair_hip.h: sqair_forecast_fan, sqair_forecast_lane_test) -- exported and
 declared, sized, and every refusal made before any HIP call."""
 import ctypes as C
-import os
-import re
+import functools
 
 import pytest
 
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
+from tests import abi_host
+from tests.abi_host import constant, err as _err, fields as header_fields, functions
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("sqair_forecast_fan_workspace_bytes", "sqair_forecast_fan", "sqair_forecast_lane_scratch_bytes", "sqair_forecast_lane_test")
+NEW =("sqair_forecast_fan_workspace_bytes", "sqair_forecast_fan", "sqair_forecast_lane_scratch_bytes", "sqair_forecast_lane_test")
 LIBS = {"product": (_capi.LIB_PATH, dict()), "wide": (_capi.WIDE_LIB_PATH, dict(n_what=64))}
 P = C.c_void_p(16)   # (a fake device address: every call below is refused before anything is dereferenced or launched)
-
-
-def _handle(path, **flags):
-    lib = _capi.lib(path)
-    cfg = make_config(make_flags(**flags), (32, 40))
-    h = C.c_void_p()
-    assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-    return lib, h
-
-
-def _err(lib, h):
-    return lib.sqair_last_error(h).decode()
+handle = functools.partial(abi_host.handle, hw=(32, 40))
 
 
 def test_symbols_are_exported_and_declared_and_the_abi_is_unchanged():
-    hdr = open(os.path.join(ROOT, "include", "sqair_hip.h")).read()
     for name in NEW:
         assert name in _capi.EXPORTED_SYMBOLS
-        assert re.search(r"\b{}\s*\(".format(name), hdr), name
-    fields = re.search(r"typedef struct SqairForecastLane \{(.*?)\} SqairForecastLane;", hdr, re.S).group(1)
-    names = re.findall(r"[\* ]\s*(\w+);", fields)
-    assert names == [n for n, _ in _capi.SqairForecastLane._fields_]
-    assert int(re.search(r"#define SQAIR_FORECAST_FAN_MAX (\d+)", hdr).group(1)) == _capi.FORECAST_FAN_MAX == 1024
+        assert name in functions(), name
+    assert [n for _, n in header_fields("SqairForecastLane")] == [n for n, _ in _capi.SqairForecastLane._fields_]
+    assert constant("SQAIR_FORECAST_FAN_MAX") == _capi.FORECAST_FAN_MAX == 1024
     # old callers pass the old struct: SqairForecastOutputs keeps its layout
-    old = re.search(r"typedef struct SqairForecastOutputs \{(.*?)\} SqairForecastOutputs;", hdr, re.S).group(1)
-    assert re.findall(r"\*\s*(\w+);", old) == ["what", "where", "presence", "presence_prob", "presence_logit", "obj_id", "canvas", "glimpse",
-                                               "log_w", "mean_canvas", "expected_count"]
-    assert _capi.ABI_VERSION == 2 and re.search(r"#define SQAIR_ABI_VERSION 2\b", hdr) and _capi.lib().sqair_abi_version() == 2
+    assert header_fields("SqairForecastOutputs") == [
+        ("float*", "what"), ("float*", "where"), ("float*", "presence"), ("float*", "presence_prob"), ("float*", "presence_logit"),
+        ("float*", "obj_id"), ("float*", "canvas"), ("float*", "glimpse"), ("const float*", "log_w"), ("float*", "mean_canvas"),
+        ("float*", "expected_count")]
+    assert _capi.ABI_VERSION == 2 == constant("SQAIR_ABI_VERSION") and _capi.lib().sqair_abi_version() == 2
 
 
 @pytest.mark.parametrize("which", sorted(LIBS))
 def test_workspace_bytes(which):
     path, flags = LIBS[which]
-    lib, h = _handle(path, k_particles=3, n_steps_per_image=2, **flags)
-    try:
+    with handle(path, k_particles=3, n_steps_per_image=2, **flags) as (lib, h):
         fan, plain = lib.sqair_forecast_fan_workspace_bytes, lib.sqair_forecast_workspace_bytes
         for F, B in ((1, 1), (2, 3), (10, 2)):
             assert fan(h, F, B, 1) >= plain(h, F, B) > 0
@@ -59,8 +43,6 @@ def test_workspace_bytes(which):
         assert fan(h, 1, 2 ** 22, 341) == -1                              # R * S * N beyond int32
         assert lib.sqair_forecast_lane_scratch_bytes(h, 2, 5) > 0
         assert lib.sqair_forecast_lane_scratch_bytes(h, 0, 5) == -1 and lib.sqair_forecast_lane_scratch_bytes(h, 2, 257) == -1
-    finally:
-        lib.sqair_destroy(h)
 
 
 def _call(lib, h, F=2, B=2, S=2, noise=True, out=True, ws=True, ws_bytes=None, lane=None, flat=True):
@@ -71,8 +53,7 @@ def _call(lib, h, F=2, B=2, S=2, noise=True, out=True, ws=True, ws_bytes=None, l
 
 
 def test_fan_refusals_before_any_hip_call():
-    lib, h = _handle(_capi.LIB_PATH, k_particles=2, n_steps_per_image=2)
-    try:
+    with handle(_capi.LIB_PATH, k_particles=2, n_steps_per_image=2) as (lib, h):
         # ---- everything sqair_forecast refuses
         assert _call(lib, h) == -1 and "state_in" in _err(lib, h) and "sqair_forecast_fan" in _err(lib, h)      # no state at all
         nb = lib.sqair_state_bytes(h, 2)
@@ -102,29 +83,20 @@ def test_fan_refusals_before_any_hip_call():
         # switching the state off refuses again
         assert lib.sqair_set_state(h, None, None, None, 0, 0) == 0
         assert _call(lib, h) == -1 and "state_in" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_fan_refuses_int32_overflow_and_sample_from_prior():
-    lib, h = _handle(_capi.LIB_PATH, k_particles=2, n_steps_per_image=2)
-    try:
+    with handle(_capi.LIB_PATH, k_particles=2, n_steps_per_image=2) as (lib, h):
         B = 2 ** 21
         nb = lib.sqair_state_bytes(h, B)
         assert lib.sqair_set_state(h, C.c_void_p(64), C.c_void_p(64), None, nb, B) == 0
         assert _call(lib, h, B=B, S=512, ws_bytes=1 << 62) == -1 and "int32" in _err(lib, h)                     # R * S * N = 2^32
-    finally:
-        lib.sqair_destroy(h)
-    lib, h = _handle(_capi.LIB_PATH, k_particles=2, n_steps_per_image=2, sample_from_prior=True)
-    try:
+    with handle(_capi.LIB_PATH, k_particles=2, n_steps_per_image=2, sample_from_prior=True) as (lib, h):
         assert _call(lib, h) == -1 and "sample_from_prior" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_lane_test_entry_refusals():
-    lib, h = _handle(_capi.LIB_PATH, k_particles=2, n_steps_per_image=2)
-    try:
+    with handle(_capi.LIB_PATH, k_particles=2, n_steps_per_image=2) as (lib, h):
         lane = _capi.SqairForecastLane(iou_min=0.5, best_row=C.c_void_p(32))
 
         def call(ptrs=(P,) * 6, F=1, B=1, K=2, S=2, lane=lane, scratch=P, nb=None):
@@ -139,5 +111,3 @@ def test_lane_test_entry_refusals():
         assert call(lane=_capi.SqairForecastLane(iou_min=0.0, best_row=C.c_void_p(32))) == -1 and "iou_min" in _err(lib, h)
         assert call(lane=_capi.SqairForecastLane(iou_min=0.5)) == -1 and "best_row" in _err(lib, h)
         assert call(nb=lib.sqair_forecast_lane_scratch_bytes(h, 1, 2) - 1) == -1 and "scratch_bytes" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)

@@ -1,58 +1,40 @@
 """No GPU: the forecast's C-ABI (include/sqair_hip.h: sqair_forecast) -- exported and declared, sized, and every refusal made
 before any HIP call."""
 import ctypes as C
-import os
-import re
+import functools
 
 import pytest
 
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
+from tests import abi_host
+from tests.abi_host import constant, err as _err, fields as header_fields, functions
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("sqair_forecast_workspace_bytes", "sqair_forecast")
 LIBS = {"product": (_capi.LIB_PATH, dict()), "wide": (_capi.WIDE_LIB_PATH, dict(n_what=64))}
-
-
-def _handle(path, **flags):
-    lib = _capi.lib(path)
-    cfg = make_config(make_flags(**flags), (32, 40))
-    h = C.c_void_p()
-    assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-    return lib, h
-
-
-def _err(lib, h):
-    return lib.sqair_last_error(h).decode()
+handle = functools.partial(abi_host.handle, hw=(32, 40))
 
 
 def test_symbols_are_exported_and_declared_and_the_abi_is_unchanged():
-    hdr = open(os.path.join(ROOT, "include", "sqair_hip.h")).read()
     for name in NEW:
         assert name in _capi.EXPORTED_SYMBOLS
-        assert re.search(r"\b{}\s*\(".format(name), hdr), name
-    assert "typedef struct SqairForecastOutputs" in hdr
-    fields = re.search(r"typedef struct SqairForecastOutputs \{(.*?)\} SqairForecastOutputs;", hdr, re.S).group(1)
-    names = re.findall(r"\*\s*(\w+);", fields)
-    assert names == [n for n, _ in _capi.SqairForecastOutputs._fields_]
+        assert name in functions(), name
+    fields = header_fields("SqairForecastOutputs")
+    assert [n for _, n in fields] == [n for n, _ in _capi.SqairForecastOutputs._fields_]
+    assert all(ty.endswith("*") for ty, _ in fields)      # pointers, every one
     assert _capi.ABI_VERSION == 2
-    assert re.search(r"#define SQAIR_ABI_VERSION 2\b", hdr)
+    assert constant("SQAIR_ABI_VERSION") == 2
     assert _capi.lib().sqair_abi_version() == 2
 
 
 @pytest.mark.parametrize("which", sorted(LIBS))
 def test_workspace_bytes_positive_and_growing(which):
     path, flags = LIBS[which]
-    lib, h = _handle(path, k_particles=3, n_steps_per_image=2, **flags)
-    try:
+    with handle(path, k_particles=3, n_steps_per_image=2, **flags) as (lib, h):
         ws = lambda F, B: lib.sqair_forecast_workspace_bytes(h, F, B)
         assert ws(1, 1) > 0
         assert ws(2, 1) > ws(1, 1) and ws(10, 1) > ws(2, 1)
         assert ws(1, 2) > ws(1, 1) and ws(3, 4) > ws(3, 2)
         assert ws(0, 1) == -1 and ws(1, 0) == -1
-    finally:
-        lib.sqair_destroy(h)
 
 
 def _call(lib, h, F=2, B=1, noise=1, ws=None, out=True, ws_bytes=None):
@@ -64,8 +46,7 @@ def _call(lib, h, F=2, B=1, noise=1, ws=None, out=True, ws_bytes=None):
 
 
 def test_refusals_before_any_hip_call():
-    lib, h = _handle(_capi.LIB_PATH, k_particles=2, n_steps_per_image=2)
-    try:
+    with handle(_capi.LIB_PATH, k_particles=2, n_steps_per_image=2) as (lib, h):
         # no state set at all
         assert _call(lib, h) == -1 and "state_in" in _err(lib, h)
         # a state without state_in (export only)
@@ -86,13 +67,8 @@ def test_refusals_before_any_hip_call():
         # switching the state off refuses again
         assert lib.sqair_set_state(h, None, None, None, 0, 0) == 0
         assert _call(lib, h, B=2) == -1 and "state_in" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_refused_with_sample_from_prior():
-    lib, h = _handle(_capi.LIB_PATH, k_particles=2, n_steps_per_image=2, sample_from_prior=True)
-    try:
+    with handle(_capi.LIB_PATH, k_particles=2, n_steps_per_image=2, sample_from_prior=True) as (lib, h):
         assert _call(lib, h) == -1 and "sample_from_prior" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)

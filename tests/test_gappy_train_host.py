@@ -2,52 +2,17 @@
 sqair_backward_carry_masked) -- exported and declared, the ABI version unchanged, every refusal made before any HIP call (dummy
 device pointers are enough) -- and the argument errors of StreamTrainer(missing=...).step(observed=...)."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
 from sqair_amd.train import StreamTrainer
+from tests.abi_host import BIG, DUMMY, LIBS, constant, err as _err, fwd_args, handle, paragraph, phrases, prototype
+from tests.test_stream_train_host import OTHER, B, _carry, _smc      # the unmasked calls' carry and SMC: the masked ones take the same
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("sqair_forward_train_carry_masked", "sqair_backward_carry_masked")
-DUMMY = C.c_void_p(0x1000)     # never dereferenced: the calls below are refused first
-OTHER = C.c_void_p(0x2000)
-BIG = 1 << 40
-B = 4
-
-
-def _handle(path=None, hw=(50, 50), **flags):
-    lib = _capi.lib(path)
-    cfg = make_config(make_flags(**flags), hw)
-    h = C.c_void_p()
-    assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-    return lib, h
-
-
-def _err(lib, h):
-    return lib.sqair_last_error(h).decode()
-
-
-def _smc(**kw):
-    f = dict(ess_frac=1.0, seed=0, uniforms=None, log_w=DUMMY.value, log_z=DUMMY.value, log_evidence=DUMMY.value,
-             ess=DUMMY.value, u_out=None, resampled=DUMMY.value, src_rows=DUMMY.value)
-    f.update(kw)
-    return _capi.SqairSmc(**f)
-
-
-def _carry(lib, h, smc=None, **kw):
-    f = dict(state_in=DUMMY.value, state_out=DUMMY.value, src_rows=DUMMY.value, state_bytes=lib.sqair_state_bytes(h, B), B=B)
-    f.update(kw)
-    c = _capi.SqairCarry(**f)
-    if smc is not None:
-        c.smc = C.pointer(smc)
-    return c
 
 
 def _calls(lib, h, carry, lw=True, b=B, mask=DUMMY):
@@ -61,29 +26,33 @@ def _calls(lib, h, carry, lw=True, b=B, mask=DUMMY):
 
 
 def test_the_symbols_are_exported_and_declared_and_the_abi_is_unchanged():
-    hdr = open(os.path.join(ROOT, "include", "sqair_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    for path in (None, _capi.WIDE_LIB_PATH):
+    for path in LIBS:
         lib = _capi.lib(path)
         for n in NEW:
             assert hasattr(lib, n) and n in _capi.EXPORTED_SYMBOLS
         assert lib.sqair_abi_version() == 2
-    assert _capi.ABI_VERSION == 2 and re.search(r"#define SQAIR_ABI_VERSION 2\b", hdr)
+    assert _capi.ABI_VERSION == 2 == constant("SQAIR_ABI_VERSION")
     # the unmasked signatures with the mask after the carry
-    assert re.search(r"\bint\s+sqair_forward_train_carry_masked\s*\([^)]*const SqairCarry\*\s*carry,\s*const int32_t\*\s*observed\s*,"
-                     r"\s*const SqairOutputs\*\s*out,", code)
-    assert re.search(r"\bint\s+sqair_backward_carry_masked\s*\([^)]*const SqairCarry\*\s*carry,\s*const int32_t\*\s*observed\s*,"
-                     r"\s*void\*\s*train_workspace,", code)
+    assert prototype("sqair_forward_train_carry_masked") == (
+        "int sqair_forward_train_carry_masked(SqairHandle* h, const float* flat_params, const void* packed, const float* obs, "
+        "const float* noise, int T, int B, const SqairCarry* carry, const int32_t* observed, const SqairOutputs* out, "
+        "void* train_workspace, int64_t workspace_bytes, void* stream)")
+    assert prototype("sqair_backward_carry_masked") == (
+        "int sqair_backward_carry_masked(SqairHandle* h, const float* flat_params, const void* packed, const float* obs, "
+        "const float* noise, const float* importance_weights, const float* vimco_signal, int T, int B, const SqairCarry* carry, "
+        "const int32_t* observed, void* train_workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, "
+        "float* flat_grad, void* stream)")
+    for name in NEW:      # ... which is all that differs from the unmasked calls
+        assert prototype(name).replace("_masked", "").replace(" const int32_t* observed,", "") == prototype(name.replace("_masked", ""))
     # SqairCarry itself did not change
     assert [n for n, _ in _capi.SqairCarry._fields_] == ["state_in", "state_out", "src_rows", "state_bytes", "B", "smc"]
     assert C.sizeof(_capi.SqairCarry) == 48
     # the one definition of the semantics sits above the calls
-    doc = hdr[hdr.index("training on gappy and ragged streams: a per-frame"):hdr.index("int sqair_forward_train_carry_masked")]
-    for word in ("DRAWN FROM p_theta", "LATER IN THE SAME", "log_weights_per_timestep = 0", "exactly zero", "s / T'", "NULL observed",
-                 "T' + 1 kernel nodes"):
-        assert word in doc, word
+    phrases(paragraph("training on gappy and ragged streams: a per-frame", "int sqair_forward_train_carry_masked"),
+            ("DRAWN FROM p_theta", "LATER IN THE SAME", "log_weights_per_timestep = 0", "exactly zero", "s / T'", "NULL observed",
+             "T' + 1 kernel nodes"))
     # sqair_set_observed keeps refusing training calls, and its text points here
-    doc = hdr[hdr.index("missing-frame steps"):hdr.index("int sqair_set_observed")]
+    doc = paragraph("missing-frame steps", "int sqair_set_observed")
     assert "out of scope" in doc and "sqair_forward_train_carry_masked" in doc
 
 
@@ -93,8 +62,7 @@ def test_the_symbols_are_exported_and_declared_and_the_abi_is_unchanged():
 @pytest.mark.parametrize("mask", [DUMMY, None])
 def test_refusals_before_any_hip_call(path, flags, mask):
     """Everything the unmasked carried calls refuse, with a mask and with NULL for one, under the masked calls' names."""
-    lib, h = _handle(path, **flags)
-    try:
+    with handle(path, **flags) as (lib, h):
         def refused(carry, words, **kw):
             f, fe, g, ge = _calls(lib, h, carry, mask=mask, **kw)
             assert f == -1 and g == -1, (words, fe, ge)
@@ -120,27 +88,18 @@ def test_refusals_before_any_hip_call(path, flags, mask):
         f, fe, g, ge = _calls(lib, h, _carry(lib, h), mask=mask)
         assert f == -1 and g == -1 and "sqair_set_observed" in fe and "sqair_set_observed" in ge
         # ... and the handle's mask keeps refusing the unmasked training calls (tests/test_missing_host.py pins the text)
-        out = _capi.SqairOutputs(log_weights_per_timestep=DUMMY.value)
-        assert lib.sqair_forward_train(h, DUMMY, DUMMY, DUMMY, DUMMY, 2, B, 0, C.byref(out), DUMMY, BIG, DUMMY) == -1
+        assert lib.sqair_forward_train(*fwd_args(h, B, T=2)) == -1
         assert "out of scope" in _err(lib, h)
         assert lib.sqair_set_state(h, None, None, None, 0, 0) == 0
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_refused_with_sample_from_prior_and_for_frames_too_large_to_train():
-    lib, h = _handle(k_particles=2, n_steps_per_image=3, sample_from_prior=True, generate_after=2)
-    try:
+    with handle(k_particles=2, n_steps_per_image=3, sample_from_prior=True, generate_after=2) as (lib, h):
         f, fe, g, ge = _calls(lib, h, _carry(lib, h))
         assert f == -1 and g == -1 and "sample_from_prior" in fe and "sample_from_prior" in ge
-    finally:
-        lib.sqair_destroy(h)
-    lib, h = _handle(hw=(256, 256), k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(hw=(256, 256), k_particles=2, n_steps_per_image=3) as (lib, h):
         f, fe, g, ge = _calls(lib, h, _carry(lib, h))
         assert f == -1 and g == -1 and "training is limited" in fe and "training is limited" in ge
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_trainer_argument_errors():

@@ -2,67 +2,42 @@
 exported and declared, sized in int64, and every refusal made before any HIP call (dummy device pointers are enough) -- and the
 argument errors of SqairStream(history=...)."""
 import ctypes as C
-import os
-import re
+import functools
 import types
 
 import pytest
 
 from sqair_amd import _capi
 from sqair_amd.carried import CarriedState
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
 from sqair_amd.stream import SqairStream
+from tests.abi_host import (BIG, DUMMY, constant, err as _err, estimate, fields as header_fields, functions, fwd_args, handle, paragraph,
+                            set_state as _state)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("sqair_history_bytes", "sqair_set_history", "sqair_history_trace")
-DUMMY = C.c_void_p(0x1000)     # never dereferenced: the calls below are refused first
 OTHER = C.c_void_p(0x2000)
-BIG = 1 << 50
 ALL, MAND = 31, 7
 
 
-def _handle(path=None, hw=(50, 50), **flags):
-    lib = _capi.lib(path)
-    cfg = make_config(make_flags(**flags), hw)
-    h = C.c_void_p()
-    assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-    return lib, h
-
-
-def _err(lib, h):
-    return lib.sqair_last_error(h).decode()
-
-
-def _state(lib, h, B):
-    assert lib.sqair_set_state(h, DUMMY, DUMMY, DUMMY, lib.sqair_state_bytes(h, B), B) == 0
-
-
 def test_symbols_are_exported_and_declared_and_the_abi_is_unchanged():
-    hdr = open(os.path.join(ROOT, "include", "sqair_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     lib = _capi.lib()
     for name in NEW:
         assert name in _capi.EXPORTED_SYMBOLS and hasattr(lib, name)
-        assert re.search(r"\b{}\s*\(".format(name), code), name
-    fields = re.search(r"typedef struct SqairTraceOutputs \{(.*?)\} SqairTraceOutputs;", code, re.S).group(1)
-    names = re.findall(r"(\w+);", fields)
-    assert names == [n for n, _ in _capi.SqairTraceOutputs._fields_]
+        assert name in functions(), name
+    assert [n for _, n in header_fields("SqairTraceOutputs")] == [n for n, _ in _capi.SqairTraceOutputs._fields_]
     for name, bit in _capi.HISTORY_FIELDS.items():
         macro = {"log_weights_per_timestep": "LOG_W"}.get(name, name.upper())
-        assert re.search(r"#define SQAIR_HIST_{}\s+{}u".format(macro, bit), hdr), name
-    assert re.search(r"#define SQAIR_HIST_MANDATORY\s+7u", hdr) and re.search(r"#define SQAIR_HIST_ALL\s+31u", hdr)
+        assert constant("SQAIR_HIST_" + macro) == bit, name
+    assert constant("SQAIR_HIST_MANDATORY") == 7 and constant("SQAIR_HIST_ALL") == 31
     assert sum(_capi.HISTORY_FIELDS[n] for n in _capi.HISTORY_MANDATORY) == MAND
-    assert _capi.ABI_VERSION == 2 and re.search(r"#define SQAIR_ABI_VERSION 2\b", hdr) and lib.sqair_abi_version() == 2
+    assert _capi.ABI_VERSION == 2 == constant("SQAIR_ABI_VERSION") and lib.sqair_abi_version() == 2
     # the history stays out of training on streams, and the header says so
-    assert "out of scope" in hdr[hdr.index("track history"):hdr.index("SQAIR_HIST_WHERE")]
+    assert "out of scope" in paragraph("track history", "SQAIR_HIST_WHERE")
 
 
 @pytest.mark.parametrize("which", ["product", "wide"])
 def test_history_bytes(which):
     path, flags = {"product": (None, dict()), "wide": (_capi.WIDE_LIB_PATH, dict(n_what=64))}[which]
-    lib, h = _handle(path, k_particles=5, n_steps_per_image=4, **flags)
-    try:
+    with handle(path, k_particles=5, n_steps_per_image=4, **flags) as (lib, h):
         nb = lambda L, T, B, f=ALL: lib.sqair_history_bytes(h, L, T, B, f)
         nw, N, K = int(flags.get("n_what", 50)), 4, 5
         # a slot holds at least the chosen fields in their own widths plus the map and the counters
@@ -80,13 +55,10 @@ def test_history_bytes(which):
         assert nb(0, 1, 1) == -1 and nb(1, 0, 1) == -1 and nb(1, 1, 0) == -1 and nb(-3, 1, 1) == -1
         assert nb(1, 1, 1, 3) == -1 and nb(1, 1, 1, MAND | 32) == -1 and nb(1, 1, 1, 0) == -1
         assert lib.sqair_history_bytes(None, 1, 1, 1, ALL) == -1
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_set_history_refusals_before_any_hip_call():
-    lib, h = _handle(k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(k_particles=2, n_steps_per_image=3) as (lib, h):
         B = 4
         need = lib.sqair_history_bytes(h, 8, 1, B, ALL)
         # no state set
@@ -103,18 +75,13 @@ def test_set_history_refusals_before_any_hip_call():
         assert lib.sqair_set_history(h, DUMMY, need, 8, ALL) == 0
         assert lib.sqair_set_history(h, DUMMY, need, 8, MAND) == 0
         assert lib.sqair_set_history(h, None, 0, 0, 0) == 0      # NULL ring: off
-    finally:
-        lib.sqair_destroy(h)
 
 
-def _fwd_args(h, B, T=1, **outs):
-    out = _capi.SqairOutputs(**{k: 0x1000 for k in outs.get("bind", ())})
-    return (h, DUMMY, DUMMY, DUMMY, DUMMY, T, B, 0, C.byref(out), DUMMY, BIG, DUMMY)
+_fwd_args = functools.partial(fwd_args, bind=())      # nothing bound but what a call names
 
 
 def test_pass_time_refusals_before_any_hip_call():
-    lib, h = _handle(k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(k_particles=2, n_steps_per_image=3) as (lib, h):
         B = 4
         _state(lib, h, B)
         need1 = lib.sqair_history_bytes(h, 8, 1, B, ALL)
@@ -141,20 +108,16 @@ def test_pass_time_refusals_before_any_hip_call():
         assert lib.sqair_set_history(h, DUMMY, BIG, 8, ALL) == 0
         _state(lib, h, B + 1)
         assert lib.sqair_history_trace(h, DUMMY, None, 1, C.byref(o), None) == -1 and "no history" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_a_refused_pass_leaves_the_handle_unchanged():
     """A pass the history would take and the estimate refuses must not fix the ring's frames per pass: the next pass, of the
     estimate's T, gets past every refusal to the pass's own argument check."""
-    lib, h = _handle(k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(k_particles=2, n_steps_per_image=3) as (lib, h):
         B = 4
         _state(lib, h, B)
         assert lib.sqair_set_history(h, DUMMY, BIG, 8, ALL) == 0
-        est = _capi.SqairLaneEstimate(iou_min=0.5, log_w=0x2000, best_row=0x3000)
-        assert lib.sqair_set_estimate(h, C.byref(est), 1, B) == 0
+        assert lib.sqair_set_estimate(h, C.byref(estimate()), 1, B) == 0
         every = [n for n, _ in _capi.SqairOutputs._fields_]
         assert lib.sqair_forward(*_fwd_args(h, B, T=3, bind=every)) == -1
         assert "sqair_set_estimate" in _err(lib, h) and "registered for passes of T = 1" in _err(lib, h)
@@ -162,24 +125,18 @@ def test_a_refused_pass_leaves_the_handle_unchanged():
         assert lib.sqair_forward(*(args[:9] + (None,) + args[10:])) == -1      # (a NULL workspace)
         assert _err(lib, h) == "sqair_forward: null argument or bad T/B", _err(lib, h)
         assert "ring" not in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_training_passes_stay_refused_with_a_history_set():
-    lib, h = _handle(k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(k_particles=2, n_steps_per_image=3) as (lib, h):
         B = 4
         _state(lib, h, B)
         assert lib.sqair_set_history(h, DUMMY, BIG, 8, ALL) == 0
         assert lib.sqair_forward_train(*_fwd_args(h, B)) == -1 and "training" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_trace_refusals_before_any_hip_call():
-    lib, h = _handle(k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(k_particles=2, n_steps_per_image=3) as (lib, h):
         B, L = 4, 8
         o = _capi.SqairTraceOutputs(T=1, max_tracks=4)
         call = lambda ring=DUMMY, lag=1, out=o: lib.sqair_history_trace(h, ring, None, lag, C.byref(out) if out is not None else None, None)
@@ -200,8 +157,6 @@ def test_trace_refusals_before_any_hip_call():
         # the track table wants 1 <= max_tracks <= 1024
         for m in (0, -1, 1025):
             assert call(out=_capi.SqairTraceOutputs(T=1, max_tracks=m, track_id=0x1000)) == -1 and "max_tracks" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_stream_argument_errors():

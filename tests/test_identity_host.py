@@ -3,82 +3,48 @@ exported and declared, the binding mirrors the header's struct, the header's par
 before any HIP call (dummy device pointers are enough), the identity goes off with the estimate and the state and takes score_ids with
 it -- and the argument errors of SqairStream(identity=...)."""
 import ctypes as C
+import functools
 import os
-import re
 
 import pytest
 
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
 from sqair_amd.stream import SqairStream
+from tests.abi_host import (DUMMY, LIBS, ROOT, constant, dummy, err as _err, estimate, fields as header_fields, fwd_args as _fwd_args,
+                            handle, paragraph, phrases, prototype, score, set_state as _state, stated_once)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DUMMY = C.c_void_p(0x1000)     # never dereferenced: the calls below are refused first
-BIG = 1 << 50
-LIBS = [None, _capi.WIDE_LIB_PATH]
 NEEDED = ("box", "presence", "obj_id")      # (best_row is the estimate's own requirement)
 REQUIRED = tuple(n for n in _capi.IDENT_MEMORY if n != "trk_what") + ("lane_id",)
 INF = float("inf")
 N = 3
-
-
-def _handle(path=None, hw=(50, 50), **flags):
-    lib = _capi.lib(path)
-    cfg = make_config(make_flags(**flags), hw)
-    h = C.c_void_p()
-    assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-    return lib, h
-
-
-def _err(lib, h):
-    return lib.sqair_last_error(h).decode()
-
-
-def _state(lib, h, B):
-    assert lib.sqair_set_state(h, DUMMY, DUMMY, DUMMY, lib.sqair_state_bytes(h, B), B) == 0
-
-
-def _est(iou_min=0.5, log_w=0x2000, best_row=0x3000, without=(), **kw):
-    kw.update({n: 0x4000 + 0x100 * i for i, n in enumerate(NEEDED + ("map_count", "what")) if n not in without})
-    return _capi.SqairLaneEstimate(iou_min=iou_min, log_w=log_w, best_row=best_row, **kw)
+_est = functools.partial(estimate, fields=NEEDED + ("map_count", "what"))
+_score = functools.partial(score, outputs=())
 
 
 def _ident(iou_min=0.3, reid_dist=4.0, reid_what=INF, M=6, max_age=10, without=(), outputs=_capi.IDENT_FIELDS):
-    kw = {n: 0x5000 + 0x100 * i for i, n in enumerate(_capi.IDENT_MEMORY) if n not in without}
-    kw.update({n: 0x7000 + 0x100 * i for i, n in enumerate(outputs) if n not in without})
-    return _capi.SqairLaneIdentity(iou_min=iou_min, reid_dist=reid_dist, reid_what=reid_what, M=M, max_age=max_age, **kw)
-
-
-def _score():
-    kw = {n: 0x8000 + 0x100 * i for i, n in enumerate(_capi.SCORE_INPUTS)}
-    return _capi.SqairLaneScore(iou_min=0.5, G=4, **kw)
-
-
-def _fwd_args(h, B, T=1, bind=("log_weights_per_timestep",)):
-    out = _capi.SqairOutputs(**{k: 0x1000 for k in bind})
-    return (h, DUMMY, DUMMY, DUMMY, DUMMY, T, B, 0, C.byref(out), DUMMY, BIG, DUMMY)
+    idt = dummy(_capi.SqairLaneIdentity, 0x5000, _capi.IDENT_MEMORY, without, iou_min=iou_min, reid_dist=reid_dist, reid_what=reid_what,
+                M=M, max_age=max_age)
+    for i, n in enumerate(outputs):
+        setattr(idt, n, None if n in without else 0x7000 + 0x100 * i)
+    return idt
 
 
 def test_the_symbols_are_exported_and_declared_and_the_abi_is_unchanged():
-    hdr = open(os.path.join(ROOT, "include", "sqair_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     names = ("sqair_set_identity", "sqair_lane_identity_test", "sqair_set_score_ids")
     for path in (None, _capi.WIDE_LIB_PATH, _capi.TIMELINE_LIB_PATH):
         lib = _capi.lib(path)
         assert all(hasattr(lib, n) for n in names) and lib.sqair_abi_version() == 2
     assert all(n in _capi.EXPORTED_SYMBOLS for n in names)
-    assert re.search(r"\bint\s+sqair_set_identity\s*\(\s*SqairHandle\*\s*h,\s*const SqairLaneIdentity\*\s*id\s*,\s*int T,\s*int B\)", code)
-    assert re.search(r"\bint\s+sqair_lane_identity_test\s*\(\s*SqairHandle\*\s*h,\s*const float\*\s*box,\s*const float\*\s*presence,"
-                     r"\s*const float\*\s*obj_id,\s*const float\*\s*what\s*,\s*const int32_t\*\s*best_row,\s*int T,\s*int B,"
-                     r"\s*const SqairLaneIdentity\*\s*id,\s*void\*\s*stream\)", code)
-    assert re.search(r"\bint\s+sqair_set_score_ids\s*\(\s*SqairHandle\*\s*h,\s*int lane_ids\s*\)", code)
-    assert _capi.ABI_VERSION == 2 and re.search(r"#define SQAIR_ABI_VERSION 2\b", hdr)
-    assert re.search(r"#define SQAIR_IDENT_MAX_TRACKS {}\b".format(_capi.IDENT_MAX_TRACKS), hdr) and _capi.IDENT_MAX_TRACKS == 16
-    assert re.search(r"#define SQAIR_IDENT_COUNTS {}\b".format(len(_capi.IDENT_COUNTS)), hdr) and len(_capi.IDENT_COUNTS) == 8
+    assert prototype("sqair_set_identity") == "int sqair_set_identity(SqairHandle* h, const SqairLaneIdentity* id, int T, int B)"
+    assert prototype("sqair_lane_identity_test") == ("int sqair_lane_identity_test(SqairHandle* h, const float* box, const float* presence, "
+                                                     "const float* obj_id, const float* what, const int32_t* best_row, int T, int B, "
+                                                     "const SqairLaneIdentity* id, void* stream)")
+    assert prototype("sqair_set_score_ids") == "int sqair_set_score_ids(SqairHandle* h, int lane_ids)"
+    assert _capi.ABI_VERSION == 2 == constant("SQAIR_ABI_VERSION")
+    assert constant("SQAIR_IDENT_MAX_TRACKS") == _capi.IDENT_MAX_TRACKS == 16
+    assert constant("SQAIR_IDENT_COUNTS") == len(_capi.IDENT_COUNTS) == 8
     # the binding's struct mirrors the header's, field for field and in order
-    body = re.search(r"typedef struct SqairLaneIdentity \{(.*?)\} SqairLaneIdentity;", code, flags=re.S).group(1)
-    fields = re.findall(r"((?:const )?(?:float|int32_t|int64_t|double)\*?)\s+(\w+);", body)
+    fields = header_fields("SqairLaneIdentity")
     assert [n for _, n in fields] == [n for n, _ in _capi.SqairLaneIdentity._fields_]
     assert [n for _, n in fields] == [n for n, _ in _capi.IDENT_SCALARS] + list(_capi.IDENT_MEMORY) + list(_capi.IDENT_FIELDS)
     assert [n for _, n in fields][:5] == ["iou_min", "reid_dist", "reid_what", "M", "max_age"]
@@ -92,41 +58,38 @@ def test_the_symbols_are_exported_and_declared_and_the_abi_is_unchanged():
     assert _capi.identity_memory_shapes(3, 6, 50) == dict(trk_id=(3, 6), trk_word=(3, 6), trk_age=(3, 6), trk_len=(3, 6), trk_box=(3, 6, 4),
                                                           trk_what=(3, 6, 50), next_id=(3,), counts=(3, 8))
     # the counters' order is the header's
-    doc = re.sub(r"\s*\n \*\s*", " ", hdr)
-    assert "counts [B,8] int64: frames, frames_invalid, objects (present slots seen), kept, bridged, reidentified, born" in doc
+    assert "counts [B,8] int64: frames, frames_invalid, objects (present slots seen), kept, bridged, reidentified, born" in paragraph()
     assert _capi.IDENT_COUNTS == ("frames", "frames_invalid", "objects", "kept", "bridged", "reidentified", "born", "ended")
 
 
 def test_the_header_states_the_semantics_once():
-    hdr = open(os.path.join(ROOT, "include", "sqair_hip.h")).read()
-    doc = hdr[hdr.index("lane identities: stable per-lane track ids"):hdr.index("typedef struct SqairLaneIdentity")]
-    doc = re.sub(r"\s*\n \*\s*", " ", doc)   # (the comment's line breaks)
-    for word in ("k_lane_identity", "one workgroup per lane", "after k_lane_estimate (and after k_lane_layers if on)", "BEFORE k_lane_score if on",
-                 "BEFORE the SMC resampler", "exactly one kernel node more", "unchanged bit for bit", "Training passes never run it",
-                 "does not read the records again", "trk_id (-1 = free", "never read", "the obj_id WORD", "next_id[b]",
-                 "Non-finite lane (best_row[t,b] == -1)", "frames_invalid += 1", "no ageing", "sq_box_iou(trk_box[e], box[t,b,j])",
-                 "ONE call of sq_assign_keep_greedy", "keep_id[e] = trk_word[e]", "col_id[j] = the obj_id word of slot j", "IoU >= iou_min",
-                 "ties to the smallest e, then the smallest j", "a NaN never passes", "how = 1 (kept)", "how = 2 (bridged",
-                 "only when reid_dist > 0", "(y + 0.5 h, x + 0.5 w)", "r = reid_dist * (trk_age[e] + 1)", "dc2 <= r * r", "dw <= reid_what",
-                 "fmaf(d, d, acc)", "/ n_what in fp32", "A NaN never passes", "minimal dw", "minimal dc2", "ties to the smallest e",
-                 "how = 3 (re-identified)", "Greedy in j on purpose", "trk_age = 0, trk_len += 1", "lane_id[t,b,j] = trk_id[e]",
-                 "track_len[t,b,j] = trk_len[e]", "the first free entry", "largest trk_age", "evicted (ended += 1)", "M >= N guarantees",
-                 "next_id[b] += 1", "how = 0 (born)", "exceeds max_age", "Coasted", "in place", "two passes of three frames leave the bits of one pass of six",
-                 "an id is never reused within a lane", "how and track_len are optional", "Refused", "M outside N..16", "reid_dist negative",
-                 "reid_what not in (0, +inf]", "max_age < 0", "any NaN among the scalars", "trk_what given while the estimate binds no what",
-                 "a pass of another T", "switch the identity off", "sqair_set_score_ids(h, 1)", "refused unless both the score and the identity are set",
-                 "puts it back to 0", "Out of scope", "lane tracks and lane forecasts", "optimal (Hungarian) assignment", "a motion model",
-                 "identities across lanes", "training passes"):
-        assert word in doc, word
-    assert hdr.count("lane identities: stable per-lane track ids") == 1
+    doc = paragraph("lane identities: stable per-lane track ids", "typedef struct SqairLaneIdentity")
+    phrases(doc, ("k_lane_identity", "one workgroup per lane", "after k_lane_estimate (and after k_lane_layers if on)",
+                  "BEFORE k_lane_score if on", "BEFORE the SMC resampler", "exactly one kernel node more", "unchanged bit for bit",
+                  "Training passes never run it", "does not read the records again", "trk_id (-1 = free", "never read", "the obj_id WORD",
+                  "next_id[b]", "Non-finite lane (best_row[t,b] == -1)", "frames_invalid += 1", "no ageing",
+                  "sq_box_iou(trk_box[e], box[t,b,j])", "ONE call of sq_assign_keep_greedy", "keep_id[e] = trk_word[e]",
+                  "col_id[j] = the obj_id word of slot j", "IoU >= iou_min", "ties to the smallest e, then the smallest j",
+                  "a NaN never passes", "how = 1 (kept)", "how = 2 (bridged", "only when reid_dist > 0", "(y + 0.5 h, x + 0.5 w)",
+                  "r = reid_dist * (trk_age[e] + 1)", "dc2 <= r * r", "dw <= reid_what", "fmaf(d, d, acc)", "/ n_what in fp32",
+                  "A NaN never passes", "minimal dw", "minimal dc2", "ties to the smallest e", "how = 3 (re-identified)",
+                  "Greedy in j on purpose", "trk_age = 0, trk_len += 1", "lane_id[t,b,j] = trk_id[e]", "track_len[t,b,j] = trk_len[e]",
+                  "the first free entry", "largest trk_age", "evicted (ended += 1)", "M >= N guarantees", "next_id[b] += 1",
+                  "how = 0 (born)", "exceeds max_age", "Coasted", "in place", "two passes of three frames leave the bits of one pass of six",
+                  "an id is never reused within a lane", "how and track_len are optional", "Refused", "M outside N..16", "reid_dist negative",
+                  "reid_what not in (0, +inf]", "max_age < 0", "any NaN among the scalars", "trk_what given while the estimate binds no what",
+                  "a pass of another T", "switch the identity off", "sqair_set_score_ids(h, 1)",
+                  "refused unless both the score and the identity are set", "puts it back to 0", "Out of scope",
+                  "lane tracks and lane forecasts", "optimal (Hungarian) assignment", "a motion model", "identities across lanes",
+                  "training passes"))
+    stated_once("lane identities: stable per-lane track ids")
     for name in ("DESIGN.md", "README.md"):      # they point to the header, they do not restate it
         assert "sqair_set_identity" in open(os.path.join(ROOT, name)).read(), name
 
 
 @pytest.mark.parametrize("path", LIBS)
 def test_set_identity_refusals_before_any_hip_call(path):
-    lib, h = _handle(path, k_particles=2, n_steps_per_image=N)
-    try:
+    with handle(path, k_particles=2, n_steps_per_image=N) as (lib, h):
         B, T = 4, 2
         on = lambda idt=None, t=T, b=B: lib.sqair_set_identity(h, C.byref(idt or _ident()), t, b)
         assert lib.sqair_set_identity(None, C.byref(_ident()), T, B) == -1
@@ -161,13 +124,10 @@ def test_set_identity_refusals_before_any_hip_call(path):
         for outs in (("lane_id",), ("lane_id", "how"), ("lane_id", "track_len")):      # how and track_len are optional
             assert on(_ident(outputs=outs)) == 0, outs
         assert lib.sqair_set_identity(h, None, 0, 0) == 0       # NULL: off
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_a_pass_of_another_t_is_refused_before_any_hip_call():
-    lib, h = _handle(k_particles=2, n_steps_per_image=N)
-    try:
+    with handle(k_particles=2, n_steps_per_image=N) as (lib, h):
         B = 4
         _state(lib, h, B)
         assert lib.sqair_set_estimate(h, C.byref(_est()), 2, B) == 0
@@ -177,15 +137,12 @@ def test_a_pass_of_another_t_is_refused_before_any_hip_call():
                 assert fn(*_fwd_args(h, B, T=T)) == -1
                 assert "T = 2" in _err(lib, h) and "T = {}".format(T) in _err(lib, h)
         assert lib.sqair_forward_train(*_fwd_args(h, B, T=2)) == -1 and "carried state" in _err(lib, h)   # training never runs it
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_the_estimate_or_the_state_going_off_takes_the_identity_with_it():
     """The identity can only be set while an estimate with its fields is: after anything that switches it off, setting score_ids is
     refused (that needs the identity) until it is set again."""
-    lib, h = _handle(k_particles=2, n_steps_per_image=N)
-    try:
+    with handle(k_particles=2, n_steps_per_image=N) as (lib, h):
         B = 4
         on = lambda T=2, b=B, **kw: lib.sqair_set_identity(h, C.byref(_ident(**kw)), T, b)
         score = lambda T=2: lib.sqair_set_score(h, C.byref(_score()), T, B)
@@ -217,13 +174,10 @@ def test_the_estimate_or_the_state_going_off_takes_the_identity_with_it():
         assert lib.sqair_set_estimate(h, C.byref(_est()), 2, B) == 0 and on() == 0
         _state(lib, h, B + 1)                                                 # another B
         assert on(2, B + 1) == -1 and "needs an estimate" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_score_ids_needs_both_and_goes_back_with_either():
-    lib, h = _handle(k_particles=2, n_steps_per_image=N)
-    try:
+    with handle(k_particles=2, n_steps_per_image=N) as (lib, h):
         B, T = 4, 2
         ids = lambda v=1: lib.sqair_set_score_ids(h, v)
         refused = lambda: ids(1) == -1 and "needs both a score" in _err(lib, h)
@@ -238,14 +192,11 @@ def test_score_ids_needs_both_and_goes_back_with_either():
         assert lib.sqair_set_identity(h, None, 0, 0) == 0 and refused()                         # the identity off
         assert lib.sqair_set_identity(h, C.byref(_ident()), T, B) == 0 and ids(1) == 0
         assert lib.sqair_set_score(h, None, 0, 0) == 0 and refused()                            # the score off
-    finally:
-        lib.sqair_destroy(h)
 
 
 @pytest.mark.parametrize("path", LIBS)
 def test_kernel_entry_point_refusals_before_any_hip_call(path):
-    lib, h = _handle(path, k_particles=2, n_steps_per_image=N)
-    try:
+    with handle(path, k_particles=2, n_steps_per_image=N) as (lib, h):
         good = dict(box=DUMMY, presence=DUMMY, obj_id=DUMMY, what=DUMMY, best_row=DUMMY, T=1, B=3)
         order = ("box", "presence", "obj_id", "what", "best_row", "T", "B")
         call = lambda idt, **kw: lib.sqair_lane_identity_test(h, *[dict(good, **kw)[k] for k in order],
@@ -263,8 +214,6 @@ def test_kernel_entry_point_refusals_before_any_hip_call(path):
         assert call(_ident(reid_dist=float("nan"))) == -1 and call(_ident(reid_what=float("nan"))) == -1
         for missing in REQUIRED:
             assert call(_ident(without=(missing,))) == -1 and "must not be NULL" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_stream_argument_errors():

@@ -14,44 +14,32 @@ calls, ``how`` and ``track_len`` are optional, and every case exercises all five
 measured figures are written to identity_parity.json there (the copy under profiles/ is such a file); without it nothing is written."""
 import ctypes as C
 import functools
-import json
-import os
 
 import numpy as np
 import pytest
 import torch
 
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
 from tests import identity_cases as IC
 from tests import identity_ref as IR
+from tests.abi_host import open_handle
+from tests.kernel_unit import merge_parity
 
 pytestmark = pytest.mark.gpu
 
-PARITY_DIR_ENV = "SQAIR_PARITY_DIR"
 INPUTS = ("box", "presence", "obj_id", "what", "best_row")
 INT_MEM = ("trk_word", "trk_age", "trk_len")
+NOTE = ("per case of tests/test_identity_kernel.py: the measured error of the fp32 restatement of IoU, dc2 and dw against "
+        "float64 times four (the fragility band), the lanes left out as fragile and the events counted over the lanes "
+        "compared; outputs, memory and counts are compared exactly")
 
 
 def _record(case, **figures):
-    where = os.environ.get(PARITY_DIR_ENV)
-    if not where:
-        return
-    path = os.path.join(where, "identity_parity.json")
-    try:
-        os.makedirs(where, exist_ok=True)
-        data = json.load(open(path)) if os.path.exists(path) else {
-            "note": "per case of tests/test_identity_kernel.py: the measured error of the fp32 restatement of IoU, dc2 and dw against "
-                    "float64 times four (the fragility band), the lanes left out as fragile and the events counted over the lanes "
-                    "compared; outputs, memory and counts are compared exactly",
-            "cases": {}}
+    def update(data):
         data["build_id"] = _capi.build_id()
         data["device"] = torch.cuda.get_device_name(0)
         data["cases"][case] = figures
-        json.dump(data, open(path, "w"), indent=1, sort_keys=True)
-    except OSError:
-        pass
+    merge_parity("identity_parity.json", lambda: {"note": NOTE, "cases": {}}, update)
 
 
 _handles = {}
@@ -60,11 +48,7 @@ _handles = {}
 def _handle(c):
     key = (c.wide, c.N, c.nw)
     if key not in _handles:
-        lib = _capi.lib(_capi.WIDE_LIB_PATH if c.wide else None)
-        cfg = make_config(make_flags(k_particles=2, n_steps_per_image=c.N, n_what=c.nw), IC.HW)
-        h = C.c_void_p()
-        assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-        _handles[key] = (lib, h)
+        _handles[key] = open_handle(_capi.WIDE_LIB_PATH if c.wide else None, IC.HW, k_particles=2, n_steps_per_image=c.N, n_what=c.nw)
     return _handles[key]
 
 

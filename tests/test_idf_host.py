@@ -2,54 +2,23 @@
 declared, the binding mirrors the header's struct, the header's paragraph carries the semantics, every refusal is made before any HIP
 call (dummy device pointers are enough), the IDF goes off with the score -- and the argument errors of SqairStream(score_idf=...)."""
 import ctypes as C
+import functools
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
 from sqair_amd.stream import SqairStream
+from tests.abi_host import (DUMMY, LIBS, ROOT, c_layout, constant, dummy, err as _err, estimate, fields as header_fields, fwd_args, handle,
+                            paragraph, phrases, prototype, score as _score, set_state as _state, stated_once)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DUMMY = C.c_void_p(0x1000)     # never dereferenced: the calls below are refused first
-LIBS = [None, _capi.WIDE_LIB_PATH]
 NEEDED = ("box", "presence", "obj_id", "map_count")
 IDF_POINTERS = _capi.IDF_TABLE + ("totals",)
-
-
-def _handle(path=None, hw=(50, 50), **flags):
-    lib = _capi.lib(path)
-    cfg = make_config(make_flags(**flags), hw)
-    h = C.c_void_p()
-    assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-    return lib, h
-
-
-def _err(lib, h):
-    return lib.sqair_last_error(h).decode()
-
-
-def _state(lib, h, B):
-    assert lib.sqair_set_state(h, DUMMY, DUMMY, DUMMY, lib.sqair_state_bytes(h, B), B) == 0
-
-
-def _est(without=()):
-    kw = {n: 0x4000 + 0x100 * i for i, n in enumerate(NEEDED) if n not in without}
-    return _capi.SqairLaneEstimate(iou_min=0.5, log_w=0x2000, best_row=0x3000, **kw)
-
-
-def _score(iou_min=0.5, G=4, without=(), outputs=_capi.SCORE_FIELDS):
-    kw = {n: 0x5000 + 0x100 * i for i, n in enumerate(_capi.SCORE_INPUTS) if n not in without}
-    kw.update({n: 0x7000 + 0x100 * i for i, n in enumerate(outputs)})
-    return _capi.SqairLaneScore(iou_min=iou_min, G=G, **kw)
+_est = functools.partial(estimate, fields=NEEDED)
 
 
 def _idf(P=8, without=()):
-    return _capi.SqairLaneIdf(P=P, **{n: 0x9000 + 0x100 * i for i, n in enumerate(IDF_POINTERS) if n not in without})
+    return dummy(_capi.SqairLaneIdf, 0x9000, IDF_POINTERS, without, P=P)
 
 
 def _ready(lib, h, B=4, T=2, **score):
@@ -59,79 +28,64 @@ def _ready(lib, h, B=4, T=2, **score):
 
 
 def test_the_symbols_are_exported_and_declared_and_the_abi_is_unchanged():
-    hdr = open(os.path.join(ROOT, "include", "sqair_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     names = ("sqair_set_idf", "sqair_lane_idf_test", "sqair_lane_idf_solve")
     for path in (None, _capi.WIDE_LIB_PATH, _capi.TIMELINE_LIB_PATH):
         lib = _capi.lib(path)
         assert all(hasattr(lib, n) for n in names) and lib.sqair_abi_version() == 2
     assert all(n in _capi.EXPORTED_SYMBOLS for n in names)
-    assert re.search(r"\bint\s+sqair_set_idf\s*\(\s*SqairHandle\*\s*h,\s*const SqairLaneIdf\*\s*idf\s*,\s*int T,\s*int B\)", code)
-    assert re.search(r"\bint\s+sqair_lane_idf_test\s*\(\s*SqairHandle\*\s*h,\s*const float\*\s*box,\s*const float\*\s*presence,"
-                     r"\s*const float\*\s*ids,\s*const int32_t\*\s*map_count,\s*int T,\s*int B,\s*const SqairLaneScore\*\s*score,"
-                     r"\s*const SqairLaneIdf\*\s*idf,\s*void\*\s*stream\)", code)
-    assert re.search(r"\bint\s+sqair_lane_idf_solve\s*\(\s*SqairHandle\*\s*h,\s*const SqairLaneIdf\*\s*idf,\s*int G,\s*int B,"
-                     r"\s*const int32_t\*\s*close\s*,\s*int64_t\*\s*open\s*,\s*int32_t\*\s*assign\s*,\s*void\*\s*stream\)", code)
-    assert _capi.ABI_VERSION == 2 and re.search(r"#define SQAIR_ABI_VERSION 2\b", hdr)
-    assert re.search(r"#define SQAIR_IDF_MAX_IDS {}\b".format(_capi.IDF_MAX_IDS), hdr) and _capi.IDF_MAX_IDS == 64
-    assert re.search(r"#define SQAIR_IDF_TOTALS {}\b".format(len(_capi.IDF_TOTALS)), hdr) and len(_capi.IDF_TOTALS) == 12
+    assert prototype("sqair_set_idf") == "int sqair_set_idf(SqairHandle* h, const SqairLaneIdf* idf, int T, int B)"
+    assert prototype("sqair_lane_idf_test") == ("int sqair_lane_idf_test(SqairHandle* h, const float* box, const float* presence, "
+                                                "const float* ids, const int32_t* map_count, int T, int B, const SqairLaneScore* score, "
+                                                "const SqairLaneIdf* idf, void* stream)")
+    assert prototype("sqair_lane_idf_solve") == ("int sqair_lane_idf_solve(SqairHandle* h, const SqairLaneIdf* idf, int G, int B, "
+                                                 "const int32_t* close, int64_t* open, int32_t* assign, void* stream)")
+    assert _capi.ABI_VERSION == 2 == constant("SQAIR_ABI_VERSION")
+    assert constant("SQAIR_IDF_MAX_IDS") == _capi.IDF_MAX_IDS == 64
+    assert constant("SQAIR_IDF_TOTALS") == len(_capi.IDF_TOTALS) == 12
     # the binding's struct mirrors the header's, field for field and in order
-    body = re.search(r"typedef struct SqairLaneIdf \{(.*?)\} SqairLaneIdf;", code, flags=re.S).group(1)
-    fields = re.findall(r"((?:const )?(?:float|int32_t|int64_t|double)\*?)\s+(\w+);", body)
+    fields = header_fields("SqairLaneIdf")
     assert [n for _, n in fields] == [n for n, _ in _capi.SqairLaneIdf._fields_] == ["P"] + list(IDF_POINTERS)
     assert [ty for ty, _ in fields] == ["int32_t"] + ["int32_t*"] * len(_capi.IDF_TABLE) + ["int64_t*"]
     assert C.sizeof(_capi.SqairLaneIdf) == 8 + 8 * 10
     assert _capi.idf_shapes(3, 4, 5) == dict(col_id=(3, 5), overlap=(3, 4, 5), row_frames=(3, 4), col_frames=(3, 5), extra_frames=(3,),
                                             matched=(3, 4), frag=(3, 4), trk_state=(3, 4), frames=(3,), totals=(3, 12))
     # the totals' order is the header's
-    doc = re.sub(r"\s*\n \*\s*", " ", hdr)
-    assert "in the order of totals: clips (1 for a clip with frames > 0), frames, trajectories, idtp, idfn, idfp, mt, pt, ml, frag" in doc
+    assert ("in the order of totals: clips (1 for a clip with frames > 0), frames, trajectories, idtp, idfn, idfp, mt, pt, ml, frag"
+            in paragraph())
     assert _capi.IDF_TOTALS == ("clips", "frames", "trajectories", "idtp", "idfn", "idfp", "mt", "pt", "ml", "frag", "ids", "overflow_ids")
 
 
 def test_the_struct_has_the_compilers_size(tmp_path):
-    """sizeof in C is what ctypes lays out (the program pattern of tests/test_capi_host.py)."""
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include "sqair_hip.h"\nint main(void) { printf("%zu %zu\\n", sizeof(SqairLaneIdf), '
-                   'sizeof(SqairLaneScore)); return 0; }\n')
-    exe = tmp_path / "size"
-    gcc = shutil.which("gcc")
-    assert gcc, "gcc is part of the image"
-    subprocess.check_call([gcc, "-std=c99", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"), str(src),
-                           "-o", str(exe)])
-    got = subprocess.check_output([str(exe)]).decode().split()
-    assert [int(v) for v in got] == [C.sizeof(_capi.SqairLaneIdf), C.sizeof(_capi.SqairLaneScore)]
+    """sizeof in C is what ctypes lays out."""
+    got = c_layout(tmp_path, dict(SqairLaneIdf=(), SqairLaneScore=()))
+    assert [got["SqairLaneIdf"][0], got["SqairLaneScore"][0]] == [C.sizeof(_capi.SqairLaneIdf), C.sizeof(_capi.SqairLaneScore)]
 
 
 def test_the_header_states_the_semantics_once():
-    hdr = open(os.path.join(ROOT, "include", "sqair_hip.h")).read()
-    doc = hdr[hdr.index("IDF1 scoring: does an identity stay on an object"):hdr.index("typedef struct SqairLaneIdf")]
-    doc = re.sub(r"\s*\n \*\s*", " ", doc)   # (the comment's line breaks)
-    for word in ("k_lane_idf", "one workgroup per lane", "after k_lane_score and BEFORE the SMC resampler", "exactly one kernel node more",
-                 "unchanged bit for bit", "Training passes, and a capture's eager pre-pass without effects, never run it",
-                 "k_lane_idf_solve", "one wavefront per lane", "integer arithmetic", "A CLIP of lane b", "Truth identity IS the slot g",
-                 "the obj_id word, or lane_id when sqair_set_score_ids(h, 1) is in force", "truth_match, which must be bound",
-                 "no atomics", "P in 1..64", "-1 = free", "never read", "bit 0 = tracked at g's last present frame", "map_count != -1",
-                 "takes the first free column", "UNKEYED", "the later j counts as unkeyed", "totals.overflow_ids", "EVERY pair",
-                 "sq_box_iou", "not only the score's matches", "frag[g] += 1", "maximum over one-to-one assignments", "dummy-node formulation",
-                 "IDFN = sum_g row_frames - IDTP", "IDFP = sum_p col_frames (used columns) + extra_frames - IDTP", "5 m >= 4 n", "5 m < n",
-                 "optimal assignments tie", "sq_assign_optimal_i32", "weights below 2^30", "frees the table", "is refused (return -1", "no score set",
-                 "binds no truth_match", "P outside 1..64", "another G", "Out of scope", "HOTA", "more than 64 predicted ids per clip"):
-        assert word in doc, word
-    assert hdr.count("IDF1 scoring: does an identity stay on an object") == 1
+    doc = paragraph("IDF1 scoring: does an identity stay on an object", "typedef struct SqairLaneIdf")
+    phrases(doc, ("k_lane_idf", "one workgroup per lane", "after k_lane_score and BEFORE the SMC resampler", "exactly one kernel node more",
+                  "unchanged bit for bit", "Training passes, and a capture's eager pre-pass without effects, never run it",
+                  "k_lane_idf_solve", "one wavefront per lane", "integer arithmetic", "A CLIP of lane b", "Truth identity IS the slot g",
+                  "the obj_id word, or lane_id when sqair_set_score_ids(h, 1) is in force", "truth_match, which must be bound",
+                  "no atomics", "P in 1..64", "-1 = free", "never read", "bit 0 = tracked at g's last present frame", "map_count != -1",
+                  "takes the first free column", "UNKEYED", "the later j counts as unkeyed", "totals.overflow_ids", "EVERY pair",
+                  "sq_box_iou", "not only the score's matches", "frag[g] += 1", "maximum over one-to-one assignments", "dummy-node formulation",
+                  "IDFN = sum_g row_frames - IDTP", "IDFP = sum_p col_frames (used columns) + extra_frames - IDTP", "5 m >= 4 n", "5 m < n",
+                  "optimal assignments tie", "sq_assign_optimal_i32", "weights below 2^30", "frees the table", "is refused (return -1",
+                  "no score set", "binds no truth_match", "P outside 1..64", "another G", "Out of scope", "HOTA",
+                  "more than 64 predicted ids per clip"))
+    stated_once("IDF1 scoring: does an identity stay on an object")
     for name in ("DESIGN.md", "README.md"):      # they point to the header, they do not restate it
         assert "sqair_set_idf" in open(os.path.join(ROOT, name)).read(), name
     # the two places that recorded the gap point here now
-    score = re.sub(r"\s*\n \*\s*", " ", hdr[hdr.index("stream scoring: CLEAR-MOT events"):hdr.index("typedef struct SqairLaneScore")])
-    assert "are sqair_set_idf's, below" in score
+    assert "are sqair_set_idf's, below" in paragraph("stream scoring: CLEAR-MOT events", "typedef struct SqairLaneScore")
     lane_h = open(os.path.join(ROOT, "sqair_amd", "csrc", "sqair_lane.h")).read()
     assert "sq_assign_optimal_i32" in lane_h and "sq_assign_keep_greedy" in lane_h
 
 
 @pytest.mark.parametrize("path", LIBS)
 def test_set_idf_refusals_before_any_hip_call(path):
-    lib, h = _handle(path, k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(path, k_particles=2, n_steps_per_image=3) as (lib, h):
         B, T = 4, 2
         on = lambda idf=None, t=T, b=B: lib.sqair_set_idf(h, C.byref(idf or _idf()), t, b)
         assert lib.sqair_set_idf(None, C.byref(_idf()), T, B) == -1
@@ -153,16 +107,13 @@ def test_set_idf_refusals_before_any_hip_call(path):
         for P in (1, 32, 64):
             assert on(_idf(P=P)) == 0
         assert lib.sqair_set_idf(h, None, 0, 0) == 0       # NULL: off
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_the_score_going_off_takes_the_idf_with_it():
     """The IDF can only be set while a score with truth_match is.  What switches it off cannot be seen from outside but for the node
     it launches (tests/test_idf_stream.py counts those); here: after everything that switches the score off, setting the IDF again is
     refused until the score is back, and a score re-registered without truth_match refuses it too."""
-    lib, h = _handle(k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(k_particles=2, n_steps_per_image=3) as (lib, h):
         B = 4
         on = lambda T=2, b=B: lib.sqair_set_idf(h, C.byref(_idf()), T, b)
         _ready(lib, h, B)
@@ -190,27 +141,20 @@ def test_the_score_going_off_takes_the_idf_with_it():
         assert on() == 0
         _state(lib, h, B + 1)                                                   # another B
         assert on(2, B + 1) == -1 and "needs a score" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_training_calls_never_run_the_idf():
-    lib, h = _handle(k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(k_particles=2, n_steps_per_image=3) as (lib, h):
         B = 4
         _ready(lib, h, B)
         assert lib.sqair_set_idf(h, C.byref(_idf()), 2, B) == 0
-        out = _capi.SqairOutputs(log_weights_per_timestep=0x1000)
-        assert lib.sqair_forward_train(h, DUMMY, DUMMY, DUMMY, DUMMY, 2, B, 0, C.byref(out), DUMMY, 1 << 50, DUMMY) == -1
+        assert lib.sqair_forward_train(*fwd_args(h, B, T=2)) == -1
         assert "carried state" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 @pytest.mark.parametrize("path", LIBS)
 def test_kernel_entry_point_refusals_before_any_hip_call(path):
-    lib, h = _handle(path, k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(path, k_particles=2, n_steps_per_image=3) as (lib, h):
         good = dict(box=DUMMY, presence=DUMMY, ids=DUMMY, map_count=DUMMY, T=1, B=3)
         order = ("box", "presence", "ids", "map_count", "T", "B")
         ref = lambda x: C.byref(x) if x is not None else None
@@ -241,8 +185,6 @@ def test_kernel_entry_point_refusals_before_any_hip_call(path):
             assert solve(_idf(P=bad)) == -1 and "1..64" in _err(lib, h)
         for missing in IDF_POINTERS:
             assert solve(_idf(without=(missing,))) == -1 and missing in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_stream_argument_errors():

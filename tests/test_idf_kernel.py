@@ -16,11 +16,10 @@ import pytest
 import torch
 
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
 from tests import idf_cases as IC
 from tests import idf_ref as R
 from tests import score_ref as SR
+from tests.abi_host import open_handle
 from tests.test_idf_solve_kernel import record, run_solve, struct, to_device
 
 pytestmark = pytest.mark.gpu
@@ -33,11 +32,7 @@ _handles = {}
 def _handle(c):
     key = (c.wide, c.N)
     if key not in _handles:
-        lib = _capi.lib(_capi.WIDE_LIB_PATH if c.wide else None)
-        cfg = make_config(make_flags(k_particles=2, n_steps_per_image=c.N, n_what=6), HW)
-        h = C.c_void_p()
-        assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-        _handles[key] = (lib, h)
+        _handles[key] = open_handle(_capi.WIDE_LIB_PATH if c.wide else None, HW, k_particles=2, n_steps_per_image=c.N, n_what=6)
     return _handles[key]
 
 

@@ -8,17 +8,15 @@ only those, totals after two closes are the sum, ``open`` and ``assign`` are opt
 SQAIR_PARITY_DIR set the cases are recorded in idf_parity.json there."""
 import ctypes as C
 import functools
-import json
-import os
 
 import numpy as np
 import pytest
 import torch
 
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
 from tests import idf_ref as R
+from tests.abi_host import open_handle
+from tests.kernel_unit import merge_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -26,27 +24,17 @@ B = 256
 SHAPES = [(1, 1), (4, 8), (5, 6), (16, 64), (16, 4), (3, 64), (7, 33)]
 REGIMES = ("ties_0_3", "up_to_2^20", "mostly_zero", "all_zero", "permuted_diagonal", "free_columns")
 LIBS = {"product": None, "wide": _capi.WIDE_LIB_PATH}
-PARITY_DIR_ENV = "SQAIR_PARITY_DIR"
+NOTE = ("per case of tests/test_idf_solve_kernel.py (solve) and tests/test_idf_kernel.py (accumulate): the lanes compared, the "
+        "lanes left out as fragile and the events counted; every compared word is an integer and is compared exactly")
 
 
 def record(section, case, **figures):
     """One case's figures into idf_parity.json under SQAIR_PARITY_DIR (tests/test_idf_kernel.py writes the same file)."""
-    where = os.environ.get(PARITY_DIR_ENV)
-    if not where:
-        return
-    path = os.path.join(where, "idf_parity.json")
-    try:
-        os.makedirs(where, exist_ok=True)
-        data = json.load(open(path)) if os.path.exists(path) else {
-            "note": "per case of tests/test_idf_solve_kernel.py (solve) and tests/test_idf_kernel.py (accumulate): the lanes compared, the "
-                    "lanes left out as fragile and the events counted; every compared word is an integer and is compared exactly",
-            "solve": {}, "accumulate": {}}
+    def update(data):
         data["build_id"] = _capi.build_id()
         data["device"] = torch.cuda.get_device_name(0)
         data[section][case] = figures
-        json.dump(data, open(path, "w"), indent=1, sort_keys=True)
-    except OSError:
-        pass
+    merge_parity("idf_parity.json", lambda: {"note": NOTE, "solve": {}, "accumulate": {}}, update)
 
 
 _handles = {}
@@ -54,11 +42,7 @@ _handles = {}
 
 def handle(lib_name):
     if lib_name not in _handles:
-        lib = _capi.lib(LIBS[lib_name])
-        cfg = make_config(make_flags(k_particles=2, n_steps_per_image=4, n_what=6), (50, 50))
-        h = C.c_void_p()
-        assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-        _handles[lib_name] = (lib, h)
+        _handles[lib_name] = open_handle(LIBS[lib_name], k_particles=2, n_steps_per_image=4, n_what=6)
     return _handles[lib_name]
 
 

@@ -3,40 +3,13 @@ the binding mirrors the header's struct, the header's paragraph carries the sema
 (dummy device pointers are enough), the layers go off with the estimate and the state -- and the argument errors of
 SqairStream(estimate_layers=...)."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
 from sqair_amd.stream import SqairStream
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DUMMY = C.c_void_p(0x1000)     # never dereferenced: the calls below are refused first
-BIG = 1 << 50
-LIBS = [None, _capi.WIDE_LIB_PATH]
-
-
-def _handle(path=None, hw=(50, 50), **flags):
-    lib = _capi.lib(path)
-    cfg = make_config(make_flags(**flags), hw)
-    h = C.c_void_p()
-    assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-    return lib, h
-
-
-def _err(lib, h):
-    return lib.sqair_last_error(h).decode()
-
-
-def _state(lib, h, B):
-    assert lib.sqair_set_state(h, DUMMY, DUMMY, DUMMY, lib.sqair_state_bytes(h, B), B) == 0
-
-
-def _est(iou_min=0.5, log_w=0x2000, best_row=0x3000, **kw):
-    return _capi.SqairLaneEstimate(iou_min=iou_min, log_w=log_w, best_row=best_row, **kw)
+from tests.abi_host import (DUMMY, LIBS, constant, err as _err, estimate as _est, fields as header_fields, fwd_args as _fwd_args, handle,
+                            paragraph, phrases, prototype, set_state as _state, stated_once)
 
 
 def _lay(cover_min=0.5, **kw):
@@ -45,26 +18,18 @@ def _lay(cover_min=0.5, **kw):
     return _capi.SqairLaneLayers(cover_min=cover_min, **kw)
 
 
-def _fwd_args(h, B, T=1, bind=("log_weights_per_timestep",)):
-    out = _capi.SqairOutputs(**{k: 0x1000 for k in bind})
-    return (h, DUMMY, DUMMY, DUMMY, DUMMY, T, B, 0, C.byref(out), DUMMY, BIG, DUMMY)
-
-
 def test_the_symbols_are_exported_and_declared_and_the_abi_is_unchanged():
-    hdr = open(os.path.join(ROOT, "include", "sqair_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     for path in (None, _capi.WIDE_LIB_PATH, _capi.TIMELINE_LIB_PATH):
         lib = _capi.lib(path)
         assert hasattr(lib, "sqair_set_layers") and hasattr(lib, "sqair_lane_layers_test") and lib.sqair_abi_version() == 2
     assert "sqair_set_layers" in _capi.EXPORTED_SYMBOLS and "sqair_lane_layers_test" in _capi.EXPORTED_SYMBOLS
-    assert re.search(r"\bint\s+sqair_set_layers\s*\(\s*SqairHandle\*\s*h,\s*const SqairLaneLayers\*\s*lay\s*,\s*int T,\s*int B\)", code)
-    assert re.search(r"\bint\s+sqair_lane_layers_test\s*\(\s*SqairHandle\*\s*h,\s*const float\*\s*glimpse,\s*const float\*\s*where,"
-                     r"\s*const float\*\s*presence,\s*const float\*\s*lw,\s*const float\*\s*log_w,\s*float iou_min,\s*int T,\s*int B,"
-                     r"\s*int K,\s*const SqairLaneLayers\*\s*lay,\s*void\*\s*stream\)", code)
-    assert _capi.ABI_VERSION == 2 and re.search(r"#define SQAIR_ABI_VERSION 2\b", hdr)
+    assert prototype("sqair_set_layers") == "int sqair_set_layers(SqairHandle* h, const SqairLaneLayers* lay, int T, int B)"
+    assert prototype("sqair_lane_layers_test") == ("int sqair_lane_layers_test(SqairHandle* h, const float* glimpse, const float* where, "
+                                                   "const float* presence, const float* lw, const float* log_w, float iou_min, int T, int B, "
+                                                   "int K, const SqairLaneLayers* lay, void* stream)")
+    assert _capi.ABI_VERSION == 2 == constant("SQAIR_ABI_VERSION")
     # the binding's struct mirrors the header's, field for field and in order
-    body = re.search(r"typedef struct SqairLaneLayers \{(.*?)\} SqairLaneLayers;", code, flags=re.S).group(1)
-    fields = re.findall(r"(float\*|int32_t\*|float)\s+(\w+);", body)
+    fields = header_fields("SqairLaneLayers")
     assert [n for _, n in fields] == [n for n, _ in _capi.SqairLaneLayers._fields_]
     assert [n for ty, n in fields if ty == "int32_t*"] == list(_capi.LAYERS_INT_FIELDS)
     assert [n for _, n in fields][1:] == list(_capi.LAYERS_FIELDS)
@@ -72,24 +37,20 @@ def test_the_symbols_are_exported_and_declared_and_the_abi_is_unchanged():
 
 
 def test_the_header_states_the_semantics_once():
-    hdr = open(os.path.join(ROOT, "include", "sqair_hip.h")).read()
-    doc = hdr[hdr.index("object layers: per-object appearance"):hdr.index("typedef struct SqairLaneLayers")]
-    doc = re.sub(r"\s*\n \*\s*", " ", doc)   # (the comment's line breaks)
-    for word in ("k_lane_layers", "directly after k_lane_estimate", "BEFORE the SMC resampler", "exactly one kernel node more",
-                 "Training passes never run it", "V(r, m) = p * (inverse spatial transformer of g)", "a glimpse of ones",
-                 "sq_canvas_coord, sq_canvas_tap", "points 1, 2, 4 and 5", "iou_min and log_w", "match[t,b,k,j] (int32)",
-                 "the estimate's support, summed in the same order", "index order", "no float atomics", "Absent j: zeros",
-                 "a convex combination", "the first present j of maximal cover", "cover_min", "A NaN never wins", "Non-finite lanes",
-                 "match and owner -1", "Coasted", "At K = 1", "sigmoid(-10 + 20 sum_j cover[j])", "owner needs no cover bound",
-                 "Refused", "Out of scope"):
-        assert word in doc, word
-    assert hdr.count("object layers: per-object appearance") == 1
+    doc = paragraph("object layers: per-object appearance", "typedef struct SqairLaneLayers")
+    phrases(doc, ("k_lane_layers", "directly after k_lane_estimate", "BEFORE the SMC resampler", "exactly one kernel node more",
+                  "Training passes never run it", "V(r, m) = p * (inverse spatial transformer of g)", "a glimpse of ones",
+                  "sq_canvas_coord, sq_canvas_tap", "points 1, 2, 4 and 5", "iou_min and log_w", "match[t,b,k,j] (int32)",
+                  "the estimate's support, summed in the same order", "index order", "no float atomics", "Absent j: zeros",
+                  "a convex combination", "the first present j of maximal cover", "cover_min", "A NaN never wins", "Non-finite lanes",
+                  "match and owner -1", "Coasted", "At K = 1", "sigmoid(-10 + 20 sum_j cover[j])", "owner needs no cover bound",
+                  "Refused", "Out of scope"))
+    stated_once("object layers: per-object appearance")
 
 
 @pytest.mark.parametrize("path", LIBS)
 def test_set_layers_refusals_before_any_hip_call(path):
-    lib, h = _handle(path, k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(path, k_particles=2, n_steps_per_image=3) as (lib, h):
         B, T = 4, 2
         assert lib.sqair_set_layers(None, C.byref(_lay()), T, B) == -1
         assert lib.sqair_set_layers(h, C.byref(_lay()), T, B) == -1 and "sqair_set_estimate" in _err(lib, h)       # no state, no estimate
@@ -109,13 +70,10 @@ def test_set_layers_refusals_before_any_hip_call(path):
         for one in ("match", "layer", "cover", "owner"):      # every pointer optional
             assert lib.sqair_set_layers(h, C.byref(_lay(**{one: 0x5000})), T, B) == 0, one
         assert lib.sqair_set_layers(h, None, 0, 0) == 0       # NULL: off
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_a_pass_of_another_t_is_refused_before_any_hip_call():
-    lib, h = _handle(k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(k_particles=2, n_steps_per_image=3) as (lib, h):
         B = 4
         _state(lib, h, B)
         assert lib.sqair_set_estimate(h, C.byref(_est()), 2, B) == 0
@@ -124,15 +82,12 @@ def test_a_pass_of_another_t_is_refused_before_any_hip_call():
             for T in (1, 3):
                 assert fn(*_fwd_args(h, B, T=T)) == -1
                 assert "T = 2" in _err(lib, h) and "T = {}".format(T) in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_the_estimate_or_the_state_going_off_takes_the_layers_with_it():
     """The layers can only be set while an estimate is: after anything that switches them off, setting them again is refused until
     the estimate is back -- and a NULL estimate, another T of the estimate, the state off and another B all switch them off."""
-    lib, h = _handle(k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(k_particles=2, n_steps_per_image=3) as (lib, h):
         B = 4
         on = lambda T=2, b=B: lib.sqair_set_layers(h, C.byref(_lay()), T, b)
         _state(lib, h, B)
@@ -150,25 +105,19 @@ def test_the_estimate_or_the_state_going_off_takes_the_layers_with_it():
         assert lib.sqair_set_estimate(h, C.byref(_est()), 2, B) == 0 and on() == 0
         _state(lib, h, B + 1)                                                 # another B
         assert on(2, B + 1) == -1 and "needs an estimate" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_training_calls_never_run_the_layers():
-    lib, h = _handle(k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(k_particles=2, n_steps_per_image=3) as (lib, h):
         B = 4
         _state(lib, h, B)
         assert lib.sqair_set_estimate(h, C.byref(_est()), 2, B) == 0 and lib.sqair_set_layers(h, C.byref(_lay()), 2, B) == 0
         assert lib.sqair_forward_train(*_fwd_args(h, B, T=2)) == -1 and "carried state" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 @pytest.mark.parametrize("path", LIBS)
 def test_kernel_entry_point_refusals_before_any_hip_call(path):
-    lib, h = _handle(path, k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(path, k_particles=2, n_steps_per_image=3) as (lib, h):
         good = dict(glimpse=DUMMY, where=DUMMY, presence=DUMMY, lw=DUMMY, log_w=DUMMY, iou_min=0.5, T=1, B=3, K=5)
         order = ("glimpse", "where", "presence", "lw", "log_w", "iou_min", "T", "B", "K")
         call = lambda lay, **kw: lib.sqair_lane_layers_test(h, *[dict(good, **kw)[k] for k in order],
@@ -182,8 +131,6 @@ def test_kernel_entry_point_refusals_before_any_hip_call(path):
             assert call(_lay(), iou_min=bad) == -1 and "iou_min" in _err(lib, h)
             assert call(_lay(cover_min=bad)) == -1 and "cover_min" in _err(lib, h)
         assert call(_capi.SqairLaneLayers(cover_min=0.5)) == -1 and "at least one of" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_stream_argument_errors():

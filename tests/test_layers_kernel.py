@@ -15,42 +15,31 @@ With SQAIR_PARITY_DIR set the largest observed errors are written to layers_pari
 file); without it nothing is written."""
 import ctypes as C
 import functools
-import json
-import os
 
 import numpy as np
 import pytest
 import torch
 
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
 from tests import layers_cases as LC
 from tests import layers_ref as L
+from tests.abi_host import open_handle
+from tests.kernel_unit import merge_parity
 
 pytestmark = pytest.mark.gpu
 
-PARITY_DIR_ENV = "SQAIR_PARITY_DIR"
 FIELDS = ("match", "layer", "cover", "owner")
+NOTE = ("largest absolute error of layer and cover against the float64 reference evaluated with the device's own match "
+        "table, per case of tests/test_layers_kernel.py (allowed: {:g}); match decisions skipped within 1e-5 of a "
+        "threshold".format(LC.TOL))
 
 
 def _record(case, **figures):
-    where = os.environ.get(PARITY_DIR_ENV)
-    if not where:
-        return
-    path = os.path.join(where, "layers_parity.json")
-    try:
-        os.makedirs(where, exist_ok=True)
-        data = json.load(open(path)) if os.path.exists(path) else {
-            "note": "largest absolute error of layer and cover against the float64 reference evaluated with the device's own match "
-                    "table, per case of tests/test_layers_kernel.py (allowed: {:g}); match decisions skipped within 1e-5 of a "
-                    "threshold".format(LC.TOL), "cases": {}}
+    def update(data):
         data["build_id"] = _capi.build_id()
         data["device"] = torch.cuda.get_device_name(0)
         data["cases"][case] = figures
-        json.dump(data, open(path, "w"), indent=1, sort_keys=True)
-    except OSError:
-        pass
+    merge_parity("layers_parity.json", lambda: {"note": NOTE, "cases": {}}, update)
 
 
 _handles = {}
@@ -59,11 +48,8 @@ _handles = {}
 def _handle(c):
     key = (c.wide, c.N, c.hw, c.G)
     if key not in _handles:
-        lib = _capi.lib(_capi.WIDE_LIB_PATH if c.wide else None)
-        cfg = make_config(make_flags(k_particles=2, n_steps_per_image=c.N, n_what=6, glimpse_size=c.G), c.hw)
-        h = C.c_void_p()
-        assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-        _handles[key] = (lib, h)
+        _handles[key] = open_handle(_capi.WIDE_LIB_PATH if c.wide else None, c.hw, k_particles=2, n_steps_per_image=c.N, n_what=6,
+                                    glimpse_size=c.G)
     return _handles[key]
 
 

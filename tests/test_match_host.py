@@ -11,38 +11,20 @@ import numpy as np
 import pytest
 
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
 from sqair_amd.stream import SqairStream
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DUMMY = C.c_void_p(0x1000)     # never dereferenced: the calls below are refused first or touch no device memory
-LIBS = [None, _capi.WIDE_LIB_PATH]
-
-
-def _handle(path=None, hw=(50, 50), **flags):
-    lib = _capi.lib(path)
-    cfg = make_config(make_flags(**flags), hw)
-    h = C.c_void_p()
-    assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-    return lib, h
-
-
-def _err(lib, h):
-    return lib.sqair_last_error(h).decode()
+from tests.abi_host import (LIBS, ROOT, constant, err as _err, estimate, handle, paragraph, phrases, prototype, score, set_state,
+                            stated_once)
 
 
 def test_the_symbol_is_exported_and_declared_and_the_abi_is_unchanged():
-    hdr = open(os.path.join(ROOT, "include", "sqair_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     for path in (None, _capi.WIDE_LIB_PATH, _capi.TIMELINE_LIB_PATH):
         lib = _capi.lib(path)
         assert hasattr(lib, "sqair_set_lane_match") and lib.sqair_abi_version() == 2
     assert "sqair_set_lane_match" in _capi.EXPORTED_SYMBOLS
-    assert re.search(r"\bint\s+sqair_set_lane_match\s*\(\s*SqairHandle\*\s*h,\s*int score,\s*int identity,\s*int traj_link\)\s*;", code)
+    assert prototype("sqair_set_lane_match") == "int sqair_set_lane_match(SqairHandle* h, int score, int identity, int traj_link)"
     fn = _capi.lib().sqair_set_lane_match
     assert fn.restype is C.c_int and list(fn.argtypes) == [C.c_void_p, C.c_int, C.c_int, C.c_int]
-    assert _capi.ABI_VERSION == 2 and re.search(r"#define SQAIR_ABI_VERSION 2\b", hdr)
+    assert _capi.ABI_VERSION == 2 == constant("SQAIR_ABI_VERSION")
     # no struct changes: the three public structs are the sizes they were
     assert C.sizeof(_capi.SqairLaneScore) == 8 + 8 * 12 and C.sizeof(_capi.SqairLaneIdentity) == 24 + 8 * 11
     # the device function stands beside the other two
@@ -53,31 +35,28 @@ def test_the_symbol_is_exported_and_declared_and_the_abi_is_unchanged():
 
 
 def test_the_header_states_the_semantics_once():
-    hdr = open(os.path.join(ROOT, "include", "sqair_hip.h")).read()
-    start = hdr.index("per-frame matching: keep + optimal where the lane block matches keep + greedy")
-    doc = re.sub(r"\s*\n \*\s*", " ", hdr[start:hdr.index("int sqair_set_lane_match(")])   # (the comment's line breaks)
-    for word in ("CLEAR-MOT", "[[0.60, 0.54], [0.54, 0.08]]", "tp 1, fn 1, fp 1", "0 = keep + greedy (the default", "1 = keep + optimal",
-                 "re-identification, births and ageing are untouched", "the link of sqair_lane_traj_score",
-                 "A kept pair is never given up, even where that costs a pair", "keeps idsw comparable",
-                 "maximises first the NUMBER of pairs, then the sum of q(g, j)", "q = __float2int_rn(IoU * 1048576.0f)", "units of 2^-20",
-                 "2^25 + q", "-1 for every other pair", "2^24 < 2^25", "below 2^30", "sq_assign_optimal_i32", "on the table as it stands",
-                 "a pair of weight -1 is never taken", "sq_assign_keep_optimal", "optimal assignments tie",
-                 "whatever sq_assign_optimal_i32 returns", "the same bits eager, graph-replayed and in split passes",
-                 "not restated as a rule", "matched and frag", "follow the score's mode", "it needs no registration",
-                 "a captured graph freezes it, as it freezes pointers", "sqair_lane_score_test, sqair_lane_identity_test and sqair_lane_idf_test",
-                 "The node count of a pass does not depend on it", "before any HIP call", "a value other than 0 or 1",
-                 "optimal re-identification", "HOTA"):
-        assert word in doc, word
-    assert hdr.count("per-frame matching: keep + optimal where the lane block matches keep + greedy") == 1
+    doc = paragraph("per-frame matching: keep + optimal where the lane block matches keep + greedy", "int sqair_set_lane_match(")
+    phrases(doc, ("CLEAR-MOT", "[[0.60, 0.54], [0.54, 0.08]]", "tp 1, fn 1, fp 1", "0 = keep + greedy (the default", "1 = keep + optimal",
+                  "re-identification, births and ageing are untouched", "the link of sqair_lane_traj_score",
+                  "A kept pair is never given up, even where that costs a pair", "keeps idsw comparable",
+                  "maximises first the NUMBER of pairs, then the sum of q(g, j)", "q = __float2int_rn(IoU * 1048576.0f)", "units of 2^-20",
+                  "2^25 + q", "-1 for every other pair", "2^24 < 2^25", "below 2^30", "sq_assign_optimal_i32", "on the table as it stands",
+                  "a pair of weight -1 is never taken", "sq_assign_keep_optimal", "optimal assignments tie",
+                  "whatever sq_assign_optimal_i32 returns", "the same bits eager, graph-replayed and in split passes",
+                  "not restated as a rule", "matched and frag", "follow the score's mode", "it needs no registration",
+                  "a captured graph freezes it, as it freezes pointers",
+                  "sqair_lane_score_test, sqair_lane_identity_test and sqair_lane_idf_test",
+                  "The node count of a pass does not depend on it", "before any HIP call", "a value other than 0 or 1",
+                  "optimal re-identification", "HOTA"))
+    stated_once("per-frame matching: keep + optimal where the lane block matches keep + greedy")
     # the three paragraphs keep their sentences and point here
-    flat = re.sub(r"\s*\n \*\s*", " ", hdr)
-    score = flat[flat.index("stream scoring: CLEAR-MOT events"):flat.index("typedef struct SqairLaneScore")]
-    ident = flat[flat.index("lane identities: stable per-lane track ids"):flat.index("typedef struct SqairLaneIdentity")]
-    traj = flat[flat.index("trajectory scoring: a lane forecast or a lane track table"):flat.index("#define SQAIR_TRAJ_COUNTS")]
-    idf = flat[flat.index("IDF1 scoring: does an identity stay on an object"):flat.index("typedef struct SqairLaneIdf")]
-    for para in (score, ident, traj):
+    score_doc = paragraph("stream scoring: CLEAR-MOT events", "typedef struct SqairLaneScore")
+    ident = paragraph("lane identities: stable per-lane track ids", "typedef struct SqairLaneIdentity")
+    traj = paragraph("trajectory scoring: a lane forecast or a lane track table", "#define SQAIR_TRAJ_COUNTS")
+    idf = paragraph("IDF1 scoring: does an identity stay on an object", "typedef struct SqairLaneIdf")
+    for para in (score_doc, ident, traj):
         assert "Out of scope" in para and "optimal (Hungarian) assignment" in para and "sqair_set_lane_match's, below" in para
-    assert "are sqair_set_idf's, below" in score and "the device function is shaped for it" in idf and "sqair_set_lane_match" in idf
+    assert "are sqair_set_idf's, below" in score_doc and "the device function is shaped for it" in idf and "sqair_set_lane_match" in idf
     for name in ("DESIGN.md", "README.md", "INTEGRATION.md"):      # they point to the header, they do not restate it
         text = open(os.path.join(ROOT, name)).read()
         assert "sqair_set_lane_match" in text, name
@@ -86,8 +65,7 @@ def test_the_header_states_the_semantics_once():
 
 @pytest.mark.parametrize("path", LIBS)
 def test_refusals_before_any_hip_call_and_a_setting_no_registration_touches(path):
-    lib, h = _handle(path, k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(path, k_particles=2, n_steps_per_image=3) as (lib, h):
         assert lib.sqair_set_lane_match(None, 0, 0, 0) == -1 and lib.sqair_set_lane_match(None, 1, 1, 1) == -1
         for bad in (2, -1, 7, 1 << 20):
             for pos, name in enumerate(("score", "identity", "traj_link")):
@@ -103,18 +81,14 @@ def test_refusals_before_any_hip_call_and_a_setting_no_registration_touches(path
         B, T = 4, 2
         assert lib.sqair_set_lane_match(h, 1, 1, 1) == 0
         assert lib.sqair_set_score(h, None, 0, 0) == 0 and lib.sqair_set_identity(h, None, 0, 0) == 0 and lib.sqair_set_idf(h, None, 0, 0) == 0
-        assert lib.sqair_set_state(h, DUMMY, DUMMY, DUMMY, lib.sqair_state_bytes(h, B), B) == 0
-        est = _capi.SqairLaneEstimate(iou_min=0.5, log_w=0x2000, best_row=0x3000, box=0x4000, presence=0x4100, obj_id=0x4200, map_count=0x4300)
+        set_state(lib, h, B)
+        est = estimate(fields=("box", "presence", "obj_id", "map_count"))
         assert lib.sqair_set_estimate(h, C.byref(est), T, B) == 0
-        kw = {n: 0x5000 + 0x100 * i for i, n in enumerate(_capi.SCORE_INPUTS)}
-        sc = _capi.SqairLaneScore(iou_min=0.5, G=4, **kw)
-        assert lib.sqair_set_score(h, C.byref(sc), T, B) == 0 and lib.sqair_set_score(h, None, 0, 0) == 0
+        assert lib.sqair_set_score(h, C.byref(score(outputs=())), T, B) == 0 and lib.sqair_set_score(h, None, 0, 0) == 0
         assert lib.sqair_set_estimate(h, None, 0, 0) == 0 and lib.sqair_set_state(h, None, None, None, 0, 0) == 0
         # ... which the stand-alone link shows: with traj_link still 1 a refusal of its own comes first, as it always did
         assert lib.sqair_lane_traj_score(h, None, None, None, 1, 1, None) == -1 and "must not be NULL" in _err(lib, h)
         assert lib.sqair_set_lane_match(h, 0, 0, 0) == 0
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_the_python_arguments_and_their_errors():

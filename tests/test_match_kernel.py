@@ -24,14 +24,13 @@ import pytest
 import torch
 
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
 from tests import identity_ref as I
 from tests import idf_ref
 from tests import match_cases as MC
 from tests import match_ref as M
 from tests import score_ref as R
 from tests import traj_score_ref as TR
+from tests.abi_host import open_handle
 from tests.test_idf_solve_kernel import struct as idf_struct, to_device as idf_to_device
 from tests.test_match_ref import record
 
@@ -47,13 +46,10 @@ _handles = {}
 def _handle(wide, N, fresh=False):
     key = (wide, N)
     if fresh or key not in _handles:
-        lib = _capi.lib(_capi.WIDE_LIB_PATH if wide else None)
-        cfg = make_config(make_flags(k_particles=2, n_steps_per_image=N, n_what=MC.NW), MC.HW)
-        h = C.c_void_p()
-        assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
+        opened = open_handle(_capi.WIDE_LIB_PATH if wide else None, MC.HW, k_particles=2, n_steps_per_image=N, n_what=MC.NW)
         if fresh:
-            return lib, h
-        _handles[key] = (lib, h)
+            return opened
+        _handles[key] = opened
     return _handles[key]
 
 

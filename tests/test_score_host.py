@@ -2,72 +2,34 @@
 binding mirrors the header's struct, the header's paragraph carries the semantics, every refusal is made before any HIP call (dummy
 device pointers are enough), the score goes off with the estimate and the state -- and the argument errors of SqairStream(score=...)."""
 import ctypes as C
+import functools
 import os
-import re
 
 import pytest
 
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
 from sqair_amd.stream import SqairStream
+from tests.abi_host import (DUMMY, LIBS, ROOT, constant, err as _err, estimate, fields as header_fields, fwd_args as _fwd_args, handle,
+                            paragraph, phrases, prototype, score as _score, set_state as _state, stated_once)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DUMMY = C.c_void_p(0x1000)     # never dereferenced: the calls below are refused first
-BIG = 1 << 50
-LIBS = [None, _capi.WIDE_LIB_PATH]
 NEEDED = ("box", "presence", "obj_id", "map_count")
-
-
-def _handle(path=None, hw=(50, 50), **flags):
-    lib = _capi.lib(path)
-    cfg = make_config(make_flags(**flags), hw)
-    h = C.c_void_p()
-    assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-    return lib, h
-
-
-def _err(lib, h):
-    return lib.sqair_last_error(h).decode()
-
-
-def _state(lib, h, B):
-    assert lib.sqair_set_state(h, DUMMY, DUMMY, DUMMY, lib.sqair_state_bytes(h, B), B) == 0
-
-
-def _est(iou_min=0.5, log_w=0x2000, best_row=0x3000, without=(), **kw):
-    kw.update({n: 0x4000 + 0x100 * i for i, n in enumerate(NEEDED) if n not in without})
-    return _capi.SqairLaneEstimate(iou_min=iou_min, log_w=log_w, best_row=best_row, **kw)
-
-
-def _score(iou_min=0.5, G=4, without=(), outputs=_capi.SCORE_FIELDS):
-    kw = {n: 0x5000 + 0x100 * i for i, n in enumerate(_capi.SCORE_INPUTS) if n not in without}
-    kw.update({n: 0x7000 + 0x100 * i for i, n in enumerate(outputs)})
-    return _capi.SqairLaneScore(iou_min=iou_min, G=G, **kw)
-
-
-def _fwd_args(h, B, T=1, bind=("log_weights_per_timestep",)):
-    out = _capi.SqairOutputs(**{k: 0x1000 for k in bind})
-    return (h, DUMMY, DUMMY, DUMMY, DUMMY, T, B, 0, C.byref(out), DUMMY, BIG, DUMMY)
+_est = functools.partial(estimate, fields=NEEDED)
 
 
 def test_the_symbols_are_exported_and_declared_and_the_abi_is_unchanged():
-    hdr = open(os.path.join(ROOT, "include", "sqair_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     for path in (None, _capi.WIDE_LIB_PATH, _capi.TIMELINE_LIB_PATH):
         lib = _capi.lib(path)
         assert hasattr(lib, "sqair_set_score") and hasattr(lib, "sqair_lane_score_test") and lib.sqair_abi_version() == 2
     assert "sqair_set_score" in _capi.EXPORTED_SYMBOLS and "sqair_lane_score_test" in _capi.EXPORTED_SYMBOLS
-    assert re.search(r"\bint\s+sqair_set_score\s*\(\s*SqairHandle\*\s*h,\s*const SqairLaneScore\*\s*score\s*,\s*int T,\s*int B\)", code)
-    assert re.search(r"\bint\s+sqair_lane_score_test\s*\(\s*SqairHandle\*\s*h,\s*const float\*\s*box,\s*const float\*\s*presence,"
-                     r"\s*const float\*\s*obj_id,\s*const int32_t\*\s*map_count,\s*int T,\s*int B,\s*const SqairLaneScore\*\s*score,"
-                     r"\s*void\*\s*stream\)", code)
-    assert _capi.ABI_VERSION == 2 and re.search(r"#define SQAIR_ABI_VERSION 2\b", hdr)
-    assert re.search(r"#define SQAIR_SCORE_MAX_TRUTH {}\b".format(_capi.SCORE_MAX_TRUTH), hdr)
-    assert re.search(r"#define SQAIR_SCORE_COUNTS {}\b".format(len(_capi.SCORE_COUNTS)), hdr)
+    assert prototype("sqair_set_score") == "int sqair_set_score(SqairHandle* h, const SqairLaneScore* score, int T, int B)"
+    assert prototype("sqair_lane_score_test") == ("int sqair_lane_score_test(SqairHandle* h, const float* box, const float* presence, "
+                                                  "const float* obj_id, const int32_t* map_count, int T, int B, "
+                                                  "const SqairLaneScore* score, void* stream)")
+    assert _capi.ABI_VERSION == 2 == constant("SQAIR_ABI_VERSION")
+    assert constant("SQAIR_SCORE_MAX_TRUTH") == _capi.SCORE_MAX_TRUTH
+    assert constant("SQAIR_SCORE_COUNTS") == len(_capi.SCORE_COUNTS)
     # the binding's struct mirrors the header's, field for field and in order
-    body = re.search(r"typedef struct SqairLaneScore \{(.*?)\} SqairLaneScore;", code, flags=re.S).group(1)
-    fields = re.findall(r"((?:const )?(?:float|int32_t|int64_t|double)\*?)\s+(\w+);", body)
+    fields = header_fields("SqairLaneScore")
     assert [n for _, n in fields] == [n for n, _ in _capi.SqairLaneScore._fields_]
     assert [n for _, n in fields] == ["iou_min", "G"] + list(_capi.SCORE_INPUTS) + list(_capi.SCORE_FIELDS)
     assert [n for ty, n in fields if ty == "int32_t*"] == ["last_id"] + list(_capi.SCORE_INT_FIELDS)
@@ -76,34 +38,29 @@ def test_the_symbols_are_exported_and_declared_and_the_abi_is_unchanged():
     assert C.sizeof(_capi.SqairLaneScore) == 8 + 8 * 12
     assert _capi.score_shapes(2, 3, 5) == dict(truth_match=(2, 3, 5), match_iou=(2, 3, 5), tp=(2, 3), fn=(2, 3), fp=(2, 3), idsw=(2, 3))
     # the counters' order is the header's
-    doc = re.sub(r"\s*\n \*\s*", " ", hdr)
-    assert "counts [B,9] int64: frames (scored), frames_invalid, truth, tp, fn, fp, idsw, count_hit, count_abs_err" in doc
+    assert "counts [B,9] int64: frames (scored), frames_invalid, truth, tp, fn, fp, idsw, count_hit, count_abs_err" in paragraph()
     assert _capi.SCORE_COUNTS == ("frames", "frames_invalid", "truth", "tp", "fn", "fp", "idsw", "count_hit", "count_abs_err")
 
 
 def test_the_header_states_the_semantics_once():
-    hdr = open(os.path.join(ROOT, "include", "sqair_hip.h")).read()
-    doc = hdr[hdr.index("stream scoring: CLEAR-MOT events"):hdr.index("typedef struct SqairLaneScore")]
-    doc = re.sub(r"\s*\n \*\s*", " ", doc)   # (the comment's line breaks)
-    for word in ("k_lane_score", "one workgroup per lane", "after k_lane_estimate (and after k_lane_layers if on)", "BEFORE the SMC resampler",
-                 "exactly one kernel node more", "unchanged bit for bit", "Training passes never run it", "does not read the records again",
-                 "truth identity IS the slot g", "truth_valid [T,B] int32", "G in 1..16", "Non-finite lanes", "map_count == -1",
-                 "frames_invalid", "Holes are allowed", "sq_box_iou", "the first unclaimed present j whose obj_id word equals last_id[b,g]",
-                 "greedy one-to-one", "ties to the smallest g, then the smallest j", "A NaN never wins", "unmatched g keep their memory",
-                 "match_iou[t,b,g]", "truth_match[t,b,g]", "count_hit += [map_count == n_truth]", "count_abs_err += |map_count - n_truth|",
-                 "updated in place", "iou_sum [B] fp64", "g in index order, frames in order, from one thread", "no float atomics", "Coasted",
-                 "the per-frame outputs are optional", "Refused", "a pass of another T", "Out of scope", "optimal (Hungarian) assignment",
-                 "IDF1", "scoring per particle row", "scoring of forecasts or lane tracks", "training passes"):
-        assert word in doc, word
-    assert hdr.count("stream scoring: CLEAR-MOT events") == 1
+    doc = paragraph("stream scoring: CLEAR-MOT events", "typedef struct SqairLaneScore")
+    phrases(doc, ("k_lane_score", "one workgroup per lane", "after k_lane_estimate (and after k_lane_layers if on)", "BEFORE the SMC resampler",
+                  "exactly one kernel node more", "unchanged bit for bit", "Training passes never run it", "does not read the records again",
+                  "truth identity IS the slot g", "truth_valid [T,B] int32", "G in 1..16", "Non-finite lanes", "map_count == -1",
+                  "frames_invalid", "Holes are allowed", "sq_box_iou", "the first unclaimed present j whose obj_id word equals last_id[b,g]",
+                  "greedy one-to-one", "ties to the smallest g, then the smallest j", "A NaN never wins", "unmatched g keep their memory",
+                  "match_iou[t,b,g]", "truth_match[t,b,g]", "count_hit += [map_count == n_truth]", "count_abs_err += |map_count - n_truth|",
+                  "updated in place", "iou_sum [B] fp64", "g in index order, frames in order, from one thread", "no float atomics", "Coasted",
+                  "the per-frame outputs are optional", "Refused", "a pass of another T", "Out of scope", "optimal (Hungarian) assignment",
+                  "IDF1", "scoring per particle row", "scoring of forecasts or lane tracks", "training passes"))
+    stated_once("stream scoring: CLEAR-MOT events")
     for name in ("DESIGN.md", "README.md"):      # they point to the header, they do not restate it
         assert "sqair_set_score" in open(os.path.join(ROOT, name)).read(), name
 
 
 @pytest.mark.parametrize("path", LIBS)
 def test_set_score_refusals_before_any_hip_call(path):
-    lib, h = _handle(path, k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(path, k_particles=2, n_steps_per_image=3) as (lib, h):
         B, T = 4, 2
         on = lambda sc=None, t=T, b=B: lib.sqair_set_score(h, C.byref(sc or _score()), t, b)
         assert lib.sqair_set_score(None, C.byref(_score()), T, B) == -1
@@ -130,13 +87,10 @@ def test_set_score_refusals_before_any_hip_call(path):
         for outs in ((), ("tp",), ("truth_match", "match_iou")):      # the per-frame outputs are optional
             assert on(_score(outputs=outs)) == 0, outs
         assert lib.sqair_set_score(h, None, 0, 0) == 0       # NULL: off
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_a_pass_of_another_t_is_refused_before_any_hip_call():
-    lib, h = _handle(k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(k_particles=2, n_steps_per_image=3) as (lib, h):
         B = 4
         _state(lib, h, B)
         assert lib.sqair_set_estimate(h, C.byref(_est()), 2, B) == 0
@@ -145,15 +99,12 @@ def test_a_pass_of_another_t_is_refused_before_any_hip_call():
             for T in (1, 3):
                 assert fn(*_fwd_args(h, B, T=T)) == -1
                 assert "T = 2" in _err(lib, h) and "T = {}".format(T) in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_the_estimate_or_the_state_going_off_takes_the_score_with_it():
     """The score can only be set while an estimate with the four fields is: after anything that switches it off, setting it again is
     refused until the estimate is back -- a NULL estimate, another T of the estimate, the state off and another B all switch it off."""
-    lib, h = _handle(k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(k_particles=2, n_steps_per_image=3) as (lib, h):
         B = 4
         on = lambda T=2, b=B: lib.sqair_set_score(h, C.byref(_score()), T, b)
         _state(lib, h, B)
@@ -173,25 +124,19 @@ def test_the_estimate_or_the_state_going_off_takes_the_score_with_it():
         assert lib.sqair_set_estimate(h, C.byref(_est()), 2, B) == 0 and on() == 0
         _state(lib, h, B + 1)                                                 # another B
         assert on(2, B + 1) == -1 and "needs an estimate" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_training_calls_never_run_the_score():
-    lib, h = _handle(k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(k_particles=2, n_steps_per_image=3) as (lib, h):
         B = 4
         _state(lib, h, B)
         assert lib.sqair_set_estimate(h, C.byref(_est()), 2, B) == 0 and lib.sqair_set_score(h, C.byref(_score()), 2, B) == 0
         assert lib.sqair_forward_train(*_fwd_args(h, B, T=2)) == -1 and "carried state" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 @pytest.mark.parametrize("path", LIBS)
 def test_kernel_entry_point_refusals_before_any_hip_call(path):
-    lib, h = _handle(path, k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(path, k_particles=2, n_steps_per_image=3) as (lib, h):
         good = dict(box=DUMMY, presence=DUMMY, obj_id=DUMMY, map_count=DUMMY, T=1, B=3)
         order = ("box", "presence", "obj_id", "map_count", "T", "B")
         call = lambda sc, **kw: lib.sqair_lane_score_test(h, *[dict(good, **kw)[k] for k in order], C.byref(sc) if sc is not None else None, DUMMY)
@@ -205,8 +150,6 @@ def test_kernel_entry_point_refusals_before_any_hip_call(path):
             assert call(_score(G=bad)) == -1 and "1..16" in _err(lib, h)
         for missing in _capi.SCORE_INPUTS:
             assert call(_score(without=(missing,))) == -1 and "must not be NULL" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_stream_argument_errors():

@@ -12,43 +12,31 @@ handed on in place), and the per-frame outputs are optional.  With SQAIR_PARITY_
 score_parity.json there (the copy under profiles/ is such a file); without it nothing is written."""
 import ctypes as C
 import functools
-import json
-import os
 
 import numpy as np
 import pytest
 import torch
 
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
 from tests import score_cases as SC
 from tests import score_ref as R
+from tests.abi_host import open_handle
+from tests.kernel_unit import merge_parity
 
 pytestmark = pytest.mark.gpu
 
-PARITY_DIR_ENV = "SQAIR_PARITY_DIR"
 INT_OUT = ("truth_match", "tp", "fn", "fp", "idsw")
+NOTE = ("per case of tests/test_score_kernel.py: the largest error of match_iou against the float64 reference and what is "
+        "allowed (four times the measured error of an fp32 restatement of sq_box_iou), the same for iou_sum per tp, the "
+        "lanes left out as fragile and the events counted; integer outputs, counts and last_id are compared exactly")
 
 
 def _record(case, **figures):
-    where = os.environ.get(PARITY_DIR_ENV)
-    if not where:
-        return
-    path = os.path.join(where, "score_parity.json")
-    try:
-        os.makedirs(where, exist_ok=True)
-        data = json.load(open(path)) if os.path.exists(path) else {
-            "note": "per case of tests/test_score_kernel.py: the largest error of match_iou against the float64 reference and what is "
-                    "allowed (four times the measured error of an fp32 restatement of sq_box_iou), the same for iou_sum per tp, the "
-                    "lanes left out as fragile and the events counted; integer outputs, counts and last_id are compared exactly",
-            "cases": {}}
+    def update(data):
         data["build_id"] = _capi.build_id()
         data["device"] = torch.cuda.get_device_name(0)
         data["cases"][case] = figures
-        json.dump(data, open(path, "w"), indent=1, sort_keys=True)
-    except OSError:
-        pass
+    merge_parity("score_parity.json", lambda: {"note": NOTE, "cases": {}}, update)
 
 
 _handles = {}
@@ -57,11 +45,7 @@ _handles = {}
 def _handle(c):
     key = (c.wide, c.N)
     if key not in _handles:
-        lib = _capi.lib(_capi.WIDE_LIB_PATH if c.wide else None)
-        cfg = make_config(make_flags(k_particles=2, n_steps_per_image=c.N, n_what=6), SC.HW)
-        h = C.c_void_p()
-        assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-        _handles[key] = (lib, h)
+        _handles[key] = open_handle(_capi.WIDE_LIB_PATH if c.wide else None, SC.HW, k_particles=2, n_steps_per_image=c.N, n_what=6)
     return _handles[key]
 
 

@@ -2,39 +2,17 @@
 the symbols and every refusal.  All of them are decided before any HIP call, so dummy device pointers are enough and no GPU is
 needed."""
 import ctypes as C
-import os
-import re
+import functools
 
 import pytest
 
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
+from tests.abi_host import BIG, DUMMY, LIBS, err as _err, fields as header_fields, functions, fwd_args, handle, smc
 
 NEW = ("sqair_forward_train_carry", "sqair_backward_carry")
-DUMMY = C.c_void_p(0x1000)     # never dereferenced: the calls below are refused first
 OTHER = C.c_void_p(0x2000)
-BIG = 1 << 40
 B = 4
-
-
-def _handle(path=None, hw=(50, 50), **flags):
-    lib = _capi.lib(path)
-    cfg = make_config(make_flags(**flags), hw)
-    h = C.c_void_p()
-    assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-    return lib, h
-
-
-def _err(lib, h):
-    return lib.sqair_last_error(h).decode()
-
-
-def _smc(**kw):
-    f = dict(ess_frac=1.0, seed=0, uniforms=None, log_w=DUMMY.value, log_z=DUMMY.value, log_evidence=DUMMY.value,
-             ess=DUMMY.value, u_out=None, resampled=DUMMY.value, src_rows=DUMMY.value)
-    f.update(kw)
-    return _capi.SqairSmc(**f)
+_smc = functools.partial(smc, ess_frac=1.0)      # (training resamples at every frame)
 
 
 def _carry(lib, h, smc=None, **kw):
@@ -56,14 +34,12 @@ def _calls(lib, h, carry, lw=True, b=B):
     return f, fe, g, _err(lib, h)
 
 
-def test_carry_symbols_are_exported_and_declared(repo_root):
-    txt = open(os.path.join(repo_root, "include", "sqair_hip.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    assert re.search(r"\}\s*SqairCarry\s*;", txt)
-    for path in (None, _capi.WIDE_LIB_PATH):
+def test_carry_symbols_are_exported_and_declared():
+    assert header_fields("SqairCarry")
+    for path in LIBS:
         lib = _capi.lib(path)
         for n in NEW:
-            assert re.search(r"\b" + n + r"\s*\(", txt), n
+            assert n in functions(), n
             assert n in _capi.EXPORTED_SYMBOLS
             assert hasattr(lib, n)
         assert lib.sqair_abi_version() == 2
@@ -81,8 +57,7 @@ def test_carry_struct_layout():
     (None, dict(k_particles=2, n_steps_per_image=3)),
     (_capi.WIDE_LIB_PATH, dict(k_particles=2, n_steps_per_image=3, n_what=64))])
 def test_carry_refusals(path, flags):
-    lib, h = _handle(path, **flags)
-    try:
+    with handle(path, **flags) as (lib, h):
         def refused(carry, words, **kw):
             f, fe, g, ge = _calls(lib, h, carry, **kw)
             assert f == -1 and g == -1, (words, fe, ge)
@@ -107,27 +82,18 @@ def test_carry_refusals(path, flags):
         assert lib.sqair_set_state(h, None, None, None, 0, 0) == 0
         # sqair_set_state keeps refusing the plain training calls (tests/test_stream_host.py pins that too)
         assert lib.sqair_set_state(h, DUMMY, DUMMY, None, lib.sqair_state_bytes(h, B), B) == 0
-        out = _capi.SqairOutputs()
-        assert lib.sqair_forward_train(h, DUMMY, DUMMY, DUMMY, DUMMY, 2, B, 0, C.byref(out), DUMMY, BIG, DUMMY) == -1
+        assert lib.sqair_forward_train(*fwd_args(h, B, T=2, bind=())) == -1
         assert "training" in _err(lib, h)
         assert lib.sqair_set_state(h, None, None, None, 0, 0) == 0
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_carry_refused_with_sample_from_prior():
-    lib, h = _handle(k_particles=2, n_steps_per_image=3, sample_from_prior=True, generate_after=2)
-    try:
+    with handle(k_particles=2, n_steps_per_image=3, sample_from_prior=True, generate_after=2) as (lib, h):
         f, fe, g, ge = _calls(lib, h, _carry(lib, h))
         assert f == -1 and g == -1 and "sample_from_prior" in fe and "sample_from_prior" in ge
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_carry_refused_for_frames_too_large_to_train():
-    lib, h = _handle(hw=(256, 256), k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(hw=(256, 256), k_particles=2, n_steps_per_image=3) as (lib, h):
         f, fe, g, ge = _calls(lib, h, _carry(lib, h))
         assert f == -1 and g == -1 and "training is limited" in fe and "training is limited" in ge
-    finally:
-        lib.sqair_destroy(h)

@@ -2,8 +2,7 @@
 declared, sized, every refusal made before any HIP call -- and the Python side: the shapes helper and SqairStream.tracks' argument
 errors."""
 import ctypes as C
-import os
-import re
+import functools
 import types
 
 import pytest
@@ -12,42 +11,29 @@ from sqair_amd import _capi
 from sqair_amd.flags import make_flags
 from sqair_amd.model import make_config
 from sqair_amd.stream import SqairStream
+from tests import abi_host
+from tests.abi_host import constant, err as _err, fields as header_fields, functions
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("sqair_trace_lane_scratch_bytes", "sqair_history_trace_lane", "sqair_track_lane_test")
 LIBS = {"product": (_capi.LIB_PATH, dict()), "wide": (_capi.WIDE_LIB_PATH, dict(n_what=64))}
 P = C.c_void_p(16)   # (a fake device address: every call below is refused before anything is dereferenced or launched)
 B, K, N, L = 2, 3, 2, 4
-
-
-def _handle(path, **flags):
-    lib = _capi.lib(path)
-    cfg = make_config(make_flags(**flags), (32, 40))
-    h = C.c_void_p()
-    assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-    return lib, h
-
-
-def _err(lib, h):
-    return lib.sqair_last_error(h).decode()
+handle = functools.partial(abi_host.handle, hw=(32, 40))
 
 
 def test_symbols_are_exported_and_declared_and_the_abi_is_unchanged():
-    hdr = open(os.path.join(ROOT, "include", "sqair_hip.h")).read()
     for name in NEW:
         assert name in _capi.EXPORTED_SYMBOLS
-        assert re.search(r"\b{}\s*\(".format(name), hdr), name
-    fields = re.search(r"typedef struct SqairTraceLane \{(.*?)\} SqairTraceLane;", hdr, re.S).group(1)
-    assert re.findall(r"[\* ]\s*(\w+);", fields) == [n for n, _ in _capi.SqairTraceLane._fields_]
+        assert name in functions(), name
+    assert [n for _, n in header_fields("SqairTraceLane")] == [n for n, _ in _capi.SqairTraceLane._fields_]
     assert _capi.SqairTraceLane._fields_[0] == ("iou_min", C.c_float)
     assert tuple(n for n, _ in _capi.SqairTraceLane._fields_[1:]) == _capi.TRACK_LANE_FIELDS
     # old callers pass the old struct: SqairTraceOutputs keeps its layout, the ABI its version
-    old = re.search(r"typedef struct SqairTraceOutputs \{(.*?)\} SqairTraceOutputs;", hdr, re.S).group(1)
-    assert re.findall(r"[\* ]\s*(\w+);", re.sub(r"/\*.*?\*/", "", old)) == ["T", "max_tracks"] + list(_capi.TRACE_FIELDS)
-    assert _capi.ABI_VERSION == 2 and re.search(r"#define SQAIR_ABI_VERSION 2\b", hdr) and _capi.lib().sqair_abi_version() == 2
+    assert [n for _, n in header_fields("SqairTraceOutputs")] == ["T", "max_tracks"] + list(_capi.TRACE_FIELDS)
+    assert _capi.ABI_VERSION == 2 == constant("SQAIR_ABI_VERSION") and _capi.lib().sqair_abi_version() == 2
     # the estimate's "out of scope" sentence points to the new call
-    scope = hdr[hdr.index("Out of scope: estimates for training passes"):]
-    assert "sqair_history_trace_lane" in scope[:300]
+    hdr = abi_host.raw()
+    assert "sqair_history_trace_lane" in hdr[hdr.index("Out of scope: estimates for training passes"):][:300]
 
 
 def test_track_lane_shapes():
@@ -66,14 +52,11 @@ def test_track_lane_shapes():
 @pytest.mark.parametrize("which", sorted(LIBS))
 def test_scratch_bytes(which):
     path, flags = LIBS[which]
-    lib, h = _handle(path, k_particles=3, n_steps_per_image=2, **flags)
-    try:
+    with handle(path, k_particles=3, n_steps_per_image=2, **flags) as (lib, h):
         nb = lib.sqair_trace_lane_scratch_bytes
         assert nb(h, 2, 5) > 0 and nb(h, 2, 5) % 4 == 0 and nb(h, 40, 5) > nb(h, 2, 5) and nb(h, 2, 256) > nb(h, 2, 5)
         assert nb(h, 2, 5) >= 4 * (2 * 5 + 2 * 2 * 5 * 2 + 2 * 2)          # the weights, the association, the ids, the objects
         assert nb(h, 0, 5) == -1 and nb(h, 2, 0) == -1 and nb(h, 2, 257) == -1
-    finally:
-        lib.sqair_destroy(h)
 
 
 def _with_history(lib, h):
@@ -96,8 +79,7 @@ def _outs(T=1, **kw):
 
 
 def test_trace_lane_refusals_before_any_hip_call():
-    lib, h = _handle(_capi.LIB_PATH, k_particles=K, n_steps_per_image=N)
-    try:
+    with handle(_capi.LIB_PATH, k_particles=K, n_steps_per_image=N) as (lib, h):
         need = lib.sqair_trace_lane_scratch_bytes(h, B, K)
         good = _capi.SqairTraceLane(iou_min=0.5, best_row=32)
 
@@ -134,8 +116,6 @@ def test_trace_lane_refusals_before_any_hip_call():
         # ---- switching the history off refuses again
         assert lib.sqair_set_history(h, None, 0, 0, 0) == 0
         assert call(ring=ring) == -1 and "no history set" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_more_than_256_particles_are_refused():
@@ -145,19 +125,15 @@ def test_more_than_256_particles_are_refused():
     cfg = make_config(make_flags(k_particles=257, n_steps_per_image=N), (32, 40))
     h = C.c_void_p()
     assert lib.sqair_create(C.byref(cfg), C.byref(h)) == -1
-    lib, h = _handle(_capi.LIB_PATH, k_particles=256, n_steps_per_image=N)
-    try:
+    with handle(_capi.LIB_PATH, k_particles=256, n_steps_per_image=N) as (lib, h):
         assert lib.sqair_trace_lane_scratch_bytes(h, B, 256) > 0 and lib.sqair_trace_lane_scratch_bytes(h, B, 257) == -1
         lane = _capi.SqairTraceLane(iou_min=0.5, best_row=32)
         assert lib.sqair_track_lane_test(h, P, P, P, P, None, 1, B, 257, C.byref(lane), P, 1 << 40, None) == -1
         assert "bad F / B / K" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_kernel_test_entry_refusals():
-    lib, h = _handle(_capi.LIB_PATH, k_particles=2, n_steps_per_image=N)
-    try:
+    with handle(_capi.LIB_PATH, k_particles=2, n_steps_per_image=N) as (lib, h):
         lane = _capi.SqairTraceLane(iou_min=0.5, best_row=32)
 
         def call(ptrs=(P,) * 4, F=1, Bq=1, Kq=2, lane=lane, scratch=P, nb=None):
@@ -172,8 +148,6 @@ def test_kernel_test_entry_refusals():
         assert call(lane=_capi.SqairTraceLane(iou_min=0.0, best_row=32)) == -1 and "iou_min" in _err(lib, h)
         assert call(lane=_capi.SqairTraceLane(iou_min=0.5)) == -1 and "best_row" in _err(lib, h)
         assert call(nb=lib.sqair_trace_lane_scratch_bytes(h, 1, 2) - 1) == -1 and "scratch_bytes" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 def test_stream_argument_errors():

@@ -3,7 +3,6 @@ the header's three structs, the header's paragraph carries the semantics once, e
 device pointers are enough) -- and the argument errors of SqairStream.forecast / tracks(truth=...) and trajectory_score()."""
 import ctypes as C
 import os
-import re
 import types
 
 import numpy as np
@@ -11,65 +10,41 @@ import pytest
 import torch
 
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
 from sqair_amd.lane import TrajScores
-from sqair_amd.model import make_config
 from sqair_amd.stream import SqairStream
+from tests.abi_host import (DUMMY, LIBS, ROOT, constant, dummy, err as _err, fields as header_fields, handle, paragraph, prototype,
+                            stated_once)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DUMMY = C.c_void_p(0x1000)     # never dereferenced: the calls below are refused first
-LIBS = [None, _capi.WIDE_LIB_PATH]
 TABLE_NEEDED = tuple(n for n in _capi.TRAJ_TABLE_FIELDS if n not in _capi.TRAJ_TABLE_OPTIONAL)
 TRUTH_NEEDED = tuple(n for n in _capi.TRAJ_TRUTH_FIELDS if n != "keep_id")
 
 
-def _handle(path=None, hw=(50, 50), **flags):
-    lib = _capi.lib(path)
-    cfg = make_config(make_flags(**flags), hw)
-    h = C.c_void_p()
-    assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-    return lib, h
-
-
-def _err(lib, h):
-    return lib.sqair_last_error(h).decode()
-
-
 def _table(without=()):
-    return _capi.SqairLaneTraj(**{n: 0x2000 + 0x100 * i for i, n in enumerate(_capi.TRAJ_TABLE_FIELDS) if n not in without})
+    return dummy(_capi.SqairLaneTraj, 0x2000, _capi.TRAJ_TABLE_FIELDS, without)
 
 
 def _truth(G=4, without=("keep_id",)):
-    return _capi.SqairTrajTruth(G=G, **{n: 0x4000 + 0x100 * i for i, n in enumerate(_capi.TRAJ_TRUTH_FIELDS) if n not in without})
+    return dummy(_capi.SqairTrajTruth, 0x4000, _capi.TRAJ_TRUTH_FIELDS, without, G=G)
 
 
-def _score(iou_min=0.5, without=(), outputs=_capi.TRAJ_FIELDS):
-    kw = {n: 0x6000 + 0x100 * i for i, n in enumerate(_capi.TRAJ_ACCUMULATORS) if n not in without}
-    kw.update({n: 0x7000 + 0x100 * i for i, n in enumerate(outputs)})
-    return _capi.SqairTrajScore(iou_min=iou_min, **kw)
-
-
-def _struct(code, name):
-    body = re.search(r"typedef struct {0} \{{(.*?)\}} {0};".format(name), code, flags=re.S).group(1)
-    return re.findall(r"((?:const )?(?:float|int32_t|int64_t|double)\*?)\s+(\w+);", body)
+def _score(iou_min=0.5, without=()):
+    return dummy(_capi.SqairTrajScore, 0x6000, _capi.TRAJ_ACCUMULATORS + _capi.TRAJ_FIELDS, without, iou_min=iou_min)
 
 
 def test_the_symbol_is_exported_and_declared_and_the_abi_is_unchanged():
-    hdr = open(os.path.join(ROOT, "include", "sqair_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     for path in (None, _capi.WIDE_LIB_PATH, _capi.TIMELINE_LIB_PATH):
         lib = _capi.lib(path)
         assert hasattr(lib, "sqair_lane_traj_score") and lib.sqair_abi_version() == 2
         assert not hasattr(lib, "sqair_lane_traj_score_test")      # the entry takes caller tensors: it is its own kernel-level entry
     assert "sqair_lane_traj_score" in _capi.EXPORTED_SYMBOLS
-    assert re.search(r"\bint\s+sqair_lane_traj_score\s*\(\s*SqairHandle\*\s*h,\s*const SqairLaneTraj\*\s*table,\s*const SqairTrajTruth\*\s*truth,"
-                     r"\s*const SqairTrajScore\*\s*score,\s*int F,\s*int B,\s*void\*\s*stream\)", code)
-    assert _capi.ABI_VERSION == 2 and re.search(r"#define SQAIR_ABI_VERSION 2\b", hdr)
-    assert re.search(r"#define SQAIR_TRAJ_COUNTS {}\b".format(len(_capi.TRAJ_COUNTS)), hdr)
-    assert re.search(r"#define SQAIR_TRAJ_SUMS {}\b".format(len(_capi.TRAJ_SUMS)), hdr)
-    assert re.search(r"#define SQAIR_TRAJ_LANE_COUNTS {}\b".format(len(_capi.TRAJ_LANE_COUNTS)), hdr)
+    assert prototype("sqair_lane_traj_score") == ("int sqair_lane_traj_score(SqairHandle* h, const SqairLaneTraj* table, "
+                                                  "const SqairTrajTruth* truth, const SqairTrajScore* score, int F, int B, void* stream)")
+    assert _capi.ABI_VERSION == 2 == constant("SQAIR_ABI_VERSION")
+    assert constant("SQAIR_TRAJ_COUNTS") == len(_capi.TRAJ_COUNTS)
+    assert constant("SQAIR_TRAJ_SUMS") == len(_capi.TRAJ_SUMS)
+    assert constant("SQAIR_TRAJ_LANE_COUNTS") == len(_capi.TRAJ_LANE_COUNTS)
     # the binding's structs mirror the header's, field for field and in order
-    tab, tru, sco = (_struct(code, n) for n in ("SqairLaneTraj", "SqairTrajTruth", "SqairTrajScore"))
+    tab, tru, sco = (header_fields(n) for n in ("SqairLaneTraj", "SqairTrajTruth", "SqairTrajScore"))
     assert [n for _, n in tab] == [n for n, _ in _capi.SqairLaneTraj._fields_] == list(_capi.TRAJ_TABLE_FIELDS)
     assert [n for _, n in tru] == [n for n, _ in _capi.SqairTrajTruth._fields_] == ["G"] + list(_capi.TRAJ_TRUTH_FIELDS)
     assert [n for _, n in sco] == [n for n, _ in _capi.SqairTrajScore._fields_] == ["iou_min"] + list(_capi.TRAJ_ACCUMULATORS + _capi.TRAJ_FIELDS)
@@ -87,7 +62,7 @@ def test_the_symbol_is_exported_and_declared_and_the_abi_is_unchanged():
     shared = [n for n in _capi.TRAJ_TABLE_FIELDS if n != "valid_mass"]
     assert all(n in _capi.FORECAST_LANE_FIELDS and n in _capi.TRACK_LANE_FIELDS for n in shared) and "valid_mass" in _capi.TRACK_LANE_FIELDS
     # the counters' order is the header's
-    doc = re.sub(r"\s*\n \*\s*", " ", hdr)
+    doc = paragraph()
     assert "counts[f,b,:] int64 = (frames, pairs, hits, lost, gone, count_hit, count_abs_err)" in doc
     assert "fp64 = (iou_sum, centre_err_sum, brier_sum)" in doc
     assert "lane_counts[b,:] += (calls, calls_invalid, anchor_truth, linked)" in doc
@@ -97,9 +72,7 @@ def test_the_symbol_is_exported_and_declared_and_the_abi_is_unchanged():
 
 
 def test_the_header_states_the_semantics_once():
-    hdr = open(os.path.join(ROOT, "include", "sqair_hip.h")).read()
-    doc = hdr[hdr.index("trajectory scoring: a lane forecast or a lane track table"):hdr.index("#define SQAIR_TRAJ_COUNTS")]
-    doc = re.sub(r"\s*\n \*\s*", " ", doc)   # (the comment's line breaks)
+    doc = paragraph("trajectory scoring: a lane forecast or a lane track table", "#define SQAIR_TRAJ_COUNTS")
     once = ("k_lane_traj_score", "neither registered on the handle nor part of a pass", "after sqair_forecast_fan or sqair_history_trace_lane",
             "The handle gives N and the error text only", "it is its own kernel-level entry", "NULL: mass 1 everywhere",
             "the last stepped frame (frame F-1 of lane tracks, the frame before f = 0 of a forecast)", "Lane not scored",
@@ -115,15 +88,15 @@ def test_the_header_states_the_semantics_once():
             "calibration of box_std", "trajectory scoring per particle row", "truth for departed objects", "a truth ring kept by the stream")
     shared = ("g in index order", "no float atomics", "before any HIP call", "G outside 1..16", "iou_min NaN or outside (0, 1]",
               "Out of scope", "optimal (Hungarian) assignment")      # other paragraphs say these of their own kernels
-    flat = re.sub(r"\s*\n \*\s*", " ", hdr)
+    flat = paragraph()
     for word in once:
         assert doc.count(word) == 1, word
         assert word in shared or flat.count(word) == 1, word         # stated in this paragraph and nowhere else
     assert "truth identity IS the slot g" in doc
-    assert hdr.count("trajectory scoring: a lane forecast or a lane track table") == 1
+    stated_once("trajectory scoring: a lane forecast or a lane track table")
     # the score's paragraph is as it was, a pointer follows it
-    assert "scoring of forecasts or lane tracks; training passes. */" in hdr
-    assert "Forecasts and lane tracks are scored by sqair_lane_traj_score" in hdr
+    assert "scoring of forecasts or lane tracks; training passes. */" in flat
+    assert "Forecasts and lane tracks are scored by sqair_lane_traj_score" in flat
     for name in ("DESIGN.md", "README.md", os.path.join("tools", "README.md")):      # they point to the header, they do not restate it
         text = open(os.path.join(ROOT, name)).read()
         assert ("sqair_lane_traj_score" in text or "traj_score_time" in text), name
@@ -132,8 +105,7 @@ def test_the_header_states_the_semantics_once():
 
 @pytest.mark.parametrize("path", LIBS)
 def test_refusals_before_any_hip_call(path):
-    lib, h = _handle(path, k_particles=2, n_steps_per_image=3)
-    try:
+    with handle(path, k_particles=2, n_steps_per_image=3) as (lib, h):
         good = dict(table=_table(), truth=_truth(), score=_score(), F=5, B=3)
 
         def call(**kw):
@@ -158,8 +130,6 @@ def test_refusals_before_any_hip_call(path):
         for bad in (0.0, -0.5, 1.0000001, float("nan"), float("inf")):
             assert call(score=_score(iou_min=bad)) == -1 and "iou_min must lie in (0, 1]" in _err(lib, h), bad
         assert call(table=_table(without=("obj_id",)), truth=_truth(without=())) == -1 and "keep_id needs the table's obj_id" in _err(lib, h)
-    finally:
-        lib.sqair_destroy(h)
 
 
 # ---- the stream's argument errors: all raised before the core is touched -------------------------------------------------------------

@@ -12,39 +12,28 @@ calls bit for bit, ``sums`` included; an invalid-anchor lane's accumulators are 
 SQAIR_PARITY_DIR set the measured figures are added to traj_score_parity.json there (the copy under profiles/ is such a file)."""
 import ctypes as C
 import functools
-import json
-import os
 
 import numpy as np
 import pytest
 import torch
 
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
 from tests import traj_score_cases as TC
 from tests import traj_score_ref as R
+from tests.abi_host import open_handle
+from tests.kernel_unit import merge_parity
 
 pytestmark = pytest.mark.gpu
 
-PARITY_DIR_ENV = "SQAIR_PARITY_DIR"
 IDS = [TC.case_id(c) for c in TC.CASES]
 
 
 def _record(case, **figures):
-    where = os.environ.get(PARITY_DIR_ENV)
-    if not where:
-        return
-    path = os.path.join(where, "traj_score_parity.json")
-    try:
-        os.makedirs(where, exist_ok=True)
-        data = json.load(open(path)) if os.path.exists(path) else {"cases": {}}
+    def update(data):
         data["build_id"] = _capi.build_id()
         data["device"] = torch.cuda.get_device_name(0)
         data["cases"].setdefault(case, {})["kernel"] = figures
-        json.dump(data, open(path, "w"), indent=1, sort_keys=True)
-    except OSError:
-        pass
+    merge_parity("traj_score_parity.json", lambda: {"cases": {}}, update)
 
 
 _handles = {}
@@ -53,11 +42,7 @@ _handles = {}
 def _handle(c):
     key = (c.wide, c.N)
     if key not in _handles:
-        lib = _capi.lib(_capi.WIDE_LIB_PATH if c.wide else None)
-        cfg = make_config(make_flags(k_particles=TC.K, n_steps_per_image=c.N, n_what=6), TC.HW)
-        h = C.c_void_p()
-        assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-        _handles[key] = (lib, h)
+        _handles[key] = open_handle(_capi.WIDE_LIB_PATH if c.wide else None, TC.HW, k_particles=TC.K, n_steps_per_image=c.N, n_what=6)
     return _handles[key]
 
 
