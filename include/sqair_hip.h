@@ -949,7 +949,7 @@ int sqair_set_score_ids(SqairHandle* h, int lane_ids /* 0: the estimate's obj_id
  * switches it off, and so does sqair_set_score registering a score without truth_match or with another G.
  * Out of scope: optimal per-frame matching inside k_lane_score or k_lane_identity (the device function is shaped for it:
  * sqair_set_lane_match, below, is that change); truth
- * identities other than the slot; HOTA; IDF1 per particle row, or for forecasts and lane tracks; identities across lanes; training
+ * identities other than the slot; HOTA (sqair_set_hota, below); IDF1 per particle row, or for forecasts and lane tracks; identities across lanes; training
  * passes; more than 64 predicted ids per clip -- reported through overflow_ids, not solved. */
 #define SQAIR_IDF_MAX_IDS 64
 #define SQAIR_IDF_TOTALS 12
@@ -980,6 +980,94 @@ int sqair_lane_idf_test(SqairHandle* h, const float* box, const float* presence,
  * NULL idf, G outside 1..16, B < 1, what sqair_set_idf refuses for idf. */
 int sqair_lane_idf_solve(SqairHandle* h, const SqairLaneIdf* idf, int G, int B, const int32_t* close /* device [B] or NULL */,
                          int64_t* open /* [B,12] or NULL */, int32_t* assign /* [B,G] or NULL */, void* stream);
+
+/* ---- HOTA scoring: detection, association and localisation in one figure -- a per-clip match log, a two-pass solve on the device ---
+ * CLEAR-MOT (sqair_set_score) is dominated by detection, IDF1 (sqair_set_idf) by association.  HOTA (Luiten et al., IJCV 2020)
+ * separates detection (DetA), association (AssA) and localisation (LocA) and combines them, HOTA_a = sqrt(DetA_a AssA_a), over nineteen
+ * localisation thresholds a = 0.05 i.  It needs two passes over a clip: the per-frame matching maximises IoU x a global alignment score
+ * between a truth identity and a predicted identity, and that score needs the whole clip.  So with a HOTA set, every following
+ * inference pass with a carried state, an estimate and a score runs one more kernel, k_lane_hota, one workgroup per lane looping over
+ * the pass's frames in order, which appends one record per scored frame to the lane's CLIP LOG: after k_lane_score (and after
+ * k_lane_idf when that is on) and BEFORE the SMC resampler.  A pass with HOTA on has exactly one kernel node more; with it off nothing
+ * is launched and every other output, blob and accumulator is unchanged bit for bit.  Training passes, and a capture's eager pre-pass
+ * without effects, never run it.  sqair_lane_hota_solve, a stand-alone capturable call (one launch of k_lane_hota_solve, one workgroup
+ * per lane), makes both passes over the log when the caller reads the score or a clip ends.  After the fp32 IoU everything is integer
+ * arithmetic: graph replay, eager calls and split passes agree exactly.
+ * 1. Units.  A clip, the truth identity (the slot g) and the predicted identity (the id word the score is handed) are exactly the
+ *    IDF's points 1 and 3: scored frames are those with truth_valid != 0 and map_count != -1, every other frame touches nothing.  The
+ *    columns follow the IDF's rule 3a in a column table of HOTA's own, col_id [B,P], P in 1..64, -1 = free: HOTA works with or without
+ *    an IDF.  The score's iou_min and truth_match are NOT read: HOTA has its own thresholds and its own matching.
+ * 2. Log, per lane, persistent on the device, written by the lane's one workgroup; L in 1..4096 records.  A scored frame takes the
+ *    next record, number frames[b], and frames[b] += 1; with the log full (frames[b] == L) the frame adds 1 to dropped_frames[b] and
+ *    touches nothing else -- no column either.  A record holds
+ *      log_q   [B,L,G,N] int32  q = __float2int_rn(IoU * 1048576.0f), the IoU of sq_box_iou on the words the score reads in units of
+ *                               2^-20, for a present truth g and a KEYED present object j; -1 for every other pair;
+ *      log_col [B,L,N]   int32  the column of j; -1: j is absent, -2: j is present but unkeyed;
+ *      log_row [B,L]     int32  bit g is set when truth g is present.
+ *    Every word of a record in use was written when it was taken: stale log words are never read.  A frame with at least one unkeyed
+ *    object adds 1 to totals_c.overflow_ids, at once.  All int32; the caller starts with col_id = -1, frames and dropped_frames 0.
+ * 3. Solve, pass 1, over the lane's records in order.  Per record, over its pairs with q >= 0: R_g = sum_j q, C_j = sum_g q and
+ *    n(g,j) = (q * 2^20) / (R_g + C_j - q) in int64, truncating, 0 when the denominator is 0 -- the pair's share of everything either
+ *    of the two overlaps in the frame; pot[g, col(j)] += n.  row_frames[g] += 1 for each present g, col_frames[col(j)] += 1 for each
+ *    keyed j, extra += 1 for each unkeyed j.  Then gas[g,p] = (pot * 2^20) / ((row_frames[g] + col_frames[p]) * 2^20 - pot), 0 when
+ *    the denominator is 0: TrackEval's global_alignment_score in units of 2^-20.
+ * 4. Solve, pass 2: ONE assignment per record, not one per threshold.  w[g,j] = (gas[g, col(j)] * q[g,j]) >> 15 for the pairs with
+ *    q >= 0, -1 elsewhere: w <= 2^25, sixteen pairs stay below 2^30, the exact range of sq_assign_optimal_i32 (csrc/sqair_lane.h),
+ *    which is called on the table as it stands.  Among equally optimal assignments the result is whatever that function returns:
+ *    deterministic, not restated as a rule.  For each matched pair and each threshold i = 1..19 with A_i = ceil(i * 2^20 / 20) -- so
+ *    that A_10 = 2^19 --: if q >= A_i then tp_i += 1, loc_i += q and mc_i[g, col(j)] += 1.  match [B,L,G] (optional) = the j matched
+ *    with truth g in each record in use, or -1.
+ * 5. Figures, per lane and threshold: fn_i = sum_g row_frames - tp_i, fp_i = sum_p col_frames + extra - tp_i, and in double, in a
+ *    fixed order (one thread, the cells (g, p) in index order) over the cells with mc_i > 0: ass_i = sum mc^2 / (row_frames[g] +
+ *    col_frames[p] - mc), assre_i = sum mc^2 / row_frames[g], asspr_i = sum mc^2 / col_frames[p].  The integers do not depend on the
+ *    schedule (mc is kept with integer atomics in the caller's scratch `work`), the doubles are summed after them.
+ * 6. Totals and close, as for the IDF.  totals_i [B,19,4] int64 = (tp, fn, fp, loc), totals_f [B,19,3] double = (ass, assre, asspr),
+ *    totals_c [B,4] int64 = (clips, frames, dropped_frames, overflow_ids; clips is 1 for a clip with frames > 0, overflow_ids always 0
+ *    in a clip's figures: 2 has counted it), in/out, the caller zeroes them.  Without `close` the solve writes the open clip's figures
+ *    to open_i, open_f, open_c (each optional, shaped as the totals) and match and changes nothing else but `work`.  For a lane with
+ *    close[b] != 0 it also adds them to the totals and frees the lane: col_id = -1 for every column, frames and dropped_frames = 0.
+ *    The totals combine clips the way TrackEval combines sequences: counts add, and AssA = ass / tp is weighted by TP.  The ratios are
+ *    the caller's: DetA = tp / (tp + fn + fp), DetRe = tp / (tp + fn), DetPr = tp / (tp + fp), AssA = ass / tp, AssRe = assre / tp,
+ *    AssPr = asspr / tp, LocA = loc / (2^20 tp), HOTA_a = sqrt(DetA AssA), and HOTA their mean over the nineteen thresholds.
+ * Pointers are remembered by the handle and frozen into captured graphs.  NULL hota: off.  sqair_set_hota is refused (return -1, text
+ * in sqair_last_error, before any HIP call) with no score set (sqair_set_score); for a T other than the estimate's or a B other than
+ * the state's; for P outside 1..64; for L outside 1..4096; for a NULL col_id, log_q, log_col, log_row, frames, dropped_frames, work,
+ * totals_i, totals_f or totals_c.  HOTA goes off with the score: everything that switches the score off switches it off, and so does
+ * sqair_set_score registering a score with another G.
+ * Out of scope: a tie rule among optimal assignments; HOTA per particle row, or for forecasts and lane tracks; truth identities other
+ * than the slot; clips longer than L frames -- reported through dropped_frames, not scored; training passes. */
+#define SQAIR_HOTA_ALPHAS 19
+#define SQAIR_HOTA_MAX_IDS 64
+#define SQAIR_HOTA_MAX_FRAMES 4096
+typedef struct SqairLaneHota {
+  int32_t P;                      /* id columns per lane, 1..64 */
+  int32_t L;                      /* log records per lane, 1..4096 */
+  /* the log, in/out, persists across passes; the caller starts with col_id = -1, frames and dropped_frames 0 */
+  int32_t* col_id;                /* [B,P]     the id word of the column, -1 = free */
+  int32_t* log_q;                 /* [B,L,G,N] */
+  int32_t* log_col;               /* [B,L,N] */
+  int32_t* log_row;               /* [B,L] */
+  int32_t* frames;                /* [B] records in use */
+  int32_t* dropped_frames;        /* [B] scored frames of the open clip that found the log full */
+  int32_t* work;                  /* [B,G,P,20] the solve's scratch (the pair histogram); any content */
+  int64_t* totals_i;              /* [B,19,4] in/out: tp, fn, fp, loc */
+  double* totals_f;               /* [B,19,3] in/out: ass, assre, asspr */
+  int64_t* totals_c;              /* [B,4] in/out: clips, frames, dropped_frames, overflow_ids */
+} SqairLaneHota;
+int sqair_set_hota(SqairHandle* h, const SqairLaneHota* hota /* NULL: off */, int T, int B);
+/* Kernel-level check of the append (tests): k_lane_hota on caller buffers, no state and no pass, with the handle's N and any G in
+ * 1..16.  box [T,B,N,4], presence, ids [T,B,N] (32-bit words) and map_count [T,B] stand for the estimate's outputs, score for the
+ * registered score: its truth_box, truth_present, truth_valid and G are read, nothing of it is written.  Refused (return -1, before any
+ * HIP call): a NULL box / presence / ids / map_count / score / hota, T or B out of range, G out of range, a NULL truth_box,
+ * truth_present or truth_valid, what sqair_set_hota refuses for hota. */
+int sqair_lane_hota_test(SqairHandle* h, const float* box, const float* presence, const float* ids, const int32_t* map_count, int T, int B,
+                         const SqairLaneScore* score, const SqairLaneHota* hota, void* stream);
+/* The solve (points 3 to 6): stand-alone and capturable -- nothing is registered on the handle and no pass runs it.  It takes the
+ * caller's tensors, so the tests call the kernel through it as it stands.  The handle gives the error text only.  Refused (return -1,
+ * before any HIP call): a NULL hota, G outside 1..16, N outside 1..16, B < 1, what sqair_set_hota refuses for hota. */
+int sqair_lane_hota_solve(SqairHandle* h, const SqairLaneHota* hota, int G, int N, int B, const int32_t* close /* device [B] or NULL */,
+                          int64_t* open_i /* [B,19,4] or NULL */, double* open_f /* [B,19,3] or NULL */, int64_t* open_c /* [B,4] or NULL */,
+                          int32_t* match /* [B,L,G] or NULL */, void* stream);
 
 /* ---- per-frame matching: keep + optimal where the lane block matches keep + greedy --------------------------------------------
  * The lane block makes three per-frame correspondences, each by keep + greedy: truth x lane object in the stream score (its points 2
@@ -1016,7 +1104,7 @@ int sqair_lane_idf_solve(SqairHandle* h, const SqairLaneIdf* idf, int G, int B, 
  *    last reads only truth_match, whatever mode wrote it).  The node count of a pass does not depend on it.
  * Refused (return -1, text in sqair_last_error, before any HIP call): a NULL handle; a value other than 0 or 1 -- nothing is changed
  * then.  Not offered: a stated tie-break among optimal assignments; optimal re-identification (the identity's step 4); matching per
- * particle row; HOTA; training passes. */
+ * particle row; HOTA (sqair_set_hota, above); training passes. */
 int sqair_set_lane_match(SqairHandle* h, int score, int identity, int traj_link);
 
 /* ---- objective ---------------------------------------------------------------------------------

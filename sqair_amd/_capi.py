@@ -112,6 +112,32 @@ def idf_shapes(B, G, P):
                 trk_state=(B, G), frames=(B,), totals=(B, len(IDF_TOTALS)))
 
 
+# HOTA scoring (include/sqair_hip.h: sqair_set_hota): the log's fields of SqairLaneHota in declaration order (the column table, the
+# records, the counters and the solve's scratch), then the three totals and their columns; the solve's optional outputs
+HOTA_TOTALS = ("totals_i", "totals_f", "totals_c")
+HOTA_LOG = _pointers("SqairLaneHota", without=HOTA_TOTALS)
+HOTA_INT = ("tp", "fn", "fp", "loc")
+HOTA_FLOAT = ("ass", "assre", "asspr")
+HOTA_CLIP = ("clips", "frames", "dropped_frames", "overflow_ids")
+HOTA_ALPHAS = _K["SQAIR_HOTA_ALPHAS"]
+HOTA_MAX_IDS = _K["SQAIR_HOTA_MAX_IDS"]
+HOTA_MAX_FRAMES = _K["SQAIR_HOTA_MAX_FRAMES"]
+HOTA_BINS = HOTA_ALPHAS + 1
+
+
+def hota_shapes(B, G, N, P, L):
+    """The log's shapes for G truth slots, N object slots, P id columns and L records per lane, and the totals."""
+    return dict(col_id=(B, P), log_q=(B, L, G, N), log_col=(B, L, N), log_row=(B, L), frames=(B,), dropped_frames=(B,),
+                work=(B, G, P, HOTA_BINS), totals_i=(B, HOTA_ALPHAS, len(HOTA_INT)), totals_f=(B, HOTA_ALPHAS, len(HOTA_FLOAT)),
+                totals_c=(B, len(HOTA_CLIP)))
+
+
+def hota_solve_shapes(B, G, L):
+    """The shapes of sqair_lane_hota_solve's optional outputs, and of its mask."""
+    return dict(open_i=(B, HOTA_ALPHAS, len(HOTA_INT)), open_f=(B, HOTA_ALPHAS, len(HOTA_FLOAT)), open_c=(B, len(HOTA_CLIP)),
+                match=(B, L, G), close=(B,))
+
+
 # lane identities (include/sqair_hip.h: sqair_set_identity): the names the per-frame outputs of SqairLaneIdentity have in a step's
 # ``lane`` dict; the scalars before them and the memory, the rest of its pointers; the columns of ``counts``
 IDENT_LANE_NAMES = dict(lane_id="lane_id", how="id_how", track_len="track_len")

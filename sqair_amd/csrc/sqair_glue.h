@@ -493,6 +493,35 @@ struct LaneIdfSolveArgs {
   int G, B;
 };
 int sq_launch_lane_idf_solve(const LaneIdfSolveArgs& a, hipStream_t s);
+// HOTA scoring (sqair_set_hota; include/sqair_hip.h states the semantics): k_lane_hota, one workgroup per lane b looping over the pass's
+// frames in order, one record of the lane's clip log per scored frame.  box / presence / ids [T][B][N] and map_count [T][B] are the
+// words k_lane_score was handed (or a test's buffers); of `sc` the truth and G are read.
+constexpr int SQ_HOTA_MAXP = 64;
+constexpr int SQ_HOTA_MAXL = 4096;
+constexpr int SQ_HOTA_BINS = SQAIR_HOTA_ALPHAS + 1;   // a matched pair's bin: the number of thresholds its q reaches, 0..19
+struct LaneHotaArgs {
+  const float* box;                    // [T][B][N][4]
+  const float* presence;               // [T][B][N]
+  const float* ids;                    // [T][B][N] 32-bit id words
+  const int32_t* map_count;            // [T][B]
+  SqairLaneScore sc;                   // read-only here
+  SqairLaneHota hota;                  // P, L, the column table, the log and totals_c
+  int T, B, N;
+};
+int sq_launch_lane_hota(const LaneHotaArgs& a, hipStream_t s);
+// The solve (sqair_lane_hota_solve): k_lane_hota_solve, one workgroup of four wavefronts per lane b: pass 1 over the records in order,
+// the alignment scores, pass 2 with a wavefront per record, the figures; for the lanes of `close` the figures into the totals and the
+// lane freed.
+struct LaneHotaSolveArgs {
+  SqairLaneHota hota;
+  const int32_t* close;                // [B] or NULL
+  int64_t* open_i;                     // [B][19][4] or NULL
+  double* open_f;                      // [B][19][3] or NULL
+  int64_t* open_c;                     // [B][4] or NULL
+  int32_t* match;                      // [B][L][G] or NULL
+  int G, N, B;
+};
+int sq_launch_lane_hota_solve(const LaneHotaSolveArgs& a, hipStream_t s);
 
 // Object forecasts (sqair_forecast_fan; include/sqair_hip.h states the semantics).  Fan-out: rollout row q = r * S + s.
 // k_forecast_fan_src expands the source map, src_fan[q] = src[q / S] (NULL: q / S), an index outside [0, R) of the blob -> -1.

@@ -216,6 +216,33 @@ __device__ __forceinline__ int sq_assign_keep_greedy(const float* iou, const int
   return n;
 }
 
+// The column of ONE present lane object j in a table of id words in LDS, cid[0..P) with -1 = free (the IDF's rule 3a, include/sqair_hip.h;
+// the HOTA log's too) -- one thread's walk, the objects of a frame in index order, jcol[0..j) holding the columns of the earlier ones
+// (any negative value: none).  The column whose word equals `word` is j's, unless an earlier object of the frame holds it; a
+// non-negative word that is in no column takes the first free one -- cid is written, `fresh` says so and the caller starts the
+// column's other words.  Returns the column, or a negative value for an unkeyed object: a negative word, no free column, a word
+// held twice in the frame.
+__device__ __forceinline__ int sq_lane_id_column(int* cid, const int P, const int word, const int* jcol, const int j, bool& fresh) {
+  fresh = false;
+  int col = -1, free_col = -1;
+  if (word >= 0) {
+    for (int p = 0; p < P; ++p) {
+      const int id = cid[p];
+      if (id == word) { col = p; break; }
+      if (id < 0 && free_col < 0) free_col = p;
+    }
+    if (col >= 0) {
+      for (int jj = 0; jj < j; ++jj)
+        if (jcol[jj] == col) col = -2;   // an earlier object of the frame holds the word
+    } else if (free_col >= 0) {
+      col = free_col;
+      cid[col] = word;
+      fresh = true;
+    }
+  }
+  return col;
+}
+
 // Maximum-weight one-to-one assignment of rows g < G to columns p < P over an int32 table in LDS, w[g * ld + p], for ONE wavefront:
 // all 64 lanes call it together, lane p owns column p (P <= 64, G <= 64).  Rows and columns may stay unassigned -- every row g has a
 // private dummy column of weight 0, owned by lane g, so a pair of negative weight is never taken --: the optimum is the maximum over

@@ -1,5 +1,5 @@
 // The per-lane answers: the kernels that turn a lane's K particle rows into one answer per lane -- the SMC resampler, the forecast
-// summaries, the lane estimate, the object layers, the stream score, the lane identities, the lane forecast, the lane tracks and the trajectory score of those two.  None of them is a hop of the frame loop (once per pass or
+// summaries, the lane estimate, the object layers, the stream score, the lane identities, the lane forecast, the lane tracks, the trajectory score of those two, the IDF1 table and the HOTA clip log with their solves.  None of them is a hop of the frame loop (once per pass or
 // per call, on B workgroups), and they are a translation unit -- a code object -- of their own so that work on them moves no kernel of the pass
 // (DESIGN.md section 3h).  Their compositions are the device functions of sqair_lane.h.  Every lane-wide sum is one thread's loop in
 // index order: the same bits on every replay, and K <= 256 adds are nothing next to the pass.
@@ -1034,21 +1034,11 @@ __global__ __launch_bounds__(256) void k_lane_idf(const LaneIdfArgs a SQ_TLP) {
         s_jcol[j] = -1;
         if (a.presence[tb * N + j] == 0.0f) continue;
         const int word = (int)sq_word(a.ids + tb * N + j);
-        int col = -1, free_col = -1;
-        if (word >= 0) {
-          for (int p = 0; p < P; ++p) {
-            const int id = s_cid[p];
-            if (id == word) { col = p; break; }
-            if (id < 0 && free_col < 0) free_col = p;
-          }
-          if (col >= 0) {
-            for (int jj = 0; jj < j; ++jj)
-              if (s_jcol[jj] == col) col = -2;   // an earlier object of the frame holds the word
-          } else if (free_col >= 0) {
-            col = free_col;
-            s_cid[col] = word; s_cfr[col] = 0;
-            for (int g = 0; g < G; ++g) s_ov[g * P + col] = 0;
-          }
+        bool fresh;
+        const int col = sq_lane_id_column(s_cid, P, word, s_jcol, j, fresh);
+        if (fresh) {
+          s_cfr[col] = 0;
+          for (int g = 0; g < G; ++g) s_ov[g * P + col] = 0;
         }
         if (col >= 0) { s_jcol[j] = col; s_cfr[col] += 1; }
         else ++unkeyed;
@@ -1134,5 +1124,227 @@ __global__ __launch_bounds__(64) void k_lane_idf_solve(const LaneIdfSolveArgs a 
 }
 int sq_launch_lane_idf_solve(const LaneIdfSolveArgs& a, hipStream_t s) {
   SQ_LAUNCH(k_lane_idf_solve, dim3(a.B), dim3(64), 0, s, a);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// HOTA scoring (sqair_set_hota; LaneHotaArgs / LaneHotaSolveArgs in sqair_glue.h; the semantics: include/sqair_hip.h, points 1-6)
+// ------------------------------------------------------------------------------------------------
+// k_lane_hota: workgroup = lane b, looping over the pass's frames in order with the lane's column table in LDS across them.  Per
+// scored frame thread 0 takes the next record -- or counts the frame as dropped when the log is full --, finds or makes the column
+// of every present lane object (sq_lane_id_column: the IDF's walk) and writes the record's row word; then thread j < N stores its
+// object's column and thread i < G * N computes the IoU of pair (g, j) = (i / N, i % N) on the words the score read and stores its
+// q: every word of the record is written.  Every branch around a barrier depends on truth_valid[t, b], map_count[t, b] and whether
+// the log is full alone: uniform over the workgroup.
+__global__ __launch_bounds__(256) void k_lane_hota(const LaneHotaArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ int s_cid[SQ_HOTA_MAXP];
+  __shared__ int s_jcol[SQ_MAXN];
+  __shared__ int s_rec;
+  const SqairLaneScore& o = a.sc;
+  const SqairLaneHota& f = a.hota;
+  const int b = blockIdx.x, tid = threadIdx.x, G = o.G, N = a.N, P = f.P, L = f.L;
+  if (tid < P) s_cid[tid] = f.col_id[(size_t)b * P + tid];
+  int frames = tid == 0 ? f.frames[b] : 0, c_drop = 0, c_over = 0;   // (thread 0's)
+  for (int t = 0; t < a.T; ++t) {
+    const size_t tb = (size_t)t * a.B + b;
+    if (o.truth_valid[tb] == 0 || a.map_count[tb] == -1) continue;   // no truth, or a non-finite lane: nothing is touched
+    __syncthreads();   // (the table is loaded; the last frame's readers are done with s_jcol and s_rec)
+    // ---- the record, the columns of the frame's objects and the truth's row word, one thread
+    if (tid == 0) {
+      int rec = -1;
+      if (frames >= 0 && frames < L) {
+        rec = frames++;
+        int unkeyed = 0, row = 0;
+        for (int j = 0; j < N; ++j) {
+          s_jcol[j] = -1;
+          if (a.presence[tb * N + j] == 0.0f) continue;
+          bool fresh;
+          const int col = sq_lane_id_column(s_cid, P, (int)sq_word(a.ids + tb * N + j), s_jcol, j, fresh);
+          s_jcol[j] = col >= 0 ? col : -2;
+          unkeyed += col < 0;
+        }
+        for (int g = 0; g < G; ++g) row |= (o.truth_present[tb * G + g] != 0) << g;
+        f.log_row[(size_t)b * L + rec] = row;
+        c_over += unkeyed > 0;
+      } else {
+        ++c_drop;
+      }
+      s_rec = rec;
+    }
+    __syncthreads();
+    const int rec = s_rec;
+    if (rec < 0) continue;   // the log is full
+    const size_t r = (size_t)b * L + rec;
+    if (tid < N) f.log_col[r * N + tid] = s_jcol[tid];
+    if (tid < G * N) {
+      const int g = tid / N, j = tid - g * N;
+      int q = -1;
+      if (s_jcol[j] >= 0 && o.truth_present[tb * G + g] != 0) {
+        const float* p = o.truth_box + (tb * G + g) * 4;
+        const float* w = a.box + (tb * N + j) * 4;
+        q = __float2int_rn(sq_box_iou(SqBox{p[0], p[1], p[2], p[3]}, SqBox{w[0], w[1], w[2], w[3]}) * 1048576.0f);
+      }
+      f.log_q[r * G * N + tid] = q;
+    }
+  }
+  __syncthreads();
+  if (tid < P) f.col_id[(size_t)b * P + tid] = s_cid[tid];
+  if (tid == 0) {
+    f.frames[b] = frames; f.dropped_frames[b] += c_drop;
+    f.totals_c[(size_t)b * 4 + 3] += c_over;
+  }
+}
+int sq_launch_lane_hota(const LaneHotaArgs& a, hipStream_t s) {
+  SQ_LAUNCH(k_lane_hota, dim3(a.B), dim3(256), 0, s, a);
+  return 0;
+}
+
+// k_lane_hota_solve: workgroup = lane b, four wavefronts.
+//   pass 1   the records in order, one barrier each (the record at work and the next one in two LDS buffers): thread i < G * N forms
+//            R_g and C_j of its pair (g, j) from the record in LDS and adds n to cell (g, col(j)) of pot -- the columns of a record
+//            are distinct, so a cell has one writer per record, and the barrier orders the records --; thread g counts its row,
+//            thread j its column.  Then gas, one thread per cell.
+//   pass 2   the records are independent: wavefront v takes records v, v + 4, ..  It builds the int32 table in its own LDS, calls
+//            sq_assign_optimal_i32 on it, and lane g files its matched pair under k = the number of thresholds its q reaches
+//            (q >= A_i exactly for i <= (20 q) >> 20): one integer atomic each on the pair histogram work[g][p][k] in global memory
+//            and on the lane's tp and loc bins in LDS.  Integer sums: they do not depend on the schedule.
+//   figures  one thread per cell turns its bins into mc_i (a suffix sum); then lane i - 1 of wavefront 0 owns threshold i: tp, loc,
+//            fn, fp and the three double sums over the cells in index order -- one thread, a fixed order.
+// The histogram is read back with device-scope atomic loads: the atomics that filled it were performed in L2.  A column index read
+// from the log is used only inside 0..P-1, a record count only inside 0..L: a log the caller wrote cannot index outside LDS.
+__device__ __forceinline__ int sq_hota_word(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__global__ __launch_bounds__(256) void k_lane_hota_solve(const LaneHotaSolveArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  constexpr int MAXC = SQ_SCORE_MAXG * SQ_HOTA_MAXP, MAXPAIR = SQ_SCORE_MAXG * 16, BINS = SQ_HOTA_BINS;
+  __shared__ long long s_pot[MAXC];
+  __shared__ int s_gas[MAXC];
+  __shared__ int s_q[2][MAXPAIR], s_col[2][16];
+  __shared__ int s_w[4][MAXPAIR], s_r2c[4][SQ_SCORE_MAXG];
+  __shared__ int s_rfr[SQ_SCORE_MAXG], s_cfr[SQ_HOTA_MAXP], s_extra, s_tp[BINS];
+  __shared__ unsigned long long s_loc[BINS];
+  const SqairLaneHota& f = a.hota;
+  const int b = blockIdx.x, tid = threadIdx.x, G = a.G, N = a.N, P = f.P, L = f.L, GN = G * N, GP = G * P;
+  const int F = min(max(f.frames[b], 0), L);
+  int* work = f.work + (size_t)b * GP * BINS;
+  for (int i = tid; i < GP; i += 256) s_pot[i] = 0;
+  for (int i = tid; i < GP * BINS; i += 256) work[i] = 0;
+  if (tid < G) s_rfr[tid] = 0;
+  if (tid < P) s_cfr[tid] = 0;
+  if (tid < BINS) { s_tp[tid] = 0; s_loc[tid] = 0ull; }
+  if (tid == 0) s_extra = 0;
+  __threadfence();   // (the zeroes are in L2 before any wavefront's atomics)
+  __syncthreads();
+  // ---- pass 1
+  const int g = tid / N, j = tid - g * N;
+  for (int rec = 0; rec < F; ++rec) {
+    const size_t r = (size_t)b * L + rec;
+    const int buf = rec & 1, row = f.log_row[r];
+    if (tid < GN) s_q[buf][tid] = f.log_q[r * GN + tid];
+    if (tid < N) s_col[buf][tid] = f.log_col[r * N + tid];
+    __syncthreads();   // (record rec is in its buffer; the last record's adds are done)
+    if (tid < GN) {
+      const int q = s_q[buf][tid], col = s_col[buf][j];
+      if (q >= 0 && col >= 0 && col < P) {
+        long long R = 0, C = 0;
+        for (int jj = 0; jj < N; ++jj) R += max(s_q[buf][g * N + jj], 0);
+        for (int gg = 0; gg < G; ++gg) C += max(s_q[buf][gg * N + j], 0);
+        const long long den = R + C - q;
+        if (den > 0) s_pot[g * P + col] += ((long long)q << 20) / den;
+      }
+    }
+    if (tid < G && ((row >> tid) & 1)) s_rfr[tid] += 1;
+    if (tid < N) {
+      const int col = s_col[buf][tid];
+      if (col >= 0 && col < P) s_cfr[col] += 1;
+      else if (col == -2) atomicAdd(&s_extra, 1);
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < GP; i += 256) {
+    const long long pot = s_pot[i], den = ((long long)(s_rfr[i / P] + s_cfr[i % P]) << 20) - pot;
+    s_gas[i] = den > 0 ? (int)((pot << 20) / den) : 0;
+  }
+  __syncthreads();
+  // ---- pass 2
+  const int wv = tid >> 6, ln = tid & 63;
+  for (int rec = wv; rec < F; rec += 4) {
+    const size_t r = (size_t)b * L + rec;
+    for (int i = ln; i < GN; i += 64) {
+      const int q = f.log_q[r * GN + i], col = f.log_col[r * N + i % N];
+      s_w[wv][i] = (q >= 0 && col >= 0 && col < P) ? (int)(((long long)s_gas[(i / N) * P + col] * q) >> 15) : -1;
+    }
+    sq_wave_lds_order();
+    sq_assign_optimal_i32(s_w[wv], N, G, N, s_r2c[wv]);
+    sq_wave_lds_order();
+    if (ln < G) {
+      const int jm = s_r2c[wv][ln];
+      if (a.match) a.match[r * G + ln] = jm;
+      if (jm >= 0) {
+        const int q = f.log_q[r * GN + ln * N + jm], col = f.log_col[r * N + jm];
+        const int k = min((int)((20ll * q) >> 20), BINS - 1);
+        atomicAdd(&s_tp[k], 1);
+        atomicAdd(&s_loc[k], (unsigned long long)q);
+        atomicAdd(&work[(ln * P + col) * BINS + k], 1);
+      }
+    }
+    sq_wave_lds_order();   // (the table and row_to_col are read before the next record overwrites them)
+  }
+  __threadfence();
+  __syncthreads();
+  // ---- figures: mc_i = the pairs of the cell with k >= i, in place
+  for (int c = tid; c < GP; c += 256) {
+    int acc = 0;
+    for (int k = BINS - 1; k >= 1; --k) {
+      acc += sq_hota_word(work + c * BINS + k);
+      __hip_atomic_store(work + c * BINS + k, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  __threadfence();
+  __syncthreads();
+  const bool closed = a.close && a.close[b] != 0;
+  if (tid < SQAIR_HOTA_ALPHAS) {
+    const int i = tid + 1;
+    long long tp = 0, loc = 0, n_row = 0, n_col = 0;
+    for (int k = i; k < BINS; ++k) { tp += s_tp[k]; loc += (long long)s_loc[k]; }
+    for (int gg = 0; gg < G; ++gg) n_row += s_rfr[gg];
+    for (int p = 0; p < P; ++p) n_col += s_cfr[p];
+    double ass = 0.0, re = 0.0, pr = 0.0;
+    for (int c = 0; c < GP; ++c) {
+      const int mc = sq_hota_word(work + c * BINS + i);
+      if (mc <= 0) continue;
+      const int rf = s_rfr[c / P], cf = s_cfr[c % P];
+      const double m2 = (double)mc * (double)mc;
+      ass += m2 / (double)(rf + cf - mc);
+      re += m2 / (double)rf;
+      pr += m2 / (double)cf;
+    }
+    const long long fi[4] = {tp, n_row - tp, n_col + s_extra - tp, loc};
+    const double ff[3] = {ass, re, pr};
+    const size_t e = (size_t)b * SQAIR_HOTA_ALPHAS + tid;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (a.open_i) a.open_i[e * 4 + k] = fi[k];
+      if (closed) f.totals_i[e * 4 + k] += fi[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      if (a.open_f) a.open_f[e * 3 + k] = ff[k];
+      if (closed) f.totals_f[e * 3 + k] += ff[k];
+    }
+  }
+  if (tid == 0) {
+    const long long fc[4] = {F > 0, F, f.dropped_frames[b], 0};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (a.open_c) a.open_c[(size_t)b * 4 + k] = fc[k];
+      if (closed) f.totals_c[(size_t)b * 4 + k] += fc[k];
+    }
+    if (closed) { f.frames[b] = 0; f.dropped_frames[b] = 0; }
+  }
+  if (closed && tid < P) f.col_id[(size_t)b * P + tid] = -1;
+}
+int sq_launch_lane_hota_solve(const LaneHotaSolveArgs& a, hipStream_t s) {
+  SQ_LAUNCH(k_lane_hota_solve, dim3(a.B), dim3(256), 0, s, a);
   return 0;
 }

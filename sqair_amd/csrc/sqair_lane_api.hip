@@ -1,9 +1,9 @@
 // libsqair_hip.so -- the lane answers on the native side of the C ABI (include/sqair_hip.h): the estimate and its followers, the
-// layers, the identity, the score and the IDF1 table.  Their registration on a handle as one block (SqLaneSet, sqair_internal.h:
-// sqair_set_estimate / _layers / _score / _identity / _score_ids / _idf), the estimate's refusal of a pass, ONE builder per kernel's arguments -- called by the
+// layers, the identity, the score, the IDF1 table and the HOTA log.  Their registration on a handle as one block (SqLaneSet, sqair_internal.h:
+// sqair_set_estimate / _layers / _score / _identity / _score_ids / _idf / _hota), the estimate's refusal of a pass, ONE builder per kernel's arguments -- called by the
 // pass and by the kernel-level entry point alike --, the pass's launch sequence (sq_launch_lane_answers, called by sq_forward_impl
 // with the block sq_resolve_pass resolved) and the stand-alone entry points (sqair_lane_*_test, sqair_lane_traj_score,
-// sqair_lane_idf_solve).  Host code
+// sqair_lane_idf_solve, sqair_lane_hota_solve).  Host code
 // only: the kernels and their launchers live in sqair_lane.hip, which work here does not move.  A further follower is one member
 // of SqLaneSet, its registration and builder here, and one line of sq_launch_lane_answers.
 #include "sqair_internal.h"
@@ -39,6 +39,16 @@ static int sq_idf_fields(SqairHandle* h, const std::string& who, const SqairLane
     return sq_no(h, who + "col_id, overlap, row_frames, col_frames, extra_frames, matched, frag, trk_state, frames and totals must not be NULL");
   return 0;
 }
+static int sq_hota_fields(SqairHandle* h, const std::string& who, const SqairLaneHota& c) {
+  if (c.P < 1 || c.P > SQ_HOTA_MAXP)
+    return sq_no(h, who + "P = " + std::to_string(c.P) + " must lie in 1.." + std::to_string(SQ_HOTA_MAXP));
+  if (c.L < 1 || c.L > SQ_HOTA_MAXL)
+    return sq_no(h, who + "L = " + std::to_string(c.L) + " must lie in 1.." + std::to_string(SQ_HOTA_MAXL));
+  if (!c.col_id || !c.log_q || !c.log_col || !c.log_row || !c.frames || !c.dropped_frames || !c.work || !c.totals_i || !c.totals_f ||
+      !c.totals_c)
+    return sq_no(h, who + "col_id, log_q, log_col, log_row, frames, dropped_frames, work, totals_i, totals_f and totals_c must not be NULL");
+  return 0;
+}
 static int sq_identity_fields(SqairHandle* h, const std::string& who, const SqairLaneIdentity& c) {
   const int N = h->cfg.n_steps_per_image;
   if (c.M < N || c.M > SQ_IDENT_MAXM)
@@ -59,7 +69,9 @@ static void sq_layers_off(SqLaneSet& l) { l.lay_on = false; l.lay = SqairLaneLay
 // (the score reads the identity's ids only while both are on: either going off puts score_ids back to 0)
 // (and the IDF reads the score's truth and its truth_match: it goes off with it)
 static void sq_idf_off(SqLaneSet& l) { l.idf_on = false; l.idf = SqairLaneIdf{}; }
-static void sq_score_off(SqLaneSet& l) { l.score_on = false; l.score = SqairLaneScore{}; l.score_ids = false; sq_idf_off(l); }
+// (and so does the HOTA log: the truth and the id words are the score's)
+static void sq_hota_off(SqLaneSet& l) { l.hota_on = false; l.hota = SqairLaneHota{}; }
+static void sq_score_off(SqLaneSet& l) { l.score_on = false; l.score = SqairLaneScore{}; l.score_ids = false; sq_idf_off(l); sq_hota_off(l); }
 static void sq_identity_off(SqLaneSet& l) { l.ident_on = false; l.ident = SqairLaneIdentity{}; l.score_ids = false; }
 // what the followers need of the estimate they read (best_row is never NULL in a registered estimate; `what`: the identity keeps an
 // appearance, trk_what, and reads the estimate's)
@@ -134,6 +146,7 @@ extern "C" int sqair_set_score(SqairHandle* h, const SqairLaneScore* score, int 
   if (sq_follower_shape_refusal(h, who, T, B) != 0 || sq_score_fields(h, who, *score) != 0) return -1;
   // a re-registered score drops the IDF it can no longer feed: a table sized for the other G, the output it reads gone
   if (h->lane.score_on && (!score->truth_match || score->G != h->lane.score.G)) sq_idf_off(h->lane);
+  if (h->lane.score_on && score->G != h->lane.score.G) sq_hota_off(h->lane);   // (a log sized for the other G)
   h->lane.score_on = true; h->lane.score = *score;
   return 0;
 }
@@ -150,6 +163,19 @@ extern "C" int sqair_set_idf(SqairHandle* h, const SqairLaneIdf* idf, int T, int
     return sq_no(h, who + "the score (sqair_set_score) must bind truth_match: the trajectory statistics read the score's matches");
   if (sq_follower_shape_refusal(h, who, T, B) != 0 || sq_idf_fields(h, who, *idf) != 0) return -1;
   h->lane.idf_on = true; h->lane.idf = *idf;
+  return 0;
+}
+extern "C" int sqair_set_hota(SqairHandle* h, const SqairLaneHota* hota, int T, int B) {
+  if (!h) return -1;
+  if (!hota) {
+    sq_hota_off(h->lane);
+    return 0;
+  }
+  const std::string who = "sqair_set_hota: ";
+  if (!h->state_on || !h->lane.est_on || !h->lane.score_on)
+    return sq_no(h, who + "needs a score (sqair_set_score): the log is keyed by the truth and the id words the score reads");
+  if (sq_follower_shape_refusal(h, who, T, B) != 0 || sq_hota_fields(h, who, *hota) != 0) return -1;
+  h->lane.hota_on = true; h->lane.hota = *hota;
   return 0;
 }
 extern "C" int sqair_set_identity(SqairHandle* h, const SqairLaneIdentity* id, int T, int B) {
@@ -233,6 +259,14 @@ static LaneIdfArgs sq_idf_args(const SqairConfig& c, const float* box, const flo
   a.T = T; a.B = B; a.N = c.n_steps_per_image;
   return a;
 }
+// (`ids`: as for the IDF; of `score` the truth and G are read)
+static LaneHotaArgs sq_hota_args(const SqairConfig& c, const float* box, const float* presence, const float* ids, const int32_t* map_count,
+                                 const SqairLaneScore& score, const SqairLaneHota& hota, int T, int B) {
+  LaneHotaArgs a; memset(&a, 0, sizeof(a));
+  a.box = box; a.presence = presence; a.ids = ids; a.map_count = map_count; a.sc = score; a.hota = hota;
+  a.T = T; a.B = B; a.N = c.n_steps_per_image;
+  return a;
+}
 
 // ------------------------------------------------------------------------------------------------
 // the pass: every lane launch, in the one order they have.  The estimate comes before the resampler zeroes the weights it reads
@@ -266,6 +300,8 @@ int sq_launch_lane_answers(SqairHandle* h, const SqLaneSet& l, const float* rec,
     sq_launch_lane_score(sq_score_args(c, e.box, e.presence, ids, e.map_count, l.score, T, B, l.score_match), s);
     // IDF1 scoring: the clip's identity overlap table (sqair_set_idf), accumulated in place on the words the score just read
     if (l.idf_on) sq_launch_lane_idf(sq_idf_args(c, e.box, e.presence, ids, e.map_count, l.score, l.idf, T, B), s);
+    // HOTA scoring: one record of the clip log per scored frame (sqair_set_hota), on the same words
+    if (l.hota_on) sq_launch_lane_hota(sq_hota_args(c, e.box, e.presence, ids, e.map_count, l.score, l.hota, T, B), s);
   }
   return 0;
 }
@@ -354,6 +390,36 @@ extern "C" int sqair_lane_idf_solve(SqairHandle* h, const SqairLaneIdf* idf, int
   LaneIdfSolveArgs a; memset(&a, 0, sizeof(a));
   a.idf = *idf; a.close = close; a.open = open; a.assign = assign; a.G = G; a.B = B;
   sq_launch_lane_idf_solve(a, (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+extern "C" int sqair_lane_hota_test(SqairHandle* h, const float* box, const float* presence, const float* ids, const int32_t* map_count,
+                                    int T, int B, const SqairLaneScore* score, const SqairLaneHota* hota, void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_lane_hota_test: ";
+  if (!box || !presence || !ids || !map_count || !score || !hota || T < 1 || B < 1 || T > 65535)
+    return sq_no(h, who + "null box / presence / ids / map_count / score / hota or bad T / B");
+  if (sq_truth_slots_refusal(h, who, score->G) != 0) return -1;
+  if (!score->truth_box || !score->truth_present || !score->truth_valid)
+    return sq_no(h, who + "the score's truth_box, truth_present and truth_valid must not be NULL");
+  if (sq_hota_fields(h, who, *hota) != 0) return -1;
+  sq_launch_lane_hota(sq_hota_args(h->cfg, box, presence, ids, map_count, *score, *hota, T, B), (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+// the HOTA solve (include/sqair_hip.h: sqair_lane_hota_solve): a stand-alone call on the log the passes -- or a test -- filled, nothing
+// registered on the handle, which gives the error text
+extern "C" int sqair_lane_hota_solve(SqairHandle* h, const SqairLaneHota* hota, int G, int N, int B, const int32_t* close, int64_t* open_i,
+                                     double* open_f, int64_t* open_c, int32_t* match, void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_lane_hota_solve: ";
+  if (!hota) return sq_no(h, who + "hota must not be NULL");
+  if (B < 1) return sq_no(h, who + "B = " + std::to_string(B) + " must be >= 1");
+  if (N < 1 || N > 16) return sq_no(h, who + "N = " + std::to_string(N) + " must lie in 1..16");
+  if (sq_truth_slots_refusal(h, who, G) != 0 || sq_hota_fields(h, who, *hota) != 0) return -1;
+  LaneHotaSolveArgs a; memset(&a, 0, sizeof(a));
+  a.hota = *hota; a.close = close; a.open_i = open_i; a.open_f = open_f; a.open_c = open_c; a.match = match; a.G = G; a.N = N; a.B = B;
+  sq_launch_lane_hota_solve(a, (hipStream_t)stream);
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }

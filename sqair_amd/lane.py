@@ -46,6 +46,14 @@ one-to-one assignment of truths to ids on the device (sqair_lane_idf_solve) and 
 tracked / mostly lost and the fragmentations.  ``reset(lanes)`` closes those lanes' clips -- their figures go into the totals and
 their tables are freed -- before it forgets their identities: a new clip has new truth identities.
 
+``score_hota=True`` (with ``score=True``): CLEAR-MOT is dominated by detection, IDF1 by association; HOTA separates detection,
+association and localisation and combines them.  It needs two passes over a clip, so the stream keeps a per-lane clip log on the
+device -- per scored frame the IoU of every (truth, keyed lane object) pair in units of 2^-20, the objects' id columns (up to
+``score_hota_ids`` per clip, the IDF's column rule) and the truths present, up to ``score_hota_frames`` frames per clip -- with one
+more kernel of the pass after the score's and the IDF's (sqair_set_hota); ``hota_score()`` makes both passes on the device
+(sqair_lane_hota_solve) and returns HOTA, DetA, AssA, LocA and their parts.  ``reset(lanes)`` closes those lanes' clips as it does
+the IDF's.
+
 ``forecast(..., lane=True, truth=...)`` and ``tracks(..., lane=True, truth=...)`` score the two answers that reach over time -- the
 lane forecast and the lane tracks -- against the truth's trajectories with one more launch after the call's own
 (sqair_lane_traj_score): truth and lane objects are linked once, at the last stepped frame, and every horizon or traced frame then
@@ -117,6 +125,35 @@ def _ratio(a, b):
     return float(a) / b if b else float("nan")
 
 
+def hota_figures(ints, floats):
+    """The ratios of HOTA (include/sqair_hip.h: sqair_set_hota, point 6) from one set of totals, ``ints`` [19, 4] = (tp, fn, fp, loc)
+    and ``floats`` [19, 3] = (ass, assre, asspr): ``hota_alpha``, ``deta_alpha``, ``assa_alpha`` [19] float64 arrays, their means over
+    the thresholds ``hota``, ``deta``, ``assa``, ``detre``, ``detpr``, ``assre``, ``asspr``, ``loca``, and ``hota0`` / ``loca0``, the
+    figures at alpha = 0.05.  A ratio without a denominator is NaN, and so is a mean over one.  With leading axes ([..., 19, 4] and
+    [..., 19, 3]) a list of such dicts, one per set, computed together."""
+    ints, floats = np.asarray(ints, np.float64), np.asarray(floats, np.float64)
+    if ints.ndim > 2:
+        lead = ints.shape[:-2]
+        return _hota_figures(ints.reshape((-1,) + ints.shape[-2:]), floats.reshape((-1,) + floats.shape[-2:]), int(np.prod(lead)))
+    return _hota_figures(ints[None], floats[None], 1)[0]
+
+
+def _hota_figures(ints, floats, n_sets):
+    tp, fn, fp, loc = (ints[..., i] for i in range(4))
+    div = lambda a, b: np.where(b != 0, a / np.where(b != 0, b, 1.0), np.nan)
+    per = dict(deta=div(tp, tp + fn + fp), detre=div(tp, tp + fn), detpr=div(tp, tp + fp), assa=div(floats[..., 0], tp),
+               assre=div(floats[..., 1], tp), asspr=div(floats[..., 2], tp), loca=div(loc / 1048576.0, tp))
+    per["hota"] = np.sqrt(per["deta"] * per["assa"])
+    mean = {n: v.mean(-1).tolist() for n, v in per.items()}
+    out = []
+    for i in range(n_sets):
+        res = {n: v[i] for n, v in mean.items()}
+        res.update(hota_alpha=per["hota"][i], deta_alpha=per["deta"][i], assa_alpha=per["assa"][i], hota0=float(per["hota"][i, 0]),
+                   loca0=float(per["loca"][i, 0]))
+        out.append(res)
+    return out
+
+
 def field_views(shapes, int_fields, device):
     """The fields {name: shape} as views of ONE float32 allocation, each 16-byte aligned (``int_fields``: viewed as int32), so that
     they are copied out with one launch instead of one per field.  Returns (flat, views): views(flat or a clone of it) -> {name: view}."""
@@ -139,11 +176,13 @@ class LaneAnswers(object):
     stream touches either); ``register`` allocates the buffers and registers them on the core's handle.  ``flat`` / ``views``: ONE
     allocation and its views by field, ``est`` (field_views) -- everything a step copies out as ``out["lane"]``; ``score_buf`` and
     ``ident_buf``: the score's truth, accumulators and identity memory, the identity's track table and counters; ``idf_buf``: the
-    IDF1 table of every lane's open clip and the totals over the closed ones."""
+    IDF1 table of every lane's open clip and the totals over the closed ones; ``hota_buf``: the HOTA log of every lane's open clip
+    and its totals."""
 
     def __init__(self, who, estimate, estimate_iou, estimate_canvas, estimate_layers, layers_cover_min, score, score_iou, score_truth,
                  identity, identity_iou, identity_tracks, identity_max_age, identity_reid_dist, identity_reid_what, identity_appearance,
-                 score_ids, score_idf=False, score_idf_ids=32, score_match="greedy", identity_match="greedy"):
+                 score_ids, score_idf=False, score_idf_ids=32, score_match="greedy", identity_match="greedy", score_hota=False,
+                 score_hota_ids=32, score_hota_frames=256):
         self.step_fn, who = who + ".step: ", who + ": "
 
         def bad(why):
@@ -187,6 +226,12 @@ class LaneAnswers(object):
             bad("score_idf is for a stream with score=True")
         if score_idf and not is_int_in(score_idf_ids, 1, _capi.IDF_MAX_IDS):
             bad("score_idf_ids must be an integer in [1, {}]".format(_capi.IDF_MAX_IDS))
+        if score_hota and not score:
+            bad("score_hota is for a stream with score=True")
+        if score_hota and not is_int_in(score_hota_ids, 1, _capi.HOTA_MAX_IDS):
+            bad("score_hota_ids must be an integer in [1, {}]".format(_capi.HOTA_MAX_IDS))
+        if score_hota and not is_int_in(score_hota_frames, 1, _capi.HOTA_MAX_FRAMES):
+            bad("score_hota_frames must be an integer in [1, {}]".format(_capi.HOTA_MAX_FRAMES))
         for name, v, flag, needs in (("score_match", score_match, score, "score=True"),
                                      ("identity_match", identity_match, identity, "identity=True")):
             if v not in MATCH_MODES:
@@ -195,6 +240,8 @@ class LaneAnswers(object):
                 bad("{}='optimal' is for a stream with {}".format(name, needs))
         self.score_match, self.identity_match = MATCH_MODES.index(score_match), MATCH_MODES.index(identity_match)
         self.idf, self.P = bool(score_idf), int(score_idf_ids) if score_idf else 0
+        self.hota = bool(score_hota)
+        self.hota_P, self.hota_L = (int(score_hota_ids), int(score_hota_frames)) if score_hota else (0, 0)
         self.who = who
         self.estimate, self.canvas, self.layers = bool(estimate), bool(estimate_canvas), bool(estimate_layers)
         self.scored, self.identified, self.appearance = bool(score), bool(identity), bool(identity_appearance)
@@ -269,6 +316,15 @@ class LaneAnswers(object):
             self._idf_out = zeros_of("sqair_lane_idf_solve", dict(open=(B, len(_capi.IDF_TOTALS)), assign=(B, G), close=(B,)), core.device)
             sync()
             core.check(lib.sqair_set_idf(h, C.byref(self._idf_c), T, B), "sqair_set_idf")
+        if self.hota:   # the clip log of every lane, the totals over the closed clips, and what a solve writes
+            self.hota_buf = zeros_of("SqairLaneHota", _capi.hota_shapes(B, G, N, self.hota_P, self.hota_L), core.device)
+            self.hota_buf["col_id"].fill_(-1)
+            self._hota_c = _capi.SqairLaneHota(P=self.hota_P, L=self.hota_L, **{n: t.data_ptr() for n, t in self.hota_buf.items()})
+            shapes = _capi.hota_solve_shapes(B, G, self.hota_L)
+            del shapes["match"]
+            self._hota_out = zeros_of("sqair_lane_hota_solve", shapes, core.device)
+            sync()
+            core.check(lib.sqair_set_hota(h, C.byref(self._hota_c), T, B), "sqair_set_hota")
 
     # ---- per step ------------------------------------------------------------------------------------------------------------
     def check_truth(self, truth):
@@ -310,7 +366,7 @@ class LaneAnswers(object):
         """The follow-ups of a stream's ``reset(lanes)`` (``lanes`` checked and distinct; ``on_core_stream``: the carried state's context):
         the score forgets those lanes' identities (``last_id``) and keeps their counters; the identity frees their track entries
         (``trk_id`` = -1) and keeps their ``next_id``.  Before either, a stream with ``score_idf`` closes those lanes' clips: one solve
-        with their mask, their figures into the totals, their tables freed."""
+        with their mask, their figures into the totals, their tables freed; a stream with ``score_hota`` does the same with its log."""
         if lanes and (self.scored or self.identified):
             with on_core_stream():
                 if self.idf:
@@ -318,6 +374,11 @@ class LaneAnswers(object):
                     close.zero_()
                     close[torch.as_tensor(lanes, device=close.device)] = 1
                     self._solve(close)
+                if self.hota:
+                    close = self._hota_out["close"]
+                    close.zero_()
+                    close[torch.as_tensor(lanes, device=close.device)] = 1
+                    self._hota_solve(close)
                 for j in lanes:
                     if self.scored:
                         self.score_buf["last_id"][j].fill_(-1)
@@ -371,6 +432,41 @@ class LaneAnswers(object):
         res["ml_rate"] = _ratio(tot["ml"], tot["trajectories"])
         res["frag_per_lane"], res["frag"] = res["frag"], tot["frag"]
         res["exact"] = tot["overflow_ids"] == 0
+        return res
+
+    def _hota_solve(self, close=None):
+        """One solve on the current stream (include/sqair_hip.h: sqair_lane_hota_solve) into ``_hota_out``; ``close``: the device mask
+        [B] of the lanes whose clip ends."""
+        core, o = self.core, self._hota_out
+        core.check(core.lib.sqair_lane_hota_solve(core.handle, C.byref(self._hota_c), self.G, core.N, self.B,
+                                                  None if close is None else close.data_ptr(), o["open_i"].data_ptr(),
+                                                  o["open_f"].data_ptr(), o["open_c"].data_ptr(), None, core._stream()),
+                   "sqair_lane_hota_solve")
+
+    def hota_score(self, reset=False):
+        if not self.hota:
+            raise ValueError("SqairStream.hota_score: the stream keeps no HOTA log (SqairStream(..., estimate=True, score=True, "
+                             "score_hota=True))")
+        core, buf = self.core, self.hota_buf
+        with torch.cuda.device(core.device):
+            core._join_in()
+            with core.on_stream():
+                self._hota_solve()
+                got = {n: (buf["totals" + n[4:]] + self._hota_out[n]) for n in ("open_i", "open_f", "open_c")}
+                if reset:   # the totals from zero, every lane free (what a close leaves, without counting the clip)
+                    buf["col_id"].fill_(-1)
+                    for n in _capi.HOTA_TOTALS + ("frames", "dropped_frames"):
+                        buf[n].zero_()
+            core._join_out()
+        got = {n: t.cpu() for n, t in got.items()}
+        res = _columns(got["open_i"], _capi.HOTA_INT)
+        res.update(_columns(got["open_f"], [n + "_sum" for n in _capi.HOTA_FLOAT]))      # (assre, asspr: the ratios' means, below)
+        res.update(_columns(got["open_c"], _capi.HOTA_CLIP))
+        ints, floats = got["open_i"].numpy(), got["open_f"].numpy()      # (the lanes and, last, their sum: one set of ratios each)
+        sets = hota_figures(np.concatenate([ints, ints.sum(0)[None]]), np.concatenate([floats, floats.sum(0)[None]]))
+        res["lanes"] = sets[:-1]
+        res.update(sets[-1])
+        res["exact"] = int(res["dropped_frames"].sum()) == 0 and int(res["overflow_ids"].sum()) == 0
         return res
 
     def identities(self):

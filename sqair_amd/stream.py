@@ -43,7 +43,7 @@ With ``estimate=True`` a step also returns ``out["lane"]``: one answer per lane 
 say more about it, each one more kernel of the pass -- ``estimate_layers`` which pixels each object occupies, ``identity`` a track id
 that stays on an object, ``score`` the CLEAR-MOT events against a step's ``truth`` (``score()``, ``identities()``; ``score_match`` / ``identity_match`` =
 "optimal": their per-frame matching as keep + optimal, sqair_set_lane_match), ``score_idf`` the identity overlap table
-IDF1 is solved from (``idf_score()``); ``forecast`` and
+IDF1 is solved from (``idf_score()``), ``score_hota`` the clip log HOTA is solved from (``hota_score()``); ``forecast`` and
 ``tracks`` with ``lane=True, truth=...`` score the lane forecast and the lane tracks (``trajectory_score(kind)``).  sqair_amd/lane.py
 holds all of it and says what each returns.
 
@@ -76,7 +76,7 @@ class SqairStream(object):
                  estimate_iou=0.5, estimate_canvas=False, estimate_layers=False, layers_cover_min=0.5, score=False, score_iou=0.5,
                  score_truth=None, identity=False, identity_iou=0.3, identity_tracks=None, identity_max_age=10, identity_reid_dist=4.0,
                  identity_reid_what=float("inf"), identity_appearance=True, score_ids="row", score_idf=False, score_idf_ids=32,
-                 score_match="greedy", identity_match="greedy"):
+                 score_match="greedy", identity_match="greedy", score_hota=False, score_hota_ids=32, score_hota_frames=256):
         if core.cfg.sample_from_prior:
             raise ValueError("SqairStream: generation modes (sample_from_prior) do not carry a state across calls")
         if resample not in (None, "systematic"):
@@ -87,7 +87,7 @@ class SqairStream(object):
         la = self.lane = LaneAnswers("SqairStream", estimate, estimate_iou, estimate_canvas, estimate_layers, layers_cover_min, score,
                                      score_iou, score_truth, identity, identity_iou, identity_tracks, identity_max_age,
                                      identity_reid_dist, identity_reid_what, identity_appearance, score_ids, score_idf, score_idf_ids,
-                                     score_match, identity_match)   # (checks only)
+                                     score_match, identity_match, score_hota, score_hota_ids, score_hota_frames)   # (checks only)
         self.smc = resample is not None
         self.ess_frac = ess_frac
         self.core = core
@@ -142,8 +142,9 @@ class SqairStream(object):
         carried(n) for n in ("state", "log_weight_sum", "log_z", "log_evidence", "ess", "u", "resampled", "_src", "_armed",
                              "_src_is_identity", "history", "history_fields"))
     # the lane answers', likewise
-    estimate, scored, identified, G, M, _est_flat, _est_views, _est, _score, _ident, _idf = (
-        lane_answer(n) for n in ("estimate", "scored", "identified", "G", "M", "flat", "views", "est", "score_buf", "ident_buf", "idf_buf"))
+    estimate, scored, identified, G, M, _est_flat, _est_views, _est, _score, _ident, _idf, _hota = (
+        lane_answer(n) for n in ("estimate", "scored", "identified", "G", "M", "flat", "views", "est", "score_buf", "ident_buf", "idf_buf",
+                                 "hota_buf"))
     _traj = lane_answer("acc", of="traj")
 
     def _set_smc(self, uniforms):
@@ -163,7 +164,8 @@ class SqairStream(object):
         stream also forgets those lanes' identities (``last_id``: a new clip has new ones); their counters stay.  A stream with
         ``identity=True`` frees those lanes' track entries (``trk_id`` = -1) and keeps their ``next_id``: an id is never reused within
         a lane.  A stream with ``score_idf=True`` first closes those lanes' clips (one solve on the device): their IDF1 figures go
-        into the totals and their tables are freed -- a new clip has new truth identities."""
+        into the totals and their tables are freed -- a new clip has new truth identities.  A stream with ``score_hota=True`` closes
+        their HOTA clips the same way."""
         self.carried.reset(lanes)
         self.lane.reset(sorted(set(self.carried.check_lanes(lanes))), self.carried._on_core_stream)
 
@@ -255,6 +257,18 @@ class SqairStream(object):
         ``exact``: no frame held an object without a column (``overflow_ids`` == 0: more than ``score_idf_ids`` ids in a clip, a
         negative id word).  ``reset``: the totals start again from zero and every table is freed afterwards."""
         return self.lane.idf_score(reset)
+
+    def hota_score(self, reset=False):
+        """HOTA so far (include/sqair_hip.h: sqair_set_hota): one solve on the device, nothing closed.  Per lane, the totals over the
+        closed clips plus the open clip: ``tp``, ``fn``, ``fp``, ``loc`` [B, 19] int64 and ``ass_sum``, ``assre_sum``, ``asspr_sum`` [B, 19] float64
+        per threshold alpha = 0.05 .. 0.95, ``clips``, ``frames``, ``dropped_frames``, ``overflow_ids`` [B] (host tensors).  Pooled over
+        the lanes -- counts add, AssA is weighted by TP, as TrackEval combines sequences -- and, in ``lanes`` [B], for each lane alone:
+        ``hota_alpha``, ``deta_alpha``, ``assa_alpha`` [19] with DetA = tp / (tp + fn + fp), AssA = ass_sum / tp and HOTA_alpha =
+        sqrt(DetA AssA); their means over the thresholds ``hota``, ``deta``, ``assa``, ``detre``, ``detpr``, ``assre``, ``asspr``,
+        ``loca``; ``hota0`` and ``loca0`` at alpha = 0.05; each NaN where a denominator is 0.  ``exact``: no frame was dropped (a clip
+        longer than ``score_hota_frames``) and no object was without a column (more than ``score_hota_ids`` ids in a clip, a negative
+        id word).  ``reset``: the totals start again from zero and every log is freed afterwards."""
+        return self.lane.hota_score(reset)
 
     # ---- lane identities --------------------------------------------------------------------------------------------------
     def identities(self):

@@ -76,6 +76,15 @@ score optimal, identity greedy, identity optimal; the scored legs are fed a devi
 optimal - greedy is reported next to the resampler's node of the same run.  Recorded, not gated on:
 
     python tools/stream_time.py --match [--out profiles/stream_match_time.json]
+
+With --hota: the price of HOTA scoring (SqairStream(estimate=True, score=True, score_hota=True), include/sqair_hip.h: sqair_set_hota).
+Streams at cfg-2's batch alternating in one process as with --history: plain, SMC, SMC + estimate, score, SMC + score, score + HOTA,
+SMC + score + HOTA; the scored legs are fed a device-resident truth as with --score, and the timed legs' logs are long enough that
+every timed step appends a record (a step that finds its log full does less).  The HOTA node is reported next to the score's and the
+resampler's node of the same run; the median time of ``hota_score()`` -- the solve over a full log, its copies and the host's ratios
+-- is measured separately at ``score_hota_frames`` 64 and 256.  Recorded, not gated on:
+
+    python tools/stream_time.py --hota [--out profiles/stream_hota_time.json]
 """
 import argparse
 import json
@@ -388,6 +397,54 @@ def time_idf(B, K, N, steps, warmup, rounds=10, hw=(50, 50), P=32):
     return res
 
 
+def time_hota(B, K, N, steps, warmup, rounds=10, hw=(50, 50), P=32, solve_frames=(64, 256)):
+    smc = dict(resample="systematic", ess_frac=0.5)
+    sc = dict(estimate=True, score=True, score_truth=N)
+    L = _capi.HOTA_MAX_FRAMES
+    assert 2 * (warmup + max(steps // rounds, 1) * rounds) <= L, "the timed legs' logs would fill up: fewer --steps"
+    hota = dict(sc, score_hota=True, score_hota_ids=P, score_hota_frames=L)
+    legs = dict(plain={}, smc=smc, smc_estimate=dict(estimate=True, **smc), score=sc, smc_score=dict(sc, **smc), score_hota=hota,
+                smc_score_hota=dict(hota, **smc))
+    for n in solve_frames:   # (stepped along untimed until their logs are full, for hota_score() below)
+        legs["solve_{}".format(n)] = dict(hota, score_hota_frames=n, **smc)
+    rng = np.random.default_rng(3)
+    box = np.concatenate([rng.uniform(-5, 35, (1, B, N, 2)), rng.uniform(8, 28, (1, B, N, 2))], -1).astype(np.float32)
+    truth = dict(box=torch.as_tensor(box).cuda(), present=torch.ones((1, B, N), dtype=torch.int32).cuda(),
+                 valid=torch.ones((1, B), dtype=torch.int32).cuda())
+    step_kw = {n: dict(truth=truth) for n in legs if "score" in n or n.startswith("solve_")}
+    streams, res, med, thr = alternating_streams(legs, B, K, N, steps, warmup, rounds, hw, step_kw)
+    res["P"], res["L_timed_legs"] = P, L
+    res["records_in_use"] = {n: int(st._hota["frames"].min()) for n, st in streams.items() if st.lane.hota}
+    for n in solve_frames:   # hota_score(): the solve, the copies and the ratios, every call waited for
+        st = streams["solve_{}".format(n)]
+        assert int(st._hota["frames"].min()) == n, "the log is not full"
+        with st.core.on_stream():
+            for _ in range(5):
+                st.hota_score()
+            torch.cuda.synchronize()
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(50)]
+            for x, y in ev:
+                x.record()
+                got = st.hota_score()
+                y.record()
+                st.core.stream.synchronize()
+        ms = [x.elapsed_time(y) for x, y in ev]
+        res["hota_score_ms_L{}".format(n)] = dict(median=float(np.median(ms)), p10=float(np.percentile(ms, 10)), p90=float(np.percentile(ms, 90)))
+        res["hota_score_L{}".format(n)] = {k: got[k] for k in ("hota", "deta", "assa", "loca", "exact")}
+    for key, v in (("latency", med), ("back_to_back", thr)):
+        one_node = v["smc"] - v["plain"]            # the yardstick: one dependent node (the resampler) on this machine, this run
+        added = dict(score_node_on_smc_estimate=v["smc_score"] - v["smc_estimate"], hota_node_on_score=v["score_hota"] - v["score"],
+                     hota_node_on_smc_score=v["smc_score_hota"] - v["smc_score"])
+        res["us_" + key] = dict(smc_node=1e3 * one_node, **{n: 1e3 * a for n, a in added.items()},
+                                **{n + "_over_smc_node": (a / one_node if one_node > 0 else None) for n, a in added.items()})
+    for n in solve_frames:
+        for k in ("ms_per_frame_median", "ms_per_frame_p10", "ms_per_frame_p90", "ms_per_frame_back_to_back"):
+            res[k].pop("solve_{}".format(n))      # (most of their steps found the log full: not a step's price)
+    for st in streams.values():
+        st.close()
+    return res
+
+
 def time_match(B, K, N, steps, warmup, rounds=10, hw=(50, 50)):
     smc = dict(resample="systematic", ess_frac=0.5)
     est = dict(estimate=True, **smc)
@@ -436,10 +493,13 @@ def main():
     ap.add_argument("--identity", action="store_true", help="plain / SMC / estimate / identity / SMC + estimate / SMC + identity / score / score + identity, alternating (profiles/stream_identity_time.json)")
     ap.add_argument("--idf", action="store_true", help="score and score + IDF, each with and without SMC, alternating; idf_score() apart (profiles/stream_idf_time.json)")
     ap.add_argument("--match", action="store_true", help="score and identity, greedy and optimal, with SMC and the estimate, alternating (profiles/stream_match_time.json)")
+    ap.add_argument("--hota", action="store_true", help="score and score + HOTA, each with and without SMC, alternating; hota_score() apart (profiles/stream_hota_time.json)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     ov, _, _, _ = config_inputs(2)
-    if args.match:
+    if args.hota:
+        shapes = [dict(name="cfg2_batch_hota", **time_hota(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
+    elif args.match:
         shapes = [dict(name="cfg2_batch_match", **time_match(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
     elif args.idf:
         shapes = [dict(name="cfg2_batch_idf", **time_idf(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
