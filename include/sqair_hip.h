@@ -1113,7 +1113,11 @@ int sqair_set_lane_match(SqairHandle* h, int score, int identity, int traj_link)
  * ops.ess ops.py:52-59, _imp_weighted_mean model.py:202-205).
  *   log_w_t, disc_lp_t: [T,B*K]; scalars_out[16]:
  *     0 elbo_vae  1 elbo_iwae  2 vimco_target (already / T)  3 ess
- *   iw_means_in/out: optional n_means x [T,B*K] tensors -> n_means importance-weighted per-frame means */
+ *   iw_means_in/out: optional n_means x [T,B*K] tensors -> n_means importance-weighted per-frame means; both may be NULL
+ *     with n_means = 0 only.  disc_lp_t and each of log_weights .. scalars_out may be NULL; scalars_out[4..15] and
+ *     iw_means_out[n_means..7] are not written.  k_particles = 1 gives NaN for the VIMCO signal and target, like the reference.
+ * Refused (return -1, text in sqair_last_error, before any HIP call): n_means > 0 with iw_means_in NULL, with a NULL among its
+ * first n_means pointers, or with iw_means_out NULL; T * B * k_particles above 2147483647 (the kernels index with int). */
 int sqair_elbo(SqairHandle* h, const float* log_w_t, const float* disc_lp_t, int T, int B,
                float* log_weights /*[B,K]*/, float* elbo_iwae_per_example /*[B]*/,
                float* importance_weights /*[B,K]*/, float* vimco_signal /*[B,K]*/, float* scalars_out /*[16]*/,
@@ -1185,7 +1189,9 @@ int sqair_st_insert_loglik_bwd(SqairHandle* h, const float* glimpse, const float
                                const float* g_data_ll, float* d_glimpse, float* d_where_logits,
                                float* d_mean_img, void* scratch, int64_t scratch_bytes, int B, void* stream);
 /* Gradient of the VIMCO target (already / T) w.r.t. the per-frame log weights and discrete log-probs [T,B*K],
- * from the importance weights and the learning signal sqair_elbo returned. */
+ * from the importance weights and the learning signal sqair_elbo returned.
+ * Refused (return -1, text in sqair_last_error, before any HIP call): T * B * k_particles above 2147483647 (the kernel indexes
+ * with int). */
 int sqair_elbo_bwd(SqairHandle* h, const float* importance_weights, const float* vimco_signal, int T, int B,
                    float* g_log_w_t, float* g_disc_lp_t, void* stream);
 /* Decoder branch of sqair_backward on its own (unit-test entry: the same host function and kernels as the full pass).

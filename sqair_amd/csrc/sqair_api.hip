@@ -1747,6 +1747,15 @@ extern "C" int sqair_elbo(SqairHandle* h, const float* log_w_t, const float* dis
                           float* scalars_out, const float* const* iw_means_in, int n_means, float* iw_means_out,
                           void* stream) {
   if (!h || !log_w_t || T < 1 || B < 1 || n_means < 0 || n_means > 8) return -1;
+  // the kernels load means.p[q][..] and store means_out[q] for every q < n_means, and index [T, B, K] with int
+  auto missing = [&](const std::string& what) {   // (the text is built only where the call is refused)
+    return sq_no(h, "sqair_elbo: " + what + " must not be NULL with n_means = " + std::to_string(n_means));
+  };
+  if (n_means > 0 && !iw_means_in) return missing("iw_means_in");
+  for (int q = 0; q < n_means; ++q)
+    if (!iw_means_in[q]) return missing("iw_means_in[" + std::to_string(q) + "]");
+  if (n_means > 0 && !iw_means_out) return missing("iw_means_out");
+  if (sq_tbk_refusal(h, "sqair_elbo: ", T, B, h->cfg.k_particles, "the kernels index with int") != 0) return -1;
   sq_launch_elbo(log_w_t, disc_lp_t, T, B, h->cfg.k_particles, log_weights, elbo_iwae_per_example, importance_weights,
                  vimco_signal, scalars_out, iw_means_in, n_means, iw_means_out, (hipStream_t)stream, h->opt_vi_target);
   SQ_CHECK_HIP(hipGetLastError());

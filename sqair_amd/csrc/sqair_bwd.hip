@@ -782,6 +782,7 @@ extern "C" int sqair_elbo_bwd(SqairHandle* h, const float* importance_weights, c
   if (!h || !importance_weights || !vimco_signal || !g_log_w_t || !g_disc_lp_t || T < 1 || B < 1) return -1;
   SqairConfig c;
   if (sqair_get_config(h, &c) != 0) return -1;
+  if (sq_tbk_refusal(h, "sqair_elbo_bwd: ", T, B, c.k_particles, "the kernel indexes with int") != 0) return -1;
   const int n = T * B * c.k_particles;
   SQ_LAUNCH(k_elbo_bwd, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, importance_weights,
                      vimco_signal, T, B, c.k_particles, g_log_w_t, g_disc_lp_t);

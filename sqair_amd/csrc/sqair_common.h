@@ -115,6 +115,15 @@ struct PackedLayer {
 
 struct SqairHandle;
 void sq_set_error(SqairHandle* h, const std::string& msg);
+static inline int sq_no(SqairHandle* h, const std::string& why) { sq_set_error(h, why); return -1; }   // a refusal: -1 + error text
+// 0 where [T, B, K] can be indexed with int (T, B >= 1), else the refusal "<who>T * B * k_particles = T * B * K must not exceed
+// 2147483647 (<why>)": the objective kernels (k_elbo, k_elbo_wide, k_elbo_bwd) index with int
+static inline int sq_tbk_refusal(SqairHandle* h, const char* who, int T, int B, int K, const char* why) {
+  const long long n_tb = (long long)T * B;   // (below 2^62; times K only once it is known to be small)
+  if (n_tb <= 2147483647LL && n_tb * K <= 2147483647LL) return 0;
+  return sq_no(h, std::string(who) + "T * B * k_particles = " + std::to_string(T) + " * " + std::to_string(B) + " * " + std::to_string(K) +
+                      " must not exceed 2147483647 (" + why + ")");
+}
 // Raises a kernel's dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) on the CURRENT device, once per
 // (kernel, device): the attribute belongs to the device's copy of the kernel, so a process that drives several devices (one
 // handle each) has to set it on each of them.  Returns 0 or -2; the HIP error is not swallowed.

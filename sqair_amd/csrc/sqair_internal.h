@@ -246,7 +246,7 @@ struct Workspace {
 };
 Workspace sq_carve(const SqairHandle* h, int T, int B, float* base, bool train);
 
-static inline int sq_no(SqairHandle* h, const std::string& why) { sq_set_error(h, why); return -1; }   // a refusal: -1 + error text
+// (sq_no, a refusal: -1 + error text, stands beside sq_set_error in sqair_common.h)
 static inline int sq_refuse(SqairHandle* h, const char* who, const std::string& why) { return sq_no(h, std::string(who) + ": " + why); }
 // -1 + "<who><name> must lie in (0, 1]" unless it does: an IoU or coverage threshold (NaN fails both comparisons)
 static inline int sq_unit_refusal(SqairHandle* h, const std::string& who, const char* name, float v) {
