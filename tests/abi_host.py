@@ -1,6 +1,7 @@
 """The harness of the host-side ABI tests (tests/test_*_host.py) and of the lane kernels' GPU tests: the header as text and as
-sqair_amd/_abi.py parses it, a C compiler on programs that include it, handles that close themselves, and the dummy structs the
-refusal tests hand over.  Importable without a GPU and without a built library: only lib() behind open_handle() loads one.
+sqair_amd/_abi.py parses it, a C compiler on programs that include it, handles that close themselves, the dummy structs the
+refusal tests hand over, and the handles the lane solves' GPU tests keep.  Importable without a GPU and without a built library:
+only lib() behind open_handle() loads one.
 
 What a test expects -- a field list, a prototype, a phrase, a refusal's text -- stays with the test and is stated there in full; what
 is here is how it obtains the thing it judges."""
@@ -158,3 +159,31 @@ def smc(ess_frac=0.5, seed=7, log_w=DUMMY.value, src_rows=DUMMY.value, **more):
     f = dict(uniforms=None, log_z=DUMMY.value, log_evidence=DUMMY.value, ess=DUMMY.value, u_out=None, resampled=DUMMY.value)
     f.update(more)
     return _capi.SqairSmc(ess_frac=ess_frac, seed=seed, log_w=log_w, src_rows=src_rows, **f)
+
+
+CARRY_B = 4
+OTHER = C.c_void_p(0x2000)      # a second fake device address
+train_smc = functools.partial(smc, ess_frac=1.0)      # (training resamples at every frame)
+
+
+def carry(lib, h, smc=None, **kw):
+    """A SqairCarry of CARRY_B lanes on dummy pointers, its state_bytes the handle's; ``smc``: the SqairSmc it points to."""
+    f = dict(state_in=DUMMY.value, state_out=DUMMY.value, src_rows=DUMMY.value, state_bytes=lib.sqair_state_bytes(h, CARRY_B), B=CARRY_B)
+    f.update(kw)
+    c = _capi.SqairCarry(**f)
+    if smc is not None:
+        c.smc = C.pointer(smc)
+    return c
+
+
+# ------------------------------------------------------------------------------------------------ handles kept for a session
+LANE_LIBS = {"product": None, "wide": _capi.WIDE_LIB_PATH}
+_kept = {}
+
+
+def kept_handle(key, path=None, hw=(50, 50), **flags):
+    """open_handle once per key, kept for the session: the lane solves' GPU tests (tests/idf_cases.py, tests/hota_cases.py) open one
+    handle per library."""
+    if key not in _kept:
+        _kept[key] = open_handle(path, hw, **flags)
+    return _kept[key]

@@ -6,7 +6,7 @@ lives under tests/ because it calls the oracle).  On the GPU box:
 Every case draws sizes (particles, slots, frames, sequences, frame shape, n_what, n_units), cells, priors and the boolean model
 flags at random inside the library's limits, a decision-stable noise draw on the ORACLE's margin (tests/hip_util.stable_noise),
 and compares presence / ids exactly, every output at 5e-4 scaled, the bounds at 1e-4 relative; with --grad also every
-parameter's gradient against autograd through the fp64 oracle (tests/test_hip_backward._full_backward_case's bar).  With --chain
+parameter's gradient against autograd through the fp64 oracle (tests/pass_cases.full_backward_case's bar).  With --chain
 the sizes are drawn inside what the in-launch slot chain takes (VanillaRNN slot cell, GRU temporal cell, n_units 8) and the
 pass with `slot_chain` on must reproduce the launches bit for bit, eager and as a graph replay.  With --gen the generation
 modes (`sample_from_prior`, frames after a random `generate_after` drawn from the priors: seq.py:198-200,
@@ -30,7 +30,7 @@ sys.path.insert(0, ROOT)
 from sqair_amd.data import make_sequences, to_float  # noqa: E402
 from sqair_amd.flags import make_flags  # noqa: E402
 from tests.hip_util import params32, run_hip, stable_noise  # noqa: E402
-from tests.test_hip_forward import _check_against  # noqa: E402
+from tests.pass_cases import chain_inputs, chain_run, check_against  # noqa: E402
 
 
 def draw_case(rng):
@@ -51,13 +51,12 @@ def draw_case(rng):
 
 
 def run_chain_case(flags, hw, T, B, seed):
-    from tests.test_slot_chain import _inputs, _run
     K, N = flags["k_particles"], flags["n_steps_per_image"]
     extra = {k: v for k, v in flags.items() if k not in ("k_particles", "n_steps_per_image")}
-    F, d, obs, P, noise = _inputs(B, K, N, T, hw, seed=seed, obj_size=max(2, min(20, min(hw) // 2)), **extra)
-    _, _, ref = _run(F, hw, d, obs, P, noise, K, chain=False, use_graph=False)
+    F, d, obs, P, noise = chain_inputs(B, K, N, T, hw, seed=seed, obj_size=max(2, min(20, min(hw) // 2)), **extra)
+    _, _, ref = chain_run(F, hw, d, obs, P, noise, K, chain=False, use_graph=False)
     for use_graph in (False, True):
-        _, _, got = _run(F, hw, d, obs, P, noise, K, chain=True, use_graph=use_graph)   # (debug on: every chain launch's status is checked)
+        _, _, got = chain_run(F, hw, d, obs, P, noise, K, chain=True, use_graph=use_graph)   # (debug on: every chain launch's status is checked)
         for k, v in ref.items():
             assert np.array_equal(v, got[k], equal_nan=True), (k, use_graph)
 
@@ -120,15 +119,15 @@ def run_case(flags, hw, T, B, seed, grad, edits=None):
     F = make_flags(**flags)
     K, N = int(F.k_particles), int(F.n_steps_per_image)
     if grad:
-        from tests.test_hip_backward import _check_report, _full_backward_case
+        from tests.pass_cases import check_report, full_backward_case
         extra = {k: v for k, v in flags.items() if k not in ("k_particles", "n_steps_per_image")}
-        report, ref, _ = _full_backward_case(max(K, 2), N, T, B, hw, seed=seed, flags=extra, edits=edits)
+        report, ref, _ = full_backward_case(max(K, 2), N, T, B, hw, seed=seed, flags=extra, edits=edits)
         if edits:
             from oracle import sqair_oracle as O
             from tests import latent_regimes as LR
             print("     " + LR.table(LR.counts_of(ref.outputs, O.make_cfg(make_flags(**dict(flags, k_particles=max(K, 2))), hw))))
         try:
-            _check_report(report, ill_scale=True)
+            check_report(report, ill_scale=True)
         except AssertionError:
             # Second bar for parameters whose gradient is tiny against the pass's largest one (sums of cancelling terms: the fp32
             # ORACLE misses the fp64 one by the same amount there -- seed 2 case 11: prop.where_bias.l1.b, |grad| 1.7e-2 of 54,
@@ -153,7 +152,7 @@ def run_case(flags, hw, T, B, seed, grad, edits=None):
     ref_out = {k: v.numpy() for k, v in ref.outputs.items() if not k.startswith("_")}
     ref_model = {k: getattr(ref, k).numpy() for k in ("log_weights", "elbo_iwae_per_example", "elbo_vae", "elbo_iwae",
                                                       "data_ll", "kl", "log_p_z", "log_q_z_given_x")}
-    _check_against(m, ref_out, ref_model, list(ref_out), T)
+    check_against(m, ref_out, ref_model, list(ref_out), T)
 
 
 def main():

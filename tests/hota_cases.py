@@ -11,11 +11,16 @@ sees more ids than P columns; b % 13 == 5 gives its first present object a negat
 the second.  Lane 7 is non-finite (map_count -1) from frame 2 on, lane 9 has no truthed frame, every other lane loses a tenth of its
 frames' truth; with T = 40 every lane of the cases with L = 16 and L = 32 that is scored throughout has more scored frames than L."""
 import collections
+import ctypes as C
 import functools
 
 import numpy as np
+import torch
 
+from sqair_amd import _capi
+from tests import hota_ref as R
 from tests import score_ref as SR
+from tests.abi_host import LANE_LIBS, kept_handle
 
 Case = collections.namedtuple("Case", "G N P L wide seed")
 CASES = [Case(4, 4, 32, 64, False, 4432), Case(1, 4, 8, 16, False, 1408), Case(16, 14, 64, 32, True, 1614)]
@@ -88,3 +93,68 @@ def make(c):
     for a in out.values():
         a.setflags(write=False)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ the solve on caller logs (GPU)
+RTOL = 1e-12
+
+
+def record(section, case, **figures):
+    """One case's figures into hota_parity.json under SQAIR_PARITY_DIR."""
+    from tests.kernel_unit import merge_parity
+
+    def update(data):
+        data["build_id"] = _capi.build_id()
+        data["device"] = torch.cuda.get_device_name(0)
+        data[section][case] = figures
+    merge_parity("hota_parity.json", R.fresh_parity, update)
+
+
+def handle(lib_name, N=4):
+    return kept_handle(("hota", lib_name, N), LANE_LIBS[lib_name], HW, k_particles=2, n_steps_per_image=N, n_what=6)
+
+
+def to_device(log, G, P):
+    d = {n: torch.from_numpy(np.array(v)).cuda() for n, v in log.items()}
+    d["work"] = torch.full((log["col_id"].shape[0], G, P, _capi.HOTA_BINS), 12345, dtype=torch.int32, device="cuda")   # any content
+    return d
+
+
+def struct(d, P, L):
+    return _capi.SqairLaneHota(P=P, L=L, **{n: d[n].data_ptr() for n in _capi.HOTA_LOG + _capi.HOTA_TOTALS})
+
+
+def run_solve(lib_name, d, G, N, P, L, close=None, want=("open_i", "open_f", "open_c", "match"), stream=None):
+    """One launch on the device log ``d`` (updated in place); returns {name: array} of the outputs asked for."""
+    lib, h = handle(lib_name)
+    n = d["col_id"].shape[0]
+    shapes = _capi.hota_solve_shapes(n, G, L)
+    out = {k: torch.full(shapes[k], -7, dtype=getattr(torch, _capi.field_dtype("sqair_lane_hota_solve", k)), device="cuda") for k in want}
+    mask = None if close is None else torch.from_numpy(np.asarray(close, np.int32)).cuda()
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    rc = lib.sqair_lane_hota_solve(h, C.byref(struct(d, P, L)), G, N, n, None if mask is None else mask.data_ptr(), ptr("open_i"),
+                                   ptr("open_f"), ptr("open_c"), ptr("match"), C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream))
+    assert rc == 0, lib.sqair_last_error(h)
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def judged(log, got, close=None):
+    """Judges the device's ``match`` of every record in use on the reference's tables, imposes it, and returns the reference's
+    (log after, open_i, open_f, open_c) with the number of records judged and of those whose matching is not SciPy's own."""
+    _, _, _, _, own, tables = R.solve(log)
+    B, L, G = got["match"].shape
+    n = differ = 0
+    for b in range(B):
+        F = int(log["frames"][b])
+        assert (got["match"][b, F:] == -7).all(), (b, F, got["match"][b, F:])      # the records not in use: nothing is written
+        for r in range(F):
+            R.judge(tables[b][r], got["match"][b, r])
+            n += 1
+            differ += not np.array_equal(got["match"][b, r], own[b, r])
+    after, oi, of, oc, _, _ = R.solve(log, close=close, match=got["match"])
+    return after, oi, of, oc, n, differ
+
+
+def close_enough(a, b):
+    return np.allclose(a, b, rtol=RTOL, atol=0.0)

@@ -21,6 +21,14 @@ A = [-(-(i * UNIT) // 20) for i in range(1, ALPHAS + 1)]      # ceil(i 2^20 / 20
 INT, FLOAT, CLIP = ("tp", "fn", "fp", "loc"), ("ass", "assre", "asspr"), ("clips", "frames", "dropped_frames", "overflow_ids")
 LOG = ("col_id", "log_q", "log_col", "log_row", "frames", "dropped_frames")
 TOTALS = ("totals_i", "totals_f", "totals_c")
+NOTE = ("statement_vs_float: the header's integer statement of HOTA against the published algorithm in float64 on the clips of "
+        "tests/hota_cases.py (CPU); device_vs_scipy: the share of records where the device's matching is not SciPy's own and the HOTA "
+        "difference that makes (tests/test_hota_solve_kernel.py, recorded, not gated)")
+
+
+def fresh_parity():
+    """hota_parity.json before its first case: tests/test_hota_ref.py and tests/test_hota_solve_kernel.py write the same file."""
+    return {"note": NOTE, "statement_vs_float": {}, "device_vs_scipy": {}}
 
 
 # ------------------------------------------------------------------------------------------------ the log (points 1 and 2)

@@ -9,12 +9,17 @@ object of a frame carries a negative id; in every 17th lane the second present o
 int32 words of the float ids.  ``truth_match`` is the score's own output for these inputs (tests/score_ref.py), which the kernel under
 test only reads."""
 import collections
+import ctypes as C
 import functools
 
 import numpy as np
+import torch
 
+from sqair_amd import _capi
+from tests import idf_ref as R
 from tests import score_cases as SC
 from tests import score_ref as SR
+from tests.abi_host import LANE_LIBS, kept_handle
 
 Case = collections.namedtuple("Case", "G N P iou_min wide seed")
 CASES = [Case(G, N, P, iou, wide, 1000 * G + 10 * P + int(10 * iou))
@@ -60,3 +65,47 @@ def make(c):
     for a in x.values():
         a.setflags(write=False)
     return x
+
+
+# ------------------------------------------------------------------------------------------------ the solve on caller tables (GPU)
+NOTE = ("per case of tests/test_idf_solve_kernel.py (solve) and tests/test_idf_kernel.py (accumulate): the lanes compared, the "
+        "lanes left out as fragile and the events counted; every compared word is an integer and is compared exactly")
+
+
+def record(section, case, **figures):
+    """One case's figures into idf_parity.json under SQAIR_PARITY_DIR (tests/test_idf_solve_kernel.py and tests/test_idf_kernel.py
+    write the same file)."""
+    from tests.kernel_unit import merge_parity
+
+    def update(data):
+        data["build_id"] = _capi.build_id()
+        data["device"] = torch.cuda.get_device_name(0)
+        data[section][case] = figures
+    merge_parity("idf_parity.json", lambda: {"note": NOTE, "solve": {}, "accumulate": {}}, update)
+
+
+def handle(lib_name):
+    return kept_handle(("idf", lib_name), LANE_LIBS[lib_name], k_particles=2, n_steps_per_image=4, n_what=6)
+
+
+def to_device(t):
+    return {n: torch.from_numpy(np.array(v)).cuda() for n, v in t.items()}
+
+
+def struct(d, P):
+    return _capi.SqairLaneIdf(P=P, **{n: d[n].data_ptr() for n in _capi.IDF_TABLE + ("totals",)})
+
+
+def run_solve(lib_name, d, G, P, close=None, want_open=True, want_assign=True):
+    """One launch on the device table ``d`` (updated in place); returns (open, assign) as arrays or None."""
+    lib, h = handle(lib_name)
+    n = d["col_id"].shape[0]
+    open_ = torch.full((n, len(R.TOTALS)), -7, dtype=torch.int64, device="cuda") if want_open else None
+    assign = torch.full((n, G), -7, dtype=torch.int32, device="cuda") if want_assign else None
+    mask = None if close is None else torch.from_numpy(np.asarray(close, np.int32)).cuda()
+    ptr = lambda t: None if t is None else t.data_ptr()
+    rc = lib.sqair_lane_idf_solve(h, C.byref(struct(d, P)), G, n, ptr(mask), ptr(open_), ptr(assign),
+                                  C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == 0, lib.sqair_last_error(h)
+    torch.cuda.synchronize()
+    return (None if open_ is None else open_.cpu().numpy()), (None if assign is None else assign.cpu().numpy())

@@ -1,6 +1,7 @@
 """The harness of the kernel unit tests (tests/test_slot_adjoint_kernels.py, test_slot_forward_kernels.py, test_logprob_kernels.py, and
-the parity file of test_dense_contract.py): handles on the unit entries of sqair_unit_test.hip, device buffers that know which words the
-kernel owns, the per-file figures and their JSON, the judge, the case cache and the bars.  Importable without a GPU: the CPU tests build
+the forward layer and parity file of test_dense_contract.py and test_linear_strip.py): handles on the unit entries of
+sqair_unit_test.hip, device buffers that know which words the kernel owns, the per-file figures and their JSON, the judge, the case
+cache and the bars.  Importable without a GPU: the CPU tests build
 the test modules' cases and bars through it; only Buf, Handle.pack and a test's own launches touch the device.
 
 What differs by file stays with the file and comes in as an argument: the error metric and the per-output scales, which outputs are
@@ -10,6 +11,7 @@ import json
 import os
 
 import numpy as np
+import pytest
 import torch
 
 from sqair_amd import _capi
@@ -17,7 +19,7 @@ from sqair_amd.flags import make_flags
 from sqair_amd.model import make_config
 from sqair_amd.params import param_spec
 from tests import slot_adjoint_ref as R
-from tests.hip_util import stream
+from tests.hip_util import dev, stream
 
 PARITY_DIR_ENV = "SQAIR_PARITY_DIR"
 LAYOUT = ("W", "PRES", "ID", "WHERE", "WHAT", "LOGIT", "WHERE_LOC", "WHERE_SCALE", "WHAT_LOC", "WHAT_SCALE", "PROB", "snh", "psnh",
@@ -244,3 +246,146 @@ def image(rng, B_, H, W):
             img[b] += rng.uniform(0.3, 1.0) * np.sin(2 * np.pi * (fy * yy + fx * xx) + ph)
     img = 0.5 + 0.45 * img / np.abs(img).max((1, 2), keepdims=True)
     return f32(np.clip(0.9 * img + 0.1 * rng.uniform(size=img.shape), 0.0, 1.0))
+
+
+# ------------------------------------------------------------------------------------------------ the dense operand contract
+# (tests/test_dense_contract.py and tests/test_linear_strip.py: one forward layer's operands, its launch and what is asserted of it)
+NONE, ELU, TANH, SIGMOID, SOFTPLUS_MIN = range(5)
+
+
+def dense_record(case, **figures):
+    def update(data):
+        data["build_id"] = _capi.build_id()
+        data["device"] = torch.cuda.get_device_name(0)
+        data["cases"][case] = figures
+
+    merge_parity("dense_contract_parity.json", lambda: {
+        "note": "per case of tests/test_dense_contract.py: the kernel family the launcher chose, the largest error against the "
+                "float64 reference, the bar and err / bar.  Forward errors are absolute; dX errors are relative to the "
+                "destination's largest reference value; GRU destinations add `f32_formula_err` (the same formulas in numpy "
+                "float32 from the rounded float64 GEMM result) and `allowance` = 4 x that, which is part of their bar.",
+        "cases": {}}, update)
+
+
+@pytest.fixture(scope="module", name="handle")
+def dense_handle():
+    """The module-scoped handle of the dense contract tests: a test file imports it by name."""
+    lib = _capi.lib()
+    cfg = make_config(make_flags(k_particles=3, n_steps_per_image=4), (50, 50))
+    h = C.c_void_p()
+    rc = lib.sqair_create(C.byref(cfg), C.byref(h))
+    assert rc == 0, ("sqair_create", rc)
+    yield lib, h
+    lib.sqair_destroy(h)
+
+
+def took(before):
+    """The routes counted since `before`, as {family: launches}."""
+    after = _capi.dense_routes()
+    return {k: after[k] - before[k] for k in after if after[k] != before[k]}
+
+
+def act64(v, act):
+    with np.errstate(over="ignore"):
+        return [v, np.where(v > 0, v, np.expm1(np.minimum(v, 0))), np.tanh(v), 1.0 / (1.0 + np.exp(-v)),
+                np.maximum(v, 0) + np.log1p(np.exp(-np.abs(v))) + 1e-2][act]
+
+
+RICH = ((20, 5, False), (33, 1, False), (27, 1, True))   # (width, row divisor, broadcast) per segment
+SCALE, SCALE_DEV = 0.5, 1.25
+
+
+class Fwd:
+    """One layer's operands on the device (sized for `M` rows; any smaller row count launches on the same buffers) and both
+    descriptions of it: rich, and plain (what k_linear_big's vector fast path takes)."""
+
+    def __init__(self, seed, M, segs, N):
+        rng = np.random.default_rng(seed)
+        self.M, self.segs, self.N = M, segs, N
+        self.K = sum(w for w, _, _ in segs)
+        self.x, self.ld = [], []
+        for width, rdiv, bcast in segs:
+            wpad = (width + 3) & ~3
+            ld = 0 if bcast else wpad + 4
+            buf = rng.standard_normal((1 if bcast else -(-M // rdiv), max(ld, wpad))).astype(np.float32)
+            buf[:, width:] *= 1e3   # the pad columns: finite by contract, and nothing may come of them
+            self.x.append(buf)
+            self.ld.append(ld)
+        self.w = (rng.standard_normal((self.K, N)) / np.sqrt(self.K)).astype(np.float32)
+        self.b = rng.standard_normal(N).astype(np.float32)
+        self.add_ld = ((N + 3) & ~3) + 4
+        self.add = rng.standard_normal((M, self.add_ld)).astype(np.float32)
+        self.d_x = [dev(x) for x in self.x]
+        self.d_w, self.d_b, self.d_add = dev(self.w), dev(self.b), dev(self.add)
+        self.d_scale = dev(np.array([SCALE_DEV], np.float32))
+        kc, nt = sum((w + 15) // 16 for w, _, _ in segs), (N + 15) // 16
+        self.kc, self.nt = kc, nt
+        self.scratch = torch.empty(2 * nt * kc * 256 + 32 * nt + 256, dtype=torch.float32, device="cuda")
+
+    def describe(self, rich):
+        N = self.N
+        if rich:
+            return dict(add_n=N - 7, add_rdiv=3, act_a=ELU, act_b=SOFTPLUS_MIN, act_split=N // 2 + 1)
+        return dict(add_n=(N - 8) & ~3, add_rdiv=1, act_a=ELU, act_b=NONE, act_split=1 << 30)
+
+    def reference(self, rich, M):
+        """(out [M, N], max |pre-activation|) in float64."""
+        d = self.describe(rich)
+        rows = np.arange(M)
+        X = np.concatenate([x[np.zeros(M, int) if bcast else rows // rdiv, :width].astype(F64)
+                            for x, (width, rdiv, bcast) in zip(self.x, self.segs)], 1)
+        pre = X @ self.w.astype(F64) + self.b.astype(F64)
+        pre[:, :d["add_n"]] += self.add[rows // d["add_rdiv"], :d["add_n"]].astype(F64)
+        n = np.arange(self.N)
+        out = np.where(n < d["act_split"], act64(pre, d["act_a"]), act64(pre, d["act_b"]))
+        return out * SCALE * SCALE_DEV, float(np.abs(pre).max())
+
+    def contract(self, rich, M, out, out_ld, seg_ptr=None, seg_ld=None):
+        d = self.describe(rich)
+        c = _capi.SqairDenseContract()
+        c.nseg = len(self.segs)
+        for i, (width, rdiv, _) in enumerate(self.segs):
+            c.seg[i].p = self.d_x[i].data_ptr() if seg_ptr is None or i else seg_ptr
+            c.seg[i].ld = self.ld[i] if seg_ld is None or i else seg_ld
+            c.seg[i].width, c.seg[i].rdiv = width, rdiv
+        c.w, c.b, c.add = self.d_w.data_ptr(), self.d_b.data_ptr(), self.d_add.data_ptr()
+        c.add_ld, c.add_n, c.add_rdiv = self.add_ld, d["add_n"], d["add_rdiv"]
+        c.act_a, c.act_b, c.act_split = d["act_a"], d["act_b"], d["act_split"]
+        c.scale, c.scale_ptr = SCALE, self.d_scale.data_ptr()
+        c.out, c.out_ld, c.M, c.N = out.data_ptr(), out_ld, M, self.N
+        c.scratch, c.scratch_bytes = self.scratch.data_ptr(), self.scratch.numel() * 4
+        return c
+
+    def bar(self, max_pre):
+        return 2e-5 * max(1.0, np.sqrt(self.K / 256.0)) * SCALE * SCALE_DEV * max(1.0, max_pre)
+
+
+def run_fwd(handle, case, L, rich, M, out_pad, family, ref=None):
+    """One launch: route, untouched pad columns, finite and within the bar.  Returns the output's first N columns."""
+    lib, h = handle
+    out_ld = L.N + out_pad
+    out = torch.full((M, out_ld), float("nan"), device="cuda")
+    before = _capi.dense_routes()
+    rc = lib.sqair_linear_contract_test(h, C.byref(L.contract(rich, M, out, out_ld)), stream())
+    assert rc == 0, lib.sqair_last_error(h)
+    routes = took(before)
+    assert routes == {family: 1}, "{}: meant for {}, the launcher took {}".format(case, family, routes)
+    got = out.cpu().numpy()
+    assert np.array_equal(bits(got[:, L.N:]), bits(np.full((M, out_pad), np.nan))), case + ": columns beyond N were written"
+    ref, max_pre = L.reference(rich, M) if ref is None else ref
+    assert np.isfinite(got[:, :L.N]).all(), (case, np.argwhere(~np.isfinite(got[:, :L.N]))[:4].tolist())
+    err, bar = float(np.abs(got[:, :L.N].astype(F64) - ref).max()), L.bar(max_pre)
+    print("{}: {} max err {:.3e} bar {:.3e} (max |pre| {:.2f})".format(case, family, err, bar, max_pre))
+    dense_record(case, family=family, err=err, bar=bar, ratio=err / bar)
+    assert err < bar, (case, err, bar)
+    return got[:, :L.N]
+
+
+def segments(kc, nseg):
+    """`nseg` segments of `kc` K chunks in all, none a multiple of 16 (nor, but one, of 4) wide; kc = 7 in three segments is the
+    rich description itself."""
+    if (kc, nseg) == (7, 3):
+        return RICH
+    chunks = [kc // nseg + (1 if i < kc % nseg else 0) for i in range(nseg)]
+    kinds = ((5, False), (1, True)) if nseg == 2 else ((5, False), (1, False), (1, True), (2, False))
+    return tuple((16 * c - trim, rdiv, bcast) for c, trim, (rdiv, bcast) in zip(chunks, (12, 15, 5, 3), kinds))

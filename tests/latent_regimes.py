@@ -356,7 +356,7 @@ def bwd_noise_seed0(edits):
     return BWD_NOISE_SEED0.get(tuple(edits), 100)
 
 
-GRAD_TIGHT, GRAD_LOOSE = 5e-4, 3e-3    # tests/test_hip_backward.py: TIGHT; LOOSE for the two `*.transform.scale_offset` scalars
+GRAD_TIGHT, GRAD_LOOSE = 5e-4, 3e-3    # tests/pass_cases.py: TIGHT; LOOSE for the two `*.transform.scale_offset` scalars
 GRAD_LOOSE_NAMES = ("disc.transform.scale_offset", "prop.transform.scale_offset")
 
 # the stream, the carried training chunk, the particle filter and the forecast (sizes and seeds: the helpers of those suites)
@@ -373,11 +373,11 @@ GRAPH_FORWARD, GRAPH_TRAIN = "combined", "combined"
 # ----------------------------------------------------------------------------- distances, in the suites' own scalings
 SCALARS = ("elbo_vae", "elbo_iwae", "data_ll", "kl", "log_p_z", "log_q_z_given_x")
 VECTORS = ("log_weights", "elbo_iwae_per_example")
-OUTPUT_BAR, BOUND_BAR = 5e-4, 1e-4     # tests/test_hip_forward._check_against: every output scaled; the bounds relative
+OUTPUT_BAR, BOUND_BAR = 5e-4, 1e-4     # tests/pass_cases.check_against: every output scaled; the bounds relative
 
 
 def output_distances(model, ref):
-    """Per public output: max |model - ref| / max(|ref|, 1) (the scaling of `_check_against`); model, ref: oracle models."""
+    """Per public output: max |model - ref| / max(|ref|, 1) (the scaling of `check_against`); model, ref: oracle models."""
     out = {}
     for k, v in ref.outputs.items():
         if not k.startswith("_"):
@@ -387,7 +387,7 @@ def output_distances(model, ref):
 
 
 def bound_distances(model, ref):
-    """The bounds in `_check_against`'s scalings: the vectors as max |d| / max |ref|, the scalars as |d| / max(|ref|, 1)."""
+    """The bounds in `check_against`'s scalings: the vectors as max |d| / max |ref|, the scalars as |d| / max(|ref|, 1)."""
     out = {}
     for k in VECTORS:
         want = _np(getattr(ref, k))
@@ -412,7 +412,7 @@ def gradient_report(grads, ref_grads):
 
 
 def gradient_rel(report):
-    """{name: error / max(|grad|max, 1e-4 of the pass's largest gradient)}: `_check_report`'s `rel`."""
+    """{name: error / max(|grad|max, 1e-4 of the pass's largest gradient)}: `check_report`'s `rel`."""
     gmax = max(s for _, _, s in report)
     return {n: e / max(s, 1e-4 * gmax) for n, e, s in report}
 

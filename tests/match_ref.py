@@ -9,6 +9,8 @@ the device's own matching after judging it: equally optimal assignments tie and 
 events and the memory are compared with a reference run on the device's pairs, and the pairs themselves are held to feasibility,
 the optimal cardinality and the optimal sum of q within the rounding of q."""
 import contextlib
+import json
+import os
 
 import numpy as np
 from scipy.optimize import linear_sum_assignment
@@ -20,6 +22,7 @@ from tests import traj_score_ref as TR
 UNIT = 1048576.0        # q counts 2^-20
 BIG = 1 << 25           # one pair more outweighs every sum of q: at most 16 pairs of q <= 2^20
 NEAR = 1e-5
+PARITY_DIR_ENV = "SQAIR_PARITY_DIR"
 
 
 def q_of(iou):
@@ -268,3 +271,18 @@ class IdentityFollower(object):
     def upto(self):
         """[frames, B]: the frames before each lane's first fragile one."""
         return np.arange(self.frames)[:, None] < np.where(self.first < 0, self.frames, self.first)[None, :]
+
+
+def record(section, case, **figures):
+    """Adds ``figures`` to match_parity.json under SQAIR_PARITY_DIR (nothing without it)."""
+    where = os.environ.get(PARITY_DIR_ENV)
+    if not where:
+        return
+    path = os.path.join(where, "match_parity.json")
+    try:
+        os.makedirs(where, exist_ok=True)
+        data = json.load(open(path)) if os.path.exists(path) else {}
+        data.setdefault(section, {}).setdefault(case, {}).update(figures)
+        json.dump(data, open(path, "w"), indent=1, sort_keys=True)
+    except OSError:
+        pass

@@ -12,6 +12,8 @@ propagation_core, against central differences, and the Cholesky index order agai
 
 The metric and the sentinel helpers at the end are shared with the GPU tests, those of the log-probability kernels included
 (tests/logprob_ref.py, tests/test_logprob_kernels.py)."""
+import contextlib
+
 import numpy as np
 import torch
 
@@ -332,3 +334,24 @@ class Pitched:
         own[1:1 + self.rows, self.offset:self.offset + self.width] = True if written is None else written
         a, b = np.asarray(after, np.float32).reshape(self.host.shape).view(np.uint32), self.before.view(np.uint32)
         return bool(np.array_equal(a[~own], b[~own]))
+
+
+@contextlib.contextmanager
+def recorded():
+    """Every call of oracle.linear (its output) and oracle.mlp2_hidden (its input), by layer name, in call order."""
+    rec = {}
+    lin, mlp = O.linear, O.mlp2_hidden
+
+    def linear(P, name, x):
+        y = lin(P, name, x)
+        rec.setdefault(name, []).append(y)
+        return y
+
+    def mlp2_hidden(P, name, x):
+        rec.setdefault(name + ":in", []).append(x)
+        return mlp(P, name, x)
+    O.linear, O.mlp2_hidden = linear, mlp2_hidden
+    try:
+        yield rec
+    finally:
+        O.linear, O.mlp2_hidden = lin, mlp

@@ -18,41 +18,23 @@ import pytest
 import torch
 
 from sqair_amd.model import SqairCore
-from sqair_amd.stream import SqairStream
-from tests.test_score_stream import B, G, HW, IOU, OUTS, SMC_OUTS, _host, _make_truth, _setup
+from tests.stream_harness import OUTS, SCORE, SMC_OUTS, core as make_core, host, make_truth, same_bytes, setup, stream
 
 pytestmark = pytest.mark.gpu
 
+HW, FLAGS, B, G, IOU = SCORE.HW, SCORE.FLAGS, SCORE.B, SCORE.G, SCORE.IOU
 STEPS = 6
 
 
-def _raw(a):
-    """Anything a stream returns as the bytes it holds (NaN == NaN, -0.0 != 0.0)."""
-    if isinstance(a, torch.Tensor):
-        a = a.detach().cpu().numpy()
-    return np.ascontiguousarray(np.asarray(a)).view(np.uint8)
-
-
-def _same(a, b, where):
-    assert set(a) == set(b), where
-    for k in a:
-        if isinstance(a[k], dict):
-            _same(a[k], b[k], where + (k,))
-        else:
-            x, y = _raw(a[k]), _raw(b[k])
-            assert x.shape == y.shape and np.array_equal(x, y), where + (k,)
-
-
 def _run(F, P, obs, noise, uniforms, observed, truth, use_graph):
-    core = SqairCore(F, HW, options={"slot_chain": 1})
-    core.set_params(P)
-    st = SqairStream(core, B, outputs=OUTS, use_graph=use_graph, resample="systematic", ess_frac=0.5, seed=5, history=4, missing=True,
-                     estimate=True, estimate_iou=IOU, estimate_layers=True, score=truth is not None, score_iou=IOU, score_truth=G,
-                     identity=True, score_ids="row" if truth is None else "lane")
+    core = make_core(F, HW, P, options={"slot_chain": 1})
+    st = stream(core, B, outputs=OUTS, use_graph=use_graph, resample="systematic", ess_frac=0.5, seed=5, history=4, missing=True,
+                estimate=True, estimate_iou=IOU, estimate_layers=True, score=truth is not None, score_iou=IOU, score_truth=G,
+                identity=True, score_ids="row" if truth is None else "lane")
     outs = []
     for t in range(STEPS):
         kw = {} if truth is None else dict(truth=truth[t])
-        outs.append(_host(st.step(obs[t:t + 1], noise=noise[t:t + 1], uniforms=uniforms[t], observed=observed[t:t + 1], **kw)))
+        outs.append(host(st.step(obs[t:t + 1], noise=noise[t:t + 1], uniforms=uniforms[t], observed=observed[t:t + 1], **kw)))
         core.check_chain()      # every chain launch of the step completed
     # the chain really ran: the workspace was carved for it (slot buffers kept apart per frame and slot, control blocks) ...
     plain = SqairCore(F, HW)
@@ -68,23 +50,23 @@ def _run(F, P, obs, noise, uniforms, observed, truth, use_graph):
 
 
 def test_graph_and_eager_streams_agree_with_every_effect_on():
-    F, P, obs, noise = _setup(STEPS)
+    F, P, obs, noise = setup(FLAGS, B, STEPS, HW)
     rng = np.random.default_rng(23)
     uniforms = rng.uniform(size=(STEPS, B)).astype(np.float32)
     observed = np.ones((STEPS, B), bool)
     observed[3, 1] = False      # one lane coasts in one step
     first = _run(F, P, obs, noise, uniforms, observed, None, True)
-    truth = _make_truth(first["outs"], 1)
+    truth = make_truth(first["outs"], 1)
     truth[0]["valid"][:] = 1      # (the step a pre-pass would repeat is scored in every lane)
     graph = _run(F, P, obs, noise, uniforms, observed, truth, True)
     eager = _run(F, P, obs, noise, uniforms, observed, truth, False)
     assert graph["nodes"] == first["nodes"] + 1, (first["nodes"], graph["nodes"])      # (the score's one node)
     for t in range(STEPS):
         assert set(OUTS + SMC_OUTS + ("lane", "observed")) <= set(graph["outs"][t])
-        _same(graph["outs"][t], eager["outs"][t], ("step", t))
+        same_bytes(graph["outs"][t], eager["outs"][t], where=("step", t))
     for k in ("score", "identities", "track_table", "tracks", "ring", "state", "log_weight_sum", "log_evidence"):
         g, e = graph[k], eager[k]
-        _same(g if isinstance(g, dict) else {k: g}, e if isinstance(e, dict) else {k: e}, (k,))
+        same_bytes(g if isinstance(g, dict) else {k: g}, e if isinstance(e, dict) else {k: e}, where=(k,))
     assert sum(int(o["resampled"].sum()) for o in graph["outs"]) > 0      # the resampler went
     assert not graph["outs"][3]["observed"][0, 1] and graph["outs"][3]["observed"].sum() == B - 1
     # every scored step -- a step whose truth is valid for the lane -- counted once per lane: a pre-pass that scored would count the

@@ -28,154 +28,11 @@ import pytest
 import torch
 
 from sqair_amd import _capi
-from sqair_amd.flags import make_flags
-from sqair_amd.model import make_config
 from tests.hip_util import dev as _dev, stream
-from tests.kernel_unit import F64, bits as _bits, merge_parity
+from tests.kernel_unit import (ELU, F64, NONE, RICH, SIGMOID, SOFTPLUS_MIN, TANH, Fwd, act64, bits as _bits,
+                               dense_handle as handle, dense_record, run_fwd, segments as _segments, took as _took)  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-NONE, ELU, TANH, SIGMOID, SOFTPLUS_MIN = range(5)
-
-
-def _record(case, **figures):
-    def update(data):
-        data["build_id"] = _capi.build_id()
-        data["device"] = torch.cuda.get_device_name(0)
-        data["cases"][case] = figures
-
-    merge_parity("dense_contract_parity.json", lambda: {
-        "note": "per case of tests/test_dense_contract.py: the kernel family the launcher chose, the largest error against the "
-                "float64 reference, the bar and err / bar.  Forward errors are absolute; dX errors are relative to the "
-                "destination's largest reference value; GRU destinations add `f32_formula_err` (the same formulas in numpy "
-                "float32 from the rounded float64 GEMM result) and `allowance` = 4 x that, which is part of their bar.",
-        "cases": {}}, update)
-
-
-@pytest.fixture(scope="module")
-def handle():
-    lib = _capi.lib()
-    cfg = make_config(make_flags(k_particles=3, n_steps_per_image=4), (50, 50))
-    h = C.c_void_p()
-    assert lib.sqair_create(C.byref(cfg), C.byref(h)) == 0
-    yield lib, h
-    lib.sqair_destroy(h)
-
-
-def _took(before):
-    """The routes counted since `before`, as {family: launches}."""
-    after = _capi.dense_routes()
-    return {k: after[k] - before[k] for k in after if after[k] != before[k]}
-
-
-def _act64(v, act):
-    with np.errstate(over="ignore"):
-        return [v, np.where(v > 0, v, np.expm1(np.minimum(v, 0))), np.tanh(v), 1.0 / (1.0 + np.exp(-v)),
-                np.maximum(v, 0) + np.log1p(np.exp(-np.abs(v))) + 1e-2][act]
-
-
-# ------------------------------------------------------------------------------------------------------------------------------
-# forward
-# ------------------------------------------------------------------------------------------------------------------------------
-RICH = ((20, 5, False), (33, 1, False), (27, 1, True))   # (width, row divisor, broadcast) per segment
-SCALE, SCALE_DEV = 0.5, 1.25
-
-
-class _Fwd:
-    """One layer's operands on the device (sized for `M` rows; any smaller row count launches on the same buffers) and both
-    descriptions of it: rich, and plain (what k_linear_big's vector fast path takes)."""
-
-    def __init__(self, seed, M, segs, N):
-        rng = np.random.default_rng(seed)
-        self.M, self.segs, self.N = M, segs, N
-        self.K = sum(w for w, _, _ in segs)
-        self.x, self.ld = [], []
-        for width, rdiv, bcast in segs:
-            wpad = (width + 3) & ~3
-            ld = 0 if bcast else wpad + 4
-            buf = rng.standard_normal((1 if bcast else -(-M // rdiv), max(ld, wpad))).astype(np.float32)
-            buf[:, width:] *= 1e3   # the pad columns: finite by contract, and nothing may come of them
-            self.x.append(buf)
-            self.ld.append(ld)
-        self.w = (rng.standard_normal((self.K, N)) / np.sqrt(self.K)).astype(np.float32)
-        self.b = rng.standard_normal(N).astype(np.float32)
-        self.add_ld = ((N + 3) & ~3) + 4
-        self.add = rng.standard_normal((M, self.add_ld)).astype(np.float32)
-        self.d_x = [_dev(x) for x in self.x]
-        self.d_w, self.d_b, self.d_add = _dev(self.w), _dev(self.b), _dev(self.add)
-        self.d_scale = _dev(np.array([SCALE_DEV], np.float32))
-        kc, nt = sum((w + 15) // 16 for w, _, _ in segs), (N + 15) // 16
-        self.kc, self.nt = kc, nt
-        self.scratch = torch.empty(2 * nt * kc * 256 + 32 * nt + 256, dtype=torch.float32, device="cuda")
-
-    def describe(self, rich):
-        N = self.N
-        if rich:
-            return dict(add_n=N - 7, add_rdiv=3, act_a=ELU, act_b=SOFTPLUS_MIN, act_split=N // 2 + 1)
-        return dict(add_n=(N - 8) & ~3, add_rdiv=1, act_a=ELU, act_b=NONE, act_split=1 << 30)
-
-    def reference(self, rich, M):
-        """(out [M, N], max |pre-activation|) in float64."""
-        d = self.describe(rich)
-        rows = np.arange(M)
-        X = np.concatenate([x[np.zeros(M, int) if bcast else rows // rdiv, :width].astype(F64)
-                            for x, (width, rdiv, bcast) in zip(self.x, self.segs)], 1)
-        pre = X @ self.w.astype(F64) + self.b.astype(F64)
-        pre[:, :d["add_n"]] += self.add[rows // d["add_rdiv"], :d["add_n"]].astype(F64)
-        n = np.arange(self.N)
-        out = np.where(n < d["act_split"], _act64(pre, d["act_a"]), _act64(pre, d["act_b"]))
-        return out * SCALE * SCALE_DEV, float(np.abs(pre).max())
-
-    def contract(self, rich, M, out, out_ld, seg_ptr=None, seg_ld=None):
-        d = self.describe(rich)
-        c = _capi.SqairDenseContract()
-        c.nseg = len(self.segs)
-        for i, (width, rdiv, _) in enumerate(self.segs):
-            c.seg[i].p = self.d_x[i].data_ptr() if seg_ptr is None or i else seg_ptr
-            c.seg[i].ld = self.ld[i] if seg_ld is None or i else seg_ld
-            c.seg[i].width, c.seg[i].rdiv = width, rdiv
-        c.w, c.b, c.add = self.d_w.data_ptr(), self.d_b.data_ptr(), self.d_add.data_ptr()
-        c.add_ld, c.add_n, c.add_rdiv = self.add_ld, d["add_n"], d["add_rdiv"]
-        c.act_a, c.act_b, c.act_split = d["act_a"], d["act_b"], d["act_split"]
-        c.scale, c.scale_ptr = SCALE, self.d_scale.data_ptr()
-        c.out, c.out_ld, c.M, c.N = out.data_ptr(), out_ld, M, self.N
-        c.scratch, c.scratch_bytes = self.scratch.data_ptr(), self.scratch.numel() * 4
-        return c
-
-    def bar(self, max_pre):
-        return 2e-5 * max(1.0, np.sqrt(self.K / 256.0)) * SCALE * SCALE_DEV * max(1.0, max_pre)
-
-
-def _run_fwd(handle, case, L, rich, M, out_pad, family, ref=None):
-    """One launch: route, untouched pad columns, finite and within the bar.  Returns the output's first N columns."""
-    lib, h = handle
-    out_ld = L.N + out_pad
-    out = torch.full((M, out_ld), float("nan"), device="cuda")
-    before = _capi.dense_routes()
-    rc = lib.sqair_linear_contract_test(h, C.byref(L.contract(rich, M, out, out_ld)), stream())
-    assert rc == 0, lib.sqair_last_error(h)
-    took = _took(before)
-    assert took == {family: 1}, "{}: meant for {}, the launcher took {}".format(case, family, took)
-    got = out.cpu().numpy()
-    assert np.array_equal(_bits(got[:, L.N:]), _bits(np.full((M, out_pad), np.nan))), case + ": columns beyond N were written"
-    ref, max_pre = L.reference(rich, M) if ref is None else ref
-    assert np.isfinite(got[:, :L.N]).all(), case
-    err, bar = float(np.abs(got[:, :L.N].astype(F64) - ref).max()), L.bar(max_pre)
-    print("{}: {} max err {:.3e} bar {:.3e} (max |pre| {:.2f})".format(case, family, err, bar, max_pre))
-    _record(case, family=family, err=err, bar=bar, ratio=err / bar)
-    assert err < bar, (case, err, bar)
-    return got[:, :L.N]
-
-
-def _segments(kc, nseg):
-    """`nseg` segments of `kc` K chunks in all, none a multiple of 16 (nor, but one, of 4) wide; kc = 7 in three segments is the
-    rich description itself."""
-    if (kc, nseg) == (7, 3):
-        return RICH
-    chunks = [kc // nseg + (1 if i < kc % nseg else 0) for i in range(nseg)]
-    kinds = ((5, False), (1, True)) if nseg == 2 else ((5, False), (1, False), (1, True), (2, False))
-    return tuple((16 * c - trim, rdiv, bcast) for c, trim, (rdiv, bcast) in zip(chunks, (12, 15, 5, 3), kinds))
-
 
 # per_wave = ceil(kc / 4) selects the instantiation: 1 .. 9, and the looped 10 from kc = 37 (kc = 41: two trips for wave 0)
 SPLITK = [(1, 1), (2, 2), (3, 3), (4, 4), (7, 3), (9, 2), (13, 4), (17, 1), (21, 3), (25, 2), (29, 4), (33, 3), (37, 1), (41, 4)]
@@ -186,9 +43,9 @@ SPLITK = [(1, 1), (2, 2), (3, 3), (4, 4), (7, 3), (9, 2), (13, 4), (17, 1), (21,
 def test_forward_split_k(handle, M, kc, nseg):
     i = SPLITK.index((kc, nseg))
     N = (45, 23)[i % 2]
-    L = _Fwd(1000 + kc, M, _segments(kc, nseg), N)
+    L = Fwd(1000 + kc, M, _segments(kc, nseg), N)
     assert L.kc == kc and len(L.segs) == nseg
-    _run_fwd(handle, "fwd split-K kc={} nseg={} M={}".format(kc, nseg, M), L, True, M, (4, 1)[(i + (M == 160)) % 2], "fwd_splitk")
+    run_fwd(handle, "fwd split-K kc={} nseg={} M={}".format(kc, nseg, M), L, True, M, (4, 1)[(i + (M == 160)) % 2], "fwd_splitk")
 
 
 # the smallest shapes the dispatch sends to each family (M, segments, N); the big shapes by pick_big_shape's cost model
@@ -207,22 +64,22 @@ THROUGHPUT = [
 
 @pytest.mark.parametrize("family,M,segs,N", THROUGHPUT, ids=["{}-{}x{}".format(f, m, n) for f, m, _, n in THROUGHPUT])
 def test_forward_throughput_kernels(handle, family, M, segs, N):
-    L = _Fwd(M + N, M, segs, N)
+    L = Fwd(M + N, M, segs, N)
     case = "fwd {} M={} K={} N={}".format(family, M, L.K, N)
     ref = L.reference(True, M)
-    _run_fwd(handle, case + " rich out_ld=N+4", L, True, M, 4, family, ref)
-    _run_fwd(handle, case + " rich out_ld=N+1", L, True, M, 1, family, ref)
+    run_fwd(handle, case + " rich out_ld=N+4", L, True, M, 4, family, ref)
+    run_fwd(handle, case + " rich out_ld=N+1", L, True, M, 1, family, ref)
     if family.startswith("fwd_big"):   # the vector fast path, with an addend
-        _run_fwd(handle, case + " plain out_ld=N+4", L, False, M, 4, family)
+        run_fwd(handle, case + " plain out_ld=N+4", L, False, M, 4, family)
 
 
 @pytest.mark.parametrize("N,big,small", [(256, (6400, "fwd_big_4x2"), (6100, "fwd_big_3x2")),
                                          (128, (10000, "fwd_big_3x2"), (8192, "fwd_big_2x2"))])
 def test_tile_shape_does_not_change_a_bit(handle, N, big, small):
     """sq_launch_linear / pick_big_shape: every tile shape of k_linear_big accumulates an output in the same order."""
-    L = _Fwd(7 * N, big[0], RICH, N)
-    y_big = _run_fwd(handle, "bits N={} M={}".format(N, big[0]), L, False, big[0], 4, big[1])
-    y_small = _run_fwd(handle, "bits N={} M={}".format(N, small[0]), L, False, small[0], 4, small[1])
+    L = Fwd(7 * N, big[0], RICH, N)
+    y_big = run_fwd(handle, "bits N={} M={}".format(N, big[0]), L, False, big[0], 4, big[1])
+    y_small = run_fwd(handle, "bits N={} M={}".format(N, small[0]), L, False, small[0], 4, small[1])
     differ = _bits(y_big[:small[0]]) != _bits(y_small)
     assert not differ.any(), "{} of {} outputs differ between {} and {}".format(int(differ.sum()), differ.size, big[1], small[1])
 
@@ -231,7 +88,7 @@ def test_forward_refusals(handle):
     """A segment base off 16 bytes, or a pitch that is no multiple of 4 floats: -5, nothing launched, nothing counted."""
     lib, h = handle
     M, N = 37, 45
-    L = _Fwd(5, M + 1, RICH, N)
+    L = Fwd(5, M + 1, RICH, N)
     out = torch.full((M, N + 4), float("nan"), device="cuda")
     for what, kw in (("base", dict(seg_ptr=L.d_x[0].data_ptr() + 4)), ("pitch", dict(seg_ld=L.ld[0] + 1))):
         before = _capi.dense_routes()
@@ -264,7 +121,7 @@ def _saved_output(rng, M, ld, acts):
     out = np.empty((M, ld), np.float32)
     for c in range(ld):
         a = acts[c] if c < len(acts) else NONE
-        out[:, c] = _act64(pre[:, c], a).astype(np.float32)
+        out[:, c] = act64(pre[:, c], a).astype(np.float32)
         out[0, c], out[1, c], out[M - 1, c] = EDGES[a][0], EDGES[a][1], EDGES[a][c % 2]
     return out
 
@@ -381,7 +238,7 @@ def _check_ranges(case, D, spec, v, family):
             res.append(_check_dest(case, "range {} dst2".format(i), r["d_dst2"].cpu().numpy(), r["init2"], M, 0, n, ref, _dx_bar(D.width)))
             assert np.array_equal(_bits(r["d_dst2"].cpu().numpy()[:M, :n]), _bits(r["d_dst"].cpu().numpy()[:M, :n]))
         worst = max([worst] + res, key=lambda eb: eb[0] / eb[1])
-    _record(case, family=family, err=worst[0], bar=worst[1], ratio=worst[0] / worst[1])
+    dense_record(case, family=family, err=worst[0], bar=worst[1], ratio=worst[0] / worst[1])
 
 
 NCH_OF = {1: 1, 2: 2, 3: 3, 4: 4, 5: 5, 6: 6, 7: 7, 8: 8, 9: 9, 10: 12, 11: 12, 12: 12}
@@ -507,7 +364,7 @@ def test_dx_gru_epilogues(handle, mode, nh, M):
                 res["d_h"] = _check_dest(case, "d_h", got_dh, dh_init, M, 0, nh, ref["dh"], bar_rel, allow["dh"])
                 k = max(res, key=lambda n: res[n][0] / res[n][1])
                 key = {"dpre1 z": "dz", "dup z": "dz", "dpre1 h": "dc", "dup h": "dc", "dpre1 r": "dr", "dup r": "dr", "d_h": "dh"}[k]
-                _record(case, family=family, destination=k, err=res[k][0], bar=res[k][1], ratio=res[k][0] / res[k][1],
+                dense_record(case, family=family, destination=k, err=res[k][0], bar=res[k][1], ratio=res[k][0] / res[k][1],
                         f32_formula_err=allow[key] / 4.0, allowance=allow[key])
 
 

@@ -10,49 +10,21 @@ import numpy as np
 import pytest
 import torch
 
-from sqair_amd.data import make_sequences, to_float
-from sqair_amd.flags import make_flags
-from sqair_amd.model import SqairCore
-from sqair_amd.stream import SqairStream
 from tests import estimate_check as EC
 from tests import estimate_ref as E
-from tests.hip_util import draw_noise, params32
+from tests.stream_harness import EST_KEYS, OUTS, SCORE, SMC_OUTS, cap, carried_in, host, same_bits, same_values, setup, stream
 
 pytestmark = pytest.mark.gpu
 
-OUTS = ("what", "where", "presence", "obj_id", "log_weights_per_timestep")
-SMC_OUTS = ("ess", "resampled", "log_evidence", "ancestors")
-HW = (50, 50)
-FLAGS = dict(k_particles=3, n_steps_per_image=3)
-B = 4
-IOU = 0.5
+HW, FLAGS, B, IOU = SCORE.HW, SCORE.FLAGS, SCORE.B, SCORE.IOU
 
 
 def _setup(T, flags=FLAGS, seed=11):
-    F = make_flags(**flags)
-    obs = to_float(make_sequences(B, T=T, canvas=HW, seed=seed)["imgs"])
-    P = params32(F, HW, 3, 0.05, obs.mean((0, 1)))
-    noise = draw_noise(np.random.default_rng(seed + 1), T, B * int(F.k_particles), int(F.n_steps_per_image), 4 + int(F.n_what) + 1)
-    return F, P, obs, noise
+    return setup(flags, B, T, HW, seed)
 
 
 def _stream(F, P, **kw):
-    core = SqairCore(F, HW)
-    core.set_params(P)
-    return SqairStream(core, B, outputs=kw.pop("outputs", OUTS), **kw)
-
-
-def _host(out):
-    torch.cuda.synchronize()
-    return {k: ({n: v.cpu().numpy() for n, v in x.items()} if isinstance(x, dict) else x.cpu().numpy()) for k, x in out.items()}
-
-
-def _carried_in(st):
-    """The log weights the next step's rows carry into it: log_weight_sum through the pending source map (a reset or resample armed
-    on the host; with SMC the device buffers already hold it)."""
-    lw = st.log_weight_sum.cpu().numpy()
-    m = st.carried.pending()
-    return np.where(m >= 0, lw[np.maximum(m, 0)], np.float32(0.0)).astype(np.float32)
+    return stream((F, HW, P), B, outputs=kw.pop("outputs", OUTS), **kw)
 
 
 def _check_step(st, o, lw0, counts, canvas=False):
@@ -65,8 +37,7 @@ def _check_step(st, o, lw0, counts, canvas=False):
 
 
 def _cap(counts):
-    print(counts)
-    assert counts["decisions"] > 0 and counts["skipped"] <= 0.01 * counts["decisions"], counts
+    cap(counts)
     assert counts["agreeing"] > 0
 
 
@@ -80,15 +51,12 @@ def test_the_estimate_changes_nothing_else():
     eager = _stream(F, P, estimate=True, estimate_iou=IOU, use_graph=False, **smc)
     went = 0
     for t in range(T):
-        a, b, c = (_host(s.step(obs[t:t + 1], noise=noise[t:t + 1])) for s in (off, on, eager))
+        a, b, c = (host(s.step(obs[t:t + 1], noise=noise[t:t + 1])) for s in (off, on, eager))
         assert "lane" not in a
-        for k in OUTS + SMC_OUTS:
-            assert np.array_equal(a[k], b[k], equal_nan=True), (t, k)
+        same_values(a, b, OUTS + SMC_OUTS, t)
         for k in ("state", "log_weight_sum", "log_z", "log_evidence", "ess", "u", "resampled", "_src"):
             assert torch.equal(getattr(off, k), getattr(on, k)), (t, k)
-        for k, v in b["lane"].items():    # eager and graph: the same bits
-            assert np.array_equal(v.view(np.uint32 if v.dtype == np.float32 else v.dtype),
-                                  c["lane"][k].view(np.uint32 if v.dtype == np.float32 else v.dtype)), (t, k)
+        same_bits(b["lane"], c["lane"], b["lane"].keys(), t)    # eager and graph: the same bits
         went += int(b["resampled"].sum())
     assert went > 0
     assert on.core.graph_nodes() == off.core.graph_nodes() + 1
@@ -104,10 +72,9 @@ def test_lane_estimate_against_reference(resample, frac):
     st = _stream(F, P, estimate=True, estimate_iou=IOU, resample=resample, ess_frac=frac, seed=17)
     counts = EC.new_counts()
     for t in range(T):
-        lw0 = _carried_in(st)
-        o = _host(st.step(obs[t:t + 1], noise=noise[t:t + 1]))
-        assert set(o["lane"]) == {"best_row", "weights", "ess", "count_prob", "expected_count", "map_count", "presence", "obj_id",
-                                  "where", "what", "box", "support", "box_mean"}
+        lw0 = carried_in(st)
+        o = host(st.step(obs[t:t + 1], noise=noise[t:t + 1]))
+        assert set(o["lane"]) == EST_KEYS
         assert o["lane"]["weights"].shape == (1, B, st.K) and o["lane"]["box"].shape == (1, B, 3, 4)
         _check_step(st, o, lw0, counts)
         if resample is not None:    # the resampler's ESS of the same rows, bit for bit
@@ -127,8 +94,8 @@ def test_frames_per_step_uses_prefix_weights(resample):
     counts = EC.new_counts()
     differ = False
     for s in range(steps):
-        lw0 = _carried_in(st)
-        o = _host(st.step(obs[s * Ts:(s + 1) * Ts], noise=noise[s * Ts:(s + 1) * Ts]))
+        lw0 = carried_in(st)
+        o = host(st.step(obs[s * Ts:(s + 1) * Ts], noise=noise[s * Ts:(s + 1) * Ts]))
         ref = _check_step(st, o, lw0, counts)
         # the reference's frame t accumulates frames 0..t only: the estimate of frame 0 is that of a one-frame step
         one = E.estimate(o["where"][:1], o["presence"][:1], o["obj_id"][:1], o["log_weights_per_timestep"][:1], st.K, HW, IOU, lw0=lw0)
@@ -152,8 +119,8 @@ def test_a_coasted_lane_keeps_its_weights():
     coasted = 0
     for t in range(T):
         observed = np.ones(B, bool) if t < 2 else rng.uniform(size=B) < 0.6
-        lw0 = _carried_in(st)
-        o = _host(st.step(obs[t:t + 1], noise=noise[t:t + 1], observed=observed))
+        lw0 = carried_in(st)
+        o = host(st.step(obs[t:t + 1], noise=noise[t:t + 1], observed=observed))
         _check_step(st, o, lw0, counts)       # (the per-row outputs of a coasted lane ARE the coasted records)
         for b in np.flatnonzero(~observed):
             coasted += 1
@@ -187,10 +154,10 @@ def test_estimates_follow_reset_and_resample(resample):
         if t == 9:
             st.reset([0, 3])
             st.resample(np.arange(R)[::-1].reshape(B, K)[::-1].reshape(-1))    # every lane reversed, on top of the reset
-        lw0 = _carried_in(st)
+        lw0 = carried_in(st)
         if t == 4:
             assert (lw0[K:2 * K] == 0).all()
-        o = _host(st.step(obs[t:t + 1], noise=noise[t:t + 1]))
+        o = host(st.step(obs[t:t + 1], noise=noise[t:t + 1]))
         _check_step(st, o, lw0, counts)
     _cap(counts)
     st.close()
@@ -204,8 +171,8 @@ def test_mean_canvas_is_the_weighted_mean_of_the_steps_canvases():
     assert "canvas" in st.outputs
     counts = EC.new_counts()
     for s in range(steps):
-        lw0 = _carried_in(st)
-        o = _host(st.step(obs[s * Ts:(s + 1) * Ts], noise=noise[s * Ts:(s + 1) * Ts]))
+        lw0 = carried_in(st)
+        o = host(st.step(obs[s * Ts:(s + 1) * Ts], noise=noise[s * Ts:(s + 1) * Ts]))
         assert o["lane"]["mean_canvas"].shape == (Ts, B) + HW
         _check_step(st, o, lw0, counts, canvas=True)
         # and directly: sum_k w_k canvas_k of the step's own canvases and the weights it reported, at the weights' band (1e-5 of

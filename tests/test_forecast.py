@@ -11,20 +11,17 @@ import torch
 
 from oracle import sqair_oracle as O
 from sqair_amd import _capi
-from sqair_amd.data import make_sequences, to_float
 from sqair_amd.flags import make_flags
 from sqair_amd.model import Model, SqairCore
 from sqair_amd.stream import SqairStream
 from tests.forecast_ref import forecast_ref, prior_margin
-from tests.hip_util import MARGIN, draw_noise, params32, presence_margins
+from tests.hip_util import MARGIN, draw_noise, params32
+from tests.stream_cases import DRAWS, EXACT, ORACLE_GATE as GATE, rollout_case
+from tests.stream_harness import core as make_core, frames as _frames, host, scaled, setup
 
 pytestmark = pytest.mark.gpu
 
-GATE = 5e-4        # live-oracle gate (scaled absolute error)
 GEN_GATE = 2e-5    # HIP against HIP: the decoder's dense kernel may differ with the row count
-DRAWS = 6
-EXACT = ("presence", "obj_id")
-CLOSE = ("what", "where", "presence_prob", "presence_logit", "canvas", "glimpse")
 LSTM = dict(time_transition="LSTM", prior_transition="LSTM")
 
 # name: (flags, frame size, B, streamed frames S, forecast frames F)
@@ -43,84 +40,14 @@ CASES = {
 }
 
 
-def _scaled(got, want):
-    got = np.asarray(got, np.float64).reshape(want.shape)
-    return float(np.abs(got - want).max() / max(1.0, float(np.abs(want).max())))
-
-
-def _frames(hw, B, T, seed):
-    if min(hw) < 20:   # (the sprite generator needs room for its objects: plain random frames)
-        return np.random.default_rng(seed).uniform(size=(T, B) + tuple(hw)).astype(np.float32)
-    return to_float(make_sequences(B, T=T, canvas=hw, seed=seed)["imgs"])
-
-
-def _setup(flags, hw, B, T, seed=19, edits=None):
-    F = make_flags(**flags)
-    obs = _frames(hw, B, T, seed)
-    P = params32(F, hw, 3, 0.05, obs.mean((0, 1)))
-    if edits:   # names of tests/latent_regimes.EDITS (tests/test_regime_paths.py)
-        from tests import latent_regimes
-        P = latent_regimes.apply_edits(P, F, edits)
-    core = SqairCore(F, hw)
-    core.set_params(P)
-    return F, P, obs, core
-
-
-def _host(d):
-    return {k: v.cpu().numpy() for k, v in d.items()}
-
-
-def _reference_rollout(F, P, obs, hw, B, S, Fn):
-    """CPU: the oracle over the S streamed frames and the fp64 rollout of Fn frames from its state, on the first of DRAWS noise
-    draws whose ORACLE margins (the posterior presences and the forecast's prior draws) are decision-stable.  Returns
-    (noise, forecast noise, reference rollout, the state it started from, margin)."""
-    K, N, nzw = int(F.k_particles), int(F.n_steps_per_image), 4 + int(F.n_what) + 1
-    R = B * K
-    orc = O.SqairOracle(P, O.make_cfg(F, hw), torch.float64)
-    tiled = O.tile_input_for_iwae(torch.as_tensor(obs, dtype=torch.float64), K)
-    rng = np.random.default_rng(23)
-    for attempt in range(DRAWS):   # the oracle's margins alone decide: the posterior presences and the forecast's prior draws
-        noise, fnoise = draw_noise(rng, S, R, N, nzw), draw_noise(rng, Fn, R, N, nzw)
-        with torch.no_grad():
-            seq, state = orc.sequence(tiled, torch.as_tensor(noise, dtype=torch.float64), state=orc.initial_state(R), return_state=True)
-        ref = forecast_ref(orc, state, fnoise)
-        mg = min(float(presence_margins(seq, noise).min()), float(prior_margin(ref, fnoise).min()))
-        if mg >= MARGIN:
-            return noise, fnoise, ref, state, mg
-    raise AssertionError("no decision-stable noise draw in {} attempts (last margin {:.2e})".format(DRAWS, mg))
-
-
-def _rollout_case(case, flags, hw, B, S, Fn, require=None, edits=None):
-    """A stream over S frames, then a forecast of Fn frames against the fp64 rollout.  require(ref, state): a condition on the
-    REFERENCE rollout alone (what the case is meant to reach), checked before the HIP path runs."""
-    F, P, obs, core = _setup(flags, hw, B, S, edits=edits)
-    K = int(F.k_particles)
-    if "n_what" in flags:
-        assert core.lib is _capi.lib(_capi.WIDE_LIB_PATH)
-    noise, fnoise, ref, state, mg = _reference_rollout(F, P, obs, hw, B, S, Fn)
-    if require is not None:
-        require(ref, state)
-    st = SqairStream(core, B, frames_per_step=S, use_graph=False)
-    st.step(obs, noise=noise)
-    got = _host(st.forecast(Fn, noise=fnoise))
-    torch.cuda.synchronize()
-    for k in EXACT:
-        assert np.array_equal(got[k], ref[k].numpy().astype(np.float32)), k
-    worst = {k: _scaled(got[k], ref[k].numpy()) for k in CLOSE}
-    print(case, "margin {:.4f}".format(mg), {k: "{:.1e}".format(v) for k, v in worst.items()}, "present", int(got["presence"].sum()))
-    for k, e in worst.items():
-        assert e <= GATE, (k, e)
-    # the summaries of this forecast: the stream's weights are its running log-weight sums
-    w = got["weights"].astype(np.float64)
-    lw = st.log_weight_sum.cpu().numpy().astype(np.float64).reshape(B, K)
-    assert np.allclose(w, np.exp(lw - lw.max(1, keepdims=True)) / np.exp(lw - lw.max(1, keepdims=True)).sum(1, keepdims=True), rtol=1e-5)
-    st.close()
-    return got, ref
+def _setup(flags, hw, B, T, seed=19):
+    F, P, obs, _ = setup(flags, B, T, hw, seed, obs=_frames(hw, B, T, seed))
+    return F, P, obs, make_core(F, hw, P)
 
 
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_forecast_matches_the_fp64_rollout(case):
-    _rollout_case(case, *CASES[case])
+    rollout_case(case, *CASES[case])
 
 
 @pytest.mark.parametrize("prior", ["rnn", "rw", "guided"])
@@ -145,7 +72,7 @@ def test_forecast_is_the_generation_mode(prior):
     core.set_params(P)
     st = SqairStream(core, B, frames_per_step=t0 + 1, use_graph=False)
     st.step(obs[:t0 + 1], noise=noise[:t0 + 1])
-    got = _host(st.forecast(T - t0 - 1, noise=gen[t0 + 1:]))
+    got = host(st.forecast(T - t0 - 1, noise=gen[t0 + 1:]))
     torch.cuda.synchronize()
     frames = T - t0 - 1 if prior == "rnn" else 1
     present = 0
@@ -157,8 +84,8 @@ def test_forecast_is_the_generation_mode(prior):
         live = want["presence"] > 0
         present += int(live.sum())
         for k in ("what", "where"):
-            assert _scaled(got[k][f][live], want[k][live]) <= GEN_GATE, (f, k)
-        assert _scaled(got["canvas"][f], want["canvas"]) <= GEN_GATE, f
+            assert scaled(got[k][f][live], want[k][live]) <= GEN_GATE, (f, k)
+        assert scaled(got["canvas"][f], want["canvas"]) <= GEN_GATE, f
     assert present > 0
 
 
@@ -186,7 +113,7 @@ def test_forecasting_between_steps_changes_nothing(smc, chain):
             sa.reset([1])
             sb.reset([1])
         fc = sa.forecast(3 + s % 2)
-        oa, ob = _host(sa.step(obs[s:s + 1])), _host(sb.step(obs[s:s + 1]))
+        oa, ob = host(sa.step(obs[s:s + 1])), host(sb.step(obs[s:s + 1]))
         torch.cuda.synchronize()
         if chain:
             ca.check_chain()
@@ -254,11 +181,11 @@ def test_pending_map_reset_and_resampled_rows():
         ref = forecast_ref(orc, orc.initial_state(R), fnoise)
         if float(prior_margin(ref, fnoise)[rows].min()) >= MARGIN:
             break
-    got = _host(st.forecast(Fn, noise=fnoise))
+    got = host(st.forecast(Fn, noise=fnoise))
     assert np.array_equal(got["presence"][:, rows], ref["presence"][:, rows].numpy().astype(np.float32))
     assert np.array_equal(got["obj_id"][:, rows], ref["obj_id"][:, rows].numpy().astype(np.float32))
     for k in ("what", "where", "canvas"):
-        assert _scaled(got[k][:, rows], ref[k][:, rows].numpy()) <= GATE, k
+        assert scaled(got[k][:, rows], ref[k][:, rows].numpy()) <= GATE, k
     assert np.array_equal(got["weights"][1], np.full(K, 1.0 / K, np.float32))   # (a reset lane's weights start at zero)
     st.close()
     # SMC that resampled: row r of the forecast is the forecast of its ancestor row (one noise row for every row)
@@ -271,9 +198,9 @@ def test_pending_map_reset_and_resampled_rows():
     assert sm.resampled.cpu().numpy().all()
     anc = sm._src.cpu().numpy()
     one = np.broadcast_to(draw_noise(rng, Fn, 1, N, nzw), (Fn, R, 2, N, nzw)).copy()
-    got = _host(sm.forecast(Fn, noise=one, summaries=False))
+    got = host(sm.forecast(Fn, noise=one, summaries=False))
     ident = torch.arange(R, dtype=torch.int32, device=core2.device)
-    base = _host(_raw(sm, Fn, one, ident, summaries=False))
+    base = host(_raw(sm, Fn, one, ident, summaries=False))
     assert not np.array_equal(anc, np.arange(R))
     for k in ("what", "where", "presence", "obj_id", "canvas"):
         assert np.array_equal(got[k], base[k][:, anc]), k
@@ -290,7 +217,7 @@ def test_summaries():
     dev = core.device
     ident = torch.arange(R, dtype=torch.int32, device=dev)
     lw = torch.as_tensor(np.random.default_rng(1).normal(0, 3, R).astype(np.float32), device=dev)
-    a = _host(_raw(st, Fn, noise, ident, lw))
+    a = host(_raw(st, Fn, noise, ident, lw))
     w = np.exp(lw.cpu().numpy().astype(np.float64).reshape(B, K))
     w /= w.sum(1, keepdims=True)
     cv = a["canvas"].astype(np.float64).reshape(Fn, B, K, -1)
@@ -299,18 +226,18 @@ def test_summaries():
     want_ec = np.einsum("bk,fbk->fb", w, cnt)
     assert np.abs(a["mean_canvas"] - want_mc).max() <= 1e-5 * np.abs(want_mc).max()
     assert np.abs(a["expected_count"] - want_ec).max() <= 1e-5 * max(1.0, np.abs(want_ec).max())
-    b = _host(_raw(st, Fn, noise, ident, lw))
+    b = host(_raw(st, Fn, noise, ident, lw))
     for k in a:
         assert np.array_equal(a[k], b[k]), k   # two calls, the same bits
     # uniform when log_w is NULL
-    u = _host(_raw(st, Fn, noise, ident, None))
+    u = host(_raw(st, Fn, noise, ident, None))
     assert np.abs(u["mean_canvas"] - cv.mean(2).reshape(u["mean_canvas"].shape)).max() <= 1e-5 * np.abs(cv).max()
     assert np.abs(u["expected_count"] - cnt.mean(2)).max() <= 1e-5 * max(1.0, cnt.max())
     # one finite weight: exactly that particle's canvas; a NaN, or every weight at -inf: NaN
     lw2 = torch.full((R,), -float("inf"), device=dev)
     lw2[0 * K + 2] = 1.5                        # lane 0: particle 2 alone
     lw2[1 * K + 1] = float("nan")               # lane 1: a NaN among -inf
-    e = _host(_raw(st, Fn, noise, ident, lw2))   # lane 2: all -inf
+    e = host(_raw(st, Fn, noise, ident, lw2))   # lane 2: all -inf
     mc = e["mean_canvas"].reshape(Fn, B, -1)
     assert np.array_equal(mc[:, 0], e["canvas"].reshape(Fn, B, K, -1)[:, 0, 2])
     assert np.array_equal(e["expected_count"][:, 0], cnt[:, 0, 2].astype(np.float32))
@@ -318,7 +245,7 @@ def test_summaries():
     # a lane with a +inf weight: NaN too
     lw3 = lw.clone()
     lw3[K] = float("inf")
-    g = _host(_raw(st, Fn, noise, ident, lw3))
+    g = host(_raw(st, Fn, noise, ident, lw3))
     assert np.isnan(g["expected_count"][:, 1]).all() and np.isfinite(g["expected_count"][:, [0, 2]]).all()
     st.close()
 
@@ -331,8 +258,8 @@ def test_captured_forecast_replays_the_eager_call():
     st.step(obs)
     torch.cuda.synchronize()
     noise = draw_noise(np.random.default_rng(2), Fn, B * K, N, nzw)
-    eager = _host(_raw(st, Fn, noise, st._src, st.log_weight_sum))
-    graph = _host(_raw(st, Fn, noise, st._src, st.log_weight_sum, capture=True))
+    eager = host(_raw(st, Fn, noise, st._src, st.log_weight_sum))
+    graph = host(_raw(st, Fn, noise, st._src, st.log_weight_sum, capture=True))
     for k in eager:
         assert np.array_equal(eager[k], graph[k]), k
     assert eager["presence"].sum() > 0

@@ -13,11 +13,11 @@ import torch
 from sqair_amd import _capi
 from sqair_amd.data import make_sequences, to_float
 from sqair_amd.flags import make_flags
-from sqair_amd.model import SqairCore
 from sqair_amd.stream import SqairStream
 from tests import forecast_lane_check as FC
 from tests import forecast_lane_ref as FL
 from tests.hip_util import draw_noise, params32
+from tests.stream_harness import core as make_core, host, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -27,19 +27,9 @@ FLAGS = dict(k_particles=K, n_steps_per_image=N)
 PER_ROW = ("what", "where", "presence", "presence_prob", "presence_logit", "obj_id", "canvas", "glimpse")
 
 
-def _host(d):
-    return {k: (_host(v) if isinstance(v, dict) else v.cpu().numpy()) for k, v in d.items()}
-
-
-def _bits(x):
-    return np.ascontiguousarray(x).view(np.uint32)
-
-
 def _core(P=None, **kw):
     F = make_flags(**FLAGS)
-    core = SqairCore(F, HW, **kw)
-    core.set_params(params32(F, HW, 3, 0.05) if P is None else P)
-    return F, core
+    return F, make_core(F, HW, params32(F, HW, 3, 0.05) if P is None else P, **kw)
 
 
 def _obs(T, seed=19):
@@ -122,23 +112,22 @@ def test_s1_without_lane_is_sqair_forecast(stepped):
     st, src, lw, noise = stepped
     n1 = noise[:, :R]
     for m in (src, None):
-        a, b = _host(_raw(st, 1, n1, m, lw, fan=False)), _host(_raw(st, 1, n1, m, lw, fan=True))
-        for k in a:
-            assert np.array_equal(_bits(a[k]), _bits(b[k])), k
+        a, b = host(_raw(st, 1, n1, m, lw, fan=False)), host(_raw(st, 1, n1, m, lw, fan=True))
+        same_bits(a, b, list(a))
     assert a["where"].any() and a["canvas"].any()
 
 
 def test_every_rollout_is_the_plain_forecast_of_its_row_and_noise(stepped):
     st, src, lw, noise = stepped
     S = 4
-    fan = _host(_raw(st, S, noise, src, lw))
+    fan = host(_raw(st, S, noise, src, lw))
     n5 = noise.reshape((FN, R, S) + noise.shape[2:])
     alive = 0
     for s in range(S):
-        plain = _host(_raw(st, 1, n5[:, :, s], src, lw, fan=False))
+        plain = host(_raw(st, 1, n5[:, :, s], src, lw, fan=False))
         for k in PER_ROW:
             got = fan[k].reshape((FN, R, S) + fan[k].shape[2:])[:, :, s]
-            assert np.array_equal(_bits(got), _bits(plain[k])), (s, k)
+            same_bits({k: got}, plain, [k], s)
         alive += int(plain["presence"].sum())
     assert alive > 0
     # the rollouts of a row differ (their noise does), and a fresh row's start from the initial state
@@ -154,27 +143,26 @@ def test_every_rollout_is_the_plain_forecast_of_its_row_and_noise(stepped):
     assert np.abs(fan["mean_canvas"] - want_mc).max() <= 1e-5 * np.abs(want_mc).max()
     assert np.abs(fan["expected_count"] - want_ec).max() <= 1e-5 * max(1.0, np.abs(want_ec).max())
     # NULL log_w: uniform; a NaN lane: NaN summaries, the other lanes untouched
-    u = _host(_raw(st, S, noise, src, None))
+    u = host(_raw(st, S, noise, src, None))
     assert np.abs(u["expected_count"] - cnt.mean(2)).max() <= 1e-5 * max(1.0, cnt.max())
     lw2 = lw.clone()
     lw2[K + 1] = float("nan")
-    e = _host(_raw(st, S, noise, src, lw2))
+    e = host(_raw(st, S, noise, src, lw2))
     assert np.isnan(e["expected_count"][:, 1]).all() and np.isnan(e["mean_canvas"][:, 1]).all()
     assert np.array_equal(e["expected_count"][:, [0, 2]], fan["expected_count"][:, [0, 2]])
 
 
 def test_captured_fan_replays_the_eager_call(stepped):
     st, src, lw, noise = stepped
-    eager = _host(_raw(st, 4, noise, src, lw, lane=True))
-    graph = _host(_raw(st, 4, noise, src, lw, lane=True, capture=True))
-    for k in eager:
-        assert np.array_equal(_bits(eager[k]), _bits(graph[k])), k
+    eager = host(_raw(st, 4, noise, src, lw, lane=True))
+    graph = host(_raw(st, 4, noise, src, lw, lane=True, capture=True))
+    same_bits(eager, graph, list(eager))
     assert (eager["lane.best_row"] >= 0).all() and eager["lane.presence"].sum() > 0
 
 
 def _check_lane(st, res, S, lw):
     """res["lane"] against the reference applied to the call's own per-rollout outputs, start rows and log weights."""
-    res = _host(res)
+    res = host(res)
     ln = res["lane"]
     ref = FL.lane_forecast(ln["start_where"], ln["start_presence"], ln["start_obj_id"], res["where"], res["presence"], res["obj_id"],
                            lw, K, S, HW, 0.5)
@@ -258,7 +246,7 @@ def test_lane_forecasting_between_steps_changes_nothing(smc):
             sb.reset([1])
         fc = sa.forecast(FN, samples=4, lane=True)
         nz = _step_noise(1, 40 + s)
-        oa, ob = _host(sa.step(obs[s:s + 1], noise=nz)), _host(sb.step(obs[s:s + 1], noise=nz))
+        oa, ob = host(sa.step(obs[s:s + 1], noise=nz)), host(sb.step(obs[s:s + 1], noise=nz))
         torch.cuda.synchronize()
         assert (fc["lane"]["best_row"] >= 0).all()
         for k in ob:
@@ -275,9 +263,8 @@ def test_default_arguments_are_the_plain_forecast():
     """forecast(F) and forecast(F, samples=1) draw the same Philox noise and give the same bits; samples=4 keeps the key."""
     F, core, st = _stream()
     st.step(_obs(2), noise=_step_noise(2, 11))
-    a, b = _host(st.forecast(FN)), _host(st.forecast(FN, samples=1, lane=True))
-    for k in a:
-        assert np.array_equal(_bits(a[k]), _bits(b[k])), k
+    a, b = host(st.forecast(FN)), host(st.forecast(FN, samples=1, lane=True))
+    same_bits(a, b, list(a))
     assert "lane" in b and "lane" not in a
     with pytest.raises(ValueError):
         st.forecast(FN, samples=0)

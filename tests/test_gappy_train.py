@@ -3,7 +3,7 @@ sqair_backward_carry_masked; StreamTrainer(missing=True).step(observed=...)).
 
 1. a mask with every lane observed is the carried step: outputs and blob bit for bit, gradient to float-atomic order;
 2. chunk 2 of a stream under a mixed mask -- a lane with a gap, a lane with a ragged tail, imported rows -- against the fp64
-   reference of tests/gappy_train_ref.py, every parameter's gradient at the bars of tests/test_hip_backward.py;
+   reference of tests/gappy_train_ref.py, every parameter's gradient at the bars of tests/pass_cases.py;
 3. a chunk without any observed lane: target 0, every gradient entry 0;
 4. one lane observed in its first 2 of 4 frames: half the gradient of the 2-frame chunk;
 5. the frames of unobserved lanes do not matter;
@@ -19,21 +19,18 @@ import torch
 
 from oracle import sqair_oracle as O
 from sqair_amd import _capi
-from sqair_amd.data import make_sequences, to_float
-from sqair_amd.flags import make_flags
-from sqair_amd.model import SqairCore
 from sqair_amd.stream import SqairStream
 from sqair_amd.train import StreamTrainer
 from tests import gappy_train_ref as GR
-from tests.hip_util import MARGIN, draw_noise, params32
-from tests.test_hip_backward import TIGHT, _check_report
+from tests.hip_util import MARGIN
+from tests.pass_cases import TIGHT, check_report
+from tests.stream_harness import (OUTS, chunks as _chunks, core, gclose, noise as _noise, train_setup, train_step)
 
 pytestmark = pytest.mark.gpu
 
 HW = (32, 40)
 B, T = 3, 4
 LSTM = dict(time_transition="LSTM", prior_transition="LSTM")
-OUTS = ("what", "where", "presence", "obj_id", "log_weights_per_timestep")
 # lane 0 sees every frame, lane 1 has a gap of two frames and is observed again, lane 2's clip ends after two frames
 MASK = np.array([[1, 1, 1], [1, 0, 1], [1, 0, 0], [1, 1, 0]], bool)
 # prop_prior_step_bias = 1: a prior presence probability near 0.7, so that coasted frames drop objects and the score term of their
@@ -55,39 +52,11 @@ SMC_U = 0.37     # the resampler's uniform of every lane at the end of chunk 1
 
 
 def _setup(flags, b, frames, seed=23):
-    F = make_flags(learning_rate=0.0, **flags)   # (lr 0: the parameters are held, the optimiser step changes nothing)
-    obs = to_float(make_sequences(b, T=frames, canvas=HW, n_objects=(1, 2), obj_size=10, seed=seed)["imgs"])
-    P = params32(F, HW, 3, 0.05, obs.mean((0, 1)))
-    return F, obs, P
+    return train_setup(flags, b, frames, HW, seed)
 
 
 def _core(F, P, options=None):
-    core = SqairCore(F, HW, options=options)
-    core.set_params(P)
-    return core
-
-
-def _noise(F, rng, t, R):
-    return draw_noise(rng, t, R, int(F.n_steps_per_image), 4 + int(F.n_what) + 1)
-
-
-def _step(tr, *args, **kw):
-    """StreamTrainer.step is asynchronous on its core's stream: wait for it, return the gradient on the host."""
-    g = tr.step(*args, **kw)
-    torch.cuda.synchronize()
-    return g.cpu().numpy()
-
-
-def _gclose(got, want, tol):
-    got, want = np.asarray(got), np.asarray(want)
-    err = float(np.abs(got - want).max())
-    assert err <= tol * float(np.abs(want).max()), (err, float(np.abs(want).max()))
-
-
-def _chunks(F, obs, b, t, n, seed=5):
-    rng = np.random.default_rng(seed)
-    R = b * int(F.k_particles)
-    return [(obs[i * t:(i + 1) * t], _noise(F, rng, t, R)) for i in range(n)]
+    return core(F, HW, P, options)
 
 
 def _masks(n, b, t, seed=1):
@@ -172,12 +141,12 @@ def test_all_observed_mask_is_the_carried_step():
     ta = StreamTrainer(_core(F, P), F, B, frames_per_step=T, use_graph=False, collective=False, outputs=OUTS, missing=True)
     tb = StreamTrainer(_core(F, P), F, B, frames_per_step=T, use_graph=False, collective=False, outputs=OUTS)
     for i, (fr, nz) in enumerate(_chunks(F, obs, B, T, 2)):
-        a = _step(ta, fr, noise=nz, observed=None if i == 0 else np.ones((T, B), bool))
-        b = _step(tb, fr, noise=nz)
+        a = train_step(ta, fr, noise=nz, observed=None if i == 0 else np.ones((T, B), bool))
+        b = train_step(tb, fr, noise=nz)
         for k in ta.core.out:
             assert torch.equal(ta.core.out[k], tb.core.out[k]), (i, k)
         assert torch.equal(ta.state.view(torch.int32), tb.state.view(torch.int32)), i
-        _gclose(a, b, 1e-5)
+        gclose(a, b, 1e-5)
 
 
 # ---- 2. chunk 2 under a mixed mask against the fp64 reference ----------------------------------------------------------------------
@@ -220,7 +189,7 @@ def test_chunk_two_matches_the_fp64_reference(case):
         report.append((name, float(np.abs(g - want).max()), float(np.abs(want).max())))
     names = {n for n, _, s in report if s > 0}
     assert any(m.startswith("prop.prior") for m in names)
-    _check_report(report)
+    check_report(report)
 
 
 # ---- 3. no lane observed -----------------------------------------------------------------------------------------------------------
@@ -229,9 +198,9 @@ def test_no_lane_observed_gives_target_zero_and_a_zero_gradient():
     F, obs, P = _setup(flags, B, 2 * T)
     tr = StreamTrainer(_core(F, P), F, B, frames_per_step=T, use_graph=False, collective=False, outputs=OUTS, missing=True)
     (f1, n1), (f2, n2) = _chunks(F, obs, B, T, 2)
-    g1 = _step(tr, f1, noise=n1)
+    g1 = train_step(tr, f1, noise=n1)
     assert np.abs(g1).max() > 0 and float(tr.core.out["presence"][-1].sum()) > 0       # objects enter the chunk
-    g2 = _step(tr, np.full_like(f2, np.nan), noise=n2, observed=np.zeros((T, B), bool))
+    g2 = train_step(tr, np.full_like(f2, np.nan), noise=n2, observed=np.zeros((T, B), bool))
     assert float(tr.core.scalars[2]) == 0.0                                            # vimco_target
     assert not tr.core.out["log_weights_per_timestep"].any() and not tr.core.out["discrete_log_prob"].any()
     assert float(tr.core.out["presence"].sum()) > 0                                     # ... and coast through it
@@ -246,10 +215,10 @@ def test_ragged_tail_is_the_short_chunk_scaled(cell):
     nz = _noise(F, np.random.default_rng(7), T, 3)
     ta = StreamTrainer(_core(F, P), F, 1, frames_per_step=T, use_graph=False, collective=False, missing=True)
     tb = StreamTrainer(_core(F, P), F, 1, frames_per_step=2, use_graph=False, collective=False)
-    a = _step(ta, obs, noise=nz, observed=np.array([[1], [1], [0], [0]], bool))
-    b = _step(tb, obs[:2], noise=nz[:2])
+    a = train_step(ta, obs, noise=nz, observed=np.array([[1], [1], [0], [0]], bool))
+    b = train_step(tb, obs[:2], noise=nz[:2])
     assert float(tb.core.out["presence"].sum()) > 0
-    _gclose(a, 0.5 * b, 1e-5)
+    gclose(a, 0.5 * b, 1e-5)
 
 
 # ---- 5. the frames of unobserved lanes do not matter -------------------------------------------------------------------------------
@@ -262,13 +231,13 @@ def test_frames_of_unobserved_lanes_do_not_matter():
         mask = MASK if i else np.roll(MASK, 1, axis=1)
         other = fr.copy()
         other[~mask] = np.nan
-        a = _step(ta, fr, noise=nz, observed=mask)
-        b = _step(tb, other, noise=nz, observed=mask)
+        a = train_step(ta, fr, noise=nz, observed=mask)
+        b = train_step(tb, other, noise=nz, observed=mask)
         for k in ta.core.out:
             assert torch.equal(ta.core.out[k], tb.core.out[k]), (i, k)
         assert torch.equal(ta.state.view(torch.int32), tb.state.view(torch.int32)), i
         assert np.isfinite(b).all()
-        _gclose(a, b, 1e-5)
+        gclose(a, b, 1e-5)
 
 
 # ---- 6. with the parameters held, masked chunked training is the masked stream -----------------------------------------------------
@@ -284,7 +253,7 @@ def test_masked_chunked_training_is_the_masked_stream_and_hands_over():
         if i == 2:
             tr.reset([1])
             st.reset([1])
-        _step(tr, fr, noise=nz, observed=m)
+        train_step(tr, fr, noise=nz, observed=m)
         got = {k: tr.core.out[k].clone() for k in OUTS}
         want = st.step(fr, noise=nz, observed=m)
         torch.cuda.synchronize()
@@ -318,9 +287,9 @@ def test_one_graph_replays_every_mask_and_node_budget(smc):
     keys = []
     for (fr, nz), m in zip(chunks, masks):
         u = np.full(B, SMC_U, np.float32) if smc else None
-        a = _step(tg, fr, noise=nz, uniforms=u, observed=m)      # chunk 0 runs eagerly and captures; chunks 1..3 replay
-        b = _step(te, fr, noise=nz, uniforms=u, observed=m)
-        _gclose(a, b, 1e-5)
+        a = train_step(tg, fr, noise=nz, uniforms=u, observed=m)      # chunk 0 runs eagerly and captures; chunks 1..3 replay
+        b = train_step(te, fr, noise=nz, uniforms=u, observed=m)
+        gclose(a, b, 1e-5)
         for k in tg.core.out:
             assert torch.equal(tg.core.out[k], te.core.out[k]), k
         assert torch.equal(tg.state.view(torch.int32), te.state.view(torch.int32))
@@ -330,7 +299,7 @@ def test_one_graph_replays_every_mask_and_node_budget(smc):
     tu = StreamTrainer(_core(F, P), F, B, frames_per_step=T, collective=False, resample=rs)
     with pytest.raises(ValueError, match="missing=True"):
         tu.step(chunks[0][0], noise=chunks[0][1], observed=masks[1])
-    _step(tu, chunks[0][0], noise=chunks[0][1], uniforms=np.full(B, SMC_U, np.float32) if smc else None)
+    train_step(tu, chunks[0][0], noise=chunks[0][1], uniforms=np.full(B, SMC_U, np.float32) if smc else None)
     plain = _core(F, P)
     plain.bind(T, B, list(tu.core.out))
     plain.obs.copy_(torch.as_tensor(chunks[0][0]))

@@ -10,7 +10,7 @@ import torch
 from sqair_amd import _capi
 from sqair_amd.train import StreamTrainer
 from tests.abi_host import BIG, DUMMY, LIBS, constant, err as _err, fwd_args, handle, paragraph, phrases, prototype
-from tests.test_stream_train_host import OTHER, B, _carry, _smc      # the unmasked calls' carry and SMC: the masked ones take the same
+from tests.abi_host import CARRY_B as B, OTHER, carry as _carry, train_smc      # the unmasked calls' carry and SMC: the masked ones take the same
 
 NEW = ("sqair_forward_train_carry_masked", "sqair_backward_carry_masked")
 
@@ -74,12 +74,12 @@ def test_refusals_before_any_hip_call(path, flags, mask):
         refused(_carry(lib, h), ["B = 5", "B = 4"], b=B + 1)
         refused(_carry(lib, h, state_bytes=lib.sqair_state_bytes(h, B) - 4), ["state_bytes"])
         refused(_carry(lib, h, state_in=None), ["state_in"])
-        refused(_carry(lib, h, smc=_smc(ess_frac=0.5)), ["ess_frac"])       # adaptive-ESS training stays out of scope
-        refused(_carry(lib, h, smc=_smc(ess_frac=0.0)), ["ess_frac"])
+        refused(_carry(lib, h, smc=train_smc(ess_frac=0.5)), ["ess_frac"])       # adaptive-ESS training stays out of scope
+        refused(_carry(lib, h, smc=train_smc(ess_frac=0.0)), ["ess_frac"])
         for k in ("log_w", "log_z", "log_evidence", "ess", "resampled", "src_rows"):
-            refused(_carry(lib, h, smc=_smc(**{k: None})), ["NULL"])
-        refused(_carry(lib, h, smc=_smc(src_rows=OTHER.value)), ["src_rows"])
-        f, fe, g, ge = _calls(lib, h, _carry(lib, h, smc=_smc()), lw=False, mask=mask)
+            refused(_carry(lib, h, smc=train_smc(**{k: None})), ["NULL"])
+        refused(_carry(lib, h, smc=train_smc(src_rows=OTHER.value)), ["src_rows"])
+        f, fe, g, ge = _calls(lib, h, _carry(lib, h, smc=train_smc()), lw=False, mask=mask)
         assert f == -1 and "log_weights_per_timestep" in fe
         # a handle that carries an inference state, with or without its own mask: the registrations never mix
         assert lib.sqair_set_state(h, DUMMY, DUMMY, None, lib.sqair_state_bytes(h, B), B) == 0

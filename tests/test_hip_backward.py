@@ -12,6 +12,8 @@ from sqair_amd.flags import make_flags
 from sqair_amd.model import make_config
 from tests.hip_util import dev, rel_err, stream
 
+from tests.pass_cases import LOOSE, check_report, full_backward_case
+
 pytestmark = pytest.mark.gpu
 D = torch.float64
 
@@ -277,96 +279,18 @@ def test_rmsprop_step_matches_tf_semantics():
         lib.sqair_destroy(h)
 
 
-def _full_backward_inputs(K, N, T, B, hw, seed, flags=None, edits=None, seed0=100):
-    """CPU: flags, frames, parameters (with the named tests/latent_regimes.EDITS, if any), the decision-stable noise draw and the
-    fp64 oracle's pass through it with autograd on (seed0: the first noise seed tried).  Returns (F, obs, P, noise, oracle model,
-    oracle)."""
-    from sqair_amd.data import make_sequences, to_float
-    from tests import presence_patterns
-    from tests.hip_util import params32, stable_noise
-    F = make_flags(k_particles=K, n_steps_per_image=N, **(flags or {}))
-    d = make_sequences(B, T=T, canvas=hw, n_objects=(1, 2), obj_size=max(2, min(28, min(hw) // 2)), seed=seed)
-    obs = to_float(d["imgs"])
-    P = params32(F, hw, 4, 0.05, obs.mean((0, 1)))
-    if edits:
-        from tests import latent_regimes
-        P = latent_regimes.apply_edits(P, F, edits)
-    noise, ref, orc, _ = stable_noise(F, hw, P, obs, T, B * K, N, seed0=seed0, requires_grad=True, nzw=4 + int(F.n_what) + 1)
-    # which slot layouts the case reaches (tests/presence_patterns.py; the cases that REQUIRE some are in tests/test_presence_paths.py)
-    ref.pattern_counts = presence_patterns.count(presence_patterns.classify_outputs(ref.outputs, N))
-    print(presence_patterns.table(ref.pattern_counts))
-    return F, obs, P, noise, ref, orc
-
-
-def _full_backward_case(K, N, T, B, hw, seed, flags=None, lib_path=None, options=None, edits=None, inputs=None):
-    """inputs: what `_full_backward_inputs` returned for the same arguments, its oracle not yet differentiated (a caller that has
-    looked at the oracle's outputs first)."""
-    from sqair_amd.model import Model, SqairCore
-    F, obs, P, noise, ref, orc = inputs or _full_backward_inputs(K, N, T, B, hw, seed, flags, edits)
-    core = SqairCore(F, hw, lib_path=lib_path, options=options)
-    core.set_params(P)
-    names = ["log_weights_per_timestep", "discrete_log_prob", "presence", "prop_pres", "disc_pres"]
-    m = Model(obs, None, core, K, outputs=names)
-    core.noise.copy_(torch.as_tensor(noise).reshape(core.noise.shape))
-    core.forward(train=True)
-    torch.cuda.synchronize()
-    assert np.array_equal(core.out["prop_pres"].cpu().numpy(), ref.prop_pres.detach().numpy())
-    assert np.array_equal(core.out["disc_pres"].cpu().numpy(), ref.disc_pres.detach().numpy())
-    if not getattr(ref, "differentiated", False):
-        orc.make_target(ref).backward()
-        ref.differentiated = True
-    core.backward()
-    torch.cuda.synchronize()
-    if options and options.get("slot_chain"):
-        core.check_chain(train=True)   # (every launch of the in-launch slot chain completed: otherwise the tape means nothing)
-    got = {k: v.cpu().numpy() for k, v in core.grads_by_name().items()}
-    report = []
-    for name, g in got.items():
-        want = orc.P[name].grad
-        want = np.zeros_like(g) if want is None else want.numpy().reshape(g.shape)
-        err = float(np.abs(g - want).max())
-        scale = float(np.abs(want).max())
-        report.append((name, err, scale))
-    return report, ref, core
-
-
-# Gradient bar: 5e-4 of the parameter's largest gradient (measured: <= ~1e-4 in the regular regime).  The parameters below get
-# 3e-3: `*.transform.scale_offset` is ONE scalar added to the four raw scales of every where posterior, so its gradient is the
-# sum over all rows, frames, slots and the 4 scale columns of the gradient of `*.transform.l2.b` -- terms of both signs of size
-# ~50 that cancel to ~0.3 (measured below: |grad| 0.29 against 49 for l2.b), which amplifies the fp32 rounding of the
-# individual terms (each good to ~1e-4) by two orders of magnitude relative to the result.  Everything else holds the tight bar.
-TIGHT, LOOSE = 5e-4, 3e-3
-ILL_CONDITIONED = ("disc.transform.scale_offset", "prop.transform.scale_offset")
-
-
-def _check_report(report, tol=TIGHT, loose=ILL_CONDITIONED, ill_scale=False):
-    gmax = max(s for _, _, s in report)
-    if ill_scale:
-        # `*.transform.scale_offset` is the SUM of the four scale columns of `*.transform.l2.b`'s gradient: judge its error on the
-        # size of the terms it is made of (the loose bar above assumes the ~170x cancellation of the shipped sizes; other sizes
-        # cancel harder)
-        by = {n: s for n, _, s in report}
-        report = [(n, e, max(s, by[n.replace("scale_offset", "l2.b")]) if n in loose else s) for n, e, s in report]
-        loose = ()
-    rel = lambda e, s: e / max(s, 1e-4 * gmax)
-    bad = [(n, e, s) for n, e, s in report if not np.isfinite(e) or rel(e, s) > (LOOSE if n in loose else tol)]
-    for n, e, s in sorted(report, key=lambda r: -rel(r[1], r[2]))[:8]:
-        print("%-34s err %.3e  |grad|max %.3e  rel %.2e %s" % (n, e, s, rel(e, s), "<-- BAD" if (n, e, s) in bad else ""))
-    assert not bad, [(n, "%.2e" % rel(e, s)) for n, e, s in bad]
-
-
 def test_full_backward_single_frame_discovery_only():
     """T = 1: only discovery, the decoder and the priors are active (propagation sees no present object)."""
-    report, _, _ = _full_backward_case(K=3, N=3, T=1, B=3, hw=(50, 50), seed=5)
-    _check_report(report)
+    report, _, _ = full_backward_case(K=3, N=3, T=1, B=3, hw=(50, 50), seed=5)
+    check_report(report)
 
 
 @pytest.mark.parametrize("K,N,T,B", [(2, 1, 2, 1), (2, 2, 2, 9), (3, 1, 3, 6)])
 def test_full_backward_degenerate_sizes(K, N, T, B):
     """One slot, one sequence, and row counts that leave a last 16-row tile of 2 rows (18 rows): every parameter's gradient
     against autograd through the fp64 oracle."""
-    report, _, _ = _full_backward_case(K, N, T, B, (50, 50), seed=7)
-    _check_report(report)
+    report, _, _ = full_backward_case(K, N, T, B, (50, 50), seed=7)
+    check_report(report)
 
 
 @pytest.mark.parametrize("K,N,T,B,hw", [(3, 3, 3, 3, (50, 50)), (5, 4, 4, 2, (50, 50))])
@@ -379,9 +303,9 @@ def test_full_backward_matches_autograd(K, N, T, B, hw):
     prop + disc > N.  They cover the compaction adjoint as the identity on the propagated slots plus truncation of the discoveries.
     Real permutations (holes, holes with discoveries, rows that lose everything), forward and backward, are required and tested in
     tests/test_presence_paths.py; every presence pattern of the kernels themselves in tests/test_compact_kernel.py."""
-    report, ref, _ = _full_backward_case(K, N, T, B, hw, seed=11)
+    report, ref, _ = full_backward_case(K, N, T, B, hw, seed=11)
     assert float(ref.prop_pres.detach().sum()) > 0, "case must exercise propagation"
-    _check_report(report)
+    check_report(report)
 
 
 @pytest.mark.parametrize("cell", ["GRU", "LSTM"])
@@ -552,9 +476,9 @@ def test_checkpoint_round_trip_restores_parameters_and_optimiser_slots(tmp_path)
 def test_full_backward_flag_variants(flags):
     """The adjoint branches the default flags never take: random-walk / guided propagation priors (the prior statistics
     feed back into z_{t-1}), geometric step prior, fixed where prior, unmasked glimpses, the LSTM temporal / prior / slot-RNN cells."""
-    report, ref, _ = _full_backward_case(K=3, N=3, T=3, B=3, hw=(50, 50), seed=11, flags=flags)
+    report, ref, _ = full_backward_case(K=3, N=3, T=3, B=3, hw=(50, 50), seed=11, flags=flags)
     assert float(ref.prop_pres.detach().sum()) > 0
-    _check_report(report)
+    check_report(report)
 
 
 @pytest.mark.parametrize("flags", [dict(), dict(prop_prior_type="guided", masked_glimpse=False), dict(transition="LSTM", time_transition="LSTM"),
@@ -567,10 +491,10 @@ def test_scratch_the_backward_pass_does_not_clear_is_written_in_full(flags, monk
     if not os.path.exists(knob_lib):
         pytest.skip("knob build of the library not present (python sqair_amd/csrc/build.py --knobs)")
     monkeypatch.setenv("SQAIR_SCRATCH_POISON", "1")
-    report, _, _ = _full_backward_case(K=3, N=3, T=3, B=3, hw=(50, 50), seed=11, flags=flags, lib_path=knob_lib)
-    _check_report(report)
-    report, _, _ = _full_backward_case(K=2, N=3, T=1, B=2, hw=(50, 50), seed=5, flags=flags, lib_path=knob_lib)
-    _check_report(report)
+    report, _, _ = full_backward_case(K=3, N=3, T=3, B=3, hw=(50, 50), seed=11, flags=flags, lib_path=knob_lib)
+    check_report(report)
+    report, _, _ = full_backward_case(K=2, N=3, T=1, B=2, hw=(50, 50), seed=5, flags=flags, lib_path=knob_lib)
+    check_report(report)
 
 
 @pytest.mark.parametrize("flags", [dict(n_units=4), dict(n_what=20), dict(n_what=7), dict(glimpse_size=12), dict(glimpse_size=28),
@@ -582,12 +506,12 @@ def test_model_size_flags_forward_and_backward(flags):
     glimpse_size other than the shipped 8 / 50 / 20: all outputs feeding the objective and every gradient against the oracle.
     n_hidden values that are not a multiple of 128 run on layers padded with inert units (csrc/sqair_internal.h: SqairHandle); the
     parameters, their gradients and the final recurrent states cross the ABI in the reference's own shapes."""
-    report, ref, core = _full_backward_case(K=3, N=3, T=3, B=3, hw=(50, 50), seed=11, flags=flags)
+    report, ref, core = full_backward_case(K=3, N=3, T=3, B=3, hw=(50, 50), seed=11, flags=flags)
     assert float(ref.prop_pres.detach().sum()) > 0
     lw = core.out["log_weights_per_timestep"].cpu().numpy()
     want = ref.log_weights_per_timestep.detach().numpy()
     assert np.abs(lw - want).max() <= 1e-4 * np.abs(want).max()
-    _check_report(report)
+    check_report(report)
 
 
 @pytest.mark.parametrize("K,N,flags", [(3, 3, dict(n_what=64)), (3, 3, dict(n_what=100)), (2, 3, dict(n_what=128, glimpse_size=12)),
@@ -600,13 +524,13 @@ def test_wide_flag_range_forward_and_backward(K, N, flags):
     same sources with a larger slot record and plain-loop per-row kernels, picked by SqairCore from the flags: the log-weights and
     every gradient against the oracle, exactly like the shipped sizes."""
     from sqair_amd import _capi
-    report, ref, core = _full_backward_case(K=K, N=N, T=3 if N < 9 else 2, B=2, hw=(50, 50), seed=11, flags=flags)
+    report, ref, core = full_backward_case(K=K, N=N, T=3 if N < 9 else 2, B=2, hw=(50, 50), seed=11, flags=flags)
     assert core.lib is _capi.lib(_capi.WIDE_LIB_PATH)
     assert float(ref.prop_pres.detach().sum()) > 0
     lw = core.out["log_weights_per_timestep"].cpu().numpy()
     want = ref.log_weights_per_timestep.detach().numpy()
     assert np.abs(lw - want).max() <= 1e-4 * np.abs(want).max()
-    _check_report(report, ill_scale=True)
+    check_report(report, ill_scale=True)
 
 
 def test_scalar_hyper_parameter_flags_reach_the_kernels():
@@ -614,11 +538,11 @@ def test_scalar_hyper_parameter_flags_reach_the_kernels():
     read them: geometric step prior, fixed where prior): objective and gradients against the oracle."""
     flags = dict(output_std=0.2, scale_prior="-1.5", prop_prior_step_bias=4.0, step_success_prob=0.6, disc_prior_type="geom",
                  rec_where_prior=False, transform_var_bias=-2.0, output_scale=0.3, disc_step_bias=0.5, prop_step_bias=3.0)
-    report, ref, core = _full_backward_case(K=3, N=3, T=3, B=3, hw=(50, 50), seed=11, flags=flags)
+    report, ref, core = full_backward_case(K=3, N=3, T=3, B=3, hw=(50, 50), seed=11, flags=flags)
     lw = core.out["log_weights_per_timestep"].cpu().numpy()
     want = ref.log_weights_per_timestep.detach().numpy()
     assert np.abs(lw - want).max() <= 1e-4 * np.abs(want).max()
-    _check_report(report)
+    check_report(report)
 
 
 @pytest.mark.parametrize("K,N,T,B,hw", [(2, 6, 2, 2, (50, 50)), (2, 3, 2, 2, (128, 128)), (4, 2, 3, 5, (40, 56)), (3, 3, 2, 3, (37, 44)),
@@ -630,16 +554,16 @@ def test_full_backward_other_shapes(K, N, T, B, hw):
     whose H * W is not a multiple of 4 (they pass through a zero-padded copy), more particles than a wavefront has lanes (K = 70, 128:
     the generic ELBO kernel), 5 slots on 96 x 128 (row-wave forward with 8 slot registers, band adjoint), 70 x 150 (four columns per
     lane forward, band adjoint)."""
-    report, _, _ = _full_backward_case(K, N, T, B, hw, seed=21)
-    _check_report(report)
+    report, _, _ = full_backward_case(K, N, T, B, hw, seed=21)
+    check_report(report)
 
 
 @pytest.mark.parametrize("hw", [(12, 14), (3, 250), (257, 5), (150, 256)])
 def test_full_backward_extreme_frame_shapes(hw):
     """Frames smaller than the glimpse, degenerate aspect ratios, and the largest frame training takes (38 400 pixels: the crop
     adjoint stages the frame in LDS): every parameter's gradient against autograd through the fp64 oracle."""
-    report, _, _ = _full_backward_case(2, 2, 2, 2, hw, seed=21)
-    _check_report(report)
+    report, _, _ = full_backward_case(2, 2, 2, 2, hw, seed=21)
+    check_report(report)
 
 
 def test_one_particle_trains_with_reinforce_and_vimco_says_why_not():
@@ -725,9 +649,9 @@ def test_full_size_gradient_is_the_mean_of_shard_gradients(batch):
 def test_full_backward_cfg2_sub_batch_against_oracle():
     """Headline shape in T, K, N and frame size (T10, 50x50, K5, N4) on an 8-sequence sub-batch: every parameter's gradient
     against autograd through the fp64 oracle."""
-    report, ref, _ = _full_backward_case(K=5, N=4, T=10, B=8, hw=(50, 50), seed=1236)
+    report, ref, _ = full_backward_case(K=5, N=4, T=10, B=8, hw=(50, 50), seed=1236)
     assert float(ref.prop_pres.detach().sum()) > 0
-    _check_report(report)
+    check_report(report)
 
 
 def test_trainer_follows_the_sequence_length_curriculum():
@@ -761,8 +685,8 @@ def test_trainer_follows_the_sequence_length_curriculum():
 def test_edges_of_the_supported_range_forward_and_backward(K, N, T, B, hw):
     """N = 8 slots (SQ_MAXN), K = 64 particles, the smallest problem (one slot, one frame, one sequence): outputs and every
     parameter gradient against the fp64 oracle."""
-    report, ref, core = _full_backward_case(K, N, T, B, hw, seed=31)
-    _check_report(report)
+    report, ref, core = full_backward_case(K, N, T, B, hw, seed=31)
+    check_report(report)
     lw = core.out["log_weights_per_timestep"].cpu().numpy()
     want = ref.log_weights_per_timestep.detach().numpy()
     assert np.abs(lw - want).max() <= 1e-4 * np.abs(want).max()
@@ -836,7 +760,7 @@ def test_gradients_match_the_golden_fixture(options):
         report.append((name, float(np.abs(got[g["idx/" + name]] - g["val/" + name]).max()), float(stat[3])))
         # whole-tensor digests: the L2 norm to the same relative bar
         assert abs(np.sqrt((got * got).sum()) - stat[2]) <= LOOSE * max(stat[2], scale), name
-    _check_report(report)
+    check_report(report)
 
 
 def test_l2_term_of_the_target_and_its_gradient():

@@ -13,14 +13,14 @@ from sqair_amd import _capi
 from sqair_amd.data import config_inputs, make_sequences, to_float
 from sqair_amd.flags import make_flags
 from sqair_amd.model import Model, SqairCore
-from tests import presence_patterns
 from tests.hip_util_cpu import fixture_params
-from tests.hip_util import (GOLDEN, MARGIN, MAX_DRAWS, draw_noise, params32, presence_margins, prior_presence_margins, rel_err,
-                            run_hip, run_oracle, stable_noise)
+from tests.hip_util import (GOLDEN, MARGIN, MAX_DRAWS, draw_noise, params32, presence_margins, prior_presence_margins, run_hip,
+                            run_oracle, stable_noise)
+
+from tests.pass_cases import REL, check_against, live_oracle_case
 
 pytestmark = pytest.mark.gpu
 
-REL = 1e-4  # tolerance stated by north_star
 GOLDEN_TOL = 2e-5   # per-output gate of the committed fixtures (scaled absolute error; measured worst ~2e-6: profiles/r05_parity.json).
                     # The live-oracle cases with fp32 compounding over many steps (LSTM cells, T = 30) keep 5e-4.
 
@@ -41,34 +41,6 @@ def _record_parity(case, worst):
         pass
 
 
-def _check_against(m, ref_out, ref_model, names, T, tol=5e-4, scalar_bars=None):
-    # scalar_bars {name: absolute bar}: replaces REL * max(|ref|, 1) for that scalar where a case has MEASURED the fp32 rounding of the
-    # quantity on the oracle itself (tests/test_presence_paths.py); every other bar is the file's own
-    # discrete decisions first: exact
-    for k in ("presence", "prop_pres", "disc_pres", "obj_id", "num_steps_per_sample"):
-        if k in ref_out:
-            assert np.array_equal(getattr(m, k).cpu().numpy(), np.asarray(ref_out[k], dtype=np.float32)), k
-    worst = {}
-    for k in names:
-        got = m.outputs[k].cpu().numpy()
-        ref = np.asarray(ref_out[k])
-        if got.shape != ref.shape and got.shape[-1] == 1 and got.shape[:-1] == ref.shape:
-            # n_steps_per_image = 1: the reference squeezes EVERY output whose last dimension is 1 before it writes it
-            # (seq.py:255-257, restated by the oracle), the per-slot log-probabilities [R, 1] included; the HIP outputs keep [T, R, N]
-            got = got[..., 0]
-        assert got.shape == ref.shape, (k, got.shape, ref.shape)
-        scale = max(np.abs(ref).max(), 1.0)
-        worst[k] = float(np.abs(got - ref).max() / scale)
-    bad = {k: v for k, v in worst.items() if v > tol}
-    assert not bad, bad
-    for k in ("log_weights", "elbo_iwae_per_example"):
-        assert rel_err(getattr(m, k).cpu().numpy(), ref_model[k]) < REL, k
-    for k in ("elbo_vae", "elbo_iwae", "data_ll", "kl", "log_p_z", "log_q_z_given_x"):
-        got, ref = float(getattr(m, k)), float(ref_model[k])
-        assert abs(got - ref) <= (scalar_bars or {}).get(k, REL * max(abs(ref), 1.0)), (k, got, ref)
-    return worst
-
-
 CHAIN = {"slot_chain": 1}   # option of the library: the slot loops as one persistent launch per frame and phase (sqair_chain.h)
 
 
@@ -83,7 +55,7 @@ def test_forward_matches_golden_fixture(name, options):
     ref_model = {k[6:]: z[k] for k in z.files if k.startswith("model_")}
     m = run_hip(F, (H, W), P, z["obs"], z["noise"], nums=z["nums"], resample_u=z["resample_u"], options=options)
     names = [k for k in ref_out if k in m.outputs]
-    worst = _check_against(m, ref_out, ref_model, names, T, tol=GOLDEN_TOL)
+    worst = check_against(m, ref_out, ref_model, names, T, tol=GOLDEN_TOL)
     print(name, "worst scaled abs err:", max(worst.values()), max(worst, key=worst.get))
     _record_parity(name + ("" if options is None else "+slot_chain"), worst)
     if K > 1:
@@ -95,43 +67,12 @@ def test_forward_matches_golden_fixture(name, options):
         assert abs(float(getattr(m, k)) - float(ref_model[k])) <= 1e-4 * max(1.0, abs(float(ref_model[k]))), k
 
 
-def _live_oracle_inputs(F, hw, T, B, edits=None):
-    """Frames, parameters and the decision-stable noise draw of a live-oracle case, with the oracle's result.  edits: names of
-    tests/latent_regimes.EDITS applied to the initialised parameters (tests/test_regime_paths.py)."""
-    K, N = int(F.k_particles), int(F.n_steps_per_image)
-    d = make_sequences(B, T=T, canvas=hw, n_objects=(1, 2), obj_size=20, seed=9)
-    obs = to_float(d["imgs"])
-    P = params32(F, hw, 5, 0.05, obs.mean((0, 1)))
-    if edits:
-        from tests import latent_regimes
-        P = latent_regimes.apply_edits(P, F, edits)
-    # the draw is chosen on the ORACLE's own decision margin (never on the HIP result); presence must then agree exactly
-    noise, ref, _, margin = stable_noise(F, hw, P, obs, T, B * K, N, nums=d["nums"], nzw=4 + int(F.n_what) + 1)
-    # which slot layouts the case reaches (tests/presence_patterns.py; the cases that REQUIRE some are in tests/test_presence_paths.py)
-    counts = presence_patterns.count(presence_patterns.classify_outputs(ref.outputs, N))
-    print(presence_patterns.table(counts))
-    return dict(d=d, obs=obs, P=P, noise=noise, ref=ref, margin=margin, counts=counts)
-
-
-def _live_oracle_case(F, hw=(32, 40), T=3, B=3, tol=5e-4, options=None, inputs=None, scalar_bars=None):
-    x = inputs or _live_oracle_inputs(F, hw, T, B)
-    d, obs, P, noise, ref = x["d"], x["obs"], x["P"], x["noise"], x["ref"]
-    m = run_hip(F, hw, P, obs, noise, nums=d["nums"], options=options)
-    assert np.array_equal(m.prop_pres.cpu().numpy(), ref.prop_pres.numpy())
-    assert np.array_equal(m.disc_pres.cpu().numpy(), ref.disc_pres.numpy())
-    ref_out = {k: v.numpy() for k, v in ref.outputs.items() if not k.startswith("_")}
-    ref_model = {k: getattr(ref, k).numpy() for k in ("log_weights", "elbo_iwae_per_example", "elbo_vae", "elbo_iwae",
-                                                      "data_ll", "kl", "log_p_z", "log_q_z_given_x")}
-    _check_against(m, ref_out, ref_model, list(ref_out), T, tol, scalar_bars)
-    return m, ref
-
-
 @pytest.mark.parametrize("K,N,T,B", [(1, 1, 1, 1), (1, 4, 2, 1), (5, 1, 3, 2), (2, 2, 1, 17), (7, 3, 2, 5)])
 def test_degenerate_sizes_vs_live_oracle(K, N, T, B):
     """The smallest sizes of every dimension (one particle, one slot, one frame, one sequence) and ragged ones (17 sequences x 2
     particles = 34 rows, 35 rows: a last 16-row tile of 2 / 3 rows) against the live oracle, every output."""
     F = make_flags(k_particles=K, n_steps_per_image=N)
-    _live_oracle_case(F, hw=(32, 40), T=T, B=B)
+    live_oracle_case(F, hw=(32, 40), T=T, B=B)
 
 
 @pytest.mark.parametrize("K,N,T,B", [(256, 2, 2, 1), (2, 14, 2, 1), (64, 8, 2, 1)])
@@ -139,7 +80,7 @@ def test_maximum_sizes_vs_live_oracle(K, N, T, B):
     """The largest particle and slot counts `sqair_create` accepts (256 particles; 14 slots, on the wide build; 8 slots x 64
     particles on the product build) against the live oracle, every output."""
     F = make_flags(k_particles=K, n_steps_per_image=N)
-    _live_oracle_case(F, hw=(32, 40), T=T, B=B)
+    live_oracle_case(F, hw=(32, 40), T=T, B=B)
 
 
 @pytest.mark.parametrize("hw", [(12, 14), (200, 300), (3, 250), (257, 5)])
@@ -147,7 +88,7 @@ def test_extreme_frame_shapes_vs_live_oracle(hw):
     """Frames smaller than the 20 x 20 glimpse, much larger than the LDS-staged crop takes (60 000 pixels), and degenerate
     aspect ratios (row-wave canvas kernels: 250 columns; 5 columns) -- inference takes any H x W -- against the live oracle."""
     F = make_flags(k_particles=2, n_steps_per_image=3)
-    _live_oracle_case(F, hw=hw, T=2, B=2)
+    live_oracle_case(F, hw=hw, T=2, B=2)
 
 
 def test_empty_frames_vs_live_oracle():
@@ -163,14 +104,14 @@ def test_empty_frames_vs_live_oracle():
     ref_out = {k: v.numpy() for k, v in ref.outputs.items() if not k.startswith("_")}
     ref_model = {k: getattr(ref, k).numpy() for k in ("log_weights", "elbo_iwae_per_example", "elbo_vae", "elbo_iwae",
                                                       "data_ll", "kl", "log_p_z", "log_q_z_given_x")}
-    _check_against(m, ref_out, ref_model, list(ref_out), T)
+    check_against(m, ref_out, ref_model, list(ref_out), T)
 
 
 @pytest.mark.parametrize("prior,disc_prior,rec", [("rw", "cat", True), ("guided", "geom", True), ("rnn", "cat", False)])
 def test_forward_flag_variants_vs_live_oracle(prior, disc_prior, rec):
     F = make_flags(k_particles=2, n_steps_per_image=3, prop_prior_type=prior, disc_prior_type=disc_prior,
                    rec_where_prior=rec, masked_glimpse=(prior != "guided"))
-    _live_oracle_case(F)
+    live_oracle_case(F)
 
 
 @pytest.mark.parametrize("rnn", ["VanillaRNN", "GRU", "LSTM"])
@@ -180,13 +121,13 @@ def test_all_cell_combinations_forward(rnn):
     for tc in ("VanillaRNN", "GRU", "LSTM"):
         for pc in ("VanillaRNN", "GRU", "LSTM"):
             F = make_flags(k_particles=2, n_steps_per_image=2, transition=rnn, time_transition=tc, prior_transition=pc)
-            _live_oracle_case(F, hw=(24, 28), T=3, B=2)
+            live_oracle_case(F, hw=(24, 28), T=3, B=2)
 
 
 def test_forward_vanilla_temporal_and_prior_cells_vs_live_oracle():
     """time_transition = prior_transition = VanillaRNN (Sonnet takes any core by name, mlp_mnist_model.py:86-87,125)."""
     F = make_flags(k_particles=3, n_steps_per_image=4, time_transition="VanillaRNN", prior_transition="VanillaRNN")
-    m, ref = _live_oracle_case(F, T=4, B=3)
+    m, ref = live_oracle_case(F, T=4, B=3)
     assert float(ref.prop_pres.sum()) > 0
 
 
@@ -194,7 +135,7 @@ def test_forward_gru_slot_rnn_vs_live_oracle():
     """transition=GRU: the Sonnet GRU (reset gate applied BEFORE the recurrent candidate matmul) as the slot RNN of both
     cores, two launches per slot like the temporal cell."""
     F = make_flags(k_particles=3, n_steps_per_image=4, transition="GRU")
-    m, ref = _live_oracle_case(F, T=4, B=3)
+    m, ref = live_oracle_case(F, T=4, B=3)
     assert float(ref.prop_pres.sum()) > 0 and float(ref.disc_pres.sum()) > 0
 
 
@@ -203,7 +144,7 @@ def test_forward_lstm_slot_rnn_vs_live_oracle(cells):
     """transition=LSTM (configs/mlp_mnist_model.py:86): the slot RNN of the discovery and the propagation core carries
     (hidden, cell) from slot to slot (core.py:187-189, :304-305); every consumer reads the hidden output."""
     F = make_flags(k_particles=3, n_steps_per_image=4, transition="LSTM", time_transition=cells[0], prior_transition=cells[1])
-    m, ref = _live_oracle_case(F, T=4, B=3)
+    m, ref = live_oracle_case(F, T=4, B=3)
     assert float(ref.prop_pres.sum()) > 0 and float(ref.disc_pres.sum()) > 0
 
 
@@ -212,7 +153,7 @@ def test_forward_lstm_prior_cell_vs_live_oracle(cells):
     """prior_transition=LSTM (configs/mlp_mnist_model.py:125): the propagation prior's recurrent state is [hidden | cell],
     its Linear reads the cell output (propagate.py:80-83)."""
     F = make_flags(k_particles=2, n_steps_per_image=3, time_transition=cells[0], prior_transition=cells[1])
-    m, ref = _live_oracle_case(F, T=4, B=3)
+    m, ref = live_oracle_case(F, T=4, B=3)
     assert float(ref.prop_pres.sum()) > 0, "case must exercise propagation"
     got = m.outputs["final_prior_state"].cpu().numpy()
     want = ref.outputs["_final_prior_state"].numpy()
@@ -226,7 +167,7 @@ def test_forward_lstm_temporal_cell_vs_live_oracle(K, N, T, B):
     cell"): the temporal state of a slot is [hidden | cell], the slot networks read the CELL half (core.py:284), the
     heads read the new hidden state."""
     F = make_flags(k_particles=K, n_steps_per_image=N, time_transition="LSTM")
-    m, ref = _live_oracle_case(F, T=T, B=B)
+    m, ref = live_oracle_case(F, T=T, B=B)
     assert float(ref.prop_pres.sum()) > 0, "case must exercise propagation"
     got = m.outputs["final_temporal_state"].cpu().numpy()
     want = ref.outputs["_final_temporal_state"].numpy()
@@ -239,7 +180,7 @@ def test_long_sequence_vs_live_oracle():
     configurations, objects entering and leaving; all outputs against the oracle.  fp32 rounding compounds through 30
     recurrent frames: per-output tolerance 3e-3 of the output's scale (the ELBO terms stay within 1e-4 relative)."""
     F = make_flags(k_particles=2, n_steps_per_image=3)
-    m, ref = _live_oracle_case(F, hw=(50, 50), T=30, B=2, tol=3e-3)
+    m, ref = live_oracle_case(F, hw=(50, 50), T=30, B=2, tol=3e-3)
     assert float(ref.prop_pres.sum()) > 10
 
 
@@ -330,7 +271,7 @@ def test_other_baseline_configs_vs_oracle(cfg_id, B):
     ref_out = {k: v.numpy() for k, v in ref.outputs.items() if not k.startswith("_")}
     ref_model = {k: getattr(ref, k).numpy() for k in ("log_weights", "elbo_iwae_per_example", "elbo_vae", "elbo_iwae",
                                                       "data_ll", "kl", "log_p_z", "log_q_z_given_x")}
-    _check_against(m, ref_out, ref_model, list(ref_out), T)
+    check_against(m, ref_out, ref_model, list(ref_out), T)
 
 
 @pytest.mark.parametrize("cfg_id", [4, 5])
@@ -673,7 +614,7 @@ def test_forward_padded_hidden_width_final_states_in_reference_shapes(n_units, c
     """n_hidden = 64 / 160 / 192 run on 128- / 256-wide layers with inert padding units; all 38 outputs against the oracle and
     the final recurrent states come back in the caller's widths ([hidden | cell] halves of n_hidden each)."""
     F = make_flags(k_particles=2, n_steps_per_image=3, n_units=n_units, time_transition=cells[0], prior_transition=cells[1])
-    m, ref = _live_oracle_case(F, T=3, B=3)
+    m, ref = live_oracle_case(F, T=3, B=3)
     assert float(ref.prop_pres.sum()) > 0
     nh = 32 * n_units
     for name, mult in (("final_temporal_state", 2 if cells[0] == "LSTM" else 1), ("final_prior_state", 2 if cells[1] == "LSTM" else 1)):

@@ -5,16 +5,13 @@ import numpy as np
 import pytest
 import torch
 
-from sqair_amd import _capi
 from sqair_amd.data import make_sequences, to_float
 from sqair_amd.flags import make_flags
 from tests.hip_util import draw_noise, params32
 
+from tests.pass_cases import spec_launches
+
 pytestmark = pytest.mark.gpu
-
-
-def _spec_launches():
-    return int(_capi.lib().sqair_debug_specialised_launches())
 
 
 def _outputs(core):
@@ -49,23 +46,23 @@ def test_specialised_kernels_are_bit_identical_to_the_generic_ones(B, K, N, T, h
 
     def run_inference(spec, use_graph):
         core, m = make(spec)
-        n0 = _spec_launches()
+        n0 = spec_launches()
         m.run(noise=noise, use_graph=use_graph)
         torch.cuda.synchronize()
-        return _outputs(core), _spec_launches() - n0, (core.lib.sqair_graph_nodes(core.handle) if use_graph else 0)
+        return _outputs(core), spec_launches() - n0, (core.lib.sqair_graph_nodes(core.handle) if use_graph else 0)
 
     def run_training(spec):
         # the training-mode forward pass (tape kept) eager, then again inside ONE graph replay of a gradient evaluation (forward
         # with tape + targets + backward).  The backward pass accumulates with atomics, so the gradient itself is not compared
         # bit for bit: what the replayed forward pass left in the outputs is.
         core, m = make(spec)
-        n0 = _spec_launches()
+        n0 = spec_launches()
         with core.on_stream():
             core.noise.copy_(torch.as_tensor(noise).reshape(core.noise.shape))
             core.forward(train=True)
             core.stream.synchronize()
             eager = _outputs(core)
-            n_fwd = _spec_launches() - n0
+            n_fwd = spec_launches() - n0
             g = core.grad_step(use_graph=True).clone()
             core.stream.synchronize()
             replay = _outputs(core)

@@ -11,60 +11,21 @@ import pytest
 import torch
 
 from sqair_amd import _capi
-from sqair_amd.data import make_sequences, to_float
-from sqair_amd.flags import make_flags
-from sqair_amd.model import SqairCore
 from sqair_amd.stream import SqairStream
 from tests import history_ref as H
-from tests.hip_util import draw_noise, params32
+from tests.stream_harness import FIELD_OF, OUTS, core, history_check, history_push, host, setup
 
 pytestmark = pytest.mark.gpu
 
-OUTS = ("what", "where", "presence", "obj_id", "log_weights_per_timestep")
-SMC_OUTS = ("ess", "resampled", "log_evidence", "ancestors")
-FIELD_OF = dict(where="where", presence="presence", obj_id="obj_id", what="what", log_w="log_weights_per_timestep")
 HW = (50, 50)
 
 
 def _setup(flags, B, T, seed=11):
-    F = make_flags(**flags)
-    obs = to_float(make_sequences(B, T=T, canvas=HW, seed=seed)["imgs"])
-    P = params32(F, HW, 3, 0.05, obs.mean((0, 1)))
-    N, K = int(F.n_steps_per_image), int(F.k_particles)
-    noise = draw_noise(np.random.default_rng(seed + 1), T, B * K, N, 4 + int(F.n_what) + 1)
-    return F, P, obs, noise
+    return setup(flags, B, T, HW, seed)
 
 
 def _core(F, P, options=None):
-    core = SqairCore(F, HW, options=options)
-    core.set_params(P)
-    return core
-
-
-def _host(out):
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in out.items()}
-
-
-def _push(rec, parent, o, fields=tuple(FIELD_OF)):
-    rec.push(parent, **{k: o[FIELD_OF[k]] for k in fields})
-
-
-def _check(st, rec, start, start_rows=None, lag=None, max_tracks=None, table=True, fields=tuple(FIELD_OF)):
-    """tracks() of `st` against the reference tracer over the steps recorded in `rec`; returns the device's result."""
-    got = _host(st.tracks(lag=lag, start=start, max_tracks=max_tracks, table=table))
-    lag = st.history if lag is None else lag
-    N = st.core.N
-    M = (2 * N if max_tracks is None else max_tracks) if table else None
-    if rec.steps:
-        want = H.trace(rec.steps, st.history, lag, st.K, None if start == "last" else start_rows, M)
-    else:
-        want = H.empty_trace(st.T, st.R, N, st.core.nw, lag, st.K, fields, M)
-    assert set(want) <= set(got), sorted(set(want) - set(got))
-    for k, v in want.items():
-        assert got[k].dtype == v.dtype and H.same_bits(got[k], v), (k, start, lag, np.argwhere(got[k] != v)[:4])
-    assert ("weights" in got) == (start == "next") and ("track_id" in got) == bool(table)
-    return got
+    return core(F, HW, P, options)
 
 
 # ---- (a) a hand-driven genealogy on a plain stream ---------------------------------------------------------------------------
@@ -77,19 +38,19 @@ def test_deterministic_genealogy():
               6: ("resample", [3, 3, 3, 3, 4, -1, 6, 6]), 8: ("resample", [0, 1, 2, 3, 5, 5, 7, 7]), 9: ("resample", [2, 2, 0, 0, 4, 5, 6, 7]),
               10: ("reset", [0])}
     rec = H.Recorder(R)
-    _check(st, rec, "next", st.carried.pending())      # nothing pushed yet: every frame invalid
+    history_check(st, rec, "next", st.carried.pending())      # nothing pushed yet: every frame invalid
     coalesced = moved = False
     for t in range(T):
         if t in script:
             getattr(st, script[t][0])(script[t][1])
         parent = st.carried.pending().copy()
-        _push(rec, parent, _host(st.step(obs[t:t + 1], noise=noise[t:t + 1])))
-        last = _check(st, rec, "last")
-        _check(st, rec, "last", lag=3)
+        history_push(rec, parent, host(st.step(obs[t:t + 1], noise=noise[t:t + 1])))
+        last = history_check(st, rec, "last")
+        history_check(st, rec, "last", lag=3)
         if t + 1 in script:                            # the map armed for the next step is where "next" starts from
             getattr(st, script[t + 1][0])(script[t + 1][1])
             script.pop(t + 1)
-        nxt = _check(st, rec, "next", st.carried.pending())
+        nxt = history_check(st, rec, "next", st.carried.pending())
         for o in (last, nxt):
             ua, anc = o["unique_ancestors"], o["ancestor_row"]
             coalesced |= bool(((ua < K) & (ua > 0)).any())
@@ -108,15 +69,15 @@ def test_smc_every_step(K):
     rec = H.Recorder(B * K)
     rng = np.random.default_rng(5)
     parent = np.full(B * K, -1)
-    _check(st, rec, "next", parent)
+    history_check(st, rec, "next", parent)
     moved = False
     for t in range(T):
-        o = _host(st.step(obs[t:t + 1], noise=noise[t:t + 1], uniforms=rng.uniform(size=B).astype(np.float32)))
-        _push(rec, parent, o)
+        o = host(st.step(obs[t:t + 1], noise=noise[t:t + 1], uniforms=rng.uniform(size=B).astype(np.float32)))
+        history_push(rec, parent, o)
         parent = o["ancestors"]
         moved |= not np.array_equal(parent, np.arange(B * K))
-        _check(st, rec, "last")
-        got = _check(st, rec, "next", parent)
+        history_check(st, rec, "last")
+        got = history_check(st, rec, "next", parent)
         assert np.allclose(got["weights"], 1.0 / K, rtol=1e-6, atol=0)   # resampled: the surviving set is equally weighted
         assert np.array_equal(got["best_row"], np.arange(B) * K)
     assert moved and (got["unique_ancestors"][0] <= got["unique_ancestors"][-1]).all()
@@ -131,13 +92,13 @@ def test_adaptive_smc():
     parent = np.full(B * K, -1)
     went = 0
     for t in range(T):
-        o = _host(st.step(obs[t:t + 1]))
-        _push(rec, parent, o)
+        o = host(st.step(obs[t:t + 1]))
+        history_push(rec, parent, o)
         parent = o["ancestors"]
         went += int(o["resampled"].sum())
         if t % 7 == 6 or t == T - 1:
-            _check(st, rec, "last", lag=5)
-            got = _check(st, rec, "next", parent)
+            history_check(st, rec, "last", lag=5)
+            got = history_check(st, rec, "next", parent)
             first = np.array([int(np.flatnonzero(row == row.max())[0]) for row in got["weights"]])
             assert np.array_equal(got["best_row"], np.arange(B) * K + first)
     assert 0 < went < B * T
@@ -175,12 +136,12 @@ def test_shapes_and_options(case):
             st.reset([1])
         if not smc:
             parent = st.carried.pending().copy()
-        o = _host(st.step(obs[s * Tp:(s + 1) * Tp], noise=noise[s * Tp:(s + 1) * Tp]))
-        _push(rec, parent, o, fields)
+        o = host(st.step(obs[s * Tp:(s + 1) * Tp], noise=noise[s * Tp:(s + 1) * Tp]))
+        history_push(rec, parent, o, fields)
         nxt = o["ancestors"] if smc else st.carried.pending()
         for lag in (1, 2, L):                               # lag < L and lag = L
-            _check(st, rec, "last", lag=lag, fields=fields)
-            got = _check(st, rec, "next", nxt, lag=lag, fields=fields, table=(lag == L))
+            history_check(st, rec, "last", lag=lag, fields=fields)
+            got = history_check(st, rec, "next", nxt, lag=lag, fields=fields, table=(lag == L))
             assert got["where"].shape == (lag * Tp, B * K, 3, 4)
         parent = nxt
     assert ("what" in got) == ("what" in fields) and ("log_w" in got) == ("log_w" in fields)
@@ -203,7 +164,7 @@ def test_history_leaves_the_stream_unchanged(smc):
         if not smc and t == 4:
             a.resample(np.arange(B * 4)[::-1].copy())
             b.resample(np.arange(B * 4)[::-1].copy())
-        oa, ob = _host(a.step(obs[t:t + 1], noise=noise[t:t + 1])), _host(b.step(obs[t:t + 1], noise=noise[t:t + 1]))
+        oa, ob = host(a.step(obs[t:t + 1], noise=noise[t:t + 1])), host(b.step(obs[t:t + 1], noise=noise[t:t + 1]))
         assert set(oa) == set(ob)
         for k in oa:
             assert H.same_bits(oa[k], ob[k]), (k, t)
@@ -227,10 +188,10 @@ def test_graph_replay_equals_eager():
         st = SqairStream(_core(F, P), B, outputs=OUTS, use_graph=use_graph, seed=3, resample="systematic", ess_frac=0.5, history=L)
         rec, parent, out = H.Recorder(B * K), np.full(B * K, -1), []
         for t in range(T):
-            o = _host(st.step(obs[t:t + 1]))
-            _push(rec, parent, o)
+            o = host(st.step(obs[t:t + 1]))
+            history_push(rec, parent, o)
             parent = o["ancestors"]
-            out.append((o, _check(st, rec, "next", parent), _check(st, rec, "last", lag=2)))
+            out.append((o, history_check(st, rec, "next", parent), history_check(st, rec, "last", lag=2)))
         runs.append(out)
         st.close()      # history and state off: the trace is refused again
         o = _capi.SqairTraceOutputs(T=1)
@@ -268,10 +229,10 @@ def test_track_table():
     st = SqairStream(_core(F, P), B, outputs=OUTS, resample="systematic", ess_frac=0.5, seed=9, history=L)
     rec, parent = H.Recorder(B * K), np.full(B * K, -1)
     for t in range(T):
-        o = _host(st.step(obs[t:t + 1]))
-        _push(rec, parent, o)
+        o = host(st.step(obs[t:t + 1]))
+        history_push(rec, parent, o)
         parent = o["ancestors"]
-    full = _check(st, rec, "next", parent)                      # the default M = 2 N
+    full = history_check(st, rec, "next", parent)                      # the default M = 2 N
     assert full["track_id"].shape == (B * K, 6)
     n = full["n_tracks"]
     print("n_tracks per row:", n.tolist())
@@ -279,8 +240,8 @@ def test_track_table():
     for M in (1, int(n.max()) - 1, int(n.max()), 9):
         if M < 1:
             continue
-        got = _check(st, rec, "next", parent, max_tracks=M)
-        _check(st, rec, "last", max_tracks=M, lag=7)
+        got = history_check(st, rec, "next", parent, max_tracks=M)
+        history_check(st, rec, "last", max_tracks=M, lag=7)
         assert np.array_equal(got["n_tracks"], n)               # the true count, whatever M
         assert ((got["track_id"] >= 0).sum(1) == np.minimum(n, M)).all()
     assert (n > 1).any()                                        # M = 1 truncated at least one row
@@ -305,8 +266,8 @@ def test_weights_equal_the_forecasts(smc):
             st.resample(np.array([1, 1, 2, 3, 4, 4, 4, 7, -1, 9, 10, 11]))
         if t == 4:
             st.reset([0])
-        w_t = _host(st.tracks(start="next", table=False))
-        w_f = _host(st.forecast(1, outputs=("presence",)))["weights"]
+        w_t = host(st.tracks(start="next", table=False))
+        w_f = host(st.forecast(1, outputs=("presence",)))["weights"]
         assert w_t["weights"].shape == (B, K) and H.same_bits(w_t["weights"], w_f), t
         first = np.array([int(np.flatnonzero(row == row.max())[0]) for row in w_f])
         assert np.array_equal(w_t["best_row"], np.arange(B) * K + first)

@@ -17,7 +17,7 @@ import torch
 from sqair_amd import _capi
 from tests import hota_cases as HC
 from tests import hota_ref as R
-from tests.test_hota_solve_kernel import close_enough, handle, judged, run_solve, struct, to_device
+from tests.hota_cases import close_enough, handle, judged, run_solve, struct, to_device
 
 pytestmark = pytest.mark.gpu
 

@@ -21,14 +21,7 @@ MEASURED = {"G4_N4_P32_L64": dict(hota=2.220446049250313e-16, deta=0.0, assa=2.2
             "G1_N4_P8_L16": dict(hota=0.0, deta=0.0, assa=0.0, clips_tp_differs=0),
             "G16_N14_P64_L32_wide": dict(hota=0.0021999134305397683, deta=0.003318817384399708, assa=0.001154404532568376,
                                          clips_tp_differs=2)}
-NOTE = ("statement_vs_float: the header's integer statement of HOTA against the published algorithm in float64 on the clips of "
-        "tests/hota_cases.py (CPU); device_vs_scipy: the share of records where the device's matching is not SciPy's own and the HOTA "
-        "difference that makes (tests/test_hota_solve_kernel.py, recorded, not gated)")
 BOX = (10.0, 10.0, 4.0, 6.0)
-
-
-def fresh_parity():
-    return {"note": NOTE, "statement_vs_float": {}, "device_vs_scipy": {}}
 
 
 def clip(frames, G, N, P=8, L=64):
@@ -172,7 +165,7 @@ def test_the_integer_statement_against_the_float_algorithm(i):
 
     def update(data):
         data["statement_vs_float"][HC.case_id(HC.CASES[i])] = dict(clips=clips, clips_tp_differs=differs, **worst)
-    merge_parity("hota_parity.json", fresh_parity, update)
+    merge_parity("hota_parity.json", R.fresh_parity, update)
     assert clips >= HC.B - 1
     measured = MEASURED[HC.case_id(HC.CASES[i])]
     for n, v in worst.items():

@@ -19,29 +19,10 @@ import torch
 from sqair_amd import _capi
 from tests import hota_cases as HC
 from tests import hota_ref as R
-from tests.abi_host import open_handle
-from tests.kernel_unit import merge_parity
-from tests.test_hota_ref import fresh_parity
+from tests.abi_host import LANE_LIBS as LIBS
+from tests.hota_cases import close_enough, handle, judged, record, run_solve, struct, to_device
 
 pytestmark = pytest.mark.gpu
-
-LIBS = {"product": None, "wide": _capi.WIDE_LIB_PATH}
-RTOL = 1e-12
-_handles = {}
-
-
-def handle(lib_name, N=4):
-    if (lib_name, N) not in _handles:
-        _handles[lib_name, N] = open_handle(LIBS[lib_name], HC.HW, k_particles=2, n_steps_per_image=N, n_what=6)
-    return _handles[lib_name, N]
-
-
-def record(section, case, **figures):
-    def update(data):
-        data["build_id"] = _capi.build_id()
-        data["device"] = torch.cuda.get_device_name(0)
-        data[section][case] = figures
-    merge_parity("hota_parity.json", fresh_parity, update)
 
 
 @functools.lru_cache(maxsize=None)
@@ -59,54 +40,8 @@ def reference_log(i):
     return log
 
 
-def to_device(log, G, P):
-    d = {n: torch.from_numpy(np.array(v)).cuda() for n, v in log.items()}
-    d["work"] = torch.full((log["col_id"].shape[0], G, P, _capi.HOTA_BINS), 12345, dtype=torch.int32, device="cuda")   # any content
-    return d
-
-
-def struct(d, P, L):
-    return _capi.SqairLaneHota(P=P, L=L, **{n: d[n].data_ptr() for n in _capi.HOTA_LOG + _capi.HOTA_TOTALS})
-
-
-def run_solve(lib_name, d, G, N, P, L, close=None, want=("open_i", "open_f", "open_c", "match"), stream=None):
-    """One launch on the device log ``d`` (updated in place); returns {name: array} of the outputs asked for."""
-    lib, h = handle(lib_name)
-    n = d["col_id"].shape[0]
-    shapes = _capi.hota_solve_shapes(n, G, L)
-    out = {k: torch.full(shapes[k], -7, dtype=getattr(torch, _capi.field_dtype("sqair_lane_hota_solve", k)), device="cuda") for k in want}
-    mask = None if close is None else torch.from_numpy(np.asarray(close, np.int32)).cuda()
-    ptr = lambda k: out[k].data_ptr() if k in out else None
-    rc = lib.sqair_lane_hota_solve(h, C.byref(struct(d, P, L)), G, N, n, None if mask is None else mask.data_ptr(), ptr("open_i"),
-                                   ptr("open_f"), ptr("open_c"), ptr("match"), C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream))
-    assert rc == 0, lib.sqair_last_error(h)
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in out.items()}
-
-
 def changed(d, log):
     return [n for n in log if not np.array_equal(d[n].cpu().numpy(), log[n], equal_nan=True)]
-
-
-def judged(log, got, close=None):
-    """Judges the device's ``match`` of every record in use on the reference's tables, imposes it, and returns the reference's
-    (log after, open_i, open_f, open_c) with the number of records judged and of those whose matching is not SciPy's own."""
-    _, _, _, _, own, tables = R.solve(log)
-    B, L, G = got["match"].shape
-    n = differ = 0
-    for b in range(B):
-        F = int(log["frames"][b])
-        assert (got["match"][b, F:] == -7).all(), b                                # the records not in use: nothing is written
-        for r in range(F):
-            R.judge(tables[b][r], got["match"][b, r])
-            n += 1
-            differ += not np.array_equal(got["match"][b, r], own[b, r])
-    after, oi, of, oc, _, _ = R.solve(log, close=close, match=got["match"])
-    return after, oi, of, oc, n, differ
-
-
-def close_enough(a, b):
-    return np.allclose(a, b, rtol=RTOL, atol=0.0)
 
 
 @pytest.mark.parametrize("lib_name", list(LIBS))

@@ -1,7 +1,7 @@
 """-m gpu: HOTA scoring inside the streaming pass (include/sqair_hip.h: sqair_set_hota; SqairStream(estimate=True, score=True,
 score_hota=True)): B = 4, K = 5, N = 3, 50 x 50, SMC, identity=True with score_ids="lane", twelve steps.
 
-The truth is made from an untruthed run's own lane answers the way tests/test_score_stream.py makes its truth (shifted, rotated
+The truth is made from an untruthed run's own lane answers the way tests/test_score_stream.py makes its truth (tests/stream_harness.py: make_truth) (shifted, rotated
 between the slots every four frames, thinned, some added), so that matches, misses and id changes all occur.  Checked here: the log
 equals the reference's append (tests/hota_ref.py) on the returned lane answers -- columns, rows and counters exactly, q within +-1
 --; ``hota_score()`` equals the reference's solve of the stream's own log on the device's own matching, which is judged; every other
@@ -15,18 +15,14 @@ import pytest
 import torch
 
 from sqair_amd import _capi
-from sqair_amd.data import make_sequences, to_float
-from sqair_amd.flags import make_flags
 from sqair_amd.lane import hota_figures
-from sqair_amd.model import SqairCore
-from sqair_amd.stream import SqairStream
 from tests import hota_ref as R
-from tests.hip_util import draw_noise, params32
-from tests.test_hota_solve_kernel import RTOL
-from tests.test_score_stream import B, G, HW, IOU, N, OUTS, SMC_OUTS, _host, _make_truth, _same_bits
+from tests.hota_cases import RTOL
+from tests.stream_harness import OUTS, SCORE, SMC_OUTS, host, same_bits, setup, stream, unscored_truth
 
 pytestmark = pytest.mark.gpu
 
+HW, B, G, N, IOU = SCORE.HW, SCORE.B, SCORE.G, SCORE.N, SCORE.IOU
 FLAGS = dict(k_particles=5, n_steps_per_image=N)
 P_IDS, L_FRAMES = 6, 8
 T = 12
@@ -36,17 +32,11 @@ CARRIED = ("state", "log_weight_sum", "log_z", "log_evidence", "ess", "u", "resa
 
 
 def _setup(seed=11):
-    F = make_flags(**FLAGS)
-    obs = to_float(make_sequences(B, T=T, canvas=HW, seed=seed)["imgs"])
-    P = params32(F, HW, 3, 0.05, obs.mean((0, 1)))
-    noise = draw_noise(np.random.default_rng(seed + 1), T, B * int(F.k_particles), int(F.n_steps_per_image), 4 + int(F.n_what) + 1)
-    return F, P, obs, noise
+    return setup(FLAGS, B, T, HW, seed)
 
 
 def _stream(F, P, **kw):
-    core = SqairCore(F, HW)
-    core.set_params(P)
-    return SqairStream(core, B, outputs=OUTS, estimate=True, estimate_iou=IOU, identity=True, **dict(SMC, **kw))
+    return stream((F, HW, P), B, outputs=OUTS, estimate=True, estimate_iou=IOU, identity=True, **dict(SMC, **kw))
 
 
 def _scored(F, P, hota=True, **kw):
@@ -55,10 +45,7 @@ def _scored(F, P, hota=True, **kw):
 
 
 def _truth(F, P, obs, noise, **kw):
-    st = _stream(F, P, **kw)
-    outs = [_host(st.step(obs[t:t + 1], noise=noise[t:t + 1])) for t in range(T)]
-    st.close()
-    return _make_truth(outs, 1)
+    return unscored_truth(_stream(F, P, **kw), obs, noise)[0]
 
 
 def _log(st):
@@ -156,14 +143,14 @@ def test_hota_changes_nothing_else_and_equals_the_reference():
             assert (after["totals_c"][[1, 3], 0] == 1).all() and np.array_equal(after["totals_c"][[1, 3], 1], before["frames"][[1, 3]])
             assert np.array_equal(after["totals_i"], ref.log["totals_i"]) and np.allclose(after["totals_f"], ref.log["totals_f"], rtol=RTOL, atol=0)
             ref.log["totals_f"] = after["totals_f"]      # (within the doubles' tolerance: the rest is compared against the device's own sums)
-        o, b, c, oi, bi = (_host(s.step(obs[f], noise=noise[f], truth=truth[t])) for s in streams)
+        o, b, c, oi, bi = (host(s.step(obs[f], noise=noise[f], truth=truth[t])) for s in streams)
         for x, y, sx, sy in ((o, b, off, on), (oi, bi, off_idf, on_idf)):
             assert set(x["lane"]) == set(y["lane"])      # nothing per frame: HOTA is not a per-frame quantity
-            _same_bits(x, y, OUTS + SMC_OUTS, t)
-            _same_bits(x["lane"], y["lane"], x["lane"].keys(), t)
+            same_bits(x, y, OUTS + SMC_OUTS, t)
+            same_bits(x["lane"], y["lane"], x["lane"].keys(), t)
             for k in CARRIED:
                 assert torch.equal(getattr(sx, k), getattr(sy, k)), (t, k)
-        _same_bits(b["lane"], c["lane"], b["lane"].keys(), (t, "eager"))
+        same_bits(b["lane"], c["lane"], b["lane"].keys(), (t, "eager"))
         ref.step(b, truth[t])
     for sx, sy in ((off, on), (off_idf, on_idf)):
         for k in ("counts", "iou_sum", "last_id"):
@@ -203,7 +190,7 @@ def test_one_frame_per_step_and_four_give_the_same_tables():
     one, four = _scored(F, P, **never), _scored(F, P, frames_per_step=4, **never)
     ref = _Ref()
     for t in range(T):
-        ref.step(_host(one.step(obs[t:t + 1], noise=noise[t:t + 1], truth=truth[t])), truth[t])
+        ref.step(host(one.step(obs[t:t + 1], noise=noise[t:t + 1], truth=truth[t])), truth[t])
     for s in range(T // 4):
         f = slice(4 * s, 4 * s + 4)
         four.step(obs[f], noise=noise[f], truth={k: np.concatenate([truth[t][k] for t in range(4 * s, 4 * s + 4)]) for k in truth[0]})

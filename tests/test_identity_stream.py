@@ -14,20 +14,12 @@ import pytest
 import torch
 
 from sqair_amd import _capi
-from sqair_amd.data import make_sequences, to_float
-from sqair_amd.flags import make_flags
-from sqair_amd.model import SqairCore
-from sqair_amd.stream import SqairStream
 from tests import identity_ref as IR
 from tests import score_ref as SR
-from tests.hip_util import draw_noise, params32
+from tests.stream_harness import EST_KEYS, OUTS, SMC_OUTS, host, run, same_bits, setup, stream, words
 
 pytestmark = pytest.mark.gpu
 
-OUTS = ("what", "where", "presence", "obj_id", "log_weights_per_timestep")
-SMC_OUTS = ("ess", "resampled", "log_evidence", "ancestors")
-EST_KEYS = {"best_row", "weights", "ess", "count_prob", "expected_count", "map_count", "presence", "obj_id", "where", "what", "box",
-            "support", "box_mean"}
 ID_KEYS = {"lane_id", "id_how", "track_len"}
 HW = (50, 50)
 FLAGS = dict(k_particles=5, n_steps_per_image=3)
@@ -45,42 +37,11 @@ T = 24
 
 
 def _setup(T=T, seed=11):
-    F = make_flags(**FLAGS)
-    obs = to_float(make_sequences(B, T=T, canvas=HW, seed=seed)["imgs"])
-    P = params32(F, HW, 3, 0.05, obs.mean((0, 1)))
-    noise = draw_noise(np.random.default_rng(seed + 1), T, B * int(F.k_particles), int(F.n_steps_per_image), 4 + int(F.n_what) + 1)
-    return F, P, obs, noise
+    return setup(FLAGS, B, T, HW, seed)
 
 
 def _stream(F, P, **kw):
-    core = SqairCore(F, HW)
-    core.set_params(P)
-    return SqairStream(core, B, outputs=OUTS, estimate=True, estimate_iou=0.5, **kw)
-
-
-def _host(out):
-    torch.cuda.synchronize()
-    return {k: ({n: v.cpu().numpy() for n, v in x.items()} if isinstance(x, dict) else x.cpu().numpy()) for k, x in out.items()}
-
-
-def _bits(a):
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def _same_bits(a, b, keys, where):
-    for k in keys:
-        assert np.array_equal(_bits(a[k]), _bits(b[k])), (where, k)
-
-
-def _run(st, obs, noise, Ts=1, before=None, **step_kw):
-    outs = []
-    for s in range(obs.shape[0] // Ts):
-        if before is not None:
-            before(s)
-        f = slice(s * Ts, (s + 1) * Ts)
-        kw = {k: (v[f] if k == "observed" else v[s]) for k, v in step_kw.items()}
-        outs.append(_host(st.step(obs[f], noise=noise[f], **kw)))
-    return outs
+    return stream((F, HW, P), B, outputs=OUTS, estimate=True, estimate_iou=0.5, **kw)
 
 
 def _reference(outs, resets=None, appearance=True, cfg=CFG):
@@ -124,11 +85,11 @@ def _check(st, outs, resets=None, appearance=True, cfg=CFG):
     assert np.array_equal(ids["trk_id"].numpy()[whole], mem["trk_id"][whole]) and np.array_equal(ids["next_id"].numpy()[whole], mem["next_id"][whole])
     live = (mem["trk_id"] >= 0) & whole[:, None]
     for n in ("trk_age", "trk_len", "trk_box"):
-        assert np.array_equal(_bits(ids[n].numpy())[live], _bits(mem[n])[live]), n
+        assert np.array_equal(words(ids[n].numpy())[live], words(mem[n])[live]), n
     torch.cuda.synchronize()
     dev = {n: st._ident[n].cpu().numpy() for n in st._ident}
     assert np.array_equal(dev["trk_word"][live], mem["trk_word"][live])
-    assert ("trk_what" in dev) == appearance and (not appearance or np.array_equal(_bits(dev["trk_what"])[live], _bits(mem["trk_what"])[live]))
+    assert ("trk_what" in dev) == appearance and (not appearance or np.array_equal(words(dev["trk_what"])[live], words(mem["trk_what"])[live]))
     tot = dict(zip(IR.COUNTS, mem["counts"][whole].sum(0).tolist()))
     pooled = lambda n: float(ids[n].sum()) / float(ids["objects"].sum())      # (the stream pools its own counters, over every lane)
     assert ids["bridged_rate"] == pytest.approx(pooled("bridged")) and ids["reidentified_rate"] == pytest.approx(pooled("reidentified"))
@@ -143,13 +104,13 @@ def test_the_identity_changes_nothing_else_and_equals_the_reference():
     outs, went = [], 0
     for t in range(T):
         f = slice(t, t + 1)
-        o, b, c = (_host(s.step(obs[f], noise=noise[f])) for s in (off, on, eager))
+        o, b, c = (host(s.step(obs[f], noise=noise[f])) for s in (off, on, eager))
         assert set(o["lane"]) == EST_KEYS and set(b["lane"]) == EST_KEYS | ID_KEYS
-        _same_bits(o, b, OUTS + SMC_OUTS, t)
-        _same_bits(o["lane"], b["lane"], EST_KEYS, t)
+        same_bits(o, b, OUTS + SMC_OUTS, t)
+        same_bits(o["lane"], b["lane"], EST_KEYS, t)
         for k in ("state", "log_weight_sum", "log_z", "log_evidence", "ess", "u", "resampled", "_src"):
             assert torch.equal(getattr(off, k), getattr(on, k)), (t, k)
-        _same_bits(b["lane"], c["lane"], b["lane"].keys(), (t, "eager"))      # eager and graph: the same bits
+        same_bits(b["lane"], c["lane"], b["lane"].keys(), (t, "eager"))      # eager and graph: the same bits
         assert all(b["lane"][n].shape == (1, B, N) and b["lane"][n].dtype == np.int32 for n in ID_KEYS)
         outs.append(b)
         went += int(b["resampled"].sum())
@@ -171,16 +132,16 @@ def test_identity_against_reference(resample, Ts, appearance):
     F, P, obs, noise = _setup(seed=3)
     kw = dict(resample=resample, ess_frac=0.5, seed=17, identity_appearance=appearance, **IDENT)
     st = _stream(F, P, frames_per_step=Ts, **kw)
-    outs = _run(st, obs, noise, Ts)
+    outs = run(st, obs, noise, Ts)
     tot = _check(st, outs, appearance=appearance)
     print(resample, Ts, appearance, tot, "occurred:", [n for n in ("kept", "bridged", "reidentified", "born", "ended") if tot[n] > 0])
     if Ts == 3 and resample is None:      # three frames per step equal three single steps: the outputs and the whole memory
         # (without SMC the two runs see the same rows; the kernel's five inputs are compared first -- the estimate's weights may differ
         #  in the last bit between the two, the host adds a step's log weights to the carried sum in another order)
         one = _stream(F, P, frames_per_step=1, **kw)
-        singles = _run(one, obs, noise, 1)
+        singles = run(one, obs, noise, 1)
         for n in ("box", "presence", "obj_id", "what", "best_row") + tuple(sorted(ID_KEYS)):
-            assert np.array_equal(_bits(np.concatenate([o["lane"][n] for o in outs])), _bits(np.concatenate([o["lane"][n] for o in singles]))), n
+            assert np.array_equal(words(np.concatenate([o["lane"][n] for o in outs])), words(np.concatenate([o["lane"][n] for o in singles]))), n
         for k in st._ident:
             a, e = st._ident[k], one._ident[k]
             assert torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a, e.view(torch.int32) if e.dtype == torch.float32 else e), k
@@ -194,7 +155,7 @@ def test_a_coasted_lane_needs_no_case_of_its_own():
     rng = np.random.default_rng(2)
     observed = np.stack([np.ones(B, bool) if t < 2 else rng.uniform(size=B) < 0.6 for t in range(T)])
     st = _stream(F, P, missing=True, **IDENT)
-    outs = _run(st, obs, noise, observed=observed)
+    outs = run(st, obs, noise, observed=observed)
     tot = _check(st, outs)
     coasted = sum(int(((o["lane"]["lane_id"][0] >= 0).any(-1) & ~observed[t]).sum()) for t, o in enumerate(outs))
     print("coasted", tot, "coasted (frame, lane)s with an identified object:", coasted)
@@ -219,7 +180,7 @@ def test_reset_frees_the_lanes_tracks_and_keeps_next_id():
             assert (st._ident["trk_id"][lanes] == -1).all() and torch.equal(st._ident["trk_id"][keep], was["trk_id"][keep])
             assert all(torch.equal(st._ident[k], was[k]) for k in was if k != "trk_id")      # next_id and the counters stay
             seen[s] = int(was["next_id"][lanes].min())
-    outs = _run(st, obs, noise, before=before)
+    outs = run(st, obs, noise, before=before)
     tot = _check(st, outs, resets)
     ids = np.concatenate([o["lane"]["lane_id"] for o in outs])
     for s, lanes in resets.items():      # after a reset every id of the lane is a fresh one: never reused
@@ -267,14 +228,14 @@ def _score_reference(outs, truth, ids_of):
 def test_the_score_on_lane_ids_equals_its_reference_and_switches_no_more_often():
     F, P, obs, noise = _setup()
     plain = _stream(F, P, **SMC)
-    truth = _make_truth(_run(plain, obs, noise))
+    truth = _make_truth(run(plain, obs, noise))
     plain.close()
     sc = dict(score=True, score_iou=0.5, score_truth=G, **SMC, **IDENT_OPEN)
     row, lane = _stream(F, P, score_ids="row", **sc), _stream(F, P, score_ids="lane", **sc)
-    a, b = _run(row, obs, noise, truth=truth), _run(lane, obs, noise, truth=truth)
+    a, b = run(row, obs, noise, truth=truth), run(lane, obs, noise, truth=truth)
     assert lane.core.graph_nodes() == row.core.graph_nodes()                   # the same launches: only a pointer differs
     for x, y in zip(a, b):
-        _same_bits(x["lane"], y["lane"], EST_KEYS | ID_KEYS, "score_ids")
+        same_bits(x["lane"], y["lane"], EST_KEYS | ID_KEYS, "score_ids")
     counts_row, _ = _score_reference(a, truth, lambda l: l["obj_id"])
     counts_lane, last = _score_reference(b, truth, lambda l: l["lane_id"].view(np.float32))   # (the score takes the id as a 32-bit word)
     got_row, got_lane = row.score(), lane.score()

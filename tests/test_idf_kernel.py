@@ -20,7 +20,7 @@ from tests import idf_cases as IC
 from tests import idf_ref as R
 from tests import score_ref as SR
 from tests.abi_host import open_handle
-from tests.test_idf_solve_kernel import record, run_solve, struct, to_device
+from tests.idf_cases import record, run_solve, struct, to_device
 
 pytestmark = pytest.mark.gpu
 

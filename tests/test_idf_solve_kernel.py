@@ -6,44 +6,20 @@ exactly: IDTP and all twelve figures equal the reference's; ``assign`` is one-to
 IDTP -- it is not compared element-wise, because optimal assignments tie.  Also: ``close`` on a subset of the lanes frees those and
 only those, totals after two closes are the sum, ``open`` and ``assign`` are optional.  No tolerance is involved.  With
 SQAIR_PARITY_DIR set the cases are recorded in idf_parity.json there."""
-import ctypes as C
 import functools
 
 import numpy as np
 import pytest
-import torch
 
-from sqair_amd import _capi
 from tests import idf_ref as R
-from tests.abi_host import open_handle
-from tests.kernel_unit import merge_parity
+from tests.abi_host import LANE_LIBS as LIBS
+from tests.idf_cases import record, run_solve, to_device
 
 pytestmark = pytest.mark.gpu
 
 B = 256
 SHAPES = [(1, 1), (4, 8), (5, 6), (16, 64), (16, 4), (3, 64), (7, 33)]
 REGIMES = ("ties_0_3", "up_to_2^20", "mostly_zero", "all_zero", "permuted_diagonal", "free_columns")
-LIBS = {"product": None, "wide": _capi.WIDE_LIB_PATH}
-NOTE = ("per case of tests/test_idf_solve_kernel.py (solve) and tests/test_idf_kernel.py (accumulate): the lanes compared, the "
-        "lanes left out as fragile and the events counted; every compared word is an integer and is compared exactly")
-
-
-def record(section, case, **figures):
-    """One case's figures into idf_parity.json under SQAIR_PARITY_DIR (tests/test_idf_kernel.py writes the same file)."""
-    def update(data):
-        data["build_id"] = _capi.build_id()
-        data["device"] = torch.cuda.get_device_name(0)
-        data[section][case] = figures
-    merge_parity("idf_parity.json", lambda: {"note": NOTE, "solve": {}, "accumulate": {}}, update)
-
-
-_handles = {}
-
-
-def handle(lib_name):
-    if lib_name not in _handles:
-        _handles[lib_name] = open_handle(LIBS[lib_name], k_particles=2, n_steps_per_image=4, n_what=6)
-    return _handles[lib_name]
 
 
 @functools.lru_cache(maxsize=None)
@@ -77,29 +53,6 @@ def make_tables(G, P):
     for a in t.values():
         a.setflags(write=False)
     return t
-
-
-def to_device(t):
-    return {n: torch.from_numpy(np.array(v)).cuda() for n, v in t.items()}
-
-
-def struct(d, P):
-    return _capi.SqairLaneIdf(P=P, **{n: d[n].data_ptr() for n in _capi.IDF_TABLE + ("totals",)})
-
-
-def run_solve(lib_name, d, G, P, close=None, want_open=True, want_assign=True):
-    """One launch on the device table ``d`` (updated in place); returns (open, assign) as arrays or None."""
-    lib, h = handle(lib_name)
-    n = d["col_id"].shape[0]
-    open_ = torch.full((n, len(R.TOTALS)), -7, dtype=torch.int64, device="cuda") if want_open else None
-    assign = torch.full((n, G), -7, dtype=torch.int32, device="cuda") if want_assign else None
-    mask = None if close is None else torch.from_numpy(np.asarray(close, np.int32)).cuda()
-    ptr = lambda t: None if t is None else t.data_ptr()
-    rc = lib.sqair_lane_idf_solve(h, C.byref(struct(d, P)), G, n, ptr(mask), ptr(open_), ptr(assign),
-                                  C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0, lib.sqair_last_error(h)
-    torch.cuda.synchronize()
-    return (None if open_ is None else open_.cpu().numpy()), (None if assign is None else assign.cpu().numpy())
 
 
 def same_table(d, t):

@@ -1,7 +1,7 @@
 """-m gpu: IDF1 scoring inside the streaming pass (include/sqair_hip.h: sqair_set_idf; SqairStream(estimate=True, score=True,
 score_idf=True)): B = 4, K = 5, N = 3, 50 x 50, SMC, identity=True, 24 frames.
 
-The truth is cut from an unscored run's lane boxes the way tests/test_score_stream.py makes its truth (jittered, rotated between the
+The truth is cut from an unscored run's lane boxes the way tests/test_score_stream.py makes its truth (tests/stream_harness.py: make_truth) (jittered, rotated between the
 slots every four frames, a fifth dropped, some added).  Checked here: ``idf_score()`` equals the reference (tests/idf_ref.py) fed the
 steps' own lane outputs -- boxes, presences, id words, map_count and the score's truth_match --, every integer exactly; no frame of
 these runs has a pair within the fp32 error of the threshold (asserted), so nothing is left out; with ``score_idf`` on nothing else
@@ -13,36 +13,23 @@ import numpy as np
 import pytest
 import torch
 
-from sqair_amd import _capi
-from sqair_amd.data import make_sequences, to_float
-from sqair_amd.flags import make_flags
-from sqair_amd.model import SqairCore
-from sqair_amd.stream import SqairStream
 from tests import idf_ref as R
-from tests import score_ref as SR
-from tests.hip_util import draw_noise, params32
-from tests.test_score_stream import B, G, HW, IOU, N, OUTS, SMC_OUTS, _host, _make_truth, _same_bits
+from tests.stream_harness import IDF_IDS as P_IDS, OUTS, SCORE, SMC_OUTS, IdfRef, host, same_bits, setup, stream, unscored_truth
 
 pytestmark = pytest.mark.gpu
 
+HW, B, G, N, IOU = SCORE.HW, SCORE.B, SCORE.G, SCORE.N, SCORE.IOU
 FLAGS = dict(k_particles=5, n_steps_per_image=N)
-P_IDS = 6
 T = 24
 SMC = dict(resample="systematic", ess_frac=0.5, seed=5)
 
 
 def _setup(seed=11):
-    F = make_flags(**FLAGS)
-    obs = to_float(make_sequences(B, T=T, canvas=HW, seed=seed)["imgs"])
-    P = params32(F, HW, 3, 0.05, obs.mean((0, 1)))
-    noise = draw_noise(np.random.default_rng(seed + 1), T, B * int(F.k_particles), int(F.n_steps_per_image), 4 + int(F.n_what) + 1)
-    return F, P, obs, noise
+    return setup(FLAGS, B, T, HW, seed)
 
 
 def _stream(F, P, **kw):
-    core = SqairCore(F, HW)
-    core.set_params(P)
-    return SqairStream(core, B, outputs=OUTS, estimate=True, estimate_iou=IOU, identity=True, **dict(SMC, **kw))
+    return stream((F, HW, P), B, outputs=OUTS, estimate=True, estimate_iou=IOU, identity=True, **dict(SMC, **kw))
 
 
 def _scored(F, P, idf=True, **kw):
@@ -50,65 +37,14 @@ def _scored(F, P, idf=True, **kw):
 
 
 def _truth(F, P, obs, noise, Ts=1, observed=None, **kw):
-    st = _stream(F, P, frames_per_step=Ts, **kw)
-    outs = [_host(st.step(obs[s * Ts:(s + 1) * Ts], noise=noise[s * Ts:(s + 1) * Ts],
-                          **({} if observed is None else dict(observed=observed[s * Ts:(s + 1) * Ts]))))
-            for s in range(T // Ts)]
-    st.close()
-    return _make_truth(outs, Ts)
-
-
-class _Ref(object):
-    """The reference carried along a stream: the table, fed every step's own lane outputs."""
-
-    def __init__(self, ids="obj_id"):
-        self.table, self.ids = R.new_table(B, G, P_IDS), ids
-
-    def step(self, o, truth):
-        lane = o["lane"]
-        words = SR.words(lane["obj_id"]) if self.ids == "obj_id" else lane["lane_id"]
-        near = 4.0 * SR.iou32_error(truth["box"] * (truth["present"] != 0)[..., None], lane["box"])
-        first = R.fragile_from(SR.iou_table(truth["box"], lane["box"]), lane["presence"], lane["map_count"], truth["present"], truth["valid"],
-                               IOU, near)
-        assert near < 1e-5 and (first == lane["map_count"].shape[0]).all(), "a pair within the fp32 error of the threshold"
-        self.table = R.accumulate(self.table, lane["box"], lane["presence"], words, lane["map_count"], truth["box"], truth["present"],
-                                  truth["valid"], lane["truth_match"], IOU)
-
-    def close(self, lanes):
-        mask = np.zeros(B, np.int32)
-        mask[lanes] = 1
-        self.table, _ = R.solve(self.table, close=mask)
-
-    def check_table(self, st):
-        used = self.table["col_id"] >= 0
-        for n in _capi.IDF_TABLE + ("totals",):
-            got, want = st._idf[n].cpu().numpy(), self.table[n]
-            if n == "overlap":      # (the words of a free column are never read)
-                got, want = np.where(used[:, None, :], got, 0), np.where(used[:, None, :], want, 0)
-            if n == "col_frames":
-                got, want = np.where(used, got, 0), np.where(used, want, 0)
-            assert np.array_equal(got, want), (n, got, want)
-
-    def check_score(self, got):
-        _, open_ = R.solve(self.table)
-        per_lane = self.table["totals"] + open_
-        for i, n in enumerate(R.TOTALS):
-            key = "frag_per_lane" if n == "frag" else n
-            assert got[key].dtype == torch.int64 and np.array_equal(got[key].numpy(), per_lane[:, i]), (n, got[key], per_lane[:, i])
-        idtp = R.TOTALS.index("idtp")
-        assert got["assign"].dtype == torch.int32
-        for b in range(B):
-            R.check_assign(self.table, b, got["assign"][b].numpy(), int(open_[b, idtp]))
-        for n, v in R.pooled(per_lane).items():
-            assert got[n] == v or (np.isnan(got[n]) and np.isnan(v)), (n, got[n], v)
-        return dict(zip(R.TOTALS, per_lane.sum(0).tolist()))
+    return unscored_truth(_stream(F, P, frames_per_step=Ts, **kw), obs, noise, Ts, observed)[0]
 
 
 def test_idf_changes_nothing_else_and_equals_the_reference():
     F, P, obs, noise = _setup()
     truth = _truth(F, P, obs, noise)
     off, on, eager = _scored(F, P, idf=False), _scored(F, P), _scored(F, P, use_graph=False)
-    ref = _Ref()
+    ref = IdfRef()
     with pytest.raises(ValueError, match="keeps no IDF1 table"):
         off.idf_score()
     for t in range(T):
@@ -124,11 +60,11 @@ def test_idf_changes_nothing_else_and_equals_the_reference():
             assert (after["col_id"][1] == -1).all() and int(after["frames"][1]) == 0 and not after["row_frames"][1].any()
             assert int(after["totals"][1, 0]) == 1 and int(after["totals"][1, 1]) == int(before["frames"][1]) > 0
             ref.check_table(on)
-        o, b, c = (_host(s.step(obs[f], noise=noise[f], truth=truth[t])) for s in (off, on, eager))
+        o, b, c = (host(s.step(obs[f], noise=noise[f], truth=truth[t])) for s in (off, on, eager))
         assert set(o["lane"]) == set(b["lane"])      # nothing per frame: IDF1 is not a per-frame quantity
-        _same_bits(o, b, OUTS + SMC_OUTS, t)
-        _same_bits(o["lane"], b["lane"], o["lane"].keys(), t)
-        _same_bits(b["lane"], c["lane"], b["lane"].keys(), (t, "eager"))
+        same_bits(o, b, OUTS + SMC_OUTS, t)
+        same_bits(o["lane"], b["lane"], o["lane"].keys(), t)
+        same_bits(b["lane"], c["lane"], b["lane"].keys(), (t, "eager"))
         for k in ("state", "log_weight_sum", "log_z", "log_evidence", "ess", "u", "resampled", "_src"):
             assert torch.equal(getattr(off, k), getattr(on, k)), (t, k)
         ref.step(b, truth[t])
@@ -162,11 +98,11 @@ def test_three_frames_per_step_a_coasted_lane_and_the_table_keyed_by_lane_id(ids
     observed = np.stack([np.ones(B, bool) if t < 3 else rng.uniform(size=B) < 0.7 for t in range(T)])
     truth = _truth(F, P, obs, noise, Ts=3, observed=observed, missing=True)
     st = _scored(F, P, frames_per_step=3, missing=True, score_ids=ids)
-    ref = _Ref("lane_id" if ids == "lane" else "obj_id")
+    ref = IdfRef("lane_id" if ids == "lane" else "obj_id")
     coasted = 0
     for s in range(T // 3):
         f = slice(3 * s, 3 * s + 3)
-        o = _host(st.step(obs[f], noise=noise[f], truth=truth[s], observed=observed[f]))
+        o = host(st.step(obs[f], noise=noise[f], truth=truth[s], observed=observed[f]))
         ref.step(o, truth[s])
         coasted += int((~observed[f] & (truth[s]["valid"] != 0) & (o["lane"]["tp"] >= 0)).sum())
     ref.check_table(st)

@@ -191,10 +191,10 @@ def _show(case, what, dist, bar):
 @functools.lru_cache(maxsize=None)
 def _forward(case):
     from tests.hip_util import run_oracle
-    from tests.test_hip_forward import _live_oracle_inputs
+    from tests.pass_cases import live_oracle_inputs
     K, N, T, B, hw, flags, edits, need = LR.FORWARD[case]
     F = make_flags(k_particles=K, n_steps_per_image=N, **flags)
-    x = _live_oracle_inputs(F, hw, T, B, edits=edits)      # (fails if no decision-stable draw within MAX_DRAWS)
+    x = live_oracle_inputs(F, hw, T, B, edits=edits)      # (fails if no decision-stable draw within MAX_DRAWS)
     r32 = run_oracle(F, hw, x["P"], x["obs"], x["noise"], nums=x["d"]["nums"], dtype=torch.float32)
     return F, x, r32
 
@@ -218,8 +218,8 @@ def test_forward_case_reaches_its_regime_and_is_conditioned(case):
 
 @functools.lru_cache(maxsize=None)
 def _backward(edits, flags_items):
-    from tests.test_hip_backward import _full_backward_inputs
-    F, obs, P, noise, ref, orc = _full_backward_inputs(3, 3, 3, 3, LR.BWD_HW, LR.BWD_SEED, dict(flags_items), edits,
+    from tests.pass_cases import full_backward_inputs
+    F, obs, P, noise, ref, orc = full_backward_inputs(3, 3, 3, 3, LR.BWD_HW, LR.BWD_SEED, dict(flags_items), edits,
                                                        seed0=LR.bwd_noise_seed0(edits))
     orc.make_target(ref).backward()
     o32 = O.SqairOracle(P, O.make_cfg(F, LR.BWD_HW), torch.float32, requires_grad=True)
@@ -287,10 +287,10 @@ def test_the_clamps_own_gradient_path_is_zero_at_the_bars_resolution(monkeypatch
 
 def test_stream_case_reaches_its_regime_and_is_conditioned():
     from tests.hip_util import run_oracle
-    from tests.test_hip_forward import _live_oracle_inputs
+    from tests.pass_cases import live_oracle_inputs
     c = LR.STREAM
     F = make_flags(k_particles=c["K"], n_steps_per_image=c["N"])
-    x = _live_oracle_inputs(F, c["hw"], c["T"], c["B"], edits=c["edits"])
+    x = live_oracle_inputs(F, c["hw"], c["T"], c["B"], edits=c["edits"])
     counts = LR.counts_of(x["ref"].outputs, O.make_cfg(F, c["hw"]))
     print(LR.table(counts))
     LR.require(counts, **c["minimums"])
@@ -302,13 +302,14 @@ def test_stream_case_reaches_its_regime_and_is_conditioned():
 
 
 def test_stream_training_case_reaches_its_regime_and_is_conditioned():
-    """The oracle side of `_chunk_two_case` (tests/test_stream_train.py) without SMC: the same frames, the same generator, so the
+    """The oracle side of `chunk_two_case` (tests/stream_cases.py, the case of tests/test_stream_train.py) without SMC: the same frames, the same generator, so the
     same two noise draws; chunk 2 from the carried state with the last lane reset."""
     from tests import tbptt_ref as TR
-    from tests.test_stream_train import HW, _setup, _stable
+    from tests.stream_cases import ORACLE_HW as HW, stable_chunk as _stable
+    from tests.stream_harness import train_setup
     c = LR.STREAM_TRAIN
     B, T = 3, 3
-    F, obs, P = _setup(c["flags"], B, 2 * T, seed=23, edits=c["edits"])
+    F, obs, P = train_setup(c["flags"], B, 2 * T, HW, 23, edits=c["edits"])
     K = int(F.k_particles)
     R = B * K
     cfg = O.make_cfg(F, HW)
@@ -346,7 +347,7 @@ def test_particle_filter_case_reaches_saturated_logits_at_every_step():
     from sqair_amd.data import make_sequences, to_float
     from tests import smc_ref as S
     from tests.hip_util import MARGIN, draw_noise, params32, presence_margins
-    from tests.test_smc_oracle import DRAWS, HW
+    from tests.stream_cases import DRAWS, ORACLE_HW as HW
     c = LR.SMC
     F = make_flags(**c["flags"])
     B, TS, K, N = c["B"], c["frames_per_step"], int(F.k_particles), int(F.n_steps_per_image)
@@ -379,7 +380,8 @@ def test_forecast_case_reaches_the_floored_prior():
     """The forecast reference on its own sampled latents: with `floored_prior` every prior of a present object has both scales at
     the floor and a saturated presence logit, and the rollout stays decision-stable."""
     from tests.hip_util import params32
-    from tests.test_forecast import _frames, _reference_rollout
+    from tests.stream_cases import reference_rollout as _reference_rollout
+    from tests.stream_harness import frames as _frames
     c = LR.FORECAST
     F = make_flags(**c["flags"])
     obs = _frames(c["hw"], c["B"], c["S"], 19)

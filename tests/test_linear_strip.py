@@ -26,8 +26,7 @@ import torch
 from oracle import sqair_oracle as O
 from sqair_amd import _capi
 from tests.hip_util import dev as _dev, stream
-from tests.kernel_unit import bits as _bits
-from tests.test_dense_contract import _Fwd, _run_fwd, _segments, _took, handle  # noqa: F401  (handle: the module's fixture)
+from tests.kernel_unit import Fwd, bits as _bits, dense_handle as handle, run_fwd, segments as _segments, took  # noqa: F401  (handle: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -49,12 +48,12 @@ CONTRACT = [
 
 @pytest.mark.parametrize("M,kc,nseg,N", CONTRACT)
 def test_strip_contract(handle, M, kc, nseg, N):
-    L = _Fwd(3000 + 7 * kc + M, M, _segments(kc, nseg), N)
+    L = Fwd(3000 + 7 * kc + M, M, _segments(kc, nseg), N)
     assert L.kc == kc and len(L.segs) == nseg and ((M + 15) // 16) * L.nt > 256
     case = "fwd strip M={} kc={} nseg={} N={}".format(M, kc, nseg, N)
     ref = L.reference(True, M)
-    _run_fwd(handle, case + " rich out_ld=N+4", L, True, M, 4, "fwd_strip", ref)
-    _run_fwd(handle, case + " rich out_ld=N+1", L, True, M, 1, "fwd_strip", ref)
+    run_fwd(handle, case + " rich out_ld=N+4", L, True, M, 4, "fwd_strip", ref)
+    run_fwd(handle, case + " rich out_ld=N+1", L, True, M, 1, "fwd_strip", ref)
 
 
 def test_strip_leaves_the_gru(handle):
@@ -78,7 +77,7 @@ def test_strip_leaves_the_gru(handle):
     rc = lib.sqair_gru_test(h, dx.data_ptr(), dh.data_ptr(), df.data_ptr(), out.data_ptr(), M, Kx, scratch.data_ptr(),
                             scratch.numel() * 4, stream())
     assert rc == 0, lib.sqair_last_error(h)
-    assert _took(before) == {"fwd_splitk": 2}, _took(before)
+    assert took(before) == {"fwd_splitk": 2}, took(before)
     P64 = {k: torch.tensor(v, dtype=torch.float64) for k, v in P.items()}
     ref = O.gru(P64, "g", torch.tensor(x, dtype=torch.float64), torch.tensor(hs, dtype=torch.float64))
     assert float(np.abs(out.cpu().numpy() - ref.numpy()).max()) < 2e-5
@@ -86,9 +85,9 @@ def test_strip_leaves_the_gru(handle):
 
 @pytest.mark.parametrize("kc,nseg,N", [(23, 3, 1152), (25, 2, 900)])
 def test_strip_does_not_change_a_bit(handle, kc, nseg, N):
-    L = _Fwd(5000 + kc, 640, _segments(kc, nseg), N)
+    L = Fwd(5000 + kc, 640, _segments(kc, nseg), N)
     assert L.kc == kc
-    y_strip = _run_fwd(handle, "bits kc={} N={} M=640".format(kc, N), L, True, 640, 4, "fwd_strip")
-    y_split = _run_fwd(handle, "bits kc={} N={} M=496".format(kc, N), L, True, 496, 4, "fwd_splitk")
+    y_strip = run_fwd(handle, "bits kc={} N={} M=640".format(kc, N), L, True, 640, 4, "fwd_strip")
+    y_split = run_fwd(handle, "bits kc={} N={} M=496".format(kc, N), L, True, 496, 4, "fwd_splitk")
     differ = _bits(y_strip[:496]) != _bits(y_split)
     assert not differ.any(), "{} of {} outputs differ between fwd_strip and fwd_splitk".format(int(differ.sum()), differ.size)

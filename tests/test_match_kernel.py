@@ -31,8 +31,8 @@ from tests import match_ref as M
 from tests import score_ref as R
 from tests import traj_score_ref as TR
 from tests.abi_host import open_handle
-from tests.test_idf_solve_kernel import struct as idf_struct, to_device as idf_to_device
-from tests.test_match_ref import record
+from tests.idf_cases import struct as idf_struct, to_device as idf_to_device
+from tests.match_ref import record
 
 pytestmark = pytest.mark.gpu
 

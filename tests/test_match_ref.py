@@ -5,9 +5,6 @@ G, N >= 2 greedy and optimal differ in at least one scored frame in ten (a case 
 most 1 % of the lanes are left out for a candidate IoU within 1e-5 of iou_min.  Also measured here: e, the largest error of an fp32
 restatement of sq_box_iou on these inputs in units of 2^-20, which the GPU test's slack on the sum of q is made of.  With
 SQAIR_PARITY_DIR set the figures are added to match_parity.json there (the copy under profiles/ is such a file)."""
-import json
-import os
-
 import numpy as np
 import pytest
 
@@ -17,23 +14,7 @@ from tests import match_ref as M
 from tests import score_ref as R
 from tests import traj_score_ref as TR
 
-PARITY_DIR_ENV = "SQAIR_PARITY_DIR"
 IDS = [MC.case_id(c) for c in MC.CASES]
-
-
-def record(section, case, **figures):
-    """Adds ``figures`` to match_parity.json under SQAIR_PARITY_DIR (nothing without it)."""
-    where = os.environ.get(PARITY_DIR_ENV)
-    if not where:
-        return
-    path = os.path.join(where, "match_parity.json")
-    try:
-        os.makedirs(where, exist_ok=True)
-        data = json.load(open(path)) if os.path.exists(path) else {}
-        data.setdefault(section, {}).setdefault(case, {}).update(figures)
-        json.dump(data, open(path, "w"), indent=1, sort_keys=True)
-    except OSError:
-        pass
 
 
 @pytest.mark.parametrize("G", range(1, 6))
@@ -140,7 +121,7 @@ def test_the_cases_tell_the_modes_apart_and_leave_few_lanes_out(i):
     tot = lambda s: dict(zip(R.COUNTS, s.counts.sum(0).tolist()))
     print(MC.case_id(c), "scored frames", int(on.sum()), "greedy and optimal differ in {:.3f} (tp {:.3f}, sum of IoU {:.3f})".format(
         differ, differ_tp, differ_sum), "left out", left_out, "e = {:.3f} x 2^-20".format(e), "tp", tot(grd)["tp"], "->", tot(opt)["tp"])
-    record("cases", MC.case_id(c), scored_frames=int(on.sum()), differ=float(differ), differ_tp=float(differ_tp),
+    M.record("cases", MC.case_id(c), scored_frames=int(on.sum()), differ=float(differ), differ_tp=float(differ_tp),
            differ_iou_sum=float(differ_sum), left_out=left_out, lanes=MC.B, e_units_of_2_pow_minus_20=float(e), greedy=tot(grd),
            optimal=tot(opt))
     assert left_out <= MC.FRAGILE_CAP * MC.B

@@ -1,7 +1,7 @@
 """-m gpu: keep + optimal per-frame matching from the stream (SqairStream(score_match=..., identity_match=...), forecast(link_match=...);
 include/sqair_hip.h: sqair_set_lane_match): B = 4, K = 5, N = 3, 50 x 50, SMC, 30 frames.
 
-The truth is cut from an unscored run's lane boxes the way tests/test_score_stream.py makes its truth, with coarser jitter and two
+The truth is cut from an unscored run's lane boxes the way tests/test_score_stream.py makes its truth (tests/stream_harness.py: make_truth), with coarser jitter and two
 truths on the lane's first object, so that truths compete.  Isolation: with ``score_match="optimal"`` every output other than the
 score's (and the IDF table, which reads truth_match) is bit-identical to the greedy stream's and the graph has the same number of
 nodes; with ``identity_match="optimal"`` the same holds for everything but the identity's outputs and table (the score reads obj_id
@@ -14,56 +14,43 @@ import pytest
 import torch
 
 from sqair_amd import _capi
-from sqair_amd.data import make_sequences, to_float
-from sqair_amd.flags import make_flags
-from sqair_amd.model import SqairCore
-from sqair_amd.stream import SqairStream
 from tests import identity_ref as I
 from tests import match_ref as M
 from tests import score_ref as R
 from tests import traj_score_ref as TR
-from tests.hip_util import draw_noise, params32
-from tests.test_idf_stream import P_IDS, _Ref as IdfRef
-from tests.test_score_stream import B, G, HW, IOU, N, OUTS, SMC_OUTS, SCORE_KEYS, _host, _same_bits
-from tests.test_traj_score_stream import _host as _host_deep, _same_bits as _same_deep
+from tests.stream_harness import IDF_IDS as P_IDS, OUTS, SCORE, SMC_OUTS, IdfRef, host, same_bits, setup, stream, unscored_truth
 
 pytestmark = pytest.mark.gpu
 
+HW, B, G, N, IOU = SCORE.HW, SCORE.B, SCORE.G, SCORE.N, SCORE.IOU
 FLAGS = dict(k_particles=5, n_steps_per_image=N)
 T = 30
 SMC = dict(resample="systematic", ess_frac=0.5, seed=5)
+SCORE_KEYS = set(_capi.SCORE_FIELDS)
 IDENT_KEYS = {"lane_id", "id_how", "track_len"}
 JITTER = np.array([3.0, 3.0, 1.5, 1.5])      # px, on (y, x, h, w)
 STATE = ("state", "log_weight_sum", "log_z", "log_evidence", "ess", "u", "resampled", "_src")
 
 
 def _setup(seed=11):
-    F = make_flags(**FLAGS)
-    obs = to_float(make_sequences(B, T=T, canvas=HW, seed=seed)["imgs"])
-    P = params32(F, HW, 3, 0.05, obs.mean((0, 1)))
-    noise = draw_noise(np.random.default_rng(seed + 1), T, B * int(F.k_particles), int(F.n_steps_per_image), 4 + int(F.n_what) + 1)
-    return F, P, obs, noise
+    return setup(FLAGS, B, T, HW, seed)
 
 
 def _stream(F, P, **kw):
-    core = SqairCore(F, HW)
-    core.set_params(P)
-    return SqairStream(core, B, outputs=OUTS, estimate=True, estimate_iou=IOU, identity=True, **dict(SMC, **kw))
+    return stream((F, HW, P), B, outputs=OUTS, estimate=True, estimate_iou=IOU, identity=True, **dict(SMC, **kw))
 
 
 def _scored(F, P, **kw):
     return _stream(F, P, score=True, score_iou=IOU, score_truth=G, score_idf=True, score_idf_ids=P_IDS, **kw)
 
 
-def _truth(F, P, obs, noise, Ts=1, seed=7):
+def _cut(outs, Ts, seed=7):
     """One ``truth`` dict per step from an unscored run's lane boxes: truth g = (j + shift) % N is object j's box moved by 3 px and
     resized by 1.5 px of jitter, present four times in five; truth N is a second truth on object 0, present half of the time."""
-    st = _stream(F, P, frames_per_step=Ts)
     rng = np.random.default_rng(seed)
     truth = []
-    for s in range(T // Ts):
-        f = slice(s * Ts, (s + 1) * Ts)
-        lane = _host(st.step(obs[f], noise=noise[f]))["lane"]
+    for s, o in enumerate(outs):
+        lane = o["lane"]
         box, present = np.zeros((Ts, B, G, 4), np.float32), np.zeros((Ts, B, G), np.int32)
         for k in range(Ts):
             shift = ((s * Ts + k) // 4) % 2
@@ -76,8 +63,11 @@ def _truth(F, P, obs, noise, Ts=1, seed=7):
                 present[k, b, N] = lane["presence"][k, b, 0] != 0 and rng.uniform() < 0.5
         box[..., 2:] = np.maximum(box[..., 2:], 4.0)                       # (a box stays a box)
         truth.append(dict(box=box, present=present, valid=(rng.uniform(size=(Ts, B)) < 0.9).astype(np.int32)))
-    st.close()
     return truth
+
+
+def _truth(F, P, obs, noise, Ts=1):
+    return unscored_truth(_stream(F, P, frames_per_step=Ts), obs, noise, Ts, cut=_cut)[0]
 
 
 class _ScoreRef(object):
@@ -121,12 +111,12 @@ def test_score_match_changes_only_the_score_and_equals_the_reference():
     differ = more = 0
     for t in range(T):
         f = slice(t, t + 1)
-        o, b, c = (_host(s.step(obs[f], noise=noise[f], truth=truth[t])) for s in (grd, opt, eager))
+        o, b, c = (host(s.step(obs[f], noise=noise[f], truth=truth[t])) for s in (grd, opt, eager))
         others = set(o["lane"]) - SCORE_KEYS
         assert set(o["lane"]) == set(b["lane"]) and IDENT_KEYS <= others
-        _same_bits(o, b, OUTS + SMC_OUTS, t)
-        _same_bits(o["lane"], b["lane"], others, t)                        # the estimate's and the identity's outputs: untouched
-        _same_bits(b["lane"], c["lane"], b["lane"].keys(), (t, "eager"))   # eager and graph: the same bits
+        same_bits(o, b, OUTS + SMC_OUTS, t)
+        same_bits(o["lane"], b["lane"], others, t)                        # the estimate's and the identity's outputs: untouched
+        same_bits(b["lane"], c["lane"], b["lane"].keys(), (t, "eager"))   # eager and graph: the same bits
         for k in STATE:
             assert torch.equal(getattr(grd, k), getattr(opt, k)), (t, k)
         ref.step(b, truth[t])
@@ -159,10 +149,10 @@ def test_identity_match_changes_only_the_identity_and_equals_the_reference():
     outs = []
     for t in range(T):
         f = slice(t, t + 1)
-        o, b, c = (_host(s.step(obs[f], noise=noise[f], truth=truth[t])) for s in (grd, opt, eager))
-        _same_bits(o, b, OUTS + SMC_OUTS, t)
-        _same_bits(o["lane"], b["lane"], set(o["lane"]) - IDENT_KEYS, t)   # the score reads obj_id: it is untouched too
-        _same_bits(b["lane"], c["lane"], b["lane"].keys(), (t, "eager"))
+        o, b, c = (host(s.step(obs[f], noise=noise[f], truth=truth[t])) for s in (grd, opt, eager))
+        same_bits(o, b, OUTS + SMC_OUTS, t)
+        same_bits(o["lane"], b["lane"], set(o["lane"]) - IDENT_KEYS, t)   # the score reads obj_id: it is untouched too
+        same_bits(b["lane"], c["lane"], b["lane"].keys(), (t, "eager"))
         for k in STATE:
             assert torch.equal(getattr(grd, k), getattr(opt, k)), (t, k)
         outs.append(b["lane"])
@@ -204,9 +194,9 @@ def test_three_frames_per_step_graph_equals_eager_in_both_modes():
     ref = _ScoreRef()
     for s in range(T // 3):
         f = slice(3 * s, 3 * s + 3)
-        o, b, c = (_host(st.step(obs[f], noise=noise[f], truth=truth[s])) for st in (grd, opt, eager))
-        _same_bits(o, b, OUTS + SMC_OUTS, s)
-        _same_bits(b["lane"], c["lane"], b["lane"].keys(), (s, "eager"))
+        o, b, c = (host(st.step(obs[f], noise=noise[f], truth=truth[s])) for st in (grd, opt, eager))
+        same_bits(o, b, OUTS + SMC_OUTS, s)
+        same_bits(b["lane"], c["lane"], b["lane"].keys(), (s, "eager"))
         # (the identity's mode does not reach the score here: score_ids="row")
         ref.step(b, truth[s])
     assert opt.core.graph_nodes() == grd.core.graph_nodes()
@@ -225,7 +215,7 @@ def test_the_forecast_links_by_keep_and_optimal():
     for t in range(6):
         st.step(obs[t:t + 1], noise=noise[t:t + 1])
     FH, S = 3, 2
-    call = lambda **kw: _host_deep(st.forecast(FH, samples=S, lane=True, seed=3, **kw))
+    call = lambda **kw: host(st.forecast(FH, samples=S, lane=True, seed=3, **kw))
     lane = call()["lane"]
     rng = np.random.default_rng(3)
     a_box, a_present = np.zeros((B, G, 4), np.float32), np.zeros((B, G), np.int32)
@@ -237,7 +227,7 @@ def test_the_forecast_links_by_keep_and_optimal():
                  anchor_box=a_box, anchor_present=a_present)
     grd, opt = call(truth=truth), call(truth=truth, link_match="optimal")
     s_grd, s_opt = grd["lane"].pop("score"), opt["lane"].pop("score")
-    _same_deep(grd, opt, "forecast.")                                      # everything but the score: the same bits
+    same_bits(grd, opt, where="forecast.")                                      # everything but the score: the same bits
     tab = {n: lane[n] for n in _capi.TRAJ_TABLE_FIELDS if n in lane}
     tr = dict(anchor_box=a_box, anchor_present=a_present, anchor_valid=np.ones(B, np.int32), truth_box=truth["box"],
               truth_present=truth["present"], truth_valid=np.ones((FH, B), np.int32))

@@ -14,14 +14,13 @@ import torch
 
 from oracle import sqair_oracle as O
 from sqair_amd import _capi
-from sqair_amd.data import make_sequences, to_float
-from sqair_amd.flags import make_flags
 from sqair_amd.model import SqairCore
 from sqair_amd.stream import FORECAST_OUTPUTS, SqairStream
 from tests import history_ref as H
 from tests import smc_ref as S
 from tests.coast_ref import COASTED, COUNTS, coast_ref
-from tests.hip_util import MARGIN, draw_noise, params32
+from tests.hip_util import MARGIN, draw_noise
+from tests.stream_harness import core as make_core, host, scaled as _scaled, setup
 
 pytestmark = pytest.mark.gpu
 
@@ -58,26 +57,9 @@ def pattern(frames, B):
     return m
 
 
-def _scaled(got, want):
-    got = np.asarray(got, np.float64).reshape(want.shape)
-    return float(np.abs(got - want).max() / max(1.0, float(np.abs(want).max())))
-
-
-def _host(d):
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in d.items()}
-
-
 def _setup(flags, B, frames=T, seed=19, hw=HW, options=None, cores=1):
-    F = make_flags(**flags)
-    obs = to_float(make_sequences(B, T=frames, canvas=hw, seed=seed)["imgs"])
-    P = params32(F, hw, 3, 0.05, obs.mean((0, 1)))
-    made = []
-    for _ in range(cores):
-        core = SqairCore(F, hw, options=options)
-        core.set_params(P)
-        made.append(core)
-    return F, P, obs, made
+    F, P, obs, _ = setup(flags, B, frames, hw, seed)
+    return F, P, obs, [make_core(F, hw, P, options) for _ in range(cores)]
 
 
 def _dims(F, B):
@@ -141,7 +123,7 @@ def test_mixed_mask_matches_the_fp64_reference(case):
     worst = {}
     for t in range(T):
         frames = obs[t:t + 1].copy()
-        got = _host(st.step(frames, noise=noise[t:t + 1], observed=mask[t]))
+        got = host(st.step(frames, noise=noise[t:t + 1], observed=mask[t]))
         assert np.array_equal(got.pop("observed"), mask[t:t + 1])
         rows = np.repeat(mask[t], K)
         for k in ALL:
@@ -176,17 +158,17 @@ def test_steps_without_any_frame_are_the_forecast(cell):
     for t in range(S_):
         sa.step(obs[t:t + 1], noise=noise[t:t + 1])
         sb.step(obs[t:t + 1], noise=noise[t:t + 1])
-    want = _host(sb.forecast(Fn + 2, noise=fnoise))
+    want = host(sb.forecast(Fn + 2, noise=fnoise))
     assert want["presence"][:Fn].sum() > 0 and want["presence"][Fn - 1].sum() < want["presence"][0].sum()   # objects, and some die
     none = np.zeros(B, bool)
     blank = np.zeros((1, B) + HW, np.float32)
     for f in range(Fn):
-        got = _host(sa.step(blank, noise=fnoise[f:f + 1], observed=none))
+        got = host(sa.step(blank, noise=fnoise[f:f + 1], observed=none))
         for k in FORECAST_OUTPUTS:
             assert np.array_equal(got[k][0], want[k][f]), (f, k)
         assert not got["log_weights_per_timestep"].any()
     # the state after the F steps: a further forecast from it continues the long one
-    more = _host(sa.forecast(2, noise=fnoise[Fn:]))
+    more = host(sa.forecast(2, noise=fnoise[Fn:]))
     for k in FORECAST_OUTPUTS + ("mean_canvas", "expected_count", "weights"):
         assert np.array_equal(more[k], want[k][Fn:] if k != "weights" else want[k]), k
     sa.close()
@@ -224,7 +206,7 @@ def test_frames_of_unobserved_lanes_do_not_matter():
         f2[0, gone] = 1.0 - f1[0, gone] * 0.5
         f3[0, gone] = float("nan")     # through Python anything goes: the stream blanks the lane
         u = rng.uniform(size=B).astype(np.float32)
-        o1, o2, o3 = (_host(s.step(f, noise=noise[t:t + 1], uniforms=u, observed=mask[t])) for s, f in ((s1, f1), (s2, f2), (s3, f3)))
+        o1, o2, o3 = (host(s.step(f, noise=noise[t:t + 1], uniforms=u, observed=mask[t])) for s, f in ((s1, f1), (s2, f2), (s3, f3)))
         for k in o1:
             assert np.array_equal(o1[k], o2[k], equal_nan=True) and np.array_equal(o1[k], o3[k], equal_nan=True), (t, k)
             assert np.isfinite(o1[k]).all(), (t, k)
@@ -241,8 +223,8 @@ def test_every_lane_observed_equals_a_stream_without_a_mask():
     kw = dict(outputs=ALL, resample="systematic", ess_frac=0.5, seed=9)
     sa, sb = SqairStream(ca, B, missing=True, **kw), SqairStream(cb, B, **kw)
     for t in range(T):
-        oa = _host(sa.step(obs[t:t + 1], observed=None if t % 2 else np.ones(B, bool)))
-        ob = _host(sb.step(obs[t:t + 1]))
+        oa = host(sa.step(obs[t:t + 1], observed=None if t % 2 else np.ones(B, bool)))
+        ob = host(sb.step(obs[t:t + 1]))
         assert oa.pop("observed").all() and "observed" not in ob
         for k in ob:
             assert np.array_equal(oa[k], ob[k], equal_nan=True), (t, k)
@@ -269,7 +251,7 @@ def test_a_coasted_step_leaves_the_lanes_weights_alone(frac):
     prev = None
     for t in range(frames):
         lw0 = st.log_weight_sum.clone()
-        o = _host(st.step(obs[t:t + 1], observed=mask[t]))
+        o = host(st.step(obs[t:t + 1], observed=mask[t]))
         lw1 = st.log_weight_sum.cpu().numpy()
         for b in np.flatnonzero(~mask[t]):
             rows = slice(b * K, (b + 1) * K)
@@ -316,7 +298,7 @@ def test_gappy_stream_matches_the_fp64_particle_filter():
         lw0_ref, lz0_ref = pf.log_w.copy(), pf.log_z.copy()
         ref, rw = pf.commit(prop)
         lw0 = st.log_weight_sum.cpu().numpy()
-        o = _host(st.step(obs[s:s + 1], noise=noise, observed=mask[s]))
+        o = host(st.step(obs[s:s + 1], noise=noise, observed=mask[s]))
         # the Philox uniform is keyed by the lane's frame counter after the step: a coasted frame is time that passed
         assert np.array_equal(st.u.cpu().numpy(), S.smc_uniform(np.arange(B), pf.state.t.numpy()[::K], 41)), s
         for k in EXACT:
@@ -366,12 +348,12 @@ def test_one_graph_serves_every_mask():
     sg, se = SqairStream(ca, B, use_graph=True, **kw), SqairStream(cb, B, use_graph=False, **kw)
     captures = _count_captures(ca)
     for t in range(frames):
-        og, oe = _host(sg.step(obs[t:t + 1], observed=mask[t])), _host(se.step(obs[t:t + 1], observed=mask[t]))
+        og, oe = host(sg.step(obs[t:t + 1], observed=mask[t])), host(se.step(obs[t:t + 1], observed=mask[t]))
         for k in oe:
             assert np.array_equal(og[k], oe[k], equal_nan=True), (t, k)
         _same_streams(sg, se, t)
     assert captures() == 1
-    tg, te = _host(sg.tracks()), _host(se.tracks())
+    tg, te = host(sg.tracks()), host(se.tracks())
     for k in te:
         assert H.same_bits(tg[k], te[k]), k
     sg.close()
@@ -412,9 +394,9 @@ def test_a_pass_of_four_frames_equals_four_steps():
     present = 0
     for c in range(2):
         fr = slice(c * TS, (c + 1) * TS)
-        o4 = _host(s4.step(obs[fr], noise=noise[fr], observed=mask[fr]))
+        o4 = host(s4.step(obs[fr], noise=noise[fr], observed=mask[fr]))
         for i, t in enumerate(range(fr.start, fr.stop)):
-            o1 = _host(s1.step(obs[t:t + 1], noise=noise[t:t + 1], observed=mask[t]))
+            o1 = host(s1.step(obs[t:t + 1], noise=noise[t:t + 1], observed=mask[t]))
             for k in ALL + ("observed",):
                 assert np.array_equal(o4[k][i], o1[k][0], equal_nan=True), (t, k)
             present += int(o1["presence"][0][np.repeat(~mask[t], K)].sum())
@@ -438,7 +420,7 @@ def test_slot_chain_equals_the_launches():
     sa, sb = SqairStream(ca, B, **kw), SqairStream(cb, B, **kw)
     present = 0
     for t in range(T):
-        oa, ob = _host(sa.step(obs[t:t + 1], observed=mask[t])), _host(sb.step(obs[t:t + 1], observed=mask[t]))
+        oa, ob = host(sa.step(obs[t:t + 1], observed=mask[t])), host(sb.step(obs[t:t + 1], observed=mask[t]))
         ca.check_chain()
         for k in ob:
             assert np.array_equal(oa[k], ob[k], equal_nan=True), (t, k)
@@ -459,10 +441,10 @@ def test_tracks_return_the_coasted_frames():
     rec, steps = H.Recorder(B * K), []
     for t in range(frames):
         parent = st.carried.pending().copy()
-        o = _host(st.step(obs[t:t + 1], observed=mask[t]))
+        o = host(st.step(obs[t:t + 1], observed=mask[t]))
         rec.push(parent, **{k: o[v] for k, v in fields.items()})
         steps.append(o)
-    got = _host(st.tracks(start="last"))
+    got = host(st.tracks(start="last"))
     want = H.trace(rec.steps, L, L, K, None, 2 * core.N)
     for k, v in want.items():
         assert got[k].dtype == v.dtype and H.same_bits(got[k], v), k

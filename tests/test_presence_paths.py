@@ -22,11 +22,9 @@ from sqair_amd.model import SqairCore
 from sqair_amd.stream import SqairStream
 from tests import presence_patterns as PP
 from tests.hip_util import run_hip, run_oracle
-from tests.test_forecast import _rollout_case
-from tests.test_hip_backward import _check_report, _full_backward_case
-from tests.test_hip_forward import _live_oracle_case, _live_oracle_inputs
-from tests.test_hip_specialised import _spec_launches
-from tests.test_stream_state import PER_FRAME, _chunked, _compare, _pass, _switches
+from tests.pass_cases import check_report, full_backward_case, live_oracle_case, live_oracle_inputs, spec_launches
+from tests.stream_cases import chunk_two_case, rollout_case
+from tests.stream_harness import OUTS, chunked, compare, history_check, history_push, host, one_pass, switches
 
 pytestmark = pytest.mark.gpu
 
@@ -71,14 +69,14 @@ def _record(section, case, **figures):
 def _forward_inputs(case):
     K, N, T, B, hw, flags, minimums = FORWARD[case]
     F = make_flags(k_particles=K, n_steps_per_image=N, **dict(VANISH, **flags))
-    x = _live_oracle_inputs(F, hw, T, B)          # (prints the pattern table)
+    x = live_oracle_inputs(F, hw, T, B)          # (prints the pattern table)
     PP.require(x["counts"], **minimums)
     return F, hw, T, B, N, x
 
 
 @pytest.mark.parametrize("case", sorted(FORWARD))
 def test_forward_where_objects_vanish(case):
-    """Every output against the fp64 oracle at `_live_oracle_case`'s bar; presence, ids and step counts exact.  Where the oracle
+    """Every output against the fp64 oracle at `live_oracle_case`'s bar; presence, ids and step counts exact.  Where the oracle
     says an object changed its slot between two frames, the HIP ids must have followed the object.
 
     K3N3T3B3_wide_n_what_64: elbo_iwae = 0.5433 is a log-mean-exp of log weights up to 660 in size, so the helper's bar (1e-4
@@ -100,7 +98,7 @@ def test_forward_where_objects_vanish(case):
         err = abs(float(m0.elbo_iwae) - float(x["ref"].elbo_iwae))
         print("{}: elbo_iwae fp32 oracle - fp64 {:.3e}, bar {:.3e}, HIP - fp64 {:.3e}".format(case, dist, bars["elbo_iwae"], err))
         _record("forward_fp32_reference", case, quantity="elbo_iwae", fp32_oracle_distance=dist, bar=bars["elbo_iwae"], hip_error=err)
-    m, ref = _live_oracle_case(F, hw=hw, T=T, B=B, inputs=x, scalar_bars=bars)
+    m, ref = live_oracle_case(F, hw=hw, T=T, B=B, inputs=x, scalar_bars=bars)
     if "n_what" in FORWARD[case][5]:
         assert m.core.lib is _capi.lib(_capi.WIDE_LIB_PATH)
     want_id = ref.obj_id.numpy().reshape(T, -1, N)
@@ -131,18 +129,18 @@ def test_executors_agree_where_objects_vanish(case):
                                                    use_graph=use_graph)
     outs = lambda m: dict({k: v.detach().cpu().numpy().copy() for k, v in m.core.out.items()},
                           log_weights=m.core.log_weights.cpu().numpy().copy())
-    n0 = _spec_launches()
+    n0 = spec_launches()
     ref = outs(run({"specialised": 0}))
-    assert _spec_launches() == n0
+    assert spec_launches() == n0
     assert np.array_equal(ref["prop_pres"], x["ref"].prop_pres.numpy()) and np.array_equal(ref["disc_pres"], x["ref"].disc_pres.numpy())
     shipped = case == "K5N4T4B2_shipped_shape"
     for name, options, use_graph in (("specialised", {"specialised": 1}, False), ("specialised, graph", {"specialised": 1}, True),
                                      ("slot_chain", {"slot_chain": 1}, False), ("slot_chain, graph", {"slot_chain": 1}, True),
                                      ("slot_chain, generic", {"slot_chain": 1, "specialised": 0}, False)):
-        n0 = _spec_launches()
+        n0 = spec_launches()
         got = outs(run(options, use_graph))
         if "slot_chain" not in options:
-            assert (_spec_launches() - n0 > 0) == shipped, name   # k_compact<true> / k_crop_row<true, .> only for the shipped shape
+            assert (spec_launches() - n0 > 0) == shipped, name   # k_compact<true> / k_crop_row<true, .> only for the shipped shape
         assert set(got) == set(ref)
         for k, v in ref.items():
             assert np.array_equal(v, got[k], equal_nan=True), (case, name, k)
@@ -161,11 +159,11 @@ BACKWARD = {
 
 @pytest.mark.parametrize("case", sorted(BACKWARD))
 def test_full_backward_where_objects_vanish(case):
-    """Every parameter's gradient against autograd through the fp64 oracle at the bars of tests/test_hip_backward.py (TIGHT /
+    """Every parameter's gradient against autograd through the fp64 oracle at the bars of tests/pass_cases.py (TIGHT /
     LOOSE, `ill_scale=True` as the other non-shipped regimes), in cases whose later frames' gradients flow back through real
     permutations (`hole_before_last`)."""
     K, N, T, B, flags, options, wide = BACKWARD[case]
-    report, ref, core = _full_backward_case(K, N, T, B, (50, 50), seed=11, flags=dict(VANISH, **flags), options=options)
+    report, ref, core = full_backward_case(K, N, T, B, (50, 50), seed=11, flags=dict(VANISH, **flags), options=options)
     # (the oracle's layouts; the HIP presences have already been asserted equal to them inside the helper)
     PP.require(ref.pattern_counts, **MINIMUMS)
     assert (core.lib is _capi.lib(_capi.WIDE_LIB_PATH)) == wide
@@ -177,7 +175,7 @@ def test_full_backward_where_objects_vanish(case):
     rel = {n: e / max(max(s, by[n.replace("scale_offset", "l2.b")]) if n.endswith("transform.scale_offset") else s, 1e-4 * gmax)
            for n, e, s in report}
     _record("backward", case, tight=5e-4, patterns=ref.pattern_counts, worst_rel_err=max(rel.values()), worst_parameter=max(rel, key=rel.get))
-    _check_report(report, ill_scale=True)
+    check_report(report, ill_scale=True)
 
 
 def test_stream_chunks_cut_right_after_a_hole():
@@ -186,7 +184,7 @@ def test_stream_chunks_cut_right_after_a_hole():
     same through SqairStream's captured graph; and a reset of one lane leaves the other lanes' ids (everything of theirs) alone."""
     K, N, T, B, hw = 3, 3, 6, 4, (50, 50)
     F = make_flags(k_particles=K, n_steps_per_image=N, **VANISH)
-    x = _live_oracle_inputs(F, hw, T, B)
+    x = live_oracle_inputs(F, hw, T, B)
     PP.require(x["counts"], **MINIMUMS)
     pat = PP.classify_outputs(x["ref"].outputs, N)
     holes = np.flatnonzero(pat["hole"][:T - 1].any(1))           # frames (not the last) with a hole in some row
@@ -194,17 +192,17 @@ def test_stream_chunks_cut_right_after_a_hole():
     obs, noise = x["obs"], x["noise"]
     core = SqairCore(F, hw)
     core.set_params(x["P"])
-    whole = _pass(core, obs, noise)
+    whole = one_pass(core, obs, noise)
     assert np.array_equal(whole["prop_pres"], x["ref"].prop_pres.numpy()) and np.array_equal(whole["disc_pres"], x["ref"].disc_pres.numpy())
     assert np.array_equal(whole["obj_id"], x["ref"].obj_id.numpy().astype(np.float32))
     R = B * K
     cuts = [[int(t) + 1, T - int(t) - 1] for t in holes] + [[1] * T]
     print("chunk boundaries after the holed frames", holes.tolist(), "->", cuts)
     for sizes in cuts:
-        enc, dec = _switches(T, sizes, B, R, N, hw)
+        enc, dec = switches(T, sizes, B, R, N, hw)
         assert not enc and not dec, "the shapes of this case keep every once-per-pass layer on one kernel"
-        got, _ = _chunked(core, obs, noise, sizes)
-        _compare(got, whole)
+        got, _ = chunked(core, obs, noise, sizes)
+        compare(got, whole)
     # the captured one-frame graph, the state updated in place
     names = ("what", "where", "presence", "obj_id", "log_weights_per_timestep")
     c2 = SqairCore(F, hw)
@@ -265,7 +263,7 @@ def test_forecast_where_objects_vanish(case):
         print("forecast {}: {} objects vanish, {} (frame, row) cells compact a hole".format(case, seen["vanished"], seen["moved"]))
         assert seen["vanished"] >= 3 and seen["moved"] >= 1, seen
 
-    got, ref = _rollout_case(case + ", prop_prior_step_bias 0", flags, hw, B, S, Fn, require=require)
+    got, ref = rollout_case(case + ", prop_prior_step_bias 0", flags, hw, B, S, Fn, require=require)
     # expected_count: the weighted number of present slots per lane, against the reference's presences under the stream's weights
     cnt = ref["presence"].numpy().reshape(Fn, B, K, N).sum(-1)
     want = np.einsum("bk,fbk->fb", got["weights"].astype(np.float64), cnt)
@@ -279,7 +277,6 @@ def test_stream_training_chunk_two_starts_from_a_holed_layout():
     """The chunk-two case of tests/test_stream_train.py (imported rows, one lane reset, every gradient against `tbptt_ref` at that
     file's bar) with objects vanishing: the first chunk's LAST frame compacts a hole in an imported row, so chunk 2 starts from a
     permuted layout, and chunk 2 itself meets the minimums -- both required from the oracle's outputs."""
-    from tests.test_stream_train import _chunk_two_case
     K, N, B, T = 3, 3, 3, 3
 
     def require(out1, out2):
@@ -289,7 +286,7 @@ def test_stream_training_chunk_two_starts_from_a_holed_layout():
         assert first["hole"][T - 1, :(B - 1) * K].any(), "the last frame of chunk 1 must compact a hole in a row that chunk 2 imports"
         PP.require(PP.count(second), **MINIMUMS)
 
-    _chunk_two_case(dict(k_particles=K, n_steps_per_image=N, **VANISH), None, False, require=require)
+    chunk_two_case(dict(k_particles=K, n_steps_per_image=N, **VANISH), None, False, require=require)
 
 
 def test_history_tracks_follow_the_id_through_a_permutation():
@@ -297,10 +294,9 @@ def test_history_tracks_follow_the_id_through_a_permutation():
     for bit) in which, inside the lag window, the ORACLE moves an object to another slot: `track_where` / `track_present` must
     follow the id, not the slot."""
     from tests import history_ref as H
-    from tests.test_history import OUTS, _check, _host, _push
     K, N, T, B, hw = 3, 3, 6, 4, (50, 50)
     F = make_flags(k_particles=K, n_steps_per_image=N, **VANISH)
-    x = _live_oracle_inputs(F, hw, T, B)
+    x = live_oracle_inputs(F, hw, T, B)
     PP.require(x["counts"], **MINIMUMS)
     want_id = x["ref"].obj_id.numpy().reshape(T, B * K, N)
     moved = PP.moved_ids(want_id)
@@ -312,8 +308,8 @@ def test_history_tracks_follow_the_id_through_a_permutation():
     rec = H.Recorder(B * K)
     for t in range(T):
         parent = st.carried.pending().copy()
-        _push(rec, parent, _host(st.step(x["obs"][t:t + 1], noise=x["noise"][t:t + 1])))
-        got = _check(st, rec, "last", max_tracks=4 * N)
+        history_push(rec, parent, host(st.step(x["obs"][t:t + 1], noise=x["noise"][t:t + 1])))
+        got = history_check(st, rec, "last", max_tracks=4 * N)
     st.close()
     assert np.array_equal(got["obj_id"], want_id[T - lag:].astype(np.float32)), "the traced ids are the oracle's"
     followed = 0

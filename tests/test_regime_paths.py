@@ -35,9 +35,10 @@ from sqair_amd.flags import make_flags
 from sqair_amd.model import Model, SqairCore
 from tests import latent_regimes as LR
 from tests.hip_util import rel_err, run_hip, run_oracle
-from tests.test_hip_backward import LOOSE, TIGHT, _check_report, _full_backward_case, _full_backward_inputs
-from tests.test_hip_forward import REL, _live_oracle_case, _live_oracle_inputs
-from tests.test_hip_specialised import _spec_launches
+from tests.stream_cases import ORACLE_HW, chunk_two_case, filter_case, rollout_case
+from tests.stream_harness import chunked, compare, one_pass, switches
+from tests.pass_cases import (LOOSE, REL, TIGHT, check_report, full_backward_case, full_backward_inputs, live_oracle_case, live_oracle_inputs,
+                              spec_launches)
 
 pytestmark = pytest.mark.gpu
 
@@ -72,7 +73,7 @@ def _forward_inputs(case):
     """The oracle side of a forward case, computed once and shared by the legs that run it (nothing in it is written to)."""
     K, N, T, B, hw, flags, edits, need = LR.FORWARD[case]
     F = make_flags(k_particles=K, n_steps_per_image=N, **flags)
-    x = _live_oracle_inputs(F, hw, T, B, edits=edits)
+    x = live_oracle_inputs(F, hw, T, B, edits=edits)
     cfg = O.make_cfg(F, hw)
     x["regimes"] = LR.counts_of(x["ref"].outputs, cfg)
     print(LR.table(x["regimes"]))
@@ -89,7 +90,7 @@ def _require_forward(case):
 
 
 def _hip_errors(m, ref):
-    """(per-output scaled errors, bound errors) of a HIP model against an oracle model, in `_check_against`'s scalings."""
+    """(per-output scaled errors, bound errors) of a HIP model against an oracle model, in `check_against`'s scalings."""
     out = {}
     for k, v in ref.outputs.items():
         if not k.startswith("_") and k in m.outputs:
@@ -124,7 +125,7 @@ def _check_measured_forward(case, m, ref, r32):
 @pytest.mark.parametrize("case", sorted(LR.FORWARD))
 def test_forward_in_the_regime(case):
     """Every output against the fp64 oracle: presence, ids and step counts exact, every output at 5e-4 scaled, the bounds at 1e-4
-    relative (`_live_oracle_case`); the measured cases by the rule in this file's docstring."""
+    relative (`live_oracle_case`); the measured cases by the rule in this file's docstring."""
     K, N, T, B, hw, flags, edits, need = LR.FORWARD[case]
     F, x = _require_forward(case)
     if LR.conditioning(edits) == "measured":
@@ -132,7 +133,7 @@ def test_forward_in_the_regime(case):
         m = run_hip(F, hw, x["P"], x["obs"], x["noise"], nums=x["d"]["nums"])
         _check_measured_forward(case, m, x["ref"], r32)
     else:
-        m, _ = _live_oracle_case(F, hw=hw, T=T, B=B, inputs=x)
+        m, _ = live_oracle_case(F, hw=hw, T=T, B=B, inputs=x)
     assert (m.core.lib is _capi.lib(_capi.WIDE_LIB_PATH)) == ("n_what" in flags)
     out, bound = _hip_errors(m, x["ref"])
     worst = max(out, key=out.get)
@@ -156,22 +157,22 @@ def test_executors_agree_in_the_regime(case):
     F, x = _require_forward(case)
     run = lambda options, use_graph=False: run_hip(F, hw, x["P"], x["obs"], x["noise"], nums=x["d"]["nums"], options=options,
                                                    use_graph=use_graph)
-    n0 = _spec_launches()
+    n0 = spec_launches()
     ref = _outs(run({"specialised": 0}))
-    assert _spec_launches() == n0
+    assert spec_launches() == n0
     assert np.array_equal(ref["prop_pres"], x["ref"].prop_pres.numpy()) and np.array_equal(ref["disc_pres"], x["ref"].disc_pres.numpy())
     for name, options, use_graph in (("specialised", {"specialised": 1}, False), ("specialised, graph", {"specialised": 1}, True),
                                      ("slot_chain", {"slot_chain": 1}, False), ("slot_chain, graph", {"slot_chain": 1}, True),
                                      ("slot_chain, generic", {"slot_chain": 1, "specialised": 0}, False)):
-        n0 = _spec_launches()
+        n0 = spec_launches()
         got = _outs(run(options, use_graph))
         if "slot_chain" not in options:
-            assert _spec_launches() - n0 > 0, name
+            assert spec_launches() - n0 > 0, name
         assert set(got) == set(ref)
         for k, v in ref.items():
             assert np.array_equal(v, got[k], equal_nan=True), (case, name, k)
     if LR.conditioning(edits) == "tight":
-        _live_oracle_case(F, hw=hw, T=T, B=B, inputs=x, options={"slot_chain": 1})
+        live_oracle_case(F, hw=hw, T=T, B=B, inputs=x, options={"slot_chain": 1})
 
 
 def test_forward_graph_replay_equals_eager_in_the_regime():
@@ -190,7 +191,7 @@ def test_forward_graph_replay_equals_eager_in_the_regime():
 @functools.lru_cache(maxsize=None)
 def _backward_inputs(edits, flags_items):
     """The oracle side of a backward case (differentiated once, by the first leg that runs it), shared by its executors."""
-    inputs = _full_backward_inputs(3, 3, 3, 3, LR.BWD_HW, LR.BWD_SEED, dict(flags_items), edits, seed0=LR.bwd_noise_seed0(edits))
+    inputs = full_backward_inputs(3, 3, 3, 3, LR.BWD_HW, LR.BWD_SEED, dict(flags_items), edits, seed0=LR.bwd_noise_seed0(edits))
     F, obs, P, noise, ref, orc = inputs
     cfg = O.make_cfg(F, LR.BWD_HW)
     ref.regimes = LR.counts_of(ref.outputs, cfg)
@@ -224,8 +225,8 @@ def _fp32_gradient_distance(inputs):
 
 @pytest.mark.parametrize("case", sorted(LR.BACKWARD))
 def test_full_backward_in_the_regime(case):
-    """Every parameter's gradient against autograd through the fp64 oracle at the bars of tests/test_hip_backward.py: TIGHT, and
-    LOOSE for the two `*.transform.scale_offset` scalars (`_check_report`); the measured cases per parameter at max(that bar, 4 x the
+    """Every parameter's gradient against autograd through the fp64 oracle at the bars of tests/pass_cases.py: TIGHT, and
+    LOOSE for the two `*.transform.scale_offset` scalars (`check_report`); the measured cases per parameter at max(that bar, 4 x the
     fp32 oracle's own distance).
 
     The clamp cases additionally compare the two SCALE entries of `disc.transform.l2.b` one by one: every discovered glimpse's
@@ -236,7 +237,7 @@ def test_full_backward_in_the_regime(case):
     K, N, T, B, flags, options, wide, edits, need = LR.BACKWARD[case]
     inputs = _require_backward(case)
     orc = inputs[5]
-    report, ref, core = _full_backward_case(K, N, T, B, LR.BWD_HW, LR.BWD_SEED, flags=flags, options=options, edits=edits, inputs=inputs)
+    report, ref, core = full_backward_case(K, N, T, B, LR.BWD_HW, LR.BWD_SEED, flags=flags, options=options, edits=edits, inputs=inputs)
     assert (core.lib is _capi.lib(_capi.WIDE_LIB_PATH)) == wide
     rel = LR.gradient_rel(report)
     worst = max(rel, key=rel.get)
@@ -253,7 +254,7 @@ def test_full_backward_in_the_regime(case):
         assert not bad, bad
     else:
         _record("backward", case, bar=_sig(base), hip_error=_sig(rel), **figures)
-        _check_report(report)
+        check_report(report)
     if case in LR.CLAMP_CASES:
         want = orc.P["disc.transform.l2.b"].grad.numpy()
         got = core.grads_by_name()["disc.transform.l2.b"].cpu().numpy().reshape(want.shape)
@@ -288,24 +289,23 @@ def test_training_graph_replay_equals_eager_in_the_regime():
 def test_stream_chunks_equal_the_single_pass_in_the_regime():
     """A 12-frame sequence at the combined edit fed in chunks of 1 and of 4 frames with the state carried: bit for bit the single
     pass; and the single pass itself against the oracle at the forward bars."""
-    from tests.test_stream_state import _chunked, _compare, _pass, _switches
     c = LR.STREAM
     K, N, T, B, hw = c["K"], c["N"], c["T"], c["B"], c["hw"]
     F = make_flags(k_particles=K, n_steps_per_image=N)
-    x = _live_oracle_inputs(F, hw, T, B, edits=c["edits"])
+    x = live_oracle_inputs(F, hw, T, B, edits=c["edits"])
     counts = LR.counts_of(x["ref"].outputs, O.make_cfg(F, hw))
     print(LR.table(counts))
     LR.require(counts, **c["minimums"])
-    m, _ = _live_oracle_case(F, hw=hw, T=T, B=B, inputs=x)
+    m, _ = live_oracle_case(F, hw=hw, T=T, B=B, inputs=x)
     core = SqairCore(F, hw)
     core.set_params(x["P"])
-    whole = _pass(core, x["obs"], x["noise"])
+    whole = one_pass(core, x["obs"], x["noise"])
     assert np.array_equal(whole["presence"], x["ref"].presence.numpy()) and np.array_equal(whole["obj_id"], x["ref"].obj_id.numpy().astype(np.float32))
     for sizes in c["chunks"]:
-        enc, dec = _switches(T, list(sizes), B, B * K, N, hw)
+        enc, dec = switches(T, list(sizes), B, B * K, N, hw)
         assert not enc and not dec, "the shapes of this case keep every once-per-pass layer on one kernel"
-        got, _ = _chunked(core, x["obs"], x["noise"], list(sizes))
-        _compare(got, whole)
+        got, _ = chunked(core, x["obs"], x["noise"], list(sizes))
+        compare(got, whole)
     out, bound = _hip_errors(m, x["ref"])
     _record("stream", "single_pass_T12", regimes=counts, worst_scaled_abs_err=max(out.values()), worst_output=max(out, key=out.get),
             worst_bound_err=max(bound.values()))
@@ -314,9 +314,8 @@ def test_stream_chunks_equal_the_single_pass_in_the_regime():
 def test_stream_training_chunk_in_the_regime():
     """The chunk-two case of tests/test_stream_train.py (imported rows, one lane reset, every gradient against tests/tbptt_ref.py at
     that file's bar) at the combined edit; chunk 2 must reach the regime on the oracle, on a kink-stable draw."""
-    from tests.test_stream_train import HW, _chunk_two_case
     c = LR.STREAM_TRAIN
-    cfg = O.make_cfg(make_flags(**c["flags"]), HW)
+    cfg = O.make_cfg(make_flags(**c["flags"]), ORACLE_HW)
 
     def require(out1, out2):
         counts = LR.counts_of(out2, cfg)
@@ -326,16 +325,15 @@ def test_stream_training_chunk_in_the_regime():
         assert kinks.clearance >= 1.0, kinks.closest()
 
     with LR.kink_recorder() as kinks:
-        _chunk_two_case(c["flags"], None, False, require=require, edits=c["edits"])
+        chunk_two_case(c["flags"], None, False, require=require, edits=c["edits"])
 
 
 def test_smc_evidence_at_saturated_logits():
     """SqairStream(resample="systematic") against the fp64 particle filter of tests/smc_ref.py (tests/test_smc_oracle.py's case
     `gru` and all its bars: outputs, log weights, the evidence, decisions and ancestors) with every live presence logit beyond 17;
     every step's proposal must hold such Bernoullis on the oracle."""
-    from tests.test_smc_oracle import HW, _filter_case
     c = LR.SMC
-    cfg = O.make_cfg(make_flags(**c["flags"]), HW)
+    cfg = O.make_cfg(make_flags(**c["flags"]), ORACLE_HW)
     seen = []
 
     def require(outputs, step):
@@ -343,7 +341,7 @@ def test_smc_evidence_at_saturated_logits():
         seen.append(counts["saturated_logit"])
         LR.require(counts, **c["minimums"])
 
-    n, worst = _filter_case("saturated_presence", c["flags"], c["B"], c["frames_per_step"], c["frames"], c["ess_frac"], False,
+    n, worst = filter_case("saturated_presence", c["flags"], c["B"], c["frames_per_step"], c["frames"], c["ess_frac"], False,
                             edits=c["edits"], require=require)
     _record("smc", "saturated_presence", saturated_logits_per_step=seen, counts=n, worst=_sig(worst))
 
@@ -352,7 +350,6 @@ def test_forecast_at_the_floored_prior():
     """A forecast against the fp64 rollout of tests/forecast_ref.py at tests/test_forecast.py's gate, with the propagation prior's
     scales at their floor and its presence logit saturated -- required of the reference rollout's OWN priors (every forecast frame
     samples from them) before the device runs."""
-    from tests.test_forecast import _rollout_case
     c = LR.FORECAST
     seen = {}
 
@@ -361,6 +358,6 @@ def test_forecast_at_the_floored_prior():
         print("forecast priors:", seen)
         LR.require_prior(seen, **c["minimums"])
 
-    got, ref = _rollout_case("floored_prior", c["flags"], c["hw"], c["B"], c["S"], c["Fn"], require=require, edits=c["edits"])
+    got, ref = rollout_case("floored_prior", c["flags"], c["hw"], c["B"], c["S"], c["Fn"], require=require, edits=c["edits"])
     assert float(got["presence"][-1].sum()) >= 4
     _record("forecast", "floored_prior", prior=dict(seen))

@@ -15,95 +15,26 @@ import pytest
 import torch
 
 from sqair_amd import _capi
-from sqair_amd.data import make_sequences, to_float
-from sqair_amd.flags import make_flags
-from sqair_amd.model import SqairCore
-from sqair_amd.stream import SqairStream
 from tests import score_ref as R
-from tests.hip_util import draw_noise, params32
+from tests.stream_harness import EST_KEYS, OUTS, SCORE, SMC_OUTS, host, run, same_bits, setup, stream, unscored_truth
 
 pytestmark = pytest.mark.gpu
 
-OUTS = ("what", "where", "presence", "obj_id", "log_weights_per_timestep")
-SMC_OUTS = ("ess", "resampled", "log_evidence", "ancestors")
-EST_KEYS = {"best_row", "weights", "ess", "count_prob", "expected_count", "map_count", "presence", "obj_id", "where", "what", "box",
-            "support", "box_mean"}
 SCORE_KEYS = set(_capi.SCORE_FIELDS)
-HW = (50, 50)
-FLAGS = dict(k_particles=3, n_steps_per_image=3)
-B, G, N = 4, 4, 3
-IOU = 0.5
+HW, FLAGS, B, G, N, IOU = SCORE.HW, SCORE.FLAGS, SCORE.B, SCORE.G, SCORE.N, SCORE.IOU
 SMC = dict(resample="systematic", ess_frac=0.5, seed=5)
 
 
 def _setup(T, seed=11):
-    F = make_flags(**FLAGS)
-    obs = to_float(make_sequences(B, T=T, canvas=HW, seed=seed)["imgs"])
-    P = params32(F, HW, 3, 0.05, obs.mean((0, 1)))
-    noise = draw_noise(np.random.default_rng(seed + 1), T, B * int(F.k_particles), int(F.n_steps_per_image), 4 + int(F.n_what) + 1)
-    return F, P, obs, noise
+    return setup(FLAGS, B, T, HW, seed)
 
 
 def _stream(F, P, **kw):
-    core = SqairCore(F, HW)
-    core.set_params(P)
-    return SqairStream(core, B, outputs=OUTS, estimate=True, estimate_iou=IOU, **kw)
+    return stream((F, HW, P), B, outputs=OUTS, estimate=True, estimate_iou=IOU, **kw)
 
 
 def _scored(F, P, **kw):
     return _stream(F, P, score=True, score_iou=IOU, score_truth=G, **kw)
-
-
-def _host(out):
-    torch.cuda.synchronize()
-    return {k: ({n: v.cpu().numpy() for n, v in x.items()} if isinstance(x, dict) else x.cpu().numpy()) for k, x in out.items()}
-
-
-def _bits(a):
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def _same_bits(a, b, keys, where):
-    for k in keys:
-        assert np.array_equal(_bits(a[k]), _bits(b[k])), (where, k)
-
-
-def _run(st, obs, noise, Ts=1, truth=None, observed=None, before=None):
-    """Steps ``st`` through the clip; returns the host copies of every step's outputs.  ``before(s)``: called ahead of step s."""
-    outs = []
-    for s in range(obs.shape[0] // Ts):
-        if before is not None:
-            before(s)
-        f = slice(s * Ts, (s + 1) * Ts)
-        kw = {}
-        if truth is not None and truth[s] is not None:
-            kw["truth"] = truth[s]
-        if observed is not None:
-            kw["observed"] = observed[f]
-        outs.append(_host(st.step(obs[f], noise=noise[f], **kw)))
-    return outs
-
-
-def _make_truth(outs, Ts, seed=7):
-    """One ``truth`` dict per step from the unscored run's lane boxes (see the module's docstring)."""
-    rng = np.random.default_rng(seed)
-    truth = []
-    for s, o in enumerate(outs):
-        lane = o["lane"]
-        box = np.zeros((Ts, B, G, 4), np.float32)
-        present = np.zeros((Ts, B, G), np.int32)
-        for f in range(Ts):
-            shift = ((s * Ts + f) // 4) % 2
-            for b in range(B):
-                for j in range(N):
-                    g = (j + shift) % N
-                    box[f, b, g] = lane["box"][f, b, j] + 1.5 * rng.standard_normal(4)
-                    present[f, b, g] = lane["presence"][f, b, j] != 0 and rng.uniform() < 0.8
-                if rng.uniform() < 0.33:
-                    box[f, b, N], present[f, b, N] = (rng.uniform(0, 30), rng.uniform(0, 30), 12.0, 12.0), 1
-        valid = (rng.uniform(size=(Ts, B)) < 0.9).astype(np.int32)
-        truth.append(dict(box=box, present=present, valid=valid))
-    return truth
 
 
 class _Ref(object):
@@ -146,11 +77,7 @@ class _Ref(object):
 
 
 def _truth_for(F, P, obs, noise, observed=None, **kw):
-    Ts = kw.get("frames_per_step", 1)
-    st = _stream(F, P, **kw)
-    outs = _run(st, obs, noise, Ts, observed=observed)
-    st.close()
-    return _make_truth(outs, Ts), outs
+    return unscored_truth(_stream(F, P, **kw), obs, noise, kw.get("frames_per_step", 1), observed)
 
 
 # ---- 1. nothing else changes; one node more; graph == eager; against the reference, with SMC -------------------------------------------
@@ -163,14 +90,14 @@ def test_the_score_changes_nothing_else_and_equals_the_reference():
     went = 0
     for t in range(T):
         f = slice(t, t + 1)
-        o, b, c = (_host(s.step(obs[f], noise=noise[f], **kw)) for s, kw in ((off, {}), (on, dict(truth=truth[t])), (eager, dict(truth=truth[t]))))
+        o, b, c = (host(s.step(obs[f], noise=noise[f], **kw)) for s, kw in ((off, {}), (on, dict(truth=truth[t])), (eager, dict(truth=truth[t]))))
         assert set(o["lane"]) == EST_KEYS and set(b["lane"]) == EST_KEYS | SCORE_KEYS
-        _same_bits(o, b, OUTS + SMC_OUTS, t)
-        _same_bits(o["lane"], b["lane"], EST_KEYS, t)
-        _same_bits(a[t]["lane"], b["lane"], EST_KEYS, (t, "the run the truth was made from"))
+        same_bits(o, b, OUTS + SMC_OUTS, t)
+        same_bits(o["lane"], b["lane"], EST_KEYS, t)
+        same_bits(a[t]["lane"], b["lane"], EST_KEYS, (t, "the run the truth was made from"))
         for k in ("state", "log_weight_sum", "log_z", "log_evidence", "ess", "u", "resampled", "_src"):
             assert torch.equal(getattr(off, k), getattr(on, k)), (t, k)
-        _same_bits(b["lane"], c["lane"], b["lane"].keys(), (t, "eager"))      # eager and graph: the same bits
+        same_bits(b["lane"], c["lane"], b["lane"].keys(), (t, "eager"))      # eager and graph: the same bits
         assert b["lane"]["truth_match"].shape == (1, B, G) and b["lane"]["tp"].shape == (1, B)
         ref.step(b, truth[t])
         went += int(b["resampled"].sum())
@@ -199,7 +126,7 @@ def test_score_against_reference(resample, Ts):
     truth, _ = _truth_for(F, P, obs, noise, **kw)
     st = _scored(F, P, **kw)
     ref = _Ref()
-    for s, o in enumerate(_run(st, obs, noise, Ts, truth=truth)):
+    for s, o in enumerate(run(st, obs, noise, Ts, truth=truth)):
         ref.step(o, truth[s])
     ref.check_score(st.score())
     tot = ref.totals()
@@ -218,7 +145,7 @@ def test_a_coasted_lane_needs_no_case_of_its_own():
     st = _scored(F, P, missing=True)
     ref = _Ref()
     scored_coasted = 0
-    for t, o in enumerate(_run(st, obs, noise, truth=truth, observed=observed)):
+    for t, o in enumerate(run(st, obs, noise, truth=truth, observed=observed)):
         ref.step(o, truth[t])
         scored_coasted += int((~observed[t] & (truth[t]["valid"][0] != 0) & (o["lane"]["tp"][0] >= 0)).sum())
     ref.check_score(st.score())
@@ -248,7 +175,7 @@ def test_reset_clears_the_memory_and_a_step_without_truth_changes_no_accumulator
             assert torch.equal(before["last_id"][keep], after["last_id"][keep]) and (before["last_id"][keep] >= 0).any()
             ref.last_id[lanes] = -1
         before = state()
-        o = _host(st.step(obs[f], noise=noise[f], **({} if truth[t] is None else dict(truth=truth[t]))))
+        o = host(st.step(obs[f], noise=noise[f], **({} if truth[t] is None else dict(truth=truth[t]))))
         if truth[t] is None:
             after = state()
             assert all(torch.equal(before[k], after[k]) for k in before), t

@@ -1,8 +1,6 @@
 """The float64 reference of the slot loop's adjoint kernels (tests/slot_adjoint_ref.py), pinned without a GPU:
 every forward piece reproduces the oracle's discovery_core / propagation_core on the same inputs, autograd agrees with central
 differences, the inverted activations reproduce the tape, and the Cholesky gradient lands where oracle.fill_triangular says."""
-import contextlib
-
 import numpy as np
 import pytest
 import torch
@@ -14,27 +12,6 @@ from tests import slot_adjoint_ref as R
 
 F64 = torch.float64
 HW, G, NW, NH, B = (14, 17), 6, 7, 128, 5
-
-
-@contextlib.contextmanager
-def recorded():
-    """Every call of oracle.linear (its output) and oracle.mlp2_hidden (its input), by layer name, in call order."""
-    rec = {}
-    lin, mlp = O.linear, O.mlp2_hidden
-
-    def linear(P, name, x):
-        y = lin(P, name, x)
-        rec.setdefault(name, []).append(y)
-        return y
-
-    def mlp2_hidden(P, name, x):
-        rec.setdefault(name + ":in", []).append(x)
-        return mlp(P, name, x)
-    O.linear, O.mlp2_hidden = linear, mlp2_hidden
-    try:
-        yield rec
-    finally:
-        O.linear, O.mlp2_hidden = lin, mlp
 
 
 @pytest.fixture(scope="module")
@@ -60,7 +37,7 @@ def _close(a, b, tol=1e-12):
 def test_propagation_pieces_reproduce_the_oracle(model):
     orc, x = model
     P = orc.P
-    with recorded() as rec:
+    with R.recorded() as rec:
         out, _ = orc.propagation_core(x["img"], (x["what_tm1"], x["where_tm1"], x["pres_tm1"], x["logit_tm1"]), x["temporal"],
                                       (x["what_km1"], x["where_km1"], x["pres_km1"], x["hidden"]), x["eps_where"], x["eps_what"], x["u"])
     zeros4, zerosw = torch.zeros(B, 4, dtype=F64), torch.zeros(B, NW, dtype=F64)
@@ -95,7 +72,7 @@ def test_propagation_pieces_reproduce_the_oracle(model):
 def test_discovery_pieces_reproduce_the_oracle(model):
     orc, x = model
     P = orc.P
-    with recorded() as rec:
+    with R.recorded() as rec:
         out, _ = orc.discovery_core(x["img"], x["cond"], (x["what_km1"], x["where_km1"], x["pres_tm1"], x["hidden"]), x["eps_where"],
                                     x["eps_what"], x["u"])
     cc = dict(img=x["img"], G=G, mode=3, scale_offset=P["disc.transform.scale_offset"], eps=x["eps_where"])

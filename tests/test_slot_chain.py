@@ -6,35 +6,12 @@ import numpy as np
 import pytest
 import torch
 
-from sqair_amd.data import make_sequences, to_float
-from sqair_amd.flags import make_flags
 from sqair_amd.model import Model, SqairCore
-from tests.hip_util import draw_noise, params32
+from tests.hip_util import draw_noise
+
+from tests.pass_cases import chain_inputs, chain_run
 
 pytestmark = pytest.mark.gpu
-
-
-def _inputs(B, K, N, T, hw, seed=3, obj_size=None, **flags):
-    F = make_flags(k_particles=K, n_steps_per_image=N, **flags)
-    # (obj_size: tests/fuzz_forward.py draws canvases down to 8 x 8 -- the generator, like the reference's, re-draws a sample until
-    #  its objects fit without overlap, i.e. for ever when they cannot)
-    d = make_sequences(B, T=T, canvas=hw, seed=seed, **({"obj_size": obj_size} if obj_size else {}))
-    obs = to_float(d["imgs"])
-    P = params32(F, hw, 0, 0.05, obs.mean((0, 1)))
-    noise = draw_noise(np.random.default_rng(seed), T, B * K, N, 4 + int(F.n_what) + 1)
-    return F, d, obs, P, noise
-
-
-def _run(F, hw, d, obs, P, noise, K, chain, use_graph):
-    core = SqairCore(F, hw, options={"slot_chain": 1} if chain else None)
-    core.set_params(P)
-    m = Model(obs, None, core, K, presence=d["nums"], debug=chain)   # (debug: also asserts every chain launch completed)
-    m.run(noise=noise, use_graph=use_graph)
-    torch.cuda.synchronize()
-    out = {k: v.detach().cpu().numpy().copy() for k, v in core.out.items()}
-    out["log_weights"] = core.log_weights.cpu().numpy().copy()
-    out["scalars"] = core.scalars.cpu().numpy().copy()
-    return core, m, out
 
 
 @pytest.mark.parametrize("B,K,N,T,hw", [(4, 2, 3, 3, (50, 50)),      # one row tile
@@ -45,10 +22,10 @@ def _run(F, hw, d, obs, P, noise, K, chain, use_graph):
                                         (1, 1, 1, 2, (50, 50)),      # one row, one slot: a chain of a single slot-step
                                         (17, 2, 1, 2, (50, 50))])    # 34 rows: a last row tile of 2 rows, one slot
 def test_chain_is_bit_identical_to_the_launches(B, K, N, T, hw):
-    F, d, obs, P, noise = _inputs(B, K, N, T, hw)
-    _, _, ref = _run(F, hw, d, obs, P, noise, K, chain=False, use_graph=False)
+    F, d, obs, P, noise = chain_inputs(B, K, N, T, hw)
+    _, _, ref = chain_run(F, hw, d, obs, P, noise, K, chain=False, use_graph=False)
     for use_graph in (False, True):
-        core, m, got = _run(F, hw, d, obs, P, noise, K, chain=True, use_graph=use_graph)
+        core, m, got = chain_run(F, hw, d, obs, P, noise, K, chain=True, use_graph=use_graph)
         for k, v in ref.items():
             assert np.array_equal(v, got[k], equal_nan=True), (k, use_graph)
         if use_graph:   # the chain replaces the slot loop's launches: two launches per frame instead of ~7 per slot and phase
@@ -64,7 +41,7 @@ def test_chain_passes_with_fresh_noise_and_frames_on_one_workspace():
     the pass's sentinel fill would let a consumer read the previous pass's (different) value instead of waiting -- with the same
     inputs every pass (the other tests) a stale value equals the right one."""
     B, K, N, T, hw = 32, 5, 4, 2, (50, 50)
-    F, d, obs, P, noise = _inputs(B, K, N, T, hw)
+    F, d, obs, P, noise = chain_inputs(B, K, N, T, hw)
     rng = np.random.default_rng(11)
     cores = []
     for chain in (False, True):
@@ -96,7 +73,7 @@ def test_chain_gradients_match_the_launches():
     agree to the run-to-run reproducibility of the backward pass itself (its weight-gradient launches accumulate with float
     atomics: the same tolerance is applied between two evaluations of the launch path)."""
     B, K, N, T, hw = 8, 5, 3, 3, (50, 50)
-    F, d, obs, P, noise = _inputs(B, K, N, T, hw)
+    F, d, obs, P, noise = chain_inputs(B, K, N, T, hw)
     grads = []
     for chain in (False, True):
         core = SqairCore(F, hw, options={"slot_chain": 1} if chain else None)
@@ -119,9 +96,9 @@ def test_chain_gradients_match_the_launches():
 def test_chain_keeps_out_of_configurations_it_does_not_serve():
     """LSTM cells, more than 320 particle rows: the option is accepted, the pass runs one launch per op (and stays correct)."""
     B, K, N, T, hw = 3, 2, 2, 2, (50, 50)
-    F, d, obs, P, noise = _inputs(B, K, N, T, hw, time_transition="LSTM")
-    _, _, ref = _run(F, hw, d, obs, P, noise, K, chain=False, use_graph=True)
-    core, _, got = _run(F, hw, d, obs, P, noise, K, chain=True, use_graph=True)
+    F, d, obs, P, noise = chain_inputs(B, K, N, T, hw, time_transition="LSTM")
+    _, _, ref = chain_run(F, hw, d, obs, P, noise, K, chain=False, use_graph=True)
+    core, _, got = chain_run(F, hw, d, obs, P, noise, K, chain=True, use_graph=True)
     for k, v in ref.items():
         assert np.array_equal(v, got[k], equal_nan=True), k
     plain = SqairCore(F, hw)
@@ -137,8 +114,8 @@ def test_chain_tables_survive_fresh_operand_buffers_and_a_capture():
     open another one), and every pass -- eager on fresh buffers, and the replay of the pinned graph at the end -- stays
     bit-identical to the launch-per-op path."""
     B, K, N, T, hw = 4, 2, 3, 3, (50, 50)
-    F, d, obs, P, noise = _inputs(B, K, N, T, hw)
-    _, _, ref = _run(F, hw, d, obs, P, noise, K, chain=False, use_graph=False)
+    F, d, obs, P, noise = chain_inputs(B, K, N, T, hw)
+    _, _, ref = chain_run(F, hw, d, obs, P, noise, K, chain=False, use_graph=False)
     core = SqairCore(F, hw, options={"slot_chain": 1, "slot_chain_arena_kb": 256})
     core.set_params(P)
     m = Model(obs, None, core, K, presence=d["nums"], debug=True)

@@ -16,7 +16,6 @@ from sqair_amd.flags import make_flags
 from sqair_amd.params import init_params
 from tests import slot_adjoint_ref as R
 from tests import slot_forward_ref as SF
-from tests.test_slot_adjoint_ref import recorded
 
 F64 = torch.float64
 HW, G, NW, NH, B, N = (14, 17), 6, 7, 128, 5, 3
@@ -64,7 +63,7 @@ def test_propagation_slot_and_the_next_slots_layer(model):
     nz = x["noise"][:, 0, k]
     z_k = (x["what_tm1"][:, k], x["where_tm1"][:, k], x["pres_tm1"][:, k:k + 1], torch.zeros(B, 1, dtype=F64))
     state = (x["what_km1"], x["where_km1"], x["pres_km1"], x["hidden"])
-    with recorded() as rec:
+    with R.recorded() as rec:
         out, state2 = orc.propagation_core(x["img"], z_k, x["temporal"][:, k], state, nz[:, :4], nz[:, 4:4 + NW], nz[:, 4 + NW:])
     rec_prev, rec_new = _records(x, k, False)
     ops = SF.slot_operands(rec_prev, rec_new, x["noise"].numpy(), L, False, k, NW, F64)
@@ -99,7 +98,7 @@ def test_propagation_slot_and_the_next_slots_layer(model):
     z = SF.z_record(out["where"], out["what"], t["pres"], t["logit"])
     z_n = (x["what_tm1"][:, k + 1], x["where_tm1"][:, k + 1], x["pres_tm1"][:, k + 1:k + 2], torch.zeros(B, 1, dtype=F64))
     nz2 = x["noise"][:, 0, k + 1]
-    with recorded() as rec2:
+    with R.recorded() as rec2:
         out2, state3 = orc.propagation_core(x["img"], z_n, x["temporal"][:, k + 1], state2, nz2[:, :4], nz2[:, 4:4 + NW], nz2[:, 4 + NW:])
     tau = x["temporal"][:, k + 1, NH:] if cell == "LSTM" else x["temporal"][:, k + 1]
     loc1 = SF.gaussian_head(P, "enc.what_head", O.mlp2_hidden(P, "enc.glimpse", rec2["enc.glimpse:in"][0]))[0]
@@ -113,7 +112,7 @@ def test_discovery_slot_and_the_next_slots_layer(model):
     P, k = orc.P, 1
     nz = x["noise"][:, 1, k]
     state = (x["what_km1"], x["where_km1"], x["pres_km1"], x["hidden"])
-    with recorded() as rec:
+    with R.recorded() as rec:
         out, state2 = orc.discovery_core(x["img"], x["cond"], state, nz[:, :4], nz[:, 4:4 + NW], nz[:, 4 + NW:])
     rec_prev, rec_new = _records(x, k, True)
     ops = SF.slot_operands(rec_prev, rec_new, x["noise"].numpy(), L, True, k, NW, F64)

@@ -9,51 +9,20 @@ import pytest
 import torch
 
 from sqair_amd import _capi
-from sqair_amd.data import make_sequences, to_float
-from sqair_amd.flags import make_flags
-from sqair_amd.model import SqairCore
 from sqair_amd.stream import SqairStream
-from tests.hip_util import draw_noise, params32
+from tests.stream_harness import OUTS, SMC_OUTS, accumulate, core, host, same_values, setup
 
 pytestmark = pytest.mark.gpu
 
-OUTS = ("what", "where", "presence", "obj_id", "log_weights_per_timestep")
-SMC_OUTS = ("ess", "resampled", "log_evidence", "ancestors")
 HW = (50, 50)
 
 
 def _setup(flags, B, T, seed=11):
-    F = make_flags(**flags)
-    d = make_sequences(B, T=T, canvas=HW, seed=seed)
-    obs = to_float(d["imgs"])
-    P = params32(F, HW, 3, 0.05, obs.mean((0, 1)))
-    N, K = int(F.n_steps_per_image), int(F.k_particles)
-    noise = draw_noise(np.random.default_rng(seed + 1), T, B * K, N, 4 + int(F.n_what) + 1)
-    return F, P, obs, noise
+    return setup(flags, B, T, HW, seed)
 
 
 def _core(F, P, options=None):
-    core = SqairCore(F, HW, options=options)
-    core.set_params(P)
-    return core
-
-
-def _host(out):
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in out.items()}
-
-
-def _same(a, b, keys):
-    for k in keys:
-        assert np.array_equal(a[k], b[k], equal_nan=True), (k, np.argwhere(a[k] != b[k])[:4])
-
-
-def _accumulate(lw0, lw):
-    """a_k as the kernel forms it: the carried log weight plus this pass's frames, in frame order, in fp32."""
-    a = lw0.astype(np.float32).copy()
-    for t in range(lw.shape[0]):
-        a = (a + lw[t]).astype(np.float32)
-    return a
+    return core(F, HW, P, options)
 
 
 # ---- 1. ess_frac = 0: never resample ---------------------------------------------------------------------------------------------
@@ -65,9 +34,9 @@ def test_never_resampling_changes_nothing():
     plain = SqairStream(_core(F, P), B, outputs=OUTS)
     smc = SqairStream(_core(F, P), B, outputs=OUTS, resample="systematic", ess_frac=0.0)
     for t in range(T):
-        a = _host(plain.step(obs[t:t + 1], noise=noise[t:t + 1]))
-        b = _host(smc.step(obs[t:t + 1], noise=noise[t:t + 1]))
-        _same(a, b, OUTS)
+        a = host(plain.step(obs[t:t + 1], noise=noise[t:t + 1]))
+        b = host(smc.step(obs[t:t + 1], noise=noise[t:t + 1]))
+        same_values(a, b, OUTS)
         assert (b["resampled"] == 0).all()
         assert np.array_equal(b["ancestors"], np.arange(R))
     # the evidence after frame T is the IWAE bound of one whole T-frame pass
@@ -109,14 +78,14 @@ def test_resampler_against_numpy(flags, frac, caller):
         u_in = rng.uniform(size=B).astype(np.float32) if caller else None
         out = st.step(obs[t:t + 1], noise=noise[t:t + 1], uniforms=u_in)
         u, lw1, lz1 = st.u.clone(), st.log_weight_sum.clone(), st.log_z.clone()
-        o = _host(out)
+        o = host(out)
         lw0, lz0, u, lw1, lz1 = (x.cpu().numpy() for x in (lw0, lz0, u, lw1, lz1))
         if caller:
             assert np.array_equal(u, u_in)
         else:
             assert ((u >= 0) & (u < 1)).all()
             us.append(u)
-        a = _accumulate(lw0, o["log_weights_per_timestep"]).reshape(B, K).astype(np.float64)
+        a = accumulate(lw0, o["log_weights_per_timestep"]).reshape(B, K).astype(np.float64)
         m = a.max(1, keepdims=True)
         e = np.exp(a - m)
         S = e.sum(1)
@@ -165,9 +134,9 @@ def test_device_resampling_equals_host_resample():
     b = SqairStream(_core(F, P), B, outputs=OUTS)
     moved = False
     for t in range(T):
-        oa = _host(a.step(obs[t:t + 1], noise=noise[t:t + 1]))
-        ob = _host(b.step(obs[t:t + 1], noise=noise[t:t + 1]))
-        _same(oa, ob, OUTS)
+        oa = host(a.step(obs[t:t + 1], noise=noise[t:t + 1]))
+        ob = host(b.step(obs[t:t + 1], noise=noise[t:t + 1]))
+        same_values(oa, ob, OUTS)
         assert (oa["resampled"] == 1).all()
         moved |= not np.array_equal(oa["ancestors"], np.arange(B * a.K))
         b.resample(oa["ancestors"])
@@ -186,12 +155,12 @@ def test_graph_equals_eager(cells, chain):
     for use_graph in (False, True):
         st = SqairStream(_core(F, P, options={"slot_chain": chain}), B, outputs=OUTS, use_graph=use_graph, seed=3,
                          resample="systematic", ess_frac=0.5)
-        runs.append([_host(st.step(obs[t:t + 1])) for t in range(T)])
+        runs.append([host(st.step(obs[t:t + 1])) for t in range(T)])
         if chain:
             st.core.check_chain()
     went = 0
     for e, g in zip(*runs):
-        _same(e, g, OUTS + SMC_OUTS)
+        same_values(e, g, OUTS + SMC_OUTS)
         went += int(e["resampled"].sum())
     assert went > 0
 
@@ -215,9 +184,9 @@ def test_reset_composes_with_smc():
     z = SqairStream(_core(F, P), B, outputs=OUTS, resample="systematic", ess_frac=0.5)   # lane j's fresh start
     went = 0
     for t in range(T, 2 * T):
-        ox = _host(x.step(obs[t:t + 1], noise=noise[t:t + 1]))
-        oy = _host(y.step(obs[t:t + 1], noise=noise[t:t + 1]))
-        oz = _host(z.step(obs[t:t + 1], noise=noise[t:t + 1]))
+        ox = host(x.step(obs[t:t + 1], noise=noise[t:t + 1]))
+        oy = host(y.step(obs[t:t + 1], noise=noise[t:t + 1]))
+        oz = host(z.step(obs[t:t + 1], noise=noise[t:t + 1]))
         for k in OUTS:
             assert np.array_equal(ox[k][:, lane], oz[k][:, lane], equal_nan=True), k
             assert np.array_equal(ox[k][:, others], oy[k][:, others], equal_nan=True), k
@@ -253,16 +222,14 @@ def test_graph_has_exactly_one_node_more():
 # ---- 7. systematic invariants over a long stream -----------------------------------------------------------------------------
 def test_systematic_invariants_on_a_long_stream():
     B, K, T, frac = 8, 5, 100, 0.5
-    F = make_flags(k_particles=K, n_steps_per_image=3)
-    obs = to_float(make_sequences(B, T=T, canvas=HW, seed=41)["imgs"])
-    P = params32(F, HW, 3, 0.05, obs.mean((0, 1)))
+    F, P, obs, _ = _setup(dict(k_particles=K, n_steps_per_image=3), B, T, seed=41)
     st = SqairStream(_core(F, P), B, outputs=OUTS, resample="systematic", ess_frac=frac, seed=9)
     went = 0
     for t in range(T):
         lw0 = st.log_weight_sum.clone()
-        o = _host(st.step(obs[t:t + 1]))
+        o = host(st.step(obs[t:t + 1]))
         lw1 = st.log_weight_sum.cpu().numpy()
-        a = _accumulate(lw0.cpu().numpy(), o["log_weights_per_timestep"]).reshape(B, K).astype(np.float64)
+        a = accumulate(lw0.cpu().numpy(), o["log_weights_per_timestep"]).reshape(B, K).astype(np.float64)
         w = np.exp(a - a.max(1, keepdims=True))
         w /= w.sum(1, keepdims=True)
         assert np.array_equal(o["resampled"], (o["ess"] < np.float32(frac * K)).astype(np.int32)), t

@@ -3,104 +3,23 @@
 A sequence fed in chunks with the state carried from call to call gives the outputs of one pass over the whole sequence, bit for
 bit (same frames, same noise slices); lanes can be reset and particles resampled through the source map; one captured graph of a
 one-frame pass, replayed with the state updated in place, gives the eager results."""
-import math
-
 import numpy as np
 import pytest
 import torch
 
 from sqair_amd import _capi
-from sqair_amd.data import config_inputs, make_sequences, to_float
-from sqair_amd.flags import make_flags
-from sqair_amd.model import SqairCore
+from sqair_amd.data import config_inputs
 from sqair_amd.stream import SqairStream
-from tests.hip_util import draw_noise, params32
+from tests.stream_harness import (FINAL, PER_FRAME, blob as _blob, chunked as _chunked, compare, core as _core, one_pass,
+                                  set_state, setup, switches)
 
 pytestmark = pytest.mark.gpu
 
-PER_FRAME = [n for n in _capi.OUTPUT_FIELDS if not n.startswith("final_")]
-FINAL = [n for n in _capi.OUTPUT_FIELDS if n.startswith("final_")]
 DECODER = ("canvas", "glimpse", "data_ll_per_sample", "log_weights_per_timestep")
-GATE = 2e-5    # the repository's per-output gate (scaled absolute error), for decoder outputs whose dense kernel changes with T
-MT_ROWS, T2_ROWS, T2_KC = 6000, 512, 40   # once-per-pass layers: kernel (summation order) by row count (csrc/sqair_linear.hip)
 
 
 def _setup(flags, hw, B, T, seed=11):
-    F = make_flags(**flags)
-    d = make_sequences(B, T=T, canvas=hw, seed=seed)
-    obs = to_float(d["imgs"])
-    P = params32(F, hw, 3, 0.05, obs.mean((0, 1)))
-    N, K = int(F.n_steps_per_image), int(F.k_particles)
-    noise = draw_noise(np.random.default_rng(seed + 1), T, B * K, N, 4 + int(F.n_what) + 1)
-    return F, P, obs, noise
-
-
-def _core(F, hw, P, options=None):
-    core = SqairCore(F, hw, options=options)
-    core.set_params(P)
-    return core
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _set_state(core, B, state_in=None, state_out=None, src=None):
-    nb = core.lib.sqair_state_bytes(core.handle, B) if (state_in is not None or state_out is not None) else 0
-    core.check(core.lib.sqair_set_state(core.handle, _ptr(state_in), _ptr(state_out), _ptr(src), nb, B), "sqair_set_state")
-
-
-def _blob(core, B):
-    return torch.zeros(core.lib.sqair_state_bytes(core.handle, B) // 4, dtype=torch.float32, device=core.device)
-
-
-def _pass(core, obs, noise, state_in=None, state_out=None, src=None, t_offset=0):
-    """One eager pass of len(obs) frames (state as given; none = the handle's plain pass); every output, on the host."""
-    T, B = obs.shape[:2]
-    core.bind(T, B, "all")
-    with core.on_stream():
-        core.obs.copy_(torch.as_tensor(obs))
-        core.noise.copy_(torch.as_tensor(noise).reshape(core.noise.shape))
-        _set_state(core, B, state_in, state_out, src)
-        core.check(core.lib.sqair_forward(*core._args(t_offset)), "sqair_forward")
-    core.stream.synchronize()
-    if core.options.get("slot_chain"):
-        core.check_chain()
-    return {k: v.cpu().numpy().copy() for k, v in core.out.items()}
-
-
-def _chunked(core, obs, noise, sizes, src_before=None):
-    """The same frames as passes of `sizes` frames, the state carried in place; src_before: {chunk index: source map}."""
-    B = obs.shape[1]
-    blob = _blob(core, B)
-    outs, t0 = [], 0
-    for i, c in enumerate(sizes):
-        src = None
-        if src_before and i in src_before:
-            src = torch.as_tensor(np.asarray(src_before[i], dtype=np.int32), device=core.device)
-        outs.append(_pass(core, obs[t0:t0 + c], noise[t0:t0 + c], None if i == 0 else blob, blob, src))
-        t0 += c
-    merged = {k: np.concatenate([o[k] for o in outs]) for k in PER_FRAME}
-    merged.update({k: outs[-1][k] for k in FINAL})
-    return merged, outs
-
-
-def _switches(T, sizes, B, R, N, hw):
-    """Whether a once-per-pass layer runs another dense kernel in the whole pass than in some chunk: (encoder, decoder)."""
-    kc = math.ceil(hw[0] * hw[1] / 16)
-    enc = kc >= T2_KC and any((c * B >= T2_ROWS) != (T * B >= T2_ROWS) for c in sizes)
-    dec = any((c * R * N >= MT_ROWS) != (T * R * N >= MT_ROWS) for c in sizes)
-    return enc, dec
-
-
-def _compare(got, want, loose=()):
-    for k in PER_FRAME + FINAL:
-        if k in loose:
-            scale = max(float(np.abs(want[k]).max()), 1.0)
-            err = float(np.abs(got[k] - want[k]).max()) / scale
-            assert err <= GATE, (k, err)
-        else:
-            assert np.array_equal(got[k], want[k], equal_nan=True), (k, float(np.abs(got[k] - want[k]).max()))
+    return setup(flags, B, T, hw, seed)
 
 
 # ---- 1. chunked == whole ---------------------------------------------------------------------------------------------------
@@ -124,14 +43,14 @@ def test_chunked_passes_equal_the_whole_pass(case):
     core = _core(F, hw, P)
     if case.startswith("wide"):
         assert core.lib is _capi.lib(_capi.WIDE_LIB_PATH)
-    whole = _pass(core, obs, noise)
+    whole = one_pass(core, obs, noise)
     assert float(whole["presence"].sum()) > 0 and float(whole["obj_id"].max()) >= 0
     R, N = B * int(F.k_particles), int(F.n_steps_per_image)
     for sizes in ([3, 3, 4], [1] * T):
-        enc, dec = _switches(T, sizes, B, R, N, hw)
+        enc, dec = switches(T, sizes, B, R, N, hw)
         assert not enc and not dec, "the shapes of these cases keep every once-per-pass layer on one kernel"
         got, _ = _chunked(core, obs, noise, sizes)
-        _compare(got, whole)
+        compare(got, whole)
 
 
 @pytest.mark.parametrize("T,sizes,B", [(10, [3, 3, 4], 32), (10, [1] * 10, 32), (100, [10] * 10, 5)],
@@ -144,12 +63,12 @@ def test_cfg2_chunked_and_long_sequences(T, sizes, B):
     hw = (50, 50)
     F, P, obs, noise = _setup(ov, hw, B, T, seed=5)
     core = _core(F, hw, P)
-    whole = _pass(core, obs, noise)
+    whole = one_pass(core, obs, noise)
     R, N = B * int(F.k_particles), int(F.n_steps_per_image)
-    enc, dec = _switches(T, sizes, B, R, N, hw)
+    enc, dec = switches(T, sizes, B, R, N, hw)
     assert not enc and dec
     got, _ = _chunked(core, obs, noise, sizes)
-    _compare(got, whole, loose=DECODER)
+    compare(got, whole, loose=DECODER)
     assert float(whole["obj_id"][-1].max()) >= 0   # objects carried to the last frame
 
 
@@ -167,7 +86,7 @@ def test_graph_replayed_in_place_equals_eager_chunks(chain):
     src = torch.full((R,), -1, dtype=torch.int32, device=core.device)   # the first replay starts every row fresh
     outs = []
     with core.on_stream():
-        _set_state(core, B, blob, blob, src)
+        set_state(core, B, blob, blob, src)
         core.stream.synchronize()
         core.check(core.lib.sqair_graph_capture(*core._args(0)), "sqair_graph_capture")
         for t in range(T):
@@ -182,7 +101,7 @@ def test_graph_replayed_in_place_equals_eager_chunks(chain):
         core.check_chain()
     got = {k: np.concatenate([o[k].cpu().numpy() for o in outs]) for k in PER_FRAME}
     got.update({k: outs[-1][k].cpu().numpy() for k in FINAL})
-    _compare(got, eager)
+    compare(got, eager)
 
 
 # ---- 3. reset -------------------------------------------------------------------------------------------------------------------
@@ -197,7 +116,7 @@ def test_reset_lane_starts_a_fresh_sequence():
     src = np.arange(R)
     src[j * K:(j + 1) * K] = -1
     _, reset = _chunked(core, obs, noise, [3, 3], src_before={1: src})
-    fresh = _pass(core, obs[3:], noise[3:])   # same B, t_offset 0, chunk 2's frames
+    fresh = one_pass(core, obs[3:], noise[3:])   # same B, t_offset 0, chunk 2's frames
     lane = slice(j * K, (j + 1) * K)
     others = np.r_[0:j * K, (j + 1) * K:R]
     for k in PER_FRAME:
@@ -253,12 +172,12 @@ def test_graph_nodes_only_the_import_and_export_are_added():
             core.obs.copy_(torch.as_tensor(obs))
             core.noise.copy_(torch.as_tensor(noise).reshape(core.noise.shape))
             if mode == "set_then_off":
-                _set_state(core, B, blob, blob)
-                _set_state(core, B)
+                set_state(core, B, blob, blob)
+                set_state(core, B)
             elif mode == "in_place":
-                _set_state(core, B, blob, blob)
+                set_state(core, B, blob, blob)
             elif mode == "export_only":
-                _set_state(core, B, None, blob)
+                set_state(core, B, None, blob)
             core.stream.synchronize()
             core.check(core.lib.sqair_graph_capture(*core._args(0)), "sqair_graph_capture")
         return core.graph_nodes()
@@ -277,7 +196,7 @@ def test_sqair_stream_steps_equal_the_whole_pass():
     F, P, obs, noise = _setup(flags, hw, B, T, seed=61)
     K = int(F.k_particles)
     R = B * K
-    whole = _pass(_core(F, hw, P), obs, noise)
+    whole = one_pass(_core(F, hw, P), obs, noise)
     core = _core(F, hw, P)
     st = SqairStream(core, B, frames_per_step=1, outputs=PER_FRAME, use_graph=True)
     outs = [st.step(obs[t:t + 1], noise=noise[t:t + 1]) for t in range(T)]
@@ -317,6 +236,6 @@ def test_sqair_stream_steps_equal_the_whole_pass():
     assert st.frame == 2 * T
     st.close()
     # the handle's plain passes start from the initial state again
-    again = _pass(core, obs, noise)
+    again = one_pass(core, obs, noise)
     for k in PER_FRAME:
         assert np.array_equal(again[k], whole[k], equal_nan=True), k

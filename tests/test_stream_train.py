@@ -14,54 +14,22 @@ import pytest
 import torch
 
 from sqair_amd import _capi
-from sqair_amd.data import make_sequences, to_float
-from sqair_amd.flags import make_flags
-from sqair_amd.model import SqairCore
 from sqair_amd.stream import SqairStream
 from sqair_amd.train import StreamTrainer
-from oracle import sqair_oracle as O
-from tests import tbptt_ref as TR
-from tests.hip_util import MARGIN, draw_noise, params32, presence_margins
-from tests.test_hip_backward import _check_report
+from tests.stream_cases import ORACLE_HW as HW, chunk_two_case
+from tests.stream_harness import OUTS, chunks as _chunks, core, gclose, noise as _noise, train_setup, train_step
 
 pytestmark = pytest.mark.gpu
 
-HW = (32, 40)
 LSTM = dict(time_transition="LSTM", prior_transition="LSTM")
-OUTS = ("what", "where", "presence", "obj_id", "log_weights_per_timestep")
 
 
-def _setup(flags, B, T, seed=19, options=None, edits=None):
-    F = make_flags(learning_rate=0.0, **flags)   # (lr 0: the parameters are held, the optimiser step changes nothing)
-    obs = to_float(make_sequences(B, T=T, canvas=HW, n_objects=(1, 2), obj_size=10, seed=seed)["imgs"])
-    P = params32(F, HW, 3, 0.05, obs.mean((0, 1)))
-    if edits:   # names of tests/latent_regimes.EDITS (tests/test_regime_paths.py)
-        from tests import latent_regimes
-        P = latent_regimes.apply_edits(P, F, edits)
-    return F, obs, P
+def _setup(flags, B, T, seed=19):
+    return train_setup(flags, B, T, HW, seed)
 
 
 def _core(F, P, options=None):
-    core = SqairCore(F, HW, options=options)
-    core.set_params(P)
-    return core
-
-
-def _noise(F, rng, T, R):
-    return draw_noise(rng, T, R, int(F.n_steps_per_image), 4 + int(F.n_what) + 1)
-
-
-def _step(tr, *args, **kw):
-    """StreamTrainer.step is asynchronous on its core's stream: wait for it, return the gradient on the host."""
-    g = tr.step(*args, **kw)
-    torch.cuda.synchronize()
-    return g.cpu().numpy()
-
-
-def _gclose(got, want, tol):
-    got, want = np.asarray(got), np.asarray(want)
-    err = float(np.abs(got - want).max())
-    assert err <= tol * float(np.abs(want).max()), (err, float(np.abs(want).max()))
+    return core(F, HW, P, options)
 
 
 def test_fresh_carry_is_the_plain_step():
@@ -84,7 +52,7 @@ def test_fresh_carry_is_the_plain_step():
     core.stream.synchronize()
     for k in o0:
         assert torch.equal(o0[k], o1[k]), k
-    _gclose(g1.cpu().numpy(), g0.cpu().numpy(), 1e-5)
+    gclose(g1.cpu().numpy(), g0.cpu().numpy(), 1e-5)
     # the inference pass over the same frames and noise exports the same blob
     core.check(core.lib.sqair_set_state(core.handle, None, blob_inf.data_ptr(), None, nbytes, B), "sqair_set_state")
     with core.on_stream():
@@ -104,77 +72,9 @@ ORACLE_CASES = {
 }
 
 
-def _stable(orc, frames, K, state, rng, F, R, T, grad):
-    for _ in range(8):   # the oracle's own presence margin decides; the device is not looked at
-        noise = _noise(F, rng, T, R)
-        if grad:
-            target, out, st = TR.chunk_target(orc, frames, noise, K, state)
-        else:
-            with torch.no_grad():
-                target, out, st = TR.chunk_target(orc, frames, noise, K, state)
-        if float(presence_margins(out, noise).min()) >= MARGIN:
-            return noise, target, out, st
-    raise AssertionError("no decision-stable noise draw")
-
-
 @pytest.mark.parametrize("case", sorted(ORACLE_CASES))
 def test_chunk_two_matches_the_fp64_oracle(case):
-    _chunk_two_case(*ORACLE_CASES[case])
-
-
-def _chunk_two_case(flags, path, smc, require=None, edits=None):
-    """require(out1, out2): a condition on the ORACLE's outputs of the two chunks (what the case is meant to reach), checked before
-    the device runs chunk 2."""
-    B, T = 3, 3
-    F, obs, P = _setup(flags, B, 2 * T, seed=23, edits=edits)
-    K = int(F.k_particles)
-    R = B * K
-    core = _core(F, P)
-    if path:
-        assert core.lib is _capi.lib(path)
-    tr = StreamTrainer(core, F, B, frames_per_step=T, use_graph=False, collective=False,
-                       resample="systematic" if smc else None, outputs=("presence", "obj_id"))
-    orc = O.SqairOracle(P, O.make_cfg(F, HW), torch.float64, requires_grad=True)
-    rng = np.random.default_rng(11)
-    # chunk 1: every row fresh, on both
-    noise1, _, out1, st1 = _stable(orc, obs[:T], K, None, rng, F, R, T, grad=False)
-    tr.step(obs[:T], noise=noise1)
-    torch.cuda.synchronize()
-    for k in ("presence", "obj_id"):
-        assert np.array_equal(core.out[k].cpu().numpy(), out1[k].numpy().astype(np.float32)), k
-    # chunk 2: imported rows (through the resampler's ancestors with SMC), one lane reset
-    src = tr.ancestors.cpu().numpy().astype(np.int64) if smc else np.arange(R)
-    tr.reset([B - 1])
-    src[(B - 1) * K:] = -1
-    st2 = orc.gather_state(st1, src)
-    assert (st2.t.numpy()[:(B - 1) * K] >= 1).all()                 # imported counters
-    noise2, target, out2, _ = _stable(orc, obs[T:], K, st2, rng, F, R, T, grad=True)
-    assert out2["prop_pres"][0].detach().numpy()[:(B - 1) * K].any()          # present objects propagated at the chunk's first frame
-    if require is not None:
-        require(out1, out2)
-    for p in orc.P.values():
-        p.grad = None
-    target.backward()
-    tr.step(obs[T:], noise=noise2)
-    torch.cuda.synchronize()
-    for k in ("presence", "obj_id"):
-        assert np.array_equal(core.out[k].cpu().numpy(), out2[k].detach().numpy().astype(np.float32)), k
-    report = []
-    for name, g in core.grads_by_name().items():
-        want = orc.P[name].grad
-        g = g.cpu().numpy()
-        want = np.zeros_like(g) if want is None else want.numpy().reshape(g.shape)
-        report.append((name, float(np.abs(g - want).max()), float(np.abs(want).max())))
-    names = {n for n, _, s in report if s > 0}
-    for n in ("disc.step_prior_timestep_bias", "seq.temporal_init", "seq.prior_init"):
-        assert any(m.startswith(n) for m in names), n
-    _check_report(report)
-
-
-def _chunks(F, obs, B, T, n, seed=5):
-    rng = np.random.default_rng(seed)
-    R = B * int(F.k_particles)
-    return [(obs[i * T:(i + 1) * T], _noise(F, rng, T, R)) for i in range(n)]
+    chunk_two_case(*ORACLE_CASES[case])
 
 
 def test_chunked_training_is_streaming_and_hands_over():
@@ -188,7 +88,7 @@ def test_chunked_training_is_streaming_and_hands_over():
         if i == 2:
             tr.reset([1])
             st.reset([1])
-        _step(tr, fr, noise=nz)
+        train_step(tr, fr, noise=nz)
         got = {k: tr.core.out[k].clone() for k in OUTS}
         want = st.step(fr, noise=nz)
         torch.cuda.synchronize()
@@ -219,7 +119,7 @@ def test_smc_ancestors_and_evidence():
     moved = 0
     for fr, nz in chunks:
         u = rng.uniform(size=B).astype(np.float32)
-        _step(tr, fr, noise=nz, uniforms=u)
+        train_step(tr, fr, noise=nz, uniforms=u)
         elbo += tr.core.elbo_iwae_per_example.cpu().numpy().astype(np.float64)
         anc = tr.ancestors.clone()
         want = st.step(fr, noise=nz, uniforms=u)
@@ -247,9 +147,9 @@ def test_graph_replay_equals_eager_and_node_budget(smc):
             tg.reset([0])
             te.reset([0])
         u = np.full(B, 0.37, np.float32) if smc else None
-        a = _step(tg, fr, noise=nz, uniforms=u)
-        b = _step(te, fr, noise=nz, uniforms=u)
-        _gclose(a, b, 1e-5)
+        a = train_step(tg, fr, noise=nz, uniforms=u)
+        b = train_step(te, fr, noise=nz, uniforms=u)
+        gclose(a, b, 1e-5)
         assert torch.equal(tg.state, te.state), i
     # the plain step of the same shape and outputs, captured the same way
     plain = _core(F, P)
@@ -269,10 +169,10 @@ def test_slot_chain_carried_gradient():
     ta = StreamTrainer(_core(F, P, options={"slot_chain": 1}), F, B, frames_per_step=T, collective=False)
     tb = StreamTrainer(_core(F, P), F, B, frames_per_step=T, collective=False)
     for fr, nz in chunks:
-        a = _step(ta, fr, noise=nz)
-        b = _step(tb, fr, noise=nz)
+        a = train_step(ta, fr, noise=nz)
+        b = train_step(tb, fr, noise=nz)
         ta.core.check_chain(train=True)
-        _gclose(a, b, 1e-5)
+        gclose(a, b, 1e-5)
         assert torch.equal(ta.state, tb.state)
 
 
@@ -285,9 +185,9 @@ def test_two_shards_average_to_the_full_batch():
     full = StreamTrainer(_core(F, P), F, B, frames_per_step=T, collective=False)
     shards = [StreamTrainer(_core(F, P), F, B // 2, frames_per_step=T, collective=False) for _ in range(2)]
     for fr, nz in chunks:
-        g = _step(full, fr, noise=nz)
+        g = train_step(full, fr, noise=nz)
         gs = []
         for j, sh in enumerate(shards):
             lanes, rows = slice(j * B // 2, (j + 1) * B // 2), slice(j * B // 2 * K, (j + 1) * B // 2 * K)
-            gs.append(_step(sh, fr[:, lanes], noise=nz[:, rows]))
-        _gclose((gs[0] + gs[1]) / 2, g, 2e-4)
+            gs.append(train_step(sh, fr[:, lanes], noise=nz[:, rows]))
+        gclose((gs[0] + gs[1]) / 2, g, 2e-4)

@@ -2,26 +2,14 @@
 the symbols and every refusal.  All of them are decided before any HIP call, so dummy device pointers are enough and no GPU is
 needed."""
 import ctypes as C
-import functools
 
 import pytest
 
 from sqair_amd import _capi
-from tests.abi_host import BIG, DUMMY, LIBS, err as _err, fields as header_fields, functions, fwd_args, handle, smc
+from tests.abi_host import (BIG, CARRY_B as B, DUMMY, LIBS, OTHER, carry as _carry, err as _err, fields as header_fields, functions, fwd_args,
+                            handle, train_smc)
 
 NEW = ("sqair_forward_train_carry", "sqair_backward_carry")
-OTHER = C.c_void_p(0x2000)
-B = 4
-_smc = functools.partial(smc, ess_frac=1.0)      # (training resamples at every frame)
-
-
-def _carry(lib, h, smc=None, **kw):
-    f = dict(state_in=DUMMY.value, state_out=DUMMY.value, src_rows=DUMMY.value, state_bytes=lib.sqair_state_bytes(h, B), B=B)
-    f.update(kw)
-    c = _capi.SqairCarry(**f)
-    if smc is not None:
-        c.smc = C.pointer(smc)
-    return c
 
 
 def _calls(lib, h, carry, lw=True, b=B):
@@ -68,13 +56,13 @@ def test_carry_refusals(path, flags):
         refused(_carry(lib, h), ["B = 5", "B = 4"], b=B + 1)
         refused(_carry(lib, h, state_bytes=lib.sqair_state_bytes(h, B) - 4), ["state_bytes"])
         refused(_carry(lib, h, state_in=None), ["state_in"])
-        refused(_carry(lib, h, smc=_smc(ess_frac=0.5)), ["ess_frac"])
-        refused(_carry(lib, h, smc=_smc(ess_frac=0.0)), ["ess_frac"])
+        refused(_carry(lib, h, smc=train_smc(ess_frac=0.5)), ["ess_frac"])
+        refused(_carry(lib, h, smc=train_smc(ess_frac=0.0)), ["ess_frac"])
         for k in ("log_w", "log_z", "log_evidence", "ess", "resampled", "src_rows"):
-            refused(_carry(lib, h, smc=_smc(**{k: None})), ["NULL"])
-        refused(_carry(lib, h, smc=_smc(src_rows=OTHER.value)), ["src_rows"])
+            refused(_carry(lib, h, smc=train_smc(**{k: None})), ["NULL"])
+        refused(_carry(lib, h, smc=train_smc(src_rows=OTHER.value)), ["src_rows"])
         # the forward with SMC needs the log weights it resamples on (the backward has no outputs)
-        f, fe, g, ge = _calls(lib, h, _carry(lib, h, smc=_smc()), lw=False)
+        f, fe, g, ge = _calls(lib, h, _carry(lib, h, smc=train_smc()), lw=False)
         assert f == -1 and "log_weights_per_timestep" in fe
         # a handle that carries an inference state: the two registrations never mix
         assert lib.sqair_set_state(h, DUMMY, DUMMY, None, lib.sqair_state_bytes(h, B), B) == 0

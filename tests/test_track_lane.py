@@ -15,19 +15,14 @@ import numpy as np
 import pytest
 import torch
 
-from sqair_amd.data import make_sequences, to_float
-from sqair_amd.flags import make_flags
-from sqair_amd.model import SqairCore
 from sqair_amd.stream import SqairStream
 from tests import history_ref as H
 from tests import track_lane_check as TC
 from tests import track_lane_ref as TL
-from tests.hip_util import draw_noise, params32
+from tests.stream_harness import FIELD_OF, OUTS, core, host, setup
 
 pytestmark = pytest.mark.gpu
 
-OUTS = ("what", "where", "presence", "obj_id", "log_weights_per_timestep")
-FIELD_OF = dict(where="where", presence="presence", obj_id="obj_id", what="what", log_w="log_weights_per_timestep")
 HW = (50, 50)
 N = 3
 IOU = 0.5
@@ -36,22 +31,11 @@ B, STEPS, L = 3, 6, 4                                                         # 
 
 
 def _setup(K, T, seed=11):
-    F = make_flags(k_particles=K, n_steps_per_image=N)
-    obs = to_float(make_sequences(B, T=T, canvas=HW, seed=seed)["imgs"])
-    P = params32(F, HW, 3, 0.05, obs.mean((0, 1)))
-    noise = draw_noise(np.random.default_rng(seed + 1), T, B * K, N, 4 + int(F.n_what) + 1)
-    return F, P, obs, noise
+    return setup(dict(k_particles=K, n_steps_per_image=N), B, T, HW, seed)
 
 
 def _core(F, P):
-    core = SqairCore(F, HW)
-    core.set_params(P)
-    return core
-
-
-def _host(out):
-    torch.cuda.synchronize()
-    return {k: (_host(v) if isinstance(v, dict) else v.cpu().numpy()) for k, v in out.items()}
+    return core(F, HW, P)
 
 
 def _next_rows(st):
@@ -78,7 +62,7 @@ def _drive(K, Tp=1, missing=False, use_graph=True, ess_frac=0.5, check=True):
         """What tracks(lane=True) and forecast(lane=True) say between the same two steps."""
         nxt, lw = _next_rows(st)
         for lag in (2, L):
-            got = _host(st.tracks(lag=lag, lane=True, lane_iou=IOU, table=False))
+            got = host(st.tracks(lag=lag, lane=True, lane_iou=IOU, table=False))
             out.append(got)
             if not check:
                 continue
@@ -98,7 +82,7 @@ def _drive(K, Tp=1, missing=False, use_graph=True, ess_frac=0.5, check=True):
             totals["objects"] += int((lane["presence"] != 0).sum())
             totals["born_inside"] += int(((lane["first_frame"] > 0) & (lane["presence"] != 0)).sum())
         # ---- concatenation with the forecast taken between the same two steps
-        fc = _host(st.forecast(3, samples=4, lane=True, lane_iou=IOU, outputs=("presence",)))["lane"]
+        fc = host(st.forecast(3, samples=4, lane=True, lane_iou=IOU, outputs=("presence",)))["lane"]
         for name in SHARED:
             assert H.same_bits(got["lane"][name], fc[name]), (name, s, got["lane"][name], fc[name])
         out.append({k: fc[k] for k in SHARED})
@@ -108,7 +92,7 @@ def _drive(K, Tp=1, missing=False, use_graph=True, ess_frac=0.5, check=True):
         step_kw = dict(noise=noise[s * Tp:(s + 1) * Tp], uniforms=rng.uniform(size=B).astype(np.float32))
         if missing:
             step_kw["observed"] = rng.uniform(size=(Tp, B)) < 0.6 if s not in (0, 3) else np.ones((Tp, B), bool)
-        o = _host(st.step(obs[s * Tp:(s + 1) * Tp], **step_kw))
+        o = host(st.step(obs[s * Tp:(s + 1) * Tp], **step_kw))
         rec.push(parent, **{k: o[v] for k, v in FIELD_OF.items()})
         look(s)
         if s == 2:                             # lane 1 starts a new clip at step 3: its next rows are fresh, it has no past and no objects
@@ -150,14 +134,14 @@ def test_lane_tracks_between_steps_change_nothing():
     b = SqairStream(_core(F, P), B, outputs=OUTS, history=4, **kw)
     for t in range(T):
         b.tracks(lag=1 + t % 4, lane=True)
-        oa, ob = _host(a.step(obs[t:t + 1], noise=noise[t:t + 1])), _host(b.step(obs[t:t + 1], noise=noise[t:t + 1]))
+        oa, ob = host(a.step(obs[t:t + 1], noise=noise[t:t + 1])), host(b.step(obs[t:t + 1], noise=noise[t:t + 1]))
         assert set(oa) == set(ob)
         for k in oa:
             assert H.same_bits(oa[k], ob[k]), (k, t)
         for n in ("state", "log_weight_sum", "log_z", "log_evidence", "ess", "u", "resampled", "_src"):
             assert H.same_bits(getattr(a, n).cpu().numpy(), getattr(b, n).cpu().numpy()), (n, t)
     # the two calls share the ring's trace scratch and nothing else: a plain trace after a lane trace is still the plain trace
-    lane, plain = _host(b.tracks(lag=3, lane=True, table=False)), _host(b.tracks(lag=3, table=False))
+    lane, plain = host(b.tracks(lag=3, lane=True, table=False)), host(b.tracks(lag=3, table=False))
     for k in plain:
         assert H.same_bits(lane[k], plain[k]), k
     assert "lane" in lane and "lane" not in plain

@@ -15,12 +15,8 @@ import pytest
 import torch
 
 from sqair_amd import _capi
-from sqair_amd.data import make_sequences, to_float
-from sqair_amd.flags import make_flags
-from sqair_amd.model import SqairCore
-from sqair_amd.stream import SqairStream
 from tests import traj_score_ref as R
-from tests.hip_util import draw_noise, params32
+from tests.stream_harness import OUTS, host, same_bits, setup, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -30,51 +26,24 @@ STEPS, FH, S, LAG = 8, 4, 4, 6
 IOU = 0.5
 
 
-def _host(res):
-    torch.cuda.synchronize()
-    return {k: (_host(v) if isinstance(v, dict) else v.cpu().numpy()) for k, v in res.items()}
-
-
-def _bits(a):
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def _same_bits(a, b, where=""):
-    assert set(a) == set(b), (where, set(a) ^ set(b))
-    for k in a:
-        if isinstance(a[k], dict):
-            _same_bits(a[k], b[k], where + k + ".")
-        else:
-            assert np.array_equal(_bits(a[k]), _bits(b[k])), where + k
-
-
 @pytest.fixture(scope="module")
 def stepped():
     """A scored SMC stream with a history after eight steps (its steps scored against a truth made from an unscored run of the same
     seeds, so that the identity memory is filled), and the last step's truth."""
-    F = make_flags(k_particles=K, n_steps_per_image=N)
-    obs = to_float(make_sequences(B, T=STEPS, canvas=HW, seed=11)["imgs"])
-    P = params32(F, HW, 3, 0.05, obs.mean((0, 1)))
-    noise = draw_noise(np.random.default_rng(12), STEPS, B * K, N, 4 + int(F.n_what) + 1)
-    kw = dict(outputs=("what", "where", "presence", "obj_id", "log_weights_per_timestep"), estimate=True, estimate_iou=IOU,
-              resample="systematic", ess_frac=0.5, seed=5, history=8)
-
-    def stream(**more):
-        core = SqairCore(F, HW)
-        core.set_params(P)
-        return SqairStream(core, B, **kw, **more)
-    first = stream()
+    F, P, obs, noise = setup(dict(k_particles=K, n_steps_per_image=N), B, STEPS, HW)
+    kw = dict(outputs=OUTS, estimate=True, estimate_iou=IOU, resample="systematic", ess_frac=0.5, seed=5, history=8)
+    first = stream((F, HW, P), B, **kw)
     rng = np.random.default_rng(7)
     truths = []
     for t in range(STEPS):
-        lane = _host(first.step(obs[t:t + 1], noise=noise[t:t + 1]))["lane"]
+        lane = host(first.step(obs[t:t + 1], noise=noise[t:t + 1]))["lane"]
         box, present = np.zeros((1, B, G, 4), np.float32), np.zeros((1, B, G), np.int32)
         for j in range(N):
             box[0, :, j + 1] = lane["box"][0, :, j] + rng.standard_normal((B, 4))
             present[0, :, j + 1] = lane["presence"][0, :, j] != 0
         truths.append(dict(box=box, present=present))
     first.close()
-    st = stream(score=True, score_iou=IOU, score_truth=G)
+    st = stream((F, HW, P), B, score=True, score_iou=IOU, score_truth=G, **kw)
     for t in range(STEPS):
         st.step(obs[t:t + 1], noise=noise[t:t + 1], truth=truths[t])
     yield st, truths[-1]
@@ -160,14 +129,14 @@ def test_the_score_equals_the_reference_and_changes_nothing_else(stepped, kind):
     st, _ = stepped
     st._traj.clear()
     F = FRAMES[kind]
-    plain = _host(CALLS[kind](st))
+    plain = host(CALLS[kind](st))
     assert "score" not in plain["lane"] and not st._traj                # without truth nothing is launched, nothing is kept
     truth = _make_truth(plain["lane"], F, 21, kind == "tracks")
     if kind == "tracks":                                                # the anchor defaults to the newest frame
         truth = {n: v for n, v in truth.items() if not n.startswith("anchor")}
-    got = _host(CALLS[kind](st, truth=truth))
+    got = host(CALLS[kind](st, truth=truth))
     score = got["lane"].pop("score")
-    _same_bits(plain, got)                                              # every other output: the same bits
+    same_bits(plain, got)                                              # every other output: the same bits
     if kind == "tracks":
         truth = dict(truth, anchor_box=truth["box"][-1], anchor_present=truth["present"][-1], anchor_valid=truth["valid"][-1])
     ref, bar = _reference(got["lane"], truth)
@@ -185,8 +154,8 @@ def test_the_score_equals_the_reference_and_changes_nothing_else(stepped, kind):
     # the accumulators after one call, after a second one, and after reset=True
     one = st.trajectory_score(kind)
     _check_accumulated(one, ref, bar, 1)
-    again = _host(CALLS[kind](st, truth=truth))
-    _same_bits(dict(got, lane=dict(got["lane"], score=score)), again)
+    again = host(CALLS[kind](st, truth=truth))
+    same_bits(dict(got, lane=dict(got["lane"], score=score)), again)
     ref2, _ = _reference(got["lane"], truth, acc=dict(counts=ref.counts, sums=ref.sums, lane_counts=ref.lane_counts))
     assert np.array_equal(ref2.counts, 2 * ref.counts)
     two = st.trajectory_score(kind, reset=True)
@@ -208,11 +177,11 @@ def test_truth_equal_to_the_table_gives_iou_one_and_error_zero(stepped, kind):
     st, _ = stepped
     st._traj.clear()
     F = FRAMES[kind]
-    lane = _host(CALLS[kind](st))["lane"]
+    lane = host(CALLS[kind](st))["lane"]
     living = (lane["alive"] > 0) & (lane["presence"] != 0)[None]
     truth = dict(box=np.where(living[..., None], lane["box_mean"], 0.0).astype(np.float32), present=living.astype(np.int32),
                  anchor_box=lane["box0"], anchor_present=(lane["presence"] != 0).astype(np.int32))
-    score = _host(CALLS[kind](st, truth=truth))["lane"]["score"]
+    score = host(CALLS[kind](st, truth=truth))["lane"]["score"]
     want = np.where(lane["presence"] != 0, np.arange(N)[None], -1)
     assert np.array_equal(score["link"], want) and (score["link_iou"][want >= 0] == 1.0).all()
     pairs = score["state"] == 1
@@ -229,15 +198,15 @@ def test_truth_equal_to_the_table_gives_iou_one_and_error_zero(stepped, kind):
 def test_tracks_and_forecast_between_the_same_two_steps_give_the_same_link(stepped):
     st, _ = stepped
     st._traj.clear()
-    tk = _host(CALLS["tracks"](st))["lane"]
-    fc = _host(CALLS["forecast"](st))["lane"]
-    _same_bits({n: tk[n] for n in ("obj_id", "presence", "box0")}, {n: fc[n] for n in ("obj_id", "presence", "box0")})
+    tk = host(CALLS["tracks"](st))["lane"]
+    fc = host(CALLS["forecast"](st))["lane"]
+    same_bits({n: tk[n] for n in ("obj_id", "presence", "box0")}, {n: fc[n] for n in ("obj_id", "presence", "box0")})
     t_tk, t_fc = _make_truth(tk, LAG, 33, True), _make_truth(fc, FH, 34, False)
     for n in ("anchor_box", "anchor_present"):                          # one anchor for both
         t_fc[n] = t_tk[n]
-    a = _host(CALLS["tracks"](st, truth=t_tk))["lane"]["score"]
-    b = _host(CALLS["forecast"](st, truth=t_fc))["lane"]["score"]
-    _same_bits({n: a[n] for n in ("link", "link_iou")}, {n: b[n] for n in ("link", "link_iou")})
+    a = host(CALLS["tracks"](st, truth=t_tk))["lane"]["score"]
+    b = host(CALLS["forecast"](st, truth=t_fc))["lane"]["score"]
+    same_bits({n: a[n] for n in ("link", "link_iou")}, {n: b[n] for n in ("link", "link_iou")})
     assert (a["link"] >= 0).any() and (a["link"] == -1).any()
     both = (st.trajectory_score("tracks"), st.trajectory_score("forecast"))      # each kind keeps accumulators of its own
     assert both[0]["frames"].shape == (LAG, B) and both[1]["frames"].shape == (FH, B)
@@ -249,12 +218,12 @@ def test_link_ids_keeps_a_truth_with_the_identity_the_score_last_matched(stepped
     st._traj.clear()
     memory = st._score["last_id"].cpu().numpy()
     assert (memory >= 0).any()
-    lane = _host(CALLS["forecast"](st))["lane"]
+    lane = host(CALLS["forecast"](st))["lane"]
     truth = _make_truth(lane, FH, 41, False)
     truth["anchor_box"], truth["anchor_present"] = last["box"][0], last["present"][0]      # the truth of the last stepped frame
     for keep, kw in ((None, {}), (memory, dict(link_ids=True))):
         st._traj.clear()
-        score = _host(CALLS["forecast"](st, truth=truth, **kw))["lane"]["score"]
+        score = host(CALLS["forecast"](st, truth=truth, **kw))["lane"]["score"]
         ref, bar = _reference(lane, truth, keep)
         _check(score, ref, bar)
         assert (ref.link >= 0).any()
