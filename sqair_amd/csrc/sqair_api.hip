@@ -680,6 +680,8 @@ Workspace sq_carve(const SqairHandle* h, int T, int B, float* base, bool train) 
   w.snh = (int)snh;
   const int64_t psnh = c.prior_cell == CELL_LSTM ? 2 * nh : nh;
   w.psnh = (int)psnh;
+  w.G2 = (int)G2;
+  w.pgw = (int)(c.prior_cell == CELL_LSTM ? 4 * nh : nh);   // GRU: z gate; LSTM: the four gate pre-activations
   int64_t o = 0;
   auto take = [&](int64_t n) {
     float* p = base ? base + o : nullptr;
@@ -709,7 +711,7 @@ Workspace sq_carve(const SqairHandle* h, int T, int B, float* base, bool train) 
   w.w3_disc = take(nh * 8 + 8);
   w.temporal_p = take(F * M * snh);
   w.prior_p = take(F * M * psnh);
-  w.pgz = take(F * M * ((c.prior_cell == CELL_LSTM) ? 4 * nh : nh));  // GRU: z gate; LSTM: the four gate pre-activations
+  w.pgz = take(F * M * w.pgw);
   w.pgr = take(F * M * nh);
   w.pghc = take(F * M * nh);
   w.pgrh = take(M * nh);
@@ -768,6 +770,23 @@ Workspace sq_carve(const SqairHandle* h, int T, int B, float* base, bool train) 
   w.total = o;
   return w;
 }
+// Frame t of the workspace: every per-frame stride M * X below is the X of sq_carve's take(F * M * X) above (pstats and spre are
+// always [T]; the merged states ping-pong without a tape: Workspace::state)
+Workspace::Frame Workspace::at(int t) const {
+  const int64_t m = M;
+  Frame f;
+  f.rec_prev = rec_m_all + (size_t)t * m * rec::W; f.rec_next = f.rec_prev + m * rec::W;
+  f.rec_p = rec_p_all + (size_t)t * m * rec::W; f.rec_d = rec_d_all + (size_t)t * m * rec::W;
+  f.pstats = pstats + (size_t)t * m * PS_LD; f.spre = spre + (size_t)t * R * 128;
+  f.temporal_prev = state(temporal_m, t, snh); f.temporal_next = state(temporal_m, t + 1, snh);
+  f.prior_prev = state(prior_m, t, psnh); f.prior_next = state(prior_m, t + 1, psnh);
+  f.temporal_p = frame(temporal_p, m * snh, t); f.prior_p = frame(prior_p, m * psnh, t);
+  f.pgz = frame(pgz, m * pgw, t); f.pgr = frame(pgr, m * nh, t); f.pghc = frame(pghc, m * nh, t);
+  f.hid1 = frame(hid1, m * 256, t); f.wb = frame(wb, m * WB_LD, t); f.mask = frame(mask, m * G2, t); f.g1 = frame(g1, m * G2, t);
+  f.pea = frame(pea, m * nh, t); f.peb = frame(peb, m * nh, t); f.m1 = frame(m1, m * M1_LD, t);
+  f.lea = frame(lea, m * nh, t); f.leb = frame(leb, m * nh, t); f.c = frame(c, (int64_t)R * nh, t);
+  return f;
+}
 static Workspace carve(const SqairHandle* h, int T, int B, float* base) { return sq_carve(h, T, B, base, false); }
 
 extern "C" int64_t sqair_workspace_bytes(const SqairHandle* h, int T, int B) {
@@ -803,6 +822,24 @@ int sq_run(SqairHandle* h, Lin& l, LayerId id, int M, const float* packed, hipSt
   if (sq_chain_active(h)) return sq_chain_add_dense(h, l.a, L.kc, L.nt);   // collected into the chain launch (sqair_chain.h)
   const int rc = sq_launch_linear(l.a, L, s);
   if (rc != 0) sq_set_error(h, "internal: A-operand contract (16-byte aligned, ld % 4 == 0) violated in layer " + std::to_string((int)id));
+  return rc;
+}
+
+int sq_run_dx(SqairHandle* h, Dx& x, int M, const float* packed, hipStream_t s, const float* scale_ptr) {
+  const PackedLayer &L = h->layers[x.id], &LT = h->layersT[x.id];
+  const PackedLayout pl = packed_layout(h);
+  auto refuse = [&](const char* what) { sq_set_error(h, std::string("internal: ") + what + " in dX of layer " + std::to_string((int)x.id)); return -3; };
+  if (x.a.nranges < 1 || x.a.nranges > Dx::MAXR) return refuse("range count out of bounds");
+  for (int i = 0; i < x.a.nranges; ++i) {
+    bool is_seg = false;
+    for (int j = 0, n0 = 0; j < (int)L.seg_width.size(); n0 += (L.seg_width[j] + 15) / 16 * 16, ++j)
+      is_seg = is_seg || (x.a.r[i].n0 == n0 && x.a.r[i].n1 == n0 + L.seg_width[j]);
+    if (!is_seg) return refuse("a range that is no segment");
+  }
+  if (x.a.width != L.N || x.a.ld < L.N) return refuse("pre-activation gradient width mismatch");
+  x.a.wp = packed + pl.w + LT.w_off; x.a.wzero = packed + pl.w; x.a.scale_ptr = scale_ptr; x.a.M = M;
+  const int rc = sq_launch_linear_dx(x.a, LT.kc, LT.nt, s);
+  if (rc != 0) sq_set_error(h, "internal: A-operand contract violated in dX of layer " + std::to_string((int)x.id));
   return rc;
 }
 
@@ -895,7 +932,8 @@ SQ_LOCAL CropArgs sq_crop_args(const CropOperands& o) {
 // slots a crop launch covers (the grid's y): crop #1 all N of a row, crop #2 its one
 SQ_LOCAL int sq_crop_slots(int mode, const Dims& d) { return mode == CROP_PROP1 ? d.N : 1; }
 // Dims of the pass's launches for B sequences: frames whose H * W is not a multiple of 4 are read from a zero-padded copy of pitch P4
-// (made once in the prologue), and `spec` says which of the slot loop's kernels run in their specialised instantiations (sqair_glue.h)
+// (made once in the prologue), and `spec` says which of the slot loop's kernels run in their specialised instantiations (sqair_glue.h;
+// 0, as make_dims leaves it, for the backward pass and the adjoint unit entries: sq_pass_dims(h, B, 0))
 SQ_LOCAL Dims sq_pass_dims(const SqairHandle* h, int B, int spec_mask) {
   Dims d = make_dims(h->cfg, B);
   const int P_ = h->cfg.img_h * h->cfg.img_w;
@@ -1084,64 +1122,44 @@ SQ_LOCAL int sq_forward_impl(SqairHandle* h, const float* flat, const float* pac
     const int pp = t & 1, pn = pp ^ 1;
     const float* img = obs + (size_t)t * B * PL;
     const float* nz = noise + (size_t)t * R * 2 * N * nzw;
-    const float* rec_prev = w.rec_m_all + (size_t)t * M * RW;
-    float* rec_next = w.rec_m_all + (size_t)(t + 1) * M * RW;
-    float* rec_p_t = w.rec_p_all + (size_t)t * M * RW;
-    float* rec_d_t = w.rec_d_all + (size_t)t * M * RW;
-    float* pstats_t = w.pstats + (size_t)t * M * PS_LD;
-    float* spre_t = w.spre + (size_t)t * R * 128;
-    const float* temporal_prev = w.state(w.temporal_m, t, w.snh);
-    const float* prior_prev = w.state(w.prior_m, t, w.psnh);
-    float* temporal_p = w.frame(w.temporal_p, (int64_t)M * snh, t);
-    const float* tau_prev = temporal_prev + d.toff;  // what the slot networks read as "temporal state" (core.py:284): the
-                                                     // GRU state / the CELL half of an LSTM state, row stride snh
-    float* prior_p = w.frame(w.prior_p, (int64_t)M * psnh, t);
-    float* hid1 = w.frame(w.hid1, (int64_t)M * 256, t);
-    float* wb = w.frame(w.wb, (int64_t)M * WB_LD, t);
-    float* mask = w.frame(w.mask, (int64_t)M * G2, t);
-    float* g1 = w.frame(w.g1, (int64_t)M * G2, t);
-    float* pea = w.frame(w.pea, (int64_t)M * nh, t);
-    float* peb = w.frame(w.peb, (int64_t)M * nh, t);
-    float* m1 = w.frame(w.m1, (int64_t)M * M1_LD, t);
-    float* lea = w.frame(w.lea, (int64_t)M * nh, t);
-    float* leb = w.frame(w.leb, (int64_t)M * nh, t);
-    float* cvec = w.frame(w.c, (int64_t)R * nh, t);
+    const Workspace::Frame f = w.at(t);
+    const float* tau_prev = f.temporal_prev + d.toff;  // what the slot networks read as "temporal state" (core.py:284): the
+                                                       // GRU state / the CELL half of an LSTM state, row stride snh
 
     // ---- A. propagation prior (propagate.py:68-98): GRU over [what, where]_{t-1}, all slots ----
     {
-      const int rc = sq_prior_step(h, packed, s, M, rec_prev, prior_prev, prior_p,
-                                   w.frame(w.pgz, (int64_t)M * (c.prior_cell == CELL_LSTM ? 4 * nh : nh), t), w.pgrh, w.pgxh, pstats_t,
-                                   train ? w.frame(w.pgr, (int64_t)M * nh, t) : nullptr, train ? w.frame(w.pghc, (int64_t)M * nh, t) : nullptr);
+      const int rc = sq_prior_step(h, packed, s, M, f.rec_prev, f.prior_prev, f.prior_p,
+                                   f.pgz, w.pgrh, w.pgxh, f.pstats, train ? f.pgr : nullptr, train ? f.pghc : nullptr);
       if (rc != 0) return rc;
     }
     // ---- B. where-bias MLP and glimpse-mask MLP of every slot (core.py:292, modules.py:350-356) ----
     {
-      Lin a; a.seg(tau_prev, snh, nh).out(hid1, 256).act(ACT_ELU); RUN(a, L_TAU1, M);
-      Lin b; b.seg(hid1, 256, 128).out(wb, WB_LD); RUN(b, L_WB2, M);
-      Lin m; m.seg(hid1 + 128, 256, 128).out(mask, G2).act(ACT_SIGMOID); RUN(m, L_MASK2, M);
+      Lin a; a.seg(tau_prev, snh, nh).out(f.hid1, 256).act(ACT_ELU); RUN(a, L_TAU1, M);
+      Lin b; b.seg(f.hid1, 256, 128).out(f.wb, WB_LD); RUN(b, L_WB2, M);
+      Lin m; m.seg(f.hid1 + 128, 256, 128).out(f.mask, G2).act(ACT_SIGMOID); RUN(m, L_MASK2, M);
     }
     // ---- C. crop #1 at where_{t-1} + bias, masked, encoded -> loc1 (core.py:293-294) ----
     {
       CropOperands co; memset(&co, 0, sizeof(co));
-      co.mode = CROP_PROP1; co.img = img; co.mask = c.masked_glimpse ? mask : nullptr; co.mask_row_mul = N;
-      co.out = g1; co.out_row_mul = N; co.rec_prev = rec_prev; co.wb = wb; co.wb_ld = WB_LD; co.flat = flat;
+      co.mode = CROP_PROP1; co.img = img; co.mask = c.masked_glimpse ? f.mask : nullptr; co.mask_row_mul = N;
+      co.out = f.g1; co.out_row_mul = N; co.rec_prev = f.rec_prev; co.wb = f.wb; co.wb_ld = WB_LD; co.flat = flat;
       emit_crop(h, sq_crop_args(co), po, d, sq_crop_slots(CROP_PROP1, d), s);
-      Lin a; a.seg(g1, G2, G2).out(pea, nh).act(ACT_ELU); RUN(a, L_GENC0, M);
-      Lin b; b.seg(pea, nh, nh).out(peb, nh).act(ACT_ELU); RUN(b, L_GENC1, M);
-      Lin l; l.seg(peb, nh, nh).out(m1, M1_LD); RUN(l, L_WHAT_LOC, M);
+      Lin a; a.seg(f.g1, G2, G2).out(f.pea, nh).act(ACT_ELU); RUN(a, L_GENC0, M);
+      Lin b; b.seg(f.pea, nh, nh).out(f.peb, nh).act(ACT_ELU); RUN(b, L_GENC1, M);
+      Lin l; l.seg(f.peb, nh, nh).out(f.m1, M1_LD); RUN(l, L_WHAT_LOC, M);
     }
     // ---- D. loop-invariant pre-activations of all slots ----
     {
-      Lin p; p.seg(m1, M1_LD, nw).seg(rec_prev, RW, rec::ZW).seg(tau_prev, snh, nh).out(w.pre, pre_ld);
+      Lin p; p.seg(f.m1, M1_LD, nw).seg(f.rec_prev, RW, rec::ZW).seg(tau_prev, snh, nh).out(w.pre, pre_ld);
       RUN(p, L_PRE, M);
       if (c.time_cell == CELL_LSTM) {  // recurrent rows of the LSTM gates: h_{t-1} W_h + b of every slot
-        Lin q; q.seg(temporal_prev, snh, nh).out(w.lpre, 4 * nh); RUN(q, L_PROP_GRU2, M);
+        Lin q; q.seg(f.temporal_prev, snh, nh).out(w.lpre, 4 * nh); RUN(q, L_PROP_GRU2, M);
       }
     }
     // ---- the slot step of both slot loops ----
-    const SlotPhase prop = {0, L_PROP_RNN, L_PROP_RNN2, L_PROP_T1, L_PROP_T2, w.zero_rec, w.prop_rnn_init, rec_p_t,
+    const SlotPhase prop = {0, L_PROP_RNN, L_PROP_RNN2, L_PROP_T1, L_PROP_T2, w.zero_rec, w.prop_rnn_init, f.rec_p,
                             w.pre, pre_ld, N * pre_ld, w.pre + rw, w.w3_prop, fuse_prop};
-    const SlotPhase disc = {1, L_DISC_RNN, L_DISC_RNN2, L_DISC_T1, L_DISC_T2, w.disc_init_rec, w.disc_rnn_init, rec_d_t,
+    const SlotPhase disc = {1, L_DISC_RNN, L_DISC_RNN2, L_DISC_T1, L_DISC_T2, w.disc_init_rec, w.disc_rnn_init, f.rec_d,
                             w.pre_d, 0, rw, nullptr, w.w3_disc, fuse_disc};
     // slot RNN -> T1 -> T2 -> crop #2 (`co` arrives with the phase's own fields) -> glimpse encoder (the what head unless the
     // slot's what sample is fused into its own launch)
@@ -1204,7 +1222,7 @@ SQ_LOCAL int sq_forward_impl(SqairHandle* h, const float* flat, const float* pac
     auto slot_tail = [&](const SlotPhase& sp, int k, const float* hraw, int h_ld) {
       TailOperands io; memset(&io, 0, sizeof(io));
       io.is_disc = sp.ph; io.slot = k; io.hraw = hraw; io.h_ld = h_ld; io.enc = w.slot(w.enc, ENC_LD, t, sp.ph, k); io.enc_ld = w.sld(ENC_LD);
-      io.rec_prev = rec_prev; io.rec_new = sp.rec; io.noise = nz; io.s1p = w.slot(w.t1, T1_LD, t, sp.ph, k) + nh; io.s1p_ld = w.sld(T1_LD);
+      io.rec_prev = f.rec_prev; io.rec_new = sp.rec; io.noise = nz; io.s1p = w.slot(w.t1, T1_LD, t, sp.ph, k) + nh; io.s1p_ld = w.sld(T1_LD);
       if (train) { io.s1h_out = w.slot(w.s1h, S1_LD, t, sp.ph, k); io.s1h_ld = w.sld(S1_LD); }
       io.what_done = fw ? 1 : 0;
       const TailArgs ta = sq_tail_args(h, io, flat, packed);
@@ -1217,7 +1235,7 @@ SQ_LOCAL int sq_forward_impl(SqairHandle* h, const float* flat, const float* pac
     for (int k = 0; k < N; ++k) {
       {
         CropOperands co; memset(&co, 0, sizeof(co));
-        co.mode = CROP_PROP2; co.mask = c.masked_glimpse ? mask : nullptr; co.mask_row_mul = N; co.mask_row_add = k; co.rec_prev = rec_prev;
+        co.mode = CROP_PROP2; co.mask = c.masked_glimpse ? f.mask : nullptr; co.mask_row_mul = N; co.mask_row_add = k; co.rec_prev = f.rec_prev;
         const int rc = slot_front(prop, k, co, true);
         if (rc != 0) return rc;
       }
@@ -1231,33 +1249,33 @@ SQ_LOCAL int sq_forward_impl(SqairHandle* h, const float* flat, const float* pac
       if (c.time_cell == CELL_LSTM) {
         float* gates = train ? w.lgates + ((size_t)t * M + k) * 4 * nh : w.lgates;
         const int gld = train ? N * 4 * nh : 4 * nh;
-        Lin gl; gl.seg(r_k, rl, nh).seg(rec_p_t + (size_t)k * RW + rec::WHERE, N * RW, 4).seg(enc, el, 2 * nw)
+        Lin gl; gl.seg(r_k, rl, nh).seg(f.rec_p + (size_t)k * RW + rec::WHERE, N * RW, 4).seg(enc, el, 2 * nw)
                   .add(w.lpre + (size_t)k * 4 * nh, N * 4 * nh, 4 * nh).out(gates, gld);
         RUN(gl, L_PROP_GRU1, R);
-        sq_launch_lstm_cell(gates, gld, tau_prev + (size_t)k * snh, N * snh, temporal_p + (size_t)k * snh, N * snh, R, nh, s);
+        sq_launch_lstm_cell(gates, gld, tau_prev + (size_t)k * snh, N * snh, f.temporal_p + (size_t)k * snh, N * snh, R, nh, s);
       } else if (c.time_cell == CELL_VANILLA) {  // tau' = tanh(x W_i + [tau W_h + b, hoisted into `pre`]) in one launch
-        Lin g; g.seg(r_k, rl, nh).seg(rec_p_t + (size_t)k * RW + rec::WHERE, N * RW, 4).seg(enc, el, 2 * nw)
-                 .add(pre_k + rw + nh + nh / 2, pre_rld, nh).out(temporal_p + (size_t)k * nh, N * nh).act(ACT_TANH);
+        Lin g; g.seg(r_k, rl, nh).seg(f.rec_p + (size_t)k * RW + rec::WHERE, N * RW, 4).seg(enc, el, 2 * nw)
+                 .add(pre_k + rw + nh + nh / 2, pre_rld, nh).out(f.temporal_p + (size_t)k * nh, N * nh).act(ACT_TANH);
         RUN(g, L_PROP_GRU1, R);
       } else {
-        const float* tau_k = temporal_prev + (size_t)k * nh;
+        const float* tau_k = f.temporal_prev + (size_t)k * nh;
         float* grh_k = w.chain ? w.slot(w.grh, nh, t, 0, k) : w.grh;   // (the chain: every slot's hand-offs in their own buffers)
         float* gxh_k = w.chain ? w.slot(w.gxh, nh, t, 0, k) : w.gxh;
         const int grl = w.chain ? rl : nh;
-        Lin g1l; g1l.seg(r_k, rl, nh).seg(rec_p_t + (size_t)k * RW + rec::WHERE, N * RW, 4).seg(enc, el, 2 * nw)
+        Lin g1l; g1l.seg(r_k, rl, nh).seg(f.rec_p + (size_t)k * RW + rec::WHERE, N * RW, 4).seg(enc, el, 2 * nw)
                    .add(pre_k + rw + nh + nh / 2, pre_rld, 2 * nh).out(gz, rl)
                    .gru1(tau_k, N * nh, grh_k, grl, gxh_k, grl, nh);
         if (train) { g1l.a.o3 = w.slot(w.gr, nh, t, 0, k); g1l.a.o3_ld = rl; }
         RUN(g1l, L_PROP_GRU1, R);
-        Lin g2l; g2l.seg(grh_k, grl, nh).add(gxh_k, grl, nh).out(temporal_p + (size_t)k * nh, N * nh)
+        Lin g2l; g2l.seg(grh_k, grl, nh).add(gxh_k, grl, nh).out(f.temporal_p + (size_t)k * nh, N * nh)
                    .gru2(tau_k, N * nh, gz, rl, nh);
         if (train) { g2l.a.o1 = w.slot(w.ghc, nh, t, 0, k); g2l.a.o1_ld = rl; }
         RUN(g2l, L_PROP_GRU2, R);
       }
       // the heads on the slot's new temporal state (snh == nh unless the temporal cell is an LSTM): the what sample in the
       // layer's own launch, or the raw heads for the tail
-      if (fw) { const int rc = sq_run_what(h, 1, temporal_p + (size_t)k * snh, N * snh, R, k, nz, enc, el, rec_prev, rec_p_t, packed, s); if (rc != 0) return rc; }
-      else { Lin hd; hd.seg(temporal_p + (size_t)k * snh, N * snh, nh).out(hraw, hl); RUN(hd, L_PROP_HEADS, R); }
+      if (fw) { const int rc = sq_run_what(h, 1, f.temporal_p + (size_t)k * snh, N * snh, R, k, nz, enc, el, f.rec_prev, f.rec_p, packed, s); if (rc != 0) return rc; }
+      else { Lin hd; hd.seg(f.temporal_p + (size_t)k * snh, N * snh, nh).out(hraw, hl); RUN(hd, L_PROP_HEADS, R); }
       slot_tail(prop, k, hraw, hl);
     }
     if (w.chain) {
@@ -1268,19 +1286,19 @@ SQ_LOCAL int sq_forward_impl(SqairHandle* h, const float* flat, const float* pac
     const bool do_generate = c.sample_from_prior && c.generate_after > 0 && (t_offset + t) > c.generate_after;  // seq.py:198-200
     GenArgs ga; memset(&ga, 0, sizeof(ga));
     if (c.sample_from_prior) {
-      ga.rec_p = rec_p_t; ga.rec_d = rec_d_t; ga.rec_prev = rec_prev; ga.pstats = pstats_t; ga.ps_ld = PS_LD; ga.spre = spre_t;
+      ga.rec_p = f.rec_p; ga.rec_d = f.rec_d; ga.rec_prev = f.rec_prev; ga.pstats = f.pstats; ga.ps_ld = PS_LD; ga.spre = f.spre;
       ga.gen_noise = h->gen_noise + (size_t)t * R * 2 * N * nzw; ga.gen = w.gen + (size_t)t * M * gen::W; ga.flat = flat;
       ga.do_generate = do_generate ? 1 : 0; ga.cfg = c;
       sq_launch_generate_prop(ga, po, d, s);
     }
     // ---- F. summary of propagated latents -> discovery conditioning (sqair_modules.py:368-385, :501) ----
     {
-      Lin a; a.seg(rec_p_t, RW, rec::ZW).out(lea, nh).act(ACT_ELU); RUN(a, L_LAT0, M);
-      Lin b; b.seg(lea, nh, nh).out(leb, nh).act(ACT_ELU); RUN(b, L_LAT1, M);
-      sq_launch_latent_sum(leb, rec_p_t, cvec, d, s);
-      Lin p; p.seg(cvec, nh, nh).add(w.pre_disc + (size_t)t * B * rw, rw, rw, K).out(w.pre_d, rw); RUN(p, L_PRED, R);
+      Lin a; a.seg(f.rec_p, RW, rec::ZW).out(f.lea, nh).act(ACT_ELU); RUN(a, L_LAT0, M);
+      Lin b; b.seg(f.lea, nh, nh).out(f.leb, nh).act(ACT_ELU); RUN(b, L_LAT1, M);
+      sq_launch_latent_sum(f.leb, f.rec_p, f.c, d, s);
+      Lin p; p.seg(f.c, nh, nh).add(w.pre_disc + (size_t)t * B * rw, rw, rw, K).out(w.pre_d, rw); RUN(p, L_PRED, R);
       if (c.rec_where_prior) {
-        Lin q; q.seg(w.rn_init_state, 0, 4).seg(cvec, nh, nh).out(spre_t, 128); RUN(q, L_RNCOND, R);
+        Lin q; q.seg(w.rn_init_state, 0, 4).seg(f.c, nh, nh).out(f.spre, 128); RUN(q, L_RNCOND, R);
       }
     }
     // ---- G. discovery steps (sqair_modules.py:129-147 static_rnn over DiscoveryCore) ----
@@ -1293,7 +1311,7 @@ SQ_LOCAL int sq_forward_impl(SqairHandle* h, const float* flat, const float* pac
         if (rc != 0) return rc;
       }
       if (fw) {   // the Gaussian head writes the slot's what sample itself (`enc` has no other reader in a discovery slot)
-        const int rc = sq_run_what(h, 0, w.slot(w.e2, nh, t, 1, j), w.sld(nh), R, j, nz, nullptr, 0, nullptr, rec_d_t, packed, s);
+        const int rc = sq_run_what(h, 0, w.slot(w.e2, nh, t, 1, j), w.sld(nh), R, j, nz, nullptr, 0, nullptr, f.rec_d, packed, s);
         if (rc != 0) return rc;
       }
       slot_tail(disc, j, nullptr, 0);
@@ -1307,9 +1325,9 @@ SQ_LOCAL int sq_forward_impl(SqairHandle* h, const float* flat, const float* pac
     //      they run once for all T frames after the loop)
     {
       CompactArgs ka; memset(&ka, 0, sizeof(ka));
-      ka.rec_p = rec_p_t; ka.rec_d = rec_d_t; ka.rec_prev = rec_prev; ka.temporal_p = temporal_p;
-      ka.prior_p = prior_p; ka.last_id_prev = w.last_id[pp]; ka.last_id_next = w.last_id[pn];
-      ka.rec_next = rec_next; ka.temporal_next = w.state(w.temporal_m, t + 1, w.snh); ka.prior_next = w.state(w.prior_m, t + 1, w.psnh);
+      ka.rec_p = f.rec_p; ka.rec_d = f.rec_d; ka.rec_prev = f.rec_prev; ka.temporal_p = f.temporal_p;
+      ka.prior_p = f.prior_p; ka.last_id_prev = w.last_id[pp]; ka.last_id_next = w.last_id[pn];
+      ka.rec_next = f.rec_next; ka.temporal_next = f.temporal_next; ka.prior_next = f.prior_next;
       ka.flat = flat; ka.t = t; ka.out = out;
       ka.src_out = train ? w.src + (size_t)t * M : nullptr;
       sq_launch_compact(ka, po, d, s);
@@ -1317,9 +1335,9 @@ SQ_LOCAL int sq_forward_impl(SqairHandle* h, const float* flat, const float* pac
       // statistics and prior states of this frame, their temporal states held
       if (st.observed) {
         CoastArgs ca; memset(&ca, 0, sizeof(ca));
-        ca.observed = st.observed; ca.t = t; ca.rec_prev = rec_prev; ca.pstats = pstats_t; ca.ps_ld = PS_LD; ca.prior_p = prior_p;
-        ca.temporal_prev = temporal_prev; ca.noise = nz; ca.last_id_prev = ka.last_id_prev; ca.last_id_next = ka.last_id_next;
-        ca.rec_next = rec_next; ca.prior_next = ka.prior_next; ca.temporal_next = ka.temporal_next; ca.out = out; ca.cfg = c;
+        ca.observed = st.observed; ca.t = t; ca.rec_prev = f.rec_prev; ca.pstats = f.pstats; ca.ps_ld = PS_LD; ca.prior_p = f.prior_p;
+        ca.temporal_prev = f.temporal_prev; ca.noise = nz; ca.last_id_prev = ka.last_id_prev; ca.last_id_next = ka.last_id_next;
+        ca.rec_next = f.rec_next; ca.prior_next = ka.prior_next; ca.temporal_next = ka.temporal_next; ca.out = out; ca.cfg = c;
         sq_launch_coast_step(ca, d, s);
       }
     }

@@ -5,6 +5,7 @@
 #include <cstring>
 #include <map>
 
+#include "sqair_dx.h"
 #include "sqair_glue.h"
 #include "sqair_pack.h"
 
@@ -187,6 +188,47 @@ struct Lin {
     return *this;
   }
 };
+// builder for the routed dX GEMM of layer `id` (sqair_dx.h): the backward's counterpart of Lin.  The forward names a layer's operands
+// as segments; the reverse sweep names the same segments as destinations, and where segment i lies in the layer's padded K -- its
+// start the earlier widths each rounded up to 16, its length the true width -- is derived here from the plan (sq_run_dx checks it).
+struct SQ_LOCAL Dx {
+  DxArgs a;
+  LayerId id;
+  const PackedLayer& L;
+  static constexpr int MAXR = (int)(sizeof(DxArgs::r) / sizeof(DxRange));
+  Dx(const SqairHandle* h, LayerId layer, const float* dpre, int ld) : id(layer), L(h->layers[layer]) {
+    memset(&a, 0, sizeof(a));
+    a.dpre = dpre; a.ld = ld; a.width = L.N;
+  }
+  DxRange& last() { return a.r[(a.nranges < MAXR ? a.nranges : MAXR) - 1]; }
+  // segment i of the layer -> dst (an i the layer does not have, or one range too many: refused by sq_run_dx)
+  Dx& seg(int i, float* dst, int dst_ld) {
+    if (a.nranges++ >= MAXR) return *this;
+    const int nseg = (int)L.seg_width.size();
+    DxRange& r = last();
+    for (int j = 0; j < i && j < nseg; ++j) r.n0 += (L.seg_width[j] + 15) / 16 * 16;
+    r.n1 = r.n0 + (i >= 0 && i < nseg ? L.seg_width[i] : 0); r.dst = dst; r.dst_ld = dst_ld; r.act_split = 1 << 30;
+    return *this;
+  }
+  Dx& acc() { last().add = last().dst; last().add_ld = last().dst_ld; return *this; }
+  Dx& add(const float* p, int ld) { last().add = p; last().add_ld = ld; return *this; }
+  Dx& dact(const float* saved, int ld, int act_a, int act_b = ACT_NONE, int split = 1 << 30) {
+    last().saved = saved; last().saved_ld = ld; last().act_a = act_a; last().act_b = act_b; last().act_split = split;
+    return *this;
+  }
+  Dx& dup(float* p, int ld) { last().dst2 = p; last().dst2_ld = ld; return *this; }
+  // GRU gate adjoints in this launch's epilogue (DxGru): mode 1 = after the d h' GEMM, mode 2 = after the d(r h) GEMM
+  Dx& gru_a(const float* z, int z_ld, const float* hc, int hc_ld, const float* hprev, int h_ld, float* dpre1, int dp_ld, float* d_h,
+            int dh_ld, int acc_dh, int nh, float* dupp = nullptr, int dup_ld = 0, int dup_h_off = -1) {
+    a.gru = DxGru{1, z, z_ld, hc, hc_ld, hprev, h_ld, dpre1, dp_ld, d_h, dh_ld, acc_dh, dupp, dup_ld, dup_h_off, nh};
+    return *this;
+  }
+  Dx& gru_b(const float* r, int r_ld, const float* hprev, int h_ld, float* dpre1, int dp_ld, float* d_h, int dh_ld, int nh,
+            float* dupp = nullptr, int dup_ld = 0) {
+    a.gru = DxGru{2, r, r_ld, nullptr, 0, hprev, h_ld, dpre1, dp_ld, d_h, dh_ld, 1, dupp, dup_ld, -1, nh};
+    return *this;
+  }
+};
 
 
 
@@ -205,12 +247,15 @@ constexpr int PS_LD = 272, ENC_LD = 256, M1_LD = 128, HRAW_LD = 640, WB_LD = 4, 
 constexpr int PS_LD = 112, ENC_LD = 112, M1_LD = 64, HRAW_LD = 256, WB_LD = 4, TP_LD = 8, T1_LD = 384, S1_LD = 128;
 #endif
 
+// row of (frame t, phase ph, slot k) in a slot tape [phase][T][B'][N]: the one index formula of the workspace's tapes
+// (Workspace::slot) and of the backward's mirrors of them (BwdSpace::slot, sqair_train.hip)
+inline size_t sq_tape_row(int T, int R, int N, int t, int ph, int k) { return (size_t)(ph * T + t) * R * N + k; }
 struct Workspace {
   bool train;
   bool tape;    // per-frame / per-slot buffers are kept apart ([T] / [2 phases][T][B'][N]): training, or the in-launch slot chain
   bool chain;   // the slot loops run as chain launches (sqair_chain.h)
   unsigned* chain_ctl;   // control blocks of the pass's chain launches
-  int T, B, R, M, N, nh, snh, psnh;
+  int T, B, R, M, N, nh, snh, psnh, G2, pgw;   // (pgw: width of the prior cell's kept gates pgz)
   float *ienc_a, *ienc_b, *pre_disc;
   float *rec_m_all, *rec_p_all, *rec_d_all;
   float *temporal_m, *prior_m;                   // train: [T+1][M][snh | nh], else [2][M][snh | nh]
@@ -234,10 +279,17 @@ struct Workspace {
 
   float* frame(float* base, int64_t per_frame, int t) const { return base + (tape ? (size_t)t * per_frame : 0); }
   float* state(float* base, int t, int width) const { return base + (size_t)(tape ? t : (t & 1)) * M * width; }
+  // What both passes address of frame t: the records, the merged states on either side of it, and the per-frame buffers.  at() is the
+  // only caller of frame(): it stands beside sq_carve (sqair_api.hip), each stride against the take() that sized its buffer.
+  struct Frame {
+    float *rec_prev, *rec_next, *rec_p, *rec_d, *pstats, *spre;
+    float *temporal_prev, *temporal_next, *prior_prev, *prior_next, *temporal_p, *prior_p;
+    float *pgz, *pgr, *pghc;
+    float *hid1, *wb, *mask, *g1, *pea, *peb, *m1, *lea, *leb, *c;
+  };
+  SQ_LOCAL Frame at(int t) const;
   // slot buffer of width W: pointer of (frame t, phase ph, slot k) and its row stride
-  float* slot(float* base, int W, int t, int ph, int k) const {
-    return base + (tape ? (((size_t)(ph * T + t) * R * N) + k) * W : 0);  // [phase][T][B'][N][W]
-  }
+  float* slot(float* base, int W, int t, int ph, int k) const { return base + (tape ? sq_tape_row(T, R, N, t, ph, k) * W : 0); }
   int sld(int W) const { return tape ? N * W : W; }
   float* cslot(int t, int ph, int k) const { return tape ? slot(rc, nh, t, ph, k) : rc + (size_t)(k & 1) * R * nh; }
   float* rslot(int t, int ph, int k) const {  // RNN hidden state: ping-pong over slots when no tape is kept
@@ -333,10 +385,9 @@ SQ_LOCAL int sq_run_rnn_tail(SqairHandle* h, const TailArgs& ta, Dims d, LayerId
 // k_linear_what on the handle's L_WHAT_HEAD_I (mode 0) / L_PROP_HEADS_I (mode 1) pack
 SQ_LOCAL int sq_run_what(SqairHandle* h, int mode, const float* x, int x_ld, int M, int slot, const float* noise, const float* enc, int enc_ld,
                          const float* rec_prev, float* rec_new, const float* packed, hipStream_t s);
-// what the training pass shares with the adjoint unit entries (sqair_train.hip): the Dims of a training pass over B sequences, and
-// the steps predictor's offsets a slot-tail adjoint reads
+// what the training pass shares with the adjoint unit entries (sqair_train.hip), beside sq_pass_dims(h, B, 0), the Dims of a training
+// pass over B sequences: the steps predictor's offsets a slot-tail adjoint reads
 struct TailBwdArgs;
-SQ_LOCAL Dims sq_train_dims(const SqairHandle* h, int B);
 SQ_LOCAL void sq_tail_param_offsets(const SqairHandle* h, bool is_disc, TailBwdArgs* ta);
 // section A of a frame of the pass, and a frame of the forecast: the propagation-prior cell and its statistics (sqair_api.hip)
 SQ_LOCAL int sq_prior_step(SqairHandle* h, const float* packed, hipStream_t s, int M, const float* rec_prev, const float* prior_prev,
@@ -377,6 +428,8 @@ inline const float* sq_flat(const SqairHandle* h, const float* user_flat, const 
 }
 void sq_flat_gather(const SqairHandle* h, const float* padded_grad, float* user_grad, const void* packed, hipStream_t s);
 int sq_run(SqairHandle* h, Lin& l, LayerId id, int M, const float* packed, hipStream_t s);
+// the routed dX GEMM of x's layer over M rows; refuses what sq_run refuses, -3 + "internal: ... in dX of layer <id>", before the launch
+SQ_LOCAL int sq_run_dx(SqairHandle* h, Dx& x, int M, const float* packed, hipStream_t s, const float* scale_ptr = nullptr);
 #define RUN(l, id, M)                                   \
   do {                                                  \
     int _rc = sq_run(h, (l), (id), (M), packed, s);     \

@@ -77,40 +77,13 @@ __global__ void k_shift_inputs(const ShiftArgs a SQ_TLP) {
   }
 }
 
-// builder for the routed dX GEMM
-struct Dx {
-  DxArgs a;
-  Dx(const float* dpre, int ld) {
-    memset(&a, 0, sizeof(a));
-    a.dpre = dpre; a.ld = ld;
-  }
-  DxRange& last() { return a.r[a.nranges - 1]; }
-  Dx& to(int n0, int n1, float* dst, int dst_ld) {
-    DxRange& r = a.r[a.nranges++];
-    r.n0 = n0; r.n1 = n1; r.dst = dst; r.dst_ld = dst_ld; r.act_split = 1 << 30;
-    return *this;
-  }
-  Dx& acc() { last().add = last().dst; last().add_ld = last().dst_ld; return *this; }
-  Dx& add(const float* p, int ld) { last().add = p; last().add_ld = ld; return *this; }
-  Dx& dact(const float* saved, int ld, int act_a, int act_b = ACT_NONE, int split = 1 << 30) {
-    last().saved = saved; last().saved_ld = ld; last().act_a = act_a; last().act_b = act_b; last().act_split = split;
-    return *this;
-  }
-  Dx& dup(float* p, int ld) { last().dst2 = p; last().dst2_ld = ld; return *this; }
-  // GRU gate adjoints in this launch's epilogue (DxGru): mode 1 = after the d h' GEMM, mode 2 = after the d(r h) GEMM
-  Dx& gru_a(const float* z, int z_ld, const float* hc, int hc_ld, const float* hprev, int h_ld, float* dpre1, int dp_ld, float* d_h,
-            int dh_ld, int acc_dh, int nh, float* dupp = nullptr, int dup_ld = 0, int dup_h_off = -1) {
-    a.gru = DxGru{1, z, z_ld, hc, hc_ld, hprev, h_ld, dpre1, dp_ld, d_h, dh_ld, acc_dh, dupp, dup_ld, dup_h_off, nh};
-    return *this;
-  }
-  Dx& gru_b(const float* r, int r_ld, const float* hprev, int h_ld, float* dpre1, int dp_ld, float* d_h, int dh_ld, int nh,
-            float* dupp = nullptr, int dup_ld = 0) {
-    a.gru = DxGru{2, r, r_ld, nullptr, 0, hprev, h_ld, dpre1, dp_ld, d_h, dh_ld, 1, dupp, dup_ld, -1, nh};
-    return *this;
-  }
-};
-
 struct BwdSpace {
+  int T, R, N;
+  // the gradient mirrors of the workspace's slot tapes [2][T][R][N][W], by the workspace's own index formula; a per-frame buffer
+  // [T][R][N][W] is phase 0 of one
+  float* slot(float* base, int W, int t, int ph, int k) const { return base + sq_tape_row(T, R, N, t, ph, k) * W; }
+  float* frame(float* base, int W, int t) const { return slot(base, W, t, 0, 0); }
+  int sld(int W) const { return N * W; }
   float *g_lw, *g_dl;
   float* g_sc;                                  // [T][R] a masked carried chunk: the score coefficients of coasted (frame, row)s
   float *d_rec_m, *d_rec_p, *d_rec_d;          // gradient records
@@ -148,6 +121,7 @@ static BwdSpace carve_bwd(const SqairHandle* h, int T, int B, float* base) {
   const int64_t pre_ld = h->layers[L_PRE].nt * 16;
   BwdSpace b;
   memset(&b, 0, sizeof(b));
+  b.T = T; b.R = (int)R; b.N = (int)N;
   // Two groups: buffers the pass accumulates into or reads before it has written all of them come first and are cleared at the
   // start of every pass (zero_total floats); buffers that are WRITTEN IN FULL before anything reads them -- the decoder's
   // temporaries, the per-row mean-image terms, the A operands built for the batched weight gradients -- follow and are not.
@@ -205,6 +179,8 @@ extern "C" int64_t sqair_backward_bytes(const SqairHandle* h, int T, int B) {
   return carve_bwd(h, T, B, nullptr).total * 4;
 }
 
+// a dX launch of the sweep: the refusal's or the launch's own error text stays (CK would replace it)
+#define RUNDX(x, M) do { int _rc = sq_run_dx(h, (x), (M), packed, s); if (_rc != 0) return _rc; } while (0)
 #define CK(x) do { int _r = (x); if (_r != 0) { sq_set_error(h, std::string("sqair_backward: ") + #x); return _r; } } while (0)
 
 // dX through the transposed pack: out[M][K of the forward layer] (+)= dpre[M][N] W^T.  Single-segment layers write
@@ -226,8 +202,13 @@ static int sq_dx(SqairHandle* h, const char* who, const float* packed, LayerId i
 }
 // batched weight + bias gradients of one layer over `rows` uses: every block joins the grouped launch at the end of the pass
 // (its operands must then stay as they are until wbatch.flush), or is launched on its own when the grouped kernel does not take it
-static void sq_wgrad_layer(const SqairHandle* h, const float* packed, LayerId id, const std::vector<std::pair<const float*, int>>& segs,
-                           const float* dY, int ldy, int rows, WgradBatch& wbatch, float* flat_grad, hipStream_t s) {
+// (-3 + error text, before any of its launches, for a segment list that is not the layer's: wg[id] indexes it by segment)
+static int sq_wgrad_layer(SqairHandle* h, const float* packed, LayerId id, const std::vector<std::pair<const float*, int>>& segs,
+                          const float* dY, int ldy, int rows, WgradBatch& wbatch, float* flat_grad, hipStream_t s) {
+  if (segs.size() != h->layers[id].seg_width.size()) {
+    sq_set_error(h, "internal: segment count mismatch in the weight gradient of layer " + std::to_string((int)id));
+    return -3;
+  }
   const int* rm_dev = (const int*)packed + packed_layout(h).rm;
   // the bias gradient of a column block rides on the first weight-gradient launch of that block
   std::vector<char> bias_done(h->bg[id].size(), 0);
@@ -253,6 +234,7 @@ static void sq_wgrad_layer(const SqairHandle* h, const float* packed, LayerId id
       if (!e.a.empty()) sq_launch_colsum(dY + e.n0, ldy, rows, e.ncols, flat_grad + P(h, e.a) + e.col0, 1, s);
       if (!e.b.empty()) sq_launch_colsum(dY + e.n0, ldy, rows, e.ncols, flat_grad + P(h, e.b) + e.col0, 1, s);
     }
+  return 0;
 }
 
 // J^T: the decoder branch of all T frames (they are off the recurrence) -- the adjoint of the canvas and its log-likelihood, then
@@ -278,10 +260,10 @@ static int sq_decoder_adjoint(SqairHandle* h, const char* who, const float* flat
                         flat_grad + P(h, "dec.l2.b"), nullptr);
   if ((rc = sq_dx(h, who, packed, L_DEC2, d_gl, G2, MT, bufa, nh, false, scale, s)) != 0) return rc;
   sq_launch_dact2(bufa, nh, dec_b, nh, bufb, nh, MT, nh, ACT_ELU, ACT_ELU, 1 << 30, 0, s);
-  sq_wgrad_layer(h, packed, L_DEC1, {{dec_a, nh}}, bufb, nh, MT, wbatch, flat_grad, s);
+  if ((rc = sq_wgrad_layer(h, packed, L_DEC1, {{dec_a, nh}}, bufb, nh, MT, wbatch, flat_grad, s)) != 0) return rc;
   if ((rc = sq_dx(h, who, packed, L_DEC1, bufb, nh, MT, bufa, nh, false, nullptr, s)) != 0) return rc;
   sq_launch_dact2(bufa, nh, dec_a, nh, bufc, nh, MT, nh, ACT_ELU, ACT_ELU, 1 << 30, 0, s);
-  sq_wgrad_layer(h, packed, L_DEC0, {{rec_all, RW}}, bufc, nh, MT, wbatch, flat_grad, s);
+  if ((rc = sq_wgrad_layer(h, packed, L_DEC0, {{rec_all, RW}}, bufc, nh, MT, wbatch, flat_grad, s)) != 0) return rc;
   if ((rc = sq_dx(h, who, packed, L_DEC0, bufc, nh, MT, d_rec, d_rec_ld, true, nullptr, s)) != 0) return rc;
   return 0;
 }
@@ -302,14 +284,8 @@ struct SlotAdjPhase {
 };
 
 // The host expressions of the slot loop's element-wise adjoint launches that the pass shares with their unit entries (sqair_*_bwd_test,
-// sqair_unit_test.hip): both call these, so an entry cannot drift from the pass.
-// Dims of a training pass over B sequences: frames whose H * W is not a multiple of 4 are read from a zero-padded copy
-SQ_LOCAL Dims sq_train_dims(const SqairHandle* h, int B) {
-  Dims d = make_dims(h->cfg, B);
-  const int P_ = h->cfg.img_h * h->cfg.img_w;
-  if ((P_ & 3) != 0) d.P4 = (P_ + 3) / 4 * 4;
-  return d;
-}
+// sqair_unit_test.hip): both call these, so an entry cannot drift from the pass.  (Their Dims are the forward's with no
+// specialised kernels: sq_pass_dims(h, B, 0).)
 // the steps predictor a slot tail reads: output layer {w, b} and the first `what` row of its hidden layer ([in, nh/2] layout;
 // inputs [hidden nh | what] in discovery, [hidden nh | temporal nh | what] in propagation)
 SQ_LOCAL void sq_tail_param_offsets(const SqairHandle* h, bool is_disc, TailBwdArgs* ta) {
@@ -340,13 +316,12 @@ static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, c
   const int nh = c.n_hidden, nw = c.n_what, N = c.n_steps_per_image, K = c.k_particles;
   const int R = B * K, M = R * N, MT = M * T, G2 = c.glimpse_size * c.glimpse_size, P_ = c.img_h * c.img_w;
   const int nzw = 4 + nw + 1, RW = rec::W, nsp = nh / 2;
-  const Dims d = sq_train_dims(h, B);
+  const Dims d = sq_pass_dims(h, B, 0);
   const int snh = d.snh, gw = sq_gate_width(c, c.time_cell), psnh = d.psnh, pgw = sq_gate_width(c, c.prior_cell);
   const int rw = sq_rnn_width(c);  // slot-RNN pre-activation width; d_pre columns [rnn rw | T1 nh | S1 nsp | GRU z, r]
   const POff po = h->po;
   const Workspace w = sq_carve(h, T, B, (float*)train_workspace, true);
   const BwdSpace b = carve_bwd(h, T, B, (float*)scratch);
-  const PackedLayout pl = packed_layout(h);
   // (frames whose H * W is not a multiple of 4: the zero-padded copy the forward pass left in the training workspace)
   if ((P_ & 3) != 0) obs = w.obs_p;
   const int PL = d.P4;
@@ -370,21 +345,12 @@ static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, c
   }
 #endif
 
-  auto rundx = [&](LayerId id, Dx& dxa, int Mrows, const float* scale_ptr = nullptr) -> int {
-    const PackedLayer& LT = h->layersT[id];
-    dxa.a.width = h->layers[id].N; dxa.a.wp = packed + pl.w + LT.w_off; dxa.a.wzero = packed + pl.w;
-    dxa.a.scale_ptr = scale_ptr; dxa.a.M = Mrows;
-    const int rc = sq_launch_linear_dx(dxa.a, LT.kc, LT.nt, s);
-    if (rc != 0) sq_set_error(h, "sqair_backward: A-operand contract violated in dX of layer " + std::to_string((int)id));
-    return rc;
-  };
   WgradBatch wbatch;
   // (kept as a lambda: the ~45 calls below differ only in the layer, its operands and the row count)
+  int wgrad_rc = 0;   // (the first refusal: nothing is added after it, and the pass returns it before the grouped launch)
   auto wgrad = [&](LayerId id, std::vector<std::pair<const float*, int>> segs, const float* dY, int ldy, int rows) {
-    sq_wgrad_layer(h, packed, id, segs, dY, ldy, rows, wbatch, flat_grad, s);
+    if (wgrad_rc == 0) wgrad_rc = sq_wgrad_layer(h, packed, id, segs, dY, ldy, rows, wbatch, flat_grad, s);
   };
-  auto slotp = [&](float* base, int W, int t, int ph, int k) { return base + (((size_t)(ph * T + t) * R * N) + k) * W; };
-  auto cslotp = [&](const float* base, int W, int t, int ph, int k) { return base + (((size_t)(ph * T + t) * R * N) + k) * W; };
 
   // ================= 0. objective =================
   sq_launch_elbo_bwd(importance_weights, vimco_signal, T, B, K, b.g_lw, b.g_dl, s);
@@ -417,18 +383,15 @@ static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, c
   for (int t = T - 1; t >= 0; --t) {
     const float* img = obs + (size_t)t * B * PL;
     const float* nz = noise + (size_t)t * R * 2 * N * nzw;
-    const float* rec_prev = w.rec_m_all + (size_t)t * M * RW;
-    const float* rec_p_t = w.rec_p_all + (size_t)t * M * RW;
-    const float* rec_d_t = w.rec_d_all + (size_t)t * M * RW;
-    float* d_rec_prev = b.d_rec_m + (size_t)t * M * RW;
-    float* d_rec_next = b.d_rec_m + (size_t)(t + 1) * M * RW;
-    float* d_rec_p_t = b.d_rec_p + (size_t)t * M * RW;
-    float* d_rec_d_t = b.d_rec_d + (size_t)t * M * RW;
-    const float* temporal_prev = w.state(w.temporal_m, t, w.snh);
-    const float* prior_prev = w.state(w.prior_m, t, w.psnh);
+    const Workspace::Frame f = w.at(t);
+    float* d_rec_prev = b.frame(b.d_rec_m, RW, t);
+    float* d_rec_next = b.frame(b.d_rec_m, RW, t + 1);
+    float* d_rec_p_t = b.frame(b.d_rec_p, RW, t);
+    float* d_rec_d_t = b.frame(b.d_rec_d, RW, t);
     float* d_tau = b.d_tm(t);       // d temporal_m[t]
     float* d_pprev = b.d_pm(t);     // d prior_m[t]
-    const int rl = N * nh, t1l = N * T1_LD, gl2 = N * G2, el = N * ENC_LD, hl = N * HRAW_LD, tpl = N * TP_LD, s1l = N * S1_LD;
+    const int rl = w.sld(nh), t1l = w.sld(T1_LD), el = w.sld(ENC_LD), hl = w.sld(HRAW_LD), tpl = w.sld(TP_LD), s1l = w.sld(S1_LD);
+    const int drl = b.sld(rw), g1l = b.sld(gw);   // (row strides of the slot tapes; the mirrors keep the tape's)
 
     // ---- I^T. compaction
     {
@@ -444,81 +407,76 @@ static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, c
     //      crop #2 (`ca` arrives with the phase's own fields) with the adjoint of the transform's 8-wide output layer inside
     //      (80 launches fewer), T2 dX, then the slot RNN: T1 dX, the cell adjoint, the RNN layer's dX into the previous slot
     auto slot_adjoint = [&](const SlotAdjPhase& sp, int k, CropChainBwdArgs ca) -> int {
-      float* d_t1 = slotp(b.d_t1, T1_LD, t, sp.ph, k);
-      float* d_t2 = slotp(b.d_t2, nh, t, sp.ph, k);
-      float* d_tp = slotp(b.d_tp, TP_LD, t, sp.ph, k);
-      float* d_e1 = slotp(b.d_e1, nh, t, sp.ph, k);
-      float* d_e2 = slotp(b.d_e2, nh, t, sp.ph, k);
-      float* d_enc3 = slotp(b.d_enc3, ENC_LD, t, sp.ph, k);
-      float* d_rnn = slotp(b.d_rnn, rw, t, sp.ph, k);
-      const int drl = N * rw;
-      const float* r_k = cslotp(w.r, nh, t, sp.ph, k);
-      const float* t1 = cslotp(w.t1, T1_LD, t, sp.ph, k);
-      const float* t2 = cslotp(w.t2, nh, t, sp.ph, k);
-      const float* e1 = cslotp(w.e1, nh, t, sp.ph, k);
-      const float* e2 = cslotp(w.e2, nh, t, sp.ph, k);
+      float* d_t1 = b.slot(b.d_t1, T1_LD, t, sp.ph, k);
+      float* d_t2 = b.slot(b.d_t2, nh, t, sp.ph, k);
+      float* d_tp = b.slot(b.d_tp, TP_LD, t, sp.ph, k);
+      float* d_e1 = b.slot(b.d_e1, nh, t, sp.ph, k);
+      float* d_e2 = b.slot(b.d_e2, nh, t, sp.ph, k);
+      float* d_enc3 = b.slot(b.d_enc3, ENC_LD, t, sp.ph, k);
+      float* d_rnn = b.slot(b.d_rnn, rw, t, sp.ph, k);
+      const float* r_k = w.rslot(t, sp.ph, k);
+      const float* t1 = w.slot(w.t1, T1_LD, t, sp.ph, k);
+      const float* t2 = w.slot(w.t2, nh, t, sp.ph, k);
+      const float* e1 = w.slot(w.e1, nh, t, sp.ph, k);
+      const float* e2 = w.slot(w.e2, nh, t, sp.ph, k);
       float* d_pre_k = sp.d_pre ? sp.d_pre + (size_t)k * sp.d_pre_step : nullptr;   // columns: rnn 0:rw | T1 rw:rw+nh | ...
-      { Dx x(d_enc3, el); x.to(0, nh, d_e2, rl).dact(e2, rl, ACT_ELU); CK(rundx(L_WHAT_HEAD, x, R)); }
-      { Dx x(d_e2, rl); x.to(0, nh, d_e1, rl).dact(e1, rl, ACT_ELU); CK(rundx(L_GENC1, x, R)); }
-      { Dx x(d_e1, rl); x.to(0, G2, b.d_g, G2); CK(rundx(L_GENC0, x, R)); }
-      ca.slot = k; ca.img = img; ca.rec_prev = rec_prev; ca.rec_new = sp.rec; ca.d_rec_prev = d_rec_prev; ca.d_rec_new = sp.d_rec;
-      ca.g_out = b.d_g; ca.g_row_mul = 1; ca.tp = cslotp(w.tp, TP_LD, t, sp.ph, k); ca.tp_ld = tpl; ca.d_tp = d_tp; ca.dtp_ld = tpl;
+      { Dx x(h, L_WHAT_HEAD, d_enc3, el); x.seg(0, d_e2, rl).dact(e2, rl, ACT_ELU); RUNDX(x, R); }
+      { Dx x(h, L_GENC1, d_e2, rl); x.seg(0, d_e1, rl).dact(e1, rl, ACT_ELU); RUNDX(x, R); }
+      { Dx x(h, L_GENC0, d_e1, rl); x.seg(0, b.d_g, G2); RUNDX(x, R); }
+      ca.slot = k; ca.img = img; ca.rec_prev = f.rec_prev; ca.rec_new = sp.rec; ca.d_rec_prev = d_rec_prev; ca.d_rec_new = sp.d_rec;
+      ca.g_out = b.d_g; ca.g_row_mul = 1; ca.tp = w.slot(w.tp, TP_LD, t, sp.ph, k); ca.tp_ld = tpl; ca.d_tp = d_tp; ca.dtp_ld = tpl;
       ca.noise = nz; ca.flat = flat; ca.flat_grad = flat_grad; ca.w3 = sp.w3; ca.t2 = t2; ca.t2_ld = rl; ca.d_t2 = d_t2; ca.dt2_ld = rl;
       CK(sq_launch_crop_chain_bwd(ca, po, d, sq_crop_slots(ca.mode, d), s));
-      { Dx x(d_t2, rl); x.to(0, nh, d_t1, t1l).dact(t1, t1l, ACT_ELU).dup(d_pre_k ? d_pre_k + rw : nullptr, sp.d_pre_ld); CK(rundx(sp.t2, x, R)); }
+      { Dx x(h, sp.t2, d_t2, rl); x.seg(0, d_t1, t1l).dact(t1, t1l, ACT_ELU).dup(d_pre_k ? d_pre_k + rw : nullptr, sp.d_pre_ld); RUNDX(x, R); }
       // d h_k = T1^T + what d_r[k & 1] holds (the next slot's RNN; in propagation also the temporal cell's gate GEMM)
       const bool d_r_in = k < N - 1 || sp.d_r_every_slot;
-      if (c.rnn_cell == RNN_LSTM) {  // cell adjoint -> gate pre-activation gradients, d c_{k-1}
-        Dx x(d_t1, t1l); x.to(0, nh, b.d_hk, nh);
+      {  // (VanillaRNN: with tanh' -> the d pre-activation itself, incl. the steps-predictor columns of T1)
+        const bool van = c.rnn_cell == RNN_VANILLA;
+        Dx x(h, sp.t1, d_t1, t1l); x.seg(0, van ? d_rnn : b.d_hk, van ? rl : nh);
         if (d_r_in) x.add(b.d_r[k & 1], nh);
-        CK(rundx(sp.t1, x, R));
-        sq_launch_lstm_cell_bwd(cslotp(w.rgates, 4 * nh, t, sp.ph, k), N * 4 * nh, k == 0 ? sp.rnn_init + nh : cslotp(w.rc, nh, t, sp.ph, k - 1),
+        if (van) x.dact(r_k, rl, ACT_TANH).dup(d_pre_k, sp.d_pre_ld);
+        RUNDX(x, R);
+      }
+      if (c.rnn_cell == RNN_LSTM) {  // cell adjoint -> gate pre-activation gradients, d c_{k-1}
+        sq_launch_lstm_cell_bwd(w.slot(w.rgates, 4 * nh, t, sp.ph, k), w.sld(4 * nh), k == 0 ? sp.rnn_init + nh : w.cslot(t, sp.ph, k - 1),
                                 k == 0 ? 0 : rl, b.d_hk, nh, k < N - 1 ? b.d_cs[k & 1] : nullptr, nh, d_rnn, drl, b.d_cs[(k + 1) & 1], nh, R, nh, s,
                                 d_pre_k, sp.d_pre_ld);
       } else if (c.rnn_cell == RNN_GRU) {  // GRU adjoint in the two stages of the temporal cell; d h_{k-1} starts in d_r[(k-1)&1] / d_init
-        Dx x(d_t1, t1l); x.to(0, nh, b.d_hk, nh);
-        if (d_r_in) x.add(b.d_r[k & 1], nh);
-        CK(rundx(sp.t1, x, R));
-        const float* g3 = cslotp(w.rgates, 3 * nh, t, sp.ph, k);
-        const float* hp = k == 0 ? sp.rnn_init : cslotp(w.r, nh, t, sp.ph, k - 1);
-        const int g3l = N * 3 * nh, hpl = k == 0 ? 0 : rl;
+        const float* g3 = w.slot(w.rgates, 3 * nh, t, sp.ph, k);
+        const float* hp = k == 0 ? sp.rnn_init : w.rslot(t, sp.ph, k - 1);
+        const int g3l = w.sld(3 * nh), hpl = k == 0 ? 0 : rl;
         float* dhp = k > 0 ? b.d_r[(k - 1) & 1] : sp.d_init;
         sq_launch_gru_bwd_a(b.d_hk, nh, g3, g3l, g3 + 2 * nh, g3l, hp, hpl, d_rnn, drl, dhp, nh, R, nh, 0, s, d_pre_k, sp.d_pre_ld,
                             d_pre_k ? 2 * nh : -1);
-        { Dx y(d_rnn + 2 * nh, drl); y.to(0, nh, b.d_rh, nh); CK(rundx(sp.rnn2, y, R)); }
+        { Dx y(h, sp.rnn2, d_rnn + 2 * nh, drl); y.seg(0, b.d_rh, nh); RUNDX(y, R); }
         sq_launch_gru_bwd_b(b.d_rh, nh, g3 + nh, g3l, hp, hpl, d_rnn, drl, dhp, nh, R, nh, s, d_pre_k ? d_pre_k + nh : nullptr, sp.d_pre_ld);
-      } else {  // tanh' -> d pre-activation (incl. the steps-predictor columns of T1)
-        Dx x(d_t1, t1l); x.to(0, nh, d_rnn, rl);
-        if (d_r_in) x.add(b.d_r[k & 1], nh);
-        x.dact(r_k, rl, ACT_TANH).dup(d_pre_k, sp.d_pre_ld);
-        CK(rundx(sp.t1, x, R));
       }
-      Dx x(d_rnn, drl);
+      Dx x(h, sp.rnn, d_rnn, drl);   // [z-record of slot k - 1 | h_{k-1}]
       if (k > 0) {
-        x.to(0, rec::ZW, sp.d_rec + (size_t)(k - 1) * RW, N * RW).acc();
-        x.to(rec::ZWP, rec::ZWP + nh, b.d_r[(k - 1) & 1], nh);
+        x.seg(0, sp.d_rec + (size_t)(k - 1) * RW, N * RW).acc();
+        x.seg(1, b.d_r[(k - 1) & 1], nh);
       } else {
-        x.to(rec::ZWP, rec::ZWP + nh, sp.d_init, nh);   // d (initial hidden state): column sum after the sweep
+        x.seg(1, sp.d_init, nh);   // d (initial hidden state): column sum after the sweep
       }
       if (c.rnn_cell == RNN_GRU) x.acc();   // the gate adjoints above already put their direct part there
-      CK(rundx(sp.rnn, x, R));
+      RUNDX(x, R);
       if (k == 0 && c.rnn_cell == RNN_LSTM) sq_launch_colsum(b.d_cs[1], nh, R, nh, sp.d_init_cell, 1, s);
       return 0;
     };
 
     // ---- G^T. discovery steps
     float* d_pre_d = b.d_pre_d + (size_t)t * R * rw;
-    const SlotAdjPhase disc = {1, L_DISC_RNN, L_DISC_RNN2, L_DISC_T1, L_DISC_T2, rec_d_t, d_rec_d_t, w.disc_rnn_init,
+    const SlotAdjPhase disc = {1, L_DISC_RNN, L_DISC_RNN2, L_DISC_T1, L_DISC_T2, f.rec_d, d_rec_d_t, w.disc_rnn_init,
                                b.d_init_d + (size_t)t * R * nh, flat_grad + po.disc_rnn_init + nh, nullptr, 0, 0, w.w3_disc, false};
     for (int j = N - 1; j >= 0; --j) {
-      float* d_t1 = slotp(b.d_t1, T1_LD, t, 1, j);
-      float* d_enc3 = slotp(b.d_enc3, ENC_LD, t, 1, j);
-      const float* enc = cslotp(w.enc, ENC_LD, t, 1, j);
+      float* d_t1 = b.slot(b.d_t1, T1_LD, t, 1, j);
+      float* d_enc3 = b.slot(b.d_enc3, ENC_LD, t, 1, j);
+      const float* enc = w.slot(w.enc, ENC_LD, t, 1, j);
       {
         TailBwdArgs ta; memset(&ta, 0, sizeof(ta));
-        ta.is_disc = 1; ta.slot = j; ta.rec_prev = rec_prev; ta.rec_new = rec_d_t; ta.d_rec_new = d_rec_d_t;
-        ta.d_rec_prev = d_rec_prev; ta.s1h = cslotp(w.s1h, S1_LD, t, 1, j); ta.s1h_ld = s1l; ta.enc = enc; ta.enc_ld = el;
-        ta.noise = nz; ta.d_s1pre = d_t1 + nh; ta.ds_ld = t1l; ta.d_enc = d_enc3; ta.de_ld = el; ta.enc_pre = 1; ta.d_raw_out = slotp(b.d_raw, 1, t, 1, j); ta.dr_ld = N; ta.flat = flat;
+        ta.is_disc = 1; ta.slot = j; ta.rec_prev = f.rec_prev; ta.rec_new = f.rec_d; ta.d_rec_new = d_rec_d_t;
+        ta.d_rec_prev = d_rec_prev; ta.s1h = w.slot(w.s1h, S1_LD, t, 1, j); ta.s1h_ld = s1l; ta.enc = enc; ta.enc_ld = el;
+        ta.noise = nz; ta.d_s1pre = d_t1 + nh; ta.ds_ld = t1l; ta.d_enc = d_enc3; ta.de_ld = el; ta.enc_pre = 1; ta.d_raw_out = b.slot(b.d_raw, 1, t, 1, j); ta.dr_ld = N; ta.flat = flat;
         ta.flat_grad = flat_grad;
         sq_tail_param_offsets(h, true, &ta);
         CK(sq_launch_slot_tail_bwd(ta, d, s));
@@ -529,184 +487,153 @@ static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, c
       if (rc != 0) return rc;
     }
     // ---- F^T. conditioning of discovery on the propagated latents
-    sq_launch_sum_slots(b.d_rnn + (size_t)(T + t) * M * rw, d_pre_d, b.d_pre_disc + (size_t)t * B * rw, B, K, N, rw, s);
-    { Dx x(d_pre_d, rw); x.to(0, nh, b.d_c, nh); CK(rundx(L_PRED, x, R)); }
+    sq_launch_sum_slots(b.slot(b.d_rnn, rw, t, 1, 0), d_pre_d, b.d_pre_disc + (size_t)t * B * rw, B, K, N, rw, s);
+    { Dx x(h, L_PRED, d_pre_d, rw); x.seg(0, b.d_c, nh); RUNDX(x, R); }
     if (c.rec_where_prior) {
-      Dx x(b.d_spre + (size_t)t * R * 128, 128);
-      x.to(0, 4, b.d_rn0 + (size_t)t * R * 4, 4);
-      x.to(16, 16 + nh, b.d_c, nh).acc();
-      CK(rundx(L_RNCOND, x, R));
+      Dx x(h, L_RNCOND, b.d_spre + (size_t)t * R * 128, 128);   // [initial state 4 | conditioning nh]
+      x.seg(0, b.d_rn0 + (size_t)t * R * 4, 4);
+      x.seg(1, b.d_c, nh).acc();
+      RUNDX(x, R);
     }
     {
-      float* d_leb = b.d_leb + (size_t)t * M * nh;
-      float* d_lea = b.d_lea + (size_t)t * M * nh;
-      const float* leb = w.frame(w.leb, (int64_t)M * nh, t);
-      const float* lea = w.frame(w.lea, (int64_t)M * nh, t);
-      sq_launch_latent_sum_bwd(b.d_c, rec_p_t, leb, d_leb, d, s);
-      { Dx x(d_leb, nh); x.to(0, nh, d_lea, nh).dact(lea, nh, ACT_ELU); CK(rundx(L_LAT1, x, M)); }
-      { Dx x(d_lea, nh); x.to(0, rec::ZW, d_rec_p_t, RW).acc(); CK(rundx(L_LAT0, x, M)); }
+      float* d_leb = b.frame(b.d_leb, nh, t);
+      float* d_lea = b.frame(b.d_lea, nh, t);
+      sq_launch_latent_sum_bwd(b.d_c, f.rec_p, f.leb, d_leb, d, s);
+      { Dx x(h, L_LAT1, d_leb, nh); x.seg(0, d_lea, nh).dact(f.lea, nh, ACT_ELU); RUNDX(x, M); }
+      { Dx x(h, L_LAT0, d_lea, nh); x.seg(0, d_rec_p_t, RW).acc(); RUNDX(x, M); }
     }
     // ---- E^T. propagation slots
-    float* d_pre = b.d_pre + (size_t)t * M * pre_ld;
+    float* d_pre = b.frame(b.d_pre, pre_ld, t);
     // the mask gradient of the frame accumulates in the frame's slice of d_maskpre (cleared with the scratch) and gets the
     // sigmoid's derivative in place below
-    float* const d_mask_t = b.d_maskpre + (size_t)t * M * G2;
-    const float* mask = w.frame(w.mask, (int64_t)M * G2, t);
-    const SlotAdjPhase prop = {0, L_PROP_RNN, L_PROP_RNN2, L_PROP_T1, L_PROP_T2, rec_p_t, d_rec_p_t, w.prop_rnn_init,
+    float* const d_mask_t = b.frame(b.d_maskpre, G2, t);
+    const SlotAdjPhase prop = {0, L_PROP_RNN, L_PROP_RNN2, L_PROP_T1, L_PROP_T2, f.rec_p, d_rec_p_t, w.prop_rnn_init,
                                b.d_init_p + (size_t)t * R * nh, flat_grad + po.prop_rnn_init + nh, d_pre, pre_ld, N * pre_ld, w.w3_prop, true};
     for (int k = N - 1; k >= 0; --k) {
-      float* d_t1 = slotp(b.d_t1, T1_LD, t, 0, k);
-      float* d_enc3 = slotp(b.d_enc3, ENC_LD, t, 0, k);
-      float* d_gru1 = b.d_gru1 + ((size_t)t * M + k) * gw;   // [T][R][N][3nh (GRU) | 4nh (LSTM)], row stride N*gw
-      float* d_hraw = b.d_hraw + ((size_t)t * M + k) * HRAW_LD;
-      const int g1l = N * gw;
-      const float* enc = cslotp(w.enc, ENC_LD, t, 0, k);
-      const float* tau_k = temporal_prev + (size_t)k * snh;   // GRU: the state; LSTM: [hidden | cell], features = cell
+      float* d_t1 = b.slot(b.d_t1, T1_LD, t, 0, k);
+      float* d_enc3 = b.slot(b.d_enc3, ENC_LD, t, 0, k);
+      float* d_gru1 = b.slot(b.d_gru1, gw, t, 0, k);   // [T][R][N][3nh (GRU) | 4nh (LSTM)], row stride N*gw
+      float* d_hraw = b.slot(b.d_hraw, HRAW_LD, t, 0, k);
+      const float* enc = w.slot(w.enc, ENC_LD, t, 0, k);
+      const float* tau_k = f.temporal_prev + (size_t)k * snh;   // GRU: the state; LSTM: [hidden | cell], features = cell
       float* d_tau_k = d_tau + (size_t)k * snh;
       float* d_pre_k = d_pre + (size_t)k * pre_ld;   // columns: rnn 0:nh | T1 nh:2nh | S1 2nh:2nh+nsp | z, r
       const int pre_rld = N * pre_ld;
       {
         TailBwdArgs ta; memset(&ta, 0, sizeof(ta));
-        ta.is_disc = 0; ta.slot = k; ta.rec_prev = rec_prev; ta.rec_new = rec_p_t; ta.d_rec_new = d_rec_p_t;
-        ta.d_rec_prev = d_rec_prev; ta.s1h = cslotp(w.s1h, S1_LD, t, 0, k); ta.s1h_ld = s1l;
-        ta.hraw = cslotp(w.hraw, HRAW_LD, t, 0, k); ta.h_ld = hl; ta.enc = enc; ta.enc_ld = el; ta.noise = nz;
+        ta.is_disc = 0; ta.slot = k; ta.rec_prev = f.rec_prev; ta.rec_new = f.rec_p; ta.d_rec_new = d_rec_p_t;
+        ta.d_rec_prev = d_rec_prev; ta.s1h = w.slot(w.s1h, S1_LD, t, 0, k); ta.s1h_ld = s1l;
+        ta.hraw = w.slot(w.hraw, HRAW_LD, t, 0, k); ta.h_ld = hl; ta.enc = enc; ta.enc_ld = el; ta.noise = nz;
         ta.d_s1pre = d_t1 + nh; ta.ds_ld = t1l; ta.d_s1pre2 = d_pre_k + rw + nh; ta.ds2_ld = pre_rld;
-        ta.d_enc = b.d_enc; ta.de_ld = ENC_LD; ta.d_hraw = d_hraw; ta.dh_ld = hl; ta.d_raw_out = slotp(b.d_raw, 1, t, 0, k); ta.dr_ld = N;
+        ta.d_enc = b.d_enc; ta.de_ld = ENC_LD; ta.d_hraw = d_hraw; ta.dh_ld = hl; ta.d_raw_out = b.slot(b.d_raw, 1, t, 0, k); ta.dr_ld = N;
         ta.flat = flat; ta.flat_grad = flat_grad;
         sq_tail_param_offsets(h, false, &ta);
         CK(sq_launch_slot_tail_bwd(ta, d, s));
       }
-      // heads -> d tau'_k (the new HIDDEN state), + what the compaction sent back for this slot's new temporal state
-      if (c.time_cell == CELL_VANILLA) {  // tanh' folded into the same launch; second copy: the hoisted recurrent block of d_pre
-        Dx x(d_hraw, hl);
-        x.to(0, nh, d_gru1, g1l).add(b.d_temporal_p + (size_t)k * nh, N * nh)
-            .dact(w.frame(w.temporal_p, (int64_t)M * nh, t) + (size_t)k * nh, N * nh, ACT_TANH).dup(d_pre_k + rw + nh + nsp, pre_rld);
-        CK(rundx(L_PROP_HEADS, x, R));
-      } else if (c.time_cell == CELL_GRU) {  // d tau'_k and, in the same launch's epilogue, the gate adjoints that consume it
-        Dx x(d_hraw, hl);
-        x.to(0, nh, b.dhn, nh).add(b.d_temporal_p + (size_t)k * snh, N * snh)
-            .gru_a(cslotp(w.gz, nh, t, 0, k), rl, cslotp(w.ghc, nh, t, 0, k), rl, tau_k, N * nh, d_gru1, g1l, d_tau_k, N * nh, 1, nh,
-                   d_pre_k + rw + nh + nsp, pre_rld);
-        CK(rundx(L_PROP_HEADS, x, R));
-      } else {
-        Dx x(d_hraw, hl); x.to(0, nh, b.dhn, nh).add(b.d_temporal_p + (size_t)k * snh, N * snh); CK(rundx(L_PROP_HEADS, x, R));
+      // heads -> d tau'_k (the new HIDDEN state), + what the compaction sent back for this slot's new temporal state.  VanillaRNN:
+      // tanh' folded into the same launch, second copy into the hoisted recurrent block of d_pre; GRU: the gate adjoints that consume
+      // d tau'_k in the launch's epilogue
+      {
+        Dx x(h, L_PROP_HEADS, d_hraw, hl);
+        x.seg(0, c.time_cell == CELL_VANILLA ? d_gru1 : b.dhn, c.time_cell == CELL_VANILLA ? g1l : nh).add(b.d_temporal_p + (size_t)k * snh, N * snh);
+        if (c.time_cell == CELL_VANILLA) x.dact(f.temporal_p + (size_t)k * nh, N * nh, ACT_TANH).dup(d_pre_k + rw + nh + nsp, pre_rld);
+        if (c.time_cell == CELL_GRU)
+          x.gru_a(w.slot(w.gz, nh, t, 0, k), rl, w.slot(w.ghc, nh, t, 0, k), rl, tau_k, N * nh, d_gru1, g1l, d_tau_k, N * nh, 1, nh,
+                  d_pre_k + rw + nh + nsp, pre_rld);
+        RUNDX(x, R);
       }
-      if (c.time_cell == CELL_VANILLA) {
-      } else if (c.time_cell == CELL_LSTM) {
+      if (c.time_cell == CELL_LSTM) {
         // cell adjoint: gate pre-activation gradients (kept for the batched weight gradients and the recurrent-rows dX
         // after the slot loop) and d c_{t-1} -- the first writer of the cell half of d_tau (sections D^T / B^T accumulate)
         sq_launch_lstm_cell_bwd(w.lgates + ((size_t)t * M + k) * 4 * nh, N * 4 * nh, tau_k + nh, N * snh, b.dhn, nh,
                                 b.d_temporal_p + (size_t)k * snh + nh, N * snh, d_gru1, g1l, d_tau_k + nh, N * snh, R, nh, s);
-      } else {
-        Dx x(d_gru1 + 2 * nh, g1l);
-        x.to(0, nh, b.d_rh, nh).gru_b(cslotp(w.gr, nh, t, 0, k), rl, tau_k, N * nh, d_gru1, g1l, d_tau_k, N * nh, nh,
+      } else if (c.time_cell == CELL_GRU) {
+        Dx x(h, L_PROP_GRU2, d_gru1 + 2 * nh, g1l);
+        x.seg(0, b.d_rh, nh).gru_b(w.slot(w.gr, nh, t, 0, k), rl, tau_k, N * nh, d_gru1, g1l, d_tau_k, N * nh, nh,
                                      d_pre_k + rw + 2 * nh + nsp, pre_rld);
-        CK(rundx(L_PROP_GRU2, x, R));
+        RUNDX(x, R);
       }
       {  // gate GEMM inputs [r_k nh | where 4 (pad 16) | glimpse-encoder (loc, scale) 2 nw]
-        Dx x(d_gru1, g1l);
-        x.to(0, nh, b.d_r[k & 1], nh);
+        Dx x(h, L_PROP_GRU1, d_gru1, g1l);
+        x.seg(0, b.d_r[k & 1], nh);
         if (k < N - 1) x.acc();                                      // slot k+1's RNN already wrote d r_k there
-        x.to(nh, nh + 4, d_rec_p_t + (size_t)k * RW + rec::WHERE, N * RW).acc();
-        x.to(nh + 16, nh + 16 + 2 * nw, d_enc3, el).add(b.d_enc, ENC_LD).dact(enc, el, ACT_NONE, ACT_SOFTPLUS_MIN, nw);
-        CK(rundx(L_PROP_GRU1, x, R));
+        x.seg(1, d_rec_p_t + (size_t)k * RW + rec::WHERE, N * RW).acc();
+        x.seg(2, d_enc3, el).add(b.d_enc, ENC_LD).dact(enc, el, ACT_NONE, ACT_SOFTPLUS_MIN, nw);
+        RUNDX(x, R);
       }
       CropChainBwdArgs ca; memset(&ca, 0, sizeof(ca));
-      ca.mode = CROP_PROP2; ca.mask = c.masked_glimpse ? mask : nullptr; ca.mask_row_mul = N; ca.mask_row_add = k; ca.d_mask = d_mask_t;
+      ca.mode = CROP_PROP2; ca.mask = c.masked_glimpse ? f.mask : nullptr; ca.mask_row_mul = N; ca.mask_row_add = k; ca.d_mask = d_mask_t;
       const int rc = slot_adjoint(prop, k, ca);
       if (rc != 0) return rc;
     }
-    // ---- D^T. the loop-invariant pre-activation GEMM: segments [m1 nw (pad 64) | z_{t-1} record 56 (pad 64) | temporal nh]
-    float* d_m1 = b.d_m1 + (size_t)t * M * M1_LD;
+    // ---- D^T. the loop-invariant pre-activation GEMM: segments [m1 nw | z_{t-1} record | temporal nh]
+    float* d_m1 = b.frame(b.d_m1, M1_LD, t);
     if (c.time_cell == CELL_LSTM) {  // recurrent rows of the LSTM gates, all slots at once: d h_{t-1} = d gates W_h^T (first writer)
-      Dx x(b.d_gru1 + (size_t)t * M * gw, gw); x.to(0, nh, d_tau, snh); CK(rundx(L_PROP_GRU2, x, M));
+      Dx x(h, L_PROP_GRU2, b.frame(b.d_gru1, gw, t), gw); x.seg(0, d_tau, snh); RUNDX(x, M);
     }
     {
-      Dx x(d_pre, pre_ld);
-      x.to(0, nw, d_m1, M1_LD);
-      const int o1 = (nw + 15) / 16 * 16, o2 = o1 + rec::ZWP;   // padded segment starts: [m1 nw | record 56 | temporal nh]
-      x.to(o1, o1 + rec::ZW, d_rec_prev, RW).acc();
-      x.to(o2, o2 + nh, d_tau + d.toff, snh).acc();
-      CK(rundx(L_PRE, x, M));
+      Dx x(h, L_PRE, d_pre, pre_ld);
+      x.seg(0, d_m1, M1_LD);
+      x.seg(1, d_rec_prev, RW).acc();
+      x.seg(2, d_tau + d.toff, snh).acc();
+      RUNDX(x, M);
     }
     // ---- C^T. crop #1 and its encoder
     {
-      float* d_peb = b.d_peb + (size_t)t * M * nh;
-      float* d_pea = b.d_pea + (size_t)t * M * nh;
-      const float* peb = w.frame(w.peb, (int64_t)M * nh, t);
-      const float* pea = w.frame(w.pea, (int64_t)M * nh, t);
-      { Dx x(d_m1, M1_LD); x.to(0, nh, d_peb, nh).dact(peb, nh, ACT_ELU); CK(rundx(L_WHAT_LOC, x, M)); }
-      { Dx x(d_peb, nh); x.to(0, nh, d_pea, nh).dact(pea, nh, ACT_ELU); CK(rundx(L_GENC1, x, M)); }
-      { Dx x(d_pea, nh); x.to(0, G2, b.d_g1, G2); CK(rundx(L_GENC0, x, M)); }
+      float* d_peb = b.frame(b.d_peb, nh, t);
+      float* d_pea = b.frame(b.d_pea, nh, t);
+      { Dx x(h, L_WHAT_LOC, d_m1, M1_LD); x.seg(0, d_peb, nh).dact(f.peb, nh, ACT_ELU); RUNDX(x, M); }
+      { Dx x(h, L_GENC1, d_peb, nh); x.seg(0, d_pea, nh).dact(f.pea, nh, ACT_ELU); RUNDX(x, M); }
+      { Dx x(h, L_GENC0, d_pea, nh); x.seg(0, b.d_g1, G2); RUNDX(x, M); }
       CropChainBwdArgs ca; memset(&ca, 0, sizeof(ca));
-      ca.mode = CROP_PROP1; ca.img = img; ca.rec_prev = rec_prev; ca.d_rec_prev = d_rec_prev; ca.wb = w.frame(w.wb, (int64_t)M * WB_LD, t);
-      ca.wb_ld = WB_LD; ca.d_wb = b.d_wb + (size_t)t * M * WB_LD; ca.mask = c.masked_glimpse ? mask : nullptr; ca.mask_row_mul = N;
+      ca.mode = CROP_PROP1; ca.img = img; ca.rec_prev = f.rec_prev; ca.d_rec_prev = d_rec_prev; ca.wb = f.wb;
+      ca.wb_ld = WB_LD; ca.d_wb = b.frame(b.d_wb, WB_LD, t); ca.mask = c.masked_glimpse ? f.mask : nullptr; ca.mask_row_mul = N;
       ca.d_mask = d_mask_t; ca.g_out = b.d_g1; ca.g_row_mul = N; ca.flat = flat; ca.flat_grad = flat_grad;
       ca.mask_dact = 1;  // the frame's last contribution to d mask: the sigmoid's adjoint rides on its write (d_mask_t IS d_maskpre)
       CK(sq_launch_crop_chain_bwd(ca, po, d, sq_crop_slots(ca.mode, d), s));
     }
     // ---- B^T. mask MLP and where-bias MLP
     {
-      float* d_maskpre = b.d_maskpre + (size_t)t * M * G2;
-      float* d_hid1 = b.d_hid1 + (size_t)t * M * 256;
-      const float* hid1 = w.frame(w.hid1, (int64_t)M * 256, t);
+      float* d_hid1 = b.frame(b.d_hid1, 256, t);
       if (c.masked_glimpse) {
-        Dx x(d_maskpre, G2); x.to(0, 128, d_hid1 + 128, 256).dact(hid1 + 128, 256, ACT_ELU); CK(rundx(L_MASK2, x, M));
+        Dx x(h, L_MASK2, d_mask_t, G2); x.seg(0, d_hid1 + 128, 256).dact(f.hid1 + 128, 256, ACT_ELU); RUNDX(x, M);
       }
-      { Dx x(b.d_wb + (size_t)t * M * WB_LD, WB_LD); x.to(0, 128, d_hid1, 256).dact(hid1, 256, ACT_ELU); CK(rundx(L_WB2, x, M)); }
-      { Dx x(d_hid1, 256); x.to(0, nh, d_tau + d.toff, snh).acc(); CK(rundx(L_TAU1, x, M)); }
+      { Dx x(h, L_WB2, b.frame(b.d_wb, WB_LD, t), WB_LD); x.seg(0, d_hid1, 256).dact(f.hid1, 256, ACT_ELU); RUNDX(x, M); }
+      { Dx x(h, L_TAU1, d_hid1, 256); x.seg(0, d_tau + d.toff, snh).acc(); RUNDX(x, M); }
     }
     // ---- the coasted rows of a masked carried chunk: record t + 1, the prior state and the held temporal state back through the
     //      frame's permutation (k_coast_step_bwd).  Here: after every first writer of d temporal_m[t] (E^T, D^T; zeros for these
     //      rows), before A^T reads d_prior_p and the frame's d_pstats.
     if (observed) {
       CoastBwdArgs ca; memset(&ca, 0, sizeof(ca));
-      ca.observed = observed; ca.t = t; ca.rec_prev = rec_prev; ca.pstats = w.pstats + (size_t)t * M * PS_LD; ca.ps_ld = PS_LD;
+      ca.observed = observed; ca.t = t; ca.rec_prev = f.rec_prev; ca.pstats = f.pstats; ca.ps_ld = PS_LD;
       ca.noise = nz; ca.g_sc = b.g_sc + (size_t)t * R; ca.d_rec_next = d_rec_next; ca.d_prior_next = b.d_pm(t + 1);
-      ca.d_temporal_next = b.d_tm(t + 1); ca.d_rec_prev = d_rec_prev; ca.d_pstats = b.d_pstats + (size_t)t * M * PS_LD;
+      ca.d_temporal_next = b.d_tm(t + 1); ca.d_rec_prev = d_rec_prev; ca.d_pstats = b.frame(b.d_pstats, PS_LD, t);
       ca.d_prior_p = b.d_prior_p; ca.d_temporal_prev = d_tau; ca.cfg = c;
       sq_launch_coast_step_bwd(ca, d, s);
     }
-    // ---- A^T. prior cell
-    float* d_pgru1 = b.d_pgru1 + (size_t)t * M * pgw;
-    if (c.prior_cell == CELL_VANILLA) {
-      { Dx x(b.d_pstats + (size_t)t * M * PS_LD, PS_LD);
-        x.to(0, nh, d_pgru1, pgw).add(b.d_prior_p, nh).dact(w.frame(w.prior_p, (int64_t)M * nh, t), nh, ACT_TANH);
-        CK(rundx(L_PRIOR_LIN, x, M)); }
-      Dx x(d_pgru1, pgw);   // [z_{t-1} record 56 (pad 64) | previous state nh]
-      x.to(0, rec::ZW, d_rec_prev, RW).acc();
-      x.to(rec::ZWP, rec::ZWP + nh, d_pprev, nh);
-      CK(rundx(L_PRIOR_GRU1, x, M));
-    } else {
+    // ---- A^T. prior cell: the statistics layer's dX (VanillaRNN: tanh' in it; GRU: the gate adjoints in its epilogue), the cell,
+    //      then the gate layer's dX over [z_{t-1} record | previous hidden state nh]
+    float* d_pgru1 = b.frame(b.d_pgru1, pgw, t);
     {
-      Dx x(b.d_pstats + (size_t)t * M * PS_LD, PS_LD);
-      x.to(0, nh, b.dhn, nh).add(b.d_prior_p, psnh);
-      if (c.prior_cell == CELL_GRU)
-        x.gru_a(w.frame(w.pgz, (int64_t)M * nh, t), nh, w.frame(w.pghc, (int64_t)M * nh, t), nh, prior_prev, nh, d_pgru1, 3 * nh, d_pprev,
-                nh, 1, nh);
-      CK(rundx(L_PRIOR_LIN, x, M));
+      Dx x(h, L_PRIOR_LIN, b.frame(b.d_pstats, PS_LD, t), PS_LD);
+      if (c.prior_cell == CELL_VANILLA) x.seg(0, d_pgru1, pgw).add(b.d_prior_p, psnh).dact(f.prior_p, nh, ACT_TANH);
+      else x.seg(0, b.dhn, nh).add(b.d_prior_p, psnh);
+      if (c.prior_cell == CELL_GRU) x.gru_a(f.pgz, nh, f.pghc, nh, f.prior_prev, nh, d_pgru1, pgw, d_pprev, nh, 1, nh);
+      RUNDX(x, M);
     }
-    if (c.prior_cell == CELL_LSTM) {
-      sq_launch_lstm_cell_bwd(w.frame(w.pgz, (int64_t)M * 4 * nh, t), 4 * nh, prior_prev + nh, psnh, b.dhn, nh, b.d_prior_p + nh, psnh,
-                              d_pgru1, pgw, d_pprev + nh, psnh, M, nh, s);
-      Dx x(d_pgru1, pgw);   // [z_{t-1} record 56 (pad 64) | previous hidden state nh]
-      x.to(0, rec::ZW, d_rec_prev, RW).acc();
-      x.to(rec::ZWP, rec::ZWP + nh, d_pprev, psnh);
-      CK(rundx(L_PRIOR_GRU1, x, M));
-    } else {
-      {
-        Dx x(d_pgru1 + 2 * nh, 3 * nh);
-        x.to(0, nh, b.d_rh, nh).gru_b(w.frame(w.pgr, (int64_t)M * nh, t), nh, prior_prev, nh, d_pgru1, 3 * nh, d_pprev, nh, nh);
-        CK(rundx(L_PRIOR_GRU2, x, M));
-      }
-      {  // [z_{t-1} record 56 (pad 64) | prior state nh]
-        Dx x(d_pgru1, 3 * nh);
-        x.to(0, rec::ZW, d_rec_prev, RW).acc();
-        x.to(rec::ZWP, rec::ZWP + nh, d_pprev, nh).acc();
-        CK(rundx(L_PRIOR_GRU1, x, M));
-      }
+    if (c.prior_cell == CELL_LSTM)
+      sq_launch_lstm_cell_bwd(f.pgz, w.pgw, f.prior_prev + nh, psnh, b.dhn, nh, b.d_prior_p + nh, psnh, d_pgru1, pgw, d_pprev + nh, psnh, M, nh, s);
+    if (c.prior_cell == CELL_GRU) {
+      Dx x(h, L_PRIOR_GRU2, d_pgru1 + 2 * nh, pgw);
+      x.seg(0, b.d_rh, nh).gru_b(f.pgr, nh, f.prior_prev, nh, d_pgru1, pgw, d_pprev, nh, nh);
+      RUNDX(x, M);
     }
-    }
+    Dx x(h, L_PRIOR_GRU1, d_pgru1, pgw);
+    x.seg(0, d_rec_prev, RW).acc();
+    x.seg(1, d_pprev, psnh);
+    if (c.prior_cell == CELL_GRU) x.acc();   // the gate adjoints above already put their direct part there
+    RUNDX(x, M);
   }
   // ================= initial states, input encoder =================
   {  // one launch (they were seven to nine, each a dependent node of the chain)
@@ -731,8 +658,8 @@ static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, c
   {
     const int TB = T * B;
     // (the activation adjoints in the dX launches' epilogues, as in the slot chain)
-    { Dx x(b.d_pre_disc, rw); x.to(0, nh, b.d_ib, nh).dact(w.ienc_b, nh, ACT_ELU); CK(rundx(L_PREDISC, x, TB)); }
-    { Dx x(b.d_ib, nh); x.to(0, nh, b.d_ia, nh).dact(w.ienc_a, nh, ACT_ELU); CK(rundx(L_IENC1, x, TB)); }
+    { Dx x(h, L_PREDISC, b.d_pre_disc, rw); x.seg(0, b.d_ib, nh).dact(w.ienc_b, nh, ACT_ELU); RUNDX(x, TB); }
+    { Dx x(h, L_IENC1, b.d_ib, nh); x.seg(0, b.d_ia, nh).dact(w.ienc_a, nh, ACT_ELU); RUNDX(x, TB); }
     wgrad(L_PREDISC, {{w.ienc_b, nh}}, b.d_pre_disc, rw, TB);
     wgrad(L_IENC1, {{w.ienc_a, nh}}, b.d_ib, nh, TB);
     wgrad(L_IENC0, {{obs, PL}}, b.d_ia, nh, TB);
@@ -802,6 +729,7 @@ static int sq_backward(SqairHandle* h, const float* flat, const void* packedv, c
     wgrad(L_DISC_S1, {{w.rec_d_all, RW}}, b.d_t1 + ph1 * T1_LD + nh, T1_LD, MT);
     sq_launch_where_param_grads(b.d_tp, TP_LD, b.d_rec_p, w.rec_p_all, noise, T, d, flat_grad, po, s);
   }
+  if (wgrad_rc != 0) return wgrad_rc;
   CK(wbatch.flush(s));
   if (h->padded) sq_flat_gather(h, flat_grad, user_grad, packedv, s);
   SQ_CHECK_HIP(hipGetLastError());

@@ -79,12 +79,12 @@ extern "C" int sqair_compact_bwd_test(SqairHandle* h, const int32_t* src, const 
 // ------------------------------------------------------------------------------------------------
 // The element-wise adjoints of the slot loop on raw device buffers (unit-test entries, tests/test_slot_adjoint_kernels.py): the
 // caller's pointers and pitches reach the launchers of the reverse sweep unchanged; Dims, POff and the parameter offsets are the
-// handle's, through the helpers sq_backward itself calls (sq_train_dims, sq_tail_param_offsets, sq_crop_slots).
+// handle's, through the helpers sq_backward itself calls (sq_pass_dims, sq_tail_param_offsets, sq_crop_slots).
 // ------------------------------------------------------------------------------------------------
 extern "C" int sqair_slot_tail_bwd_test(SqairHandle* h, const SqairSlotTailBwdTest* t, void* stream) {
   SQ_UNIT_ENTRY("sqair_slot_tail_bwd_test");
   if (t->B < 1) return sq_refuse(h, who, "B < 1");
-  const Dims d = sq_train_dims(h, t->B);
+  const Dims d = sq_pass_dims(h, t->B, 0);
   const int nsp = d.nh / 2;
   const bool disc = t->is_disc != 0;
   if (t->slot < 0 || t->slot >= d.N) return sq_refuse(h, who, "slot outside [0, N)");
@@ -111,7 +111,7 @@ extern "C" int sqair_crop_chain_bwd_test(SqairHandle* h, const SqairCropChainBwd
   SQ_UNIT_ENTRY("sqair_crop_chain_bwd_test");
   if (t->B < 1) return sq_refuse(h, who, "B < 1");
   if (t->mode != CROP_PROP1 && t->mode != CROP_PROP2 && t->mode != CROP_DISC) return sq_refuse(h, who, "mode is not 1, 2 or 3");
-  const Dims d = sq_train_dims(h, t->B);
+  const Dims d = sq_pass_dims(h, t->B, 0);
   const bool p1 = t->mode == CROP_PROP1;
   const int nslots = sq_crop_slots(t->mode, d);
   if (!p1 && (t->slot < 0 || t->slot >= d.N)) return sq_refuse(h, who, "slot outside [0, N)");
@@ -141,7 +141,7 @@ extern "C" int sqair_where_param_grads_test(SqairHandle* h, const SqairWherePara
   if (t->T < 1 || t->B < 1) return sq_refuse(h, who, "T < 1 or B < 1");
   if (!t->d_tp || !t->d_rec_p || !t->rec_p || !t->noise || !t->flat_grad) return sq_refuse(h, who, "a required pointer is NULL");
   if (t->tp_ld < 8) return sq_refuse(h, who, "a pitch is smaller than the width");
-  const Dims d = sq_train_dims(h, t->B);
+  const Dims d = sq_pass_dims(h, t->B, 0);
   if ((int64_t)t->T * d.R * d.N > (int64_t)1 << 24) return sq_refuse(h, who, "more than 2^24 (frame, row, slot) rows");
   hipStream_t s = (hipStream_t)stream;
   sq_launch_where_param_grads(t->d_tp, t->tp_ld, t->d_rec_p, t->rec_p, t->noise, t->T, d, t->flat_grad, h->po, s);
@@ -198,7 +198,7 @@ extern "C" int sqair_logprob_bwd_test(SqairHandle* h, const SqairLogprobBwdTest*
       !t->d_spre || !t->flat || !t->flat_grad)
     return sq_refuse(h, who, "a required pointer is NULL");
   if (h->cfg.rec_where_prior && !t->spre) return sq_refuse(h, who, "a required pointer is NULL (spre: the recurrent where prior reads it)");
-  const Dims d = sq_train_dims(h, t->B);
+  const Dims d = sq_pass_dims(h, t->B, 0);
   if (t->ps_ld < 9 + 2 * d.nw) return sq_refuse(h, who, "a pitch is smaller than the width");
   if (sq_logprob_bwd_lds_bytes(d, t->ps_ld) > 150 * 1024) return sq_refuse(h, who, "a pitch asks for more than 150 KB of LDS");
   if (!sq_trainable_frame(h)) return sq_refuse(h, who, std::string(sqair_last_error(h)));
