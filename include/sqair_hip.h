@@ -861,8 +861,8 @@ int sqair_lane_traj_score(SqairHandle* h, const SqairLaneTraj* table, const Sqai
  * treats the id as a 32-bit word: only the pointer the launcher passes changes); refused unless both the score and the identity are
  * set; the identity or the score going off puts it back to 0.
  * Out of scope: carrying lane_id into the object lists of lane tracks and lane forecasts; optimal (Hungarian) assignment (here: step 2
- * as keep + optimal is sqair_set_lane_match's, below; step 4 stays as it is); a motion model for the unseen track; identities across
- * lanes; training passes. */
+ * as keep + optimal is sqair_set_lane_match's, below; step 4 stays as it is); a motion model for the unseen track (not in this
+ * kernel as it stands: sqair_set_motion, the motion paragraph below, is that opt-in); identities across lanes; training passes. */
 #define SQAIR_IDENT_MAX_TRACKS 16
 #define SQAIR_IDENT_COUNTS 8
 typedef struct SqairLaneIdentity {
@@ -893,6 +893,55 @@ int sqair_set_identity(SqairHandle* h, const SqairLaneIdentity* id /* NULL: off 
 int sqair_lane_identity_test(SqairHandle* h, const float* box, const float* presence, const float* obj_id, const float* what /* or NULL */,
                              const int32_t* best_row, int T, int B, const SqairLaneIdentity* id, void* stream);
 int sqair_set_score_ids(SqairHandle* h, int lane_ids /* 0: the estimate's obj_id (default); 1: the identity's lane_id */);
+
+/* ---- lane motion: a constant-velocity filter per track, inside the identity's kernel (the motion paragraph) ---------------------
+ * The identity's position link compares a slot with the track's LAST box and its re-identification searches a disc that grows around
+ * the last position: an object that moves more than about half its size per frame is born again every frame, and one that moves
+ * while unseen returns outside the disc.  With a motion set, the identity's kernel node is REPLACED by a motion instantiation of the
+ * same function (k_lane_identity_motion, or k_lane_identity_motion_opt under sqair_set_lane_match's identity = 1): the same node
+ * count, the same place in the pass, one workgroup per lane.  With it off nothing changes and nothing more is launched: k_lane_identity
+ * is the code it was, and every output, blob and accumulator is unchanged bit for bit.  Needs an identity (sqair_set_identity).
+ * The state, per lane b, entry e < M and axis a in {y, x} of the box CENTRE: five fp32 words trk_kf[b,e,a,0..5) = (p, v, Ppp, Ppv,
+ * Pvv) -- position, velocity in pixels per frame, and their covariance.  It is loaded into LDS with the rest of the table and
+ * written back at the end of the pass.  The sizes h, w are not filtered: trk_box holds the last seen ones, as before.  Free entries
+ * hold whatever they last held and are never read.  The caller starts with zeros.  The scalars: q > 0, the white-acceleration
+ * variance; r > 0, the measurement variance in px^2; v0_var > 0, the velocity variance of a newborn track; gate > 0, in sigmas.
+ * A non-finite lane (best_row[t,b] == -1) is untouched, as in point 0: no predict step, exactly as there is no ageing; its velocity
+ * and nis are 0.  Per finite frame, the identity's points in their order, with these changes:
+ * P. Predict, before point 1, one thread per (entry, axis) of every live entry: p += v; Ppp' = Ppp + 2 Ppv + Pvv + q/4; Ppv' = Ppv +
+ *    Pvv + q/2; Pvv' = Pvv + q; S = Ppp' + r.  The entry's PREDICTED BOX is (p_y - h/2, p_x - w/2, h, w), h and w from trk_box.
+ * 1. The IoU table uses the predicted box where it used trk_box[e].
+ * 4. Tables: for every live e and present j, dy, dx = the slot's centre (fmaf(0.5, h, y), fmaf(0.5, w, x)) minus (p_y, p_x), and
+ *    d2 = dy dy / S_y + dx dx / S_x.  Eligibility becomes d2 <= gate * gate (a NaN never passes): this replaces dc2 <= r * r, and
+ *    reid_dist > 0 remains only the on/off switch of re-identification.  With trk_what the dw <= reid_what gate and the ranking by
+ *    dw stay; without it the ranking key is d2, ties to the smallest e.  Still thread 0's walk, greedy in j.
+ * Points 2, 3, 5, 6, 7 and 8 are untouched, including trk_box taking the slot's words.
+ * U. Update, after the walk, one thread per (slot, axis).  For a slot linked to entry e by point 2 or 4, z its centre coordinate:
+ *    y = z - p; k0 = Ppp'/S; k1 = Ppv'/S; p += k0 y; v += k1 y; Ppp = (1 - k0) Ppp'; Ppv = (1 - k0) Ppv'; Pvv = Pvv' - k1 Ppv'.
+ *    For a slot born in point 6: (p, v, Ppp, Ppv, Pvv) = (z, 0, r, 0, v0_var), no predict in its birth frame.  Entries neither
+ *    linked nor born keep the predicted state: an unseen track coasts at its velocity and its covariance grows, so the gate widens
+ *    by itself.
+ * Outputs per frame: velocity[t,b,j,0..2) = the posterior (v_y, v_x) of the slot's track, 0 for an absent slot, a non-finite lane
+ * and a newborn; nis[t,b,j] (optional) = the d2 of the pair the slot was linked through, 0 for born or absent slots.
+ * All arithmetic is fp32, every array in LDS, one code path for eager, captured and chunked runs: a replayed graph leaves the bits
+ * of eager calls, two passes of six frames leave the bits of one pass of twelve.  A reset of a lane frees its entries as before;
+ * nothing more is needed, a free entry's state is never read.
+ * NULL m: off.  Refused (return -1, text in sqair_last_error, before any HIP call): no identity set (sqair_set_identity); a T other
+ * than the estimate's, a B other than the state's; any of q, r, v0_var, gate not finite and positive; a NULL trk_kf or velocity.
+ * The identity going off (sqair_set_identity(NULL), or the estimate or the state taking it along) switches the motion off.
+ * Out of scope: filtering h, w; the particles' spread as r; lane_id and velocity in the object lists of lane tracks and lane
+ * forecasts; training passes; identities across lanes. */
+typedef struct SqairLaneMotion {
+  float q, r, v0_var, gate;
+  float* trk_kf;     /* [B,M,2,5] in/out, persists; caller starts with zeros */
+  float* velocity;   /* [T,B,N,2] required */
+  float* nis;        /* [T,B,N]   optional */
+} SqairLaneMotion;
+int sqair_set_motion(SqairHandle* h, const SqairLaneMotion* m /* NULL: off */, int T, int B);
+/* Kernel-level check of the motion (tests): sqair_lane_identity_test with the motion instantiation on caller buffers.  NULL m: exactly
+ * sqair_lane_identity_test.  Refused (return -1, before any HIP call): what that entry refuses, what sqair_set_motion refuses for m. */
+int sqair_lane_identity_motion_test(SqairHandle* h, const float* box, const float* presence, const float* obj_id, const float* what,
+                                    const int32_t* best_row, int T, int B, const SqairLaneIdentity* id, const SqairLaneMotion* m, void* stream);
 
 /* ---- IDF1 scoring: does an identity stay on an object over its life -- global identity assignment, solved on the device ---------
  * The score's idsw counts the moments an identity changes on a greedy per-frame match; it cannot say for how long the wrong id then

@@ -160,6 +160,24 @@ def identity_memory_shapes(B, M, nw):
                 counts=(B, len(IDENT_COUNTS)))
 
 
+# lane motion (include/sqair_hip.h: sqair_set_motion): the scalars of SqairLaneMotion, its state and its per-frame outputs, which
+# keep their names in a step's ``lane`` dict; the five words of the state per (entry, axis)
+MOTION_SCALARS = tuple(n for n, t in _STRUCTS["SqairLaneMotion"]._fields_ if t is not C.c_void_p)
+MOTION_MEMORY = ("trk_kf",)
+MOTION_FIELDS = _pointers("SqairLaneMotion", without=MOTION_MEMORY)
+MOTION_STATE = ("p", "v", "Ppp", "Ppv", "Pvv")
+
+
+def motion_shapes(T, B, N):
+    """The per-frame outputs' shapes for passes of T frames."""
+    return dict(velocity=(T, B, N, 2), nis=(T, B, N))
+
+
+def motion_memory_shapes(B, M):
+    """The filter state's shape for M track entries per lane: (y, x) x MOTION_STATE."""
+    return dict(trk_kf=(B, M, 2, len(MOTION_STATE)))
+
+
 # trajectory scoring (include/sqair_hip.h: sqair_lane_traj_score): the three structs' pointer fields in declaration order -- of
 # SqairTrajScore the accumulators, then the per-call outputs and the int32 ones among them --, the columns of ``counts`` [F, B, .],
 # ``sums`` [F, B, .] and ``lane_counts`` [B, .]

@@ -456,6 +456,8 @@ struct LaneIdentArgs {
   SqairLaneIdentity id;                // the scalars, the memory, the counters and the per-frame outputs
   int T, B, N, nw;
   int match;                           // sqair_set_lane_match's identity, step 2: 0 = k_lane_identity, 1 = k_lane_identity_opt
+  int motion;                          // sqair_set_motion: 0 = the kernels above; 1 = k_lane_identity_motion / _motion_opt, which read mo
+  SqairLaneMotion mo;                  // the filter's scalars, its state and the per-frame outputs; zeros while motion is 0
 };
 int sq_launch_lane_identity(const LaneIdentArgs& a, hipStream_t s);
 // Trajectory scoring (sqair_lane_traj_score; include/sqair_hip.h states the semantics): k_lane_traj_score, grid (lane b, chunk of

@@ -47,6 +47,8 @@ struct SqLaneSet {
   SqairLaneLayers lay = {};
   bool ident_on = false;
   SqairLaneIdentity ident = {};
+  bool motion_on = false;          // sqair_set_motion: the identity's launch is its motion instantiation; only ever on with the identity
+  SqairLaneMotion motion = {};
   bool score_on = false;
   SqairLaneScore score = {};
   bool score_ids = false;

@@ -695,7 +695,12 @@ int sq_launch_lane_score(const LaneScoreArgs& a, hipStream_t s) {
 // OPT (sqair_set_lane_match, identity = 1): wave 0 makes step 2's assignment (sq_assign_keep_optimal) where thread 0 walks the
 // greedy one; the re-identification, the births and the ageing are thread 0's walk either way.  OPT = false is k_lane_identity as
 // it always was.
-template <bool OPT>
+// MOTION (sqair_set_motion; the motion paragraph of include/sqair_hip.h, points P and U): a constant-velocity filter per entry and
+// axis of the box centre, its five words (p, v, Ppp, Ppv, Pvv) in LDS with the rest of the table.  Threads i < 2M predict before step 1
+// (one barrier more, under the same uniform condition), step 1 reads the predicted box, s_dc2 holds d2 where it holds dc2, step 4's gate is
+// d2 <= gate * gate, and threads i < 2N update (or start) the filter of the entry their slot took and write velocity and nis.
+// MOTION = false is the code above, statement for statement.
+template <bool OPT, bool MOTION>
 __device__ __forceinline__ void sq_lane_identity_frames(const LaneIdentArgs& a) {
   __shared__ float s_iou[SQ_IDENT_MAXM * SQ_MAXN], s_dc2[SQ_IDENT_MAXM * SQ_MAXN], s_dw[SQ_IDENT_MAXM * SQ_MAXN];
   __shared__ float s_tbox[SQ_IDENT_MAXM * 4], s_twhat[SQ_IDENT_MAXM * SQ_MAX_NWHAT];
@@ -705,6 +710,10 @@ __device__ __forceinline__ void sq_lane_identity_frames(const LaneIdentArgs& a) 
   const SqairLaneIdentity& o = a.id;
   const int b = blockIdx.x, tid = threadIdx.x, M = o.M, N = a.N, nw = a.nw;
   const bool reid = o.reid_dist > 0.0f, app = o.trk_what != nullptr;
+  __shared__ float s_kf[MOTION ? SQ_IDENT_MAXM * 2 * 5 : 1], s_S[MOTION ? SQ_IDENT_MAXM * 2 : 1];   // (p, v, Ppp, Ppv, Pvv) and S per (entry, axis)
+  const SqairLaneMotion& mo = a.mo;
+  if constexpr (MOTION)
+    if (tid < M * 10) s_kf[tid] = mo.trk_kf[(size_t)b * M * 10 + tid];
   if (tid < M) {
     const size_t e = (size_t)b * M + tid;
     s_tid[tid] = o.trk_id[e]; s_word[tid] = o.trk_word[e]; s_age[tid] = o.trk_age[e]; s_len[tid] = o.trk_len[e];
@@ -725,7 +734,25 @@ __device__ __forceinline__ void sq_lane_identity_frames(const LaneIdentArgs& a) 
         if (o.how) o.how[tb * N + tid] = -1;
         if (o.track_len) o.track_len[tb * N + tid] = -1;
       }
+      if constexpr (MOTION) {
+        if (tid < N * 2) mo.velocity[tb * N * 2 + tid] = 0.0f;
+        if (tid < N && mo.nis) mo.nis[tb * N + tid] = 0.0f;
+      }
       continue;
+    }
+    // ---- P: every live entry's filter one frame on, per (entry, axis)
+    if constexpr (MOTION) {
+      if (tid < M * 2 && s_tid[tid >> 1] >= 0) {
+        float* k = s_kf + tid * 5;
+        const float v = k[1], ppp = k[2], ppv = k[3], pvv = k[4];
+        const float npp = ((ppp + 2.0f * ppv) + pvv) + 0.25f * mo.q;
+        k[0] = k[0] + v;
+        k[2] = npp;
+        k[3] = (ppv + pvv) + 0.5f * mo.q;
+        k[4] = pvv + mo.q;
+        s_S[tid] = npp + mo.r;
+      }
+      __syncthreads();
     }
     // ---- 1 (and 4's tables): entry e against slot j
     if (tid < M * N) {
@@ -733,11 +760,22 @@ __device__ __forceinline__ void sq_lane_identity_frames(const LaneIdentArgs& a) 
       float v = -1.0f, dc2 = 0.0f, dw = 0.0f;
       if (s_tid[e] >= 0 && a.presence[tb * N + j] != 0.0f) {
         const float* q = a.box + (tb * N + j) * 4;
-        const SqBox p = {s_tbox[e * 4 + 0], s_tbox[e * 4 + 1], s_tbox[e * 4 + 2], s_tbox[e * 4 + 3]}, bx = {q[0], q[1], q[2], q[3]};
+        SqBox p = {s_tbox[e * 4 + 0], s_tbox[e * 4 + 1], s_tbox[e * 4 + 2], s_tbox[e * 4 + 3]};
+        const SqBox bx = {q[0], q[1], q[2], q[3]};
+        if constexpr (MOTION) {   // the predicted box: the filter's centre, the last seen size
+          p.y = s_kf[e * 10] - 0.5f * p.h;
+          p.x = s_kf[e * 10 + 5] - 0.5f * p.w;
+        }
         v = sq_box_iou(p, bx);
+        if constexpr (MOTION) {
+          const float dy = fmaf(0.5f, bx.h, bx.y) - s_kf[e * 10], dx = fmaf(0.5f, bx.w, bx.x) - s_kf[e * 10 + 5];
+          dc2 = (dy * dy) / s_S[e * 2] + (dx * dx) / s_S[e * 2 + 1];
+        }
         if (reid) {
-          const float dy = fmaf(0.5f, bx.h, bx.y) - fmaf(0.5f, p.h, p.y), dx = fmaf(0.5f, bx.w, bx.x) - fmaf(0.5f, p.w, p.x);
-          dc2 = fmaf(dy, dy, dx * dx);
+          if constexpr (!MOTION) {
+            const float dy = fmaf(0.5f, bx.h, bx.y) - fmaf(0.5f, p.h, p.y), dx = fmaf(0.5f, bx.w, bx.x) - fmaf(0.5f, p.w, p.x);
+            dc2 = fmaf(dy, dy, dx * dx);
+          }
           if (app) {
             const float* wj = a.what + (tb * N + j) * nw;
             float acc = 0.0f;
@@ -778,8 +816,12 @@ __device__ __forceinline__ void sq_lane_identity_frames(const LaneIdentArgs& a) 
           float bk = 0.0f;
           for (int e = 0; e < M; ++e) {
             if (s_tid[e] < 0 || s_em[e] >= 0) continue;
-            const float r = o.reid_dist * (float)(s_age[e] + 1);
-            if (!(s_dc2[e * N + j] <= r * r)) continue;
+            if constexpr (MOTION) {
+              if (!(s_dc2[e * N + j] <= mo.gate * mo.gate)) continue;
+            } else {
+              const float r = o.reid_dist * (float)(s_age[e] + 1);
+              if (!(s_dc2[e * N + j] <= r * r)) continue;
+            }
             if (app && !(s_dw[e * N + j] <= o.reid_what)) continue;
             const float key = app ? s_dw[e * N + j] : s_dc2[e * N + j];
             if (be < 0 || key < bk) { be = e; bk = key; }
@@ -824,6 +866,33 @@ __device__ __forceinline__ void sq_lane_identity_frames(const LaneIdentArgs& a) 
       if (o.how) o.how[tb * N + tid] = s_how[tid];
       if (o.track_len) o.track_len[tb * N + tid] = e >= 0 ? s_len[e] : -1;
     }
+    // ---- U: the filter of every entry a slot took, per (slot, axis): the update of a linked one, the start of a born one
+    if constexpr (MOTION) {
+      if (tid < N * 2) {
+        const int j = tid >> 1, ax = tid & 1, e = s_je[j];
+        float vel = 0.0f, nis = 0.0f;
+        if (e >= 0) {
+          const float* q = a.box + (tb * N + j) * 4;
+          const float z = fmaf(0.5f, q[2 + ax], q[ax]);
+          float* k = s_kf + (e * 2 + ax) * 5;
+          if (s_how[j] == 0) {
+            k[0] = z; k[1] = 0.0f; k[2] = mo.r; k[3] = 0.0f; k[4] = mo.v0_var;
+          } else {
+            const float S = s_S[e * 2 + ax], ppp = k[2], ppv = k[3];
+            const float y = z - k[0], k0 = ppp / S, k1 = ppv / S;
+            k[0] = fmaf(k0, y, k[0]);
+            vel = fmaf(k1, y, k[1]);
+            k[1] = vel;
+            k[2] = (1.0f - k0) * ppp;
+            k[3] = (1.0f - k0) * ppv;
+            k[4] = fmaf(-k1, ppv, k[4]);
+            nis = s_dc2[e * N + j];
+          }
+        }
+        mo.velocity[tb * N * 2 + tid] = vel;
+        if (ax == 0 && mo.nis) mo.nis[tb * N + j] = nis;
+      }
+    }
     if (tid < N * 4) {
       const int j = tid >> 2, e = s_je[j];
       if (e >= 0) sq_put(s_tbox + e * 4 + (tid & 3), sq_word(a.box + (tb * N + j) * 4 + (tid & 3)));
@@ -842,6 +911,8 @@ __device__ __forceinline__ void sq_lane_identity_frames(const LaneIdentArgs& a) 
   if (tid < M * 4) sq_put(o.trk_box + (size_t)b * M * 4 + tid, sq_word(s_tbox + tid));
   if (app)
     for (int i = tid; i < M * nw; i += 256) sq_put(o.trk_what + (size_t)b * M * nw + i, sq_word(s_twhat + i));
+  if constexpr (MOTION)
+    if (tid < M * 10) sq_put(mo.trk_kf + (size_t)b * M * 10 + tid, sq_word(s_kf + tid));
   if (tid == 0) {
     o.next_id[b] = next;
     int64_t* c = o.counts + (size_t)b * SQAIR_IDENT_COUNTS;
@@ -850,14 +921,24 @@ __device__ __forceinline__ void sq_lane_identity_frames(const LaneIdentArgs& a) 
 }
 __global__ __launch_bounds__(256) void k_lane_identity(const LaneIdentArgs a SQ_TLP) {
   SQ_TL_SCOPE;
-  sq_lane_identity_frames<false>(a);
+  sq_lane_identity_frames<false, false>(a);
 }
 __global__ __launch_bounds__(256) void k_lane_identity_opt(const LaneIdentArgs a SQ_TLP) {
   SQ_TL_SCOPE;
-  sq_lane_identity_frames<true>(a);
+  sq_lane_identity_frames<true, false>(a);
+}
+__global__ __launch_bounds__(256) void k_lane_identity_motion(const LaneIdentArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  sq_lane_identity_frames<false, true>(a);
+}
+__global__ __launch_bounds__(256) void k_lane_identity_motion_opt(const LaneIdentArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  sq_lane_identity_frames<true, true>(a);
 }
 int sq_launch_lane_identity(const LaneIdentArgs& a, hipStream_t s) {
-  if (a.match) SQ_LAUNCH(k_lane_identity_opt, dim3(a.B), dim3(256), 0, s, a);
+  if (a.motion && a.match) SQ_LAUNCH(k_lane_identity_motion_opt, dim3(a.B), dim3(256), 0, s, a);
+  else if (a.motion) SQ_LAUNCH(k_lane_identity_motion, dim3(a.B), dim3(256), 0, s, a);
+  else if (a.match) SQ_LAUNCH(k_lane_identity_opt, dim3(a.B), dim3(256), 0, s, a);
   else SQ_LAUNCH(k_lane_identity, dim3(a.B), dim3(256), 0, s, a);
   return 0;
 }

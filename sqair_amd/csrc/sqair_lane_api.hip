@@ -1,6 +1,6 @@
 // libsqair_hip.so -- the lane answers on the native side of the C ABI (include/sqair_hip.h): the estimate and its followers, the
 // layers, the identity, the score, the IDF1 table and the HOTA log.  Their registration on a handle as one block (SqLaneSet, sqair_internal.h:
-// sqair_set_estimate / _layers / _score / _identity / _score_ids / _idf / _hota), the estimate's refusal of a pass, ONE builder per kernel's arguments -- called by the
+// sqair_set_estimate / _layers / _score / _identity / _motion / _score_ids / _idf / _hota), the estimate's refusal of a pass, ONE builder per kernel's arguments -- called by the
 // pass and by the kernel-level entry point alike --, the pass's launch sequence (sq_launch_lane_answers, called by sq_forward_impl
 // with the block sq_resolve_pass resolved) and the stand-alone entry points (sqair_lane_*_test, sqair_lane_traj_score,
 // sqair_lane_idf_solve, sqair_lane_hota_solve).  Host code
@@ -61,6 +61,14 @@ static int sq_identity_fields(SqairHandle* h, const std::string& who, const Sqai
     return sq_no(h, who + "trk_id, trk_word, trk_age, trk_len, trk_box, next_id, counts and lane_id must not be NULL");
   return 0;
 }
+static int sq_motion_fields(SqairHandle* h, const std::string& who, const SqairLaneMotion& m) {
+  const float v[4] = {m.q, m.r, m.v0_var, m.gate};
+  const char* name[4] = {"q", "r", "v0_var", "gate"};
+  for (int i = 0; i < 4; ++i)
+    if (!(v[i] > 0.0f) || !std::isfinite(v[i])) return sq_no(h, who + name[i] + " must be finite and > 0");   // (NaN fails)
+  if (!m.trk_kf || !m.velocity) return sq_no(h, who + "trk_kf and velocity must not be NULL");
+  return 0;
+}
 
 // ------------------------------------------------------------------------------------------------
 // registration: the handle's block, h->lane.  Switching the estimate off is h->lane = SqLaneSet{}: its followers go with it
@@ -72,7 +80,9 @@ static void sq_idf_off(SqLaneSet& l) { l.idf_on = false; l.idf = SqairLaneIdf{};
 // (and so does the HOTA log: the truth and the id words are the score's)
 static void sq_hota_off(SqLaneSet& l) { l.hota_on = false; l.hota = SqairLaneHota{}; }
 static void sq_score_off(SqLaneSet& l) { l.score_on = false; l.score = SqairLaneScore{}; l.score_ids = false; sq_idf_off(l); sq_hota_off(l); }
-static void sq_identity_off(SqLaneSet& l) { l.ident_on = false; l.ident = SqairLaneIdentity{}; l.score_ids = false; }
+// (the motion filter is a mode of the identity's launch: it goes off with it)
+static void sq_motion_off(SqLaneSet& l) { l.motion_on = false; l.motion = SqairLaneMotion{}; }
+static void sq_identity_off(SqLaneSet& l) { l.ident_on = false; l.ident = SqairLaneIdentity{}; l.score_ids = false; sq_motion_off(l); }
 // what the followers need of the estimate they read (best_row is never NULL in a registered estimate; `what`: the identity keeps an
 // appearance, trk_what, and reads the estimate's)
 static bool sq_estimate_scorable(const SqairLaneEstimate& e) { return e.box && e.presence && e.obj_id && e.map_count; }
@@ -195,6 +205,19 @@ extern "C" int sqair_set_identity(SqairHandle* h, const SqairLaneIdentity* id, i
   h->lane.ident_on = true; h->lane.ident = *id;
   return 0;
 }
+extern "C" int sqair_set_motion(SqairHandle* h, const SqairLaneMotion* m, int T, int B) {
+  if (!h) return -1;
+  if (!m) {
+    sq_motion_off(h->lane);
+    return 0;
+  }
+  const std::string who = "sqair_set_motion: ";
+  if (!h->state_on || !h->lane.est_on || !h->lane.ident_on)
+    return sq_no(h, who + "needs an identity (sqair_set_identity): the filter lives in the track table it keeps");
+  if (sq_follower_shape_refusal(h, who, T, B) != 0 || sq_motion_fields(h, who, *m) != 0) return -1;
+  h->lane.motion_on = true; h->lane.motion = *m;
+  return 0;
+}
 // per-frame matching (include/sqair_hip.h: sqair_set_lane_match): a plain setting of the handle, no registration; the pass reads it
 // through its resolved block (sq_resolve_pass), the stand-alone entry points read it at their launch
 extern "C" int sqair_set_lane_match(SqairHandle* h, int score, int identity, int traj_link) {
@@ -238,10 +261,12 @@ static LaneLayerArgs sq_layers_args(const SqairConfig& c, const LaneRows& rows, 
 }
 // (`what` is read only by an identity that keeps an appearance, trk_what)
 static LaneIdentArgs sq_identity_args(const SqairConfig& c, const float* box, const float* presence, const float* obj_id, const float* what,
-                                      const int32_t* best_row, const SqairLaneIdentity& id, int T, int B, int match) {
+                                      const int32_t* best_row, const SqairLaneIdentity& id, int T, int B, int match,
+                                      const SqairLaneMotion* motion = nullptr) {
   LaneIdentArgs a; memset(&a, 0, sizeof(a));
   a.box = box; a.presence = presence; a.obj_id = obj_id; a.best_row = best_row; a.what = id.trk_what ? what : nullptr; a.id = id;
   a.T = T; a.B = B; a.N = c.n_steps_per_image; a.nw = c.n_what; a.match = match;
+  if (motion) { a.motion = 1; a.mo = *motion; }
   return a;
 }
 static LaneScoreArgs sq_score_args(const SqairConfig& c, const float* box, const float* presence, const float* obj_id,
@@ -292,7 +317,10 @@ int sq_launch_lane_answers(SqairHandle* h, const SqLaneSet& l, const float* rec,
     return -2;
   }
   // lane identities: the lane's objects linked to the lane's track table (sqair_set_identity), updated in place
-  if (l.ident_on) sq_launch_lane_identity(sq_identity_args(c, e.box, e.presence, e.obj_id, e.what, e.best_row, l.ident, T, B, l.ident_match), s);
+  // (sqair_set_motion: the same node, in its motion instantiation)
+  if (l.ident_on)
+    sq_launch_lane_identity(sq_identity_args(c, e.box, e.presence, e.obj_id, e.what, e.best_row, l.ident, T, B, l.ident_match,
+                                             l.motion_on ? &l.motion : nullptr), s);
   // stream scoring: the lane answer against the caller's ground truth (sqair_set_score), accumulated in place.  sqair_set_score_ids:
   // the kernel takes the id as a 32-bit word, so the identity's int32 lane_id stands where obj_id stands
   if (l.score_on) {
@@ -361,6 +389,20 @@ extern "C" int sqair_lane_identity_test(SqairHandle* h, const float* box, const 
   if (sq_identity_fields(h, who, *id) != 0) return -1;
   if (id->trk_what && !what) return sq_no(h, who + "id->trk_what needs what");
   sq_launch_lane_identity(sq_identity_args(h->cfg, box, presence, obj_id, what, best_row, *id, T, B, h->match_ident), (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+extern "C" int sqair_lane_identity_motion_test(SqairHandle* h, const float* box, const float* presence, const float* obj_id, const float* what,
+                                               const int32_t* best_row, int T, int B, const SqairLaneIdentity* id, const SqairLaneMotion* m,
+                                               void* stream) {
+  if (!h) return -1;
+  if (!m) return sqair_lane_identity_test(h, box, presence, obj_id, what, best_row, T, B, id, stream);
+  const std::string who = "sqair_lane_identity_motion_test: ";
+  if (!box || !presence || !obj_id || !best_row || !id || T < 1 || B < 1 || T > 65535)
+    return sq_no(h, who + "null box / presence / obj_id / best_row / id or bad T / B");
+  if (sq_identity_fields(h, who, *id) != 0 || sq_motion_fields(h, who, *m) != 0) return -1;
+  if (id->trk_what && !what) return sq_no(h, who + "id->trk_what needs what");
+  sq_launch_lane_identity(sq_identity_args(h->cfg, box, presence, obj_id, what, best_row, *id, T, B, h->match_ident, m), (hipStream_t)stream);
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -38,6 +38,17 @@ within a lane.  ``score_ids="lane"`` (with ``score=True``) makes the score count
 ``obj_id``.  ``identity_match="optimal"`` makes the position link keep + optimal where it is keep + greedy (sqair_set_lane_match);
 re-identification, births and ageing are the same either way.
 
+``motion=True`` (with ``identity=True``): every track also carries a constant-velocity Kalman filter of its box centre, inside the
+identity's kernel (sqair_set_motion: the same node, no launch more).  The position link then compares a slot with the track's
+PREDICTED box, and re-identification gates on the normalised innovation -- d2 <= ``motion_gate``^2 sigmas -- where it searched a disc
+of ``identity_reid_dist`` pixels per frame unseen (``identity_reid_dist`` > 0 stays its on/off switch): a fast object keeps its id,
+and an object that moved while unseen is found where it went.  ``motion_q`` is the white-acceleration variance, ``motion_r`` the
+measurement variance in px^2, ``motion_v0`` the velocity variance of a newborn track.  ``out["lane"]`` gains ``velocity``
+[T', B, N, 2] = (v_y, v_x) in pixels per frame, 0 for an absent slot and a newborn, and with ``motion_nis=True`` also ``nis`` [T', B, N],
+the d2 of the pair each slot was linked through.  ``identities()`` gains ``trk_centre``, ``trk_vel``, ``trk_sigma`` [B, M, 2]
+(= sqrt(Ppp)) and ``trk_pred_box`` [B, M, 4], the coasted box of every live track: for ``trk_age`` > 0 that is where the filter
+thinks the unseen object is.
+
 ``score_idf=True`` (with ``score=True``): the score's idsw counts the moments an identity changes, not for how long the wrong id then
 stays.  The stream then also keeps, per lane and on the device, how many frames of the open clip every truth overlapped (IoU >=
 ``score_iou``) every predicted id -- the id words the score reads: ``obj_id``, or ``lane_id`` with ``score_ids="lane"`` --, up to
@@ -182,7 +193,8 @@ class LaneAnswers(object):
     def __init__(self, who, estimate, estimate_iou, estimate_canvas, estimate_layers, layers_cover_min, score, score_iou, score_truth,
                  identity, identity_iou, identity_tracks, identity_max_age, identity_reid_dist, identity_reid_what, identity_appearance,
                  score_ids, score_idf=False, score_idf_ids=32, score_match="greedy", identity_match="greedy", score_hota=False,
-                 score_hota_ids=32, score_hota_frames=256):
+                 score_hota_ids=32, score_hota_frames=256, motion=False, motion_q=0.25, motion_r=1.0, motion_v0=16.0, motion_gate=3.0,
+                 motion_nis=False):
         self.step_fn, who = who + ".step: ", who + ": "
 
         def bad(why):
@@ -218,6 +230,15 @@ class LaneAnswers(object):
             bad("identity_reid_dist must be >= 0")
         if identity and not self.reid_what > 0.0:   # (NaN fails too)
             bad("identity_reid_what must lie in (0, +inf]")
+        if motion and not identity:
+            bad("motion is for a stream with identity=True")
+        if motion_nis and not motion:
+            bad("motion_nis is for a stream with motion=True")
+        self.motion_scalars = dict(q=float(motion_q), r=float(motion_r), v0_var=float(motion_v0), gate=float(motion_gate))
+        for name, v in zip(("motion_q", "motion_r", "motion_v0", "motion_gate"), self.motion_scalars.values()):
+            if motion and not 0.0 < v < float("inf"):   # (NaN fails too)
+                bad(name + " must be finite and > 0")
+        self.motion, self.motion_nis = bool(motion), bool(motion_nis)
         if score_ids not in ("row", "lane"):
             bad("score_ids must be 'row' or 'lane'")
         if score_ids == "lane" and not (score and identity):
@@ -277,6 +298,8 @@ class LaneAnswers(object):
         if self.identified:
             shapes.update(_capi.identity_shapes(T, B, N))
             ints = ints + tuple(_capi.IDENT_LANE_NAMES[n] for n in _capi.IDENT_INT_FIELDS)
+        if self.motion:
+            shapes.update({n: s for n, s in _capi.motion_shapes(T, B, N).items() if n != "nis" or self.motion_nis})
         self.flat, self.views = field_views(shapes, ints, core.device)
         est = self.est = self.views(self.flat)
         sync = torch.cuda.current_stream(core.device).synchronize   # (a buffer's initial values are in place before a pass reads it)
@@ -307,6 +330,12 @@ class LaneAnswers(object):
                                           **{n: est[_capi.IDENT_LANE_NAMES[n]].data_ptr() for n in _capi.IDENT_FIELDS})
             sync()
             core.check(lib.sqair_set_identity(h, C.byref(idt), T, B), "sqair_set_identity")
+            if self.motion:   # the filter's state beside the track table: the identity's node in its motion instantiation
+                self.ident_buf.update(zeros_of("SqairLaneMotion", _capi.motion_memory_shapes(B, self.M), core.device))
+                mo = _capi.SqairLaneMotion(trk_kf=self.ident_buf["trk_kf"].data_ptr(), **self.motion_scalars,
+                                           **{n: est[n].data_ptr() for n in _capi.MOTION_FIELDS if n in est})
+                sync()
+                core.check(lib.sqair_set_motion(h, C.byref(mo), T, B), "sqair_set_motion")
             if self.score_ids == "lane":
                 core.check(lib.sqair_set_score_ids(h, 1), "sqair_set_score_ids")
         if self.idf:   # the overlap table of every lane's open clip, the totals over the closed ones, and what a solve writes
@@ -472,10 +501,16 @@ class LaneAnswers(object):
     def identities(self):
         if not self.identified:
             raise ValueError("SqairStream.identities: the stream keeps no identities (SqairStream(..., estimate=True, identity=True))")
-        got = read_back(self.core, {n: self.ident_buf[n] for n in ("counts", "next_id", "trk_id", "trk_age", "trk_len", "trk_box")})
+        names = ("counts", "next_id", "trk_id", "trk_age", "trk_len", "trk_box") + (_capi.MOTION_MEMORY if self.motion else ())
+        got = read_back(self.core, {n: self.ident_buf[n] for n in names})
         res = _columns(got.pop("counts"), _capi.IDENT_COUNTS)
         tot = {n: int(v.sum()) for n, v in res.items()}
         res.update(got)
+        if self.motion:   # the filter's state by name; the coasted box is formed here, on the host, from the table read back
+            kf = _columns(res.pop("trk_kf"), _capi.MOTION_STATE)
+            res["trk_centre"], res["trk_vel"], res["trk_sigma"] = kf["p"], kf["v"], kf["Ppp"].sqrt()
+            size = res["trk_box"][..., 2:]
+            res["trk_pred_box"] = torch.cat([kf["p"] - 0.5 * size, size], -1)
         res["bridged_rate"] = _ratio(tot["bridged"], tot["objects"])
         res["reidentified_rate"] = _ratio(tot["reidentified"], tot["objects"])
         return res

@@ -41,7 +41,7 @@ network "see" an empty scene and kill the objects.
 
 With ``estimate=True`` a step also returns ``out["lane"]``: one answer per lane and frame from the K particles, and its followers
 say more about it, each one more kernel of the pass -- ``estimate_layers`` which pixels each object occupies, ``identity`` a track id
-that stays on an object, ``score`` the CLEAR-MOT events against a step's ``truth`` (``score()``, ``identities()``; ``score_match`` / ``identity_match`` =
+that stays on an object (``motion``: with a velocity filter per track inside the same kernel, sqair_set_motion), ``score`` the CLEAR-MOT events against a step's ``truth`` (``score()``, ``identities()``; ``score_match`` / ``identity_match`` =
 "optimal": their per-frame matching as keep + optimal, sqair_set_lane_match), ``score_idf`` the identity overlap table
 IDF1 is solved from (``idf_score()``), ``score_hota`` the clip log HOTA is solved from (``hota_score()``); ``forecast`` and
 ``tracks`` with ``lane=True, truth=...`` score the lane forecast and the lane tracks (``trajectory_score(kind)``).  sqair_amd/lane.py
@@ -76,7 +76,8 @@ class SqairStream(object):
                  estimate_iou=0.5, estimate_canvas=False, estimate_layers=False, layers_cover_min=0.5, score=False, score_iou=0.5,
                  score_truth=None, identity=False, identity_iou=0.3, identity_tracks=None, identity_max_age=10, identity_reid_dist=4.0,
                  identity_reid_what=float("inf"), identity_appearance=True, score_ids="row", score_idf=False, score_idf_ids=32,
-                 score_match="greedy", identity_match="greedy", score_hota=False, score_hota_ids=32, score_hota_frames=256):
+                 score_match="greedy", identity_match="greedy", score_hota=False, score_hota_ids=32, score_hota_frames=256,
+                 motion=False, motion_q=0.25, motion_r=1.0, motion_v0=16.0, motion_gate=3.0, motion_nis=False):
         if core.cfg.sample_from_prior:
             raise ValueError("SqairStream: generation modes (sample_from_prior) do not carry a state across calls")
         if resample not in (None, "systematic"):
@@ -87,7 +88,8 @@ class SqairStream(object):
         la = self.lane = LaneAnswers("SqairStream", estimate, estimate_iou, estimate_canvas, estimate_layers, layers_cover_min, score,
                                      score_iou, score_truth, identity, identity_iou, identity_tracks, identity_max_age,
                                      identity_reid_dist, identity_reid_what, identity_appearance, score_ids, score_idf, score_idf_ids,
-                                     score_match, identity_match, score_hota, score_hota_ids, score_hota_frames)   # (checks only)
+                                     score_match, identity_match, score_hota, score_hota_ids, score_hota_frames, motion, motion_q,
+                                     motion_r, motion_v0, motion_gate, motion_nis)   # (checks only)
         self.smc = resample is not None
         self.ess_frac = ess_frac
         self.core = core
@@ -276,7 +278,8 @@ class SqairStream(object):
         ``objects``, ``kept``, ``bridged``, ``reidentified``, ``born``, ``ended`` [B] and ``next_id`` [B]; pooled over the lanes
         ``bridged_rate`` = bridged / objects and ``reidentified_rate`` = reidentified / objects (NaN without objects); and the track
         table ``trk_id``, ``trk_age``, ``trk_len`` [B, M] and ``trk_box`` [B, M, 4] (host tensors): the entries with ``trk_id`` >= 0 and
-        ``trk_age`` > 0 are the tracks remembered but currently unseen."""
+        ``trk_age`` > 0 are the tracks remembered but currently unseen.  With ``motion=True`` also the filter's state (sqair_set_motion):
+        ``trk_centre``, ``trk_vel``, ``trk_sigma`` [B, M, 2] and ``trk_pred_box`` [B, M, 4], the coasted box of every live track."""
         return self.lane.identities()
 
     # ---- trajectory scoring ------------------------------------------------------------------------------------------------

@@ -85,6 +85,13 @@ resampler's node of the same run; the median time of ``hota_score()`` -- the sol
 -- is measured separately at ``score_hota_frames`` 64 and 256.  Recorded, not gated on:
 
     python tools/stream_time.py --hota [--out profiles/stream_hota_time.json]
+
+With --motion: the price of lane motion (SqairStream(estimate=True, identity=True, motion=True), include/sqair_hip.h: sqair_set_motion)
+-- the identity's node in its motion instantiation, no node more.  Streams at cfg-2's batch alternating in one process as with
+--history, all with SMC and the estimate: SMC, SMC + estimate, identity, motion, motion with nis, identity optimal, motion optimal.  The
+difference motion - identity is reported next to the identity's and the resampler's node of the same run.  Recorded, not gated on:
+
+    python tools/stream_time.py --motion [--out profiles/stream_motion_time.json]
 """
 import argparse
 import json
@@ -478,6 +485,28 @@ def time_match(B, K, N, steps, warmup, rounds=10, hw=(50, 50)):
     return res
 
 
+def time_motion(B, K, N, steps, warmup, rounds=10, hw=(50, 50)):
+    smc = dict(resample="systematic", ess_frac=0.5)
+    est = dict(estimate=True, **smc)
+    idt = dict(est, identity=True)
+    legs = dict(plain={}, smc=smc, smc_estimate=est, identity=idt, motion=dict(idt, motion=True), motion_nis=dict(idt, motion=True, motion_nis=True),
+                identity_optimal=dict(idt, identity_match="optimal"), motion_optimal=dict(idt, identity_match="optimal", motion=True))
+    streams, res, med, thr = alternating_streams(legs, B, K, N, steps, warmup, rounds, hw)
+    res["lane_bytes_per_step"] = {n: int(streams[n]._est_flat.numel() * 4) for n in ("identity", "motion", "motion_nis")}
+    res["identities"] = {m: {n: (int(v.sum()) if torch.is_tensor(v) and v.dim() == 1 else v)
+                             for n, v in streams[m].identities().items() if not n.startswith("trk_")} for m in ("identity", "motion")}
+    for key, v in (("latency", med), ("back_to_back", thr)):
+        one_node = v["smc"] - v["plain"]            # the yardstick: one dependent node (the resampler) on this machine, this run
+        added = dict(identity_node=v["identity"] - v["smc_estimate"], motion_node=v["motion"] - v["smc_estimate"],
+                     motion_minus_identity=v["motion"] - v["identity"], motion_nis_minus_identity=v["motion_nis"] - v["identity"],
+                     motion_optimal_minus_identity_optimal=v["motion_optimal"] - v["identity_optimal"])
+        res["us_" + key] = dict(smc_node=1e3 * one_node, **{n: 1e3 * a for n, a in added.items()},
+                                **{n + "_over_smc_node": (a / one_node if one_node > 0 else None) for n, a in added.items()})
+    for st in streams.values():
+        st.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=500)
@@ -494,10 +523,13 @@ def main():
     ap.add_argument("--idf", action="store_true", help="score and score + IDF, each with and without SMC, alternating; idf_score() apart (profiles/stream_idf_time.json)")
     ap.add_argument("--match", action="store_true", help="score and identity, greedy and optimal, with SMC and the estimate, alternating (profiles/stream_match_time.json)")
     ap.add_argument("--hota", action="store_true", help="score and score + HOTA, each with and without SMC, alternating; hota_score() apart (profiles/stream_hota_time.json)")
+    ap.add_argument("--motion", action="store_true", help="identity and identity + motion, greedy and optimal, with SMC and the estimate, alternating (profiles/stream_motion_time.json)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     ov, _, _, _ = config_inputs(2)
-    if args.hota:
+    if args.motion:
+        shapes = [dict(name="cfg2_batch_motion", **time_motion(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
+    elif args.hota:
         shapes = [dict(name="cfg2_batch_hota", **time_hota(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
     elif args.match:
         shapes = [dict(name="cfg2_batch_match", **time_match(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
