@@ -943,6 +943,99 @@ int sqair_set_motion(SqairHandle* h, const SqairLaneMotion* m /* NULL: off */, i
 int sqair_lane_identity_motion_test(SqairHandle* h, const float* box, const float* presence, const float* obj_id, const float* what,
                                     const int32_t* best_row, int T, int B, const SqairLaneIdentity* id, const SqairLaneMotion* m, void* stream);
 
+/* ---- the track log: trajectories per lane_id, smoothed on the device (the track log paragraph) ----------------------------------
+ * The identity and the motion answer for the current frame.  "Where was every object of the lane over the last frames" needs the
+ * frames joined by lane_id, tracks that ended or are unseen included, and a gap filled by the motion model instead of left as a hole.
+ * With a track log set, every following inference pass with a carried state, an estimate and an identity runs one more kernel,
+ * k_lane_tracklog, one workgroup per lane over the pass's frames in order: directly after the identity's node, BEFORE k_lane_score if
+ * on and BEFORE the SMC resampler.  A pass with the log on has exactly one kernel node more; with it off nothing is launched and every
+ * other output, blob and accumulator is unchanged bit for bit.  Training passes, and a capture's eager pre-pass without effects, never
+ * run it.  It reads only the identity's own output buffers lane_id and track_len and the estimate's box and best_row.
+ * A. The log, per lane b, persistent on the device; L in 1..4096 records.  count [B] int64, the frames ever logged for the lane,
+ *    invalid ones included, read and advanced on the device; the caller starts it at 0 (and the other fields at 0).  Frame t of a pass
+ *    of T frames takes record (count[b] + t) mod L; after the pass count[b] += T.  A record holds
+ *      log_valid [B,L] int32: 0 for a non-finite lane (best_row[t,b] == -1), else 1;
+ *      log_id [B,L,N] int32: the word lane_id[t,b,j] as it stands: -1 where slot j is absent;
+ *      log_len [B,L,N] int32: the word track_len[t,b,j] as it stands;
+ *      log_box [B,L,N,4]: the estimate's four 32-bit words box[t,b,j], copied as they are.
+ *    Every word of the record is written, whether the frame is valid or not: stale words are never read, and wrap-around needs no
+ *    case of its own.  The ids of a record with log_valid == 0 are never looked at.  Words are copied, nothing is computed: a
+ *    replayed graph leaves the bytes of eager calls, two passes of five and seven frames leave the bytes of one pass of twelve.
+ * sqair_lane_tracklog_smooth, a stand-alone capturable call (one launch of k_lane_tracklog_smooth, one workgroup per lane), turns the
+ * last `lag` records into trajectories.  It registers nothing, no pass runs it, it writes only its outputs and `work`: it may
+ * interleave with passes.  C in 1..64 track columns; q, r, v0_var as in the motion paragraph.  For lane b:
+ * 1. Window.  Frames f = 0..lag-1, oldest to newest: the absolute frame number is g = count[b] - lag + f, frame_index[f,b] = g, and
+ *    its record is g mod L; g < 0 is "no record", frame_index = -1.  A frame COUNTS when it has a record with log_valid != 0.
+ * 2. Columns.  The distinct ids >= 0 in the records of the frames that count; n_tracks[b] is their number.  The C largest are kept
+ *    -- the newest ids: a tracker's caller wants the live tracks -- and listed ascending in track_id[b,0..C), padded with -1.  For a
+ *    column, f0 and f1 are the first and the last frame that counts and holds its id (in a slot j, the smallest such j), and
+ *    len0[b,c] is the log_len word of that slot at f0 (1: the track was born inside the window); -1 for a padding column.
+ * 3. Forward filter, one thread per (column, axis a in {y, x} of the box CENTRE), the motion paragraph's P and U, the same
+ *    statements in the same order (one device function each, shared with k_lane_identity_motion).  z = fmaf(0.5, size, origin) of
+ *    the slot's box words, size = h or w.  At f0 the state starts as a newborn's, whatever len0 is: (p, v, Ppp, Ppv, Pvv) =
+ *    (z, 0, r, 0, v0_var), state 1.  For f0 < f <= f1: a frame that counts does P; if the id is in the record it then does U with
+ *    that slot's z (state 1, seen), otherwise the predicted state stands (state 2, a gap).  A frame inside the span that does not
+ *    count does not step, exactly as the identity neither ages nor predicts there (state 3).  Outside the span the state is 0.
+ * 4. Backward pass (Rauch-Tung-Striebel) over the STEPPED frames (state 1 or 2) in descending order; consecutive stepped frames
+ *    are exactly one P apart.  At f1 the smoothed state is the filtered one.  For a stepped frame with filtered (p, v, a, b, c)
+ *    and the smoothed (ps+, vs+, as+, bs+, cs+) of the next stepped frame, in fp32 and in this order:
+ *      pm = p + v; am = ((a + 2 b) + c) + q/4; bm = (b + c) + q/2; cm = c + q             (P's statements)
+ *      det = fmaf(am, cm, -(bm bm)); m00 = a + b; m10 = b + c
+ *      g00 = fmaf(m00, cm, -(b bm)) / det; g01 = fmaf(b, am, -(m00 bm)) / det
+ *      g10 = fmaf(m10, cm, -(c bm)) / det; g11 = fmaf(c, am, -(m10 bm)) / det             (G = P F^T (P-)^-1, F = [[1,1],[0,1]])
+ *      dp = ps+ - pm; dv = vs+ - v; da = as+ - am; db = bs+ - bm; dc = cs+ - cm
+ *      ps = fmaf(g01, dv, fmaf(g00, dp, p)); vs = fmaf(g11, dv, fmaf(g10, dp, v))          (x_s = x + G (x_s+ - x-))
+ *      e00 = fmaf(g01, db, g00 da); e01 = fmaf(g01, dc, g00 db); e10 = fmaf(g11, db, g10 da); e11 = fmaf(g11, dc, g10 db)
+ *      as = fmaf(e01, g01, fmaf(e00, g00, a)); bs = fmaf(e01, g11, fmaf(e00, g10, b)); cs = fmaf(e11, g11, fmaf(e10, g10, c))
+ *    (P_s = P + G (P_s+ - P-) G^T).  The prediction is recomputed from the filtered state: only that is stored.
+ * 5. Outputs: state [lag,B,C] int32; filt and smooth [lag,B,C,2,5] = (p, v, Ppp, Ppv, Pvv) per axis, 0 where the state is 0 or 3;
+ *    size [lag,B,C,2] = the (h, w) words of the slot at state 1, the last seen ones at state 2, else 0: sizes are not filtered, as
+ *    in the identity's predicted box.  All arithmetic is fp32, every sum in one fixed order, no decision depends on a threshold: the
+ *    same bits come out of every replay, and with the same scalars filt's v at a seen frame after f0 of a column with len0 == 1 has
+ *    the bits of the motion's velocity for that slot.
+ * `work`: B * sqair_lane_tracklog_work_bytes(lag, C, N) bytes of the caller's, any content: the slot of every (frame, column); the
+ * filtered states live in filt.  At the limits neither fits LDS.
+ * Pointers are remembered by the handle and frozen into captured graphs.  NULL log: off.  sqair_set_tracklog is refused (return -1,
+ * text in sqair_last_error, before any HIP call) with no identity set (sqair_set_identity); for an identity without track_len bound;
+ * for a T other than the estimate's or a B other than the state's; for L outside 1..4096; for a NULL count, log_valid, log_id, log_len
+ * or log_box.  The identity going off (sqair_set_identity(NULL), or the estimate or the state taking it along) switches the log off,
+ * and so does sqair_set_identity registering an identity without track_len.
+ * Out of scope: filtering h, w; lane_id inside the object lists of lane tracks and lane forecasts; scoring the log against truth;
+ * training passes; identities across lanes. */
+#define SQAIR_TRACKLOG_MAX_FRAMES 4096
+#define SQAIR_TRACKLOG_MAX_TRACKS 64
+typedef struct SqairLaneTrackLog {
+  int32_t L;            /* records per lane, 1..4096 */
+  /* the log, in/out, persists across passes; the caller starts with zeros */
+  int64_t* count;       /* [B]       frames ever logged for the lane */
+  int32_t* log_valid;   /* [B,L] */
+  int32_t* log_id;      /* [B,L,N] */
+  int32_t* log_len;     /* [B,L,N] */
+  float*   log_box;     /* [B,L,N,4] */
+} SqairLaneTrackLog;
+int sqair_set_tracklog(SqairHandle* h, const SqairLaneTrackLog* log /* NULL: off */, int T, int B);
+/* Kernel-level check of the append (tests): k_lane_tracklog on caller buffers, no state and no pass, with the handle's N.  lane_id,
+ * track_len [T,B,N], best_row [T,B] and box [T,B,N,4] stand for the producers' outputs.  Refused (return -1, before any HIP call): a
+ * NULL lane_id / track_len / best_row / box / log, T or B out of range, what sqair_set_tracklog refuses for log. */
+int sqair_lane_tracklog_test(SqairHandle* h, const int32_t* lane_id, const int32_t* track_len, const int32_t* best_row, const float* box,
+                             int T, int B, const SqairLaneTrackLog* log, void* stream);
+/* The solve (points 1 to 5).  The handle gives the error text only.  Every output is required.  Refused (return -1, before any HIP
+ * call): a NULL log, out or work, a NULL output; lag outside 1..L; C outside 1..64; N outside 1..16; B < 1; any of q, r, v0_var not
+ * finite and positive; what sqair_set_tracklog refuses for log. */
+typedef struct SqairTrackLogOut {
+  int32_t* track_id;     /* [B,C]   ascending, -1 = padding */
+  int32_t* n_tracks;     /* [B]     the distinct ids of the window, kept or not */
+  int32_t* len0;         /* [B,C] */
+  int64_t* frame_index;  /* [lag,B] the absolute frame number, -1 = no record */
+  int32_t* state;        /* [lag,B,C] 0 outside the span, 1 seen, 2 gap, 3 a frame that does not count inside the span */
+  float*   size;         /* [lag,B,C,2] */
+  float*   filt;         /* [lag,B,C,2,5] */
+  float*   smooth;       /* [lag,B,C,2,5] */
+} SqairTrackLogOut;
+int64_t sqair_lane_tracklog_work_bytes(int lag, int C, int N);   /* per lane; 0 for arguments the solve refuses */
+int sqair_lane_tracklog_smooth(SqairHandle* h, const SqairLaneTrackLog* log, int lag, int C, int N, int B, float q, float r, float v0_var,
+                               const SqairTrackLogOut* out, void* work, void* stream);
+
 /* ---- IDF1 scoring: does an identity stay on an object over its life -- global identity assignment, solved on the device ---------
  * The score's idsw counts the moments an identity changes on a greedy per-frame match; it cannot say for how long the wrong id then
  * stays, and gives no credit for an object re-identified under its old id.  The identity measures of Ristani et al. (IDF1, IDP, IDR)

@@ -178,6 +178,27 @@ def motion_memory_shapes(B, M):
     return dict(trk_kf=(B, M, 2, len(MOTION_STATE)))
 
 
+# the track log (include/sqair_hip.h: sqair_set_tracklog): the fields of SqairLaneTrackLog -- the counter and the records -- and the
+# outputs of the solve in declaration order, with the int32 ones among them (frame_index is int64); the four values of ``state``
+TRACKLOG_FIELDS = _pointers("SqairLaneTrackLog")
+TRACKLOG_OUT_FIELDS = _pointers("SqairTrackLogOut")
+TRACKLOG_OUT_INT_FIELDS = _int32("SqairTrackLogOut", TRACKLOG_OUT_FIELDS)
+TRACKLOG_MAX_FRAMES = _K["SQAIR_TRACKLOG_MAX_FRAMES"]
+TRACKLOG_MAX_TRACKS = _K["SQAIR_TRACKLOG_MAX_TRACKS"]
+TRACKLOG_STATES = ("outside", "seen", "gap", "invalid")
+
+
+def tracklog_shapes(B, L, N):
+    """The log's shapes for L records per lane and N object slots."""
+    return dict(count=(B,), log_valid=(B, L), log_id=(B, L, N), log_len=(B, L, N), log_box=(B, L, N, 4))
+
+
+def tracklog_out_shapes(lag, B, C):
+    """The shapes of sqair_lane_tracklog_smooth's outputs for a window of ``lag`` frames and C track columns."""
+    return dict(track_id=(B, C), n_tracks=(B,), len0=(B, C), frame_index=(lag, B), state=(lag, B, C), size=(lag, B, C, 2),
+                filt=(lag, B, C, 2, len(MOTION_STATE)), smooth=(lag, B, C, 2, len(MOTION_STATE)))
+
+
 # trajectory scoring (include/sqair_hip.h: sqair_lane_traj_score): the three structs' pointer fields in declaration order -- of
 # SqairTrajScore the accumulators, then the per-call outputs and the int32 ones among them --, the columns of ``counts`` [F, B, .],
 # ``sums`` [F, B, .] and ``lane_counts`` [B, .]

@@ -524,6 +524,30 @@ struct LaneHotaSolveArgs {
   int G, N, B;
 };
 int sq_launch_lane_hota_solve(const LaneHotaSolveArgs& a, hipStream_t s);
+// The track log (sqair_set_tracklog; include/sqair_hip.h states the semantics): k_lane_tracklog, one workgroup per lane b over the
+// pass's frames in order, one record of the lane's ring per frame.  lane_id / track_len [T][B][N] and best_row [T][B] are the
+// identity's and the estimate's outputs, box [T][B][N][4] the estimate's (or a test's buffers).
+constexpr int SQ_TRACKLOG_MAXL = SQAIR_TRACKLOG_MAX_FRAMES;
+constexpr int SQ_TRACKLOG_MAXC = SQAIR_TRACKLOG_MAX_TRACKS;
+struct LaneTrackLogArgs {
+  const int32_t* lane_id;              // [T][B][N]
+  const int32_t* track_len;            // [T][B][N]
+  const int32_t* best_row;             // [T][B]
+  const float* box;                    // [T][B][N][4]
+  SqairLaneTrackLog log;               // L, count and the records
+  int T, B, N;
+};
+int sq_launch_lane_tracklog(const LaneTrackLogArgs& a, hipStream_t s);
+// The solve (sqair_lane_tracklog_smooth): k_lane_tracklog_smooth, one workgroup per lane b: the window, the columns, then one thread
+// per (column, axis) filters forward and smooths backward.  `work`: [B][lag][C] int32, the slot of every (frame, column).
+struct LaneTrackLogSmoothArgs {
+  SqairLaneTrackLog log;
+  SqairTrackLogOut out;
+  int32_t* work;
+  float q, r, v0_var;
+  int lag, C, N, B;
+};
+int sq_launch_lane_tracklog_smooth(const LaneTrackLogSmoothArgs& a, hipStream_t s);
 
 // Object forecasts (sqair_forecast_fan; include/sqair_hip.h states the semantics).  Fan-out: rollout row q = r * S + s.
 // k_forecast_fan_src expands the source map, src_fan[q] = src[q / S] (NULL: q / S), an index outside [0, R) of the blob -> -1.

@@ -38,7 +38,8 @@ struct SqHistRing {
 // only ever on with it and for its T -- the layers (k_lane_layers), the identity (k_lane_identity) and the score (k_lane_score).
 // score_ids: the score reads the identity's lane_id for obj_id; only ever with both on.  idf: the IDF1 table (k_lane_idf), after the
 // score and on the id words it was handed; only ever on with a score that binds truth_match.  hota: the HOTA clip log (k_lane_hota),
-// after the score and the IDF on the same words; only ever on with a score.  All off is SqLaneSet{}.
+// after the score and the IDF on the same words; only ever on with a score.  tracklog: the track log (k_lane_tracklog), directly
+// after the identity, whose lane_id and track_len it copies; only ever on with it.  All off is SqLaneSet{}.
 struct SqLaneSet {
   bool est_on = false;
   SqairLaneEstimate est = {};
@@ -49,6 +50,8 @@ struct SqLaneSet {
   SqairLaneIdentity ident = {};
   bool motion_on = false;          // sqair_set_motion: the identity's launch is its motion instantiation; only ever on with the identity
   SqairLaneMotion motion = {};
+  bool tracklog_on = false;        // sqair_set_tracklog: k_lane_tracklog directly after the identity's node; only ever on with the identity
+  SqairLaneTrackLog tracklog = {};
   bool score_on = false;
   SqairLaneScore score = {};
   bool score_ids = false;
@@ -125,7 +128,7 @@ struct SqairHandle {
   // missing-frame steps (sqair_set_observed): the passes' kernels read this device mask [observed_T][state_B]
   const int32_t* observed = nullptr;
   int observed_T = 0;
-  // the lane answers (sqair_set_estimate / _layers / _identity / _score / _score_ids / _idf / _hota; sqair_lane_api.hip)
+  // the lane answers (sqair_set_estimate / _layers / _identity / _motion / _tracklog / _score / _score_ids / _idf / _hota; sqair_lane_api.hip)
   SqLaneSet lane;
   // per-frame matching of the lane block (sqair_set_lane_match): a plain setting, untouched by the registrations above
   int match_score = 0, match_ident = 0, match_traj = 0;
@@ -345,7 +348,7 @@ SQ_LOCAL SmcArgs sq_smc_args(const SqairSmc& m, const float* lw, const int32_t* 
 // ---- lane answers (sqair_lane_api.hip) ----
 // the refusal of a pass with the estimate on (host only: before any HIP call; sq_resolve_pass calls it last)
 SQ_LOCAL int sq_estimate_refusal(SqairHandle* h, int T, const SqairOutputs* outp);
-// The lane launches of a pass of T frames, `l` as resolved: estimate -> layers -> identity -> score -> IDF -> HOTA over the merged records `rec`
+// The lane launches of a pass of T frames, `l` as resolved: estimate -> layers -> identity -> track log -> score -> IDF -> HOTA over the merged records `rec`
 // [T][R][N][rec::W], the decoded glimpses `glimpse` [T][R][N][G*G] and the pass's outputs.  0, or -2 + error text when the layers'
 // launch fails (dynamic LDS limit).  Of `h` only cfg and the error text.
 SQ_LOCAL int sq_launch_lane_answers(SqairHandle* h, const SqLaneSet& l, const float* rec, const float* glimpse, const SqairOutputs& out,

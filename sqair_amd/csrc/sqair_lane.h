@@ -381,3 +381,32 @@ __device__ __forceinline__ int sq_assign_keep_optimal(const float* iou, const in
   sq_wave_lds_order();
   return __shfl(n, 0, 64) + (int)(opt >> 25);
 }
+
+// The constant-velocity filter of the motion paragraph (include/sqair_hip.h: sqair_set_motion, points P and U), one (track, axis): k
+// points at its five words (p, v, Ppp, Ppv, Pvv).
+// P: one frame on; returns S = Ppp' + r.  ONE statement of the step: the identity's motion instantiation calls it on the words in
+// LDS, the track log's solve (k_lane_tracklog_smooth) on a thread's own.
+__device__ __forceinline__ float sq_kf_predict(float* k, const float q, const float r) {
+  const float v = k[1], ppp = k[2], ppv = k[3], pvv = k[4];
+  const float npp = ((ppp + 2.0f * ppv) + pvv) + 0.25f * q;
+  k[0] = k[0] + v;
+  k[2] = npp;
+  k[3] = (ppv + pvv) + 0.5f * q;
+  k[4] = pvv + q;
+  return npp + r;
+}
+// U: the predicted state with innovation variance S takes the measurement z; returns the posterior velocity.  The solve's: the
+// statements of sq_lane_identity_frames<.., true>'s update, restated -- that kernel keeps its own, because calling this function
+// from it moved one scalar instruction of its walk, and the identity kernels stay the code they are.  The two
+// are held together by bits: tests/test_tracklog_kernel.py compares the solve's velocity with the motion kernel's.
+__device__ __forceinline__ float sq_kf_update(float* k, const float S, const float z) {
+  const float ppp = k[2], ppv = k[3];
+  const float y = z - k[0], k0 = ppp / S, k1 = ppv / S;
+  k[0] = fmaf(k0, y, k[0]);
+  const float vel = fmaf(k1, y, k[1]);
+  k[1] = vel;
+  k[2] = (1.0f - k0) * ppp;
+  k[3] = (1.0f - k0) * ppv;
+  k[4] = fmaf(-k1, ppv, k[4]);
+  return vel;
+}

@@ -743,14 +743,7 @@ __device__ __forceinline__ void sq_lane_identity_frames(const LaneIdentArgs& a) 
     // ---- P: every live entry's filter one frame on, per (entry, axis)
     if constexpr (MOTION) {
       if (tid < M * 2 && s_tid[tid >> 1] >= 0) {
-        float* k = s_kf + tid * 5;
-        const float v = k[1], ppp = k[2], ppv = k[3], pvv = k[4];
-        const float npp = ((ppp + 2.0f * ppv) + pvv) + 0.25f * mo.q;
-        k[0] = k[0] + v;
-        k[2] = npp;
-        k[3] = (ppv + pvv) + 0.5f * mo.q;
-        k[4] = pvv + mo.q;
-        s_S[tid] = npp + mo.r;
+        s_S[tid] = sq_kf_predict(s_kf + tid * 5, mo.q, mo.r);
       }
       __syncthreads();
     }
@@ -1427,5 +1420,209 @@ __global__ __launch_bounds__(256) void k_lane_hota_solve(const LaneHotaSolveArgs
 }
 int sq_launch_lane_hota_solve(const LaneHotaSolveArgs& a, hipStream_t s) {
   SQ_LAUNCH(k_lane_hota_solve, dim3(a.B), dim3(256), 0, s, a);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The track log (sqair_set_tracklog; LaneTrackLogArgs / LaneTrackLogSmoothArgs in sqair_glue.h; the semantics: include/sqair_hip.h,
+// the track log paragraph, points A and 1-5)
+// ------------------------------------------------------------------------------------------------
+// k_lane_tracklog: workgroup = lane b.  Frame t of the pass takes record (count[b] + t) mod L; the words are copied as they are,
+// thread i of the frame's N * 4 box words, N ids, N lengths and one valid word, the frames in order.  Every thread reads count[b]
+// before the barrier, thread 0 advances it behind it.  A record index is formed inside 0..L-1 whatever count holds.
+__global__ __launch_bounds__(256) void k_lane_tracklog(const LaneTrackLogArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  const SqairLaneTrackLog& f = a.log;
+  const int b = blockIdx.x, tid = threadIdx.x, N = a.N, L = f.L;
+  const long long c0 = f.count[b];
+  int rec = (int)(((c0 % L) + L) % L);
+  __syncthreads();
+  for (int t = 0; t < a.T; ++t) {
+    const size_t tb = (size_t)t * a.B + b, r = (size_t)b * L + rec;
+    if (tid < N * 4) sq_put(f.log_box + r * N * 4 + tid, sq_word(a.box + tb * N * 4 + tid));
+    if (tid < N) {
+      f.log_id[r * N + tid] = a.lane_id[tb * N + tid];
+      f.log_len[r * N + tid] = a.track_len[tb * N + tid];
+    }
+    if (tid == 0) f.log_valid[r] = a.best_row[tb] != -1;
+    rec = rec + 1 == L ? 0 : rec + 1;
+  }
+  if (tid == 0) f.count[b] = c0 + a.T;
+}
+int sq_launch_lane_tracklog(const LaneTrackLogArgs& a, hipStream_t s) {
+  SQ_LAUNCH(k_lane_tracklog, dim3(a.B), dim3(256), 0, s, a);
+  return 0;
+}
+
+// k_lane_tracklog_smooth: workgroup = lane b.
+//   window   frame f of the window is record (r0 + f) mod L for f >= fmin (fmin = lag - count where the log is younger than the
+//            window), "no record" before; it COUNTS when its valid word is set.
+//   columns  up to C rounds of a workgroup maximum, "the largest id below the previous one", over the lag * N id words of the
+//            frames that count (an integer atomicMax in LDS: no order to depend on); n_tracks counts the id words that no earlier
+//            word of the window holds -- each thread walks back from its word and stops at the first sighting it meets.
+//   slots    thread i of lag * C finds the slot of column c in frame f (the smallest j) into `work`, and the first and last such
+//            frame of the column by integer atomicMin / atomicMax in LDS.
+//   filter   thread (column, axis) < 2 C walks the frames forward -- sq_kf_predict, sq_kf_update (sqair_lane.h) on its own five
+//            words -- and stores the filtered state; then backward over the stepped frames, reading its own stores back.
+// `work` and filt are global: at the limits neither fits LDS.  What a thread reads of them it wrote itself, but for `work`, which
+// is read behind a fence and a barrier.  A slot read from `work` is the one this launch wrote, inside 0..N-1; a record index is
+// formed inside 0..L-1.  No arrays in registers but a thread's five words, indexed by constants.
+__global__ __launch_bounds__(256) void k_lane_tracklog_smooth(const LaneTrackLogSmoothArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ int s_max[2], s_n, s_desc[SQ_TRACKLOG_MAXC], s_f0[SQ_TRACKLOG_MAXC], s_f1[SQ_TRACKLOG_MAXC];
+  const SqairLaneTrackLog& g = a.log;
+  const SqairTrackLogOut& o = a.out;
+  const int b = blockIdx.x, tid = threadIdx.x, N = a.N, L = g.L, lag = a.lag, C = a.C, B = a.B;
+  const long long cnt = max(g.count[b], 0ll), base = cnt - lag;
+  const int fmin = base < 0 ? (int)(-base) : 0;                    // the first frame of the window that has a record
+  const int r0 = (int)(((base % L) + L) % L);
+  const int* lvalid = g.log_valid + (size_t)b * L;
+  const int* lid = g.log_id + (size_t)b * L * N;
+  auto record = [&](int f) { const int r = r0 + f; return r >= L ? r - L : r; };   // (f < lag <= L)
+  auto counts = [&](int f) { return f >= fmin && lvalid[record(f)] != 0; };
+  // ---- 1: the window
+  for (int f = tid; f < lag; f += 256) o.frame_index[(size_t)f * B + b] = f >= fmin ? base + f : -1ll;
+  if (tid < C) { s_desc[tid] = -1; s_f0[tid] = lag; s_f1[tid] = -1; }
+  if (tid == 0) s_n = 0;
+  // ---- 2: the columns, the largest id first
+  int K = 0;
+  long long below = 1ll << 31;
+  for (int c = 0; c < C; ++c) {
+    if (tid == 0) s_max[c & 1] = -1;   // (two words in turn: a thread may still be reading the last round's)
+    __syncthreads();
+    int best = -1;
+    for (int i = tid; i < lag * N; i += 256) {
+      const int f = i / N, j = i - f * N;
+      if (!counts(f)) continue;
+      const int id = lid[(size_t)record(f) * N + j];
+      if (id >= 0 && id < below && id > best) best = id;
+    }
+    if (best >= 0) atomicMax(&s_max[c & 1], best);
+    __syncthreads();
+    const int m = s_max[c & 1];
+    if (m < 0) break;   // (uniform: every thread reads the same word behind the barrier)
+    if (tid == 0) s_desc[c] = m;
+    below = m;
+    K = c + 1;
+  }
+  // n_tracks: the id words of the window that are a first sighting
+  {
+    int first = 0;
+    for (int i = tid; i < lag * N; i += 256) {
+      const int f = i / N, j = i - f * N;
+      if (!counts(f)) continue;
+      const int id = lid[(size_t)record(f) * N + j];
+      if (id < 0) continue;
+      bool seen = false;
+      for (int jj = 0; jj < j && !seen; ++jj) seen = lid[(size_t)record(f) * N + jj] == id;
+      for (int ff = f - 1; ff >= fmin && !seen; --ff) {
+        if (lvalid[record(ff)] == 0) continue;
+        for (int jj = 0; jj < N && !seen; ++jj) seen = lid[(size_t)record(ff) * N + jj] == id;
+      }
+      first += !seen;
+    }
+    if (first) atomicAdd(&s_n, first);
+  }
+  __syncthreads();   // (s_desc, K columns of it; s_n)
+  if (tid == 0) o.n_tracks[b] = s_n;
+  if (tid < C) o.track_id[(size_t)b * C + tid] = tid < K ? s_desc[K - 1 - tid] : -1;
+  // ---- the slot of every (frame, column), and each column's span
+  int* work = a.work + (size_t)b * lag * C;
+  for (int i = tid; i < lag * C; i += 256) {
+    const int f = i / C, c = i - f * C;
+    int slot = -1;
+    if (c < K && counts(f)) {
+      const int id = s_desc[K - 1 - c];
+      const int* w = lid + (size_t)record(f) * N;
+      for (int j = N - 1; j >= 0; --j)
+        if (w[j] == id) slot = j;
+    }
+    work[i] = slot;
+    if (slot >= 0) { atomicMin(&s_f0[c], f); atomicMax(&s_f1[c], f); }
+  }
+  __threadfence();
+  __syncthreads();
+  if (tid < C) {
+    int len = -1;
+    const int f = tid < K ? s_f0[tid] : lag;
+    const int j = f < lag ? work[f * C + tid] : -1;   // (a kept id was seen in the window: f < lag and j >= 0, checked all the same)
+    if (j >= 0) len = g.log_len[((size_t)b * L + record(f)) * N + j];
+    o.len0[(size_t)b * C + tid] = len;
+  }
+  if (tid >= C * 2) return;   // (no barrier below)
+  // ---- 3: forward, thread = (column, axis)
+  const int c = tid >> 1, ax = tid & 1;
+  const int f0 = c < K ? s_f0[c] : lag, f1 = c < K ? s_f1[c] : -1;
+  const float* lbox = g.log_box + (size_t)b * L * N * 4;
+  float k[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  float size = 0.0f;
+  for (int f = 0; f < lag; ++f) {
+    const size_t e = ((size_t)f * B + b) * C + c;
+    int st = 0;
+    if (f >= f0 && f <= f1) {
+      if (!counts(f)) {
+        st = 3;
+      } else {
+        const int j = work[f * C + c];
+        float z = 0.0f;
+        if (j >= 0) {
+          const float* q = lbox + ((size_t)record(f) * N + j) * 4;
+          size = q[2 + ax];
+          z = fmaf(0.5f, size, q[ax]);
+        }
+        if (f == f0) {
+          k[0] = z; k[1] = 0.0f; k[2] = a.r; k[3] = 0.0f; k[4] = a.v0_var;
+          st = 1;
+        } else {
+          const float S = sq_kf_predict(k, a.q, a.r);
+          if (j >= 0) { sq_kf_update(k, S, z); st = 1; }
+          else st = 2;
+        }
+      }
+    }
+    const bool stepped = st == 1 || st == 2;
+    if (ax == 0) o.state[e] = st;
+    o.size[e * 2 + ax] = stepped ? size : 0.0f;
+    float* w = o.filt + (e * 2 + ax) * 5;
+    w[0] = stepped ? k[0] : 0.0f; w[1] = stepped ? k[1] : 0.0f; w[2] = stepped ? k[2] : 0.0f;
+    w[3] = stepped ? k[3] : 0.0f; w[4] = stepped ? k[4] : 0.0f;
+  }
+  // ---- 4: backward over the stepped frames; (ps, vs, as, bs, cs): the smoothed state of the next stepped frame
+  float ps = 0.0f, vs = 0.0f, as = 0.0f, bs = 0.0f, cs = 0.0f;
+  bool have = false;
+  for (int f = lag - 1; f >= 0; --f) {
+    const size_t e = (((size_t)f * B + b) * C + c) * 2 + ax;
+    float* w = o.smooth + e * 5;
+    const bool stepped = f >= f0 && f <= f1 && counts(f);
+    if (!stepped) {
+      w[0] = 0.0f; w[1] = 0.0f; w[2] = 0.0f; w[3] = 0.0f; w[4] = 0.0f;
+      continue;
+    }
+    const float* fl = o.filt + e * 5;
+    const float p = fl[0], v = fl[1], pa = fl[2], pb = fl[3], pc = fl[4];
+    if (!have) {
+      ps = p; vs = v; as = pa; bs = pb; cs = pc;
+      have = true;
+    } else {
+      float m[5] = {p, v, pa, pb, pc};
+      sq_kf_predict(m, a.q, a.r);
+      const float pm = m[0], am = m[2], bm = m[3], cm = m[4];
+      const float det = fmaf(am, cm, -(bm * bm)), m00 = pa + pb, m10 = pb + pc;
+      const float g00 = fmaf(m00, cm, -(pb * bm)) / det, g01 = fmaf(pb, am, -(m00 * bm)) / det;
+      const float g10 = fmaf(m10, cm, -(pc * bm)) / det, g11 = fmaf(pc, am, -(m10 * bm)) / det;
+      const float dp = ps - pm, dv = vs - v, da = as - am, db = bs - bm, dc = cs - cm;
+      ps = fmaf(g01, dv, fmaf(g00, dp, p));
+      vs = fmaf(g11, dv, fmaf(g10, dp, v));
+      const float e00 = fmaf(g01, db, g00 * da), e01 = fmaf(g01, dc, g00 * db);
+      const float e10 = fmaf(g11, db, g10 * da), e11 = fmaf(g11, dc, g10 * db);
+      as = fmaf(e01, g01, fmaf(e00, g00, pa));
+      bs = fmaf(e01, g11, fmaf(e00, g10, pb));
+      cs = fmaf(e11, g11, fmaf(e10, g10, pc));
+    }
+    w[0] = ps; w[1] = vs; w[2] = as; w[3] = bs; w[4] = cs;
+  }
+}
+int sq_launch_lane_tracklog_smooth(const LaneTrackLogSmoothArgs& a, hipStream_t s) {
+  SQ_LAUNCH(k_lane_tracklog_smooth, dim3(a.B), dim3(256), 0, s, a);
   return 0;
 }

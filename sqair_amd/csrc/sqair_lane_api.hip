@@ -1,9 +1,9 @@
 // libsqair_hip.so -- the lane answers on the native side of the C ABI (include/sqair_hip.h): the estimate and its followers, the
-// layers, the identity, the score, the IDF1 table and the HOTA log.  Their registration on a handle as one block (SqLaneSet, sqair_internal.h:
-// sqair_set_estimate / _layers / _score / _identity / _motion / _score_ids / _idf / _hota), the estimate's refusal of a pass, ONE builder per kernel's arguments -- called by the
+// layers, the identity, the track log, the score, the IDF1 table and the HOTA log.  Their registration on a handle as one block (SqLaneSet, sqair_internal.h:
+// sqair_set_estimate / _layers / _score / _identity / _motion / _tracklog / _score_ids / _idf / _hota), the estimate's refusal of a pass, ONE builder per kernel's arguments -- called by the
 // pass and by the kernel-level entry point alike --, the pass's launch sequence (sq_launch_lane_answers, called by sq_forward_impl
 // with the block sq_resolve_pass resolved) and the stand-alone entry points (sqair_lane_*_test, sqair_lane_traj_score,
-// sqair_lane_idf_solve, sqair_lane_hota_solve).  Host code
+// sqair_lane_idf_solve, sqair_lane_hota_solve, sqair_lane_tracklog_smooth).  Host code
 // only: the kernels and their launchers live in sqair_lane.hip, which work here does not move.  A further follower is one member
 // of SqLaneSet, its registration and builder here, and one line of sq_launch_lane_answers.
 #include "sqair_internal.h"
@@ -61,6 +61,13 @@ static int sq_identity_fields(SqairHandle* h, const std::string& who, const Sqai
     return sq_no(h, who + "trk_id, trk_word, trk_age, trk_len, trk_box, next_id, counts and lane_id must not be NULL");
   return 0;
 }
+static int sq_tracklog_fields(SqairHandle* h, const std::string& who, const SqairLaneTrackLog& c) {
+  if (c.L < 1 || c.L > SQ_TRACKLOG_MAXL)
+    return sq_no(h, who + "L = " + std::to_string(c.L) + " must lie in 1.." + std::to_string(SQ_TRACKLOG_MAXL));
+  if (!c.count || !c.log_valid || !c.log_id || !c.log_len || !c.log_box)
+    return sq_no(h, who + "count, log_valid, log_id, log_len and log_box must not be NULL");
+  return 0;
+}
 static int sq_motion_fields(SqairHandle* h, const std::string& who, const SqairLaneMotion& m) {
   const float v[4] = {m.q, m.r, m.v0_var, m.gate};
   const char* name[4] = {"q", "r", "v0_var", "gate"};
@@ -82,7 +89,12 @@ static void sq_hota_off(SqLaneSet& l) { l.hota_on = false; l.hota = SqairLaneHot
 static void sq_score_off(SqLaneSet& l) { l.score_on = false; l.score = SqairLaneScore{}; l.score_ids = false; sq_idf_off(l); sq_hota_off(l); }
 // (the motion filter is a mode of the identity's launch: it goes off with it)
 static void sq_motion_off(SqLaneSet& l) { l.motion_on = false; l.motion = SqairLaneMotion{}; }
-static void sq_identity_off(SqLaneSet& l) { l.ident_on = false; l.ident = SqairLaneIdentity{}; l.score_ids = false; sq_motion_off(l); }
+// (and so does the track log: the ids and lengths it copies are the identity's)
+static void sq_tracklog_off(SqLaneSet& l) { l.tracklog_on = false; l.tracklog = SqairLaneTrackLog{}; }
+static void sq_identity_off(SqLaneSet& l) {
+  l.ident_on = false; l.ident = SqairLaneIdentity{}; l.score_ids = false;
+  sq_motion_off(l); sq_tracklog_off(l);
+}
 // what the followers need of the estimate they read (best_row is never NULL in a registered estimate; `what`: the identity keeps an
 // appearance, trk_what, and reads the estimate's)
 static bool sq_estimate_scorable(const SqairLaneEstimate& e) { return e.box && e.presence && e.obj_id && e.map_count; }
@@ -202,7 +214,23 @@ extern "C" int sqair_set_identity(SqairHandle* h, const SqairLaneIdentity* id, i
   if (id->trk_what && !h->lane.est.what)
     return sq_no(h, who + "trk_what needs the estimate (sqair_set_estimate) to bind what: the appearance it remembers");
   if (sq_follower_shape_refusal(h, who, T, B) != 0 || sq_identity_fields(h, who, *id) != 0) return -1;
+  if (!id->track_len) sq_tracklog_off(h->lane);   // (a re-registered identity drops the log it can no longer feed)
   h->lane.ident_on = true; h->lane.ident = *id;
+  return 0;
+}
+extern "C" int sqair_set_tracklog(SqairHandle* h, const SqairLaneTrackLog* log, int T, int B) {
+  if (!h) return -1;
+  if (!log) {
+    sq_tracklog_off(h->lane);
+    return 0;
+  }
+  const std::string who = "sqair_set_tracklog: ";
+  if (!h->state_on || !h->lane.est_on || !h->lane.ident_on)
+    return sq_no(h, who + "needs an identity (sqair_set_identity): the log is keyed by the lane_id it writes");
+  if (!h->lane.ident.track_len)
+    return sq_no(h, who + "the identity (sqair_set_identity) must bind track_len: the log records it");
+  if (sq_follower_shape_refusal(h, who, T, B) != 0 || sq_tracklog_fields(h, who, *log) != 0) return -1;
+  h->lane.tracklog_on = true; h->lane.tracklog = *log;
   return 0;
 }
 extern "C" int sqair_set_motion(SqairHandle* h, const SqairLaneMotion* m, int T, int B) {
@@ -293,6 +321,14 @@ static LaneHotaArgs sq_hota_args(const SqairConfig& c, const float* box, const f
   return a;
 }
 
+static LaneTrackLogArgs sq_tracklog_args(const SqairConfig& c, const int32_t* lane_id, const int32_t* track_len, const int32_t* best_row,
+                                         const float* box, const SqairLaneTrackLog& log, int T, int B) {
+  LaneTrackLogArgs a; memset(&a, 0, sizeof(a));
+  a.lane_id = lane_id; a.track_len = track_len; a.best_row = best_row; a.box = box; a.log = log;
+  a.T = T; a.B = B; a.N = c.n_steps_per_image;
+  return a;
+}
+
 // ------------------------------------------------------------------------------------------------
 // the pass: every lane launch, in the one order they have.  The estimate comes before the resampler zeroes the weights it reads
 // and rewrites the map; the followers read the estimate's own output buffers, the identity before the score, which may read the
@@ -321,6 +357,9 @@ int sq_launch_lane_answers(SqairHandle* h, const SqLaneSet& l, const float* rec,
   if (l.ident_on)
     sq_launch_lane_identity(sq_identity_args(c, e.box, e.presence, e.obj_id, e.what, e.best_row, l.ident, T, B, l.ident_match,
                                              l.motion_on ? &l.motion : nullptr), s);
+  // the track log: the frame's lane_id, track_len and box words into the lane's ring (sqair_set_tracklog), right behind their writer
+  if (l.ident_on && l.tracklog_on)
+    sq_launch_lane_tracklog(sq_tracklog_args(c, l.ident.lane_id, l.ident.track_len, e.best_row, e.box, l.tracklog, T, B), s);
   // stream scoring: the lane answer against the caller's ground truth (sqair_set_score), accumulated in place.  sqair_set_score_ids:
   // the kernel takes the id as a 32-bit word, so the identity's int32 lane_id stands where obj_id stands
   if (l.score_on) {
@@ -462,6 +501,52 @@ extern "C" int sqair_lane_hota_solve(SqairHandle* h, const SqairLaneHota* hota, 
   LaneHotaSolveArgs a; memset(&a, 0, sizeof(a));
   a.hota = *hota; a.close = close; a.open_i = open_i; a.open_f = open_f; a.open_c = open_c; a.match = match; a.G = G; a.N = N; a.B = B;
   sq_launch_lane_hota_solve(a, (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+extern "C" int sqair_lane_tracklog_test(SqairHandle* h, const int32_t* lane_id, const int32_t* track_len, const int32_t* best_row,
+                                        const float* box, int T, int B, const SqairLaneTrackLog* log, void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_lane_tracklog_test: ";
+  if (!lane_id || !track_len || !best_row || !box || !log || T < 1 || B < 1 || T > 65535)
+    return sq_no(h, who + "null lane_id / track_len / best_row / box / log or bad T / B");
+  if (sq_tracklog_fields(h, who, *log) != 0) return -1;
+  sq_launch_lane_tracklog(sq_tracklog_args(h->cfg, lane_id, track_len, best_row, box, *log, T, B), (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+// the track log's solve (include/sqair_hip.h: sqair_lane_tracklog_smooth): a stand-alone call on the log the passes -- or a test --
+// filled, nothing registered on the handle, which gives the error text.  ONE statement of what it accepts, the scratch query's too
+static const char* sq_tracklog_shape_refusal(int lag, int C, int N) {
+  if (lag < 1 || lag > SQ_TRACKLOG_MAXL) return "lag must lie in 1..L";
+  if (C < 1 || C > SQ_TRACKLOG_MAXC) return "C must lie in 1..64";
+  if (N < 1 || N > 16) return "N must lie in 1..16";
+  return nullptr;
+}
+extern "C" int64_t sqair_lane_tracklog_work_bytes(int lag, int C, int N) {
+  if (sq_tracklog_shape_refusal(lag, C, N)) return 0;
+  return (int64_t)lag * C * (int64_t)sizeof(int32_t);
+}
+extern "C" int sqair_lane_tracklog_smooth(SqairHandle* h, const SqairLaneTrackLog* log, int lag, int C, int N, int B, float q, float r,
+                                          float v0_var, const SqairTrackLogOut* out, void* work, void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_lane_tracklog_smooth: ";
+  if (!log || !out || !work) return sq_no(h, who + "log, out and work must not be NULL");
+  if (B < 1) return sq_no(h, who + "B = " + std::to_string(B) + " must be >= 1");
+  if (sq_tracklog_fields(h, who, *log) != 0) return -1;
+  if (const char* why = sq_tracklog_shape_refusal(lag, C, N))
+    return sq_no(h, who + why + " (lag = " + std::to_string(lag) + ", L = " + std::to_string(log->L) + ", C = " + std::to_string(C) +
+                        ", N = " + std::to_string(N) + ")");
+  if (lag > log->L) return sq_no(h, who + "lag = " + std::to_string(lag) + " must lie in 1..L = " + std::to_string(log->L));
+  const float v[3] = {q, r, v0_var};
+  const char* name[3] = {"q", "r", "v0_var"};
+  for (int i = 0; i < 3; ++i)
+    if (!(v[i] > 0.0f) || !std::isfinite(v[i])) return sq_no(h, who + name[i] + " must be finite and > 0");   // (NaN fails)
+  if (!out->track_id || !out->n_tracks || !out->len0 || !out->frame_index || !out->state || !out->size || !out->filt || !out->smooth)
+    return sq_no(h, who + "track_id, n_tracks, len0, frame_index, state, size, filt and smooth must not be NULL");
+  LaneTrackLogSmoothArgs a; memset(&a, 0, sizeof(a));
+  a.log = *log; a.out = *out; a.work = (int32_t*)work; a.q = q; a.r = r; a.v0_var = v0_var; a.lag = lag; a.C = C; a.N = N; a.B = B;
+  sq_launch_lane_tracklog_smooth(a, (hipStream_t)stream);
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }

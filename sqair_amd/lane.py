@@ -49,6 +49,14 @@ the d2 of the pair each slot was linked through.  ``identities()`` gains ``trk_c
 (= sqrt(Ppp)) and ``trk_pred_box`` [B, M, 4], the coasted box of every live track: for ``trk_age`` > 0 that is where the filter
 thinks the unseen object is.
 
+``tracklog=L`` (with ``identity=True``): the stream keeps, per lane and on the device, the last L frames of ``lane_id``,
+``track_len`` and ``box`` in a ring, written by one more kernel of the pass directly behind the identity's (sqair_set_tracklog), and
+``track_log(lag)`` turns the last ``lag`` of them into one trajectory per ``lane_id`` with one launch (sqair_lane_tracklog_smooth):
+up to ``tracklog_tracks`` track columns, the newest ids, each filtered forward by the motion's constant-velocity model and smoothed
+backward (Rauch-Tung-Striebel), so that a frame in which the object was not seen holds the model's interpolation instead of a
+hole and a track that ended is still there.  It does not need ``motion=True``.  ``reset(lanes)`` empties those lanes' logs.
+``mot_rows(log, lane)`` lists a lane's smoothed boxes as MOTChallenge rows.
+
 ``score_idf=True`` (with ``score=True``): the score's idsw counts the moments an identity changes, not for how long the wrong id then
 stays.  The stream then also keeps, per lane and on the device, how many frames of the open clip every truth overlapped (IoU >=
 ``score_iou``) every predicted id -- the id words the score reads: ``obj_id``, or ``lane_id`` with ``score_ids="lane"`` --, up to
@@ -165,6 +173,31 @@ def _hota_figures(ints, floats, n_sets):
     return out
 
 
+def track_log_views(got):
+    """What ``SqairStream.track_log`` returns, formed on the host from the solve's outputs read back (include/sqair_hip.h:
+    sqair_lane_tracklog_smooth; host tensors {name: tensor} by _capi.TRACKLOG_OUT_FIELDS): ``track_id``, ``n_tracks``, ``len0``,
+    ``frame_index``, ``state`` and ``size`` as they are, and for each of ``smooth`` and ``filtered`` a dict of ``centre``, ``velocity``,
+    ``sigma`` = sqrt(max(Ppp, 0)) [lag, B, C, 2] = (y, x) and ``box`` [lag, B, C, 4] = (centre - size / 2, size)."""
+    res = {n: got[n] for n in ("track_id", "n_tracks", "len0", "frame_index", "state", "size")}
+    for name, field in (("smooth", "smooth"), ("filtered", "filt")):
+        kf = _columns(got[field], _capi.MOTION_STATE)
+        res[name] = dict(centre=kf["p"], velocity=kf["v"], sigma=kf["Ppp"].clamp(min=0.0).sqrt(),
+                         box=torch.cat([kf["p"] - 0.5 * got["size"], got["size"]], -1))
+    return res
+
+
+def mot_rows(log, lane):
+    """The MOTChallenge rows (frame, id, x, y, w, h) of lane ``lane`` of a ``track_log()`` result: one row per (frame, track) whose
+    ``state`` is 1 (seen) or 2 (a gap the smoother filled), from the smoothed boxes, ordered by frame, then by id; ``frame`` is the
+    absolute frame number ``frame_index``, x and y the box's left and top edge.  A float64 array [rows, 6]."""
+    state = np.asarray(log["state"])[:, lane]
+    box = np.asarray(log["smooth"]["box"], np.float64)[:, lane]
+    frame, ids = np.asarray(log["frame_index"])[:, lane], np.asarray(log["track_id"])[lane]
+    rows = [(frame[f], ids[c], box[f, c, 1], box[f, c, 0], box[f, c, 3], box[f, c, 2])
+            for f in range(state.shape[0]) for c in range(state.shape[1]) if state[f, c] in (1, 2)]
+    return np.asarray(rows, np.float64).reshape(-1, 6)
+
+
 def field_views(shapes, int_fields, device):
     """The fields {name: shape} as views of ONE float32 allocation, each 16-byte aligned (``int_fields``: viewed as int32), so that
     they are copied out with one launch instead of one per field.  Returns (flat, views): views(flat or a clone of it) -> {name: view}."""
@@ -186,7 +219,8 @@ class LaneAnswers(object):
     """The lane answers a stream's steps fill.  The constructor only checks its keyword group (no core, no device: it runs before the
     stream touches either); ``register`` allocates the buffers and registers them on the core's handle.  ``flat`` / ``views``: ONE
     allocation and its views by field, ``est`` (field_views) -- everything a step copies out as ``out["lane"]``; ``score_buf`` and
-    ``ident_buf``: the score's truth, accumulators and identity memory, the identity's track table and counters; ``idf_buf``: the
+    ``ident_buf``: the score's truth, accumulators and identity memory, the identity's track table and counters; ``tracklog_buf``:
+    the track log's ring of every lane; ``idf_buf``: the
     IDF1 table of every lane's open clip and the totals over the closed ones; ``hota_buf``: the HOTA log of every lane's open clip
     and its totals."""
 
@@ -194,7 +228,7 @@ class LaneAnswers(object):
                  identity, identity_iou, identity_tracks, identity_max_age, identity_reid_dist, identity_reid_what, identity_appearance,
                  score_ids, score_idf=False, score_idf_ids=32, score_match="greedy", identity_match="greedy", score_hota=False,
                  score_hota_ids=32, score_hota_frames=256, motion=False, motion_q=0.25, motion_r=1.0, motion_v0=16.0, motion_gate=3.0,
-                 motion_nis=False):
+                 motion_nis=False, tracklog=None, tracklog_tracks=16):
         self.step_fn, who = who + ".step: ", who + ": "
 
         def bad(why):
@@ -239,6 +273,14 @@ class LaneAnswers(object):
             if motion and not 0.0 < v < float("inf"):   # (NaN fails too)
                 bad(name + " must be finite and > 0")
         self.motion, self.motion_nis = bool(motion), bool(motion_nis)
+        if tracklog is not None and not identity:
+            bad("tracklog is for a stream with identity=True")
+        if tracklog is not None and not is_int_in(tracklog, 1, _capi.TRACKLOG_MAX_FRAMES):
+            bad("tracklog must be an integer in [1, {}]".format(_capi.TRACKLOG_MAX_FRAMES))
+        if tracklog is not None and not is_int_in(tracklog_tracks, 1, _capi.TRACKLOG_MAX_TRACKS):
+            bad("tracklog_tracks must be an integer in [1, {}]".format(_capi.TRACKLOG_MAX_TRACKS))
+        self.tracklog = tracklog is not None
+        self.log_L, self.log_C = (int(tracklog), int(tracklog_tracks)) if self.tracklog else (0, 0)
         if score_ids not in ("row", "lane"):
             bad("score_ids must be 'row' or 'lane'")
         if score_ids == "lane" and not (score and identity):
@@ -336,6 +378,12 @@ class LaneAnswers(object):
                                            **{n: est[n].data_ptr() for n in _capi.MOTION_FIELDS if n in est})
                 sync()
                 core.check(lib.sqair_set_motion(h, C.byref(mo), T, B), "sqair_set_motion")
+            if self.tracklog:   # the ring of every lane beside the track table: one more node, right behind the identity's
+                self.tracklog_buf = zeros_of("SqairLaneTrackLog", _capi.tracklog_shapes(B, self.log_L, N), core.device)
+                self._log_c = _capi.SqairLaneTrackLog(L=self.log_L, **{n: t.data_ptr() for n, t in self.tracklog_buf.items()})
+                self._log_out = {}   # the solve's outputs and scratch of the LAST lag asked for
+                sync()
+                core.check(lib.sqair_set_tracklog(h, C.byref(self._log_c), T, B), "sqair_set_tracklog")
             if self.score_ids == "lane":
                 core.check(lib.sqair_set_score_ids(h, 1), "sqair_set_score_ids")
         if self.idf:   # the overlap table of every lane's open clip, the totals over the closed ones, and what a solve writes
@@ -394,7 +442,7 @@ class LaneAnswers(object):
     def reset(self, lanes, on_core_stream):
         """The follow-ups of a stream's ``reset(lanes)`` (``lanes`` checked and distinct; ``on_core_stream``: the carried state's context):
         the score forgets those lanes' identities (``last_id``) and keeps their counters; the identity frees their track entries
-        (``trk_id`` = -1) and keeps their ``next_id``.  Before either, a stream with ``score_idf`` closes those lanes' clips: one solve
+        (``trk_id`` = -1) and keeps their ``next_id``, and a stream with ``tracklog`` zeroes their ``count``.  Before either, a stream with ``score_idf`` closes those lanes' clips: one solve
         with their mask, their figures into the totals, their tables freed; a stream with ``score_hota`` does the same with its log."""
         if lanes and (self.scored or self.identified):
             with on_core_stream():
@@ -413,6 +461,8 @@ class LaneAnswers(object):
                         self.score_buf["last_id"][j].fill_(-1)
                     if self.identified:
                         self.ident_buf["trk_id"][j].fill_(-1)
+                    if self.tracklog:   # (a new clip starts an empty log; ids are never reused within a lane)
+                        self.tracklog_buf["count"][j].zero_()
 
     # ---- read-outs -----------------------------------------------------------------------------------------------------------
     def score(self, reset=False):
@@ -497,6 +547,36 @@ class LaneAnswers(object):
         res.update(sets[-1])
         res["exact"] = int(res["dropped_frames"].sum()) == 0 and int(res["overflow_ids"].sum()) == 0
         return res
+
+    def track_log(self, lag=None, q=None, r=None, v0=None):
+        if not self.tracklog:
+            raise ValueError("SqairStream.track_log: the stream keeps no track log (SqairStream(..., estimate=True, identity=True, "
+                             "tracklog=L))")
+        lag = self.log_L if lag is None else lag
+        if not is_int_in(lag, 1, self.log_L):
+            raise ValueError("SqairStream.track_log: lag must be an integer in [1, tracklog = {}]".format(self.log_L))
+        m = self.motion_scalars
+        scal = dict(q=m["q"] if q is None else float(q), r=m["r"] if r is None else float(r), v0=m["v0_var"] if v0 is None else float(v0))
+        for name, v in scal.items():
+            if not 0.0 < v < float("inf"):   # (NaN fails too)
+                raise ValueError("SqairStream.track_log: {} must be finite and > 0".format(name))
+        core, B, Cn = self.core, self.B, self.log_C
+        with torch.cuda.device(core.device):
+            core._join_in()
+            with core.on_stream():
+                if self._log_out.get("lag") != lag:
+                    out = zeros_of("SqairTrackLogOut", _capi.tracklog_out_shapes(lag, B, Cn), core.device)
+                    nbytes = B * core.lib.sqair_lane_tracklog_work_bytes(lag, Cn, core.N)
+                    self._log_out = dict(lag=lag, out=out, work=torch.zeros(nbytes // 4, dtype=torch.int32, device=core.device),
+                                         c=_capi.SqairTrackLogOut(**{n: t.data_ptr() for n, t in out.items()}))
+                    torch.cuda.current_stream(core.device).synchronize()
+                o = self._log_out
+                core.check(core.lib.sqair_lane_tracklog_smooth(core.handle, C.byref(self._log_c), lag, Cn, core.N, B, scal["q"],
+                                                               scal["r"], scal["v0"], C.byref(o["c"]), o["work"].data_ptr(),
+                                                               core._stream()), "sqair_lane_tracklog_smooth")
+                got = {n: t.clone() for n, t in o["out"].items()}
+            core._join_out()
+        return track_log_views({n: t.cpu() for n, t in got.items()})
 
     def identities(self):
         if not self.identified:

@@ -41,7 +41,8 @@ network "see" an empty scene and kill the objects.
 
 With ``estimate=True`` a step also returns ``out["lane"]``: one answer per lane and frame from the K particles, and its followers
 say more about it, each one more kernel of the pass -- ``estimate_layers`` which pixels each object occupies, ``identity`` a track id
-that stays on an object (``motion``: with a velocity filter per track inside the same kernel, sqair_set_motion), ``score`` the CLEAR-MOT events against a step's ``truth`` (``score()``, ``identities()``; ``score_match`` / ``identity_match`` =
+that stays on an object (``motion``: with a velocity filter per track inside the same kernel, sqair_set_motion; ``tracklog``: the
+last frames of every lane by lane_id in a ring on the device, ``track_log()`` their smoothed trajectories, sqair_set_tracklog), ``score`` the CLEAR-MOT events against a step's ``truth`` (``score()``, ``identities()``; ``score_match`` / ``identity_match`` =
 "optimal": their per-frame matching as keep + optimal, sqair_set_lane_match), ``score_idf`` the identity overlap table
 IDF1 is solved from (``idf_score()``), ``score_hota`` the clip log HOTA is solved from (``hota_score()``); ``forecast`` and
 ``tracks`` with ``lane=True, truth=...`` score the lane forecast and the lane tracks (``trajectory_score(kind)``).  sqair_amd/lane.py
@@ -77,7 +78,8 @@ class SqairStream(object):
                  score_truth=None, identity=False, identity_iou=0.3, identity_tracks=None, identity_max_age=10, identity_reid_dist=4.0,
                  identity_reid_what=float("inf"), identity_appearance=True, score_ids="row", score_idf=False, score_idf_ids=32,
                  score_match="greedy", identity_match="greedy", score_hota=False, score_hota_ids=32, score_hota_frames=256,
-                 motion=False, motion_q=0.25, motion_r=1.0, motion_v0=16.0, motion_gate=3.0, motion_nis=False):
+                 motion=False, motion_q=0.25, motion_r=1.0, motion_v0=16.0, motion_gate=3.0, motion_nis=False, tracklog=None,
+                 tracklog_tracks=16):
         if core.cfg.sample_from_prior:
             raise ValueError("SqairStream: generation modes (sample_from_prior) do not carry a state across calls")
         if resample not in (None, "systematic"):
@@ -89,7 +91,7 @@ class SqairStream(object):
                                      score_iou, score_truth, identity, identity_iou, identity_tracks, identity_max_age,
                                      identity_reid_dist, identity_reid_what, identity_appearance, score_ids, score_idf, score_idf_ids,
                                      score_match, identity_match, score_hota, score_hota_ids, score_hota_frames, motion, motion_q,
-                                     motion_r, motion_v0, motion_gate, motion_nis)   # (checks only)
+                                     motion_r, motion_v0, motion_gate, motion_nis, tracklog, tracklog_tracks)   # (checks only)
         self.smc = resample is not None
         self.ess_frac = ess_frac
         self.core = core
@@ -144,9 +146,9 @@ class SqairStream(object):
         carried(n) for n in ("state", "log_weight_sum", "log_z", "log_evidence", "ess", "u", "resampled", "_src", "_armed",
                              "_src_is_identity", "history", "history_fields"))
     # the lane answers', likewise
-    estimate, scored, identified, G, M, _est_flat, _est_views, _est, _score, _ident, _idf, _hota = (
+    estimate, scored, identified, G, M, _est_flat, _est_views, _est, _score, _ident, _idf, _hota, _tracklog = (
         lane_answer(n) for n in ("estimate", "scored", "identified", "G", "M", "flat", "views", "est", "score_buf", "ident_buf", "idf_buf",
-                                 "hota_buf"))
+                                 "hota_buf", "tracklog_buf"))
     _traj = lane_answer("acc", of="traj")
 
     def _set_smc(self, uniforms):
@@ -167,7 +169,7 @@ class SqairStream(object):
         ``identity=True`` frees those lanes' track entries (``trk_id`` = -1) and keeps their ``next_id``: an id is never reused within
         a lane.  A stream with ``score_idf=True`` first closes those lanes' clips (one solve on the device): their IDF1 figures go
         into the totals and their tables are freed -- a new clip has new truth identities.  A stream with ``score_hota=True`` closes
-        their HOTA clips the same way."""
+        their HOTA clips the same way.  A stream with ``tracklog`` empties those lanes' logs (``count`` = 0)."""
         self.carried.reset(lanes)
         self.lane.reset(sorted(set(self.carried.check_lanes(lanes))), self.carried._on_core_stream)
 
@@ -281,6 +283,20 @@ class SqairStream(object):
         ``trk_age`` > 0 are the tracks remembered but currently unseen.  With ``motion=True`` also the filter's state (sqair_set_motion):
         ``trk_centre``, ``trk_vel``, ``trk_sigma`` [B, M, 2] and ``trk_pred_box`` [B, M, 4], the coasted box of every live track."""
         return self.lane.identities()
+
+    def track_log(self, lag=None, q=None, r=None, v0=None):
+        """The trajectories of the last ``lag`` logged frames (default: all ``tracklog`` = L of them) per ``lane_id`` (include/sqair_hip.h:
+        sqair_set_tracklog, sqair_lane_tracklog_smooth): one launch on the device.  C = ``tracklog_tracks`` columns per lane.
+        ``track_id`` [B, C] int32, the C largest ids of the window ascending, -1 = padding; ``n_tracks`` [B], the distinct ids of the
+        window, kept or not; ``len0`` [B, C], the ``track_len`` at the id's first frame in the window (1: born inside it);
+        ``frame_index`` [lag, B] int64, the frames' absolute numbers since the lane's last reset, -1 before its first; ``state``
+        [lag, B, C] int32 -- 0 outside the track's span, 1 seen, 2 a gap inside the span (the model's prediction stands), 3 a
+        non-finite frame inside the span (nothing steps) --; ``size`` [lag, B, C, 2], (h, w) as last seen.  ``smooth`` and
+        ``filtered``: dicts of ``centre``, ``velocity``, ``sigma`` [lag, B, C, 2] = (y, x) and ``box`` [lag, B, C, 4] = (y, x, h, w), the
+        Rauch-Tung-Striebel smoothed and the causal estimate of a constant-velocity filter started at the track's first frame in
+        the window; 0 where ``state`` is 0 or 3.  ``q``, ``r``, ``v0``: the filter's scalars, default the stream's ``motion_q``,
+        ``motion_r``, ``motion_v0`` (set or not: the log does not need ``motion=True``).  Host tensors."""
+        return self.lane.track_log(lag, q, r, v0)
 
     # ---- trajectory scoring ------------------------------------------------------------------------------------------------
     def _check_traj_truth(self, fn, truth, lane, F, default_anchor, link_ids, truth_iou, link_match="greedy"):

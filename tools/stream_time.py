@@ -92,6 +92,15 @@ With --motion: the price of lane motion (SqairStream(estimate=True, identity=Tru
 difference motion - identity is reported next to the identity's and the resampler's node of the same run.  Recorded, not gated on:
 
     python tools/stream_time.py --motion [--out profiles/stream_motion_time.json]
+
+With --tracklog: the price of the track log (SqairStream(estimate=True, identity=True, tracklog=L), include/sqair_hip.h:
+sqair_set_tracklog) -- one node directly behind the identity's.  Streams at cfg-2's batch alternating in one process as with --history,
+all with SMC and the estimate: SMC, SMC + estimate, identity, identity + log, motion, motion + log, and one with a history ring of the
+same length beside the log.  The log's node is reported next to the identity's and the resampler's of the same run; ``track_log()`` at
+lag 10 and 64 -- the solve, the copies and what the host forms from them, every call waited for -- against ``tracks(lag)`` of the same
+run.  Recorded, not gated on:
+
+    python tools/stream_time.py --tracklog [--out profiles/stream_tracklog_time.json]
 """
 import argparse
 import json
@@ -507,6 +516,49 @@ def time_motion(B, K, N, steps, warmup, rounds=10, hw=(50, 50)):
     return res
 
 
+def time_tracklog(B, K, N, steps, warmup, L=64, rounds=10, hw=(50, 50)):
+    smc = dict(resample="systematic", ess_frac=0.5)
+    est = dict(estimate=True, **smc)
+    idt = dict(est, identity=True)
+    log = dict(tracklog=L, tracklog_tracks=16)
+    legs = dict(plain={}, smc=smc, smc_estimate=est, identity=idt, identity_log=dict(idt, **log), motion=dict(idt, motion=True),
+                motion_log=dict(idt, motion=True, **log), motion_log_history=dict(idt, motion=True, history=L, **log))
+    streams, res, med, thr = alternating_streams(legs, B, K, N, steps, warmup, rounds, hw)
+    res.update(L=L, tracks=16, log_bytes=int(sum(t.numel() * t.element_size() for t in streams["motion_log"]._tracklog.values())))
+    for key, v in (("latency", med), ("back_to_back", thr)):
+        one_node = v["smc"] - v["plain"]            # the yardstick: one dependent node (the resampler) on this machine, this run
+        added = dict(identity_node=v["identity"] - v["smc_estimate"], log_node_on_identity=v["identity_log"] - v["identity"],
+                     log_node_on_motion=v["motion_log"] - v["motion"])
+        res["us_" + key] = dict(smc_node=1e3 * one_node, **{n: 1e3 * a for n, a in added.items()},
+                                **{n + "_over_smc_node": (a / one_node if one_node > 0 else None) for n, a in added.items()})
+    # track_log() against tracks(): both rings full (warm-up + steps > L), the same stream, every call waited for
+    st = streams["motion_log_history"]
+    assert int(st._tracklog["count"].min()) >= L, "the log is not full"
+    res["ms"] = {}
+    for lag in (10, L):
+        for name, call in (("track_log", lambda: st.track_log(lag=lag)), ("tracks", lambda: st.tracks(lag=lag))):
+            with st.core.on_stream():
+                for _ in range(5):
+                    got = call()
+                torch.cuda.synchronize()
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(50)]
+                for x, y in ev:
+                    x.record()
+                    call()
+                    y.record()
+                    st.core.stream.synchronize()
+            ms = [x.elapsed_time(y) for x, y in ev]
+            res["ms"]["{}_lag{}".format(name, lag)] = dict(median=float(np.median(ms)), p10=float(np.percentile(ms, 10)),
+                                                           p90=float(np.percentile(ms, 90)))
+            if name == "track_log":
+                res["n_tracks_lag{}".format(lag)] = dict(mean=float(got["n_tracks"].float().mean()), max=int(got["n_tracks"].max()))
+    for k in ("ms_per_frame_median", "ms_per_frame_p10", "ms_per_frame_p90", "ms_per_frame_back_to_back"):
+        res[k].pop("motion_log_history")      # (stepped along for the read-outs: not a leg of the comparison)
+    for st in streams.values():
+        st.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=500)
@@ -524,10 +576,13 @@ def main():
     ap.add_argument("--match", action="store_true", help="score and identity, greedy and optimal, with SMC and the estimate, alternating (profiles/stream_match_time.json)")
     ap.add_argument("--hota", action="store_true", help="score and score + HOTA, each with and without SMC, alternating; hota_score() apart (profiles/stream_hota_time.json)")
     ap.add_argument("--motion", action="store_true", help="identity and identity + motion, greedy and optimal, with SMC and the estimate, alternating (profiles/stream_motion_time.json)")
+    ap.add_argument("--tracklog", action="store_true", help="identity and motion with and without the track log, with SMC and the estimate, alternating; track_log() against tracks() apart (profiles/stream_tracklog_time.json)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     ov, _, _, _ = config_inputs(2)
-    if args.motion:
+    if args.tracklog:
+        shapes = [dict(name="cfg2_batch_tracklog", **time_tracklog(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
+    elif args.motion:
         shapes = [dict(name="cfg2_batch_motion", **time_motion(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
     elif args.hota:
         shapes = [dict(name="cfg2_batch_hota", **time_hota(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
