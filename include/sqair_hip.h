@@ -1000,8 +1000,8 @@ int sqair_lane_identity_motion_test(SqairHandle* h, const float* box, const floa
  * for a T other than the estimate's or a B other than the state's; for L outside 1..4096; for a NULL count, log_valid, log_id, log_len
  * or log_box.  The identity going off (sqair_set_identity(NULL), or the estimate or the state taking it along) switches the log off,
  * and so does sqair_set_identity registering an identity without track_len.
- * Out of scope: filtering h, w; lane_id inside the object lists of lane tracks and lane forecasts; scoring the log against truth;
- * training passes; identities across lanes. */
+ * Out of scope: filtering h, w; lane_id inside the object lists of lane tracks and lane forecasts; scoring the log against truth
+ * here (that is sqair_lane_tracklog_score's, next); training passes; identities across lanes. */
 #define SQAIR_TRACKLOG_MAX_FRAMES 4096
 #define SQAIR_TRACKLOG_MAX_TRACKS 64
 typedef struct SqairLaneTrackLog {
@@ -1035,6 +1035,79 @@ typedef struct SqairTrackLogOut {
 int64_t sqair_lane_tracklog_work_bytes(int lag, int C, int N);   /* per lane; 0 for arguments the solve refuses */
 int sqair_lane_tracklog_smooth(SqairHandle* h, const SqairLaneTrackLog* log, int lag, int C, int N, int B, float q, float r, float v0_var,
                                const SqairTrackLogOut* out, void* work, void* stream);
+/* The log is scored against truth by sqair_lane_tracklog_score, next. */
+
+/* ---- track log scoring: the solve's trajectories against ground-truth boxes (the track log scoring paragraph) -----------------------
+ * The track log answers "where was every lane_id over the last frames", filtered causally and smoothed, gaps filled by the motion
+ * model.  sqair_lane_tracklog_score says what that is worth on a stream with truth: does gap filling turn misses into hits or into
+ * false positives, does smoothing move the boxes towards the truth, is sigma honest, do the trajectories keep their identity.  It is a
+ * stand-alone, capturable call, one launch of k_lane_tracklog_score, one workgroup of four wavefronts per lane: it registers nothing,
+ * no pass runs it, and it writes only `score`.  It is a pure function of its inputs -- nothing of `score` is read, there are no in/out
+ * accumulators: the windows of successive calls overlap, so summing over calls is the caller's business.  The handle gives the error
+ * text only.
+ * Inputs.  `table` (read-only) is what sqair_lane_tracklog_smooth wrote for the same lag, C and B: track_id, frame_index, state, size,
+ * filt and smooth are read.  `log` gives L, count and log_valid, so that a non-finite frame is told from an empty one.  `truth` is in
+ * WINDOW ORDER, oldest to newest, as for sqair_lane_traj_score -- the caller brings the truth of the table's frames --: G in 1..16
+ * slots per lane, truth_box [lag,B,G,4] fp32 (y, x, h, w) in pixels, truth_present [lag,B,G] and truth_valid [lag,B] int32 (nonzero =
+ * set); truth identity IS the slot g, as in sqair_set_score.  score->iou_min in (0, 1].  match: 0 greedy, 1 optimal (point 3).
+ * 1. Views.  Four views v = 0..3 of the one table, src = v & 1 (0: filt, 1: smooth), fill = v >> 1.  Column c is PRESENT in view v at
+ *    frame f when state[f,b,c] == 1, or when fill is set and state[f,b,c] == 2.  Its box is (fmaf(-0.5f, h, p_y), fmaf(-0.5f, w, p_x),
+ *    h, w) with p the word 0 of src[f,b,c,axis,:] and (h, w) = size[f,b,c,:].  View 0 is what a causal tracker reported; view 3 is
+ *    what the MOTChallenge rows of the log export.  Wavefront v owns view v; the views share nothing.
+ * 2. Frames.  Frame f of lane b is SCORED when frame_index[f,b] >= 0, its record (frame_index mod L) has log_valid != 0, and
+ *    truth_valid[f,b] != 0.  A frame with a record and truth but log_valid == 0 counts one frames_invalid and nothing else; every
+ *    other frame changes nothing.  The per-frame outputs of a frame that is not scored are -1 (match) and 0 (match_iou).
+ * 3. Per scored frame and view, frames in ascending order.  Candidates: present truth g (truth_present != 0) x present column c;
+ *    holes are allowed on both sides.  IoU(g, c) is sq_box_iou, the estimate's device function, on the fp32 words.  The assignment is
+ *    the score's own device function, unchanged -- sq_assign_keep_greedy (match == 0) or sq_assign_keep_optimal (match == 1; the
+ *    per-frame matching paragraph) -- with N := C, col_id[c] = track_id[b,c] and keep_id[g] = last[v][g], the track_id truth g was
+ *    last matched with in this view, -1 at the start of EVERY call.  Events, exactly as point 4 of the stream scoring paragraph
+ *    defines them: tp = matched pairs, fn = present truths unmatched, fp = present columns unclaimed; for each matched g in index
+ *    order with id = track_id[b,c]: idsw += [last[v][g] >= 0 and last[v][g] != id], then last[v][g] = id; match[v,f,b,g] = c (-1
+ *    unmatched or absent), match_iou[v,f,b,g] = the pair's IoU (0 unmatched).
+ * 4. For each matched pair (g, c), in fp32 and in this order, with (t_y, t_x, th, tw) the truth's words, p_y, p_x the view's centre
+ *    words and Ppp_y, Ppp_x the words 2 of the view's src per axis:  ty = fmaf(0.5f, th, t_y); tx = fmaf(0.5f, tw, t_x); dy = ty - p_y;
+ *    dx = tx - p_x; err = sqrtf(fmaf(dy, dy, dx * dx)).  When both Ppp_y > 0 and Ppp_x > 0 (a NaN or a non-positive variance is not
+ *    counted): nees = dy * dy / Ppp_y + dx * dx / Ppp_x, and the pair counts in nees_n; its expectation is 2 for an honest sigma.  A
+ *    pair whose column is at state 2 also counts in gap_tp, gap_err_sum and, when its nees counts, in gap_nees_sum and gap_nees_n; a
+ *    present, unclaimed column at state 2 counts in gap_fp.  (Views 0 and 1 hold no column at state 2: their gap figures are 0.)
+ * 5. IDF over the window, per view.  ov[g][c] (int32) = the number of scored frames in which g and c are candidates with IoU(g, c) >=
+ *    iou_min -- all such pairs, no one-to-one: the overlap table of Ristani et al., point 3d of the IDF1 paragraph.  After the last
+ *    frame sq_assign_optimal_i32(ov, C, G, C, .), the IDF1 solve's device function: idtp = the optimum, idfn = (present truths over
+ *    the scored frames) - idtp, idfp = (present columns over the scored frames) - idtp, assign[v,b,g] = the column assigned to g
+ *    when their overlap is positive, else -1 (optimal assignments tie, the figures do not).  The weights are <= lag <= 4096, far
+ *    inside the solver's exact range.
+ * 6. Outputs.  counts [B,4,14] int64 per (lane, view) = frames (scored), frames_invalid, truth, tp, fn, fp, idsw, gap_tp, gap_fp,
+ *    nees_n, gap_nees_n, idtp, idfn, idfp.  sums [B,4,5] fp64 = iou_sum, err_sum, nees_sum, gap_err_sum, gap_nees_sum: each fp32 value
+ *    converted to fp64 and added by one thread, g in index order, frames in order -- no float atomics, so a replayed graph gives the
+ *    bits of an eager call.  Both are required and every word of them is written; assign [4,B,G], match and match_iou [4,lag,B,G] are
+ *    optional.
+ * 7. Refused (return -1, text in sqair_last_error, before any HIP call): a NULL log, table, truth or score; what sqair_set_tracklog
+ *    refuses for log; a NULL track_id, frame_index, state, size, filt or smooth of the table; a NULL truth_box, truth_present or
+ *    truth_valid; a NULL counts or sums; lag outside 1..L; C outside 1..64; G outside 1..16; B < 1; iou_min NaN or outside (0, 1];
+ *    match other than 0 or 1.
+ * Out of scope: sums that persist over windows; HOTA of the log; scoring per particle row; filtering h, w; truth identities other
+ * than the slot. */
+#define SQAIR_TRACKLOG_SCORE_VIEWS 4
+#define SQAIR_TRACKLOG_SCORE_COUNTS 14
+#define SQAIR_TRACKLOG_SCORE_SUMS 5
+typedef struct SqairTrackLogTruth {
+  int32_t G;                      /* truth slots per lane, 1..16 */
+  const float* truth_box;         /* [lag,B,G,4] window order */
+  const int32_t* truth_present;   /* [lag,B,G] */
+  const int32_t* truth_valid;     /* [lag,B] */
+} SqairTrackLogTruth;
+typedef struct SqairTrackLogScore {
+  float iou_min;                  /* in (0, 1] */
+  int64_t* counts;                /* [B,4,14] */
+  double* sums;                   /* [B,4,5] */
+  int32_t* assign;                /* [4,B,G]; optional */
+  int32_t* match;                 /* [4,lag,B,G]; optional */
+  float* match_iou;               /* [4,lag,B,G]; optional */
+} SqairTrackLogScore;
+int sqair_lane_tracklog_score(SqairHandle* h, const SqairLaneTrackLog* log, const SqairTrackLogOut* table /* read-only */,
+                              const SqairTrackLogTruth* truth, const SqairTrackLogScore* score,
+                              int lag, int C, int B, int match /* 0 greedy, 1 optimal */, void* stream);
 
 /* ---- IDF1 scoring: does an identity stay on an object over its life -- global identity assignment, solved on the device ---------
  * The score's idsw counts the moments an identity changes on a greedy per-frame match; it cannot say for how long the wrong id then

@@ -199,6 +199,31 @@ def tracklog_out_shapes(lag, B, C):
                 filt=(lag, B, C, 2, len(MOTION_STATE)), smooth=(lag, B, C, 2, len(MOTION_STATE)))
 
 
+# track log scoring (include/sqair_hip.h: sqair_lane_tracklog_score): the truth's pointer fields, the score's required outputs and its
+# optional ones with the int32 ones among them, the four views by name, the columns of ``counts`` [B, 4, .] and ``sums`` [B, 4, .]
+TRACKLOG_TRUTH_FIELDS = _pointers("SqairTrackLogTruth")
+TRACKLOG_SCORE_TABLE = ("track_id", "frame_index", "state", "size", "filt", "smooth")   # what the scorer reads of the solve's outputs
+TRACKLOG_SCORE_REQUIRED = ("counts", "sums")
+TRACKLOG_SCORE_FIELDS = _pointers("SqairTrackLogScore", without=TRACKLOG_SCORE_REQUIRED)
+TRACKLOG_SCORE_INT_FIELDS = _int32("SqairTrackLogScore", TRACKLOG_SCORE_FIELDS)
+TRACKLOG_SCORE_VIEWS = _counted("SQAIR_TRACKLOG_SCORE_VIEWS", "filtered", "smooth", "filtered_filled", "smooth_filled")
+TRACKLOG_SCORE_COUNTS = _counted("SQAIR_TRACKLOG_SCORE_COUNTS", "frames", "frames_invalid", "truth", "tp", "fn", "fp", "idsw", "gap_tp",
+                                 "gap_fp", "nees_n", "gap_nees_n", "idtp", "idfn", "idfp")
+TRACKLOG_SCORE_SUMS = _counted("SQAIR_TRACKLOG_SCORE_SUMS", "iou_sum", "err_sum", "nees_sum", "gap_err_sum", "gap_nees_sum")
+
+
+def tracklog_truth_shapes(lag, B, G):
+    """The truth's shapes for a window of ``lag`` frames and G truth slots per lane (window order)."""
+    return dict(truth_box=(lag, B, G, 4), truth_present=(lag, B, G), truth_valid=(lag, B))
+
+
+def tracklog_score_shapes(lag, B, G):
+    """The shapes of sqair_lane_tracklog_score's outputs, required and optional."""
+    V = len(TRACKLOG_SCORE_VIEWS)
+    return dict(counts=(B, V, len(TRACKLOG_SCORE_COUNTS)), sums=(B, V, len(TRACKLOG_SCORE_SUMS)), assign=(V, B, G), match=(V, lag, B, G),
+                match_iou=(V, lag, B, G))
+
+
 # trajectory scoring (include/sqair_hip.h: sqair_lane_traj_score): the three structs' pointer fields in declaration order -- of
 # SqairTrajScore the accumulators, then the per-call outputs and the int32 ones among them --, the columns of ``counts`` [F, B, .],
 # ``sums`` [F, B, .] and ``lane_counts`` [B, .]

@@ -548,6 +548,17 @@ struct LaneTrackLogSmoothArgs {
   int lag, C, N, B;
 };
 int sq_launch_lane_tracklog_smooth(const LaneTrackLogSmoothArgs& a, hipStream_t s);
+// Track log scoring (sqair_lane_tracklog_score; include/sqair_hip.h states the semantics): k_lane_tracklog_score, one workgroup of
+// four wavefronts per lane b, wavefront v = view v of the solve's table, walking the window's frames in order.
+struct LaneTrackLogScoreArgs {
+  SqairLaneTrackLog log;               // L, count and log_valid are read
+  SqairTrackLogOut tab;                // the solve's outputs, read-only here
+  SqairTrackLogTruth tr;               // G and the truth of the window's frames
+  SqairTrackLogScore sc;               // iou_min and the outputs
+  int lag, C, B;
+  int match;                           // 0 = sq_assign_keep_greedy, 1 = sq_assign_keep_optimal (a wave-uniform branch of the one kernel)
+};
+int sq_launch_lane_tracklog_score(const LaneTrackLogScoreArgs& a, hipStream_t s);
 
 // Object forecasts (sqair_forecast_fan; include/sqair_hip.h states the semantics).  Fan-out: rollout row q = r * S + s.
 // k_forecast_fan_src expands the source map, src_fan[q] = src[q / S] (NULL: q / S), an index outside [0, R) of the blob -> -1.

@@ -184,7 +184,7 @@ __device__ __forceinline__ void sq_lane_box_sum(const float* s_w, const SqBox* s
 // Leaves row_match[g] = j or -1 and col_claim[j] = 1 or 0; returns the number of pairs.  Greedy, not optimal: the
 // optimal (Hungarian) assignment is sq_assign_optimal_i32, below, over an int32 table and a whole wavefront's work; the per-frame
 // matches of the score, the identity and the trajectory score stay greedy unless sqair_set_lane_match asks for
-// sq_assign_keep_optimal, further below.
+// sq_assign_keep_optimal, further below; track log scoring (k_lane_tracklog_score) takes its choice of the two as an argument.
 __device__ __forceinline__ int sq_assign_keep_greedy(const float* iou, const int ld, const int G, const int N, const float iou_min,
                                                      const int* keep_id, const int* col_id, int* row_match, int* col_claim) {
   int n = 0;
@@ -325,8 +325,9 @@ __device__ __forceinline__ long long sq_assign_optimal_i32(const int* w, const i
 
 // Keep + optimal one-to-one assignment (sqair_set_lane_match): sq_assign_keep_greedy's contract -- the same IoU table in LDS, the same
 // eligibility (entry >= iou_min; -1 marks a non-candidate; a NaN never passes), the same keep_id / col_id, the same row_match /
-// col_claim and return value -- for ONE whole wavefront: all 64 lanes call it together (wave 0 of a 256-thread workgroup; the branch
-// around the call is wave-uniform).  `w` is G * N ints of LDS of the caller's, the function's own table.
+// col_claim and return value -- for ONE whole wavefront: all 64 lanes call it together (wave 0 of a 256-thread workgroup -- in
+// k_lane_tracklog_score each of the four waves, on tables of its own --; the branch around the call is wave-uniform).  `w` is G * N
+// ints of LDS of the caller's, the function's own table.
 //   keep   lane 0's walk, exactly the greedy function's keep step: a kept pair is never given up, even where that costs a pair;
 //   rest   among the unmatched rows and unclaimed columns the one-to-one assignment of eligible pairs that maximises first the
 //          number of pairs, then the sum of q(g, j) = __float2int_rn(iou * 1048576.0f), the IoU in units of 2^-20.  The wave builds

@@ -1626,3 +1626,149 @@ int sq_launch_lane_tracklog_smooth(const LaneTrackLogSmoothArgs& a, hipStream_t 
   SQ_LAUNCH(k_lane_tracklog_smooth, dim3(a.B), dim3(256), 0, s, a);
   return 0;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Track log scoring (sqair_lane_tracklog_score; LaneTrackLogScoreArgs in sqair_glue.h; the semantics: include/sqair_hip.h, the track
+// log scoring paragraph, points 1-7)
+// ------------------------------------------------------------------------------------------------
+// k_lane_tracklog_score: workgroup = lane b, wavefront v = view v of the solve's table (src = v & 1, fill = v >> 1).  The identity
+// memory makes the frames serial, the four views share nothing: each wavefront walks the window on its own, with its own tables in
+// LDS (SqTrackLogScoreWave, 13.25 KiB a wave) and no workgroup barrier anywhere.  Per scored frame the wave's lanes stage the columns'
+// and the truths' presence, lane i fills entries i, i + 64, .. of the G x C IoU table (-1 for a pair that is no candidate) and counts
+// the entry into the overlap table when it passes; lane 0 walks sq_assign_keep_greedy, or the whole wave sq_assign_keep_optimal -- the
+// branch is on a kernel argument --; lane 0 counts the events, keeping the view's counters and sums as scalars; lanes g < G write the
+// per-frame outputs.  After the window the wave solves the overlap table (sq_assign_optimal_i32).  Whether a frame is scored is read
+// by every lane from the same words and made a scalar (readfirstlane), so the wave-wide functions are called by all 64 lanes.
+// Between a lane's LDS stores and another lane's loads stands sq_wave_lds_order (sqair_lane.h): a wavefront's LDS instructions
+// execute in program order.  Nothing is indexed in registers; every index is formed inside the table: f < lag, c < C, g < G, the
+// record inside 0..L-1.
+struct SqTrackLogScoreWave {
+  float iou[SQ_SCORE_MAXG * SQ_TRACKLOG_MAXC];
+  int w[SQ_SCORE_MAXG * SQ_TRACKLOG_MAXC];     // sq_assign_keep_optimal's own table
+  int ov[SQ_SCORE_MAXG * SQ_TRACKLOG_MAXC];
+  int cid[SQ_TRACKLOG_MAXC], cpres[SQ_TRACKLOG_MAXC], cgap[SQ_TRACKLOG_MAXC], claim[SQ_TRACKLOG_MAXC];
+  int last[SQ_SCORE_MAXG], tpres[SQ_SCORE_MAXG], rm[SQ_SCORE_MAXG], assign[SQ_SCORE_MAXG];
+};
+__global__ __launch_bounds__(256) void k_lane_tracklog_score(const LaneTrackLogScoreArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ SqTrackLogScoreWave s_view[SQAIR_TRACKLOG_SCORE_VIEWS];
+  const int b = blockIdx.x, v = threadIdx.x >> 6, L = threadIdx.x & 63;
+  SqTrackLogScoreWave& s = s_view[v];
+  const SqairTrackLogOut& t = a.tab;
+  const SqairTrackLogTruth& tr = a.tr;
+  const SqairTrackLogScore& o = a.sc;
+  const int lag = a.lag, C = a.C, B = a.B, G = tr.G, LR = a.log.L;
+  const bool fill = (v >> 1) != 0;
+  const float* src = (v & 1) ? t.smooth : t.filt;
+  const float iou_min = o.iou_min;
+  const int* lvalid = a.log.log_valid + (size_t)b * LR;
+  if (L < C) s.cid[L] = t.track_id[(size_t)b * C + L];
+  if (L < G) s.last[L] = -1;
+  for (int i = L; i < G * C; i += 64) s.ov[i] = 0;
+  long long c_frames = 0, c_invalid = 0, c_truth = 0, c_tp = 0, c_fn = 0, c_fp = 0, c_idsw = 0, c_gtp = 0, c_gfp = 0, c_nn = 0, c_gnn = 0;
+  double iou_sum = 0.0, err_sum = 0.0, nees_sum = 0.0, gerr_sum = 0.0, gnees_sum = 0.0;
+  for (int f = 0; f < lag; ++f) {
+    const size_t fb = (size_t)f * B + b;
+    const long long fi = t.frame_index[fb];
+    const bool truth = tr.truth_valid[fb] != 0;
+    const bool finite = fi >= 0 && lvalid[(int)(fi % LR)] != 0;
+    const int kind = __builtin_amdgcn_readfirstlane(fi < 0 || !truth ? 0 : finite ? 2 : 1);   // 0 nothing, 1 frames_invalid, 2 scored
+    sq_wave_lds_order();   // (the last frame's readers are done with the tables)
+    if (kind != 2) {
+      c_invalid += kind;
+      if (L < G) {
+        const size_t e = (((size_t)v * lag + f) * B + b) * G + L;
+        if (o.match) o.match[e] = -1;
+        if (o.match_iou) o.match_iou[e] = 0.0f;
+      }
+      continue;
+    }
+    // ---- 1, 3: presence on both sides, the candidates' IoU, the overlap table
+    if (L < C) {
+      const int st = t.state[fb * C + L];
+      s.cpres[L] = st == 1 || (fill && st == 2);
+      s.cgap[L] = st == 2;
+    }
+    if (L < G) s.tpres[L] = tr.truth_present[fb * G + L] != 0;
+    sq_wave_lds_order();
+    for (int i = L; i < G * C; i += 64) {
+      const int g = i / C, c = i - g * C;
+      float q = -1.0f;
+      if (s.tpres[g] && s.cpres[c]) {
+        const float* p = tr.truth_box + (fb * G + g) * 4;
+        const size_t e = (fb * C + c) * 2;
+        const float h = t.size[e], w = t.size[e + 1];
+        q = sq_box_iou(SqBox{p[0], p[1], p[2], p[3]}, SqBox{fmaf(-0.5f, h, src[e * 5]), fmaf(-0.5f, w, src[(e + 1) * 5]), h, w});
+      }
+      s.iou[i] = q;
+      if (q >= iou_min) s.ov[i] += 1;
+    }
+    sq_wave_lds_order();
+    // ---- 3: the assignment
+    if (a.match) sq_assign_keep_optimal(s.iou, C, G, C, iou_min, s.last, s.cid, s.rm, s.claim, s.w);
+    else if (L == 0) sq_assign_keep_greedy(s.iou, C, G, C, iou_min, s.last, s.cid, s.rm, s.claim);
+    sq_wave_lds_order();
+    // ---- 3, 4: the events and the pairs' errors, one lane
+    if (L == 0) {
+      int n_truth = 0, tp = 0, fn = 0, fp = 0, sw = 0, gtp = 0, gfp = 0, nn = 0, gnn = 0;
+      for (int g = 0; g < G; ++g) {
+        if (!s.tpres[g]) continue;
+        ++n_truth;
+        const int c = s.rm[g];
+        if (c < 0) { ++fn; continue; }
+        ++tp;
+        const int id = s.cid[c], last = s.last[g];
+        sw += last >= 0 && last != id;
+        s.last[g] = id;
+        iou_sum += (double)s.iou[g * C + c];
+        const float* p = tr.truth_box + (fb * G + g) * 4;
+        const float* ky = src + (fb * C + c) * 10;
+        const float ty = fmaf(0.5f, p[2], p[0]), tx = fmaf(0.5f, p[3], p[1]);
+        const float dy = ty - ky[0], dx = tx - ky[5];
+        const float err = sqrtf(fmaf(dy, dy, dx * dx));
+        const float ppy = ky[2], ppx = ky[7];
+        const bool honest = ppy > 0.0f && ppx > 0.0f;   // (a NaN fails)
+        const float nees = dy * dy / ppy + dx * dx / ppx;
+        const bool gap = s.cgap[c] != 0;
+        err_sum += (double)err;
+        if (honest) { nees_sum += (double)nees; ++nn; }
+        if (gap) {
+          ++gtp;
+          gerr_sum += (double)err;
+          if (honest) { gnees_sum += (double)nees; ++gnn; }
+        }
+      }
+      for (int c = 0; c < C; ++c) {
+        const bool un = s.cpres[c] && !s.claim[c];
+        fp += un;
+        gfp += un && s.cgap[c];
+      }
+      ++c_frames; c_truth += n_truth; c_tp += tp; c_fn += fn; c_fp += fp; c_idsw += sw; c_gtp += gtp; c_gfp += gfp; c_nn += nn; c_gnn += gnn;
+    }
+    if (L < G) {
+      const size_t e = (((size_t)v * lag + f) * B + b) * G + L;
+      const int c = s.rm[L];
+      if (o.match) o.match[e] = c;
+      if (o.match_iou) o.match_iou[e] = c >= 0 ? s.iou[L * C + c] : 0.0f;
+    }
+  }
+  // ---- 5: the window's identity assignment
+  sq_wave_lds_order();
+  const long long idtp = sq_assign_optimal_i32(s.ov, C, G, C, s.assign);
+  sq_wave_lds_order();
+  if (L < G && o.assign) {
+    const int c = s.assign[L];
+    o.assign[((size_t)v * B + b) * G + L] = c >= 0 && s.ov[L * C + c] > 0 ? c : -1;
+  }
+  if (L == 0) {
+    int64_t* c = o.counts + ((size_t)b * SQAIR_TRACKLOG_SCORE_VIEWS + v) * SQAIR_TRACKLOG_SCORE_COUNTS;
+    c[0] = c_frames; c[1] = c_invalid; c[2] = c_truth; c[3] = c_tp; c[4] = c_fn; c[5] = c_fp; c[6] = c_idsw; c[7] = c_gtp; c[8] = c_gfp;
+    c[9] = c_nn; c[10] = c_gnn; c[11] = idtp; c[12] = c_truth - idtp; c[13] = c_tp + c_fp - idtp;   // (tp + fp: the present columns)
+    double* d = o.sums + ((size_t)b * SQAIR_TRACKLOG_SCORE_VIEWS + v) * SQAIR_TRACKLOG_SCORE_SUMS;
+    d[0] = iou_sum; d[1] = err_sum; d[2] = nees_sum; d[3] = gerr_sum; d[4] = gnees_sum;
+  }
+}
+int sq_launch_lane_tracklog_score(const LaneTrackLogScoreArgs& a, hipStream_t s) {
+  SQ_LAUNCH(k_lane_tracklog_score, dim3(a.B), dim3(256), 0, s, a);
+  return 0;
+}

@@ -3,7 +3,7 @@
 // sqair_set_estimate / _layers / _score / _identity / _motion / _tracklog / _score_ids / _idf / _hota), the estimate's refusal of a pass, ONE builder per kernel's arguments -- called by the
 // pass and by the kernel-level entry point alike --, the pass's launch sequence (sq_launch_lane_answers, called by sq_forward_impl
 // with the block sq_resolve_pass resolved) and the stand-alone entry points (sqair_lane_*_test, sqair_lane_traj_score,
-// sqair_lane_idf_solve, sqair_lane_hota_solve, sqair_lane_tracklog_smooth).  Host code
+// sqair_lane_idf_solve, sqair_lane_hota_solve, sqair_lane_tracklog_smooth, sqair_lane_tracklog_score).  Host code
 // only: the kernels and their launchers live in sqair_lane.hip, which work here does not move.  A further follower is one member
 // of SqLaneSet, its registration and builder here, and one line of sq_launch_lane_answers.
 #include "sqair_internal.h"
@@ -547,6 +547,31 @@ extern "C" int sqair_lane_tracklog_smooth(SqairHandle* h, const SqairLaneTrackLo
   LaneTrackLogSmoothArgs a; memset(&a, 0, sizeof(a));
   a.log = *log; a.out = *out; a.work = (int32_t*)work; a.q = q; a.r = r; a.v0_var = v0_var; a.lag = lag; a.C = C; a.N = N; a.B = B;
   sq_launch_lane_tracklog_smooth(a, (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+// track log scoring (include/sqair_hip.h: sqair_lane_tracklog_score): a stand-alone call on the table the solve wrote -- or on a test's
+// tensors --, nothing registered on the handle, which gives the error text
+extern "C" int sqair_lane_tracklog_score(SqairHandle* h, const SqairLaneTrackLog* log, const SqairTrackLogOut* table,
+                                         const SqairTrackLogTruth* truth, const SqairTrackLogScore* score, int lag, int C, int B, int match,
+                                         void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_lane_tracklog_score: ";
+  if (!log || !table || !truth || !score) return sq_no(h, who + "log, table, truth and score must not be NULL");
+  if (B < 1) return sq_no(h, who + "B = " + std::to_string(B) + " must be >= 1");
+  if (sq_tracklog_fields(h, who, *log) != 0) return -1;
+  if (lag < 1 || lag > log->L) return sq_no(h, who + "lag = " + std::to_string(lag) + " must lie in 1..L = " + std::to_string(log->L));
+  if (C < 1 || C > SQ_TRACKLOG_MAXC) return sq_no(h, who + "C = " + std::to_string(C) + " must lie in 1..64");
+  if (sq_truth_slots_refusal(h, who, truth->G) != 0 || sq_unit_refusal(h, who, "iou_min", score->iou_min) != 0) return -1;
+  if (match != 0 && match != 1) return sq_no(h, who + "match = " + std::to_string(match) + " must be 0 (greedy) or 1 (optimal)");
+  if (!table->track_id || !table->frame_index || !table->state || !table->size || !table->filt || !table->smooth)
+    return sq_no(h, who + "the table's track_id, frame_index, state, size, filt and smooth must not be NULL");
+  if (!truth->truth_box || !truth->truth_present || !truth->truth_valid)
+    return sq_no(h, who + "truth_box, truth_present and truth_valid must not be NULL");
+  if (!score->counts || !score->sums) return sq_no(h, who + "counts and sums must not be NULL");
+  LaneTrackLogScoreArgs a; memset(&a, 0, sizeof(a));
+  a.log = *log; a.tab = *table; a.tr = *truth; a.sc = *score; a.lag = lag; a.C = C; a.B = B; a.match = match;
+  sq_launch_lane_tracklog_score(a, (hipStream_t)stream);
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }

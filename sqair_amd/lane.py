@@ -57,6 +57,16 @@ backward (Rauch-Tung-Striebel), so that a frame in which the object was not seen
 hole and a track that ended is still there.  It does not need ``motion=True``.  ``reset(lanes)`` empties those lanes' logs.
 ``mot_rows(log, lane)`` lists a lane's smoothed boxes as MOTChallenge rows.
 
+``tracklog_truth=G`` (with ``tracklog=L``): the stream also keeps the truth of the last L stepped frames in a ring on the device --
+a step's ``truth`` (accepted then without ``score=True``) goes to position (frames stepped + t) mod L by small copies beside the
+score's, outside the captured graph; a step without truth leaves its positions invalid -- and ``track_log(lag, score=True)`` scores
+the log against it with one more launch behind the solve (sqair_lane_tracklog_score): four views of the one table -- ``filtered``
+and ``smooth``, each as reported and with the gaps filled -- each with the CLEAR-MOT events, the identity measures over the window,
+the centre error of every matched pair and its normalised square (``nees``, 2 for an honest sigma), and the same figures over the
+filled gaps alone: whether gap filling turned misses into hits or into false positives, whether smoothing moved the boxes towards
+the truth, whether sigma is honest.  Window frame f of every lane is stream frame (frames stepped - lag + f), whatever the lane's
+own ``count`` says after a ``reset(lanes)``, so one gather of the ring serves all lanes; ``reset(lanes)`` leaves the ring alone.
+
 ``score_idf=True`` (with ``score=True``): the score's idsw counts the moments an identity changes, not for how long the wrong id then
 stays.  The stream then also keeps, per lane and on the device, how many frames of the open clip every truth overlapped (IoU >=
 ``score_iou``) every predicted id -- the id words the score reads: ``obj_id``, or ``lane_id`` with ``score_ids="lane"`` --, up to
@@ -186,6 +196,58 @@ def track_log_views(got):
     return res
 
 
+def ring_runs(n, T, L):
+    """Where the T frames of a step go in a ring of L positions that has taken n frames: [(lo, hi, at)], frames lo..hi-1 of the step
+    to positions at.. -- frame t at (n + t) mod L, as contiguous runs; of a step longer than the ring only the last L frames stay."""
+    runs, t = [], max(0, T - L)
+    while t < T:
+        at = (n + t) % L
+        m = min(T - t, L - at)
+        runs.append((t, t + m, at))
+        t += m
+    return runs
+
+
+def ring_window(ring, n, lag):
+    """The last ``lag`` positions of a ring tensor [L, ...] that has taken n frames, in window order (oldest first): window frame f
+    is stream frame n - lag + f at position (n - lag + f) mod L.  A new tensor; frames before the ring existed (n - lag + f < 0) hold
+    whatever the position holds -- the caller invalidates them."""
+    L = ring.shape[0]
+    start = (n - lag) % L
+    if start + lag <= L:
+        return ring[start:start + lag].clone()
+    return torch.cat([ring[start:], ring[:start + lag - L]])
+
+
+def track_log_score(got):
+    """``track_log(score=True)``'s ``log["score"]``, formed on the host from the scorer's outputs read back (include/sqair_hip.h:
+    sqair_lane_tracklog_score; host tensors by _capi.tracklog_score_shapes): per view name of _capi.TRACKLOG_SCORE_VIEWS a dict of
+    the per-lane counters [B] int64 and sums [B] float64 by name, ``assign`` [B, G], ``match`` and ``match_iou`` [lag, B, G], and
+    pooled over the lanes, formed from the counters as ``score()`` and ``idf_score()`` form theirs and NaN where a denominator is 0:
+    ``mota`` = 1 - (fn + fp + idsw) / truth, ``motp`` = iou_sum / tp, ``idf1`` = 2 idtp / (2 idtp + idfp + idfn), ``idp`` = idtp /
+    (idtp + idfp), ``idr`` = idtp / (idtp + idfn), ``mean_err`` = err_sum / tp (pixels), ``nees`` = nees_sum / nees_n (2 for an
+    honest sigma), and over the filled gaps ``gap_err`` = gap_err_sum / gap_tp, ``gap_nees`` = gap_nees_sum / gap_nees_n and
+    ``gap_precision`` = gap_tp / (gap_tp + gap_fp)."""
+    res = {}
+    for v, name in enumerate(_capi.TRACKLOG_SCORE_VIEWS):
+        r = _columns(got["counts"][:, v], _capi.TRACKLOG_SCORE_COUNTS)
+        r.update(_columns(got["sums"][:, v], _capi.TRACKLOG_SCORE_SUMS))
+        tot = {n: (float if n in _capi.TRACKLOG_SCORE_SUMS else int)(t.sum()) for n, t in r.items()}
+        r.update(assign=got["assign"][v], match=got["match"][v], match_iou=got["match_iou"][v])
+        r["mota"] = 1.0 - _ratio(tot["fn"] + tot["fp"] + tot["idsw"], tot["truth"])
+        r["motp"] = _ratio(tot["iou_sum"], tot["tp"])
+        r["idf1"] = _ratio(2 * tot["idtp"], 2 * tot["idtp"] + tot["idfp"] + tot["idfn"])
+        r["idp"] = _ratio(tot["idtp"], tot["idtp"] + tot["idfp"])
+        r["idr"] = _ratio(tot["idtp"], tot["idtp"] + tot["idfn"])
+        r["mean_err"] = _ratio(tot["err_sum"], tot["tp"])
+        r["nees"] = _ratio(tot["nees_sum"], tot["nees_n"])
+        r["gap_err"] = _ratio(tot["gap_err_sum"], tot["gap_tp"])
+        r["gap_nees"] = _ratio(tot["gap_nees_sum"], tot["gap_nees_n"])
+        r["gap_precision"] = _ratio(tot["gap_tp"], tot["gap_tp"] + tot["gap_fp"])
+        res[name] = r
+    return res
+
+
 def mot_rows(log, lane):
     """The MOTChallenge rows (frame, id, x, y, w, h) of lane ``lane`` of a ``track_log()`` result: one row per (frame, track) whose
     ``state`` is 1 (seen) or 2 (a gap the smoother filled), from the smoothed boxes, ordered by frame, then by id; ``frame`` is the
@@ -220,7 +282,8 @@ class LaneAnswers(object):
     stream touches either); ``register`` allocates the buffers and registers them on the core's handle.  ``flat`` / ``views``: ONE
     allocation and its views by field, ``est`` (field_views) -- everything a step copies out as ``out["lane"]``; ``score_buf`` and
     ``ident_buf``: the score's truth, accumulators and identity memory, the identity's track table and counters; ``tracklog_buf``:
-    the track log's ring of every lane; ``idf_buf``: the
+    the track log's ring of every lane, ``truth_ring`` (with ``tracklog_truth``) the truth of the last L stepped frames beside it and
+    ``ring_frames`` the frames it has taken; ``idf_buf``: the
     IDF1 table of every lane's open clip and the totals over the closed ones; ``hota_buf``: the HOTA log of every lane's open clip
     and its totals."""
 
@@ -228,7 +291,7 @@ class LaneAnswers(object):
                  identity, identity_iou, identity_tracks, identity_max_age, identity_reid_dist, identity_reid_what, identity_appearance,
                  score_ids, score_idf=False, score_idf_ids=32, score_match="greedy", identity_match="greedy", score_hota=False,
                  score_hota_ids=32, score_hota_frames=256, motion=False, motion_q=0.25, motion_r=1.0, motion_v0=16.0, motion_gate=3.0,
-                 motion_nis=False, tracklog=None, tracklog_tracks=16):
+                 motion_nis=False, tracklog=None, tracklog_tracks=16, tracklog_truth=None):
         self.step_fn, who = who + ".step: ", who + ": "
 
         def bad(why):
@@ -281,6 +344,14 @@ class LaneAnswers(object):
             bad("tracklog_tracks must be an integer in [1, {}]".format(_capi.TRACKLOG_MAX_TRACKS))
         self.tracklog = tracklog is not None
         self.log_L, self.log_C = (int(tracklog), int(tracklog_tracks)) if self.tracklog else (0, 0)
+        if tracklog_truth is not None and not self.tracklog:
+            bad("tracklog_truth is for a stream with tracklog=L")
+        if tracklog_truth is not None and not is_int_in(tracklog_truth, 1, _capi.SCORE_MAX_TRUTH):
+            bad("tracklog_truth must be an integer in [1, {}]".format(_capi.SCORE_MAX_TRUTH))
+        self._truth_text = "tracklog_truth must equal score_truth: a step's truth feeds the score and the log's truth ring alike"
+        if tracklog_truth is not None and score and score_truth is not None and int(score_truth) != int(tracklog_truth):
+            bad(self._truth_text)
+        self.log_G = 0 if tracklog_truth is None else int(tracklog_truth)   # truth slots of the log's truth ring; 0: none is kept
         if score_ids not in ("row", "lane"):
             bad("score_ids must be 'row' or 'lane'")
         if score_ids == "lane" and not (score and identity):
@@ -315,6 +386,8 @@ class LaneAnswers(object):
         """``G`` and ``M`` for the core's N slots: the last check, and the only one that needs the core (its handle is not touched)."""
         if self.scored:
             self.G = core.N if self._truth_slots is None else int(self._truth_slots)
+            if self.log_G and self.log_G != self.G:   # (score_truth defaulted to the core's N)
+                raise ValueError(self.who + self._truth_text)
         if self.identified:
             self.M = min(_capi.IDENT_MAX_TRACKS, 2 * core.N) if self._tracks is None else int(self._tracks)
             if not core.N <= self.M:
@@ -382,6 +455,9 @@ class LaneAnswers(object):
                 self.tracklog_buf = zeros_of("SqairLaneTrackLog", _capi.tracklog_shapes(B, self.log_L, N), core.device)
                 self._log_c = _capi.SqairLaneTrackLog(L=self.log_L, **{n: t.data_ptr() for n, t in self.tracklog_buf.items()})
                 self._log_out = {}   # the solve's outputs and scratch of the LAST lag asked for
+                if self.log_G:   # the truth of the last L stepped frames beside the log: written by copies, read by track_log(score=True)
+                    self.truth_ring = zeros_of("SqairTrackLogTruth", _capi.tracklog_truth_shapes(self.log_L, B, self.log_G), core.device)
+                    self.ring_frames = 0   # frames stepped since the ring was made: frame t of a step goes to (ring_frames + t) mod L
                 sync()
                 core.check(lib.sqair_set_tracklog(h, C.byref(self._log_c), T, B), "sqair_set_tracklog")
             if self.score_ids == "lane":
@@ -409,11 +485,11 @@ class LaneAnswers(object):
         if truth is None:
             return None
         fn = self.step_fn
-        if not self.scored:
+        if not (self.scored or self.log_G):
             raise ValueError(fn + "truth is for a stream with score=True")
         if not isinstance(truth, dict) or "box" not in truth or "present" not in truth or set(truth) - {"box", "present", "valid"}:
             raise ValueError(fn + "truth must be a dict with box, present and optionally valid")
-        T, B, G = self.T, self.B, self.G
+        T, B, G = self.T, self.B, self.G if self.scored else self.log_G
         box = torch.as_tensor(truth["box"]).to(torch.float32)
         present = torch.as_tensor(truth["present"])
         valid = truth.get("valid")
@@ -425,15 +501,26 @@ class LaneAnswers(object):
 
     def feed_truth(self, truth):
         """A step's checked truth into the score's own buffers, on the current stream (as the mask of a stream with missing frames:
-        the kernel reads the stream's buffers, so one graph serves every step); without one ``truth_valid`` is zeroed once."""
-        if not self.scored:
-            return
-        if truth is not None:
-            for n, t in zip(("truth_box", "truth_present", "truth_valid"), truth):
-                self.score_buf[n].copy_(t, non_blocking=True)
-        elif not self._valid_is_zero:
-            self.score_buf["truth_valid"].zero_()
-        self._valid_is_zero = truth is None
+        the kernel reads the stream's buffers, so one graph serves every step); without one ``truth_valid`` is zeroed once.  A
+        stream with ``tracklog_truth`` then writes the step's frames into the log's truth ring, frame t at (ring_frames + t) mod L --
+        from the score's buffers where there is a score, so the truth is uploaded once --, or zeroes ``truth_valid`` there."""
+        names = ("truth_box", "truth_present", "truth_valid")
+        if self.scored:
+            if truth is not None:
+                for n, t in zip(names, truth):
+                    self.score_buf[n].copy_(t, non_blocking=True)
+            elif not self._valid_is_zero:
+                self.score_buf["truth_valid"].zero_()
+            self._valid_is_zero = truth is None
+        if self.log_G:
+            src = None if truth is None else self.score_buf if self.scored else dict(zip(names, truth))
+            for lo, hi, at in ring_runs(self.ring_frames, self.T, self.log_L):
+                if src is None:
+                    self.truth_ring["truth_valid"][at:at + hi - lo].zero_()
+                else:
+                    for n in names:
+                        self.truth_ring[n][at:at + hi - lo].copy_(src[n][lo:hi], non_blocking=True)
+            self.ring_frames += self.T
 
     def copy_out(self):
         """``out["lane"]`` of the step just run: views of one clone."""
@@ -548,7 +635,7 @@ class LaneAnswers(object):
         res["exact"] = int(res["dropped_frames"].sum()) == 0 and int(res["overflow_ids"].sum()) == 0
         return res
 
-    def track_log(self, lag=None, q=None, r=None, v0=None):
+    def track_log(self, lag=None, q=None, r=None, v0=None, score=False, score_iou=0.5, score_match="greedy"):
         if not self.tracklog:
             raise ValueError("SqairStream.track_log: the stream keeps no track log (SqairStream(..., estimate=True, identity=True, "
                              "tracklog=L))")
@@ -560,6 +647,14 @@ class LaneAnswers(object):
         for name, v in scal.items():
             if not 0.0 < v < float("inf"):   # (NaN fails too)
                 raise ValueError("SqairStream.track_log: {} must be finite and > 0".format(name))
+        if score:
+            if not self.log_G:
+                raise ValueError("SqairStream.track_log: score=True is for a stream that keeps the log's truth (SqairStream(..., "
+                                 "tracklog=L, tracklog_truth=G))")
+            score_iou = float(score_iou)
+            check_unit("SqairStream.track_log: ", "score_iou", score_iou)
+            if score_match not in MATCH_MODES:
+                raise ValueError("SqairStream.track_log: score_match must be 'greedy' or 'optimal'")
         core, B, Cn = self.core, self.B, self.log_C
         with torch.cuda.device(core.device):
             core._join_in()
@@ -575,8 +670,29 @@ class LaneAnswers(object):
                                                                scal["r"], scal["v0"], C.byref(o["c"]), o["work"].data_ptr(),
                                                                core._stream()), "sqair_lane_tracklog_smooth")
                 got = {n: t.clone() for n, t in o["out"].items()}
+                scored = self._score_log(o, lag, score_iou, MATCH_MODES.index(score_match)) if score else None
             core._join_out()
-        return track_log_views({n: t.cpu() for n, t in got.items()})
+        res = track_log_views({n: t.cpu() for n, t in got.items()})
+        if scored is not None:
+            res["score"] = track_log_score({n: t.cpu() for n, t in scored.items()})
+        return res
+
+    def _score_log(self, o, lag, iou_min, match):
+        """The scorer directly behind the solve, on the current stream and on the solve's device tensors ``o["out"]`` (include/sqair_hip.h:
+        sqair_lane_tracklog_score): the truth ring gathered into window order -- window frame f of every lane is stream frame
+        ring_frames - lag + f; a frame before the ring existed is invalid --, one launch, the outputs' copies."""
+        core, B, G, n = self.core, self.B, self.log_G, self.ring_frames
+        if "score" not in o:   # (the outputs belong to the solve's lag: another lag has dropped them with the rest)
+            o["score"] = zeros_of("SqairTrackLogScore", _capi.tracklog_score_shapes(lag, B, G), core.device)
+        truth = {k: ring_window(t, n, lag) for k, t in self.truth_ring.items()}
+        if n < lag:
+            truth["truth_valid"][:lag - n].zero_()
+        c_tab = _capi.SqairTrackLogOut(**{k: o["out"][k].data_ptr() for k in _capi.TRACKLOG_SCORE_TABLE})
+        c_truth = _capi.SqairTrackLogTruth(G=G, **{k: t.data_ptr() for k, t in truth.items()})
+        c_score = _capi.SqairTrackLogScore(iou_min=iou_min, **{k: t.data_ptr() for k, t in o["score"].items()})
+        core.check(core.lib.sqair_lane_tracklog_score(core.handle, C.byref(self._log_c), C.byref(c_tab), C.byref(c_truth), C.byref(c_score),
+                                                      lag, self.log_C, B, match, core._stream()), "sqair_lane_tracklog_score")
+        return {k: t.clone() for k, t in o["score"].items()}
 
     def identities(self):
         if not self.identified:

@@ -42,7 +42,7 @@ network "see" an empty scene and kill the objects.
 With ``estimate=True`` a step also returns ``out["lane"]``: one answer per lane and frame from the K particles, and its followers
 say more about it, each one more kernel of the pass -- ``estimate_layers`` which pixels each object occupies, ``identity`` a track id
 that stays on an object (``motion``: with a velocity filter per track inside the same kernel, sqair_set_motion; ``tracklog``: the
-last frames of every lane by lane_id in a ring on the device, ``track_log()`` their smoothed trajectories, sqair_set_tracklog), ``score`` the CLEAR-MOT events against a step's ``truth`` (``score()``, ``identities()``; ``score_match`` / ``identity_match`` =
+last frames of every lane by lane_id in a ring on the device, ``track_log()`` their smoothed trajectories, sqair_set_tracklog; ``tracklog_truth``: the steps' truth kept beside it, ``track_log(score=True)`` the trajectories scored against it, sqair_lane_tracklog_score), ``score`` the CLEAR-MOT events against a step's ``truth`` (``score()``, ``identities()``; ``score_match`` / ``identity_match`` =
 "optimal": their per-frame matching as keep + optimal, sqair_set_lane_match), ``score_idf`` the identity overlap table
 IDF1 is solved from (``idf_score()``), ``score_hota`` the clip log HOTA is solved from (``hota_score()``); ``forecast`` and
 ``tracks`` with ``lane=True, truth=...`` score the lane forecast and the lane tracks (``trajectory_score(kind)``).  sqair_amd/lane.py
@@ -79,7 +79,7 @@ class SqairStream(object):
                  identity_reid_what=float("inf"), identity_appearance=True, score_ids="row", score_idf=False, score_idf_ids=32,
                  score_match="greedy", identity_match="greedy", score_hota=False, score_hota_ids=32, score_hota_frames=256,
                  motion=False, motion_q=0.25, motion_r=1.0, motion_v0=16.0, motion_gate=3.0, motion_nis=False, tracklog=None,
-                 tracklog_tracks=16):
+                 tracklog_tracks=16, tracklog_truth=None):
         if core.cfg.sample_from_prior:
             raise ValueError("SqairStream: generation modes (sample_from_prior) do not carry a state across calls")
         if resample not in (None, "systematic"):
@@ -91,7 +91,7 @@ class SqairStream(object):
                                      score_iou, score_truth, identity, identity_iou, identity_tracks, identity_max_age,
                                      identity_reid_dist, identity_reid_what, identity_appearance, score_ids, score_idf, score_idf_ids,
                                      score_match, identity_match, score_hota, score_hota_ids, score_hota_frames, motion, motion_q,
-                                     motion_r, motion_v0, motion_gate, motion_nis, tracklog, tracklog_tracks)   # (checks only)
+                                     motion_r, motion_v0, motion_gate, motion_nis, tracklog, tracklog_tracks, tracklog_truth)   # (checks only)
         self.smc = resample is not None
         self.ess_frac = ess_frac
         self.core = core
@@ -146,9 +146,9 @@ class SqairStream(object):
         carried(n) for n in ("state", "log_weight_sum", "log_z", "log_evidence", "ess", "u", "resampled", "_src", "_armed",
                              "_src_is_identity", "history", "history_fields"))
     # the lane answers', likewise
-    estimate, scored, identified, G, M, _est_flat, _est_views, _est, _score, _ident, _idf, _hota, _tracklog = (
+    estimate, scored, identified, G, M, _est_flat, _est_views, _est, _score, _ident, _idf, _hota, _tracklog, _truth_ring = (
         lane_answer(n) for n in ("estimate", "scored", "identified", "G", "M", "flat", "views", "est", "score_buf", "ident_buf", "idf_buf",
-                                 "hota_buf", "tracklog_buf"))
+                                 "hota_buf", "tracklog_buf", "truth_ring"))
     _traj = lane_answer("acc", of="traj")
 
     def _set_smc(self, uniforms):
@@ -196,7 +196,9 @@ class SqairStream(object):
         replaced by zeros, so it may hold anything, NaN included.  Default: every lane observed.  Returned among the outputs.
         Streams with ``estimate=True`` add ``lane``: the per-lane answer {name: [T', B, ...]} of this step's rows.  ``truth``
         (streams with ``score=True``): dict(box=[T', B, G, 4] (y, x, h, w) in pixels, present=[T', B, G], valid=[T', B] or None = all),
-        with [B, ...] accepted when T' = 1; the step's lane answer is scored against it.  Default: nothing is scored."""
+        with [B, ...] accepted when T' = 1; the step's lane answer is scored against it.  Default: nothing is scored.  Streams with
+        ``tracklog_truth=G`` take it too, with or without ``score=True``, and keep it in the track log's truth ring for
+        ``track_log(score=True)``; a step without it leaves its frames of the ring without truth."""
         observed = self._check_observed(observed)   # (before the core is touched)
         truth = self.lane.check_truth(truth)
         core, cs = self.core, self.carried
@@ -284,7 +286,7 @@ class SqairStream(object):
         ``trk_centre``, ``trk_vel``, ``trk_sigma`` [B, M, 2] and ``trk_pred_box`` [B, M, 4], the coasted box of every live track."""
         return self.lane.identities()
 
-    def track_log(self, lag=None, q=None, r=None, v0=None):
+    def track_log(self, lag=None, q=None, r=None, v0=None, score=False, score_iou=0.5, score_match="greedy"):
         """The trajectories of the last ``lag`` logged frames (default: all ``tracklog`` = L of them) per ``lane_id`` (include/sqair_hip.h:
         sqair_set_tracklog, sqair_lane_tracklog_smooth): one launch on the device.  C = ``tracklog_tracks`` columns per lane.
         ``track_id`` [B, C] int32, the C largest ids of the window ascending, -1 = padding; ``n_tracks`` [B], the distinct ids of the
@@ -295,8 +297,20 @@ class SqairStream(object):
         ``filtered``: dicts of ``centre``, ``velocity``, ``sigma`` [lag, B, C, 2] = (y, x) and ``box`` [lag, B, C, 4] = (y, x, h, w), the
         Rauch-Tung-Striebel smoothed and the causal estimate of a constant-velocity filter started at the track's first frame in
         the window; 0 where ``state`` is 0 or 3.  ``q``, ``r``, ``v0``: the filter's scalars, default the stream's ``motion_q``,
-        ``motion_r``, ``motion_v0`` (set or not: the log does not need ``motion=True``).  Host tensors."""
-        return self.lane.track_log(lag, q, r, v0)
+        ``motion_r``, ``motion_v0`` (set or not: the log does not need ``motion=True``).  Host tensors.
+        ``score=True`` (a stream with ``tracklog_truth=G``) scores the table against the truth the steps were given, one more launch
+        directly behind the solve (include/sqair_hip.h: sqair_lane_tracklog_score, which states the semantics), and adds ``score``:
+        per view -- ``"filtered"`` (what a causal tracker reported), ``"smooth"``, ``"filtered_filled"`` and ``"smooth_filled"`` (the
+        gaps filled by the model: what ``mot_rows`` exports) -- the per-lane counters ``frames``, ``frames_invalid``, ``truth``, ``tp``,
+        ``fn``, ``fp``, ``idsw``, ``gap_tp``, ``gap_fp``, ``nees_n``, ``gap_nees_n``, ``idtp``, ``idfn``, ``idfp`` [B] int64 and sums
+        ``iou_sum``, ``err_sum``, ``nees_sum``, ``gap_err_sum``, ``gap_nees_sum`` [B] float64, ``assign`` [B, G] (the column the window's
+        identity assignment gives each truth, -1 none), ``match`` and ``match_iou`` [lag, B, G] (the column matched per frame), and pooled
+        over the lanes ``mota``, ``motp``, ``idf1``, ``idp``, ``idr``, ``mean_err`` (pixels between the centres of a matched pair), ``nees``
+        (its normalised square: 2 for an honest ``sigma``), ``gap_err``, ``gap_nees`` and ``gap_precision`` = gap_tp / (gap_tp + gap_fp)
+        over the filled gaps; NaN where a denominator is 0.  ``score_iou``: the IoU a pair needs; ``score_match``: per-frame matching
+        as keep + "greedy" or keep + "optimal".  The figures are those of this window alone: windows overlap, nothing accumulates.
+        Without ``score`` nothing more is launched."""
+        return self.lane.track_log(lag, q, r, v0, score, score_iou, score_match)
 
     # ---- trajectory scoring ------------------------------------------------------------------------------------------------
     def _check_traj_truth(self, fn, truth, lane, F, default_anchor, link_ids, truth_iou, link_match="greedy"):

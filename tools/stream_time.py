@@ -101,6 +101,15 @@ lag 10 and 64 -- the solve, the copies and what the host forms from them, every 
 run.  Recorded, not gated on:
 
     python tools/stream_time.py --tracklog [--out profiles/stream_tracklog_time.json]
+
+With --tracklog-score: the price of track log scoring (SqairStream(..., tracklog=L, tracklog_truth=G), ``track_log(lag, score=True)``,
+include/sqair_hip.h: sqair_lane_tracklog_score) at cfg-2's batch (L = 64, C = 16, G = 2).  Two streams alternating in one process as
+with --history, SMC + estimate + identity + log without and with the truth ring, the second fed a device-resident truth: the difference
+is the per-step cost of the ring's copies (no node is added).  Then ``track_log(lag, score=True)`` against ``track_log(lag)`` on the
+same stream, alternating, lag 10 and 64, for both matchings, every call waited for; and the scorer alone at the limits of its
+arguments (lag 4096, C 64, G 16) on one lane, where lane 0's greedy walk is long.  Recorded, not gated on:
+
+    python tools/stream_time.py --tracklog-score [--out profiles/tracklog_score_time.json]
 """
 import argparse
 import json
@@ -559,6 +568,106 @@ def time_tracklog(B, K, N, steps, warmup, L=64, rounds=10, hw=(50, 50)):
     return res
 
 
+def _timed_calls(core, calls, rounds=10, block=5):
+    """{name: [ms]} of the callables ``calls`` in alternating blocks in this process, every call waited for; round -1 is the warm-up."""
+    ms = {n: [] for n in calls}
+    for rnd in range(-1, rounds):
+        for name, call in calls.items():
+            with core.on_stream():
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(block)]
+                for x, y in ev:
+                    x.record()
+                    call()
+                    y.record()
+                    core.stream.synchronize()
+            if rnd >= 0:
+                ms[name] += [x.elapsed_time(y) for x, y in ev]
+    return ms
+
+
+def _spread(ms):
+    return dict(median=float(np.median(ms)), p10=float(np.percentile(ms, 10)), p90=float(np.percentile(ms, 90)))
+
+
+def scorer_at_the_limits(lag=4096, C=64, G=16, reps=3):
+    """k_lane_tracklog_score alone on one lane at the limits of its arguments, on a table made by hand: 64 columns in 16 clusters of four
+    around 16 truths, every pair of a cluster eligible, a quarter of the (frame, column)s a gap -- the longest walk lane 0's greedy
+    scan has.  Milliseconds per launch, every launch waited for, for both matchings."""
+    import ctypes as C_
+    core = SqairCore(make_flags(k_particles=2, n_steps_per_image=4), (50, 50))   # (a handle for the error text: the scorer reads nothing else of it)
+    lib, h = core.lib, core.handle
+    rng = np.random.default_rng(5)
+    dev = lambda a: torch.as_tensor(a).cuda()
+    centre = np.zeros((lag, 1, C, 2), np.float32)
+    cluster = np.arange(C) // 4
+    centre[..., 0] = 10.0 + 30.0 * (cluster // 4) + rng.normal(0, 0.4, (lag, 1, C))
+    centre[..., 1] = 10.0 + 30.0 * (cluster % 4) + rng.normal(0, 0.4, (lag, 1, C))
+    kf = np.zeros((lag, 1, C, 2, 5), np.float32)
+    kf[..., 0], kf[..., 2], kf[..., 4] = centre, 1.0, 1.0
+    tbox = np.zeros((lag, 1, G, 4), np.float32)
+    tbox[..., 0], tbox[..., 1], tbox[..., 2:] = 30.0 * (np.arange(G) // 4), 30.0 * (np.arange(G) % 4), 20.0
+    table = dict(track_id=dev(np.arange(C, dtype=np.int32)[None]), frame_index=dev(np.arange(lag, dtype=np.int64)[:, None]),
+                 state=dev(np.where(rng.uniform(size=(lag, 1, C)) < 0.25, 2, 1).astype(np.int32)),
+                 size=dev(np.full((lag, 1, C, 2), 20.0, np.float32)), filt=dev(kf), smooth=dev(kf))
+    log = dict(count=dev(np.full(1, lag, np.int64)), log_valid=dev(np.ones((1, lag), np.int32)), log_id=dev(np.zeros(1, np.int32)),
+               log_len=dev(np.zeros(1, np.int32)), log_box=dev(np.zeros(1, np.float32)))   # (only count and log_valid are read)
+    truth = dict(truth_box=dev(tbox), truth_present=dev(np.ones((lag, 1, G), np.int32)), truth_valid=dev(np.ones((lag, 1), np.int32)))
+    out = {k: torch.zeros(s, dtype=getattr(torch, _capi.field_dtype("SqairTrackLogScore", k)), device="cuda")
+           for k, s in _capi.tracklog_score_shapes(lag, 1, G).items()}
+    c_log = _capi.SqairLaneTrackLog(L=lag, **{k: t.data_ptr() for k, t in log.items()})
+    c_tab = _capi.SqairTrackLogOut(**{k: t.data_ptr() for k, t in table.items()})
+    c_truth = _capi.SqairTrackLogTruth(G=G, **{k: t.data_ptr() for k, t in truth.items()})
+    c_score = _capi.SqairTrackLogScore(iou_min=0.5, **{k: t.data_ptr() for k, t in out.items()})
+    res = dict(lag=lag, C=C, G=G, lanes=1)
+    for match, name in enumerate(("greedy", "optimal")):
+        ms = []
+        for i in range(reps + 1):   # (the first launch loads the code object: not counted)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            rc = lib.sqair_lane_tracklog_score(h, C_.byref(c_log), C_.byref(c_tab), C_.byref(c_truth), C_.byref(c_score), lag, C, 1, match,
+                                               C_.c_void_p(torch.cuda.current_stream().cuda_stream))
+            assert rc == 0, lib.sqair_last_error(h)
+            b.record()
+            torch.cuda.synchronize()
+            if i:
+                ms.append(a.elapsed_time(b))
+        counts = dict(zip(_capi.TRACKLOG_SCORE_COUNTS, out["counts"][0, 3].tolist()))
+        res[name] = dict(ms=_spread(ms), smooth_filled={k: counts[k] for k in ("frames", "truth", "tp", "fn", "fp", "idtp")})
+    return res
+
+
+def time_tracklog_score(B, K, N, steps, warmup, L=64, G=2, rounds=10, hw=(50, 50)):
+    smc = dict(resample="systematic", ess_frac=0.5)
+    idt = dict(estimate=True, identity=True, tracklog=L, tracklog_tracks=16, **smc)
+    legs = dict(log=idt, log_truth=dict(idt, tracklog_truth=G))
+    rng = np.random.default_rng(3)
+    box = np.concatenate([rng.uniform(-5, 35, (1, B, G, 2)), rng.uniform(8, 28, (1, B, G, 2))], -1).astype(np.float32)
+    truth = dict(box=torch.as_tensor(box).cuda(), present=torch.ones((1, B, G), dtype=torch.int32).cuda(),
+                 valid=torch.ones((1, B), dtype=torch.int32).cuda())
+    streams, res, med, thr = alternating_streams(legs, B, K, N, steps, warmup, rounds, hw, dict(log_truth=dict(truth=truth)))
+    res.update(L=L, tracks=16, G=G, ring_bytes=int(sum(t.numel() * t.element_size() for t in streams["log_truth"]._truth_ring.values())))
+    res["us_ring_copies_per_step"] = dict(latency=1e3 * (med["log_truth"] - med["log"]), back_to_back=1e3 * (thr["log_truth"] - thr["log"]))
+    st = streams["log_truth"]
+    assert int(st._tracklog["count"].min()) >= L and st.lane.ring_frames >= L, "the log is not full"
+    res["ms"], res["score_minus_plain_us"] = {}, {}
+    for lag in (10, L):
+        calls = dict(track_log=lambda: st.track_log(lag=lag),
+                     score_greedy=lambda: st.track_log(lag=lag, score=True, score_match="greedy"),
+                     score_optimal=lambda: st.track_log(lag=lag, score=True, score_match="optimal"))
+        ms = _timed_calls(st.core, calls)
+        key = "lag{}".format(lag)
+        res["ms"][key] = {n: _spread(v) for n, v in ms.items()}
+        res["score_minus_plain_us"][key] = {n: 1e3 * (float(np.median(ms[n])) - float(np.median(ms["track_log"])))
+                                            for n in ("score_greedy", "score_optimal")}
+        sc = st.track_log(lag=lag, score=True)["score"]["smooth_filled"]
+        res["smooth_filled_" + key] = {n: (int(v.sum()) if torch.is_tensor(v) and v.dim() == 1 and not v.is_floating_point() else v)
+                                       for n, v in sc.items() if n in ("frames", "truth", "tp", "fn", "fp", "gap_tp", "gap_fp", "mota", "idf1")}
+    for st in streams.values():
+        st.close()
+    res["scorer_at_the_limits"] = scorer_at_the_limits()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=500)
@@ -577,10 +686,13 @@ def main():
     ap.add_argument("--hota", action="store_true", help="score and score + HOTA, each with and without SMC, alternating; hota_score() apart (profiles/stream_hota_time.json)")
     ap.add_argument("--motion", action="store_true", help="identity and identity + motion, greedy and optimal, with SMC and the estimate, alternating (profiles/stream_motion_time.json)")
     ap.add_argument("--tracklog", action="store_true", help="identity and motion with and without the track log, with SMC and the estimate, alternating; track_log() against tracks() apart (profiles/stream_tracklog_time.json)")
+    ap.add_argument("--tracklog-score", action="store_true", help="the track log with and without its truth ring, alternating; track_log(score=True) against track_log(); the scorer at its limits (profiles/tracklog_score_time.json)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     ov, _, _, _ = config_inputs(2)
-    if args.tracklog:
+    if args.tracklog_score:
+        shapes = [dict(name="cfg2_batch_tracklog_score", **time_tracklog_score(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
+    elif args.tracklog:
         shapes = [dict(name="cfg2_batch_tracklog", **time_tracklog(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
     elif args.motion:
         shapes = [dict(name="cfg2_batch_motion", **time_motion(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
