@@ -1109,6 +1109,55 @@ int sqair_lane_tracklog_score(SqairHandle* h, const SqairLaneTrackLog* log, cons
                               const SqairTrackLogTruth* truth, const SqairTrackLogScore* score,
                               int lag, int C, int B, int match /* 0 greedy, 1 optimal */, void* stream);
 
+/* ---- motion calibration: fit q and r to the track log, without truth (the track log fit paragraph) --------------------------------
+ * The motion filter, the solve and the scorer all stand on hand-set scalars q and r; the scorer says whether they fit only where
+ * there is truth.  The filter's own innovations say it without: for a (q, r) the innovations y and their variances S of a track
+ * define the likelihood -log p = 1/2 sum (ln 2 pi S + y y / S), its minimum over a grid of candidates is the maximum-likelihood fit,
+ * and mean y y / S (the NIS) is 1 per axis for an honest filter.  sqair_lane_tracklog_fit forms the sums of that likelihood for every
+ * candidate of a Q x R grid.  It is a stand-alone, capturable call, one launch of k_lane_tracklog_fit: it registers nothing, no pass
+ * runs it, and it writes only its outputs -- counts, sums and innov; nothing of them is read.  The handle gives the error text only.
+ * Inputs.  `table` and `work` (both read-only) are what sqair_lane_tracklog_smooth wrote for the same lag, C, N and B: of the table
+ * only frame_index and state are read, of `work` the slot of every (frame, column); of `log`, L and log_box.  A frame's record is
+ * frame_index mod L, as in the scorer.  No pass may have run between the solve and the fit: a pass moves the ring under the table.
+ * The walk, per lane b, per candidate (iq, ir) with (q, r) = (fit->q[iq], fit->r[ir]), per column c and per axis a in {y, x}, frames in
+ * ascending order, st = state[f,b,c]:
+ * 1. st 0 or 3: nothing happens.
+ * 2. The first st == 1: the state starts as a newborn's, (p, v, Ppp, Ppv, Pvv) = (z, 0, r, 0, v0_var), with z = fmaf(0.5, size,
+ *    origin) of the slot's box words, exactly as in the solve's point 3; i = 0, gap = false.
+ * 3. st == 2: P; gap = true.
+ * 4. A later st == 1: S = P's return; y = z - p; nis = (y * y) / S in fp32; i += 1.  If i > burn, the term COUNTS when S > 0 and nis
+ *    is finite: n += 1, nis_sum += (double)nis, lns_sum += log((double)S) -- the logarithm taken in fp64, so that no fp32 logf enters
+ *    the definition --, and the same three into n_gap, gap_nis_sum, gap_lns_sum when gap is set; if i > burn and the term does not
+ *    count, skipped += 1.  Then U; gap = false.  innov[f,b,c,a,:] = (y, S) for candidate (0, 0) at these frames, whatever burn is; 0
+ *    everywhere else.
+ * 5. The filter is sq_kf_predict and sq_kf_update, the motion paragraph's P and U: called, not restated.
+ * Order of the sums.  A (candidate, column, axis) adds its terms in frame order in fp64; one thread then adds a candidate's 2 C
+ * partial sums in (c, a) index order.  No float atomics: a replayed graph gives the bits of an eager call.  Every word of every
+ * output is written.  counts [B,Q,R,3] int64 = n, n_gap, skipped; sums [B,Q,R,4] fp64 = nis_sum, lns_sum, gap_nis_sum, gap_lns_sum.
+ * The candidate's negative log-likelihood is 1/2 (n ln 2 pi + lns_sum + nis_sum), formed by the caller.
+ * Conditioning.  The fit conditions on the associations the log recorded: it does not re-link objects under a candidate's scalars.
+ * Refused (return -1, text in sqair_last_error, before any HIP call): a NULL log, table, work or fit; what sqair_set_tracklog refuses
+ * for log; a NULL frame_index or state of the table; a NULL counts or sums; lag outside 1..L; C outside 1..64; N outside 1..16; B < 1;
+ * Q or R outside 1..16; burn < 0; v0_var or any read q[i] / r[i] not finite and positive.
+ * Out of scope: fitting v0_var or gate; gradient or EM refinement inside a grid cell (call again with a finer grid); per-track or
+ * per-lane scalars inside the identity kernel; re-linking under the candidate scalars; the particles' spread as r; filtering h, w;
+ * sums that persist over windows; training passes. */
+#define SQAIR_TRACKLOG_FIT_MAX_GRID 16
+#define SQAIR_TRACKLOG_FIT_COUNTS 3      /* n, n_gap, skipped */
+#define SQAIR_TRACKLOG_FIT_SUMS 4        /* nis_sum, lns_sum, gap_nis_sum, gap_lns_sum */
+typedef struct SqairTrackLogFit {
+  int32_t Q, R;          /* grid sizes, 1..16 each */
+  int32_t burn;          /* >= 0: the first `burn` innovations of a column are not counted */
+  float v0_var;          /* > 0, as in the motion paragraph */
+  float q[16], r[16];    /* the first Q / R are read; each finite and > 0.  (The header parser takes a literal length only.) */
+  int64_t* counts;       /* [B,Q,R,3] required */
+  double*  sums;         /* [B,Q,R,4] required */
+  float*   innov;        /* [lag,B,C,2,2] optional: (y, S) of candidate (0, 0) */
+} SqairTrackLogFit;
+int sqair_lane_tracklog_fit(SqairHandle* h, const SqairLaneTrackLog* log, const SqairTrackLogOut* table /* read-only */,
+                            const void* work /* read-only: as the solve left it */, const SqairTrackLogFit* fit,
+                            int lag, int C, int N, int B, void* stream);
+
 /* ---- IDF1 scoring: does an identity stay on an object over its life -- global identity assignment, solved on the device ---------
  * The score's idsw counts the moments an identity changes on a greedy per-frame match; it cannot say for how long the wrong id then
  * stays, and gives no credit for an object re-identified under its old id.  The identity measures of Ristani et al. (IDF1, IDP, IDR)

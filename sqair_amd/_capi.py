@@ -224,6 +224,30 @@ def tracklog_score_shapes(lag, B, G):
                 match_iou=(V, lag, B, G))
 
 
+# motion calibration (include/sqair_hip.h: sqair_lane_tracklog_fit): what the fit reads of the solve's outputs, its required outputs,
+# the longest grid, the columns of ``counts`` [B, Q, R, .] and ``sums`` [B, Q, R, .]
+TRACKLOG_FIT_TABLE = ("frame_index", "state")
+TRACKLOG_FIT_REQUIRED = ("counts", "sums")
+TRACKLOG_FIT_MAX_GRID = _K["SQAIR_TRACKLOG_FIT_MAX_GRID"]
+TRACKLOG_FIT_COUNTS = _counted("SQAIR_TRACKLOG_FIT_COUNTS", "n", "n_gap", "skipped")
+TRACKLOG_FIT_SUMS = _counted("SQAIR_TRACKLOG_FIT_SUMS", "nis_sum", "lns_sum", "gap_nis_sum", "gap_lns_sum")
+
+
+def tracklog_fit_shapes(lag, B, C, Q, R):
+    """The shapes of sqair_lane_tracklog_fit's outputs, required and optional, for a Q x R grid of candidates."""
+    return dict(counts=(B, Q, R, len(TRACKLOG_FIT_COUNTS)), sums=(B, Q, R, len(TRACKLOG_FIT_SUMS)), innov=(lag, B, C, 2, 2))
+
+
+def tracklog_fit_struct(q_grid, r_grid, v0_var, burn, **pointers):
+    """A SqairTrackLogFit for the grids given as sequences of floats; ``pointers``: counts, sums and optionally innov (addresses)."""
+    fit = _STRUCTS["SqairTrackLogFit"](Q=len(q_grid), R=len(r_grid), burn=burn, v0_var=v0_var, **pointers)
+    for i, v in enumerate(q_grid):
+        fit.q[i] = v
+    for i, v in enumerate(r_grid):
+        fit.r[i] = v
+    return fit
+
+
 # trajectory scoring (include/sqair_hip.h: sqair_lane_traj_score): the three structs' pointer fields in declaration order -- of
 # SqairTrajScore the accumulators, then the per-call outputs and the int32 ones among them --, the columns of ``counts`` [F, B, .],
 # ``sums`` [F, B, .] and ``lane_counts`` [B, .]

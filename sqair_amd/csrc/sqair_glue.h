@@ -559,6 +559,16 @@ struct LaneTrackLogScoreArgs {
   int match;                           // 0 = sq_assign_keep_greedy, 1 = sq_assign_keep_optimal (a wave-uniform branch of the one kernel)
 };
 int sq_launch_lane_tracklog_score(const LaneTrackLogScoreArgs& a, hipStream_t s);
+// Motion calibration (sqair_lane_tracklog_fit; include/sqair_hip.h states the semantics): k_lane_tracklog_fit, workgroup (b, iq) of
+// 256 threads, one thread per (ir, column, axis) of a round of candidates, walking the window's frames in order.
+struct LaneTrackLogFitArgs {
+  SqairLaneTrackLog log;               // L and log_box are read
+  SqairTrackLogOut tab;                // the solve's outputs, read-only here: frame_index and state are read
+  const int32_t* work;                 // [B][lag][C], the solve's slots, read-only here
+  SqairTrackLogFit fit;                // the grid by value, the scalars and the outputs
+  int lag, C, N, B;
+};
+int sq_launch_lane_tracklog_fit(const LaneTrackLogFitArgs& a, hipStream_t s);
 
 // Object forecasts (sqair_forecast_fan; include/sqair_hip.h states the semantics).  Fan-out: rollout row q = r * S + s.
 // k_forecast_fan_src expands the source map, src_fan[q] = src[q / S] (NULL: q / S), an index outside [0, R) of the blob -> -1.

@@ -1772,3 +1772,122 @@ int sq_launch_lane_tracklog_score(const LaneTrackLogScoreArgs& a, hipStream_t s)
   SQ_LAUNCH(k_lane_tracklog_score, dim3(a.B), dim3(256), 0, s, a);
   return 0;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Motion calibration (sqair_lane_tracklog_fit; LaneTrackLogFitArgs in sqair_glue.h; the semantics: include/sqair_hip.h, the track log
+// fit paragraph, points 1-5)
+// ------------------------------------------------------------------------------------------------
+// k_lane_tracklog_fit: workgroup = (lane b, iq); its R candidates go in rounds of per = 256 / (2 C) at a time, thread = (candidate of
+// the round, column, axis): per * 2 C <= 256 threads walk, the rest idle (2 C need not divide 256).  The serial chain is lag steps a
+// thread; what a step reads -- the state word of (frame, column) and z of (frame, column, axis) -- does not depend on the candidate,
+// so the workgroup stages it in LDS for SQ_FIT_FRAMES frames at a time, all 256 threads, one (frame, column) each: the state, the
+// slot from `work`, the record from frame_index, the box words, z for both axes.  The walk then reads LDS only: threads of one
+// candidate read consecutive words, threads of different candidates the same word.  One code path for every lag and C.  A thread
+// keeps its five state words, three counters and four fp64 sums in registers, adding in frame order; after the window they go to
+// LDS, and thread i < per adds candidate i's 2 C partial sums in (c, a) index order and writes the candidate's words.  Every barrier
+// stands under conditions on kernel arguments alone.  LDS: 16 KiB z, 8 KiB states, 8 KiB + 3 KiB partial sums.
+// Indices: state and work inside [lag][C] of lane b; a slot is used only inside 0..N-1 and with a frame_index >= 0, the record is
+// formed inside 0..L-1 (a state 1 without either is no table of the solve's and is walked as state 0); iq < Q and ir < R <= 16.
+constexpr int SQ_FIT_FRAMES = 32;
+__global__ __launch_bounds__(256) void k_lane_tracklog_fit(const LaneTrackLogFitArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ float s_z[SQ_FIT_FRAMES * 2 * SQ_TRACKLOG_MAXC];
+  __shared__ int s_st[SQ_FIT_FRAMES * SQ_TRACKLOG_MAXC];
+  __shared__ double s_sum[256 * SQAIR_TRACKLOG_FIT_SUMS];
+  __shared__ int s_cnt[256 * SQAIR_TRACKLOG_FIT_COUNTS];
+  const SqairTrackLogOut& t = a.tab;
+  const SqairTrackLogFit& o = a.fit;
+  const int b = blockIdx.x, iq = blockIdx.y, tid = threadIdx.x;
+  const int lag = a.lag, C = a.C, N = a.N, B = a.B, LR = a.log.L, R = o.R, C2 = 2 * C, burn = o.burn;
+  const int per = 256 / C2;
+  const float q = o.q[iq], v0_var = o.v0_var;
+  const int32_t* work = a.work + (size_t)b * lag * C;
+  const float* lbox = a.log.log_box + (size_t)b * LR * N * 4;
+  const int lr = tid / C2, ca = tid - lr * C2, c = ca >> 1;
+  for (int r0 = 0; r0 < R; r0 += per) {
+    const int ir = r0 + lr;
+    const bool mine = lr < per && ir < R;
+    const float r = o.r[mine ? ir : 0];
+    float2* innov = mine && iq == 0 && ir == 0 && o.innov ? (float2*)o.innov : nullptr;   // candidate (0, 0) writes every word of it
+    float k[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    bool started = false, gap = false;
+    int i = 0, n = 0, n_gap = 0, skipped = 0;
+    double nis_sum = 0.0, lns_sum = 0.0, gnis_sum = 0.0, glns_sum = 0.0;
+    for (int f0 = 0; f0 < lag; f0 += SQ_FIT_FRAMES) {
+      const int nf = min(SQ_FIT_FRAMES, lag - f0);
+      __syncthreads();   // (the last block's walkers are done with the staged words)
+      for (int e = tid; e < nf * C; e += 256) {
+        const int fl = e / C, cc = e - fl * C, f = f0 + fl;
+        const size_t fb = (size_t)f * B + b;
+        int st = t.state[fb * C + cc];
+        float zy = 0.0f, zx = 0.0f;
+        if (st == 1) {
+          const long long fi = t.frame_index[fb];
+          const int j = work[f * C + cc];
+          if (fi >= 0 && j >= 0 && j < N) {
+            const float* p = lbox + ((size_t)(fi % LR) * N + j) * 4;
+            zy = fmaf(0.5f, p[2], p[0]);
+            zx = fmaf(0.5f, p[3], p[1]);
+          } else {
+            st = 0;
+          }
+        }
+        s_st[e] = st;
+        s_z[e * 2] = zy;
+        s_z[e * 2 + 1] = zx;
+      }
+      __syncthreads();
+      if (!mine) continue;   // (the barriers are the loop's, above)
+      for (int fl = 0; fl < nf; ++fl) {
+        const int st = s_st[fl * C + c];
+        const float z = s_z[fl * C2 + ca];
+        float y = 0.0f, S = 0.0f;
+        if (st == 1 && !started) {
+          k[0] = z; k[1] = 0.0f; k[2] = r; k[3] = 0.0f; k[4] = v0_var;
+          started = true; gap = false; i = 0;
+        } else if (st == 1) {
+          S = sq_kf_predict(k, q, r);
+          y = z - k[0];
+          const float nis = (y * y) / S;
+          ++i;
+          if (i > burn) {
+            if (S > 0.0f && isfinite(nis)) {
+              const double dn = (double)nis, dl = log((double)S);
+              ++n; nis_sum += dn; lns_sum += dl;
+              if (gap) { ++n_gap; gnis_sum += dn; glns_sum += dl; }
+            } else {
+              ++skipped;
+            }
+          }
+          sq_kf_update(k, S, z);
+          gap = false;
+        } else if (st == 2 && started) {
+          sq_kf_predict(k, q, r);
+          gap = true;
+        }
+        if (innov) innov[(((size_t)(f0 + fl) * B + b) * C + c) * 2 + (ca & 1)] = make_float2(y, S);
+      }
+    }
+    s_sum[tid * 4] = nis_sum; s_sum[tid * 4 + 1] = lns_sum; s_sum[tid * 4 + 2] = gnis_sum; s_sum[tid * 4 + 3] = glns_sum;
+    s_cnt[tid * 3] = n; s_cnt[tid * 3 + 1] = n_gap; s_cnt[tid * 3 + 2] = skipped;
+    __syncthreads();
+    if (tid < per && r0 + tid < R) {
+      long long cn = 0, cg = 0, cs = 0;
+      double d0 = 0.0, d1 = 0.0, d2 = 0.0, d3 = 0.0;
+      for (int j = tid * C2; j < (tid + 1) * C2; ++j) {
+        cn += s_cnt[j * 3]; cg += s_cnt[j * 3 + 1]; cs += s_cnt[j * 3 + 2];
+        d0 += s_sum[j * 4]; d1 += s_sum[j * 4 + 1]; d2 += s_sum[j * 4 + 2]; d3 += s_sum[j * 4 + 3];
+      }
+      const size_t e = ((size_t)b * o.Q + iq) * R + r0 + tid;
+      int64_t* cw = o.counts + e * SQAIR_TRACKLOG_FIT_COUNTS;
+      cw[0] = cn; cw[1] = cg; cw[2] = cs;
+      double* dw = o.sums + e * SQAIR_TRACKLOG_FIT_SUMS;
+      dw[0] = d0; dw[1] = d1; dw[2] = d2; dw[3] = d3;
+    }
+    __syncthreads();   // (the partial sums are read before the next round's walkers can write theirs)
+  }
+}
+int sq_launch_lane_tracklog_fit(const LaneTrackLogFitArgs& a, hipStream_t s) {
+  SQ_LAUNCH(k_lane_tracklog_fit, dim3(a.B, a.fit.Q), dim3(256), 0, s, a);
+  return 0;
+}

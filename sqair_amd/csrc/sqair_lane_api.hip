@@ -3,7 +3,7 @@
 // sqair_set_estimate / _layers / _score / _identity / _motion / _tracklog / _score_ids / _idf / _hota), the estimate's refusal of a pass, ONE builder per kernel's arguments -- called by the
 // pass and by the kernel-level entry point alike --, the pass's launch sequence (sq_launch_lane_answers, called by sq_forward_impl
 // with the block sq_resolve_pass resolved) and the stand-alone entry points (sqair_lane_*_test, sqair_lane_traj_score,
-// sqair_lane_idf_solve, sqair_lane_hota_solve, sqair_lane_tracklog_smooth, sqair_lane_tracklog_score).  Host code
+// sqair_lane_idf_solve, sqair_lane_hota_solve, sqair_lane_tracklog_smooth, sqair_lane_tracklog_score, sqair_lane_tracklog_fit).  Host code
 // only: the kernels and their launchers live in sqair_lane.hip, which work here does not move.  A further follower is one member
 // of SqLaneSet, its registration and builder here, and one line of sq_launch_lane_answers.
 #include "sqair_internal.h"
@@ -572,6 +572,36 @@ extern "C" int sqair_lane_tracklog_score(SqairHandle* h, const SqairLaneTrackLog
   LaneTrackLogScoreArgs a; memset(&a, 0, sizeof(a));
   a.log = *log; a.tab = *table; a.tr = *truth; a.sc = *score; a.lag = lag; a.C = C; a.B = B; a.match = match;
   sq_launch_lane_tracklog_score(a, (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+// motion calibration (include/sqair_hip.h: sqair_lane_tracklog_fit): a stand-alone call on the table and the slots the solve wrote --
+// or on a test's tensors --, nothing registered on the handle, which gives the error text
+extern "C" int sqair_lane_tracklog_fit(SqairHandle* h, const SqairLaneTrackLog* log, const SqairTrackLogOut* table, const void* work,
+                                       const SqairTrackLogFit* fit, int lag, int C, int N, int B, void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_lane_tracklog_fit: ";
+  if (!log || !table || !work || !fit) return sq_no(h, who + "log, table, work and fit must not be NULL");
+  if (B < 1) return sq_no(h, who + "B = " + std::to_string(B) + " must be >= 1");
+  if (sq_tracklog_fields(h, who, *log) != 0) return -1;
+  if (const char* why = sq_tracklog_shape_refusal(lag, C, N))
+    return sq_no(h, who + why + " (lag = " + std::to_string(lag) + ", L = " + std::to_string(log->L) + ", C = " + std::to_string(C) +
+                        ", N = " + std::to_string(N) + ")");
+  if (lag > log->L) return sq_no(h, who + "lag = " + std::to_string(lag) + " must lie in 1..L = " + std::to_string(log->L));
+  if (fit->Q < 1 || fit->Q > SQAIR_TRACKLOG_FIT_MAX_GRID || fit->R < 1 || fit->R > SQAIR_TRACKLOG_FIT_MAX_GRID)
+    return sq_no(h, who + "Q = " + std::to_string(fit->Q) + " and R = " + std::to_string(fit->R) + " must lie in 1..16");
+  if (fit->burn < 0) return sq_no(h, who + "burn = " + std::to_string(fit->burn) + " must be >= 0");
+  auto positive = [](float v) { return v > 0.0f && std::isfinite(v); };   // (NaN fails)
+  if (!positive(fit->v0_var)) return sq_no(h, who + "v0_var must be finite and > 0");
+  for (int i = 0; i < fit->Q; ++i)
+    if (!positive(fit->q[i])) return sq_no(h, who + "q[" + std::to_string(i) + "] must be finite and > 0");
+  for (int i = 0; i < fit->R; ++i)
+    if (!positive(fit->r[i])) return sq_no(h, who + "r[" + std::to_string(i) + "] must be finite and > 0");
+  if (!table->frame_index || !table->state) return sq_no(h, who + "the table's frame_index and state must not be NULL");
+  if (!fit->counts || !fit->sums) return sq_no(h, who + "counts and sums must not be NULL");
+  LaneTrackLogFitArgs a; memset(&a, 0, sizeof(a));
+  a.log = *log; a.tab = *table; a.work = (const int32_t*)work; a.fit = *fit; a.lag = lag; a.C = C; a.N = N; a.B = B;
+  sq_launch_lane_tracklog_fit(a, (hipStream_t)stream);
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -67,6 +67,12 @@ filled gaps alone: whether gap filling turned misses into hits or into false pos
 the truth, whether sigma is honest.  Window frame f of every lane is stream frame (frames stepped - lag + f), whatever the lane's
 own ``count`` says after a ``reset(lanes)``, so one gather of the ring serves all lanes; ``reset(lanes)`` leaves the ring alone.
 
+``track_log_fit()`` (a stream with ``tracklog=L``; no truth needed) picks the filter's ``q`` and ``r`` from the log itself: one more
+launch behind the solve (sqair_lane_tracklog_fit) walks every track of the window under every (q, r) of a grid and sums the filter's
+normalised innovations and log-variances; ``track_log_fit(got, q_grid, r_grid)`` here forms the negative log-likelihood of every
+node, its minimum -- the maximum-likelihood fit on the grid -- and ``mean_nis``, 1 for an honest filter.  ``set_motion(q, r)`` applies
+a fit: the defaults of ``track_log()`` and ``track_log_fit()`` follow, and on a stream with ``motion=True`` the following steps' filter.
+
 ``score_idf=True`` (with ``score=True``): the score's idsw counts the moments an identity changes, not for how long the wrong id then
 stays.  The stream then also keeps, per lane and on the device, how many frames of the open clip every truth overlapped (IoU >=
 ``score_iou``) every predicted id -- the id words the score reads: ``obj_id``, or ``lane_id`` with ``score_ids="lane"`` --, up to
@@ -245,6 +251,50 @@ def track_log_score(got):
         r["gap_nees"] = _ratio(tot["gap_nees_sum"], tot["gap_nees_n"])
         r["gap_precision"] = _ratio(tot["gap_tp"], tot["gap_tp"] + tot["gap_fp"])
         res[name] = r
+    return res
+
+
+def track_log_fit(got, q_grid, r_grid):
+    """``SqairStream.track_log_fit``'s result, formed on the host from the fit's outputs read back (include/sqair_hip.h:
+    sqair_lane_tracklog_fit; ``got``: host tensors or arrays ``counts`` [B, Q, R, 3], ``sums`` [B, Q, R, 4] and optionally ``innov``):
+    ``q_grid`` [Q] and ``r_grid`` [R] float64; pooled over the lanes, per grid node [Q, R]: ``n``, ``n_gap``, ``skipped`` int64, ``nll`` =
+    1/2 (n ln 2 pi + lns_sum + nis_sum) (nats), ``mean_nis`` = nis_sum / n (1 for an honest filter) and ``gap_mean_nis`` =
+    gap_nis_sum / n_gap, the same over the first innovations behind a gap, NaN where the denominator is 0; per lane [B, Q, R] the
+    same under ``lane_n``, ``lane_n_gap``, ``lane_skipped``, ``lane_nll``, ``lane_mean_nis``, ``lane_gap_mean_nis``.  ``node`` = (iq, ir),
+    the first node in index order of minimal pooled ``nll``, ``q`` and ``r`` its values: the maximum-likelihood fit on the grid;
+    ``at_edge``: the node lies on the grid's border along an axis of more than one value -- the minimum may lie outside, fit again
+    with a grid moved there.  ``lane_q``, ``lane_r`` [B]: the same per lane.  Without a counted term (pooled, or of a lane) there is
+    no fit: ``node`` is None, the values NaN, ``at_edge`` False.  Nodes are compared as they stand: where ``skipped`` differs between
+    nodes, so does the number of terms.  ``innov`` [lag, B, C, 2, 2], (y, S) of node (0, 0) per (frame, lane, column, axis), if
+    it was asked for."""
+    counts = np.asarray(torch.as_tensor(got["counts"]).numpy(), np.int64)
+    sums = np.asarray(torch.as_tensor(got["sums"]).numpy(), np.float64)
+    qg, rg = np.asarray(q_grid, np.float64).reshape(-1), np.asarray(r_grid, np.float64).reshape(-1)
+    if counts.shape[1:3] != (len(qg), len(rg)) or sums.shape[:3] != counts.shape[:3]:
+        raise ValueError("lane.track_log_fit: counts {} and sums {} given for a {} x {} grid".format(
+            tuple(counts.shape), tuple(sums.shape), len(qg), len(rg)))
+
+    def figures(c, s):
+        n, n_gap = c[..., 0], c[..., 1]
+        div = lambda a, b: np.where(b != 0, a / np.where(b != 0, b, 1), np.nan)
+        return dict(n=n, n_gap=n_gap, skipped=c[..., 2], nll=0.5 * (n * np.log(2.0 * np.pi) + s[..., 1] + s[..., 0]),
+                    mean_nis=div(s[..., 0], n), gap_mean_nis=div(s[..., 2], n_gap))
+
+    def best(f):
+        node = np.unravel_index(int(np.argmin(f["nll"])), f["nll"].shape)   # (argmin: the first of equal minima in index order)
+        return tuple(int(i) for i in node) if f["n"][node] > 0 else None
+    pooled, lanes = figures(counts.sum(0), sums.sum(0)), figures(counts, sums)
+    res = dict(q_grid=torch.from_numpy(qg.copy()), r_grid=torch.from_numpy(rg.copy()))
+    res.update({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in pooled.items()})
+    res.update({"lane_" + k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in lanes.items()})
+    node = res["node"] = best(pooled)
+    res["q"], res["r"] = (float(qg[node[0]]), float(rg[node[1]])) if node else (float("nan"), float("nan"))
+    res["at_edge"] = bool(node) and any(m > 1 and i in (0, m - 1) for i, m in zip(node, (len(qg), len(rg))))
+    lane_nodes = [best({k: v[b] for k, v in lanes.items()}) for b in range(counts.shape[0])]
+    res["lane_q"] = torch.tensor([qg[nd[0]] if nd else float("nan") for nd in lane_nodes], dtype=torch.float64)
+    res["lane_r"] = torch.tensor([rg[nd[1]] if nd else float("nan") for nd in lane_nodes], dtype=torch.float64)
+    if got.get("innov") is not None:
+        res["innov"] = torch.as_tensor(got["innov"])
     return res
 
 
@@ -635,18 +685,39 @@ class LaneAnswers(object):
         res["exact"] = int(res["dropped_frames"].sum()) == 0 and int(res["overflow_ids"].sum()) == 0
         return res
 
-    def track_log(self, lag=None, q=None, r=None, v0=None, score=False, score_iou=0.5, score_match="greedy"):
+    def _check_log_call(self, fn, lag, q, r, v0):
+        """What ``track_log`` and ``track_log_fit`` check alike: (lag, the solve's scalars {q, r, v0}, None = the stream's)."""
         if not self.tracklog:
-            raise ValueError("SqairStream.track_log: the stream keeps no track log (SqairStream(..., estimate=True, identity=True, "
-                             "tracklog=L))")
+            raise ValueError("SqairStream.{}: the stream keeps no track log (SqairStream(..., estimate=True, identity=True, "
+                             "tracklog=L))".format(fn))
         lag = self.log_L if lag is None else lag
         if not is_int_in(lag, 1, self.log_L):
-            raise ValueError("SqairStream.track_log: lag must be an integer in [1, tracklog = {}]".format(self.log_L))
+            raise ValueError("SqairStream.{}: lag must be an integer in [1, tracklog = {}]".format(fn, self.log_L))
         m = self.motion_scalars
         scal = dict(q=m["q"] if q is None else float(q), r=m["r"] if r is None else float(r), v0=m["v0_var"] if v0 is None else float(v0))
         for name, v in scal.items():
             if not 0.0 < v < float("inf"):   # (NaN fails too)
-                raise ValueError("SqairStream.track_log: {} must be finite and > 0".format(name))
+                raise ValueError("SqairStream.{}: {} must be finite and > 0".format(fn, name))
+        return lag, scal
+
+    def _solve_log(self, lag, scal):
+        """The solve's launch on the current stream (include/sqair_hip.h: sqair_lane_tracklog_smooth) into the outputs and scratch of
+        ``lag`` -- kept for the LAST lag asked for, with what the scorer and the fit add to them; returns them."""
+        core, B, Cn = self.core, self.B, self.log_C
+        if self._log_out.get("lag") != lag:
+            out = zeros_of("SqairTrackLogOut", _capi.tracklog_out_shapes(lag, B, Cn), core.device)
+            nbytes = B * core.lib.sqair_lane_tracklog_work_bytes(lag, Cn, core.N)
+            self._log_out = dict(lag=lag, out=out, work=torch.zeros(nbytes // 4, dtype=torch.int32, device=core.device),
+                                 c=_capi.SqairTrackLogOut(**{n: t.data_ptr() for n, t in out.items()}))
+            torch.cuda.current_stream(core.device).synchronize()
+        o = self._log_out
+        core.check(core.lib.sqair_lane_tracklog_smooth(core.handle, C.byref(self._log_c), lag, Cn, core.N, B, scal["q"],
+                                                       scal["r"], scal["v0"], C.byref(o["c"]), o["work"].data_ptr(),
+                                                       core._stream()), "sqair_lane_tracklog_smooth")
+        return o
+
+    def track_log(self, lag=None, q=None, r=None, v0=None, score=False, score_iou=0.5, score_match="greedy"):
+        lag, scal = self._check_log_call("track_log", lag, q, r, v0)
         if score:
             if not self.log_G:
                 raise ValueError("SqairStream.track_log: score=True is for a stream that keeps the log's truth (SqairStream(..., "
@@ -655,20 +726,11 @@ class LaneAnswers(object):
             check_unit("SqairStream.track_log: ", "score_iou", score_iou)
             if score_match not in MATCH_MODES:
                 raise ValueError("SqairStream.track_log: score_match must be 'greedy' or 'optimal'")
-        core, B, Cn = self.core, self.B, self.log_C
+        core = self.core
         with torch.cuda.device(core.device):
             core._join_in()
             with core.on_stream():
-                if self._log_out.get("lag") != lag:
-                    out = zeros_of("SqairTrackLogOut", _capi.tracklog_out_shapes(lag, B, Cn), core.device)
-                    nbytes = B * core.lib.sqair_lane_tracklog_work_bytes(lag, Cn, core.N)
-                    self._log_out = dict(lag=lag, out=out, work=torch.zeros(nbytes // 4, dtype=torch.int32, device=core.device),
-                                         c=_capi.SqairTrackLogOut(**{n: t.data_ptr() for n, t in out.items()}))
-                    torch.cuda.current_stream(core.device).synchronize()
-                o = self._log_out
-                core.check(core.lib.sqair_lane_tracklog_smooth(core.handle, C.byref(self._log_c), lag, Cn, core.N, B, scal["q"],
-                                                               scal["r"], scal["v0"], C.byref(o["c"]), o["work"].data_ptr(),
-                                                               core._stream()), "sqair_lane_tracklog_smooth")
+                o = self._solve_log(lag, scal)
                 got = {n: t.clone() for n, t in o["out"].items()}
                 scored = self._score_log(o, lag, score_iou, MATCH_MODES.index(score_match)) if score else None
             core._join_out()
@@ -693,6 +755,68 @@ class LaneAnswers(object):
         core.check(core.lib.sqair_lane_tracklog_score(core.handle, C.byref(self._log_c), C.byref(c_tab), C.byref(c_truth), C.byref(c_score),
                                                       lag, self.log_C, B, match, core._stream()), "sqair_lane_tracklog_score")
         return {k: t.clone() for k, t in o["score"].items()}
+
+    def _check_grid(self, name, grid, centre):
+        """A grid of ``track_log_fit`` as a list of floats (None: ``centre`` * 4^k, k = -4..3, so that ``centre`` is node 4)."""
+        if grid is None:
+            grid = [centre * 4.0 ** k for k in range(-4, 4)]
+        try:
+            grid = [float(v) for v in (grid.tolist() if hasattr(grid, "tolist") else grid)]
+        except (TypeError, ValueError):
+            grid = []
+        if not 1 <= len(grid) <= _capi.TRACKLOG_FIT_MAX_GRID:
+            raise ValueError("SqairStream.track_log_fit: {} must hold 1 to {} values".format(name, _capi.TRACKLOG_FIT_MAX_GRID))
+        if not all(0.0 < v < float("inf") for v in grid):   # (NaN fails too)
+            raise ValueError("SqairStream.track_log_fit: every value of {} must be finite and > 0".format(name))
+        return grid
+
+    def track_log_fit(self, lag=None, q_grid=None, r_grid=None, v0=None, burn=2, innov=False):
+        lag, scal = self._check_log_call("track_log_fit", lag, None, None, v0)
+        q_grid = self._check_grid("q_grid", q_grid, scal["q"])
+        r_grid = self._check_grid("r_grid", r_grid, scal["r"])
+        if not is_int_in(burn, 0, 2 ** 31 - 1):
+            raise ValueError("SqairStream.track_log_fit: burn must be an integer >= 0")
+        core, B, Cn = self.core, self.B, self.log_C
+        with torch.cuda.device(core.device):
+            core._join_in()
+            with core.on_stream():
+                o = self._solve_log(lag, scal)   # (state and the slots do not depend on q and r: the stream's own serve)
+                key = (len(q_grid), len(r_grid))
+                if o.get("fit_key") != key:   # (the outputs belong to the solve's lag and to the grid's size)
+                    o["fit"] = zeros_of("SqairTrackLogFit", _capi.tracklog_fit_shapes(lag, B, Cn, *key), core.device)
+                    o["fit_key"] = key
+                    torch.cuda.current_stream(core.device).synchronize()
+                buf = {k: t for k, t in o["fit"].items() if innov or k in _capi.TRACKLOG_FIT_REQUIRED}
+                c_tab = _capi.SqairTrackLogOut(**{k: o["out"][k].data_ptr() for k in _capi.TRACKLOG_FIT_TABLE})
+                c_fit = _capi.tracklog_fit_struct(q_grid, r_grid, scal["v0"], int(burn), **{k: t.data_ptr() for k, t in buf.items()})
+                core.check(core.lib.sqair_lane_tracklog_fit(core.handle, C.byref(self._log_c), C.byref(c_tab), o["work"].data_ptr(),
+                                                            C.byref(c_fit), lag, Cn, core.N, B, core._stream()), "sqair_lane_tracklog_fit")
+                got = {k: t.clone() for k, t in buf.items()}
+            core._join_out()
+        return track_log_fit({k: t.cpu() for k, t in got.items()}, q_grid, r_grid)
+
+    def set_motion(self, q=None, r=None, v0=None, gate=None):
+        """``SqairStream.set_motion``'s part here: the scalars checked and kept; on a stream with ``motion=True`` the motion registered
+        again with them and the same buffers.  Returns whether the pass changed (a captured graph is then stale)."""
+        new = dict(self.motion_scalars)
+        for key, name, v in (("q", "q", q), ("r", "r", r), ("v0_var", "v0", v0), ("gate", "gate", gate)):
+            if v is None:
+                continue
+            try:
+                new[key] = float(v)
+            except (TypeError, ValueError):
+                new[key] = float("nan")
+            if not 0.0 < new[key] < float("inf"):   # (NaN fails too)
+                raise ValueError("SqairStream.set_motion: {} must be finite and > 0".format(name))
+        self.motion_scalars = new
+        if not self.motion:
+            return False
+        core, est = self.core, self.est
+        mo = _capi.SqairLaneMotion(trk_kf=self.ident_buf["trk_kf"].data_ptr(), **new,
+                                   **{n: est[n].data_ptr() for n in _capi.MOTION_FIELDS if n in est})
+        core.stream.synchronize()   # (no pass in flight reads the scalars being replaced)
+        core.check(core.lib.sqair_set_motion(core.handle, C.byref(mo), self.T, self.B), "sqair_set_motion")
+        return True
 
     def identities(self):
         if not self.identified:

@@ -312,6 +312,30 @@ class SqairStream(object):
         Without ``score`` nothing more is launched."""
         return self.lane.track_log(lag, q, r, v0, score, score_iou, score_match)
 
+    def track_log_fit(self, lag=None, q_grid=None, r_grid=None, v0=None, burn=2, innov=False):
+        """Motion calibration: the maximum-likelihood ``q`` and ``r`` of the motion model on a grid, from the last ``lag`` logged frames
+        and without truth (include/sqair_hip.h: sqair_lane_tracklog_fit, which states the semantics): the solve, then one more launch
+        on the solve's device tensors.  Every track of the window is filtered again under every (q, r) of ``q_grid`` x ``r_grid`` (1 to
+        16 values each, finite and > 0; default the stream's ``motion_q`` * 4^k and ``motion_r`` * 4^k for k = -4..3, so that the
+        current scalars are node (4, 4)), conditioned on the associations the log recorded; the innovations y and their variances S
+        of every later sighting but a column's first ``burn`` give the sums of -log p = 1/2 sum (ln 2 pi S + y^2 / S).  ``v0``: the
+        newborn's velocity variance, default the stream's ``motion_v0`` (it is not fitted).  Returns what ``lane.track_log_fit`` forms
+        (sqair_amd/lane.py): ``q``, ``r`` and ``node``, the grid node of minimal pooled ``nll``; ``at_edge``, whether it lies on the
+        grid's border (fit again with a grid moved there); per node [Q, R] ``nll``, ``mean_nis`` (1 for an honest filter: the
+        truth-free counterpart of the score's ``nees``), ``gap_mean_nis`` (the same over the first sightings behind a gap), ``n``,
+        ``n_gap``, ``skipped`` (innovations with a non-finite or non-positive term); the same per lane under ``lane_*``, and ``lane_q``,
+        ``lane_r`` [B].  ``innov=True`` adds ``innov`` [lag, B, C, 2, 2], (y, S) of node (0, 0).  Nothing of the stream changes: apply a
+        fit with ``set_motion``.  Host tensors; the figures are those of this window alone."""
+        return self.lane.track_log_fit(lag, q_grid, r_grid, v0, burn, innov)
+
+    def set_motion(self, q=None, r=None, v0=None, gate=None):
+        """Replaces the motion model's scalars (None: kept), each finite and > 0 as the constructor checks ``motion_q``, ``motion_r``,
+        ``motion_v0`` and ``motion_gate``: the defaults of ``track_log()`` and ``track_log_fit()`` follow.  On a stream with
+        ``motion=True`` the motion is also registered again with the same buffers (sqair_set_motion) -- the tracks' filter states
+        ``trk_kf`` are kept -- and a captured graph is recaptured on the next step; on other streams only the defaults change."""
+        if self.lane.set_motion(q, r, v0, gate):
+            self._graph = False
+
     # ---- trajectory scoring ------------------------------------------------------------------------------------------------
     def _check_traj_truth(self, fn, truth, lane, F, default_anchor, link_ids, truth_iou, link_match="greedy"):
         return self.traj.check_truth(fn, truth, lane, F, default_anchor, link_ids, truth_iou, link_match)

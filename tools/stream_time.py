@@ -110,6 +110,15 @@ same stream, alternating, lag 10 and 64, for both matchings, every call waited f
 arguments (lag 4096, C 64, G 16) on one lane, where lane 0's greedy walk is long.  Recorded, not gated on:
 
     python tools/stream_time.py --tracklog-score [--out profiles/tracklog_score_time.json]
+
+With --tracklog-fit: the price of motion calibration (``track_log_fit(lag)``, include/sqair_hip.h: sqair_lane_tracklog_fit) at cfg-2's
+batch (L = 64, C = 16, the default 8 x 8 grid): ``track_log_fit(lag)`` with and without ``innov`` against ``track_log(lag)`` on the same
+stream, alternating, lag 10 and 64, every call waited for.  With --limits only the kernel alone at the limits of its arguments (lag
+4096, C 64, a 16 x 16 grid) on one lane, a run of its own so that it can be given its own time limit; its figures are added to the
+file --out names.  Recorded, not gated on:
+
+    python tools/stream_time.py --tracklog-fit [--out profiles/tracklog_fit_time.json]
+    python tools/stream_time.py --tracklog-fit --limits [--out profiles/tracklog_fit_time.json]
 """
 import argparse
 import json
@@ -122,6 +131,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from sqair_amd import _capi  # noqa: E402
+from sqair_amd import lane as lane_mod  # noqa: E402
 from sqair_amd.data import config_inputs, make_sequences, to_float  # noqa: E402
 from sqair_amd.flags import make_flags  # noqa: E402
 from sqair_amd.model import SqairCore  # noqa: E402
@@ -668,6 +678,71 @@ def time_tracklog_score(B, K, N, steps, warmup, L=64, G=2, rounds=10, hw=(50, 50
     return res
 
 
+def fit_at_the_limits(lag=4096, C=64, N=16, Q=16, R=16, reps=3):
+    """k_lane_tracklog_fit alone on one lane at the limits of its arguments, on a table made by hand: 64 columns seen in every frame
+    but a tenth of them (gaps), 256 candidates -- two a round, eight rounds a workgroup, 128 staged blocks a round, 4096 steps a
+    thread.  Milliseconds per launch, every launch waited for."""
+    import ctypes as C_
+    core = SqairCore(make_flags(k_particles=2, n_steps_per_image=4), (50, 50))   # (a handle for the error text: the fit reads nothing else of it)
+    lib, h = core.lib, core.handle
+    rng = np.random.default_rng(5)
+    dev = lambda a: torch.as_tensor(a).cuda()
+    box = np.zeros((1, lag, N, 4), np.float32)
+    box[..., :2] = 100.0 + np.cumsum(rng.normal(0, 1.0, (1, lag, N, 2)), 1)
+    box[..., 2:] = 10.0
+    state = np.where(rng.uniform(size=(lag, 1, C)) < 0.1, 2, 1).astype(np.int32)
+    state[0] = 1
+    table = dict(frame_index=dev(np.arange(lag, dtype=np.int64)[:, None]), state=dev(state))
+    work = dev(np.broadcast_to(np.arange(C, dtype=np.int32) % N, (1, lag, C)).copy())
+    log = dict(count=dev(np.full(1, lag, np.int64)), log_valid=dev(np.ones((1, lag), np.int32)), log_id=dev(np.zeros(1, np.int32)),
+               log_len=dev(np.zeros(1, np.int32)), log_box=dev(box))   # (only L and log_box are read)
+    out = {k: torch.zeros(s, dtype=getattr(torch, _capi.field_dtype("SqairTrackLogFit", k)), device="cuda")
+           for k, s in _capi.tracklog_fit_shapes(lag, 1, C, Q, R).items()}
+    c_log = _capi.SqairLaneTrackLog(L=lag, **{k: t.data_ptr() for k, t in log.items()})
+    c_tab = _capi.SqairTrackLogOut(**{k: t.data_ptr() for k, t in table.items()})
+    grid = [0.01 * 2.0 ** k for k in range(16)]
+    c_fit = _capi.tracklog_fit_struct(grid[:Q], grid[:R], 16.0, 2, **{k: t.data_ptr() for k, t in out.items()})
+    ms = []
+    for i in range(reps + 1):   # (the first launch loads the code object: not counted)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        rc = lib.sqair_lane_tracklog_fit(h, C_.byref(c_log), C_.byref(c_tab), work.data_ptr(), C_.byref(c_fit), lag, C, N, 1,
+                                         C_.c_void_p(torch.cuda.current_stream().cuda_stream))
+        assert rc == 0, lib.sqair_last_error(h)
+        b.record()
+        torch.cuda.synchronize()
+        if i:
+            ms.append(a.elapsed_time(b))
+    fit = lane_mod.track_log_fit({k: t.cpu() for k, t in out.items() if k != "innov"}, grid[:Q], grid[:R])
+    return dict(lag=lag, C=C, N=N, Q=Q, R=R, lanes=1, ms=_spread(ms), terms=int(fit["n"][fit["node"]]), q=fit["q"], r=fit["r"],
+                mean_nis=float(fit["mean_nis"][fit["node"]]))
+
+
+def time_tracklog_fit(B, K, N, steps, warmup, L=64, rounds=10, hw=(50, 50)):
+    smc = dict(resample="systematic", ess_frac=0.5)
+    legs = dict(log=dict(estimate=True, identity=True, tracklog=L, tracklog_tracks=16, **smc))
+    streams, res, med, thr = alternating_streams(legs, B, K, N, steps, warmup, rounds, hw)
+    st = streams["log"]
+    assert int(st._tracklog["count"].min()) >= L, "the log is not full"
+    res.update(L=L, tracks=16, grid=[8, 8], burn=2)
+    res["ms"], res["fit_minus_plain_us"] = {}, {}
+    for lag in (10, L):
+        calls = dict(track_log=lambda: st.track_log(lag=lag), track_log_fit=lambda: st.track_log_fit(lag=lag),
+                     track_log_fit_innov=lambda: st.track_log_fit(lag=lag, innov=True))
+        ms = _timed_calls(st.core, calls)
+        key = "lag{}".format(lag)
+        res["ms"][key] = {n: _spread(v) for n, v in ms.items()}
+        res["fit_minus_plain_us"][key] = {n: 1e3 * (float(np.median(ms[n])) - float(np.median(ms["track_log"])))
+                                          for n in ("track_log_fit", "track_log_fit_innov")}
+        fit = st.track_log_fit(lag=lag)
+        res["fit_" + key] = dict(node=fit["node"], q=fit["q"], r=fit["r"], at_edge=fit["at_edge"], terms=int(fit["n"].max()),
+                                 mean_nis_at_the_fit=float(fit["mean_nis"][fit["node"]]) if fit["node"] else None,
+                                 mean_nis_at_the_defaults=float(fit["mean_nis"][4, 4]))
+    for st in streams.values():
+        st.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=500)
@@ -687,10 +762,22 @@ def main():
     ap.add_argument("--motion", action="store_true", help="identity and identity + motion, greedy and optimal, with SMC and the estimate, alternating (profiles/stream_motion_time.json)")
     ap.add_argument("--tracklog", action="store_true", help="identity and motion with and without the track log, with SMC and the estimate, alternating; track_log() against tracks() apart (profiles/stream_tracklog_time.json)")
     ap.add_argument("--tracklog-score", action="store_true", help="the track log with and without its truth ring, alternating; track_log(score=True) against track_log(); the scorer at its limits (profiles/tracklog_score_time.json)")
+    ap.add_argument("--tracklog-fit", action="store_true", help="track_log_fit(lag) against track_log(lag) at lag 10 and 64 with the 8 x 8 grid (profiles/tracklog_fit_time.json); with --limits: k_lane_tracklog_fit alone at its limits, added to the file --out names")
+    ap.add_argument("--limits", action="store_true", help="with --tracklog-fit: only the kernel at the limits of its arguments (lag 4096, C 64, 16 x 16, one lane)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     ov, _, _, _ = config_inputs(2)
-    if args.tracklog_score:
+    if args.tracklog_fit and args.limits:
+        res = json.load(open(args.out)) if args.out and os.path.exists(args.out) else dict(build_id=_capi.build_id(), device=torch.cuda.get_device_name(0), shapes=[])
+        assert res["build_id"] == _capi.build_id(), "the file was written by another build"
+        res["fit_at_the_limits"] = fit_at_the_limits()
+        print(json.dumps(res["fit_at_the_limits"]))
+        if args.out:
+            json.dump(res, open(args.out, "w"), indent=1)
+        return
+    if args.tracklog_fit:
+        shapes = [dict(name="cfg2_batch_tracklog_fit", **time_tracklog_fit(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
+    elif args.tracklog_score:
         shapes = [dict(name="cfg2_batch_tracklog_score", **time_tracklog_score(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
     elif args.tracklog:
         shapes = [dict(name="cfg2_batch_tracklog", **time_tracklog(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
