@@ -1158,6 +1158,71 @@ int sqair_lane_tracklog_fit(SqairHandle* h, const SqairLaneTrackLog* log, const 
                             const void* work /* read-only: as the solve left it */, const SqairTrackLogFit* fit,
                             int lag, int C, int N, int B, void* stream);
 
+/* ---- track log stitching: join a track's fragments with hindsight (the track log stitching paragraph) --------------------------------
+ * The identity kernel looks backwards only: it re-identifies an object with a track unseen for at most max_age frames, and its gate
+ * is on position, because a newborn has no velocity yet.  So one object often sits in the solve's table as several columns with
+ * disjoint spans, each smoothed on its own.  The log holds what a causal tracker never has: the later frames of the new fragment, and
+ * so its velocity at its birth.  sqair_lane_tracklog_stitch links fragments by that hindsight and solves the joined columns again.  It
+ * is a stand-alone, capturable call, one launch of k_lane_tracklog_stitch, one workgroup of 256 threads per lane: it registers nothing,
+ * no pass runs it, it reads nothing of a previous call, and it writes only its outputs -- `stitched`, `work_out` and the link outputs;
+ * nothing of them is read but what this launch wrote.  The handle gives the error text only.
+ * Inputs (read-only).  `log`; `table` and `work` exactly as sqair_lane_tracklog_smooth left them for the same lag, C, N and B; q, r,
+ * v0_var, the solve's.  No pass may have run between the solve and the stitch: a pass moves the ring under the table.  stitch->gate,
+ * finite and > 0, in sigmas; stitch->max_gap in 0..lag.  `stitched` is a second SqairTrackLogOut of the same lag, C and B, `work_out`
+ * a second `work` of the same size; both are outputs.  For lane b:
+ * 1. Fragments.  The kept columns c with track_id[b,c] >= 0.  f0_c and f1_c are the first and the last frame with state[f,b,c] != 0;
+ *    both are state 1 by the solve's construction.
+ * 2. Candidates.  A link a -> b (a != b, both fragments) is a candidate when f1_a < f0_b; len0[b,cb] == 1 -- the successor was born at
+ *    f0_b, inside the window, after the predecessor was last seen --; and gap <= max_gap, gap being the number of frames strictly
+ *    between f1_a and f0_b that COUNT in the solve's sense (point 1 of the track log paragraph).
+ * 3. Distance, per axis in {y, x}, in fp32 and in this order.  (pa, va, Aa, Ba, Ca) = filt[f1_a,b,a,axis,:] coasted with P
+ *    (sq_kf_predict, called, not restated) once per frame that counts in (f1_a, f0_b], gap + 1 times: frames that do not count do not
+ *    step, as in the solve.  (pb, vb, Ab, Bb, Cb) = smooth[f0_b,b,cb,axis,:], the successor's backward-informed birth state under
+ *    its diffuse start prior.  The two rest on disjoint measurements, so their difference has covariance Pa + Pb:
+ *      A = Aa + Ab; Bm = Ba + Bb; Cm = Ca + Cb; det = fmaf(A, Cm, -(Bm Bm)); dp = pb - pa; dv = vb - va
+ *      num = fmaf(A dv, dv, fmaf(-2, Bm dv, Cm dp) dp); d2_axis = num / det          (= (Cm dp^2 - 2 Bm dp dv + A dv^2) / det)
+ *    d2 = d2_y + d2_x, four degrees of freedom.  A candidate is ELIGIBLE when det_y > 0, det_x > 0 and d2 <= gate gate (the product
+ *    formed in fp32).  A NaN never passes.
+ * 4. Assignment over the C x C table in LDS (at most 16 KiB), rows = predecessors, columns = successors: weight 2^28 + q for an
+ *    eligible pair, q = min(max(__float2int_rn((1 - d2 / (gate gate)) * 1048576.0f), 0), 2^20); -1 for every other pair.  Wave 0 calls
+ *    sq_assign_optimal_i32, the IDF1 solve's device function.  64 pairs x 2^20 < 2^28: cardinality first, the smallest total d2 (in
+ *    units of gate^2 2^-20) second; every weight is below 2^30, the solver's exact range.  Among equally optimal assignments the
+ *    result is the solver's: deterministic, not restated as a rule.
+ * 5. Chains.  A fragment has at most one successor and one predecessor and links go forward in time: they form chains of
+ *    time-disjoint fragments.  A chain's root is its first fragment; it has the chain's smallest column and id.
+ * 6. The stitched table, SqairTrackLogOut's layout with the same lag, C and B: one column per chain, in the order of the roots'
+ *    columns -- track_id = the root's id, ascending, padded with -1 --; len0 the root's; n_tracks = the solve's minus the number of
+ *    links; frame_index copied.  work_out[f,c'] = the `work` word of the chain's fragment whose span f0..f1 holds f (taken only inside
+ *    0..N-1), -1 elsewhere.  On these columns, with f0 the root's and f1 the last fragment's, points 3 and 4 of the track log
+ *    paragraph run as they stand -- ONE device function, sq_tracklog_walk, called by both kernels --: a bridged frame that counts is
+ *    state 2 and is interpolated with the measurements of both sides, one that does not count is state 3; size, filt and smooth
+ *    follow that paragraph's point 5.  The stitched table is by definition what the solve would have written had the identity kept
+ *    one id: where it did, the bits are the solve's.
+ * 7. Link outputs, every word written: link_next [B,C] int32, the successor's column in the SOLVE's table, -1 without one; link_d2
+ *    [B,C] fp32, the link's d2, 0 without one; link_gap [B,C] int32, the link's gap, -1 without one; root [B,C] int32, the stitched
+ *    column the solve's column went to, -1 for a padding column; n_links [B] int32.
+ * Refused (return -1, text in sqair_last_error, before any HIP call): a NULL log, table, work, stitch, stitched or work_out; what
+ * sqair_set_tracklog refuses for log; lag outside 1..L; C outside 1..64; N outside 1..16; B < 1; any of q, r, v0_var not finite and
+ * positive; a NULL track_id, n_tracks, len0, frame_index, state, filt or smooth of the table; a NULL field of stitched; a NULL
+ * link_next, link_d2, link_gap, root or n_links; gate not finite and positive; max_gap outside 0..lag; a field of stitched, or work_out,
+ * sharing its pointer with a field of the table or with work.
+ * Out of scope: re-linking inside a fragment; splitting a track; appearance in the distance (the log does not hold it); fitting on
+ * the stitched table; links to tracks not among the C kept columns; a stated tie rule; stitching inside the pass or feeding links
+ * back to the identity kernel; filtering h, w; training passes. */
+typedef struct SqairTrackLogStitch {
+  float gate;            /* finite, > 0: a link needs d2 <= gate^2 */
+  int32_t max_gap;       /* 0..lag: the counting frames a link may bridge */
+  int32_t* link_next;    /* [B,C] */
+  float*   link_d2;      /* [B,C] */
+  int32_t* link_gap;     /* [B,C] */
+  int32_t* root;         /* [B,C] */
+  int32_t* n_links;      /* [B] */
+} SqairTrackLogStitch;
+int sqair_lane_tracklog_stitch(SqairHandle* h, const SqairLaneTrackLog* log, const SqairTrackLogOut* table /* read-only */,
+                               const void* work /* read-only: as the solve left it */, int lag, int C, int N, int B, float q, float r,
+                               float v0_var, const SqairTrackLogStitch* stitch, const SqairTrackLogOut* stitched, void* work_out,
+                               void* stream);
+
 /* ---- IDF1 scoring: does an identity stay on an object over its life -- global identity assignment, solved on the device ---------
  * The score's idsw counts the moments an identity changes on a greedy per-frame match; it cannot say for how long the wrong id then
  * stays, and gives no credit for an object re-identified under its old id.  The identity measures of Ristani et al. (IDF1, IDP, IDR)

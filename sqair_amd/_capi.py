@@ -248,6 +248,18 @@ def tracklog_fit_struct(q_grid, r_grid, v0_var, burn, **pointers):
     return fit
 
 
+# track log stitching (include/sqair_hip.h: sqair_lane_tracklog_stitch): the link outputs in declaration order, the result's names for
+# them, what the stitch reads of the solve's outputs
+TRACKLOG_STITCH_FIELDS = _pointers("SqairTrackLogStitch")
+TRACKLOG_STITCH_LINKS = dict(zip(("next", "d2", "gap", "root", "n_links"), TRACKLOG_STITCH_FIELDS))
+TRACKLOG_STITCH_TABLE = ("track_id", "n_tracks", "len0", "frame_index", "state", "filt", "smooth")
+
+
+def tracklog_stitch_shapes(B, C):
+    """The shapes of sqair_lane_tracklog_stitch's link outputs for C track columns."""
+    return dict(link_next=(B, C), link_d2=(B, C), link_gap=(B, C), root=(B, C), n_links=(B,))
+
+
 # trajectory scoring (include/sqair_hip.h: sqair_lane_traj_score): the three structs' pointer fields in declaration order -- of
 # SqairTrajScore the accumulators, then the per-call outputs and the int32 ones among them --, the columns of ``counts`` [F, B, .],
 # ``sums`` [F, B, .] and ``lane_counts`` [B, .]

@@ -569,6 +569,20 @@ struct LaneTrackLogFitArgs {
   int lag, C, N, B;
 };
 int sq_launch_lane_tracklog_fit(const LaneTrackLogFitArgs& a, hipStream_t s);
+// Track log stitching (sqair_lane_tracklog_stitch; include/sqair_hip.h states the semantics): k_lane_tracklog_stitch, one workgroup
+// of 256 threads per lane b: the fragments' spans, the C x C table of link weights in LDS, wave 0's assignment, the chains, then one
+// thread per (stitched column, axis) walks the solve's filter and smoother over the joined slots.
+struct LaneTrackLogStitchArgs {
+  SqairLaneTrackLog log;               // L, count, log_valid and log_box are read
+  SqairTrackLogOut tab;                // the solve's outputs, read-only here
+  const int32_t* work;                 // [B][lag][C], the solve's slots, read-only here
+  SqairTrackLogStitch st;              // gate, max_gap and the link outputs
+  SqairTrackLogOut out;                // the stitched table
+  int32_t* work_out;                   // [B][lag][C], the slots of the stitched columns
+  float q, r, v0_var;
+  int lag, C, N, B;
+};
+int sq_launch_lane_tracklog_stitch(const LaneTrackLogStitchArgs& a, hipStream_t s);
 
 // Object forecasts (sqair_forecast_fan; include/sqair_hip.h states the semantics).  Fan-out: rollout row q = r * S + s.
 // k_forecast_fan_src expands the source map, src_fan[q] = src[q / S] (NULL: q / S), an index outside [0, R) of the blob -> -1.

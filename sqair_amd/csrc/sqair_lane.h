@@ -411,3 +411,107 @@ __device__ __forceinline__ float sq_kf_update(float* k, const float S, const flo
   k[4] = fmaf(-k1, ppv, k[4]);
   return vel;
 }
+
+// The solve's walk (include/sqair_hip.h: the track log paragraph, points 3 to 5) of ONE (column c, axis ax) of lane b over the window's
+// frames: forward -- sq_kf_predict, sq_kf_update on the thread's own five words -- storing state, size and the filtered state; then
+// backward (Rauch-Tung-Striebel) over the stepped frames, reading its own stores back.  ONE statement of it: k_lane_tracklog_smooth
+// walks its own slots, k_lane_tracklog_stitch the joined ones -- `work` is where the slot of (frame, column) is read, [lag][C] of the
+// lane, written by the calling launch in front of a fence and a barrier.  f0..f1 is the column's span (f0 > f1: none: all zeros);
+// counts(f) and record(f) are the caller's: whether frame f counts, and its record inside 0..L-1.  A slot read is used inside 0..N-1
+// by the caller's construction.  No arrays in registers but a thread's five words, indexed by constants.
+template <class Counts, class Record>
+__device__ __forceinline__ void sq_tracklog_walk(const SqairTrackLogOut& o, const int* work, const float* lbox, Counts counts, Record record,
+                                                 const int f0, const int f1, const int b, const int c, const int ax, const int lag,
+                                                 const int B, const int C, const int N, const float q, const float r, const float v0_var) {
+  // ---- 3: forward
+  float k[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  float size = 0.0f;
+  for (int f = 0; f < lag; ++f) {
+    const size_t e = ((size_t)f * B + b) * C + c;
+    int st = 0;
+    if (f >= f0 && f <= f1) {
+      if (!counts(f)) {
+        st = 3;
+      } else {
+        const int j = work[f * C + c];
+        float z = 0.0f;
+        if (j >= 0) {
+          const float* w = lbox + ((size_t)record(f) * N + j) * 4;
+          size = w[2 + ax];
+          z = fmaf(0.5f, size, w[ax]);
+        }
+        if (f == f0) {
+          k[0] = z; k[1] = 0.0f; k[2] = r; k[3] = 0.0f; k[4] = v0_var;
+          st = 1;
+        } else {
+          const float S = sq_kf_predict(k, q, r);
+          if (j >= 0) { sq_kf_update(k, S, z); st = 1; }
+          else st = 2;
+        }
+      }
+    }
+    const bool stepped = st == 1 || st == 2;
+    if (ax == 0) o.state[e] = st;
+    o.size[e * 2 + ax] = stepped ? size : 0.0f;
+    float* w = o.filt + (e * 2 + ax) * 5;
+    w[0] = stepped ? k[0] : 0.0f; w[1] = stepped ? k[1] : 0.0f; w[2] = stepped ? k[2] : 0.0f;
+    w[3] = stepped ? k[3] : 0.0f; w[4] = stepped ? k[4] : 0.0f;
+  }
+  // ---- 4: backward over the stepped frames; (ps, vs, as, bs, cs): the smoothed state of the next stepped frame
+  float ps = 0.0f, vs = 0.0f, as = 0.0f, bs = 0.0f, cs = 0.0f;
+  bool have = false;
+  for (int f = lag - 1; f >= 0; --f) {
+    const size_t e = (((size_t)f * B + b) * C + c) * 2 + ax;
+    float* w = o.smooth + e * 5;
+    const bool stepped = f >= f0 && f <= f1 && counts(f);
+    if (!stepped) {
+      w[0] = 0.0f; w[1] = 0.0f; w[2] = 0.0f; w[3] = 0.0f; w[4] = 0.0f;
+      continue;
+    }
+    const float* fl = o.filt + e * 5;
+    const float p = fl[0], v = fl[1], pa = fl[2], pb = fl[3], pc = fl[4];
+    if (!have) {
+      ps = p; vs = v; as = pa; bs = pb; cs = pc;
+      have = true;
+    } else {
+      float m[5] = {p, v, pa, pb, pc};
+      sq_kf_predict(m, q, r);
+      const float pm = m[0], am = m[2], bm = m[3], cm = m[4];
+      const float det = fmaf(am, cm, -(bm * bm)), m00 = pa + pb, m10 = pb + pc;
+      const float g00 = fmaf(m00, cm, -(pb * bm)) / det, g01 = fmaf(pb, am, -(m00 * bm)) / det;
+      const float g10 = fmaf(m10, cm, -(pc * bm)) / det, g11 = fmaf(pc, am, -(m10 * bm)) / det;
+      const float dp = ps - pm, dv = vs - v, da = as - am, db = bs - bm, dc = cs - cm;
+      ps = fmaf(g01, dv, fmaf(g00, dp, p));
+      vs = fmaf(g11, dv, fmaf(g10, dp, v));
+      const float e00 = fmaf(g01, db, g00 * da), e01 = fmaf(g01, dc, g00 * db);
+      const float e10 = fmaf(g11, db, g10 * da), e11 = fmaf(g11, dc, g10 * db);
+      as = fmaf(e01, g01, fmaf(e00, g00, pa));
+      bs = fmaf(e01, g11, fmaf(e00, g10, pb));
+      cs = fmaf(e11, g11, fmaf(e10, g10, pc));
+    }
+    w[0] = ps; w[1] = vs; w[2] = as; w[3] = bs; w[4] = cs;
+  }
+}
+
+// The stitch's state distance of one axis (include/sqair_hip.h: the track log stitching paragraph, point 3): `fa` points at the
+// predecessor's five filtered words at its last sighting, coasted here `steps` frames with sq_kf_predict; `sb` at the successor's
+// five smoothed words at its birth.  Returns d2_axis and leaves det in `det`.  The fma order is the header's.
+__device__ __forceinline__ float sq_stitch_d2_axis(const float* fa, const float* sb, const int steps, const float q, const float r, float& det) {
+  float k[5] = {fa[0], fa[1], fa[2], fa[3], fa[4]};
+  for (int i = 0; i < steps; ++i) sq_kf_predict(k, q, r);
+  const float A = k[2] + sb[2], Bm = k[3] + sb[3], Cm = k[4] + sb[4];
+  det = fmaf(A, Cm, -(Bm * Bm));
+  const float dp = sb[0] - k[0], dv = sb[1] - k[1];
+  const float num = fmaf(A * dv, dv, fmaf(-2.0f, Bm * dv, Cm * dp) * dp);
+  return num / det;
+}
+// Both axes of a pair: d2 = d2_y + d2_x; `ok` is the eligibility of point 3 (both det > 0 and d2 <= gate2; a NaN fails).
+__device__ __forceinline__ float sq_stitch_d2(const float* fa, const float* sb, const int steps, const float q, const float r,
+                                              const float gate2, bool& ok) {
+  float det_y, det_x;
+  const float d2y = sq_stitch_d2_axis(fa, sb, steps, q, r, det_y);
+  const float d2x = sq_stitch_d2_axis(fa + 5, sb + 5, steps, q, r, det_x);
+  const float d2 = d2y + d2x;
+  ok = det_y > 0.0f && det_x > 0.0f && d2 <= gate2;
+  return d2;
+}

@@ -1463,7 +1463,8 @@ int sq_launch_lane_tracklog(const LaneTrackLogArgs& a, hipStream_t s) {
 //   slots    thread i of lag * C finds the slot of column c in frame f (the smallest j) into `work`, and the first and last such
 //            frame of the column by integer atomicMin / atomicMax in LDS.
 //   filter   thread (column, axis) < 2 C walks the frames forward -- sq_kf_predict, sq_kf_update (sqair_lane.h) on its own five
-//            words -- and stores the filtered state; then backward over the stepped frames, reading its own stores back.
+//            words -- and stores the filtered state; then backward over the stepped frames, reading its own stores back:
+//            sq_tracklog_walk (sqair_lane.h), the one statement of it, k_lane_tracklog_stitch's too.
 // `work` and filt are global: at the limits neither fits LDS.  What a thread reads of them it wrote itself, but for `work`, which
 // is read behind a fence and a barrier.  A slot read from `work` is the one this launch wrote, inside 0..N-1; a record index is
 // formed inside 0..L-1.  No arrays in registers but a thread's five words, indexed by constants.
@@ -1550,77 +1551,10 @@ __global__ __launch_bounds__(256) void k_lane_tracklog_smooth(const LaneTrackLog
     o.len0[(size_t)b * C + tid] = len;
   }
   if (tid >= C * 2) return;   // (no barrier below)
-  // ---- 3: forward, thread = (column, axis)
+  // ---- 3, 4: forward and backward, thread = (column, axis): the walk of sqair_lane.h, on this launch's own slots
   const int c = tid >> 1, ax = tid & 1;
   const int f0 = c < K ? s_f0[c] : lag, f1 = c < K ? s_f1[c] : -1;
-  const float* lbox = g.log_box + (size_t)b * L * N * 4;
-  float k[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-  float size = 0.0f;
-  for (int f = 0; f < lag; ++f) {
-    const size_t e = ((size_t)f * B + b) * C + c;
-    int st = 0;
-    if (f >= f0 && f <= f1) {
-      if (!counts(f)) {
-        st = 3;
-      } else {
-        const int j = work[f * C + c];
-        float z = 0.0f;
-        if (j >= 0) {
-          const float* q = lbox + ((size_t)record(f) * N + j) * 4;
-          size = q[2 + ax];
-          z = fmaf(0.5f, size, q[ax]);
-        }
-        if (f == f0) {
-          k[0] = z; k[1] = 0.0f; k[2] = a.r; k[3] = 0.0f; k[4] = a.v0_var;
-          st = 1;
-        } else {
-          const float S = sq_kf_predict(k, a.q, a.r);
-          if (j >= 0) { sq_kf_update(k, S, z); st = 1; }
-          else st = 2;
-        }
-      }
-    }
-    const bool stepped = st == 1 || st == 2;
-    if (ax == 0) o.state[e] = st;
-    o.size[e * 2 + ax] = stepped ? size : 0.0f;
-    float* w = o.filt + (e * 2 + ax) * 5;
-    w[0] = stepped ? k[0] : 0.0f; w[1] = stepped ? k[1] : 0.0f; w[2] = stepped ? k[2] : 0.0f;
-    w[3] = stepped ? k[3] : 0.0f; w[4] = stepped ? k[4] : 0.0f;
-  }
-  // ---- 4: backward over the stepped frames; (ps, vs, as, bs, cs): the smoothed state of the next stepped frame
-  float ps = 0.0f, vs = 0.0f, as = 0.0f, bs = 0.0f, cs = 0.0f;
-  bool have = false;
-  for (int f = lag - 1; f >= 0; --f) {
-    const size_t e = (((size_t)f * B + b) * C + c) * 2 + ax;
-    float* w = o.smooth + e * 5;
-    const bool stepped = f >= f0 && f <= f1 && counts(f);
-    if (!stepped) {
-      w[0] = 0.0f; w[1] = 0.0f; w[2] = 0.0f; w[3] = 0.0f; w[4] = 0.0f;
-      continue;
-    }
-    const float* fl = o.filt + e * 5;
-    const float p = fl[0], v = fl[1], pa = fl[2], pb = fl[3], pc = fl[4];
-    if (!have) {
-      ps = p; vs = v; as = pa; bs = pb; cs = pc;
-      have = true;
-    } else {
-      float m[5] = {p, v, pa, pb, pc};
-      sq_kf_predict(m, a.q, a.r);
-      const float pm = m[0], am = m[2], bm = m[3], cm = m[4];
-      const float det = fmaf(am, cm, -(bm * bm)), m00 = pa + pb, m10 = pb + pc;
-      const float g00 = fmaf(m00, cm, -(pb * bm)) / det, g01 = fmaf(pb, am, -(m00 * bm)) / det;
-      const float g10 = fmaf(m10, cm, -(pc * bm)) / det, g11 = fmaf(pc, am, -(m10 * bm)) / det;
-      const float dp = ps - pm, dv = vs - v, da = as - am, db = bs - bm, dc = cs - cm;
-      ps = fmaf(g01, dv, fmaf(g00, dp, p));
-      vs = fmaf(g11, dv, fmaf(g10, dp, v));
-      const float e00 = fmaf(g01, db, g00 * da), e01 = fmaf(g01, dc, g00 * db);
-      const float e10 = fmaf(g11, db, g10 * da), e11 = fmaf(g11, dc, g10 * db);
-      as = fmaf(e01, g01, fmaf(e00, g00, pa));
-      bs = fmaf(e01, g11, fmaf(e00, g10, pb));
-      cs = fmaf(e11, g11, fmaf(e10, g10, pc));
-    }
-    w[0] = ps; w[1] = vs; w[2] = as; w[3] = bs; w[4] = cs;
-  }
+  sq_tracklog_walk(o, work, g.log_box + (size_t)b * L * N * 4, counts, record, f0, f1, b, c, ax, lag, B, C, N, a.q, a.r, a.v0_var);
 }
 int sq_launch_lane_tracklog_smooth(const LaneTrackLogSmoothArgs& a, hipStream_t s) {
   SQ_LAUNCH(k_lane_tracklog_smooth, dim3(a.B), dim3(256), 0, s, a);
@@ -1889,5 +1823,172 @@ __global__ __launch_bounds__(256) void k_lane_tracklog_fit(const LaneTrackLogFit
 }
 int sq_launch_lane_tracklog_fit(const LaneTrackLogFitArgs& a, hipStream_t s) {
   SQ_LAUNCH(k_lane_tracklog_fit, dim3(a.B, a.fit.Q), dim3(256), 0, s, a);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Track log stitching (sqair_lane_tracklog_stitch; LaneTrackLogStitchArgs in sqair_glue.h; the semantics: include/sqair_hip.h, the
+// track log stitching paragraph, points 1-7)
+// ------------------------------------------------------------------------------------------------
+// k_lane_tracklog_stitch: workgroup = lane b, 256 threads.
+//   window   the solve's own: record(f) and counts(f) from count, L and log_valid; s_pre[f] = the counting frames below f (thread t
+//            counts frames 16 t .. 16 t + 15, then adds the partial counts below it: lag <= 4096 = 256 * 16), so that a gap is a
+//            difference of two words.
+//   spans    thread i of lag * C: integer atomicMin / atomicMax in LDS over the frames with state != 0.
+//   table    thread i of C * C = (predecessor, successor): the candidate test in integers, then sq_stitch_d2 (sqair_lane.h) on the
+//            predecessor's filtered words at f1 and the successor's smoothed words at f0 -- global, read-only, the solve's -- and the
+//            weight into s_w.  Wave 0 calls sq_assign_optimal_i32 on it; the branch is wave-uniform.
+//   chains   thread c < C: its link (taken only with a positive weight), its root by walking s_prev (at most C steps), the root's
+//            rank among the roots = the stitched column; a root walks s_next to the chain's last fragment.
+//   slots    thread i of lag * C = (frame, stitched column) walks its chain to the fragment whose span holds the frame and copies
+//            that `work` word into work_out (inside 0..N-1, else -1): one writer per word.
+//   filter   behind a fence and a barrier, thread (stitched column, axis) < 2 C: sq_tracklog_walk on work_out, as the solve.
+// Every barrier stands under conditions on kernel arguments alone.  Indices: f < lag, columns < C -- what the solver returns is
+// checked against 0..C-1 before it is used --, s_pre inside 0..lag, a record inside 0..L-1, a slot inside 0..N-1.  No arrays in
+// registers but five state words indexed by constants.  LDS: 16 KiB weights, 8 KiB s_pre, 3 KiB the rest.
+constexpr int SQ_STITCH_CHUNK = SQ_TRACKLOG_MAXL / 256;
+__global__ __launch_bounds__(256) void k_lane_tracklog_stitch(const LaneTrackLogStitchArgs a SQ_TLP) {
+  SQ_TL_SCOPE;
+  __shared__ int s_w[SQ_TRACKLOG_MAXC * SQ_TRACKLOG_MAXC];
+  __shared__ unsigned short s_pre[SQ_TRACKLOG_MAXL + 1];
+  __shared__ int s_part[256];
+  __shared__ int s_id[SQ_TRACKLOG_MAXC], s_f0[SQ_TRACKLOG_MAXC], s_f1[SQ_TRACKLOG_MAXC], s_next[SQ_TRACKLOG_MAXC], s_prev[SQ_TRACKLOG_MAXC];
+  __shared__ int s_rootof[SQ_TRACKLOG_MAXC], s_last[SQ_TRACKLOG_MAXC], s_tot[2];
+  const SqairLaneTrackLog& g = a.log;
+  const SqairTrackLogOut& t = a.tab;
+  const SqairTrackLogOut& o = a.out;
+  const SqairTrackLogStitch& st = a.st;
+  const int b = blockIdx.x, tid = threadIdx.x, N = a.N, L = g.L, lag = a.lag, C = a.C, B = a.B;
+  const long long cnt = max(g.count[b], 0ll), base = cnt - lag;
+  const int fmin = base < 0 ? (int)(-base) : 0;                    // the first frame of the window that has a record
+  const int r0 = (int)(((base % L) + L) % L);
+  const int* lvalid = g.log_valid + (size_t)b * L;
+  auto record = [&](int f) { const int r = r0 + f; return r >= L ? r - L : r; };   // (f < lag <= L)
+  auto counts = [&](int f) { return f >= fmin && lvalid[record(f)] != 0; };
+  const float gate2 = st.gate * st.gate;
+  const int32_t* work = a.work + (size_t)b * lag * C;
+  // ---- the window: the counting frames below every frame
+  const int lo = min(tid * SQ_STITCH_CHUNK, lag), hi = min(lo + SQ_STITCH_CHUNK, lag);
+  {
+    int n = 0;
+    for (int f = lo; f < hi; ++f) n += counts(f);
+    s_part[tid] = n;
+  }
+  if (tid < C) { s_id[tid] = t.track_id[(size_t)b * C + tid]; s_f0[tid] = lag; s_f1[tid] = -1; s_next[tid] = -1; s_prev[tid] = -1; }
+  __syncthreads();
+  {
+    int off = 0;
+    for (int i = 0; i < tid; ++i) off += s_part[i];
+    for (int f = lo; f < hi; ++f) { s_pre[f] = (unsigned short)off; off += counts(f); }
+    if (lo < lag && hi == lag) s_pre[lag] = (unsigned short)off;
+  }
+  // ---- 1: the fragments' spans; 6: frame_index
+  for (int i = tid; i < lag * C; i += 256) {
+    const int f = i / C, c = i - f * C;
+    if (t.state[((size_t)f * B + b) * C + c] != 0) { atomicMin(&s_f0[c], f); atomicMax(&s_f1[c], f); }
+  }
+  for (int f = tid; f < lag; f += 256) o.frame_index[(size_t)f * B + b] = t.frame_index[(size_t)f * B + b];
+  __syncthreads();
+  // ---- 2, 3, 4: the candidates, their distance, the weights
+  for (int i = tid; i < C * C; i += 256) {
+    const int ca = i / C, cb = i - ca * C;
+    const int fa = s_f1[ca], fb = s_f0[cb];
+    int w = -1;
+    if (ca != cb && s_id[ca] >= 0 && s_id[cb] >= 0 && fa >= 0 && fb < lag && fa < fb && t.len0[(size_t)b * C + cb] == 1) {
+      const int gap = (int)s_pre[fb] - (int)s_pre[fa + 1], steps = (int)s_pre[fb + 1] - (int)s_pre[fa + 1];
+      if (gap <= st.max_gap) {
+        bool ok;
+        const float d2 = sq_stitch_d2(t.filt + (((size_t)fa * B + b) * C + ca) * 10, t.smooth + (((size_t)fb * B + b) * C + cb) * 10, steps,
+                                      a.q, a.r, gate2, ok);
+        if (ok) w = (1 << 28) + min(max(__float2int_rn((1.0f - d2 / gate2) * 1048576.0f), 0), 1 << 20);
+      }
+    }
+    s_w[i] = w;
+  }
+  __syncthreads();
+  if (tid < 64) sq_assign_optimal_i32(s_w, C, C, C, s_next);
+  __syncthreads();
+  // ---- 5: the links (a pair of weight -1 is never taken; checked all the same), then the chains
+  int nx = -1;
+  if (tid < C) {
+    nx = s_next[tid];
+    if (nx < 0 || nx >= C || s_w[tid * C + nx] <= 0) nx = -1;
+  }
+  __syncthreads();   // (every s_next word is read before any is rewritten)
+  if (tid < C) {
+    s_next[tid] = nx;
+    if (nx >= 0) s_prev[nx] = tid;   // (one to one: one writer)
+  }
+  __syncthreads();
+  if (tid < C) {
+    int idx = -1;
+    if (s_id[tid] >= 0) {
+      int rt = tid;
+      for (int i = 0; i < C && s_prev[rt] >= 0; ++i) rt = s_prev[rt];
+      idx = 0;
+      for (int cc = 0; cc < rt; ++cc) idx += s_id[cc] >= 0 && s_prev[cc] < 0;
+      if (rt == tid) {
+        int last = tid;
+        for (int i = 0; i < C && s_next[last] >= 0; ++i) last = s_next[last];
+        s_rootof[idx] = tid;
+        s_last[idx] = last;
+      }
+    }
+    // ---- 7: the link outputs
+    const size_t e = (size_t)b * C + tid;
+    float d2 = 0.0f;
+    int gap = -1;
+    if (nx >= 0) {
+      const int fa = s_f1[tid], fb = s_f0[nx];
+      bool ok;
+      gap = (int)s_pre[fb] - (int)s_pre[fa + 1];
+      d2 = sq_stitch_d2(t.filt + (((size_t)fa * B + b) * C + tid) * 10, t.smooth + (((size_t)fb * B + b) * C + nx) * 10,
+                        (int)s_pre[fb + 1] - (int)s_pre[fa + 1], a.q, a.r, gate2, ok);
+    }
+    st.root[e] = idx;
+    st.link_next[e] = nx;
+    st.link_d2[e] = d2;
+    st.link_gap[e] = gap;
+  }
+  if (tid == 0) {
+    int links = 0, roots = 0;
+    for (int c = 0; c < C; ++c) { links += s_next[c] >= 0; roots += s_id[c] >= 0 && s_prev[c] < 0; }
+    s_tot[0] = links; s_tot[1] = roots;
+  }
+  __syncthreads();
+  // ---- 6: the stitched table: one column per chain, in the order of the roots
+  const int K = s_tot[1];
+  if (tid == 0) { st.n_links[b] = s_tot[0]; o.n_tracks[b] = t.n_tracks[b] - s_tot[0]; }
+  if (tid < C) {
+    const int rc = tid < K ? s_rootof[tid] : -1;
+    o.track_id[(size_t)b * C + tid] = rc >= 0 ? s_id[rc] : -1;
+    o.len0[(size_t)b * C + tid] = rc >= 0 ? t.len0[(size_t)b * C + rc] : -1;
+  }
+  int* wout = a.work_out + (size_t)b * lag * C;
+  for (int i = tid; i < lag * C; i += 256) {
+    const int f = i / C, c = i - f * C;
+    int slot = -1;
+    if (c < K) {
+      int fr = s_rootof[c];
+      for (int n = 0; n < C && fr >= 0; ++n) {
+        if (f >= s_f0[fr] && f <= s_f1[fr]) {
+          const int j = work[f * C + fr];
+          slot = j >= 0 && j < N ? j : -1;
+          break;
+        }
+        fr = s_next[fr];
+      }
+    }
+    wout[i] = slot;
+  }
+  __threadfence();
+  __syncthreads();
+  if (tid >= C * 2) return;   // (no barrier below)
+  const int c = tid >> 1, ax = tid & 1;
+  const int f0 = c < K ? s_f0[s_rootof[c]] : lag, f1 = c < K ? s_f1[s_last[c]] : -1;
+  sq_tracklog_walk(o, wout, g.log_box + (size_t)b * L * N * 4, counts, record, f0, f1, b, c, ax, lag, B, C, N, a.q, a.r, a.v0_var);
+}
+int sq_launch_lane_tracklog_stitch(const LaneTrackLogStitchArgs& a, hipStream_t s) {
+  SQ_LAUNCH(k_lane_tracklog_stitch, dim3(a.B), dim3(256), 0, s, a);
   return 0;
 }

@@ -3,7 +3,7 @@
 // sqair_set_estimate / _layers / _score / _identity / _motion / _tracklog / _score_ids / _idf / _hota), the estimate's refusal of a pass, ONE builder per kernel's arguments -- called by the
 // pass and by the kernel-level entry point alike --, the pass's launch sequence (sq_launch_lane_answers, called by sq_forward_impl
 // with the block sq_resolve_pass resolved) and the stand-alone entry points (sqair_lane_*_test, sqair_lane_traj_score,
-// sqair_lane_idf_solve, sqair_lane_hota_solve, sqair_lane_tracklog_smooth, sqair_lane_tracklog_score, sqair_lane_tracklog_fit).  Host code
+// sqair_lane_idf_solve, sqair_lane_hota_solve, sqair_lane_tracklog_smooth, sqair_lane_tracklog_score, sqair_lane_tracklog_fit, sqair_lane_tracklog_stitch).  Host code
 // only: the kernels and their launchers live in sqair_lane.hip, which work here does not move.  A further follower is one member
 // of SqLaneSet, its registration and builder here, and one line of sq_launch_lane_answers.
 #include "sqair_internal.h"
@@ -602,6 +602,47 @@ extern "C" int sqair_lane_tracklog_fit(SqairHandle* h, const SqairLaneTrackLog* 
   LaneTrackLogFitArgs a; memset(&a, 0, sizeof(a));
   a.log = *log; a.tab = *table; a.work = (const int32_t*)work; a.fit = *fit; a.lag = lag; a.C = C; a.N = N; a.B = B;
   sq_launch_lane_tracklog_fit(a, (hipStream_t)stream);
+  SQ_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+// track log stitching (include/sqair_hip.h: sqair_lane_tracklog_stitch): a stand-alone call on the table and the slots the solve wrote
+// -- or on a test's tensors --, nothing registered on the handle, which gives the error text
+extern "C" int sqair_lane_tracklog_stitch(SqairHandle* h, const SqairLaneTrackLog* log, const SqairTrackLogOut* table, const void* work,
+                                          int lag, int C, int N, int B, float q, float r, float v0_var, const SqairTrackLogStitch* stitch,
+                                          const SqairTrackLogOut* stitched, void* work_out, void* stream) {
+  if (!h) return -1;
+  const std::string who = "sqair_lane_tracklog_stitch: ";
+  if (!log || !table || !work || !stitch || !stitched || !work_out)
+    return sq_no(h, who + "log, table, work, stitch, stitched and work_out must not be NULL");
+  if (B < 1) return sq_no(h, who + "B = " + std::to_string(B) + " must be >= 1");
+  if (sq_tracklog_fields(h, who, *log) != 0) return -1;
+  if (const char* why = sq_tracklog_shape_refusal(lag, C, N))
+    return sq_no(h, who + why + " (lag = " + std::to_string(lag) + ", L = " + std::to_string(log->L) + ", C = " + std::to_string(C) +
+                        ", N = " + std::to_string(N) + ")");
+  if (lag > log->L) return sq_no(h, who + "lag = " + std::to_string(lag) + " must lie in 1..L = " + std::to_string(log->L));
+  const float v[4] = {q, r, v0_var, stitch->gate};
+  const char* name[4] = {"q", "r", "v0_var", "gate"};
+  for (int i = 0; i < 4; ++i)
+    if (!(v[i] > 0.0f) || !std::isfinite(v[i])) return sq_no(h, who + name[i] + " must be finite and > 0");   // (NaN fails)
+  if (stitch->max_gap < 0 || stitch->max_gap > lag)
+    return sq_no(h, who + "max_gap = " + std::to_string(stitch->max_gap) + " must lie in 0..lag = " + std::to_string(lag));
+  if (!table->track_id || !table->n_tracks || !table->len0 || !table->frame_index || !table->state || !table->filt || !table->smooth)
+    return sq_no(h, who + "the table's track_id, n_tracks, len0, frame_index, state, filt and smooth must not be NULL");
+  const SqairTrackLogOut& o = *stitched;
+  if (!o.track_id || !o.n_tracks || !o.len0 || !o.frame_index || !o.state || !o.size || !o.filt || !o.smooth)
+    return sq_no(h, who + "stitched's track_id, n_tracks, len0, frame_index, state, size, filt and smooth must not be NULL");
+  if (!stitch->link_next || !stitch->link_d2 || !stitch->link_gap || !stitch->root || !stitch->n_links)
+    return sq_no(h, who + "link_next, link_d2, link_gap, root and n_links must not be NULL");
+  const void* in[9] = {table->track_id, table->n_tracks, table->len0, table->frame_index, table->state, table->size, table->filt,
+                       table->smooth, work};
+  const void* out[9] = {o.track_id, o.n_tracks, o.len0, o.frame_index, o.state, o.size, o.filt, o.smooth, work_out};
+  for (int i = 0; i < 9; ++i)
+    for (int j = 0; j < 9; ++j)
+      if (in[i] && in[i] == out[j]) return sq_no(h, who + "stitched and work_out must not share a pointer with table or work");
+  LaneTrackLogStitchArgs a; memset(&a, 0, sizeof(a));
+  a.log = *log; a.tab = *table; a.work = (const int32_t*)work; a.st = *stitch; a.out = o; a.work_out = (int32_t*)work_out;
+  a.q = q; a.r = r; a.v0_var = v0_var; a.lag = lag; a.C = C; a.N = N; a.B = B;
+  sq_launch_lane_tracklog_stitch(a, (hipStream_t)stream);
   SQ_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -73,6 +73,11 @@ normalised innovations and log-variances; ``track_log_fit(got, q_grid, r_grid)``
 node, its minimum -- the maximum-likelihood fit on the grid -- and ``mean_nis``, 1 for an honest filter.  ``set_motion(q, r)`` applies
 a fit: the defaults of ``track_log()`` and ``track_log_fit()`` follow, and on a stream with ``motion=True`` the following steps' filter.
 
+``track_log(lag, stitch=True)`` joins the fragments one object left in the log under several ids: one more launch behind the solve
+(sqair_lane_tracklog_stitch) links a column that ended to a column born later when the old one's coasted state and the new one's
+smoothed state at birth agree within ``stitch_gate`` sigmas, one to one, and solves the joined columns again; the result gains
+``stitched`` -- the same keys for the stitched table, ``links``, and with ``score=True`` its own ``score``.
+
 ``score_idf=True`` (with ``score=True``): the score's idsw counts the moments an identity changes, not for how long the wrong id then
 stays.  The stream then also keeps, per lane and on the device, how many frames of the open clip every truth overlapped (IoU >=
 ``score_iou``) every predicted id -- the id words the score reads: ``obj_id``, or ``lane_id`` with ``score_ids="lane"`` --, up to
@@ -716,7 +721,8 @@ class LaneAnswers(object):
                                                        core._stream()), "sqair_lane_tracklog_smooth")
         return o
 
-    def track_log(self, lag=None, q=None, r=None, v0=None, score=False, score_iou=0.5, score_match="greedy"):
+    def track_log(self, lag=None, q=None, r=None, v0=None, score=False, score_iou=0.5, score_match="greedy", stitch=False,
+                  stitch_gate=3.5, stitch_max_gap=None):
         lag, scal = self._check_log_call("track_log", lag, q, r, v0)
         if score:
             if not self.log_G:
@@ -726,35 +732,74 @@ class LaneAnswers(object):
             check_unit("SqairStream.track_log: ", "score_iou", score_iou)
             if score_match not in MATCH_MODES:
                 raise ValueError("SqairStream.track_log: score_match must be 'greedy' or 'optimal'")
+        if stitch:
+            try:
+                stitch_gate = float(stitch_gate)
+            except (TypeError, ValueError):
+                stitch_gate = float("nan")
+            if not 0.0 < stitch_gate < float("inf"):   # (NaN fails too)
+                raise ValueError("SqairStream.track_log: stitch_gate must be finite and > 0")
+            stitch_max_gap = lag if stitch_max_gap is None else stitch_max_gap
+            if not is_int_in(stitch_max_gap, 0, lag):
+                raise ValueError("SqairStream.track_log: stitch_max_gap must be an integer in [0, lag = {}]".format(lag))
         core = self.core
+        match = MATCH_MODES.index(score_match) if score else 0
         with torch.cuda.device(core.device):
             core._join_in()
             with core.on_stream():
                 o = self._solve_log(lag, scal)
                 got = {n: t.clone() for n, t in o["out"].items()}
-                scored = self._score_log(o, lag, score_iou, MATCH_MODES.index(score_match)) if score else None
+                scored = self._score_log(o, o["out"], "score", lag, score_iou, match) if score else None
+                if stitch:
+                    st = self._stitch_log(o, lag, scal, stitch_gate, int(stitch_max_gap))
+                    joined = {n: t.clone() for n, t in st["out"].items()}
+                    links = {n: t.clone() for n, t in st["links"].items()}
+                    joined_score = self._score_log(o, st["out"], "stitch_score", lag, score_iou, match) if score else None
             core._join_out()
         res = track_log_views({n: t.cpu() for n, t in got.items()})
         if scored is not None:
             res["score"] = track_log_score({n: t.cpu() for n, t in scored.items()})
+        if stitch:
+            res["stitched"] = track_log_views({n: t.cpu() for n, t in joined.items()})
+            res["stitched"]["links"] = {name: links[field].cpu() for name, field in _capi.TRACKLOG_STITCH_LINKS.items()}
+            if joined_score is not None:
+                res["stitched"]["score"] = track_log_score({n: t.cpu() for n, t in joined_score.items()})
         return res
 
-    def _score_log(self, o, lag, iou_min, match):
-        """The scorer directly behind the solve, on the current stream and on the solve's device tensors ``o["out"]`` (include/sqair_hip.h:
-        sqair_lane_tracklog_score): the truth ring gathered into window order -- window frame f of every lane is stream frame
-        ring_frames - lag + f; a frame before the ring existed is invalid --, one launch, the outputs' copies."""
+    def _stitch_log(self, o, lag, scal, gate, max_gap):
+        """The stitch directly behind the solve, on the current stream and on the solve's device tensors ``o`` (include/sqair_hip.h:
+        sqair_lane_tracklog_stitch): one launch into a second table, a second ``work`` and the link outputs, kept with the solve's."""
+        core, B, Cn = self.core, self.B, self.log_C
+        if "stitch" not in o:   # (the outputs belong to the solve's lag: another lag has dropped them with the rest)
+            out = zeros_of("SqairTrackLogOut", _capi.tracklog_out_shapes(lag, B, Cn), core.device)
+            o["stitch"] = dict(out=out, work=torch.zeros_like(o["work"]),
+                               links=zeros_of("SqairTrackLogStitch", _capi.tracklog_stitch_shapes(B, Cn), core.device),
+                               c=_capi.SqairTrackLogOut(**{n: t.data_ptr() for n, t in out.items()}))
+            torch.cuda.current_stream(core.device).synchronize()
+        st = o["stitch"]
+        c_st = _capi.SqairTrackLogStitch(gate=gate, max_gap=max_gap, **{n: t.data_ptr() for n, t in st["links"].items()})
+        core.check(core.lib.sqair_lane_tracklog_stitch(core.handle, C.byref(self._log_c), C.byref(o["c"]), o["work"].data_ptr(), lag, Cn,
+                                                       core.N, B, scal["q"], scal["r"], scal["v0"], C.byref(c_st), C.byref(st["c"]),
+                                                       st["work"].data_ptr(), core._stream()), "sqair_lane_tracklog_stitch")
+        return st
+
+    def _score_log(self, o, table, key, lag, iou_min, match):
+        """The scorer on the current stream and on the device tensors ``table`` -- the solve's ``o["out"]``, directly behind it, or the
+        stitch's, behind that (include/sqair_hip.h: sqair_lane_tracklog_score) --, its outputs kept under ``o[key]``: the truth ring
+        gathered into window order -- window frame f of every lane is stream frame ring_frames - lag + f; a frame before the ring
+        existed is invalid --, one launch, the outputs' copies."""
         core, B, G, n = self.core, self.B, self.log_G, self.ring_frames
-        if "score" not in o:   # (the outputs belong to the solve's lag: another lag has dropped them with the rest)
-            o["score"] = zeros_of("SqairTrackLogScore", _capi.tracklog_score_shapes(lag, B, G), core.device)
+        if key not in o:   # (the outputs belong to the solve's lag: another lag has dropped them with the rest)
+            o[key] = zeros_of("SqairTrackLogScore", _capi.tracklog_score_shapes(lag, B, G), core.device)
         truth = {k: ring_window(t, n, lag) for k, t in self.truth_ring.items()}
         if n < lag:
             truth["truth_valid"][:lag - n].zero_()
-        c_tab = _capi.SqairTrackLogOut(**{k: o["out"][k].data_ptr() for k in _capi.TRACKLOG_SCORE_TABLE})
+        c_tab = _capi.SqairTrackLogOut(**{k: table[k].data_ptr() for k in _capi.TRACKLOG_SCORE_TABLE})
         c_truth = _capi.SqairTrackLogTruth(G=G, **{k: t.data_ptr() for k, t in truth.items()})
-        c_score = _capi.SqairTrackLogScore(iou_min=iou_min, **{k: t.data_ptr() for k, t in o["score"].items()})
+        c_score = _capi.SqairTrackLogScore(iou_min=iou_min, **{k: t.data_ptr() for k, t in o[key].items()})
         core.check(core.lib.sqair_lane_tracklog_score(core.handle, C.byref(self._log_c), C.byref(c_tab), C.byref(c_truth), C.byref(c_score),
                                                       lag, self.log_C, B, match, core._stream()), "sqair_lane_tracklog_score")
-        return {k: t.clone() for k, t in o["score"].items()}
+        return {k: t.clone() for k, t in o[key].items()}
 
     def _check_grid(self, name, grid, centre):
         """A grid of ``track_log_fit`` as a list of floats (None: ``centre`` * 4^k, k = -4..3, so that ``centre`` is node 4)."""

@@ -286,7 +286,8 @@ class SqairStream(object):
         ``trk_centre``, ``trk_vel``, ``trk_sigma`` [B, M, 2] and ``trk_pred_box`` [B, M, 4], the coasted box of every live track."""
         return self.lane.identities()
 
-    def track_log(self, lag=None, q=None, r=None, v0=None, score=False, score_iou=0.5, score_match="greedy"):
+    def track_log(self, lag=None, q=None, r=None, v0=None, score=False, score_iou=0.5, score_match="greedy", stitch=False,
+                  stitch_gate=3.5, stitch_max_gap=None):
         """The trajectories of the last ``lag`` logged frames (default: all ``tracklog`` = L of them) per ``lane_id`` (include/sqair_hip.h:
         sqair_set_tracklog, sqair_lane_tracklog_smooth): one launch on the device.  C = ``tracklog_tracks`` columns per lane.
         ``track_id`` [B, C] int32, the C largest ids of the window ascending, -1 = padding; ``n_tracks`` [B], the distinct ids of the
@@ -309,8 +310,17 @@ class SqairStream(object):
         (its normalised square: 2 for an honest ``sigma``), ``gap_err``, ``gap_nees`` and ``gap_precision`` = gap_tp / (gap_tp + gap_fp)
         over the filled gaps; NaN where a denominator is 0.  ``score_iou``: the IoU a pair needs; ``score_match``: per-frame matching
         as keep + "greedy" or keep + "optimal".  The figures are those of this window alone: windows overlap, nothing accumulates.
-        Without ``score`` nothing more is launched."""
-        return self.lane.track_log(lag, q, r, v0, score, score_iou, score_match)
+        Without ``score`` nothing more is launched.
+        ``stitch=True`` joins the fragments of a track with hindsight, one more launch directly behind the solve on its device tensors
+        (include/sqair_hip.h: sqair_lane_tracklog_stitch, which states the semantics): a column that ended is linked to a column born
+        later (``len0`` == 1) across at most ``stitch_max_gap`` counting frames (default ``lag``) when the old one's coasted state and
+        the new one's smoothed state at birth lie within ``stitch_gate`` sigmas (four degrees of freedom), the links are chosen one
+        to one on the device, and the joined columns are filtered and smoothed again.  The result gains ``stitched``: the same keys
+        as the plain result for the stitched table -- ``mot_rows(res["stitched"], lane)`` works unchanged -- and ``links``: ``next``
+        [B, C] (the successor's column in the plain table, -1 none), ``d2`` (0 without a link), ``gap`` (-1 without), ``root`` [B, C]
+        (the stitched column a plain column went to) and ``n_links`` [B].  With ``score=True`` as well the scorer runs a second time,
+        on the stitched table, into ``stitched["score"]``.  Without ``stitch`` nothing more is launched and the result is unchanged."""
+        return self.lane.track_log(lag, q, r, v0, score, score_iou, score_match, stitch, stitch_gate, stitch_max_gap)
 
     def track_log_fit(self, lag=None, q_grid=None, r_grid=None, v0=None, burn=2, innov=False):
         """Motion calibration: the maximum-likelihood ``q`` and ``r`` of the motion model on a grid, from the last ``lag`` logged frames

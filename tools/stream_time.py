@@ -743,6 +743,29 @@ def time_tracklog_fit(B, K, N, steps, warmup, L=64, rounds=10, hw=(50, 50)):
     return res
 
 
+def time_tracklog_stitch(B, K, N, steps, warmup, L=64, rounds=10, hw=(50, 50)):
+    """track_log(lag, stitch=True) against track_log(lag) on the same stream, alternating, at lag 10 and L."""
+    smc = dict(resample="systematic", ess_frac=0.5)
+    legs = dict(log=dict(estimate=True, identity=True, tracklog=L, tracklog_tracks=16, **smc))
+    streams, res, med, thr = alternating_streams(legs, B, K, N, steps, warmup, rounds, hw)
+    st = streams["log"]
+    assert int(st._tracklog["count"].min()) >= L, "the log is not full"
+    res.update(L=L, tracks=16, gate=3.5)
+    res["ms"], res["stitch_minus_plain_us"], res["links"] = {}, {}, {}
+    for lag in (10, L):
+        calls = dict(track_log=lambda: st.track_log(lag=lag), track_log_stitch=lambda: st.track_log(lag=lag, stitch=True))
+        ms = _timed_calls(st.core, calls)
+        key = "lag{}".format(lag)
+        res["ms"][key] = {n: _spread(v) for n, v in ms.items()}
+        res["stitch_minus_plain_us"][key] = 1e3 * (float(np.median(ms["track_log_stitch"])) - float(np.median(ms["track_log"])))
+        got = st.track_log(lag=lag, stitch=True)
+        res["links"][key] = dict(links=int(got["stitched"]["links"]["n_links"].sum()), tracks=int(got["n_tracks"].sum()),
+                                 stitched_tracks=int(got["stitched"]["n_tracks"].sum()))
+    for st in streams.values():
+        st.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=500)
@@ -763,6 +786,7 @@ def main():
     ap.add_argument("--tracklog", action="store_true", help="identity and motion with and without the track log, with SMC and the estimate, alternating; track_log() against tracks() apart (profiles/stream_tracklog_time.json)")
     ap.add_argument("--tracklog-score", action="store_true", help="the track log with and without its truth ring, alternating; track_log(score=True) against track_log(); the scorer at its limits (profiles/tracklog_score_time.json)")
     ap.add_argument("--tracklog-fit", action="store_true", help="track_log_fit(lag) against track_log(lag) at lag 10 and 64 with the 8 x 8 grid (profiles/tracklog_fit_time.json); with --limits: k_lane_tracklog_fit alone at its limits, added to the file --out names")
+    ap.add_argument("--tracklog-stitch", action="store_true", help="track_log(lag, stitch=True) against track_log(lag) at lag 10 and 64, alternating (profiles/tracklog_stitch_time.json)")
     ap.add_argument("--limits", action="store_true", help="with --tracklog-fit: only the kernel at the limits of its arguments (lag 4096, C 64, 16 x 16, one lane)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
@@ -775,7 +799,9 @@ def main():
         if args.out:
             json.dump(res, open(args.out, "w"), indent=1)
         return
-    if args.tracklog_fit:
+    if args.tracklog_stitch:
+        shapes = [dict(name="cfg2_batch_tracklog_stitch", **time_tracklog_stitch(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
+    elif args.tracklog_fit:
         shapes = [dict(name="cfg2_batch_tracklog_fit", **time_tracklog_fit(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
     elif args.tracklog_score:
         shapes = [dict(name="cfg2_batch_tracklog_score", **time_tracklog_score(32, ov["k_particles"], ov["n_steps_per_image"], args.steps, args.warmup))]
